@@ -10,6 +10,10 @@ One step = forward + L1 loss + backward of the whole network (every NAFBlock / c
 libdcpt_hip.so), gradient all-reduce over RCCL when N > 1 (torch DDP buckets, overlapped with
 backward), and the fused AdamW update.  Inputs are synthetic (torch.rand, resident in HBM before the
 timed region), weights are the keyed deterministic init.  Prints ONE JSON line on rank 0.
+
+``--dump-outputs DIR`` (rank 0) writes what the last timed step computed, as float32 / float64 .npy files: the network
+output, the loss, and the same fixed sample of the updated parameters and of their gradients (``dump_step_outputs``).
+The same arguments give the same inputs on every run, so two builds can be compared file by file.
 """
 from __future__ import annotations
 
@@ -241,6 +245,57 @@ def ddp_wrap_overhead(unwrapped_ms: float) -> dict:
         return {"error": repr(e)[:300]}
 
 
+DUMP_SEED = 20240607
+DUMP_PARAM_SAMPLES = 1 << 21       # 2 Mi elements of the ~68 M parameters (8 MB per file)
+DUMP_OUTPUT_MAX = 8 << 20          # outputs up to 32 MB are written whole, larger ones (--batch > 42) as a sample of this many
+
+
+def _seeded_sample(total: int, n: int, salt: int):
+    """Sorted, distinct flat indices into ``total`` elements: the same for the same (total, n, salt) on every run."""
+    import numpy as np
+
+    if total <= n:
+        return np.arange(total, dtype=np.int64)
+    rng = np.random.default_rng([DUMP_SEED, salt])
+    return np.unique(rng.integers(0, total, size=n, dtype=np.int64))
+
+
+def dump_step_outputs(out_dir: str, out: torch.Tensor, loss: torch.Tensor, net: torch.nn.Module) -> dict:
+    """What a caller of the timed step receives after its last call, written as .npy files (about 41 MB at the quoted batch):
+    output.npy (the network output, float32; sampled above DUMP_OUTPUT_MAX elements), loss.npy (float64, shape (1,)),
+    params_sample.npy / grads_sample.npy (float32: the parameters after the AdamW update and the gradients that update used,
+    at the same seeded flat indices into the parameters concatenated in ``named_parameters()`` order)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    flat_out = out.detach().reshape(-1)
+    if flat_out.numel() > DUMP_OUTPUT_MAX:
+        idx = torch.from_numpy(_seeded_sample(flat_out.numel(), DUMP_OUTPUT_MAX, 1)).to(flat_out.device)
+        flat_out = flat_out.index_select(0, idx)
+        arrays = {"output": flat_out.float().cpu().numpy()}
+    else:
+        arrays = {"output": out.detach().float().cpu().numpy()}
+    arrays["loss"] = np.array([float(loss.detach())], dtype=np.float64)
+    params = [p for _, p in net.named_parameters()]
+    sizes = np.array([p.numel() for p in params], dtype=np.int64)
+    starts = np.concatenate([[0], np.cumsum(sizes)])
+    idx = _seeded_sample(int(starts[-1]), DUMP_PARAM_SAMPLES, 2)
+    owner = np.searchsorted(starts, idx, side="right") - 1
+    vals, grads = [], []
+    for i in np.unique(owner):
+        p = params[i]
+        local = torch.from_numpy(idx[owner == i] - starts[i]).to(p.device)
+        vals.append(p.detach().reshape(-1).index_select(0, local).float().cpu())
+        g = p.grad
+        grads.append(torch.full((local.numel(),), float("nan")) if g is None else g.detach().reshape(-1).index_select(0, local).float().cpu())
+    arrays["params_sample"] = torch.cat(vals).numpy()
+    arrays["grads_sample"] = torch.cat(grads).numpy()
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+    return {"dir": out_dir, "files": {k: list(v.shape) for k, v in arrays.items()},
+            "mbytes": round(sum(v.nbytes for v in arrays.values()) / 1e6, 2)}
+
+
 def spawn_ranks(n: int, script: str = None) -> None:
     """`python bench.py --gpus N` without a launcher: re-execute this command (or ``script``: bench_extra.py) under torch.distributed.run,
     one process per GPU."""
@@ -281,12 +336,17 @@ def main():
     ap.add_argument("--no-prof", action="store_true", help="do not bracket GEMM launches with HIP events")
     ap.add_argument("--side-stream", type=int, default=1, help="0: keep the weight-gradient GEMMs on the main stream")
     ap.add_argument("--iso-steps", type=int, default=3, help="steps of the serialized per-kernel timing pass (0 = skip)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (output, loss, a fixed sample of the updated parameters and of "
+                         "their gradients) as .npy files into DIR (rank 0)")
     args = ap.parse_args()
 
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs an MI355X (no CPU fallback for the product path)")
     if args.gpus < 1:
         raise SystemExit(f"--gpus {args.gpus}: need at least one GPU")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit(f"--steps {args.steps} --warmup {args.warmup}: need at least one timed step and no negative warm-up")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # plain `python bench.py --gpus N`: become the launcher -- build the library once, then one rank per GPU under
         # torch.distributed.run (the same command line the driver uses); rank 0 of the children prints the JSON line
@@ -346,12 +406,16 @@ def main():
     lq = torch.rand((args.batch, 3, SIZE, SIZE), generator=g, device=dev)
     gt = torch.rand((args.batch, 3, SIZE, SIZE), generator=g, device=dev)
 
-    def step():
+    last_out = []   # the output of the last timed step, kept only for --dump-outputs
+
+    def step(keep_out=False):
         opt.zero_grad(set_to_none=True)
         out = model(lq)
         loss = (out - gt).abs().mean()
         loss.backward()
         opt.step()
+        if keep_out:
+            last_out.append(out.detach())
         return loss
 
     for _ in range(args.warmup):
@@ -381,13 +445,15 @@ def main():
     barrier()
     if use_prof:
         lib.dcpt_prof_enable(SAMPLE)
+    dump = args.dump_outputs is not None and rank == 0
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        loss = step()
+    for i in range(args.steps):
+        loss = step(keep_out=dump and i == args.steps - 1)
     barrier()
     dt = time.perf_counter() - t0
     loss_val = float(loss.detach())
     prof_rows = read_prof() if use_prof else []
+    dumped = dump_step_outputs(args.dump_outputs, last_out.pop(), loss, net) if dump else None   # before any later step moves the parameters
     for r in prof_rows:   # sampled -> per-step totals are extrapolated; per-launch figures are exact for the sampled launches
         for k in ("launches", "ms", "flops", "bytes"):
             r[k] = r[k] * SAMPLE
@@ -545,6 +611,8 @@ def main():
         except (OSError, ValueError, KeyError):
             pass
         res["lib_digest"] = lib_digest()
+        if dumped is not None:
+            res["dumped_outputs"] = dumped
         if args.path_check_shared_device:
             res["invalid"] = "path check: the ranks shared a device and the collectives went over gloo -- not a measurement"
         if world == 1 and not args.no_secondary:

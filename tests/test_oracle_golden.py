@@ -218,7 +218,11 @@ def test_dcdist_step(golden_dir):
     (l_pix + l_cls).backward()
     assert abs(float(l_pix) - float(g["l_pixel"])) < 1e-5 and abs(float(l_cls) - float(g["l_classify"])) < 1e-5
     _close(logits, g["logits"], rtol=1e-4, atol=1e-5)
-    _close(pix, g["pix"], rtol=1e-4, atol=1e-5)
+    # The image leaves 17 transformer blocks: float32 runs of the same math on different CPUs (kernel choice, summation order) differ
+    # by up to ~4e-5 on it, and so does the reference's own float32 image from the exact (float64) one -- above an absolute 1e-5 on
+    # the near-zero pixels.  The absolute part is therefore scaled to the image (max |pix| ~ 15); test_dcdist_step_f64 pins the
+    # same step to the reference's float64 run at 1e-9.
+    _close(pix, g["pix"], rtol=1e-4, atol=1e-5 * float(np.abs(g["pix"]).max()))
     for n, l2 in zip([str(s) for s in g["g_names"]], g["g_l2"]):
         mine = float(Pg[n].grad.double().pow(2).sum().sqrt())
         assert abs(mine - l2) <= 2e-4 * max(1e-7, l2), (n, mine, l2)
@@ -226,6 +230,39 @@ def test_dcdist_step(golden_dir):
         if k.startswith("g.") and k != "g_names":
             ref = g[k]
             assert np.abs(Pg[k[2:]].grad.numpy() - ref).max() <= 2e-4 * max(1e-7, np.abs(ref).max()), k
+
+
+def test_dcdist_step_f64(golden_dir):
+    """test_dcdist_step in float64 (weights and inputs: the same float32 keyed values, cast exactly) against the reference's float64
+    run (dcdist_step_f64.npz): the restatement is the same math to rounding, on any CPU"""
+    from basicsr.archs import build_network
+    from oracle import dc_oracle as D
+    from oracle import restormer_oracle as R
+
+    g = np.load(os.path.join(golden_dir, "dcdist_step_f64.npz"))
+    cfg_g = dict(dim=16, num_blocks=[4, 6, 6, 1], num_refinement_blocks=1, heads=[1, 2, 4, 8])
+    cfg_dc = dict(feature_dims=[32, 32, 64], num_res_blocks=1, num_classes=5)
+    shapes = {k: tuple(v.shape) for k, v in build_network(dict(type="Restormer_origin", **cfg_g)).state_dict().items()}
+    Pg = _req({k: v.double() for k, v in keyed_state_dict(shapes, seed=0).items()})
+    Pd = {k: v.double() for k, v in keyed_state_dict(D.dc_param_shapes(**cfg_dc), seed=0).items()}   # frozen
+    lq, gt = keyed_input("dist.lq", (2, 3, 32, 32)).double(), keyed_input("dist.gt", (2, 3, 32, 32)).double()
+    pix, taps = R.restormer_forward(lq, Pg, origin=True)
+    assert pix.dtype == torch.float64 and [list(t.shape) for t in taps] == g["tap_shapes"].tolist()
+    logits = D.dc_forward(taps[::-1], Pd)
+    assert logits.dtype == torch.float64
+    l_pix = (pix - gt).abs().mean()
+    l_cls = torch.nn.functional.cross_entropy(logits, torch.tensor([4, 1]))
+    (l_pix + l_cls).backward()
+    assert abs(float(l_pix) - float(g["l_pixel"])) < 1e-12 and abs(float(l_cls) - float(g["l_classify"])) < 1e-12
+    _close(logits, g["logits"], rtol=1e-9, atol=1e-12)
+    _close(pix, g["pix"], rtol=1e-9, atol=1e-9 * float(np.abs(g["pix"]).max()))
+    for n, l2 in zip([str(s) for s in g["g_names"]], g["g_l2"]):
+        mine = float(Pg[n].grad.pow(2).sum().sqrt())
+        assert abs(mine - l2) <= 1e-8 * max(1e-12, l2), (n, mine, l2)
+    for k in g.files:
+        if k.startswith("g.") and k != "g_names":
+            ref = g[k]
+            assert np.abs(Pg[k[2:]].grad.numpy() - ref).max() <= 1e-8 * max(1e-12, np.abs(ref).max()), k
 
 
 R_CFG = dict(dim=16, num_blocks=[1, 1, 1, 1], num_refinement_blocks=1, heads=[1, 2, 4, 8])
