@@ -2,7 +2,7 @@
 """Headline benchmark: megapixels/s, forward+backward, NAFNet-64 (enc [1,1,1,28], mid 1, dec [1,1,1,1]),
 256x256, batch 32 per GPU, fp32 (BASELINE.json metric; configs[1]).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -10,6 +10,13 @@ One step = forward + L1 loss + backward of the whole network (every NAFBlock / c
 libdcpt_hip.so), gradient all-reduce over RCCL when N > 1 (torch DDP buckets, overlapped with
 backward), and the fused AdamW update.  Inputs are synthetic (torch.rand, resident in HBM before the
 timed region), weights are the keyed deterministic init.  Prints ONE JSON line on rank 0.
+
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, the outputs of
+``--dump-outputs`` and the line (its roofline from the launches sampled inside the timed region).
+``--full`` adds everything that takes runs of its own: the serialized per-kernel pass, the step
+without the optimizer (``ms_fwd_bwd``), and on one GPU the secondary workloads (other precisions,
+configs[2]-[4], the one-rank DDP wrap) and the CPU baseline (``--no-secondary`` / ``--no-cpu-baseline``
+leave those out again).
 
 ``--dump-outputs DIR`` (rank 0) writes what the last timed step computed, as float32 / float64 .npy files: the network
 output, the loss, and the same fixed sample of the updated parameters and of their gradients (``dump_step_outputs``).
@@ -230,14 +237,14 @@ def ddp_wrap_overhead(unwrapped_ms: float) -> dict:
     tools/ddp_probe.py vs profiles/r4/ddp_probe.txt) -- against the unwrapped ms_per_step of this run."""
     import subprocess
 
-    cmd = [sys.executable, os.path.abspath(__file__), "--force-ddp", "--no-secondary", "--no-cpu-baseline", "--steps", "6", "--warmup", "4"]
+    cmd = [sys.executable, os.path.abspath(__file__), "--force-ddp", "--steps", "6", "--warmup", "4"]
     try:
         out = subprocess.run(cmd, capture_output=True, text=True, timeout=240, cwd=ROOT).stdout.strip().splitlines()
         line = json.loads([ln for ln in out if ln.startswith("{")][-1])
         ms = float(line["ms_per_step"])
         return {"workload": "the headline step with the network wrapped in DistributedDataParallel (64 MB buckets as gradient views, built-in "
                             "all-reduce hook, the blocks' gradients written straight into the bucket views: dcpt_amd/ddp.py) on a 1-rank RCCL group",
-                "command": "python bench.py --force-ddp --no-secondary --no-cpu-baseline --steps 6 --warmup 4",
+                "command": "python bench.py --force-ddp --steps 6 --warmup 4",
                 "ms_per_step": round(ms, 3), "unwrapped_ms_per_step": round(unwrapped_ms, 3),
                 "ddp_wrap_overhead_ms": round(ms - unwrapped_ms, 3), "ddp_wrap_overhead_frac": round(ms / unwrapped_ms - 1.0, 4),
                 "rccl_ranks": line["config"].get("rccl_ranks")}
@@ -325,17 +332,20 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=BATCH, help="per-GPU batch (the metric is quoted at 32)")
     ap.add_argument("--force-ddp", action="store_true", help="wrap in DistributedDataParallel even with one rank (path check)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what takes runs of its own: the serialized per-kernel pass, the step without the optimizer, and "
+                         "(one GPU) the secondary workloads and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--path-check-shared-device", action="store_true",
                     help="PATH CHECK ONLY, never a measurement: the ranks share the visible GPU(s) and the collectives go over gloo, so that the "
                          "multi-rank code path can be exercised on a one-GPU box (the line is marked invalid)")
     ap.add_argument("--gemm-precision", default="fp32", choices=["fp32", "bf16x3"],
                     help="fp32: the exact fp32 MFMA kernels (the headline); bf16x3: the wide GEMMs on the bf16 pipe with split operands "
                          "(fp32-class, reported as its own line -- never the headline)")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the bf16 DCPT steps (configs[2]) timed after the headline region")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the secondary workloads timed after the headline region")
     ap.add_argument("--no-prof", action="store_true", help="do not bracket GEMM launches with HIP events")
     ap.add_argument("--side-stream", type=int, default=1, help="0: keep the weight-gradient GEMMs on the main stream")
-    ap.add_argument("--iso-steps", type=int, default=3, help="steps of the serialized per-kernel timing pass (0 = skip)")
+    ap.add_argument("--iso-steps", type=int, default=3, help="with --full: steps of the serialized per-kernel timing pass (0 = skip)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the last timed step computed (output, loss, a fixed sample of the updated parameters and of "
                          "their gradients) as .npy files into DIR (rank 0)")
@@ -459,9 +469,9 @@ def main():
             r[k] = r[k] * SAMPLE
     # With the weight-gradient side stream the GEMMs of two streams overlap, so an event pair around one launch also
     # spans its neighbours' work: per-kernel durations are taken from a short SERIALIZED pass (same steps, side stream
-    # off) after the timed region; the as-run figures of the timed region are reported next to them.
+    # off) after the timed region (--full); the as-run figures of the timed region are reported next to them.
     asrun_rows, iso_ms = None, None
-    if use_prof and args.side_stream and args.iso_steps > 0:
+    if args.full and use_prof and args.side_stream and args.iso_steps > 0:
         asrun_rows = prof_rows
         lib.dcpt_set_side_stream(0)
         step()
@@ -478,7 +488,7 @@ def main():
                 r[k] = r[k] * args.steps / args.iso_steps
         lib.dcpt_set_side_stream(1)
     # SURVEY 8d defines the step as forward + loss + backward (+ all-reduce), optimizer excluded: the same steps without opt.step(),
-    # timed right after the timed region (value / ms_per_step keep the optimizer: the conservative figure)
+    # timed right after the timed region with --full (value / ms_per_step keep the optimizer: the conservative figure)
     nfb = max(1, min(args.steps, 10))
 
     def step_fb():
@@ -487,18 +497,21 @@ def main():
         if use_ddp:   # (what the optimizer's post-step hook does in a full step: the bucket views may be written in place again)
             dcpt_ddp.refresh_views(net.parameters())
 
-    step_fb()
-    barrier()
-    t_fb = time.perf_counter()
-    for _ in range(nfb):
+    dt_fb = None
+    if args.full:
         step_fb()
-    barrier()
-    dt_fb = (time.perf_counter() - t_fb) / nfb
+        barrier()
+        t_fb = time.perf_counter()
+        for _ in range(nfb):
+            step_fb()
+        barrier()
+        dt_fb = (time.perf_counter() - t_fb) / nfb
     rccl_ranks = None
     if use_ddp:
-        tf = torch.tensor([dt_fb], device=dev, dtype=torch.float64)
-        dist.all_reduce(tf, op=dist.ReduceOp.MAX)
-        dt_fb = float(tf.item())
+        if dt_fb is not None:
+            tf = torch.tensor([dt_fb], device=dev, dtype=torch.float64)
+            dist.all_reduce(tf, op=dist.ReduceOp.MAX)
+            dt_fb = float(tf.item())
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
@@ -519,10 +532,12 @@ def main():
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": round(ms_per_step, 3),
-            "ms_fwd_bwd": round(dt_fb * 1e3, 3),
-            "value_fwd_bwd": round(mp / dt_fb, 3),
-            "fwd_bwd_note": f"forward + L1 + backward (+ all-reduce) WITHOUT the optimizer (SURVEY 8d's step), {nfb} steps timed right after the "
-                            "timed region; value / ms_per_step include the fused AdamW update",
+            **({} if dt_fb is None else {
+                "ms_fwd_bwd": round(dt_fb * 1e3, 3),
+                "value_fwd_bwd": round(mp / dt_fb, 3),
+                "fwd_bwd_note": f"forward + L1 + backward (+ all-reduce) WITHOUT the optimizer (SURVEY 8d's step), {nfb} steps timed right "
+                                "after the timed region; value / ms_per_step include the fused AdamW update",
+            }),
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,
@@ -575,7 +590,8 @@ def main():
                              (f"in a serialized pass of {args.iso_steps} steps right after the timed region (weight-gradient side "
                               f"stream off, {iso_ms:.1f} ms/step); as_run = events around every {SAMPLE}th GEMM launch inside the timed "
                               "region, where launches of the two streams overlap" if asrun_rows is not None else
-                              f"around every {SAMPLE}th GEMM launch inside the timed region")),
+                              f"around every {SAMPLE}th GEMM launch inside the timed region" +
+                              (", where launches of the two streams overlap (--full adds a serialized pass)" if args.side_stream else ""))),
                 "by_kernel": [dict(kernel=r["kernel"], MNK=[r["M"], r["N"], r["K"]], launches=r["launches"],
                                    ms_per_step=round(r["ms"] / args.steps, 3),
                                    tflops=round(r["flops"] / (r["ms"] * 1e-3) / 1e12, 2),
@@ -615,7 +631,7 @@ def main():
             res["dumped_outputs"] = dumped
         if args.path_check_shared_device:
             res["invalid"] = "path check: the ranks shared a device and the collectives went over gloo -- not a measurement"
-        if world == 1 and not args.no_secondary:
+        if world == 1 and args.full and not args.no_secondary:
             sec = {}
             if args.gemm_precision == "fp32":
                 # the SAME network / batch / step with the wide GEMMs in the opt-in split-operand mode (gemm_x3.hip: fp32 operands as
@@ -681,7 +697,7 @@ def main():
             sec["infer2k_bf16_edge32"] = BX.run_infer2k(dev, "bf16_edge32", steps=3, warmup=2)
             torch.cuda.empty_cache()
             res["secondary"] = sec
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline()
         try:   # RCCL prints its version banner through C stdio, which is block-buffered on a pipe: push it out BEFORE the line, so that
             ctypes.CDLL(None).fflush(None)   # the JSON line is the last line of the output

@@ -9,7 +9,7 @@ DF.set_gemm_precision('bf16x3', min_tiles=1)
 sys.exit(pytest.main(['tests/test_gpu_parity.py', 'tests/test_gpu_dcpt_step.py', 'tests/test_gpu_dchead.py', '-x', '-q', '-m', 'gpu']))
 " 2>&1 | tail -12) > $OUT/parity_forced.log 2>&1
 tail -4 $OUT/parity_forced.log
-for m in fp32 bf16x3; do (timeout 300 python bench.py --no-cpu-baseline --no-secondary --gemm-precision $m 2>&1 | tail -1) > $OUT/bench_$m.json; done
+for m in fp32 bf16x3; do (timeout 300 python bench.py --full --no-cpu-baseline --no-secondary --gemm-precision $m 2>&1 | tail -1) > $OUT/bench_$m.json; done
 python - <<PY
 import json
 for m in ("fp32","bf16x3"):
