@@ -2,7 +2,7 @@
 """Secondary workloads of BASELINE.json (configs[2..4]) on ONE MI355X -- evidence for DESIGN.md, not the driver's
 contract (that is bench.py).  Prints one JSON line per workload.
 
-    python bench_extra.py --workload dcpt|restormer|infer2k|naf [--dtype fp32|bf16] [--steps K] [--warmup W]
+    python bench_extra.py --workload dcpt|restormer|infer2k|naf|swinir [--dtype fp32|bf16] [--steps K] [--warmup W]
 
 ``--dtype bf16`` (dcpt, naf, infer2k): every feature map of the encoder in bf16 storage with fp32 accumulation (act_dtype="bf16";
 dcpt: the classifier head too unless --head-dtype fp32); images, parameters and the optimizer stay fp32.  Its lines carry BOTH
@@ -89,6 +89,66 @@ def run_restormer(dev, save="balanced", steps=5, warmup=2, B=64, S=128, rank=0, 
                 peak_mem_gb=round(torch.cuda.max_memory_allocated() / 2 ** 30, 2))
 
 
+SWINIR_5D = dict(embed_dim=180, depths=[6] * 6, num_heads=[6] * 6, mlp_ratio=2.0, window_size=8, upscale=1)
+
+
+def swinir_fwd_flops_per_pixel(embed_dim=180, depths=(6,) * 6, mlp_ratio=2.0, window_size=8, in_chans=3, **_):
+    """per output pixel: every Swin block 2 (3C^2 + C^2 + 2 C hidden) for qkv / proj / fc1+fc2 and 4 ws^2 C for the window products
+    (q k^T and p v), one 3 x 3 C -> C conv per RSTB and conv_after_body, the two edge convs"""
+    C, hidden, n2 = embed_dim, int(embed_dim * mlp_ratio), window_size * window_size
+    blocks = sum(depths) * (2 * (4 * C * C + 2 * C * hidden) + 4 * n2 * C)
+    convs = (len(depths) + 1) * 2 * 9 * C * C + 2 * 2 * 9 * in_chans * C
+    return blocks + convs
+
+
+def run_swinir(dev, steps=5, warmup=2, B=8, S=256, train_batches=(12, 8, 4, 2, 1)):
+    """the 5D SwinIR (options/all_in_one/test/test_SwinIR_5d.yml) at S x S: inference at batch B, and one training step (fwd + L1 + bwd + AdamW)
+    at the largest batch of ``train_batches`` that fits in device memory; rates against the fp32-MFMA roof"""
+    from basicsr.archs import build_network
+    from dcpt_amd.keyed_init import fill_module_
+    from dcpt_amd.optim import FusedAdamW
+
+    g = torch.Generator(device=dev).manual_seed(1234)
+    net = fill_module_(build_network(dict(type="SwinIR", **SWINIR_5D))).to(dev)
+    fpp = swinir_fwd_flops_per_pixel(**SWINIR_5D)
+    x = torch.rand((B, 3, S, S), generator=g, device=dev)
+
+    def infer():
+        with torch.no_grad():
+            net(x)
+
+    dt_inf = timed(infer, steps, warmup)
+    del x
+    torch.cuda.empty_cache()
+    optm = FusedAdamW(net.parameters(), lr=1e-4)
+    res = dict(workload=f"SwinIR 5D (embed 180, depths [6]*6, heads [6]*6, ws 8, mlp 2), {S}x{S}, fp32",
+               fwd_gflop_per_image=round(fpp * S * S / 1e9, 1), infer_batch=B, infer_ms_per_batch=round(dt_inf * 1e3, 2),
+               infer_tflops=round(fpp * S * S * B / dt_inf / 1e12, 2), infer_mfma_frac=round(fpp * S * S * B / dt_inf / 157.3e12, 4),
+               infer_roof_ms=round(fpp * S * S * B / 157.3e12 * 1e3, 1), steps=steps, warmup=warmup)
+    for tb in train_batches:
+        try:
+            lq = torch.rand((tb, 3, S, S), generator=g, device=dev)
+            gt = torch.rand((tb, 3, S, S), generator=g, device=dev)
+
+            def step():
+                optm.zero_grad(set_to_none=True)
+                (net(lq) - gt).abs().mean().backward()
+                optm.step()
+
+            torch.cuda.reset_peak_memory_stats()
+            dt = timed(step, steps, warmup)
+        except torch.cuda.OutOfMemoryError:
+            lq = gt = None
+            optm.zero_grad(set_to_none=True)
+            torch.cuda.empty_cache()
+            continue
+        flops = 3 * fpp * S * S * tb   # backward = 2 x forward (data and weight gradients)
+        res.update(train_batch=tb, train_ms_per_step=round(dt * 1e3, 2), train_tflops=round(flops / dt / 1e12, 2),
+                   train_mfma_frac=round(flops / dt / 157.3e12, 4), train_peak_mem_gb=round(torch.cuda.max_memory_allocated() / 2 ** 30, 2))
+        break
+    return res
+
+
 def run_infer2k(dev, dtype="fp32", steps=5, warmup=2, S=2048, streams=2):
     """BASELINE.json configs[4]: one S x S image through SRModel.test_tile (reference sr_model.py:273-361), 512-pixel tiles with 16 pixels
     of context, NAFNet-64 inference."""
@@ -122,7 +182,7 @@ def run_infer2k(dev, dtype="fp32", steps=5, warmup=2, S=2048, streams=2):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", required=True, choices=["dcpt", "restormer", "infer2k", "naf"])
+    ap.add_argument("--workload", required=True, choices=["dcpt", "restormer", "infer2k", "naf", "swinir"])
     ap.add_argument("--dtype", default="fp32", choices=["fp32", "bf16", "bf16_tail32", "bf16_edge32"])
     ap.add_argument("--head-dtype", default=None, choices=["fp32", "bf16"], help="dcpt: classifier-head activations (default: --dtype)")
     ap.add_argument("--restormer-save", default="balanced", choices=["auto", "lean", "balanced", "full"], help="what the Restormer halves keep for backward")
@@ -247,6 +307,8 @@ def main():
             res.update(alg_tflops=round(flops / dt / 1e12, 2), mfma_frac=round(flops / dt / 157.3e12, 4))
     elif args.workload == "restormer":
         res = run_restormer(dev, args.restormer_save, args.steps, args.warmup, args.batch or 64, args.size or 128, rank=rank, world=world)
+    elif args.workload == "swinir":
+        res = run_swinir(dev, args.steps, args.warmup, args.batch or 8, args.size or 256)
     else:
         res = run_infer2k(dev, args.dtype, args.steps, args.warmup, args.size or 2048, args.tile_streams)
     res["peak_mem_gb"] = round(torch.cuda.max_memory_allocated() / 2 ** 30, 2)

@@ -67,6 +67,28 @@ class GdfnSaved(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in GDFN_SAVED_FIELDS]
 
 
+SWIN_ATTN_PARAM_FIELDS = ("norm_w", "norm_b", "qkv_w", "qkv_b", "proj_w", "proj_b")
+SWIN_ATTN_SAVED_FIELDS = ("mu", "rstd", "qkv", "att", "lse")
+SWIN_MLP_PARAM_FIELDS = ("norm_w", "norm_b", "fc1_w", "fc1_b", "fc2_w", "fc2_b")
+SWIN_MLP_SAVED_FIELDS = ("mu", "rstd", "h")
+
+
+class SwinAttnParams(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in SWIN_ATTN_PARAM_FIELDS]
+
+
+class SwinAttnSaved(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in SWIN_ATTN_SAVED_FIELDS]
+
+
+class SwinMlpParams(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in SWIN_MLP_PARAM_FIELDS]
+
+
+class SwinMlpSaved(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in SWIN_MLP_SAVED_FIELDS]
+
+
 class BneckGroup(C.Structure):   # dcpt_bneck_group_t: one conv -> LayerNorm group of the classifier head's BottleneckBlock
     _fields_ = [("w", C.c_void_p), ("wpacked", C.c_void_p), ("wpacked_bytes", C.c_size_t), ("lnw", C.c_void_p), ("lnb", C.c_void_p),
                 ("z", C.c_void_p), ("y", C.c_void_p), ("mu", C.c_void_p), ("rstd", C.c_void_p), ("dw", C.c_void_p), ("dlnw", C.c_void_p),
@@ -196,6 +218,20 @@ SIGNATURES = {
                              cint, cint, stream_t]),
     "dcpt_gdfn_bwd": (cint, [C.POINTER(GdfnParams), C.POINTER(GdfnParams), f32p, C.POINTER(GdfnSaved), f32p, f32p, C.c_void_p,
                              sz, cint, cint, cint, cint, cint, cint, stream_t]),
+    "dcpt_swin_attn_ws_bytes": (sz, [cint, cint, cint, cint, cint, cint]),
+    "dcpt_swin_attn_fwd": (cint, [C.POINTER(SwinAttnParams), f32p, f32p, C.POINTER(SwinAttnSaved), C.c_void_p, sz, cint, cint, cint,
+                                  cint, cint, cint, cint, stream_t]),
+    "dcpt_swin_attn_bwd": (cint, [C.POINTER(SwinAttnParams), C.POINTER(SwinAttnParams), f32p, C.POINTER(SwinAttnSaved), f32p, f32p,
+                                  C.c_void_p, sz, cint, cint, cint, cint, cint, cint, cint, stream_t]),
+    "dcpt_swin_mlp_ws_bytes": (sz, [cint, cint, cint, cint, cint, cint]),
+    "dcpt_swin_mlp_fwd": (cint, [C.POINTER(SwinMlpParams), f32p, f32p, C.POINTER(SwinMlpSaved), C.c_void_p, sz, cint, cint, cint,
+                                 cint, cint, stream_t]),
+    "dcpt_swin_mlp_bwd": (cint, [C.POINTER(SwinMlpParams), C.POINTER(SwinMlpParams), f32p, C.POINTER(SwinMlpSaved), f32p, f32p,
+                                 C.c_void_p, sz, cint, cint, cint, cint, cint, stream_t]),
+    "dcpt_conv3x3_res_ws_bytes": (sz, [cint, cint, cint, cint, cint]),
+    "dcpt_conv3x3_res_fwd": (cint, [f32p, f32p, f32p, f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint, stream_t]),
+    "dcpt_conv3x3_res_bwd": (cint, [f32p, f32p, f32p, f32p, f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint, stream_t]),
+    "dcpt_img_affine": (cint, [f32p, f32p, f32p, cint, cint, cint, C.c_float, cint, stream_t]),
     "dcpt_prompt_mix_fwd": (cint, [f32p, f32p, f32p, f32p, cint, cint, cint, cint, cint, cint, stream_t]),
     "dcpt_prompt_mix_bwd_ws_bytes": (sz, [cint, cint, cint]),
     "dcpt_prompt_mix_bwd": (cint, [f32p, f32p, f32p, f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint, cint, cint, stream_t]),

@@ -317,6 +317,7 @@ int launch_gemm_nt(const GemmNT& pin, int aload, int epi, hipStream_t s) {
     CASE(A_PLAIN, E_SCATTER_ADD)
     CASE(A_GATHER, E_PLAIN)
     CASE(A_CONV3, E_PLAIN)
+    CASE(A_CONV3, E_RESID)
     CASE(A_LNBF, E_PLAIN)
     CASE(A_LN, E_PLAIN)
     CASE(A_PLAIN, E_RESID)

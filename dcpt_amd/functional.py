@@ -2056,3 +2056,191 @@ class _PromptMixFn(torch.autograd.Function):
 
 def prompt_mix(logits, prompt_param, H, W):
     return _PromptMixFn.apply(logits, prompt_param, H, W)
+
+
+# ------------------------------------------------------------------------------------------------
+# SwinIR (include/dcpt_hip.h dcpt_swin_*, dcpt_conv3x3_res_*, dcpt_img_affine).  Token maps are (B, C, H, W) channels_last tensors: the
+# reference's (B, L, C) token rows are exactly the NHWC rows.  ``grad_mode`` is decided by the caller (inside an autograd Function's
+# forward grad mode is off): without it the forward keeps nothing for backward -- every intermediate lives in the workspace.
+from ._lib import SwinAttnParams, SwinAttnSaved, SwinMlpParams, SwinMlpSaved  # noqa: E402
+
+
+def _wants_grad(*ts) -> bool:
+    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in ts)
+
+
+@_remember_gemm_mode
+class _SwinAttnFn(torch.autograd.Function):
+    """x + proj(WMSA_shift(qkv(LN1(x))))  (swinir_arch.py SwinTransformerBlock up to its first residual, WindowAttention)."""
+
+    @staticmethod
+    def forward(ctx, x, grad_mode, heads, window, shift, norm_w, norm_b, qkv_w, qkv_b, proj_w, proj_b):
+        lib = _lib.load()
+        _require_gpu(x, norm_w, norm_b, qkv_w, qkv_b, proj_w, proj_b)
+        x = _nhwc(x)
+        ps = [_contig(t.detach()) for t in (norm_w, norm_b, qkv_w, qkv_b, proj_w, proj_b)]
+        B, Cc, H, W = x.shape
+        dev = x.device
+        M = B * H * W
+        y = _empty_nhwc(B, Cc, H, W, dev)
+        pp = SwinAttnParams(*[t.data_ptr() for t in ps])
+        ws = _workspace(dev, lib.dcpt_swin_attn_ws_bytes(B, H, W, Cc, heads, 0))
+        sv = None
+        if grad_mode:
+            stats = torch.empty((2, M), dtype=torch.float32, device=dev)
+            qkv = torch.empty((M, 3 * Cc), dtype=torch.float32, device=dev)
+            att = torch.empty((M, Cc), dtype=torch.float32, device=dev)
+            lse = torch.empty((M, heads), dtype=torch.float32, device=dev)
+            sv = SwinAttnSaved(stats[0].data_ptr(), stats[1].data_ptr(), qkv.data_ptr(), att.data_ptr(), lse.data_ptr())
+        check(lib.dcpt_swin_attn_fwd(C.byref(pp), x.data_ptr(), y.data_ptr(), None if sv is None else C.byref(sv), ws.data_ptr(), ws.numel(),
+                                     B, H, W, Cc, heads, window, shift, _stream(dev)), "dcpt_swin_attn_fwd")
+        if grad_mode:
+            ctx.save_for_backward(x, stats, qkv, att, lse, *ps)
+        ctx.geom = (heads, window, shift)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        lib = _lib.load()
+        x, stats, qkv, att, lse, *ps = ctx.saved_tensors
+        heads, window, shift = ctx.geom
+        dy = _nhwc(dy)
+        B, Cc, H, W = x.shape
+        dev = x.device
+        dx = _empty_nhwc(B, Cc, H, W, dev)
+        grads = [torch.empty_like(t) for t in ps]
+        sv = SwinAttnSaved(stats[0].data_ptr(), stats[1].data_ptr(), qkv.data_ptr(), att.data_ptr(), lse.data_ptr())
+        pp = SwinAttnParams(*[t.data_ptr() for t in ps])
+        gg = SwinAttnParams(*[t.data_ptr() for t in grads])
+        ws = _workspace(dev, lib.dcpt_swin_attn_ws_bytes(B, H, W, Cc, heads, 1))
+        check(lib.dcpt_swin_attn_bwd(C.byref(pp), C.byref(gg), x.data_ptr(), C.byref(sv), dy.data_ptr(), dx.data_ptr(), ws.data_ptr(),
+                                     ws.numel(), B, H, W, Cc, heads, window, shift, _stream(dev)), "dcpt_swin_attn_bwd")
+        return (dx, None, None, None, None, *grads)
+
+
+def swin_attn(x, norm_w, norm_b, qkv_w, qkv_b, proj_w, proj_b, heads, window, shift):
+    ps = (norm_w, norm_b, qkv_w, qkv_b, proj_w, proj_b)
+    return _SwinAttnFn.apply(x, _wants_grad(x, *ps), int(heads), int(window), int(shift), *ps)
+
+
+@_remember_gemm_mode
+class _SwinMlpFn(torch.autograd.Function):
+    """x + fc2(gelu(fc1(LN2(x))))  (swinir_arch.py SwinTransformerBlock's second residual, Mlp)."""
+
+    @staticmethod
+    def forward(ctx, x, grad_mode, norm_w, norm_b, fc1_w, fc1_b, fc2_w, fc2_b):
+        lib = _lib.load()
+        _require_gpu(x, norm_w, norm_b, fc1_w, fc1_b, fc2_w, fc2_b)
+        x = _nhwc(x)
+        ps = [_contig(t.detach()) for t in (norm_w, norm_b, fc1_w, fc1_b, fc2_w, fc2_b)]
+        B, Cc, H, W = x.shape
+        dev = x.device
+        M, hidden = B * H * W, ps[2].shape[0]
+        y = _empty_nhwc(B, Cc, H, W, dev)
+        pp = SwinMlpParams(*[t.data_ptr() for t in ps])
+        ws = _workspace(dev, lib.dcpt_swin_mlp_ws_bytes(B, H, W, Cc, hidden, 0))
+        sv = None
+        if grad_mode:
+            stats = torch.empty((2, M), dtype=torch.float32, device=dev)
+            h = torch.empty((M, hidden), dtype=torch.float32, device=dev)
+            sv = SwinMlpSaved(stats[0].data_ptr(), stats[1].data_ptr(), h.data_ptr())
+        check(lib.dcpt_swin_mlp_fwd(C.byref(pp), x.data_ptr(), y.data_ptr(), None if sv is None else C.byref(sv), ws.data_ptr(), ws.numel(),
+                                    B, H, W, Cc, hidden, _stream(dev)), "dcpt_swin_mlp_fwd")
+        if grad_mode:
+            ctx.save_for_backward(x, stats, h, *ps)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        lib = _lib.load()
+        x, stats, h, *ps = ctx.saved_tensors
+        dy = _nhwc(dy)
+        B, Cc, H, W = x.shape
+        dev = x.device
+        hidden = ps[2].shape[0]
+        dx = _empty_nhwc(B, Cc, H, W, dev)
+        grads = [torch.empty_like(t) for t in ps]
+        sv = SwinMlpSaved(stats[0].data_ptr(), stats[1].data_ptr(), h.data_ptr())
+        pp = SwinMlpParams(*[t.data_ptr() for t in ps])
+        gg = SwinMlpParams(*[t.data_ptr() for t in grads])
+        ws = _workspace(dev, lib.dcpt_swin_mlp_ws_bytes(B, H, W, Cc, hidden, 1))
+        check(lib.dcpt_swin_mlp_bwd(C.byref(pp), C.byref(gg), x.data_ptr(), C.byref(sv), dy.data_ptr(), dx.data_ptr(), ws.data_ptr(),
+                                    ws.numel(), B, H, W, Cc, hidden, _stream(dev)), "dcpt_swin_mlp_bwd")
+        return (dx, None, *grads)
+
+
+def swin_mlp(x, norm_w, norm_b, fc1_w, fc1_b, fc2_w, fc2_b):
+    ps = (norm_w, norm_b, fc1_w, fc1_b, fc2_w, fc2_b)
+    return _SwinMlpFn.apply(x, _wants_grad(x, *ps), *ps)
+
+
+@_remember_gemm_mode
+class _Conv3x3ResFn(torch.autograd.Function):
+    """res + conv3x3(x) + bias, NHWC -> NHWC (the RSTB conv and conv_after_body, swinir_arch.py:634-640, :1098-1099)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, res):
+        lib = _lib.load()
+        _require_gpu(x, weight, bias, res)
+        x, res = _nhwc(x), _nhwc(res)
+        w_, b_ = _contig(weight.detach()), _contig(bias.detach())
+        B, Cc, H, W = x.shape
+        dev = x.device
+        y = _empty_nhwc(B, Cc, H, W, dev)
+        ws = _workspace(dev, lib.dcpt_conv3x3_res_ws_bytes(B, H, W, Cc, 0))
+        check(lib.dcpt_conv3x3_res_fwd(x.data_ptr(), w_.data_ptr(), b_.data_ptr(), res.data_ptr(), y.data_ptr(), ws.data_ptr(), ws.numel(),
+                                       B, H, W, Cc, _stream(dev)), "dcpt_conv3x3_res_fwd")
+        ctx.save_for_backward(x, w_)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        lib = _lib.load()
+        x, w_ = ctx.saved_tensors
+        dy = _nhwc(dy)
+        B, Cc, H, W = x.shape
+        dev = x.device
+        dx = _empty_nhwc(B, Cc, H, W, dev)
+        dw = torch.empty_like(w_)
+        db = torch.empty((Cc,), dtype=torch.float32, device=dev)
+        ws = _workspace(dev, lib.dcpt_conv3x3_res_ws_bytes(B, H, W, Cc, 1))
+        check(lib.dcpt_conv3x3_res_bwd(dy.data_ptr(), x.data_ptr(), w_.data_ptr(), dx.data_ptr(), dw.data_ptr(), db.data_ptr(), ws.data_ptr(),
+                                       ws.numel(), B, H, W, Cc, _stream(dev)), "dcpt_conv3x3_res_bwd")
+        return dx, dw, db, dy
+
+
+def conv3x3_res(x, weight, bias, res):
+    return _Conv3x3ResFn.apply(x, weight, bias, res)
+
+
+class _ImgAffineFn(torch.autograd.Function):
+    """dir 0: (x - mean) * r;  dir 1: x / r + mean   (NCHW image, swinir_arch.py:1064-1065, :1102)."""
+
+    @staticmethod
+    def forward(ctx, x, mean, r, direction):
+        lib = _lib.load()
+        _require_gpu(x, mean)
+        x = _contig(x)
+        m = _contig(mean.detach().reshape(-1))
+        B, Cc, H, W = x.shape
+        if m.numel() != Cc:
+            raise ValueError(f"mean has {m.numel()} entries for {Cc} channels")
+        y = torch.empty_like(x)
+        check(lib.dcpt_img_affine(x.data_ptr(), m.data_ptr(), y.data_ptr(), B, Cc, H * W, float(r), int(direction), _stream(x.device)),
+              "dcpt_img_affine")
+        ctx.geom = (float(r), int(direction))
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        lib = _lib.load()
+        r, direction = ctx.geom
+        dy = _contig(dy)
+        B, Cc, H, W = dy.shape
+        dx = torch.empty_like(dy)
+        check(lib.dcpt_img_affine(dy.data_ptr(), None, dx.data_ptr(), B, Cc, H * W, r, direction, _stream(dy.device)), "dcpt_img_affine")
+        return dx, None, None, None
+
+
+def img_affine(x, mean, r, direction):
+    return _ImgAffineFn.apply(x, mean, r, direction)

@@ -463,6 +463,57 @@ int dcpt_gdfn_fwd(const dcpt_gdfn_params* p, const float* x, float* y, const dcp
 int dcpt_gdfn_bwd(const dcpt_gdfn_params* p, const dcpt_gdfn_params_grads* g, const float* x, const dcpt_gdfn_saved* saved,
                   const float* dy, float* dx, void* ws, size_t ws_bytes, int B, int H, int W, int C, int hidden, int flags,
                   dcpt_stream_t stream);
+/* ---- SwinIR blocks (basicsr/archs/swinir_arch.py; the variant without relative-position bias and without shift mask) -----------
+ * Tokens are NHWC rows x [B][H][W][C] (= the reference's (B, L, C) with L = H*W row-major).  LayerNorm eps 1e-5.
+ * Attention half (SwinTransformerBlock :319-372 up to the first residual, WindowAttention :142-195):
+ *   y = x + proj(WMSA(qkv(LN1(x))))  with windows of window x window tokens on the map rolled by -shift (wrapping, unmasked);
+ *   qkv columns (s * heads + h) * head_dim + d (s = q, k, v), softmax(head_dim^-0.5 q k^T) v per (window, head).
+ *   Supported: C % 4 == 0, C % heads == 0, head_dim <= 64, window^2 <= 64, H and W multiples of window, 0 <= shift < window.
+ * saved may be NULL in forward (nothing kept for backward: inference); backward needs every field. */
+typedef struct {
+    const float* norm_w; const float* norm_b;   /* [C] */
+    const float* qkv_w; const float* qkv_b;     /* [3C][C], [3C] */
+    const float* proj_w; const float* proj_b;   /* [C][C], [C] */
+} dcpt_swin_attn_params;
+typedef struct { float* norm_w; float* norm_b; float* qkv_w; float* qkv_b; float* proj_w; float* proj_b; } dcpt_swin_attn_params_grads;
+typedef struct {   /* M = B*H*W */
+    float* mu; float* rstd;   /* [M] LayerNorm statistics */
+    float* qkv;               /* [M][3C] */
+    float* att;               /* [M][C] attention output (proj input) */
+    float* lse;               /* [M][heads] per-row log-sum-exp of the scores */
+} dcpt_swin_attn_saved;
+size_t dcpt_swin_attn_ws_bytes(int B, int H, int W, int C, int heads, int backward);
+int dcpt_swin_attn_fwd(const dcpt_swin_attn_params* p, const float* x, float* y, const dcpt_swin_attn_saved* saved, void* ws, size_t ws_bytes,
+                       int B, int H, int W, int C, int heads, int window, int shift, dcpt_stream_t stream);
+int dcpt_swin_attn_bwd(const dcpt_swin_attn_params* p, const dcpt_swin_attn_params_grads* g, const float* x, const dcpt_swin_attn_saved* saved,
+                       const float* dy, float* dx, void* ws, size_t ws_bytes, int B, int H, int W, int C, int heads, int window, int shift,
+                       dcpt_stream_t stream);
+/* MLP half (:370, Mlp :17-41):  y = x + fc2(gelu(fc1(LN2(x)))), erf GELU; hidden % 4 == 0.  saved may be NULL in forward. */
+typedef struct {
+    const float* norm_w; const float* norm_b;   /* [C] */
+    const float* fc1_w; const float* fc1_b;     /* [hidden][C], [hidden] */
+    const float* fc2_w; const float* fc2_b;     /* [C][hidden], [C] */
+} dcpt_swin_mlp_params;
+typedef struct { float* norm_w; float* norm_b; float* fc1_w; float* fc1_b; float* fc2_w; float* fc2_b; } dcpt_swin_mlp_params_grads;
+typedef struct {
+    float* mu; float* rstd;   /* [M] */
+    float* h;                 /* [M][hidden] fc1 output before the GELU */
+} dcpt_swin_mlp_saved;
+size_t dcpt_swin_mlp_ws_bytes(int B, int H, int W, int C, int hidden, int backward);
+int dcpt_swin_mlp_fwd(const dcpt_swin_mlp_params* p, const float* x, float* y, const dcpt_swin_mlp_saved* saved, void* ws, size_t ws_bytes,
+                      int B, int H, int W, int C, int hidden, dcpt_stream_t stream);
+int dcpt_swin_mlp_bwd(const dcpt_swin_mlp_params* p, const dcpt_swin_mlp_params_grads* g, const float* x, const dcpt_swin_mlp_saved* saved,
+                      const float* dy, float* dx, void* ws, size_t ws_bytes, int B, int H, int W, int C, int hidden, dcpt_stream_t stream);
+/* RSTB conv / conv_after_body (:634-640, :1098-1099):  y = res + conv3x3(x) + bias, x / res / y NHWC [B][H][W][C], w [C][C][3][3],
+ * zero padding 1.  Backward: dx = conv^T(dy), dw, dbias (the residual's gradient is dy itself). */
+size_t dcpt_conv3x3_res_ws_bytes(int B, int H, int W, int C, int backward);
+int dcpt_conv3x3_res_fwd(const float* x, const float* w, const float* bias, const float* res, float* y, void* ws, size_t ws_bytes, int B, int H,
+                         int W, int C, dcpt_stream_t stream);
+int dcpt_conv3x3_res_bwd(const float* dy, const float* x, const float* w, float* dx, float* dw, float* dbias, void* ws, size_t ws_bytes, int B,
+                         int H, int W, int C, dcpt_stream_t stream);
+/* SwinIR's image normalisation (:1064-1065, :1102):  dir 0: y = (x - mean[c]) * r;  dir 1: y = x / r + mean[c].  x, y NCHW
+ * [B][C][HW]; mean [C] or NULL (then the same two maps are the backward passes: dy * r and dy / r). */
+int dcpt_img_affine(const float* x, const float* mean, float* y, int B, int C, int HW, float r, int dir, dcpt_stream_t stream);
 /* PromptIR's PromptGenBlock (basicsr/archs/promptir_arch.py:237-262) between its linear layer and its 3x3 conv:
  *   out[b] = bilinear_{(S,S)->(H,W), align_corners=False}( sum_l softmax(logits[b])[l] * param[l] )   as NHWC [B][H][W][D].
  * logits [B][L] (= dcpt_meanpool_fc_fwd of the block input), param [L][D][S][S] (the (1,L,D,S,S) parameter), weights [B][L]
