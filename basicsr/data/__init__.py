@@ -32,18 +32,25 @@ def _labelled(sample, opt):
 
 
 def paired_random_crop_augment(lq, gt, opt):
-    """train phase (reference basicsr/data/paired_image_dataset.py:152-166 with transforms.py paired_random_crop / augment,
-    scale 1): the same random ``gt_size`` crop, horizontal flip and 90-degree rotation (vertical flip + transpose) of both
-    images, drawn from Python's ``random`` like the reference."""
+    """train phase (reference basicsr/data/paired_image_dataset.py:152-166 with transforms.py paired_random_crop / augment): a
+    ``gt_size // scale`` patch of the LQ image and the co-located ``gt_size`` patch of the GT image (``opt["scale"]``, default 1:
+    the same crop of both), then the same horizontal flip and 90-degree rotation (vertical flip + transpose) of both images, drawn
+    from Python's ``random`` like the reference."""
     import random
 
     size = opt.get("gt_size")
     if size:
-        _, h, w = gt.shape
-        if h < size or w < size:
-            raise ValueError(f"image ({h}, {w}) is smaller than the training patch ({size}, {size})")
-        top, left = random.randint(0, h - size), random.randint(0, w - size)
-        lq, gt = lq[:, top:top + size, left:left + size], gt[:, top:top + size, left:left + size]
+        scale = int(opt.get("scale", 1) or 1)
+        _, h, w = lq.shape
+        _, h_gt, w_gt = gt.shape
+        if h_gt != h * scale or w_gt != w * scale:
+            raise ValueError(f"Scale mismatches. GT ({h_gt}, {w_gt}) is not {scale}x multiplication of LQ ({h}, {w}).")
+        lsize = size // scale
+        if h < lsize or w < lsize:
+            raise ValueError(f"image ({h}, {w}) is smaller than the training patch ({lsize}, {lsize})")
+        top, left = random.randint(0, h - lsize), random.randint(0, w - lsize)
+        lq = lq[:, top:top + lsize, left:left + lsize]
+        gt = gt[:, top * scale:top * scale + size, left * scale:left * scale + size]
     hflip = opt.get("use_hflip", opt.get("use_flip", False)) and random.random() < 0.5
     vflip = opt.get("use_rot", False) and random.random() < 0.5
     rot90 = opt.get("use_rot", False) and random.random() < 0.5
@@ -145,7 +152,7 @@ class PairedImageDenoiseDataset(tdata.Dataset):
         path = osp.join(self.gt_root, self.names[index])
         gt = _read_rgb(path)
         if self.opt.get("phase") == "train":
-            _, gt = paired_random_crop_augment(gt, gt, self.opt)
+            _, gt = paired_random_crop_augment(gt, gt, {**self.opt, "scale": 1})   # the reference crops at scale 1 here (:368-370)
         elif self.opt.get("center_crop") is not None:
             gt = _center_crop(gt, self.opt["center_crop"])
         if self.sigma_type == "constant":

@@ -2,7 +2,7 @@
 """Secondary workloads of BASELINE.json (configs[2..4]) on ONE MI355X -- evidence for DESIGN.md, not the driver's
 contract (that is bench.py).  Prints one JSON line per workload.
 
-    python bench_extra.py --workload dcpt|restormer|infer2k|naf|swinir [--dtype fp32|bf16] [--steps K] [--warmup W]
+    python bench_extra.py --workload dcpt|restormer|infer2k|naf|swinir|rcan [--dtype fp32|bf16] [--steps K] [--warmup W]
 
 ``--dtype bf16`` (dcpt, naf, infer2k): every feature map of the encoder in bf16 storage with fp32 accumulation (act_dtype="bf16";
 dcpt: the classifier head too unless --head-dtype fp32); images, parameters and the optimizer stay fp32.  Its lines carry BOTH
@@ -149,6 +149,62 @@ def run_swinir(dev, steps=5, warmup=2, B=8, S=256, train_batches=(12, 8, 4, 2, 1
     return res
 
 
+def rcan_fwd_flops_per_lr_pixel(num_in_ch=3, num_out_ch=3, num_feat=64, num_group=10, num_block=16, upscale=4, **_):
+    """per LR pixel: 2 per MAC of every 3 x 3 conv at its own resolution -- the two convs of every RCAB, the group convs and
+    conv_after_body (C -> C), conv_first, each Upsample stage (C -> r^2 C at its input resolution) and conv_last at the HR resolution;
+    the channel attention's pooling and FCs are per image, not per pixel, and left out"""
+    C = num_feat
+    body = (num_group * (2 * num_block + 1) + 1) * 2 * 9 * C * C
+    stages = [2] * (upscale.bit_length() - 1) if upscale & (upscale - 1) == 0 else [3]
+    up, area = 0, 1
+    for r in stages:
+        up += area * 2 * 9 * C * r * r * C
+        area *= r * r
+    return body + 2 * 9 * num_in_ch * C + up + area * 2 * 9 * C * num_out_ch
+
+
+def run_rcan(dev, steps=5, warmup=2, B=16, S=48, S_inf=256):
+    """the default x4 RCAN (64 features, 10 x 16 RCABs): one training step (fwd + L1 + bwd + AdamW) at B x S^2 LR patches, and inference of
+    one S_inf^2 LR image; rates against the fp32-MFMA roof from the FLOPs counted above"""
+    from basicsr.archs import build_network
+    from dcpt_amd.keyed_init import fill_module_
+    from dcpt_amd.optim import FusedAdamW
+
+    cfg = dict(num_in_ch=3, num_out_ch=3)
+    g = torch.Generator(device=dev).manual_seed(1234)
+    net = fill_module_(build_network(dict(type="RCAN", **cfg))).to(dev)
+    fpp = rcan_fwd_flops_per_lr_pixel(**cfg)
+    optm = FusedAdamW(net.parameters(), lr=1e-4)
+    lq = torch.rand((B, 3, S, S), generator=g, device=dev)
+    gt = torch.rand((B, 3, 4 * S, 4 * S), generator=g, device=dev)
+
+    def step():
+        optm.zero_grad(set_to_none=True)
+        (net(lq) - gt).abs().mean().backward()
+        optm.step()
+
+    dt = timed(step, steps, warmup)
+    flops = 3 * fpp * S * S * B   # backward = 2 x forward (data and weight gradients)
+    train = dict(workload=f"RCAN x4 (64 feat, 10 groups x 16 RCABs) fwd+L1+bwd+AdamW, B={B}, {S}x{S} LR -> {4 * S}x{4 * S}, fp32",
+                 fwd_mflop_per_lr_pixel=round(fpp / 1e6, 3), ms_per_step=round(dt * 1e3, 2), alg_tflops=round(flops / dt / 1e12, 2),
+                 mfma_frac=round(flops / dt / 157.3e12, 4), roof_ms=round(flops / 157.3e12 * 1e3, 2), steps=steps, warmup=warmup)
+    optm.zero_grad(set_to_none=True)
+    del lq, gt
+    torch.cuda.empty_cache()
+    x = torch.rand((1, 3, S_inf, S_inf), generator=g, device=dev)
+
+    def infer():
+        with torch.no_grad():
+            net(x)
+
+    dt_inf = timed(infer, steps, warmup)
+    f_inf = fpp * S_inf * S_inf
+    infer_line = dict(workload=f"RCAN x4 inference, 1 x {S_inf}x{S_inf} LR -> {4 * S_inf}x{4 * S_inf}, fp32",
+                      fwd_mflop_per_lr_pixel=round(fpp / 1e6, 3), ms_per_image=round(dt_inf * 1e3, 2), alg_tflops=round(f_inf / dt_inf / 1e12, 2),
+                      mfma_frac=round(f_inf / dt_inf / 157.3e12, 4), roof_ms=round(f_inf / 157.3e12 * 1e3, 2), steps=steps, warmup=warmup)
+    return [train, infer_line]
+
+
 def run_infer2k(dev, dtype="fp32", steps=5, warmup=2, S=2048, streams=2):
     """BASELINE.json configs[4]: one S x S image through SRModel.test_tile (reference sr_model.py:273-361), 512-pixel tiles with 16 pixels
     of context, NAFNet-64 inference."""
@@ -182,7 +238,7 @@ def run_infer2k(dev, dtype="fp32", steps=5, warmup=2, S=2048, streams=2):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", required=True, choices=["dcpt", "restormer", "infer2k", "naf", "swinir"])
+    ap.add_argument("--workload", required=True, choices=["dcpt", "restormer", "infer2k", "naf", "swinir", "rcan"])
     ap.add_argument("--dtype", default="fp32", choices=["fp32", "bf16", "bf16_tail32", "bf16_edge32"])
     ap.add_argument("--head-dtype", default=None, choices=["fp32", "bf16"], help="dcpt: classifier-head activations (default: --dtype)")
     ap.add_argument("--restormer-save", default="balanced", choices=["auto", "lean", "balanced", "full"], help="what the Restormer halves keep for backward")
@@ -309,6 +365,11 @@ def main():
         res = run_restormer(dev, args.restormer_save, args.steps, args.warmup, args.batch or 64, args.size or 128, rank=rank, world=world)
     elif args.workload == "swinir":
         res = run_swinir(dev, args.steps, args.warmup, args.batch or 8, args.size or 256)
+    elif args.workload == "rcan":
+        lines = run_rcan(dev, args.steps, args.warmup, args.batch or 16, args.size or 48)
+        for line in lines[:-1]:
+            print(json.dumps(line), flush=True)
+        res = lines[-1]
     else:
         res = run_infer2k(dev, args.dtype, args.steps, args.warmup, args.size or 2048, args.tile_streams)
     res["peak_mem_gb"] = round(torch.cuda.max_memory_allocated() / 2 ** 30, 2)

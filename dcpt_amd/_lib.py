@@ -89,6 +89,18 @@ class SwinMlpSaved(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in SWIN_MLP_SAVED_FIELDS]
 
 
+RCAB_PARAM_FIELDS = ("conv1_w", "conv1_b", "conv2_w", "conv2_b", "ca1_w", "ca1_b", "ca2_w", "ca2_b")
+RCAB_SAVED_FIELDS = ("h", "t", "pooled", "s")
+
+
+class RcabParams(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in RCAB_PARAM_FIELDS]
+
+
+class RcabSaved(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in RCAB_SAVED_FIELDS]
+
+
 class BneckGroup(C.Structure):   # dcpt_bneck_group_t: one conv -> LayerNorm group of the classifier head's BottleneckBlock
     _fields_ = [("w", C.c_void_p), ("wpacked", C.c_void_p), ("wpacked_bytes", C.c_size_t), ("lnw", C.c_void_p), ("lnb", C.c_void_p),
                 ("z", C.c_void_p), ("y", C.c_void_p), ("mu", C.c_void_p), ("rstd", C.c_void_p), ("dw", C.c_void_p), ("dlnw", C.c_void_p),
@@ -232,6 +244,14 @@ SIGNATURES = {
     "dcpt_conv3x3_res_fwd": (cint, [f32p, f32p, f32p, f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint, stream_t]),
     "dcpt_conv3x3_res_bwd": (cint, [f32p, f32p, f32p, f32p, f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint, stream_t]),
     "dcpt_img_affine": (cint, [f32p, f32p, f32p, cint, cint, cint, C.c_float, cint, stream_t]),
+    "dcpt_rcab_ws_bytes": (sz, [cint, cint, cint, cint, cint, cint]),
+    "dcpt_rcab_fwd": (cint, [C.POINTER(RcabParams), f32p, f32p, C.POINTER(RcabSaved), C.c_void_p, sz, cint, cint, cint, cint, cint, C.c_float,
+                             stream_t]),
+    "dcpt_rcab_bwd": (cint, [C.POINTER(RcabParams), C.POINTER(RcabParams), f32p, C.POINTER(RcabSaved), f32p, f32p, C.c_void_p, sz, cint,
+                             cint, cint, cint, cint, C.c_float, stream_t]),
+    "dcpt_conv3x3_ps_ws_bytes": (sz, [cint, cint, cint, cint, cint, cint]),
+    "dcpt_conv3x3_ps_fwd": (cint, [f32p, f32p, f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint, cint, stream_t]),
+    "dcpt_conv3x3_ps_bwd": (cint, [f32p, f32p, f32p, f32p, f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint, cint, stream_t]),
     "dcpt_prompt_mix_fwd": (cint, [f32p, f32p, f32p, f32p, cint, cint, cint, cint, cint, cint, stream_t]),
     "dcpt_prompt_mix_bwd_ws_bytes": (sz, [cint, cint, cint]),
     "dcpt_prompt_mix_bwd": (cint, [f32p, f32p, f32p, f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint, cint, cint, stream_t]),

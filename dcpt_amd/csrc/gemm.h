@@ -9,7 +9,7 @@
 #include "dcpt_common.h"
 
 enum GemmALoad { A_PLAIN = 0, A_LN = 1, A_SCALE = 2, A_SG = 3, A_GATHER = 4, A_CONV3 = 5, A_LNBF = 6 };
-enum GemmEpi { E_PLAIN = 0, E_BIAS = 1, E_RESID = 2, E_SGBWD = 3, E_SCATTER = 4, E_SCATTER_ADD = 5, E_ADDSCALED = 6, E_MUL = 7, E_BIASGATE = 8, E_DOTCOL = 9, E_LNBWD = 10, E_RESIDLN = 11, E_LNBWD2 = 12 };
+enum GemmEpi { E_PLAIN = 0, E_BIAS = 1, E_RESID = 2, E_SGBWD = 3, E_SCATTER = 4, E_SCATTER_ADD = 5, E_ADDSCALED = 6, E_MUL = 7, E_BIASGATE = 8, E_DOTCOL = 9, E_LNBWD = 10, E_RESIDLN = 11, E_LNBWD2 = 12, E_RELU = 13, E_BIASCOL = 14, E_PSHUF = 15 };
 
 struct GemmNT {
     const float* A;   // [M][lda]   (A_SG: 2K columns; A_GATHER: fine NHWC image, see g*)
@@ -62,6 +62,12 @@ struct GemmNT {
     float* gate;          // E_BIASGATE (N = 2*Ch, SimpleGate input): C = acc + bias as usual AND gate[m][c] = C[m][c] * C[m][Ch + c],
                           // [M][Ch] row-major; a block's tile then holds BN/2 columns of each half
     int ldres;            // row stride of res (0 = ldc)
+    // E_RELU: C = relu(acc + bias); with res (a ReLU output of the same shape) the ReLU backward C = [res > 0] (acc + bias)
+    // E_BIASCOL: C = acc + bias AND per-image column sums of C: the tile's rows of image b (P = pixels per image) sum to
+    //   colpart[(m0 / 128 + b) * N + n] (tile / image pairs that overlap have distinct m0 / 128 + b); fixed order, no atomics
+    // E_PSHUF: C = acc + bias written through PixelShuffle(psr) into the fine NHWC image [B][psr gH][psr gW][gC]: column
+    //   (i psr + j) gC + ch <-> fine pixel (psr h + i, psr w + j), channel ch (the caller orders the weight rows to match)
+    int psr;
     // batching: grid.y = nb1*nb2 problems; pointer offsets b1*s?1 + b2*s?2 (elements)
     int nb1, nb2;
     int64_t sA1, sA2, sB1, sB2, sC1, sC2, sR1, sR2, sS1, sS2;

@@ -290,6 +290,11 @@ int launch_gemm_nt(const GemmNT& pin, int aload, int epi, hipStream_t s) {
     if (epi == E_LNBWD)
         DCPT_CHECK_ARG(p.colpart && p.res && p.mu && p.rstd && p.lnw && p.N <= 128 && p.N % 4 == 0 && p.nb1 * p.nb2 == 1,
                        "gemm_nt: LayerNorm-backward epilogue needs N <= 128 and res / mu / rstd / lnw / colpart");
+    if (epi == E_BIASCOL) DCPT_CHECK_ARG(p.colpart && p.P > 0 && p.M % p.P == 0 && p.nb1 * p.nb2 == 1, "gemm_nt: per-image column-sum epilogue needs colpart and P | M");
+    if (epi == E_PSHUF)
+        DCPT_CHECK_ARG(p.psr >= 1 && p.gC % 4 == 0 && p.N == p.psr * p.psr * p.gC && p.nb1 * p.nb2 == 1 &&
+                           2.0 * p.psr * p.gH * p.psr * p.gW * (double)p.gC * 4.0 < (double)WIN_BYTES,
+                       "gemm_nt: pixel-shuffle epilogue needs N == psr^2 gC, gC %% 4 == 0 and a fine image below 512 MB");
     if (aload == A_CONV3) DCPT_CHECK_ARG(p.gC % 4 == 0 && p.K == 9 * p.gC, "gemm_nt: conv3 needs K == 9*gC, gC %% 4 == 0");
     // algorithmic work of this launch (for the live roofline in bench.py)
     const double mn = (double)p.M * p.N, mk = (double)p.M * p.K;
@@ -318,6 +323,9 @@ int launch_gemm_nt(const GemmNT& pin, int aload, int epi, hipStream_t s) {
     CASE(A_GATHER, E_PLAIN)
     CASE(A_CONV3, E_PLAIN)
     CASE(A_CONV3, E_RESID)
+    CASE(A_CONV3, E_RELU)
+    CASE(A_CONV3, E_BIASCOL)
+    CASE(A_CONV3, E_PSHUF)
     CASE(A_LNBF, E_PLAIN)
     CASE(A_LN, E_PLAIN)
     CASE(A_PLAIN, E_RESID)

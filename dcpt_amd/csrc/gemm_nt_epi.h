@@ -5,13 +5,13 @@
 
 namespace {
 
-// element index of output row m in the fine NHWC image of the scatter epilogues (i = j = ch = 0)
-__device__ __forceinline__ int64_t scatter_elem(const GemmNT& p, int64_t m) {
+// element index of output row m in the fine NHWC image of the scatter epilogues (i = j = ch = 0); r = upscale factor
+__device__ __forceinline__ int64_t scatter_elem(const GemmNT& p, int64_t m, int r = 2) {
     const int w = (int)(m % p.gW);
     const int64_t t = m / p.gW;
     const int h = (int)(t % p.gH);
     const int64_t b = t / p.gH;
-    return ((b * (2 * p.gH) + 2 * h) * (int64_t)(2 * p.gW) + 2 * w) * p.gC;
+    return ((b * (r * p.gH) + r * h) * (int64_t)(r * p.gW) + r * w) * p.gC;
 }
 
 // Epilogue: the accumulators are first parked in LDS ([ROWS][BN] floats, reusing the operand tiles'
@@ -63,23 +63,24 @@ __device__ __forceinline__ void epilogue_rows(const GemmNT& p, const float* __re
     const int n = n0 + 4 * q;
     const bool nok = (QP == Q || q < Q) && n < p.N;
     float4 bias = f4_zero(), cs = make_float4(1.f, 1.f, 1.f, 1.f);
-    if constexpr (EK == E_BIAS || EK == E_RESID || EK == E_MUL || EK == E_RESIDLN) {
+    if constexpr (EK == E_BIAS || EK == E_RESID || EK == E_MUL || EK == E_RESIDLN || EK == E_RELU || EK == E_BIASCOL || EK == E_PSHUF) {
         if (p.bias && nok) bias = ldg4(p.bias + n);
     }
     if constexpr (EK == E_RESID || EK == E_ADDSCALED || EK == E_RESIDLN) {
         if (p.cscale && nok) cs = ldg4(p.cscale + n);
     }
-    constexpr bool SCAT = (EK == E_SCATTER || EK == E_SCATTER_ADD);
+    constexpr bool SCAT = (EK == E_SCATTER || EK == E_SCATTER_ADD || EK == E_PSHUF);
+    const int sr = (EK == E_PSHUF) ? p.psr : 2;   // upscale factor of the scatter
     // windows
     int64_t cbase;
     uint32_t coladd;  // byte offset of this thread's column group inside a row
     if constexpr (SCAT) {
         const int64_t mf = (m0 < p.M) ? m0 : 0;
-        cbase = scatter_elem(p, mf);
+        cbase = scatter_elem(p, mf, sr);
         const int nn = nok ? n : 0;
         const int ij = nn / p.gC;
         const int ch = nn - ij * p.gC;
-        coladd = (uint32_t)((((ij >> 1) * (2 * p.gW) + (ij & 1)) * p.gC + ch) * 4);
+        coladd = (uint32_t)((((ij / sr) * (sr * p.gW) + (ij % sr)) * p.gC + ch) * 4);
     } else {
         cbase = m0 * (int64_t)p.ldc;
         coladd = 4u * (uint32_t)n;
@@ -90,6 +91,9 @@ __device__ __forceinline__ void epilogue_rows(const GemmNT& p, const float* __re
     if constexpr (EK == E_RESIDLN) rsX = make_rsrc(p.ln_out + m0 * (int64_t)p.ldc);
     if constexpr (EK == E_LNBWD || EK == E_LNBWD2) rsX = make_rsrc((p.aux ? p.aux : p.res) + m0 * (int64_t)ldres);
     if constexpr (EK == E_SCATTER_ADD) rsR = make_rsrc(p.res + cbase);
+    if constexpr (EK == E_RELU) {
+        if (p.res) rsR = make_rsrc(p.res + m0 * (int64_t)ldres);
+    }
     if constexpr (EK == E_SGBWD) rsX = make_rsrc(p.aux + m0 * (2 * (int64_t)p.N));
     constexpr int HALF = (EK == E_SGBWD) ? 2 : 1;   // SGBWD needs two loads per row: do it in two halves
     constexpr int ITH = IT / HALF;
@@ -124,12 +128,15 @@ __device__ __forceinline__ void epilogue_rows(const GemmNT& p, const float* __re
             pre1[it] = f4_zero();
             pre2[it] = f4_zero();
             if constexpr (SCAT) {
-                addr[it] = ok ? (uint32_t)((scatter_elem(p, m) - cbase) * 4) + coladd : ROW_SENT;
+                addr[it] = ok ? (uint32_t)((scatter_elem(p, m, sr) - cbase) * 4) + coladd : ROW_SENT;
                 if constexpr (EK == E_SCATTER_ADD) pre1[it] = buf_ld4(rsR, addr[it]);
             } else {
                 addr[it] = ok ? (uint32_t)rl * (uint32_t)p.ldc * 4u + coladd : ROW_SENT;
                 if constexpr (EK == E_RESID || EK == E_ADDSCALED || EK == E_MUL || EK == E_DOTCOL || EK == E_LNBWD || EK == E_RESIDLN || EK == E_LNBWD2)
                     pre1[it] = buf_ld4(rsR, ok ? (uint32_t)rl * (uint32_t)ldres * 4u + coladd : ROW_SENT);
+                if constexpr (EK == E_RELU) {
+                    if (p.res) pre1[it] = buf_ld4(rsR, ok ? (uint32_t)rl * (uint32_t)ldres * 4u + coladd : ROW_SENT);
+                }
                 if constexpr (EK == E_LNBWD || EK == E_LNBWD2) {
                     if (p.aux) pre2[it] = buf_ld4(rsX, ok ? (uint32_t)rl * (uint32_t)ldres * 4u + coladd : ROW_SENT);
                 }
@@ -211,8 +218,12 @@ __device__ __forceinline__ void epilogue_rows(const GemmNT& p, const float* __re
                 dot = f4_fma(v, pre1[it], dot);   // rows past M loaded 0
             } else if constexpr (EK == E_PLAIN || EK == E_SCATTER) {
                 buf_st4(rsC, addr[it], v);
-            } else if constexpr (EK == E_BIAS) {
+            } else if constexpr (EK == E_BIAS || EK == E_BIASCOL || EK == E_PSHUF) {
                 buf_st4(rsC, addr[it], f4_add(v, bias));
+            } else if constexpr (EK == E_RELU) {
+                const float4 u = f4_add(v, bias);
+                const float4 g = p.res ? pre1[it] : u;   // forward: the value itself; backward: the saved ReLU output
+                buf_st4(rsC, addr[it], make_float4(g.x > 0.f ? u.x : 0.f, g.y > 0.f ? u.y : 0.f, g.z > 0.f ? u.z : 0.f, g.w > 0.f ? u.w : 0.f));
             } else if constexpr (EK == E_RESID) {
                 buf_st4(rsC, addr[it], f4_fma(f4_add(v, bias), cs, pre1[it]));
             } else if constexpr (EK == E_ADDSCALED) {
@@ -254,6 +265,25 @@ __device__ __forceinline__ void epilogue_rows(const GemmNT& p, const float* __re
                 for (int g = 1; g < RPP; ++g) t = f4_add(t, *reinterpret_cast<const float4*>(&sm[g * BN + 4 * q]));
                 stg4(p.colpart + ((m0 / ROWS) * 2 + pl) * (int64_t)p.N + n, t);
             }
+        }
+    }
+    if constexpr (EK == E_BIASCOL) {
+        // per-image column sums of C = acc + bias: work item (image bb of the tile, column c) sums its rows of the staged tile in
+        // row order (Cs is still intact: the loop above only read it)
+        const int64_t mend = (m0 + ROWS < p.M) ? m0 + ROWS : p.M;
+        const int64_t bfirst = m0 / p.P;
+        const int nimg = (int)((mend - 1) / p.P - bfirst) + 1;
+        for (int e = tid; e < nimg * BN; e += NT_) {
+            const int c = e % BN;
+            const int64_t bb = bfirst + e / BN;
+            const int nc = n0 + c;
+            if (nc >= p.N) continue;
+            const int lo = (int)((bb * p.P > m0 ? bb * p.P : m0) - m0);
+            const int hi = (int)(((bb + 1) * p.P < mend ? (bb + 1) * p.P : mend) - m0);
+            float sum = 0.f;
+            for (int rl = lo; rl < hi; ++rl) sum += Cs[rl * BN + c];
+            if (p.bias) sum = fmaf((float)(hi - lo), p.bias[nc], sum);
+            p.colpart[(m0 / ROWS + bb) * (int64_t)p.N + nc] = sum;
         }
     }
     if constexpr (EK == E_DOTCOL) {

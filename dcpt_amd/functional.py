@@ -2244,3 +2244,105 @@ class _ImgAffineFn(torch.autograd.Function):
 
 def img_affine(x, mean, r, direction):
     return _ImgAffineFn.apply(x, mean, r, direction)
+
+
+# ------------------------------------------------------------------------------------------------
+# RCAN (include/dcpt_hip.h dcpt_rcab_*, dcpt_conv3x3_ps_*).  Feature maps are (B, C, H, W) channels_last tensors.
+from ._lib import RcabParams, RcabSaved  # noqa: E402
+
+
+@_remember_gemm_mode
+class _RcabFn(torch.autograd.Function):
+    """x + res_scale * CA(conv2(relu(conv1(x))))  (rcan_arch.py RCAB, ChannelAttention)."""
+
+    @staticmethod
+    def forward(ctx, x, grad_mode, res_scale, conv1_w, conv1_b, conv2_w, conv2_b, ca1_w, ca1_b, ca2_w, ca2_b):
+        lib = _lib.load()
+        _require_gpu(x, conv1_w, conv1_b, conv2_w, conv2_b, ca1_w, ca1_b, ca2_w, ca2_b)
+        x = _nhwc(x)
+        ps = [_contig(t.detach()) for t in (conv1_w, conv1_b, conv2_w, conv2_b, ca1_w, ca1_b, ca2_w, ca2_b)]
+        B, Cc, H, W = x.shape
+        Cr = ps[4].shape[0]
+        dev = x.device
+        y = _empty_nhwc(B, Cc, H, W, dev)
+        pp = RcabParams(*[t.data_ptr() for t in ps])
+        ws = _workspace(dev, lib.dcpt_rcab_ws_bytes(B, H, W, Cc, Cr, 0))
+        sv = None
+        if grad_mode:
+            h = _empty_nhwc(B, Cc, H, W, dev)
+            t = _empty_nhwc(B, Cc, H, W, dev)
+            ps_ = torch.empty((2, B, Cc), dtype=torch.float32, device=dev)
+            sv = RcabSaved(h.data_ptr(), t.data_ptr(), ps_[0].data_ptr(), ps_[1].data_ptr())
+        check(lib.dcpt_rcab_fwd(C.byref(pp), x.data_ptr(), y.data_ptr(), None if sv is None else C.byref(sv), ws.data_ptr(), ws.numel(),
+                                B, H, W, Cc, Cr, float(res_scale), _stream(dev)), "dcpt_rcab_fwd")
+        if grad_mode:
+            ctx.save_for_backward(x, h, t, ps_, *ps)
+        ctx.res_scale = float(res_scale)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        lib = _lib.load()
+        x, h, t, ps_, *ps = ctx.saved_tensors
+        dy = _nhwc(dy)
+        B, Cc, H, W = x.shape
+        Cr = ps[4].shape[0]
+        dev = x.device
+        dx = _empty_nhwc(B, Cc, H, W, dev)
+        grads = [torch.empty_like(p) for p in ps]
+        sv = RcabSaved(h.data_ptr(), t.data_ptr(), ps_[0].data_ptr(), ps_[1].data_ptr())
+        pp = RcabParams(*[p.data_ptr() for p in ps])
+        gg = RcabParams(*[g.data_ptr() for g in grads])
+        ws = _workspace(dev, lib.dcpt_rcab_ws_bytes(B, H, W, Cc, Cr, 1))
+        check(lib.dcpt_rcab_bwd(C.byref(pp), C.byref(gg), x.data_ptr(), C.byref(sv), dy.data_ptr(), dx.data_ptr(), ws.data_ptr(), ws.numel(),
+                                B, H, W, Cc, Cr, ctx.res_scale, _stream(dev)), "dcpt_rcab_bwd")
+        return (dx, None, None, *grads)
+
+
+def rcab(x, conv1_w, conv1_b, conv2_w, conv2_b, ca1_w, ca1_b, ca2_w, ca2_b, res_scale=1.0):
+    """one RCAB as one autograd node; ``ca1_w`` / ``ca2_w`` may keep their 1 x 1 kernel dims ([Cr][C][1][1], [C][Cr][1][1])"""
+    ps = (conv1_w, conv1_b, conv2_w, conv2_b, ca1_w, ca1_b, ca2_w, ca2_b)
+    return _RcabFn.apply(x, _wants_grad(x, *ps), float(res_scale), *ps)
+
+
+@_remember_gemm_mode
+class _Conv3x3PsFn(torch.autograd.Function):
+    """PixelShuffle(r)(conv3x3(x) + bias), NHWC -> NHWC (one stage of arch_util.py Upsample)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, r):
+        lib = _lib.load()
+        _require_gpu(x, weight, bias)
+        x = _nhwc(x)
+        w_, b_ = _contig(weight.detach()), _contig(bias.detach())
+        B, Cc, H, W = x.shape
+        if tuple(w_.shape) != (r * r * Cc, Cc, 3, 3):
+            raise ValueError(f"conv3x3_ps: weight {tuple(w_.shape)} for C={Cc}, r={r} (expected ({r * r * Cc}, {Cc}, 3, 3))")
+        dev = x.device
+        y = _empty_nhwc(B, Cc, r * H, r * W, dev)
+        ws = _workspace(dev, lib.dcpt_conv3x3_ps_ws_bytes(B, H, W, Cc, r, 0))
+        check(lib.dcpt_conv3x3_ps_fwd(x.data_ptr(), w_.data_ptr(), b_.data_ptr(), y.data_ptr(), ws.data_ptr(), ws.numel(), B, H, W, Cc, r,
+                                      _stream(dev)), "dcpt_conv3x3_ps_fwd")
+        ctx.save_for_backward(x, w_)
+        ctx.r = r
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        lib = _lib.load()
+        x, w_ = ctx.saved_tensors
+        r = ctx.r
+        dy = _nhwc(dy)
+        B, Cc, H, W = x.shape
+        dev = x.device
+        dx = _empty_nhwc(B, Cc, H, W, dev)
+        dw = torch.empty_like(w_)
+        db = torch.empty((w_.shape[0],), dtype=torch.float32, device=dev)
+        ws = _workspace(dev, lib.dcpt_conv3x3_ps_ws_bytes(B, H, W, Cc, r, 1))
+        check(lib.dcpt_conv3x3_ps_bwd(dy.data_ptr(), x.data_ptr(), w_.data_ptr(), dx.data_ptr(), dw.data_ptr(), db.data_ptr(), ws.data_ptr(),
+                                      ws.numel(), B, H, W, Cc, r, _stream(dev)), "dcpt_conv3x3_ps_bwd")
+        return dx, dw, db, None
+
+
+def conv3x3_ps(x, weight, bias, r):
+    return _Conv3x3PsFn.apply(x, weight, bias, int(r))

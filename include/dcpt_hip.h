@@ -514,6 +514,38 @@ int dcpt_conv3x3_res_bwd(const float* dy, const float* x, const float* w, float*
 /* SwinIR's image normalisation (:1064-1065, :1102):  dir 0: y = (x - mean[c]) * r;  dir 1: y = x / r + mean[c].  x, y NCHW
  * [B][C][HW]; mean [C] or NULL (then the same two maps are the backward passes: dy * r and dy / r). */
 int dcpt_img_affine(const float* x, const float* mean, float* y, int B, int C, int HW, float r, int dir, dcpt_stream_t stream);
+/* ---- RCAN (basicsr/archs/rcan_arch.py) --------------------------------------------------------------------------------------------
+ * Feature maps are NHWC [B][H][W][C], C % 4 == 0.  The image normalisation and conv_first / conv_last / the group convs use
+ * dcpt_img_affine, dcpt_conv3x3_in_*, dcpt_conv3x3_out_* and dcpt_conv3x3_res_*.
+ * RCAB (:32-54, ChannelAttention :9-29):  y = x + res_scale * CA(conv2(relu(conv1(x) + b1)) + b2),
+ *   CA(t) = t * sigmoid(W2 relu(W1 mean_hw(t) + b1') + b2') per image and channel; W1 [Cr][C] (the 1x1 conv C -> C/squeeze), W2 [C][Cr],
+ *   any Cr >= 1.  saved may be NULL in forward (nothing kept for backward: inference); backward needs every field.  No atomics. */
+typedef struct {
+    const float* conv1_w; const float* conv1_b;   /* rcab.0: [C][C][3][3], [C] */
+    const float* conv2_w; const float* conv2_b;   /* rcab.2: [C][C][3][3], [C] */
+    const float* ca1_w; const float* ca1_b;       /* rcab.3.attention.1: [Cr][C] (x 1 x 1), [Cr] */
+    const float* ca2_w; const float* ca2_b;       /* rcab.3.attention.3: [C][Cr] (x 1 x 1), [C] */
+} dcpt_rcab_params;
+typedef struct { float* conv1_w; float* conv1_b; float* conv2_w; float* conv2_b; float* ca1_w; float* ca1_b; float* ca2_w; float* ca2_b; } dcpt_rcab_params_grads;
+typedef struct {   /* M = B*H*W */
+    float* h;        /* [M][C] relu(conv1(x) + b1) */
+    float* t;        /* [M][C] conv2(h) + b2 */
+    float* pooled;   /* [B][C] mean_hw(t) */
+    float* s;        /* [B][C] channel-attention scale */
+} dcpt_rcab_saved;
+size_t dcpt_rcab_ws_bytes(int B, int H, int W, int C, int Cr, int backward);   /* 0 for unsupported arguments */
+int dcpt_rcab_fwd(const dcpt_rcab_params* p, const float* x, float* y, const dcpt_rcab_saved* saved, void* ws, size_t ws_bytes, int B, int H,
+                  int W, int C, int Cr, float res_scale, dcpt_stream_t stream);
+int dcpt_rcab_bwd(const dcpt_rcab_params* p, const dcpt_rcab_params_grads* g, const float* x, const dcpt_rcab_saved* saved, const float* dy,
+                  float* dx, void* ws, size_t ws_bytes, int B, int H, int W, int C, int Cr, float res_scale, dcpt_stream_t stream);
+/* One Upsample stage (arch_util.py Upsample: Conv2d(C, r^2 C, 3, 1, 1) + PixelShuffle(r)), r in {2, 3}:
+ *   y = PixelShuffle(r)(conv3x3(x, w) + bias),  x NHWC [B][H][W][C], w [r^2 C][C][3][3], bias [r^2 C], y NHWC [B][rH][rW][C];
+ *   y channel c at sub-pixel (i, j) is conv channel c r^2 + i r + j.  Backward: dx, dw, dbias from dy. */
+size_t dcpt_conv3x3_ps_ws_bytes(int B, int H, int W, int C, int r, int backward);   /* 0 for unsupported arguments */
+int dcpt_conv3x3_ps_fwd(const float* x, const float* w, const float* bias, float* y, void* ws, size_t ws_bytes, int B, int H, int W, int C, int r,
+                        dcpt_stream_t stream);
+int dcpt_conv3x3_ps_bwd(const float* dy, const float* x, const float* w, float* dx, float* dw, float* dbias, void* ws, size_t ws_bytes, int B,
+                        int H, int W, int C, int r, dcpt_stream_t stream);
 /* PromptIR's PromptGenBlock (basicsr/archs/promptir_arch.py:237-262) between its linear layer and its 3x3 conv:
  *   out[b] = bilinear_{(S,S)->(H,W), align_corners=False}( sum_l softmax(logits[b])[l] * param[l] )   as NHWC [B][H][W][D].
  * logits [B][L] (= dcpt_meanpool_fc_fwd of the block input), param [L][D][S][S] (the (1,L,D,S,S) parameter), weights [B][L]
