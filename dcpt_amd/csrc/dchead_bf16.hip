@@ -125,7 +125,10 @@ size_t conv_layout(int B, int H, int W, int Cin, int Cout, int ks, int backward,
         if (with_ln) {
             w.ln_nblk = ln_bwd_bf16_num_blocks(M, Cout);
             w.ln_tiles = (int)cdiv64(M, 128);
-            w.lnpart = a.get<float>((size_t)(w.ln_nblk > w.ln_tiles ? w.ln_nblk : w.ln_tiles) * 2 * Cout);
+            // rows: the stand-alone kernel's blocks, or one per 128-row half of the GEMM's tiles -- 2 cdiv(M, 256) on the 256-row kernel, an
+            // explicit bound although that kernel skips a half past M (gemm_bf16_256.hip) and the reduction reads ln_tiles rows
+            const int64_t tile_rows = 2 * cdiv64(M, 256);
+            w.lnpart = a.get<float>((size_t)(w.ln_nblk > tile_rows ? w.ln_nblk : tile_rows) * 2 * Cout);
         }
     }
     if (out) *out = w;

@@ -301,10 +301,14 @@ __global__ __launch_bounds__(512) void gemm_nt_bf16_256_kernel(const GemmNTB pin
             for (int i = 0; i < 2; ++i) asm volatile("" ::"v"(acc[a][b][i]));
     return;
 #endif
+    // A 128-row half whose first row is at or past M has nothing to write, and must not run its epilogue at all: the column-sum epilogues
+    // (EB_DOTCOL, EB_LNBWDM) store one partial row per 128-row half without a row guard, and their buffers are sized by cdiv(M, 128).  The
+    // condition is the same for the whole workgroup, so leaving the loop skips the epilogue's barriers on every thread alike.
     if constexpr (TALL) {
         // four 128 x 128 quadrants (A0..A3 against the one B half): whole rows of a 128-column output, so the LayerNorm epilogues run as they are
 #pragma unroll
         for (int a = 0; a < 4; ++a) {
+            if (m0 + a * 128 >= p.M) break;
             float* const Cs = Cs0 + (a & 1) * (128 * 128);   // alternate two 64 KB buffers: one barrier per quadrant
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
@@ -323,6 +327,7 @@ __global__ __launch_bounds__(512) void gemm_nt_bf16_256_kernel(const GemmNTB pin
         // a LayerNorm epilogue needs whole rows: the tile is parked as two [128][256] halves (N == 256: one column tile per row block)
 #pragma unroll
         for (int a = 0; a < 2; ++a) {
+            if (m0 + a * 128 >= p.M) break;
             float* const Cs = Cs0;
 #pragma unroll
             for (int b = 0; b < 2; ++b)
@@ -342,6 +347,7 @@ __global__ __launch_bounds__(512) void gemm_nt_bf16_256_kernel(const GemmNTB pin
     } else if constexpr (GATE) {
 #pragma unroll
         for (int a = 0; a < 2; ++a) {
+            if (m0 + a * 128 >= p.M) break;
             float* const Cs = Cs0;   // [128][256]: columns 0..127 first gate half, 128..255 second
 #pragma unroll
             for (int b = 0; b < 2; ++b)
@@ -362,6 +368,7 @@ __global__ __launch_bounds__(512) void gemm_nt_bf16_256_kernel(const GemmNTB pin
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const int a = q >> 1, b = q & 1;
+            if (m0 + a * 128 >= p.M) break;
             float* const Cs = Cs0 + (q & 1) * (128 * 128);   // alternate two 64 KB buffers: one barrier per quadrant
 #pragma unroll
             for (int i = 0; i < 2; ++i) {

@@ -516,6 +516,7 @@ __global__ __launch_bounds__(512) void gemm_nt_x3_kernel(const GemmX3 pin) {
     if constexpr (GATE) {
 #pragma unroll
         for (int a = 0; a < 2; ++a) {
+            if (m0 + a * 128 >= p.M) break;
             float* const Cs = Cs0;   // [128][256]: columns 0..127 first gate half, 128..255 second
             if (ah == a) {
 #pragma unroll
@@ -536,6 +537,9 @@ __global__ __launch_bounds__(512) void gemm_nt_x3_kernel(const GemmX3 pin) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const int a = q >> 1, b = q & 1;
+            // (a half past M writes nothing, and E_DOTCOL's unguarded column-sum row would land past a cdiv(M, 128)-row colpart; uniform
+            // over the workgroup, so the barriers stay balanced)
+            if (m0 + a * 128 >= p.M) break;
             float* const Cs = Cs0 + (q & 1) * (128 * 128);
 #ifndef X3_ABL_NOPARK
             if (ah == a) {

@@ -1349,8 +1349,9 @@ class _BottleneckFn(torch.autograd.Function):
         _require_gpu(w1, lw1, lb1, w2, lw2, lb2, w3, lw3, lb3)
         x = _nhwc(x)
         dev = x.device
-        B, _, H, W = x.shape
-        if bf:
+        B, C_, H, W = x.shape
+        ctx.fused = bf and _BottleneckFn._geometry_ok(C_, w1, lw1, lb1, w2, lw2, lb2, w3, lw3, lb3)
+        if ctx.fused:
             return _BottleneckFn._forward_bf16(ctx, lib, x, ((w1, lw1, lb1), (w2, lw2, lb2), (w3, lw3, lb3)), packs)
         empty = _empty_nhwc_bf16 if bf else _empty_nhwc
         ws_bytes = lib.dcpt_conv_ln_bf16_ws_bytes if bf else lib.dcpt_conv_ln_ws_bytes
@@ -1379,6 +1380,14 @@ class _BottleneckFn(torch.autograd.Function):
         return cur
 
     @staticmethod
+    def _geometry_ok(C_, w1, lw1, lb1, w2, lw2, lb2, w3, lw3, lb3):
+        """the one-call bf16 entry points assume C -> 2C (1x1) -> 2C (3x3) -> C (1x1), taken from x alone: any other width (BottleneckBlock's
+        ``bottleneck_channels``) takes the per-group path"""
+        C2 = 2 * C_
+        return (tuple(w1.shape) == (C2, C_, 1, 1) and tuple(w2.shape) == (C2, C2, 3, 3) and tuple(w3.shape) == (C_, C2, 1, 1)
+                and all(tuple(t.shape) == (C2,) for t in (lw1, lb1, lw2, lb2)) and tuple(lw3.shape) == (C_,) and tuple(lb3.shape) == (C_,))
+
+    @staticmethod
     def _forward_bf16(ctx, lib, x, groups, packs):
         """bf16 activations: the whole block in ONE library call (dcpt_bottleneck_fwd_bf16, ABI 15: LayerNorms in the GEMM epilogues)"""
         dev = x.device
@@ -1397,10 +1406,11 @@ class _BottleneckFn(torch.autograd.Function):
             pkbufs.append(pck.buf if pkp is not None else None)
             saved += [w_, lw_, z, y, stats]
             keep.append(lb_)
-        ctx.lnb = keep   # (the backward recomputes the inner ReLU masks from z: it needs the LayerNorm biases)
         ws = _workspace(dev, lib.dcpt_bottleneck_bf16_ws_bytes(B, H, W, C_, 0))
         check(lib.dcpt_bottleneck_fwd_bf16(x.data_ptr(), garr, ws.data_ptr(), ws.numel(), B, H, W, C_, _stream(dev)), "dcpt_bottleneck_fwd_bf16")
-        ctx.save_for_backward(*saved)
+        # the LayerNorm biases last: the backward recomputes the inner ReLU masks from z with them, so an in-place update between forward and
+        # backward must trip autograd's version check
+        ctx.save_for_backward(*saved, *keep)
         ctx.bf = True
         ctx.pkbufs = pkbufs   # (the backward of THIS forward reads the same operand images)
         return saved[-2]
@@ -1418,7 +1428,7 @@ class _BottleneckFn(torch.autograd.Function):
             w_, lw_, z, y, stats = sv[1 + 5 * k: 6 + 5 * k]
             dw, dlw, dlb = torch.empty_like(w_), torch.empty_like(lw_), torch.empty_like(lw_)
             pk = ctx.pkbufs[k]
-            garr[k] = _lib.BneckGroup(w_.data_ptr(), _p(pk), 0 if pk is None else pk.numel(), lw_.data_ptr(), ctx.lnb[k].data_ptr(), z.data_ptr(), y.data_ptr(),
+            garr[k] = _lib.BneckGroup(w_.data_ptr(), _p(pk), 0 if pk is None else pk.numel(), lw_.data_ptr(), sv[16 + k].data_ptr(), z.data_ptr(), y.data_ptr(),
                                       stats[0].data_ptr(), stats[1].data_ptr(), dw.data_ptr(), dlw.data_ptr(), dlb.data_ptr())
             grads += [dw, dlw, dlb]
         dx = _empty_nhwc_bf16(B, C_, H, W, dev)
@@ -1430,7 +1440,7 @@ class _BottleneckFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         lib = _lib.load()
-        if ctx.bf:
+        if ctx.fused:
             return _BottleneckFn._backward_bf16(ctx, lib, dy)
         sv = ctx.saved_tensors
         x, bf = sv[0], ctx.bf
