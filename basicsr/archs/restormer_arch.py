@@ -6,6 +6,10 @@ TransformerBlock is two autograd nodes: ``dcpt_mdta_*`` (LayerNorm -> qkv 1x1 ->
 attention as batched MFMA GEMMs -> project_out + residual) and ``dcpt_gdfn_*`` (LayerNorm -> project_in -> depthwise 3x3 ->
 GELU gate -> project_out + residual).  Down/Upsample are a dense 3x3 implicit-GEMM conv + an NHWC pixel (un)shuffle; skip
 connections are NHWC channel concats.  Child modules only own the parameters.
+
+``act_dtype="bf16"`` (this repo's extension, default "fp32"): every feature map from the patch_embed output to the output conv's
+input is stored in bf16 (dcpt_amd/csrc/restormer_bf16.hip); statistics, attention matrices, parameters, their gradients and the
+optimizer stay fp32, images go in and come out in fp32, and the state_dict is the same.
 """
 from __future__ import annotations
 
@@ -71,6 +75,7 @@ class Attention(nn.Module):
 class TransformerBlock(nn.Module):
     eps_1e5 = False   # PromptIR's copies of these blocks use LayerNorm eps 1e-5 ...
     softmax = False   # ... and softmax instead of ReLU attention (basicsr/archs/promptir_arch.py)
+    bf16 = False      # bf16 activation storage (set by the network's act_dtype)
 
     def __init__(self, dim, num_heads, ffn_expansion_factor, bias, LayerNorm_type):
         super().__init__()
@@ -84,21 +89,24 @@ class TransformerBlock(nn.Module):
         self.ffn = FeedForward(dim, ffn_expansion_factor, bias)
 
     def forward(self, x):
+        mdta, gdfn = (DF.mdta_bf16, DF.gdfn_bf16) if self.bf16 else (DF.mdta, DF.gdfn)
         w1, b1 = self.norm1.wb()
-        x = DF.mdta(x, w1, b1, self.attn.qkv.weight, self.attn.qkv_dwconv.weight, self.attn.project_out.weight,
-                    self.attn.temperature, self.attn.num_heads, self.norm1.biasfree, self.eps_1e5, self.softmax)
+        x = mdta(x, w1, b1, self.attn.qkv.weight, self.attn.qkv_dwconv.weight, self.attn.project_out.weight,
+                 self.attn.temperature, self.attn.num_heads, self.norm1.biasfree, self.eps_1e5, self.softmax)
         w2, b2 = self.norm2.wb()
-        return DF.gdfn(x, w2, b2, self.ffn.project_in.weight, self.ffn.dwconv.weight, self.ffn.project_out.weight,
-                       self.norm2.biasfree, self.eps_1e5)
+        return gdfn(x, w2, b2, self.ffn.project_in.weight, self.ffn.dwconv.weight, self.ffn.project_out.weight,
+                    self.norm2.biasfree, self.eps_1e5)
 
 
 class OverlapPatchEmbed(nn.Module):
+    bf16 = False
+
     def __init__(self, in_c=3, embed_dim=48, bias=False):
         super().__init__()
         self.proj = nn.Conv2d(in_c, embed_dim, kernel_size=3, stride=1, padding=1, bias=False)
 
     def forward(self, x):
-        return DF.conv3x3_in(x, self.proj.weight, None)
+        return DF.conv3x3_in(x, self.proj.weight, None, out_bf16=self.bf16)
 
 
 class Downsample(nn.Module):
@@ -140,6 +148,15 @@ class _RestormerBase(nn.Module):
         if save_mode not in (None, "auto", "full", "balanced", "lean"):
             raise ValueError(f"save_mode must be 'full', 'balanced', 'lean' or 'auto', got {save_mode!r}")
         self.save_mode = save_mode
+
+    def _set_act_dtype(self, act_dtype):
+        if act_dtype not in ("fp32", "bf16"):
+            raise ValueError(f"act_dtype must be 'fp32' or 'bf16', got {act_dtype!r}")
+        self.act_dtype = act_dtype
+        if act_dtype == "bf16":   # the blocks and the first conv switch storage; the glue ops follow the dtype of their input
+            for m in self.modules():
+                if isinstance(m, (TransformerBlock, OverlapPatchEmbed)):
+                    m.bf16 = True
 
     def _build(self, inp_channels, out_channels, dim, num_blocks, num_refinement_blocks, heads, ffn_expansion_factor, bias,
                LayerNorm_type, make_level):
@@ -187,7 +204,7 @@ class _RestormerBase(nn.Module):
 class Restormer(_RestormerBase):
     def __init__(self, inp_channels=3, out_channels=3, dim=48, num_blocks=[4, 6, 6, 8], num_refinement_blocks=4,
                  heads=[1, 2, 4, 8], ffn_expansion_factor=2.66, bias=False, LayerNorm_type="BiasFree", dual_pixel_task=False,
-                 scale=1, window_size=8, save_mode=None):
+                 scale=1, window_size=8, save_mode=None, act_dtype="fp32"):
         super().__init__()
         self._set_save_mode(save_mode)
         if dual_pixel_task or scale != 1:
@@ -196,6 +213,7 @@ class Restormer(_RestormerBase):
         self._build(inp_channels, out_channels, dim, num_blocks, num_refinement_blocks, heads, ffn_expansion_factor, bias,
                     LayerNorm_type,
                     lambda d, h, n: SequentialTransformerBlock(d, h, n, ffn_expansion_factor, bias, LayerNorm_type))
+        self._set_act_dtype(act_dtype)
 
     def forward(self, inp_img, hook=None):
         with DF.restormer_save(self.save_mode, inp_img.device):
@@ -210,7 +228,8 @@ class Restormer_origin(_RestormerBase):
     """reference :425-517: plain nn.Sequential levels, WithBias LayerNorm default, no ``hook`` argument."""
 
     def __init__(self, inp_channels=3, out_channels=3, dim=48, num_blocks=[4, 6, 6, 8], num_refinement_blocks=4,
-                 heads=[1, 2, 4, 8], ffn_expansion_factor=2.66, bias=False, LayerNorm_type="WithBias", dual_pixel_task=False, save_mode=None):
+                 heads=[1, 2, 4, 8], ffn_expansion_factor=2.66, bias=False, LayerNorm_type="WithBias", dual_pixel_task=False, save_mode=None,
+                 act_dtype="fp32"):
         super().__init__()
         self._set_save_mode(save_mode)
         if dual_pixel_task:
@@ -219,6 +238,7 @@ class Restormer_origin(_RestormerBase):
         self._build(inp_channels, out_channels, dim, num_blocks, num_refinement_blocks, heads, ffn_expansion_factor, bias,
                     LayerNorm_type,
                     lambda d, h, n: nn.Sequential(*[TransformerBlock(d, h, ffn_expansion_factor, bias, LayerNorm_type) for _ in range(n)]))
+        self._set_act_dtype(act_dtype)
 
     def forward(self, inp_img):
         with DF.restormer_save(self.save_mode, inp_img.device):

@@ -4,7 +4,7 @@ contract (that is bench.py).  Prints one JSON line per workload.
 
     python bench_extra.py --workload dcpt|restormer|infer2k|naf|swinir|rcan [--dtype fp32|bf16] [--steps K] [--warmup W]
 
-``--dtype bf16`` (dcpt, naf, infer2k): every feature map of the encoder in bf16 storage with fp32 accumulation (act_dtype="bf16";
+``--dtype bf16`` (dcpt, naf, infer2k, restormer): every feature map of the encoder in bf16 storage with fp32 accumulation (act_dtype="bf16";
 dcpt: the classifier head too unless --head-dtype fp32); images, parameters and the optimizer stay fp32.  Its lines carry BOTH
 rooflines: the bf16 MFMA peak (2.5 PF dense) and the HBM roof with the bf16 algorithmic bytes -- in bf16 the network is HBM-bound
 (SURVEY 8d).
@@ -51,9 +51,10 @@ def timed(fn, steps, warmup):
     return dt
 
 
-def run_restormer(dev, save="balanced", steps=5, warmup=2, B=64, S=128, rank=0, world=1):
+def run_restormer(dev, save="balanced", steps=5, warmup=2, B=64, S=128, rank=0, world=1, dtype="fp32"):
     """BASELINE.json configs[3]: Restormer defaults (reference restormer_arch.py:234-422), fwd + L1 + bwd (+ gradient all-reduce: the network
-    in DistributedDataParallel as base_model.py:108-115 wraps it, when world > 1) + AdamW, fp32."""
+    in DistributedDataParallel as base_model.py:108-115 wraps it, when world > 1) + AdamW, fp32; dtype "bf16": act_dtype="bf16" (feature
+    maps in bf16 storage, fp32 accumulation / parameters / optimizer), reported against the bf16 MFMA peak."""
     from basicsr.archs import build_network
     from dcpt_amd import functional as DF
     from dcpt_amd.keyed_init import fill_module_
@@ -61,7 +62,7 @@ def run_restormer(dev, save="balanced", steps=5, warmup=2, B=64, S=128, rank=0, 
     g = torch.Generator(device=dev).manual_seed(1234 + rank)
     torch.cuda.reset_peak_memory_stats()
     DF.set_restormer_save(save)
-    net = fill_module_(build_network(dict(type="Restormer"))).to(dev)
+    net = fill_module_(build_network(dict(type="Restormer", **({} if dtype == "fp32" else dict(act_dtype=dtype))))).to(dev)
     bare = net
     if world > 1:
         from torch.nn.parallel import DistributedDataParallel
@@ -82,10 +83,11 @@ def run_restormer(dev, save="balanced", steps=5, warmup=2, B=64, S=128, rank=0, 
 
     dt = timed(step, steps, warmup)
     flops = B * (S / 128.0) ** 2 * 232e9      # 77.45 GF fwd -> 232 GF fwd+bwd per 128^2 image
-    return dict(workload=f"Restormer (dim 48, [4,6,6,8], BiasFree LN) fwd+L1+bwd+AdamW, B={B}, {S}x{S}, fp32, saved tensors: {save} "
+    peak = 2.5e15 if dtype == "bf16" else 157.3e12
+    return dict(workload=f"Restormer (dim 48, [4,6,6,8], BiasFree LN) fwd+L1+bwd+AdamW, B={B}, {S}x{S}, {dtype}, saved tensors: {save} "
                          "(BASELINE.json configs[3])",
                 ms_per_step=round(dt * 1e3, 2), megapixels_per_s=round(world * B * S * S / 1e6 / dt, 3), steps=steps, warmup=warmup,
-                alg_tflops=round(flops / dt / 1e12, 2), mfma_frac=round(flops / dt / 157.3e12, 4),
+                alg_tflops=round(flops / dt / 1e12, 2), mfma_frac=round(flops / dt / peak, 4),
                 peak_mem_gb=round(torch.cuda.max_memory_allocated() / 2 ** 30, 2))
 
 
@@ -362,7 +364,10 @@ def main():
         else:
             res.update(alg_tflops=round(flops / dt / 1e12, 2), mfma_frac=round(flops / dt / 157.3e12, 4))
     elif args.workload == "restormer":
-        res = run_restormer(dev, args.restormer_save, args.steps, args.warmup, args.batch or 64, args.size or 128, rank=rank, world=world)
+        if args.dtype not in ("fp32", "bf16"):
+            raise SystemExit("--workload restormer: --dtype fp32 or bf16")
+        res = run_restormer(dev, args.restormer_save, args.steps, args.warmup, args.batch or 64, args.size or 128, rank=rank, world=world,
+                            dtype=args.dtype)
     elif args.workload == "swinir":
         res = run_swinir(dev, args.steps, args.warmup, args.batch or 8, args.size or 256)
     elif args.workload == "rcan":

@@ -230,6 +230,24 @@ SIGNATURES = {
                              cint, cint, stream_t]),
     "dcpt_gdfn_bwd": (cint, [C.POINTER(GdfnParams), C.POINTER(GdfnParams), f32p, C.POINTER(GdfnSaved), f32p, f32p, C.c_void_p,
                              sz, cint, cint, cint, cint, cint, cint, stream_t]),
+    # Restormer with bf16 activation storage (restormer_bf16.hip): the saved structs have the field order of MdtaSaved / GdfnSaved
+    "dcpt_mdta_bf16_ws_bytes": (sz, [cint, cint, cint, cint, cint, cint]),
+    "dcpt_mdta_bf16_fwd": (cint, [C.POINTER(MdtaParams), f32p, f32p, C.POINTER(MdtaSaved), C.c_void_p, sz, cint, cint, cint, cint,
+                                  cint, cint, stream_t]),
+    "dcpt_mdta_bf16_bwd": (cint, [C.POINTER(MdtaParams), C.POINTER(MdtaParams), f32p, C.POINTER(MdtaSaved), f32p, f32p, C.c_void_p,
+                                  sz, cint, cint, cint, cint, cint, cint, stream_t]),
+    "dcpt_gdfn_bf16_ws_bytes": (sz, [cint, cint, cint, cint, cint, cint]),
+    "dcpt_gdfn_bf16_fwd": (cint, [C.POINTER(GdfnParams), f32p, f32p, C.POINTER(GdfnSaved), C.c_void_p, sz, cint, cint, cint, cint,
+                                  cint, cint, stream_t]),
+    "dcpt_gdfn_bf16_bwd": (cint, [C.POINTER(GdfnParams), C.POINTER(GdfnParams), f32p, C.POINTER(GdfnSaved), f32p, f32p, C.c_void_p,
+                                  sz, cint, cint, cint, cint, cint, cint, stream_t]),
+    "dcpt_pixel_unshuffle_bf16": (cint, [f32p, f32p, cint, cint, cint, cint, stream_t]),
+    "dcpt_pixel_shuffle_bf16": (cint, [f32p, f32p, cint, cint, cint, cint, stream_t]),
+    "dcpt_concat_channels_bf16": (cint, [f32p, f32p, f32p, i64, cint, cint, stream_t]),
+    "dcpt_split_channels_bf16": (cint, [f32p, f32p, f32p, i64, cint, cint, stream_t]),
+    "dcpt_conv_bf16_ws_bytes": (sz, [cint, cint, cint, cint, cint, cint, cint]),
+    "dcpt_conv_fwd_bf16": (cint, [f32p, f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint, cint, cint, stream_t]),
+    "dcpt_conv_bwd_bf16": (cint, [f32p, f32p, f32p, f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint, cint, cint, stream_t]),
     "dcpt_swin_attn_ws_bytes": (sz, [cint, cint, cint, cint, cint, cint]),
     "dcpt_swin_attn_fwd": (cint, [C.POINTER(SwinAttnParams), f32p, f32p, C.POINTER(SwinAttnSaved), C.c_void_p, sz, cint, cint, cint,
                                   cint, cint, cint, cint, stream_t]),

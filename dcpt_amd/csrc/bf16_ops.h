@@ -53,6 +53,11 @@ int launch_dw_bwd_fused_bf16(const bf16_t* dts, const bf16_t* t1, const float* w
 int launch_dw_ring_fwd_bf16(const bf16_t* t1, const float* w2p, const float* b2, bf16_t* t2, float* pool_part, const DwGeom& g, hipStream_t s);
 int launch_dw_ring_bwd_fused_bf16(const bf16_t* dts, const bf16_t* t1, const float* w2p, const float* b2, const float* simg, const float* dpool,
                                   bf16_t* dt1, float* wpart, const DwGeom& g, hipStream_t s);
+// the Restormer GDFN forms (kernels.h: launch_dw_ring_gelu_fwd_f32 / _bwd_gelu_f32) in bf16 storage; usable where
+// dw_ring_usable / dw_ring_bwd_usable({B, H, W, Ch}, 2) hold (Ch % 8 == 0)
+int launch_dw_ring_gelu_fwd_bf16(const bf16_t* u, const float* w2p, bf16_t* t, int B, int H, int W, int Ch, hipStream_t s);
+int launch_dw_ring_bwd_gelu_bf16(const bf16_t* dt, const bf16_t* u, const float* w2p, bf16_t* du, float* wpart, int B, int H, int W, int Ch,
+                                 hipStream_t s);
 
 // conv3x3.hip: the network-edge 3x3 convs with the feature side in bf16 storage
 int launch_conv3x3_s2b_bf16(const float* x, const float* w, const float* bias, bf16_t* y, int B, int H, int W, int Cs, int Cb, int wmode, hipStream_t s);

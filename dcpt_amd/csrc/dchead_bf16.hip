@@ -552,3 +552,39 @@ extern "C" int dcpt_conv_wpack_bf16_multi(const float* const* w, void* const* pa
     }
     return DCPT_OK;
 }
+
+// ---- plain bias-free conv (1 x 1 or dense 3 x 3, pad 1) in bf16 storage: the Restormer glue (Down/Upsample convs, reduce_chan_level*) ----
+// Same GEMMs as the head's conv groups above without the LayerNorm; weights packed in the call.
+extern "C" size_t dcpt_conv_bf16_ws_bytes(int B, int H, int W, int Cin, int Cout, int ksize, int backward) {
+    return conv_layout(B, H, W, Cin, Cout, ksize, backward, false, nullptr, 0, nullptr);
+}
+
+extern "C" int dcpt_conv_fwd_bf16(const uint16_t* x, const float* w, uint16_t* y, void* ws, size_t ws_bytes, int B, int H, int W, int Cin, int Cout,
+                                  int ksize, dcpt_stream_t stream) {
+    hipStream_t s = (hipStream_t)stream;
+    DCPT_CHECK_ARG(x && w && y, "conv_fwd_bf16: null argument");
+    DCPT_CHECK_ARG(B > 0 && H > 0 && W > 0 && conv_shape_ok(Cin, Cout, ksize), "conv_fwd_bf16: ksize=%d Cin=%d Cout=%d (channels %% 8 == 0, Cout <= 1024)",
+                   ksize, Cin, Cout);
+    ConvWsB cw;
+    const size_t need = conv_layout(B, H, W, Cin, Cout, ksize, 0, false, ws, ws_bytes, &cw);
+    if (ws == nullptr || need > ws_bytes) {
+        dcpt_set_error("conv_fwd_bf16: workspace too small");
+        return DCPT_ERR_WS;
+    }
+    return conv_fwd(x, w, y, cw, B, H, W, Cin, Cout, ksize, s);
+}
+
+extern "C" int dcpt_conv_bwd_bf16(const uint16_t* dy, const uint16_t* x, const float* w, uint16_t* dx, float* dw, void* ws, size_t ws_bytes, int B,
+                                  int H, int W, int Cin, int Cout, int ksize, dcpt_stream_t stream) {
+    hipStream_t s = (hipStream_t)stream;
+    DCPT_CHECK_ARG(dy && x && w && dx && dw, "conv_bwd_bf16: null argument");
+    DCPT_CHECK_ARG(B > 0 && H > 0 && W > 0 && conv_shape_ok(Cin, Cout, ksize) && Cin <= 1024,
+                   "conv_bwd_bf16: ksize=%d Cin=%d Cout=%d (channels %% 8 == 0, <= 1024)", ksize, Cin, Cout);
+    ConvWsB cw;
+    const size_t need = conv_layout(B, H, W, Cin, Cout, ksize, 1, false, ws, ws_bytes, &cw);
+    if (ws == nullptr || need > ws_bytes) {
+        dcpt_set_error("conv_bwd_bf16: workspace too small");
+        return DCPT_ERR_WS;
+    }
+    return conv_bwd(dy, x, w, dx, dw, cw, B, H, W, Cin, Cout, ksize, s);
+}

@@ -796,3 +796,18 @@ int launch_dw_ring_gelu_fwd_f32(const float* u, const float* w2p, float* t, int 
     const DwGeom g{B, H, W, Ch};
     return launch_fwd<float, 1>(u, w2p, nullptr, t, nullptr, g, s);
 }
+
+// the GDFN forms with bf16 storage (restormer_bf16.hip): u / t / dt / du / dy / x / dx bf16, taps and partials fp32, the exact
+// erf GELU.  The bf16 backward does not write the gate product on the way (tout is an fp32-only option): its callers keep t or recompute it
+// with launch_dw_ring_gelu_fwd_bf16.
+int launch_dw_ring_gelu_fwd_bf16(const bf16_t* u, const float* w2p, bf16_t* t, int B, int H, int W, int Ch, hipStream_t s) {
+    trace_tag("dw.ring_gelu_fwd_bf16");
+    const DwGeom g{B, H, W, Ch};
+    return launch_fwd<bf16_t, 1>(u, w2p, nullptr, t, nullptr, g, s);
+}
+int launch_dw_ring_bwd_gelu_bf16(const bf16_t* dt, const bf16_t* u, const float* w2p, bf16_t* du, float* wpart, int B, int H, int W, int Ch,
+                                 hipStream_t s) {
+    trace_tag("dw.ring_bwd_gelu_bf16");
+    const DwGeom g{B, H, W, Ch};
+    return launch_bwd<bf16_t, 1>(dt, u, w2p, nullptr, nullptr, nullptr, du, wpart, g, s);
+}

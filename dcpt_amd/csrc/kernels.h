@@ -161,3 +161,14 @@ int launch_nchw_channel_sum(const float* x, float* part, float* out, int B, int 
 // layout converters for arbitrary C
 int launch_nchw_to_nhwc(const float* x, float* y, int B, int C, int HW, hipStream_t s);
 int launch_nhwc_to_nchw(const float* x, float* y, int B, int C, int HW, hipStream_t s);
+
+// restormer.hip: fp32 pieces of the MDTA / GDFN blocks shared with their bf16-storage form (restormer_bf16.hip)
+int launch_mdta_sq_norm(const float* part, int nblk, float* nrm, int B, int C2, hipStream_t s);
+int launch_mdta_attn_finalize(const float* slab, int splits, const float* nrm, const float* temp, float* ghat, float* attn, float* attnT,
+                              int B, int heads, int ch, int c, bool softmax, hipStream_t s);
+int launch_mdta_attn_bwd(const float* slab, int splits, const float* attn, const float* ghat, const float* nrm, const float* temp, float* dG,
+                         float* dGT, float* cqk, float* dtemp_part, float* scratch, int B, int heads, int ch, int c, bool softmax, hipStream_t s);
+int launch_mdta_dtemp_reduce(const float* part, float* dtemp, int B, int heads, hipStream_t s);
+// GDFN weight packs with the hidden width padded to hp (modes of gdfn_pack_kernel / gdfn_unpack_kernel)
+int launch_gdfn_pack(const float* in, float* out, int c, int h, int hp, int mode, hipStream_t s);
+int launch_gdfn_unpack(const float* in, float* out, int c, int h, int hp, int mode, hipStream_t s);

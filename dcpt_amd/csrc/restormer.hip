@@ -741,3 +741,58 @@ extern "C" int dcpt_split_channels(const float* cat, float* a, float* b, int64_t
     DCPT_CHECK_LAUNCH("split_channels");
     return DCPT_OK;
 }
+
+// =====================================================================================================
+// The fp32 pieces that the bf16-storage blocks (restormer_bf16.hip) share with these: the L2 norms, the attention finalize /
+// backward over fp32 Gram slabs, the temperature reduction and the GDFN weight (un)packing.  Same kernels, same launch shapes.
+int launch_mdta_sq_norm(const float* part, int nblk, float* nrm, int B, int C2, hipStream_t s) {
+    sq_norm_kernel<<<dim3(cdiv(B * C2, 256)), dim3(256), 0, s>>>(part, nblk, nrm, B, C2);
+    DCPT_CHECK_LAUNCH("sq_norm");
+    return DCPT_OK;
+}
+
+int launch_mdta_attn_finalize(const float* slab, int splits, const float* nrm, const float* temp, float* ghat, float* attn, float* attnT,
+                              int B, int heads, int ch, int c, bool softmax, hipStream_t s) {
+    if (softmax) {
+        DCPT_CHECK_ARG(ch <= 64 * SM_MAXU, "mdta: softmax attention supports up to %d channels per head", 64 * SM_MAXU);
+        attn_finalize_softmax_kernel<<<dim3(B * heads), dim3(256), 0, s>>>(slab, splits, nrm, temp, ghat, attn, attnT, heads, ch, c);
+    } else {
+        attn_finalize_kernel<<<dim3(B * heads), dim3(256), 0, s>>>(slab, splits, nrm, temp, ghat, attn, attnT, heads, ch, c);
+    }
+    DCPT_CHECK_LAUNCH("attn_finalize");
+    return DCPT_OK;
+}
+
+int launch_mdta_attn_bwd(const float* slab, int splits, const float* attn, const float* ghat, const float* nrm, const float* temp, float* dG,
+                         float* dGT, float* cqk, float* dtemp_part, float* scratch, int B, int heads, int ch, int c, bool softmax, hipStream_t s) {
+    if (softmax) {
+        DCPT_CHECK_ARG(ch <= 256, "mdta: softmax attention supports up to 256 channels per head");
+        attn_bwd_kernel<true><<<dim3(B * heads), dim3(256), 0, s>>>(slab, splits, attn, ghat, nrm, temp, dG, dGT, cqk, dtemp_part, scratch,
+                                                                    heads, ch, c);
+    } else {
+        attn_bwd_kernel<false><<<dim3(B * heads), dim3(256), 0, s>>>(slab, splits, attn, ghat, nrm, temp, dG, dGT, cqk, dtemp_part, scratch,
+                                                                     heads, ch, c);
+    }
+    DCPT_CHECK_LAUNCH("attn_bwd");
+    return DCPT_OK;
+}
+
+int launch_mdta_dtemp_reduce(const float* part, float* dtemp, int B, int heads, hipStream_t s) {
+    dtemp_reduce_kernel<<<dim3(cdiv(heads, 64)), dim3(64), 0, s>>>(part, dtemp, B, heads);
+    DCPT_CHECK_LAUNCH("dtemp_reduce");
+    return DCPT_OK;
+}
+
+int launch_gdfn_pack(const float* in, float* out, int c, int h, int hp, int mode, hipStream_t s) {
+    const int64_t n = mode == 1 ? (int64_t)18 * hp : (mode == 0 || mode == 4) ? (int64_t)2 * hp * c : (int64_t)c * hp;
+    gdfn_pack_kernel<<<dim3(grid_for(n)), dim3(256), 0, s>>>(in, out, c, h, hp, mode);
+    DCPT_CHECK_LAUNCH("gdfn_pack");
+    return DCPT_OK;
+}
+
+int launch_gdfn_unpack(const float* in, float* out, int c, int h, int hp, int mode, hipStream_t s) {
+    const int64_t n = mode == 0 ? (int64_t)2 * h * c : mode == 1 ? (int64_t)2 * h * 9 : (int64_t)c * h;
+    gdfn_unpack_kernel<<<dim3(grid_for(n)), dim3(256), 0, s>>>(in, out, c, h, hp, mode);
+    DCPT_CHECK_LAUNCH("gdfn_unpack");
+    return DCPT_OK;
+}

@@ -1744,6 +1744,8 @@ class _ConvFn(torch.autograd.Function):
 
 
 def conv_nobias(x, weight):
+    if x.dtype == torch.bfloat16:
+        return _ConvBf16Fn.apply(x, weight)
     return _ConvFn.apply(x, weight)
 
 
@@ -1790,10 +1792,14 @@ class _PixelShuffleFn(torch.autograd.Function):
 
 
 def pixel_unshuffle2(x):
+    if x.dtype == torch.bfloat16:
+        return _PixelShuffleBf16Fn.apply(x, False)
     return _PixelUnshuffleFn.apply(x)
 
 
 def pixel_shuffle2(x):
+    if x.dtype == torch.bfloat16:
+        return _PixelShuffleBf16Fn.apply(x, True)
     return _PixelShuffleFn.apply(x)
 
 
@@ -1826,6 +1832,8 @@ class _ConcatFn(torch.autograd.Function):
 
 
 def concat_channels(a, b):
+    if a.dtype == torch.bfloat16:
+        return _ConcatBf16Fn.apply(a, b)
     return _ConcatFn.apply(a, b)
 
 
@@ -2024,6 +2032,249 @@ class _GDFNFn(torch.autograd.Function):
 def gdfn(x, norm_w, norm_b, in_w, dw_w, out_w, biasfree, eps_1e5=False):
     flags = (LN_BIASFREE if biasfree else 0) | (LN_EPS_1E5 if eps_1e5 else 0)
     return _GDFNFn.apply(x, norm_w, norm_b, in_w, dw_w, out_w, flags)
+
+
+# ------------------------------------------------------------------------------------------------
+# Restormer with bf16 activation storage (restormer_bf16.hip; Restormer / Restormer_origin with act_dtype="bf16"): the feature maps and
+# the tensors the halves keep are bf16, statistics / attention matrices / parameters / parameter gradients fp32.  The save modes keep
+# the same sets of tensors as the fp32 nodes above (bit-identical results in every mode).
+class _MDTABf16Fn(torch.autograd.Function):
+    """_MDTAFn with bf16 storage -> dcpt_mdta_bf16_fwd / _bwd."""
+
+    @staticmethod
+    def forward(ctx, x, norm_w, norm_b, qkv_w, dw_w, proj_w, temperature, heads, flags, train):
+        lib = _lib.load()
+        _require_gpu_bf16(x)
+        _require_gpu(norm_w, norm_b, qkv_w, dw_w, proj_w, temperature)
+        x = _nhwc(x)
+        ps = [None if t is None else _contig(t.detach()) for t in (norm_w, norm_b, qkv_w, dw_w, proj_w, temperature)]
+        B, Cc, H, W = x.shape
+        dev = x.device
+        M, ch = B * H * W, Cc // heads
+        nograd = not train
+        y = _empty_nhwc_bf16(B, Cc, H, W, dev)
+        stats = torch.empty((2, M), dtype=torch.float32, device=dev)
+        mode = "lean" if nograd else _restormer_mode(dev)
+        qkv1 = None if mode == "lean" else _empty_nhwc_bf16(B, 3 * Cc, H, W, dev)
+        qkv = _empty_nhwc_bf16(B, 3 * Cc, H, W, dev)
+        nrm = torch.empty((B, 2 * Cc), dtype=torch.float32, device=dev)
+        att = torch.empty((3, B, heads, ch, ch), dtype=torch.float32, device=dev)
+        out_att = None if mode != "full" else _empty_nhwc_bf16(B, Cc, H, W, dev)
+        xn = None if mode != "full" else _empty_nhwc_bf16(B, Cc, H, W, dev)
+        sv = MdtaSaved(stats[0].data_ptr(), stats[1].data_ptr(), _p(qkv1), qkv.data_ptr(), nrm.data_ptr(),
+                       att[0].data_ptr(), att[1].data_ptr(), att[2].data_ptr(), _p(out_att), _p(xn))
+        pp = MdtaParams(*[_p(t) for t in ps])
+        ws = _workspace(dev, lib.dcpt_mdta_bf16_ws_bytes(B, H, W, Cc, heads, 2 if mode == "full" else 0))
+        check(lib.dcpt_mdta_bf16_fwd(C.byref(pp), x.data_ptr(), y.data_ptr(), C.byref(sv), ws.data_ptr(), ws.numel(), B, H, W, Cc,
+                                     heads, int(flags), _stream(dev)), "dcpt_mdta_bf16_fwd")
+        ctx.heads, ctx.flags = heads, int(flags)
+        ctx.has_bias = ps[1] is not None
+        if nograd:   # nothing is kept for a backward pass that cannot happen
+            return y
+        kept = [t for t in (qkv1, out_att, xn) if t is not None]
+        ctx.kept = (qkv1 is not None, out_att is not None, xn is not None)
+        ctx.save_for_backward(x, stats, qkv, nrm, att, *kept, *[t for t in ps if t is not None])
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        lib = _lib.load()
+        x, stats, qkv, nrm, att, *ps = ctx.saved_tensors
+        ps = list(ps)
+        qkv1, out_att, xn = (ps.pop(0) if k else None for k in ctx.kept)
+        if ctx.has_bias:
+            norm_w, norm_b, qkv_w, dw_w, proj_w, temp = ps
+        else:
+            norm_w, qkv_w, dw_w, proj_w, temp = ps
+            norm_b = None
+        _require_gpu_bf16(dy)
+        dy = _nhwc(dy)
+        B, Cc, H, W = x.shape
+        dev = x.device
+        dx = _empty_nhwc_bf16(B, Cc, H, W, dev)
+        plist = [norm_w, norm_b, qkv_w, dw_w, proj_w, temp]
+        grads = [None if t is None else torch.empty_like(t) for t in plist]
+        sv = MdtaSaved(stats[0].data_ptr(), stats[1].data_ptr(), _p(qkv1), qkv.data_ptr(), nrm.data_ptr(),
+                       att[0].data_ptr(), att[1].data_ptr(), att[2].data_ptr(), _p(out_att), _p(xn))
+        pp = MdtaParams(*[_p(t) for t in plist])
+        gg = MdtaParams(*[_p(t) for t in grads])
+        ws = _workspace(dev, lib.dcpt_mdta_bf16_ws_bytes(B, H, W, Cc, ctx.heads, 3 if all(ctx.kept) else 1))
+        check(lib.dcpt_mdta_bf16_bwd(C.byref(pp), C.byref(gg), x.data_ptr(), C.byref(sv), dy.data_ptr(), dx.data_ptr(), ws.data_ptr(),
+                                     ws.numel(), B, H, W, Cc, ctx.heads, ctx.flags, _stream(dev)), "dcpt_mdta_bf16_bwd")
+        return (dx, *grads, None, None, None)
+
+
+def _train(*ts) -> bool:
+    """a backward pass can follow (autograd.Function.forward itself always runs with grad mode off)"""
+    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in ts)
+
+
+def mdta_bf16(x, norm_w, norm_b, qkv_w, dw_w, proj_w, temperature, heads, biasfree, eps_1e5=False, softmax=False):
+    """mdta() with bf16 activation storage: x and the result are torch.bfloat16 NHWC maps."""
+    flags = (LN_BIASFREE if biasfree else 0) | (LN_EPS_1E5 if eps_1e5 else 0) | (ATTN_SOFTMAX if softmax else 0)
+    train = _train(x, norm_w, norm_b, qkv_w, dw_w, proj_w, temperature)
+    return _MDTABf16Fn.apply(x, norm_w, norm_b, qkv_w, dw_w, proj_w, temperature, heads, flags, train)
+
+
+class _GDFNBf16Fn(torch.autograd.Function):
+    """_GDFNFn with bf16 storage -> dcpt_gdfn_bf16_fwd / _bwd (hidden padded to a multiple of 8)."""
+
+    @staticmethod
+    def forward(ctx, x, norm_w, norm_b, in_w, dw_w, out_w, flags, train):
+        lib = _lib.load()
+        _require_gpu_bf16(x)
+        _require_gpu(norm_w, norm_b, in_w, dw_w, out_w)
+        x = _nhwc(x)
+        ps = [None if t is None else _contig(t.detach()) for t in (norm_w, norm_b, in_w, dw_w, out_w)]
+        B, Cc, H, W = x.shape
+        dev = x.device
+        M = B * H * W
+        hidden = ps[4].shape[1]
+        hp = (hidden + 7) // 8 * 8
+        nograd = not train
+        y = _empty_nhwc_bf16(B, Cc, H, W, dev)
+        stats = torch.empty((2, M), dtype=torch.float32, device=dev)
+        full = not nograd and _restormer_mode(dev) == "full"
+        u = _empty_nhwc_bf16(B, 2 * hp, H, W, dev)
+        t = _empty_nhwc_bf16(B, hp, H, W, dev) if full else None
+        xn = _empty_nhwc_bf16(B, Cc, H, W, dev) if full else None
+        sv = GdfnSaved(stats[0].data_ptr(), stats[1].data_ptr(), u.data_ptr(), _p(t), _p(xn))
+        pp = GdfnParams(*[_p(q) for q in ps])
+        ws = _workspace(dev, lib.dcpt_gdfn_bf16_ws_bytes(B, H, W, Cc, hidden, 2 if full else 0))
+        check(lib.dcpt_gdfn_bf16_fwd(C.byref(pp), x.data_ptr(), y.data_ptr(), C.byref(sv), ws.data_ptr(), ws.numel(), B, H, W, Cc,
+                                     hidden, int(flags), _stream(dev)), "dcpt_gdfn_bf16_fwd")
+        ctx.full = full
+        ctx.has_bias, ctx.flags, ctx.hidden = ps[1] is not None, int(flags), hidden
+        if nograd:
+            return y
+        ctx.save_for_backward(x, stats, u, *([t, xn] if full else []), *[q for q in ps if q is not None])
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        lib = _lib.load()
+        x, stats, u, *ps = ctx.saved_tensors
+        t = xn = None
+        if ctx.full:
+            t, xn, *ps = ps
+        if ctx.has_bias:
+            norm_w, norm_b, in_w, dw_w, out_w = ps
+        else:
+            norm_w, in_w, dw_w, out_w = ps
+            norm_b = None
+        _require_gpu_bf16(dy)
+        dy = _nhwc(dy)
+        B, Cc, H, W = x.shape
+        dev = x.device
+        dx = _empty_nhwc_bf16(B, Cc, H, W, dev)
+        plist = [norm_w, norm_b, in_w, dw_w, out_w]
+        grads = [None if q is None else torch.empty_like(q) for q in plist]
+        sv = GdfnSaved(stats[0].data_ptr(), stats[1].data_ptr(), u.data_ptr(), _p(t), _p(xn))
+        pp = GdfnParams(*[_p(q) for q in plist])
+        gg = GdfnParams(*[_p(q) for q in grads])
+        ws = _workspace(dev, lib.dcpt_gdfn_bf16_ws_bytes(B, H, W, Cc, ctx.hidden, 3 if ctx.full else 1))
+        check(lib.dcpt_gdfn_bf16_bwd(C.byref(pp), C.byref(gg), x.data_ptr(), C.byref(sv), dy.data_ptr(), dx.data_ptr(), ws.data_ptr(),
+                                     ws.numel(), B, H, W, Cc, ctx.hidden, ctx.flags, _stream(dev)), "dcpt_gdfn_bf16_bwd")
+        return (dx, *grads, None, None)
+
+
+def gdfn_bf16(x, norm_w, norm_b, in_w, dw_w, out_w, biasfree, eps_1e5=False):
+    """gdfn() with bf16 activation storage."""
+    flags = (LN_BIASFREE if biasfree else 0) | (LN_EPS_1E5 if eps_1e5 else 0)
+    return _GDFNBf16Fn.apply(x, norm_w, norm_b, in_w, dw_w, out_w, flags, _train(x, norm_w, norm_b, in_w, dw_w, out_w))
+
+
+class _ConvBf16Fn(torch.autograd.Function):
+    """_ConvFn with bf16 NHWC features (dcpt_conv_fwd_bf16 / _bwd_bf16); weight and its gradient fp32."""
+
+    @staticmethod
+    def forward(ctx, x, weight):
+        lib = _lib.load()
+        _require_gpu_bf16(x)
+        _require_gpu(weight)
+        x = _nhwc(x)
+        w_ = _contig(weight.detach())
+        B, Cin, H, W = x.shape
+        Cout, ks = w_.shape[0], w_.shape[2]
+        dev = x.device
+        y = _empty_nhwc_bf16(B, Cout, H, W, dev)
+        ws = _workspace(dev, lib.dcpt_conv_bf16_ws_bytes(B, H, W, Cin, Cout, ks, 0))
+        check(lib.dcpt_conv_fwd_bf16(x.data_ptr(), w_.data_ptr(), y.data_ptr(), ws.data_ptr(), ws.numel(), B, H, W, Cin, Cout, ks,
+                                     _stream(dev)), "dcpt_conv_fwd_bf16")
+        ctx.save_for_backward(x, w_)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        lib = _lib.load()
+        x, w_ = ctx.saved_tensors
+        _require_gpu_bf16(dy)
+        dy = _nhwc(dy)
+        B, Cin, H, W = x.shape
+        Cout, ks = w_.shape[0], w_.shape[2]
+        dev = x.device
+        dx = _empty_nhwc_bf16(B, Cin, H, W, dev)
+        dw = torch.empty_like(w_)
+        ws = _workspace(dev, lib.dcpt_conv_bf16_ws_bytes(B, H, W, Cin, Cout, ks, 1))
+        check(lib.dcpt_conv_bwd_bf16(dy.data_ptr(), x.data_ptr(), w_.data_ptr(), dx.data_ptr(), dw.data_ptr(), ws.data_ptr(),
+                                     ws.numel(), B, H, W, Cin, Cout, ks, _stream(dev)), "dcpt_conv_bwd_bf16")
+        return dx, dw
+
+
+def _shuffle_bf16(lib, x, up):
+    x = _nhwc(x)
+    B, Cc, H, W = x.shape
+    if up:
+        y = _empty_nhwc_bf16(B, Cc // 4, 2 * H, 2 * W, x.device)
+        check(lib.dcpt_pixel_shuffle_bf16(x.data_ptr(), y.data_ptr(), B, H, W, Cc, _stream(x.device)), "dcpt_pixel_shuffle_bf16")
+    else:
+        y = _empty_nhwc_bf16(B, 4 * Cc, H // 2, W // 2, x.device)
+        check(lib.dcpt_pixel_unshuffle_bf16(x.data_ptr(), y.data_ptr(), B, H, W, Cc, _stream(x.device)), "dcpt_pixel_unshuffle_bf16")
+    return y
+
+
+class _PixelShuffleBf16Fn(torch.autograd.Function):
+    """PixelShuffle(2) (up) / PixelUnshuffle(2) on bf16 NHWC maps; the backward is the other one."""
+
+    @staticmethod
+    def forward(ctx, x, up):
+        _require_gpu_bf16(x)
+        ctx.up = bool(up)
+        return _shuffle_bf16(_lib.load(), x, ctx.up)
+
+    @staticmethod
+    def backward(ctx, dy):
+        _require_gpu_bf16(dy)
+        return _shuffle_bf16(_lib.load(), dy, not ctx.up), None
+
+
+class _ConcatBf16Fn(torch.autograd.Function):
+    """torch.cat([a, b], 1) on bf16 NHWC maps."""
+
+    @staticmethod
+    def forward(ctx, a, b):
+        lib = _lib.load()
+        _require_gpu_bf16(a, b)
+        a, b = _nhwc(a), _nhwc(b)
+        B, Ca, H, W = a.shape
+        Cb = b.shape[1]
+        out = _empty_nhwc_bf16(B, Ca + Cb, H, W, a.device)
+        check(lib.dcpt_concat_channels_bf16(a.data_ptr(), b.data_ptr(), out.data_ptr(), B * H * W, Ca, Cb, _stream(a.device)),
+              "dcpt_concat_channels_bf16")
+        ctx.dims = (Ca, Cb)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        lib = _lib.load()
+        _require_gpu_bf16(dout)
+        dout = _nhwc(dout)
+        Ca, Cb = ctx.dims
+        B, _, H, W = dout.shape
+        da, db = _empty_nhwc_bf16(B, Ca, H, W, dout.device), _empty_nhwc_bf16(B, Cb, H, W, dout.device)
+        check(lib.dcpt_split_channels_bf16(dout.data_ptr(), da.data_ptr(), db.data_ptr(), B * H * W, Ca, Cb, _stream(dout.device)),
+              "dcpt_split_channels_bf16")
+        return da, db
 
 
 # ------------------------------------------------------------------------------------------------

@@ -463,6 +463,56 @@ int dcpt_gdfn_fwd(const dcpt_gdfn_params* p, const float* x, float* y, const dcp
 int dcpt_gdfn_bwd(const dcpt_gdfn_params* p, const dcpt_gdfn_params_grads* g, const float* x, const dcpt_gdfn_saved* saved,
                   const float* dy, float* dx, void* ws, size_t ws_bytes, int B, int H, int W, int C, int hidden, int flags,
                   dcpt_stream_t stream);
+/* ---- Restormer blocks with bf16 activation storage (restormer_bf16.hip; Restormer / Restormer_origin with act_dtype "bf16") ------
+ * The same two halves as dcpt_mdta_* / dcpt_gdfn_* above (reference restormer_arch.py:75-100, :103-145, :148-159), the same parameter
+ * structs and flags (DCPT_LN_BIASFREE | DCPT_LN_EPS_1E5 | DCPT_ATTN_SOFTMAX; eps 1e-6, or 1e-5 with the flag); x, y, dy, dx and every
+ * [M][.] tensor of the saved structs are bf16 (RNE on store), while mu / rstd, the L2 norms, ghat / attn / attnT, the parameters and
+ * all parameter gradients (temperature included) are fp32 and every sum is accumulated in fp32.  No atomics: results are run-to-run
+ * bit-identical, and identical across the save modes (the LEAN-mode NULLs of the fp32 structs apply field by field).
+ * MDTA: C % heads == 0, ch = C / heads a multiple of 8 and <= 96, C <= 1024.
+ * GDFN: C % 8 == 0, C <= 1024; hidden is padded to hp = a multiple of 8 (u [M][2hp], t [M][hp]; pad columns are zero).
+ * The *_ws_bytes queries return 0 for a shape the entry points reject; their `backward` argument is 0 / 1 (forward / backward), plus 2
+ * when the call will pass every optional saved tensor (MDTA: xn, qkv1, out_att; GDFN: xn, t -- the "full" save mode): the workspace then
+ * holds no copies of them. */
+typedef struct {   /* field order of dcpt_mdta_saved */
+    float* mu; float* rstd;       /* [M] fp32 */
+    uint16_t* qkv1;               /* [M][3C] bf16, may be NULL (lean) */
+    uint16_t* qkv;                /* [M][3C] bf16 */
+    float* nrm;                   /* [B][2C] fp32 */
+    float* ghat; float* attn; float* attnT;   /* [B][heads][ch][ch] fp32 */
+    uint16_t* out_att;            /* [M][C] bf16, may be NULL */
+    uint16_t* xn;                 /* [M][C] bf16, may be NULL */
+} dcpt_mdta_saved_bf16;
+size_t dcpt_mdta_bf16_ws_bytes(int B, int H, int W, int C, int heads, int backward);
+int dcpt_mdta_bf16_fwd(const dcpt_mdta_params* p, const uint16_t* x, uint16_t* y, const dcpt_mdta_saved_bf16* saved, void* ws, size_t ws_bytes,
+                       int B, int H, int W, int C, int heads, int flags, dcpt_stream_t stream);
+int dcpt_mdta_bf16_bwd(const dcpt_mdta_params* p, const dcpt_mdta_params_grads* g, const uint16_t* x, const dcpt_mdta_saved_bf16* saved,
+                       const uint16_t* dy, uint16_t* dx, void* ws, size_t ws_bytes, int B, int H, int W, int C, int heads, int flags,
+                       dcpt_stream_t stream);
+typedef struct {   /* field order of dcpt_gdfn_saved; hp = hidden rounded up to a multiple of 8 */
+    float* mu; float* rstd;   /* [M] fp32 */
+    uint16_t* u;              /* [M][2hp] bf16 */
+    uint16_t* t;              /* [M][hp] bf16, may be NULL */
+    uint16_t* xn;             /* [M][C] bf16, may be NULL */
+} dcpt_gdfn_saved_bf16;
+size_t dcpt_gdfn_bf16_ws_bytes(int B, int H, int W, int C, int hidden, int backward);
+int dcpt_gdfn_bf16_fwd(const dcpt_gdfn_params* p, const uint16_t* x, uint16_t* y, const dcpt_gdfn_saved_bf16* saved, void* ws, size_t ws_bytes,
+                       int B, int H, int W, int C, int hidden, int flags, dcpt_stream_t stream);
+int dcpt_gdfn_bf16_bwd(const dcpt_gdfn_params* p, const dcpt_gdfn_params_grads* g, const uint16_t* x, const dcpt_gdfn_saved_bf16* saved,
+                       const uint16_t* dy, uint16_t* dx, void* ws, size_t ws_bytes, int B, int H, int W, int C, int hidden, int flags,
+                       dcpt_stream_t stream);
+/* the glue between the bf16 blocks (restormer_arch.py:175-202 Down/Upsample, :390-400 skip concat, reduce_chan_level* 1 x 1):
+ * dcpt_pixel_(un)shuffle / dcpt_concat_channels / dcpt_split_channels with bf16 elements (concat / split: Ca, Cb % 8 == 0), and the
+ * bias-free conv of dcpt_conv_fwd / _bwd (ksize 1 or 3, pad 1) with bf16 x / y / dy / dx, fp32 w / dw (Cin, Cout % 8 == 0, <= 1024). */
+int dcpt_pixel_unshuffle_bf16(const uint16_t* x, uint16_t* y, int B, int H, int W, int C, dcpt_stream_t stream);
+int dcpt_pixel_shuffle_bf16(const uint16_t* x, uint16_t* y, int B, int H, int W, int C4, dcpt_stream_t stream);
+int dcpt_concat_channels_bf16(const uint16_t* a, const uint16_t* b, uint16_t* out, int64_t M, int Ca, int Cb, dcpt_stream_t stream);
+int dcpt_split_channels_bf16(const uint16_t* cat, uint16_t* a, uint16_t* b, int64_t M, int Ca, int Cb, dcpt_stream_t stream);
+size_t dcpt_conv_bf16_ws_bytes(int B, int H, int W, int Cin, int Cout, int ksize, int backward);
+int dcpt_conv_fwd_bf16(const uint16_t* x, const float* w, uint16_t* y, void* ws, size_t ws_bytes, int B, int H, int W, int Cin, int Cout,
+                       int ksize, dcpt_stream_t stream);
+int dcpt_conv_bwd_bf16(const uint16_t* dy, const uint16_t* x, const float* w, uint16_t* dx, float* dw, void* ws, size_t ws_bytes, int B, int H,
+                       int W, int Cin, int Cout, int ksize, dcpt_stream_t stream);
 /* ---- SwinIR blocks (basicsr/archs/swinir_arch.py; the variant without relative-position bias and without shift mask) -----------
  * Tokens are NHWC rows x [B][H][W][C] (= the reference's (B, L, C) with L = H*W row-major).  LayerNorm eps 1e-5.
  * Attention half (SwinTransformerBlock :319-372 up to the first residual, WindowAttention :142-195):
