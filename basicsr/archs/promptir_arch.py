@@ -6,6 +6,13 @@ their PromptIR variants (LayerNorm eps 1e-5, softmax attention: ``DCPT_LN_EPS_1E
 ``dcpt_meanpool_fc`` (mean over the pixels + linear) -> ``dcpt_prompt_mix`` (softmax-weighted sum of the prompt components,
 bilinear resize, NHWC) -> a dense 3x3 implicit-GEMM conv; the prompt is concatenated in NHWC, refined by one block
 (``noise_level*``) and reduced by a 1x1 GEMM.  Like the reference, the prompt / channel sizes are hard-wired for ``dim=48``.
+
+``act_dtype="bf16"`` (this repo's extension, default "fp32"), as in restormer_arch.py: every feature map from the patch_embed output
+to the output conv's input is stored in bf16 -- the transformer blocks (``noise_level*`` included) on restormer_bf16.hip, the prompt
+blocks on ``dcpt_meanpool_fc_*_bf16`` -> ``dcpt_prompt_mix_*_bf16`` -> the bf16 3x3 conv.  ``noise_level3`` (704 channels, 4 heads of
+176) runs its per-head attention products on the wide-head kernels of restormer_bf16.hip.  Statistics, attention matrices, the
+prompt logits / weights, parameters, their gradients and the optimizer stay fp32; images go in and come out in fp32, and the
+state_dict is the same.
 """
 from __future__ import annotations
 
@@ -15,7 +22,7 @@ import torch.nn as nn
 from basicsr.utils.registry import ARCH_REGISTRY
 from dcpt_amd import functional as DF
 
-from .restormer_arch import Downsample, OverlapPatchEmbed, Upsample
+from .restormer_arch import Downsample, OverlapPatchEmbed, Upsample, set_act_dtype
 from .restormer_arch import TransformerBlock as _RestormerBlock
 
 
@@ -37,14 +44,15 @@ class PromptGenBlock(nn.Module):
     def forward(self, x):
         _, _, H, W = x.shape
         logits = DF.meanpool_fc(x, self.linear_layer.weight, self.linear_layer.bias)
-        return DF.conv_nobias(DF.prompt_mix(logits, self.prompt_param, H, W), self.conv3x3.weight)
+        prompt = DF.prompt_mix(logits, self.prompt_param, H, W, out_bf16=x.dtype == torch.bfloat16)
+        return DF.conv_nobias(prompt, self.conv3x3.weight)
 
 
 @ARCH_REGISTRY.register()
 class PromptIR(nn.Module):
     def __init__(self, inp_channels=3, out_channels=3, dim=48, num_blocks=[4, 6, 6, 8], num_refinement_blocks=4,
                  heads=[1, 2, 4, 8], ffn_expansion_factor=2.66, bias=False, LayerNorm_type="WithBias", decoder=True,
-                 window_size=8):
+                 window_size=8, act_dtype="fp32"):
         super().__init__()
         if bias:
             raise NotImplementedError("bias=True convs are not on the DCPT path (the reference's option files keep bias=False)")
@@ -81,6 +89,7 @@ class PromptIR(nn.Module):
         self.decoder_level1 = blocks(int(dim * 2 ** 1), heads[0], num_blocks[0])
         self.refinement = blocks(int(dim * 2 ** 1), heads[0], num_refinement_blocks)
         self.output = nn.Conv2d(int(dim * 2 ** 1), out_channels, kernel_size=3, stride=1, padding=1, bias=bias)
+        set_act_dtype(self, act_dtype)
 
     def _prompted(self, x, prompt, noise, reduce):
         x = DF.concat_channels(x, prompt(x))

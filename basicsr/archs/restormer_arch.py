@@ -136,6 +136,17 @@ class SequentialTransformerBlock(nn.Module):
         return self.body(x)
 
 
+def set_act_dtype(net, act_dtype):
+    """``act_dtype`` of a network built from these blocks (Restormer, Restormer_origin, PromptIR)."""
+    if act_dtype not in ("fp32", "bf16"):
+        raise ValueError(f"act_dtype must be 'fp32' or 'bf16', got {act_dtype!r}")
+    net.act_dtype = act_dtype
+    if act_dtype == "bf16":   # the blocks and the first conv switch storage; the glue ops follow the dtype of their input
+        for m in net.modules():
+            if isinstance(m, (TransformerBlock, OverlapPatchEmbed)):
+                m.bf16 = True
+
+
 def _trunc_normal_(t, std=0.02):
     nn.init.trunc_normal_(t, mean=0.0, std=std, a=-2.0, b=2.0)
 
@@ -150,13 +161,7 @@ class _RestormerBase(nn.Module):
         self.save_mode = save_mode
 
     def _set_act_dtype(self, act_dtype):
-        if act_dtype not in ("fp32", "bf16"):
-            raise ValueError(f"act_dtype must be 'fp32' or 'bf16', got {act_dtype!r}")
-        self.act_dtype = act_dtype
-        if act_dtype == "bf16":   # the blocks and the first conv switch storage; the glue ops follow the dtype of their input
-            for m in self.modules():
-                if isinstance(m, (TransformerBlock, OverlapPatchEmbed)):
-                    m.bf16 = True
+        set_act_dtype(self, act_dtype)
 
     def _build(self, inp_channels, out_channels, dim, num_blocks, num_refinement_blocks, heads, ffn_expansion_factor, bias,
                LayerNorm_type, make_level):

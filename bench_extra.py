@@ -2,9 +2,9 @@
 """Secondary workloads of BASELINE.json (configs[2..4]) on ONE MI355X -- evidence for DESIGN.md, not the driver's
 contract (that is bench.py).  Prints one JSON line per workload.
 
-    python bench_extra.py --workload dcpt|restormer|infer2k|naf|swinir|rcan [--dtype fp32|bf16] [--steps K] [--warmup W]
+    python bench_extra.py --workload dcpt|restormer|promptir|infer2k|naf|swinir|rcan [--dtype fp32|bf16] [--steps K] [--warmup W]
 
-``--dtype bf16`` (dcpt, naf, infer2k, restormer): every feature map of the encoder in bf16 storage with fp32 accumulation (act_dtype="bf16";
+``--dtype bf16`` (dcpt, naf, infer2k, restormer, promptir): every feature map of the encoder in bf16 storage with fp32 accumulation (act_dtype="bf16";
 dcpt: the classifier head too unless --head-dtype fp32); images, parameters and the optimizer stay fp32.  Its lines carry BOTH
 rooflines: the bf16 MFMA peak (2.5 PF dense) and the HBM roof with the bf16 algorithmic bytes -- in bf16 the network is HBM-bound
 (SURVEY 8d).
@@ -88,6 +88,35 @@ def run_restormer(dev, save="balanced", steps=5, warmup=2, B=64, S=128, rank=0, 
                          "(BASELINE.json configs[3])",
                 ms_per_step=round(dt * 1e3, 2), megapixels_per_s=round(world * B * S * S / 1e6 / dt, 3), steps=steps, warmup=warmup,
                 alg_tflops=round(flops / dt / 1e12, 2), mfma_frac=round(flops / dt / peak, 4),
+                peak_mem_gb=round(torch.cuda.max_memory_allocated() / 2 ** 30, 2))
+
+
+def run_promptir(dev, save="balanced", steps=5, warmup=2, B=32, S=128, dtype="fp32"):
+    """PromptIR defaults (dim 48, [4,6,6,8], 4 refinement blocks, WithBias LN, the 3 prompt blocks; the network behind
+    options/all_in_one/test/test_PromptIR_5d.yml), fwd + L1 + bwd + FusedAdamW; dtype "bf16": act_dtype="bf16".  B = 32 at 128 x 128 by
+    default: the fp32 step fits the device with room to spare."""
+    from basicsr.archs import build_network
+    from dcpt_amd import functional as DF
+    from dcpt_amd.keyed_init import fill_module_
+    from dcpt_amd.optim import FusedAdamW
+
+    g = torch.Generator(device=dev).manual_seed(1234)
+    torch.cuda.reset_peak_memory_stats()
+    DF.set_restormer_save(save)
+    net = fill_module_(build_network(dict(type="PromptIR", act_dtype=dtype))).to(dev)
+    optm = FusedAdamW(net.parameters(), lr=1e-4)
+    lq = torch.rand((B, 3, S, S), generator=g, device=dev)
+    gt = torch.rand((B, 3, S, S), generator=g, device=dev)
+
+    def step():
+        optm.zero_grad(set_to_none=True)
+        (net(lq) - gt).abs().mean().backward()
+        optm.step()
+
+    dt = timed(step, steps, warmup)
+    return dict(workload=f"PromptIR (dim 48, [4,6,6,8], 4 refinement blocks, WithBias LN, 3 prompt blocks) fwd+L1+bwd+AdamW, B={B}, "
+                         f"{S}x{S}, {dtype}, saved tensors: {save}",
+                ms_per_step=round(dt * 1e3, 2), megapixels_per_s=round(B * S * S / 1e6 / dt, 3), steps=steps, warmup=warmup, batch=B,
                 peak_mem_gb=round(torch.cuda.max_memory_allocated() / 2 ** 30, 2))
 
 
@@ -240,7 +269,7 @@ def run_infer2k(dev, dtype="fp32", steps=5, warmup=2, S=2048, streams=2):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", required=True, choices=["dcpt", "restormer", "infer2k", "naf", "swinir", "rcan"])
+    ap.add_argument("--workload", required=True, choices=["dcpt", "restormer", "promptir", "infer2k", "naf", "swinir", "rcan"])
     ap.add_argument("--dtype", default="fp32", choices=["fp32", "bf16", "bf16_tail32", "bf16_edge32"])
     ap.add_argument("--head-dtype", default=None, choices=["fp32", "bf16"], help="dcpt: classifier-head activations (default: --dtype)")
     ap.add_argument("--restormer-save", default="balanced", choices=["auto", "lean", "balanced", "full"], help="what the Restormer halves keep for backward")
@@ -368,6 +397,10 @@ def main():
             raise SystemExit("--workload restormer: --dtype fp32 or bf16")
         res = run_restormer(dev, args.restormer_save, args.steps, args.warmup, args.batch or 64, args.size or 128, rank=rank, world=world,
                             dtype=args.dtype)
+    elif args.workload == "promptir":
+        if args.dtype not in ("fp32", "bf16"):
+            raise SystemExit("--workload promptir: --dtype fp32 or bf16")
+        res = run_promptir(dev, args.restormer_save, args.steps, args.warmup, args.batch or 32, args.size or 128, dtype=args.dtype)
     elif args.workload == "swinir":
         res = run_swinir(dev, args.steps, args.warmup, args.batch or 8, args.size or 256)
     elif args.workload == "rcan":

@@ -3,7 +3,10 @@
 // The mean over the pixels + linear layer in front of it is dcpt_meanpool_fc_*, the conv behind it dcpt_conv_* (dense 3x3).
 // Bilinear = F.interpolate(mode="bilinear", align_corners=False): src = (dst + 0.5) * S / H - 0.5 clamped at 0, neighbours
 // x0 = floor(src), x1 = min(x0 + 1, S - 1), weights (1 - l, l).
-#include "dcpt_common.h"
+// The _bf16 entry points write (forward) / read (backward) the NHWC map in bf16 (rounded once, on store); the logits, the softmax
+// weights, the parameter, its gradient and dlogits stay fp32, and the kernels are the fp32 ones with the map's element type swapped.
+#include "bf16.h"
+#include "prof.h"
 #include "../../include/dcpt_hip.h"
 
 namespace {
@@ -39,9 +42,16 @@ __global__ void prompt_softmax_kernel(const float* __restrict__ logits, float* _
     for (int l = 0; l < L; ++l) w[b * L + l] = e[l] / s;
 }
 
+// NHWC map element: fp32 or bf16 (4 channels = one 16- / 8-byte store, one rounding per element)
+__device__ __forceinline__ void store4(float* p, float4 v) { stg4(p, v); }
+__device__ __forceinline__ void store4(bf16_t* p, float4 v) { *reinterpret_cast<u32x2*>(p) = bf4_pack(v); }
+__device__ __forceinline__ float load1(const float* p) { return *p; }
+__device__ __forceinline__ float load1(const bf16_t* p) { return bf_lo((uint32_t)*p); }
+
 // thread = (b, y, x, 4 channels)
+template <typename T>
 __global__ __launch_bounds__(256) void prompt_mix_fwd_kernel(const float* __restrict__ w, const float* __restrict__ param,
-                                                             float* __restrict__ out, int B, int L, int D, int S, int H, int W) {
+                                                             T* __restrict__ out, int B, int L, int D, int S, int H, int W) {
     const int nq = D / 4;
     const int64_t total = (int64_t)B * H * W * nq;
     const float sy = (float)S / (float)H, sx = (float)S / (float)W;
@@ -67,12 +77,13 @@ __global__ __launch_bounds__(256) void prompt_mix_fwd_kernel(const float* __rest
             }
             o[j] = ry.l0 * (rx.l0 * p00 + rx.l1 * p01) + ry.l1 * (rx.l0 * p10 + rx.l1 * p11);
         }
-        stg4(out + pix * D + 4 * q, make_float4(o[0], o[1], o[2], o[3]));
+        store4(out + pix * D + 4 * q, make_float4(o[0], o[1], o[2], o[3]));
     }
 }
 
 // dP[b][sy][sx][d] = sum over the output pixels whose bilinear footprint contains (sy, sx); gather, fixed order
-__global__ __launch_bounds__(256) void prompt_mix_bwd_dp_kernel(const float* __restrict__ dout, float* __restrict__ dP, int B, int D, int S,
+template <typename T>
+__global__ __launch_bounds__(256) void prompt_mix_bwd_dp_kernel(const T* __restrict__ dout, float* __restrict__ dP, int B, int D, int S,
                                                                 int H, int W) {
     const int64_t total = (int64_t)B * S * S * D;
     const float scy = (float)S / (float)H, scx = (float)S / (float)W;
@@ -101,7 +112,7 @@ __global__ __launch_bounds__(256) void prompt_mix_bwd_dp_kernel(const float* __r
                 if (rx.i0 == sx) cx += rx.l0;
                 if (rx.i1 == sx) cx += rx.l1;
                 if (cx == 0.f) continue;
-                acc = fmaf(cy * cx, dout[(((int64_t)b * H + y) * W + x) * D + d], acc);
+                acc = fmaf(cy * cx, load1(dout + (((int64_t)b * H + y) * W + x) * D + d), acc);
             }
         }
         dP[i] = acc;
@@ -166,34 +177,66 @@ inline unsigned grid_for(int64_t n) {
 
 extern "C" size_t dcpt_prompt_mix_bwd_ws_bytes(int B, int D, int S) { return align_up((size_t)B * D * S * S * sizeof(float), 256); }
 
-extern "C" int dcpt_prompt_mix_fwd(const float* logits, const float* param, float* weights, float* out, int B, int L, int D, int S, int H,
-                                   int W, dcpt_stream_t stream) {
-    hipStream_t s = (hipStream_t)stream;
-    DCPT_CHECK_ARG(logits && param && weights && out, "prompt_mix_fwd: null argument");
-    DCPT_CHECK_ARG(B > 0 && L >= 1 && L <= MAXL && D > 0 && D % 4 == 0 && S > 0 && H > 0 && W > 0,
-                   "prompt_mix_fwd: bad shape (prompt_len <= %d, prompt_dim %% 4 == 0)", MAXL);
+namespace {
+
+template <typename T>
+int prompt_mix_fwd(const float* logits, const float* param, float* weights, T* out, int B, int L, int D, int S, int H, int W, hipStream_t s) {
     prompt_softmax_kernel<<<dim3(cdiv(B, 64)), dim3(64), 0, s>>>(logits, weights, B, L);
     DCPT_CHECK_LAUNCH("prompt_softmax");
-    prompt_mix_fwd_kernel<<<dim3(grid_for((int64_t)B * H * W * (D / 4))), dim3(256), 0, s>>>(weights, param, out, B, L, D, S, H, W);
+    prompt_mix_fwd_kernel<T><<<dim3(grid_for((int64_t)B * H * W * (D / 4))), dim3(256), 0, s>>>(weights, param, out, B, L, D, S, H, W);
     DCPT_CHECK_LAUNCH("prompt_mix_fwd");
     return DCPT_OK;
 }
 
-extern "C" int dcpt_prompt_mix_bwd(const float* dout, const float* param, const float* weights, float* dlogits, float* dparam, void* ws,
-                                   size_t ws_bytes, int B, int L, int D, int S, int H, int W, dcpt_stream_t stream) {
-    hipStream_t s = (hipStream_t)stream;
-    DCPT_CHECK_ARG(dout && param && weights && dlogits && dparam, "prompt_mix_bwd: null argument");
-    DCPT_CHECK_ARG(B > 0 && L >= 1 && L <= MAXL && D > 0 && D % 4 == 0 && S > 0 && H > 0 && W > 0, "prompt_mix_bwd: bad shape");
+template <typename T>
+int prompt_mix_bwd(const T* dout, const float* param, const float* weights, float* dlogits, float* dparam, void* ws, size_t ws_bytes, int B,
+                   int L, int D, int S, int H, int W, const char* name, hipStream_t s) {
     if (ws == nullptr || ws_bytes < dcpt_prompt_mix_bwd_ws_bytes(B, D, S)) {
-        dcpt_set_error("prompt_mix_bwd: workspace too small");
+        dcpt_set_error("%s: workspace too small", name);
         return DCPT_ERR_WS;
     }
     float* dP = (float*)ws;
-    prompt_mix_bwd_dp_kernel<<<dim3(grid_for((int64_t)B * S * S * D)), dim3(256), 0, s>>>(dout, dP, B, D, S, H, W);
+    prompt_mix_bwd_dp_kernel<T><<<dim3(grid_for((int64_t)B * S * S * D)), dim3(256), 0, s>>>(dout, dP, B, D, S, H, W);
     DCPT_CHECK_LAUNCH("prompt_mix_bwd_dp");
     prompt_mix_bwd_param_kernel<<<dim3(grid_for((int64_t)L * D * S * S)), dim3(256), 0, s>>>(dP, weights, dparam, B, L, D, S);
     DCPT_CHECK_LAUNCH("prompt_mix_bwd_param");
     prompt_mix_bwd_logits_kernel<<<dim3(B), dim3(256), 0, s>>>(dP, param, weights, dlogits, L, D, S);
     DCPT_CHECK_LAUNCH("prompt_mix_bwd_logits");
     return DCPT_OK;
+}
+
+}  // namespace
+
+extern "C" int dcpt_prompt_mix_fwd(const float* logits, const float* param, float* weights, float* out, int B, int L, int D, int S, int H,
+                                   int W, dcpt_stream_t stream) {
+    DCPT_CHECK_ARG(logits && param && weights && out, "prompt_mix_fwd: null argument");
+    DCPT_CHECK_ARG(B > 0 && L >= 1 && L <= MAXL && D > 0 && D % 4 == 0 && S > 0 && H > 0 && W > 0,
+                   "prompt_mix_fwd: bad shape (prompt_len <= %d, prompt_dim %% 4 == 0)", MAXL);
+    return prompt_mix_fwd(logits, param, weights, out, B, L, D, S, H, W, (hipStream_t)stream);
+}
+
+extern "C" int dcpt_prompt_mix_bwd(const float* dout, const float* param, const float* weights, float* dlogits, float* dparam, void* ws,
+                                   size_t ws_bytes, int B, int L, int D, int S, int H, int W, dcpt_stream_t stream) {
+    DCPT_CHECK_ARG(dout && param && weights && dlogits && dparam, "prompt_mix_bwd: null argument");
+    DCPT_CHECK_ARG(B > 0 && L >= 1 && L <= MAXL && D > 0 && D % 4 == 0 && S > 0 && H > 0 && W > 0, "prompt_mix_bwd: bad shape");
+    return prompt_mix_bwd(dout, param, weights, dlogits, dparam, ws, ws_bytes, B, L, D, S, H, W, "prompt_mix_bwd", (hipStream_t)stream);
+}
+
+extern "C" int dcpt_prompt_mix_fwd_bf16(const float* logits, const float* param, float* weights, uint16_t* out, int B, int L, int D, int S,
+                                        int H, int W, dcpt_stream_t stream) {
+    DCPT_CHECK_ARG(logits && param && weights && out, "prompt_mix_fwd_bf16: null argument");
+    DCPT_CHECK_ARG(B > 0 && L >= 1 && L <= MAXL && D > 0 && D % 8 == 0 && S > 0 && H > 0 && W > 0,
+                   "prompt_mix_fwd_bf16: bad shape (prompt_len <= %d, prompt_dim %% 8 == 0)", MAXL);
+    trace_tag("prompt_bf16.mix");
+    return prompt_mix_fwd(logits, param, weights, reinterpret_cast<bf16_t*>(out), B, L, D, S, H, W, (hipStream_t)stream);
+}
+
+extern "C" int dcpt_prompt_mix_bwd_bf16(const uint16_t* dout, const float* param, const float* weights, float* dlogits, float* dparam,
+                                        void* ws, size_t ws_bytes, int B, int L, int D, int S, int H, int W, dcpt_stream_t stream) {
+    DCPT_CHECK_ARG(dout && param && weights && dlogits && dparam, "prompt_mix_bwd_bf16: null argument");
+    DCPT_CHECK_ARG(B > 0 && L >= 1 && L <= MAXL && D > 0 && D % 8 == 0 && S > 0 && H > 0 && W > 0,
+                   "prompt_mix_bwd_bf16: bad shape (prompt_len <= %d, prompt_dim %% 8 == 0)", MAXL);
+    trace_tag("prompt_bf16.mix");
+    return prompt_mix_bwd(reinterpret_cast<const bf16_t*>(dout), param, weights, dlogits, dparam, ws, ws_bytes, B, L, D, S, H, W,
+                          "prompt_mix_bwd_bf16", (hipStream_t)stream);
 }

@@ -11,6 +11,7 @@
 // with ch = C / heads (48 in the default net) -- too narrow for the GEMM tiles -- and have two kernels of their own here:
 //   gram   G[i][j]  = sum_p X[p][i] Y[p][j]             over fixed 256-pixel splits (fp32 slabs, reduced in order by the finalize)
 //   apply  O[p][i]  = sum_j A[i][j] V[p][j] (+ cs_i R[p][i])   A in LDS (fp32), a 32-pixel tile of V next to it
+// for heads of up to 96 channels; wider heads (up to 256: PromptIR's noise_level3 has 176) run tiled forms of the two (*_wide_bf16_kernel).
 // The attention finalize / backward (ReLU or softmax, temperature, norms) are the fp32 kernels of restormer.hip.  Nothing is
 // accumulated with atomics, and no split depends on the batch size: a sample's output does not depend on its batch.
 #include "bf16.h"
@@ -330,7 +331,7 @@ __global__ __launch_bounds__(256) void dw_plain_bwd_w_kernel(const bf16_t* __res
 // ---- per-(image, head) products -------------------------------------------------------------------------------------------
 constexpr int GRAM_ROWS = 256;   // pixels per split (fixed: the splits of an image do not depend on the batch)
 constexpr int GRAM_TILE = 32;
-constexpr int CH_MAX = 96;       // channels per head of the bf16 blocks (LDS of the apply kernel)
+constexpr int CH_MAX = 96;       // channels per head of these two kernels (LDS of the apply kernel); wider heads: *_wide_bf16_kernel
 
 // slab[z][split][i][j] = sum_{p in split} X[b][p][xo + h ch + i] * Y[b][p][yo + h ch + j],  z = b heads + h, grid (splits, B heads)
 template <int MAXU>
@@ -383,7 +384,82 @@ __global__ __launch_bounds__(256) void gram_bf16_kernel(const bf16_t* __restrict
 
 int gram_splits(int P) { return cdiv(P, GRAM_ROWS); }
 
+// ---- wide heads: CH_MAX < ch <= CH_WIDE (PromptIR's 704-channel noise_level3 block: 4 heads of 176) -----------------------
+// The narrow kernels keep a whole ch x ch product per block (accumulators / LDS); these tile it instead.  Every output element is
+// the same fp32 fmaf chain as in the narrow kernels (pixels resp. j in increasing order), so the numerics are those of the narrow path.
+constexpr int CH_WIDE = 256;     // the fp32 softmax attention kernels' limit (restormer.hip SM_MAXU)
+constexpr int WG_T = 64;         // gram: a 64 x 64 tile of G per block, 4 x 4 entries per thread (rows ty + 16 a, columns tx + 16 c)
+
+// grid (splits, B heads, ceil(ch / 64)^2); slab layout as gram_bf16_kernel
+__global__ __launch_bounds__(256) void gram_wide_bf16_kernel(const bf16_t* __restrict__ X, int ldx, const bf16_t* __restrict__ Y, int ldy,
+                                                             float* __restrict__ slab, int P, int heads, int ch) {
+    __shared__ float xs[GRAM_TILE][WG_T];
+    __shared__ float ys[GRAM_TILE][WG_T];
+    const int z = blockIdx.y, b = z / heads, h = z % heads, split = blockIdx.x, splits = gridDim.x;
+    const int nt = (ch + WG_T - 1) / WG_T;
+    const int i0 = (int)(blockIdx.z / nt) * WG_T, j0 = (int)(blockIdx.z % nt) * WG_T;
+    const int p0 = split * GRAM_ROWS, p1 = p0 + GRAM_ROWS < P ? p0 + GRAM_ROWS : P;
+    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+    float acc[4][4];
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) acc[a][c] = 0.f;
+    const bf16_t* xb = X + (int64_t)b * P * ldx + h * ch + i0;
+    const bf16_t* yb = Y + (int64_t)b * P * ldy + h * ch + j0;
+    for (int pt = p0; pt < p1; pt += GRAM_TILE) {
+        // 2 maps x 32 pixels x 8 groups of 8 channels = 512 16-byte pieces, two per thread; outside the split / the head: zeros
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const int idx = threadIdx.x + 256 * k;
+            const int which = idx >> 8, r = (idx >> 3) & 31, c = (idx & 7) * 8, p = pt + r;
+            float* d = which ? &ys[r][c] : &xs[r][c];
+            if (p < p1 && (which ? j0 : i0) + c < ch) {
+                const u32x4 v = which ? *reinterpret_cast<const u32x4*>(yb + (int64_t)p * ldy + c) : *reinterpret_cast<const u32x4*>(xb + (int64_t)p * ldx + c);
+                d[0] = bf_lo(v.x); d[1] = bf_hi(v.x); d[2] = bf_lo(v.y); d[3] = bf_hi(v.y);
+                d[4] = bf_lo(v.z); d[5] = bf_hi(v.z); d[6] = bf_lo(v.w); d[7] = bf_hi(v.w);
+            } else {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) d[e] = 0.f;
+            }
+        }
+        __syncthreads();
+#pragma unroll 4
+        for (int r = 0; r < GRAM_TILE; ++r) {
+            float xv[4], yv[4];
+#pragma unroll
+            for (int a = 0; a < 4; ++a) {
+                xv[a] = xs[r][ty + 16 * a];
+                yv[a] = ys[r][tx + 16 * a];
+            }
+#pragma unroll
+            for (int a = 0; a < 4; ++a)
+#pragma unroll
+                for (int c = 0; c < 4; ++c) acc[a][c] = fmaf(xv[a], yv[c], acc[a][c]);
+        }
+        __syncthreads();
+    }
+    float* out = slab + ((int64_t)z * splits + split) * ch * ch;
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+        const int i = i0 + ty + 16 * a;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const int j = j0 + tx + 16 * c;
+            if (i < ch && j < ch) out[(int64_t)i * ch + j] = acc[a][c];
+        }
+    }
+}
+
 int launch_gram(const bf16_t* X, int ldx, const bf16_t* Y, int ldy, float* slab, int B, int P, int heads, int ch, hipStream_t s) {
+    if (ch > CH_MAX) {
+        trace_tag("rst_bf16.gram_wide");
+        const int nt = cdiv(ch, WG_T);
+        gram_wide_bf16_kernel<<<dim3((unsigned)gram_splits(P), (unsigned)(B * heads), (unsigned)(nt * nt)), dim3(256), 0, s>>>(X, ldx, Y, ldy,
+                                                                                                                                slab, P, heads, ch);
+        DCPT_CHECK_LAUNCH("rst_bf16_gram_wide");
+        return DCPT_OK;
+    }
     trace_tag("rst_bf16.gram");
     const dim3 grid((unsigned)gram_splits(P), (unsigned)(B * heads)), blk(256);
     const int need = cdiv(ch * ch, 256);
@@ -454,8 +530,74 @@ __global__ __launch_bounds__(256) void apply_bf16_kernel(const float* __restrict
     }
 }
 
+// wide heads: apply_bf16_kernel tiled over the output channels.  grid (P / 64, B heads, ch / 32); dynamic LDS: the fp32 A^T tile
+// [ch][32] (A is never rounded) + the 64-pixel V tile [64][ch] kept in bf16 (widened on read, exact) = 256 ch bytes, 64 KiB at ch = 256:
+// two blocks per CU.  A thread computes 8 consecutive i of one pixel (4 threads per pixel) and stores 16 bytes, like the narrow kernel.
+constexpr int WA_IT = 32;   // output channels per block
+constexpr int WA_PT = 64;   // pixels per block
+__global__ __launch_bounds__(256) void apply_wide_bf16_kernel(const float* __restrict__ A, const bf16_t* __restrict__ V, int ldv,
+                                                              const bf16_t* __restrict__ R, int ldr, const float* __restrict__ cs, int csb,
+                                                              bf16_t* __restrict__ O, int ldo, int P, int heads, int ch) {
+    extern __shared__ float sm[];
+    float* at = sm;                                              // at[j * 32 + ii] = A[i0 + ii][j]
+    bf16_t* vs = reinterpret_cast<bf16_t*>(sm + ch * WA_IT);    // vs[r * ch + j]
+    const int z = blockIdx.y, b = z / heads, h = z % heads;
+    const int p0 = blockIdx.x * WA_PT, i0 = blockIdx.z * WA_IT;
+    const int g8 = ch / 8;
+    const float* Az = A + (int64_t)z * ch * ch;
+    for (int e = threadIdx.x; e < WA_IT * ch; e += 256) {
+        const int j = e / WA_IT, ii = e % WA_IT, i = i0 + ii;
+        at[e] = i < ch ? Az[(int64_t)i * ch + j] : 0.f;
+    }
+    const bf16_t* vb = V + (int64_t)b * P * ldv + h * ch;
+    for (int idx = threadIdx.x; idx < WA_PT * g8; idx += 256) {
+        const int r = idx / g8, c = (idx % g8) * 8, p = p0 + r;
+        u32x4 v = {0u, 0u, 0u, 0u};
+        if (p < P) v = *reinterpret_cast<const u32x4*>(vb + (int64_t)p * ldv + c);
+        *reinterpret_cast<u32x4*>(vs + r * ch + c) = v;
+    }
+    __syncthreads();
+    const int r = threadIdx.x >> 2, ii0 = (threadIdx.x & 3) * 8, p = p0 + r, i = i0 + ii0;
+    if (p >= P || i >= ch) return;
+    float acc[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[e] = 0.f;
+    const uint32_t* vr = reinterpret_cast<const uint32_t*>(vs + r * ch);
+    for (int j2 = 0; j2 < ch / 2; ++j2) {
+        const uint32_t vv = vr[j2];
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            const float v = t ? bf_hi(vv) : bf_lo(vv);
+            const float* arow = at + (2 * j2 + t) * WA_IT + ii0;
+            const float4 a0 = *reinterpret_cast<const float4*>(arow);
+            const float4 a1 = *reinterpret_cast<const float4*>(arow + 4);
+            acc[0] = fmaf(a0.x, v, acc[0]); acc[1] = fmaf(a0.y, v, acc[1]); acc[2] = fmaf(a0.z, v, acc[2]); acc[3] = fmaf(a0.w, v, acc[3]);
+            acc[4] = fmaf(a1.x, v, acc[4]); acc[5] = fmaf(a1.y, v, acc[5]); acc[6] = fmaf(a1.z, v, acc[6]); acc[7] = fmaf(a1.w, v, acc[7]);
+        }
+    }
+    const int64_t row = (int64_t)b * P + p;
+    if (R) {
+        const u32x4 rv = *reinterpret_cast<const u32x4*>(R + row * ldr + h * ch + i);
+        const float rr[8] = {bf_lo(rv.x), bf_hi(rv.x), bf_lo(rv.y), bf_hi(rv.y), bf_lo(rv.z), bf_hi(rv.z), bf_lo(rv.w), bf_hi(rv.w)};
+        const float* c = cs + (int64_t)b * csb + h * ch + i;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc[e] = fmaf(c[e], rr[e], acc[e]);
+    }
+    u32x4 wv;
+    wv.x = bf_pack(acc[0], acc[1]); wv.y = bf_pack(acc[2], acc[3]); wv.z = bf_pack(acc[4], acc[5]); wv.w = bf_pack(acc[6], acc[7]);
+    *reinterpret_cast<u32x4*>(O + row * ldo + h * ch + i) = wv;
+}
+
 int launch_apply(const float* A, const bf16_t* V, int ldv, const bf16_t* R, int ldr, const float* cs, int csb, bf16_t* O, int ldo, int B, int P,
                  int heads, int ch, hipStream_t s) {
+    if (ch > CH_MAX) {
+        trace_tag("rst_bf16.apply_wide");
+        const size_t lds = (size_t)ch * WA_IT * sizeof(float) + (size_t)WA_PT * ch * sizeof(bf16_t);
+        apply_wide_bf16_kernel<<<dim3((unsigned)cdiv(P, WA_PT), (unsigned)(B * heads), (unsigned)cdiv(ch, WA_IT)), dim3(256), lds, s>>>(
+            A, V, ldv, R, ldr, cs, csb, O, ldo, P, heads, ch);
+        DCPT_CHECK_LAUNCH("rst_bf16_apply_wide");
+        return DCPT_OK;
+    }
     trace_tag("rst_bf16.apply");
     const size_t lds = (size_t)(ch * ch + GRAM_TILE * ch) * sizeof(float);
     apply_bf16_kernel<<<dim3((unsigned)cdiv(P, GRAM_TILE), (unsigned)(B * heads)), dim3(256), lds, s>>>(A, V, ldv, R, ldr, cs, csb, O, ldo, P, heads, ch);
@@ -511,7 +653,7 @@ struct MdtaWsB {
 };
 
 bool mdta_shape_ok(int B, int H, int W, int C, int heads) {
-    return B > 0 && H > 0 && W > 0 && heads > 0 && C % heads == 0 && (C / heads) % 8 == 0 && C / heads <= CH_MAX && C <= 1024;
+    return B > 0 && H > 0 && W > 0 && heads > 0 && C % heads == 0 && (C / heads) % 8 == 0 && C / heads <= CH_WIDE && C <= 1024;
 }
 
 // kept: the caller supplies xn, qkv1 and out_att (full save mode), so their workspace copies are not reserved
@@ -618,7 +760,7 @@ extern "C" int dcpt_mdta_bf16_fwd(const dcpt_mdta_params* p, const uint16_t* x, 
                        sv->nrm && sv->ghat && sv->attn && sv->attnT,
                    "mdta_bf16_fwd: null argument");
     DCPT_CHECK_ARG(mdta_shape_ok(B, H, W, C, heads),
-                   "mdta_bf16_fwd: C=%d heads=%d (C %% heads == 0, C / heads a multiple of 8 and <= %d)", C, heads, CH_MAX);
+                   "mdta_bf16_fwd: C=%d heads=%d (C %% heads == 0, C / heads a multiple of 8 and <= %d, C <= 1024)", C, heads, CH_WIDE);
     const bool biasfree = flags & DCPT_LN_BIASFREE;
     DCPT_CHECK_ARG(biasfree || p->norm_b, "mdta_bf16_fwd: WithBias LayerNorm needs norm_b");
     const float ln_eps = (flags & DCPT_LN_EPS_1E5) ? 1e-5f : 1e-6f;
@@ -660,7 +802,7 @@ extern "C" int dcpt_mdta_bf16_bwd(const dcpt_mdta_params* p, const dcpt_mdta_par
                        gr->temperature,
                    "mdta_bf16_bwd: null argument");
     DCPT_CHECK_ARG(mdta_shape_ok(B, H, W, C, heads),
-                   "mdta_bf16_bwd: C=%d heads=%d (C %% heads == 0, C / heads a multiple of 8 and <= %d)", C, heads, CH_MAX);
+                   "mdta_bf16_bwd: C=%d heads=%d (C %% heads == 0, C / heads a multiple of 8 and <= %d, C <= 1024)", C, heads, CH_WIDE);
     const bool biasfree = flags & DCPT_LN_BIASFREE;
     DCPT_CHECK_ARG(biasfree || (p->norm_b && gr->norm_b), "mdta_bf16_bwd: WithBias LayerNorm needs norm_b and its gradient");
     const float ln_eps = (flags & DCPT_LN_EPS_1E5) ? 1e-5f : 1e-6f;

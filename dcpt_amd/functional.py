@@ -2315,7 +2315,48 @@ class _PromptMixFn(torch.autograd.Function):
         return dlogits, dparam, None, None
 
 
-def prompt_mix(logits, prompt_param, H, W):
+class _PromptMixBf16Fn(torch.autograd.Function):
+    """_PromptMixFn with the NHWC map in bf16 storage (dcpt_prompt_mix_fwd_bf16 / _bwd_bf16); logits, softmax weights, prompt_param and
+    their gradients fp32."""
+
+    @staticmethod
+    def forward(ctx, logits, prompt_param, H, W):
+        lib = _lib.load()
+        _require_gpu(logits, prompt_param)
+        lg, pp = _contig(logits.detach()), _contig(prompt_param.detach())
+        B, L = lg.shape
+        _, L2, D, S, S2 = pp.shape
+        if L2 != L or S2 != S:
+            raise ValueError(f"prompt_param {tuple(pp.shape)} does not match logits {tuple(lg.shape)}")
+        dev = lg.device
+        wsm = torch.empty((B, L), dtype=torch.float32, device=dev)
+        out = _empty_nhwc_bf16(B, D, H, W, dev)
+        check(lib.dcpt_prompt_mix_fwd_bf16(lg.data_ptr(), pp.data_ptr(), wsm.data_ptr(), out.data_ptr(), B, L, D, S, H, W, _stream(dev)),
+              "dcpt_prompt_mix_fwd_bf16")
+        ctx.save_for_backward(pp, wsm)
+        ctx.geom = (B, L, D, S, H, W)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        lib = _lib.load()
+        pp, wsm = ctx.saved_tensors
+        B, L, D, S, H, W = ctx.geom
+        _require_gpu_bf16(dout)
+        dout = _nhwc(dout)
+        dev = dout.device
+        dlogits = torch.empty((B, L), dtype=torch.float32, device=dev)
+        dparam = torch.empty_like(pp)
+        ws = _workspace(dev, lib.dcpt_prompt_mix_bwd_ws_bytes(B, D, S))
+        check(lib.dcpt_prompt_mix_bwd_bf16(dout.data_ptr(), pp.data_ptr(), wsm.data_ptr(), dlogits.data_ptr(), dparam.data_ptr(),
+                                           ws.data_ptr(), ws.numel(), B, L, D, S, H, W, _stream(dev)), "dcpt_prompt_mix_bwd_bf16")
+        return dlogits, dparam, None, None
+
+
+def prompt_mix(logits, prompt_param, H, W, out_bf16=False):
+    """``out_bf16``: the map in bf16 storage (PromptIR with act_dtype="bf16"), otherwise fp32."""
+    if out_bf16:
+        return _PromptMixBf16Fn.apply(logits, prompt_param, H, W)
     return _PromptMixFn.apply(logits, prompt_param, H, W)
 
 

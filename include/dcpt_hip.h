@@ -469,7 +469,8 @@ int dcpt_gdfn_bwd(const dcpt_gdfn_params* p, const dcpt_gdfn_params_grads* g, co
  * [M][.] tensor of the saved structs are bf16 (RNE on store), while mu / rstd, the L2 norms, ghat / attn / attnT, the parameters and
  * all parameter gradients (temperature included) are fp32 and every sum is accumulated in fp32.  No atomics: results are run-to-run
  * bit-identical, and identical across the save modes (the LEAN-mode NULLs of the fp32 structs apply field by field).
- * MDTA: C % heads == 0, ch = C / heads a multiple of 8 and <= 96, C <= 1024.
+ * MDTA: C % heads == 0, ch = C / heads a multiple of 8 and <= 256, C <= 1024 (heads wider than 96 channels run on kernels of their
+ *       own, tiled over the head's channels; up to 96 the results are those of ABI 15 as first released).
  * GDFN: C % 8 == 0, C <= 1024; hidden is padded to hp = a multiple of 8 (u [M][2hp], t [M][hp]; pad columns are zero).
  * The *_ws_bytes queries return 0 for a shape the entry points reject; their `backward` argument is 0 / 1 (forward / backward), plus 2
  * when the call will pass every optional saved tensor (MDTA: xn, qkv1, out_att; GDFN: xn, t -- the "full" save mode): the workspace then
@@ -605,6 +606,12 @@ int dcpt_prompt_mix_fwd(const float* logits, const float* param, float* weights,
 size_t dcpt_prompt_mix_bwd_ws_bytes(int B, int D, int S);
 int dcpt_prompt_mix_bwd(const float* dout, const float* param, const float* weights, float* dlogits, float* dparam, void* ws,
                         size_t ws_bytes, int B, int L, int D, int S, int H, int W, dcpt_stream_t stream);
+/* The same with the NHWC map in bf16 (PromptIR with act_dtype="bf16"): out / dout [B][H][W][D] bf16, D % 8 == 0; logits, weights,
+ * param, dlogits, dparam fp32; workspace dcpt_prompt_mix_bwd_ws_bytes. */
+int dcpt_prompt_mix_fwd_bf16(const float* logits, const float* param, float* weights, uint16_t* out, int B, int L, int D, int S, int H, int W,
+                             dcpt_stream_t stream);
+int dcpt_prompt_mix_bwd_bf16(const uint16_t* dout, const float* param, const float* weights, float* dlogits, float* dparam, void* ws,
+                             size_t ws_bytes, int B, int L, int D, int S, int H, int W, dcpt_stream_t stream);
 /* NHWC PixelUnshuffle(2): x [B][H][W][C] -> y [B][H/2][W/2][4C];  PixelShuffle(2): x [B][H][W][C4] -> y [B][2H][2W][C4/4] */
 int dcpt_pixel_unshuffle(const float* x, float* y, int B, int H, int W, int C, dcpt_stream_t stream);
 int dcpt_pixel_shuffle(const float* x, float* y, int B, int H, int W, int C4, dcpt_stream_t stream);
