@@ -173,12 +173,16 @@ class gemm_precision:
         return False
 
 
-def _remember_gemm_mode(cls):
-    """forward notes the active mode on the node, backward re-activates it (a no-op comparison when nothing changed)"""
+def _remember_gemm_mode(cls, fp32_only=False):
+    """forward notes the active mode on the node, backward re-activates it (a no-op comparison when nothing changed).  ``fp32_only``: a
+    node whose feature map (its first argument) is in bf16 storage notes nothing, so its backward never switches the mode (a switch also
+    turns the side stream off): the mode is an fp32-storage matter, and the bf16-storage forms of these ops have
+    always run their backward under whatever was active."""
     fwd, bwd = cls.forward, cls.backward
 
     def forward(ctx, *args):
-        ctx._gemm_mode = _GEMM_ACTIVE
+        if not (fp32_only and args[0].dtype == torch.bfloat16):
+            ctx._gemm_mode = _GEMM_ACTIVE
         return fwd(ctx, *args)
 
     def backward(ctx, *grads):
@@ -195,6 +199,10 @@ def _remember_gemm_mode(cls):
     cls.forward = staticmethod(forward)
     cls.backward = staticmethod(backward)
     return cls
+
+
+def _remember_gemm_mode_fp32(cls):
+    return _remember_gemm_mode(cls, fp32_only=True)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -810,27 +818,31 @@ def layernorm2d(x, weight, bias, eps=1e-6):
 
 # ------------------------------------------------------------------------------------------------
 class _IntroFn(torch.autograd.Function):
-    """3x3 conv, image NCHW -> features NHWC (reference nafnet_arch.py:202-210, :252)."""
+    """3x3 conv, image NCHW -> features NHWC (reference nafnet_arch.py:202-210, :252).  The image, the parameters and their gradients are
+    fp32; ``out_bf16`` puts the feature side (y, and the dy that comes back) in bf16 storage (edge_bf16.hip)."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias):
+    def forward(ctx, x, weight, bias, out_bf16):
         lib = _lib.load()
         _require_gpu(x, weight, bias)
         x = _contig(x)
         w_, b_ = _contig(weight.detach()), (None if bias is None else _contig(bias.detach()))
         B, Cin, H, W = x.shape
         Cout = w_.shape[0]
-        y = _empty_nhwc(B, Cout, H, W, x.device)
-        check(lib.dcpt_conv3x3_in_fwd(x.data_ptr(), w_.data_ptr(), _p(b_), y.data_ptr(), B, H, W, Cin, Cout,
-                                      _stream(x.device)), "dcpt_conv3x3_in_fwd")
+        bf = bool(out_bf16)
+        y = (_empty_nhwc_bf16 if bf else _empty_nhwc)(B, Cout, H, W, x.device)
+        fn = lib.dcpt_conv3x3_in_fwd_bf16 if bf else lib.dcpt_conv3x3_in_fwd
+        check(fn(x.data_ptr(), w_.data_ptr(), _p(b_), y.data_ptr(), B, H, W, Cin, Cout, _stream(x.device)), fn.__name__)
         ctx.save_for_backward(x, w_)
-        ctx.has_bias = bias is not None
+        ctx.has_bias, ctx.bf = bias is not None, bf
         return y
 
     @staticmethod
     def backward(ctx, dy):
         lib = _lib.load()
         x, w_ = ctx.saved_tensors
+        if ctx.bf:
+            _require_gpu_bf16(dy)
         dy = _nhwc(dy)
         B, Cin, H, W = x.shape
         Cout = w_.shape[0]
@@ -840,93 +852,20 @@ class _IntroFn(torch.autograd.Function):
         dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
         nws = lib.dcpt_conv3x3_in_bwd_ws_bytes(B, H, W, Cin, Cout)
         ws = _workspace(dev, nws)
-        check(lib.dcpt_conv3x3_in_bwd(dy.data_ptr(), x.data_ptr(), w_.data_ptr(), _p(dx), dw.data_ptr(), db.data_ptr(),
-                                      ws.data_ptr(), ws.numel(), B, H, W, Cin, Cout, _stream(dev)), "dcpt_conv3x3_in_bwd")
-        return dx, dw, (db if ctx.has_bias else None)
+        fn = lib.dcpt_conv3x3_in_bwd_bf16 if ctx.bf else lib.dcpt_conv3x3_in_bwd
+        check(fn(dy.data_ptr(), x.data_ptr(), w_.data_ptr(), _p(dx), dw.data_ptr(), db.data_ptr(), ws.data_ptr(), ws.numel(), B, H, W,
+                 Cin, Cout, _stream(dev)), fn.__name__)
+        return dx, dw, (db if ctx.has_bias else None), None
 
 
 class _EndingFn(torch.autograd.Function):
-    """3x3 conv, features NHWC -> image NCHW, + residual image (reference nafnet_arch.py:211-219, :271-272)."""
+    """3x3 conv, features NHWC -> image NCHW, + residual image (reference nafnet_arch.py:211-219, :271-272).  Features (and dx) fp32 or
+    bf16 by x.dtype; the image, the residual image, the parameters and their gradients are fp32 in both."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, res):
         lib = _lib.load()
-        _require_gpu(x, weight, bias, res)
-        x = _nhwc(x)
-        w_, b_ = _contig(weight.detach()), (None if bias is None else _contig(bias.detach()))
-        res_ = None if res is None else _contig(res)
-        B, Cin, H, W = x.shape
-        Cout = w_.shape[0]
-        y = torch.empty((B, Cout, H, W), dtype=torch.float32, device=x.device)
-        check(lib.dcpt_conv3x3_out_fwd(x.data_ptr(), w_.data_ptr(), _p(b_), _p(res_), y.data_ptr(), B, H, W, Cin, Cout,
-                                       _stream(x.device)), "dcpt_conv3x3_out_fwd")
-        ctx.save_for_backward(x, w_)
-        ctx.has_bias = bias is not None
-        ctx.has_res = res is not None
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        lib = _lib.load()
-        x, w_ = ctx.saved_tensors
-        dy = _contig(dy)
-        B, Cin, H, W = x.shape
-        Cout = w_.shape[0]
-        dev = x.device
-        dx = _empty_nhwc(B, Cin, H, W, dev)
-        dw = torch.empty_like(w_)
-        db = torch.empty((Cout,), dtype=torch.float32, device=dev)
-        nws = lib.dcpt_conv3x3_out_bwd_ws_bytes(B, H, W, Cin, Cout)
-        ws = _workspace(dev, nws)
-        check(lib.dcpt_conv3x3_out_bwd(dy.data_ptr(), x.data_ptr(), w_.data_ptr(), dx.data_ptr(), dw.data_ptr(),
-                                       db.data_ptr(), ws.data_ptr(), ws.numel(), B, H, W, Cin, Cout, _stream(dev)),
-              "dcpt_conv3x3_out_bwd")
-        return dx, dw, (db if ctx.has_bias else None), (dy if ctx.has_res and ctx.needs_input_grad[3] else None)
-
-
-class _IntroBf16Fn(torch.autograd.Function):
-    """_IntroFn with the feature side in bf16 storage (edge_bf16.hip): fp32 image in, bf16 NHWC features out."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias):
-        lib = _lib.load()
-        _require_gpu(x, weight, bias)
-        x = _contig(x)
-        w_, b_ = _contig(weight.detach()), (None if bias is None else _contig(bias.detach()))
-        B, Cin, H, W = x.shape
-        Cout = w_.shape[0]
-        y = _empty_nhwc_bf16(B, Cout, H, W, x.device)
-        check(lib.dcpt_conv3x3_in_fwd_bf16(x.data_ptr(), w_.data_ptr(), _p(b_), y.data_ptr(), B, H, W, Cin, Cout, _stream(x.device)),
-              "dcpt_conv3x3_in_fwd_bf16")
-        ctx.save_for_backward(x, w_)
-        ctx.has_bias = bias is not None
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        lib = _lib.load()
-        x, w_ = ctx.saved_tensors
-        _require_gpu_bf16(dy)
-        dy = _nhwc(dy)
-        B, Cin, H, W = x.shape
-        Cout = w_.shape[0]
-        dev = x.device
-        dw = torch.empty_like(w_)
-        db = torch.empty((Cout,), dtype=torch.float32, device=dev)
-        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
-        ws = _workspace(dev, lib.dcpt_conv3x3_in_bwd_ws_bytes(B, H, W, Cin, Cout))
-        check(lib.dcpt_conv3x3_in_bwd_bf16(dy.data_ptr(), x.data_ptr(), w_.data_ptr(), _p(dx), dw.data_ptr(), db.data_ptr(), ws.data_ptr(),
-                                           ws.numel(), B, H, W, Cin, Cout, _stream(dev)), "dcpt_conv3x3_in_bwd_bf16")
-        return dx, dw, (db if ctx.has_bias else None)
-
-
-class _EndingBf16Fn(torch.autograd.Function):
-    """_EndingFn with bf16 NHWC features in, fp32 image (+ residual image) out."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, res):
-        lib = _lib.load()
-        _require_gpu_bf16(x)
+        _require_gpu_feat(x)
         _require_gpu(weight, bias, res)
         x = _nhwc(x)
         w_, b_ = _contig(weight.detach()), (None if bias is None else _contig(bias.detach()))
@@ -934,8 +873,8 @@ class _EndingBf16Fn(torch.autograd.Function):
         B, Cin, H, W = x.shape
         Cout = w_.shape[0]
         y = torch.empty((B, Cout, H, W), dtype=torch.float32, device=x.device)
-        check(lib.dcpt_conv3x3_out_fwd_bf16(x.data_ptr(), w_.data_ptr(), _p(b_), _p(res_), y.data_ptr(), B, H, W, Cin, Cout,
-                                            _stream(x.device)), "dcpt_conv3x3_out_fwd_bf16")
+        fn = lib.dcpt_conv3x3_out_fwd_bf16 if x.dtype == torch.bfloat16 else lib.dcpt_conv3x3_out_fwd
+        check(fn(x.data_ptr(), w_.data_ptr(), _p(b_), _p(res_), y.data_ptr(), B, H, W, Cin, Cout, _stream(x.device)), fn.__name__)
         ctx.save_for_backward(x, w_)
         ctx.has_bias = bias is not None
         ctx.has_res = res is not None
@@ -945,124 +884,53 @@ class _EndingBf16Fn(torch.autograd.Function):
     def backward(ctx, dy):
         lib = _lib.load()
         x, w_ = ctx.saved_tensors
+        bf = x.dtype == torch.bfloat16
         dy = _contig(dy)
         B, Cin, H, W = x.shape
         Cout = w_.shape[0]
         dev = x.device
-        dx = _empty_nhwc_bf16(B, Cin, H, W, dev)
+        dx = (_empty_nhwc_bf16 if bf else _empty_nhwc)(B, Cin, H, W, dev)
         dw = torch.empty_like(w_)
         db = torch.empty((Cout,), dtype=torch.float32, device=dev)
-        ws = _workspace(dev, lib.dcpt_conv3x3_out_bwd_ws_bytes(B, H, W, Cin, Cout))
-        check(lib.dcpt_conv3x3_out_bwd_bf16(dy.data_ptr(), x.data_ptr(), w_.data_ptr(), dx.data_ptr(), dw.data_ptr(), db.data_ptr(),
-                                            ws.data_ptr(), ws.numel(), B, H, W, Cin, Cout, _stream(dev)), "dcpt_conv3x3_out_bwd_bf16")
+        nws = lib.dcpt_conv3x3_out_bwd_ws_bytes(B, H, W, Cin, Cout)
+        ws = _workspace(dev, nws)
+        fn = lib.dcpt_conv3x3_out_bwd_bf16 if bf else lib.dcpt_conv3x3_out_bwd
+        check(fn(dy.data_ptr(), x.data_ptr(), w_.data_ptr(), dx.data_ptr(), dw.data_ptr(), db.data_ptr(), ws.data_ptr(), ws.numel(),
+                 B, H, W, Cin, Cout, _stream(dev)), fn.__name__)
         return dx, dw, (db if ctx.has_bias else None), (dy if ctx.has_res and ctx.needs_input_grad[3] else None)
 
 
 def conv3x3_in(x, weight, bias, out_bf16=False):
     """3x3 conv image -> features; ``out_bf16``: emit bf16-storage features (the first layer of the bf16 path)"""
-    return _IntroBf16Fn.apply(x, weight, bias) if out_bf16 else _IntroFn.apply(x, weight, bias)
+    return _IntroFn.apply(x, weight, bias, out_bf16)
 
 
 def conv3x3_out(x, weight, bias, res=None):
-    if x.dtype == torch.bfloat16:
-        return _EndingBf16Fn.apply(x, weight, bias, res)
     return _EndingFn.apply(x, weight, bias, res)
 
 
 # ------------------------------------------------------------------------------------------------
-@_remember_gemm_mode
+@_remember_gemm_mode_fp32
 class _DownFn(torch.autograd.Function):
-    """Conv2d(C, 2C, 2, 2) (reference nafnet_arch.py:230)."""
+    """Conv2d(C, 2C, 2, 2) (reference nafnet_arch.py:230); fp32 or bf16 storage (edge_bf16.hip) by x.dtype, parameters fp32."""
 
     @staticmethod
     def forward(ctx, x, weight, bias):
         lib = _lib.load()
-        _require_gpu(x, weight, bias)
-        x = _nhwc(x)
-        w_, b_ = _contig(weight.detach()), (None if bias is None else _contig(bias.detach()))
-        B, Cc, H, W = x.shape
-        if H % 2 or W % 2:
-            raise ValueError(f"down2x2: H={H}, W={W} must be even")
-        y = _empty_nhwc(B, 2 * Cc, H // 2, W // 2, x.device)
-        nws = lib.dcpt_down2x2_ws_bytes(B, H, W, Cc, 0)
-        ws = _workspace(x.device, nws)
-        check(lib.dcpt_down2x2_fwd(x.data_ptr(), w_.data_ptr(), _p(b_), y.data_ptr(), ws.data_ptr(), ws.numel(), B, H, W,
-                                   Cc, _stream(x.device)), "dcpt_down2x2_fwd")
-        ctx.save_for_backward(x, w_)
-        ctx.has_bias = bias is not None
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        lib = _lib.load()
-        x, w_ = ctx.saved_tensors
-        dy = _nhwc(dy)
-        B, Cc, H, W = x.shape
-        dev = x.device
-        dx = _empty_nhwc(B, Cc, H, W, dev)
-        dw = torch.empty_like(w_)
-        db = torch.empty((2 * Cc,), dtype=torch.float32, device=dev)
-        nws = lib.dcpt_down2x2_ws_bytes(B, H, W, Cc, 1)
-        ws = _workspace(dev, nws)
-        check(lib.dcpt_down2x2_bwd(dy.data_ptr(), x.data_ptr(), w_.data_ptr(), dx.data_ptr(), dw.data_ptr(), db.data_ptr(),
-                                   ws.data_ptr(), ws.numel(), B, H, W, Cc, _stream(dev)), "dcpt_down2x2_bwd")
-        return dx, dw, (db if ctx.has_bias else None)
-
-
-@_remember_gemm_mode
-class _UpFn(torch.autograd.Function):
-    """Conv2d(C, 2C, 1, bias=False) + PixelShuffle(2) + skip add (reference nafnet_arch.py:238-242, :264-265)."""
-
-    @staticmethod
-    def forward(ctx, x, weight, skip):
-        lib = _lib.load()
-        _require_gpu(x, weight, skip)
-        x = _nhwc(x)
-        w_ = _contig(weight.detach())
-        skip_ = None if skip is None else _nhwc(skip)
-        B, Cc, H, W = x.shape
-        y = _empty_nhwc(B, Cc // 2, 2 * H, 2 * W, x.device)
-        nws = lib.dcpt_up_ps_ws_bytes(B, H, W, Cc, 0)
-        ws = _workspace(x.device, nws)
-        check(lib.dcpt_up_ps_fwd(x.data_ptr(), w_.data_ptr(), _p(skip_), y.data_ptr(), ws.data_ptr(), ws.numel(), B, H, W,
-                                 Cc, _stream(x.device)), "dcpt_up_ps_fwd")
-        ctx.save_for_backward(x, w_)
-        ctx.has_skip = skip is not None
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        lib = _lib.load()
-        x, w_ = ctx.saved_tensors
-        dy = _nhwc(dy)
-        B, Cc, H, W = x.shape
-        dev = x.device
-        dx = _empty_nhwc(B, Cc, H, W, dev)
-        dw = torch.empty_like(w_)
-        nws = lib.dcpt_up_ps_ws_bytes(B, H, W, Cc, 1)
-        ws = _workspace(dev, nws)
-        check(lib.dcpt_up_ps_bwd(dy.data_ptr(), x.data_ptr(), w_.data_ptr(), dx.data_ptr(), dw.data_ptr(), ws.data_ptr(),
-                                 ws.numel(), B, H, W, Cc, _stream(dev)), "dcpt_up_ps_bwd")
-        return dx, dw, (dy if ctx.has_skip else None)
-
-
-class _DownBf16Fn(torch.autograd.Function):
-    """_DownFn in bf16 storage (edge_bf16.hip)."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias):
-        lib = _lib.load()
-        _require_gpu_bf16(x)
+        _require_gpu_feat(x)
         _require_gpu(weight, bias)
         x = _nhwc(x)
+        bf = x.dtype == torch.bfloat16
         w_, b_ = _contig(weight.detach()), (None if bias is None else _contig(bias.detach()))
         B, Cc, H, W = x.shape
         if H % 2 or W % 2:
             raise ValueError(f"down2x2: H={H}, W={W} must be even")
-        y = _empty_nhwc_bf16(B, 2 * Cc, H // 2, W // 2, x.device)
-        ws = _workspace(x.device, lib.dcpt_down2x2_bf16_ws_bytes(B, H, W, Cc, 0))
-        check(lib.dcpt_down2x2_fwd_bf16(x.data_ptr(), w_.data_ptr(), _p(b_), y.data_ptr(), ws.data_ptr(), ws.numel(), B, H, W, Cc,
-                                        _stream(x.device)), "dcpt_down2x2_fwd_bf16")
+        y = (_empty_nhwc_bf16 if bf else _empty_nhwc)(B, 2 * Cc, H // 2, W // 2, x.device)
+        nws = (lib.dcpt_down2x2_bf16_ws_bytes if bf else lib.dcpt_down2x2_ws_bytes)(B, H, W, Cc, 0)
+        ws = _workspace(x.device, nws)
+        fn = lib.dcpt_down2x2_fwd_bf16 if bf else lib.dcpt_down2x2_fwd
+        check(fn(x.data_ptr(), w_.data_ptr(), _p(b_), y.data_ptr(), ws.data_ptr(), ws.numel(), B, H, W, Cc, _stream(x.device)),
+              fn.__name__)
         ctx.save_for_backward(x, w_)
         ctx.has_bias = bias is not None
         return y
@@ -1071,35 +939,46 @@ class _DownBf16Fn(torch.autograd.Function):
     def backward(ctx, dy):
         lib = _lib.load()
         x, w_ = ctx.saved_tensors
-        _require_gpu_bf16(dy)
+        bf = x.dtype == torch.bfloat16
+        if bf:
+            _require_gpu_bf16(dy)
         dy = _nhwc(dy)
         B, Cc, H, W = x.shape
         dev = x.device
-        dx = _empty_nhwc_bf16(B, Cc, H, W, dev)
+        dx = (_empty_nhwc_bf16 if bf else _empty_nhwc)(B, Cc, H, W, dev)
         dw = torch.empty_like(w_)
         db = torch.empty((2 * Cc,), dtype=torch.float32, device=dev)
-        ws = _workspace(dev, lib.dcpt_down2x2_bf16_ws_bytes(B, H, W, Cc, 1))
-        check(lib.dcpt_down2x2_bwd_bf16(dy.data_ptr(), x.data_ptr(), w_.data_ptr(), dx.data_ptr(), dw.data_ptr(), db.data_ptr(), ws.data_ptr(),
-                                        ws.numel(), B, H, W, Cc, _stream(dev)), "dcpt_down2x2_bwd_bf16")
+        nws = (lib.dcpt_down2x2_bf16_ws_bytes if bf else lib.dcpt_down2x2_ws_bytes)(B, H, W, Cc, 1)
+        ws = _workspace(dev, nws)
+        fn = lib.dcpt_down2x2_bwd_bf16 if bf else lib.dcpt_down2x2_bwd
+        check(fn(dy.data_ptr(), x.data_ptr(), w_.data_ptr(), dx.data_ptr(), dw.data_ptr(), db.data_ptr(), ws.data_ptr(), ws.numel(),
+                 B, H, W, Cc, _stream(dev)), fn.__name__)
         return dx, dw, (db if ctx.has_bias else None)
 
 
-class _UpBf16Fn(torch.autograd.Function):
-    """_UpFn in bf16 storage (edge_bf16.hip)."""
+@_remember_gemm_mode_fp32
+class _UpFn(torch.autograd.Function):
+    """Conv2d(C, 2C, 1, bias=False) + PixelShuffle(2) + skip add (reference nafnet_arch.py:238-242, :264-265); fp32 or bf16 storage
+    (edge_bf16.hip) by x.dtype -- the skip is stored like x --, the weight fp32."""
 
     @staticmethod
     def forward(ctx, x, weight, skip):
         lib = _lib.load()
-        _require_gpu_bf16(x, *([] if skip is None else [skip]))
+        _require_gpu_feat(x, skip)
         _require_gpu(weight)
+        if skip is not None and skip.dtype != x.dtype:
+            raise _lib.DcptHipError("up_ps: x and skip must have the same storage dtype")
         x = _nhwc(x)
+        bf = x.dtype == torch.bfloat16
         w_ = _contig(weight.detach())
         skip_ = None if skip is None else _nhwc(skip)
         B, Cc, H, W = x.shape
-        y = _empty_nhwc_bf16(B, Cc // 2, 2 * H, 2 * W, x.device)
-        ws = _workspace(x.device, lib.dcpt_up_ps_bf16_ws_bytes(B, H, W, Cc, 0))
-        check(lib.dcpt_up_ps_fwd_bf16(x.data_ptr(), w_.data_ptr(), _p(skip_), y.data_ptr(), ws.data_ptr(), ws.numel(), B, H, W, Cc,
-                                      _stream(x.device)), "dcpt_up_ps_fwd_bf16")
+        y = (_empty_nhwc_bf16 if bf else _empty_nhwc)(B, Cc // 2, 2 * H, 2 * W, x.device)
+        nws = (lib.dcpt_up_ps_bf16_ws_bytes if bf else lib.dcpt_up_ps_ws_bytes)(B, H, W, Cc, 0)
+        ws = _workspace(x.device, nws)
+        fn = lib.dcpt_up_ps_fwd_bf16 if bf else lib.dcpt_up_ps_fwd
+        check(fn(x.data_ptr(), w_.data_ptr(), _p(skip_), y.data_ptr(), ws.data_ptr(), ws.numel(), B, H, W, Cc, _stream(x.device)),
+              fn.__name__)
         ctx.save_for_backward(x, w_)
         ctx.has_skip = skip is not None
         return y
@@ -1108,20 +987,24 @@ class _UpBf16Fn(torch.autograd.Function):
     def backward(ctx, dy):
         lib = _lib.load()
         x, w_ = ctx.saved_tensors
-        _require_gpu_bf16(dy)
+        bf = x.dtype == torch.bfloat16
+        if bf:
+            _require_gpu_bf16(dy)
         dy = _nhwc(dy)
         B, Cc, H, W = x.shape
         dev = x.device
-        dx = _empty_nhwc_bf16(B, Cc, H, W, dev)
+        dx = (_empty_nhwc_bf16 if bf else _empty_nhwc)(B, Cc, H, W, dev)
         dw = torch.empty_like(w_)
-        ws = _workspace(dev, lib.dcpt_up_ps_bf16_ws_bytes(B, H, W, Cc, 1))
-        check(lib.dcpt_up_ps_bwd_bf16(dy.data_ptr(), x.data_ptr(), w_.data_ptr(), dx.data_ptr(), dw.data_ptr(), ws.data_ptr(), ws.numel(), B, H, W,
-                                      Cc, _stream(dev)), "dcpt_up_ps_bwd_bf16")
+        nws = (lib.dcpt_up_ps_bf16_ws_bytes if bf else lib.dcpt_up_ps_ws_bytes)(B, H, W, Cc, 1)
+        ws = _workspace(dev, nws)
+        fn = lib.dcpt_up_ps_bwd_bf16 if bf else lib.dcpt_up_ps_bwd
+        check(fn(dy.data_ptr(), x.data_ptr(), w_.data_ptr(), dx.data_ptr(), dw.data_ptr(), ws.data_ptr(), ws.numel(), B, H, W, Cc,
+                 _stream(dev)), fn.__name__)
         return dx, dw, (dy if ctx.has_skip else None)
 
 
 def down2x2(x, weight, bias):
-    return _DownBf16Fn.apply(x, weight, bias) if x.dtype == torch.bfloat16 else _DownFn.apply(x, weight, bias)
+    return _DownFn.apply(x, weight, bias)
 
 
 @_remember_gemm_mode
@@ -1180,8 +1063,6 @@ def down2x2_skip(x, weight, bias):
 
 
 def up_ps(x, weight, skip=None):
-    if x.dtype == torch.bfloat16:
-        return _UpBf16Fn.apply(x, weight, skip)
     return _UpFn.apply(x, weight, skip)
 
 
@@ -1707,23 +1588,26 @@ def meanpool_fc(x, fw, fb):
 from ._lib import GdfnParams, GdfnSaved, MdtaParams, MdtaSaved  # noqa: E402
 
 
-@_remember_gemm_mode
+@_remember_gemm_mode_fp32
 class _ConvFn(torch.autograd.Function):
-    """bias-free conv (1x1 or dense 3x3 / pad 1), NHWC -> NHWC."""
+    """bias-free conv (1x1 or dense 3x3 / pad 1), NHWC -> NHWC; fp32 or bf16 features by x.dtype, the weight and its gradient fp32."""
 
     @staticmethod
     def forward(ctx, x, weight):
         lib = _lib.load()
-        _require_gpu(x, weight)
+        _require_gpu_feat(x)
+        _require_gpu(weight)
         x = _nhwc(x)
+        bf = x.dtype == torch.bfloat16
         w_ = _contig(weight.detach())
         B, Cin, H, W = x.shape
         Cout, ks = w_.shape[0], w_.shape[2]
         dev = x.device
-        y = _empty_nhwc(B, Cout, H, W, dev)
-        ws = _workspace(dev, lib.dcpt_conv_ws_bytes(B, H, W, Cin, Cout, ks, 0))
-        check(lib.dcpt_conv_fwd(x.data_ptr(), w_.data_ptr(), y.data_ptr(), ws.data_ptr(), ws.numel(), B, H, W, Cin, Cout, ks,
-                                _stream(dev)), "dcpt_conv_fwd")
+        y = (_empty_nhwc_bf16 if bf else _empty_nhwc)(B, Cout, H, W, dev)
+        ws = _workspace(dev, (lib.dcpt_conv_bf16_ws_bytes if bf else lib.dcpt_conv_ws_bytes)(B, H, W, Cin, Cout, ks, 0))
+        fn = lib.dcpt_conv_fwd_bf16 if bf else lib.dcpt_conv_fwd
+        check(fn(x.data_ptr(), w_.data_ptr(), y.data_ptr(), ws.data_ptr(), ws.numel(), B, H, W, Cin, Cout, ks, _stream(dev)),
+              fn.__name__)
         ctx.save_for_backward(x, w_)
         return y
 
@@ -1731,109 +1615,99 @@ class _ConvFn(torch.autograd.Function):
     def backward(ctx, dy):
         lib = _lib.load()
         x, w_ = ctx.saved_tensors
+        bf = x.dtype == torch.bfloat16
+        if bf:
+            _require_gpu_bf16(dy)
         dy = _nhwc(dy)
         B, Cin, H, W = x.shape
         Cout, ks = w_.shape[0], w_.shape[2]
         dev = x.device
-        dx = _empty_nhwc(B, Cin, H, W, dev)
+        dx = (_empty_nhwc_bf16 if bf else _empty_nhwc)(B, Cin, H, W, dev)
         dw = torch.empty_like(w_)
-        ws = _workspace(dev, lib.dcpt_conv_ws_bytes(B, H, W, Cin, Cout, ks, 1))
-        check(lib.dcpt_conv_bwd(dy.data_ptr(), x.data_ptr(), w_.data_ptr(), dx.data_ptr(), dw.data_ptr(), ws.data_ptr(),
-                                ws.numel(), B, H, W, Cin, Cout, ks, _stream(dev)), "dcpt_conv_bwd")
+        ws = _workspace(dev, (lib.dcpt_conv_bf16_ws_bytes if bf else lib.dcpt_conv_ws_bytes)(B, H, W, Cin, Cout, ks, 1))
+        fn = lib.dcpt_conv_bwd_bf16 if bf else lib.dcpt_conv_bwd
+        check(fn(dy.data_ptr(), x.data_ptr(), w_.data_ptr(), dx.data_ptr(), dw.data_ptr(), ws.data_ptr(), ws.numel(), B, H, W, Cin,
+                 Cout, ks, _stream(dev)), fn.__name__)
         return dx, dw
 
 
 def conv_nobias(x, weight):
-    if x.dtype == torch.bfloat16:
-        return _ConvBf16Fn.apply(x, weight)
     return _ConvFn.apply(x, weight)
 
 
-class _PixelUnshuffleFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x):
-        lib = _lib.load()
-        _require_gpu(x)
-        x = _nhwc(x)
-        B, Cc, H, W = x.shape
-        y = _empty_nhwc(B, 4 * Cc, H // 2, W // 2, x.device)
-        check(lib.dcpt_pixel_unshuffle(x.data_ptr(), y.data_ptr(), B, H, W, Cc, _stream(x.device)), "dcpt_pixel_unshuffle")
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        lib = _lib.load()
-        dy = _nhwc(dy)
-        B, C4, H, W = dy.shape
-        dx = _empty_nhwc(B, C4 // 4, 2 * H, 2 * W, dy.device)
-        check(lib.dcpt_pixel_shuffle(dy.data_ptr(), dx.data_ptr(), B, H, W, C4, _stream(dy.device)), "dcpt_pixel_shuffle")
-        return dx
+def _shuffle(lib, x, up):
+    x = _nhwc(x)
+    bf = x.dtype == torch.bfloat16
+    B, Cc, H, W = x.shape
+    if up:
+        y = (_empty_nhwc_bf16 if bf else _empty_nhwc)(B, Cc // 4, 2 * H, 2 * W, x.device)
+        fn = lib.dcpt_pixel_shuffle_bf16 if bf else lib.dcpt_pixel_shuffle
+    else:
+        y = (_empty_nhwc_bf16 if bf else _empty_nhwc)(B, 4 * Cc, H // 2, W // 2, x.device)
+        fn = lib.dcpt_pixel_unshuffle_bf16 if bf else lib.dcpt_pixel_unshuffle
+    check(fn(x.data_ptr(), y.data_ptr(), B, H, W, Cc, _stream(x.device)), fn.__name__)
+    return y
 
 
 class _PixelShuffleFn(torch.autograd.Function):
+    """PixelShuffle(2) (up) / PixelUnshuffle(2) on fp32 or bf16 NHWC maps; the backward is the other one, in the forward's storage."""
+
     @staticmethod
-    def forward(ctx, x):
-        lib = _lib.load()
-        _require_gpu(x)
-        x = _nhwc(x)
-        B, C4, H, W = x.shape
-        y = _empty_nhwc(B, C4 // 4, 2 * H, 2 * W, x.device)
-        check(lib.dcpt_pixel_shuffle(x.data_ptr(), y.data_ptr(), B, H, W, C4, _stream(x.device)), "dcpt_pixel_shuffle")
-        return y
+    def forward(ctx, x, up):
+        _require_gpu_feat(x)
+        ctx.up, ctx.bf = bool(up), x.dtype == torch.bfloat16
+        return _shuffle(_lib.load(), x, ctx.up)
 
     @staticmethod
     def backward(ctx, dy):
-        lib = _lib.load()
-        dy = _nhwc(dy)
-        B, Cc, H, W = dy.shape
-        dx = _empty_nhwc(B, 4 * Cc, H // 2, W // 2, dy.device)
-        check(lib.dcpt_pixel_unshuffle(dy.data_ptr(), dx.data_ptr(), B, H, W, Cc, _stream(dy.device)), "dcpt_pixel_unshuffle")
-        return dx
+        (_require_gpu_bf16 if ctx.bf else _require_gpu)(dy)
+        return _shuffle(_lib.load(), dy, not ctx.up), None
 
 
 def pixel_unshuffle2(x):
-    if x.dtype == torch.bfloat16:
-        return _PixelShuffleBf16Fn.apply(x, False)
-    return _PixelUnshuffleFn.apply(x)
+    return _PixelShuffleFn.apply(x, False)
 
 
 def pixel_shuffle2(x):
-    if x.dtype == torch.bfloat16:
-        return _PixelShuffleBf16Fn.apply(x, True)
-    return _PixelShuffleFn.apply(x)
+    return _PixelShuffleFn.apply(x, True)
 
 
 class _ConcatFn(torch.autograd.Function):
-    """torch.cat([a, b], 1) on NHWC maps."""
+    """torch.cat([a, b], 1) on NHWC maps, both fp32 or both bf16."""
 
     @staticmethod
     def forward(ctx, a, b):
         lib = _lib.load()
-        _require_gpu(a, b)
+        _require_gpu_feat(a, b)
+        if a.dtype != b.dtype:
+            raise _lib.DcptHipError("concat_channels: a and b must have the same storage dtype")
         a, b = _nhwc(a), _nhwc(b)
+        bf = a.dtype == torch.bfloat16
         B, Ca, H, W = a.shape
         Cb = b.shape[1]
-        out = _empty_nhwc(B, Ca + Cb, H, W, a.device)
-        check(lib.dcpt_concat_channels(a.data_ptr(), b.data_ptr(), out.data_ptr(), B * H * W, Ca, Cb, _stream(a.device)),
-              "dcpt_concat_channels")
-        ctx.dims = (Ca, Cb)
+        out = (_empty_nhwc_bf16 if bf else _empty_nhwc)(B, Ca + Cb, H, W, a.device)
+        fn = lib.dcpt_concat_channels_bf16 if bf else lib.dcpt_concat_channels
+        check(fn(a.data_ptr(), b.data_ptr(), out.data_ptr(), B * H * W, Ca, Cb, _stream(a.device)), fn.__name__)
+        ctx.dims, ctx.bf = (Ca, Cb), bf
         return out
 
     @staticmethod
     def backward(ctx, dout):
         lib = _lib.load()
+        bf = ctx.bf
+        if bf:
+            _require_gpu_bf16(dout)
         dout = _nhwc(dout)
         Ca, Cb = ctx.dims
         B, _, H, W = dout.shape
-        da, db = _empty_nhwc(B, Ca, H, W, dout.device), _empty_nhwc(B, Cb, H, W, dout.device)
-        check(lib.dcpt_split_channels(dout.data_ptr(), da.data_ptr(), db.data_ptr(), B * H * W, Ca, Cb, _stream(dout.device)),
-              "dcpt_split_channels")
+        da = (_empty_nhwc_bf16 if bf else _empty_nhwc)(B, Ca, H, W, dout.device)
+        db = (_empty_nhwc_bf16 if bf else _empty_nhwc)(B, Cb, H, W, dout.device)
+        fn = lib.dcpt_split_channels_bf16 if bf else lib.dcpt_split_channels
+        check(fn(dout.data_ptr(), da.data_ptr(), db.data_ptr(), B * H * W, Ca, Cb, _stream(dout.device)), fn.__name__)
         return da, db
 
 
 def concat_channels(a, b):
-    if a.dtype == torch.bfloat16:
-        return _ConcatBf16Fn.apply(a, b)
     return _ConcatFn.apply(a, b)
 
 
@@ -1900,173 +1774,48 @@ def _restormer_mode(dev) -> str:
     return _resolve_restormer_mode(_RESTORMER_SAVE, dev)   # a bare MDTA / GDFN call outside a network
 
 
-@_remember_gemm_mode
+# Both halves run in fp32 or in bf16 activation storage, by x.dtype (restormer_bf16.hip; Restormer / Restormer_origin / PromptIR with
+# act_dtype="bf16"): in bf16 storage the feature maps and the tensors the halves keep are bf16, statistics / attention matrices /
+# parameters / parameter gradients fp32.  The save modes keep the same sets of tensors in both storages (bit-identical results in every
+# mode).  Two things differ beyond the storage: a bf16-storage forward with no backward to come (``train`` False, decided by the caller:
+# grad mode is off inside Function.forward) runs as "lean" / not full and keeps nothing, while an fp32 forward allocates what the save
+# mode says whatever the grad mode; and bit 1 of the workspace queries' mode argument (everything kept: a smaller workspace) exists in
+# the bf16 queries only.
+@_remember_gemm_mode_fp32
 class _MDTAFn(torch.autograd.Function):
-    """x + project_out(attn(LN(x)))  (restormer_arch.py:103-145, :156-157)."""
-
-    @staticmethod
-    def forward(ctx, x, norm_w, norm_b, qkv_w, dw_w, proj_w, temperature, heads, biasfree):
-        lib = _lib.load()
-        _require_gpu(x, norm_w, norm_b, qkv_w, dw_w, proj_w, temperature)
-        x = _nhwc(x)
-        ps = [None if t is None else _contig(t.detach()) for t in (norm_w, norm_b, qkv_w, dw_w, proj_w, temperature)]
-        B, Cc, H, W = x.shape
-        dev = x.device
-        M, ch = B * H * W, Cc // heads
-        y = _empty_nhwc(B, Cc, H, W, dev)
-        stats = torch.empty((2, M), dtype=torch.float32, device=dev)
-        mode = _restormer_mode(dev)
-        qkv1 = None if mode == "lean" else _empty_nhwc(B, 3 * Cc, H, W, dev)
-        qkv = _empty_nhwc(B, 3 * Cc, H, W, dev)
-        nrm = torch.empty((B, 2 * Cc), dtype=torch.float32, device=dev)
-        att = torch.empty((3, B, heads, ch, ch), dtype=torch.float32, device=dev)
-        out_att = None if mode != "full" else _empty_nhwc(B, Cc, H, W, dev)
-        xn = None if mode != "full" else _empty_nhwc(B, Cc, H, W, dev)
-        sv = MdtaSaved(stats[0].data_ptr(), stats[1].data_ptr(), _p(qkv1), qkv.data_ptr(), nrm.data_ptr(),
-                       att[0].data_ptr(), att[1].data_ptr(), att[2].data_ptr(), _p(out_att), _p(xn))
-        pp = MdtaParams(*[_p(t) for t in ps])
-        ws = _workspace(dev, lib.dcpt_mdta_ws_bytes(B, H, W, Cc, heads, 0))
-        check(lib.dcpt_mdta_fwd(C.byref(pp), x.data_ptr(), y.data_ptr(), C.byref(sv), ws.data_ptr(), ws.numel(), B, H, W, Cc,
-                                heads, int(biasfree), _stream(dev)), "dcpt_mdta_fwd")
-        kept = [t for t in (qkv1, out_att, xn) if t is not None]
-        ctx.kept = (qkv1 is not None, out_att is not None, xn is not None)
-        ctx.save_for_backward(x, stats, qkv, nrm, att, *kept, *[t for t in ps if t is not None])
-        ctx.has_bias = ps[1] is not None
-        ctx.heads, ctx.biasfree = heads, int(biasfree)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        lib = _lib.load()
-        x, stats, qkv, nrm, att, *ps = ctx.saved_tensors
-        ps = list(ps)
-        qkv1, out_att, xn = (ps.pop(0) if k else None for k in ctx.kept)
-        if ctx.has_bias:
-            norm_w, norm_b, qkv_w, dw_w, proj_w, temp = ps
-        else:
-            norm_w, qkv_w, dw_w, proj_w, temp = ps
-            norm_b = None
-        dy = _nhwc(dy)
-        B, Cc, H, W = x.shape
-        dev = x.device
-        dx = _empty_nhwc(B, Cc, H, W, dev)
-        plist = [norm_w, norm_b, qkv_w, dw_w, proj_w, temp]
-        grads = [None if t is None else torch.empty_like(t) for t in plist]
-        sv = MdtaSaved(stats[0].data_ptr(), stats[1].data_ptr(), _p(qkv1), qkv.data_ptr(), nrm.data_ptr(),
-                       att[0].data_ptr(), att[1].data_ptr(), att[2].data_ptr(), _p(out_att), _p(xn))
-        pp = MdtaParams(*[_p(t) for t in plist])
-        gg = MdtaParams(*[_p(t) for t in grads])
-        ws = _workspace(dev, lib.dcpt_mdta_ws_bytes(B, H, W, Cc, ctx.heads, 1))
-        check(lib.dcpt_mdta_bwd(C.byref(pp), C.byref(gg), x.data_ptr(), C.byref(sv), dy.data_ptr(), dx.data_ptr(), ws.data_ptr(),
-                                ws.numel(), B, H, W, Cc, ctx.heads, int(ctx.biasfree), _stream(dev)), "dcpt_mdta_bwd")
-        return (dx, *grads, None, None)
-
-
-LN_BIASFREE, LN_EPS_1E5, ATTN_SOFTMAX = 1, 2, 4   # include/dcpt_hip.h: DCPT_LN_BIASFREE, DCPT_LN_EPS_1E5, DCPT_ATTN_SOFTMAX
-
-
-def mdta(x, norm_w, norm_b, qkv_w, dw_w, proj_w, temperature, heads, biasfree, eps_1e5=False, softmax=False):
-    """``eps_1e5`` / ``softmax``: the PromptIR variants (LayerNorm eps 1e-5, softmax instead of ReLU attention)."""
-    flags = (LN_BIASFREE if biasfree else 0) | (LN_EPS_1E5 if eps_1e5 else 0) | (ATTN_SOFTMAX if softmax else 0)
-    return _MDTAFn.apply(x, norm_w, norm_b, qkv_w, dw_w, proj_w, temperature, heads, flags)
-
-
-@_remember_gemm_mode
-class _GDFNFn(torch.autograd.Function):
-    """x + project_out(gelu(x1) * x2)  (restormer_arch.py:75-100, :158)."""
-
-    @staticmethod
-    def forward(ctx, x, norm_w, norm_b, in_w, dw_w, out_w, biasfree):
-        lib = _lib.load()
-        _require_gpu(x, norm_w, norm_b, in_w, dw_w, out_w)
-        x = _nhwc(x)
-        ps = [None if t is None else _contig(t.detach()) for t in (norm_w, norm_b, in_w, dw_w, out_w)]
-        B, Cc, H, W = x.shape
-        dev = x.device
-        M = B * H * W
-        hidden = ps[4].shape[1]
-        hp = (hidden + 3) // 4 * 4
-        y = _empty_nhwc(B, Cc, H, W, dev)
-        stats = torch.empty((2, M), dtype=torch.float32, device=dev)
-        full = _restormer_mode(dev) == "full"
-        u = _empty_nhwc(B, 2 * hp, H, W, dev)
-        t = _empty_nhwc(B, hp, H, W, dev) if full else None
-        xn = _empty_nhwc(B, Cc, H, W, dev) if full else None
-        sv = GdfnSaved(stats[0].data_ptr(), stats[1].data_ptr(), u.data_ptr(), _p(t), _p(xn))
-        pp = GdfnParams(*[_p(q) for q in ps])
-        ws = _workspace(dev, lib.dcpt_gdfn_ws_bytes(B, H, W, Cc, hidden, 0))
-        check(lib.dcpt_gdfn_fwd(C.byref(pp), x.data_ptr(), y.data_ptr(), C.byref(sv), ws.data_ptr(), ws.numel(), B, H, W, Cc,
-                                hidden, int(biasfree), _stream(dev)), "dcpt_gdfn_fwd")
-        ctx.full = full
-        ctx.save_for_backward(x, stats, u, *([t, xn] if full else []), *[q for q in ps if q is not None])
-        ctx.has_bias, ctx.biasfree, ctx.hidden = ps[1] is not None, int(biasfree), hidden
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        lib = _lib.load()
-        x, stats, u, *ps = ctx.saved_tensors
-        t = xn = None
-        if ctx.full:
-            t, xn, *ps = ps
-        if ctx.has_bias:
-            norm_w, norm_b, in_w, dw_w, out_w = ps
-        else:
-            norm_w, in_w, dw_w, out_w = ps
-            norm_b = None
-        dy = _nhwc(dy)
-        B, Cc, H, W = x.shape
-        dev = x.device
-        dx = _empty_nhwc(B, Cc, H, W, dev)
-        plist = [norm_w, norm_b, in_w, dw_w, out_w]
-        grads = [None if q is None else torch.empty_like(q) for q in plist]
-        sv = GdfnSaved(stats[0].data_ptr(), stats[1].data_ptr(), u.data_ptr(), _p(t), _p(xn))
-        pp = GdfnParams(*[_p(q) for q in plist])
-        gg = GdfnParams(*[_p(q) for q in grads])
-        ws = _workspace(dev, lib.dcpt_gdfn_ws_bytes(B, H, W, Cc, ctx.hidden, 1))
-        check(lib.dcpt_gdfn_bwd(C.byref(pp), C.byref(gg), x.data_ptr(), C.byref(sv), dy.data_ptr(), dx.data_ptr(), ws.data_ptr(),
-                                ws.numel(), B, H, W, Cc, ctx.hidden, int(ctx.biasfree), _stream(dev)), "dcpt_gdfn_bwd")
-        return (dx, *grads, None)
-
-
-def gdfn(x, norm_w, norm_b, in_w, dw_w, out_w, biasfree, eps_1e5=False):
-    flags = (LN_BIASFREE if biasfree else 0) | (LN_EPS_1E5 if eps_1e5 else 0)
-    return _GDFNFn.apply(x, norm_w, norm_b, in_w, dw_w, out_w, flags)
-
-
-# ------------------------------------------------------------------------------------------------
-# Restormer with bf16 activation storage (restormer_bf16.hip; Restormer / Restormer_origin with act_dtype="bf16"): the feature maps and
-# the tensors the halves keep are bf16, statistics / attention matrices / parameters / parameter gradients fp32.  The save modes keep
-# the same sets of tensors as the fp32 nodes above (bit-identical results in every mode).
-class _MDTABf16Fn(torch.autograd.Function):
-    """_MDTAFn with bf16 storage -> dcpt_mdta_bf16_fwd / _bwd."""
+    """x + project_out(attn(LN(x)))  (restormer_arch.py:103-145, :156-157) -> dcpt_mdta_fwd / _bwd or dcpt_mdta_bf16_fwd / _bwd."""
 
     @staticmethod
     def forward(ctx, x, norm_w, norm_b, qkv_w, dw_w, proj_w, temperature, heads, flags, train):
         lib = _lib.load()
-        _require_gpu_bf16(x)
+        _require_gpu_feat(x)
         _require_gpu(norm_w, norm_b, qkv_w, dw_w, proj_w, temperature)
         x = _nhwc(x)
+        bf = x.dtype == torch.bfloat16
         ps = [None if t is None else _contig(t.detach()) for t in (norm_w, norm_b, qkv_w, dw_w, proj_w, temperature)]
         B, Cc, H, W = x.shape
         dev = x.device
         M, ch = B * H * W, Cc // heads
-        nograd = not train
-        y = _empty_nhwc_bf16(B, Cc, H, W, dev)
+        nograd = bf and not train
+        y = (_empty_nhwc_bf16 if bf else _empty_nhwc)(B, Cc, H, W, dev)
         stats = torch.empty((2, M), dtype=torch.float32, device=dev)
         mode = "lean" if nograd else _restormer_mode(dev)
-        qkv1 = None if mode == "lean" else _empty_nhwc_bf16(B, 3 * Cc, H, W, dev)
-        qkv = _empty_nhwc_bf16(B, 3 * Cc, H, W, dev)
+        qkv1 = None if mode == "lean" else (_empty_nhwc_bf16 if bf else _empty_nhwc)(B, 3 * Cc, H, W, dev)
+        qkv = (_empty_nhwc_bf16 if bf else _empty_nhwc)(B, 3 * Cc, H, W, dev)
         nrm = torch.empty((B, 2 * Cc), dtype=torch.float32, device=dev)
         att = torch.empty((3, B, heads, ch, ch), dtype=torch.float32, device=dev)
-        out_att = None if mode != "full" else _empty_nhwc_bf16(B, Cc, H, W, dev)
-        xn = None if mode != "full" else _empty_nhwc_bf16(B, Cc, H, W, dev)
+        out_att = None if mode != "full" else (_empty_nhwc_bf16 if bf else _empty_nhwc)(B, Cc, H, W, dev)
+        xn = None if mode != "full" else (_empty_nhwc_bf16 if bf else _empty_nhwc)(B, Cc, H, W, dev)
         sv = MdtaSaved(stats[0].data_ptr(), stats[1].data_ptr(), _p(qkv1), qkv.data_ptr(), nrm.data_ptr(),
                        att[0].data_ptr(), att[1].data_ptr(), att[2].data_ptr(), _p(out_att), _p(xn))
         pp = MdtaParams(*[_p(t) for t in ps])
-        ws = _workspace(dev, lib.dcpt_mdta_bf16_ws_bytes(B, H, W, Cc, heads, 2 if mode == "full" else 0))
-        check(lib.dcpt_mdta_bf16_fwd(C.byref(pp), x.data_ptr(), y.data_ptr(), C.byref(sv), ws.data_ptr(), ws.numel(), B, H, W, Cc,
-                                     heads, int(flags), _stream(dev)), "dcpt_mdta_bf16_fwd")
+        if bf:
+            ws = _workspace(dev, lib.dcpt_mdta_bf16_ws_bytes(B, H, W, Cc, heads, 2 if mode == "full" else 0))
+        else:
+            ws = _workspace(dev, lib.dcpt_mdta_ws_bytes(B, H, W, Cc, heads, 0))
+        fn = lib.dcpt_mdta_bf16_fwd if bf else lib.dcpt_mdta_fwd
+        check(fn(C.byref(pp), x.data_ptr(), y.data_ptr(), C.byref(sv), ws.data_ptr(), ws.numel(), B, H, W, Cc, heads, int(flags),
+                 _stream(dev)), fn.__name__)
         ctx.heads, ctx.flags = heads, int(flags)
         ctx.has_bias = ps[1] is not None
         if nograd:   # nothing is kept for a backward pass that cannot happen
@@ -2087,21 +1836,30 @@ class _MDTABf16Fn(torch.autograd.Function):
         else:
             norm_w, qkv_w, dw_w, proj_w, temp = ps
             norm_b = None
-        _require_gpu_bf16(dy)
+        bf = x.dtype == torch.bfloat16
+        if bf:
+            _require_gpu_bf16(dy)
         dy = _nhwc(dy)
         B, Cc, H, W = x.shape
         dev = x.device
-        dx = _empty_nhwc_bf16(B, Cc, H, W, dev)
+        dx = (_empty_nhwc_bf16 if bf else _empty_nhwc)(B, Cc, H, W, dev)
         plist = [norm_w, norm_b, qkv_w, dw_w, proj_w, temp]
         grads = [None if t is None else torch.empty_like(t) for t in plist]
         sv = MdtaSaved(stats[0].data_ptr(), stats[1].data_ptr(), _p(qkv1), qkv.data_ptr(), nrm.data_ptr(),
                        att[0].data_ptr(), att[1].data_ptr(), att[2].data_ptr(), _p(out_att), _p(xn))
         pp = MdtaParams(*[_p(t) for t in plist])
         gg = MdtaParams(*[_p(t) for t in grads])
-        ws = _workspace(dev, lib.dcpt_mdta_bf16_ws_bytes(B, H, W, Cc, ctx.heads, 3 if all(ctx.kept) else 1))
-        check(lib.dcpt_mdta_bf16_bwd(C.byref(pp), C.byref(gg), x.data_ptr(), C.byref(sv), dy.data_ptr(), dx.data_ptr(), ws.data_ptr(),
-                                     ws.numel(), B, H, W, Cc, ctx.heads, ctx.flags, _stream(dev)), "dcpt_mdta_bf16_bwd")
+        if bf:
+            ws = _workspace(dev, lib.dcpt_mdta_bf16_ws_bytes(B, H, W, Cc, ctx.heads, 3 if all(ctx.kept) else 1))
+        else:
+            ws = _workspace(dev, lib.dcpt_mdta_ws_bytes(B, H, W, Cc, ctx.heads, 1))
+        fn = lib.dcpt_mdta_bf16_bwd if bf else lib.dcpt_mdta_bwd
+        check(fn(C.byref(pp), C.byref(gg), x.data_ptr(), C.byref(sv), dy.data_ptr(), dx.data_ptr(), ws.data_ptr(), ws.numel(), B, H, W,
+                 Cc, ctx.heads, ctx.flags, _stream(dev)), fn.__name__)
         return (dx, *grads, None, None, None)
+
+
+LN_BIASFREE, LN_EPS_1E5, ATTN_SOFTMAX = 1, 2, 4   # include/dcpt_hip.h: DCPT_LN_BIASFREE, DCPT_LN_EPS_1E5, DCPT_ATTN_SOFTMAX
 
 
 def _train(*ts) -> bool:
@@ -2109,40 +1867,48 @@ def _train(*ts) -> bool:
     return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in ts)
 
 
-def mdta_bf16(x, norm_w, norm_b, qkv_w, dw_w, proj_w, temperature, heads, biasfree, eps_1e5=False, softmax=False):
-    """mdta() with bf16 activation storage: x and the result are torch.bfloat16 NHWC maps."""
+def mdta(x, norm_w, norm_b, qkv_w, dw_w, proj_w, temperature, heads, biasfree, eps_1e5=False, softmax=False):
+    """``eps_1e5`` / ``softmax``: the PromptIR variants (LayerNorm eps 1e-5, softmax instead of ReLU attention).  x and the result are
+    fp32 or torch.bfloat16 NHWC maps (bf16 activation storage)."""
     flags = (LN_BIASFREE if biasfree else 0) | (LN_EPS_1E5 if eps_1e5 else 0) | (ATTN_SOFTMAX if softmax else 0)
     train = _train(x, norm_w, norm_b, qkv_w, dw_w, proj_w, temperature)
-    return _MDTABf16Fn.apply(x, norm_w, norm_b, qkv_w, dw_w, proj_w, temperature, heads, flags, train)
+    return _MDTAFn.apply(x, norm_w, norm_b, qkv_w, dw_w, proj_w, temperature, heads, flags, train)
 
 
-class _GDFNBf16Fn(torch.autograd.Function):
-    """_GDFNFn with bf16 storage -> dcpt_gdfn_bf16_fwd / _bwd (hidden padded to a multiple of 8)."""
+@_remember_gemm_mode_fp32
+class _GDFNFn(torch.autograd.Function):
+    """x + project_out(gelu(x1) * x2)  (restormer_arch.py:75-100, :158) -> dcpt_gdfn_fwd / _bwd (hidden padded to a multiple of 4) or
+    dcpt_gdfn_bf16_fwd / _bwd (to a multiple of 8)."""
 
     @staticmethod
     def forward(ctx, x, norm_w, norm_b, in_w, dw_w, out_w, flags, train):
         lib = _lib.load()
-        _require_gpu_bf16(x)
+        _require_gpu_feat(x)
         _require_gpu(norm_w, norm_b, in_w, dw_w, out_w)
         x = _nhwc(x)
+        bf = x.dtype == torch.bfloat16
         ps = [None if t is None else _contig(t.detach()) for t in (norm_w, norm_b, in_w, dw_w, out_w)]
         B, Cc, H, W = x.shape
         dev = x.device
         M = B * H * W
         hidden = ps[4].shape[1]
-        hp = (hidden + 7) // 8 * 8
-        nograd = not train
-        y = _empty_nhwc_bf16(B, Cc, H, W, dev)
+        hp = (hidden + 7) // 8 * 8 if bf else (hidden + 3) // 4 * 4
+        nograd = bf and not train
+        y = (_empty_nhwc_bf16 if bf else _empty_nhwc)(B, Cc, H, W, dev)
         stats = torch.empty((2, M), dtype=torch.float32, device=dev)
         full = not nograd and _restormer_mode(dev) == "full"
-        u = _empty_nhwc_bf16(B, 2 * hp, H, W, dev)
-        t = _empty_nhwc_bf16(B, hp, H, W, dev) if full else None
-        xn = _empty_nhwc_bf16(B, Cc, H, W, dev) if full else None
+        u = (_empty_nhwc_bf16 if bf else _empty_nhwc)(B, 2 * hp, H, W, dev)
+        t = (_empty_nhwc_bf16 if bf else _empty_nhwc)(B, hp, H, W, dev) if full else None
+        xn = (_empty_nhwc_bf16 if bf else _empty_nhwc)(B, Cc, H, W, dev) if full else None
         sv = GdfnSaved(stats[0].data_ptr(), stats[1].data_ptr(), u.data_ptr(), _p(t), _p(xn))
         pp = GdfnParams(*[_p(q) for q in ps])
-        ws = _workspace(dev, lib.dcpt_gdfn_bf16_ws_bytes(B, H, W, Cc, hidden, 2 if full else 0))
-        check(lib.dcpt_gdfn_bf16_fwd(C.byref(pp), x.data_ptr(), y.data_ptr(), C.byref(sv), ws.data_ptr(), ws.numel(), B, H, W, Cc,
-                                     hidden, int(flags), _stream(dev)), "dcpt_gdfn_bf16_fwd")
+        if bf:
+            ws = _workspace(dev, lib.dcpt_gdfn_bf16_ws_bytes(B, H, W, Cc, hidden, 2 if full else 0))
+        else:
+            ws = _workspace(dev, lib.dcpt_gdfn_ws_bytes(B, H, W, Cc, hidden, 0))
+        fn = lib.dcpt_gdfn_bf16_fwd if bf else lib.dcpt_gdfn_fwd
+        check(fn(C.byref(pp), x.data_ptr(), y.data_ptr(), C.byref(sv), ws.data_ptr(), ws.numel(), B, H, W, Cc, hidden, int(flags),
+                 _stream(dev)), fn.__name__)
         ctx.full = full
         ctx.has_bias, ctx.flags, ctx.hidden = ps[1] is not None, int(flags), hidden
         if nograd:
@@ -2162,128 +1928,53 @@ class _GDFNBf16Fn(torch.autograd.Function):
         else:
             norm_w, in_w, dw_w, out_w = ps
             norm_b = None
-        _require_gpu_bf16(dy)
+        bf = x.dtype == torch.bfloat16
+        if bf:
+            _require_gpu_bf16(dy)
         dy = _nhwc(dy)
         B, Cc, H, W = x.shape
         dev = x.device
-        dx = _empty_nhwc_bf16(B, Cc, H, W, dev)
+        dx = (_empty_nhwc_bf16 if bf else _empty_nhwc)(B, Cc, H, W, dev)
         plist = [norm_w, norm_b, in_w, dw_w, out_w]
         grads = [None if q is None else torch.empty_like(q) for q in plist]
         sv = GdfnSaved(stats[0].data_ptr(), stats[1].data_ptr(), u.data_ptr(), _p(t), _p(xn))
         pp = GdfnParams(*[_p(q) for q in plist])
         gg = GdfnParams(*[_p(q) for q in grads])
-        ws = _workspace(dev, lib.dcpt_gdfn_bf16_ws_bytes(B, H, W, Cc, ctx.hidden, 3 if ctx.full else 1))
-        check(lib.dcpt_gdfn_bf16_bwd(C.byref(pp), C.byref(gg), x.data_ptr(), C.byref(sv), dy.data_ptr(), dx.data_ptr(), ws.data_ptr(),
-                                     ws.numel(), B, H, W, Cc, ctx.hidden, ctx.flags, _stream(dev)), "dcpt_gdfn_bf16_bwd")
+        if bf:
+            ws = _workspace(dev, lib.dcpt_gdfn_bf16_ws_bytes(B, H, W, Cc, ctx.hidden, 3 if ctx.full else 1))
+        else:
+            ws = _workspace(dev, lib.dcpt_gdfn_ws_bytes(B, H, W, Cc, ctx.hidden, 1))
+        fn = lib.dcpt_gdfn_bf16_bwd if bf else lib.dcpt_gdfn_bwd
+        check(fn(C.byref(pp), C.byref(gg), x.data_ptr(), C.byref(sv), dy.data_ptr(), dx.data_ptr(), ws.data_ptr(), ws.numel(), B, H, W,
+                 Cc, ctx.hidden, ctx.flags, _stream(dev)), fn.__name__)
         return (dx, *grads, None, None)
 
 
-def gdfn_bf16(x, norm_w, norm_b, in_w, dw_w, out_w, biasfree, eps_1e5=False):
-    """gdfn() with bf16 activation storage."""
+def gdfn(x, norm_w, norm_b, in_w, dw_w, out_w, biasfree, eps_1e5=False):
     flags = (LN_BIASFREE if biasfree else 0) | (LN_EPS_1E5 if eps_1e5 else 0)
-    return _GDFNBf16Fn.apply(x, norm_w, norm_b, in_w, dw_w, out_w, flags, _train(x, norm_w, norm_b, in_w, dw_w, out_w))
+    return _GDFNFn.apply(x, norm_w, norm_b, in_w, dw_w, out_w, flags, _train(x, norm_w, norm_b, in_w, dw_w, out_w))
 
 
-class _ConvBf16Fn(torch.autograd.Function):
-    """_ConvFn with bf16 NHWC features (dcpt_conv_fwd_bf16 / _bwd_bf16); weight and its gradient fp32."""
-
-    @staticmethod
-    def forward(ctx, x, weight):
-        lib = _lib.load()
-        _require_gpu_bf16(x)
-        _require_gpu(weight)
-        x = _nhwc(x)
-        w_ = _contig(weight.detach())
-        B, Cin, H, W = x.shape
-        Cout, ks = w_.shape[0], w_.shape[2]
-        dev = x.device
-        y = _empty_nhwc_bf16(B, Cout, H, W, dev)
-        ws = _workspace(dev, lib.dcpt_conv_bf16_ws_bytes(B, H, W, Cin, Cout, ks, 0))
-        check(lib.dcpt_conv_fwd_bf16(x.data_ptr(), w_.data_ptr(), y.data_ptr(), ws.data_ptr(), ws.numel(), B, H, W, Cin, Cout, ks,
-                                     _stream(dev)), "dcpt_conv_fwd_bf16")
-        ctx.save_for_backward(x, w_)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        lib = _lib.load()
-        x, w_ = ctx.saved_tensors
-        _require_gpu_bf16(dy)
-        dy = _nhwc(dy)
-        B, Cin, H, W = x.shape
-        Cout, ks = w_.shape[0], w_.shape[2]
-        dev = x.device
-        dx = _empty_nhwc_bf16(B, Cin, H, W, dev)
-        dw = torch.empty_like(w_)
-        ws = _workspace(dev, lib.dcpt_conv_bf16_ws_bytes(B, H, W, Cin, Cout, ks, 1))
-        check(lib.dcpt_conv_bwd_bf16(dy.data_ptr(), x.data_ptr(), w_.data_ptr(), dx.data_ptr(), dw.data_ptr(), ws.data_ptr(),
-                                     ws.numel(), B, H, W, Cin, Cout, ks, _stream(dev)), "dcpt_conv_bwd_bf16")
-        return dx, dw
+def mdta_bf16(x, norm_w, norm_b, qkv_w, dw_w, proj_w, temperature, heads, biasfree, eps_1e5=False, softmax=False):
+    """mdta() for callers that mean bf16 activation storage: anything but a torch.bfloat16 x is an error."""
+    _require_gpu_bf16(x)
+    return mdta(x, norm_w, norm_b, qkv_w, dw_w, proj_w, temperature, heads, biasfree, eps_1e5, softmax)
 
 
-def _shuffle_bf16(lib, x, up):
-    x = _nhwc(x)
-    B, Cc, H, W = x.shape
-    if up:
-        y = _empty_nhwc_bf16(B, Cc // 4, 2 * H, 2 * W, x.device)
-        check(lib.dcpt_pixel_shuffle_bf16(x.data_ptr(), y.data_ptr(), B, H, W, Cc, _stream(x.device)), "dcpt_pixel_shuffle_bf16")
-    else:
-        y = _empty_nhwc_bf16(B, 4 * Cc, H // 2, W // 2, x.device)
-        check(lib.dcpt_pixel_unshuffle_bf16(x.data_ptr(), y.data_ptr(), B, H, W, Cc, _stream(x.device)), "dcpt_pixel_unshuffle_bf16")
-    return y
-
-
-class _PixelShuffleBf16Fn(torch.autograd.Function):
-    """PixelShuffle(2) (up) / PixelUnshuffle(2) on bf16 NHWC maps; the backward is the other one."""
-
-    @staticmethod
-    def forward(ctx, x, up):
-        _require_gpu_bf16(x)
-        ctx.up = bool(up)
-        return _shuffle_bf16(_lib.load(), x, ctx.up)
-
-    @staticmethod
-    def backward(ctx, dy):
-        _require_gpu_bf16(dy)
-        return _shuffle_bf16(_lib.load(), dy, not ctx.up), None
-
-
-class _ConcatBf16Fn(torch.autograd.Function):
-    """torch.cat([a, b], 1) on bf16 NHWC maps."""
-
-    @staticmethod
-    def forward(ctx, a, b):
-        lib = _lib.load()
-        _require_gpu_bf16(a, b)
-        a, b = _nhwc(a), _nhwc(b)
-        B, Ca, H, W = a.shape
-        Cb = b.shape[1]
-        out = _empty_nhwc_bf16(B, Ca + Cb, H, W, a.device)
-        check(lib.dcpt_concat_channels_bf16(a.data_ptr(), b.data_ptr(), out.data_ptr(), B * H * W, Ca, Cb, _stream(a.device)),
-              "dcpt_concat_channels_bf16")
-        ctx.dims = (Ca, Cb)
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        lib = _lib.load()
-        _require_gpu_bf16(dout)
-        dout = _nhwc(dout)
-        Ca, Cb = ctx.dims
-        B, _, H, W = dout.shape
-        da, db = _empty_nhwc_bf16(B, Ca, H, W, dout.device), _empty_nhwc_bf16(B, Cb, H, W, dout.device)
-        check(lib.dcpt_split_channels_bf16(dout.data_ptr(), da.data_ptr(), db.data_ptr(), B * H * W, Ca, Cb, _stream(dout.device)),
-              "dcpt_split_channels_bf16")
-        return da, db
+def gdfn_bf16(x, norm_w, norm_b, in_w, dw_w, out_w, biasfree, eps_1e5=False):
+    """gdfn() for callers that mean bf16 activation storage."""
+    _require_gpu_bf16(x)
+    return gdfn(x, norm_w, norm_b, in_w, dw_w, out_w, biasfree, eps_1e5)
 
 
 # ------------------------------------------------------------------------------------------------
 class _PromptMixFn(torch.autograd.Function):
     """bilinear_(H,W)( sum_l softmax(logits)[b, l] * prompt_param[l] ) as an NHWC map
-    (PromptGenBlock.forward, basicsr/archs/promptir_arch.py:253-259)."""
+    (PromptGenBlock.forward, basicsr/archs/promptir_arch.py:253-259).  ``out_bf16``: the map (and the dout that comes back) in bf16
+    storage (dcpt_prompt_mix_fwd_bf16 / _bwd_bf16); logits, softmax weights, prompt_param and their gradients are fp32 in both."""
 
     @staticmethod
-    def forward(ctx, logits, prompt_param, H, W):
+    def forward(ctx, logits, prompt_param, H, W, out_bf16):
         lib = _lib.load()
         _require_gpu(logits, prompt_param)
         lg, pp = _contig(logits.detach()), _contig(prompt_param.detach())
@@ -2292,12 +1983,13 @@ class _PromptMixFn(torch.autograd.Function):
         if L2 != L or S2 != S:
             raise ValueError(f"prompt_param {tuple(pp.shape)} does not match logits {tuple(lg.shape)}")
         dev = lg.device
+        bf = bool(out_bf16)
         wsm = torch.empty((B, L), dtype=torch.float32, device=dev)
-        out = _empty_nhwc(B, D, H, W, dev)
-        check(lib.dcpt_prompt_mix_fwd(lg.data_ptr(), pp.data_ptr(), wsm.data_ptr(), out.data_ptr(), B, L, D, S, H, W, _stream(dev)),
-              "dcpt_prompt_mix_fwd")
+        out = (_empty_nhwc_bf16 if bf else _empty_nhwc)(B, D, H, W, dev)
+        fn = lib.dcpt_prompt_mix_fwd_bf16 if bf else lib.dcpt_prompt_mix_fwd
+        check(fn(lg.data_ptr(), pp.data_ptr(), wsm.data_ptr(), out.data_ptr(), B, L, D, S, H, W, _stream(dev)), fn.__name__)
         ctx.save_for_backward(pp, wsm)
-        ctx.geom = (B, L, D, S, H, W)
+        ctx.geom, ctx.bf = (B, L, D, S, H, W), bf
         return out
 
     @staticmethod
@@ -2305,59 +1997,22 @@ class _PromptMixFn(torch.autograd.Function):
         lib = _lib.load()
         pp, wsm = ctx.saved_tensors
         B, L, D, S, H, W = ctx.geom
+        if ctx.bf:
+            _require_gpu_bf16(dout)
         dout = _nhwc(dout)
         dev = dout.device
         dlogits = torch.empty((B, L), dtype=torch.float32, device=dev)
         dparam = torch.empty_like(pp)
         ws = _workspace(dev, lib.dcpt_prompt_mix_bwd_ws_bytes(B, D, S))
-        check(lib.dcpt_prompt_mix_bwd(dout.data_ptr(), pp.data_ptr(), wsm.data_ptr(), dlogits.data_ptr(), dparam.data_ptr(),
-                                      ws.data_ptr(), ws.numel(), B, L, D, S, H, W, _stream(dev)), "dcpt_prompt_mix_bwd")
-        return dlogits, dparam, None, None
-
-
-class _PromptMixBf16Fn(torch.autograd.Function):
-    """_PromptMixFn with the NHWC map in bf16 storage (dcpt_prompt_mix_fwd_bf16 / _bwd_bf16); logits, softmax weights, prompt_param and
-    their gradients fp32."""
-
-    @staticmethod
-    def forward(ctx, logits, prompt_param, H, W):
-        lib = _lib.load()
-        _require_gpu(logits, prompt_param)
-        lg, pp = _contig(logits.detach()), _contig(prompt_param.detach())
-        B, L = lg.shape
-        _, L2, D, S, S2 = pp.shape
-        if L2 != L or S2 != S:
-            raise ValueError(f"prompt_param {tuple(pp.shape)} does not match logits {tuple(lg.shape)}")
-        dev = lg.device
-        wsm = torch.empty((B, L), dtype=torch.float32, device=dev)
-        out = _empty_nhwc_bf16(B, D, H, W, dev)
-        check(lib.dcpt_prompt_mix_fwd_bf16(lg.data_ptr(), pp.data_ptr(), wsm.data_ptr(), out.data_ptr(), B, L, D, S, H, W, _stream(dev)),
-              "dcpt_prompt_mix_fwd_bf16")
-        ctx.save_for_backward(pp, wsm)
-        ctx.geom = (B, L, D, S, H, W)
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        lib = _lib.load()
-        pp, wsm = ctx.saved_tensors
-        B, L, D, S, H, W = ctx.geom
-        _require_gpu_bf16(dout)
-        dout = _nhwc(dout)
-        dev = dout.device
-        dlogits = torch.empty((B, L), dtype=torch.float32, device=dev)
-        dparam = torch.empty_like(pp)
-        ws = _workspace(dev, lib.dcpt_prompt_mix_bwd_ws_bytes(B, D, S))
-        check(lib.dcpt_prompt_mix_bwd_bf16(dout.data_ptr(), pp.data_ptr(), wsm.data_ptr(), dlogits.data_ptr(), dparam.data_ptr(),
-                                           ws.data_ptr(), ws.numel(), B, L, D, S, H, W, _stream(dev)), "dcpt_prompt_mix_bwd_bf16")
-        return dlogits, dparam, None, None
+        fn = lib.dcpt_prompt_mix_bwd_bf16 if ctx.bf else lib.dcpt_prompt_mix_bwd
+        check(fn(dout.data_ptr(), pp.data_ptr(), wsm.data_ptr(), dlogits.data_ptr(), dparam.data_ptr(), ws.data_ptr(), ws.numel(),
+                 B, L, D, S, H, W, _stream(dev)), fn.__name__)
+        return dlogits, dparam, None, None, None
 
 
 def prompt_mix(logits, prompt_param, H, W, out_bf16=False):
     """``out_bf16``: the map in bf16 storage (PromptIR with act_dtype="bf16"), otherwise fp32."""
-    if out_bf16:
-        return _PromptMixBf16Fn.apply(logits, prompt_param, H, W)
-    return _PromptMixFn.apply(logits, prompt_param, H, W)
+    return _PromptMixFn.apply(logits, prompt_param, H, W, out_bf16)
 
 
 # ------------------------------------------------------------------------------------------------
