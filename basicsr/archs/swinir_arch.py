@@ -3,7 +3,10 @@
 Registry name ``SwinIR``, constructor kwargs, ``forward(x, hook=False)`` and ``state_dict`` keys / shapes as the reference's DCPT
 variant (basicsr/archs/swinir_arch.py): window attention WITHOUT relative-position bias and WITHOUT the shift mask (odd blocks
 still roll the map by -window_size // 2, so the edge windows wrap around unmasked), encoder RSTBs under ``encode_layers.{i}``
-and decoder RSTBs as attributes ``decode_layers{i}``, ``upsampler=''`` / ``upscale=1`` only.
+and decoder RSTBs as attributes ``decode_layers{i}``.  All four forms of the reference are built: restoration (``upsampler=''``),
+classical SR (``'pixelshuffle'``, upscale 2 / 3 / 4 / 8), lightweight SR (``'pixelshuffledirect'``, 2 / 3 / 4) and real-world SR
+(``'nearest+conv'``, 2 / 4), with ``resi_connection`` ``'1conv'`` or ``'3conv'`` (``embed_dim % 16 == 0``).  As in the reference, the
+three SR forms add no image residual and do not undo the input normalisation.
 
 Every Swin block is two autograd nodes: ``dcpt_swin_attn_*`` (LayerNorm in the qkv GEMM's operand loader -> window attention
 kernel on the un-shifted token rows -> proj GEMM + bias + residual) and ``dcpt_swin_mlp_*`` (LayerNorm -> fc1 -> erf GELU ->
@@ -76,19 +79,70 @@ class BasicLayer(nn.Module):
             for i in range(depth))
 
 
-class RSTB(nn.Module):
-    """residual Swin group: x + conv3x3(blocks(x)) + bias."""
+def _residual_conv(dim, resi_connection):
+    """the reference's ``conv`` / ``conv_after_body``: one 3x3 conv, or the 3conv bottleneck whose LeakyReLUs (indices 1, 3) own nothing"""
+    if resi_connection == "1conv":
+        return nn.Conv2d(dim, dim, 3, 1, 1)
+    return nn.Sequential(nn.Conv2d(dim, dim // 4, 3, 1, 1), nn.LeakyReLU(negative_slope=0.2, inplace=True),
+                         nn.Conv2d(dim // 4, dim // 4, 1, 1, 0), nn.LeakyReLU(negative_slope=0.2, inplace=True),
+                         nn.Conv2d(dim // 4, dim, 3, 1, 1))
 
-    def __init__(self, dim, input_resolution, depth, num_heads, window_size, mlp_ratio):
+
+def _apply_residual_conv(conv, t, res):
+    """res + conv(t) as one autograd node"""
+    if isinstance(conv, nn.Conv2d):
+        return DF.conv3x3_res(t, conv.weight, conv.bias, res)
+    return DF.conv3conv_res(t, conv[0].weight, conv[0].bias, conv[2].weight, conv[2].bias, conv[4].weight, conv[4].bias, res)
+
+
+class RSTB(nn.Module):
+    """residual Swin group: x + conv(blocks(x)), conv = one 3x3 conv or the 3conv bottleneck."""
+
+    def __init__(self, dim, input_resolution, depth, num_heads, window_size, mlp_ratio, resi_connection="1conv"):
         super().__init__()
         self.residual_group = BasicLayer(dim, input_resolution, depth, num_heads, window_size, mlp_ratio)
-        self.conv = nn.Conv2d(dim, dim, 3, 1, 1)
+        self.conv = _residual_conv(dim, resi_connection)
 
     def forward(self, x):
         t = x
         for blk in self.residual_group.blocks:
             t = blk(t)
-        return DF.conv3x3_res(t, self.conv.weight, self.conv.bias, x)
+        return _apply_residual_conv(self.conv, t, x)
+
+
+class Upsample(nn.Sequential):
+    """classical upsampler: (conv3x3 C -> 4C, PixelShuffle(2)) per factor of two, or one (conv3x3 C -> 9C, PixelShuffle(3)); the convs sit at
+    the even indices, as in the reference; each stage runs as one DF.conv3x3_ps node"""
+
+    def __init__(self, scale, num_feat):
+        m = []
+        if scale & (scale - 1) == 0:
+            for _ in range(scale.bit_length() - 1):
+                m += [nn.Conv2d(num_feat, 4 * num_feat, 3, 1, 1), nn.PixelShuffle(2)]
+        elif scale == 3:
+            m += [nn.Conv2d(num_feat, 9 * num_feat, 3, 1, 1), nn.PixelShuffle(3)]
+        else:
+            raise ValueError(f"scale {scale} is not supported. Supported scales: 2^n and 3.")
+        super().__init__(*m)
+
+    def forward(self, x):
+        for i in range(0, len(self), 2):
+            x = DF.conv3x3_ps(x, self[i].weight, self[i].bias, self[i + 1].upscale_factor)
+        return x
+
+
+class UpsampleOneStep(nn.Sequential):
+    """lightweight upsampler: conv3x3 C -> r^2 num_out_ch + PixelShuffle(r), written as the NCHW image by one DF.conv3x3_ps_out node"""
+
+    def __init__(self, scale, num_feat, num_out_ch):
+        super().__init__(nn.Conv2d(num_feat, scale * scale * num_out_ch, 3, 1, 1), nn.PixelShuffle(scale))
+
+    def forward(self, x):
+        return DF.conv3x3_ps_out(x, self[0].weight, self[0].bias, self[1].upscale_factor)
+
+
+SR_SCALES = {"pixelshuffle": (2, 3, 4, 8), "pixelshuffledirect": (2, 3, 4), "nearest+conv": (2, 4)}
+NUM_FEAT = 64   # the reference's fixed width of the reconstruction tail
 
 
 class PatchEmbed(nn.Module):
@@ -106,11 +160,22 @@ class SwinIR(nn.Module):
                  norm_layer=nn.LayerNorm, ape=False, patch_norm=True, use_checkpoint=False, upscale=1, img_range=1.0, upsampler="",
                  resi_connection="1conv", **kwargs):
         super().__init__()
-        if upsampler != "" or upscale != 1:
-            raise NotImplementedError(f"upsampler={upsampler!r} / upscale={upscale}: only the restoration form (upsampler '', upscale 1) "
-                                      "is on the DCPT path")
-        if resi_connection != "1conv":
-            raise NotImplementedError(f"resi_connection={resi_connection!r}: only '1conv' is on the DCPT path")
+        if upsampler == "":
+            if upscale != 1:
+                raise NotImplementedError(f"upscale={upscale} without an upsampler: the restoration form (upsampler '') has upscale 1")
+        elif upsampler not in SR_SCALES:
+            raise NotImplementedError(f"upsampler={upsampler!r}: one of '', 'pixelshuffle', 'pixelshuffledirect', 'nearest+conv'")
+        elif upscale not in SR_SCALES[upsampler]:
+            raise NotImplementedError(f"upsampler={upsampler!r} with upscale={upscale}: the DCPT path has upscale in {SR_SCALES[upsampler]}"
+                                      + (" (the reference silently builds x2 for any other value)" if upsampler == "nearest+conv" else ""))
+        if upsampler == "pixelshuffledirect" and in_chans > 4:
+            raise NotImplementedError(f"upsampler='pixelshuffledirect' with in_chans={in_chans}: at most 4 image channels")
+        if resi_connection not in ("1conv", "3conv"):
+            raise NotImplementedError(f"resi_connection={resi_connection!r}: '1conv' or '3conv'")
+        if resi_connection == "3conv" and embed_dim % 16:
+            raise NotImplementedError(f"resi_connection='3conv' with embed_dim={embed_dim}: the inner maps are embed_dim // 4 = {embed_dim // 4} "
+                                      "channels wide and the NHWC kernels work on float4 channel groups, so embed_dim must be a multiple "
+                                      "of 16 (the default width 180 is not; the published 3conv model is 240 wide)")
         if ape:
             raise NotImplementedError("ape=True (absolute position embedding) is not on the DCPT path")
         if drop_rate > 0 or attn_drop_rate > 0 or drop_path_rate > 0:
@@ -137,12 +202,28 @@ class SwinIR(nn.Module):
         self.patch_embed = PatchEmbed(embed_dim, patch_norm)
         half = self.num_layers // 2
         self.encode_layers = nn.ModuleList(
-            RSTB(embed_dim, res, depths[i], num_heads[i], window_size, mlp_ratio) for i in range(half))
+            RSTB(embed_dim, res, depths[i], num_heads[i], window_size, mlp_ratio, resi_connection) for i in range(half))
         for i in range(half):
-            setattr(self, f"decode_layers{i}", RSTB(embed_dim, res, depths[i + 3], num_heads[i + 3], window_size, mlp_ratio))
+            setattr(self, f"decode_layers{i}", RSTB(embed_dim, res, depths[i + 3], num_heads[i + 3], window_size, mlp_ratio, resi_connection))
         self.norm = nn.LayerNorm(embed_dim)
-        self.conv_after_body = nn.Conv2d(embed_dim, embed_dim, 3, 1, 1)
-        self.conv_last = nn.Conv2d(embed_dim, in_chans, 3, 1, 1)
+        self.conv_after_body = _residual_conv(embed_dim, resi_connection)
+        # reconstruction (reference :981-1011; num_feat = 64 and num_out_ch = in_chans are fixed there)
+        if upsampler == "pixelshuffle":
+            self.conv_before_upsample = nn.Sequential(nn.Conv2d(embed_dim, NUM_FEAT, 3, 1, 1), nn.LeakyReLU(inplace=True))
+            self.upsample = Upsample(upscale, NUM_FEAT)
+            self.conv_last = nn.Conv2d(NUM_FEAT, in_chans, 3, 1, 1)
+        elif upsampler == "pixelshuffledirect":
+            self.upsample = UpsampleOneStep(upscale, embed_dim, in_chans)
+        elif upsampler == "nearest+conv":
+            self.conv_before_upsample = nn.Sequential(nn.Conv2d(embed_dim, NUM_FEAT, 3, 1, 1), nn.LeakyReLU(inplace=True))
+            self.conv_up1 = nn.Conv2d(NUM_FEAT, NUM_FEAT, 3, 1, 1)
+            if upscale == 4:
+                self.conv_up2 = nn.Conv2d(NUM_FEAT, NUM_FEAT, 3, 1, 1)
+            self.conv_hr = nn.Conv2d(NUM_FEAT, NUM_FEAT, 3, 1, 1)
+            self.conv_last = nn.Conv2d(NUM_FEAT, in_chans, 3, 1, 1)
+            self.lrelu = nn.LeakyReLU(negative_slope=0.2, inplace=True)
+        else:
+            self.conv_last = nn.Conv2d(embed_dim, in_chans, 3, 1, 1)
         self.apply(self._init_weights)
 
     @staticmethod
@@ -175,6 +256,21 @@ class SwinIR(nn.Module):
         for layer in self.layers():
             t = layer(t)
         t = DF.layernorm2d(t, self.norm.weight, self.norm.bias, LN_EPS)
-        res = DF.conv3x3_res(t, self.conv_after_body.weight, self.conv_after_body.bias, x_first)
-        out = DF.conv3x3_out(res, self.conv_last.weight, self.conv_last.bias, xn)
-        return DF.img_affine(out, mean, self.img_range, 1)
+        res = _apply_residual_conv(self.conv_after_body, t, x_first)
+        if self.upsampler == "":
+            out = DF.conv3x3_out(res, self.conv_last.weight, self.conv_last.bias, xn)
+            return DF.img_affine(out, mean, self.img_range, 1)
+        # the SR branches (reference :1069-1100) add no image residual and leave the output in the normalised range
+        if self.upsampler == "pixelshuffledirect":
+            return self.upsample(res)
+        cb = self.conv_before_upsample[0]
+        t = DF.conv3x3_act(res, cb.weight, cb.bias, self.conv_before_upsample[1].negative_slope)
+        if self.upsampler == "pixelshuffle":
+            t = self.upsample(t)
+        else:
+            slope = self.lrelu.negative_slope
+            t = DF.up2_conv3x3_act(t, self.conv_up1.weight, self.conv_up1.bias, slope)
+            if self.upscale == 4:
+                t = DF.up2_conv3x3_act(t, self.conv_up2.weight, self.conv_up2.bias, slope)
+            t = DF.conv3x3_act(t, self.conv_hr.weight, self.conv_hr.bias, slope)
+        return DF.conv3x3_out(t, self.conv_last.weight, self.conv_last.bias)

@@ -132,16 +132,41 @@ def swinir_fwd_flops_per_pixel(embed_dim=180, depths=(6,) * 6, mlp_ratio=2.0, wi
     return blocks + convs
 
 
-def run_swinir(dev, steps=5, warmup=2, B=8, S=256, train_batches=(12, 8, 4, 2, 1)):
+def swinir_sr_tail_macs_per_lr_pixel(upsampler, upscale, embed_dim=180, in_chans=3, num_feat=64):
+    """forward MACs per LR pixel of everything after conv_after_body, each 3 x 3 conv at its own resolution (classical x4 at width 180:
+    103 680 + 147 456 + 589 824 + 27 648 = 868 608; nearest+conv x4: 103 680 + 147 456 + 589 824 + 589 824 + 27 648 = 1 458 432)"""
+    C, F, r = embed_dim, num_feat, upscale
+    if upsampler == "":
+        return 9 * C * in_chans
+    if upsampler == "pixelshuffledirect":
+        return 9 * C * r * r * in_chans
+    macs, area = 9 * C * F, 1
+    if upsampler == "pixelshuffle":
+        for s in ([2] * (r.bit_length() - 1) if r & (r - 1) == 0 else [3]):
+            macs += area * 9 * F * s * s * F
+            area *= s * s
+    else:
+        for _ in range(r.bit_length() - 1):   # conv_up1 (, conv_up2) on the up-sampled grids
+            area *= 4
+            macs += area * 9 * F * F
+        macs += area * 9 * F * F              # conv_hr
+    return macs + area * 9 * F * in_chans
+
+
+def run_swinir(dev, steps=5, warmup=2, B=8, S=256, train_batches=(12, 8, 4, 2, 1), upsampler="", upscale=1):
     """the 5D SwinIR (options/all_in_one/test/test_SwinIR_5d.yml) at S x S: inference at batch B, and one training step (fwd + L1 + bwd + AdamW)
-    at the largest batch of ``train_batches`` that fits in device memory; rates against the fp32-MFMA roof"""
+    at the largest batch of ``train_batches`` that fits in device memory; rates against the fp32-MFMA roof.  With ``upsampler`` / ``upscale``:
+    the same body with that super-resolution tail, S x S the LR size; FLOPs per LR pixel = the body's count with the restoration form's
+    conv_last replaced by the tail's"""
     from basicsr.archs import build_network
     from dcpt_amd.keyed_init import fill_module_
     from dcpt_amd.optim import FusedAdamW
 
     g = torch.Generator(device=dev).manual_seed(1234)
-    net = fill_module_(build_network(dict(type="SwinIR", **SWINIR_5D))).to(dev)
-    fpp = swinir_fwd_flops_per_pixel(**SWINIR_5D)
+    cfg = dict(SWINIR_5D, upsampler=upsampler, upscale=upscale)
+    net = fill_module_(build_network(dict(type="SwinIR", **cfg))).to(dev)
+    tail = 2 * swinir_sr_tail_macs_per_lr_pixel(upsampler, upscale, cfg["embed_dim"])
+    fpp = swinir_fwd_flops_per_pixel(**SWINIR_5D) - 2 * swinir_sr_tail_macs_per_lr_pixel("", 1, cfg["embed_dim"]) + tail
     x = torch.rand((B, 3, S, S), generator=g, device=dev)
 
     def infer():
@@ -152,14 +177,17 @@ def run_swinir(dev, steps=5, warmup=2, B=8, S=256, train_batches=(12, 8, 4, 2, 1
     del x
     torch.cuda.empty_cache()
     optm = FusedAdamW(net.parameters(), lr=1e-4)
-    res = dict(workload=f"SwinIR 5D (embed 180, depths [6]*6, heads [6]*6, ws 8, mlp 2), {S}x{S}, fp32",
+    form = f" + {upsampler} x{upscale}, LR" if upsampler else ","
+    res = dict(workload=f"SwinIR 5D (embed 180, depths [6]*6, heads [6]*6, ws 8, mlp 2){form} {S}x{S}, fp32",
                fwd_gflop_per_image=round(fpp * S * S / 1e9, 1), infer_batch=B, infer_ms_per_batch=round(dt_inf * 1e3, 2),
                infer_tflops=round(fpp * S * S * B / dt_inf / 1e12, 2), infer_mfma_frac=round(fpp * S * S * B / dt_inf / 157.3e12, 4),
                infer_roof_ms=round(fpp * S * S * B / 157.3e12 * 1e3, 1), steps=steps, warmup=warmup)
+    if upsampler:
+        res.update(tail_mmac_per_lr_pixel=round(tail / 2e6, 6), tail_flop_share=round(tail / fpp, 4))
     for tb in train_batches:
         try:
             lq = torch.rand((tb, 3, S, S), generator=g, device=dev)
-            gt = torch.rand((tb, 3, S, S), generator=g, device=dev)
+            gt = torch.rand((tb, 3, upscale * S, upscale * S), generator=g, device=dev)
 
             def step():
                 optm.zero_grad(set_to_none=True)
@@ -275,6 +303,8 @@ def main():
     ap.add_argument("--restormer-save", default="balanced", choices=["auto", "lean", "balanced", "full"], help="what the Restormer halves keep for backward")
     ap.add_argument("--optimizer", default="dcpt", choices=["dcpt", "torch"], help="A/B: torch = torch.optim.AdamW(fused=True) instead of dcpt_amd.optim.FusedAdamW")
     ap.add_argument("--two-pass", action="store_true", help="dcpt A/B: train.batched_encoder_passes false (the reference's two encoder passes, B each, instead of one pass over 2B)")
+    ap.add_argument("--upsampler", default="", choices=["", "pixelshuffle", "pixelshuffledirect", "nearest+conv"], help="swinir: super-resolution tail")
+    ap.add_argument("--upscale", type=int, default=1, help="swinir: scale of --upsampler")
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--tile-streams", type=int, default=2, help="infer2k: HIP streams the tile batches run on (tile.streams)")
@@ -402,7 +432,11 @@ def main():
             raise SystemExit("--workload promptir: --dtype fp32 or bf16")
         res = run_promptir(dev, args.restormer_save, args.steps, args.warmup, args.batch or 32, args.size or 128, dtype=args.dtype)
     elif args.workload == "swinir":
-        res = run_swinir(dev, args.steps, args.warmup, args.batch or 8, args.size or 256)
+        if (args.upsampler == "") != (args.upscale == 1):
+            raise SystemExit("--upsampler and --upscale go together (an upsampler needs a scale above 1)")
+        sr = args.upsampler != ""   # the SR forms are measured at 64 x 64 LR, training at the inference batch first
+        res = run_swinir(dev, args.steps, args.warmup, args.batch or 8, args.size or (64 if sr else 256),
+                         train_batches=(args.batch or 8, 4, 2, 1) if sr else (12, 8, 4, 2, 1), upsampler=args.upsampler, upscale=args.upscale)
     elif args.workload == "rcan":
         lines = run_rcan(dev, args.steps, args.warmup, args.batch or 16, args.size or 48)
         for line in lines[:-1]:

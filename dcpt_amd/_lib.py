@@ -101,6 +101,10 @@ class RcabSaved(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in RCAB_SAVED_FIELDS]
 
 
+class Conv3convParams(C.Structure):   # dcpt_conv3conv_params (and, with writable pointers, dcpt_conv3conv_params_grads)
+    _fields_ = [(n, C.c_void_p) for n in ("conv1_w", "conv1_b", "conv2_w", "conv2_b", "conv3_w", "conv3_b")]
+
+
 class BneckGroup(C.Structure):   # dcpt_bneck_group_t: one conv -> LayerNorm group of the classifier head's BottleneckBlock
     _fields_ = [("w", C.c_void_p), ("wpacked", C.c_void_p), ("wpacked_bytes", C.c_size_t), ("lnw", C.c_void_p), ("lnb", C.c_void_p),
                 ("z", C.c_void_p), ("y", C.c_void_p), ("mu", C.c_void_p), ("rstd", C.c_void_p), ("dw", C.c_void_p), ("dlnw", C.c_void_p),
@@ -270,6 +274,22 @@ SIGNATURES = {
     "dcpt_conv3x3_ps_ws_bytes": (sz, [cint, cint, cint, cint, cint, cint]),
     "dcpt_conv3x3_ps_fwd": (cint, [f32p, f32p, f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint, cint, stream_t]),
     "dcpt_conv3x3_ps_bwd": (cint, [f32p, f32p, f32p, f32p, f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint, cint, stream_t]),
+    "dcpt_conv3x3_act_ws_bytes": (sz, [cint, cint, cint, cint, cint, cint]),
+    "dcpt_conv3x3_act_fwd": (cint, [f32p, f32p, f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint, cint, C.c_float, stream_t]),
+    "dcpt_conv3x3_act_bwd": (cint, [f32p, f32p, f32p, f32p, f32p, f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint, cint, C.c_float,
+                                    stream_t]),
+    "dcpt_up2_conv3x3_act_ws_bytes": (sz, [cint, cint, cint, cint, cint]),
+    "dcpt_up2_conv3x3_act_fwd": (cint, [f32p, f32p, f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint, C.c_float, stream_t]),
+    "dcpt_up2_conv3x3_act_bwd": (cint, [f32p, f32p, f32p, f32p, f32p, f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint, C.c_float,
+                                        stream_t]),
+    "dcpt_conv3x3_ps_out_ws_bytes": (sz, [cint, cint, cint, cint, cint, cint, cint]),
+    "dcpt_conv3x3_ps_out_fwd": (cint, [f32p, f32p, f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint, cint, cint, stream_t]),
+    "dcpt_conv3x3_ps_out_bwd": (cint, [f32p, f32p, f32p, f32p, f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint, cint, cint, stream_t]),
+    "dcpt_conv3conv_res_ws_bytes": (sz, [cint, cint, cint, cint, cint]),
+    "dcpt_conv3conv_res_fwd": (cint, [C.POINTER(Conv3convParams), f32p, f32p, f32p, f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint,
+                                      stream_t]),
+    "dcpt_conv3conv_res_bwd": (cint, [C.POINTER(Conv3convParams), C.POINTER(Conv3convParams), f32p, f32p, f32p, f32p, f32p, C.c_void_p, sz,
+                                      cint, cint, cint, cint, stream_t]),
     "dcpt_prompt_mix_fwd": (cint, [f32p, f32p, f32p, f32p, cint, cint, cint, cint, cint, cint, stream_t]),
     "dcpt_prompt_mix_bwd_ws_bytes": (sz, [cint, cint, cint]),
     "dcpt_prompt_mix_bwd": (cint, [f32p, f32p, f32p, f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint, cint, cint, stream_t]),

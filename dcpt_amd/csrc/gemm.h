@@ -8,8 +8,8 @@
 #pragma once
 #include "dcpt_common.h"
 
-enum GemmALoad { A_PLAIN = 0, A_LN = 1, A_SCALE = 2, A_SG = 3, A_GATHER = 4, A_CONV3 = 5, A_LNBF = 6 };
-enum GemmEpi { E_PLAIN = 0, E_BIAS = 1, E_RESID = 2, E_SGBWD = 3, E_SCATTER = 4, E_SCATTER_ADD = 5, E_ADDSCALED = 6, E_MUL = 7, E_BIASGATE = 8, E_DOTCOL = 9, E_LNBWD = 10, E_RESIDLN = 11, E_LNBWD2 = 12, E_RELU = 13, E_BIASCOL = 14, E_PSHUF = 15 };
+enum GemmALoad { A_PLAIN = 0, A_LN = 1, A_SCALE = 2, A_SG = 3, A_GATHER = 4, A_CONV3 = 5, A_LNBF = 6, A_CONV3UP = 7 };
+enum GemmEpi { E_PLAIN = 0, E_BIAS = 1, E_RESID = 2, E_SGBWD = 3, E_SCATTER = 4, E_SCATTER_ADD = 5, E_ADDSCALED = 6, E_MUL = 7, E_BIASGATE = 8, E_DOTCOL = 9, E_LNBWD = 10, E_RESIDLN = 11, E_LNBWD2 = 12, E_RELU = 13, E_BIASCOL = 14, E_PSHUF = 15, E_LRELU = 16 };
 
 struct GemmNT {
     const float* A;   // [M][lda]   (A_SG: 2K columns; A_GATHER: fine NHWC image, see g*)
@@ -30,6 +30,9 @@ struct GemmNT {
     // column index = (2*i + j) * gC + ch  <->  fine pixel (2h+i, 2w+j), channel ch
     // A_CONV3 (implicit GEMM of a dense 3x3, zero pad 1): image gH x gW with gC channels, K = 9*gC,
     // column index = tap * gC + ch, tap = 3*ky + kx  <->  pixel (h+ky-1, w+kx-1)
+    // A_CONV3UP: the same 3x3 over the nearest-neighbour 2x up-sampling of a gH x gW image, which is never materialised: the rows are
+    // the pixels of the 2gH x 2gW grid (M = B*2gH*2gW), tap pixel (h', w') of that grid (zero padding applied there) reads source
+    // pixel (h' >> 1, w' >> 1)
     int gH, gW, gC;
     // epilogues
     const float* bias;    // [N] (may be null)
@@ -68,6 +71,9 @@ struct GemmNT {
     // E_PSHUF: C = acc + bias written through PixelShuffle(psr) into the fine NHWC image [B][psr gH][psr gW][gC]: column
     //   (i psr + j) gC + ch <-> fine pixel (psr h + i, psr w + j), channel ch (the caller orders the weight rows to match)
     int psr;
+    // E_LRELU: C = lrelu(acc + bias, slope); with res (a LeakyReLU output of the same shape, slope > 0) its backward
+    //   C = (res > 0 ? 1 : slope) * (acc + bias)   (res == 0 takes the slope branch, as torch does)
+    float slope;
     // batching: grid.y = nb1*nb2 problems; pointer offsets b1*s?1 + b2*s?2 (elements)
     int nb1, nb2;
     int64_t sA1, sA2, sB1, sB2, sC1, sC2, sR1, sR2, sS1, sS2;

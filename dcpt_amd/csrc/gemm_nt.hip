@@ -53,7 +53,7 @@ template <int BM, int BN, int WM, int WN, int AK, int EK, int BK>
 __global__ __launch_bounds__(WM * WN * 64) void gemm_nt_kernel(const GemmNT pin) {
     static_assert(BK == 32 && WM * WN == 4, "32-deep k-tiles, 4 waves");
     constexpr int NTHR = 256;
-    constexpr bool A_DMA = (AK == A_PLAIN || AK == A_GATHER || AK == A_CONV3);  // pure data movement
+    constexpr bool A_DMA = (AK == A_PLAIN || AK == A_GATHER || AK == A_CONV3 || AK == A_CONV3UP);  // pure data movement
     GemmNT p = pin;
     TL_STAMP(0) TL_HWID()
     int lin, batch;
@@ -296,6 +296,11 @@ int launch_gemm_nt(const GemmNT& pin, int aload, int epi, hipStream_t s) {
                            2.0 * p.psr * p.gH * p.psr * p.gW * (double)p.gC * 4.0 < (double)WIN_BYTES,
                        "gemm_nt: pixel-shuffle epilogue needs N == psr^2 gC, gC %% 4 == 0 and a fine image below 512 MB");
     if (aload == A_CONV3) DCPT_CHECK_ARG(p.gC % 4 == 0 && p.K == 9 * p.gC, "gemm_nt: conv3 needs K == 9*gC, gC %% 4 == 0");
+    if (aload == A_CONV3UP)
+        DCPT_CHECK_ARG(p.gC % 4 == 0 && p.K == 9 * p.gC && p.gH > 0 && p.gW > 0 && p.M % (4 * (int64_t)p.gH * p.gW) == 0 &&
+                           (double)p.gH * p.gW * p.gC * 4.0 < 1.0e9,
+                       "gemm_nt: up-sampled conv3 needs K == 9*gC, gC %% 4 == 0, M == B*2gH*2gW and a source image below 1 GB");
+    if (epi == E_LRELU) DCPT_CHECK_ARG(p.nb1 * p.nb2 == 1 && (!p.res || p.slope > 0.f), "gemm_nt: LeakyReLU backward needs slope > 0");
     // algorithmic work of this launch (for the live roofline in bench.py)
     const double mn = (double)p.M * p.N, mk = (double)p.M * p.K;
     double bytes = mk * (aload == A_SG ? 2 : 1) + mn * (epi == E_SGBWD ? 4 : epi == E_BIASGATE ? 1.5 : 1) + (double)p.N * p.K;
@@ -307,7 +312,8 @@ int launch_gemm_nt(const GemmNT& pin, int aload, int epi, hipStream_t s) {
     if (epi == E_SGBWD && p.rowpart) DCPT_CHECK_ARG(p.uvec && p.cvec, "gemm_nt: SimpleGate-backward row partials need uvec / cvec");
     if (epi == E_RESIDLN) bytes += 2 * mn;
     const double nbat = (double)((p.nb1 > 0 ? p.nb1 : 1) * (p.nb2 > 0 ? p.nb2 : 1));
-    ProfScope prof(s, PROF_NT + aload * 16 + epi, p.M, p.N, p.K, 2.0 * mn * p.K * nbat, bytes * 4.0 * nbat);
+    ProfScope prof(s, PROF_NT + aload * 16 + (epi == E_LRELU ? (int)E_RELU : epi),   // (16 epilogue ids per loader: LeakyReLU shares ReLU's)
+                    p.M, p.N, p.K, 2.0 * mn * p.K * nbat, bytes * 4.0 * nbat);
     if (gemm_nt_x3_ok(p, aload, epi)) return launch_gemm_nt_x3(p, aload, epi, s);   // (opt-in mode; off unless dcpt_set_gemm_x3 was called)
 #define CASE(AK, EK) \
     if (aload == AK && epi == EK) return launch_cfg<AK, EK>(p, s);
@@ -325,6 +331,9 @@ int launch_gemm_nt(const GemmNT& pin, int aload, int epi, hipStream_t s) {
     CASE(A_CONV3, E_RESID)
     CASE(A_CONV3, E_RELU)
     CASE(A_CONV3, E_BIASCOL)
+    CASE(A_CONV3, E_LRELU)
+    CASE(A_CONV3UP, E_LRELU)
+    CASE(A_PLAIN, E_LRELU)
     CASE(A_CONV3, E_PSHUF)
     CASE(A_LNBF, E_PLAIN)
     CASE(A_LN, E_PLAIN)

@@ -63,7 +63,7 @@ __device__ __forceinline__ void epilogue_rows(const GemmNT& p, const float* __re
     const int n = n0 + 4 * q;
     const bool nok = (QP == Q || q < Q) && n < p.N;
     float4 bias = f4_zero(), cs = make_float4(1.f, 1.f, 1.f, 1.f);
-    if constexpr (EK == E_BIAS || EK == E_RESID || EK == E_MUL || EK == E_RESIDLN || EK == E_RELU || EK == E_BIASCOL || EK == E_PSHUF) {
+    if constexpr (EK == E_BIAS || EK == E_RESID || EK == E_MUL || EK == E_RESIDLN || EK == E_RELU || EK == E_BIASCOL || EK == E_PSHUF || EK == E_LRELU) {
         if (p.bias && nok) bias = ldg4(p.bias + n);
     }
     if constexpr (EK == E_RESID || EK == E_ADDSCALED || EK == E_RESIDLN) {
@@ -91,7 +91,7 @@ __device__ __forceinline__ void epilogue_rows(const GemmNT& p, const float* __re
     if constexpr (EK == E_RESIDLN) rsX = make_rsrc(p.ln_out + m0 * (int64_t)p.ldc);
     if constexpr (EK == E_LNBWD || EK == E_LNBWD2) rsX = make_rsrc((p.aux ? p.aux : p.res) + m0 * (int64_t)ldres);
     if constexpr (EK == E_SCATTER_ADD) rsR = make_rsrc(p.res + cbase);
-    if constexpr (EK == E_RELU) {
+    if constexpr (EK == E_RELU || EK == E_LRELU) {
         if (p.res) rsR = make_rsrc(p.res + m0 * (int64_t)ldres);
     }
     if constexpr (EK == E_SGBWD) rsX = make_rsrc(p.aux + m0 * (2 * (int64_t)p.N));
@@ -134,7 +134,7 @@ __device__ __forceinline__ void epilogue_rows(const GemmNT& p, const float* __re
                 addr[it] = ok ? (uint32_t)rl * (uint32_t)p.ldc * 4u + coladd : ROW_SENT;
                 if constexpr (EK == E_RESID || EK == E_ADDSCALED || EK == E_MUL || EK == E_DOTCOL || EK == E_LNBWD || EK == E_RESIDLN || EK == E_LNBWD2)
                     pre1[it] = buf_ld4(rsR, ok ? (uint32_t)rl * (uint32_t)ldres * 4u + coladd : ROW_SENT);
-                if constexpr (EK == E_RELU) {
+                if constexpr (EK == E_RELU || EK == E_LRELU) {
                     if (p.res) pre1[it] = buf_ld4(rsR, ok ? (uint32_t)rl * (uint32_t)ldres * 4u + coladd : ROW_SENT);
                 }
                 if constexpr (EK == E_LNBWD || EK == E_LNBWD2) {
@@ -224,6 +224,12 @@ __device__ __forceinline__ void epilogue_rows(const GemmNT& p, const float* __re
                 const float4 u = f4_add(v, bias);
                 const float4 g = p.res ? pre1[it] : u;   // forward: the value itself; backward: the saved ReLU output
                 buf_st4(rsC, addr[it], make_float4(g.x > 0.f ? u.x : 0.f, g.y > 0.f ? u.y : 0.f, g.z > 0.f ? u.z : 0.f, g.w > 0.f ? u.w : 0.f));
+            } else if constexpr (EK == E_LRELU) {
+                const float4 u = f4_add(v, bias);
+                const float4 g = p.res ? pre1[it] : u;   // forward: the value itself; backward: the saved LeakyReLU output
+                const float sl = p.slope;
+                buf_st4(rsC, addr[it], make_float4(g.x > 0.f ? u.x : sl * u.x, g.y > 0.f ? u.y : sl * u.y, g.z > 0.f ? u.z : sl * u.z,
+                                                   g.w > 0.f ? u.w : sl * u.w));
             } else if constexpr (EK == E_RESID) {
                 buf_st4(rsC, addr[it], f4_fma(f4_add(v, bias), cs, pre1[it]));
             } else if constexpr (EK == E_ADDSCALED) {

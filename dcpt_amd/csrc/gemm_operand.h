@@ -47,6 +47,12 @@ __device__ __forceinline__ int64_t row_elem(const Operand& o, int64_t m) {
         return ((b * (2 * o.gH) + 2 * h) * (int64_t)(2 * o.gW) + 2 * w) * o.gC;
     } else if constexpr (KIND == A_CONV3) {
         return m * (int64_t)o.gC;
+    } else if constexpr (KIND == A_CONV3UP) {   // source pixel under row m of the 2gH x 2gW grid
+        const int w2 = (int)(m % (2 * o.gW));
+        const int64_t t = m / (2 * o.gW);
+        const int h2 = (int)(t % (2 * o.gH));
+        const int64_t b = t / (2 * o.gH);
+        return ((b * o.gH + (h2 >> 1)) * (int64_t)o.gW + (w2 >> 1)) * o.gC;
     } else {
         return m * (int64_t)o.ld;
     }
@@ -56,7 +62,9 @@ __device__ __forceinline__ int64_t row_elem(const Operand& o, int64_t m) {
 template <int KIND>
 __device__ __forceinline__ void open_window(Operand& o, int64_t m_first) {
     int64_t base = row_elem<KIND>(o, m_first);
-    if constexpr (KIND == A_CONV3) {  // taps reach one image row + one pixel back
+    // A_CONV3UP: a later row of the tile sits on the same or a later fine row, so no tap reaches below source row
+    // (h' >> 1) - 1 of the first row either
+    if constexpr (KIND == A_CONV3 || KIND == A_CONV3UP) {  // taps reach one image row + one pixel back
         base -= (int64_t)(o.gW + 1) * o.gC;
         if (base < 0) base = 0;
     }
@@ -80,6 +88,15 @@ __device__ __forceinline__ void make_row(const Operand& o, int64_t m, RowCtx& rc
         rc.w = (int)(mm % o.gW);
         rc.h = (int)((mm / o.gW) % o.gH);
     }
+    if constexpr (KIND == A_CONV3UP) {
+        // off = first element of the row's IMAGE relative to the window (may lie before it: the unsigned sum with a tap's pixel
+        // offset in elem_voff is exact mod 2^32, and every tap that passes the range test lies inside the window);
+        // h, w = coordinates on the 2gH x 2gW grid, pushed out of range for a row past M so that every tap is dropped
+        const int64_t t = mm / (2 * o.gW);
+        rc.w = (int)(mm % (2 * o.gW));
+        rc.h = valid ? (int)(t % (2 * o.gH)) : -8;
+        rc.off = (uint32_t)(((t / (2 * o.gH)) * o.gH * (int64_t)o.gW * o.gC - o.base) * 4);
+    }
     if constexpr (KIND == A_LN) {
         rc.mu = o.mu[mm];
         rc.rstd = o.rstd[mm];
@@ -100,6 +117,13 @@ __device__ __forceinline__ uint32_t elem_voff(const Operand& o, const RowCtx& rc
         const int hh = rc.h + ky - 1, ww = rc.w + kx - 1;
         ok = ok && hh >= 0 && hh < o.gH && ww >= 0 && ww < o.gW;
         v = rc.off + (uint32_t)((((ky - 1) * o.gW + (kx - 1)) * o.gC + ch) * 4);
+    } else if constexpr (KIND == A_CONV3UP) {
+        const int tap = c / o.gC;
+        const int ch = c - tap * o.gC;
+        const int ky = tap / 3, kx = tap - 3 * ky;
+        const int hh = rc.h + ky - 1, ww = rc.w + kx - 1;
+        ok = ok && hh >= 0 && hh < 2 * o.gH && ww >= 0 && ww < 2 * o.gW;
+        v = rc.off + (uint32_t)((((hh >> 1) * o.gW + (ww >> 1)) * o.gC + ch) * 4);
     } else if constexpr (KIND == A_GATHER) {
         const int ij = c / o.gC;
         const int ch = c - ij * o.gC;

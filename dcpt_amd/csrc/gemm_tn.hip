@@ -27,7 +27,7 @@ namespace {
 constexpr int BR = 32;  // reduction rows per LDS tile
 
 template <int KIND>
-constexpr bool is_dma() { return KIND == A_PLAIN || KIND == A_GATHER || KIND == A_CONV3; }
+constexpr bool is_dma() { return KIND == A_PLAIN || KIND == A_GATHER || KIND == A_CONV3 || KIND == A_CONV3UP; }
 
 template <int BN, int BKo, int WN, int WK, int XK, int YK>
 __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(const GemmTN pin) {
@@ -390,6 +390,7 @@ int launch_gemm_tn(const GemmTN& pin, int xload, int yload, hipStream_t s) {
     CASE(A_PLAIN, A_GATHER)
     CASE(A_GATHER, A_PLAIN)
     CASE(A_PLAIN, A_CONV3)
+    CASE(A_PLAIN, A_CONV3UP)
     CASE(A_PLAIN, A_LNBF)
 #undef CASE
     dcpt_set_error("gemm_tn: unsupported loader combination %d/%d", xload, yload);

@@ -2303,3 +2303,193 @@ class _Conv3x3PsFn(torch.autograd.Function):
 
 def conv3x3_ps(x, weight, bias, r):
     return _Conv3x3PsFn.apply(x, weight, bias, int(r))
+
+
+# ------------------------------------------------------------------------------------------------
+# SwinIR super-resolution tail and the "3conv" residual (include/dcpt_hip.h dcpt_conv3x3_act_*, dcpt_up2_conv3x3_act_*,
+# dcpt_conv3x3_ps_out_*, dcpt_conv3conv_res_*).
+from ._lib import Conv3convParams  # noqa: E402
+
+
+def _check_conv_weight(name, w_, b_, cout, cin, k=3):
+    if tuple(w_.shape) != (cout, cin, k, k) or tuple(b_.shape) != (cout,):
+        raise ValueError(f"{name}: weight {tuple(w_.shape)} / bias {tuple(b_.shape)} (expected ({cout}, {cin}, {k}, {k}) / ({cout},))")
+
+
+def _check_ws(name, nbytes, what):
+    if nbytes == 0:
+        raise ValueError(f"{name}: unsupported arguments ({what})")
+    return nbytes
+
+
+@_remember_gemm_mode
+class _Conv3x3ActFn(torch.autograd.Function):
+    """lrelu(conv3x3(x) + bias, slope), NHWC -> NHWC, Cin != Cout allowed; ``up2``: the conv runs over the nearest-2x up-sampling of x,
+    which is never materialised (swinir_arch.py:983-985, :1085-1100)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, slope, up2):
+        lib = _lib.load()
+        _require_gpu(x, weight, bias)
+        x = _nhwc(x)
+        w_, b_ = _contig(weight.detach()), _contig(bias.detach())
+        B, Cin, H, W = x.shape
+        Cout = w_.shape[0]
+        name = "up2_conv3x3_act" if up2 else "conv3x3_act"
+        _check_conv_weight(name, w_, b_, Cout, Cin)
+        if up2 and Cout != Cin:
+            raise ValueError(f"up2_conv3x3_act: C -> C only (weight {tuple(w_.shape)})")
+        if not 0.0 <= slope <= 1.0:
+            raise ValueError(f"{name}: slope {slope} outside [0, 1]")
+        dev = x.device
+        what = f"B={B} H={H} W={W} Cin={Cin} Cout={Cout}: channels must be multiples of 4"
+        if up2:
+            y = _empty_nhwc(B, Cout, 2 * H, 2 * W, dev)
+            ws = _workspace(dev, _check_ws(name, lib.dcpt_up2_conv3x3_act_ws_bytes(B, H, W, Cin, 0), what))
+            check(lib.dcpt_up2_conv3x3_act_fwd(x.data_ptr(), w_.data_ptr(), b_.data_ptr(), y.data_ptr(), ws.data_ptr(), ws.numel(), B, H, W,
+                                               Cin, slope, _stream(dev)), "dcpt_up2_conv3x3_act_fwd")
+        else:
+            y = _empty_nhwc(B, Cout, H, W, dev)
+            ws = _workspace(dev, _check_ws(name, lib.dcpt_conv3x3_act_ws_bytes(B, H, W, Cin, Cout, 0), what))
+            check(lib.dcpt_conv3x3_act_fwd(x.data_ptr(), w_.data_ptr(), b_.data_ptr(), y.data_ptr(), ws.data_ptr(), ws.numel(), B, H, W, Cin,
+                                           Cout, slope, _stream(dev)), "dcpt_conv3x3_act_fwd")
+        ctx.save_for_backward(x, y, w_)
+        ctx.geom = (slope, up2)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        lib = _lib.load()
+        x, y, w_ = ctx.saved_tensors
+        slope, up2 = ctx.geom
+        dy = _nhwc(dy)
+        B, Cin, H, W = x.shape
+        Cout = w_.shape[0]
+        dev = x.device
+        dx = _empty_nhwc(B, Cin, H, W, dev)
+        dw = torch.empty_like(w_)
+        db = torch.empty((Cout,), dtype=torch.float32, device=dev)
+        if up2:
+            ws = _workspace(dev, lib.dcpt_up2_conv3x3_act_ws_bytes(B, H, W, Cin, 1))
+            check(lib.dcpt_up2_conv3x3_act_bwd(dy.data_ptr(), x.data_ptr(), y.data_ptr(), w_.data_ptr(), dx.data_ptr(), dw.data_ptr(),
+                                               db.data_ptr(), ws.data_ptr(), ws.numel(), B, H, W, Cin, slope, _stream(dev)),
+                  "dcpt_up2_conv3x3_act_bwd")
+        else:
+            ws = _workspace(dev, lib.dcpt_conv3x3_act_ws_bytes(B, H, W, Cin, Cout, 1))
+            check(lib.dcpt_conv3x3_act_bwd(dy.data_ptr(), x.data_ptr(), y.data_ptr(), w_.data_ptr(), dx.data_ptr(), dw.data_ptr(),
+                                           db.data_ptr(), ws.data_ptr(), ws.numel(), B, H, W, Cin, Cout, slope, _stream(dev)),
+                  "dcpt_conv3x3_act_bwd")
+        return dx, dw, db, None, None
+
+
+def conv3x3_act(x, weight, bias, slope=0.01):
+    """lrelu(conv3x3(x) + bias, slope); ``slope=1`` is the plain biased conv"""
+    return _Conv3x3ActFn.apply(x, weight, bias, float(slope), False)
+
+
+def up2_conv3x3_act(x, weight, bias, slope=0.2):
+    """lrelu(conv3x3(nearest2x(x)) + bias, slope), (B, C, H, W) -> (B, C, 2H, 2W)"""
+    return _Conv3x3ActFn.apply(x, weight, bias, float(slope), True)
+
+
+@_remember_gemm_mode
+class _Conv3x3PsOutFn(torch.autograd.Function):
+    """PixelShuffle(r)(conv3x3(x) + bias), features NHWC -> image NCHW (UpsampleOneStep, swinir_arch.py:771-787)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, r):
+        lib = _lib.load()
+        _require_gpu(x, weight, bias)
+        x = _nhwc(x)
+        w_, b_ = _contig(weight.detach()), _contig(bias.detach())
+        B, Cc, H, W = x.shape
+        N = w_.shape[0]
+        if r < 1 or N % (r * r):
+            raise ValueError(f"conv3x3_ps_out: {N} conv channels are not a multiple of r^2 = {r * r}")
+        _check_conv_weight("conv3x3_ps_out", w_, b_, N, Cc)
+        Cimg = N // (r * r)
+        dev = x.device
+        nws = _check_ws("conv3x3_ps_out", lib.dcpt_conv3x3_ps_out_ws_bytes(B, H, W, Cc, Cimg, r, 0),
+                        f"C={Cc} Cimg={Cimg} r={r}: C a multiple of 4, at most 4 image channels, r in 2, 3, 4")
+        y = torch.empty((B, Cimg, r * H, r * W), dtype=torch.float32, device=dev)
+        ws = _workspace(dev, nws)
+        check(lib.dcpt_conv3x3_ps_out_fwd(x.data_ptr(), w_.data_ptr(), b_.data_ptr(), y.data_ptr(), ws.data_ptr(), ws.numel(), B, H, W, Cc,
+                                          Cimg, r, _stream(dev)), "dcpt_conv3x3_ps_out_fwd")
+        ctx.save_for_backward(x, w_)
+        ctx.geom = (Cimg, r)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        lib = _lib.load()
+        x, w_ = ctx.saved_tensors
+        Cimg, r = ctx.geom
+        dy = _contig(dy)
+        B, Cc, H, W = x.shape
+        dev = x.device
+        dx = _empty_nhwc(B, Cc, H, W, dev)
+        dw = torch.empty_like(w_)
+        db = torch.empty((w_.shape[0],), dtype=torch.float32, device=dev)
+        ws = _workspace(dev, lib.dcpt_conv3x3_ps_out_ws_bytes(B, H, W, Cc, Cimg, r, 1))
+        check(lib.dcpt_conv3x3_ps_out_bwd(dy.data_ptr(), x.data_ptr(), w_.data_ptr(), dx.data_ptr(), dw.data_ptr(), db.data_ptr(),
+                                          ws.data_ptr(), ws.numel(), B, H, W, Cc, Cimg, r, _stream(dev)), "dcpt_conv3x3_ps_out_bwd")
+        return dx, dw, db, None
+
+
+def conv3x3_ps_out(x, weight, bias, r):
+    return _Conv3x3PsOutFn.apply(x, weight, bias, int(r))
+
+
+@_remember_gemm_mode
+class _Conv3convResFn(torch.autograd.Function):
+    """res + conv3x3(lrelu(conv1x1(lrelu(conv3x3(x))))), slopes 0.2, C -> C/4 -> C/4 -> C (resi_connection="3conv",
+    swinir_arch.py:608-616, :969-977)."""
+
+    @staticmethod
+    def forward(ctx, x, grad_mode, res, w1, b1, w2, b2, w3, b3):
+        lib = _lib.load()
+        _require_gpu(x, res, w1, b1, w2, b2, w3, b3)
+        x, res = _nhwc(x), _nhwc(res)
+        ps = [_contig(t.detach()) for t in (w1, b1, w2, b2, w3, b3)]
+        B, Cc, H, W = x.shape
+        Cq = Cc // 4
+        if res.shape != x.shape:
+            raise ValueError(f"conv3conv_res: residual {tuple(res.shape)} for input {tuple(x.shape)}")
+        _check_conv_weight("conv3conv_res conv.0", ps[0], ps[1], Cq, Cc)
+        _check_conv_weight("conv3conv_res conv.2", ps[2], ps[3], Cq, Cq, 1)
+        _check_conv_weight("conv3conv_res conv.4", ps[4], ps[5], Cc, Cq)
+        dev = x.device
+        nws = _check_ws("conv3conv_res", lib.dcpt_conv3conv_res_ws_bytes(B, H, W, Cc, 0), f"C={Cc} must be a multiple of 16")
+        y = _empty_nhwc(B, Cc, H, W, dev)
+        a1 = a2 = None
+        if grad_mode:
+            a1, a2 = _empty_nhwc(B, Cq, H, W, dev), _empty_nhwc(B, Cq, H, W, dev)
+        pp = Conv3convParams(*[t.data_ptr() for t in ps])
+        ws = _workspace(dev, nws)
+        check(lib.dcpt_conv3conv_res_fwd(C.byref(pp), x.data_ptr(), res.data_ptr(), y.data_ptr(), _p(a1), _p(a2), ws.data_ptr(), ws.numel(),
+                                         B, H, W, Cc, _stream(dev)), "dcpt_conv3conv_res_fwd")
+        if grad_mode:
+            ctx.save_for_backward(x, a1, a2, *ps)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        lib = _lib.load()
+        x, a1, a2, *ps = ctx.saved_tensors
+        dy = _nhwc(dy)
+        B, Cc, H, W = x.shape
+        dev = x.device
+        dx = _empty_nhwc(B, Cc, H, W, dev)
+        grads = [torch.empty_like(p) for p in ps]
+        pp = Conv3convParams(*[p.data_ptr() for p in ps])
+        gg = Conv3convParams(*[g.data_ptr() for g in grads])
+        ws = _workspace(dev, lib.dcpt_conv3conv_res_ws_bytes(B, H, W, Cc, 1))
+        check(lib.dcpt_conv3conv_res_bwd(C.byref(pp), C.byref(gg), x.data_ptr(), a1.data_ptr(), a2.data_ptr(), dy.data_ptr(), dx.data_ptr(),
+                                         ws.data_ptr(), ws.numel(), B, H, W, Cc, _stream(dev)), "dcpt_conv3conv_res_bwd")
+        return (dx, None, dy, *grads)
+
+
+def conv3conv_res(x, w1, b1, w2, b2, w3, b3, res):
+    """the "3conv" residual as one autograd node; ``w2`` keeps its 1 x 1 kernel dims ([Cq][Cq][1][1])"""
+    ps = (w1, b1, w2, b2, w3, b3)
+    return _Conv3convResFn.apply(x, _wants_grad(x, res, *ps), res, *ps)

@@ -597,6 +597,48 @@ int dcpt_conv3x3_ps_fwd(const float* x, const float* w, const float* bias, float
                         dcpt_stream_t stream);
 int dcpt_conv3x3_ps_bwd(const float* dy, const float* x, const float* w, float* dx, float* dw, float* dbias, void* ws, size_t ws_bytes, int B,
                         int H, int W, int C, int r, dcpt_stream_t stream);
+/* ---- SwinIR super-resolution tail and the "3conv" residual (basicsr/archs/swinir_arch.py) ---------------------------------------------
+ * fp32, NHWC feature maps, implicit-GEMM convs with the LeakyReLU in the GEMM epilogue.  Every *_ws_bytes returns 0 for unsupported
+ * arguments.  Backward takes the activation mask from the sign of the saved OUTPUT y (y > 0: 1, else slope; 0 <= slope <= 1).
+ * conv_before_upsample (:983-985, :1000-1002; nn.LeakyReLU default slope 0.01) and conv_hr + lrelu (:1100, slope 0.2):
+ *   y = lrelu(conv3x3(x, w) + bias, slope),  x [B][H][W][Cin], w [Cout][Cin][3][3], y [B][H][W][Cout], Cin % 4 == Cout % 4 == 0
+ *   (slope 1 = the plain biased conv). */
+size_t dcpt_conv3x3_act_ws_bytes(int B, int H, int W, int Cin, int Cout, int backward);
+int dcpt_conv3x3_act_fwd(const float* x, const float* w, const float* bias, float* y, void* ws, size_t ws_bytes, int B, int H, int W, int Cin,
+                         int Cout, float slope, dcpt_stream_t stream);
+int dcpt_conv3x3_act_bwd(const float* dy, const float* x, const float* y, const float* w, float* dx, float* dw, float* dbias, void* ws,
+                         size_t ws_bytes, int B, int H, int W, int Cin, int Cout, float slope, dcpt_stream_t stream);
+/* conv_up1 / conv_up2 of the nearest+conv upsampler (:1085-1099):  y = lrelu(conv3x3(nearest2x(x), w) + bias, slope), x [B][H][W][C],
+ * w [C][C][3][3], y [B][2H][2W][C].  The up-sampled map is never written: tap pixel (h', w') of the 2H x 2W grid (zero padding applied
+ * there) reads x at (h' >> 1, w' >> 1).  Backward: dgrad on the 2H x 2W grid (workspace) and a 2 x 2 sum. */
+size_t dcpt_up2_conv3x3_act_ws_bytes(int B, int H, int W, int C, int backward);
+int dcpt_up2_conv3x3_act_fwd(const float* x, const float* w, const float* bias, float* y, void* ws, size_t ws_bytes, int B, int H, int W, int C,
+                             float slope, dcpt_stream_t stream);
+int dcpt_up2_conv3x3_act_bwd(const float* dy, const float* x, const float* y, const float* w, float* dx, float* dw, float* dbias, void* ws,
+                             size_t ws_bytes, int B, int H, int W, int C, float slope, dcpt_stream_t stream);
+/* UpsampleOneStep (:771-787):  y = PixelShuffle(r)(conv3x3(x, w) + bias) as the NCHW image [B][Cimg][rH][rW], x [B][H][W][C],
+ * w [r^2 Cimg][C][3][3], r in {2, 3, 4}, Cimg <= 4; conv channel c r^2 + i r + j is image channel c at sub-pixel (i, j). */
+size_t dcpt_conv3x3_ps_out_ws_bytes(int B, int H, int W, int C, int Cimg, int r, int backward);
+int dcpt_conv3x3_ps_out_fwd(const float* x, const float* w, const float* bias, float* y, void* ws, size_t ws_bytes, int B, int H, int W, int C,
+                            int Cimg, int r, dcpt_stream_t stream);
+int dcpt_conv3x3_ps_out_bwd(const float* dy, const float* x, const float* w, float* dx, float* dw, float* dbias, void* ws, size_t ws_bytes,
+                            int B, int H, int W, int C, int Cimg, int r, dcpt_stream_t stream);
+/* RSTB conv / conv_after_body with resi_connection="3conv" (:608-616, :969-977), Cq = C / 4, C % 16 == 0, both slopes 0.2:
+ *   a1 = lrelu(conv3x3(x, w1) + b1) [M][Cq],  a2 = lrelu(a1 W2^T + b2) [M][Cq],  y = res + conv3x3(a2, w3) + b3.
+ * Forward writes a1 / a2 for backward (both NULL: keep nothing).  Backward: dx and the six parameter gradients; the residual's
+ * gradient is dy itself. */
+typedef struct {
+    const float* conv1_w; const float* conv1_b;   /* conv.0: [Cq][C][3][3], [Cq] */
+    const float* conv2_w; const float* conv2_b;   /* conv.2: [Cq][Cq] (x 1 x 1), [Cq] */
+    const float* conv3_w; const float* conv3_b;   /* conv.4: [C][Cq][3][3], [C] */
+} dcpt_conv3conv_params;
+typedef struct { float* conv1_w; float* conv1_b; float* conv2_w; float* conv2_b; float* conv3_w; float* conv3_b; } dcpt_conv3conv_params_grads;
+size_t dcpt_conv3conv_res_ws_bytes(int B, int H, int W, int C, int backward);
+int dcpt_conv3conv_res_fwd(const dcpt_conv3conv_params* p, const float* x, const float* res, float* y, float* a1, float* a2, void* ws,
+                           size_t ws_bytes, int B, int H, int W, int C, dcpt_stream_t stream);
+int dcpt_conv3conv_res_bwd(const dcpt_conv3conv_params* p, const dcpt_conv3conv_params_grads* g, const float* x, const float* a1,
+                           const float* a2, const float* dy, float* dx, void* ws, size_t ws_bytes, int B, int H, int W, int C,
+                           dcpt_stream_t stream);
 /* PromptIR's PromptGenBlock (basicsr/archs/promptir_arch.py:237-262) between its linear layer and its 3x3 conv:
  *   out[b] = bilinear_{(S,S)->(H,W), align_corners=False}( sum_l softmax(logits[b])[l] * param[l] )   as NHWC [B][H][W][D].
  * logits [B][L] (= dcpt_meanpool_fc_fwd of the block input), param [L][D][S][S] (the (1,L,D,S,S) parameter), weights [B][L]
