@@ -8,6 +8,9 @@ autograd node backed by ``dcpt_conv_ln_fwd/bwd`` (1x1 and dense 3x3 convolutions
 as an implicit GEMM), the downsample layers by ``dcpt_conv1x1_pool_relu_*``, the softmax feature mixing by
 ``dcpt_mix_*`` and the head by ``dcpt_meanpool_fc_*``.  Child modules only own the parameters.
 
+``downsample=True`` (:622-637, the mode a SwinIR encoder uses): every feature is a full-resolution tap, (B, L, C) tokens or a 4-D map, and
+stage ``i`` mixes it nearest-down-sampled by ``2**i`` -- ``dcpt_mix_stride_*`` reads the grid positions in place.  fp32 only.
+
 ``act_dtype="bf16"`` (an extension; the reference computes in fp32 only): the bottleneck groups and the downsample layers run on
 the bf16-storage kernels (``dcpt_conv_ln_*_bf16``, ``dcpt_conv1x1_pool_relu_*_bf16``: bf16 activations, fp32 parameters and
 accumulation); the mixing step and mean + Linear stay fp32 behind casts.  Needs feature_dims that are multiples of 8.
@@ -151,15 +154,67 @@ class _DCHead(nn.Module):
 class PromptIR_NoImg_DC(_DCHead):
     def __init__(self, feature_dims, num_res_blocks=2, num_classes=3, downsample=False, act_dtype="fp32"):
         super().__init__()
-        if downsample:
-            raise NotImplementedError("downsample=True (token inputs) is not on the DCPT path")
-        self.downsample = downsample
+        if downsample and act_dtype != "fp32":
+            raise NotImplementedError("downsample=True (SwinIR's token taps) is fp32 only: SwinIR has no bf16 storage mode and its width "
+                                      "180 is not a multiple of 8")
+        self.downsample = bool(downsample)
         self._build_stages(feature_dims, num_res_blocks, num_classes)
         self._set_act_dtype(act_dtype)
 
     def forward(self, lq, features):
         """``lq`` is accepted and ignored, exactly like the reference (:621)."""
+        if self.downsample:
+            return self._run_token_stages(features)
         return self._run_stages(None, features)
+
+    def _token_maps(self, features):
+        """downsample=True (:624-631): every feature is a full-resolution tap -- the reference's (B, L, C) tokens, L a perfect square,
+        viewed as the NHWC map they are (token l is pixel (l // w, l % w): no transpose pass), or a 4-D map (what this repository's RSTBs
+        emit; any H x W).  -> [(map, stride)]: stage i mixes the map nearest-down-sampled by 2**i (:635-636).  A 4-D map that already has
+        the stage's size -- the strided tap view of the stacked DCPT step (DF.tap_split(..., stride=2**i)) -- is taken as it is.  The
+        caller's list is left alone (the reference overwrites its entries)."""
+        n = len(self.feature_dims)
+        if len(features) != n:
+            raise ValueError(f"PromptIR_NoImg_DC(downsample=True): {len(features)} features for feature_dims of length {n}")
+        maps = []
+        for i, f in enumerate(features):
+            if f.dim() == 3:
+                b, L, c = f.shape
+                w = int(round(L ** 0.5))
+                if w * w != L:
+                    raise ValueError(f"PromptIR_NoImg_DC(downsample=True): feature {i} has {L} tokens, which is not a square map "
+                                     "(pass a 4-D map for other shapes)")
+                f = f.reshape(b, w, w, c).permute(0, 3, 1, 2)   # a view of dense tokens: logical NCHW over NHWC memory
+            elif f.dim() != 4:
+                raise ValueError(f"PromptIR_NoImg_DC(downsample=True): feature {i} must be (B, L, C) tokens or a (B, C, H, W) map, "
+                                 f"got {tuple(f.shape)}")
+            if f.shape[1] != self.feature_dims[i]:
+                raise ValueError(f"PromptIR_NoImg_DC(downsample=True): feature {i} has {f.shape[1]} channels, feature_dims says "
+                                 f"{self.feature_dims[i]}")
+            maps.append(f)
+        H, W = maps[0].shape[2:]
+        if H % (1 << n) or W % (1 << n):
+            raise ValueError(f"PromptIR_NoImg_DC(downsample=True): the {H} x {W} maps must be a multiple of {1 << n} = "
+                             f"2**len(feature_dims) in both directions ({n} stages, each halving the map)")
+        out = []
+        for i, f in enumerate(maps):
+            if tuple(f.shape[2:]) == (H, W):
+                out.append((f, 1 << i))
+            elif tuple(f.shape[2:]) == (H >> i, W >> i):
+                out.append((f, 1))
+            else:
+                raise ValueError(f"PromptIR_NoImg_DC(downsample=True): feature {i} is {f.shape[2]} x {f.shape[3]}; expected the full "
+                                 f"{H} x {W} map (or its {H >> i} x {W >> i} grid view)")
+        return out
+
+    def _run_token_stages(self, features):
+        x = None
+        for i, (feature, s) in enumerate(self._token_maps(features)):
+            x = DF.mix(x, feature, self.mixing_weights, i, stride=s)
+            x = self.bottleneck_layers[i](x)
+            x = self.downsample_layers[i](x)
+        x = self.last_stage(x)
+        return DF.meanpool_fc(x, self.fc.weight, self.fc.bias)
 
 
 @ARCH_REGISTRY.register()

@@ -255,6 +255,8 @@ class SwinIR(nn.Module):
             t = DF.layernorm2d(t, self.patch_embed.norm.weight, self.patch_embed.norm.bias, LN_EPS)
         for layer in self.layers():
             t = layer(t)
+        if hook:   # the tap pass of the DCPT step: the forward hooks on decode_layers{i} have fired and the caller drops the image (the
+            return None   # reference computes the tail and discards it, ...pretrain_model.py:154; NAFNetBaseline returns None here too)
         t = DF.layernorm2d(t, self.norm.weight, self.norm.bias, LN_EPS)
         res = _apply_residual_conv(self.conv_after_body, t, x_first)
         if self.upsampler == "":

@@ -62,22 +62,53 @@ class DCPTModel(BaseModel):
             # one autograd node for both uses, so that the two gradients are merged in place instead of zero-padded and added
             from dcpt_amd.functional import tap_split
 
-            through, tap = tap_split(output, rng[0], rng[1])
+            # (a token head, PromptIR_NoImg_DC(downsample=True), mixes tap k of ITS order down-sampled by 2**k, and it consumes the
+            # hooks reversed: the stride belongs to the head's index, not to the firing order)
+            k = len(self.hooks) - 1 - len(self.hook_outputs)
+            stride = 1 << k if self._token_head() and k >= 0 else 1
+            through, tap = tap_split(output, rng[0], rng[1], stride=stride)
             self.hook_outputs.append(tap)
             return head + (through,) if head else through   # (a tuple output stays a tuple downstream: only its last element is replaced)
         self.hook_outputs.append(output.detach() if self.freeze_encoder else output)
         return None
 
-    def install_hooks(self):
+    def _token_head(self) -> bool:
+        return bool(getattr(self.get_bare_model(self.net_dc), "downsample", False))
+
+    def select_hook_modules(self):
+        """[(name, module)] of the bare net_g that the taps hook.  ``hook_depth`` 1 (default) is the reference's rule (:65-68):
+        ``hook_names in name and name.count(".") == 1``.  ``hook_depth: 0`` takes the direct children whose name contains hook_names,
+        containers (ModuleList / ModuleDict) left out: what the reference's rule selects on its DDP-wrapped net, where
+        ``module.decode_layers0`` has one dot -- SwinIR's decoder RSTBs, attributes of the net itself, which the published multi-GPU
+        runs tapped (on the bare net the one-dot rule picks their never-called ``residual_group`` / ``conv`` children instead)."""
         hook_names = self.opt.get("hook_names", None)
         if hook_names is None:
             raise ValueError("hook_names is required (e.g. 'decoder' for NAFNet, 'decoder_level' for Restormer)")
+        depth = self.opt.get("hook_depth", 1)
+        if depth not in (0, 1):
+            raise ValueError(f"hook_depth must be 0 or 1, got {depth!r}")
+        net = self.get_bare_model(self.net_g)
+        if depth == 0:
+            return [(name, m) for name, m in net.named_children()
+                    if hook_names in name and not isinstance(m, (torch.nn.ModuleList, torch.nn.ModuleDict))]
         # reference :65-68 (it walks the wrapped net, whose names gain a "module." prefix under DDP and then never match)
-        for name, module in self.get_bare_model(self.net_g).named_modules():
-            if hook_names in name and name.count(".") == 1:
-                self.hooks.append(module.register_forward_hook(self.hook_forward_fn))
+        return [(name, m) for name, m in net.named_modules() if hook_names in name and name.count(".") == 1]
+
+    def install_hooks(self):
+        picked = self.select_hook_modules()
+        self.hook_module_names = [name for name, _ in picked]
+        for _, module in picked:
+            self.hooks.append(module.register_forward_hook(self.hook_forward_fn))
         if not self.hooks:
-            raise ValueError(f"no module of net_g matches hook_names={hook_names!r}")
+            raise ValueError(f"no module of net_g matches hook_names={self.opt.get('hook_names')!r}")
+
+    def _classify(self):
+        """head on the collected taps, last hook first (reference :155)"""
+        dims = getattr(self.get_bare_model(self.net_dc), "feature_dims", None)
+        if self._token_head() and dims is not None and len(self.hook_outputs) != len(dims):
+            raise RuntimeError(f"the head has {len(dims)} stages (feature_dims {list(dims)}) but {len(self.hook_outputs)} taps were collected "
+                               f"from the hooked modules {self.hook_module_names}: check hook_names / hook_depth")
+        return self.net_dc(self.lq, self.hook_outputs[::-1])
 
     def init_training_settings(self):
         self.net_g.train()
@@ -168,7 +199,7 @@ class DCPTModel(BaseModel):
                 self.net_g(self.lq, hook=True)
         else:
             self.net_g(self.lq, hook=True)  # returns None; the hooks collect decoder0..3
-        cls_output = self.net_dc(self.lq, self.hook_outputs[::-1])
+        cls_output = self._classify()
         l_classify = self.cri_classify(cls_output, self.dataset_idx)
         l_total = l_total + l_classify
         loss_dict["l_classify"] = l_classify
@@ -188,7 +219,7 @@ class DCPTModel(BaseModel):
         self.hook_outputs = []
         with torch.no_grad():
             self.net_g(self.lq, hook=True)
-            self.cls_output = self.net_dc(self.lq, self.hook_outputs[::-1])
+            self.cls_output = self._classify()
         self.hook_outputs = []
 
     def dist_validation(self, dataloader, current_iter, tb_logger, save_img, clamp=True):

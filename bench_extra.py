@@ -2,7 +2,7 @@
 """Secondary workloads of BASELINE.json (configs[2..4]) on ONE MI355X -- evidence for DESIGN.md, not the driver's
 contract (that is bench.py).  Prints one JSON line per workload.
 
-    python bench_extra.py --workload dcpt|restormer|promptir|infer2k|naf|swinir|rcan [--dtype fp32|bf16] [--steps K] [--warmup W]
+    python bench_extra.py --workload dcpt|dcpt_swinir|restormer|promptir|infer2k|naf|swinir|rcan [--dtype fp32|bf16] [--steps K] [--warmup W]
 
 ``--dtype bf16`` (dcpt, naf, infer2k, restormer, promptir): every feature map of the encoder in bf16 storage with fp32 accumulation (act_dtype="bf16";
 dcpt: the classifier head too unless --head-dtype fp32); images, parameters and the optimizer stay fp32.  Its lines carry BOTH
@@ -297,12 +297,14 @@ def run_infer2k(dev, dtype="fp32", steps=5, warmup=2, S=2048, streams=2):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", required=True, choices=["dcpt", "restormer", "promptir", "infer2k", "naf", "swinir", "rcan"])
+    ap.add_argument("--workload", required=True, choices=["dcpt", "dcpt_swinir", "restormer", "promptir", "infer2k", "naf", "swinir", "rcan"])
     ap.add_argument("--dtype", default="fp32", choices=["fp32", "bf16", "bf16_tail32", "bf16_edge32"])
     ap.add_argument("--head-dtype", default=None, choices=["fp32", "bf16"], help="dcpt: classifier-head activations (default: --dtype)")
     ap.add_argument("--restormer-save", default="balanced", choices=["auto", "lean", "balanced", "full"], help="what the Restormer halves keep for backward")
     ap.add_argument("--optimizer", default="dcpt", choices=["dcpt", "torch"], help="A/B: torch = torch.optim.AdamW(fused=True) instead of dcpt_amd.optim.FusedAdamW")
     ap.add_argument("--two-pass", action="store_true", help="dcpt A/B: train.batched_encoder_passes false (the reference's two encoder passes, B each, instead of one pass over 2B)")
+    ap.add_argument("--torch-taps", action="store_true", help="dcpt_swinir A/B: the strided taps as torch indexing (feature[:, :, ::s, ::s] into the dense "
+                    "mix: a gather copy forward; a zero fill, a strided scatter and a full-map add backward) instead of dcpt_mix_stride_* / dcpt_grid_add")
     ap.add_argument("--upsampler", default="", choices=["", "pixelshuffle", "pixelshuffledirect", "nearest+conv"], help="swinir: super-resolution tail")
     ap.add_argument("--upscale", type=int, default=1, help="swinir: scale of --upsampler")
     ap.add_argument("--steps", type=int, default=5)
@@ -422,6 +424,35 @@ def main():
                        note="fractions = time bound / measured step; encoder bf16 (2.5 PF, bf16 bytes), head on its own pipe's peak")
         else:
             res.update(alg_tflops=round(flops / dt / 1e12, 2), mfma_frac=round(flops / dt / 157.3e12, 4))
+    elif args.workload == "dcpt_swinir":
+        # the SwinIR step of train_DCPT_SwinIR_5d.yml: 5D SwinIR encoder, token head on the three decoder RSTBs (hook_depth 0), fp32
+        if args.dtype != "fp32" or world > 1:
+            raise SystemExit("--workload dcpt_swinir: fp32, one GPU")
+        B, S = args.batch or 8, args.size or 128
+        from basicsr.models import build_model
+        from dcpt_amd import functional as DF
+
+        if args.torch_taps:   # bench-only: what the step would cost with the taps written as torch indexing
+            dense_mix = DF.mix
+            DF.tap_split = lambda x, lo, hi, stride=1: (x, x[lo:hi])
+            DF.mix = lambda prev, feat, mw, idx, stride=1: dense_mix(prev, feat[:, :, ::stride, ::stride].contiguous(memory_format=torch.channels_last), mw, idx)
+        opt = dict(name="b", model_type="DCPTModel", scale=1, num_gpu=1, dist=False, rank=0, world_size=1, is_train=True,
+                   hook_names="decode_layers", hook_depth=0,
+                   network_g=dict(type="SwinIR", img_size=S, embed_dim=180, depths=[6] * 6, num_heads=[6] * 6, mlp_ratio=2.0, window_size=8, upscale=1),
+                   network_dc=dict(type="PromptIR_NoImg_DC", feature_dims=[180, 180, 180], num_res_blocks=2, num_classes=5, downsample=True),
+                   path=dict(), train=dict(pixel_opt=dict(type="L1Loss"), classify_opt=dict(type="CrossEntropyLoss"),
+                                           batched_encoder_passes=not args.two_pass,
+                                           optim_g=dict(type="AdamW", lr=1e-4, fused=True), optim_dc=dict(type="AdamW", lr=1e-4, fused=True)))
+        m = build_model(opt)
+        fill_module_(m.net_g)
+        fill_module_(m.net_dc)
+        m.feed_data({"lq": torch.rand((B, 3, S, S), generator=g, device=dev), "gt": torch.rand((B, 3, S, S), generator=g, device=dev),
+                     "dataset_idx": torch.randint(0, 5, (B,), generator=g, device=dev)})
+        dt = timed(lambda: m.optimize_parameters(1), args.steps, args.warmup)
+        res = dict(workload=f"DCPT step: SwinIR 5D x2 fwd + PromptIR_NoImg_DC(downsample=True) head on decode_layers0..2 + bwd + 2x AdamW, B={B}, "
+                            f"{S}x{S}, fp32, {'two passes' if args.two_pass else 'stacked pass'}, taps: "
+                            f"{'torch indexing' if args.torch_taps else 'strided HIP kernels'}",
+                   ms_per_step=round(dt * 1e3, 2), megapixels_per_s=round(B * S * S / 1e6 / dt, 3), log=m.get_current_log())
     elif args.workload == "restormer":
         if args.dtype not in ("fp32", "bf16"):
             raise SystemExit("--workload restormer: --dtype fp32 or bf16")

@@ -212,6 +212,12 @@ SIGNATURES = {
     "dcpt_mix_fwd": (cint, [f32p, f32p, f32p, cint, cint, f32p, i64, stream_t]),
     "dcpt_mix_bwd_ws_bytes": (sz, [i64]),
     "dcpt_mix_bwd": (cint, [f32p, f32p, f32p, cint, cint, f32p, f32p, C.c_void_p, sz, i64, stream_t]),
+    "dcpt_mix_stride_fwd": (cint, [f32p, f32p, f32p, cint, cint, f32p, cint, cint, cint, cint, cint, i64, i64, i64, stream_t]),
+    "dcpt_mix_stride_bwd_ws_bytes": (sz, [i64]),
+    "dcpt_mix_stride_bwd": (cint, [f32p, f32p, f32p, cint, cint, f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint, cint, i64, i64, i64,
+                                   stream_t]),
+    "dcpt_grid_add": (cint, [f32p, f32p, cint, cint, cint, cint, cint, cint, cint, stream_t]),
+    "dcpt_grid_scatter": (cint, [f32p, f32p, cint, cint, cint, cint, cint, cint, cint, stream_t]),
     "dcpt_meanpool_fc_ws_bytes": (sz, [cint, cint, cint]),
     "dcpt_meanpool_fc_fwd": (cint, [f32p, f32p, f32p, f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint, stream_t]),
     "dcpt_meanpool_fc_bwd": (cint, [f32p, f32p, f32p, f32p, f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint, stream_t]),

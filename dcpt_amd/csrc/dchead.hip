@@ -8,6 +8,7 @@
 #include "bf16.h"
 #include "gemm.h"
 #include "kernels.h"
+#include "prof.h"
 #include "../../include/dcpt_hip.h"
 
 namespace {
@@ -147,6 +148,84 @@ __global__ __launch_bounds__(256) void mix_bwd_final_kernel(const float* __restr
         const float ds = red[0];
         const float si = softmax_i(mw, n, idx), sj = softmax_i(mw, n, threadIdx.x);
         dmix[threadIdx.x] = ds * si * ((threadIdx.x == idx ? 1.f : 0.f) - sj);
+    }
+}
+
+// ---- mixing a strided tap (downsample=True, :622-637) ---------------------------------------------
+// The tap of stage i is the nearest down-sampling of a full-resolution map by s = 2**i: pixel (h, w) of the coarse map is pixel
+// (h*s, w*s) of the fine one (F.interpolate(scale_factor=1/s), nearest).  Output quad i of the coarse [B][Hc][Wc][C] map reads
+// feat + b*sb + h*sh + w*sw (sh / sw already hold the factor s), so a batch-sliced or pre-strided view is read in place.  The loops
+// walk the OUTPUT in mix_fwd_kernel / mix_bwd_kernel's order with their arithmetic: at s == 1 on a dense map both give the same bits.
+struct TapGeom {
+    int Hc, Wc, nq;           // coarse height / width, float4 groups per pixel
+    int64_t sb, sh, sw;       // element strides of the tap: batch, coarse row, coarse pixel
+};
+__device__ __forceinline__ int64_t tap_offset(const TapGeom& g, int64_t i) {
+    const int q = (int)(i % g.nq);
+    int64_t t = i / g.nq;
+    const int w = (int)(t % g.Wc);
+    t /= g.Wc;
+    const int h = (int)(t % g.Hc);
+    const int64_t b = t / g.Hc;
+    return b * g.sb + h * g.sh + w * g.sw + 4 * q;
+}
+
+__global__ __launch_bounds__(256) void mix_stride_fwd_kernel(const float* __restrict__ prev, const float* __restrict__ feat,
+                                                             const float* __restrict__ mw, int n, int idx, float* __restrict__ out,
+                                                             TapGeom g, int64_t nq) {
+    const float s = softmax_i(mw, n, idx);
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nq; i += (int64_t)gridDim.x * 256) {
+        const float4 f = ldg4(feat + tap_offset(g, i));
+        float4 o = f4_scale(f, s);
+        if (prev) o = f4_add(o, ldg4(prev + 4 * i));
+        stg4(out + 4 * i, o);
+    }
+}
+
+// dfeat_c = s*dout (compact, coarse) ; part[block] = sum dout*feat[grid]
+__global__ __launch_bounds__(256) void mix_stride_bwd_kernel(const float* __restrict__ dout, const float* __restrict__ feat,
+                                                             const float* __restrict__ mw, int n, int idx, float* __restrict__ dfeat_c,
+                                                             float* __restrict__ part, TapGeom g, int64_t nq) {
+    __shared__ float red[256];
+    const float s = softmax_i(mw, n, idx);
+    float acc = 0.f;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nq; i += (int64_t)gridDim.x * 256) {
+        const float4 gq = ldg4(dout + 4 * i), f = ldg4(feat + tap_offset(g, i));
+        acc += f4_sum(f4_mul(gq, f));
+        stg4(dfeat_c + 4 * i, f4_scale(gq, s));
+    }
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) part[blockIdx.x] = red[0];
+}
+
+// g[lo + b][h*s][w*s][:] += d[b][h][w][:]: the tap's compact gradient merged into the main path's dense [B][H][W][C] gradient
+__global__ __launch_bounds__(256) void grid_add_kernel(float* __restrict__ gm, const float* __restrict__ d, TapGeom g, int64_t nq) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nq; i += (int64_t)gridDim.x * 256) {
+        float* p = gm + tap_offset(g, i);
+        stg4(p, f4_add(ldg4(p), ldg4(d + 4 * i)));
+    }
+}
+
+// the same into a fresh map: out[B][H][W][C] = d on the grid positions of samples lo..hi-1, zero elsewhere (one pass over out)
+__global__ __launch_bounds__(256) void grid_scatter_kernel(const float* __restrict__ d, float* __restrict__ out, int lo, int hi, int H,
+                                                           int W, int nqc, int s, int64_t nq) {
+    const int Hc = H / s, Wc = W / s;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nq; i += (int64_t)gridDim.x * 256) {
+        const int q = (int)(i % nqc);
+        int64_t t = i / nqc;
+        const int w = (int)(t % W);
+        t /= W;
+        const int h = (int)(t % H);
+        const int64_t b = t / H;
+        float4 v = f4_zero();
+        if (b >= lo && b < hi && (h & (s - 1)) == 0 && (w & (s - 1)) == 0)
+            v = ldg4(d + ((((b - lo) * Hc + h / s) * (int64_t)Wc + w / s) * nqc + q) * 4);
+        stg4(out + 4 * i, v);
     }
 }
 
@@ -477,6 +556,79 @@ extern "C" int dcpt_mix_bwd(const float* dout, const float* feat, const float* m
 extern "C" int dcpt_mix_bwd_bf16(const uint16_t* dout, const uint16_t* feat, const float* mixing_weights, int n, int idx, uint16_t* dfeat,
                                  float* dmix, void* ws, size_t ws_bytes, int64_t numel, dcpt_stream_t stream) {
     return mix_bwd_t<bf16_t>(dout, feat, mixing_weights, n, idx, dfeat, dmix, ws, ws_bytes, numel, (hipStream_t)stream);
+}
+
+// ---- strided taps (PromptIR_NoImg_DC(downsample=True)) ----------------------------------------------
+static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+static bool pow2(int s) { return s >= 1 && (s & (s - 1)) == 0; }
+
+static int tap_geom(const char* what, const float* feat, int B, int H, int W, int C, int s, int64_t sb, int64_t sh, int64_t sw, TapGeom* g) {
+    DCPT_CHECK_ARG(B > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0, "%s: B=%d H=%d W=%d C=%d (C must be a multiple of 4)", what, B, H, W, C);
+    DCPT_CHECK_ARG(pow2(s) && H % s == 0 && W % s == 0, "%s: stride %d must be a power of two that divides H=%d and W=%d", what, s, H, W);
+    DCPT_CHECK_ARG(sb >= 0 && sh >= 0 && sw >= C && sb % 4 == 0 && sh % 4 == 0 && sw % 4 == 0 && aligned16(feat),
+                   "%s: the map's strides (%lld, %lld, %lld) must be multiples of 4 elements, pixels at least C apart, 16-byte aligned", what,
+                   (long long)sb, (long long)sh, (long long)sw);
+    *g = TapGeom{H / s, W / s, C / 4, sb, sh * s, sw * s};
+    return DCPT_OK;
+}
+
+extern "C" int dcpt_mix_stride_fwd(const float* prev, const float* feat, const float* mixing_weights, int n, int idx, float* out, int B, int H,
+                                   int W, int C, int s, int64_t sb, int64_t sh, int64_t sw, dcpt_stream_t stream) {
+    DCPT_CHECK_ARG(feat && mixing_weights && out && n >= 1 && n <= 64 && idx >= 0 && idx < n && aligned16(prev) && aligned16(out),
+                   "mix_stride_fwd: bad argument");
+    TapGeom g;
+    DCPT_TRY(tap_geom("mix_stride_fwd", feat, B, H, W, C, s, sb, sh, sw, &g));
+    const int64_t nq = (int64_t)B * g.Hc * g.Wc * g.nq;
+    mix_stride_fwd_kernel<<<dim3(grid_for(nq)), dim3(256), 0, (hipStream_t)stream>>>(prev, feat, mixing_weights, n, idx, out, g, nq);
+    DCPT_CHECK_LAUNCH("mix_stride_fwd");
+    trace_tag("head.mix_stride_fwd");
+    return DCPT_OK;
+}
+
+extern "C" size_t dcpt_mix_stride_bwd_ws_bytes(int64_t numel_coarse) { return dcpt_mix_bwd_ws_bytes(numel_coarse); }
+
+extern "C" int dcpt_mix_stride_bwd(const float* dout, const float* feat, const float* mixing_weights, int n, int idx, float* dfeat_c,
+                                   float* dmix, void* ws, size_t ws_bytes, int B, int H, int W, int C, int s, int64_t sb, int64_t sh,
+                                   int64_t sw, dcpt_stream_t stream) {
+    DCPT_CHECK_ARG(dout && feat && mixing_weights && dfeat_c && dmix && n >= 1 && n <= 64 && idx >= 0 && idx < n && aligned16(dout) &&
+                       aligned16(dfeat_c), "mix_stride_bwd: bad argument");
+    TapGeom g;
+    DCPT_TRY(tap_geom("mix_stride_bwd", feat, B, H, W, C, s, sb, sh, sw, &g));
+    const int64_t nq = (int64_t)B * g.Hc * g.Wc * g.nq;
+    if (ws == nullptr || ws_bytes < dcpt_mix_stride_bwd_ws_bytes(nq * 4)) {
+        dcpt_set_error("mix_stride_bwd: workspace too small");
+        return DCPT_ERR_WS;
+    }
+    const unsigned nb = grid_for(nq);
+    mix_stride_bwd_kernel<<<dim3(nb), dim3(256), 0, (hipStream_t)stream>>>(dout, feat, mixing_weights, n, idx, dfeat_c, (float*)ws, g, nq);
+    DCPT_CHECK_LAUNCH("mix_stride_bwd");
+    mix_bwd_final_kernel<<<dim3(1), dim3(256), 0, (hipStream_t)stream>>>((float*)ws, (int)nb, mixing_weights, n, idx, dmix);
+    DCPT_CHECK_LAUNCH("mix_stride_bwd_final");
+    trace_tag("head.mix_stride_bwd");
+    return DCPT_OK;
+}
+
+extern "C" int dcpt_grid_add(float* g, const float* dfeat_c, int B, int lo, int hi, int H, int W, int C, int s, dcpt_stream_t stream) {
+    DCPT_CHECK_ARG(g && dfeat_c && aligned16(dfeat_c) && 0 <= lo && lo < hi && hi <= B, "grid_add: bad argument (B=%d, rows %d..%d)", B, lo, hi);
+    TapGeom tg;
+    DCPT_TRY(tap_geom("grid_add", g, hi - lo, H, W, C, s, (int64_t)H * W * C, (int64_t)W * C, C, &tg));
+    const int64_t nq = (int64_t)(hi - lo) * tg.Hc * tg.Wc * tg.nq;
+    grid_add_kernel<<<dim3(grid_for(nq)), dim3(256), 0, (hipStream_t)stream>>>(g + (int64_t)lo * H * W * C, dfeat_c, tg, nq);
+    DCPT_CHECK_LAUNCH("grid_add");
+    trace_tag("head.grid_add");
+    return DCPT_OK;
+}
+
+extern "C" int dcpt_grid_scatter(const float* dfeat_c, float* out, int B, int lo, int hi, int H, int W, int C, int s, dcpt_stream_t stream) {
+    DCPT_CHECK_ARG(out && dfeat_c && aligned16(dfeat_c) && 0 <= lo && lo < hi && hi <= B, "grid_scatter: bad argument (B=%d, rows %d..%d)", B, lo,
+                   hi);
+    TapGeom tg;
+    DCPT_TRY(tap_geom("grid_scatter", out, B, H, W, C, s, (int64_t)H * W * C, (int64_t)W * C, C, &tg));
+    const int64_t nq = (int64_t)B * H * W * (C / 4);
+    grid_scatter_kernel<<<dim3(grid_for(nq)), dim3(256), 0, (hipStream_t)stream>>>(dfeat_c, out, lo, hi, H, W, C / 4, s, nq);
+    DCPT_CHECK_LAUNCH("grid_scatter");
+    trace_tag("head.grid_scatter");
+    return DCPT_OK;
 }
 
 // ---------------------------------------------------------------------------------------------

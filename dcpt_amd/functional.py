@@ -765,9 +765,53 @@ class _TapSplitFn(torch.autograd.Function):
         return g, None, None
 
 
-def tap_split(x, lo, hi):
-    """-> (x, x[lo:hi]) with the two gradients merged in place on the way back (one use of x downstream, one tap)"""
-    return _TapSplitFn.apply(x, lo, hi)
+def _is_nhwc(x) -> bool:
+    n, c, h, w = x.shape
+    return x.stride() == (h * w * c, 1, w * c, c)
+
+
+class _TapSplitStrideFn(torch.autograd.Function):
+    """(x, x[lo:hi, :, ::s, ::s]): _TapSplitFn for a tap that is nearest-down-sampled by s on its way into the head (the SwinIR step:
+    PromptIR_NoImg_DC(downsample=True), degrad_classify_arch.py:634-637).  The tap is a VIEW -- its strides carry the batch range and the
+    grid, ``mix`` reads it in place -- so its gradient arrives compact (hi-lo, C, H/s, W/s) and is added into the grid positions of rows
+    lo..hi-1 of the main path's gradient by dcpt_grid_add: no zero fill of a full map, no strided scatter, no full-map add.  In place when
+    that gradient is provably private (_private_grad), into a copy otherwise; with no main-path gradient at all, dcpt_grid_scatter writes
+    the zero-padded map in one pass."""
+
+    @staticmethod
+    def forward(ctx, x, lo, hi, stride):
+        s = int(stride)
+        _require_gpu(x)
+        if x.dim() != 4 or s < 1 or s & (s - 1) or x.shape[2] % s or x.shape[3] % s or x.shape[1] % 4:
+            raise ValueError(f"tap_split: stride {s} must be a power of two that divides the map {tuple(x.shape)} (channels a multiple of 4)")
+        ctx.meta = (tuple(x.shape), int(lo), int(hi), s)
+        return x.view(x.shape), x[lo:hi, :, ::s, ::s]
+
+    @staticmethod
+    def backward(ctx, g, gs):
+        shape, lo, hi, s = ctx.meta
+        if gs is None:
+            return g, None, None, None
+        lib = _lib.load()
+        B, Cc, H, W = shape
+        _require_gpu(gs, g)
+        gs = _nhwc(gs)
+        if g is None:
+            g = _empty_nhwc(B, Cc, H, W, gs.device)
+            check(lib.dcpt_grid_scatter(gs.data_ptr(), g.data_ptr(), B, lo, hi, H, W, Cc, s, _stream(gs.device)), "dcpt_grid_scatter")
+            return g, None, None, None
+        if not _is_nhwc(g) or not _private_grad(g):
+            g = _force_nhwc(g)
+        check(lib.dcpt_grid_add(g.data_ptr(), gs.data_ptr(), B, lo, hi, H, W, Cc, s, _stream(gs.device)), "dcpt_grid_add")
+        return g, None, None, None
+
+
+def tap_split(x, lo, hi, stride=1):
+    """-> (x, x[lo:hi]) with the two gradients merged in place on the way back (one use of x downstream, one tap).  ``stride`` s > 1: the
+    tap is x[lo:hi, :, ::s, ::s], a view for ``mix`` to read in place; its compact gradient is merged by dcpt_grid_add (fp32 maps)."""
+    if stride == 1:
+        return _TapSplitFn.apply(x, lo, hi)
+    return _TapSplitStrideFn.apply(x, lo, hi, stride)
 
 
 def take_batch(x, lo, hi):
@@ -1532,8 +1576,80 @@ class _MixFn(torch.autograd.Function):
         return (dout if ctx.has_prev else None), dfeat, dmix, None
 
 
-def mix(prev, feat, mixing_weights, idx):
-    return _MixFn.apply(prev, feat, mixing_weights, idx)
+def _tap_view(feat):
+    """an fp32 (B, C, H, W) view the strided kernels can read in place (contiguous channels, strides that keep float4 alignment)
+    -> (feat, sb, sh, sw); anything else is made dense NHWC first"""
+    if feat.dim() != 4:
+        raise ValueError(f"expected a 4-D NCHW tensor, got {tuple(feat.shape)}")
+    B, Cc, H, W = feat.shape
+    sb, sc, sh, sw = feat.stride()
+    if (sc != 1 and Cc > 1) or sb % 4 or sh % 4 or sw % 4 or (W > 1 and sw < Cc) or feat.data_ptr() % 16:
+        feat = _nhwc(feat)
+        sb, sc, sh, sw = feat.stride()
+    return feat, sb, sh, max(sw, Cc)
+
+
+class _MixStrideFn(torch.autograd.Function):
+    """prev + softmax(mixing_weights)[idx] * feat[:, :, ::s, ::s]: the mixing step of PromptIR_NoImg_DC(downsample=True)
+    (degrad_classify_arch.py:634-637, F.interpolate(feature, scale_factor=1 / 2**i) in nearest mode reads source index dst * s) without
+    the gather copy: dcpt_mix_stride_fwd reads the grid positions of ``feat`` through its strides (a batch slice or the strided tap of
+    ``tap_split`` included).  The gradient of ``feat`` has feat's shape: the compact s * dout when stride == 1 (a pre-strided tap: its
+    producer scatters), the zero-padded map written in one pass by dcpt_grid_scatter otherwise; none when feat needs none."""
+
+    @staticmethod
+    def forward(ctx, prev, feat, mixing_weights, idx, stride):
+        lib = _lib.load()
+        _require_gpu(prev, feat, mixing_weights)
+        s = int(stride)
+        feat, sb, sh, sw = _tap_view(feat)
+        B, Cc, H, W = feat.shape
+        if s < 1 or s & (s - 1) or H % s or W % s:
+            raise ValueError(f"mix: stride {s} must be a power of two that divides the {H} x {W} map")
+        prev_ = None if prev is None else _nhwc(prev)
+        if prev_ is not None and tuple(prev_.shape) != (B, Cc, H // s, W // s):
+            raise ValueError(f"mix: prev {tuple(prev_.shape)} does not match the tap {(B, Cc, H // s, W // s)}")
+        mw = _contig(mixing_weights.detach())
+        out = _empty_nhwc(B, Cc, H // s, W // s, feat.device)
+        check(lib.dcpt_mix_stride_fwd(_p(prev_), feat.data_ptr(), mw.data_ptr(), mw.numel(), int(idx), out.data_ptr(), B, H, W, Cc, s,
+                                      sb, sh, sw, _stream(feat.device)), "dcpt_mix_stride_fwd")
+        ctx.save_for_backward(feat, mw)
+        ctx.meta = (int(idx), prev is not None, s, sb, sh, sw)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        lib = _lib.load()
+        feat, mw = ctx.saved_tensors
+        idx, has_prev, s, sb, sh, sw = ctx.meta
+        B, Cc, H, W = feat.shape
+        dev = feat.device
+        _require_gpu(dout)
+        dout = _nhwc(dout)
+        dfeat = _empty_nhwc(B, Cc, H // s, W // s, dev)
+        dmix = torch.empty_like(mw)
+        ws = _workspace(dev, lib.dcpt_mix_stride_bwd_ws_bytes(dfeat.numel()))
+        check(lib.dcpt_mix_stride_bwd(dout.data_ptr(), feat.data_ptr(), mw.data_ptr(), mw.numel(), idx, dfeat.data_ptr(), dmix.data_ptr(),
+                                      ws.data_ptr(), ws.numel(), B, H, W, Cc, s, sb, sh, sw, _stream(dev)), "dcpt_mix_stride_bwd")
+        if not ctx.needs_input_grad[1]:
+            dfeat = None
+        elif s > 1:
+            full = _empty_nhwc(B, Cc, H, W, dev)
+            check(lib.dcpt_grid_scatter(dfeat.data_ptr(), full.data_ptr(), B, 0, B, H, W, Cc, s, _stream(dev)), "dcpt_grid_scatter")
+            dfeat = full
+        return (dout if has_prev else None), dfeat, dmix, None, None
+
+
+def mix_stride(prev, feat, mixing_weights, idx, stride=1):
+    """prev + softmax(mixing_weights)[idx] * feat[:, :, ::stride, ::stride] on the strided kernels, whatever the stride (fp32)"""
+    return _MixStrideFn.apply(prev, feat, mixing_weights, idx, stride)
+
+
+def mix(prev, feat, mixing_weights, idx, stride=1):
+    """``stride`` > 1, or an fp32 tap that is a strided view with contiguous channels (``tap_split(..., stride=s)``): read in place by
+    the strided kernels; everything else is the dense node"""
+    if stride == 1 and (feat.dim() != 4 or feat.dtype != torch.float32 or feat.stride(1) != 1 or _is_nhwc(feat)):
+        return _MixFn.apply(prev, feat, mixing_weights, idx)
+    return _MixStrideFn.apply(prev, feat, mixing_weights, idx, stride)
 
 
 @_remember_gemm_mode

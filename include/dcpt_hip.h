@@ -367,6 +367,27 @@ int dcpt_mix_fwd(const float* prev, const float* feat, const float* mixing_weigh
 size_t dcpt_mix_bwd_ws_bytes(int64_t numel);
 int dcpt_mix_bwd(const float* dout, const float* feat, const float* mixing_weights, int n, int idx, float* dfeat, float* dmix,
                  void* ws, size_t ws_bytes, int64_t numel, dcpt_stream_t stream);
+/* downsample=True (:622-637, the SwinIR head; additive, ABI unchanged): stage i mixes the nearest down-sampling of a full-resolution
+ * map by s = 2**i, F.interpolate(feature, scale_factor=1/s) of :636, which reads source pixel (h*s, w*s).
+ *   out[B][H/s][W/s][C] = prev + softmax(mixing_weights)[idx] * feat[b][h*s][w*s][:]          (prev may be NULL)
+ * feat is an NHWC map [B][H][W][C] addressed as feat + b*sb + y*sh + x*sw (element strides of batch, row and pixel; channels are
+ * contiguous), so a batch slice of a larger map or an already strided view is read in place; out, prev, dout and dfeat_c are dense.
+ * C % 4 == 0, s a power of two that divides H and W, strides multiples of 4, 16-byte aligned pointers.  With s == 1 and dense strides
+ * the results equal dcpt_mix_fwd / dcpt_mix_bwd bit for bit.  The backward writes the COMPACT gradient dfeat_c[B][H/s][W/s][C] =
+ * softmax[idx] * dout and dmix (per-block partials in a fixed order + one finishing block: no atomics, repeatable bit for bit);
+ * workspace dcpt_mix_stride_bwd_ws_bytes(B * (H/s) * (W/s) * C).  The gradient of prev equals dout. */
+int dcpt_mix_stride_fwd(const float* prev, const float* feat, const float* mixing_weights, int n, int idx, float* out, int B, int H, int W,
+                        int C, int s, int64_t sb, int64_t sh, int64_t sw, dcpt_stream_t stream);
+size_t dcpt_mix_stride_bwd_ws_bytes(int64_t numel_coarse);
+int dcpt_mix_stride_bwd(const float* dout, const float* feat, const float* mixing_weights, int n, int idx, float* dfeat_c, float* dmix,
+                        void* ws, size_t ws_bytes, int B, int H, int W, int C, int s, int64_t sb, int64_t sh, int64_t sw,
+                        dcpt_stream_t stream);
+/* the backward of that down-sampling (:636) merged into the gradient of the map's other use (the encoder going on after the hook,
+ * ...pretrain_model.py:88-91,154-163): g[b][h*s][w*s][:] += dfeat_c[b - lo][h][w][:] for samples lo <= b < hi of the dense NHWC
+ * gradient g[B][H][W][C], in place.  dcpt_grid_scatter writes the same into a fresh map in one pass: out[B][H][W][C] = dfeat_c on
+ * the grid positions of samples lo..hi-1, zero everywhere else. */
+int dcpt_grid_add(float* g, const float* dfeat_c, int B, int lo, int hi, int H, int W, int C, int s, dcpt_stream_t stream);
+int dcpt_grid_scatter(const float* dfeat_c, float* out, int B, int lo, int hi, int H, int W, int C, int s, dcpt_stream_t stream);
 /* :639-640: mean over the P pixels of each image, then Linear(C, NC).  x [B][P][C] */
 size_t dcpt_meanpool_fc_ws_bytes(int B, int P, int C);
 int dcpt_meanpool_fc_fwd(const float* x, const float* fw, const float* fb, float* pooled, float* logits, void* ws, size_t ws_bytes,
