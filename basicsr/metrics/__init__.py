@@ -20,14 +20,18 @@ on stand-ins for those two OpenCV routines written here -- the result would pin 
 OpenCV, not against the reference, so no such fixture is committed.  What is checked instead: ``calculate_ssim`` against an
 independently written scipy implementation of the published formula (11 x 11 Gaussian, sigma 1.5, "valid" window, C1 = (0.01 L)^2,
 C2 = (0.03 L)^2, float64; tests/test_plumbing_cpu.py::test_metrics_match_independent_implementations), and the acceptance gate of
-``north_star`` is stated in PSNR (<= 0.01 dB), which IS pinned."""
+``north_star`` is stated in PSNR (<= 0.01 dB), which IS pinned.
+
+``calculate_psnr_device`` / ``calculate_ssim_device`` / ``MetricSums`` score BCHW tensors that are already on the device with the fused HIP
+kernel of dcpt_amd/csrc/metrics.hip (same arithmetic, image_range 255 or 1); the host functions above stay the yardstick they are tested
+against (tests/test_gpu_metrics.py)."""
 from copy import deepcopy
 
 import numpy as np
 
 from basicsr.utils.registry import METRIC_REGISTRY
 
-__all__ = ["calculate_metric", "calculate_psnr", "calculate_ssim"]
+__all__ = ["calculate_metric", "calculate_psnr", "calculate_ssim", "calculate_psnr_device", "calculate_ssim_device", "MetricSums"]
 
 
 def _reorder(img, input_order):
@@ -125,6 +129,80 @@ def calculate_ssim(img, img2, crop_border, input_order="BCHW", test_y_channel=Fa
         for j in range(x.shape[2]):
             ssims.append(_ssim(x[..., j], y[..., j], image_range))
     return float(np.array(ssims).mean())
+
+
+class MetricSums:
+    """Device-side PSNR / SSIM of a whole dataset (dcpt_amd.functional.image_metric_sums: one fused HIP kernel per call, no host sync):
+    ``add(img, img2)`` takes (B, C, H, W) fp32 device tensors in [0, 1] and keeps the per-image sums on the device; ``result()`` copies
+    them to the host in ONE transfer and returns ``{"psnr": [...], "ssim": [...]}`` with one value per ``add`` call -- what
+    ``calculate_psnr`` / ``calculate_ssim`` return for that batch, finished with the same numpy expressions (``np.mean`` of the squared
+    error, ``10 log10(L^2 / mse)``, ``inf`` on ``mse == 0``, the mean over images and over (image, channel))."""
+
+    def __init__(self, crop_border=0, input_order="BCHW", test_y_channel=False, image_range=255, psnr=True, ssim=True, **kwargs):
+        if input_order != "BCHW":
+            raise ValueError(f"the device metrics take BCHW tensors (input_order {input_order})")
+        if image_range not in (255, 1):
+            raise ValueError(f"image_range {image_range}: the device metrics know 255 and 1")
+        self.crop_border, self.test_y_channel, self.image_range = int(crop_border), bool(test_y_channel), image_range
+        self.psnr, self.ssim = bool(psnr), bool(ssim)
+        self._parts = []   # per add(): (sse (B,), ssim sums (B, C') or None, pixels per image, SSIM-map positions per channel)
+
+    def add(self, img, img2):
+        from dcpt_amd import functional as DF
+
+        sse, sums = DF.image_metric_sums(img, img2, self.crop_border, self.test_y_channel, self.image_range, ssim=self.ssim)
+        b, c, h, w = img.shape
+        hc, wc = h - 2 * self.crop_border, w - 2 * self.crop_border
+        cp = 1 if (self.test_y_channel and c == 3) else c
+        self._parts.append((sse, sums, hc * wc * cp, (hc - 10) * (wc - 10)))
+
+    def result(self):
+        import torch
+
+        out = {"psnr": [], "ssim": []}
+        if not self._parts:
+            return out
+        # one transfer: every piece travels as 8-byte words (the exact int64 sums bit for bit)
+        flat = [t.reshape(-1).view(torch.int64) for sse, sums, _, _ in self._parts for t in (sse, sums) if t is not None]
+        host = torch.cat(flat).cpu().numpy()
+        pos = 0
+        for sse, sums, npix, npos in self._parts:
+            raw = host[pos:pos + sse.numel()]
+            pos += sse.numel()
+            if self.psnr:
+                out["psnr"].append(_psnr_of_sums(raw if sse.dtype == torch.int64 else raw.view(np.float64), npix, self.image_range))
+            if sums is not None:
+                per_map = host[pos:pos + sums.numel()].view(np.float64) / npos
+                pos += sums.numel()
+                out["ssim"].append(float(per_map.mean()))
+        return out
+
+
+def _psnr_of_sums(sse, npix, image_range):
+    """calculate_psnr's loop over the images of one batch, from their squared-error sums"""
+    psnrs = []
+    for s in sse:
+        mse = np.float64(s) / npix
+        if mse == 0:
+            return float("inf")
+        psnrs.append(10.0 * np.log10(image_range * image_range / mse))
+    return float(np.array(psnrs).mean())
+
+
+@METRIC_REGISTRY.register()
+def calculate_psnr_device(img, img2, crop_border, input_order="BCHW", test_y_channel=False, image_range=255, **kwargs):
+    """``calculate_psnr`` for (B, C, H, W) fp32 tensors on the device; returns a Python float (this call synchronises)"""
+    acc = MetricSums(crop_border, input_order, test_y_channel, image_range, ssim=False)
+    acc.add(img, img2)
+    return acc.result()["psnr"][0]
+
+
+@METRIC_REGISTRY.register()
+def calculate_ssim_device(img, img2, crop_border, input_order="BCHW", test_y_channel=False, image_range=255, **kwargs):
+    """``calculate_ssim`` for (B, C, H, W) fp32 tensors on the device; returns a Python float (this call synchronises)"""
+    acc = MetricSums(crop_border, input_order, test_y_channel, image_range, psnr=False)
+    acc.add(img, img2)
+    return acc.result()["ssim"][0]
 
 
 def calculate_metric(data, opt):

@@ -286,6 +286,8 @@ class SRModel(BaseModel):
         metrics_opt = self.opt["val"].get("metrics") or {}
         results = OrderedDict((m, 0.0) for m in metrics_opt)
         n = 0
+        on_device = self._device_metric_plan(metrics_opt, clamp)   # {metric: (accumulator key, "psnr" / "ssim")}; empty = the host route
+        sums = {}
         for val_data in dataloader:
             self.feed_data(val_data)
             if self._tile_shard():
@@ -305,6 +307,13 @@ class SRModel(BaseModel):
                 self.test()
             self.post_test()
             if self.opt.get("rank", 0) != 0:   # (tile-sharded validation: only rank 0 holds the assembled image)
+                del self.lq, self.output
+                if hasattr(self, "gt"):
+                    del self.gt
+                continue
+            if on_device:
+                self._validate_on_device(val_data, name, save_img, metrics_opt, on_device, sums, results)
+                n += 1
                 del self.lq, self.output
                 if hasattr(self, "gt"):
                     del self.gt
@@ -332,6 +341,12 @@ class SRModel(BaseModel):
             del self.lq, self.output
             if hasattr(self, "gt"):
                 del self.gt
+        for key, acc in sums.items():   # the one synchronisation of the device route: every image's sums in one transfer
+            per_batch = acc.result()
+            for m, (k, kind) in on_device.items():
+                if k == key:
+                    for v in per_batch[kind]:
+                        results[m] += v
         for m in results:
             results[m] /= max(1, n)
         self.metric_results = results
@@ -343,6 +358,52 @@ class SRModel(BaseModel):
             for m, v in results.items():
                 tb_logger.add_scalar(f"metrics/{name}/{m}", v, current_iter)
         return results
+
+    def _device_metric_plan(self, metrics_opt, clamp):
+        """``val.device_metrics: true`` (opt-in): which metrics are scored on the device (basicsr.metrics.MetricSums), as
+        {name: ((crop_border, test_y_channel, image_range), "psnr" | "ssim")}.  Only what the kernel mirrors exactly qualifies: clamped
+        images, ``calculate_psnr`` / ``calculate_ssim``, BCHW order, image_range 255 or 1; any other metric keeps the host function, and
+        without ``clamp`` (raw outputs, NaNs included) or off the GPU the whole call does."""
+        if not self.opt["val"].get("device_metrics", False) or not clamp or self.device.type != "cuda":
+            return {}
+        plan = {}
+        for m, mo in metrics_opt.items():
+            kind = {"calculate_psnr": "psnr", "calculate_ssim": "ssim"}.get(mo.get("type"))
+            if kind is None or mo.get("input_order", "BCHW") != "BCHW" or mo.get("image_range", 255) not in (255, 1):
+                continue
+            plan[m] = ((int(mo.get("crop_border", 0)), bool(mo.get("test_y_channel", False)), mo.get("image_range", 255)), kind)
+        return plan
+
+    def _validate_on_device(self, val_data, name, save_img, metrics_opt, on_device, sums, results):
+        """one validation batch of the device route: clamp on the device, hand ``self.output`` / ``self.gt`` to the accumulators without
+        ``get_current_visuals()``; the result travels to the host only for ``save_img`` or a metric that stayed on the host"""
+        from basicsr.metrics import MetricSums
+
+        result_dev = self.output.detach().float().clamp(0, 1)
+        host_metrics = [m for m in metrics_opt if m not in on_device] if hasattr(self, "gt") else []
+        result = result_dev.cpu() if (save_img or host_metrics) else None
+        if save_img:
+            import os
+
+            from PIL import Image
+
+            stem = osp.splitext(osp.basename(val_data["lq_path"][0]))[0]
+            folder = osp.join(self.opt["path"]["visualization"], name)
+            os.makedirs(folder, exist_ok=True)
+            Image.fromarray(tensor2img_rgb(result)).save(osp.join(folder, f"{stem}_{self.opt['name']}.png"))
+        if not hasattr(self, "gt") or not metrics_opt:
+            return
+        gt_dev = self.gt.detach().float().clamp(0, 1)
+        for key in dict.fromkeys(key for key, _ in on_device.values()):   # one accumulator (one launch pair) per distinct option set
+            if key not in sums:
+                kinds = {k for kk, k in on_device.values() if kk == key}
+                sums[key] = MetricSums(crop_border=key[0], test_y_channel=key[1], image_range=key[2], psnr="psnr" in kinds,
+                                       ssim="ssim" in kinds)
+            sums[key].add(result_dev, gt_dev)
+        if host_metrics:
+            gt = gt_dev.cpu().numpy()
+            for m in host_metrics:
+                results[m] += calculate_metric(dict(img=result.numpy(), img2=gt), metrics_opt[m])
 
     def save(self, epoch, current_iter):
         if hasattr(self, "net_g_ema"):

@@ -2,7 +2,7 @@
 """Secondary workloads of BASELINE.json (configs[2..4]) on ONE MI355X -- evidence for DESIGN.md, not the driver's
 contract (that is bench.py).  Prints one JSON line per workload.
 
-    python bench_extra.py --workload dcpt|dcpt_swinir|restormer|promptir|infer2k|naf|swinir|rcan [--dtype fp32|bf16] [--steps K] [--warmup W]
+    python bench_extra.py --workload dcpt|dcpt_swinir|restormer|promptir|infer2k|naf|swinir|rcan|val_metrics [--dtype fp32|bf16] [--steps K] [--warmup W]
 
 ``--dtype bf16`` (dcpt, naf, infer2k, restormer, promptir): every feature map of the encoder in bf16 storage with fp32 accumulation (act_dtype="bf16";
 dcpt: the classifier head too unless --head-dtype fp32); images, parameters and the optimizer stay fp32.  Its lines carry BOTH
@@ -295,9 +295,43 @@ def run_infer2k(dev, dtype="fp32", steps=5, warmup=2, S=2048, streams=2):
                 peak_mem_gb=round(torch.cuda.max_memory_allocated() / 2 ** 30, 2))
 
 
+def run_val_metrics(dev, steps=5, warmup=2, H=1080, W=2048):
+    """PSNR + SSIM of one 3 x H x W pair as validation scores it (crop_border 0, RGB, image_range 255): the host functions of
+    basicsr.metrics on the arrays SRModel.get_current_visuals hands them (one repetition, its three device-to-host copies included)
+    against calculate_psnr_device / calculate_ssim_device's kernel on the tensors where they are (sums fetched in one transfer)."""
+    from basicsr.metrics import MetricSums, calculate_psnr, calculate_ssim
+
+    g = torch.Generator(device=dev).manual_seed(1234)
+    gt = torch.rand((1, 3, H, W), generator=g, device=dev)
+    out = (gt + 0.05 * torch.randn((1, 3, H, W), generator=g, device=dev)).clamp(0, 1)
+    lq = torch.rand((1, 3, H, W), generator=g, device=dev)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    _, res_h, gt_h = lq.cpu(), out.cpu().clamp(0, 1).numpy(), gt.cpu().clamp(0, 1).numpy()
+    t_copy = time.perf_counter() - t0
+    psnr_h = calculate_psnr(res_h, gt_h, 0)
+    t_psnr = time.perf_counter() - t0 - t_copy
+    ssim_h = calculate_ssim(res_h, gt_h, 0)
+    t_host = time.perf_counter() - t0
+    vals = {}
+
+    def device():
+        acc = MetricSums(crop_border=0)
+        acc.add(out.clamp(0, 1), gt.clamp(0, 1))
+        vals.update(acc.result())
+
+    dt = timed(device, steps, warmup)
+    return dict(workload=f"validation metrics of one 3 x {H} x {W} pair: PSNR + SSIM, crop_border 0, RGB, image_range 255",
+                host_ms=round(t_host * 1e3, 2), host_copy_ms=round(t_copy * 1e3, 2), host_psnr_ms=round(t_psnr * 1e3, 2),
+                host_ssim_ms=round((t_host - t_copy - t_psnr) * 1e3, 2), host_repetitions=1,
+                device_ms=round(dt * 1e3, 3), steps=steps, warmup=warmup, psnr_host=psnr_h, psnr_device=vals["psnr"][0], ssim_host=ssim_h,
+                ssim_device=vals["ssim"][0], note="device_ms: clamp of both images + two launches + one 32-byte transfer, host clock around "
+                                                  "a synchronised region")
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", required=True, choices=["dcpt", "dcpt_swinir", "restormer", "promptir", "infer2k", "naf", "swinir", "rcan"])
+    ap.add_argument("--workload", required=True, choices=["dcpt", "dcpt_swinir", "restormer", "promptir", "infer2k", "naf", "swinir", "rcan", "val_metrics"])
     ap.add_argument("--dtype", default="fp32", choices=["fp32", "bf16", "bf16_tail32", "bf16_edge32"])
     ap.add_argument("--head-dtype", default=None, choices=["fp32", "bf16"], help="dcpt: classifier-head activations (default: --dtype)")
     ap.add_argument("--restormer-save", default="balanced", choices=["auto", "lean", "balanced", "full"], help="what the Restormer halves keep for backward")
@@ -473,6 +507,8 @@ def main():
         for line in lines[:-1]:
             print(json.dumps(line), flush=True)
         res = lines[-1]
+    elif args.workload == "val_metrics":
+        res = run_val_metrics(dev, args.steps, args.warmup)
     else:
         res = run_infer2k(dev, args.dtype, args.steps, args.warmup, args.size or 2048, args.tile_streams)
     res["peak_mem_gb"] = round(torch.cuda.max_memory_allocated() / 2 ** 30, 2)

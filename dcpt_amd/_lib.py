@@ -308,6 +308,8 @@ SIGNATURES = {
     "dcpt_bottleneck_bf16_ws_bytes": (sz, [cint, cint, cint, cint, cint]),
     "dcpt_bottleneck_fwd_bf16": (cint, [f32p, C.POINTER(BneckGroup), C.c_void_p, sz, cint, cint, cint, cint, stream_t]),
     "dcpt_bottleneck_bwd_bf16": (cint, [f32p, f32p, C.POINTER(BneckGroup), f32p, C.c_void_p, sz, cint, cint, cint, cint, stream_t]),
+    "dcpt_imgmetric_ws_bytes": (sz, [cint, cint, cint, cint, cint, cint]),
+    "dcpt_imgmetric": (cint, [f32p, f32p, C.c_void_p, C.c_void_p, C.c_void_p, sz, cint, cint, cint, cint, cint, cint, stream_t]),
     "dcpt_trace_enable": (cint, [cint]),
     "dcpt_trace_read": (sz, [C.c_char_p, sz]),
     "dcpt_prof_enable": (cint, [cint]),

@@ -295,3 +295,54 @@ extern "C" int dcpt_nchw_to_nhwc(const float* x, float* y, int B, int C, int HW,
 extern "C" int dcpt_nhwc_to_nchw(const float* x, float* y, int B, int C, int HW, dcpt_stream_t stream) {
     return launch_nhwc_to_nchw(x, y, B, C, HW, (hipStream_t)stream);
 }
+
+// ---------------------------------------------------------------------------------------------
+// validation metrics (metrics.hip)
+namespace {
+struct MetricWs {
+    double* ssim_part;
+    void* sse_part;
+};
+// 0 on success; the message names what is wrong with the shape / flags
+const char* metric_check(int B, int C, int H, int W, int crop, int flags) {
+    if (B <= 0 || H <= 0 || W <= 0) return "imgmetric: bad shape";
+    if (C != 1 && C != 3) return "imgmetric: C must be 1 or 3";
+    if (crop < 0) return "imgmetric: crop_border must be >= 0";
+    if (flags & ~(DCPT_METRIC_Y | DCPT_METRIC_SSIM | DCPT_METRIC_RANGE1)) return "imgmetric: unknown flag (image_range is 255, or 1 with DCPT_METRIC_RANGE1)";
+    if (H - 2 * crop <= 0 || W - 2 * crop <= 0) return "imgmetric: nothing left after the crop";
+    if ((flags & DCPT_METRIC_SSIM) && (H - 2 * crop < 11 || W - 2 * crop < 11)) return "imgmetric: SSIM needs a cropped image of at least 11 x 11";
+    if ((int64_t)B * C > 65535) return "imgmetric: B * C above 65535";
+    return nullptr;
+}
+size_t metric_layout(int B, int C, int H, int W, int crop, int flags, void* base, size_t bytes, MetricWs* out) {
+    WsAlloc a(base, base ? bytes : (size_t)-1);
+    const int Cp = ((flags & DCPT_METRIC_Y) && C == 3) ? 1 : C;
+    const size_t n = (size_t)B * Cp * metric_num_tiles(H - 2 * crop, W - 2 * crop);
+    MetricWs w{};
+    w.ssim_part = a.get<double>(n);
+    w.sse_part = a.get<uint64_t>(n);
+    if (out) *out = w;
+    return a.off;
+}
+}  // namespace
+
+extern "C" size_t dcpt_imgmetric_ws_bytes(int B, int C, int H, int W, int crop_border, int flags) {
+    if (metric_check(B, C, H, W, crop_border, flags)) return 0;
+    return metric_layout(B, C, H, W, crop_border, flags, nullptr, 0, nullptr);
+}
+
+extern "C" int dcpt_imgmetric(const float* img, const float* img2, void* sse_out, double* ssim_out, void* ws, size_t ws_bytes, int B, int C,
+                              int H, int W, int crop_border, int flags, dcpt_stream_t stream) {
+    const int want_ssim = (flags & DCPT_METRIC_SSIM) != 0;
+    DCPT_CHECK_ARG(img && img2 && sse_out && (ssim_out || !want_ssim), "imgmetric: null argument");
+    const char* bad = metric_check(B, C, H, W, crop_border, flags);
+    DCPT_CHECK_ARG(!bad, "%s (B=%d C=%d H=%d W=%d crop_border=%d flags=0x%x)", bad, B, C, H, W, crop_border, flags);
+    MetricWs m;
+    const size_t need = metric_layout(B, C, H, W, crop_border, flags, ws, ws_bytes, &m);
+    if (ws == nullptr || need > ws_bytes) {
+        dcpt_set_error("imgmetric: workspace too small");
+        return DCPT_ERR_WS;
+    }
+    return launch_imgmetric(img, img2, sse_out, ssim_out, m.ssim_part, m.sse_part, B, C, H, W, crop_border, (flags & DCPT_METRIC_Y) != 0,
+                            (flags & DCPT_METRIC_RANGE1) ? 1 : 255, want_ssim, (hipStream_t)stream);
+}

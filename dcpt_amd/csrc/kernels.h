@@ -172,3 +172,12 @@ int launch_mdta_dtemp_reduce(const float* part, float* dtemp, int B, int heads, 
 // GDFN weight packs with the hidden width padded to hp (modes of gdfn_pack_kernel / gdfn_unpack_kernel)
 int launch_gdfn_pack(const float* in, float* out, int c, int h, int hp, int mode, hipStream_t s);
 int launch_gdfn_unpack(const float* in, float* out, int c, int h, int hp, int mode, hipStream_t s);
+
+// ---- metrics.hip --------------------------------------------------------------------------
+// PSNR / SSIM sums of NCHW image pairs (dcpt_imgmetric).  One workgroup per METRIC_TH x METRIC_TW tile of SSIM-map positions of one
+// (image, scored channel); each writes one partial into ssim_part / sse_part [B * C'][metric_num_tiles], a second kernel adds them.
+#define METRIC_TH 16
+#define METRIC_TW 32
+int metric_num_tiles(int Hc, int Wc);
+int launch_imgmetric(const float* img, const float* img2, void* sse_out, double* ssim_out, double* ssim_part, void* sse_part, int B, int C,
+                     int H, int W, int crop, int luma, int range, int want_ssim, hipStream_t s);

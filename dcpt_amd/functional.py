@@ -2609,3 +2609,37 @@ def conv3conv_res(x, w1, b1, w2, b2, w3, b3, res):
     """the "3conv" residual as one autograd node; ``w2`` keeps its 1 x 1 kernel dims ([Cq][Cq][1][1])"""
     ps = (w1, b1, w2, b2, w3, b3)
     return _Conv3convResFn.apply(x, _wants_grad(x, res, *ps), res, *ps)
+
+
+# ------------------------------------------------------------------------------------------------
+# Validation metrics (include/dcpt_hip.h dcpt_imgmetric): the sums behind PSNR / SSIM of NCHW image pairs, no autograd, no host sync.
+METRIC_TILE = (16, 32)   # (TH, TW) of dcpt_amd/csrc/kernels.h: SSIM-map positions per workgroup (the tests aim at the tile edges)
+_METRIC_Y, _METRIC_SSIM, _METRIC_RANGE1 = 1, 2, 4
+
+
+def image_metric_sums(img, img2, crop_border=0, test_y_channel=False, image_range=255, ssim=True):
+    """``img`` / ``img2``: (B, C, H, W) fp32 device tensors in [0, 1], C in {1, 3}.  Returns ``(sse, ssim_sums)`` as device tensors, nothing
+    is synchronised: ``sse`` (B,) is the squared error per image after quantisation / crop / luma as basicsr.metrics forms it -- int64
+    (exact) for image_range 255 without luma, float64 otherwise; ``ssim_sums`` (B, C') float64 holds the sum of the SSIM map per scored
+    channel (C' = 1 for luma), or None with ``ssim=False``."""
+    lib = _lib.load()
+    if not (torch.is_tensor(img) and torch.is_tensor(img2)):
+        raise _lib.DcptHipError(f"image_metric_sums takes device tensors (got {type(img).__name__}); host arrays go to basicsr.metrics.calculate_psnr / calculate_ssim")
+    _require_gpu(img, img2)
+    if img.dim() != 4 or img.shape != img2.shape:
+        raise ValueError(f"expected two (B, C, H, W) tensors of one shape, got {tuple(img.shape)} and {tuple(img2.shape)}")
+    if image_range not in (255, 1):
+        raise ValueError(f"image_range {image_range}: the device metrics know 255 and 1")
+    img, img2 = _contig(img.detach()), _contig(img2.detach())
+    B, Cc, H, W = img.shape
+    dev = img.device
+    luma = bool(test_y_channel) and Cc == 3
+    flags = (_METRIC_Y if test_y_channel else 0) | (_METRIC_SSIM if ssim else 0) | (_METRIC_RANGE1 if image_range == 1 else 0)
+    crop = int(crop_border)
+    sse = torch.empty(B, dtype=torch.int64 if (image_range == 255 and not luma) else torch.float64, device=dev)
+    sums = torch.empty(B, 1 if luma else Cc, dtype=torch.float64, device=dev) if ssim else None
+    nws = lib.dcpt_imgmetric_ws_bytes(B, Cc, H, W, crop, flags)   # (0 for arguments the entry point refuses: it then names the reason)
+    ws = _workspace(dev, nws)
+    check(lib.dcpt_imgmetric(img.data_ptr(), img2.data_ptr(), sse.data_ptr(), _p(sums), ws.data_ptr(), nws, B, Cc, H, W, crop, flags,
+                             _stream(dev)), "dcpt_imgmetric")
+    return sse, sums

@@ -692,6 +692,27 @@ int dcpt_fused_bias_act(const float* x, const float* bias, const float* ref, flo
 int dcpt_nchw_to_nhwc(const float* x, float* y, int B, int C, int HW, dcpt_stream_t stream);
 int dcpt_nhwc_to_nchw(const float* x, float* y, int B, int C, int HW, dcpt_stream_t stream);
 
+/* ---- validation metrics: the sums behind PSNR and SSIM, on the device ----------------------------------
+ * replaces the host arithmetic of basicsr/metrics/psnr_ssim.py:11-75 (calculate_psnr), :113-183 (calculate_ssim) and :483-512 (_ssim)
+ * for a batch of image pairs that is already on the device.  img, img2: dense NCHW fp32 [B][C][H][W] with values in [0, 1], C in {1, 3}.
+ * Per element, as the reference does it: rintf(x * 255) in fp32 (round half to even; skipped with DCPT_METRIC_RANGE1), crop_border
+ * pixels dropped on every side by addressing, with DCPT_METRIC_Y and C == 3 the BT.601 luma ((24.966 b + 128.553 g + 65.481 r + 16) / 255
+ * in fp64 on value / image_range, rounded to fp32, times image_range) as ONE channel; then
+ *   sse_out[B]      the sum of squared differences of image b over its channels: int64 (exact) on the quantised RGB / gray path, i.e.
+ *                   image_range 255 without luma; fp64 on the luma and DCPT_METRIC_RANGE1 paths;
+ *   ssim_out[B][C'] fp64, the sum of the SSIM map (11-tap Gaussian, sigma 1.5, "valid" window, C1 = (0.01 L)^2, C2 = (0.03 L)^2, all in
+ *                   fp64) over its (H' - 10) x (W' - 10) positions, H' = H - 2 crop_border; C' = 1 for luma, C otherwise.  Written only
+ *                   with DCPT_METRIC_SSIM (may be NULL without it).
+ * The host divides by the counts and takes the logarithm.  Two launches on `stream`, no atomics: the same input gives the same bits.
+ * Errors (before any launch): null pointers, C not in {1, 3}, unknown flag bits, a cropped size <= 0, a cropped size under 11 with
+ * DCPT_METRIC_SSIM, workspace too small.  dcpt_imgmetric_ws_bytes needs no device and returns 0 for arguments dcpt_imgmetric refuses. */
+#define DCPT_METRIC_Y 1       /* test_y_channel */
+#define DCPT_METRIC_SSIM 2    /* also the SSIM sums */
+#define DCPT_METRIC_RANGE1 4  /* image_range = 1 (no quantisation); without it image_range = 255 */
+size_t dcpt_imgmetric_ws_bytes(int B, int C, int H, int W, int crop_border, int flags);
+int dcpt_imgmetric(const float* img, const float* img2, void* sse_out, double* ssim_out, void* ws, size_t ws_bytes, int B, int C, int H, int W,
+                   int crop_border, int flags, dcpt_stream_t stream);
+
 /* ---- optional launch profiling (bench.py) -------------------------------------------------------
  * While enabled, MFMA GEMM launches are bracketed by HIP events on their own stream: every launch for on = 1, every
  * on-th launch for on > 1 (sampling keeps the perturbation of a timed region small: an event pair costs ~3 us of queue time).
