@@ -79,6 +79,7 @@ class DCDistModel(SRModel):
         if self.cri_classify is None and self.cri_pixel is None:
             raise ValueError("Classify loss and Pixel loss are both None.")
         self.setup_optimizers()
+        self._setup_fused_step_tail()   # train.fused_step_tail (SRModel)
         if train_opt.get("scheduler"):
             self.setup_schedulers()
 
@@ -116,12 +117,16 @@ class DCDistModel(SRModel):
             l_total = l_total + l_classify
             loss_dict["l_classify"] = l_classify
         l_total.backward()
-        if self.grad_clip:
-            torch.nn.utils.clip_grad_norm_(self.net_g.parameters(), self.grad_clip)
-        self.optimizer_g.step()
+        fused_tail = getattr(self, "fused_step_tail", False)
+        if fused_tail:
+            self._fused_step_tail()
+        else:
+            if self.grad_clip:
+                torch.nn.utils.clip_grad_norm_(self.net_g.parameters(), self.grad_clip)
+            self.optimizer_g.step()
         self.hook_outputs = []
         self.log_dict = self.reduce_loss_dict(loss_dict)
-        if self.ema_decay > 0:
+        if self.ema_decay > 0 and not fused_tail:
             self.model_ema(decay=self.ema_decay)
 
     def test(self):

@@ -63,8 +63,39 @@ class SRModel(BaseModel):
         if self.cri_pix is None:
             raise ValueError("Both pixel and perceptual losses are None.")
         self.setup_optimizers()
+        self._setup_fused_step_tail()
         if train_opt.get("scheduler"):
             self.setup_schedulers()
+
+    def _setup_fused_step_tail(self):
+        """``train.fused_step_tail: true`` (opt-in): clip_grad_norm_, optimizer.step() and model_ema() of a step (reference
+        sr_model.py:166-174) as ONE call of the library optimizer (dcpt_amd.optim.FusedAdamW.step(max_grad_norm=, ema=)): the norm and the
+        clip coefficient stay on the device, the AdamW kernel applies the coefficient and updates the EMA copy.  Unlike the default route it
+        leaves ``p.grad`` unscaled.  Needs ``optim_g: {type: AdamW, fused: true}`` on the GPU; with any other optimizer the default route
+        is kept and a warning says so."""
+        self.fused_step_tail = False
+        if not self.opt["train"].get("fused_step_tail", False):
+            return
+        from dcpt_amd.optim import FusedAdamW
+
+        if isinstance(self.optimizer_g, FusedAdamW):
+            self.fused_step_tail = True
+        else:
+            get_root_logger().warning(f"train.fused_step_tail needs optim_g {{type: AdamW, fused: true}} on CUDA parameters; optimizer_g is "
+                                      f"{type(self.optimizer_g).__name__}: keeping clip_grad_norm_ / step / model_ema.")
+
+    def _fused_step_tail(self):
+        """the one call that replaces clip + step + EMA; under DDP it runs after backward(), on the all-reduced gradients"""
+        from dcpt_amd import functional as DF
+
+        ema = None
+        if getattr(self, "ema_decay", 0) > 0:
+            if getattr(self, "_ema_map", None) is None:   # by name, as model_ema: every named parameter of the EMA network
+                src = dict(self.get_bare_model(self.net_g).named_parameters())
+                self._ema_map = {src[k]: v for k, v in self.net_g_ema.named_parameters()}
+            ema = (self._ema_map, self.ema_decay)
+        self.optimizer_g.step(max_grad_norm=self.grad_clip or None, ema=ema)
+        DF.invalidate_packed_weights()   # (as model_ema: net_g_ema's parameters have new values)
 
     def _init_ema(self, only_if_checkpoint_has_ema=False):
         """reference sr_model.py:70-79: with a pretrained / resumed network the EMA copy is loaded from the checkpoint's
@@ -106,11 +137,15 @@ class SRModel(BaseModel):
         l_pix = self.cri_pix(self.output, self.gt)
         loss_dict["l_pix"] = l_pix
         l_pix.backward()
-        if self.grad_clip:
-            torch.nn.utils.clip_grad_norm_(self.net_g.parameters(), self.grad_clip)
-        self.optimizer_g.step()
+        fused_tail = getattr(self, "fused_step_tail", False)
+        if fused_tail:
+            self._fused_step_tail()
+        else:
+            if self.grad_clip:
+                torch.nn.utils.clip_grad_norm_(self.net_g.parameters(), self.grad_clip)
+            self.optimizer_g.step()
         self.log_dict = self.reduce_loss_dict(loss_dict)
-        if getattr(self, "ema_decay", 0) > 0:
+        if getattr(self, "ema_decay", 0) > 0 and not fused_tail:
             self.model_ema(decay=self.ema_decay)
 
     # -- inference -----------------------------------------------------------------------------

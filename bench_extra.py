@@ -2,7 +2,7 @@
 """Secondary workloads of BASELINE.json (configs[2..4]) on ONE MI355X -- evidence for DESIGN.md, not the driver's
 contract (that is bench.py).  Prints one JSON line per workload.
 
-    python bench_extra.py --workload dcpt|dcpt_swinir|restormer|promptir|infer2k|naf|swinir|rcan|val_metrics [--dtype fp32|bf16] [--steps K] [--warmup W]
+    python bench_extra.py --workload dcpt|dcpt_swinir|restormer|promptir|infer2k|naf|swinir|rcan|val_metrics|step_tail [--dtype fp32|bf16] [--steps K] [--warmup W]
 
 ``--dtype bf16`` (dcpt, naf, infer2k, restormer, promptir): every feature map of the encoder in bf16 storage with fp32 accumulation (act_dtype="bf16";
 dcpt: the classifier head too unless --head-dtype fp32); images, parameters and the optimizer stay fp32.  Its lines carry BOTH
@@ -51,7 +51,8 @@ def timed(fn, steps, warmup):
     return dt
 
 
-def run_restormer(dev, save="balanced", steps=5, warmup=2, B=64, S=128, rank=0, world=1, dtype="fp32"):
+def run_restormer(dev, save="balanced", steps=5, warmup=2, B=64, S=128, rank=0, world=1, dtype="fp32", grad_clip=0.0, ema_decay=0.0,
+                  fused_step_tail=False):
     """BASELINE.json configs[3]: Restormer defaults (reference restormer_arch.py:234-422), fwd + L1 + bwd (+ gradient all-reduce: the network
     in DistributedDataParallel as base_model.py:108-115 wraps it, when world > 1) + AdamW, fp32; dtype "bf16": act_dtype="bf16" (feature
     maps in bf16 storage, fp32 accumulation / parameters / optimizer), reported against the bf16 MFMA peak."""
@@ -76,10 +77,24 @@ def run_restormer(dev, save="balanced", steps=5, warmup=2, B=64, S=128, rank=0, 
     lq = torch.rand((B, 3, S, S), generator=g, device=dev)
     gt = torch.rand((B, 3, S, S), generator=g, device=dev)
 
+    # --grad-clip / --ema-decay: the step tail of SRModel.optimize_parameters (clip_grad_norm_, step, model_ema's foreach pair), or with
+    # --fused-step-tail the one call of train.fused_step_tail
+    params = list(bare.parameters())
+    ema = [p.detach().clone() for p in params] if ema_decay > 0 else None
+    ema_arg = (dict(zip(params, ema)), ema_decay) if ema is not None else None
+
     def step():
         optm.zero_grad(set_to_none=True)
         (net(lq) - gt).abs().mean().backward()
+        if fused_step_tail:
+            optm.step(max_grad_norm=grad_clip or None, ema=ema_arg)
+            return
+        if grad_clip:
+            torch.nn.utils.clip_grad_norm_(params, grad_clip)
         optm.step()
+        if ema is not None:
+            torch._foreach_mul_(ema, ema_decay)
+            torch._foreach_add_(ema, [p.detach() for p in params], alpha=1 - ema_decay)
 
     dt = timed(step, steps, warmup)
     flops = B * (S / 128.0) ** 2 * 232e9      # 77.45 GF fwd -> 232 GF fwd+bwd per 128^2 image
@@ -88,7 +103,8 @@ def run_restormer(dev, save="balanced", steps=5, warmup=2, B=64, S=128, rank=0, 
                          "(BASELINE.json configs[3])",
                 ms_per_step=round(dt * 1e3, 2), megapixels_per_s=round(world * B * S * S / 1e6 / dt, 3), steps=steps, warmup=warmup,
                 alg_tflops=round(flops / dt / 1e12, 2), mfma_frac=round(flops / dt / peak, 4),
-                peak_mem_gb=round(torch.cuda.max_memory_allocated() / 2 ** 30, 2))
+                peak_mem_gb=round(torch.cuda.max_memory_allocated() / 2 ** 30, 2),
+                **(dict(grad_clip=grad_clip, ema_decay=ema_decay, fused_step_tail=bool(fused_step_tail)) if (grad_clip or ema_decay) else {}))
 
 
 def run_promptir(dev, save="balanced", steps=5, warmup=2, B=32, S=128, dtype="fp32"):
@@ -329,9 +345,73 @@ def run_val_metrics(dev, steps=5, warmup=2, H=1080, W=2048):
                                                   "a synchronised region")
 
 
+def run_step_tail(dev, steps=50, warmup=5, rounds=7, max_norm=1.0, decay=0.999):
+    """The tail of a fine-tuning step (reference sr_model.py:166-174) on the parameter list of NAFNet-64 [1,1,1,28] -- shapes only, no
+    forward, random gradients: clip_grad_norm_ + FusedAdamW.step() + the _foreach_mul_ / _foreach_add_ pair of model_ema (the torch route)
+    against the one call FusedAdamW.step(max_grad_norm=, ema=).  Each on its own copy of the list, alternating, ``rounds`` windows of
+    ``steps`` steps each, the median window of each; launch counts of one step from the library's launch trace (it sees the library's
+    kernels only: the foreach kernels of the torch route are not in it)."""
+    import ctypes
+    import statistics
+
+    from basicsr.archs import build_network
+    from dcpt_amd import _lib
+    from dcpt_amd.optim import FusedAdamW
+
+    shapes = [tuple(p.shape) for p in build_network(dict(type="NAFNetBaseline", **NAF)).parameters()]
+    g = torch.Generator(device=dev).manual_seed(1234)
+
+    def make():
+        ps = [torch.nn.Parameter(torch.randn(s, generator=g, device=dev) * 0.05) for s in shapes]
+        for p in ps:
+            p.grad = torch.randn(p.shape, generator=g, device=dev) * 1e-3
+        return ps, [p.detach().clone() for p in ps], FusedAdamW(ps, lr=1e-4, betas=(0.9, 0.9), weight_decay=0.0)
+
+    (pa, ea, oa), (pb, eb, ob) = make(), make()
+    ema_b = (dict(zip(pb, eb)), decay)
+
+    def torch_route_plain():
+        torch.nn.utils.clip_grad_norm_(pa, max_norm)
+        oa.step()
+        torch._foreach_mul_(ea, decay)
+        torch._foreach_add_(ea, [p.detach() for p in pa], alpha=1 - decay)
+
+    def fused():
+        ob.step(max_grad_norm=max_norm, ema=ema_b)
+
+    def trace(fn):
+        lib = _lib.load()
+        lib.dcpt_trace_enable(1)
+        fn()
+        need = lib.dcpt_trace_read(None, 0)
+        buf = ctypes.create_string_buffer(int(need) + 16)
+        lib.dcpt_trace_read(buf, len(buf))
+        lib.dcpt_trace_enable(0)
+        return {ln.rpartition(" ")[0]: int(ln.rpartition(" ")[2]) for ln in buf.value.decode().splitlines() if ln.strip()}
+
+    for fn in (torch_route_plain, fused):
+        for _ in range(warmup):
+            fn()
+    launches_torch, launches_fused = trace(torch_route_plain), trace(fused)
+    ta, tb = [], []
+    for _ in range(rounds):
+        ta.append(timed(torch_route_plain, steps, 1))
+        tb.append(timed(fused, steps, 1))
+    numel = sum(p.numel() for p in pa)
+    mt, mf = statistics.median(ta), statistics.median(tb)
+    return dict(workload=f"step tail on the NAFNet-64 [1,1,1,28] parameter list ({len(shapes)} tensors, {numel / 1e6:.1f} M parameters): clip + AdamW + EMA",
+                torch_route_ms=round(mt * 1e3, 4), fused_ms=round(mf * 1e3, 4), ratio=round(mt / mf, 3),
+                torch_route_ms_windows=[round(t * 1e3, 4) for t in ta], fused_ms_windows=[round(t * 1e3, 4) for t in tb],
+                steps_per_window=steps, rounds=rounds, library_launches_torch_route=launches_torch, library_launches_fused=launches_fused,
+                alg_gbytes_torch_route=round(15 * 4 * numel / 1e9, 2), alg_gbytes_fused=round(10 * 4 * numel / 1e9, 2),
+                fused_hbm_frac=round(10 * 4 * numel / mf / 8e12, 4),
+                note="torch route = clip_grad_norm_ + FusedAdamW.step() + _foreach_mul_/_foreach_add_; host clock around synchronised windows, "
+                     "the two routes alternating in one process; max_norm below the gradient norm: both routes multiply every gradient")
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", required=True, choices=["dcpt", "dcpt_swinir", "restormer", "promptir", "infer2k", "naf", "swinir", "rcan", "val_metrics"])
+    ap.add_argument("--workload", required=True, choices=["dcpt", "dcpt_swinir", "restormer", "promptir", "infer2k", "naf", "swinir", "rcan", "val_metrics", "step_tail"])
     ap.add_argument("--dtype", default="fp32", choices=["fp32", "bf16", "bf16_tail32", "bf16_edge32"])
     ap.add_argument("--head-dtype", default=None, choices=["fp32", "bf16"], help="dcpt: classifier-head activations (default: --dtype)")
     ap.add_argument("--restormer-save", default="balanced", choices=["auto", "lean", "balanced", "full"], help="what the Restormer halves keep for backward")
@@ -341,6 +421,9 @@ def main():
                     "mix: a gather copy forward; a zero fill, a strided scatter and a full-map add backward) instead of dcpt_mix_stride_* / dcpt_grid_add")
     ap.add_argument("--upsampler", default="", choices=["", "pixelshuffle", "pixelshuffledirect", "nearest+conv"], help="swinir: super-resolution tail")
     ap.add_argument("--upscale", type=int, default=1, help="swinir: scale of --upsampler")
+    ap.add_argument("--grad-clip", type=float, default=0.0, help="restormer: clip_grad_norm_ before the optimizer step (grad_clip of the YAML)")
+    ap.add_argument("--ema-decay", type=float, default=0.0, help="restormer: EMA copy of the parameters updated after the step (train.ema_decay)")
+    ap.add_argument("--fused-step-tail", action="store_true", help="restormer: clip + step + EMA as the one call of train.fused_step_tail")
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--tile-streams", type=int, default=2, help="infer2k: HIP streams the tile batches run on (tile.streams)")
@@ -491,7 +574,7 @@ def main():
         if args.dtype not in ("fp32", "bf16"):
             raise SystemExit("--workload restormer: --dtype fp32 or bf16")
         res = run_restormer(dev, args.restormer_save, args.steps, args.warmup, args.batch or 64, args.size or 128, rank=rank, world=world,
-                            dtype=args.dtype)
+                            dtype=args.dtype, grad_clip=args.grad_clip, ema_decay=args.ema_decay, fused_step_tail=args.fused_step_tail)
     elif args.workload == "promptir":
         if args.dtype not in ("fp32", "bf16"):
             raise SystemExit("--workload promptir: --dtype fp32 or bf16")
@@ -509,6 +592,8 @@ def main():
         res = lines[-1]
     elif args.workload == "val_metrics":
         res = run_val_metrics(dev, args.steps, args.warmup)
+    elif args.workload == "step_tail":
+        res = run_step_tail(dev, max(args.steps, 20), args.warmup)
     else:
         res = run_infer2k(dev, args.dtype, args.steps, args.warmup, args.size or 2048, args.tile_streams)
     res["peak_mem_gb"] = round(torch.cuda.max_memory_allocated() / 2 ** 30, 2)

@@ -317,6 +317,10 @@ SIGNATURES = {
     "dcpt_set_side_stream": (cint, [cint]),
     "dcpt_adamw_step": (cint, [cint, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                C.POINTER(C.c_int64), C.c_void_p, stream_t]),
+    "dcpt_adamw_step_ex": (cint, [cint, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                  C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_void_p, f32p, C.c_double, stream_t]),
+    "dcpt_grad_norm_ws_bytes": (sz, [cint, C.POINTER(C.c_int64)]),
+    "dcpt_grad_norm": (cint, [cint, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_float, C.c_void_p, sz, f32p, stream_t]),
     "dcpt_allreduce_flat": (cint, [f32p, sz, C.c_void_p, C.c_float, stream_t]),
     "dcpt_nchw_to_nhwc": (cint, [f32p, f32p, cint, cint, cint, stream_t]),
     "dcpt_nhwc_to_nchw": (cint, [f32p, f32p, cint, cint, cint, stream_t]),

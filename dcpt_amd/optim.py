@@ -101,8 +101,153 @@ class FusedAdamW(torch.optim.Optimizer):
         plans[gi] = plan
         return plan
 
+    def _grads_of(self, plan):
+        """this step's gradients of a plan's parameters, in the parameters' layout (a gradient of another dtype / layout / device is replaced by
+        a copy in place of ``p.grad``: the update walks the four storages in step)"""
+        gs = []
+        for p, strd in zip(plan["ps"], plan["strides"]):
+            g = p.grad
+            if g.dtype != torch.float32 or g.stride() != strd or g.device != p.device or g.is_sparse:
+                if g.is_sparse:
+                    raise RuntimeError("FusedAdamW does not support sparse gradients")
+                g2 = torch.empty_like(p)
+                g2.copy_(g)
+                g = p.grad = g2
+            gs.append(g)
+        return gs
+
+    @staticmethod
+    def _hparams(group, t):
+        b1, b2 = group["betas"]
+        return _HParams(float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]),
+                        1.0 - float(b1) ** t, 1.0 - float(b2) ** t, int(bool(group["maximize"])))
+
     @torch.no_grad()
-    def step(self, closure=None):
+    def step(self, closure=None, *, max_grad_norm=None, ema=None):
+        """One AdamW step.  With the two keyword arguments it is the whole tail of a fine-tuning step (reference sr_model.py:166-174:
+        ``clip_grad_norm_``, ``optimizer.step()``, ``model_ema()``) in one call:
+
+        ``max_grad_norm``: clip by the global 2-norm over the gradients of ALL param groups, as ``torch.nn.utils.clip_grad_norm_(params,
+        max_grad_norm)`` with ``error_if_nonfinite=False``.  Norm and coefficient are computed and kept on the device (dcpt_grad_norm) and
+        the AdamW kernel multiplies the gradient by the coefficient in registers: ``p.grad`` is NOT scaled in place -- the one observable
+        difference from the torch route.  Afterwards ``self.grad_norm`` is a one-element fp32 device tensor with the pre-clip total norm
+        (what ``clip_grad_norm_`` returns); the library never reads it back.
+
+        ``ema = (mapping, decay)``: ``mapping[p]`` is the EMA copy of parameter ``p``; every entry becomes ``decay * e + (1 - decay) * p``
+        with the stepped ``p`` (reference base_model.py:86-95).  An fp32 copy on the parameter's device with the parameter's strides is
+        updated by the AdamW kernel itself; every other entry -- a parameter without a gradient this step, a frozen one, one that is not
+        this optimizer's, another layout -- by a ``_foreach_mul_`` / ``_foreach_add_`` pair over exactly those.  Hand in the same mapping
+        object every step: which entries ride in the kernel is planned once per mapping."""
+        if max_grad_norm is None and ema is None:
+            return self._step_plain(closure)
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        lib = _lib.load()
+        work = []
+        for gi, group in enumerate(self.param_groups):
+            plan = self._plan(gi, group)
+            if plan["n"] == 0:
+                continue
+            if not plan["one_device"]:
+                raise RuntimeError("FusedAdamW: the parameters of a group must live on one device")
+            work.append((group, plan, self._grads_of(plan)))
+        coef_ptr = None
+        if max_grad_norm is not None:
+            coef_ptr = self._grad_norm(lib, work, float(max_grad_norm))
+        mapping, decay, riders, rest = None, 0.0, None, None
+        if ema is not None:
+            mapping, decay = ema[0], float(ema[1])
+            riders, rest = self._ema_plan(mapping, [plan for _, plan, _ in work])
+        for wi, (group, plan, gs) in enumerate(work):
+            ps, es = plan["ps"], (riders[wi] if riders is not None else None)
+            steps = {st["step"] for st in plan["states"]}
+            dev = plan["dev"]
+            with torch.cuda.device(dev):
+                stream = torch.cuda.current_stream(dev).cuda_stream
+                for t0 in steps:
+                    h = self._hparams(group, t0 + 1.0)
+                    sel = range(plan["n"]) if len(steps) == 1 else [i for i, st in enumerate(plan["states"]) if st["step"] == t0]
+                    # tensors whose EMA copy rides in the kernel, and the others
+                    parts = [(sel, False)] if es is None else [([i for i in sel if es[i] is not None], True), ([i for i in sel if es[i] is None], False)]
+                    for idx, with_ema in parts:
+                        if len(idx) == 0:
+                            continue
+                        arr = C.c_void_p * len(idx)
+                        whole = len(idx) == plan["n"]
+                        rc = lib.dcpt_adamw_step_ex(
+                            len(idx), arr(*[ps[i].data_ptr() for i in idx]), arr(*[gs[i].data_ptr() for i in idx]),
+                            plan["m_ptr"] if whole else arr(*[plan["m"][i].data_ptr() for i in idx]),
+                            plan["v_ptr"] if whole else arr(*[plan["v"][i].data_ptr() for i in idx]),
+                            arr(*[es[i].data_ptr() for i in idx]) if with_ema else None,
+                            plan["numel"] if whole else (C.c_int64 * len(idx))(*[ps[i].numel() for i in idx]), C.byref(h), coef_ptr, decay, stream)
+                        _lib.check(rc, "dcpt_adamw_step_ex")
+            for st in plan["states"]:
+                st["step"] += 1.0
+            torch.autograd.graph.increment_version(ps)
+            if es is not None:
+                torch.autograd.graph.increment_version([e for e in es if e is not None])
+        if rest:   # (the foreach kernels bump the versions themselves)
+            torch._foreach_mul_(rest[0], decay)
+            torch._foreach_add_(rest[0], rest[1], alpha=1 - decay)
+        return loss
+
+    def _grad_norm(self, lib, work, max_norm):
+        """dcpt_grad_norm over the gradients of every group; returns the device address of the clip coefficient.  The workspace and the
+        two result floats live on the optimizer and grow only with the block count."""
+        gs = [g for _, _, glist in work for g in glist]
+        devs = {plan["dev"] for _, plan, _ in work}
+        if len(devs) > 1:
+            raise RuntimeError("FusedAdamW: max_grad_norm needs every parameter on one device")
+        d = self.__dict__
+        if not gs:
+            dev = self.param_groups[0]["params"][0].device
+        else:
+            dev = gs[0].device
+        out = d.get("_gn_out")
+        if out is None or out.device != dev:
+            out = d["_gn_out"] = torch.zeros(2, dtype=torch.float32, device=dev)
+            d["_gn_ws"] = None
+        n = len(gs)
+        numel = (C.c_int64 * n)(*[g.numel() for g in gs])
+        need = int(lib.dcpt_grad_norm_ws_bytes(n, numel))
+        ws = d.get("_gn_ws")
+        if ws is None or ws.numel() * 8 < need:
+            ws = d["_gn_ws"] = torch.empty(max(1, need // 8), dtype=torch.float64, device=dev)
+        with torch.cuda.device(dev):
+            rc = lib.dcpt_grad_norm(n, (C.c_void_p * n)(*[g.data_ptr() for g in gs]), numel, max_norm, ws.data_ptr(), ws.numel() * 8,
+                                    out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(rc, "dcpt_grad_norm")
+        self.grad_norm = out[0:1]
+        return out.data_ptr() + 4
+
+    def _ema_plan(self, mapping, plans):
+        """(per plan: the EMA copy of each stepped parameter that rides in the kernel or None, ([copies], [parameters]) of every other entry
+        of ``mapping`` or None); planned once per mapping object and set of plans"""
+        c = self.__dict__.get("_ema_cache")
+        if c is not None and c["mapping"] is mapping and len(c["plans"]) == len(plans) and all(a is b for a, b in zip(c["plans"], plans)) \
+                and c["len"] == len(mapping):
+            return c["riders"], c["rest"]
+        riders, covered = [], set()
+        for plan in plans:
+            es = []
+            for p in plan["ps"]:
+                e = mapping.get(p)
+                ok = e is not None and e.dtype == torch.float32 and e.device == p.device and e.shape == p.shape and e.stride() == p.stride() \
+                    and e.layout == torch.strided and id(p) not in covered
+                if ok:
+                    covered.add(id(p))
+                es.append(e if ok else None)
+            riders.append(es)
+        dst = [e for p, e in mapping.items() if id(p) not in covered]
+        src = [p for p in mapping if id(p) not in covered]   # (the parameters themselves: ``p.data = ...`` may swap their storage)
+        rest = (dst, src) if dst else None
+        self.__dict__["_ema_cache"] = dict(mapping=mapping, plans=list(plans), len=len(mapping), riders=riders, rest=rest)
+        return riders, rest
+
+    @torch.no_grad()
+    def _step_plain(self, closure=None):
         loss = None
         if closure is not None:
             with torch.enable_grad():

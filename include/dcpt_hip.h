@@ -746,6 +746,31 @@ typedef struct {
 int dcpt_adamw_step(int n, float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
                     const int64_t* numel, const dcpt_adamw_hparams* h, dcpt_stream_t stream);
 
+/* ---- fused step tail: gradient-norm clip and EMA around the AdamW kernel ---------------------------------------
+ * replaces the three calls that end a fine-tuning step of the reference, sr_model.py:166-174 (clip_grad_norm_(parameters, max_norm),
+ * optimizer.step(), model_ema(decay)) with base_model.py:86-95 (model_ema: ema = decay ema + (1 - decay) p per parameter).
+ *
+ * dcpt_grad_norm: the global 2-norm of a LIST of fp32 gradients and torch's clip coefficient, both left in DEVICE memory:
+ *     out2[0] = norm = (float)sqrt(sum g^2), the squares accumulated in fp64 (one double per 4096-element block in `workspace`, summed
+ *     in a fixed order: two calls on the same data give the same bits);  out2[1] = coef = min(1, max_norm / (norm + 1e-6)) in fp32, a
+ *     NaN norm giving a NaN coefficient (clip_grad_norm_ with error_if_nonfinite=False).
+ * `grads / numel` are HOST arrays of n entries (0 <= numel < 2^32 - 4096; empty entries are skipped and may be null).  `workspace` holds
+ * dcpt_grad_norm_ws_bytes(n, numel) bytes = 8 x sum ceil(numel / 4096) (the query needs no device; 0 for an invalid list).  One launch
+ * per 80 non-empty tensors and one single-block launch that writes out2 -- also when every tensor is empty ({0, 1}).  Arguments are
+ * checked before the first launch.
+ *
+ * dcpt_adamw_step_ex: dcpt_adamw_step with two optional stages in the same kernel.  clip_coef != NULL: a DEVICE pointer to one float
+ * (out2 + 1 of dcpt_grad_norm), g *= *clip_coef before the update -- the gradient buffers themselves are NOT scaled.  ema != NULL: a
+ * HOST array of n device pointers, tensor i laid out as params[i]; after the update ema[i] = ema[i] ema_decay + (1 - ema_decay) p_new
+ * (the product rounded, then one fused multiply-add: the rounding of torch's _foreach_mul_ / _foreach_add_(alpha) pair).  With both
+ * NULL it is dcpt_adamw_step. */
+size_t dcpt_grad_norm_ws_bytes(int n, const int64_t* numel);
+int dcpt_grad_norm(int n, const float* const* grads, const int64_t* numel, float max_norm, void* workspace, size_t workspace_bytes,
+                   float* out2, dcpt_stream_t stream);
+int dcpt_adamw_step_ex(int n, float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                       float* const* ema, const int64_t* numel, const dcpt_adamw_hparams* h, const float* clip_coef, double ema_decay,
+                       dcpt_stream_t stream);
+
 /* ---- gradient all-reduce (data-parallel step) -------------------------------------------------------
  * replaces what torch DistributedDataParallel does for the reference (basicsr/models/base_model.py:108-115: bucketed
  * all-reduce(SUM) / world of the gradients; :448 the loss reduce) for hosts that drive the collective themselves:
