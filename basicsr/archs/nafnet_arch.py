@@ -104,8 +104,10 @@ class NAFBlock(nn.Module):
         if isinstance(pool, AvgPool2d) and pool.kernel_size is not None:
             k1, k2 = int(pool.kernel_size[0]), int(pool.kernel_size[1])
             if not (k1 >= inp.shape[-2] and k2 >= inp.shape[-1]):  # arch_util.py:352-353: window covers the map -> global mean
-                if self.act_bf16:
-                    raise NotImplementedError("the TLSC (local-mean SCA) block is fp32 only: build NAFNet with act_dtype='fp32'")
+                if self.act_bf16:   # bf16 in / out on the bf16 local-mean kernels, the block's weight pack shared with the global form
+                    if getattr(self, "_packed_bf16", None) is None:
+                        self._packed_bf16 = DF.PackedWeightsBf16()
+                    return DF.nafblock_local_bf16(DF.to_bf16(inp), self.fused_params(), k1, k2, self._packed_bf16)
                 return DF.nafblock_local(inp, self.fused_params(), k1, k2)
         if self.act_bf16:   # bf16 in / out (an fp32 input -- a block used on its own -- is cast once)
             if getattr(self, "_packed_bf16", None) is None:
@@ -202,7 +204,8 @@ class NAFNetBaseline(nn.Module):
             # instead of 36); the blocks then find their pack current
             blocks = self.__dict__.get("_bf16_blocks")
             if blocks is None:   # (a plain attribute, not a registered submodule list; rebuilt by set_act_dtype)
-                blocks = [m for m in self.modules() if isinstance(m, NAFBlock) and m.act_bf16 and not m.local_sca()]
+                # (TLSC blocks included: dcpt_nafblock_local_fwd_bf16 reads the same pack)
+                blocks = [m for m in self.modules() if isinstance(m, NAFBlock) and m.act_bf16]
                 for m in blocks:
                     if getattr(m, "_packed_bf16", None) is None:
                         m._packed_bf16 = DF.PackedWeightsBf16()
@@ -240,7 +243,9 @@ class NAFNetBaseline(nn.Module):
 @ARCH_REGISTRY.register()
 class NAFNet(Local_Base, NAFNetBaseline):
     """TLSC test-time variant (reference nafnet_arch.py:277-288): every SCA global mean becomes a local box mean of
-    1.5 x the training patch size (scaled per level); inference only."""
+    1.5 x the training patch size (scaled per level); inference only.  With a bf16 ``act_dtype`` the blocks in bf16 storage run
+    ``dcpt_nafblock_local_fwd_bf16`` and the groups that the mixed modes keep in fp32 (``set_act_dtype``) run ``dcpt_nafblock_local_fwd``;
+    the 0.01-dB statement for ``bf16_edge32`` was established for the global-mean network and has not been re-measured for TLSC."""
 
     def __init__(self, *args, train_size=(1, 3, 128, 128), fast_imp=False, **kwargs):
         Local_Base.__init__(self)

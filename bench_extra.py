@@ -2,7 +2,7 @@
 """Secondary workloads of BASELINE.json (configs[2..4]) on ONE MI355X -- evidence for DESIGN.md, not the driver's
 contract (that is bench.py).  Prints one JSON line per workload.
 
-    python bench_extra.py --workload dcpt|dcpt_swinir|restormer|promptir|infer2k|naf|swinir|rcan|val_metrics|step_tail [--dtype fp32|bf16] [--steps K] [--warmup W]
+    python bench_extra.py --workload dcpt|dcpt_swinir|restormer|promptir|infer2k|naf|swinir|rcan|val_metrics|step_tail|tlsc [--dtype fp32|bf16] [--steps K] [--warmup W]
 
 ``--dtype bf16`` (dcpt, naf, infer2k, restormer, promptir): every feature map of the encoder in bf16 storage with fp32 accumulation (act_dtype="bf16";
 dcpt: the classifier head too unless --head-dtype fp32); images, parameters and the optimizer stay fp32.  Its lines carry BOTH
@@ -311,6 +311,46 @@ def run_infer2k(dev, dtype="fp32", steps=5, warmup=2, S=2048, streams=2):
                 peak_mem_gb=round(torch.cuda.max_memory_allocated() / 2 ** 30, 2))
 
 
+def run_tlsc(dev, steps=5, warmup=2, H=1080, W=2048, tile=0, streams=2, dtypes=("fp32", "bf16", "bf16_tail32", "bf16_edge32")):
+    """The reference's large-image variant, ``NAFNet`` (TLSC: every SCA mean a local box mean of 1.5 x train_size, scaled per level; reference
+    nafnet_arch.py:277-288), NAFNet-64 with train_size 256 on one 3 x H x W image, in all four feature-map storage modes: whole image
+    (pre_test pads to a multiple of 16) or, with ``tile`` > 0, through SRModel.test_tile with tile_pad 16.  ms per image per mode, the fp32
+    number of the same run as the baseline."""
+    from basicsr.models import build_model
+    from dcpt_amd import functional as DF
+    from dcpt_amd.keyed_init import fill_module_
+
+    g = torch.Generator(device=dev).manual_seed(1234)
+    img = torch.rand((1, 3, H, W), generator=g, device=dev)
+    ms, mem = {}, {}
+    for dt in dtypes:
+        torch.cuda.reset_peak_memory_stats()
+        opt = dict(name="b", model_type="SRModel", scale=1, num_gpu=1, dist=False, rank=0, world_size=1, is_train=False,
+                   network_g=dict(type="NAFNet", train_size=(1, 3, 256, 256), window_size=16, **dict(NAF, act_dtype=dt)), path=dict(),
+                   val=dict(save_img=False))
+        if tile:
+            opt["tile"] = dict(infer_size=tile, tile_pad=16, streams=streams)
+        m = build_model(opt)
+        fill_module_(m.net_g)
+
+        def run():
+            m.feed_data({"lq": img})
+            m.pre_test()
+            m.test_tile() if tile else m.test()
+            m.post_test()
+
+        ms[dt] = round(timed(run, steps, warmup) * 1e3, 2)
+        mem[dt] = round(torch.cuda.max_memory_allocated() / 2 ** 30, 2)
+        del m
+        DF.release_workspaces()
+        torch.cuda.empty_cache()
+    how = f"test_tile infer_size {tile} / tile_pad 16 on {streams} stream(s)" if tile else "whole image"
+    base = ms.get("fp32")
+    return dict(workload=f"NAFNet-64 TLSC inference (NAFNet, train_size 256), 3x{H}x{W}, {how}", ms_per_image=ms,
+                speedup_vs_fp32={k: round(base / v, 2) for k, v in ms.items()} if base else None, peak_mem_gb_per_mode=mem, steps=steps,
+                warmup=warmup)
+
+
 def run_val_metrics(dev, steps=5, warmup=2, H=1080, W=2048):
     """PSNR + SSIM of one 3 x H x W pair as validation scores it (crop_border 0, RGB, image_range 255): the host functions of
     basicsr.metrics on the arrays SRModel.get_current_visuals hands them (one repetition, its three device-to-host copies included)
@@ -411,7 +451,7 @@ def run_step_tail(dev, steps=50, warmup=5, rounds=7, max_norm=1.0, decay=0.999):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", required=True, choices=["dcpt", "dcpt_swinir", "restormer", "promptir", "infer2k", "naf", "swinir", "rcan", "val_metrics", "step_tail"])
+    ap.add_argument("--workload", required=True, choices=["dcpt", "dcpt_swinir", "restormer", "promptir", "infer2k", "naf", "swinir", "rcan", "val_metrics", "step_tail", "tlsc"])
     ap.add_argument("--dtype", default="fp32", choices=["fp32", "bf16", "bf16_tail32", "bf16_edge32"])
     ap.add_argument("--head-dtype", default=None, choices=["fp32", "bf16"], help="dcpt: classifier-head activations (default: --dtype)")
     ap.add_argument("--restormer-save", default="balanced", choices=["auto", "lean", "balanced", "full"], help="what the Restormer halves keep for backward")
@@ -427,6 +467,7 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--tile-streams", type=int, default=2, help="infer2k: HIP streams the tile batches run on (tile.streams)")
+    ap.add_argument("--tile", type=int, default=0, help="tlsc: 0 = the whole 1080 x 2048 image in one forward, else test_tile's infer_size (tile_pad 16)")
     ap.add_argument("--batch", type=int, default=0)
     ap.add_argument("--size", type=int, default=0)
     ap.add_argument("--side-stream", type=int, default=1, choices=[0, 1], help="0: weight-gradient work on the caller's stream (serialized kernel times)")
@@ -594,6 +635,8 @@ def main():
         res = run_val_metrics(dev, args.steps, args.warmup)
     elif args.workload == "step_tail":
         res = run_step_tail(dev, max(args.steps, 20), args.warmup)
+    elif args.workload == "tlsc":
+        res = run_tlsc(dev, args.steps, args.warmup, tile=args.tile, streams=args.tile_streams)
     else:
         res = run_infer2k(dev, args.dtype, args.steps, args.warmup, args.size or 2048, args.tile_streams)
     res["peak_mem_gb"] = round(torch.cuda.max_memory_allocated() / 2 ** 30, 2)

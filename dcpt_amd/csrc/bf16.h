@@ -87,7 +87,7 @@ __device__ __forceinline__ float f8_sum(f8 a) { return f4_sum(a.lo) + f4_sum(a.h
 
 // ---- launchers of the bf16 kernels (gemm_bf16.hip, bf16_ops.hip) ----------------------------------------------------------
 enum GemmEpiB { EB_PLAIN = 0, EB_BIAS = 1, EB_RESID = 2, EB_SGBWD = 3, EB_BIASGATE = 4, EB_DOTCOL = 5, EB_LNBWD2 = 6, EB_SCATTER = 7, EB_SCATTER_ADD = 8,
-                EB_LNFWD = 9, EB_LNBWDM = 10 };
+                EB_LNFWD = 9, EB_LNBWDM = 10, EB_MUL = 11 };
 
 // C[m][n] = sum_k A[m][k] * Bw[n][k]  on v_mfma_f32_32x32x16_bf16; A, Bw, C, res, aux, gate bf16; bias / cscale / colpart fp32.
 struct GemmNTB {
@@ -98,6 +98,7 @@ struct GemmNTB {
     int N, K, lda, ldc;
     const float* bias;      // [N] or null
     const bf16_t* res;      // EB_RESID: C = res + (acc + bias) * cscale[n];  EB_DOTCOL: colpart[m/128][n] = sum_rows acc * res
+                            // EB_MUL (the bf16 twin of gemm.h's E_MUL): C = (acc + bias) * res, one rounding
     int ldres;              // 0 = ldc
     const float* cscale;    // [N] or null (= 1)
     const bf16_t* aux;      // EB_SGBWD: v [M][2N]:  C[:, n] = acc * v[:, N + n],  C[:, N + n] = acc * v[:, n]

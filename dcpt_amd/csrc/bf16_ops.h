@@ -41,6 +41,11 @@ int launch_wpack_bf16(const WpackBJobsL& jobs, hipStream_t s, int grid_cap = 256
 int launch_scale_rows_bf16(const bf16_t* x, const float* simg, bf16_t* out, int64_t M, int C, int P, hipStream_t s);
 int launch_sca_ds_part_bf16(const bf16_t* dts, const bf16_t* t2, float* ds_part, int B, int C, int P, int nslices, hipStream_t s);
 
+// tlsc_bf16.hip: k1 x k2 box mean of a bf16 NHWC map, replicate-padded back to H x W (k1 <= H, k2 <= W, C % 8 == 0); rowsum: fp32 scratch of
+// box_mean_bf16_rowsum_floats elements
+size_t box_mean_bf16_rowsum_floats(int B, int H, int W, int C, int k2);
+int launch_box_mean_bf16(const bf16_t* in, float* rowsum, bf16_t* out, int B, int H, int W, int C, int k1, int k2, hipStream_t s);
+
 // dwconv.hip
 int dw_num_blocks_per_image_bf16(const DwGeom& g);
 int dw_num_blocks_per_image_fused_bf16(const DwGeom& g);

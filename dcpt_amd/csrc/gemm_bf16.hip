@@ -456,6 +456,7 @@ int launch_gemm_nt_bf16(const GemmNTB& pin, int epi, hipStream_t s) {
     if (epi == EB_BIASGATE) DCPT_CHECK_ARG(p.gate && p.N % 16 == 0, "gemm_nt_bf16: gate epilogue needs gate != null, N %% 16 == 0");
     if (epi == EB_DOTCOL) DCPT_CHECK_ARG(p.colpart && p.res && p.nb == 1, "gemm_nt_bf16: column-dot epilogue needs colpart and res");
     if (epi == EB_RESID) DCPT_CHECK_ARG(p.res, "gemm_nt_bf16: residual epilogue needs res");
+    if (epi == EB_MUL) DCPT_CHECK_ARG(p.res && !p.conv3 && !p.gather2, "gemm_nt_bf16: multiply epilogue needs res and a plain A operand");
     if (epi == EB_SGBWD) DCPT_CHECK_ARG(p.aux && p.ldc == 2 * p.N && (!p.rowpart || (p.uvec && p.cvec)), "gemm_nt_bf16: SimpleGate-backward epilogue needs aux and ldc == 2N");
     if (epi == EB_LNBWD2)
         DCPT_CHECK_ARG(p.res && p.mu && p.rstd && p.lnw && p.colpart && p.rowpart && p.rowparts >= 1 && p.rowparts <= 8 && p.nb == 1,
@@ -470,22 +471,26 @@ int launch_gemm_nt_bf16(const GemmNTB& pin, int epi, hipStream_t s) {
                        "gemm_nt_bf16: masked LayerNorm-backward epilogue needs aux / mu / rstd / lnw / colpart, dense rows and N=%d inside one column tile", p.N);
     const double mn = (double)p.M * p.N, mk = (double)p.M * p.K;
     double bytes = mk + mn * (epi == EB_SGBWD ? 4 : epi == EB_BIASGATE ? 1.5 : 1) + (double)p.N * p.K;
-    if (epi == EB_RESID || epi == EB_DOTCOL || epi == EB_SCATTER_ADD) bytes += mn;
+    if (epi == EB_RESID || epi == EB_DOTCOL || epi == EB_SCATTER_ADD || epi == EB_MUL) bytes += mn;
     if (epi == EB_LNBWD2) bytes += 2 * mn;
     if (epi == EB_LNFWD) bytes += mn * (p.res ? 2 : 1);
     if (epi == EB_LNBWDM) bytes += mn * (1 + (p.ymask ? 1 : 0) + (p.y2 ? 1 : 0));
     ProfScope prof(s, PROF_NT + 256 + epi, p.M, p.N, p.K, 2.0 * mn * p.K * p.nb, bytes * 2.0 * p.nb);
+    if (epi == EB_MUL) trace_tag("nt_bf16.epi_mul");   // (next to the tile-class tag below: the TLSC block's attention product)
     static const int use256 = dcpt_tuning("DCPT_NT256", 1);   // (A/B switch while the kernel is being tuned)
     static const int usetall = dcpt_tuning("DCPT_NT_TALL", 1);   // (A/B switch)
     if (use256 && usetall && gemm_nt_bf16_tall_ok(p, epi, usetall == 2 ? 1 : 192)) {
         trace_tag(p.conv3 ? "nt_bf16.tall512_conv3" : "nt_bf16.tall512");
+        if (epi == EB_MUL) trace_tag("nt_bf16.epi_mul.tall512");   // (which tile class served the multiply epilogue: a test's handle)
         return launch_gemm_nt_bf16_tall(p, epi, s);
     }
     if (use256 && gemm_nt_bf16_256_ok(p, epi, use256 == 2 ? 1 : 192)) {
         trace_tag(p.conv3 ? "nt_bf16.256_conv3" : "nt_bf16.256");
+        if (epi == EB_MUL) trace_tag("nt_bf16.epi_mul.256");
         return launch_gemm_nt_bf16_256(p, epi, s);
     }
     trace_tag(p.conv3 ? "nt_bf16.128_conv3" : p.gather2 ? "nt_bf16.128_gather2" : "nt_bf16.128");
+    if (epi == EB_MUL) trace_tag("nt_bf16.epi_mul.128");
     switch (epi) {
         case EB_PLAIN: return launch_nt<EB_PLAIN>(p, s);
         case EB_BIAS: return launch_nt<EB_BIAS>(p, s);
@@ -498,6 +503,7 @@ int launch_gemm_nt_bf16(const GemmNTB& pin, int epi, hipStream_t s) {
         case EB_SCATTER_ADD: return launch_nt<EB_SCATTER_ADD>(p, s);
         case EB_LNFWD: return launch_nt<EB_LNFWD>(p, s);
         case EB_LNBWDM: return launch_nt<EB_LNBWDM>(p, s);
+        case EB_MUL: return launch_nt<EB_MUL>(p, s);
     }
     dcpt_set_error("gemm_nt_bf16: unknown epilogue %d", epi);
     return DCPT_ERR_ARG;

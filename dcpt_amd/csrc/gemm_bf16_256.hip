@@ -408,8 +408,8 @@ bool gemm_nt_bf16_tall_ok(const GemmNTB& p, int epi, int min_tiles) {
     if (p.N != 128 || p.gather2 || p.K % 128 != 0 || p.K < 128 || (p.nb > 1)) return false;
     // (the masked LayerNorm-backward epilogue stays on the 128-row kernel: on this tile it measured +0.2 ms per launch at the head's stage 0 --
     // four quadrant epilogues with their column sums in a row and no second block on the CU to run under them; profiles/r6/head_tall_tile/)
-    if (!(epi == EB_PLAIN || epi == EB_RESID || epi == EB_LNFWD)) return false;
-    if (p.conv3 && (epi == EB_RESID || p.gC % 64 != 0 || p.K != 9 * p.gC || p.K / 64 >= 2048)) return false;
+    if (!(epi == EB_PLAIN || epi == EB_RESID || epi == EB_LNFWD || epi == EB_MUL)) return false;
+    if (p.conv3 && (epi == EB_RESID || epi == EB_MUL || p.gC % 64 != 0 || p.K != 9 * p.gC || p.K / 64 >= 2048)) return false;
     return cdiv64(p.M, 512) >= min_tiles;
 }
 
@@ -421,6 +421,7 @@ int launch_gemm_nt_bf16_tall(const GemmNTB& p, int epi, hipStream_t s) {
     } else {
         if (epi == EB_LNFWD) gemm_nt_bf16_256_kernel<EB_LNFWD, 0, true><<<grid, dim3(512), 0, s>>>(p);
         else if (epi == EB_RESID) gemm_nt_bf16_256_kernel<EB_RESID, 0, true><<<grid, dim3(512), 0, s>>>(p);
+        else if (epi == EB_MUL) gemm_nt_bf16_256_kernel<EB_MUL, 0, true><<<grid, dim3(512), 0, s>>>(p);
         else gemm_nt_bf16_256_kernel<EB_PLAIN, 0, true><<<grid, dim3(512), 0, s>>>(p);
     }
     DCPT_CHECK_LAUNCH("gemm_nt_bf16 tall");
@@ -446,6 +447,7 @@ int launch_gemm_nt_bf16_256(const GemmNTB& p, int epi, hipStream_t s) {
         case EB_DOTCOL: gemm_nt_bf16_256_kernel<EB_DOTCOL><<<grid, dim3(512), 0, s>>>(p); break;
         case EB_LNFWD: gemm_nt_bf16_256_kernel<EB_LNFWD><<<grid, dim3(512), 0, s>>>(p); break;
         case EB_LNBWDM: gemm_nt_bf16_256_kernel<EB_LNBWDM><<<grid, dim3(512), 0, s>>>(p); break;
+        case EB_MUL: gemm_nt_bf16_256_kernel<EB_MUL><<<grid, dim3(512), 0, s>>>(p); break;
         default: dcpt_set_error("gemm_nt_bf16_256: epilogue %d not supported", epi); return DCPT_ERR_ARG;
     }
     DCPT_CHECK_LAUNCH("gemm_nt_bf16_256");

@@ -30,7 +30,7 @@ __device__ __forceinline__ void epilogue8(const GemmNTB& p, float* __restrict__ 
     const bool nok = GATE ? (n < Ch) : (n < p.N);
     const int ldres = p.ldres ? p.ldres : p.ldc;
     f8 bias = f8_zero(), bias2 = f8_zero(), cs = f8{make_float4(1.f, 1.f, 1.f, 1.f), make_float4(1.f, 1.f, 1.f, 1.f)};
-    if constexpr (EK == EB_BIAS || EK == EB_RESID) {
+    if constexpr (EK == EB_BIAS || EK == EB_RESID || EK == EB_MUL) {
         if (p.bias && nok) bias = f8_ld(p.bias + n);
     }
     if constexpr (GATE) {
@@ -54,7 +54,7 @@ __device__ __forceinline__ void epilogue8(const GemmNTB& p, float* __restrict__ 
     const rsrc_t rsC = make_rsrc(p.C + cbase);
     rsrc_t rsR = rsC, rsX = rsC;
     if constexpr (EK == EB_SCATTER_ADD) rsR = make_rsrc(p.res + cbase);
-    if constexpr (EK == EB_RESID || EK == EB_DOTCOL || EK == EB_LNBWD2) rsR = make_rsrc(p.res + m0 * (int64_t)ldres);
+    if constexpr (EK == EB_RESID || EK == EB_DOTCOL || EK == EB_LNBWD2 || EK == EB_MUL) rsR = make_rsrc(p.res + m0 * (int64_t)ldres);
     if constexpr (EK == EB_LNBWD2) rsX = make_rsrc((p.aux ? p.aux : p.res) + m0 * (int64_t)ldres);
     rsrc_t rsY = rsC;   // EB_LNFWD: y2 (the LayerNorm output);  EB_LNBWDM: y2 (the masked gradient, optional) -- rows as C's
     if constexpr (EK == EB_LNFWD) {
@@ -99,7 +99,7 @@ __device__ __forceinline__ void epilogue8(const GemmNTB& p, float* __restrict__ 
             const bool ok = (m0 + rl < p.M) && nok;
             pre1[it] = f8_zero();
             pre2[it] = f8_zero();
-            if constexpr (EK == EB_RESID || EK == EB_DOTCOL || EK == EB_LNBWD2)
+            if constexpr (EK == EB_RESID || EK == EB_DOTCOL || EK == EB_LNBWD2 || EK == EB_MUL)
                 pre1[it] = bbuf_ld8(rsR, ok ? ((uint32_t)rl * (uint32_t)ldres + (uint32_t)n) * 2u : ROW_SENT);
             if constexpr (EK == EB_SCATTER_ADD) pre1[it] = bbuf_ld8(rsR, ok ? (uint32_t)((fine_elem(p, m0 + rl) - cbase) * 2) + coladd : ROW_SENT);
             if constexpr (EK == EB_LNBWD2) {
@@ -147,6 +147,8 @@ __device__ __forceinline__ void epilogue8(const GemmNTB& p, float* __restrict__ 
                 bbuf_st8(rsC, o, f8_add(v, bias));
             } else if constexpr (EK == EB_RESID) {
                 bbuf_st8(rsC, o, f8_fma(f8_add(v, bias), cs, pre1[it]));
+            } else if constexpr (EK == EB_MUL) {
+                bbuf_st8(rsC, o, f8_mul(f8_add(v, bias), pre1[it]));   // (rows past M: the store is dropped by the range check)
             } else if constexpr (EK == EB_SGBWD) {
                 const f8 d1 = f8_mul(v, pre2[it]), d2 = f8_mul(v, pre1[it]);
                 bbuf_st8(rsC, o, d1);

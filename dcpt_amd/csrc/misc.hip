@@ -2,6 +2,7 @@
 // weight packing/transposition, and the deterministic split-slab reduction of weight gradients.
 // Reference: basicsr/archs/nafnet_arch.py:116-127,173 (SCA), :162-163,178,186 (beta/gamma).
 #include "kernels.h"
+#include "prof.h"
 
 namespace {
 
@@ -354,6 +355,7 @@ __global__ __launch_bounds__(256) void box_cols_kernel(const float* __restrict__
 
 int launch_box_mean(const float* in, float* rowsum, float* out, int B, int H, int W, int C, int k1, int k2, hipStream_t s) {
     DCPT_CHECK_ARG(C % 4 == 0 && k1 >= 1 && k2 >= 1 && k1 <= H && k2 <= W, "box_mean: bad window %dx%d for %dx%d", k1, k2, H, W);
+    trace_tag("tlsc.box_mean_f32");
     box_rows_kernel<<<dim3((unsigned)cdiv64((int64_t)B * H * (C / 4), 256)), dim3(256), 0, s>>>(in, rowsum, B, H, W, C, k2);
     DCPT_CHECK_LAUNCH("box_rows");
     box_cols_kernel<<<dim3((unsigned)cdiv64((int64_t)B * W * (C / 4), 256)), dim3(256), 0, s>>>(rowsum, out, B, H, W, C, k1, k2);
@@ -364,6 +366,7 @@ int launch_box_mean(const float* in, float* rowsum, float* out, int B, int H, in
 int launch_sca_fwd(const float* pool_part, int nblk, const float* Wsca, const float* bsca, float* pooled, float* simg,
                    int B, int C, int P, hipStream_t s) {
     DCPT_CHECK_ARG(C % 4 == 0 && C * 4 <= 65536, "sca_fwd: C=%d unsupported", C);
+    trace_tag("sca_fwd");
     sca_fwd_kernel<<<dim3(B, cdiv(C, SCA_OPB)), dim3(256), C * sizeof(float), s>>>(pool_part, nblk, Wsca, bsca, pooled, simg, C,
                                                                                 1.0f / (float)P);
     DCPT_CHECK_LAUNCH("sca_fwd");

@@ -337,6 +337,82 @@ extern "C" int dcpt_nafblock_wpack_bf16(const dcpt_nafblock_params* p, void* pac
     return pack_all(p, k, C, (hipStream_t)stream);
 }
 
+// The two halves that the global-mean forward and the TLSC forward (dcpt_nafblock_local_fwd_bf16 below) share; what lies between them --
+// the channel attention and conv3 -- is where the two differ.
+namespace {
+struct HeadB {
+    const bf16_t *W1, *Wf1;   // conv1 as a GEMM operand / as the chain kernel's stream
+    float* w2p;               // depthwise taps [9][2C]; pack_dw: made here from p->conv2_w
+    bool pack_dw;
+    bf16_t *t1, *xn1, *t2;
+    float *mu1, *rstd1, *pool_part;
+};
+// t1 = conv1(LayerNorm1(inp)) + b1 in the form the width and the pixel count select, then t2 = SimpleGate(dw3x3(t1) + b2) with the pooling partials
+int fwd_head_bf16(const dcpt_nafblock_params* p, const bf16_t* inp, const HeadB& h, int B, int H, int W, int C, hipStream_t s) {
+    const int64_t M = (int64_t)B * H * W;
+    const float eps = 1e-6f;
+    if (ffn_fused(C)) {   // narrow levels: LayerNorm1 -> conv1 in one pass over the input (ffn_bf16.hip)
+        FfnFwdB f{};
+        f.y = inp; f.lnw = p->norm1_w; f.lnb = p->norm1_b; f.W4 = h.W1; f.b4 = p->conv1_b; f.v = h.t1; f.xn2 = h.xn1; f.mu = h.mu1;
+        f.rstd = h.rstd1; f.M = M; f.eps = eps;
+        DCPT_TRY(launch_ln_conv_bf16(f, C, s));
+    } else if (ffn_chain_use(C, M) && chain_head_on()) {   // wide levels: the same pair on the chain kernel (chain_bf16.hip, HEAD form)
+        ChainFwdB f{};
+        f.y = inp; f.lnw = p->norm1_w; f.lnb = p->norm1_b; f.Wf = h.Wf1; f.b4 = p->conv1_b; f.v = h.t1; f.xn2 = h.xn1; f.mu = h.mu1;
+        f.rstd = h.rstd1; f.M = M; f.eps = eps;
+        DCPT_TRY(launch_chain_head_bf16(f, C, s));
+    } else {
+        DCPT_TRY(launch_ln_fwd_bf16(inp, p->norm1_w, p->norm1_b, h.xn1, h.mu1, h.rstd1, M, C, eps, s));
+        GemmNTB g{};
+        g.M = M; g.A = h.xn1; g.lda = C; g.K = C; g.Bw = h.W1; g.N = 2 * C; g.C = h.t1; g.ldc = 2 * C; g.bias = p->conv1_b;
+        DCPT_TRY(launch_gemm_nt_bf16(g, EB_BIAS, s));
+    }
+    DwGeom dg{B, H, W, C};
+    if (h.pack_dw) DCPT_TRY(launch_dw_pack_weights(p->conv2_w, h.w2p, 2 * C, s));
+    if (dw_ring_usable(dg, 2)) return launch_dw_ring_fwd_bf16(h.t1, h.w2p, p->conv2_b, h.t2, h.pool_part, dg, s);
+    return launch_dw_fwd_bf16(h.t1, h.w2p, p->conv2_b, h.t2, h.pool_part, dg, s);
+}
+
+struct TailB {
+    const bf16_t *W4, *W5, *Wf;   // conv4 / conv5 as GEMM operands / as the chain kernel's stream
+    bf16_t *v, *xn2, *g;          // the caller's kept tensors (null where it keeps none)
+    float *mu2, *rstd2;
+    bf16_t *xn2_ws, *g_ws;        // stand-ins for the three-kernel form where the caller's are null
+    float *mu2_ws, *rstd2_ws;
+};
+// out = y + gamma (conv5(SimpleGate(conv4(LayerNorm2(y)))) + b5); c3 != null: conv3 in front of the chain kernel (y is then written by it)
+int fwd_ffn_bf16(const dcpt_nafblock_params* p, bf16_t* y, bf16_t* out, const TailB& t, int64_t M, int C, hipStream_t s, const ChainFwdB* c3 = nullptr) {
+    const float eps = 1e-6f;
+    if (ffn_fused(C)) {   // narrow levels: LayerNorm2 -> conv4 -> SimpleGate -> conv5 -> residual in one pass over y (ffn_bf16.hip)
+        FfnFwdB f{};
+        f.y = y; f.lnw = p->norm2_w; f.lnb = p->norm2_b; f.W4 = t.W4; f.W5 = t.W5; f.b4 = p->conv4_b; f.b5 = p->conv5_b; f.gamma = p->gamma;
+        // (LN2(y), the gate and the statistics are recomputed by the backward kernels: xn2 / g / mu2 / rstd2 stay unwritten)
+        f.out = out; f.v = t.v; f.M = M; f.eps = eps;
+        return launch_ffn_fwd_bf16(f, C, s);
+    }
+    if (ffn_chain_use(C, M)) {   // wide levels: the same chain per 128-pixel tile with the weights streamed past it (chain_bf16.hip)
+        ChainFwdB f{};
+        f.y = y; f.lnw = p->norm2_w; f.lnb = p->norm2_b; f.Wf = t.Wf; f.b4 = p->conv4_b; f.b5 = p->conv5_b; f.gamma = p->gamma;
+        f.out = out; f.v = t.v; f.xn2 = t.xn2; f.g = t.g; f.mu = t.mu2; f.rstd = t.rstd2; f.M = M; f.eps = eps;
+        if (c3) {   // y = inp + beta (conv3(t2 s) + b3) is produced by the same kernel
+            f.t2 = c3->t2; f.inp = c3->inp; f.W3f = c3->W3f; f.b3 = c3->b3; f.beta = c3->beta; f.P = c3->P;
+        }
+        return launch_chain_fwd_bf16(f, C, s);
+    }
+    // (inference at a chain width with a pixel count the chain kernel is not used for: LN2(y) / the gate / the statistics live in the workspace)
+    bf16_t* const xn2 = t.xn2 ? t.xn2 : t.xn2_ws;
+    bf16_t* const gt = t.g ? t.g : t.g_ws;
+    DCPT_TRY(launch_ln_fwd_bf16(y, p->norm2_w, p->norm2_b, xn2, t.mu2 ? t.mu2 : t.mu2_ws, t.rstd2 ? t.rstd2 : t.rstd2_ws, M, C, eps, s));
+    GemmNTB g{};
+    g.M = M; g.A = xn2; g.lda = C; g.K = C; g.Bw = t.W4; g.N = 2 * C; g.C = t.v; g.ldc = 2 * C; g.bias = p->conv4_b; g.gate = gt;
+    DCPT_TRY(launch_gemm_nt_bf16(g, EB_BIASGATE, s));
+    g = GemmNTB{};
+    g.M = M; g.A = gt; g.lda = C; g.K = C; g.Bw = t.W5; g.N = C; g.C = out; g.ldc = C; g.bias = p->conv5_b; g.res = y; g.ldres = C;
+    g.cscale = p->gamma;
+    return launch_gemm_nt_bf16(g, EB_RESID, s);
+}
+}  // namespace
+
 static int nafblock_fwd_bf16_impl(const dcpt_nafblock_params* p, const uint16_t* inp, uint16_t* out, const dcpt_nafblock_saved_bf16* sv,
                                   void* ws, size_t ws_bytes, int B, int H, int W, int C, const void* packed, size_t packed_bytes,
                                   dcpt_stream_t stream) {
@@ -357,7 +433,6 @@ static int nafblock_fwd_bf16_impl(const dcpt_nafblock_params* p, const uint16_t*
     }
     const int64_t M = (int64_t)B * H * W;
     const int P = H * W;
-    const float eps = 1e-6f;
     // operand copies of the weights that do not depend on SCA: the caller's per-block pack, or made here
     WpackBJobs j{};
     if (packed) {
@@ -383,25 +458,12 @@ static int nafblock_fwd_bf16_impl(const dcpt_nafblock_params* p, const uint16_t*
         DCPT_TRY(launch_wpack_bf16(j, s));
     }
     GemmNTB g{};
-    if (ffn_fused(C)) {   // narrow levels: LayerNorm1 -> conv1 in one pass over the input (ffn_bf16.hip)
-        FfnFwdB f{};
-        f.y = inp; f.lnw = p->norm1_w; f.lnb = p->norm1_b; f.W4 = w.W1; f.b4 = p->conv1_b; f.v = sv->t1; f.xn2 = sv->xn1; f.mu = sv->mu1;
-        f.rstd = sv->rstd1; f.M = M; f.eps = eps;
-        DCPT_TRY(launch_ln_conv_bf16(f, C, s));
-    } else if (ffn_chain_use(C, M) && chain_head_on()) {   // wide levels: the same pair on the chain kernel (chain_bf16.hip, HEAD form)
-        ChainFwdB f{};
-        f.y = inp; f.lnw = p->norm1_w; f.lnb = p->norm1_b; f.Wf = w.Wf1; f.b4 = p->conv1_b; f.v = sv->t1; f.xn2 = sv->xn1; f.mu = sv->mu1;
-        f.rstd = sv->rstd1; f.M = M; f.eps = eps;
-        DCPT_TRY(launch_chain_head_bf16(f, C, s));
-    } else {
-        DCPT_TRY(launch_ln_fwd_bf16(inp, p->norm1_w, p->norm1_b, sv->xn1, sv->mu1, sv->rstd1, M, C, eps, s));
-        g.M = M; g.A = sv->xn1; g.lda = C; g.K = C; g.Bw = w.W1; g.N = 2 * C; g.C = sv->t1; g.ldc = 2 * C; g.bias = p->conv1_b;
-        DCPT_TRY(launch_gemm_nt_bf16(g, EB_BIAS, s));
+    {
+        HeadB h{};
+        h.W1 = w.W1; h.Wf1 = w.Wf1; h.w2p = w.w2p; h.pack_dw = !packed; h.t1 = sv->t1; h.xn1 = sv->xn1; h.t2 = sv->t2; h.mu1 = sv->mu1;
+        h.rstd1 = sv->rstd1; h.pool_part = w.pool_part;
+        DCPT_TRY(fwd_head_bf16(p, inp, h, B, H, W, C, s));
     }
-    DwGeom dg{B, H, W, C};
-    if (!packed) DCPT_TRY(launch_dw_pack_weights(p->conv2_w, w.w2p, 2 * C, s));
-    if (dw_ring_usable(dg, 2)) DCPT_TRY(launch_dw_ring_fwd_bf16(sv->t1, w.w2p, p->conv2_b, sv->t2, w.pool_part, dg, s));
-    else DCPT_TRY(launch_dw_fwd_bf16(sv->t1, w.w2p, p->conv2_b, sv->t2, w.pool_part, dg, s));
     DCPT_TRY(launch_sca_fwd(w.pool_part, w.nblk_pool, p->sca_w, p->sca_b, sv->pooled, sv->s, B, C, P, s));
     // wide levels, images of whole 128-pixel tiles: conv3 runs IN FRONT of the chain kernel below (its per-image weights as fragment streams)
     const bool conv3_in_chain = ffn_chain_use(C, M) && chain_conv3_on() && !w.scale_act && P % 128 == 0;
@@ -427,33 +489,12 @@ static int nafblock_fwd_bf16_impl(const dcpt_nafblock_params* p, const uint16_t*
         g.nb = B; g.sA = (int64_t)P * C; g.sB = (int64_t)C * C; g.sC = (int64_t)P * C; g.sR = (int64_t)P * C;
     }
     if (!conv3_in_chain) DCPT_TRY(launch_gemm_nt_bf16(g, EB_RESID, s));
-    if (ffn_fused(C)) {   // narrow levels: LayerNorm2 -> conv4 -> SimpleGate -> conv5 -> residual in one pass over y (ffn_bf16.hip)
-        FfnFwdB f{};
-        f.y = sv->y; f.lnw = p->norm2_w; f.lnb = p->norm2_b; f.W4 = w.W4; f.W5 = w.W5; f.b4 = p->conv4_b; f.b5 = p->conv5_b; f.gamma = p->gamma;
-        // (LN2(y), the gate and the statistics are recomputed by the backward kernels: sv->xn2 / g / mu2 / rstd2 stay unwritten)
-        f.out = out; f.v = sv->v; f.M = M; f.eps = eps;
-        return launch_ffn_fwd_bf16(f, C, s);
-    }
-    if (ffn_chain_use(C, M)) {   // wide levels: the same chain per 128-pixel tile with the weights streamed past it (chain_bf16.hip)
-        ChainFwdB f{};
-        f.y = sv->y; f.lnw = p->norm2_w; f.lnb = p->norm2_b; f.Wf = w.Wf; f.b4 = p->conv4_b; f.b5 = p->conv5_b; f.gamma = p->gamma;
-        f.out = out; f.v = sv->v; f.xn2 = sv->xn2; f.g = sv->g; f.mu = sv->mu2; f.rstd = sv->rstd2; f.M = M; f.eps = eps;
-        if (conv3_in_chain) {   // y = inp + beta (conv3(t2 s) + b3) is produced by the same kernel
-            f.t2 = sv->t2; f.inp = inp; f.W3f = w.W3s; f.b3 = p->conv3_b; f.beta = p->beta; f.P = P;
-        }
-        return launch_chain_fwd_bf16(f, C, s);
-    }
-    // (inference at a chain width with a pixel count the chain kernel is not used for: LN2(y) / the gate / the statistics live in the workspace)
-    bf16_t* const xn2 = sv->xn2 ? sv->xn2 : w.xn2;
-    bf16_t* const gt = sv->g ? sv->g : w.g;
-    DCPT_TRY(launch_ln_fwd_bf16(sv->y, p->norm2_w, p->norm2_b, xn2, sv->mu2 ? sv->mu2 : w.mu2, sv->rstd2 ? sv->rstd2 : w.rstd2, M, C, eps, s));
-    g = GemmNTB{};
-    g.M = M; g.A = xn2; g.lda = C; g.K = C; g.Bw = w.W4; g.N = 2 * C; g.C = sv->v; g.ldc = 2 * C; g.bias = p->conv4_b; g.gate = gt;
-    DCPT_TRY(launch_gemm_nt_bf16(g, EB_BIASGATE, s));
-    g = GemmNTB{};
-    g.M = M; g.A = gt; g.lda = C; g.K = C; g.Bw = w.W5; g.N = C; g.C = out; g.ldc = C; g.bias = p->conv5_b; g.res = sv->y; g.ldres = C;
-    g.cscale = p->gamma;
-    return launch_gemm_nt_bf16(g, EB_RESID, s);
+    TailB t{};
+    t.W4 = w.W4; t.W5 = w.W5; t.Wf = w.Wf; t.v = sv->v; t.xn2 = sv->xn2; t.g = sv->g; t.mu2 = sv->mu2; t.rstd2 = sv->rstd2;
+    t.xn2_ws = w.xn2; t.g_ws = w.g; t.mu2_ws = w.mu2; t.rstd2_ws = w.rstd2;
+    ChainFwdB c3{};
+    c3.t2 = sv->t2; c3.inp = inp; c3.W3f = w.W3s; c3.b3 = p->conv3_b; c3.beta = p->beta; c3.P = P;
+    return fwd_ffn_bf16(p, sv->y, out, t, M, C, s, conv3_in_chain ? &c3 : nullptr);
 }
 
 extern "C" int dcpt_nafblock_fwd_bf16(const dcpt_nafblock_params* p, const uint16_t* inp, uint16_t* out, const dcpt_nafblock_saved_bf16* sv,
@@ -465,6 +506,111 @@ extern "C" int dcpt_nafblock_fwd_bf16_packed(const dcpt_nafblock_params* p, cons
                                              int C, dcpt_stream_t stream) {
     DCPT_CHECK_ARG(packed, "nafblock_fwd_bf16_packed: null packed weights");
     return nafblock_fwd_bf16_impl(p, inp, out, sv, ws, ws_bytes, B, H, W, C, packed, packed_bytes, stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// TLSC variant in bf16 storage (reference nafnet_arch.py:277-288 NAFNet(Local_Base) + arch_util.py:313-455; the fp32 twin is
+// dcpt_nafblock_local_fwd in nafblock.hip): inference only, nothing is kept.  SCA's global mean is a k1 x k2 local box mean, so the
+// attention scale is a per-pixel map:  mean = boxmean(t2) (tlsc_bf16.hip, rounded once),  t2s = bf16((Wsca mean + bsca) * t2) (one GEMM,
+// epilogue EB_MUL, one rounding),  y = inp + beta (conv3(t2s) + b3).  Both halves around that are the global forward's own (fwd_head_bf16,
+// fwd_ffn_bf16): the same kernels at every width and pixel count.
+namespace {
+struct LocalWsB {
+    float* w2p;
+    float* pool_part;
+    bf16_t *W1, *W4, *W5, *W3, *Wsca, *Wf, *Wf1;
+    bf16_t *t1, *t2, *xn, *t2s, *y;
+    float *mu, *rstd;
+};
+size_t local_layout_bf16(int B, int H, int W, int C, void* base, size_t bytes, LocalWsB* out) {
+    WsAlloc a(base, base ? bytes : (size_t)-1);
+    const size_t M = (size_t)B * H * W;
+    DwGeom g{B, H, W, C};
+    LocalWsB w{};
+    const int nblk_pool = dw_ring_usable(g, 2) ? dw_ring_num_blocks_per_image(g, 2) : dw_num_blocks_per_image_bf16(g);
+    w.w2p = a.get<float>((size_t)18 * C);
+    w.pool_part = a.get<float>((size_t)B * nblk_pool * C);   // (the depthwise kernels write their pooling partials; nobody reads them here)
+    w.W1 = a.get<bf16_t>((size_t)2 * C * C);
+    w.W4 = a.get<bf16_t>((size_t)2 * C * C);
+    w.W5 = a.get<bf16_t>((size_t)C * C);
+    w.W3 = a.get<bf16_t>((size_t)C * C);
+    w.Wsca = a.get<bf16_t>((size_t)C * C);
+    w.Wf = ffn_chain(C) ? a.get<bf16_t>(chain_wstream_elems(C)) : nullptr;
+    w.Wf1 = ffn_chain(C) ? a.get<bf16_t>(chain_head_wstream_elems(C)) : nullptr;
+    w.t1 = a.get<bf16_t>(M * 2 * C);   // conv1's output; once t2 exists the box mean's fp32 row sums lie here (B H Wo C floats <= M 2C bf16)
+    w.t2 = a.get<bf16_t>(M * C);
+    w.xn = a.get<bf16_t>(M * C);       // LN1(inp), then the mean map, then LN2(y) where the second half is three kernels
+    w.t2s = a.get<bf16_t>(M * C);      // t2 * smap, then SimpleGate(v) where the second half is three kernels
+    w.y = a.get<bf16_t>(M * C);
+    w.mu = a.get<float>(M);
+    w.rstd = a.get<float>(M);
+    if (out) *out = w;
+    return a.off;
+}
+}  // namespace
+
+extern "C" size_t dcpt_nafblock_local_fwd_bf16_ws_bytes(int B, int H, int W, int C, int k1, int k2) {
+    (void)k1;
+    (void)k2;
+    if (!shape_ok(B, H, W, C)) return 0;
+    return local_layout_bf16(B, H, W, C, nullptr, 0, nullptr);
+}
+
+extern "C" int dcpt_nafblock_local_fwd_bf16(const dcpt_nafblock_params* p, const void* packed, size_t packed_bytes, const uint16_t* inp,
+                                            uint16_t* out, void* ws, size_t ws_bytes, int B, int H, int W, int C, int k1, int k2,
+                                            dcpt_stream_t stream) {
+    hipStream_t s = (hipStream_t)stream;
+    DCPT_CHECK_ARG(p && inp && out, "nafblock_local_fwd_bf16: null argument");
+    DCPT_CHECK_ARG(shape_ok(B, H, W, C) && k1 >= 1 && k2 >= 1, "nafblock_local_fwd_bf16: bad shape B=%d H=%d W=%d C=%d k=%dx%d (C %% 8 == 0, C <= 1024)",
+                   B, H, W, C, k1, k2);
+    if (k1 > H) k1 = H;   // arch_util.py:381 k = min(size, kernel)
+    if (k2 > W) k2 = W;
+    LocalWsB w;
+    const size_t need = local_layout_bf16(B, H, W, C, ws, ws_bytes, &w);
+    if (need > ws_bytes || ws == nullptr) {
+        dcpt_set_error("nafblock_local_fwd_bf16: workspace too small (%zu < %zu)", ws_bytes, need);
+        return DCPT_ERR_WS;
+    }
+    const int64_t M = (int64_t)B * H * W;
+    // operand copies of the weights: the caller's per-block pack (whose layout has no place for sca_w: that one copy is made here), or all here
+    WpackBJobs j{};
+    if (packed) {
+        PackB k;
+        DCPT_CHECK_ARG(pack_layout(C, const_cast<void*>(packed), packed_bytes, &k) <= packed_bytes, "nafblock_local_fwd_bf16: packed weights buffer too small");
+        w.W1 = k.W1; w.W4 = k.W4; w.W5 = k.W5; w.W3 = k.W3; w.w2p = k.w2p; w.Wf = k.Wf; w.Wf1 = k.Wf1;
+        j.n = 1;
+        j.in[0] = p->sca_w; j.out[0] = w.Wsca; j.N[0] = C; j.K[0] = C;
+    } else {
+        j.n = 5;
+        j.in[0] = p->conv1_w; j.out[0] = w.W1; j.N[0] = 2 * C; j.K[0] = C;
+        j.in[1] = p->conv4_w; j.out[1] = w.W4; j.N[1] = 2 * C; j.K[1] = C;
+        j.in[2] = p->conv5_w; j.out[2] = w.W5; j.N[2] = C; j.K[2] = C;
+        j.in[3] = p->conv3_w; j.out[3] = w.W3; j.N[3] = C; j.K[3] = C;
+        j.in[4] = p->sca_w; j.out[4] = w.Wsca; j.N[4] = C; j.K[4] = C;
+        if (w.Wf) {
+            j.in[5] = p->conv4_w; j.rs[5] = p->conv5_w; j.out[5] = w.Wf; j.N[5] = 3 * C; j.K[5] = C; j.transpose[5] = 9;
+            j.in[6] = p->conv1_w; j.rs[6] = nullptr; j.out[6] = w.Wf1; j.N[6] = 2 * C; j.K[6] = C; j.transpose[6] = 9;
+            j.n = 7;
+        }
+    }
+    DCPT_TRY(launch_wpack_bf16(j, s));
+    HeadB h{};
+    h.W1 = w.W1; h.Wf1 = w.Wf1; h.w2p = w.w2p; h.pack_dw = !packed; h.t1 = w.t1; h.xn1 = w.xn; h.t2 = w.t2; h.mu1 = w.mu; h.rstd1 = w.rstd;
+    h.pool_part = w.pool_part;
+    DCPT_TRY(fwd_head_bf16(p, inp, h, B, H, W, C, s));
+    bf16_t* const mmap = w.xn;   // LN1(inp) is dead
+    DCPT_TRY(launch_box_mean_bf16(w.t2, reinterpret_cast<float*>(w.t1), mmap, B, H, W, C, k1, k2, s));
+    GemmNTB g{};
+    g.M = M; g.A = mmap; g.lda = C; g.K = C; g.Bw = w.Wsca; g.N = C; g.C = w.t2s; g.ldc = C; g.bias = p->sca_b; g.res = w.t2; g.ldres = C;
+    DCPT_TRY(launch_gemm_nt_bf16(g, EB_MUL, s));
+    g = GemmNTB{};
+    g.M = M; g.A = w.t2s; g.lda = C; g.K = C; g.Bw = w.W3; g.N = C; g.C = w.y; g.ldc = C; g.bias = p->conv3_b; g.res = inp; g.ldres = C;
+    g.cscale = p->beta;
+    DCPT_TRY(launch_gemm_nt_bf16(g, EB_RESID, s));
+    TailB t{};
+    t.W4 = w.W4; t.W5 = w.W5; t.Wf = w.Wf;
+    t.xn2_ws = w.xn; t.g_ws = w.t2s; t.mu2_ws = w.mu; t.rstd2_ws = w.rstd;   // (the mean map and t2 * smap are dead once y exists)
+    return fwd_ffn_bf16(p, w.y, out, t, M, C, s);
 }
 
 static int nafblock_bwd_bf16_impl(const dcpt_nafblock_params* p, const dcpt_nafblock_grads* gr, const uint16_t* inp,

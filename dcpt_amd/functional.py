@@ -693,6 +693,46 @@ def nafblock_local(inp: torch.Tensor, params: Dict[str, torch.Tensor], k1: int, 
     return out
 
 
+def nafblock_local_bf16(inp: torch.Tensor, params: Dict[str, torch.Tensor], k1: int, k2: int, packed: PackedWeightsBf16 = None) -> torch.Tensor:
+    """TLSC inference forward in bf16 storage (dcpt_nafblock_local_fwd_bf16; reference nafnet_arch.py:277-288 + arch_util.py:313-455): bf16
+    activations in / out, fp32 parameters; ``packed``: the block's weight-pack cache as for ``nafblock_bf16`` (without it the call packs its
+    own operand copies).  Inference only, like ``nafblock_local``."""
+    if torch.is_grad_enabled() and (inp.requires_grad or any(p.requires_grad for p in params.values())):
+        raise NotImplementedError("the TLSC NAFNet variant is inference-only: call it under torch.no_grad()")
+    lib = _lib.load()
+    ps = [_contig(params[k].detach()) for k in PARAM_FIELDS]
+    _require_gpu_bf16(inp)
+    _require_gpu(*ps)
+    inp = _nhwc(inp)
+    B, Cc, H, W = inp.shape
+    if Cc % 8:
+        raise _lib.DcptHipError(f"the bf16-storage path needs channel counts that are multiples of 8 (got {Cc})")
+    buf = packed.get(params) if packed is not None else None
+    out = _empty_nhwc_bf16(B, Cc, H, W, inp.device)
+    pp = NafBlockParams(*[p.data_ptr() for p in ps])
+    ws = _workspace(inp.device, lib.dcpt_nafblock_local_fwd_bf16_ws_bytes(B, H, W, Cc, int(k1), int(k2)))
+    check(lib.dcpt_nafblock_local_fwd_bf16(C.byref(pp), None if buf is None else buf.data_ptr(), 0 if buf is None else buf.numel(), inp.data_ptr(),
+                                           out.data_ptr(), ws.data_ptr(), ws.numel(), B, H, W, Cc, int(k1), int(k2), _stream(inp.device)),
+          "dcpt_nafblock_local_fwd_bf16")
+    return out
+
+
+def box_mean_bf16(x: torch.Tensor, k1: int, k2: int) -> torch.Tensor:
+    """k1 x k2 local mean of a bf16 feature map, replicate-padded back to its size (dcpt_box_mean_bf16; reference arch_util.py:378-396):
+    the pooling of the TLSC block on its own.  No autograd."""
+    lib = _lib.load()
+    _require_gpu_bf16(x)
+    x = _nhwc(x.detach())
+    B, Cc, H, W = x.shape
+    if Cc % 8:
+        raise _lib.DcptHipError(f"box_mean_bf16 needs a channel count that is a multiple of 8 (got {Cc})")
+    out = _empty_nhwc_bf16(B, Cc, H, W, x.device)
+    ws = _workspace(x.device, lib.dcpt_box_mean_bf16_ws_bytes(B, H, W, Cc, int(k1), int(k2)))
+    check(lib.dcpt_box_mean_bf16(x.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(), B, H, W, Cc, int(k1), int(k2), _stream(x.device)),
+          "dcpt_box_mean_bf16")
+    return out
+
+
 # ------------------------------------------------------------------------------------------------
 class _TakeBatchFn(torch.autograd.Function):
     """x[lo:hi] along the batch axis as a view; the backward builds the zero-padded gradient WITH THE INPUT'S STRIDES (torch's own

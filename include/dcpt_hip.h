@@ -302,6 +302,25 @@ size_t dcpt_nafblock_local_ws_bytes(int B, int H, int W, int C, int k1, int k2);
 int dcpt_nafblock_local_fwd(const dcpt_nafblock_params* p, const float* inp, float* out, void* ws, size_t ws_bytes, int B, int H,
                             int W, int C, int k1, int k2, dcpt_stream_t stream);
 
+/* The TLSC block in bf16 storage (still ABI 15: purely additive).  Same network semantics as dcpt_nafblock_local_fwd (nafnet_arch.py:277-288
+ * `NAFNet`, arch_util.py:313-455; the local mean itself arch_util.py:378-396) on bf16 activations with fp32 parameters: LayerNorm1 -> conv1 and
+ * the depthwise + SimpleGate forward as dcpt_nafblock_fwd_bf16 runs them at that width and pixel count, the k1 x k2 box mean of t2 (fp32
+ * window sums, one rounding to bf16 after the divide), t2s = bf16((Wsca mean + bsca) * t2) as ONE bf16 GEMM whose epilogue multiplies
+ * (one rounding), conv3 with bias / beta / residual, and the second half exactly as the global forward chooses it.  Inference only: nothing
+ * is kept.  k1 / k2 are clamped to H / W (arch_util.py:381); callers use the plain dcpt_nafblock_fwd_bf16 when the window covers the
+ * whole map (arch_util.py:352-353).  C % 8 == 0, C <= 1024.  `packed`: the block's dcpt_nafblock_wpack_bf16 buffer, or NULL -- the call then
+ * packs its weights itself; the operand copy of sca_w is made in the call either way (the pack layout is unchanged).  Workspace too small:
+ * DCPT_ERR_WS, nothing launched.  No synchronisation. */
+size_t dcpt_nafblock_local_fwd_bf16_ws_bytes(int B, int H, int W, int C, int k1, int k2);
+int dcpt_nafblock_local_fwd_bf16(const dcpt_nafblock_params* p, const void* packed, size_t packed_bytes, const uint16_t* inp, uint16_t* out,
+                                 void* ws, size_t ws_bytes, int B, int H, int W, int C, int k1, int k2, dcpt_stream_t stream);
+/* The box mean of that block on its own (arch_util.py:378-396): out[b][h][w][c] = mean of the k1 x k2 window of `in` (bf16 NHWC) whose
+ * top-left corner is (clamp(h - (k1-1)/2, 0, H-k1), clamp(w - (k2-1)/2, 0, W-k2)) -- the (H-k1+1) x (W-k2+1) valid means replicate-padded
+ * back to H x W with the smaller pad on the left / top.  k1 / k2 are clamped to H / W.  ws: dcpt_box_mean_bf16_ws_bytes (fp32 row sums). */
+size_t dcpt_box_mean_bf16_ws_bytes(int B, int H, int W, int C, int k1, int k2);
+int dcpt_box_mean_bf16(const uint16_t* in, uint16_t* out, void* ws, size_t ws_bytes, int B, int H, int W, int C, int k1, int k2,
+                       dcpt_stream_t stream);
+
 /* ---- network-edge 3x3 convs ------------------------------------------------------------------
  * intro: nafnet_arch.py:202-210,252  x NCHW [B][Cin][H][W] -> y NHWC [B][H][W][Cout]
  * ending: nafnet_arch.py:211-219,271-272  x NHWC -> y NCHW [B][Cout][H][W] (+ res NCHW, may be NULL) */
