@@ -8,7 +8,6 @@
 // the end stay on the fp32 kernels of dchead.hip behind casts (they touch each tensor once).
 #include "bf16_ops.h"
 #include "prof.h"
-#include "side.h"
 #include "../../include/dcpt_hip.h"
 
 namespace {
@@ -216,10 +215,7 @@ bool conv_bwd_below_ok(int64_t M, int Cin, int Cout, int ks) {   // may the Laye
 
 int conv_bwd(const bf16_t* dz, const bf16_t* x, const float* w, bf16_t* dx, float* dw, const ConvWsB& cw, int B, int H, int W, int Cin, int Cout,
              int ks, hipStream_t s, const FinCols* ln = nullptr, const bf16_t* dx_add = nullptr, const void* pk = nullptr,
-             const LnBelow* below = nullptr, hipStream_t sw = nullptr) {
-    // sw: the stream of the weight-gradient GEMM and the parameter-gradient reductions (a side stream forked by the caller once dz and the
-    // LayerNorm partials are ready; default: s)
-    if (!sw) sw = s;
+             const LnBelow* below = nullptr) {
     const int64_t M = (int64_t)B * H * W;
     GemmNTB g{};
     g.M = M; g.A = dz; g.N = Cin; g.C = dx; g.ldc = Cin; g.Bw = pk ? pk_bwd(pk, Cin, Cout, ks) : cw.wp;
@@ -243,7 +239,7 @@ int conv_bwd(const bf16_t* dz, const bf16_t* x, const float* w, bf16_t* dx, floa
         if (dx) DCPT_TRY(launch_gemm_nt_bf16(g, EDX, s));
         GemmTNG wg = cw.wg;
         wg.p[0].X = dz; wg.p[0].Y = x;
-        DCPT_TRY(launch_gemm_tn_bf16_256(wg, sw));
+        DCPT_TRY(launch_gemm_tn_bf16_256(wg, s));
         FinJobs f{};
         f.nslab = 1;
         f.slab[0].slab = wg.p[0].slab; f.slab[0].N = Cout; f.slab[0].K = wg.p[0].K; f.slab[0].splits = wg.p[0].slots; f.slab[0].cs_rows = wg.p[0].splits;
@@ -252,9 +248,9 @@ int conv_bwd(const bf16_t* dz, const bf16_t* x, const float* w, bf16_t* dx, floa
             f.ncols = 1;
             f.cols[0] = *ln;
         }
-        return launch_wgrad_finish(f, sw);
+        return launch_wgrad_finish(f, s);
     }
-    if (ln) DCPT_TRY(launch_colpart_reduce(ln->part, ln->R, 2, ln->C, ln->out0, ln->out1, nullptr, sw));
+    if (ln) DCPT_TRY(launch_colpart_reduce(ln->part, ln->R, 2, ln->C, ln->out0, ln->out1, nullptr, s));
     GemmTNB t{};
     t.M = M; t.X = dz; t.ldx = Cout; t.N = Cout; t.Y = x; t.slab = cw.slab; t.colsum = nullptr; t.splits = cw.splits; t.rows_per_split = cw.rps;
     if (ks == 1) {
@@ -262,15 +258,15 @@ int conv_bwd(const bf16_t* dz, const bf16_t* x, const float* w, bf16_t* dx, floa
         g.lda = Cout; g.K = Cout;
         if (dx) DCPT_TRY(launch_gemm_nt_bf16(g, EDX, s));
         t.ldy = Cin; t.K = Cin;
-        DCPT_TRY(launch_gemm_tn_bf16(t, sw));
-        return launch_wgrad_reduce(cw.slab, nullptr, cw.splits, 0, Cout, Cin, nullptr, nullptr, nullptr, dw, nullptr, nullptr, WR_PLAIN, sw);
+        DCPT_TRY(launch_gemm_tn_bf16(t, s));
+        return launch_wgrad_reduce(cw.slab, nullptr, cw.splits, 0, Cout, Cin, nullptr, nullptr, nullptr, dw, nullptr, nullptr, WR_PLAIN, s);
     }
     if (!pk && dx) DCPT_TRY(pack(w, cw.wp, Cout, 9 * Cin, 3, s));
     g.K = 9 * Cout; g.conv3 = 1; g.gH = H; g.gW = W; g.gC = Cout;
     if (dx) DCPT_TRY(launch_gemm_nt_bf16(g, EDX, s));
     t.K = 9 * Cin; t.yconv = 1; t.gH = H; t.gW = W; t.gC = Cin; t.ldy = Cin;
-    DCPT_TRY(launch_gemm_tn_bf16(t, sw));
-    return launch_wgrad_reduce(cw.slab, nullptr, cw.splits, 0, Cout, 9 * Cin, nullptr, nullptr, nullptr, dw, nullptr, nullptr, WR_CONV3, sw);
+    DCPT_TRY(launch_gemm_tn_bf16(t, s));
+    return launch_wgrad_reduce(cw.slab, nullptr, cw.splits, 0, Cout, 9 * Cin, nullptr, nullptr, nullptr, dw, nullptr, nullptr, WR_CONV3, s);
 }
 
 bool conv_shape_ok(int Cin, int Cout, int ks) { return (ks == 1 || ks == 3) && Cin % 8 == 0 && Cout % 8 == 0 && Cout <= 1024; }
@@ -433,34 +429,30 @@ extern "C" int dcpt_bottleneck_bwd_bf16(const uint16_t* dout, const uint16_t* x,
     trace_tag("head.ln_bwd_kernel");
     DCPT_TRY(launch_ln_act_bwd_bf16(dout, g[2].z, g[2].mu, g[2].rstd, g[2].lnw, g[2].y, bw.dshort, bw.cw[2].dz, bw.cw[2].lnpart, bw.cw[2].ln_nblk, M, C, s));
     int ln_rows = bw.cw[2].ln_nblk;   // rows of the current group's lnpart
-    // The three weight-gradient GEMMs and their reductions are off the chain dout -> dx and CAN run on the side stream (side.hip), forked as each
-    // dz is ready -- measured and left off: head alone 27.7 / 28.1 ms with, 28.1 / 28.1 without; DCPT step 91.5 / 92.3 with, 92.0 / 92.0 without
+    // The three weight-gradient GEMMs and their reductions are off the chain dout -> dx and could run on a side stream (side.hip), forked as each
+    // dz is ready -- measured and not kept: head alone 27.7 / 28.1 ms with, 28.1 / 28.1 without; DCPT step 91.5 / 92.3 with, 92.0 / 92.0 without
     // (profiles/r6/head_ln_epilogues/).  Every GEMM here owns whole CUs (one 256-row tile = 128-160 KB of LDS), so blocks of the two streams take
     // turns on a CU instead of sharing it: the kernels overlap in time (sum of durations 43 ms in a 29-ms span) and slow each other down by the
     // same amount.
-    static const int use_side = dcpt_tuning("DCPT_HEAD_SIDE", 0);
-    Side* sd = use_side ? side_for(s) : nullptr;
-    hipStream_t sw = side_stream(sd, s);
     for (int k = 2; k >= 0; --k) {
         const ConvWsB& cw = bw.cw[k];
-        DCPT_TRY(side_fork(sd, 2 - k, s));   // dz of group k and its LayerNorm partials are ready
         const FinCols ln{cw.lnpart, g[k].dlnw, g[k].dlnb, ln_rows, 2, gm.Cout[k], 0};
         const bf16_t* xin = k == 0 ? x : g[k - 1].y;
         if (k == 0) {
-            DCPT_TRY(conv_bwd(cw.dz, xin, g[k].w, dx, g[k].dw, cw, B, H, W, gm.Cin[k], gm.Cout[k], gm.ks[k], s, &ln, bw.dshort, g[k].wpacked, nullptr, sw));
+            DCPT_TRY(conv_bwd(cw.dz, xin, g[k].w, dx, g[k].dw, cw, B, H, W, gm.Cin[k], gm.Cout[k], gm.ks[k], s, &ln, bw.dshort, g[k].wpacked));
         } else if (conv_bwd_below_ok(M, gm.Cin[k], gm.Cout[k], gm.ks[k])) {
             const LnBelow lb{g[k - 1].z, g[k - 1].mu, g[k - 1].rstd, g[k - 1].lnw, g[k - 1].lnb, bw.cw[k - 1].dz, bw.cw[k - 1].lnpart};
-            DCPT_TRY(conv_bwd(cw.dz, xin, g[k].w, nullptr, g[k].dw, cw, B, H, W, gm.Cin[k], gm.Cout[k], gm.ks[k], s, &ln, nullptr, g[k].wpacked, &lb, sw));
+            DCPT_TRY(conv_bwd(cw.dz, xin, g[k].w, nullptr, g[k].dw, cw, B, H, W, gm.Cin[k], gm.Cout[k], gm.ks[k], s, &ln, nullptr, g[k].wpacked, &lb));
             ln_rows = bw.cw[k - 1].ln_tiles;
         } else {
-            DCPT_TRY(conv_bwd(cw.dz, xin, g[k].w, bw.dybuf, g[k].dw, cw, B, H, W, gm.Cin[k], gm.Cout[k], gm.ks[k], s, &ln, nullptr, g[k].wpacked, nullptr, sw));
+            DCPT_TRY(conv_bwd(cw.dz, xin, g[k].w, bw.dybuf, g[k].dw, cw, B, H, W, gm.Cin[k], gm.Cout[k], gm.ks[k], s, &ln, nullptr, g[k].wpacked));
             trace_tag("head.ln_bwd_kernel");
             DCPT_TRY(launch_ln_act_bwd_bf16(bw.dybuf, g[k - 1].z, g[k - 1].mu, g[k - 1].rstd, g[k - 1].lnw, g[k - 1].y, nullptr, bw.cw[k - 1].dz,
                                             bw.cw[k - 1].lnpart, bw.cw[k - 1].ln_nblk, M, gm.Cout[k - 1], s));
             ln_rows = bw.cw[k - 1].ln_nblk;
         }
     }
-    return side_join(sd, s);   // the caller's stream continues only after every parameter gradient is written
+    return DCPT_OK;
 }
 
 extern "C" size_t dcpt_conv1x1_pool_relu_bf16_ws_bytes(int B, int H, int W, int Cin, int Cout, int backward) {

@@ -19,7 +19,7 @@ namespace {
 
 constexpr int RH = 8;  // rows per band
 
-// A thread owns VW channels (4 by default; VW = 2 keeps the 9 (x2) taps, the running rows and the loads at ~80 VGPRs
+// A thread owns VW channels (always 4, DW_WIDTH below; VW = 2 keeps the 9 (x2) taps, the running rows and the loads at ~80 VGPRs
 // -> 5-7 waves per SIMD instead of 2-3, which measured no faster on MI355X), and every global access is a range-checked
 // buffer access relative to the image, so halo rows / columns are ordinary loads that return 0 (no exec-mask
 // branches: the loads of a row are all in flight together).
@@ -143,11 +143,6 @@ struct DwP {
     float* part;        // fwd: pool_part [B][NBLK][C]; bwd_b: wpart [B*NBLK][10][2C]
     int B, H, W, C;
     int Ctot;  // bwd_b / plain: total channel count of the depthwise conv
-    // fused backward, optional: per-pixel partials of  dt1 . u  and  dt1 . (t1 - cvec)  over this block's channel chunk,
-    // rowpart[pixel][gridDim.x][2] -- the two row sums of the LayerNorm backward downstream (gemm.h, E_LNBWD2)
-    float* rowpart;
-    const float* uvec;   // [2C]
-    const float* cvec;   // [2C]
 };
 
 __device__ __forceinline__ float gelu_f(float a) { return 0.5f * a * (1.f + erff(a * 0.70710678118654752f)); }
@@ -340,159 +335,6 @@ __global__ __launch_bounds__(256) void dw_bwd_b_kernel(const DwP p) {
     for (int t = 0; t < 10; ++t) dw_block_reduce<VW>(red, wa[t], tid, ql, pl, mp.QB, mp.PB, qok, part + t * C2 + c0);
 }
 
-// Fused SimpleGate + depthwise backward (NAFNet):  dt1 = dw3x3^T(da),  da_1 = dt2 * a_2,  da_2 = dt2 * a_1,
-// a = dw3x3(t1) + b2 (recomputed),  dt2 = dts * s + dpool,  plus the per-block partial sums of dw2[ch][tap] and db2[ch].
-// `da` never goes to memory.  A thread owns VW channels of ONE half at one pixel column and streams down its row range; the
-// thread of the other half sits in the neighbouring lane (lane ^ 1), and the only thing the two exchange is the recomputed
-// conv output: da_own = dt2 * a_other, one DPP quad-permute per value.  For every t1 row a thread loads columns x-2..x+2,
-// advances the forward-conv accumulators of columns x-1, x, x+1, turns the completed row of a into da at those three
-// columns, and feeds it to the transposed-conv accumulators and the tap gradients (which pair da[row][x] with the t1 rows
-// it still holds).  Splitting the halves across lanes halves the per-thread state of the earlier one-thread-both-halves form,
-// which makes VW = 4 (16-byte accesses) fit: measured on the training step, split + VW 4 is +0.5 % over the unsplit VW 2
-// kernel, while split + VW 2 (106 VGPRs, 4 waves/SIMD) is -1 % -- the kernel is limited by memory instructions issued per
-// byte, not by occupancy.
-// HBM traffic: t1 and dts once (+2-row halos), dt1 once -- 5 tensor units instead of 11 for the two-kernel form.
-template <int VW, typename ST = float>
-__global__ __launch_bounds__(256) void dw_bwd_fused_kernel(const DwP p) {
-    constexpr uint32_t ES = sizeof(ST);
-    __shared__ float red[256 * VW];
-    const int C = p.C, C2 = 2 * p.C;
-    const DwMap mp = dw_map(p.H, p.W, C2 / VW);   // "groups" = (channel group, half) pairs
-    const DwBlk bk = dw_block(mp);
-    const int tid = threadIdx.x;
-    const int ql = tid % mp.QB, pl = tid / mp.QB;
-    const int hq = bk.x * mp.QB + ql;             // even: first half, odd: second half of channel group hq / 2
-    const int b = bk.z;
-    const bool qok = hq < mp.QW;
-    const int cg = VW * (hq >> 1);                // channels inside a half (dts / s / dpool index)
-    const int co = (hq & 1) * C + cg;             // this thread's channels of t1 / dt1 / the depthwise weights
-    vf<VW> w[9];
-#pragma unroll
-    for (int t = 0; t < 9; ++t) w[t] = gld<VW>(p.w2p + t * C2 + co, qok);
-    const vf<VW> bias = gld<VW>(p.b2 + co, qok && p.b2);
-    vf<VW> sv, dpv = vz<VW>();
-#pragma unroll
-    VFOR sv.v[i_] = 1.f;
-    if (qok && p.simg) {
-        sv = gld<VW>(p.simg + (int64_t)b * C + cg, true);
-        dpv = gld<VW>(p.dpool + (int64_t)b * C + cg, true);
-    }
-    vf<VW> uv = vz<VW>(), cv = vz<VW>();
-    if (p.rowpart && qok) {
-        uv = gld<VW>(p.uvec + co, true);
-        cv = gld<VW>(p.cvec + co, true);
-    }
-    vf<VW> g[10];   // tap gradients (0..8) and bias gradient (9)
-#pragma unroll
-    for (int t = 0; t < 10; ++t) g[t] = vz<VW>();
-    const int wc = bk.y % mp.nwc, nrp = gridDim.y / mp.nwc, rpp = (p.H + nrp - 1) / nrp;
-    const int x = wc * mp.PB + pl;
-    const bool ok = qok && x < p.W;
-    const int h0 = (bk.y / mp.nwc) * rpp;
-    const int h1 = (h0 + rpp < p.H) ? h0 + rpp : p.H;
-    const int rb = h0 - 2 > 0 ? h0 - 2 : 0;
-    const int64_t img = ((int64_t)b * p.H + rb) * p.W;
-    const rsrc_t rs_t = make_rsrc((const ST*)p.in0 + img * C2);
-    const rsrc_t rs_d = make_rsrc((const ST*)p.in1 + img * C);
-    const rsrc_t rs_o = make_rsrc((ST*)p.out + img * C2);
-    // column validity of x-2 .. x+2 (a column outside the image: its t1 is zero padding, its da does not exist)
-    uint32_t cs[5];
-    bool cin[5];
-#pragma unroll
-    for (int j = 0; j < 5; ++j) {
-        cin[j] = ok && x + j - 2 >= 0 && x + j - 2 < p.W;
-        cs[j] = cin[j] ? 0u : COL_SENT;
-    }
-    // forward-conv running accumulators of columns x-1, x, x+1 (index 0..2): A0 = row r-1 (complete after this step), A1 = row r
-    vf<VW> A0[3], A1[3];
-    // transposed-conv running accumulators at column x: B0 = output row rho-1, B1 = output row rho
-    vf<VW> B0 = vz<VW>(), B1 = vz<VW>();
-    // t1 at columns x-1..x+1 of the two previous rows (for the tap gradients)
-    vf<VW> Tm[3], Tc[3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) A0[j] = A1[j] = Tm[j] = Tc[j] = vz<VW>();
-    for (int r = h0 - 2; r <= h1 + 1; ++r) {
-        // ---- t1 row r, columns x-2..x+2
-        const bool rin = r >= 0 && r < p.H;
-        const uint32_t ro = rin ? (uint32_t)(((r - rb) * p.W + x) * C2 + co) * ES : ROW_SENT;
-        vf<VW> T[5];
-#pragma unroll
-        for (int j = 0; j < 5; ++j) T[j] = bldT<VW, ST>(rs_t, (ro + (uint32_t)((j - 2) * C2 * (int)ES)) | cs[j]);
-        // ---- dts of row rho = r-1 at columns x-1..x+1
-        const int rho = r - 1;
-        const bool rho_in = rho >= 0 && rho < p.H;
-        vf<VW> D[3];
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-            D[j] = bldT<VW, ST>(rs_d, rho_in ? ((uint32_t)(((rho - rb) * p.W + x + j - 1) * C + cg) * ES) | cs[j + 1] : ROW_SENT);
-        // ---- forward conv: row r contributes kernel row 2 to a[r-1], row 1 to a[r], row 0 to a[r+1]
-        vf<VW> A2[3];
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            A0[j] = vfma(w[6], T[j], vfma(w[7], T[j + 1], vfma(w[8], T[j + 2], A0[j])));
-            A1[j] = vfma(w[3], T[j], vfma(w[4], T[j + 1], vfma(w[5], T[j + 2], A1[j])));
-            A2[j] = vfma(w[0], T[j], vfma(w[1], T[j + 1], vmul(w[2], T[j + 2])));
-        }
-        // ---- da of row rho at columns x-1..x+1 (zero where the pixel does not exist): dt2 * (a of the OTHER half, lane ^ 1)
-        vf<VW> da[3];
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            const bool pin = rho_in && cin[j + 1];
-            const vf<VW> dt2 = vfma(D[j], sv, dpv);
-            const vf<VW> a_own = vadd(A0[j], bias);
-            vf<VW> a_other;
-#pragma unroll
-            VFOR a_other.v[i_] = dpp_perm<0xB1>(a_own.v[i_]);
-            da[j] = pin ? vmul(dt2, a_other) : vz<VW>();
-        }
-        // ---- transposed conv: da row rho feeds dt1 rows rho-1 (ky = 0), rho (ky = 1), rho+1 (ky = 2); da[.][x-1+j] <-> kx = 2-j
-        B0 = vfma(w[2], da[0], vfma(w[1], da[1], vfma(w[0], da[2], B0)));
-        B1 = vfma(w[5], da[0], vfma(w[4], da[1], vfma(w[3], da[2], B1)));
-        const vf<VW> B2 = vfma(w[8], da[0], vfma(w[7], da[1], vmul(w[6], da[2])));
-        {
-            const int y = rho - 1;   // complete now
-            bstT<VW, ST>(rs_o, (ok && y >= h0 && y < h1) ? (uint32_t)(((y - rb) * p.W + x) * C2 + co) * ES : ROW_SENT, B0);
-            if (p.rowpart) {   // t1[y][x] is Tm[1] here (rows r-2 = y, r-1, r are in Tm, Tc, T)
-                float a1 = 0.f, a2 = 0.f;
-#pragma unroll
-                VFOR {
-                    a1 = fmaf(B0.v[i_], uv.v[i_], a1);
-                    a2 = fmaf(B0.v[i_], Tm[1].v[i_] - cv.v[i_], a2);
-                }
-                if (!qok) a1 = a2 = 0.f;
-                a1 = group_sum(a1, mp.QB);   // the QB lanes of this pixel (one channel chunk)
-                a2 = group_sum(a2, mp.QB);
-                if (ql == 0 && x < p.W && y >= h0 && y < h1)
-                    *reinterpret_cast<float2*>(p.rowpart + ((((int64_t)b * p.H + y) * p.W + x) * gridDim.x + bk.x) * 2) = make_float2(a1, a2);
-            }
-        }
-        // ---- tap gradients: da[rho][x] with t1 rows rho-1 (Tm), rho (Tc), rho+1 (= row r, T) at columns x-1..x+1; rows of this
-        //      block's range only, so that every pixel is counted once
-        if (rho >= h0 && rho < h1) {
-#pragma unroll
-            for (int kx = 0; kx < 3; ++kx) {
-                g[0 * 3 + kx] = vfma(da[1], Tm[kx], g[0 * 3 + kx]);
-                g[1 * 3 + kx] = vfma(da[1], Tc[kx], g[1 * 3 + kx]);
-                g[2 * 3 + kx] = vfma(da[1], T[kx + 1], g[2 * 3 + kx]);
-            }
-            g[9] = vadd(g[9], da[1]);
-        }
-        // ---- shift the pipelines
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            A0[j] = A1[j];
-            A1[j] = A2[j];
-            Tm[j] = Tc[j];
-            Tc[j] = T[j + 1];
-        }
-        B0 = B1;
-        B1 = B2;
-    }
-    float* part = p.part + ((int64_t)b * gridDim.y + bk.y) * 10 * C2;
-#pragma unroll
-    for (int t = 0; t < 10; ++t) dw_block_reduce<VW>(red, g[t], tid, ql, pl, mp.QB, mp.PB, qok, part + t * C2 + co);
-}
-
 // Plain depthwise 3x3 (no bias, no gate) over Ctot channels (Restormer MDTA qkv_dwconv), plus per-block partial
 // sums of out^2 for the first nsq channels (the L2 norms of q and k over the pixels).
 template <int VW>
@@ -573,27 +415,13 @@ __global__ __launch_bounds__(256) void dw_wgrad_reduce_kernel(const float* __res
     }
 }
 
-// channels per thread (2 or 4) and grid target; DCPT_DW_VW / DCPT_DW_BLOCKS override them for experiments
-int dw_vw() {
-    static int v = 0;
-    if (v == 0) {
-        v = dcpt_tuning("DCPT_DW_VW", 4) == 2 ? 2 : 4;
-    }
-    return v;
-}
-int dw_target_blocks() {
-    static int v = 0;
-    if (v == 0) {
-        v = dcpt_tuning("DCPT_DW_BLOCKS", 1024);
-        if (v <= 0) v = 1024;
-    }
-    return v;
-}
+constexpr int DW_WIDTH = 4;                // channels per thread (16-byte accesses)
+constexpr int DW_TARGET_BLOCKS = 1024;  // grid target
 
 int nblk_for(const DwGeom& g, int quads) {
     const DwMap mp = dw_map(g.H, g.W, quads);
     // column chunks x row parts; a part is at least RH rows so that the two halo rows stay a small fraction
-    int64_t nrp = cdiv64(cdiv64(dw_target_blocks(), (int64_t)g.B * mp.nqc), mp.nwc);
+    int64_t nrp = cdiv64(cdiv64(DW_TARGET_BLOCKS, (int64_t)g.B * mp.nqc), mp.nwc);
     const int64_t maxp = g.H / RH > 0 ? g.H / RH : 1;
     if (nrp > maxp) nrp = maxp;
     if (nrp < 1) nrp = 1;
@@ -601,25 +429,12 @@ int nblk_for(const DwGeom& g, int quads) {
 }
 }  // namespace
 
-int dw_fused_vw() {   // channels per thread of the fused backward kernel (DCPT_DW_FUSED_VW overrides for experiments)
-    static int v = 0;
-    if (v == 0) {
-        v = dcpt_tuning("DCPT_DW_FUSED_VW", 4) == 2 ? 2 : 4;
-    }
-    return v;
-}
-int dw_num_blocks_per_image_fused(const DwGeom& g) { return nblk_for(g, 2 * g.C / dw_fused_vw()); }
-int dw_num_blocks_per_image(const DwGeom& g) { return nblk_for(g, g.C / dw_vw()); }
+int dw_num_blocks_per_image(const DwGeom& g) { return nblk_for(g, g.C / DW_WIDTH); }
 
 // a block's windows span its row range + halo: (rows/part + 5) * W * Ct floats must fit the 32-bit offsets
 #define DW_CHECK_RANGE(H, W, Ct, NBLK, NWC)                                                                             \
     DCPT_CHECK_ARG(((double)cdiv((H), (NBLK) / (NWC) > 0 ? (NBLK) / (NWC) : 1) + 5.0) * (W) * (Ct) * 4.0 < 1.0e9,        \
                    "depthwise conv: a row range of a %d x %d x %d image exceeds the 32-bit window", H, W, Ct)
-#define DW_LAUNCH(KERNEL, ...)                                  \
-    do {                                                        \
-        if (dw_vw() == 2) KERNEL<2 __VA_ARGS__;                 \
-        else KERNEL<4 __VA_ARGS__;                              \
-    } while (0)
 
 int launch_dw_pack_weights(const float* w2, float* w2p, int C2, hipStream_t s) {
     dw_pack_kernel<<<dim3(cdiv(C2 * 9, 256)), dim3(256), 0, s>>>(w2, w2p, C2);
@@ -634,73 +449,17 @@ int launch_dw_fwd(const float* t1, const float* w2p, const float* b2, float* t2,
     DwP p{};
     p.in0 = t1; p.w2p = w2p; p.b2 = b2; p.out = t2; p.part = pool_part;
     p.B = g.B; p.H = g.H; p.W = g.W; p.C = g.C;
-    const DwMap mp = dw_map(g.H, g.W, g.C / dw_vw());
+    const DwMap mp = dw_map(g.H, g.W, g.C / DW_WIDTH);
     DW_CHECK_RANGE(g.H, g.W, 2 * g.C, dw_num_blocks_per_image(g), mp.nwc);
-    DW_LAUNCH(dw_gate_kernel, , 0, 0><<<dim3(mp.nqc, dw_num_blocks_per_image(g), g.B), dim3(256), 0, s>>>(p));
+    dw_gate_kernel<DW_WIDTH, 0, 0><<<dim3(mp.nqc, dw_num_blocks_per_image(g), g.B), dim3(256), 0, s>>>(p);
     DCPT_CHECK_LAUNCH("dw_fwd");
-    return DCPT_OK;
-}
-
-int dw_fused_row_chunks(const DwGeom& g) { return dw_map(g.H, g.W, 2 * g.C / dw_fused_vw()).nqc; }
-
-int launch_dw_bwd_fused(const float* dts, const float* t1, const float* w2p, const float* b2, const float* simg, const float* dpool,
-                        float* dt1, float* wpart, const DwGeom& g, hipStream_t s, float* rowpart, const float* uvec, const float* cvec) {
-    trace_tag("dw.reg_bwd_f32");
-    DCPT_CHECK_ARG(g.C % 4 == 0 && g.B <= 65535, "dw_bwd: C=%d must be a multiple of 4", g.C);
-    DwP p{};
-    p.in0 = t1; p.in1 = dts; p.w2p = w2p; p.b2 = b2; p.simg = simg; p.dpool = dpool; p.out = dt1; p.part = wpart;
-    p.rowpart = rowpart; p.uvec = uvec; p.cvec = cvec;
-    p.B = g.B; p.H = g.H; p.W = g.W; p.C = g.C;
-    const int vw = dw_fused_vw();
-    const DwMap mp = dw_map(g.H, g.W, 2 * g.C / vw);
-    const int nblk = dw_num_blocks_per_image_fused(g);
-    DW_CHECK_RANGE(g.H, g.W, 2 * g.C, nblk, mp.nwc);
-    if (vw == 2) dw_bwd_fused_kernel<2><<<dim3(mp.nqc, nblk, g.B), dim3(256), 0, s>>>(p);
-    else dw_bwd_fused_kernel<4><<<dim3(mp.nqc, nblk, g.B), dim3(256), 0, s>>>(p);
-    DCPT_CHECK_LAUNCH("dw_bwd_fused");
-    return DCPT_OK;
-}
-
-// ---- bf16-storage variants (bf16.h): same kernels, activations read / written as bf16, partial sums and parameters fp32
-int launch_dw_fwd_bf16(const bf16_t* t1, const float* w2p, const float* b2, bf16_t* t2, float* pool_part, const DwGeom& g, hipStream_t s) {
-    trace_tag("dw.reg_fwd_bf16");
-    DCPT_CHECK_ARG(g.C % 4 == 0 && g.B <= 65535, "dw_fwd_bf16: C=%d must be a multiple of 4, B<=65535", g.C);
-    DwP p{};
-    p.in0 = reinterpret_cast<const float*>(t1); p.w2p = w2p; p.b2 = b2; p.out = reinterpret_cast<float*>(t2); p.part = pool_part;
-    p.B = g.B; p.H = g.H; p.W = g.W; p.C = g.C;
-    const DwMap mp = dw_map(g.H, g.W, g.C / 4);
-    const int nblk = nblk_for(g, g.C / 4);
-    DW_CHECK_RANGE(g.H, g.W, 2 * g.C, nblk, mp.nwc);
-    dw_gate_kernel<4, 0, 0, bf16_t><<<dim3(mp.nqc, nblk, g.B), dim3(256), 0, s>>>(p);
-    DCPT_CHECK_LAUNCH("dw_fwd_bf16");
-    return DCPT_OK;
-}
-int dw_num_blocks_per_image_bf16(const DwGeom& g) { return nblk_for(g, g.C / 4); }
-int dw_num_blocks_per_image_fused_bf16(const DwGeom& g) { return nblk_for(g, 2 * g.C / 4); }
-
-int dw_fused_row_chunks_bf16(const DwGeom& g) { return dw_map(g.H, g.W, 2 * g.C / 4).nqc; }
-
-int launch_dw_bwd_fused_bf16(const bf16_t* dts, const bf16_t* t1, const float* w2p, const float* b2, const float* simg, const float* dpool,
-                             bf16_t* dt1, float* wpart, const DwGeom& g, hipStream_t s, float* rowpart, const float* uvec, const float* cvec) {
-    trace_tag("dw.reg_bwd_bf16");
-    DCPT_CHECK_ARG(g.C % 4 == 0 && g.B <= 65535, "dw_bwd_bf16: C=%d must be a multiple of 4", g.C);
-    DwP p{};
-    p.in0 = reinterpret_cast<const float*>(t1); p.in1 = reinterpret_cast<const float*>(dts); p.w2p = w2p; p.b2 = b2; p.simg = simg;
-    p.dpool = dpool; p.out = reinterpret_cast<float*>(dt1); p.part = wpart;
-    p.rowpart = rowpart; p.uvec = uvec; p.cvec = cvec;
-    p.B = g.B; p.H = g.H; p.W = g.W; p.C = g.C;
-    const DwMap mp = dw_map(g.H, g.W, 2 * g.C / 4);
-    const int nblk = nblk_for(g, 2 * g.C / 4);
-    DW_CHECK_RANGE(g.H, g.W, 2 * g.C, nblk, mp.nwc);
-    dw_bwd_fused_kernel<4, bf16_t><<<dim3(mp.nqc, nblk, g.B), dim3(256), 0, s>>>(p);
-    DCPT_CHECK_LAUNCH("dw_bwd_fused_bf16");
     return DCPT_OK;
 }
 
 // ---- generic entry points used by the Restormer blocks ---------------------------------------------
 int dw_num_blocks_generic(int B, int H, int W, int Ctot) {
     DwGeom g{B, H, W, Ctot};
-    return nblk_for(g, Ctot / dw_vw());
+    return nblk_for(g, Ctot / DW_WIDTH);
 }
 
 int launch_dw_gelu_fwd(const float* u, const float* w2p, float* t, int B, int H, int W, int Ch, hipStream_t s) {
@@ -708,9 +467,9 @@ int launch_dw_gelu_fwd(const float* u, const float* w2p, float* t, int B, int H,
     DwP p{};
     p.in0 = u; p.w2p = w2p; p.out = t; p.B = B; p.H = H; p.W = W; p.C = Ch;
     DwGeom g{B, H, W, Ch};
-    const DwMap mp = dw_map(H, W, Ch / dw_vw());
+    const DwMap mp = dw_map(H, W, Ch / DW_WIDTH);
     DW_CHECK_RANGE(H, W, 2 * Ch, dw_num_blocks_per_image(g), mp.nwc);
-    DW_LAUNCH(dw_gate_kernel, , 0, 1><<<dim3(mp.nqc, dw_num_blocks_per_image(g), B), dim3(256), 0, s>>>(p));
+    dw_gate_kernel<DW_WIDTH, 0, 1><<<dim3(mp.nqc, dw_num_blocks_per_image(g), B), dim3(256), 0, s>>>(p);
     DCPT_CHECK_LAUNCH("dw_gelu_fwd");
     return DCPT_OK;
 }
@@ -720,9 +479,9 @@ int launch_dw_gelu_bwd_a(const float* dt, const float* u, const float* w2p, floa
     DwP p{};
     p.in0 = u; p.in1 = dt; p.w2p = w2p; p.out = da; p.B = B; p.H = H; p.W = W; p.C = Ch;
     DwGeom g{B, H, W, Ch};
-    const DwMap mp = dw_map(H, W, Ch / dw_vw());
+    const DwMap mp = dw_map(H, W, Ch / DW_WIDTH);
     DW_CHECK_RANGE(H, W, 2 * Ch, dw_num_blocks_per_image(g), mp.nwc);
-    DW_LAUNCH(dw_gate_kernel, , 1, 1><<<dim3(mp.nqc, dw_num_blocks_per_image(g), B), dim3(256), 0, s>>>(p));
+    dw_gate_kernel<DW_WIDTH, 1, 1><<<dim3(mp.nqc, dw_num_blocks_per_image(g), B), dim3(256), 0, s>>>(p);
     DCPT_CHECK_LAUNCH("dw_gelu_bwd_a");
     return DCPT_OK;
 }
@@ -732,9 +491,9 @@ int launch_dw_plain_fwd(const float* x, const float* w2p, float* y, float* sq_pa
     DCPT_CHECK_ARG(Ctot % 4 == 0 && nsq % 4 == 0 && B <= 65535, "dw_plain_fwd: Ctot=%d", Ctot);
     DwP p{};
     p.in0 = x; p.w2p = w2p; p.out = y; p.part = sq_part; p.B = B; p.H = H; p.W = W; p.Ctot = Ctot;
-    const DwMap mp = dw_map(H, W, Ctot / dw_vw());
+    const DwMap mp = dw_map(H, W, Ctot / DW_WIDTH);
     DW_CHECK_RANGE(H, W, Ctot, dw_num_blocks_generic(B, H, W, Ctot), mp.nwc);
-    DW_LAUNCH(dw_plain_kernel, ><<<dim3(mp.nqc, dw_num_blocks_generic(B, H, W, Ctot), B), dim3(256), 0, s>>>(p, nsq));
+    dw_plain_kernel<DW_WIDTH><<<dim3(mp.nqc, dw_num_blocks_generic(B, H, W, Ctot), B), dim3(256), 0, s>>>(p, nsq);
     DCPT_CHECK_LAUNCH("dw_plain_fwd");
     return DCPT_OK;
 }
@@ -745,9 +504,9 @@ int launch_dw_generic_bwd(const float* dy, const float* x, const float* w2p, flo
     DCPT_CHECK_ARG(Ctot % 4 == 0 && B <= 65535, "dw_generic_bwd: Ctot=%d", Ctot);
     DwP p{};
     p.in0 = dy; p.in1 = x; p.w2p = w2p; p.out = dx; p.part = wpart; p.B = B; p.H = H; p.W = W; p.Ctot = Ctot;
-    const DwMap mp = dw_map(H, W, Ctot / dw_vw());
+    const DwMap mp = dw_map(H, W, Ctot / DW_WIDTH);
     DW_CHECK_RANGE(H, W, Ctot, dw_num_blocks_generic(B, H, W, Ctot), mp.nwc);
-    DW_LAUNCH(dw_bwd_b_kernel, ><<<dim3(mp.nqc, dw_num_blocks_generic(B, H, W, Ctot), B), dim3(256), 0, s>>>(p));
+    dw_bwd_b_kernel<DW_WIDTH><<<dim3(mp.nqc, dw_num_blocks_generic(B, H, W, Ctot), B), dim3(256), 0, s>>>(p);
     DCPT_CHECK_LAUNCH("dw_generic_bwd");
     return DCPT_OK;
 }

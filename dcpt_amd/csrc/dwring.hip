@@ -293,11 +293,6 @@ DwrGeom dwr_geom(const DwGeom& g, int es) {
     return d;
 }
 
-bool dwr_enabled() {
-    static const int on = dcpt_tuning("DCPT_DW_RING", 1);
-    return on != 0;
-}
-
 template <typename ST, int GATE = 0>
 int launch_fwd(const void* t1, const float* w2p, const float* b2, void* t2, float* pool_part, const DwGeom& g, hipStream_t s) {
     const DwrGeom d = dwr_geom(g, (int)sizeof(ST));
@@ -312,10 +307,10 @@ int launch_fwd(const void* t1, const float* w2p, const float* b2, void* t2, floa
 
 
 // ---- fused SimpleGate + depthwise BACKWARD on the row ring ------------------------------------------------------------------
-// Same math as dw_bwd_fused_kernel (dwconv.hip):  a = dw3x3(t1) + b2 (recomputed),  dt2 = dts * s + dpool,  da_1 = dt2 * a_2,
-// da_2 = dt2 * a_1,  dt1 = dw3x3^T(da),  per-block partial sums of the tap / bias gradients.  The register version recomputes a
-// at three columns per thread (5 overlapping global loads of t1 and 3 of dts per pixel: it takes 826 / 790 us at level 0 in
-// fp32 / bf16 -- the same time for half the bytes, i.e. it is instruction-bound).  Here every quantity is computed ONCE:
+// a = dw3x3(t1) + b2 (recomputed),  dt2 = dts * s + dpool,  da_1 = dt2 * a_2,
+// da_2 = dt2 * a_1,  dt1 = dw3x3^T(da),  per-block partial sums of the tap / bias gradients.  The retired register version recomputed a
+// at three columns per thread (5 overlapping global loads of t1 and 3 of dts per pixel: it took 826 / 790 us at level 0 in
+// fp32 / bf16 -- the same time for half the bytes, i.e. it was instruction-bound).  Here every quantity is computed ONCE:
 //   * t1 row r and dts row r-1 arrive by LDS-DMA in ring slot (it % R), R - 2 rows ahead;
 //   * a thread owns TWO channels of BOTH gate halves at TWO adjacent pixels: it completes a[r-1] from the running forward-conv
 //     accumulators, forms da[r-1] at its two pixels (both halves are in the thread, no lane exchange), accumulates the 2 x 9 tap
@@ -707,11 +702,6 @@ DwrBGeom dwr_bwd_geom(const DwGeom& g) {
     return d;
 }
 
-bool dwr_bwd_enabled() {
-    static const int on = dcpt_tuning("DCPT_DW_RING_BWD", 1);
-    return on != 0;
-}
-
 template <typename ST, int GATE = 0>
 int launch_bwd(const void* dts, const void* t1, const float* w2p, const float* b2, const float* simg, const float* dpool, void* dt1,
                float* wpart, const DwGeom& g, hipStream_t s, float* tout = nullptr) {
@@ -747,7 +737,7 @@ int launch_bwd(const void* dts, const void* t1, const float* w2p, const float* b
 
 }  // namespace
 
-bool dw_ring_usable(const DwGeom& g, int es) { return dwr_enabled() && g.B <= 65535 && (g.C * es) % 16 == 0 && g.W >= 1; }
+bool dw_ring_usable(const DwGeom& g, int es) { return g.B <= 65535 && (g.C * es) % 16 == 0 && g.W >= 1; }
 int dw_ring_num_blocks_per_image(const DwGeom& g, int es) {
     const DwrGeom d = dwr_geom(g, es);
     return d.nwc * d.nrp;
@@ -762,7 +752,7 @@ int launch_dw_ring_fwd_bf16(const bf16_t* t1, const float* w2p, const float* b2,
 }
 
 // fused SimpleGate + depthwise backward on the ring; wpart[B][dw_ring_bwd_num_blocks_per_image][10][2C]
-bool dw_ring_bwd_usable(const DwGeom& g, int es) { return dwr_bwd_enabled() && g.B <= 65535 && (g.C * es) % 16 == 0 && g.C % 2 == 0 && g.W >= 1; }
+bool dw_ring_bwd_usable(const DwGeom& g, int es) { return g.B <= 65535 && (g.C * es) % 16 == 0 && g.C % 2 == 0 && g.W >= 1; }
 int dw_ring_bwd_num_blocks_per_image(const DwGeom& g) {
     const DwrBGeom d = dwr_bwd_geom(g);
     return d.nwc * d.nrp;

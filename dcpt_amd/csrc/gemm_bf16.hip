@@ -457,10 +457,7 @@ int launch_gemm_nt_bf16(const GemmNTB& pin, int epi, hipStream_t s) {
     if (epi == EB_DOTCOL) DCPT_CHECK_ARG(p.colpart && p.res && p.nb == 1, "gemm_nt_bf16: column-dot epilogue needs colpart and res");
     if (epi == EB_RESID) DCPT_CHECK_ARG(p.res, "gemm_nt_bf16: residual epilogue needs res");
     if (epi == EB_MUL) DCPT_CHECK_ARG(p.res && !p.conv3 && !p.gather2, "gemm_nt_bf16: multiply epilogue needs res and a plain A operand");
-    if (epi == EB_SGBWD) DCPT_CHECK_ARG(p.aux && p.ldc == 2 * p.N && (!p.rowpart || (p.uvec && p.cvec)), "gemm_nt_bf16: SimpleGate-backward epilogue needs aux and ldc == 2N");
-    if (epi == EB_LNBWD2)
-        DCPT_CHECK_ARG(p.res && p.mu && p.rstd && p.lnw && p.colpart && p.rowpart && p.rowparts >= 1 && p.rowparts <= 8 && p.nb == 1,
-                       "gemm_nt_bf16: LayerNorm-backward epilogue needs res / mu / rstd / lnw / colpart / rowpart (<= 8 partials per row)");
+    if (epi == EB_SGBWD) DCPT_CHECK_ARG(p.aux && p.ldc == 2 * p.N, "gemm_nt_bf16: SimpleGate-backward epilogue needs aux and ldc == 2N");
     if (epi == EB_LNFWD)
         DCPT_CHECK_ARG(p.y2 && p.lnw && p.lnb && p.mu_out && p.rstd_out && p.ldc == p.N && p.nb == 1 && !p.gather2 &&
                            gemm_nt_bf16_ln_epi_ok(p.M, p.N, p.K, p.conv3, p.gC),
@@ -472,7 +469,6 @@ int launch_gemm_nt_bf16(const GemmNTB& pin, int epi, hipStream_t s) {
     const double mn = (double)p.M * p.N, mk = (double)p.M * p.K;
     double bytes = mk + mn * (epi == EB_SGBWD ? 4 : epi == EB_BIASGATE ? 1.5 : 1) + (double)p.N * p.K;
     if (epi == EB_RESID || epi == EB_DOTCOL || epi == EB_SCATTER_ADD || epi == EB_MUL) bytes += mn;
-    if (epi == EB_LNBWD2) bytes += 2 * mn;
     if (epi == EB_LNFWD) bytes += mn * (p.res ? 2 : 1);
     if (epi == EB_LNBWDM) bytes += mn * (1 + (p.ymask ? 1 : 0) + (p.y2 ? 1 : 0));
     ProfScope prof(s, PROF_NT + 256 + epi, p.M, p.N, p.K, 2.0 * mn * p.K * p.nb, bytes * 2.0 * p.nb);
@@ -498,7 +494,6 @@ int launch_gemm_nt_bf16(const GemmNTB& pin, int epi, hipStream_t s) {
         case EB_SGBWD: return launch_nt<EB_SGBWD>(p, s);
         case EB_BIASGATE: return launch_nt<EB_BIASGATE>(p, s);
         case EB_DOTCOL: return launch_nt<EB_DOTCOL>(p, s);
-        case EB_LNBWD2: return launch_nt<EB_LNBWD2>(p, s);
         case EB_SCATTER: return launch_nt<EB_SCATTER>(p, s);
         case EB_SCATTER_ADD: return launch_nt<EB_SCATTER_ADD>(p, s);
         case EB_LNFWD: return launch_nt<EB_LNFWD>(p, s);
@@ -519,12 +514,6 @@ bool gemm_nt_bf16_ln_epi_ok(int64_t M, int N, int K, int conv3, int gC) {
     GemmNTB q{};
     q.M = M; q.N = N; q.K = K; q.conv3 = conv3; q.gC = gC; q.nb = 1;
     return use256 && gemm_nt_bf16_256_ok(q, EB_LNFWD, use256 == 2 ? 1 : 192);
-}
-
-int gemm_nt_bf16_tiles_n(const GemmNTB& p, int epi) {
-    const bool gate = epi == EB_BIASGATE;
-    const int ncols = gate ? p.N / 2 : p.N;
-    return ncols <= (gate ? 32 : 64) ? cdiv(ncols, gate ? 32 : 64) : cdiv(ncols, gate ? 64 : 128);
 }
 
 int gemm_tn_bf16_tiles_k(int N, int K) {

@@ -321,7 +321,7 @@ __global__ __launch_bounds__(512) void gemm_nt_bf16_256_kernel(const GemmNTB pin
             }
             __syncthreads();
             epilogue8<EK, 128, 128, 512>(p, Cs, m0 + a * 128, n0, tid);
-            if constexpr (EK == EB_DOTCOL || EK == EB_LNBWD2 || EK == EB_LNBWDM) __syncthreads();   // (their column sums reuse the buffer)
+            if constexpr (EK == EB_DOTCOL || EK == EB_LNBWDM) __syncthreads();   // (their column sums reuse the buffer)
         }
     } else if constexpr (EK == EB_LNFWD || EK == EB_LNBWDM) {
         // a LayerNorm epilogue needs whole rows: the tile is parked as two [128][256] halves (N == 256: one column tile per row block)
@@ -381,7 +381,7 @@ __global__ __launch_bounds__(512) void gemm_nt_bf16_256_kernel(const GemmNTB pin
             }
             __syncthreads();
             epilogue8<EK, 128, 128, 512>(p, Cs, m0 + a * 128, n0 + b * 128, tid);
-            if constexpr (EK == EB_DOTCOL || EK == EB_LNBWD2) __syncthreads();   // (their column sums reuse the buffer)
+            if constexpr (EK == EB_DOTCOL) __syncthreads();   // (their column sums reuse the buffer)
         }
     }
 }
@@ -391,7 +391,7 @@ __global__ __launch_bounds__(512) void gemm_nt_bf16_256_kernel(const GemmNTB pin
 // Eligibility of a launch for the 256 x 256 kernel: plain operands, full 256-column tiles (128 per gate half), k-tiles in pairs, and
 // enough tiles to fill most of the 256 CUs (one block per CU).
 bool gemm_nt_bf16_256_ok(const GemmNTB& p, int epi, int min_tiles) {
-    if (p.gather2 || epi == EB_SCATTER || epi == EB_SCATTER_ADD || epi == EB_LNBWD2) return false;
+    if (p.gather2 || epi == EB_SCATTER || epi == EB_SCATTER_ADD) return false;
     const bool lnepi = epi == EB_LNFWD || epi == EB_LNBWDM;
     if (lnepi && p.N != 256) return false;
     if (p.conv3 && ((epi != EB_PLAIN && !lnepi) || p.gC % 64 != 0 || p.K != 9 * p.gC || p.K / 64 >= 2048 || (p.nb > 1))) return false;

@@ -54,8 +54,7 @@ __device__ __forceinline__ void epilogue8(const GemmNTB& p, float* __restrict__ 
     const rsrc_t rsC = make_rsrc(p.C + cbase);
     rsrc_t rsR = rsC, rsX = rsC;
     if constexpr (EK == EB_SCATTER_ADD) rsR = make_rsrc(p.res + cbase);
-    if constexpr (EK == EB_RESID || EK == EB_DOTCOL || EK == EB_LNBWD2 || EK == EB_MUL) rsR = make_rsrc(p.res + m0 * (int64_t)ldres);
-    if constexpr (EK == EB_LNBWD2) rsX = make_rsrc((p.aux ? p.aux : p.res) + m0 * (int64_t)ldres);
+    if constexpr (EK == EB_RESID || EK == EB_DOTCOL || EK == EB_MUL) rsR = make_rsrc(p.res + m0 * (int64_t)ldres);
     rsrc_t rsY = rsC;   // EB_LNFWD: y2 (the LayerNorm output);  EB_LNBWDM: y2 (the masked gradient, optional) -- rows as C's
     if constexpr (EK == EB_LNFWD) {
         rsR = make_rsrc(p.res + m0 * (int64_t)p.ldc);
@@ -69,8 +68,8 @@ __device__ __forceinline__ void epilogue8(const GemmNTB& p, float* __restrict__ 
     f8 lnb8 = f8_zero();
     if constexpr (EK == EB_SGBWD) rsX = make_rsrc(p.aux + m0 * (2 * (int64_t)p.N));
     if constexpr (GATE) rsX = make_rsrc(p.gate + m0 * (int64_t)Ch);
-    f8 dot = f8_zero(), dot2 = f8_zero(), lnw8 = f8_zero(), u_lo = f8_zero(), u_hi = f8_zero(), c_lo = f8_zero(), c_hi = f8_zero();
-    if constexpr (EK == EB_LNBWD2 || EK == EB_LNFWD || EK == EB_LNBWDM) {
+    f8 dot = f8_zero(), dot2 = f8_zero(), lnw8 = f8_zero();
+    if constexpr (EK == EB_LNFWD || EK == EB_LNBWDM) {
         if (nok) lnw8 = f8_ld(p.lnw + n);
     }
     if constexpr (EK == EB_LNFWD) {
@@ -78,14 +77,6 @@ __device__ __forceinline__ void epilogue8(const GemmNTB& p, float* __restrict__ 
     }
     if constexpr (EK == EB_LNBWDM) {
         if (nok && p.relu && !p.ymask) lnb8 = f8_ld(p.lnb + n);
-    }
-    if constexpr (EK == EB_SGBWD) {
-        if (p.rowpart && nok) {
-            u_lo = f8_ld(p.uvec + n);
-            u_hi = f8_ld(p.uvec + p.N + n);
-            c_lo = f8_ld(p.cvec + n);
-            c_hi = f8_ld(p.cvec + p.N + n);
-        }
     }
     // two 16-byte loads per row: prefetch in two halves (registers); the masked LayerNorm backward keeps two rows in flight per thread
     constexpr int HALF = (EK == EB_SGBWD) ? 2 : (EK == EB_LNBWDM && IT >= 4) ? IT / 2 : 1;
@@ -99,12 +90,9 @@ __device__ __forceinline__ void epilogue8(const GemmNTB& p, float* __restrict__ 
             const bool ok = (m0 + rl < p.M) && nok;
             pre1[it] = f8_zero();
             pre2[it] = f8_zero();
-            if constexpr (EK == EB_RESID || EK == EB_DOTCOL || EK == EB_LNBWD2 || EK == EB_MUL)
+            if constexpr (EK == EB_RESID || EK == EB_DOTCOL || EK == EB_MUL)
                 pre1[it] = bbuf_ld8(rsR, ok ? ((uint32_t)rl * (uint32_t)ldres + (uint32_t)n) * 2u : ROW_SENT);
             if constexpr (EK == EB_SCATTER_ADD) pre1[it] = bbuf_ld8(rsR, ok ? (uint32_t)((fine_elem(p, m0 + rl) - cbase) * 2) + coladd : ROW_SENT);
-            if constexpr (EK == EB_LNBWD2) {
-                if (p.aux) pre2[it] = bbuf_ld8(rsX, ok ? ((uint32_t)rl * (uint32_t)ldres + (uint32_t)n) * 2u : ROW_SENT);
-            }
             if constexpr (EK == EB_SGBWD) {
                 const uint32_t xo = ok ? ((uint32_t)rl * (uint32_t)p.N * 2u + (uint32_t)n) * 2u : ROW_SENT;
                 pre1[it] = bbuf_ld8(rsX, xo);
@@ -153,22 +141,6 @@ __device__ __forceinline__ void epilogue8(const GemmNTB& p, float* __restrict__ 
                 const f8 d1 = f8_mul(v, pre2[it]), d2 = f8_mul(v, pre1[it]);
                 bbuf_st8(rsC, o, d1);
                 bbuf_st8(rsC, o + 2u * (uint32_t)p.N, d2);
-                if (p.rowpart) {
-                    const int64_t m = m0 + rl;
-                    f8 z1, z2;
-                    z1.lo = make_float4(pre1[it].lo.x - c_lo.lo.x, pre1[it].lo.y - c_lo.lo.y, pre1[it].lo.z - c_lo.lo.z, pre1[it].lo.w - c_lo.lo.w);
-                    z1.hi = make_float4(pre1[it].hi.x - c_lo.hi.x, pre1[it].hi.y - c_lo.hi.y, pre1[it].hi.z - c_lo.hi.z, pre1[it].hi.w - c_lo.hi.w);
-                    z2.lo = make_float4(pre2[it].lo.x - c_hi.lo.x, pre2[it].lo.y - c_hi.lo.y, pre2[it].lo.z - c_hi.lo.z, pre2[it].lo.w - c_hi.lo.w);
-                    z2.hi = make_float4(pre2[it].hi.x - c_hi.hi.x, pre2[it].hi.y - c_hi.hi.y, pre2[it].hi.z - c_hi.hi.z, pre2[it].hi.w - c_hi.hi.w);
-                    float a1 = nok ? f8_sum(f8_mul(d1, u_lo)) + f8_sum(f8_mul(d2, u_hi)) : 0.f;
-                    float a2 = nok ? f8_sum(f8_mul(d1, z1)) + f8_sum(f8_mul(d2, z2)) : 0.f;
-                    a1 = group_sum(a1, Q);
-                    a2 = group_sum(a2, Q);
-                    if (q == 0 && m < p.M) {
-                        const int np = (p.N + BN - 1) / BN;
-                        *reinterpret_cast<float2*>(p.rowpart + (m * np + n0 / BN) * 2) = make_float2(a1, a2);
-                    }
-                }
             } else if constexpr (EK == EB_LNFWD) {
                 // (the expressions, the lane -> channel map and the reduction tree of ln_fwd_bf16_kernel: the two paths agree bit for bit)
                 const int64_t m = m0 + rl;
@@ -228,38 +200,13 @@ __device__ __forceinline__ void epilogue8(const GemmNTB& p, float* __restrict__ 
                 bbuf_st8(rsC, o, d);
                 dot = f8_fma(g, xh, dot);   // (rows past M: g = 0, xhat = 0)
                 dot2 = f8_add(dot2, g);
-            } else if constexpr (EK == EB_LNBWD2) {
-                const int64_t m = m0 + rl;
-                const bool rok = m < p.M;
-                const float mean = rok ? p.mu[m] : 0.f, rs = rok ? p.rstd[m] : 0.f;
-                float a1 = 0.f, a2 = 0.f;
-                if (rok && q < p.rowparts) {
-                    const float2 pr = *reinterpret_cast<const float2*>(p.rowpart + (m * p.rowparts + q) * 2);
-                    a1 = pr.x;
-                    a2 = pr.y;
-                }
-                const float invN = 1.0f / (float)p.N;
-                const float s1 = group_sum(a1, Q) * invN, s2 = group_sum(a2, Q) * invN;
-                f8 xh, d;
-                xh.lo = make_float4((pre1[it].lo.x - mean) * rs, (pre1[it].lo.y - mean) * rs, (pre1[it].lo.z - mean) * rs, (pre1[it].lo.w - mean) * rs);
-                xh.hi = make_float4((pre1[it].hi.x - mean) * rs, (pre1[it].hi.y - mean) * rs, (pre1[it].hi.z - mean) * rs, (pre1[it].hi.w - mean) * rs);
-                const f8 gw = f8_mul(v, lnw8);
-                d.lo = make_float4(rs * (gw.lo.x - xh.lo.x * s2 - s1), rs * (gw.lo.y - xh.lo.y * s2 - s1), rs * (gw.lo.z - xh.lo.z * s2 - s1),
-                                   rs * (gw.lo.w - xh.lo.w * s2 - s1));
-                d.hi = make_float4(rs * (gw.hi.x - xh.hi.x * s2 - s1), rs * (gw.hi.y - xh.hi.y * s2 - s1), rs * (gw.hi.z - xh.hi.z * s2 - s1),
-                                   rs * (gw.hi.w - xh.hi.w * s2 - s1));
-                bbuf_st8(rsC, o, f8_add(d, pre2[it]));
-                if (rok && nok) {
-                    dot = f8_fma(v, xh, dot);
-                    dot2 = f8_add(dot2, v);
-                }
             } else {   // EB_DOTCOL
                 bbuf_st8(rsC, o, v);
                 dot = f8_fma(v, pre1[it], dot);   // rows past M loaded 0
             }
         }
     }
-    if constexpr (EK == EB_LNBWD2 || EK == EB_LNBWDM) {
+    if constexpr (EK == EB_LNBWDM) {
         // the two column-sum planes (-> LayerNorm weight / bias gradients) over the tile's rows, as for EB_DOTCOL
 #pragma unroll
         for (int pl = 0; pl < 2; ++pl) {

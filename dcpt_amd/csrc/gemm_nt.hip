@@ -233,12 +233,11 @@ int nt_pick_bn(const GemmNT& p, int epi) {
     const bool gate = (epi == E_BIASGATE);
     const unsigned nbatch = (unsigned)((p.nb1 > 0 ? p.nb1 : 1) * (p.nb2 > 0 ? p.nb2 : 1));
     if (epi == E_LNBWD || epi == E_RESIDLN) return p.N <= 64 ? 64 : 128;
-    static const int smallk = dcpt_tuning("DCPT_NT_SMALLK", 0);
     static const int use96 = dcpt_tuning("DCPT_NT_96", 1);
     static const int use64_below = dcpt_tuning("DCPT_NT_64_BELOW", 2100);
     if (!gate && use96 && p.N > 64 && cdiv(p.N, 96) * 96 < cdiv(p.N, 128) * 128 && cdiv64(p.M, 128) * cdiv(p.N, 96) * nbatch > 256) return 96;
     const int64_t tiles128 = cdiv64(p.M, 128) * (gate ? cdiv(p.N / 2, 64) : cdiv(p.N, 128));
-    if (p.N <= 64 || tiles128 * nbatch < use64_below || p.K <= smallk) return 64;
+    if (p.N <= 64 || tiles128 * nbatch < use64_below) return 64;
     return 128;
 }
 
@@ -261,13 +260,6 @@ int launch_cfg(const GemmNT& p, hipStream_t s) {
 }
 
 }  // namespace
-
-int gemm_nt_tiles_n(const GemmNT& pin, int aload, int epi) {
-    (void)aload;
-    GemmNT p = pin;
-    const int bn = nt_pick_bn(p, epi);
-    return epi == E_BIASGATE ? cdiv(p.N / 2, bn / 2) : cdiv(p.N, bn);
-}
 
 int launch_gemm_nt(const GemmNT& pin, int aload, int epi, hipStream_t s) {
     GemmNT p = pin;
@@ -305,11 +297,7 @@ int launch_gemm_nt(const GemmNT& pin, int aload, int epi, hipStream_t s) {
     const double mn = (double)p.M * p.N, mk = (double)p.M * p.K;
     double bytes = mk * (aload == A_SG ? 2 : 1) + mn * (epi == E_SGBWD ? 4 : epi == E_BIASGATE ? 1.5 : 1) + (double)p.N * p.K;
     if (epi == E_RESID || epi == E_SCATTER_ADD || epi == E_DOTCOL) bytes += mn;
-    if (epi == E_LNBWD || epi == E_LNBWD2) bytes += 2 * mn;
-    if (epi == E_LNBWD2)
-        DCPT_CHECK_ARG(p.colpart && p.res && p.mu && p.rstd && p.lnw && p.rowpart && p.rowparts >= 1 && p.rowparts <= 16 && p.N % 4 == 0 &&
-                           p.nb1 * p.nb2 == 1, "gemm_nt: LayerNorm-backward (row sums supplied) epilogue needs res / mu / rstd / lnw / colpart / rowpart, <= 16 row partials");
-    if (epi == E_SGBWD && p.rowpart) DCPT_CHECK_ARG(p.uvec && p.cvec, "gemm_nt: SimpleGate-backward row partials need uvec / cvec");
+    if (epi == E_LNBWD) bytes += 2 * mn;
     if (epi == E_RESIDLN) bytes += 2 * mn;
     const double nbat = (double)((p.nb1 > 0 ? p.nb1 : 1) * (p.nb2 > 0 ? p.nb2 : 1));
     ProfScope prof(s, PROF_NT + aload * 16 + (epi == E_LRELU ? (int)E_RELU : epi),   // (16 epilogue ids per loader: LeakyReLU shares ReLU's)
@@ -343,7 +331,6 @@ int launch_gemm_nt(const GemmNT& pin, int aload, int epi, hipStream_t s) {
     CASE(A_PLAIN, E_BIASGATE)
     CASE(A_PLAIN, E_DOTCOL)
     CASE(A_PLAIN, E_LNBWD)
-    CASE(A_PLAIN, E_LNBWD2)
     CASE(A_SCALE, E_RESIDLN)
 #undef CASE
     dcpt_set_error("gemm_nt: unsupported loader/epilogue combination %d/%d", aload, epi);

@@ -87,9 +87,9 @@ __device__ __forceinline__ void epilogue_rows(const GemmNT& p, const float* __re
     }
     const rsrc_t rsC = make_rsrc(p.C + cbase);
     rsrc_t rsR = rsC, rsX = rsC;
-    if constexpr (EK == E_RESID || EK == E_ADDSCALED || EK == E_MUL || EK == E_DOTCOL || EK == E_LNBWD || EK == E_RESIDLN || EK == E_LNBWD2) rsR = make_rsrc(p.res + m0 * (int64_t)ldres);
+    if constexpr (EK == E_RESID || EK == E_ADDSCALED || EK == E_MUL || EK == E_DOTCOL || EK == E_LNBWD || EK == E_RESIDLN) rsR = make_rsrc(p.res + m0 * (int64_t)ldres);
     if constexpr (EK == E_RESIDLN) rsX = make_rsrc(p.ln_out + m0 * (int64_t)p.ldc);
-    if constexpr (EK == E_LNBWD || EK == E_LNBWD2) rsX = make_rsrc((p.aux ? p.aux : p.res) + m0 * (int64_t)ldres);
+    if constexpr (EK == E_LNBWD) rsX = make_rsrc((p.aux ? p.aux : p.res) + m0 * (int64_t)ldres);
     if constexpr (EK == E_SCATTER_ADD) rsR = make_rsrc(p.res + cbase);
     if constexpr (EK == E_RELU || EK == E_LRELU) {
         if (p.res) rsR = make_rsrc(p.res + m0 * (int64_t)ldres);
@@ -100,18 +100,8 @@ __device__ __forceinline__ void epilogue_rows(const GemmNT& p, const float* __re
     float4 dot = f4_zero();   // E_DOTCOL / E_LNBWD: this thread's part of the column sums
     float4 dot2 = f4_zero();  // E_LNBWD: second plane (sum of g)
     float4 lnw4 = f4_zero(), lnb4 = f4_zero();
-    if constexpr (EK == E_LNBWD || EK == E_RESIDLN || EK == E_LNBWD2) {
+    if constexpr (EK == E_LNBWD || EK == E_RESIDLN) {
         if (nok) lnw4 = ldg4(p.lnw + n);
-    }
-    // E_SGBWD with row partials: this thread's entries of u / cvec for both halves of the gate
-    float4 u_lo = f4_zero(), u_hi = f4_zero(), c_lo = f4_zero(), c_hi = f4_zero();
-    if constexpr (EK == E_SGBWD) {
-        if (p.rowpart && nok) {
-            u_lo = ldg4(p.uvec + n);
-            u_hi = ldg4(p.uvec + p.N + n);
-            c_lo = ldg4(p.cvec + n);
-            c_hi = ldg4(p.cvec + p.N + n);
-        }
     }
     if constexpr (EK == E_RESIDLN) {
         if (nok && p.lnb) lnb4 = ldg4(p.lnb + n);
@@ -132,12 +122,12 @@ __device__ __forceinline__ void epilogue_rows(const GemmNT& p, const float* __re
                 if constexpr (EK == E_SCATTER_ADD) pre1[it] = buf_ld4(rsR, addr[it]);
             } else {
                 addr[it] = ok ? (uint32_t)rl * (uint32_t)p.ldc * 4u + coladd : ROW_SENT;
-                if constexpr (EK == E_RESID || EK == E_ADDSCALED || EK == E_MUL || EK == E_DOTCOL || EK == E_LNBWD || EK == E_RESIDLN || EK == E_LNBWD2)
+                if constexpr (EK == E_RESID || EK == E_ADDSCALED || EK == E_MUL || EK == E_DOTCOL || EK == E_LNBWD || EK == E_RESIDLN)
                     pre1[it] = buf_ld4(rsR, ok ? (uint32_t)rl * (uint32_t)ldres * 4u + coladd : ROW_SENT);
                 if constexpr (EK == E_RELU || EK == E_LRELU) {
                     if (p.res) pre1[it] = buf_ld4(rsR, ok ? (uint32_t)rl * (uint32_t)ldres * 4u + coladd : ROW_SENT);
                 }
-                if constexpr (EK == E_LNBWD || EK == E_LNBWD2) {
+                if constexpr (EK == E_LNBWD) {
                     if (p.aux) pre2[it] = buf_ld4(rsX, ok ? (uint32_t)rl * (uint32_t)ldres * 4u + coladd : ROW_SENT);
                 }
                 if constexpr (EK == E_SGBWD) {
@@ -187,32 +177,6 @@ __device__ __forceinline__ void epilogue_rows(const GemmNT& p, const float* __re
                     dot = f4_fma(v, xh, dot);
                     dot2 = f4_add(dot2, v);
                 }
-            } else if constexpr (EK == E_LNBWD2) {
-                // the row sums come from the producer of dZ: lane q of the row's lane group fetches partial q, the group adds them
-                const int64_t m = m0 + rl;
-                const bool rok = m < p.M;
-                const float mean = rok ? p.mu[m] : 0.f, rs = rok ? p.rstd[m] : 0.f;
-                float a1 = 0.f, a2 = 0.f;
-                if (rok && q < p.rowparts) {
-                    const float2 pr = *reinterpret_cast<const float2*>(p.rowpart + (m * p.rowparts + q) * 2);
-                    a1 = pr.x;
-                    a2 = pr.y;
-                }
-                const float invN = 1.0f / (float)p.N;
-                const float s1 = group_sum(a1, QP) * invN, s2 = group_sum(a2, QP) * invN;
-                const float4 xh = make_float4((pre1[it].x - mean) * rs, (pre1[it].y - mean) * rs, (pre1[it].z - mean) * rs,
-                                              (pre1[it].w - mean) * rs);
-                const float4 gw = f4_mul(v, lnw4);
-                float4 d;
-                d.x = rs * (gw.x - xh.x * s2 - s1);
-                d.y = rs * (gw.y - xh.y * s2 - s1);
-                d.z = rs * (gw.z - xh.z * s2 - s1);
-                d.w = rs * (gw.w - xh.w * s2 - s1);
-                buf_st4(rsC, addr[it], f4_add(d, pre2[it]));
-                if (rok && nok) {
-                    dot = f4_fma(v, xh, dot);
-                    dot2 = f4_add(dot2, v);
-                }
             } else if constexpr (EK == E_DOTCOL) {
                 buf_st4(rsC, addr[it], v);
                 dot = f4_fma(v, pre1[it], dot);   // rows past M loaded 0
@@ -240,25 +204,12 @@ __device__ __forceinline__ void epilogue_rows(const GemmNT& p, const float* __re
                 const float4 d1 = f4_mul(v, pre2[it]), d2 = f4_mul(v, pre1[it]);   // gradients of the first / second half of the gate input
                 buf_st4(rsC, addr[it], d1);
                 buf_st4(rsC, addr[it] + 4u * (uint32_t)p.N, d2);
-                if (p.rowpart) {   // row partials of  dZ . u  and  dZ . (Z - cvec)  for the LayerNorm backward downstream (E_LNBWD2)
-                    const int64_t m = m0 + rl;
-                    const float4 z1 = make_float4(pre1[it].x - c_lo.x, pre1[it].y - c_lo.y, pre1[it].z - c_lo.z, pre1[it].w - c_lo.w);
-                    const float4 z2 = make_float4(pre2[it].x - c_hi.x, pre2[it].y - c_hi.y, pre2[it].z - c_hi.z, pre2[it].w - c_hi.w);
-                    float a1 = nok ? f4_sum(f4_mul(d1, u_lo)) + f4_sum(f4_mul(d2, u_hi)) : 0.f;
-                    float a2 = nok ? f4_sum(f4_mul(d1, z1)) + f4_sum(f4_mul(d2, z2)) : 0.f;
-                    a1 = group_sum(a1, QP);
-                    a2 = group_sum(a2, QP);
-                    if (q == 0 && m < p.M) {
-                        const int np = (p.N + BN - 1) / BN;
-                        *reinterpret_cast<float2*>(p.rowpart + (m * np + n0 / BN) * 2) = make_float2(a1, a2);
-                    }
-                }
             } else {  // E_SCATTER_ADD
                 buf_st4(rsC, addr[it], f4_add(v, pre1[it]));
             }
         }
     }
-    if constexpr (EK == E_LNBWD || EK == E_LNBWD2) {
+    if constexpr (EK == E_LNBWD) {
         // the two column-sum planes over the tile's rows, as for E_DOTCOL
         float* sm = const_cast<float*>(Cs);
         for (int pl = 0; pl < 2; ++pl) {

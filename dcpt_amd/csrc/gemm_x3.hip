@@ -882,7 +882,6 @@ bool gemm_nt_x3_ok(const GemmNT& p, int aload, int epi) {
     if (!(epi == E_PLAIN || epi == E_BIAS || epi == E_RESID || epi == E_SGBWD || epi == E_BIASGATE || epi == E_DOTCOL || epi == E_ADDSCALED ||
           epi == E_MUL))
         return false;
-    if (epi == E_SGBWD && p.rowpart) return false;
     if (p.K % 64 != 0 || p.N % 256 != 0 || p.lda % 4 != 0) return false;
     int64_t nb = (int64_t)(p.nb1 > 0 ? p.nb1 : 1) * (p.nb2 > 0 ? p.nb2 : 1);
     int64_t M = p.M;

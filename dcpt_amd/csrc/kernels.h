@@ -34,27 +34,6 @@ int launch_dw_pack_weights(const float* w2, float* w2p, int C2, hipStream_t s); 
 // t2 = SG(dw3x3(t1) + b2); pool_part[B][NBLK][C] partial sums of t2
 int launch_dw_fwd(const float* t1, const float* w2p, const float* b2, float* t2, float* pool_part, const DwGeom& g,
                   hipStream_t s);
-// SimpleGate-backward + transposed depthwise + tap-gradient partials in one pass (da = gate-backward(dts * s + dpool) is never
-// written): dt1 and wpart[B*NBLKf][10][2C], NBLKf = dw_num_blocks_per_image_fused
-int dw_num_blocks_per_image_fused(const DwGeom& g);
-// optional rowpart[pixel][dw_fused_row_chunks][2]: per-pixel partials of dt1 . uvec and dt1 . (t1 - cvec) (gemm.h, E_LNBWD2)
-int dw_fused_row_chunks(const DwGeom& g);
-int launch_dw_bwd_fused(const float* dts, const float* t1, const float* w2p, const float* b2, const float* simg, const float* dpool,
-                        float* dt1, float* wpart, const DwGeom& g, hipStream_t s, float* rowpart = nullptr, const float* uvec = nullptr,
-                        const float* cvec = nullptr);
-// LayerNorm-through-conv vectors of the row-sum identities (gemm.h, E_LNBWD2), for a 1x1 conv W [N2][C] (+ bias bz) applied to
-// LN(x) * w + b:   u[j] = sum_c W[j][c] w[c],   cvec[j] = bz[j] + sum_c W[j][c] b[c];   grid.y = job (two LayerNorms per block)
-struct LnVecJobs {
-    const float* W[2];
-    const float* bz[2];
-    const float* lnw[2];
-    const float* lnb[2];
-    float* u[2];
-    float* cvec[2];
-    int N2, C, n;
-    int round_bf16;   // the bf16 path: W enters as its bf16-rounded GEMM operand copy
-};
-int launch_lnvec(const LnVecJobs& jobs, hipStream_t s);
 // dw2[ch*9+tap] and db2[ch] from wpart[R][10][C2]
 int launch_dw_wgrad_reduce(const float* wpart, int R, int C2, float* dw2, float* db2, hipStream_t s);
 
@@ -62,7 +41,8 @@ int launch_dw_wgrad_reduce(const float* wpart, int R, int C2, float* dw2, float*
 bool dw_ring_usable(const DwGeom& g, int elem_bytes);
 int dw_ring_num_blocks_per_image(const DwGeom& g, int elem_bytes);
 int launch_dw_ring_fwd_f32(const float* t1, const float* w2p, const float* b2, float* t2, float* pool_part, const DwGeom& g, hipStream_t s);
-// launch_dw_bwd_fused on the ring (no row partials); wpart[B][dw_ring_bwd_num_blocks_per_image][10][2C]
+// SimpleGate-backward + transposed depthwise + tap-gradient partials in one pass (da = gate-backward(dts * s + dpool) is never
+// written): dt1 and wpart[B][dw_ring_bwd_num_blocks_per_image][10][2C]
 bool dw_ring_bwd_usable(const DwGeom& g, int elem_bytes);
 int dw_ring_bwd_num_blocks_per_image(const DwGeom& g);
 int launch_dw_ring_bwd_fused_f32(const float* dts, const float* t1, const float* w2p, const float* b2, const float* simg, const float* dpool,

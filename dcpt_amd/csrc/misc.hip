@@ -443,41 +443,6 @@ __global__ __launch_bounds__(256) void wpack_multi_kernel(const WpackJobs jobs) 
     }
 }
 
-// one wave per output j: u[j] = W[j][:] . lnw,  cvec[j] = bz[j] + W[j][:] . lnb
-__global__ __launch_bounds__(256) void lnvec_kernel(const LnVecJobs jobs) {
-    const int y = blockIdx.y, lane = threadIdx.x & 63;
-    const int j = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (j >= jobs.N2) return;
-    const float* __restrict__ w = jobs.W[y] + (int64_t)j * jobs.C;
-    float a = 0.f, b = 0.f;
-    for (int c = 4 * lane; c < jobs.C; c += 256) {
-        float4 wv = ldg4(w + c);
-        if (jobs.round_bf16) {   // round-to-nearest-even to bf16, as the operand pack does
-            auto r = [](float x) {
-                uint32_t u = __builtin_bit_cast(uint32_t, x);
-                u += 0x7fffu + ((u >> 16) & 1u);
-                return __builtin_bit_cast(float, u & 0xffff0000u);
-            };
-            wv = make_float4(r(wv.x), r(wv.y), r(wv.z), r(wv.w));
-        }
-        a += f4_sum(f4_mul(wv, ldg4(jobs.lnw[y] + c)));
-        b += f4_sum(f4_mul(wv, ldg4(jobs.lnb[y] + c)));
-    }
-    a = wave_sum(a);
-    b = wave_sum(b);
-    if (lane == 0) {
-        jobs.u[y][j] = a;
-        jobs.cvec[y][j] = b + (jobs.bz[y] ? jobs.bz[y][j] : 0.f);
-    }
-}
-
-int launch_lnvec(const LnVecJobs& jobs, hipStream_t s) {
-    DCPT_CHECK_ARG(jobs.n >= 1 && jobs.n <= 2 && jobs.C % 4 == 0, "lnvec: bad job");
-    lnvec_kernel<<<dim3(cdiv(jobs.N2, 4), jobs.n), dim3(256), 0, s>>>(jobs);
-    DCPT_CHECK_LAUNCH("lnvec");
-    return DCPT_OK;
-}
-
 int launch_wpack_multi(const WpackJobs& jobs, hipStream_t s) {
     DCPT_CHECK_ARG(jobs.n >= 1 && jobs.n <= WPACK_MAX_JOBS, "wpack_multi: %d jobs", jobs.n);
     int64_t mx = 0;

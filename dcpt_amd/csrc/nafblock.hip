@@ -32,7 +32,7 @@ struct FwdWs {
 size_t fwd_ws_layout(int B, int H, int W, int C, void* base, size_t bytes, FwdWs* out) {
     WsAlloc a(base, base ? bytes : (size_t)-1);
     DwGeom g{B, H, W, C};
-    const int nblk = dw_ring_usable(g, 4) ? dw_ring_num_blocks_per_image(g, 4) : dw_num_blocks_per_image(g);
+    const int nblk = dw_ring_num_blocks_per_image(g, 4);
     float* w2p = a.get<float>((size_t)9 * 2 * C);
     float* pp = a.get<float>((size_t)B * nblk * C);
     if (out) {
@@ -54,9 +54,6 @@ struct BwdWs {
     float *ds_part, *ds, *dpool;
     float* wpart;
     int ln_nblk, nblk_b;
-    // LayerNorm backward with supplied row sums (C > 128, gemm.h E_LNBWD2): u / cvec of conv4 o LN2 and conv1 o LN1, row partials
-    float *u4, *c4, *u1, *c1, *rowpart;
-    int rp_sg, rp_dw;   // partials per row written by the SimpleGate-backward GEMM / the fused depthwise backward
     float* ffn_part;    // LayerNorm2 column partials of the fused narrowest-level backward (ffn_f32.hip): [waves][2][C]
 };
 
@@ -102,7 +99,7 @@ size_t bwd_ws_layout(int B, int H, int W, int C, void* base, size_t bytes, BwdWs
     w.ln_nblk = ln_bwd_num_blocks(M, C);
     {
         // LayerNorm column partials: [ln_nblk][3][C] from ln_bwd, or [M / 128 tiles][2][C] from the E_LNBWD GEMM epilogue
-        const size_t a1 = (size_t)w.ln_nblk * 3 * C, a2 = (size_t)cdiv64(M, 128) * 2 * C;   // E_LNBWD / E_LNBWD2 tiles
+        const size_t a1 = (size_t)w.ln_nblk * 3 * C, a2 = (size_t)cdiv64(M, 128) * 2 * C;   // E_LNBWD tiles
         w.lnpart = a.get<float>(a1 > a2 ? a1 : a2);
         w.lnpart2 = a.get<float>(a1 > a2 ? a1 : a2);
     }
@@ -112,33 +109,11 @@ size_t bwd_ws_layout(int B, int H, int W, int C, void* base, size_t bytes, BwdWs
     }
     w.ds = a.get<float>((size_t)B * C);
     w.dpool = a.get<float>((size_t)B * C);
-    {   // tap-gradient partials of the fused depthwise backward: the ring kernel's or the register kernel's block count
-        const int n1 = dw_num_blocks_per_image_fused(g), n2 = dw_ring_bwd_usable(g, 4) ? dw_ring_bwd_num_blocks_per_image(g) : 0;
-        w.nblk_b = n1 > n2 ? n1 : n2;
-    }
+    w.nblk_b = dw_ring_bwd_num_blocks_per_image(g);   // tap-gradient partials of the fused depthwise backward
     w.wpart = a.get<float>((size_t)B * w.nblk_b * 10 * 2 * C);
-    w.u4 = a.get<float>((size_t)2 * C);
-    w.c4 = a.get<float>((size_t)2 * C);
-    w.u1 = a.get<float>((size_t)2 * C);
-    w.c1 = a.get<float>((size_t)2 * C);
-    w.rp_sg = cdiv(C, 64);   // upper bound over the tile widths the SimpleGate-backward launch may pick (64 / 96 / 128)
-    w.rp_dw = dw_fused_row_chunks(g);
-    w.rowpart = a.get<float>((size_t)M * (w.rp_sg > w.rp_dw ? w.rp_sg : w.rp_dw) * 2);
     w.ffn_part = ffn_fused_f32(C) ? a.get<float>((size_t)ffn_bwd_f32_waves(M) * 2 * C) : nullptr;
     if (out) *out = w;
     return a.off;
-}
-
-// Wide levels (C > 128): the LayerNorm backward's two row sums are linear in the gradient that enters the conv behind the
-// LayerNorm (dv for conv4 o LN2, dt1 for conv1 o LN1) -- gemm.h, E_LNBWD2 -- so the kernels that PRODUCE those gradients leave
-// them as per-row partials and the dgrad GEMM applies the LayerNorm backward elementwise in its epilogue: no separate
-// bandwidth kernel, the LayerNorm's incoming gradient is never written.
-// OFF by default (DCPT_LN_ROWSUMS=1 enables it): exact and 4 tensor passes lighter, but measured SLOWER in fp32 -- the step goes
-// from 120.7 to 124.4 ms, a level-3 block's backward from 1.95 to 2.09 ms: the wide levels' GEMMs are MFMA-bound, their
-// epilogues are exposed time, and the separate LayerNorm kernel was overlapping the side stream's weight-gradient GEMMs.
-bool ln_rowsums(int C, int rp_sg, int rp_dw) {
-    static const int on = dcpt_tuning("DCPT_LN_ROWSUMS", 0);
-    return on && C > 128 && rp_sg <= 16 && rp_dw <= 16;
 }
 
 // Narrow levels (C <= 128: one GEMM tile spans all channels): LayerNorm backward runs inside the epilogue of the dgrad GEMM
@@ -180,7 +155,7 @@ extern "C" int dcpt_nafblock_fwd(const dcpt_nafblock_params* p, const float* inp
                                  void* ws, size_t ws_bytes, int B, int H, int W, int C, dcpt_stream_t stream) {
     hipStream_t s = (hipStream_t)stream;
     DCPT_CHECK_ARG(p && inp && out && sv, "nafblock_fwd: null argument");
-    DCPT_CHECK_ARG(B > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0, "nafblock_fwd: bad shape B=%d H=%d W=%d C=%d (C %% 4 == 0)", B, H, W, C);
+    DCPT_CHECK_ARG(B > 0 && B <= 65535 && H > 0 && W > 0 && C > 0 && C % 4 == 0, "nafblock_fwd: bad shape B=%d H=%d W=%d C=%d (B <= 65535, C %% 4 == 0)", B, H, W, C);
     FwdWs w;
     const size_t need = fwd_ws_layout(B, H, W, C, ws, ws_bytes, &w);
     if (need > ws_bytes || ws == nullptr) {
@@ -213,8 +188,7 @@ extern "C" int dcpt_nafblock_fwd(const dcpt_nafblock_params* p, const float* inp
     // t2 = SG(dw(t1)+b2) and pooling partials
     DwGeom dg{B, H, W, C};
     DCPT_TRY(launch_dw_pack_weights(p->conv2_w, w.w2p, 2 * C, s));
-    if (dw_ring_usable(dg, 4)) DCPT_TRY(launch_dw_ring_fwd_f32(sv->t1, w.w2p, p->conv2_b, sv->t2, w.pool_part, dg, s));
-    else DCPT_TRY(launch_dw_fwd(sv->t1, w.w2p, p->conv2_b, sv->t2, w.pool_part, dg, s));
+    DCPT_TRY(launch_dw_ring_fwd_f32(sv->t1, w.w2p, p->conv2_b, sv->t2, w.pool_part, dg, s));
     DCPT_TRY(launch_sca_fwd(w.pool_part, w.nblk_pool, p->sca_w, p->sca_b, sv->pooled, sv->s, B, C, P, s));
     // y = inp + (conv3(t2*s)+b3)*beta
     g = GemmNT{};
@@ -254,7 +228,7 @@ extern "C" int dcpt_nafblock_bwd(const dcpt_nafblock_params* p, const dcpt_nafbl
     DCPT_CHECK_ARG(p && gr && inp && sv && dout && dinp, "nafblock_bwd: null argument");
     DCPT_CHECK_ARG(sv->v && sv->mu1 && sv->rstd1 && sv->mu2 && sv->rstd2 && (ffn_fused_f32(C) || (sv->xn1 && sv->xn2 && sv->g)),
                    "nafblock_bwd: saved tensors missing");
-    DCPT_CHECK_ARG(B > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0, "nafblock_bwd: bad shape B=%d H=%d W=%d C=%d", B, H, W, C);
+    DCPT_CHECK_ARG(B > 0 && B <= 65535 && H > 0 && W > 0 && C > 0 && C % 4 == 0, "nafblock_bwd: bad shape B=%d H=%d W=%d C=%d (B <= 65535, C %% 4 == 0)", B, H, W, C);
     BwdWs w;
     const size_t need = bwd_ws_layout(B, H, W, C, ws, ws_bytes, &w);
     if (need > ws_bytes || ws == nullptr) {
@@ -288,30 +262,17 @@ extern "C" int dcpt_nafblock_bwd(const dcpt_nafblock_params* p, const dcpt_nafbl
     DCPT_TRY(side_fork(sd, 0, s));      // dout / saved activations / packed weights are ready
 
     const bool lne = ln_in_epilogue(C);
-    const bool lrs = !lne && ln_rowsums(C, w.rp_sg, w.rp_dw);
-    if (lrs) {
-        LnVecJobs lj{};
-        lj.n = 2; lj.N2 = C2; lj.C = C;
-        lj.W[0] = p->conv4_w; lj.bz[0] = p->conv4_b; lj.lnw[0] = p->norm2_w; lj.lnb[0] = p->norm2_b; lj.u[0] = w.u4; lj.cvec[0] = w.c4;
-        lj.W[1] = p->conv1_w; lj.bz[1] = p->conv1_b; lj.lnw[1] = p->norm1_w; lj.lnb[1] = p->norm1_b; lj.u[1] = w.u1; lj.cvec[1] = w.c1;
-        DCPT_TRY(launch_lnvec(lj, s));
-    }
     GemmNT g{};
     GemmTN tp{};
     const bool ffn = ffn_fused_f32(C);   // narrowest level: B1 + B3 + B5 as one pass (ffn_f32.hip); the forward kept neither LN outputs nor the gate
-    int rp_b1 = 0;
     if (ffn) {
         FfnBwdF f{};
         f.dout = dout; f.v = sv->v; f.y = sv->y; f.wT5 = w.wT5; f.wT4 = w.wT4; f.lnw = p->norm2_w; f.dv = dv; f.dy = dy; f.lnpart = w.ffn_part;
         f.M = M; f.eps = 1e-6f;
         DCPT_TRY(launch_ffn_bwd_f32(f, C, s));
     } else {
-        // B1: dv = SG'(dout*gamma * W5; v)  (+ the row sums of LN2's backward, which are linear in dv)
+        // B1: dv = SG'(dout*gamma * W5; v)
         g.M = M; g.A = dout; g.lda = C; g.K = C; g.Bw = w.wT5; g.N = C; g.C = dv; g.ldc = C2; g.aux = sv->v;
-        if (lrs) {
-            g.rowpart = w.rowpart; g.uvec = w.u4; g.cvec = w.c4;
-            rp_b1 = gemm_nt_tiles_n(g, A_PLAIN, E_SGBWD);
-        }
         DCPT_TRY(launch_gemm_nt(g, A_PLAIN, E_SGBWD, s));
     }
     // B2: conv5 / gamma gradients
@@ -330,10 +291,6 @@ extern "C" int dcpt_nafblock_bwd(const dcpt_nafblock_params* p, const dcpt_nafbl
     } else if (lne) {   // B3 + B5 in one launch: dy = dout + LN2-backward(dv * W4^T)
         g.C = dy; g.res = sv->y; g.ldres = C; g.aux = dout; g.mu = sv->mu2; g.rstd = sv->rstd2; g.lnw = p->norm2_w; g.colpart = w.lnpart;
         DCPT_TRY(launch_gemm_nt(g, A_PLAIN, E_LNBWD, s));
-    } else if (lrs) {   // the same in one launch at any width: the row sums were left by B1
-        g.C = dy; g.res = sv->y; g.ldres = C; g.aux = dout; g.mu = sv->mu2; g.rstd = sv->rstd2; g.lnw = p->norm2_w; g.colpart = w.lnpart;
-        g.rowpart = w.rowpart; g.rowparts = rp_b1;
-        DCPT_TRY(launch_gemm_nt(g, A_PLAIN, E_LNBWD2, s));
     } else {
         DCPT_TRY(launch_gemm_nt(g, A_PLAIN, E_PLAIN, s));
     }
@@ -346,10 +303,10 @@ extern "C" int dcpt_nafblock_bwd(const dcpt_nafblock_params* p, const dcpt_nafbl
     DCPT_TRY(wgrad(dv, C2, C2, sv->xn2, C, C, A_PLAIN, tp, M, w.slab, w.colsum, nullptr, nullptr, nullptr, gr->conv4_w, nullptr,
                    gr->conv4_b, sw));
     // B5: dy = dout + LN2-backward
-    if (!ffn && !lne && !lrs) DCPT_TRY(launch_ln_bwd(gln, sv->y, sv->mu2, sv->rstd2, p->norm2_w, dout, dy, w.lnpart, w.ln_nblk, M, C, s));
+    if (!ffn && !lne) DCPT_TRY(launch_ln_bwd(gln, sv->y, sv->mu2, sv->rstd2, p->norm2_w, dout, dy, w.lnpart, w.ln_nblk, M, C, s));
     DCPT_TRY(side_fork(sd, 2, s));      // dy, LN2 partial sums
     if (ffn) DCPT_TRY(launch_colpart_reduce(w.ffn_part, ffn_bwd_f32_waves(M), 2, C, gr->norm2_w, gr->norm2_b, nullptr, sw));
-    else if (lne || lrs) DCPT_TRY(launch_colpart_reduce(w.lnpart, ln_tiles, 2, C, gr->norm2_w, gr->norm2_b, nullptr, sw));
+    else if (lne) DCPT_TRY(launch_colpart_reduce(w.lnpart, ln_tiles, 2, C, gr->norm2_w, gr->norm2_b, nullptr, sw));
     else DCPT_TRY(launch_colpart_reduce(w.lnpart, w.ln_nblk, 3, C, gr->norm2_w, gr->norm2_b, nullptr, sw));
     // B6: dts = d(t2*s)
     // when an image is a whole number of 128-pixel GEMM tiles, SCA's ds[b][k] = sum_p dts * t2 comes out of this GEMM's epilogue
@@ -388,24 +345,16 @@ extern "C" int dcpt_nafblock_bwd(const dcpt_nafblock_params* p, const dcpt_nafbl
     DCPT_TRY(launch_sca_dpool(w.ds_part, ds_slices, p->sca_w, w.dpool, B, C, P, s));
     // B9/B10: SimpleGate + depthwise conv backward
     (void)da;   // the fused kernel keeps da on chip
-    // (wide levels: + the row sums of LN1's backward, linear in dt1; the LN2 partials in the same buffer were consumed by B3)
-    const bool ring_b = !lrs && dw_ring_bwd_usable(dg, 4);   // dwring.hip: every quantity computed once, rows by LDS-DMA
-    const int nblk_b = ring_b ? dw_ring_bwd_num_blocks_per_image(dg) : dw_num_blocks_per_image_fused(dg);
-    if (ring_b) DCPT_TRY(launch_dw_ring_bwd_fused_f32(dts, sv->t1, w.w2p, p->conv2_b, sv->s, w.dpool, dt1, w.wpart, dg, s));
-    else DCPT_TRY(launch_dw_bwd_fused(dts, sv->t1, w.w2p, p->conv2_b, sv->s, w.dpool, dt1, w.wpart, dg, s, lrs ? w.rowpart : nullptr, w.u1, w.c1));
+    DCPT_TRY(launch_dw_ring_bwd_fused_f32(dts, sv->t1, w.w2p, p->conv2_b, sv->s, w.dpool, dt1, w.wpart, dg, s));   // dwring.hip: every quantity computed once, rows by LDS-DMA
     DCPT_TRY(side_fork(sd, 3, s));      // dt1, depthwise and SCA partial sums
     DCPT_TRY(launch_sca_wgrad(w.ds_part, ds_slices, w.ds, sv->pooled, gr->sca_w, gr->sca_b, B, C, sw));
-    DCPT_TRY(launch_dw_wgrad_reduce(w.wpart, B * nblk_b, C2, gr->conv2_w, gr->conv2_b, sw));
+    DCPT_TRY(launch_dw_wgrad_reduce(w.wpart, B * w.nblk_b, C2, gr->conv2_w, gr->conv2_b, sw));
     // B11: grad w.r.t. LN1 output
     g = GemmNT{};
     g.M = M; g.A = dt1; g.lda = C2; g.K = C2; g.Bw = w.wT1; g.N = C; g.C = gln; g.ldc = C;
     if (lne) {   // B11 + B13 in one launch: dinp = dy + LN1-backward(dt1 * W1^T)
         g.C = dinp; g.res = inp; g.ldres = C; g.aux = dy; g.mu = sv->mu1; g.rstd = sv->rstd1; g.lnw = p->norm1_w; g.colpart = w.lnpart2;
         DCPT_TRY(launch_gemm_nt(g, A_PLAIN, E_LNBWD, s));
-    } else if (lrs) {
-        g.C = dinp; g.res = inp; g.ldres = C; g.aux = dy; g.mu = sv->mu1; g.rstd = sv->rstd1; g.lnw = p->norm1_w; g.colpart = w.lnpart2;
-        g.rowpart = w.rowpart; g.rowparts = w.rp_dw;
-        DCPT_TRY(launch_gemm_nt(g, A_PLAIN, E_LNBWD2, s));
     } else {
         DCPT_TRY(launch_gemm_nt(g, A_PLAIN, E_PLAIN, s));
     }
@@ -418,9 +367,9 @@ extern "C" int dcpt_nafblock_bwd(const dcpt_nafblock_params* p, const dcpt_nafbl
     DCPT_TRY(wgrad(dt1, C2, C2, sv->xn1, C, C, A_PLAIN, tp, M, w.slab, w.colsum, nullptr, nullptr, nullptr, gr->conv1_w, nullptr,
                    gr->conv1_b, sw));
     // B13: dinp = dy + LN1-backward
-    if (!lne && !lrs) DCPT_TRY(launch_ln_bwd(gln, inp, sv->mu1, sv->rstd1, p->norm1_w, dy, dinp, w.lnpart2, w.ln_nblk, M, C, s));
+    if (!lne) DCPT_TRY(launch_ln_bwd(gln, inp, sv->mu1, sv->rstd1, p->norm1_w, dy, dinp, w.lnpart2, w.ln_nblk, M, C, s));
     DCPT_TRY(side_fork(sd, 5, s));      // LN1 partial sums
-    if (lne || lrs) DCPT_TRY(launch_colpart_reduce(w.lnpart2, ln_tiles, 2, C, gr->norm1_w, gr->norm1_b, nullptr, sw));
+    if (lne) DCPT_TRY(launch_colpart_reduce(w.lnpart2, ln_tiles, 2, C, gr->norm1_w, gr->norm1_b, nullptr, sw));
     else DCPT_TRY(launch_colpart_reduce(w.lnpart2, w.ln_nblk, 3, C, gr->norm1_w, gr->norm1_b, nullptr, sw));
     DCPT_TRY(side_join(sd, s));      // the caller's stream continues only after every weight gradient is written
     return DCPT_OK;

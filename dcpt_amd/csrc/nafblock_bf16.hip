@@ -37,13 +37,6 @@ bool ffn_fused(int C) {
 // 128) keeps the three-kernel chain, which scales with M (measured: 2K tiled inference 25.9 -> 58 ms with the chain kernel forced).
 bool ffn_chain(int C) { return !ffn_fused(C) && chain_fwd_bf16_ok(C, 1 << 20); }
 bool ffn_chain_use(int C, int64_t M) { return !ffn_fused(C) && chain_fwd_bf16_ok(C, M); }
-bool chain_conv3_on() {
-    // OFF: built, parity-green and measured (profiles/r5/bf16_block_level3_kernels_conv3_in_chain_negative.txt): the kernel with conv3 in front
-    // takes 120-123 us where the chain kernel + the separate conv3 launch take 86.5 + 35.4 -- one tile per CU serialises the extra tile load, GEMM,
-    // two barriers and the accumulator-layout round trip through LDS that the 256 x 256-tile GEMM overlaps across its tiles; same-box step +0.2 ms.
-    static const int on = dcpt_tuning("DCPT_CHAIN_CONV3", 0);
-    return on != 0;
-}
 bool chain_mid_on() {
     static const int on = dcpt_tuning("DCPT_CHAIN_MID", 1);
     return on != 0;
@@ -71,7 +64,7 @@ size_t fwd_layout(int B, int H, int W, int C, void* base, size_t bytes, FwdWsB* 
     WsAlloc a(base, base ? bytes : (size_t)-1);
     DwGeom g{B, H, W, C};
     FwdWsB w{};
-    w.nblk_pool = dw_ring_usable(g, 2) ? dw_ring_num_blocks_per_image(g, 2) : dw_num_blocks_per_image_bf16(g);
+    w.nblk_pool = dw_ring_num_blocks_per_image(g, 2);
     w.w2p = a.get<float>((size_t)18 * C);
     w.pool_part = a.get<float>((size_t)B * w.nblk_pool * C);
     w.W1 = a.get<bf16_t>((size_t)2 * C * C);
@@ -106,10 +99,6 @@ struct BwdWsB {
     float *ds_part, *ds, *dpool, *wpart;
     int ln_nblk, nblk_b, ds_slices;
     bool ds_fused;
-    // LayerNorm backward inside the dgrad GEMM epilogues (row sums supplied by the producers of dv / dt1: bf16.h EB_LNBWD2)
-    float *u4, *c4, *u1, *c1, *rowpart;
-    int rp_sg, rp_dw;
-    bool lrs;
     float *ffn_g5, *ffn_g4, *ffn_cs5, *ffn_cs4;   // per-wave slabs / column sums of ffn_wgrad_bf16
     float *ffn_part, *ffn_part1;   // LayerNorm2 / LayerNorm1 column partials of the fused narrow-level backward kernels: [waves][2][C] each
     // wide levels (C % 256 == 0): the four weight gradients as two grouped 256 x 256-tile launches + one finisher (gemm_tn_bf16_256.hip)
@@ -188,28 +177,8 @@ size_t bwd_layout(int B, int H, int W, int C, void* base, size_t bytes, BwdWsB* 
     w.ds_part = a.get<float>((size_t)B * w.ds_slices * C);
     w.ds = a.get<float>((size_t)B * C);
     w.dpool = a.get<float>((size_t)B * C);
-    {
-        const int n1 = dw_num_blocks_per_image_fused_bf16(g), n2 = dw_ring_bwd_usable(g, 2) ? dw_ring_bwd_num_blocks_per_image(g) : 0;
-        w.nblk_b = n1 > n2 ? n1 : n2;
-    }
+    w.nblk_b = dw_ring_bwd_num_blocks_per_image(g);
     w.wpart = a.get<float>((size_t)B * w.nblk_b * 10 * 2 * C);
-    w.u4 = a.get<float>((size_t)2 * C);
-    w.c4 = a.get<float>((size_t)2 * C);
-    w.u1 = a.get<float>((size_t)2 * C);
-    w.c1 = a.get<float>((size_t)2 * C);
-    {
-        GemmNTB q{};
-        q.N = C;
-        w.rp_sg = gemm_nt_bf16_tiles_n(q, EB_SGBWD);
-    }
-    w.rp_dw = dw_fused_row_chunks_bf16(g);
-    // OFF by default: exact and 4 tensor passes lighter, but measured slower at EVERY level also in bf16 (same box, A/B: level-0
-    // backward 2.68 vs 2.47 ms, level 3 0.64 vs 0.60 ms, the NAFNet-64 step 53.2 vs 51.3 ms).  A GEMM whose epilogue moves more bytes
-    // than its k-loop runs at ~3 TB/s -- its loads are not overlapped across tiles -- while the separate LayerNorm kernel streams
-    // at 5.3 TB/s; the two passes it saves do not pay for that.
-    static const int on = dcpt_tuning("DCPT_LN_ROWSUMS_BF16", 0);
-    w.lrs = on && w.rp_sg <= 8 && w.rp_dw <= 8;
-    w.rowpart = a.get<float>((size_t)M * (w.rp_sg > w.rp_dw ? w.rp_sg : w.rp_dw) * 2);
     {   // the GEMM-epilogue form of the LayerNorm column partials: [M / 128 tiles][2][C]
         const size_t need = (size_t)cdiv64(M, 128) * 2 * C;
         if (need > (size_t)w.ln_nblk * 2 * C) {
@@ -217,7 +186,7 @@ size_t bwd_layout(int B, int H, int W, int C, void* base, size_t bytes, BwdWsB* 
             w.lnpart2 = a.get<float>(need);
         }
     }
-    w.mid = ffn_chain_use(C, M) && chain_mid_on() && w.ds_fused && w.tn256 && !w.lrs;
+    w.mid = ffn_chain_use(C, M) && chain_mid_on() && w.ds_fused && w.tn256;
     w.ffn_part = ffn_fused(C) ? a.get<float>((size_t)ffn_bwd_bf16_waves(M) * 2 * C) : nullptr;
     w.ffn_part1 = ffn_fused(C) ? a.get<float>((size_t)ffn_bwd_bf16_waves(M) * 2 * C) : nullptr;
     w.ffn_g5 = w.ffn_g4 = w.ffn_cs5 = w.ffn_cs4 = nullptr;
@@ -243,7 +212,7 @@ int wgrad_b(const bf16_t* X, int N, const bf16_t* Y, int K, int64_t M, float* sl
                                WR_PLAIN, s);
 }
 
-bool shape_ok(int B, int H, int W, int C) { return B > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0 && C <= 1024; }
+bool shape_ok(int B, int H, int W, int C) { return B > 0 && B <= 65535 && H > 0 && W > 0 && C > 0 && C % 8 == 0 && C <= 1024; }
 
 // The operand copies of a block's weights that depend on the PARAMETERS only (not on activations): bf16 [N][K] copies for the forward
 // GEMMs, transposed (and beta / gamma-scaled) copies for the data-gradient GEMMs, the depthwise taps as [9][2C] fp32.  A caller that
@@ -369,8 +338,7 @@ int fwd_head_bf16(const dcpt_nafblock_params* p, const bf16_t* inp, const HeadB&
     }
     DwGeom dg{B, H, W, C};
     if (h.pack_dw) DCPT_TRY(launch_dw_pack_weights(p->conv2_w, h.w2p, 2 * C, s));
-    if (dw_ring_usable(dg, 2)) return launch_dw_ring_fwd_bf16(h.t1, h.w2p, p->conv2_b, h.t2, h.pool_part, dg, s);
-    return launch_dw_fwd_bf16(h.t1, h.w2p, p->conv2_b, h.t2, h.pool_part, dg, s);
+    return launch_dw_ring_fwd_bf16(h.t1, h.w2p, p->conv2_b, h.t2, h.pool_part, dg, s);
 }
 
 struct TailB {
@@ -380,8 +348,8 @@ struct TailB {
     bf16_t *xn2_ws, *g_ws;        // stand-ins for the three-kernel form where the caller's are null
     float *mu2_ws, *rstd2_ws;
 };
-// out = y + gamma (conv5(SimpleGate(conv4(LayerNorm2(y)))) + b5); c3 != null: conv3 in front of the chain kernel (y is then written by it)
-int fwd_ffn_bf16(const dcpt_nafblock_params* p, bf16_t* y, bf16_t* out, const TailB& t, int64_t M, int C, hipStream_t s, const ChainFwdB* c3 = nullptr) {
+// out = y + gamma (conv5(SimpleGate(conv4(LayerNorm2(y)))) + b5)
+int fwd_ffn_bf16(const dcpt_nafblock_params* p, bf16_t* y, bf16_t* out, const TailB& t, int64_t M, int C, hipStream_t s) {
     const float eps = 1e-6f;
     if (ffn_fused(C)) {   // narrow levels: LayerNorm2 -> conv4 -> SimpleGate -> conv5 -> residual in one pass over y (ffn_bf16.hip)
         FfnFwdB f{};
@@ -394,9 +362,6 @@ int fwd_ffn_bf16(const dcpt_nafblock_params* p, bf16_t* y, bf16_t* out, const Ta
         ChainFwdB f{};
         f.y = y; f.lnw = p->norm2_w; f.lnb = p->norm2_b; f.Wf = t.Wf; f.b4 = p->conv4_b; f.b5 = p->conv5_b; f.gamma = p->gamma;
         f.out = out; f.v = t.v; f.xn2 = t.xn2; f.g = t.g; f.mu = t.mu2; f.rstd = t.rstd2; f.M = M; f.eps = eps;
-        if (c3) {   // y = inp + beta (conv3(t2 s) + b3) is produced by the same kernel
-            f.t2 = c3->t2; f.inp = c3->inp; f.W3f = c3->W3f; f.b3 = c3->b3; f.beta = c3->beta; f.P = c3->P;
-        }
         return launch_chain_fwd_bf16(f, C, s);
     }
     // (inference at a chain width with a pixel count the chain kernel is not used for: LN2(y) / the gate / the statistics live in the workspace)
@@ -418,7 +383,7 @@ static int nafblock_fwd_bf16_impl(const dcpt_nafblock_params* p, const uint16_t*
                                   dcpt_stream_t stream) {
     hipStream_t s = (hipStream_t)stream;
     DCPT_CHECK_ARG(p && inp && out && sv, "nafblock_fwd_bf16: null argument");
-    DCPT_CHECK_ARG(shape_ok(B, H, W, C), "nafblock_fwd_bf16: bad shape B=%d H=%d W=%d C=%d (C %% 8 == 0, C <= 1024)", B, H, W, C);
+    DCPT_CHECK_ARG(shape_ok(B, H, W, C), "nafblock_fwd_bf16: bad shape B=%d H=%d W=%d C=%d (B <= 65535, C %% 8 == 0, C <= 1024)", B, H, W, C);
     DCPT_CHECK_ARG(sv->t1 && sv->t2 && sv->y && sv->xn1 && sv->mu1 && sv->rstd1 && sv->pooled && sv->s, "nafblock_fwd_bf16: saved buffers missing");
     const bool infer = !sv->v && !sv->xn2 && !sv->g && !sv->mu2 && !sv->rstd2;   // inference with the fused second half: nothing of it is kept
     // (v alone may be null anywhere: a caller that runs no backward -- the bias+gate epilogue then writes SimpleGate(v) only)
@@ -465,15 +430,8 @@ static int nafblock_fwd_bf16_impl(const dcpt_nafblock_params* p, const uint16_t*
         DCPT_TRY(fwd_head_bf16(p, inp, h, B, H, W, C, s));
     }
     DCPT_TRY(launch_sca_fwd(w.pool_part, w.nblk_pool, p->sca_w, p->sca_b, sv->pooled, sv->s, B, C, P, s));
-    // wide levels, images of whole 128-pixel tiles: conv3 runs IN FRONT of the chain kernel below (its per-image weights as fragment streams)
-    const bool conv3_in_chain = ffn_chain_use(C, M) && chain_conv3_on() && !w.scale_act && P % 128 == 0;
     g = GemmNTB{};
-    if (conv3_in_chain) {
-        j = WpackBJobs{};
-        j.n = 1;
-        j.in[0] = p->conv3_w; j.out[0] = w.W3s; j.N[0] = C; j.K[0] = C; j.kscale[0] = sv->s; j.nimg[0] = B; j.transpose[0] = 11;
-        DCPT_TRY(launch_wpack_bf16(j, s));
-    } else if (w.scale_act) {
+    if (w.scale_act) {
         // y = inp + (conv3(t2 * s) + b3) * beta with the scale on the activations (small images): one pass over t2, one GEMM
         DCPT_TRY(launch_scale_rows_bf16(sv->t2, sv->s, w.t2s, M, C, P, s));
         g.M = M; g.A = w.t2s; g.lda = C; g.K = C; g.Bw = w.W3; g.N = C; g.C = sv->y; g.ldc = C; g.bias = p->conv3_b;
@@ -488,13 +446,11 @@ static int nafblock_fwd_bf16_impl(const dcpt_nafblock_params* p, const uint16_t*
         g.res = inp; g.ldres = C; g.cscale = p->beta;
         g.nb = B; g.sA = (int64_t)P * C; g.sB = (int64_t)C * C; g.sC = (int64_t)P * C; g.sR = (int64_t)P * C;
     }
-    if (!conv3_in_chain) DCPT_TRY(launch_gemm_nt_bf16(g, EB_RESID, s));
+    DCPT_TRY(launch_gemm_nt_bf16(g, EB_RESID, s));
     TailB t{};
     t.W4 = w.W4; t.W5 = w.W5; t.Wf = w.Wf; t.v = sv->v; t.xn2 = sv->xn2; t.g = sv->g; t.mu2 = sv->mu2; t.rstd2 = sv->rstd2;
     t.xn2_ws = w.xn2; t.g_ws = w.g; t.mu2_ws = w.mu2; t.rstd2_ws = w.rstd2;
-    ChainFwdB c3{};
-    c3.t2 = sv->t2; c3.inp = inp; c3.W3f = w.W3s; c3.b3 = p->conv3_b; c3.beta = p->beta; c3.P = P;
-    return fwd_ffn_bf16(p, sv->y, out, t, M, C, s, conv3_in_chain ? &c3 : nullptr);
+    return fwd_ffn_bf16(p, sv->y, out, t, M, C, s);
 }
 
 extern "C" int dcpt_nafblock_fwd_bf16(const dcpt_nafblock_params* p, const uint16_t* inp, uint16_t* out, const dcpt_nafblock_saved_bf16* sv,
@@ -527,7 +483,7 @@ size_t local_layout_bf16(int B, int H, int W, int C, void* base, size_t bytes, L
     const size_t M = (size_t)B * H * W;
     DwGeom g{B, H, W, C};
     LocalWsB w{};
-    const int nblk_pool = dw_ring_usable(g, 2) ? dw_ring_num_blocks_per_image(g, 2) : dw_num_blocks_per_image_bf16(g);
+    const int nblk_pool = dw_ring_num_blocks_per_image(g, 2);
     w.w2p = a.get<float>((size_t)18 * C);
     w.pool_part = a.get<float>((size_t)B * nblk_pool * C);   // (the depthwise kernels write their pooling partials; nobody reads them here)
     w.W1 = a.get<bf16_t>((size_t)2 * C * C);
@@ -561,7 +517,7 @@ extern "C" int dcpt_nafblock_local_fwd_bf16(const dcpt_nafblock_params* p, const
                                             dcpt_stream_t stream) {
     hipStream_t s = (hipStream_t)stream;
     DCPT_CHECK_ARG(p && inp && out, "nafblock_local_fwd_bf16: null argument");
-    DCPT_CHECK_ARG(shape_ok(B, H, W, C) && k1 >= 1 && k2 >= 1, "nafblock_local_fwd_bf16: bad shape B=%d H=%d W=%d C=%d k=%dx%d (C %% 8 == 0, C <= 1024)",
+    DCPT_CHECK_ARG(shape_ok(B, H, W, C) && k1 >= 1 && k2 >= 1, "nafblock_local_fwd_bf16: bad shape B=%d H=%d W=%d C=%d k=%dx%d (B <= 65535, C %% 8 == 0, C <= 1024)",
                    B, H, W, C, k1, k2);
     if (k1 > H) k1 = H;   // arch_util.py:381 k = min(size, kernel)
     if (k2 > W) k2 = W;
@@ -618,7 +574,7 @@ static int nafblock_bwd_bf16_impl(const dcpt_nafblock_params* p, const dcpt_nafb
                                   int H, int W, int C, const void* packed, size_t packed_bytes, dcpt_stream_t stream) {
     hipStream_t s = (hipStream_t)stream;
     DCPT_CHECK_ARG(p && gr && inp && sv && dout && dinp, "nafblock_bwd_bf16: null argument");
-    DCPT_CHECK_ARG(shape_ok(B, H, W, C), "nafblock_bwd_bf16: bad shape B=%d H=%d W=%d C=%d", B, H, W, C);
+    DCPT_CHECK_ARG(shape_ok(B, H, W, C), "nafblock_bwd_bf16: bad shape B=%d H=%d W=%d C=%d (B <= 65535, C %% 8 == 0, C <= 1024)", B, H, W, C);
     BwdWsB w;
     const size_t need = bwd_layout(B, H, W, C, ws, ws_bytes, &w);
     if (need > ws_bytes || ws == nullptr) {
@@ -651,13 +607,6 @@ static int nafblock_bwd_bf16_impl(const dcpt_nafblock_params* p, const dcpt_nafb
     }
 
     const int ln_tiles = (int)cdiv64(M, 128);
-    if (w.lrs) {   // u = W w_ln, c = b_conv + W b_ln for conv4 o LN2 and conv1 o LN1 (fp32; gemm.h E_LNBWD2)
-        LnVecJobs lj{};
-        lj.n = 2; lj.N2 = C2; lj.C = C; lj.round_bf16 = 1;
-        lj.W[0] = p->conv4_w; lj.bz[0] = p->conv4_b; lj.lnw[0] = p->norm2_w; lj.lnb[0] = p->norm2_b; lj.u[0] = w.u4; lj.cvec[0] = w.c4;
-        lj.W[1] = p->conv1_w; lj.bz[1] = p->conv1_b; lj.lnw[1] = p->norm1_w; lj.lnb[1] = p->norm1_b; lj.u[1] = w.u1; lj.cvec[1] = w.c1;
-        DCPT_TRY(launch_lnvec(lj, s));
-    }
     // weight-gradient side stream: 0 never, 1 always, 2 only at the levels without the grouped 256-tile weight-gradient launch (whose
     // 128-KB blocks cannot share a CU with a main-stream GEMM block: with it the two streams only time-slice)
     static const int side_mode = dcpt_tuning("DCPT_BF16_SIDE", 2);
@@ -684,11 +633,8 @@ static int nafblock_bwd_bf16_impl(const dcpt_nafblock_params* p, const dcpt_nafb
         DCPT_TRY(side_fork(sd, 2, s));
         DCPT_TRY(launch_colpart_reduce(w.ffn_part, ffn_bwd_bf16_waves(M), 2, C, gr->norm2_w, gr->norm2_b, nullptr, sw));
     } else {
-        // B1: dv = SimpleGate'(dout * gamma * W5; v)   (+ the row sums of LN2's backward, linear in dv)
+        // B1: dv = SimpleGate'(dout * gamma * W5; v)
         g.M = M; g.A = dout; g.lda = C; g.K = C; g.Bw = w.wT5; g.N = C; g.C = w.dv; g.ldc = C2; g.aux = sv->v;
-        if (w.lrs) {
-            g.rowpart = w.rowpart; g.uvec = w.u4; g.cvec = w.c4;
-        }
         DCPT_TRY(launch_gemm_nt_bf16(g, EB_SGBWD, s));
         // B2: conv5 / gamma gradients
         if (!w.tn256) DCPT_TRY(wgrad_b(dout, C, sv->g, C, M, w.slab, w.colsum, p->gamma, p->conv5_w, p->conv5_b, gr->conv5_w, gr->gamma, gr->conv5_b, sw));
@@ -696,19 +642,13 @@ static int nafblock_bwd_bf16_impl(const dcpt_nafblock_params* p, const dcpt_nafb
         // B3: gradient of LN2's output
         g = GemmNTB{};
         g.M = M; g.A = w.dv; g.lda = C2; g.K = C2; g.Bw = w.wT4; g.N = C; g.C = w.gln; g.ldc = C;
-        if (w.lrs) {   // B3 + B5 in one launch: dy = dout + LN2-backward(dv W4^T), the LayerNorm's incoming gradient is never written
-            g.C = w.dy; g.res = sv->y; g.ldres = C; g.aux = dout; g.mu = sv->mu2; g.rstd = sv->rstd2; g.lnw = p->norm2_w; g.colpart = w.lnpart;
-            g.rowpart = w.rowpart; g.rowparts = w.rp_sg;
-            DCPT_TRY(launch_gemm_nt_bf16(g, EB_LNBWD2, s));
-        } else {
-            DCPT_TRY(launch_gemm_nt_bf16(g, EB_PLAIN, s));
-        }
+        DCPT_TRY(launch_gemm_nt_bf16(g, EB_PLAIN, s));
         // B4: conv4 gradients
         if (!w.tn256) DCPT_TRY(wgrad_b(w.dv, C2, sv->xn2, C, M, w.slab, w.colsum, nullptr, nullptr, nullptr, gr->conv4_w, nullptr, gr->conv4_b, sw));
         // B5: dy = dout + LN2-backward  (with the chain kernel: part of B6 below)
-        if (!w.lrs && !w.mid) DCPT_TRY(launch_ln_bwd_bf16(w.gln, sv->y, sv->mu2, sv->rstd2, p->norm2_w, dout, w.dy, w.lnpart, w.ln_nblk, M, C, s));
+        if (!w.mid) DCPT_TRY(launch_ln_bwd_bf16(w.gln, sv->y, sv->mu2, sv->rstd2, p->norm2_w, dout, w.dy, w.lnpart, w.ln_nblk, M, C, s));
         DCPT_TRY(side_fork(sd, 2, s));
-        if (!w.tn256) DCPT_TRY(launch_colpart_reduce(w.lnpart, (w.lrs || w.mid) ? ln_tiles : w.ln_nblk, 2, C, gr->norm2_w, gr->norm2_b, nullptr, sw));
+        if (!w.tn256) DCPT_TRY(launch_colpart_reduce(w.lnpart, w.mid ? ln_tiles : w.ln_nblk, 2, C, gr->norm2_w, gr->norm2_b, nullptr, sw));
     }
     // B6: dts = d(t2 * s) (+ SCA's per-image channel sums out of the epilogue when an image is a whole number of 128-pixel tiles)
     g = GemmNTB{};
@@ -745,12 +685,7 @@ static int nafblock_bwd_bf16_impl(const dcpt_nafblock_params* p, const dcpt_nafb
     // B8: SCA backward
     DCPT_TRY(launch_sca_dpool(w.ds_part, w.ds_slices, p->sca_w, w.dpool, B, C, P, s, w.tn256 ? w.ds : nullptr));
     // B9 / B10: SimpleGate + depthwise backward, da on chip
-    const bool ring_b = !w.lrs && dw_ring_bwd_usable(dg, 2);
-    const int nblk_b = ring_b ? dw_ring_bwd_num_blocks_per_image(dg) : dw_num_blocks_per_image_fused_bf16(dg);
-    if (ring_b) DCPT_TRY(launch_dw_ring_bwd_fused_bf16(w.dts, sv->t1, w.w2p, p->conv2_b, sv->s, w.dpool, w.dt1, w.wpart, dg, s));
-    else
-        DCPT_TRY(launch_dw_bwd_fused_bf16(w.dts, sv->t1, w.w2p, p->conv2_b, sv->s, w.dpool, w.dt1, w.wpart, dg, s, w.lrs ? w.rowpart : nullptr, w.u1,
-                                          w.c1));
+    DCPT_TRY(launch_dw_ring_bwd_fused_bf16(w.dts, sv->t1, w.w2p, p->conv2_b, sv->s, w.dpool, w.dt1, w.wpart, dg, s));
     DCPT_TRY(side_fork(sd, 3, s));
     if (w.tn256) {   // B2 + B4 + B7 + B12 as ONE grouped launch: G5 = dout^T g, G4 = dv^T LN2(y), G3 = dy^T t2 (per image, or t2 * s), G1 = dt1^T LN1(inp)
         w.wg.p[0].X = dout; w.wg.p[0].Y = sv->g;
@@ -760,7 +695,7 @@ static int nafblock_bwd_bf16_impl(const dcpt_nafblock_params* p, const dcpt_nafb
         DCPT_TRY(launch_gemm_tn_bf16_256(w.wg, sw));
     } else {
         DCPT_TRY(launch_sca_wgrad(w.ds_part, w.ds_slices, w.ds, sv->pooled, gr->sca_w, gr->sca_b, B, C, sw));
-        DCPT_TRY(launch_dw_wgrad_reduce(w.wpart, B * nblk_b, C2, gr->conv2_w, gr->conv2_b, sw));
+        DCPT_TRY(launch_dw_wgrad_reduce(w.wpart, B * w.nblk_b, C2, gr->conv2_w, gr->conv2_b, sw));
     }
     if (ffn) {
         // B11 + B13 in one pass (ffn_bf16.hip): dinp = dy + LayerNorm1 backward of dt1 W1^T
@@ -774,17 +709,11 @@ static int nafblock_bwd_bf16_impl(const dcpt_nafblock_params* p, const dcpt_nafb
         // B11: gradient of LN1's output
         g = GemmNTB{};
         g.M = M; g.A = w.dt1; g.lda = C2; g.K = C2; g.Bw = w.wT1; g.N = C; g.C = w.gln; g.ldc = C;
-        if (w.lrs) {   // B11 + B13: dinp = dy + LN1-backward(dt1 W1^T)
-            g.C = dinp; g.res = inp; g.ldres = C; g.aux = w.dy; g.mu = sv->mu1; g.rstd = sv->rstd1; g.lnw = p->norm1_w; g.colpart = w.lnpart2;
-            g.rowpart = w.rowpart; g.rowparts = w.rp_dw;
-            DCPT_TRY(launch_gemm_nt_bf16(g, EB_LNBWD2, s));
-        } else {
-            DCPT_TRY(launch_gemm_nt_bf16(g, EB_PLAIN, s));
-        }
+        DCPT_TRY(launch_gemm_nt_bf16(g, EB_PLAIN, s));
         // B12: conv1 gradients
         if (!w.tn256) DCPT_TRY(wgrad_b(w.dt1, C2, sv->xn1, C, M, w.slab, w.colsum, nullptr, nullptr, nullptr, gr->conv1_w, nullptr, gr->conv1_b, sw));
         // B13: dinp = dy + LN1-backward
-        if (!w.lrs) DCPT_TRY(launch_ln_bwd_bf16(w.gln, inp, sv->mu1, sv->rstd1, p->norm1_w, w.dy, dinp, w.lnpart2, w.ln_nblk, M, C, s));
+        DCPT_TRY(launch_ln_bwd_bf16(w.gln, inp, sv->mu1, sv->rstd1, p->norm1_w, w.dy, dinp, w.lnpart2, w.ln_nblk, M, C, s));
         DCPT_TRY(side_fork(sd, 5, s));
         if (w.tn256) {
             // the finisher: the four weight gradients out of their partial sums (gain algebra of nafblock.hip: dW = gain G,
@@ -806,15 +735,14 @@ static int nafblock_bwd_bf16_impl(const dcpt_nafblock_params* p, const dcpt_nafb
                 f.slab[2].ks_div = q[2]->seg_rows > 0 ? 1 : (int)(P / q[2]->rows_per_split);
             }
             f.slab[3].dW = gr->conv1_w; f.slab[3].dbias = gr->conv1_b;
-            const int lnR = w.lrs ? ln_tiles : w.ln_nblk;
             f.ncols = 3;
-            f.cols[0] = FinCols{w.lnpart, gr->norm2_w, gr->norm2_b, w.mid ? ln_tiles : lnR, 2, C, 0};
-            f.cols[1] = FinCols{w.lnpart2, gr->norm1_w, gr->norm1_b, lnR, 2, C, 0};
-            f.cols[2] = FinCols{w.wpart, gr->conv2_w, gr->conv2_b, B * nblk_b, 10, C2, 1};
+            f.cols[0] = FinCols{w.lnpart, gr->norm2_w, gr->norm2_b, w.mid ? ln_tiles : w.ln_nblk, 2, C, 0};
+            f.cols[1] = FinCols{w.lnpart2, gr->norm1_w, gr->norm1_b, w.ln_nblk, 2, C, 0};
+            f.cols[2] = FinCols{w.wpart, gr->conv2_w, gr->conv2_b, B * w.nblk_b, 10, C2, 1};
             f.sca = FinSca{w.ds, sv->pooled, gr->sca_w, gr->sca_b, B, C};
             DCPT_TRY(launch_wgrad_finish(f, sw));
         } else {
-            DCPT_TRY(launch_colpart_reduce(w.lnpart2, w.lrs ? ln_tiles : w.ln_nblk, 2, C, gr->norm1_w, gr->norm1_b, nullptr, sw));
+            DCPT_TRY(launch_colpart_reduce(w.lnpart2, w.ln_nblk, 2, C, gr->norm1_w, gr->norm1_b, nullptr, sw));
         }
     }
     DCPT_TRY(side_join(sd, s));

@@ -17,7 +17,7 @@
 
 namespace {
 
-// depthwise backward on the ring kernels (dwring.hip) when the channel count allows it (Ctot % 8 == 0); DCPT_DW_RING_BWD=0 disables
+// depthwise backward on the ring kernels (dwring.hip) when the channel count allows it (Ctot % 8 == 0)
 bool dwf_ring(int B, int H, int W, int Ctot) { return Ctot % 8 == 0 && dw_ring_usable(DwGeom{B, H, W, Ctot / 2}, 4); }
 bool dwb_ring(int B, int H, int W, int Ctot) { return Ctot % 8 == 0 && dw_ring_bwd_usable(DwGeom{B, H, W, Ctot / 2}, 4); }
 

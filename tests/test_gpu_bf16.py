@@ -79,6 +79,9 @@ KERNELS_OF_SHAPE = {   # shape -> (families that must run, families that must no
     (2, 512, 8, 16): (("nt_bf16.128", "tn_bf16.256_grouped", "wgrad_finish", "ln_fwd_bf16"), _CHAINS + ("nt_bf16.256", "tn_bf16.128")),
     (1, 1024, 8, 8): (("nt_bf16.128", "tn_bf16.256_grouped", "wgrad_finish"), _CHAINS + ("nt_bf16.256", "tn_bf16.128")),
     (1, 16, 11, 70): (("dw.ring_fwd_bf16", "dw.ring_bwd_bf16"), _CHAINS),
+    # the ring kernels' smallest geometries: fewer rows than the ring prefetches, a single row
+    (1, 8, 2, 3): (("dw.ring_fwd_bf16", "dw.ring_bwd_bf16"), _CHAINS),
+    (2, 16, 1, 5): (("dw.ring_fwd_bf16", "dw.ring_bwd_bf16"), _CHAINS),
     # the 256 x 256-tile NT kernel, the grouped weight gradient + finisher and all three chain forms (whole-tile images)
     (24, 512, 32, 32): (("nt_bf16.256", "tn_bf16.256_grouped", "wgrad_finish") + _CHAINS[:3], ("nt_bf16.128", "tn_bf16.128", "ln_fwd_bf16")),
     (13, 512, 48, 40): (("nt_bf16.256", "tn_bf16.256_grouped", "wgrad_finish") + _CHAINS[:3], ("nt_bf16.128", "tn_bf16.128", "ln_fwd_bf16")),
@@ -95,7 +98,9 @@ KERNELS_OF_SHAPE = {   # shape -> (families that must run, families that must no
                                    # the chain kernels of the wide levels (chain_bf16.hip: taken when the 128-pixel tiles fill 3/4 of the chip's last
                                    # round): images of 15 tiles (FFN + HEAD + the backward MID form, odd tile count per image), images that are no
                                    # whole number of tiles (no MID form; M = 28 800), two rounds of tiles at C = 256 (M = 49 152)
-                                   (13, 512, 48, 40), (200, 512, 12, 12), (48, 256, 32, 32)])
+                                   (13, 512, 48, 40), (200, 512, 12, 12), (48, 256, 32, 32),
+                                   # the depthwise ring kernels' smallest geometries: fewer rows than the ring prefetches, a single row
+                                   (1, 8, 2, 3), (2, 16, 1, 5)])
 def test_nafblock_bf16_oracle(dev, shape):
     from dcpt_amd import functional as DF
     from kernel_trace import kernel_trace

@@ -119,8 +119,11 @@ def test_nafblock_golden(dev, golden_dir, c):
 # columns (W > 64), the 8-piece single tile (32 < W <= 64), and two row parts (H >= 64 with few blocks)
 # (3, 64, 5, 7) / (5, 64, 48, 40): the fused forward chains of the narrowest level (ffn_f32.hip) with a ragged last group of 32 pixels
 # (M = 105) and with more groups than the launch has waves' ring slots (M = 9600)
+# (2, 8, 1, 1) / (1, 8, 2, 3) / (1, 8, 3, 1): the ring kernels' smallest geometries (they are the only NAFNet depthwise kernels): a one-pixel
+# map, fewer rows than the ring prefetches, a one-pixel row
 @pytest.mark.parametrize("B,c,H,W", [(1, 8, 5, 7), (3, 24, 9, 4), (2, 128, 12, 20), (1, 512, 8, 8), (2, 32, 33, 17),
-                                     (1, 16, 11, 70), (1, 24, 6, 50), (1, 8, 70, 9), (3, 64, 5, 7), (5, 64, 48, 40)])
+                                     (1, 16, 11, 70), (1, 24, 6, 50), (1, 8, 70, 9), (3, 64, 5, 7), (5, 64, 48, 40),
+                                     (2, 8, 1, 1), (1, 8, 2, 3), (1, 8, 3, 1)])
 def test_nafblock_oracle(dev, B, c, H, W):
     P = block_params(c, f"ob{c}.")
     x = keyed_input(f"ob{c}.x", (B, c, H, W), lo=-1.0, hi=1.0)
@@ -134,6 +137,20 @@ def test_nafblock_oracle(dev, B, c, H, W):
     check("dx", dx, xr.grad, 5e-5)
     for k in P:
         check("grad " + k, grads[k], Pr[k].grad, 1e-4)
+
+
+def test_nafblock_batch_limit(dev):
+    """The depthwise ring kernels put the image index in grid.z: a batch above 65535 is refused by the entry point's argument check,
+    before the first launch."""
+    from dcpt_amd import functional as DF
+    from dcpt_amd._lib import DcptHipError
+
+    c = 8
+    P = block_params(c, "bl.")
+    Pg = {k: v.to(dev) for k, v in P.items()}
+    x = torch.zeros((65536, c, 1, 1), device=dev)
+    with pytest.raises(DcptHipError, match="65535"):
+        DF.nafblock(x, {fk: Pg[rk] for fk, rk in FUSED.items()})
 
 
 def test_nafblock_zero_gain(dev):
