@@ -12,7 +12,7 @@ import threading
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libdcpt_hip.so")   # the in-tree build is the only library the product loads
 
-ABI_VERSION = 15
+ABI_VERSION = 16
 _lib = None
 _lock = threading.Lock()
 
@@ -129,10 +129,10 @@ SIGNATURES = {
                                  f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint, stream_t]),
     "dcpt_nafblock_fwd_bf16_ws_bytes": (sz, [cint, cint, cint, cint]),
     "dcpt_nafblock_bwd_bf16_ws_bytes": (sz, [cint, cint, cint, cint]),
-    "dcpt_nafblock_fwd_bf16": (cint, [C.POINTER(NafBlockParams), f32p, f32p, C.POINTER(NafBlockSavedBf16), C.c_void_p, sz,
+    "dcpt_nafblock_fwd_bf16": (cint, [C.POINTER(NafBlockParams), C.c_void_p, sz, f32p, f32p, C.POINTER(NafBlockSavedBf16), C.c_void_p, sz,
                                       cint, cint, cint, cint, stream_t]),
-    "dcpt_nafblock_bwd_bf16": (cint, [C.POINTER(NafBlockParams), C.POINTER(NafBlockGrads), f32p, C.POINTER(NafBlockSavedBf16),
-                                      f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint, stream_t]),
+    "dcpt_nafblock_bwd_bf16": (cint, [C.POINTER(NafBlockParams), C.c_void_p, sz, C.POINTER(NafBlockGrads), f32p,
+                                      C.POINTER(NafBlockSavedBf16), f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint, stream_t]),
     "dcpt_set_gemm_x3": (cint, [C.c_void_p, sz, cint]),
     "dcpt_gemm_x3_scratch_misses": (C.c_longlong, []),
     "dcpt_nafblock_wpack_bf16_bytes": (sz, [cint]),
@@ -140,44 +140,30 @@ SIGNATURES = {
     "dcpt_nafblock_fused_ffn": (cint, [cint]),
     "dcpt_nafblock_wpack_bf16": (cint, [C.POINTER(NafBlockParams), C.c_void_p, sz, cint, stream_t]),
     "dcpt_nafblock_wpack_bf16_multi": (cint, [C.POINTER(NafBlockParams), C.POINTER(C.c_void_p), C.POINTER(sz), C.POINTER(cint), cint, stream_t]),
-    "dcpt_nafblock_fwd_bf16_packed": (cint, [C.POINTER(NafBlockParams), C.c_void_p, sz, f32p, f32p, C.POINTER(NafBlockSavedBf16), C.c_void_p, sz,
-                                             cint, cint, cint, cint, stream_t]),
-    "dcpt_nafblock_bwd_bf16_packed": (cint, [C.POINTER(NafBlockParams), C.c_void_p, sz, C.POINTER(NafBlockGrads), f32p,
-                                             C.POINTER(NafBlockSavedBf16), f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint, stream_t]),
     "dcpt_conv1x1_wgrad_bf16_ws_bytes": (sz, [i64, cint, cint]),
     "dcpt_conv1x1_wgrad_bf16": (cint, [f32p, f32p, f32p, f32p, C.c_void_p, sz, i64, cint, cint, stream_t]),
     "dcpt_cast_f32_bf16": (cint, [f32p, f32p, i64, stream_t]),
     "dcpt_cast_bf16_f32": (cint, [f32p, f32p, i64, stream_t]),
     "dcpt_conv_ln_bf16_ws_bytes": (sz, [cint, cint, cint, cint, cint, cint, cint]),
-    "dcpt_conv_ln_fwd_bf16": (cint, [f32p, f32p, f32p, f32p, f32p, cint, f32p, f32p, f32p, f32p, C.c_void_p, sz, cint, cint, cint,
-                                     cint, cint, cint, stream_t]),
-    "dcpt_conv_ln_bwd_bf16": (cint, [f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, C.c_void_p, sz,
-                                     cint, cint, cint, cint, cint, cint, cint, stream_t]),
-    "dcpt_conv_ln_bwd_acc_bf16": (cint, [f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, C.c_void_p, sz,
-                                         cint, cint, cint, cint, cint, cint, cint, stream_t]),
+    "dcpt_conv_ln_fwd_bf16": (cint, [f32p, f32p, C.c_void_p, sz, f32p, f32p, f32p, cint, f32p, f32p, f32p, f32p, C.c_void_p, sz, cint,
+                                     cint, cint, cint, cint, cint, stream_t]),
+    "dcpt_conv_ln_bwd_bf16": (cint, [f32p, f32p, f32p, C.c_void_p, sz, f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p,
+                                     f32p, C.c_void_p, sz, cint, cint, cint, cint, cint, cint, cint, stream_t]),
     "dcpt_conv1x1_pool_relu_bf16_ws_bytes": (sz, [cint, cint, cint, cint, cint, cint]),
-    "dcpt_conv1x1_pool_relu_fwd_bf16": (cint, [f32p, f32p, f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint, cint, stream_t]),
-    "dcpt_conv1x1_pool_relu_bwd_bf16": (cint, [f32p, f32p, f32p, f32p, f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint, cint,
+    "dcpt_conv1x1_pool_relu_fwd_bf16": (cint, [f32p, f32p, C.c_void_p, sz, f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint, cint,
                                                stream_t]),
+    "dcpt_conv1x1_pool_relu_bwd_bf16": (cint, [f32p, f32p, f32p, C.c_void_p, sz, f32p, f32p, f32p, C.c_void_p, sz, cint, cint, cint,
+                                               cint, cint, stream_t]),
     "dcpt_conv_wpack_bf16_bytes": (sz, [cint, cint, cint]),
     "dcpt_conv_wpack_bf16_multi": (cint, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(sz), C.POINTER(cint), C.POINTER(cint),
                                           C.POINTER(cint), cint, stream_t]),
-    "dcpt_conv_ln_fwd_bf16_packed": (cint, [f32p, f32p, C.c_void_p, sz, f32p, f32p, f32p, cint, f32p, f32p, f32p, f32p, C.c_void_p, sz, cint,
-                                            cint, cint, cint, cint, cint, stream_t]),
-    "dcpt_conv_ln_bwd_acc_bf16_packed": (cint, [f32p, f32p, f32p, C.c_void_p, sz, f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p,
-                                                f32p, C.c_void_p, sz, cint, cint, cint, cint, cint, cint, cint, stream_t]),
-    "dcpt_conv1x1_pool_relu_fwd_bf16_packed": (cint, [f32p, f32p, C.c_void_p, sz, f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint, cint,
-                                                      stream_t]),
-    "dcpt_conv1x1_pool_relu_bwd_bf16_packed": (cint, [f32p, f32p, f32p, C.c_void_p, sz, f32p, f32p, f32p, C.c_void_p, sz, cint, cint, cint,
-                                                      cint, cint, stream_t]),
     "dcpt_conv3x3_in_fwd_bf16": (cint, [f32p, f32p, f32p, f32p, cint, cint, cint, cint, cint, stream_t]),
     "dcpt_conv3x3_in_bwd_bf16": (cint, [f32p, f32p, f32p, f32p, f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint, cint, stream_t]),
     "dcpt_conv3x3_out_fwd_bf16": (cint, [f32p, f32p, f32p, f32p, f32p, cint, cint, cint, cint, cint, stream_t]),
     "dcpt_conv3x3_out_bwd_bf16": (cint, [f32p, f32p, f32p, f32p, f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint, cint, stream_t]),
     "dcpt_down2x2_bf16_ws_bytes": (sz, [cint, cint, cint, cint, cint]),
     "dcpt_down2x2_fwd_bf16": (cint, [f32p, f32p, f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint, stream_t]),
-    "dcpt_down2x2_bwd_bf16": (cint, [f32p, f32p, f32p, f32p, f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint, stream_t]),
-    "dcpt_down2x2_bwd_acc_bf16": (cint, [f32p, f32p, f32p, f32p, f32p, f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint, stream_t]),
+    "dcpt_down2x2_bwd_bf16": (cint, [f32p, f32p, f32p, f32p, f32p, f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint, stream_t]),
     "dcpt_up_ps_bf16_ws_bytes": (sz, [cint, cint, cint, cint, cint]),
     "dcpt_up_ps_fwd_bf16": (cint, [f32p, f32p, f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint, stream_t]),
     "dcpt_up_ps_bwd_bf16": (cint, [f32p, f32p, f32p, f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint, stream_t]),
@@ -197,8 +183,7 @@ SIGNATURES = {
     "dcpt_conv3x3_out_bwd": (cint, [f32p, f32p, f32p, f32p, f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint, cint, stream_t]),
     "dcpt_down2x2_ws_bytes": (sz, [cint, cint, cint, cint, cint]),
     "dcpt_down2x2_fwd": (cint, [f32p, f32p, f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint, stream_t]),
-    "dcpt_down2x2_bwd": (cint, [f32p, f32p, f32p, f32p, f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint, stream_t]),
-    "dcpt_down2x2_bwd_acc": (cint, [f32p, f32p, f32p, f32p, f32p, f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint, stream_t]),
+    "dcpt_down2x2_bwd": (cint, [f32p, f32p, f32p, f32p, f32p, f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint, stream_t]),
     "dcpt_up_ps_ws_bytes": (sz, [cint, cint, cint, cint, cint]),
     "dcpt_up_ps_fwd": (cint, [f32p, f32p, f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint, stream_t]),
     "dcpt_up_ps_bwd": (cint, [f32p, f32p, f32p, f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint, stream_t]),
@@ -206,10 +191,8 @@ SIGNATURES = {
     "dcpt_conv_ln_ws_bytes": (sz, [cint, cint, cint, cint, cint, cint, cint]),
     "dcpt_conv_ln_fwd": (cint, [f32p, f32p, f32p, f32p, f32p, cint, f32p, f32p, f32p, f32p, C.c_void_p, sz, cint, cint, cint,
                                 cint, cint, cint, stream_t]),
-    "dcpt_conv_ln_bwd": (cint, [f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, C.c_void_p, sz,
+    "dcpt_conv_ln_bwd": (cint, [f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, C.c_void_p, sz,
                                 cint, cint, cint, cint, cint, cint, cint, stream_t]),
-    "dcpt_conv_ln_bwd_acc": (cint, [f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, C.c_void_p, sz,
-                                    cint, cint, cint, cint, cint, cint, cint, stream_t]),
     "dcpt_conv1x1_pool_relu_ws_bytes": (sz, [cint, cint, cint, cint, cint, cint]),
     "dcpt_conv1x1_pool_relu_fwd": (cint, [f32p, f32p, f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint, cint, stream_t]),
     "dcpt_conv1x1_pool_relu_bwd": (cint, [f32p, f32p, f32p, f32p, f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint, cint,
@@ -327,8 +310,6 @@ SIGNATURES = {
     "dcpt_grad_norm_ws_bytes": (sz, [cint, C.POINTER(C.c_int64)]),
     "dcpt_grad_norm": (cint, [cint, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_float, C.c_void_p, sz, f32p, stream_t]),
     "dcpt_allreduce_flat": (cint, [f32p, sz, C.c_void_p, C.c_float, stream_t]),
-    "dcpt_nchw_to_nhwc": (cint, [f32p, f32p, cint, cint, cint, stream_t]),
-    "dcpt_nhwc_to_nchw": (cint, [f32p, f32p, cint, cint, cint, stream_t]),
 }
 
 

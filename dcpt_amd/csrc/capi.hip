@@ -16,7 +16,7 @@ void dcpt_set_error(const char* fmt, ...) {
 }
 
 extern "C" const char* dcpt_last_error(void) { return g_err; }
-extern "C" int dcpt_abi_version(void) { return 15; }   // 15: + dcpt_bottleneck_fwd_bf16 / _bwd_bf16 (the head's BottleneckBlock in one call, LayerNorms in GEMM epilogues), dcpt_trace_enable / dcpt_trace_read (launch trace for the tests); 14: + dcpt_conv_wpack_bf16_multi and the *_packed forms of the bf16 head's conv entry points (cached operand copies of the weights); 13: + dcpt_conv_ln_bwd_acc / _bf16 (the BottleneckBlock's shortcut gradient summed in the data-gradient GEMM), dcpt_down2x2_bwd_acc / _bf16 (the skip connection's gradient summed in the down layer's scatter epilogue); 12: + dcpt_adamw_step (multi-tensor AdamW); 11: + dcpt_mix_*_bf16 / dcpt_meanpool_fc_*_bf16 (the all-bf16 head without cast passes), dcpt_nafblock_bf16_fused_ffn may return 2 (chain kernel of the wide levels); 10: + dcpt_nafblock_wpack_bf16_multi; 9: + dcpt_conv1x1_wgrad_bf16 (grouped 256 x 256-tile weight-gradient GEMM + finisher); 8: + dcpt_nafblock_fused_ffn / dcpt_nafblock_bf16_fused_ffn (fused 1 x 1 chains of the narrowest level; saved tensors that become optional); 7: + per-block packed weights for the bf16 NAFBlock (dcpt_nafblock_wpack_bf16, *_packed); 6: + bf16-storage intro / ending / down / up layers; 5: + bf16-storage classifier-head groups; 4: + bf16-storage NAFBlock and casts; 3: + dcpt_allreduce_flat; 2: dcpt_nafblock_saved / mdta / gdfn saved structs carry the kept LN (and gate) tensors
+extern "C" int dcpt_abi_version(void) { return 16; }   // 16: one entry point per op, optional operands are NULL -- REMOVED: the *_packed and *_acc names (dcpt_conv_ln_fwd_bf16_packed, dcpt_conv_ln_bwd_acc / _acc_bf16 / _acc_bf16_packed, dcpt_conv1x1_pool_relu_fwd / _bwd_bf16_packed, dcpt_down2x2_bwd_acc / _acc_bf16, dcpt_nafblock_fwd / _bwd_bf16_packed) and dcpt_nchw_to_nhwc / dcpt_nhwc_to_nchw; CHANGED SIGNATURE: the plain names now take the full argument list of the removed form (dcpt_conv_ln_fwd_bf16, dcpt_conv_ln_bwd_bf16, dcpt_conv1x1_pool_relu_fwd_bf16 / _bwd_bf16, dcpt_nafblock_fwd_bf16 / _bwd_bf16: w/ the cached pack, NULL = pack in the call; dcpt_conv_ln_bwd, dcpt_conv_ln_bwd_bf16, dcpt_down2x2_bwd / _bf16: dx_add, NULL = none); 15: + dcpt_bottleneck_fwd_bf16 / _bwd_bf16 (the head's BottleneckBlock in one call, LayerNorms in GEMM epilogues), dcpt_trace_enable / dcpt_trace_read (launch trace for the tests); 14: + dcpt_conv_wpack_bf16_multi and the *_packed forms of the bf16 head's conv entry points (cached operand copies of the weights); 13: + dcpt_conv_ln_bwd_acc / _bf16 (the BottleneckBlock's shortcut gradient summed in the data-gradient GEMM), dcpt_down2x2_bwd_acc / _bf16 (the skip connection's gradient summed in the down layer's scatter epilogue); 12: + dcpt_adamw_step (multi-tensor AdamW); 11: + dcpt_mix_*_bf16 / dcpt_meanpool_fc_*_bf16 (the all-bf16 head without cast passes), dcpt_nafblock_bf16_fused_ffn may return 2 (chain kernel of the wide levels); 10: + dcpt_nafblock_wpack_bf16_multi; 9: + dcpt_conv1x1_wgrad_bf16 (grouped 256 x 256-tile weight-gradient GEMM + finisher); 8: + dcpt_nafblock_fused_ffn / dcpt_nafblock_bf16_fused_ffn (fused 1 x 1 chains of the narrowest level; saved tensors that become optional); 7: + per-block packed weights for the bf16 NAFBlock (dcpt_nafblock_wpack_bf16, *_packed); 6: + bf16-storage intro / ending / down / up layers; 5: + bf16-storage classifier-head groups; 4: + bf16-storage NAFBlock and casts; 3: + dcpt_allreduce_flat; 2: dcpt_nafblock_saved / mdta / gdfn saved structs carry the kept LN (and gate) tensors
 
 // ---------------------------------------------------------------------------------------------
 extern "C" int dcpt_ln2d_fwd(const float* x, const float* weight, const float* bias, float* y, float* mu, float* rstd,
@@ -148,13 +148,8 @@ extern "C" int dcpt_down2x2_fwd(const float* x, const float* w, const float* bia
     return launch_gemm_nt(g, A_GATHER, E_BIAS, s);
 }
 
-extern "C" int dcpt_down2x2_bwd(const float* dy, const float* x, const float* w, float* dx, float* dw, float* dbias, void* ws,
-                                size_t ws_bytes, int B, int H, int W, int C, dcpt_stream_t stream) {
-    return dcpt_down2x2_bwd_acc(dy, x, w, nullptr, dx, dw, dbias, ws, ws_bytes, B, H, W, C, stream);
-}
-
-extern "C" int dcpt_down2x2_bwd_acc(const float* dy, const float* x, const float* w, const float* dx_add, float* dx, float* dw, float* dbias,
-                                    void* ws, size_t ws_bytes, int B, int H, int W, int C, dcpt_stream_t stream) {
+extern "C" int dcpt_down2x2_bwd(const float* dy, const float* x, const float* w, const float* dx_add, float* dx, float* dw, float* dbias,
+                                void* ws, size_t ws_bytes, int B, int H, int W, int C, dcpt_stream_t stream) {
     hipStream_t s = (hipStream_t)stream;
     DCPT_CHECK_ARG(dy && x && w && dx && dw && dbias, "down2x2_bwd: null argument");
     DCPT_CHECK_ARG(H % 2 == 0 && W % 2 == 0 && C % 4 == 0, "down2x2_bwd: bad shape");
@@ -287,13 +282,6 @@ extern "C" int dcpt_fused_bias_act(const float* x, const float* bias, const floa
                                                                                      grad, alpha, scale);
     DCPT_CHECK_LAUNCH("fused_bias_act");
     return DCPT_OK;
-}
-
-extern "C" int dcpt_nchw_to_nhwc(const float* x, float* y, int B, int C, int HW, dcpt_stream_t stream) {
-    return launch_nchw_to_nhwc(x, y, B, C, HW, (hipStream_t)stream);
-}
-extern "C" int dcpt_nhwc_to_nchw(const float* x, float* y, int B, int C, int HW, dcpt_stream_t stream) {
-    return launch_nhwc_to_nchw(x, y, B, C, HW, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -315,28 +315,6 @@ __global__ __launch_bounds__(256) void nchw_channel_sum_kernel(const float* __re
     if (tid == 0) out[(stage == 0) ? (int64_t)c * nsl + j : c] = red[0];
 }
 
-// tiled transposes between [B][C][HW] and [B][HW][C]
-__global__ __launch_bounds__(256) void layout_transpose_kernel(const float* __restrict__ x, float* __restrict__ y, int R,
-                                                               int Cc) {
-    // per batch: in [R][Cc] -> out [Cc][R]
-    __shared__ float tile[32][33];
-    const int b = blockIdx.z;
-    const float* xi = x + (int64_t)b * R * Cc;
-    float* yo = y + (int64_t)b * R * Cc;
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;  // 32 x 8
-    const int r0 = blockIdx.y * 32, c0 = blockIdx.x * 32;
-    for (int i = ty; i < 32; i += 8) {
-        const int r = r0 + i, c = c0 + tx;
-        tile[i][tx] = (r < R && c < Cc) ? xi[(int64_t)r * Cc + c] : 0.f;
-    }
-    __syncthreads();
-    for (int i = ty; i < 32; i += 8) {
-        const int c = c0 + i, r = r0 + tx;
-        if (r < R && c < Cc) yo[(int64_t)c * R + r] = tile[tx][i];
-    }
-}
-
-
 // ================================================================================================================================
 // MFMA forms of the three edge kernels (round 5).  The VALU kernels above spend 27 FMAs per feature element (K = Cs * 9 taps) and, with packed
 // fp32 off (build.py), run at 2.5 - 4 x their HBM time: 237 / 409 / 256 us (s2b / b2s / wgrad, B = 32, 256 x 256, Cb = 64, fp32) against
@@ -906,20 +884,5 @@ int launch_nchw_channel_sum(const float* x, float* part, float* out, int B, int 
     DCPT_CHECK_LAUNCH("nchw_channel_sum");
     nchw_channel_sum_kernel<<<dim3(C, 1), dim3(256), 0, s>>>(part, out, B, C, HW, 128, 1);
     DCPT_CHECK_LAUNCH("nchw_channel_sum2");
-    return DCPT_OK;
-}
-
-int launch_nchw_to_nhwc(const float* x, float* y, int B, int C, int HW, hipStream_t s) {
-    // in [C][HW] -> out [HW][C]
-    DCPT_CHECK_ARG(B <= 65535, "nchw_to_nhwc: B too large");
-    layout_transpose_kernel<<<dim3(cdiv(HW, 32), cdiv(C, 32), B), dim3(256), 0, s>>>(x, y, C, HW);
-    DCPT_CHECK_LAUNCH("nchw_to_nhwc");
-    return DCPT_OK;
-}
-
-int launch_nhwc_to_nchw(const float* x, float* y, int B, int C, int HW, hipStream_t s) {
-    DCPT_CHECK_ARG(B <= 65535, "nhwc_to_nchw: B too large");
-    layout_transpose_kernel<<<dim3(cdiv(C, 32), cdiv(HW, 32), B), dim3(256), 0, s>>>(x, y, HW, C);
-    DCPT_CHECK_LAUNCH("nhwc_to_nchw");
     return DCPT_OK;
 }

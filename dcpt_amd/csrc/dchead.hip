@@ -426,10 +426,10 @@ extern "C" int dcpt_conv_ln_fwd(const float* x, const float* w, const float* lnw
     return launch_ln_act_fwd(z, lnw, lnb, res, relu, y, mu, rstd, (int64_t)B * H * W, Cout, 1e-6f, s);  // eps: degrad_classify_arch.py:24
 }
 
-extern "C" int dcpt_conv_ln_bwd_acc(const float* dy, const float* x, const float* w, const float* lnw, const float* z, const float* y,
-                                    const float* mu, const float* rstd, const float* dx_add, float* dx, float* dw, float* dlnw, float* dlnb,
-                                    float* dres, void* ws, size_t ws_bytes, int B, int H, int W, int Cin, int Cout, int ksize, int relu,
-                                    dcpt_stream_t stream) {
+extern "C" int dcpt_conv_ln_bwd(const float* dy, const float* x, const float* w, const float* lnw, const float* z, const float* y,
+                                const float* mu, const float* rstd, const float* dx_add, float* dx, float* dw, float* dlnw, float* dlnb,
+                                float* dres, void* ws, size_t ws_bytes, int B, int H, int W, int Cin, int Cout, int ksize, int relu,
+                                dcpt_stream_t stream) {
     hipStream_t s = (hipStream_t)stream;
     DCPT_CHECK_ARG(dy && x && w && lnw && z && mu && rstd && dw && dlnw && dlnb, "conv_ln_bwd: null argument");
     DCPT_CHECK_ARG(!relu || y, "conv_ln_bwd: relu needs the saved output y");
@@ -445,13 +445,6 @@ extern "C" int dcpt_conv_ln_bwd_acc(const float* dy, const float* x, const float
     DCPT_TRY(launch_ln_act_bwd(dy, z, mu, rstd, lnw, nullptr, relu ? y : nullptr, dres, cw.dz, cw.lnpart, cw.ln_nblk, M, Cout, s));
     DCPT_TRY(launch_colpart_reduce(cw.lnpart, cw.ln_nblk, 3, Cout, dlnw, dlnb, nullptr, s));
     return conv_bwd(cw.dz, x, w, dx, dw, cw, B, H, W, Cin, Cout, ksize, s, dx_add);
-}
-
-extern "C" int dcpt_conv_ln_bwd(const float* dy, const float* x, const float* w, const float* lnw, const float* z, const float* y,
-                                const float* mu, const float* rstd, float* dx, float* dw, float* dlnw, float* dlnb, float* dres,
-                                void* ws, size_t ws_bytes, int B, int H, int W, int Cin, int Cout, int ksize, int relu,
-                                dcpt_stream_t stream) {
-    return dcpt_conv_ln_bwd_acc(dy, x, w, lnw, z, y, mu, rstd, nullptr, dx, dw, dlnw, dlnb, dres, ws, ws_bytes, B, H, W, Cin, Cout, ksize, relu, stream);
 }
 
 extern "C" size_t dcpt_conv_ws_bytes(int B, int H, int W, int Cin, int Cout, int ksize, int backward) {

@@ -277,9 +277,9 @@ extern "C" size_t dcpt_conv_ln_bf16_ws_bytes(int B, int H, int W, int Cin, int C
     return conv_layout(B, H, W, Cin, Cout, ksize, backward, true, nullptr, 0, nullptr);
 }
 
-extern "C" int dcpt_conv_ln_fwd_bf16_packed(const uint16_t* x, const float* w, const void* wpacked, size_t wpacked_bytes, const float* lnw,
-                                            const float* lnb, const uint16_t* res, int relu, uint16_t* z, uint16_t* y, float* mu, float* rstd,
-                                            void* ws, size_t ws_bytes, int B, int H, int W, int Cin, int Cout, int ksize, dcpt_stream_t stream) {
+extern "C" int dcpt_conv_ln_fwd_bf16(const uint16_t* x, const float* w, const void* wpacked, size_t wpacked_bytes, const float* lnw,
+                                     const float* lnb, const uint16_t* res, int relu, uint16_t* z, uint16_t* y, float* mu, float* rstd,
+                                     void* ws, size_t ws_bytes, int B, int H, int W, int Cin, int Cout, int ksize, dcpt_stream_t stream) {
     hipStream_t s = (hipStream_t)stream;
     DCPT_CHECK_ARG(x && (w || wpacked) && lnw && lnb && z && y && mu && rstd, "conv_ln_fwd_bf16: null argument");
     DCPT_TRY(pk_check(wpacked, wpacked_bytes, Cin, Cout, ksize, "conv_ln_fwd_bf16"));
@@ -293,17 +293,10 @@ extern "C" int dcpt_conv_ln_fwd_bf16_packed(const uint16_t* x, const float* w, c
     return conv_ln_fwd_group(x, w, wpacked, lnw, lnb, res, relu, z, y, mu, rstd, cw, B, H, W, Cin, Cout, ksize, s);
 }
 
-extern "C" int dcpt_conv_ln_fwd_bf16(const uint16_t* x, const float* w, const float* lnw, const float* lnb, const uint16_t* res, int relu,
-                                     uint16_t* z, uint16_t* y, float* mu, float* rstd, void* ws, size_t ws_bytes, int B, int H, int W, int Cin,
-                                     int Cout, int ksize, dcpt_stream_t stream) {
-    DCPT_CHECK_ARG(w, "conv_ln_fwd_bf16: null argument");
-    return dcpt_conv_ln_fwd_bf16_packed(x, w, nullptr, 0, lnw, lnb, res, relu, z, y, mu, rstd, ws, ws_bytes, B, H, W, Cin, Cout, ksize, stream);
-}
-
-extern "C" int dcpt_conv_ln_bwd_acc_bf16_packed(const uint16_t* dy, const uint16_t* x, const float* w, const void* wpacked, size_t wpacked_bytes,
-                                                const float* lnw, const uint16_t* z, const uint16_t* y, const float* mu, const float* rstd,
-                                                const uint16_t* dx_add, uint16_t* dx, float* dw, float* dlnw, float* dlnb, uint16_t* dres, void* ws,
-                                                size_t ws_bytes, int B, int H, int W, int Cin, int Cout, int ksize, int relu, dcpt_stream_t stream) {
+extern "C" int dcpt_conv_ln_bwd_bf16(const uint16_t* dy, const uint16_t* x, const float* w, const void* wpacked, size_t wpacked_bytes,
+                                     const float* lnw, const uint16_t* z, const uint16_t* y, const float* mu, const float* rstd,
+                                     const uint16_t* dx_add, uint16_t* dx, float* dw, float* dlnw, float* dlnb, uint16_t* dres, void* ws,
+                                     size_t ws_bytes, int B, int H, int W, int Cin, int Cout, int ksize, int relu, dcpt_stream_t stream) {
     hipStream_t s = (hipStream_t)stream;
     DCPT_CHECK_ARG(dy && x && (w || wpacked) && lnw && z && mu && rstd && dw && dlnw && dlnb, "conv_ln_bwd_bf16: null argument");
     DCPT_TRY(pk_check(wpacked, wpacked_bytes, Cin, Cout, ksize, "conv_ln_bwd_bf16"));
@@ -320,21 +313,6 @@ extern "C" int dcpt_conv_ln_bwd_acc_bf16_packed(const uint16_t* dy, const uint16
     DCPT_TRY(launch_ln_act_bwd_bf16(dy, z, mu, rstd, lnw, relu ? y : nullptr, dres, cw.dz, cw.lnpart, cw.ln_nblk, M, Cout, s));
     const FinCols ln{cw.lnpart, dlnw, dlnb, cw.ln_nblk, 2, Cout, 0};
     return conv_bwd(cw.dz, x, w, dx, dw, cw, B, H, W, Cin, Cout, ksize, s, &ln, dx_add, wpacked);
-}
-
-extern "C" int dcpt_conv_ln_bwd_acc_bf16(const uint16_t* dy, const uint16_t* x, const float* w, const float* lnw, const uint16_t* z, const uint16_t* y,
-                                         const float* mu, const float* rstd, const uint16_t* dx_add, uint16_t* dx, float* dw, float* dlnw, float* dlnb,
-                                         uint16_t* dres, void* ws, size_t ws_bytes, int B, int H, int W, int Cin, int Cout, int ksize, int relu,
-                                         dcpt_stream_t stream) {
-    DCPT_CHECK_ARG(w, "conv_ln_bwd_bf16: null argument");
-    return dcpt_conv_ln_bwd_acc_bf16_packed(dy, x, w, nullptr, 0, lnw, z, y, mu, rstd, dx_add, dx, dw, dlnw, dlnb, dres, ws, ws_bytes, B, H, W, Cin,
-                                            Cout, ksize, relu, stream);
-}
-
-extern "C" int dcpt_conv_ln_bwd_bf16(const uint16_t* dy, const uint16_t* x, const float* w, const float* lnw, const uint16_t* z, const uint16_t* y,
-                                     const float* mu, const float* rstd, uint16_t* dx, float* dw, float* dlnw, float* dlnb, uint16_t* dres,
-                                     void* ws, size_t ws_bytes, int B, int H, int W, int Cin, int Cout, int ksize, int relu, dcpt_stream_t stream) {
-    return dcpt_conv_ln_bwd_acc_bf16(dy, x, w, lnw, z, y, mu, rstd, nullptr, dx, dw, dlnw, dlnb, dres, ws, ws_bytes, B, H, W, Cin, Cout, ksize, relu, stream);
 }
 
 // ---- the whole BottleneckBlock in one call (ABI 15) -------------------------------------------------------------------------------------
@@ -459,9 +437,9 @@ extern "C" size_t dcpt_conv1x1_pool_relu_bf16_ws_bytes(int B, int H, int W, int 
     return conv_layout(B, H, W, Cin, Cout, 1, backward, false, nullptr, 0, nullptr);
 }
 
-extern "C" int dcpt_conv1x1_pool_relu_fwd_bf16_packed(const uint16_t* x, const float* w, const void* wpacked, size_t wpacked_bytes, uint16_t* z,
-                                                      uint16_t* y, void* ws, size_t ws_bytes, int B, int H, int W, int Cin, int Cout,
-                                                      dcpt_stream_t stream) {
+extern "C" int dcpt_conv1x1_pool_relu_fwd_bf16(const uint16_t* x, const float* w, const void* wpacked, size_t wpacked_bytes, uint16_t* z,
+                                               uint16_t* y, void* ws, size_t ws_bytes, int B, int H, int W, int Cin, int Cout,
+                                               dcpt_stream_t stream) {
     hipStream_t s = (hipStream_t)stream;
     DCPT_CHECK_ARG(x && (w || wpacked) && z && y, "conv1x1_pool_relu_fwd_bf16: null argument");
     DCPT_TRY(pk_check(wpacked, wpacked_bytes, Cin, Cout, 1, "conv1x1_pool_relu_fwd_bf16"));
@@ -478,15 +456,9 @@ extern "C" int dcpt_conv1x1_pool_relu_fwd_bf16_packed(const uint16_t* x, const f
     return DCPT_OK;
 }
 
-extern "C" int dcpt_conv1x1_pool_relu_fwd_bf16(const uint16_t* x, const float* w, uint16_t* z, uint16_t* y, void* ws, size_t ws_bytes, int B, int H,
-                                               int W, int Cin, int Cout, dcpt_stream_t stream) {
-    DCPT_CHECK_ARG(w, "conv1x1_pool_relu_fwd_bf16: null argument");
-    return dcpt_conv1x1_pool_relu_fwd_bf16_packed(x, w, nullptr, 0, z, y, ws, ws_bytes, B, H, W, Cin, Cout, stream);
-}
-
-extern "C" int dcpt_conv1x1_pool_relu_bwd_bf16_packed(const uint16_t* dy, const uint16_t* x, const float* w, const void* wpacked, size_t wpacked_bytes,
-                                                      const uint16_t* z, uint16_t* dx, float* dw, void* ws, size_t ws_bytes, int B, int H, int W,
-                                                      int Cin, int Cout, dcpt_stream_t stream) {
+extern "C" int dcpt_conv1x1_pool_relu_bwd_bf16(const uint16_t* dy, const uint16_t* x, const float* w, const void* wpacked, size_t wpacked_bytes,
+                                               const uint16_t* z, uint16_t* dx, float* dw, void* ws, size_t ws_bytes, int B, int H, int W,
+                                               int Cin, int Cout, dcpt_stream_t stream) {
     hipStream_t s = (hipStream_t)stream;
     DCPT_CHECK_ARG(dy && x && (w || wpacked) && z && dx && dw, "conv1x1_pool_relu_bwd_bf16: null argument");
     DCPT_TRY(pk_check(wpacked, wpacked_bytes, Cin, Cout, 1, "conv1x1_pool_relu_bwd_bf16"));
@@ -500,12 +472,6 @@ extern "C" int dcpt_conv1x1_pool_relu_bwd_bf16_packed(const uint16_t* dy, const 
     pool_relu_bwd_bf16_kernel<<<dim3(grid_for((int64_t)B * (H / 2) * (W / 2) * (Cout / 4))), dim3(256), 0, s>>>(z, dy, cw.dz, B, H, W, Cout);
     DCPT_CHECK_LAUNCH("pool_relu_bwd_bf16");
     return conv_bwd(cw.dz, x, w, dx, dw, cw, B, H, W, Cin, Cout, 1, s, nullptr, nullptr, wpacked);
-}
-
-extern "C" int dcpt_conv1x1_pool_relu_bwd_bf16(const uint16_t* dy, const uint16_t* x, const float* w, const uint16_t* z, uint16_t* dx, float* dw,
-                                               void* ws, size_t ws_bytes, int B, int H, int W, int Cin, int Cout, dcpt_stream_t stream) {
-    DCPT_CHECK_ARG(w, "conv1x1_pool_relu_bwd_bf16: null argument");
-    return dcpt_conv1x1_pool_relu_bwd_bf16_packed(dy, x, w, nullptr, 0, z, dx, dw, ws, ws_bytes, B, H, W, Cin, Cout, stream);
 }
 
 // ---- the two operand images of n convs in a few launches (ABI 14) ----

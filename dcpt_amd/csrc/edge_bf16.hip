@@ -79,13 +79,8 @@ extern "C" int dcpt_down2x2_fwd_bf16(const uint16_t* x, const float* w, const fl
     return launch_gemm_nt_bf16(g, EB_BIAS, s);
 }
 
-extern "C" int dcpt_down2x2_bwd_bf16(const uint16_t* dy, const uint16_t* x, const float* w, uint16_t* dx, float* dw, float* dbias, void* ws,
-                                     size_t ws_bytes, int B, int H, int W, int C, dcpt_stream_t stream) {
-    return dcpt_down2x2_bwd_acc_bf16(dy, x, w, nullptr, dx, dw, dbias, ws, ws_bytes, B, H, W, C, stream);
-}
-
-extern "C" int dcpt_down2x2_bwd_acc_bf16(const uint16_t* dy, const uint16_t* x, const float* w, const uint16_t* dx_add, uint16_t* dx, float* dw,
-                                         float* dbias, void* ws, size_t ws_bytes, int B, int H, int W, int C, dcpt_stream_t stream) {
+extern "C" int dcpt_down2x2_bwd_bf16(const uint16_t* dy, const uint16_t* x, const float* w, const uint16_t* dx_add, uint16_t* dx, float* dw,
+                                     float* dbias, void* ws, size_t ws_bytes, int B, int H, int W, int C, dcpt_stream_t stream) {
     hipStream_t s = (hipStream_t)stream;
     DCPT_CHECK_ARG(dy && x && w && dx && dw && dbias, "down2x2_bwd_bf16: null argument");
     DCPT_CHECK_ARG(B > 0 && H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0 && C % 8 == 0, "down2x2_bwd_bf16: bad shape");

@@ -138,9 +138,6 @@ int launch_conv3x3_wgrad(const float* big, const float* small, float* part, int 
                          int W, int Cs, int Cb, int omode, hipStream_t s);
 // out[c] = sum_{b,h,w} x[b][c][h][w]   (NCHW, tiny C); part: [C][128] scratch
 int launch_nchw_channel_sum(const float* x, float* part, float* out, int B, int C, int HW, hipStream_t s);
-// layout converters for arbitrary C
-int launch_nchw_to_nhwc(const float* x, float* y, int B, int C, int HW, hipStream_t s);
-int launch_nhwc_to_nchw(const float* x, float* y, int B, int C, int HW, hipStream_t s);
 
 // restormer.hip: fp32 pieces of the MDTA / GDFN blocks shared with their bf16-storage form (restormer_bf16.hip)
 int launch_mdta_sq_norm(const float* part, int nblk, float* nrm, int B, int C2, hipStream_t s);

@@ -217,7 +217,7 @@ bool shape_ok(int B, int H, int W, int C) { return B > 0 && B <= 65535 && H > 0 
 // The operand copies of a block's weights that depend on the PARAMETERS only (not on activations): bf16 [N][K] copies for the forward
 // GEMMs, transposed (and beta / gamma-scaled) copies for the data-gradient GEMMs, the depthwise taps as [9][2C] fp32.  A caller that
 // keeps this buffer per block and refreshes it when the parameters change (once per optimizer step) saves the per-call packs:
-// 5 launches per block and step (dcpt_nafblock_wpack_bf16 / *_packed entry points).
+// 5 launches per block and step (dcpt_nafblock_wpack_bf16 and the `packed` argument of the entry points).
 struct PackB {
     bf16_t *W1, *W4, *W5, *wT5, *wT4, *wT3, *wT1, *W3, *Wf, *Wf1, *WfT3;
     float* w2p;
@@ -453,14 +453,10 @@ static int nafblock_fwd_bf16_impl(const dcpt_nafblock_params* p, const uint16_t*
     return fwd_ffn_bf16(p, sv->y, out, t, M, C, s);
 }
 
-extern "C" int dcpt_nafblock_fwd_bf16(const dcpt_nafblock_params* p, const uint16_t* inp, uint16_t* out, const dcpt_nafblock_saved_bf16* sv,
-                                      void* ws, size_t ws_bytes, int B, int H, int W, int C, dcpt_stream_t stream) {
-    return nafblock_fwd_bf16_impl(p, inp, out, sv, ws, ws_bytes, B, H, W, C, nullptr, 0, stream);
-}
-extern "C" int dcpt_nafblock_fwd_bf16_packed(const dcpt_nafblock_params* p, const void* packed, size_t packed_bytes, const uint16_t* inp,
-                                             uint16_t* out, const dcpt_nafblock_saved_bf16* sv, void* ws, size_t ws_bytes, int B, int H, int W,
-                                             int C, dcpt_stream_t stream) {
-    DCPT_CHECK_ARG(packed, "nafblock_fwd_bf16_packed: null packed weights");
+// packed == NULL: the block's operand copies are packed into the workspace in this call
+extern "C" int dcpt_nafblock_fwd_bf16(const dcpt_nafblock_params* p, const void* packed, size_t packed_bytes, const uint16_t* inp,
+                                      uint16_t* out, const dcpt_nafblock_saved_bf16* sv, void* ws, size_t ws_bytes, int B, int H, int W,
+                                      int C, dcpt_stream_t stream) {
     return nafblock_fwd_bf16_impl(p, inp, out, sv, ws, ws_bytes, B, H, W, C, packed, packed_bytes, stream);
 }
 
@@ -749,15 +745,9 @@ static int nafblock_bwd_bf16_impl(const dcpt_nafblock_params* p, const dcpt_nafb
     return DCPT_OK;
 }
 
-extern "C" int dcpt_nafblock_bwd_bf16(const dcpt_nafblock_params* p, const dcpt_nafblock_grads* gr, const uint16_t* inp,
-                                      const dcpt_nafblock_saved_bf16* sv, const uint16_t* dout, uint16_t* dinp, void* ws, size_t ws_bytes, int B,
-                                      int H, int W, int C, dcpt_stream_t stream) {
-    return nafblock_bwd_bf16_impl(p, gr, inp, sv, dout, dinp, ws, ws_bytes, B, H, W, C, nullptr, 0, stream);
-}
-extern "C" int dcpt_nafblock_bwd_bf16_packed(const dcpt_nafblock_params* p, const void* packed, size_t packed_bytes, const dcpt_nafblock_grads* gr,
-                                             const uint16_t* inp, const dcpt_nafblock_saved_bf16* sv, const uint16_t* dout, uint16_t* dinp, void* ws,
-                                             size_t ws_bytes, int B, int H, int W, int C, dcpt_stream_t stream) {
-    DCPT_CHECK_ARG(packed, "nafblock_bwd_bf16_packed: null packed weights");
+extern "C" int dcpt_nafblock_bwd_bf16(const dcpt_nafblock_params* p, const void* packed, size_t packed_bytes, const dcpt_nafblock_grads* gr,
+                                      const uint16_t* inp, const dcpt_nafblock_saved_bf16* sv, const uint16_t* dout, uint16_t* dinp, void* ws,
+                                      size_t ws_bytes, int B, int H, int W, int C, dcpt_stream_t stream) {
     return nafblock_bwd_bf16_impl(p, gr, inp, sv, dout, dinp, ws, ws_bytes, B, H, W, C, packed, packed_bytes, stream);
 }
 

@@ -356,12 +356,8 @@ class _NAFBlockBf16Fn(torch.autograd.Function):
         ps = NafBlockParams(*[p.data_ptr() for p in params])
         sv = _saved_bf16(t1, v, acts, stats, sca, infer)
         ws = _workspace(dev, lib.dcpt_nafblock_fwd_bf16_ws_bytes(B, H, W, Cc))
-        if packed is None:
-            check(lib.dcpt_nafblock_fwd_bf16(C.byref(ps), inp.data_ptr(), out.data_ptr(), C.byref(sv), ws.data_ptr(), ws.numel(),
-                                             B, H, W, Cc, _stream(dev)), "dcpt_nafblock_fwd_bf16")
-        else:
-            check(lib.dcpt_nafblock_fwd_bf16_packed(C.byref(ps), packed.data_ptr(), packed.numel(), inp.data_ptr(), out.data_ptr(), C.byref(sv),
-                                                    ws.data_ptr(), ws.numel(), B, H, W, Cc, _stream(dev)), "dcpt_nafblock_fwd_bf16_packed")
+        check(lib.dcpt_nafblock_fwd_bf16(C.byref(ps), _p(packed), 0 if packed is None else packed.numel(), inp.data_ptr(), out.data_ptr(),
+                                         C.byref(sv), ws.data_ptr(), ws.numel(), B, H, W, Cc, _stream(dev)), "dcpt_nafblock_fwd_bf16")
         ctx.packed = packed   # (a plain byte buffer owned by the module; the backward of THIS forward reads the same pack)
         if not nograd:
             ctx.save_for_backward(inp, t1, v, acts, stats, sca, *params)
@@ -381,13 +377,9 @@ class _NAFBlockBf16Fn(torch.autograd.Function):
         sv = _saved_bf16(t1, v, acts, stats, sca, False)
         ws = _workspace(dev, lib.dcpt_nafblock_bwd_bf16_ws_bytes(B, H, W, Cc))
         packed = ctx.packed
-        if packed is None:
-            check(lib.dcpt_nafblock_bwd_bf16(C.byref(ps), C.byref(gs), inp.data_ptr(), C.byref(sv), dout.data_ptr(), dinp.data_ptr(),
-                                             ws.data_ptr(), ws.numel(), B, H, W, Cc, _stream(dev)), "dcpt_nafblock_bwd_bf16")
-        else:
-            check(lib.dcpt_nafblock_bwd_bf16_packed(C.byref(ps), packed.data_ptr(), packed.numel(), C.byref(gs), inp.data_ptr(), C.byref(sv),
-                                                    dout.data_ptr(), dinp.data_ptr(), ws.data_ptr(), ws.numel(), B, H, W, Cc, _stream(dev)),
-                  "dcpt_nafblock_bwd_bf16_packed")
+        check(lib.dcpt_nafblock_bwd_bf16(C.byref(ps), _p(packed), 0 if packed is None else packed.numel(), C.byref(gs), inp.data_ptr(),
+                                         C.byref(sv), dout.data_ptr(), dinp.data_ptr(), ws.data_ptr(), ws.numel(), B, H, W, Cc, _stream(dev)),
+              "dcpt_nafblock_bwd_bf16")
         return (dinp, None, None, *grads)
 
 
@@ -607,6 +599,17 @@ def _pk(packed, weight):
     return buf.data_ptr(), buf.numel()
 
 
+def _pk_buf(packed, weight):
+    """the buffer behind _pk (refreshed if stale), or None without a cache: what a node keeps for the backward of THIS forward, which reads
+    the same images"""
+    return packed.buf if _pk(packed, weight)[0] is not None else None
+
+
+def _pkargs(buf):
+    """(pointer, bytes) of a _pk_buf result; (0, 0) without one: the entry point packs in the call"""
+    return _p(buf), 0 if buf is None else buf.numel()
+
+
 def nafblock_bf16(inp: torch.Tensor, params: Dict[str, torch.Tensor], packed: PackedWeightsBf16 = None) -> torch.Tensor:
     """bf16 activations in / out, fp32 parameters (dict with the keys of _lib.PARAM_FIELDS); ``packed``: the block's weight-pack cache
     (without it every call packs its own operand copies)."""
@@ -664,7 +667,7 @@ def _cast(lib, x, to_bf16):
         raise _lib.DcptHipError("cast: element count must be a multiple of 8")
     y = torch.empty_like(x, dtype=dst)   # preserves the (dense NHWC) strides
     fn = lib.dcpt_cast_f32_bf16 if to_bf16 else lib.dcpt_cast_bf16_f32
-    check(fn(x.data_ptr(), y.data_ptr(), x.numel(), _stream(x.device)), "dcpt_cast")
+    check(fn(x.data_ptr(), y.data_ptr(), x.numel(), _stream(x.device)), fn.__name__)
     return y
 
 
@@ -1035,7 +1038,7 @@ class _DownFn(torch.autograd.Function):
         nws = (lib.dcpt_down2x2_bf16_ws_bytes if bf else lib.dcpt_down2x2_ws_bytes)(B, H, W, Cc, 1)
         ws = _workspace(dev, nws)
         fn = lib.dcpt_down2x2_bwd_bf16 if bf else lib.dcpt_down2x2_bwd
-        check(fn(dy.data_ptr(), x.data_ptr(), w_.data_ptr(), dx.data_ptr(), dw.data_ptr(), db.data_ptr(), ws.data_ptr(), ws.numel(),
+        check(fn(dy.data_ptr(), x.data_ptr(), w_.data_ptr(), None, dx.data_ptr(), dw.data_ptr(), db.data_ptr(), ws.data_ptr(), ws.numel(),
                  B, H, W, Cc, _stream(dev)), fn.__name__)
         return dx, dw, (db if ctx.has_bias else None)
 
@@ -1096,7 +1099,7 @@ class _DownSkipFn(torch.autograd.Function):
     """(down2x2(x), x) for an encoder group's output, which has TWO consumers: the down layer and the skip connection into the decoder
     (reference nafnet_arch.py:255-258, :264-265).  As two uses autograd sums the two gradients with a pass of its own over the feature map
     (four `add` launches per step, the level-0 one over the largest tensor of the network); here the skip's gradient -- the up layer's
-    dy, untouched -- is the ``dx_add`` of the down layer's backward (dcpt_down2x2_bwd_acc*, ABI 13): summed in the scatter epilogue of
+    dy, untouched -- is the ``dx_add`` of the down layer's backward (dcpt_down2x2_bwd*): summed in the scatter epilogue of
     its data-gradient GEMM.  fp32 or bf16 activations by x.dtype."""
 
     @staticmethod
@@ -1112,8 +1115,9 @@ class _DownSkipFn(torch.autograd.Function):
             raise ValueError(f"down2x2: H={H}, W={W} must be even")
         y = (_empty_nhwc_bf16 if bf else _empty_nhwc)(B, 2 * Cc, H // 2, W // 2, x.device)
         ws = _workspace(x.device, (lib.dcpt_down2x2_bf16_ws_bytes if bf else lib.dcpt_down2x2_ws_bytes)(B, H, W, Cc, 0))
-        check((lib.dcpt_down2x2_fwd_bf16 if bf else lib.dcpt_down2x2_fwd)(x.data_ptr(), w_.data_ptr(), _p(b_), y.data_ptr(), ws.data_ptr(),
-                                                                          ws.numel(), B, H, W, Cc, _stream(x.device)), "dcpt_down2x2_fwd")
+        fn = lib.dcpt_down2x2_fwd_bf16 if bf else lib.dcpt_down2x2_fwd
+        check(fn(x.data_ptr(), w_.data_ptr(), _p(b_), y.data_ptr(), ws.data_ptr(), ws.numel(), B, H, W, Cc, _stream(x.device)),
+              fn.__name__)
         ctx.save_for_backward(x, w_)
         ctx.has_bias, ctx.bf = bias is not None, bf
         return y, x.view(x.shape)
@@ -1134,9 +1138,9 @@ class _DownSkipFn(torch.autograd.Function):
         dw = torch.empty_like(w_)
         db = torch.empty((2 * Cc,), dtype=torch.float32, device=dev)
         ws = _workspace(dev, (lib.dcpt_down2x2_bf16_ws_bytes if bf else lib.dcpt_down2x2_ws_bytes)(B, H, W, Cc, 1))
-        check((lib.dcpt_down2x2_bwd_acc_bf16 if bf else lib.dcpt_down2x2_bwd_acc)(
-            dy.data_ptr(), x.data_ptr(), w_.data_ptr(), _p(dskip), dx.data_ptr(), dw.data_ptr(), db.data_ptr(), ws.data_ptr(), ws.numel(),
-            B, H, W, Cc, _stream(dev)), "dcpt_down2x2_bwd_acc")
+        fn = lib.dcpt_down2x2_bwd_bf16 if bf else lib.dcpt_down2x2_bwd
+        check(fn(dy.data_ptr(), x.data_ptr(), w_.data_ptr(), _p(dskip), dx.data_ptr(), dw.data_ptr(), db.data_ptr(), ws.data_ptr(), ws.numel(),
+                 B, H, W, Cc, _stream(dev)), fn.__name__)
         return dx, dw, (db if ctx.has_bias else None)
 
 
@@ -1194,28 +1198,58 @@ def fused_leaky_relu(x, bias, negative_slope=0.2, scale=2 ** 0.5):
 
 # ------------------------------------------------------------------------------------------------
 # degradation-classifier head (reference basicsr/archs/degrad_classify_arch.py)
-@_remember_gemm_mode
+def _conv_ln_fwd(lib, x, w_, pk, lw, lb, res, relu):
+    """ONE conv -> channels-first LayerNorm -> [+res] -> [ReLU] group: dcpt_conv_ln_fwd, or dcpt_conv_ln_fwd_bf16 with the conv's cached operand
+    images ``pk`` (a byte buffer or None), by x.dtype.  Returns z (conv output), y and the LayerNorm statistics [2][B H W]."""
+    bf = x.dtype == torch.bfloat16
+    B, Cin, H, W = x.shape
+    Cout, ks = w_.shape[0], w_.shape[2]
+    dev = x.device
+    empty = _empty_nhwc_bf16 if bf else _empty_nhwc
+    z, y = empty(B, Cout, H, W, dev), empty(B, Cout, H, W, dev)
+    stats = torch.empty((2, B * H * W), dtype=torch.float32, device=dev)
+    ws = _workspace(dev, (lib.dcpt_conv_ln_bf16_ws_bytes if bf else lib.dcpt_conv_ln_ws_bytes)(B, H, W, Cin, Cout, ks, 0))
+    fn = lib.dcpt_conv_ln_fwd_bf16 if bf else lib.dcpt_conv_ln_fwd
+    check(fn(x.data_ptr(), w_.data_ptr(), *(_pkargs(pk) if bf else ()), lw.data_ptr(), lb.data_ptr(), _p(res), int(bool(relu)), z.data_ptr(),
+             y.data_ptr(), stats[0].data_ptr(), stats[1].data_ptr(), ws.data_ptr(), ws.numel(), B, H, W, Cin, Cout, ks, _stream(dev)), fn.__name__)
+    return z, y, stats
+
+
+def _conv_ln_bwd(lib, dy, x, w_, pk, lw, z, y, stats, dx_add, has_res, relu):
+    """backward of _conv_ln_fwd (dcpt_conv_ln_bwd / _bf16 by x.dtype): dx = dx_add + conv^T(dz) (dx_add may be None).  Returns dx, dw, dlnw,
+    dlnb and dres (None without a residual input)."""
+    bf = x.dtype == torch.bfloat16
+    B, Cin, H, W = x.shape
+    Cout, ks = w_.shape[0], w_.shape[2]
+    dev = x.device
+    empty = _empty_nhwc_bf16 if bf else _empty_nhwc
+    dx = empty(B, Cin, H, W, dev)
+    dw = torch.empty_like(w_)
+    dlw, dlb = torch.empty_like(lw), torch.empty_like(lw)
+    dres = empty(B, Cout, H, W, dev) if has_res else None
+    ws = _workspace(dev, (lib.dcpt_conv_ln_bf16_ws_bytes if bf else lib.dcpt_conv_ln_ws_bytes)(B, H, W, Cin, Cout, ks, 1))
+    fn = lib.dcpt_conv_ln_bwd_bf16 if bf else lib.dcpt_conv_ln_bwd
+    check(fn(dy.data_ptr(), x.data_ptr(), w_.data_ptr(), *(_pkargs(pk) if bf else ()), lw.data_ptr(), z.data_ptr(), y.data_ptr(),
+             stats[0].data_ptr(), stats[1].data_ptr(), _p(dx_add), dx.data_ptr(), dw.data_ptr(), dlw.data_ptr(), dlb.data_ptr(), _p(dres),
+             ws.data_ptr(), ws.numel(), B, H, W, Cin, Cout, ks, int(relu), _stream(dev)), fn.__name__)
+    return dx, dw, dlw, dlb, dres
+
+
+@_remember_gemm_mode_fp32
 class _ConvLNFn(torch.autograd.Function):
     """conv(1x1 | 3x3, no bias) -> channels-first LayerNorm -> [+res] -> [ReLU]
-    (Conv2d wrapper :69-103 with norm=LN; BottleneckBlock tail :227-243)."""
+    (Conv2d wrapper :69-103 with norm=LN; BottleneckBlock tail :227-243).  fp32 or bf16 activations (x, res, z, y and their gradients) by
+    x.dtype, parameters fp32; ``packed``: the conv's PackedConvBf16 cache (bf16 activations only)."""
 
     @staticmethod
-    def forward(ctx, x, weight, lnw, lnb, res, relu):
+    def forward(ctx, x, weight, lnw, lnb, res, relu, packed):
         lib = _lib.load()
-        _require_gpu(x, weight, lnw, lnb, res)
+        _require_gpu(weight, lnw, lnb)   # (conv_ln / conv_ln_bf16 have checked the feature maps)
         x = _nhwc(x)
         res_ = None if res is None else _nhwc(res)
         w_, lw, lb = _contig(weight.detach()), _contig(lnw.detach()), _contig(lnb.detach())
-        B, Cin, H, W = x.shape
-        Cout, ks = w_.shape[0], w_.shape[2]
-        dev = x.device
-        z = _empty_nhwc(B, Cout, H, W, dev)
-        y = _empty_nhwc(B, Cout, H, W, dev)
-        stats = torch.empty((2, B * H * W), dtype=torch.float32, device=dev)
-        ws = _workspace(dev, lib.dcpt_conv_ln_ws_bytes(B, H, W, Cin, Cout, ks, 0))
-        check(lib.dcpt_conv_ln_fwd(x.data_ptr(), w_.data_ptr(), lw.data_ptr(), lb.data_ptr(), _p(res_), int(bool(relu)),
-                                   z.data_ptr(), y.data_ptr(), stats[0].data_ptr(), stats[1].data_ptr(), ws.data_ptr(),
-                                   ws.numel(), B, H, W, Cin, Cout, ks, _stream(dev)), "dcpt_conv_ln_fwd")
+        ctx.pk = _pk_buf(packed, weight)
+        z, y, stats = _conv_ln_fwd(lib, x, w_, ctx.pk, lw, lb, res_, relu)
         ctx.save_for_backward(x, w_, lw, z, y, stats)
         ctx.relu, ctx.has_res = bool(relu), res is not None
         return y
@@ -1224,76 +1258,18 @@ class _ConvLNFn(torch.autograd.Function):
     def backward(ctx, dy):
         lib = _lib.load()
         x, w_, lw, z, y, stats = ctx.saved_tensors
-        dy = _nhwc(dy)
-        B, Cin, H, W = x.shape
-        Cout, ks = w_.shape[0], w_.shape[2]
-        dev = x.device
-        dx = _empty_nhwc(B, Cin, H, W, dev)
-        dw = torch.empty_like(w_)
-        dlw, dlb = torch.empty_like(lw), torch.empty_like(lw)
-        dres = _empty_nhwc(B, Cout, H, W, dev) if ctx.has_res else None
-        ws = _workspace(dev, lib.dcpt_conv_ln_ws_bytes(B, H, W, Cin, Cout, ks, 1))
-        check(lib.dcpt_conv_ln_bwd(dy.data_ptr(), x.data_ptr(), w_.data_ptr(), lw.data_ptr(), z.data_ptr(), y.data_ptr(),
-                                   stats[0].data_ptr(), stats[1].data_ptr(), dx.data_ptr(), dw.data_ptr(), dlw.data_ptr(),
-                                   dlb.data_ptr(), _p(dres), ws.data_ptr(), ws.numel(), B, H, W, Cin, Cout, ks,
-                                   int(ctx.relu), _stream(dev)), "dcpt_conv_ln_bwd")
-        return dx, dw, dlw, dlb, dres, None
+        dy = _nhwc(dy.to(torch.bfloat16) if x.dtype == torch.bfloat16 and dy.dtype != torch.bfloat16 else dy)
+        return (*_conv_ln_bwd(lib, dy, x, w_, ctx.pk, lw, z, y, stats, None, ctx.has_res, ctx.relu), None, None)
 
 
 def conv_ln(x, weight, lnw, lnb, res=None, relu=True):
-    return _ConvLNFn.apply(x, weight, lnw, lnb, res, relu)
-
-
-class _ConvLNBf16Fn(torch.autograd.Function):
-    """_ConvLNFn with bf16 activations (dcpt_conv_ln_fwd_bf16 / bwd_bf16): x, res, z, y and their gradients bf16; parameters fp32."""
-
-    @staticmethod
-    def forward(ctx, x, weight, lnw, lnb, res, relu, packed=None):
-        lib = _lib.load()
-        _require_gpu_bf16(x, *([] if res is None else [res]))
-        _require_gpu(weight, lnw, lnb)
-        x = _nhwc(x)
-        res_ = None if res is None else _nhwc(res)
-        w_, lw, lb = _contig(weight.detach()), _contig(lnw.detach()), _contig(lnb.detach())
-        B, Cin, H, W = x.shape
-        Cout, ks = w_.shape[0], w_.shape[2]
-        dev = x.device
-        z = _empty_nhwc_bf16(B, Cout, H, W, dev)
-        y = _empty_nhwc_bf16(B, Cout, H, W, dev)
-        stats = torch.empty((2, B * H * W), dtype=torch.float32, device=dev)
-        ws = _workspace(dev, lib.dcpt_conv_ln_bf16_ws_bytes(B, H, W, Cin, Cout, ks, 0))
-        pkp, pkn = _pk(packed, weight)
-        check(lib.dcpt_conv_ln_fwd_bf16_packed(x.data_ptr(), w_.data_ptr(), pkp, pkn, lw.data_ptr(), lb.data_ptr(), _p(res_), int(bool(relu)),
-                                               z.data_ptr(), y.data_ptr(), stats[0].data_ptr(), stats[1].data_ptr(), ws.data_ptr(),
-                                               ws.numel(), B, H, W, Cin, Cout, ks, _stream(dev)), "dcpt_conv_ln_fwd_bf16")
-        ctx.save_for_backward(x, w_, lw, z, y, stats)
-        ctx.relu, ctx.has_res = bool(relu), res is not None
-        ctx.pk = (packed.buf if pkp is not None else None)   # (the backward of THIS forward reads the same images)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        lib = _lib.load()
-        x, w_, lw, z, y, stats = ctx.saved_tensors
-        dy = _nhwc(dy if dy.dtype == torch.bfloat16 else dy.to(torch.bfloat16))
-        B, Cin, H, W = x.shape
-        Cout, ks = w_.shape[0], w_.shape[2]
-        dev = x.device
-        dx = _empty_nhwc_bf16(B, Cin, H, W, dev)
-        dw = torch.empty_like(w_)
-        dlw, dlb = torch.empty_like(lw), torch.empty_like(lw)
-        dres = _empty_nhwc_bf16(B, Cout, H, W, dev) if ctx.has_res else None
-        ws = _workspace(dev, lib.dcpt_conv_ln_bf16_ws_bytes(B, H, W, Cin, Cout, ks, 1))
-        pk = ctx.pk
-        check(lib.dcpt_conv_ln_bwd_acc_bf16_packed(dy.data_ptr(), x.data_ptr(), w_.data_ptr(), _p(pk), 0 if pk is None else pk.numel(),
-                                                   lw.data_ptr(), z.data_ptr(), y.data_ptr(), stats[0].data_ptr(), stats[1].data_ptr(), None,
-                                                   dx.data_ptr(), dw.data_ptr(), dlw.data_ptr(), dlb.data_ptr(), _p(dres), ws.data_ptr(),
-                                                   ws.numel(), B, H, W, Cin, Cout, ks, int(ctx.relu), _stream(dev)), "dcpt_conv_ln_bwd_bf16")
-        return dx, dw, dlw, dlb, dres, None, None
+    _require_gpu(x, res)
+    return _ConvLNFn.apply(x, weight, lnw, lnb, res, relu, None)
 
 
 def conv_ln_bf16(x, weight, lnw, lnb, res=None, relu=True, packed: PackedConvBf16 = None):
-    return _ConvLNBf16Fn.apply(x, weight, lnw, lnb, res, relu, packed)
+    _require_gpu_bf16(x, *([] if res is None else [res]))
+    return _ConvLNFn.apply(x, weight, lnw, lnb, res, relu, packed)
 
 
 @_remember_gemm_mode
@@ -1302,7 +1278,7 @@ class _BottleneckFn(torch.autograd.Function):
     autograd node: relu(LN(conv1(x))) -> relu(LN(conv2(.))) -> relu(LN(conv3(.)) + x), the three conv -> LN groups through the same C
     entry points as conv_ln / conv_ln_bf16 (fp32 or bf16 activations by x.dtype).  As three nodes the block's input has two consumers
     (conv1 and the shortcut) and autograd sums their gradients with a pass of its own over the feature map -- 10 of the 18 bf16 `add`
-    launches of a DCPT step; here conv3's shortcut gradient is conv1's ``dx_add`` (dcpt_conv_ln_bwd_acc*, ABI 13): summed in the epilogue
+    launches of a DCPT step; here conv3's shortcut gradient is conv1's ``dx_add`` (dcpt_conv_ln_bwd*): summed in the epilogue
     of conv1's data-gradient GEMM."""
 
     @staticmethod
@@ -1313,30 +1289,15 @@ class _BottleneckFn(torch.autograd.Function):
         (_require_gpu_bf16 if bf else _require_gpu)(x)
         _require_gpu(w1, lw1, lb1, w2, lw2, lb2, w3, lw3, lb3)
         x = _nhwc(x)
-        dev = x.device
-        B, C_, H, W = x.shape
+        C_ = x.shape[1]
         ctx.fused = bf and _BottleneckFn._geometry_ok(C_, w1, lw1, lb1, w2, lw2, lb2, w3, lw3, lb3)
         if ctx.fused:
             return _BottleneckFn._forward_bf16(ctx, lib, x, ((w1, lw1, lb1), (w2, lw2, lb2), (w3, lw3, lb3)), packs)
-        empty = _empty_nhwc_bf16 if bf else _empty_nhwc
-        ws_bytes = lib.dcpt_conv_ln_bf16_ws_bytes if bf else lib.dcpt_conv_ln_ws_bytes
         saved, cur, pkbufs = [x], x, []
         for (w, lw, lb, res, pck) in ((w1, lw1, lb1, None, packs[0]), (w2, lw2, lb2, None, packs[1]), (w3, lw3, lb3, x, packs[2])):
             w_, lw_, lb_ = _contig(w.detach()), _contig(lw.detach()), _contig(lb.detach())
-            Cout, Cin, ks = w_.shape[0], w_.shape[1], w_.shape[2]
-            z, y = empty(B, Cout, H, W, dev), empty(B, Cout, H, W, dev)
-            stats = torch.empty((2, B * H * W), dtype=torch.float32, device=dev)
-            ws = _workspace(dev, ws_bytes(B, H, W, Cin, Cout, ks, 0))
-            if bf:
-                pkp, pkn = _pk(pck, w)
-                check(lib.dcpt_conv_ln_fwd_bf16_packed(cur.data_ptr(), w_.data_ptr(), pkp, pkn, lw_.data_ptr(), lb_.data_ptr(), _p(res), 1,
-                                                       z.data_ptr(), y.data_ptr(), stats[0].data_ptr(), stats[1].data_ptr(), ws.data_ptr(),
-                                                       ws.numel(), B, H, W, Cin, Cout, ks, _stream(dev)), "dcpt_conv_ln_fwd_bf16")
-                pkbufs.append(pck.buf if pkp is not None else None)
-            else:
-                check(lib.dcpt_conv_ln_fwd(cur.data_ptr(), w_.data_ptr(), lw_.data_ptr(), lb_.data_ptr(), _p(res), 1, z.data_ptr(),
-                                           y.data_ptr(), stats[0].data_ptr(), stats[1].data_ptr(), ws.data_ptr(), ws.numel(), B, H, W, Cin,
-                                           Cout, ks, _stream(dev)), "dcpt_conv_ln_fwd")
+            pkbufs.append(_pk_buf(pck, w))
+            z, y, stats = _conv_ln_fwd(lib, cur, w_, pkbufs[-1], lw_, lb_, res, 1)
             saved += [w_, lw_, z, y, stats]
             cur = y
         ctx.save_for_backward(*saved)
@@ -1409,36 +1370,15 @@ class _BottleneckFn(torch.autograd.Function):
             return _BottleneckFn._backward_bf16(ctx, lib, dy)
         sv = ctx.saved_tensors
         x, bf = sv[0], ctx.bf
-        dev = x.device
-        B, _, H, W = x.shape
-        empty = _empty_nhwc_bf16 if bf else _empty_nhwc
-        ws_bytes = lib.dcpt_conv_ln_bf16_ws_bytes if bf else lib.dcpt_conv_ln_ws_bytes
         g = _nhwc(dy if (not bf or dy.dtype == torch.bfloat16) else dy.to(torch.bfloat16))
         grads, dshort = [None] * 9, None
         for k in (2, 1, 0):   # conv3 (its dres = the shortcut gradient), conv2, conv1 (dx = dx_add + ...)
             w_, lw_, z, y, stats = sv[1 + 5 * k: 6 + 5 * k]
             xin = x if k == 0 else sv[5 * k - 1]      # the y of group k - 1
-            Cout, Cin, ks = w_.shape[0], w_.shape[1], w_.shape[2]
-            dx = empty(B, Cin, H, W, dev)
-            dw, dlw, dlb = torch.empty_like(w_), torch.empty_like(lw_), torch.empty_like(lw_)
-            dres = empty(B, Cout, H, W, dev) if k == 2 else None
-            ws = _workspace(dev, ws_bytes(B, H, W, Cin, Cout, ks, 1))
-            if bf:
-                pk = ctx.pkbufs[k]
-                check(lib.dcpt_conv_ln_bwd_acc_bf16_packed(g.data_ptr(), xin.data_ptr(), w_.data_ptr(), _p(pk), 0 if pk is None else pk.numel(),
-                                                           lw_.data_ptr(), z.data_ptr(), y.data_ptr(), stats[0].data_ptr(), stats[1].data_ptr(),
-                                                           _p(dshort if k == 0 else None), dx.data_ptr(), dw.data_ptr(), dlw.data_ptr(),
-                                                           dlb.data_ptr(), _p(dres), ws.data_ptr(), ws.numel(), B, H, W, Cin, Cout, ks, 1,
-                                                           _stream(dev)), "dcpt_conv_ln_bwd_acc_bf16")
-            else:
-                check(lib.dcpt_conv_ln_bwd_acc(g.data_ptr(), xin.data_ptr(), w_.data_ptr(), lw_.data_ptr(), z.data_ptr(), y.data_ptr(),
-                                               stats[0].data_ptr(), stats[1].data_ptr(), _p(dshort if k == 0 else None), dx.data_ptr(),
-                                               dw.data_ptr(), dlw.data_ptr(), dlb.data_ptr(), _p(dres), ws.data_ptr(), ws.numel(), B, H, W,
-                                               Cin, Cout, ks, 1, _stream(dev)), "dcpt_conv_ln_bwd_acc")
+            g, dw, dlw, dlb, dres = _conv_ln_bwd(lib, g, xin, w_, ctx.pkbufs[k], lw_, z, y, stats, dshort if k == 0 else None, k == 2, 1)
             if k == 2:
                 dshort = dres
             grads[3 * k: 3 * k + 3] = [dw, dlw, dlb]
-            g = dx
         return (g, *grads, None)
 
 
@@ -1446,51 +1386,6 @@ def bottleneck(x, w1, lw1, lb1, w2, lw2, lb2, w3, lw3, lb3, packs=None):
     """relu(LN(conv3(relu(LN(conv2(relu(LN(conv1(x)))))))) + x) as one autograd node (fp32 or bf16 activations); ``packs``: the three convs'
     PackedConvBf16 caches (bf16 activations)"""
     return _BottleneckFn.apply(x, w1, lw1, lb1, w2, lw2, lb2, w3, lw3, lb3, packs)
-
-
-class _ConvPoolReluBf16Fn(torch.autograd.Function):
-    """_ConvPoolReluFn with bf16 activations."""
-
-    @staticmethod
-    def forward(ctx, x, weight, packed=None):
-        lib = _lib.load()
-        _require_gpu_bf16(x)
-        _require_gpu(weight)
-        x = _nhwc(x)
-        w_ = _contig(weight.detach())
-        B, Cin, H, W = x.shape
-        Cout = w_.shape[0]
-        dev = x.device
-        z = _empty_nhwc_bf16(B, Cout, H, W, dev)
-        y = _empty_nhwc_bf16(B, Cout, H // 2, W // 2, dev)
-        ws = _workspace(dev, lib.dcpt_conv1x1_pool_relu_bf16_ws_bytes(B, H, W, Cin, Cout, 0))
-        pkp, pkn = _pk(packed, weight)
-        check(lib.dcpt_conv1x1_pool_relu_fwd_bf16_packed(x.data_ptr(), w_.data_ptr(), pkp, pkn, z.data_ptr(), y.data_ptr(), ws.data_ptr(),
-                                                         ws.numel(), B, H, W, Cin, Cout, _stream(dev)), "dcpt_conv1x1_pool_relu_fwd_bf16")
-        ctx.save_for_backward(x, w_, z)
-        ctx.pk = (packed.buf if pkp is not None else None)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        lib = _lib.load()
-        x, w_, z = ctx.saved_tensors
-        dy = _nhwc(dy if dy.dtype == torch.bfloat16 else dy.to(torch.bfloat16))
-        B, Cin, H, W = x.shape
-        Cout = w_.shape[0]
-        dev = x.device
-        dx = _empty_nhwc_bf16(B, Cin, H, W, dev)
-        dw = torch.empty_like(w_)
-        ws = _workspace(dev, lib.dcpt_conv1x1_pool_relu_bf16_ws_bytes(B, H, W, Cin, Cout, 1))
-        pk = ctx.pk
-        check(lib.dcpt_conv1x1_pool_relu_bwd_bf16_packed(dy.data_ptr(), x.data_ptr(), w_.data_ptr(), _p(pk), 0 if pk is None else pk.numel(),
-                                                         z.data_ptr(), dx.data_ptr(), dw.data_ptr(), ws.data_ptr(), ws.numel(), B, H, W, Cin,
-                                                         Cout, _stream(dev)), "dcpt_conv1x1_pool_relu_bwd_bf16")
-        return dx, dw, None
-
-
-def conv1x1_pool_relu_bf16(x, weight, packed: PackedConvBf16 = None):
-    return _ConvPoolReluBf16Fn.apply(x, weight, packed)
 
 
 class _PatchUnfoldFn(torch.autograd.Function):
@@ -1535,24 +1430,29 @@ def conv_embed_ln(x, weight, bias, lnw, lnb, stride=2, pad=3):
     return conv_ln(A, wext, lnw, lnb, None, relu=False)
 
 
-@_remember_gemm_mode
+@_remember_gemm_mode_fp32
 class _ConvPoolReluFn(torch.autograd.Function):
-    """Conv2d(1x1, bias=False) -> MaxPool2d(2,2) -> ReLU (degrad_classify_arch.py:596-602)."""
+    """Conv2d(1x1, bias=False) -> MaxPool2d(2,2) -> ReLU (degrad_classify_arch.py:596-602); fp32 or bf16 activations by x.dtype, the weight
+    fp32; ``packed``: the conv's PackedConvBf16 cache (bf16 activations only)."""
 
     @staticmethod
-    def forward(ctx, x, weight):
+    def forward(ctx, x, weight, packed):
         lib = _lib.load()
-        _require_gpu(x, weight)
+        _require_gpu(weight)   # (conv1x1_pool_relu / conv1x1_pool_relu_bf16 have checked the feature map)
         x = _nhwc(x)
+        bf = x.dtype == torch.bfloat16
         w_ = _contig(weight.detach())
         B, Cin, H, W = x.shape
         Cout = w_.shape[0]
         dev = x.device
-        z = _empty_nhwc(B, Cout, H, W, dev)
-        y = _empty_nhwc(B, Cout, H // 2, W // 2, dev)
-        ws = _workspace(dev, lib.dcpt_conv1x1_pool_relu_ws_bytes(B, H, W, Cin, Cout, 0))
-        check(lib.dcpt_conv1x1_pool_relu_fwd(x.data_ptr(), w_.data_ptr(), z.data_ptr(), y.data_ptr(), ws.data_ptr(), ws.numel(),
-                                             B, H, W, Cin, Cout, _stream(dev)), "dcpt_conv1x1_pool_relu_fwd")
+        empty = _empty_nhwc_bf16 if bf else _empty_nhwc
+        z = empty(B, Cout, H, W, dev)
+        y = empty(B, Cout, H // 2, W // 2, dev)
+        ws = _workspace(dev, (lib.dcpt_conv1x1_pool_relu_bf16_ws_bytes if bf else lib.dcpt_conv1x1_pool_relu_ws_bytes)(B, H, W, Cin, Cout, 0))
+        ctx.pk = _pk_buf(packed, weight)
+        fn = lib.dcpt_conv1x1_pool_relu_fwd_bf16 if bf else lib.dcpt_conv1x1_pool_relu_fwd
+        check(fn(x.data_ptr(), w_.data_ptr(), *(_pkargs(ctx.pk) if bf else ()), z.data_ptr(), y.data_ptr(), ws.data_ptr(), ws.numel(),
+                 B, H, W, Cin, Cout, _stream(dev)), fn.__name__)
         ctx.save_for_backward(x, w_, z)
         return y
 
@@ -1560,21 +1460,28 @@ class _ConvPoolReluFn(torch.autograd.Function):
     def backward(ctx, dy):
         lib = _lib.load()
         x, w_, z = ctx.saved_tensors
-        dy = _nhwc(dy)
+        bf = x.dtype == torch.bfloat16
+        dy = _nhwc(dy.to(torch.bfloat16) if bf and dy.dtype != torch.bfloat16 else dy)
         B, Cin, H, W = x.shape
         Cout = w_.shape[0]
         dev = x.device
-        dx = _empty_nhwc(B, Cin, H, W, dev)
+        dx = (_empty_nhwc_bf16 if bf else _empty_nhwc)(B, Cin, H, W, dev)
         dw = torch.empty_like(w_)
-        ws = _workspace(dev, lib.dcpt_conv1x1_pool_relu_ws_bytes(B, H, W, Cin, Cout, 1))
-        check(lib.dcpt_conv1x1_pool_relu_bwd(dy.data_ptr(), x.data_ptr(), w_.data_ptr(), z.data_ptr(), dx.data_ptr(),
-                                             dw.data_ptr(), ws.data_ptr(), ws.numel(), B, H, W, Cin, Cout, _stream(dev)),
-              "dcpt_conv1x1_pool_relu_bwd")
-        return dx, dw
+        ws = _workspace(dev, (lib.dcpt_conv1x1_pool_relu_bf16_ws_bytes if bf else lib.dcpt_conv1x1_pool_relu_ws_bytes)(B, H, W, Cin, Cout, 1))
+        fn = lib.dcpt_conv1x1_pool_relu_bwd_bf16 if bf else lib.dcpt_conv1x1_pool_relu_bwd
+        check(fn(dy.data_ptr(), x.data_ptr(), w_.data_ptr(), *(_pkargs(ctx.pk) if bf else ()), z.data_ptr(), dx.data_ptr(), dw.data_ptr(),
+                 ws.data_ptr(), ws.numel(), B, H, W, Cin, Cout, _stream(dev)), fn.__name__)
+        return dx, dw, None
 
 
 def conv1x1_pool_relu(x, weight):
-    return _ConvPoolReluFn.apply(x, weight)
+    _require_gpu(x)
+    return _ConvPoolReluFn.apply(x, weight, None)
+
+
+def conv1x1_pool_relu_bf16(x, weight, packed: PackedConvBf16 = None):
+    _require_gpu_bf16(x)
+    return _ConvPoolReluFn.apply(x, weight, packed)
 
 
 class _MixFn(torch.autograd.Function):
@@ -1595,7 +1502,7 @@ class _MixFn(torch.autograd.Function):
         out = (_empty_nhwc_bf16 if bf else _empty_nhwc)(*feat.shape, feat.device)
         fn = lib.dcpt_mix_fwd_bf16 if bf else lib.dcpt_mix_fwd
         check(fn(_p(prev_), feat.data_ptr(), mw.data_ptr(), mw.numel(), int(idx), out.data_ptr(), feat.numel(), _stream(feat.device)),
-              "dcpt_mix_fwd")
+              fn.__name__)
         ctx.save_for_backward(feat, mw)
         ctx.idx, ctx.has_prev = int(idx), prev is not None
         return out
@@ -1612,7 +1519,7 @@ class _MixFn(torch.autograd.Function):
         ws = _workspace(dev, lib.dcpt_mix_bwd_ws_bytes(feat.numel()))
         fn = lib.dcpt_mix_bwd_bf16 if bf else lib.dcpt_mix_bwd
         check(fn(dout.data_ptr(), feat.data_ptr(), mw.data_ptr(), mw.numel(), ctx.idx, dfeat.data_ptr(), dmix.data_ptr(), ws.data_ptr(),
-                 ws.numel(), feat.numel(), _stream(dev)), "dcpt_mix_bwd")
+                 ws.numel(), feat.numel(), _stream(dev)), fn.__name__)
         return (dout if ctx.has_prev else None), dfeat, dmix, None
 
 
@@ -1712,7 +1619,7 @@ class _MeanPoolFCFn(torch.autograd.Function):
         bf = x.dtype == torch.bfloat16   # bf16-storage feature map: pooled in fp32 straight from it, its gradient stored in bf16
         fn = lib.dcpt_meanpool_fc_fwd_bf16 if bf else lib.dcpt_meanpool_fc_fwd
         check(fn(x.data_ptr(), fw_.data_ptr(), _p(fb_), pooled.data_ptr(), logits.data_ptr(), ws.data_ptr(), ws.numel(), B, H * W, Cc, NC,
-                 _stream(dev)), "dcpt_meanpool_fc_fwd")
+                 _stream(dev)), fn.__name__)
         ctx.save_for_backward(pooled, fw_)
         ctx.shape, ctx.has_bias, ctx.bf = (B, Cc, H, W), fb is not None, bf
         return logits
@@ -1731,7 +1638,7 @@ class _MeanPoolFCFn(torch.autograd.Function):
         ws = _workspace(dev, lib.dcpt_meanpool_fc_ws_bytes(B, H * W, Cc))
         fn = lib.dcpt_meanpool_fc_bwd_bf16 if ctx.bf else lib.dcpt_meanpool_fc_bwd
         check(fn(dl.data_ptr(), pooled.data_ptr(), fw_.data_ptr(), dx.data_ptr(), dfw.data_ptr(), dfb.data_ptr(), ws.data_ptr(), ws.numel(),
-                 B, H * W, Cc, NC, _stream(dev)), "dcpt_meanpool_fc_bwd")
+                 B, H * W, Cc, NC, _stream(dev)), fn.__name__)
         return dx, dfw, (dfb if ctx.has_bias else None)
 
 

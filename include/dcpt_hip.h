@@ -139,17 +139,19 @@ typedef struct {
 } dcpt_nafblock_saved_bf16;
 size_t dcpt_nafblock_fwd_bf16_ws_bytes(int B, int H, int W, int C);
 size_t dcpt_nafblock_bwd_bf16_ws_bytes(int B, int H, int W, int C);
-int dcpt_nafblock_fwd_bf16(const dcpt_nafblock_params* p, const uint16_t* inp, uint16_t* out, const dcpt_nafblock_saved_bf16* saved,
-                           void* ws, size_t ws_bytes, int B, int H, int W, int C, dcpt_stream_t stream);
-int dcpt_nafblock_bwd_bf16(const dcpt_nafblock_params* p, const dcpt_nafblock_grads* g, const uint16_t* inp,
-                           const dcpt_nafblock_saved_bf16* saved, const uint16_t* dout, uint16_t* dinp, void* ws, size_t ws_bytes,
-                           int B, int H, int W, int C, dcpt_stream_t stream);
+/* packed / packed_bytes: the block's dcpt_nafblock_wpack_bf16 buffer (below), or NULL, 0 -- the call then packs the weights into its workspace */
+int dcpt_nafblock_fwd_bf16(const dcpt_nafblock_params* p, const void* packed, size_t packed_bytes, const uint16_t* inp, uint16_t* out,
+                           const dcpt_nafblock_saved_bf16* saved, void* ws, size_t ws_bytes, int B, int H, int W, int C,
+                           dcpt_stream_t stream);
+int dcpt_nafblock_bwd_bf16(const dcpt_nafblock_params* p, const void* packed, size_t packed_bytes, const dcpt_nafblock_grads* g,
+                           const uint16_t* inp, const dcpt_nafblock_saved_bf16* saved, const uint16_t* dout, uint16_t* dinp, void* ws,
+                           size_t ws_bytes, int B, int H, int W, int C, dcpt_stream_t stream);
 /* Per-block operand copies of the weights (ABI 7).  Everything the block's GEMMs and depthwise kernels read of the PARAMETERS --
  * bf16 [N][K] copies of conv1 / conv4 / conv5, transposed (beta / gamma-scaled) copies of conv5 / conv4 / conv3 / conv1 for the data
  * gradients, the depthwise taps as [9][2C] fp32 -- depends on the parameters only: a caller that keeps one buffer of
  * dcpt_nafblock_wpack_bf16_bytes(C) per block and re-runs dcpt_nafblock_wpack_bf16 (ONE launch) whenever the block's parameters
- * changed (once per optimizer step) hands it to the *_packed forms below, which then launch no pack kernels except the per-image
- * SCA-scaled conv3 weights (5 launches fewer per block and step).  Results are bit-identical to dcpt_nafblock_fwd/bwd_bf16. */
+ * changed (once per optimizer step) hands it to dcpt_nafblock_fwd/bwd_bf16 as `packed`, which then launch no pack kernels except the
+ * per-image SCA-scaled conv3 weights (5 launches fewer per block and step).  Results are bit-identical to those with packed == NULL. */
 size_t dcpt_nafblock_wpack_bf16_bytes(int C);
 /* 1 when dcpt_nafblock_fwd_bf16 at width C runs the second half of the block (LayerNorm2 -> conv4 -> SimpleGate -> conv5 -> residual,
  * nafnet_arch.py:180-186) as ONE kernel (ffn_bf16.hip, the narrow levels): a caller that will not run the backward pass (inference)
@@ -175,13 +177,6 @@ int dcpt_nafblock_wpack_bf16_multi(const dcpt_nafblock_params* ps, void* const* 
 size_t dcpt_conv1x1_wgrad_bf16_ws_bytes(int64_t M, int N, int K);
 int dcpt_conv1x1_wgrad_bf16(const uint16_t* dY, const uint16_t* X, float* dW, float* db, void* ws, size_t ws_bytes, int64_t M, int N, int K,
                             dcpt_stream_t stream);
-
-int dcpt_nafblock_fwd_bf16_packed(const dcpt_nafblock_params* p, const void* packed, size_t packed_bytes, const uint16_t* inp, uint16_t* out,
-                                  const dcpt_nafblock_saved_bf16* saved, void* ws, size_t ws_bytes, int B, int H, int W, int C,
-                                  dcpt_stream_t stream);
-int dcpt_nafblock_bwd_bf16_packed(const dcpt_nafblock_params* p, const void* packed, size_t packed_bytes, const dcpt_nafblock_grads* g,
-                                  const uint16_t* inp, const dcpt_nafblock_saved_bf16* saved, const uint16_t* dout, uint16_t* dinp, void* ws,
-                                  size_t ws_bytes, int B, int H, int W, int C, dcpt_stream_t stream);
 /* fp32 <-> bf16 (RNE) on n contiguous elements, n % 8 == 0: the edges of the bf16 path */
 int dcpt_cast_f32_bf16(const float* x, uint16_t* y, int64_t n, dcpt_stream_t stream);
 int dcpt_cast_bf16_f32(const uint16_t* x, float* y, int64_t n, dcpt_stream_t stream);
@@ -202,11 +197,9 @@ int dcpt_conv3x3_out_bwd_bf16(const float* dy, const uint16_t* x, const float* w
 size_t dcpt_down2x2_bf16_ws_bytes(int B, int H, int W, int C, int backward);
 int dcpt_down2x2_fwd_bf16(const uint16_t* x, const float* w, const float* bias, uint16_t* y, void* ws, size_t ws_bytes, int B, int H, int W, int C,
                           dcpt_stream_t stream);
-int dcpt_down2x2_bwd_bf16(const uint16_t* dy, const uint16_t* x, const float* w, uint16_t* dx, float* dw, float* dbias, void* ws, size_t ws_bytes,
-                          int B, int H, int W, int C, dcpt_stream_t stream);
-/* ABI 13: dx = dx_add + the down layer's data gradient (dx_add [B][H][W][C] or NULL): see dcpt_down2x2_bwd_acc */
-int dcpt_down2x2_bwd_acc_bf16(const uint16_t* dy, const uint16_t* x, const float* w, const uint16_t* dx_add, uint16_t* dx, float* dw, float* dbias,
-                              void* ws, size_t ws_bytes, int B, int H, int W, int C, dcpt_stream_t stream);
+/* dx = dx_add + the down layer's data gradient (dx_add [B][H][W][C] or NULL): see dcpt_down2x2_bwd */
+int dcpt_down2x2_bwd_bf16(const uint16_t* dy, const uint16_t* x, const float* w, const uint16_t* dx_add, uint16_t* dx, float* dw, float* dbias,
+                          void* ws, size_t ws_bytes, int B, int H, int W, int C, dcpt_stream_t stream);
 size_t dcpt_up_ps_bf16_ws_bytes(int B, int H, int W, int C, int backward);
 int dcpt_up_ps_fwd_bf16(const uint16_t* x, const float* w, const uint16_t* skip /* may be NULL */, uint16_t* y, void* ws, size_t ws_bytes, int B,
                         int H, int W, int C, dcpt_stream_t stream);
@@ -217,50 +210,36 @@ int dcpt_up_ps_bwd_bf16(const uint16_t* dy, const uint16_t* x, const float* w, u
  * conv1x1 -> MaxPool2d(2,2) -> ReLU downsamples of degrad_classify_arch.py (:69-103, :227-243, :596-602) with bf16 activations
  * (x, z = conv output, y and their gradients), fp32 parameters / gradients / statistics; same argument meaning as dcpt_conv_ln_* and
  * dcpt_conv1x1_pool_relu_* below.  Channel counts must be multiples of 8, Cout <= 1024. */
-size_t dcpt_conv_ln_bf16_ws_bytes(int B, int H, int W, int Cin, int Cout, int ksize, int backward);
-int dcpt_conv_ln_fwd_bf16(const uint16_t* x, const float* w, const float* lnw, const float* lnb, const uint16_t* res, int relu, uint16_t* z,
-                          uint16_t* y, float* mu, float* rstd, void* ws, size_t ws_bytes, int B, int H, int W, int Cin, int Cout, int ksize,
-                          dcpt_stream_t stream);
-int dcpt_conv_ln_bwd_bf16(const uint16_t* dy, const uint16_t* x, const float* w, const float* lnw, const uint16_t* z, const uint16_t* y,
-                          const float* mu, const float* rstd, uint16_t* dx, float* dw, float* dlnw, float* dlnb, uint16_t* dres, void* ws,
-                          size_t ws_bytes, int B, int H, int W, int Cin, int Cout, int ksize, int relu, dcpt_stream_t stream);
-/* ABI 13: as dcpt_conv_ln_bwd_bf16 with dx = dx_add + conv^T(dz) (dx_add [B][H][W][Cin] or NULL; may alias dx).  The BottleneckBlock's input
- * feeds conv1 AND the shortcut (degrad_classify_arch.py:227-243): conv3's dres goes in as conv1's dx_add and the two gradients are summed
- * in the data-gradient GEMM's epilogue instead of by an extra pass over the feature map. */
-int dcpt_conv_ln_bwd_acc_bf16(const uint16_t* dy, const uint16_t* x, const float* w, const float* lnw, const uint16_t* z, const uint16_t* y,
-                              const float* mu, const float* rstd, const uint16_t* dx_add, uint16_t* dx, float* dw, float* dlnw, float* dlnb,
-                              uint16_t* dres, void* ws, size_t ws_bytes, int B, int H, int W, int Cin, int Cout, int ksize, int relu,
-                              dcpt_stream_t stream);
-size_t dcpt_conv1x1_pool_relu_bf16_ws_bytes(int B, int H, int W, int Cin, int Cout, int backward);
-int dcpt_conv1x1_pool_relu_fwd_bf16(const uint16_t* x, const float* w, uint16_t* z, uint16_t* y, void* ws, size_t ws_bytes, int B, int H, int W,
-                                    int Cin, int Cout, dcpt_stream_t stream);
-int dcpt_conv1x1_pool_relu_bwd_bf16(const uint16_t* dy, const uint16_t* x, const float* w, const uint16_t* z, uint16_t* dx, float* dw, void* ws,
-                                    size_t ws_bytes, int B, int H, int W, int Cin, int Cout, dcpt_stream_t stream);
-/* ABI 14: cached operand copies of the head's conv weights.  The entry points above pack their bf16 operand image of `w` on every call (one small
- * launch in front of each GEMM: 68 per step of the DCPT head).  A caller that keeps one buffer of dcpt_conv_wpack_bf16_bytes(Cin, Cout, ksize) bytes
+/* ABI 14: cached operand copies of the head's conv weights.  With wpacked == NULL the entry points below pack their bf16 operand image of `w`
+ * in the call (one small launch in front of each GEMM: 68 per step of the DCPT head).  A caller that keeps one buffer of dcpt_conv_wpack_bf16_bytes(Cin, Cout, ksize) bytes
  * per conv (device memory, 256-byte aligned) fills all of them with dcpt_conv_wpack_bf16_multi (n convs: a launch per 40 convs, the 3 x 3 and the
- * 1 x 1 convs apart) once per optimizer step -- whenever the weights may have changed -- and passes it as `wpacked` to the *_packed forms: same
+ * 1 x 1 convs apart) once per optimizer step -- whenever the weights may have changed -- and passes it as `wpacked`: same
  * results bit for bit, no pack launches.  A buffer holds the forward image ([Cout][ksize ksize Cin]) and the data gradient's (transposed; taps
- * flipped for the 3 x 3).  wpacked == NULL: packs in the call, exactly the unpacked entry point (`w` may be NULL only when wpacked is given). */
+ * flipped for the 3 x 3).  `w` may be NULL only when wpacked is given. */
 size_t dcpt_conv_wpack_bf16_bytes(int Cin, int Cout, int ksize);
 int dcpt_conv_wpack_bf16_multi(const float* const* w, void* const* packed, const size_t* packed_bytes, const int* Cin, const int* Cout,
                                const int* ksize, int n, dcpt_stream_t stream);
-int dcpt_conv_ln_fwd_bf16_packed(const uint16_t* x, const float* w, const void* wpacked, size_t wpacked_bytes, const float* lnw, const float* lnb,
-                                 const uint16_t* res, int relu, uint16_t* z, uint16_t* y, float* mu, float* rstd, void* ws, size_t ws_bytes, int B,
-                                 int H, int W, int Cin, int Cout, int ksize, dcpt_stream_t stream);
-int dcpt_conv_ln_bwd_acc_bf16_packed(const uint16_t* dy, const uint16_t* x, const float* w, const void* wpacked, size_t wpacked_bytes,
-                                     const float* lnw, const uint16_t* z, const uint16_t* y, const float* mu, const float* rstd,
-                                     const uint16_t* dx_add, uint16_t* dx, float* dw, float* dlnw, float* dlnb, uint16_t* dres, void* ws,
-                                     size_t ws_bytes, int B, int H, int W, int Cin, int Cout, int ksize, int relu, dcpt_stream_t stream);
-int dcpt_conv1x1_pool_relu_fwd_bf16_packed(const uint16_t* x, const float* w, const void* wpacked, size_t wpacked_bytes, uint16_t* z, uint16_t* y,
-                                           void* ws, size_t ws_bytes, int B, int H, int W, int Cin, int Cout, dcpt_stream_t stream);
-int dcpt_conv1x1_pool_relu_bwd_bf16_packed(const uint16_t* dy, const uint16_t* x, const float* w, const void* wpacked, size_t wpacked_bytes,
-                                           const uint16_t* z, uint16_t* dx, float* dw, void* ws, size_t ws_bytes, int B, int H, int W, int Cin,
-                                           int Cout, dcpt_stream_t stream);
+size_t dcpt_conv_ln_bf16_ws_bytes(int B, int H, int W, int Cin, int Cout, int ksize, int backward);
+int dcpt_conv_ln_fwd_bf16(const uint16_t* x, const float* w, const void* wpacked, size_t wpacked_bytes, const float* lnw, const float* lnb,
+                          const uint16_t* res, int relu, uint16_t* z, uint16_t* y, float* mu, float* rstd, void* ws, size_t ws_bytes, int B,
+                          int H, int W, int Cin, int Cout, int ksize, dcpt_stream_t stream);
+/* dx = dx_add + conv^T(dz) (dx_add [B][H][W][Cin] or NULL; may alias dx).  The BottleneckBlock's input feeds conv1 AND the shortcut
+ * (degrad_classify_arch.py:227-243): conv3's dres goes in as conv1's dx_add and the two gradients are summed in the data-gradient GEMM's
+ * epilogue instead of by an extra pass over the feature map. */
+int dcpt_conv_ln_bwd_bf16(const uint16_t* dy, const uint16_t* x, const float* w, const void* wpacked, size_t wpacked_bytes,
+                          const float* lnw, const uint16_t* z, const uint16_t* y, const float* mu, const float* rstd,
+                          const uint16_t* dx_add, uint16_t* dx, float* dw, float* dlnw, float* dlnb, uint16_t* dres, void* ws,
+                          size_t ws_bytes, int B, int H, int W, int Cin, int Cout, int ksize, int relu, dcpt_stream_t stream);
+size_t dcpt_conv1x1_pool_relu_bf16_ws_bytes(int B, int H, int W, int Cin, int Cout, int backward);
+int dcpt_conv1x1_pool_relu_fwd_bf16(const uint16_t* x, const float* w, const void* wpacked, size_t wpacked_bytes, uint16_t* z, uint16_t* y,
+                                    void* ws, size_t ws_bytes, int B, int H, int W, int Cin, int Cout, dcpt_stream_t stream);
+int dcpt_conv1x1_pool_relu_bwd_bf16(const uint16_t* dy, const uint16_t* x, const float* w, const void* wpacked, size_t wpacked_bytes,
+                                    const uint16_t* z, uint16_t* dx, float* dw, void* ws, size_t ws_bytes, int B, int H, int W, int Cin,
+                                    int Cout, dcpt_stream_t stream);
 
 /* ABI 15: the classifier head's BottleneckBlock as ONE call (reference basicsr/archs/degrad_classify_arch.py:132-243 as the DCPT head builds it:
  * identity shortcut, LN norm, bias-free convs -- relu(LN(conv1 1x1 C -> 2C)) -> relu(LN(conv2 3x3 2C -> 2C)) -> relu(LN(conv3 1x1 2C -> C) + x)),
- * bf16 activations.  Same arithmetic as three dcpt_conv_ln_fwd_bf16 / dcpt_conv_ln_bwd_acc_bf16 calls (forward: bit-identical), fewer passes:
+ * bf16 activations.  Same arithmetic as three dcpt_conv_ln_fwd_bf16 / dcpt_conv_ln_bwd_bf16 calls (forward: bit-identical), fewer passes:
  * a channels-first LayerNorm (:17-44) runs in the epilogue of the GEMM that produces its input wherever a row fits one column tile (<= 128
  * channels, or 256 on the 256-row kernel), and in backward the two inner LayerNorms ride in the epilogues of the data-gradient GEMMs above
  * them, so the gradients of the two inner activations are never written.  group[0..2] = conv1, conv2, conv3:
@@ -341,13 +320,11 @@ int dcpt_conv3x3_out_bwd(const float* dy, const float* x, const float* w, float*
 size_t dcpt_down2x2_ws_bytes(int B, int H, int W, int C, int backward);
 int dcpt_down2x2_fwd(const float* x, const float* w, const float* bias, float* y, void* ws, size_t ws_bytes, int B,
                      int H, int W, int C, dcpt_stream_t stream);
-int dcpt_down2x2_bwd(const float* dy, const float* x, const float* w, float* dx, float* dw, float* dbias, void* ws,
-                     size_t ws_bytes, int B, int H, int W, int C, dcpt_stream_t stream);
-/* ABI 13: dx = dx_add + the data gradient (dx_add NHWC [B][H][W][C] or NULL).  An encoder group's output feeds the down layer AND the skip
+/* dx = dx_add + the data gradient (dx_add NHWC [B][H][W][C] or NULL).  An encoder group's output feeds the down layer AND the skip
  * connection (nafnet_arch.py:255-258, :264-265): the skip's gradient (= the up layer's dy) is summed in the scatter epilogue of the down
  * layer's data-gradient GEMM instead of by a pass of autograd's own over the feature map. */
-int dcpt_down2x2_bwd_acc(const float* dy, const float* x, const float* w, const float* dx_add, float* dx, float* dw, float* dbias, void* ws,
-                         size_t ws_bytes, int B, int H, int W, int C, dcpt_stream_t stream);
+int dcpt_down2x2_bwd(const float* dy, const float* x, const float* w, const float* dx_add, float* dx, float* dw, float* dbias, void* ws,
+                     size_t ws_bytes, int B, int H, int W, int C, dcpt_stream_t stream);
 
 /* ---- up: Conv2d(C, 2C, 1, bias=False) + PixelShuffle(2) + skip add (nafnet_arch.py:238-242,264-265)
  * x [B][H][W][C], skip/y [B][2H][2W][C/2];  w [2C][C][1][1].  The skip gradient equals dy. */
@@ -365,15 +342,11 @@ size_t dcpt_conv_ln_ws_bytes(int B, int H, int W, int Cin, int Cout, int ksize, 
 int dcpt_conv_ln_fwd(const float* x, const float* w, const float* lnw, const float* lnb, const float* res, int relu, float* z,
                      float* y, float* mu, float* rstd, void* ws, size_t ws_bytes, int B, int H, int W, int Cin, int Cout,
                      int ksize, dcpt_stream_t stream);
-/* dres (may be NULL) receives the gradient of the residual input; dx may be NULL */
+/* dres (may be NULL) receives the gradient of the residual input; dx may be NULL.  dx = dx_add + conv^T(dz) (dx_add NHWC [B][H][W][Cin] or
+ * NULL; may alias dx) -- the shortcut gradient of a BottleneckBlock (:227-243) summed in the data-gradient GEMM's epilogue */
 int dcpt_conv_ln_bwd(const float* dy, const float* x, const float* w, const float* lnw, const float* z, const float* y,
-                     const float* mu, const float* rstd, float* dx, float* dw, float* dlnw, float* dlnb, float* dres, void* ws,
-                     size_t ws_bytes, int B, int H, int W, int Cin, int Cout, int ksize, int relu, dcpt_stream_t stream);
-/* ABI 13: dx = dx_add + conv^T(dz) (dx_add NHWC [B][H][W][Cin] or NULL; may alias dx) -- the shortcut gradient of a BottleneckBlock
- * (:227-243) summed in the data-gradient GEMM's epilogue */
-int dcpt_conv_ln_bwd_acc(const float* dy, const float* x, const float* w, const float* lnw, const float* z, const float* y,
-                         const float* mu, const float* rstd, const float* dx_add, float* dx, float* dw, float* dlnw, float* dlnb, float* dres,
-                         void* ws, size_t ws_bytes, int B, int H, int W, int Cin, int Cout, int ksize, int relu, dcpt_stream_t stream);
+                     const float* mu, const float* rstd, const float* dx_add, float* dx, float* dw, float* dlnw, float* dlnb, float* dres,
+                     void* ws, size_t ws_bytes, int B, int H, int W, int Cin, int Cout, int ksize, int relu, dcpt_stream_t stream);
 /* downsample layer :596-602: Conv2d(Cin, Cout, 1, bias=False) -> MaxPool2d(2,2) -> ReLU; y [B][H/2][W/2][Cout] */
 size_t dcpt_conv1x1_pool_relu_ws_bytes(int B, int H, int W, int Cin, int Cout, int backward);
 int dcpt_conv1x1_pool_relu_fwd(const float* x, const float* w, float* z, float* y, void* ws, size_t ws_bytes, int B, int H, int W,
@@ -706,10 +679,6 @@ int dcpt_split_channels(const float* cat, float* a, float* b, int64_t M, int Ca,
  * {1: linear, 3: leaky relu(alpha)}; grad 0: forward, 1: first derivative w.r.t. x using `ref` sign. */
 int dcpt_fused_bias_act(const float* x, const float* bias, const float* ref, float* y, int64_t n, int size_b,
                         int64_t step_b, int act, int grad, float alpha, float scale, dcpt_stream_t stream);
-
-/* ---- layout helpers (arbitrary C) ----------------------------------------------------------- */
-int dcpt_nchw_to_nhwc(const float* x, float* y, int B, int C, int HW, dcpt_stream_t stream);
-int dcpt_nhwc_to_nchw(const float* x, float* y, int B, int C, int HW, dcpt_stream_t stream);
 
 /* ---- validation metrics: the sums behind PSNR and SSIM, on the device ----------------------------------
  * replaces the host arithmetic of basicsr/metrics/psnr_ssim.py:11-75 (calculate_psnr), :113-183 (calculate_ssim) and :483-512 (_ssim)

@@ -1,7 +1,8 @@
-"""CPU: the C-ABI library builds, loads and exports every symbol include/dcpt_hip.h declares;
+"""CPU: the C-ABI library builds, loads and exports every symbol include/dcpt_hip.h declares, and no other;
 the Python binding table mirrors the header; the product path refuses CPU tensors (no fallback)."""
 import os
 import re
+import subprocess
 
 import pytest
 import torch
@@ -25,7 +26,11 @@ def test_library_builds_and_exports_header_symbols():
     for s in syms:
         assert hasattr(lib, s), f"{s} declared in dcpt_hip.h but not exported"
     assert sorted(_lib.SIGNATURES.keys()) == syms, "ctypes table and header disagree"
-    assert lib.dcpt_abi_version() == _lib.ABI_VERSION == 15
+    # and the reverse: every unmangled dcpt_* function the library defines is declared (a deleted declaration whose extern "C" body stayed)
+    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    exported = sorted(f[2] for f in (ln.split() for ln in out.splitlines()) if len(f) == 3 and f[1] in "TW" and f[2].startswith("dcpt_"))
+    assert exported == syms, f"exported but not declared in dcpt_hip.h: {sorted(set(exported) - set(syms))}"
+    assert lib.dcpt_abi_version() == _lib.ABI_VERSION == 16
 
 
 def test_workspace_queries_need_no_gpu():

@@ -33,7 +33,7 @@ def test_new_entry_points_in_header_table_and_library():
         assert s in _lib.SIGNATURES, f"{s} is not in dcpt_amd._lib.SIGNATURES"
         assert s in exported, f"{s} is not exported by the library"
     lib = _lib.load()
-    assert lib.dcpt_abi_version() == _lib.ABI_VERSION == 15   # purely additive
+    assert lib.dcpt_abi_version() == _lib.ABI_VERSION == 16
     assert lib.dcpt_mix_stride_bwd_ws_bytes(2 * 4 * 4 * 180) == lib.dcpt_mix_bwd_ws_bytes(2 * 4 * 4 * 180) > 0
 
 

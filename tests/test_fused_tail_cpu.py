@@ -16,7 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("dcpt_grad_norm_ws_bytes", "dcpt_grad_norm", "dcpt_adamw_step_ex")
 
 
-def test_header_and_ctypes_table_carry_the_three_names_and_abi_stays_15():
+def test_header_and_ctypes_table_carry_the_three_names_and_the_abi_version():
     from dcpt_amd import _lib
 
     txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "dcpt_hip.h")).read(), flags=re.S)
@@ -25,7 +25,7 @@ def test_header_and_ctypes_table_carry_the_three_names_and_abi_stays_15():
         assert re.search(r"\b%s\s*\(" % n, txt), f"{n} is not declared in dcpt_hip.h"
         assert n in _lib.SIGNATURES and hasattr(lib, n)
     assert "dcpt_adamw_step" in _lib.SIGNATURES   # the plain entry stays
-    assert lib.dcpt_abi_version() == _lib.ABI_VERSION == 15
+    assert lib.dcpt_abi_version() == _lib.ABI_VERSION == 16
 
 
 def test_grad_norm_workspace_query():

@@ -813,8 +813,8 @@ def test_bf16_training_trajectory_tracks_fp32(dev):
 
 
 def test_packed_weights_cache_is_exact_and_follows_the_parameters(dev):
-    """dcpt_nafblock_wpack_bf16 + the *_packed entry points (functional.PackedWeightsBf16): bit-identical outputs and gradients to the
-    per-call packs; ONE pack serves the forward, the backward and a second forward; an in-place parameter update (what an optimizer
+    """dcpt_nafblock_wpack_bf16 + the ``packed`` argument of dcpt_nafblock_fwd_bf16 / bwd_bf16 (functional.PackedWeightsBf16): bit-identical
+    outputs and gradients to the per-call packs; ONE pack serves the forward, the backward and a second forward; an in-place parameter update (what an optimizer
     step or load_state_dict does) refreshes it; the module keeps its cache out of the state dict."""
     from basicsr.archs.nafnet_arch import NAFBlock
     from dcpt_amd import functional as DF
@@ -848,6 +848,35 @@ def test_packed_weights_cache_is_exact_and_follows_the_parameters(dev):
     assert not torch.equal(ref2[0], ref[0])
     assert torch.equal(ref2[0], got2[0]) and torch.equal(ref2[1], got2[1]) and all(torch.equal(a, b) for a, b in zip(ref2[2], got2[2]))
     assert not any("packed" in k for k in blk.state_dict())
+
+
+@pytest.mark.parametrize("c", [64, 256])
+def test_nafblock_bf16_packs_in_the_call_without_a_cache(dev, c):
+    """packed=None reaches dcpt_nafblock_fwd_bf16 / bwd_bf16 as packed == NULL: the call packs its operand copies into the workspace.
+    Against packed=PackedWeightsBf16() (packed once, ahead of the call), forward + backward, bit for bit -- at the widths on either side
+    of dcpt_nafblock_bf16_fused_ffn (64: 1, 256: 2), which take different pack layouts."""
+    from basicsr.archs.nafnet_arch import NAFBlock
+    from dcpt_amd import _lib
+    from dcpt_amd import functional as DF
+    from dcpt_amd.keyed_init import fill_module_
+
+    assert _lib.load().dcpt_nafblock_bf16_fused_ffn(c) == (1 if c == 64 else 2)
+    blk = fill_module_(NAFBlock(c)).to(dev)
+    x = keyed_input("pknull.x", (1, c, 8, 8), lo=-1.5, hi=1.5).to(dev).bfloat16().contiguous(memory_format=torch.channels_last)
+    gw = keyed_input("pknull.g", (1, c, 8, 8), lo=-1, hi=1).to(dev).bfloat16().contiguous(memory_format=torch.channels_last)
+
+    def run(packed):
+        for p in blk.parameters():
+            p.grad = None
+        xi = x.clone().requires_grad_(True)
+        y = DF.nafblock_bf16(xi, blk.fused_params(), packed=packed)
+        y.backward(gw)
+        return [y.detach().clone(), xi.grad.clone()] + [p.grad.clone() for p in blk.parameters()]
+
+    ref, got = run(DF.PackedWeightsBf16()), run(None)
+    assert len(ref) == len(got) == 2 + len(_lib.PARAM_FIELDS)
+    for k, (a, b) in enumerate(zip(ref, got)):
+        assert torch.equal(a, b), k
 
 
 @pytest.mark.gpu
@@ -1069,6 +1098,6 @@ def test_dc_head_bf16_cached_conv_packs(dev):
     y = torch.zeros(1, 8, 8, 64, dtype=torch.bfloat16, device=dev)
     ws = torch.zeros(lib.dcpt_conv1x1_pool_relu_bf16_ws_bytes(1, 16, 16, 32, 64, 0), dtype=torch.uint8, device=dev)
     small = torch.zeros(64, dtype=torch.uint8, device=dev)
-    rc = lib.dcpt_conv1x1_pool_relu_fwd_bf16_packed(x.data_ptr(), w.data_ptr(), small.data_ptr(), small.numel(), z.data_ptr(), y.data_ptr(),
+    rc = lib.dcpt_conv1x1_pool_relu_fwd_bf16(x.data_ptr(), w.data_ptr(), small.data_ptr(), small.numel(), z.data_ptr(), y.data_ptr(),
                                                     ws.data_ptr(), ws.numel(), 1, 16, 16, 32, 64, None)
     assert rc != 0 and b"packed weights too small" in lib.dcpt_last_error()

@@ -68,7 +68,7 @@ def test_conv_ln(dev, B, Cin, Cout, H, W, ks, relu, res):
                                         (3, 64, 13, 11, True), (1, 128, 224, 224, True), (1, 40, 9, 9, True), (2, 64, 225, 223, True)])
 def test_bottleneck_node(dev, B, C, H, W, bf):
     """DF.bottleneck (the BottleneckBlock of the reference, degrad_classify_arch.py:132-243, as ONE autograd node with the shortcut
-    gradient summed in conv1's data-gradient GEMM: dcpt_conv_ln_bwd_acc*) against the PyTorch-CPU restatement of the reference lines (fp32)
+    gradient summed in conv1's data-gradient GEMM: the dx_add of dcpt_conv_ln_bwd*) against the PyTorch-CPU restatement of the reference lines (fp32)
     and against the three-node chain of conv_ln calls it replaces (both dtypes)."""
     from dcpt_amd import functional as DF
 

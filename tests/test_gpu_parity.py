@@ -251,7 +251,7 @@ def test_down_up(dev, B, C, H, W):
 @pytest.mark.parametrize("B,C,H,W,bf", [(2, 8, 4, 6, False), (1, 64, 16, 16, False), (2, 16, 8, 4, True), (1, 64, 16, 16, True)])
 def test_down_skip_node(dev, B, C, H, W, bf):
     """DF.down2x2_skip: an encoder group's output with its two consumers (down layer, skip connection; reference nafnet_arch.py:255-258,
-    :264-265) as one autograd node, the skip's gradient summed in the down layer's scatter epilogue (dcpt_down2x2_bwd_acc*): against
+    :264-265) as one autograd node, the skip's gradient summed in the down layer's scatter epilogue (the dx_add of dcpt_down2x2_bwd*): against
     F.conv2d + a second use of x on the CPU (fp32) and against the two-node form (both dtypes)."""
     from dcpt_amd import functional as DF
 

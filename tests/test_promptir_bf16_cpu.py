@@ -47,7 +47,7 @@ def test_ws_queries_reject():
     assert lib.dcpt_mdta_bf16_ws_bytes(2, 16, 16, 264, 1, 0) == 0     # head width 264 > 256
     assert lib.dcpt_mdta_bf16_ws_bytes(2, 16, 16, 48, 12, 0) == 0     # head width 4
     assert lib.dcpt_mdta_bf16_ws_bytes(2, 16, 16, 1056, 4, 0) == 0    # C > 1024
-    assert lib.dcpt_abi_version() == 15
+    assert lib.dcpt_abi_version() == 16
     # the GDFN of the 704-channel block (hidden int(704 * 2.66) = 1872) at PromptIR's level-3 maps of 128 / 64 patches
     for hw in (32, 16):
         assert lib.dcpt_gdfn_bf16_ws_bytes(2, hw, hw, 704, 1872, 1) > 0

@@ -46,7 +46,7 @@ def test_ws_queries_without_gpu():
     assert lib.dcpt_mdta_bf16_ws_bytes(2, 16, 16, 48, 5, 0) == 0      # C % heads
     assert lib.dcpt_mdta_bf16_ws_bytes(2, 16, 16, 48, 12, 0) == 0     # head width 4
     assert lib.dcpt_gdfn_bf16_ws_bytes(2, 16, 16, 48, 0, 0) == 0      # hidden
-    assert lib.dcpt_abi_version() == 15
+    assert lib.dcpt_abi_version() == 16
 
 
 def _err(rc):

@@ -32,7 +32,7 @@ def test_symbols_in_header_signatures_and_library():
         assert len(_lib.SIGNATURES[name][1]) == _header_argc(name), name
         assert re.search(r"\sT\s+" + name + r"$", exported, flags=re.M), f"{name} is not exported"
         assert getattr(lib, name).argtypes is not None
-    assert lib.dcpt_abi_version() == _lib.ABI_VERSION == 15   # purely additive
+    assert lib.dcpt_abi_version() == _lib.ABI_VERSION == 16
     text = open(os.path.join(ROOT, "include", "dcpt_hip.h")).read()
     assert "arch_util.py:378-396" in text and "nafnet_arch.py:277-288" in text   # the prototypes cite the reference
 
