@@ -8,6 +8,13 @@ Every RCAB is one autograd node (``dcpt_rcab_*``: conv1 + bias + ReLU, conv2 + b
 the CA FCs, ``x + res_scale * t * s``); every group conv and ``conv_after_body`` is ``dcpt_conv3x3_res_*`` with the skip as its residual;
 every Upsample stage is ``dcpt_conv3x3_ps_*`` (3 x 3 conv + PixelShuffle(r) in one GEMM).  Feature maps are channels_last.  Child modules
 only own the parameters.
+
+``act_dtype="bf16"`` (this repo's extension, default "fp32"; ``network_g.act_dtype`` in the options, ``set_act_dtype`` on an existing network):
+INFERENCE on bf16 activation storage.  ``conv_first`` emits a bf16 map, every RCAB (``dcpt_rcab_fwd_bf16``), group conv / ``conv_after_body``
+(``dcpt_conv3x3_res_fwd_bf16``) and Upsample stage (``dcpt_conv3x3_ps_fwd_bf16``) reads and writes bf16 maps, ``conv_last`` takes the bf16 map
+to the fp32 image: no fp32 feature map of the network's width exists.  Parameters, accumulation, the pooled mean, the CA FCs and the sigmoid
+stay fp32.  There is no backward pass: a bf16 forward that would have to record one raises ``NotImplementedError``.  The bf16 operand images
+of the 3 x 3 weights are cached per conv (``DF.PackedConvBf16``) and the stale ones refreshed in one call at the top of the forward.
 """
 from __future__ import annotations
 
@@ -18,6 +25,19 @@ import torch.nn as nn
 
 from basicsr.utils.registry import ARCH_REGISTRY
 from dcpt_amd import functional as DF
+
+
+_ACT_DTYPES = ("fp32", "bf16")
+
+
+def _pack_of(conv):
+    """the conv's cache of its bf16 operand images (a plain attribute: not part of the state_dict); None for a conv wider than the cached
+    form takes (its entry point then packs in the call)"""
+    if conv.out_channels > 1024:
+        return None
+    if getattr(conv, "_packed_bf16", None) is None:
+        conv._packed_bf16 = DF.PackedConvBf16()
+    return conv._packed_bf16
 
 
 class ChannelAttention(nn.Module):
@@ -45,6 +65,9 @@ class RCAB(nn.Module):
 
     def forward(self, x):
         c1, c2, att = self.rcab[0], self.rcab[2], self.rcab[3].attention
+        if x.dtype == torch.bfloat16:   # bf16 storage (RCAN.set_act_dtype): the maps follow the dtype conv_first emitted
+            return DF.rcab_bf16(x, c1.weight, c1.bias, c2.weight, c2.bias, att[1].weight, att[1].bias, att[3].weight, att[3].bias, self.res_scale,
+                                _pack_of(c1), _pack_of(c2))
         return DF.rcab(x, c1.weight, c1.bias, c2.weight, c2.bias, att[1].weight, att[1].bias, att[3].weight, att[3].bias, self.res_scale)
 
 
@@ -59,6 +82,8 @@ class ResidualGroup(nn.Module):
         t = x
         for blk in self.residual_group:
             t = blk(t)
+        if x.dtype == torch.bfloat16:
+            return DF.conv3x3_res_bf16(t, self.conv.weight, self.conv.bias, x, _pack_of(self.conv))
         return DF.conv3x3_res(t, self.conv.weight, self.conv.bias, x)
 
 
@@ -81,15 +106,20 @@ class Upsample(nn.Sequential):
     def forward(self, x):
         mods = list(self)
         for conv, shuffle in zip(mods[0::2], mods[1::2]):
-            x = DF.conv3x3_ps(x, conv.weight, conv.bias, shuffle.upscale_factor)
+            if x.dtype == torch.bfloat16:
+                x = DF.conv3x3_ps_bf16(x, conv.weight, conv.bias, shuffle.upscale_factor, _pack_of(conv))
+            else:
+                x = DF.conv3x3_ps(x, conv.weight, conv.bias, shuffle.upscale_factor)
         return x
 
 
 @ARCH_REGISTRY.register()
 class RCAN(nn.Module):
     def __init__(self, num_in_ch, num_out_ch, num_feat=64, num_group=10, num_block=16, squeeze_factor=16, upscale=4, res_scale=1,
-                 img_range=255.0, rgb_mean=(0.4488, 0.4371, 0.4040)):
+                 img_range=255.0, rgb_mean=(0.4488, 0.4371, 0.4040), act_dtype="fp32"):
         super().__init__()
+        if act_dtype not in _ACT_DTYPES:
+            raise ValueError(f"act_dtype must be one of {_ACT_DTYPES}, got {act_dtype!r}")
         if num_feat % 4:
             raise NotImplementedError(f"num_feat={num_feat}: the RCAN kernels need a multiple of 4 channels")
         if num_feat // squeeze_factor < 1:
@@ -103,6 +133,26 @@ class RCAN(nn.Module):
         self.conv_after_body = nn.Conv2d(num_feat, num_feat, 3, 1, 1)
         self.upsample = Upsample(upscale, num_feat)
         self.conv_last = nn.Conv2d(num_feat, num_out_ch, 3, 1, 1)
+        self._num_feat = num_feat
+        self.set_act_dtype(act_dtype)
+
+    def set_act_dtype(self, act_dtype):
+        """"fp32" (the reference's arithmetic) or "bf16" (inference on bf16 activation storage); the parameters are untouched"""
+        if act_dtype not in _ACT_DTYPES:
+            raise ValueError(f"act_dtype must be one of {_ACT_DTYPES}, got {act_dtype!r}")
+        if act_dtype == "bf16" and self._num_feat % 8:
+            raise ValueError(f"act_dtype='bf16' needs num_feat % 8 == 0 (16-byte bf16 channel vectors), got num_feat={self._num_feat}")
+        self.act_dtype = act_dtype
+
+    def _convs_bf16(self):
+        """(cache, weight) of every 3 x 3 conv of the body and the tail that has a cached bf16 operand image"""
+        convs = self.__dict__.get("_bf16_convs")
+        if convs is None:   # (a plain attribute, not a registered submodule list)
+            convs = [m for part in (self.body, self.upsample) for m in part.modules() if isinstance(m, nn.Conv2d) and m.kernel_size == (3, 3)]
+            convs.append(self.conv_after_body)
+            convs = [m for m in convs if _pack_of(m) is not None]
+            self.__dict__["_bf16_convs"] = convs
+        return [(m._packed_bf16, m.weight) for m in convs]
 
     def forward(self, x):
         self.mean = self.mean.type_as(x)
@@ -110,11 +160,21 @@ class RCAN(nn.Module):
         mean = self.mean.reshape(-1)
         if mean.numel() != cin:
             raise ValueError(f"RCAN: rgb_mean has {mean.numel()} entries for a {cin}-channel input")
+        bf = self.act_dtype == "bf16"
+        if bf:
+            if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+                raise NotImplementedError("RCAN: bf16 storage for RCAN is inference-only (there is no bf16 backward pass); run the forward under "
+                                          "torch.no_grad() or switch to set_act_dtype('fp32')")
+            if x.is_cuda:   # the operand images of all 3 x 3 weights in one call where they are stale; the convs then find their pack current
+                DF.pack_convs_bf16(self._convs_bf16())
         xn = DF.img_affine(x, mean, self.img_range, 0)
-        x_first = DF.conv3x3_in(xn, self.conv_first.weight, self.conv_first.bias)
+        x_first = DF.conv3x3_in(xn, self.conv_first.weight, self.conv_first.bias, out_bf16=bf)
         t = x_first
         for group in self.body:
             t = group(t)
-        res = DF.conv3x3_res(t, self.conv_after_body.weight, self.conv_after_body.bias, x_first)
+        if bf:
+            res = DF.conv3x3_res_bf16(t, self.conv_after_body.weight, self.conv_after_body.bias, x_first, _pack_of(self.conv_after_body))
+        else:
+            res = DF.conv3x3_res(t, self.conv_after_body.weight, self.conv_after_body.bias, x_first)
         out = DF.conv3x3_out(self.upsample(res), self.conv_last.weight, self.conv_last.bias)
         return DF.img_affine(out, mean, self.img_range, 1)

@@ -4,7 +4,7 @@ contract (that is bench.py).  Prints one JSON line per workload.
 
     python bench_extra.py --workload dcpt|dcpt_swinir|restormer|promptir|infer2k|naf|swinir|rcan|val_metrics|step_tail|tlsc [--dtype fp32|bf16] [--steps K] [--warmup W]
 
-``--dtype bf16`` (dcpt, naf, infer2k, restormer, promptir): every feature map of the encoder in bf16 storage with fp32 accumulation (act_dtype="bf16";
+``--dtype bf16`` (dcpt, naf, infer2k, restormer, promptir; rcan: the inference line only, next to fp32): every feature map of the encoder in bf16 storage with fp32 accumulation (act_dtype="bf16";
 dcpt: the classifier head too unless --head-dtype fp32); images, parameters and the optimizer stay fp32.  Its lines carry BOTH
 rooflines: the bf16 MFMA peak (2.5 PF dense) and the HBM roof with the bf16 algorithmic bytes -- in bf16 the network is HBM-bound
 (SURVEY 8d).
@@ -238,9 +238,11 @@ def rcan_fwd_flops_per_lr_pixel(num_in_ch=3, num_out_ch=3, num_feat=64, num_grou
     return body + 2 * 9 * num_in_ch * C + up + area * 2 * 9 * C * num_out_ch
 
 
-def run_rcan(dev, steps=5, warmup=2, B=16, S=48, S_inf=256):
+def run_rcan(dev, steps=5, warmup=2, B=16, S=48, S_inf=256, dtype="fp32"):
     """the default x4 RCAN (64 features, 10 x 16 RCABs): one training step (fwd + L1 + bwd + AdamW) at B x S^2 LR patches, and inference of
-    one S_inf^2 LR image; rates against the fp32-MFMA roof from the FLOPs counted above"""
+    one S_inf^2 LR image; rates against the fp32-MFMA roof from the FLOPs counted above.  ``dtype="bf16"``: the inference line also holds the
+    same network on bf16 activation storage (set_act_dtype), fp32 and bf16 images alternating in this process, with the peak memory of each
+    above the resident state (weights, weight packs, workspaces); training stays fp32 (there is no bf16 backward)"""
     from basicsr.archs import build_network
     from dcpt_amd.keyed_init import fill_module_
     from dcpt_amd.optim import FusedAdamW
@@ -277,6 +279,35 @@ def run_rcan(dev, steps=5, warmup=2, B=16, S=48, S_inf=256):
     infer_line = dict(workload=f"RCAN x4 inference, 1 x {S_inf}x{S_inf} LR -> {4 * S_inf}x{4 * S_inf}, fp32",
                       fwd_mflop_per_lr_pixel=round(fpp / 1e6, 3), ms_per_image=round(dt_inf * 1e3, 2), alg_tflops=round(f_inf / dt_inf / 1e12, 2),
                       mfma_frac=round(f_inf / dt_inf / 157.3e12, 4), roof_ms=round(f_inf / 157.3e12 * 1e3, 2), steps=steps, warmup=warmup)
+    if dtype == "bf16":
+        times, peaks = {"fp32": [], "bf16": []}, {}
+        for act in ("fp32", "bf16"):   # warm both paths (workspaces, weight packs), then the peak of one image above what stays resident
+            net.set_act_dtype(act)
+            for _ in range(max(warmup, 1)):
+                infer()
+            torch.cuda.synchronize()
+            base = torch.cuda.memory_allocated()
+            torch.cuda.reset_peak_memory_stats()
+            infer()
+            torch.cuda.synchronize()
+            peaks[act] = torch.cuda.max_memory_allocated() - base
+        for _ in range(steps):
+            for act in ("fp32", "bf16"):
+                net.set_act_dtype(act)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                infer()
+                torch.cuda.synchronize()
+                times[act].append(time.perf_counter() - t0)
+        net.set_act_dtype("fp32")
+        med = {k: sorted(v)[len(v) // 2] for k, v in times.items()}
+        infer_line.update(workload=f"RCAN x4 inference, 1 x {S_inf}x{S_inf} LR -> {4 * S_inf}x{4 * S_inf}, fp32 and bf16 storage alternating",
+                          ms_per_image=round(med["fp32"] * 1e3, 2), ms_per_image_bf16=round(med["bf16"] * 1e3, 2),
+                          ms_per_image_min=round(min(times["fp32"]) * 1e3, 2), ms_per_image_bf16_min=round(min(times["bf16"]) * 1e3, 2),
+                          bf16_speedup=round(med["fp32"] / med["bf16"], 3), alg_tflops=round(f_inf / med["fp32"] / 1e12, 2),
+                          alg_tflops_bf16=round(f_inf / med["bf16"] / 1e12, 2), mfma_frac=round(f_inf / med["fp32"] / 157.3e12, 4),
+                          peak_act_mem_mb=round(peaks["fp32"] / 2 ** 20, 1), peak_act_mem_mb_bf16=round(peaks["bf16"] / 2 ** 20, 1),
+                          timing="median of per-image wall times, one synchronize per image")
     return [train, infer_line]
 
 
@@ -627,7 +658,9 @@ def main():
         res = run_swinir(dev, args.steps, args.warmup, args.batch or 8, args.size or (64 if sr else 256),
                          train_batches=(args.batch or 8, 4, 2, 1) if sr else (12, 8, 4, 2, 1), upsampler=args.upsampler, upscale=args.upscale)
     elif args.workload == "rcan":
-        lines = run_rcan(dev, args.steps, args.warmup, args.batch or 16, args.size or 48)
+        if args.dtype not in ("fp32", "bf16"):
+            raise SystemExit("--workload rcan: --dtype fp32 or bf16")
+        lines = run_rcan(dev, args.steps, args.warmup, args.batch or 16, args.size or 48, dtype=args.dtype)
         for line in lines[:-1]:
             print(json.dumps(line), flush=True)
         res = lines[-1]

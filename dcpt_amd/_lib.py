@@ -276,6 +276,13 @@ SIGNATURES = {
     "dcpt_up2_conv3x3_act_fwd": (cint, [f32p, f32p, f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint, C.c_float, stream_t]),
     "dcpt_up2_conv3x3_act_bwd": (cint, [f32p, f32p, f32p, f32p, f32p, f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint, C.c_float,
                                         stream_t]),
+    "dcpt_rcab_bf16_ws_bytes": (sz, [cint, cint, cint, cint, cint]),
+    "dcpt_rcab_fwd_bf16": (cint, [C.POINTER(RcabParams), C.c_void_p, sz, C.c_void_p, sz, f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint, cint,
+                                  C.c_float, stream_t]),
+    "dcpt_conv3x3_res_bf16_ws_bytes": (sz, [cint, cint, cint, cint]),
+    "dcpt_conv3x3_res_fwd_bf16": (cint, [f32p, f32p, C.c_void_p, sz, f32p, f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint, stream_t]),
+    "dcpt_conv3x3_ps_bf16_ws_bytes": (sz, [cint, cint, cint, cint, cint]),
+    "dcpt_conv3x3_ps_fwd_bf16": (cint, [f32p, f32p, C.c_void_p, sz, f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint, cint, stream_t]),
     "dcpt_conv3x3_ps_out_ws_bytes": (sz, [cint, cint, cint, cint, cint, cint, cint]),
     "dcpt_conv3x3_ps_out_fwd": (cint, [f32p, f32p, f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint, cint, cint, stream_t]),
     "dcpt_conv3x3_ps_out_bwd": (cint, [f32p, f32p, f32p, f32p, f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint, cint, cint, stream_t]),

@@ -87,7 +87,11 @@ __device__ __forceinline__ float f8_sum(f8 a) { return f4_sum(a.lo) + f4_sum(a.h
 
 // ---- launchers of the bf16 kernels (gemm_bf16.hip, bf16_ops.hip) ----------------------------------------------------------
 enum GemmEpiB { EB_PLAIN = 0, EB_BIAS = 1, EB_RESID = 2, EB_SGBWD = 3, EB_BIASGATE = 4, EB_DOTCOL = 5, EB_SCATTER = 7, EB_SCATTER_ADD = 8,
-                EB_LNFWD = 9, EB_LNBWDM = 10, EB_MUL = 11 };
+                EB_LNFWD = 9, EB_LNBWDM = 10, EB_MUL = 11,
+                // RCAN in bf16 storage (rcan_bf16.hip), conv3 operand only, 128-row kernel only:
+                EB_BIASRELU = 12,   // C = relu(acc + bias)
+                EB_BIASCOL = 13,    // C = acc + bias AND colpart[(tile, image)][n] = the fp32 column sums of acc + bias over the tile's rows (row tiles per image)
+                EB_PSHUF = 14 };    // C = PixelShuffle(psr)(acc + bias): the scatter epilogue with a bias, for psr in {2, 3}
 
 // C[m][n] = sum_k A[m][k] * Bw[n][k]  on v_mfma_f32_32x32x16_bf16; A, Bw, C, res, aux, gate bf16; bias / cscale / colpart fp32.
 struct GemmNTB {
@@ -129,6 +133,15 @@ struct GemmNTB {
     const bf16_t* ymask;
     int relu;
     float eps;
+    // EB_BIASCOL (the bf16 twin of gemm.h's E_BIASCOL): P = pixels per image, M % P == 0.  The rows are tiled PER IMAGE (B cdiv(P, 128) row tiles,
+    // the last of an image ragged) so that an image's sums do not depend on its place in the batch; colpart has the fp32 kernel's layout --
+    // cdiv(M, 128) + B - 1 rows, image b's in rows (b P) / 128 + b .. ((b + 1) P - 1) / 128 + b, each written by exactly one block (no atomics) --
+    // and is summed by rcan.hip's CA kernel.
+    int P;
+    // EB_PSHUF: C is the fine NHWC image [.][psr gH][psr gW][gC], N = psr^2 gC, GEMM column (i psr + j) gC + c is fine pixel (psr h + i, psr w + j),
+    // channel c, and it is conv channel c psr^2 + i psr + j: Bw rows and bias entries are read in the conv's own order (a cached operand image
+    // serves as it is), the permutation is applied by the loader / the epilogue.
+    int psr;
 };
 // N (= row length) for which the two LayerNorm epilogues exist on a launch of M rows; conv3: the implicit 3 x 3 form of the GEMM
 bool gemm_nt_bf16_ln_epi_ok(int64_t M, int N, int K, int conv3, int gC);

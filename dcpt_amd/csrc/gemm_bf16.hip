@@ -56,7 +56,14 @@ __global__ __launch_bounds__(256) void gemm_nt_bf16_kernel(const GemmNTB pin) {
     const int wm = wave / WN, wn = wave % WN;
     const int Ch = p.N / 2;
     const int tilesN = GATE ? (Ch + BN / 2 - 1) / (BN / 2) : (p.N + BN - 1) / BN;
-    const int64_t m0 = (int64_t)(lin / tilesN) * BM;
+    int64_t m0 = (int64_t)(lin / tilesN) * BM;
+    if constexpr (EK == EB_BIASCOL) {
+        // row tiles PER IMAGE (the last one of an image ragged): what an image's column sums are added from then depends on the image alone, not on
+        // where it lies in the batch -- a batched forward equals the one-image forwards bit for bit.  Rows past the image's end are rows past M.
+        const int tpi = (p.P + BM - 1) / BM, tm = lin / tilesN, b = tm / tpi;
+        m0 = (int64_t)b * p.P + (int64_t)(tm - b * tpi) * BM;
+        p.M = (int64_t)(b + 1) * p.P;
+    }
     const int n0 = (lin % tilesN) * (GATE ? BN / 2 : BN);
 
     // conv3: the window starts one image row + one pixel before the tile's first pixel (clipped at the tensor start)
@@ -67,7 +74,8 @@ __global__ __launch_bounds__(256) void gemm_nt_bf16_kernel(const GemmNTB pin) {
     }
     if constexpr (GATH) apix0 = fine_elem(p, apix0);   // (elements, not pixels)
     const i32x4 rsA = make_rsrc_dma(p.A + (GATH ? apix0 : apix0 * (int64_t)(CONV ? p.gC : p.lda)));
-    const i32x4 rsB = make_rsrc_dma(p.Bw + (GATE ? 0 : (int64_t)n0 * p.K));
+    constexpr bool PSH = (EK == EB_PSHUF);   // Bw rows in the conv's channel order: GEMM column n reads row (n % gC) psr^2 + n / gC
+    const i32x4 rsB = make_rsrc_dma(p.Bw + ((GATE || PSH) ? 0 : (int64_t)n0 * p.K));
     // staging map: thread -> row (tid >> 3) + 32 * pass, LDS slot tid & 7 = logical 16-byte chunk slot ^ ((row >> 1) & 7)
     const int lrow = tid >> 3;
     const int lk = 8 * ((tid & 7) ^ ((tid >> 4) & 7));   // first k element of this thread's chunk inside a k-tile
@@ -96,6 +104,9 @@ __global__ __launch_bounds__(256) void gemm_nt_bf16_kernel(const GemmNTB pin) {
             const int hl = nl % (BN / 2);
             const int n = (nl < BN / 2 ? 0 : Ch) + n0 + hl;
             boff[i] = (n0 + hl < Ch) ? ((uint32_t)n * (uint32_t)p.K + (uint32_t)lk) * 2u : ROW_SENT;
+        } else if constexpr (PSH) {
+            const int n = n0 + nl, ij = n / p.gC, row = (n - ij * p.gC) * (p.psr * p.psr) + ij;
+            boff[i] = (n < p.N) ? ((uint32_t)row * (uint32_t)p.K + (uint32_t)lk) * 2u : ROW_SENT;
         } else {
             boff[i] = (n0 + nl < p.N) ? ((uint32_t)nl * (uint32_t)p.K + (uint32_t)lk) * 2u : ROW_SENT;
         }
@@ -204,10 +215,12 @@ int launch_nt(const GemmNTB& p, hipStream_t s) {
     constexpr bool GATE = (EK == EB_BIASGATE);
     const unsigned nb = (unsigned)(p.nb > 0 ? p.nb : 1);
     const int ncols = GATE ? p.N / 2 : p.N;
-    if constexpr (EK == EB_PLAIN || EK == EB_LNFWD || EK == EB_LNBWDM) {
+    constexpr bool CONV_ONLY = (EK == EB_BIASRELU || EK == EB_BIASCOL || EK == EB_PSHUF);   // (checked by launch_gemm_nt_bf16: no plain-A instance)
+    if constexpr (EK == EB_PLAIN || EK == EB_LNFWD || EK == EB_LNBWDM || EK == EB_RESID || CONV_ONLY) {
         if (p.conv3) {
-            if (ncols <= 64) gemm_nt_bf16_kernel<128, 64, 4, 1, EK, 1><<<dim3((unsigned)(cdiv64(p.M, 128) * cdiv(ncols, 64)), nb), dim3(256), 0, s>>>(p);
-            else gemm_nt_bf16_kernel<128, 128, 2, 2, EK, 1><<<dim3((unsigned)(cdiv64(p.M, 128) * cdiv(ncols, 128)), nb), dim3(256), 0, s>>>(p);
+            const int64_t tm = (EK == EB_BIASCOL) ? (p.M / p.P) * cdiv(p.P, 128) : cdiv64(p.M, 128);   // (EB_BIASCOL: row tiles per image)
+            if (ncols <= 64) gemm_nt_bf16_kernel<128, 64, 4, 1, EK, 1><<<dim3((unsigned)(tm * cdiv(ncols, 64)), nb), dim3(256), 0, s>>>(p);
+            else gemm_nt_bf16_kernel<128, 128, 2, 2, EK, 1><<<dim3((unsigned)(tm * cdiv(ncols, 128)), nb), dim3(256), 0, s>>>(p);
             DCPT_CHECK_LAUNCH("gemm_nt_bf16 conv3");
             return DCPT_OK;
         }
@@ -220,15 +233,20 @@ int launch_nt(const GemmNTB& p, hipStream_t s) {
             return DCPT_OK;
         }
     }
-    if (ncols <= (GATE ? 32 : 64)) {
-        const int64_t tiles = cdiv64(p.M, 128) * cdiv(ncols, GATE ? 32 : 64);
-        gemm_nt_bf16_kernel<128, 64, 4, 1, EK><<<dim3((unsigned)tiles, nb), dim3(256), 0, s>>>(p);
+    if constexpr (CONV_ONLY) {
+        dcpt_set_error("gemm_nt_bf16: epilogue %d exists for the conv3 operand only", EK);
+        return DCPT_ERR_ARG;
     } else {
-        const int64_t tiles = cdiv64(p.M, 128) * cdiv(ncols, GATE ? 64 : 128);
-        gemm_nt_bf16_kernel<128, 128, 2, 2, EK><<<dim3((unsigned)tiles, nb), dim3(256), 0, s>>>(p);
+        if (ncols <= (GATE ? 32 : 64)) {
+            const int64_t tiles = cdiv64(p.M, 128) * cdiv(ncols, GATE ? 32 : 64);
+            gemm_nt_bf16_kernel<128, 64, 4, 1, EK><<<dim3((unsigned)tiles, nb), dim3(256), 0, s>>>(p);
+        } else {
+            const int64_t tiles = cdiv64(p.M, 128) * cdiv(ncols, GATE ? 64 : 128);
+            gemm_nt_bf16_kernel<128, 128, 2, 2, EK><<<dim3((unsigned)tiles, nb), dim3(256), 0, s>>>(p);
+        }
+        DCPT_CHECK_LAUNCH("gemm_nt_bf16");
+        return DCPT_OK;
     }
-    DCPT_CHECK_LAUNCH("gemm_nt_bf16");
-    return DCPT_OK;
 }
 
 // ------------------------------------------------------------------------------------------------------------------------
@@ -439,9 +457,19 @@ int launch_gemm_nt_bf16(const GemmNTB& pin, int epi, hipStream_t s) {
     DCPT_CHECK_ARG(p.K % 8 == 0 && p.N % 8 == 0 && p.lda % 8 == 0 && p.ldc % 8 == 0 && p.ldres % 8 == 0,
                    "gemm_nt_bf16: K=%d, N=%d and the row strides must be multiples of 8 (16-byte rows)", p.K, p.N);
     if (p.conv3)
-        DCPT_CHECK_ARG((epi == EB_PLAIN || epi == EB_LNFWD || epi == EB_LNBWDM) && p.gC % 8 == 0 && p.K == 9 * p.gC && p.nb == 1 &&
-                           (double)(130 + 2 * p.gW + 2) * p.gC * 2.0 < 1.0e9,
-                       "gemm_nt_bf16: conv3 needs the plain or a LayerNorm epilogue, K == 9 * gC, gC %% 8 == 0");
+        DCPT_CHECK_ARG((epi == EB_PLAIN || epi == EB_LNFWD || epi == EB_LNBWDM || epi == EB_RESID || epi == EB_BIASRELU || epi == EB_BIASCOL ||
+                        epi == EB_PSHUF) &&
+                           p.gC % 8 == 0 && p.K == 9 * p.gC && p.nb == 1 && (double)(130 + 2 * p.gW + 2) * p.gC * 2.0 < 1.0e9,
+                       "gemm_nt_bf16: conv3 needs the plain, a LayerNorm, the residual or an RCAN epilogue, K == 9 * gC, gC %% 8 == 0");
+    if (epi == EB_BIASRELU || epi == EB_BIASCOL || epi == EB_PSHUF)
+        DCPT_CHECK_ARG(p.conv3 && !p.gather2, "gemm_nt_bf16: the RCAN epilogues (%d) exist for the conv3 operand only", epi);
+    if (epi == EB_BIASCOL)
+        DCPT_CHECK_ARG(p.colpart && p.P > 0 && p.M % p.P == 0 && p.ldc == p.N && (p.M / p.P) * cdiv(p.P, 128) * cdiv(p.N, 32) < (1ll << 31),
+                       "gemm_nt_bf16: column-sum epilogue needs colpart, P > 0 with M %% P == 0, dense rows");
+    if (epi == EB_PSHUF)
+        DCPT_CHECK_ARG((p.psr == 2 || p.psr == 3) && p.N == p.psr * p.psr * p.gC &&
+                           (double)(130 + 2 * p.gW) * (double)(p.psr * p.psr) * p.gC * 2.0 < 1.0e9,
+                       "gemm_nt_bf16: pixel-shuffle epilogue needs psr in {2, 3}, N == psr^2 * gC and a fine image inside the 32-bit window");
     if (p.gather2)
         DCPT_CHECK_ARG((epi == EB_PLAIN || epi == EB_BIAS) && !p.conv3 && p.gC % 8 == 0 && p.K == 4 * p.gC && p.nb == 1 &&
                            (double)(130 + 2 * p.gW) * 4.0 * p.gC * 2.0 < 1.0e9,
@@ -499,6 +527,9 @@ int launch_gemm_nt_bf16(const GemmNTB& pin, int epi, hipStream_t s) {
         case EB_LNFWD: return launch_nt<EB_LNFWD>(p, s);
         case EB_LNBWDM: return launch_nt<EB_LNBWDM>(p, s);
         case EB_MUL: return launch_nt<EB_MUL>(p, s);
+        case EB_BIASRELU: return launch_nt<EB_BIASRELU>(p, s);
+        case EB_BIASCOL: return launch_nt<EB_BIASCOL>(p, s);
+        case EB_PSHUF: return launch_nt<EB_PSHUF>(p, s);
     }
     dcpt_set_error("gemm_nt_bf16: unknown epilogue %d", epi);
     return DCPT_ERR_ARG;

@@ -15,6 +15,15 @@ __device__ __forceinline__ int64_t fine_elem(const P& p, int64_t m) {
     const int64_t b = t / p.gH;
     return ((b * (2 * p.gH) + 2 * h) * (int64_t)(2 * p.gW) + 2 * w) * p.gC;
 }
+// the same for an upscale factor r (EB_PSHUF: fine image r gH x r gW x gC)
+template <typename P>
+__device__ __forceinline__ int64_t fine_elem_r(const P& p, int64_t m, int r) {
+    const int w = (int)(m % p.gW);
+    const int64_t t = m / p.gW;
+    const int h = (int)(t % p.gH);
+    const int64_t b = t / p.gH;
+    return ((b * (r * p.gH) + r * h) * (int64_t)(r * p.gW) + r * w) * p.gC;
+}
 
 template <int EK, int BM, int BN, int NT = 256>   // NT: threads of the block
 __device__ __forceinline__ void epilogue8(const GemmNTB& p, float* __restrict__ Cs, int64_t m0, int n0, int tid) {
@@ -30,7 +39,7 @@ __device__ __forceinline__ void epilogue8(const GemmNTB& p, float* __restrict__ 
     const bool nok = GATE ? (n < Ch) : (n < p.N);
     const int ldres = p.ldres ? p.ldres : p.ldc;
     f8 bias = f8_zero(), bias2 = f8_zero(), cs = f8{make_float4(1.f, 1.f, 1.f, 1.f), make_float4(1.f, 1.f, 1.f, 1.f)};
-    if constexpr (EK == EB_BIAS || EK == EB_RESID || EK == EB_MUL) {
+    if constexpr (EK == EB_BIAS || EK == EB_RESID || EK == EB_MUL || EK == EB_BIASRELU || EK == EB_BIASCOL) {
         if (p.bias && nok) bias = f8_ld(p.bias + n);
     }
     if constexpr (GATE) {
@@ -50,6 +59,19 @@ __device__ __forceinline__ void epilogue8(const GemmNTB& p, float* __restrict__ 
         const int nn = nok ? n : 0;
         const int ij = nn / p.gC, ch = nn - ij * p.gC;
         coladd = (uint32_t)((((ij >> 1) * (2 * p.gW) + (ij & 1)) * p.gC + ch) * 2);
+    }
+    if constexpr (EK == EB_PSHUF) {
+        const int sr = p.psr;
+        cbase = fine_elem_r(p, m0 < p.M ? m0 : 0, sr);
+        const int nn = nok ? n : 0;
+        const int ij = nn / p.gC, ch = nn - ij * p.gC;   // (gC % 8 == 0: the 8 columns are channels ch .. ch + 7 of ONE sub-pixel)
+        coladd = (uint32_t)((((ij / sr) * (sr * p.gW) + (ij % sr)) * p.gC + ch) * 2);
+        if (p.bias && nok) {   // conv channel of (sub-pixel ij, channel c) = c sr^2 + ij
+            const float* bp = p.bias + (int64_t)ch * (sr * sr) + ij;
+            const int st = sr * sr;
+            bias.lo = make_float4(bp[0], bp[st], bp[2 * st], bp[3 * st]);
+            bias.hi = make_float4(bp[4 * st], bp[5 * st], bp[6 * st], bp[7 * st]);
+        }
     }
     const rsrc_t rsC = make_rsrc(p.C + cbase);
     rsrc_t rsR = rsC, rsX = rsC;
@@ -113,6 +135,7 @@ __device__ __forceinline__ void epilogue8(const GemmNTB& p, float* __restrict__ 
             const bool ok = (m0 + rl < p.M) && nok;
             uint32_t o = ok ? ((uint32_t)rl * (uint32_t)p.ldc + (uint32_t)n) * 2u : ROW_SENT;
             if constexpr (SCAT) o = ok ? (uint32_t)((fine_elem(p, m0 + rl) - cbase) * 2) + coladd : ROW_SENT;
+            if constexpr (EK == EB_PSHUF) o = ok ? (uint32_t)((fine_elem_r(p, m0 + rl, p.psr) - cbase) * 2) + coladd : ROW_SENT;
             f8 v;
             v.lo = *reinterpret_cast<const float4*>(&Cs[rl * BN + 8 * q]);
             v.hi = *reinterpret_cast<const float4*>(&Cs[rl * BN + 8 * q + 4]);
@@ -131,8 +154,12 @@ __device__ __forceinline__ void epilogue8(const GemmNTB& p, float* __restrict__ 
                 bbuf_st8(rsC, o, v);
             } else if constexpr (EK == EB_SCATTER_ADD) {
                 bbuf_st8(rsC, o, f8_add(v, pre1[it]));
-            } else if constexpr (EK == EB_BIAS) {
+            } else if constexpr (EK == EB_BIAS || EK == EB_BIASCOL || EK == EB_PSHUF) {
                 bbuf_st8(rsC, o, f8_add(v, bias));
+            } else if constexpr (EK == EB_BIASRELU) {
+                const f8 u = f8_add(v, bias);
+                bbuf_st8(rsC, o, f8{make_float4(fmaxf(u.lo.x, 0.f), fmaxf(u.lo.y, 0.f), fmaxf(u.lo.z, 0.f), fmaxf(u.lo.w, 0.f)),
+                                    make_float4(fmaxf(u.hi.x, 0.f), fmaxf(u.hi.y, 0.f), fmaxf(u.hi.z, 0.f), fmaxf(u.hi.w, 0.f))});
             } else if constexpr (EK == EB_RESID) {
                 bbuf_st8(rsC, o, f8_fma(f8_add(v, bias), cs, pre1[it]));
             } else if constexpr (EK == EB_MUL) {
@@ -225,6 +252,29 @@ __device__ __forceinline__ void epilogue8(const GemmNTB& p, float* __restrict__ 
                 stg4(dst, a);
                 stg4(dst + 4, b);
             }
+        }
+    }
+    if constexpr (EK == EB_BIASCOL) {
+        // column sums of acc + bias BEFORE the rounding to bf16 (gemm_nt_epi.h's E_BIASCOL), over the tile's rows in row order (Cs is intact: the
+        // loop above only read it).  The kernel tiles the rows per image for this epilogue (p.M = the end of the tile's image b), so a tile holds
+        // rows of ONE image: tile j of the image writes colpart row t0 + b + j, t0 = (b P) / BM -- the rows rcan.hip's CA kernel adds up for image
+        // b are t0 + b .. t1 + b, t1 = ((b + 1) P - 1) / BM, which are the image's cdiv(P, BM) tiles, or one row more where the image crosses one
+        // more BM-row boundary of the batch: the image's last tile writes zeros there.  Every row has exactly one writer (no atomics), and the
+        // terms and their order do not depend on b.
+        const int64_t b = m0 / p.P, i0 = b * p.P;
+        const int j = (int)((m0 - i0) / BM);
+        const int hi = (int)((m0 + BM < p.M ? m0 + BM : p.M) - m0);
+        const int64_t t0 = i0 / BM, t1 = (i0 + p.P - 1) / BM;
+        const int64_t row = t0 + b + j;
+        const bool pad = (m0 + BM >= p.M) && (t0 + j < t1);
+        for (int c = tid; c < BN; c += NT) {
+            const int nc = n0 + c;
+            if (nc >= p.N) continue;
+            float sum = 0.f;
+            for (int rl = 0; rl < hi; ++rl) sum += Cs[rl * BN + c];
+            if (p.bias) sum = fmaf((float)hi, p.bias[nc], sum);
+            p.colpart[row * (int64_t)p.N + nc] = sum;
+            if (pad) p.colpart[(row + 1) * (int64_t)p.N + nc] = 0.f;
         }
     }
     if constexpr (EK == EB_DOTCOL) {

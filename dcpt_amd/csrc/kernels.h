@@ -87,6 +87,9 @@ int launch_sca_wgrad(const float* ds_part, int nslices, float* ds, const float* 
 
 // TLSC box mean (arch_util.py:378-396): out[M][C] local k1 x k2 mean of in, replicate-padded; rowsum: [B][H][W-k2+1][C] scratch
 int launch_box_mean(const float* in, float* rowsum, float* out, int B, int H, int W, int C, int k1, int k2, hipStream_t s);
+// rcan.hip: RCAN's channel attention of B images from the per-(128-row tile, image) column sums of t (E_BIASCOL / EB_BIASCOL): pooled, s [B][C]
+int launch_rcan_ca_fwd(const float* colpart, const float* w1, const float* b1, const float* w2, const float* b2, float* pooled, float* sc, int B,
+                       int P, int C, int Cr, hipStream_t s);
 
 enum WPackMode {
     WP_TRANSPOSE = 0,   // out[k][n] = in[n][k] * (rs ? rs[n] : 1)             in: [N][K]

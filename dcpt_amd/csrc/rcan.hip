@@ -337,6 +337,16 @@ int check_ps(int B, int H, int W, int C, int r, const char* who) {
 
 }  // namespace
 
+// the channel-attention kernel on the column sums a conv2 epilogue left (one partial row per (128-row tile, image) pair), for the bf16-storage
+// RCAB (rcan_bf16.hip), whose pooled sums, FCs and sigmoid stay fp32: the launch of dcpt_rcab_fwd below
+int launch_rcan_ca_fwd(const float* colpart, const float* w1, const float* b1, const float* w2, const float* b2, float* pooled, float* sc, int B,
+                       int P, int C, int Cr, hipStream_t s) {
+    const int G = dot_groups(C);
+    ca_fwd_kernel<<<dim3(B), dim3(256), (size_t)(C + Cr + G * C) * 4, s>>>(colpart, w1, b1, w2, b2, pooled, sc, P, C, Cr, G);
+    DCPT_CHECK_LAUNCH("rcab_ca_fwd");
+    return DCPT_OK;
+}
+
 // =====================================================================================================
 extern "C" size_t dcpt_rcab_ws_bytes(int B, int H, int W, int C, int Cr, int backward) {
     if (!rcab_dims_ok(B, H, W, C, Cr)) return 0;

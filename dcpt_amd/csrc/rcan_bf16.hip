@@ -1,0 +1,222 @@
+// RCAN inference on bf16 activation storage (reference basicsr/archs/rcan_arch.py; the fp32 twins are in rcan.hip and swin.hip):
+//   RCAB (:32-54, ChannelAttention :9-29)   y = bf16(x + res_scale * t * s)                        dcpt_rcab_fwd_bf16
+//   group conv / conv_after_body (:79-82, :147)   y = bf16(res + conv3x3(x) + bias)                dcpt_conv3x3_res_fwd_bf16
+//   Upsample stage (arch_util.py Upsample)   y = bf16(PixelShuffle(r)(conv3x3(x) + bias)), r 2 | 3   dcpt_conv3x3_ps_fwd_bf16
+// Forward only: nothing is kept for a backward pass, there is none.
+//
+// Feature maps are bf16 NHWC rows [M][C] (M = B*H*W, C % 8 == 0); parameters are fp32.  Every conv is the implicit 3 x 3 form (conv3) of the
+// bf16 NT GEMM (gemm_bf16.hip, fp32 accumulation) on the 128-row kernel, with the epilogues this file adds to it (gemm_bf16_epi.h):
+//   h = bf16(relu(conv1(x) + b1))         EB_BIASRELU
+//   t = bf16(conv2(h) + b2)               EB_BIASCOL: the per-image column sums are taken from the fp32 accumulator + bias BEFORE the rounding,
+//                                         one partial row per (tile, image) pair in a fixed order -- no atomics, run-to-run bit-identical.
+//                                         This GEMM tiles its rows per image, so the terms of an image's sum and their order do not depend on
+//                                         the batch: a batched forward equals the one-image forwards bit for bit (tiled inference batches
+//                                         tiles of equal shape, and a bf16 rounding downstream would amplify a last-bit difference of s)
+//   s = sigmoid(W2 relu(W1 mean_hw(t) + b1') + b2')   rcan.hip's CA kernel on those fp32 sums (launch_rcan_ca_fwd): pooling, FCs, sigmoid fp32
+//   y = bf16(x + res_scale * t * s)       rcab_scale_bf16_kernel below: 16-byte vectors, one rounding
+// Storage points (where a value is rounded to bf16): the weight operand images, h, t, y, and the outputs of the other two entry points.
+// Each conv's weight comes as its cached operand image (dcpt_conv_wpack_bf16_multi; the forward half is used) or is packed in the call.
+// The pixel shuffle reads the cached image in the conv's own channel order: GEMM column (i r + j) C + c is conv channel c r^2 + i r + j, the
+// GEMM's weight loader and bias load apply that map (EB_PSHUF), so no reordered copy of the weights exists and r = 3 takes the same path as
+// r = 2 -- the GEMM's scatter epilogue writes the shuffled bf16 image directly, no intermediate map in any precision.
+#include "bf16_ops.h"
+#include "prof.h"
+#include "../../include/dcpt_hip.h"
+
+namespace {
+
+__device__ __forceinline__ f8 bf8_ldg(const bf16_t* p) {
+    const uint4 w = *reinterpret_cast<const uint4*>(p);
+    f8 o;
+    o.lo = make_float4(bf_lo(w.x), bf_hi(w.x), bf_lo(w.y), bf_hi(w.y));
+    o.hi = make_float4(bf_lo(w.z), bf_hi(w.z), bf_lo(w.w), bf_hi(w.w));
+    return o;
+}
+__device__ __forceinline__ void bf8_stg(bf16_t* p, f8 v) {
+    uint4 w;
+    w.x = bf_pack(v.lo.x, v.lo.y);
+    w.y = bf_pack(v.lo.z, v.lo.w);
+    w.z = bf_pack(v.hi.x, v.hi.y);
+    w.w = bf_pack(v.hi.z, v.hi.w);
+    *reinterpret_cast<uint4*>(p) = w;
+}
+
+// y = bf16(x + rs * t * s[b][c])   (groups of 8 channels; C % 8 == 0; the expression of rcan.hip's rcab_scale_kernel)
+__global__ __launch_bounds__(256) void rcab_scale_bf16_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ t, const float* __restrict__ s,
+                                                              bf16_t* __restrict__ y, int64_t n8, int C, int64_t PC, float rs) {
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n8; e += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t el = 8 * e;
+        const f8 sv = f8_ld(s + (el / PC) * C + el % C);
+        const f8 xv = bf8_ldg(x + el), tv = bf8_ldg(t + el);
+        f8 o;
+        o.lo = make_float4(fmaf(rs * tv.lo.x, sv.lo.x, xv.lo.x), fmaf(rs * tv.lo.y, sv.lo.y, xv.lo.y), fmaf(rs * tv.lo.z, sv.lo.z, xv.lo.z),
+                           fmaf(rs * tv.lo.w, sv.lo.w, xv.lo.w));
+        o.hi = make_float4(fmaf(rs * tv.hi.x, sv.hi.x, xv.hi.x), fmaf(rs * tv.hi.y, sv.hi.y, xv.hi.y), fmaf(rs * tv.hi.z, sv.hi.z, xv.hi.z),
+                           fmaf(rs * tv.hi.w, sv.hi.w, xv.hi.w));
+        bf8_stg(y + el, o);
+    }
+}
+
+inline unsigned ew_grid(int64_t n) {
+    int64_t nb = cdiv64(n, 256);
+    if (nb > 16384) nb = 16384;
+    return (unsigned)(nb < 1 ? 1 : nb);
+}
+
+// the limits launch_gemm_nt_bf16 enforces for a conv3 launch of Cout columns over a [B][H][W][C] map (checked here so that an entry point
+// refuses before its first launch, and so that the workspace queries answer 0 without a device); channels <= 1024 as the cached operand images
+bool conv3_ok(int B, int H, int W, int C, int Cout) {
+    if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 8 != 0 || C > 1024 || Cout <= 0 || Cout % 8 != 0) return false;
+    if ((int64_t)H * W >= (1 << 30)) return false;
+    const int64_t M = (int64_t)B * H * W;
+    return (double)(130 + 2 * W + 2) * C * 2.0 < 1.0e9 && 9 * C < (1 << 20) && Cout < (1 << 20) && (double)Cout * 9.0 * C * 2.0 < 1.0e9 &&
+           (cdiv64(M, 128) + B) * cdiv(Cout, 32) < (1ll << 31);   // (+ B: the conv2 GEMM of an RCAB tiles its rows per image)
+}
+bool rcab_ok(int B, int H, int W, int C, int Cr) { return conv3_ok(B, H, W, C, C) && Cr >= 1 && Cr <= C; }
+bool ps_ok(int B, int H, int W, int C, int r) {
+    return (r == 2 || r == 3) && conv3_ok(B, H, W, C, r * r * C) && (double)(130 + 2 * W) * (double)(r * r) * C * 2.0 < 1.0e9;
+}
+
+// the forward operand image [Cout][9 C] of a conv: the first half of its cached pack, or packed here into `wp`
+int operand(const float* w, const void* pk, bf16_t* wp, int C, int Cout, const bf16_t** out, hipStream_t s) {
+    if (pk) {
+        *out = static_cast<const bf16_t*>(pk);
+        return DCPT_OK;
+    }
+    trace_tag("rcan_bf16.wpack_per_call");   // (not reached with the network's cached images)
+    WpackBJobs j{};
+    j.n = 1;
+    j.in[0] = w; j.out[0] = wp; j.N[0] = Cout; j.K[0] = 9 * C; j.transpose[0] = 2;
+    *out = wp;
+    return launch_wpack_bf16(j, s);
+}
+int pk_check(const float* w, const void* pk, size_t pk_bytes, int C, int Cout, const char* who) {
+    DCPT_CHECK_ARG(w || pk, "%s: null argument (weights)", who);
+    DCPT_CHECK_ARG(pk == nullptr || pk_bytes >= dcpt_conv_wpack_bf16_bytes(C, Cout, 3), "%s: packed weights too small (dcpt_conv_wpack_bf16_bytes)", who);
+    return DCPT_OK;
+}
+
+GemmNTB conv3_problem(const bf16_t* x, const bf16_t* Bw, bf16_t* y, int B, int H, int W, int C, int Cout, const float* bias) {
+    GemmNTB g{};
+    g.M = (int64_t)B * H * W; g.A = x; g.K = 9 * C; g.conv3 = 1; g.gH = H; g.gW = W; g.gC = C; g.Bw = Bw; g.N = Cout; g.C = y; g.ldc = Cout;
+    g.bias = bias; g.nb = 1;
+    return g;
+}
+
+struct RcabWsB {
+    bf16_t *wp1, *wp2;   // operand images packed in the call (unused with cached ones)
+    float* colpart;      // [(tiles_m + B - 1)][C] tile / image column sums of t
+    bf16_t *h, *t;       // [M][C]
+    float *pooled, *s;   // [B][C]
+};
+size_t rcab_layout(int B, int H, int W, int C, void* base, size_t bytes, RcabWsB* out) {
+    WsAlloc a(base, base ? bytes : (size_t)-1);
+    RcabWsB w{};
+    const int64_t M = (int64_t)B * H * W;
+    w.wp1 = a.get<bf16_t>((size_t)9 * C * C);
+    w.wp2 = a.get<bf16_t>((size_t)9 * C * C);
+    w.colpart = a.get<float>((size_t)(cdiv64(M, 128) + B - 1) * C);
+    w.h = a.get<bf16_t>((size_t)M * C);
+    w.t = a.get<bf16_t>((size_t)M * C);
+    w.pooled = a.get<float>((size_t)B * C);
+    w.s = a.get<float>((size_t)B * C);
+    if (out) *out = w;
+    return a.off;
+}
+
+}  // namespace
+
+// =====================================================================================================
+extern "C" size_t dcpt_rcab_bf16_ws_bytes(int B, int H, int W, int C, int Cr) {
+    if (!rcab_ok(B, H, W, C, Cr)) return 0;
+    return rcab_layout(B, H, W, C, nullptr, 0, nullptr);
+}
+
+extern "C" int dcpt_rcab_fwd_bf16(const dcpt_rcab_params* p, const void* wpacked1, size_t wpacked1_bytes, const void* wpacked2,
+                                  size_t wpacked2_bytes, const uint16_t* x, uint16_t* y, void* ws, size_t ws_bytes, int B, int H, int W, int C,
+                                  int Cr, float res_scale, dcpt_stream_t stream) {
+    hipStream_t s = (hipStream_t)stream;
+    DCPT_CHECK_ARG(p && x && y && p->conv1_b && p->conv2_b && p->ca1_w && p->ca1_b && p->ca2_w && p->ca2_b, "rcab_fwd_bf16: null argument");
+    DCPT_CHECK_ARG(rcab_ok(B, H, W, C, Cr), "rcab_fwd_bf16: B=%d H=%d W=%d C=%d Cr=%d (C a positive multiple of 8 up to 1024, 1 <= Cr <= C, one map inside the 32-bit windows)",
+                   B, H, W, C, Cr);
+    DCPT_TRY(pk_check(p->conv1_w, wpacked1, wpacked1_bytes, C, C, "rcab_fwd_bf16"));
+    DCPT_TRY(pk_check(p->conv2_w, wpacked2, wpacked2_bytes, C, C, "rcab_fwd_bf16"));
+    RcabWsB w;
+    const size_t need = rcab_layout(B, H, W, C, ws, ws_bytes, &w);
+    if (ws == nullptr || need > ws_bytes) {
+        dcpt_set_error("rcab_fwd_bf16: workspace too small (%zu < %zu)", ws_bytes, need);
+        return DCPT_ERR_WS;
+    }
+    const int P = H * W;
+    const int64_t M = (int64_t)B * P;
+    trace_tag("rcan_bf16.rcab_fwd");
+    const bf16_t *b1, *b2;
+    DCPT_TRY(operand(p->conv1_w, wpacked1, w.wp1, C, C, &b1, s));
+    DCPT_TRY(operand(p->conv2_w, wpacked2, w.wp2, C, C, &b2, s));
+    // h = relu(conv1(x) + b1)
+    GemmNTB g = conv3_problem(x, b1, w.h, B, H, W, C, C, p->conv1_b);
+    DCPT_TRY(launch_gemm_nt_bf16(g, EB_BIASRELU, s));
+    // t = conv2(h) + b2, and the per-image column sums of its fp32 values
+    g = conv3_problem(w.h, b2, w.t, B, H, W, C, C, p->conv2_b);
+    g.colpart = w.colpart; g.P = P;
+    DCPT_TRY(launch_gemm_nt_bf16(g, EB_BIASCOL, s));
+    DCPT_TRY(launch_rcan_ca_fwd(w.colpart, p->ca1_w, p->ca1_b, p->ca2_w, p->ca2_b, w.pooled, w.s, B, P, C, Cr, s));
+    const int64_t n8 = M * C / 8;
+    rcab_scale_bf16_kernel<<<dim3(ew_grid(n8)), dim3(256), 0, s>>>(x, w.t, w.s, y, n8, C, (int64_t)P * C, res_scale);
+    DCPT_CHECK_LAUNCH("rcab_scale_bf16");
+    return DCPT_OK;
+}
+
+// =====================================================================================================
+extern "C" size_t dcpt_conv3x3_res_bf16_ws_bytes(int B, int H, int W, int C) {
+    if (!conv3_ok(B, H, W, C, C)) return 0;
+    return align_up((size_t)9 * C * C * sizeof(bf16_t), 256);
+}
+
+extern "C" int dcpt_conv3x3_res_fwd_bf16(const uint16_t* x, const float* w, const void* wpacked, size_t wpacked_bytes, const float* bias,
+                                         const uint16_t* res, uint16_t* y, void* ws, size_t ws_bytes, int B, int H, int W, int C,
+                                         dcpt_stream_t stream) {
+    hipStream_t s = (hipStream_t)stream;
+    DCPT_CHECK_ARG(x && bias && res && y, "conv3x3_res_fwd_bf16: null argument");
+    DCPT_CHECK_ARG(conv3_ok(B, H, W, C, C), "conv3x3_res_fwd_bf16: B=%d H=%d W=%d C=%d (C a positive multiple of 8 up to 1024, one map inside the 32-bit windows)",
+                   B, H, W, C);
+    DCPT_TRY(pk_check(w, wpacked, wpacked_bytes, C, C, "conv3x3_res_fwd_bf16"));
+    const size_t need = dcpt_conv3x3_res_bf16_ws_bytes(B, H, W, C);
+    if (ws == nullptr || ws_bytes < need) {
+        dcpt_set_error("conv3x3_res_fwd_bf16: workspace too small (%zu < %zu)", ws_bytes, need);
+        return DCPT_ERR_WS;
+    }
+    trace_tag("rcan_bf16.res_fwd");
+    const bf16_t* bw;
+    DCPT_TRY(operand(w, wpacked, static_cast<bf16_t*>(ws), C, C, &bw, s));
+    GemmNTB g = conv3_problem(x, bw, y, B, H, W, C, C, bias);
+    g.res = res;
+    return launch_gemm_nt_bf16(g, EB_RESID, s);
+}
+
+// =====================================================================================================
+extern "C" size_t dcpt_conv3x3_ps_bf16_ws_bytes(int B, int H, int W, int C, int r) {
+    if (!ps_ok(B, H, W, C, r)) return 0;
+    return align_up((size_t)9 * r * r * C * C * sizeof(bf16_t), 256);
+}
+
+extern "C" int dcpt_conv3x3_ps_fwd_bf16(const uint16_t* x, const float* w, const void* wpacked, size_t wpacked_bytes, const float* bias,
+                                        uint16_t* y, void* ws, size_t ws_bytes, int B, int H, int W, int C, int r, dcpt_stream_t stream) {
+    hipStream_t s = (hipStream_t)stream;
+    DCPT_CHECK_ARG(x && bias && y, "conv3x3_ps_fwd_bf16: null argument");
+    DCPT_CHECK_ARG(ps_ok(B, H, W, C, r), "conv3x3_ps_fwd_bf16: B=%d H=%d W=%d C=%d r=%d (C a positive multiple of 8 up to 1024, r 2 or 3, one map inside the 32-bit windows)",
+                   B, H, W, C, r);
+    const int N = r * r * C;
+    DCPT_TRY(pk_check(w, wpacked, wpacked_bytes, C, N, "conv3x3_ps_fwd_bf16"));
+    const size_t need = dcpt_conv3x3_ps_bf16_ws_bytes(B, H, W, C, r);
+    if (ws == nullptr || ws_bytes < need) {
+        dcpt_set_error("conv3x3_ps_fwd_bf16: workspace too small (%zu < %zu)", ws_bytes, need);
+        return DCPT_ERR_WS;
+    }
+    trace_tag("rcan_bf16.ps_fwd");
+    const bf16_t* bw;
+    DCPT_TRY(operand(w, wpacked, static_cast<bf16_t*>(ws), C, N, &bw, s));
+    GemmNTB g = conv3_problem(x, bw, y, B, H, W, C, N, bias);
+    g.psr = r;
+    return launch_gemm_nt_bf16(g, EB_PSHUF, s);
+}

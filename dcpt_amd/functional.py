@@ -2368,6 +2368,76 @@ def conv3x3_ps(x, weight, bias, r):
     return _Conv3x3PsFn.apply(x, weight, bias, int(r))
 
 
+# RCAN on bf16 activation storage (include/dcpt_hip.h dcpt_rcab_fwd_bf16, dcpt_conv3x3_res_fwd_bf16, dcpt_conv3x3_ps_fwd_bf16): forward only.
+# Feature maps are torch.bfloat16 channels_last, parameters fp32; ``packed*``: the conv's PackedConvBf16 cache (without it the call packs).
+def _inference_only(name, *ts):
+    if _wants_grad(*ts):
+        raise NotImplementedError(f"{name}: bf16 storage for RCAN is inference-only (there is no backward pass); run it under torch.no_grad()")
+
+
+def rcab_bf16(x, conv1_w, conv1_b, conv2_w, conv2_b, ca1_w, ca1_b, ca2_w, ca2_b, res_scale=1.0, packed1: PackedConvBf16 = None,
+              packed2: PackedConvBf16 = None):
+    """bf16(x + res_scale * CA(conv2(relu(conv1(x)))))  (rcan_arch.py RCAB, ChannelAttention); h, t and y are rounded to bf16 where they are
+    stored, the pooled mean (of the fp32 t), the CA FCs and the sigmoid are fp32"""
+    lib = _lib.load()
+    ps = (conv1_w, conv1_b, conv2_w, conv2_b, ca1_w, ca1_b, ca2_w, ca2_b)
+    _require_gpu_bf16(x)
+    _require_gpu(*ps)
+    _inference_only("rcab_bf16", x, *ps)
+    x = _nhwc(x)
+    ps_ = [_contig(t.detach()) for t in ps]
+    B, Cc, H, W = x.shape
+    Cr = ps_[4].shape[0]
+    if tuple(ps_[0].shape) != (Cc, Cc, 3, 3) or tuple(ps_[2].shape) != (Cc, Cc, 3, 3) or ps_[4].numel() != Cr * Cc or ps_[6].numel() != Cr * Cc:
+        raise ValueError(f"rcab_bf16: parameter shapes do not fit C={Cc} (conv {tuple(ps_[0].shape)} / {tuple(ps_[2].shape)}, CA {tuple(ps_[4].shape)})")
+    dev = x.device
+    y = _empty_nhwc_bf16(B, Cc, H, W, dev)
+    ws = _workspace(dev, _check_ws("rcab_bf16", lib.dcpt_rcab_bf16_ws_bytes(B, H, W, Cc, Cr), f"B={B} H={H} W={W} C={Cc} Cr={Cr}; C % 8 == 0"))
+    pp = RcabParams(*[t.data_ptr() for t in ps_])
+    check(lib.dcpt_rcab_fwd_bf16(C.byref(pp), *_pk(packed1, conv1_w), *_pk(packed2, conv2_w), x.data_ptr(), y.data_ptr(), ws.data_ptr(),
+                                 ws.numel(), B, H, W, Cc, Cr, float(res_scale), _stream(dev)), "dcpt_rcab_fwd_bf16")
+    return y
+
+
+def conv3x3_res_bf16(x, weight, bias, res, packed: PackedConvBf16 = None):
+    """bf16(res + conv3x3(x) + bias): RCAN's group conv and conv_after_body on bf16 maps"""
+    lib = _lib.load()
+    _require_gpu_bf16(x, res)
+    _require_gpu(weight, bias)
+    _inference_only("conv3x3_res_bf16", x, res, weight, bias)
+    x, res = _nhwc(x), _nhwc(res)
+    w_, b_ = _contig(weight.detach()), _contig(bias.detach())
+    B, Cc, H, W = x.shape
+    _check_conv_weight("conv3x3_res_bf16", w_, b_, Cc, Cc)
+    if res.shape != x.shape:
+        raise ValueError(f"conv3x3_res_bf16: residual {tuple(res.shape)} for a map {tuple(x.shape)}")
+    dev = x.device
+    y = _empty_nhwc_bf16(B, Cc, H, W, dev)
+    ws = _workspace(dev, _check_ws("conv3x3_res_bf16", lib.dcpt_conv3x3_res_bf16_ws_bytes(B, H, W, Cc), f"B={B} H={H} W={W} C={Cc}; C % 8 == 0"))
+    check(lib.dcpt_conv3x3_res_fwd_bf16(x.data_ptr(), w_.data_ptr(), *_pk(packed, weight), b_.data_ptr(), res.data_ptr(), y.data_ptr(),
+                                        ws.data_ptr(), ws.numel(), B, H, W, Cc, _stream(dev)), "dcpt_conv3x3_res_fwd_bf16")
+    return y
+
+
+def conv3x3_ps_bf16(x, weight, bias, r, packed: PackedConvBf16 = None):
+    """bf16(PixelShuffle(r)(conv3x3(x) + bias)), r in {2, 3}: one stage of arch_util.py Upsample on bf16 maps"""
+    lib = _lib.load()
+    r = int(r)
+    _require_gpu_bf16(x)
+    _require_gpu(weight, bias)
+    _inference_only("conv3x3_ps_bf16", x, weight, bias)
+    x = _nhwc(x)
+    w_, b_ = _contig(weight.detach()), _contig(bias.detach())
+    B, Cc, H, W = x.shape
+    _check_conv_weight("conv3x3_ps_bf16", w_, b_, r * r * Cc, Cc)
+    dev = x.device
+    ws = _workspace(dev, _check_ws("conv3x3_ps_bf16", lib.dcpt_conv3x3_ps_bf16_ws_bytes(B, H, W, Cc, r), f"B={B} H={H} W={W} C={Cc} r={r}; C % 8 == 0, r 2 or 3"))
+    y = _empty_nhwc_bf16(B, Cc, r * H, r * W, dev)
+    check(lib.dcpt_conv3x3_ps_fwd_bf16(x.data_ptr(), w_.data_ptr(), *_pk(packed, weight), b_.data_ptr(), y.data_ptr(), ws.data_ptr(), ws.numel(),
+                                       B, H, W, Cc, r, _stream(dev)), "dcpt_conv3x3_ps_fwd_bf16")
+    return y
+
+
 # ------------------------------------------------------------------------------------------------
 # SwinIR super-resolution tail and the "3conv" residual (include/dcpt_hip.h dcpt_conv3x3_act_*, dcpt_up2_conv3x3_act_*,
 # dcpt_conv3x3_ps_out_*, dcpt_conv3conv_res_*).

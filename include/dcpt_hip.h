@@ -610,6 +610,28 @@ int dcpt_conv3x3_ps_fwd(const float* x, const float* w, const float* bias, float
                         dcpt_stream_t stream);
 int dcpt_conv3x3_ps_bwd(const float* dy, const float* x, const float* w, float* dx, float* dw, float* dbias, void* ws, size_t ws_bytes, int B,
                         int H, int W, int C, int r, dcpt_stream_t stream);
+/* ---- RCAN inference on bf16 activation storage (rcan_bf16.hip) ---------------------------------------------------------------------
+ * Forward only.  Feature maps are bf16 NHWC [B][H][W][C] (16-byte aligned), C % 8 == 0, C <= 1024; parameters fp32; fp32 accumulation.
+ * Every conv takes w [Cout][C][3][3] fp32 and/or its cached operand images (wpacked, dcpt_conv_wpack_bf16_bytes(C, Cout, 3) bytes filled by
+ * dcpt_conv_wpack_bf16_multi; NULL, 0: packed in the call -- then w must be given).  Values are rounded to bf16 where they are stored: the
+ * weight operand images, h, t, y.  Every *_ws_bytes needs no device and returns 0 for unsupported arguments; arguments are checked before
+ * the first launch.  No synchronisation, no global state, no atomics (bit-identical run to run).
+ * RCAB (rcan_arch.py:32-54, ChannelAttention :9-29):  y = bf16(x + res_scale * t * s),  h = bf16(relu(conv1(x) + b1)),
+ *   t = bf16(conv2(h) + b2),  s = sigmoid(W2 relu(W1 mean_hw(t) + b1') + b2') with the mean taken over the fp32 values of t before their
+ *   rounding; pooling, FCs and sigmoid in fp32.  p->conv1_w / conv2_w may be NULL where the packed image is given.  Four launches. */
+size_t dcpt_rcab_bf16_ws_bytes(int B, int H, int W, int C, int Cr);
+int dcpt_rcab_fwd_bf16(const dcpt_rcab_params* p, const void* wpacked1, size_t wpacked1_bytes, const void* wpacked2, size_t wpacked2_bytes,
+                       const uint16_t* x, uint16_t* y, void* ws, size_t ws_bytes, int B, int H, int W, int C, int Cr, float res_scale,
+                       dcpt_stream_t stream);
+/* Group conv / conv_after_body (rcan_arch.py:79-82, :147):  y = bf16(res + conv3x3(x) + bias), one GEMM with the residual in its epilogue. */
+size_t dcpt_conv3x3_res_bf16_ws_bytes(int B, int H, int W, int C);
+int dcpt_conv3x3_res_fwd_bf16(const uint16_t* x, const float* w, const void* wpacked, size_t wpacked_bytes, const float* bias,
+                              const uint16_t* res, uint16_t* y, void* ws, size_t ws_bytes, int B, int H, int W, int C, dcpt_stream_t stream);
+/* One Upsample stage (arch_util.py Upsample), r in {2, 3}:  y = bf16(PixelShuffle(r)(conv3x3(x, w) + bias)), w [r^2 C][C][3][3], bias [r^2 C]
+ *   in the conv's own channel order, y [B][rH][rW][C]; one GEMM whose epilogue writes the shuffled image (no intermediate map). */
+size_t dcpt_conv3x3_ps_bf16_ws_bytes(int B, int H, int W, int C, int r);
+int dcpt_conv3x3_ps_fwd_bf16(const uint16_t* x, const float* w, const void* wpacked, size_t wpacked_bytes, const float* bias, uint16_t* y,
+                             void* ws, size_t ws_bytes, int B, int H, int W, int C, int r, dcpt_stream_t stream);
 /* ---- SwinIR super-resolution tail and the "3conv" residual (basicsr/archs/swinir_arch.py) ---------------------------------------------
  * fp32, NHWC feature maps, implicit-GEMM convs with the LeakyReLU in the GEMM epilogue.  Every *_ws_bytes returns 0 for unsupported
  * arguments.  Backward takes the activation mask from the sign of the saved OUTPUT y (y > 0: 1, else slope; 0 <= slope <= 1).
