@@ -34,10 +34,7 @@ extern "C" int dcpt_ln2d_bwd(const float* dy, const float* x, const float* mu, c
     DCPT_CHECK_ARG(dy && x && mu && rstd && weight && dx, "ln2d_bwd: null argument");
     DCPT_CHECK_ARG(C > 0 && C % 4 == 0 && M > 0, "ln2d_bwd: bad shape");
     const int nblk = ln_bwd_num_blocks(M, C);
-    if (ws == nullptr || ws_bytes < dcpt_ln2d_bwd_ws_bytes(M, C)) {
-        dcpt_set_error("ln2d_bwd: workspace too small");
-        return DCPT_ERR_WS;
-    }
+    DCPT_CHECK_WS("ln2d_bwd", ws, ws_bytes, dcpt_ln2d_bwd_ws_bytes(M, C));
     DCPT_TRY(launch_ln_bwd(dy, x, mu, rstd, weight, nullptr, dx, (float*)ws, nblk, M, C, s));
     DCPT_TRY(launch_colpart_reduce((float*)ws, nblk, 3, C, dweight, dbias, nullptr, s));
     return DCPT_OK;
@@ -59,10 +56,7 @@ extern "C" int dcpt_conv3x3_in_bwd(const float* dy, const float* x, const float*
                                    void* ws, size_t ws_bytes, int B, int H, int W, int Cin, int Cout, dcpt_stream_t stream) {
     hipStream_t s = (hipStream_t)stream;
     DCPT_CHECK_ARG(dy && x && w && dw && dbias, "conv3x3_in_bwd: null argument");
-    if (ws == nullptr || ws_bytes < dcpt_conv3x3_in_bwd_ws_bytes(B, H, W, Cin, Cout)) {
-        dcpt_set_error("conv3x3_in_bwd: workspace too small");
-        return DCPT_ERR_WS;
-    }
+    DCPT_CHECK_WS("conv3x3_in_bwd", ws, ws_bytes, dcpt_conv3x3_in_bwd_ws_bytes(B, H, W, Cin, Cout));
     const int nblk = conv3x3_wgrad_num_blocks(B, H, W, Cout);
     // dW[c][s][tap] = sum_p dy[p][c] * x[p+off][s];  db[c] = sum_p dy[p][c]
     DCPT_TRY(launch_conv3x3_wgrad(dy, x, (float*)ws, nblk, dw, dbias, B, H, W, Cin, Cout, 0, s));
@@ -86,10 +80,7 @@ extern "C" int dcpt_conv3x3_out_bwd(const float* dy, const float* x, const float
                                     void* ws, size_t ws_bytes, int B, int H, int W, int Cin, int Cout, dcpt_stream_t stream) {
     hipStream_t s = (hipStream_t)stream;
     DCPT_CHECK_ARG(dy && x && w && dx && dw && dbias, "conv3x3_out_bwd: null argument");
-    if (ws == nullptr || ws_bytes < dcpt_conv3x3_out_bwd_ws_bytes(B, H, W, Cin, Cout)) {
-        dcpt_set_error("conv3x3_out_bwd: workspace too small");
-        return DCPT_ERR_WS;
-    }
+    DCPT_CHECK_WS("conv3x3_out_bwd", ws, ws_bytes, dcpt_conv3x3_out_bwd_ws_bytes(B, H, W, Cin, Cout));
     // dx[p][c] = sum_{s,tap} dy[p-off][s] * w[s][c][tap]
     DCPT_TRY(launch_conv3x3_s2b(dy, w, nullptr, dx, B, H, W, Cout, Cin, 1, s));
     // dW[s][c][tap] = sum_p dy[p][s]*x[p+off][c] = sum_p' x[p'][c]*dy[p'-off][s]  (flipped-tap form)
@@ -136,10 +127,7 @@ extern "C" int dcpt_down2x2_fwd(const float* x, const float* w, const float* bia
     DCPT_CHECK_ARG(H % 2 == 0 && W % 2 == 0 && C % 4 == 0, "down2x2_fwd: H=%d W=%d must be even, C=%d %% 4", H, W, C);
     DownWs d;
     const size_t need = down_layout(B, H, W, C, 0, ws, ws_bytes, &d);
-    if (ws == nullptr || need > ws_bytes) {
-        dcpt_set_error("down2x2_fwd: workspace too small");
-        return DCPT_ERR_WS;
-    }
+    DCPT_CHECK_WS("down2x2_fwd", ws, ws_bytes, need);
     DCPT_TRY(launch_wpack(w, d.wp, nullptr, 2 * C, 4 * C, WP_DOWN, s));
     GemmNT g{};
     g.M = (int64_t)B * (H / 2) * (W / 2);
@@ -155,10 +143,7 @@ extern "C" int dcpt_down2x2_bwd(const float* dy, const float* x, const float* w,
     DCPT_CHECK_ARG(H % 2 == 0 && W % 2 == 0 && C % 4 == 0, "down2x2_bwd: bad shape");
     DownWs d;
     const size_t need = down_layout(B, H, W, C, 1, ws, ws_bytes, &d);
-    if (ws == nullptr || need > ws_bytes) {
-        dcpt_set_error("down2x2_bwd: workspace too small");
-        return DCPT_ERR_WS;
-    }
+    DCPT_CHECK_WS("down2x2_bwd", ws, ws_bytes, need);
     const int64_t Mc = (int64_t)B * (H / 2) * (W / 2);
     // dx (fine) = scatter( dy [Mc][2C] x Wp^T )  ;  Bw [N=4C][K=2C]
     DCPT_TRY(launch_wpack(w, d.wp, nullptr, 2 * C, 4 * C, WP_DOWN_T, s));
@@ -211,10 +196,7 @@ extern "C" int dcpt_up_ps_fwd(const float* x, const float* w, const float* skip,
     DCPT_CHECK_ARG(C % 8 == 0, "up_ps_fwd: C=%d must be a multiple of 8", C);
     UpWs u;
     const size_t need = up_layout(B, H, W, C, 0, ws, ws_bytes, &u);
-    if (ws == nullptr || need > ws_bytes) {
-        dcpt_set_error("up_ps_fwd: workspace too small");
-        return DCPT_ERR_WS;
-    }
+    DCPT_CHECK_WS("up_ps_fwd", ws, ws_bytes, need);
     DCPT_TRY(launch_wpack(w, u.wp, nullptr, 2 * C, C, WP_UP, s));
     GemmNT g{};
     g.M = (int64_t)B * H * W; g.A = x; g.lda = C; g.K = C; g.Bw = u.wp; g.N = 2 * C; g.C = y;
@@ -229,10 +211,7 @@ extern "C" int dcpt_up_ps_bwd(const float* dy, const float* x, const float* w, f
     DCPT_CHECK_ARG(C % 8 == 0, "up_ps_bwd: C=%d must be a multiple of 8", C);
     UpWs u;
     const size_t need = up_layout(B, H, W, C, 1, ws, ws_bytes, &u);
-    if (ws == nullptr || need > ws_bytes) {
-        dcpt_set_error("up_ps_bwd: workspace too small");
-        return DCPT_ERR_WS;
-    }
+    DCPT_CHECK_WS("up_ps_bwd", ws, ws_bytes, need);
     const int64_t M = (int64_t)B * H * W;
     // dx[m][ic] = sum_n' gather(dy)[m][n'] * Wp[n'][ic]  ->  Bw [N=C][K=2C] = Wp^T
     DCPT_TRY(launch_wpack(w, u.wp, nullptr, 2 * C, C, WP_UP_T, s));
@@ -327,10 +306,7 @@ extern "C" int dcpt_imgmetric(const float* img, const float* img2, void* sse_out
     DCPT_CHECK_ARG(!bad, "%s (B=%d C=%d H=%d W=%d crop_border=%d flags=0x%x)", bad, B, C, H, W, crop_border, flags);
     MetricWs m;
     const size_t need = metric_layout(B, C, H, W, crop_border, flags, ws, ws_bytes, &m);
-    if (ws == nullptr || need > ws_bytes) {
-        dcpt_set_error("imgmetric: workspace too small");
-        return DCPT_ERR_WS;
-    }
+    DCPT_CHECK_WS("imgmetric", ws, ws_bytes, need);
     return launch_imgmetric(img, img2, sse_out, ssim_out, m.ssim_part, m.sse_part, B, C, H, W, crop_border, (flags & DCPT_METRIC_Y) != 0,
                             (flags & DCPT_METRIC_RANGE1) ? 1 : 255, want_ssim, (hipStream_t)stream);
 }

@@ -334,8 +334,6 @@ struct ConvWs {
     float* dz;      // [M][Cout]  (backward)
     float* slab;
     float* lnpart;
-    int splits;
-    int64_t rps;
     int ln_nblk;
 };
 
@@ -348,8 +346,11 @@ size_t conv_layout(int B, int H, int W, int Cin, int Cout, int ks, int backward,
     w.wp = a.get<float>((size_t)Cout * K);
     if (backward) {
         w.dz = a.get<float>((size_t)M * Cout);
-        gemm_tn_plan(M, Cout, K, &w.splits, &w.rps);
-        w.slab = a.get<float>((size_t)w.splits * Cout * K);
+        // (launch_wgrad plans the split again at call time: gemm_tn_plan is a pure function of (M, N, K) and the process-wide
+        // split-operand mode, so it arrives at the plan this slab is sized with)
+        size_t sl = 0, cs = 0;
+        wgrad_need(M, Cout, K, &sl, &cs);
+        w.slab = a.get<float>(sl);
         if (with_ln) {
             w.ln_nblk = ln_bwd_num_blocks(M, Cout);
             w.lnpart = a.get<float>((size_t)w.ln_nblk * 3 * Cout);
@@ -361,46 +362,32 @@ size_t conv_layout(int B, int H, int W, int Cin, int Cout, int ks, int backward,
 
 int conv_fwd(const float* x, const float* w, float* z, const ConvWs& cw, int B, int H, int W, int Cin, int Cout, int ks,
              hipStream_t s) {
-    GemmNT g{};
-    g.M = (int64_t)B * H * W; g.A = x; g.N = Cout; g.C = z; g.ldc = Cout;
-    if (ks == 1) {
-        g.lda = Cin; g.K = Cin; g.Bw = w;  // [Cout][Cin][1][1] is already [N][K]
-        return launch_gemm_nt(g, A_PLAIN, E_PLAIN, s);
-    }
+    if (ks == 1)   // [Cout][Cin][1][1] is already [N][K]
+        return launch_gemm_nt(gemm_nt_linear(x, Cin, (int64_t)B * H * W, Cin, w, Cout, z, Cout), A_PLAIN, E_PLAIN, s);
     DCPT_TRY(launch_wpack(w, cw.wp, nullptr, Cout, 9 * Cin, WP_CONV3, s));
-    g.K = 9 * Cin; g.gH = H; g.gW = W; g.gC = Cin; g.Bw = cw.wp;
-    return launch_gemm_nt(g, A_CONV3, E_PLAIN, s);
+    return launch_gemm_nt(gemm_nt_conv3(x, B, H, W, Cin, cw.wp, Cout, z, Cout), A_CONV3, E_PLAIN, s);
 }
 
 // dx = conv^T(dz), dw = wgrad(dz, x)
 int conv_bwd(const float* dz, const float* x, const float* w, float* dx, float* dw, const ConvWs& cw, int B, int H, int W, int Cin,
              int Cout, int ks, hipStream_t s, const float* dx_add = nullptr) {
     const int64_t M = (int64_t)B * H * W;
-    GemmNT g{};
-    g.M = M; g.A = dz; g.N = Cin; g.C = dx; g.ldc = Cin; g.Bw = cw.wp;
-    g.res = dx_add; g.ldres = Cin;
     const int EDX = dx_add ? E_RESID : E_PLAIN;   // dx = dx_add + dz W (the shortcut gradient of a bottleneck block rides in the epilogue)
     GemmTN t{};
-    t.M = M; t.X = dz; t.ldx = Cout; t.N = Cout; t.Y = x; t.slab = cw.slab; t.colsum = nullptr; t.splits = cw.splits;
-    t.rows_per_split = cw.rps;
     if (ks == 1) {
         DCPT_TRY(launch_wpack(w, cw.wp, nullptr, Cout, Cin, WP_TRANSPOSE, s));
-        g.lda = Cout; g.K = Cout;
+        GemmNT g = gemm_nt_linear(dz, Cout, M, Cout, cw.wp, Cin, dx, Cin);
+        g.res = dx_add; g.ldres = Cin;
         if (dx) DCPT_TRY(launch_gemm_nt(g, A_PLAIN, EDX, s));
-        t.ldy = Cin; t.K = Cin;
-        DCPT_TRY(launch_gemm_tn(t, A_PLAIN, A_PLAIN, s));
-        DCPT_TRY(launch_wgrad_reduce(cw.slab, nullptr, cw.splits, 0, Cout, Cin, nullptr, nullptr, nullptr, dw, nullptr, nullptr,
-                                     WR_PLAIN, s));
-    } else {
-        DCPT_TRY(launch_wpack(w, cw.wp, nullptr, Cout, 9 * Cin, WP_CONV3_T, s));
-        g.K = 9 * Cout; g.gH = H; g.gW = W; g.gC = Cout;
-        if (dx) DCPT_TRY(launch_gemm_nt(g, A_CONV3, EDX, s));
-        t.K = 9 * Cin; t.gH = H; t.gW = W; t.gC = Cin;
-        DCPT_TRY(launch_gemm_tn(t, A_PLAIN, A_CONV3, s));
-        DCPT_TRY(launch_wgrad_reduce(cw.slab, nullptr, cw.splits, 0, Cout, 9 * Cin, nullptr, nullptr, nullptr, dw, nullptr, nullptr,
-                                     WR_CONV3, s));
+        return launch_wgrad(t, A_PLAIN, dz, Cout, Cout, x, Cin, Cin, M, cw.slab, nullptr, dw, nullptr, WR_PLAIN, s);
     }
-    return DCPT_OK;
+    // (not launch_conv3_bwd: no bias, and dx is optional)
+    DCPT_TRY(launch_wpack(w, cw.wp, nullptr, Cout, 9 * Cin, WP_CONV3_T, s));
+    GemmNT g = gemm_nt_conv3(dz, B, H, W, Cout, cw.wp, Cin, dx, Cin);
+    g.res = dx_add; g.ldres = Cin;
+    if (dx) DCPT_TRY(launch_gemm_nt(g, A_CONV3, EDX, s));
+    t.gH = H; t.gW = W; t.gC = Cin;
+    return launch_wgrad(t, A_CONV3, dz, Cout, Cout, x, Cin, 9 * Cin, M, cw.slab, nullptr, dw, nullptr, WR_CONV3, s);
 }
 
 }  // namespace
@@ -418,10 +405,7 @@ extern "C" int dcpt_conv_ln_fwd(const float* x, const float* w, const float* lnw
     DCPT_CHECK_ARG((ksize == 1 || ksize == 3) && Cin % 4 == 0 && Cout % 4 == 0, "conv_ln_fwd: ksize=%d Cin=%d Cout=%d", ksize, Cin, Cout);
     ConvWs cw;
     const size_t need = conv_layout(B, H, W, Cin, Cout, ksize, 0, true, ws, ws_bytes, &cw);
-    if (ws == nullptr || need > ws_bytes) {
-        dcpt_set_error("conv_ln_fwd: workspace too small");
-        return DCPT_ERR_WS;
-    }
+    DCPT_CHECK_WS("conv_ln_fwd", ws, ws_bytes, need);
     DCPT_TRY(conv_fwd(x, w, z, cw, B, H, W, Cin, Cout, ksize, s));
     return launch_ln_act_fwd(z, lnw, lnb, res, relu, y, mu, rstd, (int64_t)B * H * W, Cout, 1e-6f, s);  // eps: degrad_classify_arch.py:24
 }
@@ -437,10 +421,7 @@ extern "C" int dcpt_conv_ln_bwd(const float* dy, const float* x, const float* w,
     DCPT_CHECK_ARG((ksize == 1 || ksize == 3) && Cin % 4 == 0 && Cout % 4 == 0, "conv_ln_bwd: bad shape");
     ConvWs cw;
     const size_t need = conv_layout(B, H, W, Cin, Cout, ksize, 1, true, ws, ws_bytes, &cw);
-    if (ws == nullptr || need > ws_bytes) {
-        dcpt_set_error("conv_ln_bwd: workspace too small");
-        return DCPT_ERR_WS;
-    }
+    DCPT_CHECK_WS("conv_ln_bwd", ws, ws_bytes, need);
     const int64_t M = (int64_t)B * H * W;
     DCPT_TRY(launch_ln_act_bwd(dy, z, mu, rstd, lnw, nullptr, relu ? y : nullptr, dres, cw.dz, cw.lnpart, cw.ln_nblk, M, Cout, s));
     DCPT_TRY(launch_colpart_reduce(cw.lnpart, cw.ln_nblk, 3, Cout, dlnw, dlnb, nullptr, s));
@@ -457,10 +438,7 @@ extern "C" int dcpt_conv_fwd(const float* x, const float* w, float* y, void* ws,
     DCPT_CHECK_ARG((ksize == 1 || ksize == 3) && Cin % 4 == 0 && Cout % 4 == 0, "conv_fwd: ksize=%d Cin=%d Cout=%d", ksize, Cin, Cout);
     ConvWs cw;
     const size_t need = conv_layout(B, H, W, Cin, Cout, ksize, 0, false, ws, ws_bytes, &cw);
-    if (ws == nullptr || need > ws_bytes) {
-        dcpt_set_error("conv_fwd: workspace too small");
-        return DCPT_ERR_WS;
-    }
+    DCPT_CHECK_WS("conv_fwd", ws, ws_bytes, need);
     return conv_fwd(x, w, y, cw, B, H, W, Cin, Cout, ksize, (hipStream_t)stream);
 }
 
@@ -470,10 +448,7 @@ extern "C" int dcpt_conv_bwd(const float* dy, const float* x, const float* w, fl
     DCPT_CHECK_ARG((ksize == 1 || ksize == 3) && Cin % 4 == 0 && Cout % 4 == 0, "conv_bwd: bad shape");
     ConvWs cw;
     const size_t need = conv_layout(B, H, W, Cin, Cout, ksize, 1, false, ws, ws_bytes, &cw);
-    if (ws == nullptr || need > ws_bytes) {
-        dcpt_set_error("conv_bwd: workspace too small");
-        return DCPT_ERR_WS;
-    }
+    DCPT_CHECK_WS("conv_bwd", ws, ws_bytes, need);
     return conv_bwd(dy, x, w, dx, dw, cw, B, H, W, Cin, Cout, ksize, (hipStream_t)stream);
 }
 
@@ -499,10 +474,7 @@ extern "C" int dcpt_conv1x1_pool_relu_bwd(const float* dy, const float* x, const
     DCPT_CHECK_ARG(dy && x && w && z && dx && dw, "conv1x1_pool_relu_bwd: null argument");
     ConvWs cw;
     const size_t need = conv_layout(B, H, W, Cin, Cout, 1, 1, false, ws, ws_bytes, &cw);
-    if (ws == nullptr || need > ws_bytes) {
-        dcpt_set_error("conv1x1_pool_relu_bwd: workspace too small");
-        return DCPT_ERR_WS;
-    }
+    DCPT_CHECK_WS("conv1x1_pool_relu_bwd", ws, ws_bytes, need);
     pool_relu_bwd_kernel<<<dim3(grid_for((int64_t)B * (H / 2) * (W / 2) * (Cout / 4))), dim3(256), 0, s>>>(z, dy, cw.dz, B, H, W, Cout);
     DCPT_CHECK_LAUNCH("pool_relu_bwd");
     return conv_bwd(cw.dz, x, w, dx, dw, cw, B, H, W, Cin, Cout, 1, s);
@@ -531,10 +503,7 @@ template <typename ST>
 static int mix_bwd_t(const ST* dout, const ST* feat, const float* mixing_weights, int n, int idx, ST* dfeat, float* dmix, void* ws,
                      size_t ws_bytes, int64_t numel, hipStream_t s) {
     DCPT_CHECK_ARG(dout && feat && mixing_weights && dfeat && dmix && n >= 1 && n <= 64 && numel % 4 == 0, "mix_bwd: bad argument");
-    if (ws == nullptr || ws_bytes < dcpt_mix_bwd_ws_bytes(numel)) {
-        dcpt_set_error("mix_bwd: workspace too small");
-        return DCPT_ERR_WS;
-    }
+    DCPT_CHECK_WS("mix_bwd", ws, ws_bytes, dcpt_mix_bwd_ws_bytes(numel));
     const unsigned nb = grid_for(numel / 4);
     mix_bwd_kernel<ST><<<dim3(nb), dim3(256), 0, s>>>(dout, feat, mixing_weights, n, idx, dfeat, (float*)ws, numel / 4);
     DCPT_CHECK_LAUNCH("mix_bwd");
@@ -588,10 +557,7 @@ extern "C" int dcpt_mix_stride_bwd(const float* dout, const float* feat, const f
     TapGeom g;
     DCPT_TRY(tap_geom("mix_stride_bwd", feat, B, H, W, C, s, sb, sh, sw, &g));
     const int64_t nq = (int64_t)B * g.Hc * g.Wc * g.nq;
-    if (ws == nullptr || ws_bytes < dcpt_mix_stride_bwd_ws_bytes(nq * 4)) {
-        dcpt_set_error("mix_stride_bwd: workspace too small");
-        return DCPT_ERR_WS;
-    }
+    DCPT_CHECK_WS("mix_stride_bwd", ws, ws_bytes, dcpt_mix_stride_bwd_ws_bytes(nq * 4));
     const unsigned nb = grid_for(nq);
     mix_stride_bwd_kernel<<<dim3(nb), dim3(256), 0, (hipStream_t)stream>>>(dout, feat, mixing_weights, n, idx, dfeat_c, (float*)ws, g, nq);
     DCPT_CHECK_LAUNCH("mix_stride_bwd");
@@ -640,10 +606,7 @@ template <typename ST>
 static int meanpool_fc_fwd_t(const ST* x, const float* fw, const float* fb, float* pooled, float* logits, void* ws, size_t ws_bytes, int B,
                              int P, int C, int NC, hipStream_t s) {
     DCPT_CHECK_ARG(x && fw && pooled && logits && C % 4 == 0 && B <= 65535 && C * 4 <= 65536, "meanpool_fc_fwd: bad argument");
-    if (ws == nullptr || ws_bytes < dcpt_meanpool_fc_ws_bytes(B, P, C)) {
-        dcpt_set_error("meanpool_fc_fwd: workspace too small");
-        return DCPT_ERR_WS;
-    }
+    DCPT_CHECK_WS("meanpool_fc_fwd", ws, ws_bytes, dcpt_meanpool_fc_ws_bytes(B, P, C));
     const int nsl = pool_slices(P), nq = C / 4;
     int qb = 1;
     while (qb < nq && qb < 256) qb <<= 1;
@@ -666,10 +629,7 @@ template <typename ST>
 static int meanpool_fc_bwd_t(const float* dlogits, const float* pooled, const float* fw, ST* dx, float* dfw, float* dfb, void* ws,
                              size_t ws_bytes, int B, int P, int C, int NC, hipStream_t s) {
     DCPT_CHECK_ARG(dlogits && pooled && fw && dx && dfw && dfb && C % 4 == 0, "meanpool_fc_bwd: bad argument");
-    if (ws == nullptr || ws_bytes < dcpt_meanpool_fc_ws_bytes(B, P, C)) {
-        dcpt_set_error("meanpool_fc_bwd: workspace too small");
-        return DCPT_ERR_WS;
-    }
+    DCPT_CHECK_WS("meanpool_fc_bwd", ws, ws_bytes, dcpt_meanpool_fc_ws_bytes(B, P, C));
     float* dxrow = (float*)ws;
     const int64_t mx = (int64_t)B * C > (int64_t)NC * C ? (int64_t)B * C : (int64_t)NC * C;
     fc_bwd_kernel<<<dim3((unsigned)cdiv64(mx, 256), 3), dim3(256), 0, s>>>(dlogits, pooled, fw, dxrow, dfw, dfb, B, C, NC, 1.0f / (float)P);

@@ -286,10 +286,7 @@ extern "C" int dcpt_conv_ln_fwd_bf16(const uint16_t* x, const float* w, const vo
     DCPT_CHECK_ARG(conv_shape_ok(Cin, Cout, ksize), "conv_ln_fwd_bf16: ksize=%d Cin=%d Cout=%d (channels %% 8 == 0, Cout <= 1024)", ksize, Cin, Cout);
     ConvWsB cw;
     const size_t need = conv_layout(B, H, W, Cin, Cout, ksize, 0, true, ws, ws_bytes, &cw);
-    if (ws == nullptr || need > ws_bytes) {
-        dcpt_set_error("conv_ln_fwd_bf16: workspace too small");
-        return DCPT_ERR_WS;
-    }
+    DCPT_CHECK_WS("conv_ln_fwd_bf16", ws, ws_bytes, need);
     return conv_ln_fwd_group(x, w, wpacked, lnw, lnb, res, relu, z, y, mu, rstd, cw, B, H, W, Cin, Cout, ksize, s);
 }
 
@@ -305,10 +302,7 @@ extern "C" int dcpt_conv_ln_bwd_bf16(const uint16_t* dy, const uint16_t* x, cons
     DCPT_CHECK_ARG(conv_shape_ok(Cin, Cout, ksize), "conv_ln_bwd_bf16: bad shape");
     ConvWsB cw;
     const size_t need = conv_layout(B, H, W, Cin, Cout, ksize, 1, true, ws, ws_bytes, &cw);
-    if (ws == nullptr || need > ws_bytes) {
-        dcpt_set_error("conv_ln_bwd_bf16: workspace too small");
-        return DCPT_ERR_WS;
-    }
+    DCPT_CHECK_WS("conv_ln_bwd_bf16", ws, ws_bytes, need);
     const int64_t M = (int64_t)B * H * W;
     DCPT_TRY(launch_ln_act_bwd_bf16(dy, z, mu, rstd, lnw, relu ? y : nullptr, dres, cw.dz, cw.lnpart, cw.ln_nblk, M, Cout, s));
     const FinCols ln{cw.lnpart, dlnw, dlnb, cw.ln_nblk, 2, Cout, 0};
@@ -376,10 +370,7 @@ extern "C" int dcpt_bottleneck_fwd_bf16(const uint16_t* x, const dcpt_bneck_grou
     DCPT_TRY(bneck_check(g, C, false, "bottleneck_fwd_bf16"));
     BneckWs bw;
     const size_t need = bneck_layout(B, H, W, C, 0, ws, ws_bytes, &bw);
-    if (ws == nullptr || need > ws_bytes) {
-        dcpt_set_error("bottleneck_fwd_bf16: workspace too small");
-        return DCPT_ERR_WS;
-    }
+    DCPT_CHECK_WS("bottleneck_fwd_bf16", ws, ws_bytes, need);
     const BneckGeom gm = bneck_geom(C);
     const bf16_t* cur = x;
     for (int k = 0; k < 3; ++k) {
@@ -397,10 +388,7 @@ extern "C" int dcpt_bottleneck_bwd_bf16(const uint16_t* dout, const uint16_t* x,
     DCPT_TRY(bneck_check(g, C, true, "bottleneck_bwd_bf16"));
     BneckWs bw;
     const size_t need = bneck_layout(B, H, W, C, 1, ws, ws_bytes, &bw);
-    if (ws == nullptr || need > ws_bytes) {
-        dcpt_set_error("bottleneck_bwd_bf16: workspace too small");
-        return DCPT_ERR_WS;
-    }
+    DCPT_CHECK_WS("bottleneck_bwd_bf16", ws, ws_bytes, need);
     const BneckGeom gm = bneck_geom(C);
     const int64_t M = (int64_t)B * H * W;
     // the block's last LayerNorm: gradient from outside, masked by the block's output; the masked gradient is the shortcut's
@@ -446,10 +434,7 @@ extern "C" int dcpt_conv1x1_pool_relu_fwd_bf16(const uint16_t* x, const float* w
     DCPT_CHECK_ARG(H % 2 == 0 && W % 2 == 0 && conv_shape_ok(Cin, Cout, 1), "conv1x1_pool_relu_fwd_bf16: bad shape");
     ConvWsB cw;
     const size_t need = conv_layout(B, H, W, Cin, Cout, 1, 0, false, ws, ws_bytes, &cw);
-    if (ws == nullptr || need > ws_bytes) {
-        dcpt_set_error("conv1x1_pool_relu_fwd_bf16: workspace too small");
-        return DCPT_ERR_WS;
-    }
+    DCPT_CHECK_WS("conv1x1_pool_relu_fwd_bf16", ws, ws_bytes, need);
     DCPT_TRY(conv_fwd(x, w, z, cw, B, H, W, Cin, Cout, 1, s, wpacked));
     pool_relu_fwd_bf16_kernel<<<dim3(grid_for((int64_t)B * (H / 2) * (W / 2) * (Cout / 4))), dim3(256), 0, s>>>(z, y, B, H, W, Cout);
     DCPT_CHECK_LAUNCH("pool_relu_fwd_bf16");
@@ -465,10 +450,7 @@ extern "C" int dcpt_conv1x1_pool_relu_bwd_bf16(const uint16_t* dy, const uint16_
     DCPT_CHECK_ARG(H % 2 == 0 && W % 2 == 0 && conv_shape_ok(Cin, Cout, 1), "conv1x1_pool_relu_bwd_bf16: bad shape");
     ConvWsB cw;
     const size_t need = conv_layout(B, H, W, Cin, Cout, 1, 1, false, ws, ws_bytes, &cw);
-    if (ws == nullptr || need > ws_bytes) {
-        dcpt_set_error("conv1x1_pool_relu_bwd_bf16: workspace too small");
-        return DCPT_ERR_WS;
-    }
+    DCPT_CHECK_WS("conv1x1_pool_relu_bwd_bf16", ws, ws_bytes, need);
     pool_relu_bwd_bf16_kernel<<<dim3(grid_for((int64_t)B * (H / 2) * (W / 2) * (Cout / 4))), dim3(256), 0, s>>>(z, dy, cw.dz, B, H, W, Cout);
     DCPT_CHECK_LAUNCH("pool_relu_bwd_bf16");
     return conv_bwd(cw.dz, x, w, dx, dw, cw, B, H, W, Cin, Cout, 1, s, nullptr, nullptr, wpacked);
@@ -525,10 +507,7 @@ extern "C" int dcpt_conv_fwd_bf16(const uint16_t* x, const float* w, uint16_t* y
                    ksize, Cin, Cout);
     ConvWsB cw;
     const size_t need = conv_layout(B, H, W, Cin, Cout, ksize, 0, false, ws, ws_bytes, &cw);
-    if (ws == nullptr || need > ws_bytes) {
-        dcpt_set_error("conv_fwd_bf16: workspace too small");
-        return DCPT_ERR_WS;
-    }
+    DCPT_CHECK_WS("conv_fwd_bf16", ws, ws_bytes, need);
     return conv_fwd(x, w, y, cw, B, H, W, Cin, Cout, ksize, s);
 }
 
@@ -540,9 +519,6 @@ extern "C" int dcpt_conv_bwd_bf16(const uint16_t* dy, const uint16_t* x, const f
                    "conv_bwd_bf16: ksize=%d Cin=%d Cout=%d (channels %% 8 == 0, <= 1024)", ksize, Cin, Cout);
     ConvWsB cw;
     const size_t need = conv_layout(B, H, W, Cin, Cout, ksize, 1, false, ws, ws_bytes, &cw);
-    if (ws == nullptr || need > ws_bytes) {
-        dcpt_set_error("conv_bwd_bf16: workspace too small");
-        return DCPT_ERR_WS;
-    }
+    DCPT_CHECK_WS("conv_bwd_bf16", ws, ws_bytes, need);
     return conv_bwd(dy, x, w, dx, dw, cw, B, H, W, Cin, Cout, ksize, s);
 }

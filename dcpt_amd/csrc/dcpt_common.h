@@ -22,6 +22,17 @@ void dcpt_set_error(const char* fmt, ...);
         }                                    \
     } while (0)
 
+// Every entry point that takes a caller-owned workspace refuses one that is null or smaller than its *_ws_bytes query (`who` may be a
+// run-time string).  Callers rely on DCPT_ERR_WS and on the words "workspace too small".
+#define DCPT_CHECK_WS(who, ws, ws_bytes, need)                                                                                \
+    do {                                                                                                                      \
+        const size_t need__ = (need);                                                                                         \
+        if ((ws) == nullptr || need__ > (size_t)(ws_bytes)) {                                                                 \
+            dcpt_set_error("%s: workspace too small (%zu < %zu)", who, (ws) ? (size_t)(ws_bytes) : (size_t)0, need__);        \
+            return DCPT_ERR_WS;                                                                                               \
+        }                                                                                                                     \
+    } while (0)
+
 #define DCPT_CHECK_LAUNCH(name)                                                     \
     do {                                                                            \
         hipError_t e__ = hipGetLastError();                                         \
@@ -53,6 +64,12 @@ static inline int dcpt_tuning(const char* name, int dflt) {
 
 static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
+// grid of a 256-thread grid-stride element-wise kernel over n elements (not kernels.h's grid_for: that one has another block cap)
+static inline unsigned ew_grid(int64_t n) {
+    int64_t nb = cdiv64(n, 256);
+    if (nb > 16384) nb = 16384;
+    return (unsigned)(nb < 1 ? 1 : nb);
+}
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 // Bump allocator over a caller-owned workspace (the caller -- PyTorch -- owns every buffer).

@@ -67,10 +67,7 @@ extern "C" int dcpt_down2x2_fwd_bf16(const uint16_t* x, const float* w, const fl
     DCPT_CHECK_ARG(B > 0 && H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0 && C % 8 == 0, "down2x2_fwd_bf16: H=%d W=%d must be even, C=%d %% 8", H, W, C);
     EdgeWsB d;
     const size_t need = down_layout_b(B, H, W, C, 0, ws, ws_bytes, &d);
-    if (ws == nullptr || need > ws_bytes) {
-        dcpt_set_error("down2x2_fwd_bf16: workspace too small");
-        return DCPT_ERR_WS;
-    }
+    DCPT_CHECK_WS("down2x2_fwd_bf16", ws, ws_bytes, need);
     DCPT_TRY(pack1(w, d.wp, 2 * C, 4 * C, 4, s));
     GemmNTB g{};
     g.M = (int64_t)B * (H / 2) * (W / 2);
@@ -86,10 +83,7 @@ extern "C" int dcpt_down2x2_bwd_bf16(const uint16_t* dy, const uint16_t* x, cons
     DCPT_CHECK_ARG(B > 0 && H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0 && C % 8 == 0, "down2x2_bwd_bf16: bad shape");
     EdgeWsB d;
     const size_t need = down_layout_b(B, H, W, C, 1, ws, ws_bytes, &d);
-    if (ws == nullptr || need > ws_bytes) {
-        dcpt_set_error("down2x2_bwd_bf16: workspace too small");
-        return DCPT_ERR_WS;
-    }
+    DCPT_CHECK_WS("down2x2_bwd_bf16", ws, ws_bytes, need);
     const int64_t Mc = (int64_t)B * (H / 2) * (W / 2);
     // dx (fine) = scatter(dy [Mc][2C] x Wp^T):  Bw [N = 4C][K = 2C]
     DCPT_TRY(pack1(w, d.wp, 2 * C, 4 * C, 5, s));
@@ -117,10 +111,7 @@ extern "C" int dcpt_up_ps_fwd_bf16(const uint16_t* x, const float* w, const uint
     DCPT_CHECK_ARG(B > 0 && H > 0 && W > 0 && C % 16 == 0, "up_ps_fwd_bf16: C=%d must be a multiple of 16", C);
     EdgeWsB u;
     const size_t need = up_layout_b(B, H, W, C, 0, ws, ws_bytes, &u);
-    if (ws == nullptr || need > ws_bytes) {
-        dcpt_set_error("up_ps_fwd_bf16: workspace too small");
-        return DCPT_ERR_WS;
-    }
+    DCPT_CHECK_WS("up_ps_fwd_bf16", ws, ws_bytes, need);
     DCPT_TRY(pack1(w, u.wp, 2 * C, C, 6, s));
     GemmNTB g{};
     g.M = (int64_t)B * H * W; g.A = x; g.lda = C; g.K = C; g.Bw = u.wp; g.N = 2 * C; g.C = y; g.ldc = 2 * C;
@@ -135,10 +126,7 @@ extern "C" int dcpt_up_ps_bwd_bf16(const uint16_t* dy, const uint16_t* x, const 
     DCPT_CHECK_ARG(B > 0 && H > 0 && W > 0 && C % 16 == 0, "up_ps_bwd_bf16: C=%d must be a multiple of 16", C);
     EdgeWsB u;
     const size_t need = up_layout_b(B, H, W, C, 1, ws, ws_bytes, &u);
-    if (ws == nullptr || need > ws_bytes) {
-        dcpt_set_error("up_ps_bwd_bf16: workspace too small");
-        return DCPT_ERR_WS;
-    }
+    DCPT_CHECK_WS("up_ps_bwd_bf16", ws, ws_bytes, need);
     const int64_t M = (int64_t)B * H * W;
     // dx[m][ic] = sum_n' gather(dy)[m][n'] * Wp[n'][ic]:  Bw [N = C][K = 2C] = Wp^T
     DCPT_TRY(pack1(w, u.wp, 2 * C, C, 7, s));
@@ -164,10 +152,7 @@ extern "C" int dcpt_conv3x3_in_bwd_bf16(const uint16_t* dy, const float* x, cons
                                         size_t ws_bytes, int B, int H, int W, int Cin, int Cout, dcpt_stream_t stream) {
     hipStream_t s = (hipStream_t)stream;
     DCPT_CHECK_ARG(dy && x && w && dw && dbias, "conv3x3_in_bwd_bf16: null argument");
-    if (ws == nullptr || ws_bytes < dcpt_conv3x3_in_bwd_ws_bytes(B, H, W, Cin, Cout)) {
-        dcpt_set_error("conv3x3_in_bwd_bf16: workspace too small");
-        return DCPT_ERR_WS;
-    }
+    DCPT_CHECK_WS("conv3x3_in_bwd_bf16", ws, ws_bytes, dcpt_conv3x3_in_bwd_ws_bytes(B, H, W, Cin, Cout));
     const int nblk = conv3x3_wgrad_num_blocks(B, H, W, Cout);
     DCPT_TRY(launch_conv3x3_wgrad_bf16(dy, x, (float*)ws, nblk, dw, dbias, B, H, W, Cin, Cout, 0, s));
     if (dx) DCPT_TRY(launch_conv3x3_b2s_bf16(dy, w, nullptr, nullptr, dx, B, H, W, Cin, Cout, 1, s));
@@ -185,10 +170,7 @@ extern "C" int dcpt_conv3x3_out_bwd_bf16(const float* dy, const uint16_t* x, con
                                          size_t ws_bytes, int B, int H, int W, int Cin, int Cout, dcpt_stream_t stream) {
     hipStream_t s = (hipStream_t)stream;
     DCPT_CHECK_ARG(dy && x && w && dx && dw && dbias, "conv3x3_out_bwd_bf16: null argument");
-    if (ws == nullptr || ws_bytes < dcpt_conv3x3_out_bwd_ws_bytes(B, H, W, Cin, Cout)) {
-        dcpt_set_error("conv3x3_out_bwd_bf16: workspace too small");
-        return DCPT_ERR_WS;
-    }
+    DCPT_CHECK_WS("conv3x3_out_bwd_bf16", ws, ws_bytes, dcpt_conv3x3_out_bwd_ws_bytes(B, H, W, Cin, Cout));
     DCPT_TRY(launch_conv3x3_s2b_bf16(dy, w, nullptr, dx, B, H, W, Cout, Cin, 1, s));
     const int nblk = conv3x3_wgrad_num_blocks(B, H, W, Cin);
     DCPT_TRY(launch_conv3x3_wgrad_bf16(x, dy, (float*)ws, nblk, dw, nullptr, B, H, W, Cout, Cin, 1, s));

@@ -69,6 +69,20 @@ struct GemmNT {
 };
 
 int launch_gemm_nt(const GemmNT& p, int aload, int epi, hipStream_t stream);
+// The two common fills; the caller sets the epilogue fields (bias, res, slope, psr, colpart, P, LayerNorm pointers) afterwards.
+// Implicit 3x3 conv (A_CONV3) of the NHWC map x [B][H][W][Cin] with the packed weight wp [Cout][9 Cin]  (A_CONV3UP: the caller
+// puts M on the fine 2H x 2W grid)
+inline GemmNT gemm_nt_conv3(const float* x, int B, int H, int W, int Cin, const float* wp, int Cout, float* out, int ldc) {
+    GemmNT g{};
+    g.M = (int64_t)B * H * W; g.A = x; g.K = 9 * Cin; g.gH = H; g.gW = W; g.gC = Cin; g.Bw = wp; g.N = Cout; g.C = out; g.ldc = ldc;
+    return g;
+}
+// Linear layer on rows: out[m][n] = sum_k A[m][k] W[n][k]
+inline GemmNT gemm_nt_linear(const float* A, int lda, int64_t M, int K, const float* W, int N, float* out, int ldc) {
+    GemmNT g{};
+    g.M = M; g.A = A; g.lda = lda; g.K = K; g.Bw = W; g.N = N; g.C = out; g.ldc = ldc;
+    return g;
+}
 // opt-in split-operand mode (gemm_x3.hip, dcpt_set_gemm_x3): fp32-class results on the bf16 matrix pipe; launch_gemm_nt routes eligible
 // launches there while the mode is on
 bool gemm_nt_x3_ok(const GemmNT& p, int aload, int epi);

@@ -118,7 +118,26 @@ enum WReduceMode { WR_PLAIN = 0, WR_DOWN = 1, WR_UP = 2, WR_CONV3 = 3 };
 //           (cs = sum over the cs_rows partial rows colsum[r][n])
 int launch_wgrad_reduce(const float* slab, const float* colsum, int splits, int cs_rows, int N, int K, const float* rowscale,
                         const float* W, const float* wbias, float* dW, float* dgain, float* dbias, int mode, hipStream_t s);
-// as above, with slab s weighted by kscale[(s / splits_per_image)][k] (every split inside one image; SCA scale folded into the reduce)
+// The fp32 weight gradient of a layer on rows, start to end: plans the split of the TN GEMM, runs it into slab / colsum and reduces:
+//   dW[n][k] = sum_m X[m][n] Y'(m, k)   (mode WR_PLAIN, or WR_CONV3: dW[n][ic][tap] from Y' = the 3x3 im2col),  db[n] = sum_m X[m][n]
+// proto carries the Y loader's fields (LayerNorm / scale pointers, conv geometry gH, gW, gC); colsum == null: no bias gradient.
+// A layer whose output is scaled by a learnt per-channel gain (NAFBlock's beta / gamma) passes WgradGain: dW is then scaled by
+// rowscale[n], db too, and dgain[n] = sum_k W[n][k] G[n][k] + wbias[n] db'[n].
+// wgrad_need raises *slab_floats / *colsum_floats to what one such gradient needs, so a layout calls it once per layer that shares the buffers.
+struct GemmTN;
+struct WgradGain {
+    const float *rowscale, *W, *wbias;
+    float* dgain;
+};
+void wgrad_need(int64_t M, int N, int K, size_t* slab_floats, size_t* colsum_floats);
+int launch_wgrad(const GemmTN& proto, int yload, const float* X, int ldx, int N, const float* Y, int ldy, int K, int64_t M, float* slab,
+                 float* colsum, float* dW, float* db, int mode, hipStream_t s, const WgradGain& gain = WgradGain{});
+// The backward of a biased dense 3x3 conv on NHWC rows, y = conv3x3(x; w [Cout][Cin][3][3]) + b, from dz = dL/dy [M][Cout]:
+// packs w transposed with flipped taps into wT [Cin][9 Cout], dx [M][Cin] = epi(conv3x3(dz; wT)) with the GEMM epilogue epi and its
+// res / slope operands (E_PLAIN; E_RESID adds res; E_RELU / E_LRELU mask by the saved activation res), then dw, db from dz and x.
+int launch_conv3_bwd(const float* dz, const float* x, const float* w, float* wT, int B, int H, int W, int Cin, int Cout, int epi,
+                     const float* res, float slope, float* dx, float* slab, float* colsum, float* dw, float* db, hipStream_t s);
+// as launch_wgrad_reduce, with slab s weighted by kscale[(s / splits_per_image)][k] (every split inside one image; SCA scale folded into the reduce)
 int launch_wgrad_reduce_scaled(const float* slab, const float* colsum, int splits, int cs_rows, int N, int K, const float* rowscale,
                                const float* W, const float* wbias, float* dW, float* dgain, float* dbias, int mode,
                                const float* kscale, int splits_per_image, hipStream_t s);

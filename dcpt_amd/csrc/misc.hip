@@ -1,6 +1,7 @@
 // Small kernels around the GEMMs: SCA (simplified channel attention) forward/backward pieces,
 // weight packing/transposition, and the deterministic split-slab reduction of weight gradients.
 // Reference: basicsr/archs/nafnet_arch.py:116-127,173 (SCA), :162-163,178,186 (beta/gamma).
+#include "gemm.h"
 #include "kernels.h"
 #include "prof.h"
 
@@ -463,6 +464,37 @@ int launch_wpack(const float* in, float* out, const float* rs, int N, int K, int
 int launch_wgrad_reduce(const float* slab, const float* colsum, int splits, int cs_rows, int N, int K, const float* rowscale,
                         const float* W, const float* wbias, float* dW, float* dgain, float* dbias, int mode, hipStream_t s) {
     return launch_wgrad_reduce_scaled(slab, colsum, splits, cs_rows, N, K, rowscale, W, wbias, dW, dgain, dbias, mode, nullptr, 1, s);
+}
+
+void wgrad_need(int64_t M, int N, int K, size_t* slab_floats, size_t* colsum_floats) {
+    int sp;
+    int64_t rps;
+    gemm_tn_plan(M, N, K, &sp, &rps);
+    const size_t a = (size_t)sp * N * K, b = (size_t)sp * gemm_tn_tiles_k(N, K) * N;
+    if (a > *slab_floats) *slab_floats = a;
+    if (b > *colsum_floats) *colsum_floats = b;
+}
+
+int launch_wgrad(const GemmTN& proto, int yload, const float* X, int ldx, int N, const float* Y, int ldy, int K, int64_t M, float* slab,
+                 float* colsum, float* dW, float* db, int mode, hipStream_t s, const WgradGain& gain) {
+    GemmTN t = proto;
+    t.X = X; t.ldx = ldx; t.N = N; t.Y = Y; t.ldy = ldy; t.K = K; t.M = M;
+    t.slab = slab; t.colsum = colsum;
+    gemm_tn_plan(M, N, K, &t.splits, &t.rows_per_split);   // the plan wgrad_need sized the buffers with
+    DCPT_TRY(launch_gemm_tn(t, A_PLAIN, yload, s));
+    return launch_wgrad_reduce(slab, colsum, t.splits, colsum ? t.splits * gemm_tn_tiles_k(N, K) : 0, N, K, gain.rowscale, gain.W, gain.wbias,
+                               dW, gain.dgain, db, mode, s);
+}
+
+int launch_conv3_bwd(const float* dz, const float* x, const float* w, float* wT, int B, int H, int W, int Cin, int Cout, int epi,
+                     const float* res, float slope, float* dx, float* slab, float* colsum, float* dw, float* db, hipStream_t s) {
+    DCPT_TRY(launch_wpack(w, wT, nullptr, Cout, 9 * Cin, WP_CONV3_T, s));
+    GemmNT g = gemm_nt_conv3(dz, B, H, W, Cout, wT, Cin, dx, Cin);
+    g.res = res; g.slope = slope;
+    DCPT_TRY(launch_gemm_nt(g, A_CONV3, epi, s));
+    GemmTN t{};
+    t.gH = H; t.gW = W; t.gC = Cin;
+    return launch_wgrad(t, A_CONV3, dz, Cout, Cout, x, Cin, 9 * Cin, g.M, slab, colsum, dw, db, WR_CONV3, s);
 }
 
 int launch_wgrad_reduce_scaled(const float* slab, const float* colsum, int splits, int cs_rows, int N, int K, const float* rowscale,

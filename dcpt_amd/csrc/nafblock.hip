@@ -132,19 +132,6 @@ bool ln_in_epilogue(int C) {
     return on && C <= 128;
 }
 
-int wgrad(const float* X, int ldx, int N, const float* Y, int ldy, int K, int yload, const GemmTN& proto, int64_t M,
-          float* slab, float* colsum, const float* rowscale, const float* Wfor_gain, const float* wbias, float* dW,
-          float* dgain, float* dbias, hipStream_t s) {
-    GemmTN t = proto;
-    t.X = X; t.ldx = ldx; t.N = N; t.Y = Y; t.ldy = ldy; t.K = K; t.M = M;
-    t.slab = slab; t.colsum = colsum;
-    gemm_tn_plan(M, N, K, &t.splits, &t.rows_per_split);
-    DCPT_TRY(launch_gemm_tn(t, A_PLAIN, yload, s));
-    DCPT_TRY(launch_wgrad_reduce(slab, colsum, t.splits, t.splits * gemm_tn_tiles_k(N, K), N, K, rowscale, Wfor_gain, wbias, dW,
-                                 dgain, dbias, WR_PLAIN, s));
-    return DCPT_OK;
-}
-
 }  // namespace
 
 extern "C" int dcpt_nafblock_fused_ffn(int C) { return ffn_fused_f32(C) ? 1 : 0; }
@@ -158,10 +145,7 @@ extern "C" int dcpt_nafblock_fwd(const dcpt_nafblock_params* p, const float* inp
     DCPT_CHECK_ARG(B > 0 && B <= 65535 && H > 0 && W > 0 && C > 0 && C % 4 == 0, "nafblock_fwd: bad shape B=%d H=%d W=%d C=%d (B <= 65535, C %% 4 == 0)", B, H, W, C);
     FwdWs w;
     const size_t need = fwd_ws_layout(B, H, W, C, ws, ws_bytes, &w);
-    if (need > ws_bytes || ws == nullptr) {
-        dcpt_set_error("nafblock_fwd: workspace too small (%zu < %zu)", ws_bytes, need);
-        return DCPT_ERR_WS;
-    }
+    DCPT_CHECK_WS("nafblock_fwd", ws, ws_bytes, need);
     const int64_t M = (int64_t)B * H * W;
     const int P = H * W;
     const float eps = 1e-6f;  // nafnet_arch.py:57
@@ -231,10 +215,7 @@ extern "C" int dcpt_nafblock_bwd(const dcpt_nafblock_params* p, const dcpt_nafbl
     DCPT_CHECK_ARG(B > 0 && B <= 65535 && H > 0 && W > 0 && C > 0 && C % 4 == 0, "nafblock_bwd: bad shape B=%d H=%d W=%d C=%d (B <= 65535, C %% 4 == 0)", B, H, W, C);
     BwdWs w;
     const size_t need = bwd_ws_layout(B, H, W, C, ws, ws_bytes, &w);
-    if (need > ws_bytes || ws == nullptr) {
-        dcpt_set_error("nafblock_bwd: workspace too small (%zu < %zu)", ws_bytes, need);
-        return DCPT_ERR_WS;
-    }
+    DCPT_CHECK_WS("nafblock_bwd", ws, ws_bytes, need);
     const int64_t M = (int64_t)B * H * W;
     const int P = H * W;
     const int C2 = 2 * C;
@@ -277,10 +258,11 @@ extern "C" int dcpt_nafblock_bwd(const dcpt_nafblock_params* p, const dcpt_nafbl
     }
     // B2: conv5 / gamma gradients
     tp = GemmTN{};
-    if (ffn) DCPT_TRY(wgrad(dout, C, C, sv->v, C2, C, A_SG, tp, M, w.slab, w.colsum, p->gamma, p->conv5_w, p->conv5_b, gr->conv5_w, gr->gamma, gr->conv5_b, sw));
+    if (ffn) DCPT_TRY(launch_wgrad(tp, A_SG, dout, C, C, sv->v, C2, C, M, w.slab, w.colsum, gr->conv5_w, gr->conv5_b, WR_PLAIN, sw,
+                                   WgradGain{p->gamma, p->conv5_w, p->conv5_b, gr->gamma}));
     else
-    DCPT_TRY(wgrad(dout, C, C, sv->g, C, C, A_PLAIN, tp, M, w.slab, w.colsum, p->gamma, p->conv5_w, p->conv5_b, gr->conv5_w,
-                   gr->gamma, gr->conv5_b, sw));
+    DCPT_TRY(launch_wgrad(tp, A_PLAIN, dout, C, C, sv->g, C, C, M, w.slab, w.colsum, gr->conv5_w, gr->conv5_b, WR_PLAIN, sw,
+                          WgradGain{p->gamma, p->conv5_w, p->conv5_b, gr->gamma}));
     DCPT_TRY(side_fork(sd, 1, s));      // dv
     // B3: grad w.r.t. LN2 output
     g = GemmNT{};
@@ -298,10 +280,9 @@ extern "C" int dcpt_nafblock_bwd(const dcpt_nafblock_params* p, const dcpt_nafbl
     tp = GemmTN{};
     if (ffn) {
         tp.mu = sv->mu2; tp.rstd = sv->rstd2; tp.lnw = p->norm2_w; tp.lnb = p->norm2_b;
-        DCPT_TRY(wgrad(dv, C2, C2, sv->y, C, C, A_LN, tp, M, w.slab, w.colsum, nullptr, nullptr, nullptr, gr->conv4_w, nullptr, gr->conv4_b, sw));
+        DCPT_TRY(launch_wgrad(tp, A_LN, dv, C2, C2, sv->y, C, C, M, w.slab, w.colsum, gr->conv4_w, gr->conv4_b, WR_PLAIN, sw));
     } else
-    DCPT_TRY(wgrad(dv, C2, C2, sv->xn2, C, C, A_PLAIN, tp, M, w.slab, w.colsum, nullptr, nullptr, nullptr, gr->conv4_w, nullptr,
-                   gr->conv4_b, sw));
+    DCPT_TRY(launch_wgrad(tp, A_PLAIN, dv, C2, C2, sv->xn2, C, C, M, w.slab, w.colsum, gr->conv4_w, gr->conv4_b, WR_PLAIN, sw));
     // B5: dy = dout + LN2-backward
     if (!ffn && !lne) DCPT_TRY(launch_ln_bwd(gln, sv->y, sv->mu2, sv->rstd2, p->norm2_w, dout, dy, w.lnpart, w.ln_nblk, M, C, s));
     DCPT_TRY(side_fork(sd, 2, s));      // dy, LN2 partial sums
@@ -336,8 +317,8 @@ extern "C" int dcpt_nafblock_bwd(const dcpt_nafblock_params* p, const dcpt_nafbl
         } else {
             tp = GemmTN{};
             tp.simg = sv->s; tp.P = P;
-            DCPT_TRY(wgrad(dy, C, C, sv->t2, C, C, A_SCALE, tp, M, w.slab, w.colsum, p->beta, p->conv3_w, p->conv3_b, gr->conv3_w,
-                           gr->beta, gr->conv3_b, sw));
+            DCPT_TRY(launch_wgrad(tp, A_SCALE, dy, C, C, sv->t2, C, C, M, w.slab, w.colsum, gr->conv3_w, gr->conv3_b, WR_PLAIN, sw,
+                                  WgradGain{p->beta, p->conv3_w, p->conv3_b, gr->beta}));
         }
     }
     // B8: SCA backward
@@ -362,10 +343,9 @@ extern "C" int dcpt_nafblock_bwd(const dcpt_nafblock_params* p, const dcpt_nafbl
     tp = GemmTN{};
     if (ffn) {
         tp.mu = sv->mu1; tp.rstd = sv->rstd1; tp.lnw = p->norm1_w; tp.lnb = p->norm1_b;
-        DCPT_TRY(wgrad(dt1, C2, C2, inp, C, C, A_LN, tp, M, w.slab, w.colsum, nullptr, nullptr, nullptr, gr->conv1_w, nullptr, gr->conv1_b, sw));
+        DCPT_TRY(launch_wgrad(tp, A_LN, dt1, C2, C2, inp, C, C, M, w.slab, w.colsum, gr->conv1_w, gr->conv1_b, WR_PLAIN, sw));
     } else
-    DCPT_TRY(wgrad(dt1, C2, C2, sv->xn1, C, C, A_PLAIN, tp, M, w.slab, w.colsum, nullptr, nullptr, nullptr, gr->conv1_w, nullptr,
-                   gr->conv1_b, sw));
+    DCPT_TRY(launch_wgrad(tp, A_PLAIN, dt1, C2, C2, sv->xn1, C, C, M, w.slab, w.colsum, gr->conv1_w, gr->conv1_b, WR_PLAIN, sw));
     // B13: dinp = dy + LN1-backward
     if (!lne) DCPT_TRY(launch_ln_bwd(gln, inp, sv->mu1, sv->rstd1, p->norm1_w, dy, dinp, w.lnpart2, w.ln_nblk, M, C, s));
     DCPT_TRY(side_fork(sd, 5, s));      // LN1 partial sums
@@ -420,10 +400,7 @@ extern "C" int dcpt_nafblock_local_fwd(const dcpt_nafblock_params* p, const floa
     if (k2 > W) k2 = W;
     LocalWs w;
     const size_t need = local_layout(B, H, W, C, k2, ws, ws_bytes, &w);
-    if (ws == nullptr || need > ws_bytes) {
-        dcpt_set_error("nafblock_local_fwd: workspace too small (%zu < %zu)", ws_bytes, need);
-        return DCPT_ERR_WS;
-    }
+    DCPT_CHECK_WS("nafblock_local_fwd", ws, ws_bytes, need);
     const int64_t M = (int64_t)B * H * W;
     float* mu = w.stats;
     float* rstd = w.stats + M;

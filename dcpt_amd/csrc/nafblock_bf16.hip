@@ -392,10 +392,7 @@ static int nafblock_fwd_bf16_impl(const dcpt_nafblock_params* p, const uint16_t*
                    "dcpt_nafblock_bf16_fused_ffn(C) is 1; v alone may be null when no backward pass follows)");
     FwdWsB w;
     const size_t need = fwd_layout(B, H, W, C, ws, ws_bytes, &w);
-    if (need > ws_bytes || ws == nullptr) {
-        dcpt_set_error("nafblock_fwd_bf16: workspace too small (%zu < %zu)", ws_bytes, need);
-        return DCPT_ERR_WS;
-    }
+    DCPT_CHECK_WS("nafblock_fwd_bf16", ws, ws_bytes, need);
     const int64_t M = (int64_t)B * H * W;
     const int P = H * W;
     // operand copies of the weights that do not depend on SCA: the caller's per-block pack, or made here
@@ -519,10 +516,7 @@ extern "C" int dcpt_nafblock_local_fwd_bf16(const dcpt_nafblock_params* p, const
     if (k2 > W) k2 = W;
     LocalWsB w;
     const size_t need = local_layout_bf16(B, H, W, C, ws, ws_bytes, &w);
-    if (need > ws_bytes || ws == nullptr) {
-        dcpt_set_error("nafblock_local_fwd_bf16: workspace too small (%zu < %zu)", ws_bytes, need);
-        return DCPT_ERR_WS;
-    }
+    DCPT_CHECK_WS("nafblock_local_fwd_bf16", ws, ws_bytes, need);
     const int64_t M = (int64_t)B * H * W;
     // operand copies of the weights: the caller's per-block pack (whose layout has no place for sca_w: that one copy is made here), or all here
     WpackBJobs j{};
@@ -573,10 +567,7 @@ static int nafblock_bwd_bf16_impl(const dcpt_nafblock_params* p, const dcpt_nafb
     DCPT_CHECK_ARG(shape_ok(B, H, W, C), "nafblock_bwd_bf16: bad shape B=%d H=%d W=%d C=%d (B <= 65535, C %% 8 == 0, C <= 1024)", B, H, W, C);
     BwdWsB w;
     const size_t need = bwd_layout(B, H, W, C, ws, ws_bytes, &w);
-    if (need > ws_bytes || ws == nullptr) {
-        dcpt_set_error("nafblock_bwd_bf16: workspace too small (%zu < %zu)", ws_bytes, need);
-        return DCPT_ERR_WS;
-    }
+    DCPT_CHECK_WS("nafblock_bwd_bf16", ws, ws_bytes, need);
     const int64_t M = (int64_t)B * H * W;
     const int P = H * W;
     const int C2 = 2 * C;
@@ -791,10 +782,7 @@ extern "C" int dcpt_conv1x1_wgrad_bf16(const uint16_t* dY, const uint16_t* X, fl
                    N, K);
     WgWs w;
     const size_t need = wg_layout(M, N, K, ws, ws_bytes, &w);
-    if (need > ws_bytes || ws == nullptr) {
-        dcpt_set_error("conv1x1_wgrad_bf16: workspace too small (%zu < %zu)", ws_bytes, need);
-        return DCPT_ERR_WS;
-    }
+    DCPT_CHECK_WS("conv1x1_wgrad_bf16", ws, ws_bytes, need);
     if (w.tn256) {
         w.g.p[0].X = dY; w.g.p[0].Y = X;
         if (!db) w.g.p[0].colsum = nullptr;

@@ -191,10 +191,7 @@ int prompt_mix_fwd(const float* logits, const float* param, float* weights, T* o
 template <typename T>
 int prompt_mix_bwd(const T* dout, const float* param, const float* weights, float* dlogits, float* dparam, void* ws, size_t ws_bytes, int B,
                    int L, int D, int S, int H, int W, const char* name, hipStream_t s) {
-    if (ws == nullptr || ws_bytes < dcpt_prompt_mix_bwd_ws_bytes(B, D, S)) {
-        dcpt_set_error("%s: workspace too small", name);
-        return DCPT_ERR_WS;
-    }
+    DCPT_CHECK_WS(name, ws, ws_bytes, dcpt_prompt_mix_bwd_ws_bytes(B, D, S));
     float* dP = (float*)ws;
     prompt_mix_bwd_dp_kernel<T><<<dim3(grid_for((int64_t)B * S * S * D)), dim3(256), 0, s>>>(dout, dP, B, D, S, H, W);
     DCPT_CHECK_LAUNCH("prompt_mix_bwd_dp");

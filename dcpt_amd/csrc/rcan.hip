@@ -23,12 +23,6 @@
 
 namespace {
 
-inline unsigned ew_grid(int64_t n) {
-    int64_t nb = cdiv64(n, 256);
-    if (nb > 16384) nb = 16384;
-    return (unsigned)(nb < 1 ? 1 : nb);
-}
-
 // ---- channel attention ------------------------------------------------------------------------------
 // one workgroup per image b: pooled = (sum of the tile / image column sums) / P, h = relu(W1 pooled + b1), s = sigmoid(W2 h + b2).
 // G groups of C threads split the image's tiles (a 256^2 image has 512 of them), then add their G partials in a fixed order.
@@ -215,30 +209,6 @@ __global__ void ps_gather_kernel(const float4* __restrict__ dy, float4* __restri
     }
 }
 
-// ---- weight gradients on the TN kernel (as swin.hip) ------------------------------------------------------
-struct Wgrad {
-    float* slab;
-    float* colsum;
-};
-void wgrad_need(int64_t M, int N, int K, size_t* slab, size_t* cs) {
-    int sp;
-    int64_t rps;
-    gemm_tn_plan(M, N, K, &sp, &rps);
-    const size_t a = (size_t)sp * N * K, b = (size_t)sp * gemm_tn_tiles_k(N, K) * N;
-    if (a > *slab) *slab = a;
-    if (b > *cs) *cs = b;
-}
-// dW[n][ic][tap] = sum_m X[m][n] conv3-im2col(Y)(m, tap*Ci + ic), db[n] = sum_m X[m][n]
-int wgrad_conv3(const float* X, int N, const float* Y, int Ci, int H, int W, int64_t M, const Wgrad& w, float* dW, float* db, hipStream_t s) {
-    GemmTN t{};
-    t.X = X; t.ldx = N; t.N = N; t.Y = Y; t.ldy = Ci; t.K = 9 * Ci; t.M = M; t.gH = H; t.gW = W; t.gC = Ci;
-    t.slab = w.slab; t.colsum = w.colsum;
-    gemm_tn_plan(M, N, t.K, &t.splits, &t.rows_per_split);
-    DCPT_TRY(launch_gemm_tn(t, A_PLAIN, A_CONV3, s));
-    return launch_wgrad_reduce(w.slab, w.colsum, t.splits, t.splits * gemm_tn_tiles_k(N, t.K), N, t.K, nullptr, nullptr, nullptr, dW, nullptr,
-                               db, WR_CONV3, s);
-}
-
 // ---- RCAB workspace ---------------------------------------------------------------------------------
 int dot_splits(int B, int P) {
     int ns = cdiv(512, B);
@@ -362,10 +332,7 @@ extern "C" int dcpt_rcab_fwd(const dcpt_rcab_params* p, const float* x, float* y
     DCPT_TRY(check_rcab(B, H, W, C, Cr, "rcab_fwd"));
     RcabWs w;
     const size_t need = rcab_layout(B, H, W, C, Cr, 0, ws, ws_bytes, &w);
-    if (ws == nullptr || need > ws_bytes) {
-        dcpt_set_error("rcab_fwd: workspace too small");
-        return DCPT_ERR_WS;
-    }
+    DCPT_CHECK_WS("rcab_fwd", ws, ws_bytes, need);
     const int P = H * W;
     const int64_t M = (int64_t)B * P;
     float* h = sv ? sv->h : w.h;
@@ -376,8 +343,8 @@ extern "C" int dcpt_rcab_fwd(const dcpt_rcab_params* p, const float* x, float* y
     DCPT_TRY(launch_wpack(p->conv1_w, w.wp1, nullptr, C, 9 * C, WP_CONV3, s));
     DCPT_TRY(launch_wpack(p->conv2_w, w.wp2, nullptr, C, 9 * C, WP_CONV3, s));
     // h = relu(conv1(x) + b1)
-    GemmNT g{};
-    g.M = M; g.A = x; g.K = 9 * C; g.gH = H; g.gW = W; g.gC = C; g.Bw = w.wp1; g.N = C; g.C = h; g.ldc = C; g.bias = p->conv1_b;
+    GemmNT g = gemm_nt_conv3(x, B, H, W, C, w.wp1, C, h, C);
+    g.bias = p->conv1_b;
     DCPT_TRY(launch_gemm_nt(g, A_CONV3, E_RELU, s));
     // t = conv2(h) + b2, and its per-image column sums
     g.A = h; g.Bw = w.wp2; g.C = t; g.bias = p->conv2_b; g.colpart = w.colpart; g.P = P;
@@ -406,10 +373,7 @@ extern "C" int dcpt_rcab_bwd(const dcpt_rcab_params* p, const dcpt_rcab_params_g
     DCPT_TRY(check_rcab(B, H, W, C, Cr, "rcab_bwd"));
     RcabWs w;
     const size_t need = rcab_layout(B, H, W, C, Cr, 1, ws, ws_bytes, &w);
-    if (ws == nullptr || need > ws_bytes) {
-        dcpt_set_error("rcab_bwd: workspace too small");
-        return DCPT_ERR_WS;
-    }
+    DCPT_CHECK_WS("rcab_bwd", ws, ws_bytes, need);
     const int P = H * W;
     const int64_t M = (int64_t)B * P;
     const int64_t n4 = M * C / 4;
@@ -427,18 +391,11 @@ extern "C" int dcpt_rcab_bwd(const dcpt_rcab_params* p, const dcpt_rcab_params_g
     rcab_dt_kernel<<<dim3(ew_grid(n4)), dim3(256), 0, s>>>(reinterpret_cast<const float4*>(dy), sv->s, w.dpool, reinterpret_cast<float4*>(w.dt),
                                                            n4, C, (int64_t)P * C, res_scale);
     DCPT_CHECK_LAUNCH("rcab_dt");
-    const Wgrad wg{w.slab, w.colsum};
     // conv2: dh = [h > 0] conv2^T(dt);  dW2, db2 from dt and h
-    DCPT_TRY(launch_wpack(p->conv2_w, w.wp2, nullptr, C, 9 * C, WP_CONV3_T, s));
-    GemmNT g{};
-    g.M = M; g.A = w.dt; g.K = 9 * C; g.gH = H; g.gW = W; g.gC = C; g.Bw = w.wp2; g.N = C; g.C = w.dh; g.ldc = C; g.res = sv->h;
-    DCPT_TRY(launch_gemm_nt(g, A_CONV3, E_RELU, s));
-    DCPT_TRY(wgrad_conv3(w.dt, C, sv->h, C, H, W, M, wg, gr->conv2_w, gr->conv2_b, s));
+    DCPT_TRY(launch_conv3_bwd(w.dt, sv->h, p->conv2_w, w.wp2, B, H, W, C, C, E_RELU, sv->h, 0.f, w.dh, w.slab, w.colsum, gr->conv2_w,
+                              gr->conv2_b, s));
     // conv1: dx = dy + conv1^T(dh);  dW1, db1 from dh and x
-    DCPT_TRY(launch_wpack(p->conv1_w, w.wp1, nullptr, C, 9 * C, WP_CONV3_T, s));
-    g.A = w.dh; g.Bw = w.wp1; g.C = dx; g.res = dy;
-    DCPT_TRY(launch_gemm_nt(g, A_CONV3, E_RESID, s));
-    return wgrad_conv3(w.dh, C, x, C, H, W, M, wg, gr->conv1_w, gr->conv1_b, s);
+    return launch_conv3_bwd(w.dh, x, p->conv1_w, w.wp1, B, H, W, C, C, E_RESID, dy, 0.f, dx, w.slab, w.colsum, gr->conv1_w, gr->conv1_b, s);
 }
 
 // =====================================================================================================
@@ -454,10 +411,7 @@ extern "C" int dcpt_conv3x3_ps_fwd(const float* x, const float* w, const float* 
     DCPT_TRY(check_ps(B, H, W, C, r, "conv3x3_ps_fwd"));
     PsWs pw;
     const size_t need = ps_layout(B, H, W, C, r, 0, ws, ws_bytes, &pw);
-    if (ws == nullptr || need > ws_bytes) {
-        dcpt_set_error("conv3x3_ps_fwd: workspace too small");
-        return DCPT_ERR_WS;
-    }
+    DCPT_CHECK_WS("conv3x3_ps_fwd", ws, ws_bytes, need);
     const int N = r * r * C;
     trace_tag("rcan_ps_fwd");
     ps_rowperm_kernel<<<dim3(ew_grid((int64_t)N * 9 * C)), dim3(256), 0, s>>>(w, pw.wq, N, 9 * C, C, r, 0);
@@ -465,8 +419,7 @@ extern "C" int dcpt_conv3x3_ps_fwd(const float* x, const float* w, const float* 
     ps_rowperm_kernel<<<dim3(ew_grid(N)), dim3(256), 0, s>>>(bias, pw.bq, N, 1, C, r, 0);
     DCPT_CHECK_LAUNCH("ps_rowperm");
     DCPT_TRY(launch_wpack(pw.wq, pw.wp, nullptr, N, 9 * C, WP_CONV3, s));
-    GemmNT g{};
-    g.M = (int64_t)B * H * W; g.A = x; g.K = 9 * C; g.gH = H; g.gW = W; g.gC = C; g.Bw = pw.wp; g.N = N; g.C = y; g.ldc = N;
+    GemmNT g = gemm_nt_conv3(x, B, H, W, C, pw.wp, N, y, N);
     g.bias = pw.bq; g.psr = r;
     return launch_gemm_nt(g, A_CONV3, E_PSHUF, s);
 }
@@ -478,10 +431,7 @@ extern "C" int dcpt_conv3x3_ps_bwd(const float* dy, const float* x, const float*
     DCPT_TRY(check_ps(B, H, W, C, r, "conv3x3_ps_bwd"));
     PsWs pw;
     const size_t need = ps_layout(B, H, W, C, r, 1, ws, ws_bytes, &pw);
-    if (ws == nullptr || need > ws_bytes) {
-        dcpt_set_error("conv3x3_ps_bwd: workspace too small");
-        return DCPT_ERR_WS;
-    }
+    DCPT_CHECK_WS("conv3x3_ps_bwd", ws, ws_bytes, need);
     const int N = r * r * C;
     const int64_t M = (int64_t)B * H * W;
     trace_tag("rcan_ps_bwd");
@@ -491,12 +441,8 @@ extern "C" int dcpt_conv3x3_ps_bwd(const float* dy, const float* x, const float*
     DCPT_CHECK_LAUNCH("ps_gather");
     ps_rowperm_kernel<<<dim3(ew_grid((int64_t)N * 9 * C)), dim3(256), 0, s>>>(w, pw.wq, N, 9 * C, C, r, 0);
     DCPT_CHECK_LAUNCH("ps_rowperm");
-    // dx = conv^T(dz): a 3x3 conv of the N-channel map dz with the transposed, flipped weights
-    DCPT_TRY(launch_wpack(pw.wq, pw.wp, nullptr, N, 9 * C, WP_CONV3_T, s));
-    GemmNT g{};
-    g.M = M; g.A = pw.dz; g.K = 9 * N; g.gH = H; g.gW = W; g.gC = N; g.Bw = pw.wp; g.N = C; g.C = dx; g.ldc = C;
-    DCPT_TRY(launch_gemm_nt(g, A_CONV3, E_PLAIN, s));
-    DCPT_TRY(wgrad_conv3(pw.dz, N, x, C, H, W, M, Wgrad{pw.slab, pw.colsum}, pw.dwq, pw.dbq, s));
+    // dx = conv^T(dz): a 3x3 conv of the N-channel map dz with the transposed, flipped weights; the gradients in GEMM column order
+    DCPT_TRY(launch_conv3_bwd(pw.dz, x, pw.wq, pw.wp, B, H, W, C, N, E_PLAIN, nullptr, 0.f, dx, pw.slab, pw.colsum, pw.dwq, pw.dbq, s));
     ps_rowperm_kernel<<<dim3(ew_grid((int64_t)N * 9 * C)), dim3(256), 0, s>>>(pw.dwq, dw, N, 9 * C, C, r, 1);
     DCPT_CHECK_LAUNCH("ps_rowperm");
     ps_rowperm_kernel<<<dim3(ew_grid(N)), dim3(256), 0, s>>>(pw.dbq, dbias, N, 1, C, r, 1);

@@ -57,12 +57,6 @@ __global__ __launch_bounds__(256) void rcab_scale_bf16_kernel(const bf16_t* __re
     }
 }
 
-inline unsigned ew_grid(int64_t n) {
-    int64_t nb = cdiv64(n, 256);
-    if (nb > 16384) nb = 16384;
-    return (unsigned)(nb < 1 ? 1 : nb);
-}
-
 // the limits launch_gemm_nt_bf16 enforces for a conv3 launch of Cout columns over a [B][H][W][C] map (checked here so that an entry point
 // refuses before its first launch, and so that the workspace queries answer 0 without a device); channels <= 1024 as the cached operand images
 bool conv3_ok(int B, int H, int W, int C, int Cout) {
@@ -143,10 +137,7 @@ extern "C" int dcpt_rcab_fwd_bf16(const dcpt_rcab_params* p, const void* wpacked
     DCPT_TRY(pk_check(p->conv2_w, wpacked2, wpacked2_bytes, C, C, "rcab_fwd_bf16"));
     RcabWsB w;
     const size_t need = rcab_layout(B, H, W, C, ws, ws_bytes, &w);
-    if (ws == nullptr || need > ws_bytes) {
-        dcpt_set_error("rcab_fwd_bf16: workspace too small (%zu < %zu)", ws_bytes, need);
-        return DCPT_ERR_WS;
-    }
+    DCPT_CHECK_WS("rcab_fwd_bf16", ws, ws_bytes, need);
     const int P = H * W;
     const int64_t M = (int64_t)B * P;
     trace_tag("rcan_bf16.rcab_fwd");
@@ -182,10 +173,7 @@ extern "C" int dcpt_conv3x3_res_fwd_bf16(const uint16_t* x, const float* w, cons
                    B, H, W, C);
     DCPT_TRY(pk_check(w, wpacked, wpacked_bytes, C, C, "conv3x3_res_fwd_bf16"));
     const size_t need = dcpt_conv3x3_res_bf16_ws_bytes(B, H, W, C);
-    if (ws == nullptr || ws_bytes < need) {
-        dcpt_set_error("conv3x3_res_fwd_bf16: workspace too small (%zu < %zu)", ws_bytes, need);
-        return DCPT_ERR_WS;
-    }
+    DCPT_CHECK_WS("conv3x3_res_fwd_bf16", ws, ws_bytes, need);
     trace_tag("rcan_bf16.res_fwd");
     const bf16_t* bw;
     DCPT_TRY(operand(w, wpacked, static_cast<bf16_t*>(ws), C, C, &bw, s));
@@ -209,10 +197,7 @@ extern "C" int dcpt_conv3x3_ps_fwd_bf16(const uint16_t* x, const float* w, const
     const int N = r * r * C;
     DCPT_TRY(pk_check(w, wpacked, wpacked_bytes, C, N, "conv3x3_ps_fwd_bf16"));
     const size_t need = dcpt_conv3x3_ps_bf16_ws_bytes(B, H, W, C, r);
-    if (ws == nullptr || ws_bytes < need) {
-        dcpt_set_error("conv3x3_ps_fwd_bf16: workspace too small (%zu < %zu)", ws_bytes, need);
-        return DCPT_ERR_WS;
-    }
+    DCPT_CHECK_WS("conv3x3_ps_fwd_bf16", ws, ws_bytes, need);
     trace_tag("rcan_bf16.ps_fwd");
     const bf16_t* bw;
     DCPT_TRY(operand(w, wpacked, static_cast<bf16_t*>(ws), C, N, &bw, s));

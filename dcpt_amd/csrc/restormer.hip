@@ -404,15 +404,6 @@ size_t gdfn_layout(int B, int H, int W, int c, int hp, int backward, void* base,
     return a.off;
 }
 
-int tn_reduce(const float* X, int ldx, int N, const float* Y, int ldy, int K, int yload, const GemmTN& proto, int64_t M,
-              float* slab, float* dW, hipStream_t s) {
-    GemmTN t = proto;
-    t.X = X; t.ldx = ldx; t.N = N; t.Y = Y; t.ldy = ldy; t.K = K; t.M = M; t.slab = slab; t.colsum = nullptr;
-    gemm_tn_plan(M, N, K, &t.splits, &t.rows_per_split);
-    DCPT_TRY(launch_gemm_tn(t, A_PLAIN, yload, s));
-    return launch_wgrad_reduce(slab, nullptr, t.splits, 0, N, K, nullptr, nullptr, nullptr, dW, nullptr, nullptr, WR_PLAIN, s);
-}
-
 }  // namespace
 
 // =====================================================================================================
@@ -431,10 +422,7 @@ extern "C" int dcpt_mdta_fwd(const dcpt_mdta_params* p, const float* x, float* y
     DCPT_CHECK_ARG(heads > 0 && C % heads == 0 && (C / heads) % 4 == 0, "mdta_fwd: C=%d heads=%d (C/heads must be a multiple of 4)", C, heads);
     MdtaWs w;
     const size_t need = mdta_layout(B, H, W, C, heads, 0, ws, ws_bytes, &w);
-    if (ws == nullptr || need > ws_bytes) {
-        dcpt_set_error("mdta_fwd: workspace too small");
-        return DCPT_ERR_WS;
-    }
+    DCPT_CHECK_WS("mdta_fwd", ws, ws_bytes, need);
     const int64_t M = (int64_t)B * H * W;
     const int P = H * W, ch = C / heads, C3 = 3 * C;
     // the normalised activations are materialised once (restormer_arch.py:40,59); the qkv conv and, in backward, its weight
@@ -493,10 +481,7 @@ extern "C" int dcpt_mdta_bwd(const dcpt_mdta_params* p, const dcpt_mdta_params_g
     DCPT_CHECK_ARG(heads > 0 && C % heads == 0 && (C / heads) % 4 == 0, "mdta_bwd: bad shape");
     MdtaWs w;
     const size_t need = mdta_layout(B, H, W, C, heads, 1, ws, ws_bytes, &w);
-    if (ws == nullptr || need > ws_bytes) {
-        dcpt_set_error("mdta_bwd: workspace too small");
-        return DCPT_ERR_WS;
-    }
+    DCPT_CHECK_WS("mdta_bwd", ws, ws_bytes, need);
     const int64_t M = (int64_t)B * H * W;
     const int P = H * W, ch = C / heads, C3 = 3 * C;
     GemmNT g{};
@@ -533,7 +518,7 @@ extern "C" int dcpt_mdta_bwd(const dcpt_mdta_params* p, const dcpt_mdta_params_g
     DCPT_TRY(launch_wpack(p->proj_w, w.wT_proj, nullptr, C, C, WP_TRANSPOSE, s));
     g.M = M; g.A = dy; g.lda = C; g.K = C; g.Bw = w.wT_proj; g.N = C; g.C = w.d_att; g.ldc = C;
     DCPT_TRY(launch_gemm_nt(g, A_PLAIN, E_PLAIN, s));
-    DCPT_TRY(tn_reduce(dy, C, C, out_att, C, C, A_PLAIN, tp, M, w.slab, gr->proj_w, sw));
+    DCPT_TRY(launch_wgrad(tp, A_PLAIN, dy, C, C, out_att, C, C, M, w.slab, nullptr, gr->proj_w, nullptr, WR_PLAIN, sw));
     // B2: dattn[i][j] = sum_p d_att[p][i] v[p][j]   (batched TN)
     GemmTN t{};
     t.M = P; t.X = w.d_att; t.ldx = C; t.N = ch; t.Y = sv->qkv + 2 * C; t.ldy = C3; t.K = ch;
@@ -585,7 +570,7 @@ extern "C" int dcpt_mdta_bwd(const dcpt_mdta_params* p, const dcpt_mdta_params_g
     g.M = M; g.A = w.dqkv1; g.lda = C3; g.K = C3; g.Bw = w.wT_qkv; g.N = C; g.C = w.dxn; g.ldc = C;
     DCPT_TRY(launch_gemm_nt(g, A_PLAIN, E_PLAIN, s));
     tp = GemmTN{};
-    DCPT_TRY(tn_reduce(w.dqkv1, C3, C3, xn, C, C, A_PLAIN, tp, M, w.slab, gr->qkv_w, sw));
+    DCPT_TRY(launch_wgrad(tp, A_PLAIN, w.dqkv1, C3, C3, xn, C, C, M, w.slab, nullptr, gr->qkv_w, nullptr, WR_PLAIN, sw));
     // B7: dx = dy + LN-backward
     DCPT_TRY(launch_ln_bwd_ex(w.dxn, x, sv->mu, sv->rstd, p->norm_w, dy, nullptr, nullptr, biasfree, dx, w.lnpart, w.ln_nblk, M, C, s));
     DCPT_TRY(side_fork(sd, 2, s));          // LayerNorm partial sums
@@ -609,10 +594,7 @@ extern "C" int dcpt_gdfn_fwd(const dcpt_gdfn_params* p, const float* x, float* y
     const int hp = (hidden + 3) / 4 * 4;
     GdfnWs w;
     const size_t need = gdfn_layout(B, H, W, C, hp, 0, ws, ws_bytes, &w);
-    if (ws == nullptr || need > ws_bytes) {
-        dcpt_set_error("gdfn_fwd: workspace too small");
-        return DCPT_ERR_WS;
-    }
+    DCPT_CHECK_WS("gdfn_fwd", ws, ws_bytes, need);
     const int64_t M = (int64_t)B * H * W;
     gdfn_pack_kernel<<<dim3(grid_for((int64_t)2 * hp * C)), dim3(256), 0, s>>>(p->in_w, w.wp_in, C, hidden, hp, 0);
     gdfn_pack_kernel<<<dim3(grid_for((int64_t)18 * hp)), dim3(256), 0, s>>>(p->dw_w, w.w2p, C, hidden, hp, 1);
@@ -643,10 +625,7 @@ extern "C" int dcpt_gdfn_bwd(const dcpt_gdfn_params* p, const dcpt_gdfn_params_g
     const int hp = (hidden + 3) / 4 * 4;
     GdfnWs w;
     const size_t need = gdfn_layout(B, H, W, C, hp, 1, ws, ws_bytes, &w);
-    if (ws == nullptr || need > ws_bytes) {
-        dcpt_set_error("gdfn_bwd: workspace too small");
-        return DCPT_ERR_WS;
-    }
+    DCPT_CHECK_WS("gdfn_bwd", ws, ws_bytes, need);
     const int64_t M = (int64_t)B * H * W;
     gdfn_pack_kernel<<<dim3(grid_for((int64_t)18 * hp)), dim3(256), 0, s>>>(p->dw_w, w.w2p, C, hidden, hp, 1);
     gdfn_pack_kernel<<<dim3(grid_for((int64_t)hp * C)), dim3(256), 0, s>>>(p->out_w, w.wT_out, C, hidden, hp, 3);
@@ -677,7 +656,7 @@ extern "C" int dcpt_gdfn_bwd(const dcpt_gdfn_params* p, const dcpt_gdfn_params_g
     g.M = M; g.A = dy; g.lda = C; g.K = C; g.Bw = w.wT_out; g.N = hp; g.C = w.dt; g.ldc = hp;
     DCPT_TRY(launch_gemm_nt(g, A_PLAIN, E_PLAIN, s));
     if (!t_from_bwd) {
-        DCPT_TRY(tn_reduce(dy, C, C, tg, hp, hp, A_PLAIN, tp, M, w.slab, g_out, sw));
+        DCPT_TRY(launch_wgrad(tp, A_PLAIN, dy, C, C, tg, hp, hp, M, w.slab, nullptr, g_out, nullptr, WR_PLAIN, sw));
         gdfn_unpack_kernel<<<dim3(grid_for((int64_t)C * hidden)), dim3(256), 0, sw>>>(g_out, gr->out_w, C, hidden, hp, 2);
         DCPT_CHECK_LAUNCH("gdfn_unpack_out");
     }
@@ -687,7 +666,7 @@ extern "C" int dcpt_gdfn_bwd(const dcpt_gdfn_params* p, const dcpt_gdfn_params_g
         nblk_dwb = dw_ring_bwd_num_blocks_per_image(DwGeom{B, H, W, hp});
         DCPT_TRY(launch_dw_ring_bwd_gelu_f32(w.dt, sv->u, w.w2p, w.du, w.wpart, B, H, W, hp, s, t_from_bwd ? w.r_t : nullptr));
         if (t_from_bwd) {
-            DCPT_TRY(tn_reduce(dy, C, C, tg, hp, hp, A_PLAIN, tp, M, w.slab, g_out, sw));
+            DCPT_TRY(launch_wgrad(tp, A_PLAIN, dy, C, C, tg, hp, hp, M, w.slab, nullptr, g_out, nullptr, WR_PLAIN, sw));
             gdfn_unpack_kernel<<<dim3(grid_for((int64_t)C * hidden)), dim3(256), 0, sw>>>(g_out, gr->out_w, C, hidden, hp, 2);
             DCPT_CHECK_LAUNCH("gdfn_unpack_out");
         }
@@ -704,7 +683,7 @@ extern "C" int dcpt_gdfn_bwd(const dcpt_gdfn_params* p, const dcpt_gdfn_params_g
     g.M = M; g.A = w.du; g.lda = 2 * hp; g.K = 2 * hp; g.Bw = w.wT_in; g.N = C; g.C = w.dxn; g.ldc = C;
     DCPT_TRY(launch_gemm_nt(g, A_PLAIN, E_PLAIN, s));
     tp = GemmTN{};
-    DCPT_TRY(tn_reduce(w.du, 2 * hp, 2 * hp, xn, C, C, A_PLAIN, tp, M, w.slab, g_in, sw));
+    DCPT_TRY(launch_wgrad(tp, A_PLAIN, w.du, 2 * hp, 2 * hp, xn, C, C, M, w.slab, nullptr, g_in, nullptr, WR_PLAIN, sw));
     gdfn_unpack_kernel<<<dim3(grid_for((int64_t)2 * hidden * C)), dim3(256), 0, sw>>>(g_in, gr->in_w, C, hidden, hp, 0);
     DCPT_CHECK_LAUNCH("gdfn_unpack_in");
     DCPT_TRY(launch_ln_bwd_ex(w.dxn, x, sv->mu, sv->rstd, p->norm_w, dy, nullptr, nullptr, biasfree, dx, w.lnpart, w.ln_nblk, M, C, s));

@@ -767,10 +767,7 @@ extern "C" int dcpt_mdta_bf16_fwd(const dcpt_mdta_params* p, const uint16_t* x, 
     const bool softmax = (flags & DCPT_ATTN_SOFTMAX) != 0;
     MdtaWsB w;
     const size_t need = mdta_layout(B, H, W, C, heads, 0, sv->xn && sv->qkv1 && sv->out_att, ws, ws_bytes, &w);
-    if (ws == nullptr || need > ws_bytes) {
-        dcpt_set_error("mdta_bf16_fwd: workspace too small");
-        return DCPT_ERR_WS;
-    }
+    DCPT_CHECK_WS("mdta_bf16_fwd", ws, ws_bytes, need);
     const int64_t M = (int64_t)B * H * W;
     const int P = H * W, ch = C / heads, C3 = 3 * C;
     const bf16_t* xb = reinterpret_cast<const bf16_t*>(x);
@@ -809,10 +806,7 @@ extern "C" int dcpt_mdta_bf16_bwd(const dcpt_mdta_params* p, const dcpt_mdta_par
     const bool softmax = (flags & DCPT_ATTN_SOFTMAX) != 0;
     MdtaWsB w;
     const size_t need = mdta_layout(B, H, W, C, heads, 1, sv->xn && sv->qkv1 && sv->out_att, ws, ws_bytes, &w);
-    if (ws == nullptr || need > ws_bytes) {
-        dcpt_set_error("mdta_bf16_bwd: workspace too small");
-        return DCPT_ERR_WS;
-    }
+    DCPT_CHECK_WS("mdta_bf16_bwd", ws, ws_bytes, need);
     const int64_t M = (int64_t)B * H * W;
     const int P = H * W, ch = C / heads, C3 = 3 * C;
     const bf16_t* xb = reinterpret_cast<const bf16_t*>(x);
@@ -886,10 +880,7 @@ extern "C" int dcpt_gdfn_bf16_fwd(const dcpt_gdfn_params* p, const uint16_t* x, 
     const int hp = gdfn_hp(hidden);
     GdfnWsB w;
     const size_t need = gdfn_layout(B, H, W, C, hp, 0, sv->xn && sv->t, ws, ws_bytes, &w);
-    if (ws == nullptr || need > ws_bytes) {
-        dcpt_set_error("gdfn_bf16_fwd: workspace too small");
-        return DCPT_ERR_WS;
-    }
+    DCPT_CHECK_WS("gdfn_bf16_fwd", ws, ws_bytes, need);
     const int64_t M = (int64_t)B * H * W;
     const bf16_t* xb = reinterpret_cast<const bf16_t*>(x);
     bf16_t* xn = sv->xn ? reinterpret_cast<bf16_t*>(sv->xn) : w.r_xn;
@@ -920,10 +911,7 @@ extern "C" int dcpt_gdfn_bf16_bwd(const dcpt_gdfn_params* p, const dcpt_gdfn_par
     const int hp = gdfn_hp(hidden);
     GdfnWsB w;
     const size_t need = gdfn_layout(B, H, W, C, hp, 1, sv->xn && sv->t, ws, ws_bytes, &w);
-    if (ws == nullptr || need > ws_bytes) {
-        dcpt_set_error("gdfn_bf16_bwd: workspace too small");
-        return DCPT_ERR_WS;
-    }
+    DCPT_CHECK_WS("gdfn_bf16_bwd", ws, ws_bytes, need);
     const int64_t M = (int64_t)B * H * W;
     const bf16_t* xb = reinterpret_cast<const bf16_t*>(x);
     const bf16_t* dyb = reinterpret_cast<const bf16_t*>(dy);

@@ -209,12 +209,6 @@ __global__ void img_affine_kernel(const float* __restrict__ x, const float* __re
     }
 }
 
-inline unsigned ew_grid(int64_t n) {
-    int64_t nb = cdiv64(n, 256);
-    if (nb > 16384) nb = 16384;
-    return (unsigned)(nb < 1 ? 1 : nb);
-}
-
 int check_window(int B, int H, int W, int C, int heads, int window, int shift, const char* who) {
     DCPT_CHECK_ARG(B > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0, "%s: B=%d H=%d W=%d C=%d (C must be a positive multiple of 4)", who, B,
                    H, W, C);
@@ -250,30 +244,6 @@ int launch_wattn_bwd(const float* qkv, const float* o, const float* dout, const 
     else swin_wattn_bwd_kernel<64><<<grid, dim3(256), 0, s>>>(qkv, o, dout, lse, dqkv, g, scale);
     DCPT_CHECK_LAUNCH("swin_wattn_bwd");
     return DCPT_OK;
-}
-
-// weight and bias gradient of a linear layer on rows: dW[n][k] = sum_m X[m][n] Y'(m, k), db[n] = sum_m X[m][n]
-struct Wgrad {
-    float* slab;
-    float* colsum;
-};
-void wgrad_need(int64_t M, int N, int K, size_t* slab, size_t* cs) {
-    int sp;
-    int64_t rps;
-    gemm_tn_plan(M, N, K, &sp, &rps);
-    const size_t a = (size_t)sp * N * K, b = (size_t)sp * gemm_tn_tiles_k(N, K) * N;
-    if (a > *slab) *slab = a;
-    if (b > *cs) *cs = b;
-}
-int wgrad_bias(const float* X, int N, const float* Y, int K, int yload, const GemmTN& proto, int64_t M, const Wgrad& w, float* dW,
-               float* db, int mode, hipStream_t s) {
-    GemmTN t = proto;
-    t.X = X; t.ldx = N; t.N = N; t.Y = Y; t.ldy = (yload == A_CONV3) ? t.gC : K; t.K = K; t.M = M;
-    t.slab = w.slab; t.colsum = w.colsum;
-    gemm_tn_plan(M, N, K, &t.splits, &t.rows_per_split);
-    DCPT_TRY(launch_gemm_tn(t, A_PLAIN, yload, s));
-    return launch_wgrad_reduce(w.slab, w.colsum, t.splits, t.splits * gemm_tn_tiles_k(N, K), N, K, nullptr, nullptr, nullptr, dW, nullptr,
-                               db, mode, s);
 }
 
 // ---- attention half workspace ----------------------------------------------------------------------
@@ -385,23 +355,19 @@ extern "C" int dcpt_swin_attn_fwd(const dcpt_swin_attn_params* p, const float* x
     DCPT_TRY(check_window(B, H, W, C, heads, window, shift, "swin_attn_fwd"));
     AttnWs w;
     const size_t need = attn_layout(B, H, W, C, 0, ws, ws_bytes, &w);
-    if (ws == nullptr || need > ws_bytes) {
-        dcpt_set_error("swin_attn_fwd: workspace too small");
-        return DCPT_ERR_WS;
-    }
+    DCPT_CHECK_WS("swin_attn_fwd", ws, ws_bytes, need);
     const int64_t M = (int64_t)B * H * W;
     float* mu = sv ? sv->mu : w.mu;
     float* rstd = sv ? sv->rstd : w.rstd;
     float* qkv = sv ? sv->qkv : w.qkv;
     float* att = sv ? sv->att : w.att;
     DCPT_TRY(launch_ln_stats(x, mu, rstd, M, C, SWIN_LN_EPS, s));
-    GemmNT g{};
-    g.M = M; g.A = x; g.lda = C; g.K = C; g.Bw = p->qkv_w; g.N = 3 * C; g.C = qkv; g.ldc = 3 * C; g.bias = p->qkv_b;
-    g.mu = mu; g.rstd = rstd; g.lnw = p->norm_w; g.lnb = p->norm_b;
+    GemmNT g = gemm_nt_linear(x, C, M, C, p->qkv_w, 3 * C, qkv, 3 * C);
+    g.bias = p->qkv_b; g.mu = mu; g.rstd = rstd; g.lnw = p->norm_w; g.lnb = p->norm_b;
     DCPT_TRY(launch_gemm_nt(g, A_LN, E_BIAS, s));
     DCPT_TRY(launch_wattn_fwd(qkv, att, sv ? sv->lse : nullptr, win_geom(B, H, W, C, heads, window, shift), s));
-    g = GemmNT{};
-    g.M = M; g.A = att; g.lda = C; g.K = C; g.Bw = p->proj_w; g.N = C; g.C = y; g.ldc = C; g.res = x; g.bias = p->proj_b;
+    g = gemm_nt_linear(att, C, M, C, p->proj_w, C, y, C);
+    g.res = x; g.bias = p->proj_b;
     return launch_gemm_nt(g, A_PLAIN, E_RESID, s);
 }
 
@@ -416,28 +382,20 @@ extern "C" int dcpt_swin_attn_bwd(const dcpt_swin_attn_params* p, const dcpt_swi
     DCPT_TRY(check_window(B, H, W, C, heads, window, shift, "swin_attn_bwd"));
     AttnWs w;
     const size_t need = attn_layout(B, H, W, C, 1, ws, ws_bytes, &w);
-    if (ws == nullptr || need > ws_bytes) {
-        dcpt_set_error("swin_attn_bwd: workspace too small");
-        return DCPT_ERR_WS;
-    }
+    DCPT_CHECK_WS("swin_attn_bwd", ws, ws_bytes, need);
     const int64_t M = (int64_t)B * H * W;
-    const Wgrad wg{w.slab, w.colsum};
     // proj: d(att) = dy Wproj;  dWproj = dy^T att, dbproj = colsum(dy)
     DCPT_TRY(launch_wpack(p->proj_w, w.wT_proj, nullptr, C, C, WP_TRANSPOSE, s));
-    GemmNT g{};
-    g.M = M; g.A = dy; g.lda = C; g.K = C; g.Bw = w.wT_proj; g.N = C; g.C = w.datt; g.ldc = C;
-    DCPT_TRY(launch_gemm_nt(g, A_PLAIN, E_PLAIN, s));
+    DCPT_TRY(launch_gemm_nt(gemm_nt_linear(dy, C, M, C, w.wT_proj, C, w.datt, C), A_PLAIN, E_PLAIN, s));
     GemmTN tp{};
-    DCPT_TRY(wgrad_bias(dy, C, sv->att, C, A_PLAIN, tp, M, wg, gr->proj_w, gr->proj_b, WR_PLAIN, s));
+    DCPT_TRY(launch_wgrad(tp, A_PLAIN, dy, C, C, sv->att, C, C, M, w.slab, w.colsum, gr->proj_w, gr->proj_b, WR_PLAIN, s));
     // windowed attention
     DCPT_TRY(launch_wattn_bwd(sv->qkv, sv->att, w.datt, sv->lse, w.dqkv, win_geom(B, H, W, C, heads, window, shift), s));
     // qkv: d(LN1 x) = dqkv Wqkv;  dWqkv = dqkv^T LN1(x) (LayerNorm in the operand loader), dbqkv = colsum(dqkv)
     DCPT_TRY(launch_wpack(p->qkv_w, w.wT_qkv, nullptr, 3 * C, C, WP_TRANSPOSE, s));
-    g = GemmNT{};
-    g.M = M; g.A = w.dqkv; g.lda = 3 * C; g.K = 3 * C; g.Bw = w.wT_qkv; g.N = C; g.C = w.dxn; g.ldc = C;
-    DCPT_TRY(launch_gemm_nt(g, A_PLAIN, E_PLAIN, s));
+    DCPT_TRY(launch_gemm_nt(gemm_nt_linear(w.dqkv, 3 * C, M, 3 * C, w.wT_qkv, C, w.dxn, C), A_PLAIN, E_PLAIN, s));
     tp.mu = sv->mu; tp.rstd = sv->rstd; tp.lnw = p->norm_w; tp.lnb = p->norm_b;
-    DCPT_TRY(wgrad_bias(w.dqkv, 3 * C, x, C, A_LN, tp, M, wg, gr->qkv_w, gr->qkv_b, WR_PLAIN, s));
+    DCPT_TRY(launch_wgrad(tp, A_LN, w.dqkv, 3 * C, 3 * C, x, C, C, M, w.slab, w.colsum, gr->qkv_w, gr->qkv_b, WR_PLAIN, s));
     // dx = dy + LN-backward
     DCPT_TRY(launch_ln_bwd(w.dxn, x, sv->mu, sv->rstd, p->norm_w, dy, dx, w.lnpart, w.ln_nblk, M, C, s));
     return launch_colpart_reduce(w.lnpart, w.ln_nblk, 3, C, gr->norm_w, gr->norm_b, nullptr, s);
@@ -457,23 +415,19 @@ extern "C" int dcpt_swin_mlp_fwd(const dcpt_swin_mlp_params* p, const float* x, 
                    "swin_mlp_fwd: C=%d hidden=%d (multiples of 4)", C, hidden);
     MlpWs w;
     const size_t need = mlp_layout(B, H, W, C, hidden, 0, ws, ws_bytes, &w);
-    if (ws == nullptr || need > ws_bytes) {
-        dcpt_set_error("swin_mlp_fwd: workspace too small");
-        return DCPT_ERR_WS;
-    }
+    DCPT_CHECK_WS("swin_mlp_fwd", ws, ws_bytes, need);
     const int64_t M = (int64_t)B * H * W;
     float* mu = sv ? sv->mu : w.mu;
     float* rstd = sv ? sv->rstd : w.rstd;
     float* h = sv ? sv->h : w.h;
     DCPT_TRY(launch_ln_stats(x, mu, rstd, M, C, SWIN_LN_EPS, s));
-    GemmNT g{};
-    g.M = M; g.A = x; g.lda = C; g.K = C; g.Bw = p->fc1_w; g.N = hidden; g.C = h; g.ldc = hidden; g.bias = p->fc1_b;
-    g.mu = mu; g.rstd = rstd; g.lnw = p->norm_w; g.lnb = p->norm_b;
+    GemmNT g = gemm_nt_linear(x, C, M, C, p->fc1_w, hidden, h, hidden);
+    g.bias = p->fc1_b; g.mu = mu; g.rstd = rstd; g.lnw = p->norm_w; g.lnb = p->norm_b;
     DCPT_TRY(launch_gemm_nt(g, A_LN, E_BIAS, s));
     gelu_fwd_kernel<<<dim3(ew_grid(M * hidden)), dim3(256), 0, s>>>(h, w.g, M * hidden);
     DCPT_CHECK_LAUNCH("swin_gelu_fwd");
-    g = GemmNT{};
-    g.M = M; g.A = w.g; g.lda = hidden; g.K = hidden; g.Bw = p->fc2_w; g.N = C; g.C = y; g.ldc = C; g.res = x; g.bias = p->fc2_b;
+    g = gemm_nt_linear(w.g, hidden, M, hidden, p->fc2_w, C, y, C);
+    g.res = x; g.bias = p->fc2_b;
     return launch_gemm_nt(g, A_PLAIN, E_RESID, s);
 }
 
@@ -489,30 +443,22 @@ extern "C" int dcpt_swin_mlp_bwd(const dcpt_swin_mlp_params* p, const dcpt_swin_
                    "swin_mlp_bwd: C=%d hidden=%d (multiples of 4)", C, hidden);
     MlpWs w;
     const size_t need = mlp_layout(B, H, W, C, hidden, 1, ws, ws_bytes, &w);
-    if (ws == nullptr || need > ws_bytes) {
-        dcpt_set_error("swin_mlp_bwd: workspace too small");
-        return DCPT_ERR_WS;
-    }
+    DCPT_CHECK_WS("swin_mlp_bwd", ws, ws_bytes, need);
     const int64_t M = (int64_t)B * H * W;
-    const Wgrad wg{w.slab, w.colsum};
     gelu_fwd_kernel<<<dim3(ew_grid(M * hidden)), dim3(256), 0, s>>>(sv->h, w.g, M * hidden);   // the fc2 operand, recomputed
     DCPT_CHECK_LAUNCH("swin_gelu_fwd");
     // fc2: dg = dy W2;  dW2 = dy^T gelu(h), db2 = colsum(dy)
     DCPT_TRY(launch_wpack(p->fc2_w, w.wT2, nullptr, C, hidden, WP_TRANSPOSE, s));
-    GemmNT g{};
-    g.M = M; g.A = dy; g.lda = C; g.K = C; g.Bw = w.wT2; g.N = hidden; g.C = w.dh; g.ldc = hidden;
-    DCPT_TRY(launch_gemm_nt(g, A_PLAIN, E_PLAIN, s));
+    DCPT_TRY(launch_gemm_nt(gemm_nt_linear(dy, C, M, C, w.wT2, hidden, w.dh, hidden), A_PLAIN, E_PLAIN, s));
     GemmTN tp{};
-    DCPT_TRY(wgrad_bias(dy, C, w.g, hidden, A_PLAIN, tp, M, wg, gr->fc2_w, gr->fc2_b, WR_PLAIN, s));
+    DCPT_TRY(launch_wgrad(tp, A_PLAIN, dy, C, C, w.g, hidden, hidden, M, w.slab, w.colsum, gr->fc2_w, gr->fc2_b, WR_PLAIN, s));
     gelu_bwd_kernel<<<dim3(ew_grid(M * hidden)), dim3(256), 0, s>>>(sv->h, w.dh, M * hidden);
     DCPT_CHECK_LAUNCH("swin_gelu_bwd");
     // fc1: d(LN2 x) = dh W1;  dW1 = dh^T LN2(x), db1 = colsum(dh)
     DCPT_TRY(launch_wpack(p->fc1_w, w.wT1, nullptr, hidden, C, WP_TRANSPOSE, s));
-    g = GemmNT{};
-    g.M = M; g.A = w.dh; g.lda = hidden; g.K = hidden; g.Bw = w.wT1; g.N = C; g.C = w.dxn; g.ldc = C;
-    DCPT_TRY(launch_gemm_nt(g, A_PLAIN, E_PLAIN, s));
+    DCPT_TRY(launch_gemm_nt(gemm_nt_linear(w.dh, hidden, M, hidden, w.wT1, C, w.dxn, C), A_PLAIN, E_PLAIN, s));
     tp.mu = sv->mu; tp.rstd = sv->rstd; tp.lnw = p->norm_w; tp.lnb = p->norm_b;
-    DCPT_TRY(wgrad_bias(w.dh, hidden, x, C, A_LN, tp, M, wg, gr->fc1_w, gr->fc1_b, WR_PLAIN, s));
+    DCPT_TRY(launch_wgrad(tp, A_LN, w.dh, hidden, hidden, x, C, C, M, w.slab, w.colsum, gr->fc1_w, gr->fc1_b, WR_PLAIN, s));
     DCPT_TRY(launch_ln_bwd(w.dxn, x, sv->mu, sv->rstd, p->norm_w, dy, dx, w.lnpart, w.ln_nblk, M, C, s));
     return launch_colpart_reduce(w.lnpart, w.ln_nblk, 3, C, gr->norm_w, gr->norm_b, nullptr, s);
 }
@@ -529,14 +475,10 @@ extern "C" int dcpt_conv3x3_res_fwd(const float* x, const float* w, const float*
     DCPT_CHECK_ARG(B > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0, "conv3x3_res_fwd: C=%d must be a positive multiple of 4", C);
     ConvResWs cw;
     const size_t need = convres_layout(B, H, W, C, 0, ws, ws_bytes, &cw);
-    if (ws == nullptr || need > ws_bytes) {
-        dcpt_set_error("conv3x3_res_fwd: workspace too small");
-        return DCPT_ERR_WS;
-    }
+    DCPT_CHECK_WS("conv3x3_res_fwd", ws, ws_bytes, need);
     trace_tag("swin_conv3x3_res_fwd");
     DCPT_TRY(launch_wpack(w, cw.wp, nullptr, C, 9 * C, WP_CONV3, s));
-    GemmNT g{};
-    g.M = (int64_t)B * H * W; g.A = x; g.K = 9 * C; g.gH = H; g.gW = W; g.gC = C; g.Bw = cw.wp; g.N = C; g.C = y; g.ldc = C;
+    GemmNT g = gemm_nt_conv3(x, B, H, W, C, cw.wp, C, y, C);
     g.bias = bias; g.res = res;
     return launch_gemm_nt(g, A_CONV3, E_RESID, s);
 }
@@ -548,19 +490,9 @@ extern "C" int dcpt_conv3x3_res_bwd(const float* dy, const float* x, const float
     DCPT_CHECK_ARG(B > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0, "conv3x3_res_bwd: C=%d must be a positive multiple of 4", C);
     ConvResWs cw;
     const size_t need = convres_layout(B, H, W, C, 1, ws, ws_bytes, &cw);
-    if (ws == nullptr || need > ws_bytes) {
-        dcpt_set_error("conv3x3_res_bwd: workspace too small");
-        return DCPT_ERR_WS;
-    }
+    DCPT_CHECK_WS("conv3x3_res_bwd", ws, ws_bytes, need);
     trace_tag("swin_conv3x3_res_bwd");
-    const int64_t M = (int64_t)B * H * W;
-    DCPT_TRY(launch_wpack(w, cw.wp, nullptr, C, 9 * C, WP_CONV3_T, s));
-    GemmNT g{};
-    g.M = M; g.A = dy; g.K = 9 * C; g.gH = H; g.gW = W; g.gC = C; g.Bw = cw.wp; g.N = C; g.C = dx; g.ldc = C;
-    DCPT_TRY(launch_gemm_nt(g, A_CONV3, E_PLAIN, s));
-    GemmTN t{};
-    t.gH = H; t.gW = W; t.gC = C;
-    return wgrad_bias(dy, C, x, 9 * C, A_CONV3, t, M, Wgrad{cw.slab, cw.colsum}, dw, dbias, WR_CONV3, s);
+    return launch_conv3_bwd(dy, x, w, cw.wp, B, H, W, C, C, E_PLAIN, nullptr, 0.f, dx, cw.slab, cw.colsum, dw, dbias, s);
 }
 
 // =====================================================================================================

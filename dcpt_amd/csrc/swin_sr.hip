@@ -23,12 +23,6 @@ namespace {
 
 constexpr float SLOPE_3CONV = 0.2f;
 
-inline unsigned ew_grid(int64_t n) {
-    int64_t nb = cdiv64(n, 256);
-    if (nb > 16384) nb = 16384;
-    return (unsigned)(nb < 1 ? 1 : nb);
-}
-
 // dz = dy * (y > 0 ? 1 : slope)
 __global__ void lrelu_mask_kernel(const float4* __restrict__ dy, const float4* __restrict__ y, float4* __restrict__ dz, int64_t n4, float slope) {
     for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n4; e += (int64_t)gridDim.x * blockDim.x) {
@@ -92,31 +86,6 @@ __global__ void ps_img_gather_kernel(const float* __restrict__ dimg, float* __re
     }
 }
 
-// ---- weight gradients on the TN kernel (as rcan.hip / swin.hip) ------------------------------------------------
-struct Wgrad {
-    float* slab;
-    float* colsum;
-};
-void wgrad_need(int64_t M, int N, int K, size_t* slab, size_t* cs) {
-    int sp;
-    int64_t rps;
-    gemm_tn_plan(M, N, K, &sp, &rps);
-    const size_t a = (size_t)sp * N * K, b = (size_t)sp * gemm_tn_tiles_k(N, K) * N;
-    if (a > *slab) *slab = a;
-    if (b > *cs) *cs = b;
-}
-// yload A_PLAIN: dW[n][k] = sum_m X[m][n] Y[m][k] (K = columns of Y);  A_CONV3 / A_CONV3UP: dW[n][ic][tap] over the im2col of the
-// gH x gW (x 2) image Y with Ci channels (K = 9 Ci);  db[n] = sum_m X[m][n]
-int wgrad(const float* X, int N, const float* Y, int K, int yload, int gH, int gW, int64_t M, const Wgrad& w, float* dW, float* db, hipStream_t s) {
-    GemmTN t{};
-    t.X = X; t.ldx = N; t.N = N; t.Y = Y; t.K = K; t.M = M; t.gH = gH; t.gW = gW; t.gC = K / 9; t.ldy = (yload == A_PLAIN) ? K : K / 9;
-    t.slab = w.slab; t.colsum = w.colsum;
-    gemm_tn_plan(M, N, K, &t.splits, &t.rows_per_split);
-    DCPT_TRY(launch_gemm_tn(t, A_PLAIN, yload, s));
-    return launch_wgrad_reduce(w.slab, w.colsum, t.splits, t.splits * gemm_tn_tiles_k(N, K), N, K, nullptr, nullptr, nullptr, dW, nullptr, db,
-                               yload == A_PLAIN ? WR_PLAIN : WR_CONV3, s);
-}
-
 int lrelu_mask(const float* dy, const float* y, float* dz, int64_t n, float slope, hipStream_t s) {
     lrelu_mask_kernel<<<dim3(ew_grid(n / 4)), dim3(256), 0, s>>>(reinterpret_cast<const float4*>(dy), reinterpret_cast<const float4*>(y),
                                                                  reinterpret_cast<float4*>(dz), n / 4, slope);
@@ -126,12 +95,6 @@ int lrelu_mask(const float* dy, const float* y, float* dz, int64_t n, float slop
 
 bool map_ok(int B, int H, int W) { return B > 0 && H > 0 && W > 0 && (int64_t)H * W < (1 << 28) && (int64_t)B * H * W < (1ll << 40); }
 bool slope_ok(float slope) { return slope >= 0.f && slope <= 1.f; }
-
-#define WS_OR_FAIL(name, need)                        \
-    if (ws == nullptr || (need) > ws_bytes) {         \
-        dcpt_set_error(name ": workspace too small"); \
-        return DCPT_ERR_WS;                           \
-    }
 
 // ---- conv + LeakyReLU (optionally over the nearest-2x up-sampling) ------------------------------------------------
 struct ActWs {
@@ -168,15 +131,12 @@ int act_fwd(const char* who, const float* x, const float* w, const float* bias, 
                    (double)slope);
     ActWs aw;
     const size_t need = act_layout(B, H, W, Cin, Cout, up, 0, ws, ws_bytes, &aw);
-    if (ws == nullptr || need > ws_bytes) {
-        dcpt_set_error("%s: workspace too small", who);
-        return DCPT_ERR_WS;
-    }
+    DCPT_CHECK_WS(who, ws, ws_bytes, need);
     trace_tag(up ? "swinsr_up2_conv_act_fwd" : "swinsr_conv_act_fwd");
     DCPT_TRY(launch_wpack(w, aw.wp, nullptr, Cout, 9 * Cin, WP_CONV3, s));
-    GemmNT g{};
-    g.M = (int64_t)B * H * W * (up ? 4 : 1); g.A = x; g.K = 9 * Cin; g.gH = H; g.gW = W; g.gC = Cin; g.Bw = aw.wp; g.N = Cout; g.C = y;
-    g.ldc = Cout; g.bias = bias; g.slope = slope;
+    GemmNT g = gemm_nt_conv3(x, B, H, W, Cin, aw.wp, Cout, y, Cout);
+    if (up) g.M *= 4;   // the rows are the pixels of the 2H x 2W grid
+    g.bias = bias; g.slope = slope;
     return launch_gemm_nt(g, up ? A_CONV3UP : A_CONV3, E_LRELU, s);
 }
 
@@ -188,26 +148,21 @@ int act_bwd(const char* who, const float* dy, const float* x, const float* y, co
                    (double)slope);
     ActWs aw;
     const size_t need = act_layout(B, H, W, Cin, Cout, up, 1, ws, ws_bytes, &aw);
-    if (ws == nullptr || need > ws_bytes) {
-        dcpt_set_error("%s: workspace too small", who);
-        return DCPT_ERR_WS;
-    }
+    DCPT_CHECK_WS(who, ws, ws_bytes, need);
     trace_tag(up ? "swinsr_up2_conv_act_bwd" : "swinsr_conv_act_bwd");
     const int64_t M = (int64_t)B * H * W, Mo = up ? 4 * M : M;
-    const int Ho = up ? 2 * H : H, Wo = up ? 2 * W : W;
     DCPT_TRY(lrelu_mask(dy, y, aw.dz, Mo * Cout, slope, s));
-    // dgrad on the output grid: a 3x3 conv of dz with the transposed, flipped weights
+    if (!up) return launch_conv3_bwd(aw.dz, x, w, aw.wp, B, H, W, Cin, Cout, E_PLAIN, nullptr, 0.f, dx, aw.slab, aw.colsum, dw, dbias, s);
+    // dgrad on the 2H x 2W output grid: a 3x3 conv of dz with the transposed, flipped weights, then the sum of each 2 x 2 block
     DCPT_TRY(launch_wpack(w, aw.wp, nullptr, Cout, 9 * Cin, WP_CONV3_T, s));
-    GemmNT g{};
-    g.M = Mo; g.A = aw.dz; g.K = 9 * Cout; g.gH = Ho; g.gW = Wo; g.gC = Cout; g.Bw = aw.wp; g.N = Cin; g.C = up ? aw.du : dx; g.ldc = Cin;
-    DCPT_TRY(launch_gemm_nt(g, A_CONV3, E_PLAIN, s));
-    if (up) {
-        const int64_t n4 = M * Cin / 4;
-        sum2x2_kernel<<<dim3(ew_grid(n4)), dim3(256), 0, s>>>(reinterpret_cast<const float4*>(aw.du), reinterpret_cast<float4*>(dx), n4, H, W,
-                                                              Cin / 4);
-        DCPT_CHECK_LAUNCH("sum2x2");
-    }
-    return wgrad(aw.dz, Cout, x, 9 * Cin, up ? A_CONV3UP : A_CONV3, H, W, Mo, Wgrad{aw.slab, aw.colsum}, dw, dbias, s);
+    DCPT_TRY(launch_gemm_nt(gemm_nt_conv3(aw.dz, B, 2 * H, 2 * W, Cout, aw.wp, Cin, aw.du, Cin), A_CONV3, E_PLAIN, s));
+    const int64_t n4 = M * Cin / 4;
+    sum2x2_kernel<<<dim3(ew_grid(n4)), dim3(256), 0, s>>>(reinterpret_cast<const float4*>(aw.du), reinterpret_cast<float4*>(dx), n4, H, W,
+                                                          Cin / 4);
+    DCPT_CHECK_LAUNCH("sum2x2");
+    GemmTN t{};
+    t.gH = H; t.gW = W; t.gC = Cin;   // the coarse map x; the rows are on the fine grid
+    return launch_wgrad(t, A_CONV3UP, aw.dz, Cout, Cout, x, Cin, 9 * Cin, Mo, aw.slab, aw.colsum, dw, dbias, WR_CONV3, s);
 }
 
 // ---- one-step upsampler -------------------------------------------------------------------------------------
@@ -331,7 +286,7 @@ extern "C" int dcpt_conv3x3_ps_out_fwd(const float* x, const float* w, const flo
     DCPT_TRY(check_psout(B, H, W, C, Cimg, r, "conv3x3_ps_out_fwd"));
     PsOutWs pw;
     const size_t need = psout_layout(B, H, W, C, Cimg, r, 0, ws, ws_bytes, &pw);
-    WS_OR_FAIL("conv3x3_ps_out_fwd", need)
+    DCPT_CHECK_WS("conv3x3_ps_out_fwd", ws, ws_bytes, need);
     const int N = r * r * Cimg, Np = ps_npad(Cimg, r);
     const int64_t M = (int64_t)B * H * W;
     trace_tag("swinsr_ps_out_fwd");
@@ -340,8 +295,8 @@ extern "C" int dcpt_conv3x3_ps_out_fwd(const float* x, const float* w, const flo
     pad_copy_kernel<<<dim3(1), dim3(256), 0, s>>>(bias, pw.bq, N, Np);
     DCPT_CHECK_LAUNCH("pad_copy");
     DCPT_TRY(launch_wpack(pw.wq, pw.wp, nullptr, Np, 9 * C, WP_CONV3, s));
-    GemmNT g{};
-    g.M = M; g.A = x; g.K = 9 * C; g.gH = H; g.gW = W; g.gC = C; g.Bw = pw.wp; g.N = Np; g.C = pw.z; g.ldc = Np; g.bias = pw.bq; g.slope = 1.f;
+    GemmNT g = gemm_nt_conv3(x, B, H, W, C, pw.wp, Np, pw.z, Np);
+    g.bias = pw.bq; g.slope = 1.f;
     DCPT_TRY(launch_gemm_nt(g, A_CONV3, E_LRELU, s));   // slope 1: the plain biased conv
     const int64_t n = M * N;
     ps_img_scatter_kernel<<<dim3(ew_grid(n)), dim3(256), 0, s>>>(pw.z, y, n, H, W, Cimg, r, Np);
@@ -356,7 +311,7 @@ extern "C" int dcpt_conv3x3_ps_out_bwd(const float* dy, const float* x, const fl
     DCPT_TRY(check_psout(B, H, W, C, Cimg, r, "conv3x3_ps_out_bwd"));
     PsOutWs pw;
     const size_t need = psout_layout(B, H, W, C, Cimg, r, 1, ws, ws_bytes, &pw);
-    WS_OR_FAIL("conv3x3_ps_out_bwd", need)
+    DCPT_CHECK_WS("conv3x3_ps_out_bwd", ws, ws_bytes, need);
     const int N = r * r * Cimg, Np = ps_npad(Cimg, r);
     const int64_t M = (int64_t)B * H * W;
     trace_tag("swinsr_ps_out_bwd");
@@ -365,11 +320,7 @@ extern "C" int dcpt_conv3x3_ps_out_bwd(const float* dy, const float* x, const fl
     pad_copy_kernel<<<dim3(ew_grid((int64_t)Np * 9 * C)), dim3(256), 0, s>>>(w, pw.wq, (int64_t)N * 9 * C, (int64_t)Np * 9 * C);
     DCPT_CHECK_LAUNCH("pad_copy");
     // dx = conv^T(dz): a 3x3 conv of the Npad-channel map dz with the transposed, flipped weights (the padding rows are zero)
-    DCPT_TRY(launch_wpack(pw.wq, pw.wp, nullptr, Np, 9 * C, WP_CONV3_T, s));
-    GemmNT g{};
-    g.M = M; g.A = pw.z; g.K = 9 * Np; g.gH = H; g.gW = W; g.gC = Np; g.Bw = pw.wp; g.N = C; g.C = dx; g.ldc = C;
-    DCPT_TRY(launch_gemm_nt(g, A_CONV3, E_PLAIN, s));
-    DCPT_TRY(wgrad(pw.z, Np, x, 9 * C, A_CONV3, H, W, M, Wgrad{pw.slab, pw.colsum}, pw.dwq, pw.dbq, s));
+    DCPT_TRY(launch_conv3_bwd(pw.z, x, pw.wq, pw.wp, B, H, W, C, Np, E_PLAIN, nullptr, 0.f, dx, pw.slab, pw.colsum, pw.dwq, pw.dbq, s));
     pad_copy_kernel<<<dim3(ew_grid((int64_t)N * 9 * C)), dim3(256), 0, s>>>(pw.dwq, dw, (int64_t)N * 9 * C, (int64_t)N * 9 * C);
     DCPT_CHECK_LAUNCH("pad_copy");
     pad_copy_kernel<<<dim3(1), dim3(256), 0, s>>>(pw.dbq, dbias, N, N);
@@ -392,7 +343,7 @@ extern "C" int dcpt_conv3conv_res_fwd(const dcpt_conv3conv_params* p, const floa
     DCPT_TRY(check_c3(B, H, W, C, "conv3conv_res_fwd"));
     C3Ws cw;
     const size_t need = c3_layout(B, H, W, C, 0, ws, ws_bytes, &cw);
-    WS_OR_FAIL("conv3conv_res_fwd", need)
+    DCPT_CHECK_WS("conv3conv_res_fwd", ws, ws_bytes, need);
     const int Cq = C / 4;
     const int64_t M = (int64_t)B * H * W;
     if (!a1) {
@@ -402,15 +353,14 @@ extern "C" int dcpt_conv3conv_res_fwd(const dcpt_conv3conv_params* p, const floa
     trace_tag("swinsr_conv3conv_fwd");
     DCPT_TRY(launch_wpack(p->conv1_w, cw.wp1, nullptr, Cq, 9 * C, WP_CONV3, s));
     DCPT_TRY(launch_wpack(p->conv3_w, cw.wp3, nullptr, C, 9 * Cq, WP_CONV3, s));
-    GemmNT g{};
-    g.M = M; g.A = x; g.K = 9 * C; g.gH = H; g.gW = W; g.gC = C; g.Bw = cw.wp1; g.N = Cq; g.C = a1; g.ldc = Cq; g.bias = p->conv1_b;
-    g.slope = SLOPE_3CONV;
+    GemmNT g = gemm_nt_conv3(x, B, H, W, C, cw.wp1, Cq, a1, Cq);
+    g.bias = p->conv1_b; g.slope = SLOPE_3CONV;
     DCPT_TRY(launch_gemm_nt(g, A_CONV3, E_LRELU, s));
-    g = GemmNT{};
-    g.M = M; g.A = a1; g.lda = Cq; g.K = Cq; g.Bw = p->conv2_w; g.N = Cq; g.C = a2; g.ldc = Cq; g.bias = p->conv2_b; g.slope = SLOPE_3CONV;
+    g = gemm_nt_linear(a1, Cq, M, Cq, p->conv2_w, Cq, a2, Cq);
+    g.bias = p->conv2_b; g.slope = SLOPE_3CONV;
     DCPT_TRY(launch_gemm_nt(g, A_PLAIN, E_LRELU, s));
-    g = GemmNT{};
-    g.M = M; g.A = a2; g.K = 9 * Cq; g.gH = H; g.gW = W; g.gC = Cq; g.Bw = cw.wp3; g.N = C; g.C = y; g.ldc = C; g.bias = p->conv3_b; g.res = res;
+    g = gemm_nt_conv3(a2, B, H, W, Cq, cw.wp3, C, y, C);
+    g.bias = p->conv3_b; g.res = res;
     return launch_gemm_nt(g, A_CONV3, E_RESID, s);
 }
 
@@ -423,28 +373,20 @@ extern "C" int dcpt_conv3conv_res_bwd(const dcpt_conv3conv_params* p, const dcpt
     DCPT_TRY(check_c3(B, H, W, C, "conv3conv_res_bwd"));
     C3Ws cw;
     const size_t need = c3_layout(B, H, W, C, 1, ws, ws_bytes, &cw);
-    WS_OR_FAIL("conv3conv_res_bwd", need)
+    DCPT_CHECK_WS("conv3conv_res_bwd", ws, ws_bytes, need);
     const int Cq = C / 4;
     const int64_t M = (int64_t)B * H * W;
-    const Wgrad wg{cw.slab, cw.colsum};
     trace_tag("swinsr_conv3conv_bwd");
     // conv3: d2 = lrelu'(a2) conv3^T(dy);  dW3, db3 from dy and a2
-    DCPT_TRY(launch_wpack(p->conv3_w, cw.wp1, nullptr, C, 9 * Cq, WP_CONV3_T, s));
-    GemmNT g{};
-    g.M = M; g.A = dy; g.K = 9 * C; g.gH = H; g.gW = W; g.gC = C; g.Bw = cw.wp1; g.N = Cq; g.C = cw.d2; g.ldc = Cq; g.res = a2;
-    g.slope = SLOPE_3CONV;
-    DCPT_TRY(launch_gemm_nt(g, A_CONV3, E_LRELU, s));
-    DCPT_TRY(wgrad(dy, C, a2, 9 * Cq, A_CONV3, H, W, M, wg, gr->conv3_w, gr->conv3_b, s));
+    DCPT_TRY(launch_conv3_bwd(dy, a2, p->conv3_w, cw.wp1, B, H, W, Cq, C, E_LRELU, a2, SLOPE_3CONV, cw.d2, cw.slab, cw.colsum, gr->conv3_w,
+                              gr->conv3_b, s));
     // conv2 (1x1): d1 = lrelu'(a1) (d2 W2);  dW2 = d2^T a1, db2 = colsum(d2)
     DCPT_TRY(launch_wpack(p->conv2_w, cw.wT2, nullptr, Cq, Cq, WP_TRANSPOSE, s));
-    g = GemmNT{};
-    g.M = M; g.A = cw.d2; g.lda = Cq; g.K = Cq; g.Bw = cw.wT2; g.N = Cq; g.C = cw.d1; g.ldc = Cq; g.res = a1; g.slope = SLOPE_3CONV;
+    GemmNT g = gemm_nt_linear(cw.d2, Cq, M, Cq, cw.wT2, Cq, cw.d1, Cq);
+    g.res = a1; g.slope = SLOPE_3CONV;
     DCPT_TRY(launch_gemm_nt(g, A_PLAIN, E_LRELU, s));
-    DCPT_TRY(wgrad(cw.d2, Cq, a1, Cq, A_PLAIN, H, W, M, wg, gr->conv2_w, gr->conv2_b, s));
+    DCPT_TRY(launch_wgrad(GemmTN{}, A_PLAIN, cw.d2, Cq, Cq, a1, Cq, Cq, M, cw.slab, cw.colsum, gr->conv2_w, gr->conv2_b, WR_PLAIN, s));
     // conv1: dx = conv1^T(d1);  dW1, db1 from d1 and x   (the residual's gradient is dy itself)
-    DCPT_TRY(launch_wpack(p->conv1_w, cw.wp1, nullptr, Cq, 9 * C, WP_CONV3_T, s));
-    g = GemmNT{};
-    g.M = M; g.A = cw.d1; g.K = 9 * Cq; g.gH = H; g.gW = W; g.gC = Cq; g.Bw = cw.wp1; g.N = C; g.C = dx; g.ldc = C;
-    DCPT_TRY(launch_gemm_nt(g, A_CONV3, E_PLAIN, s));
-    return wgrad(cw.d1, Cq, x, 9 * C, A_CONV3, H, W, M, wg, gr->conv1_w, gr->conv1_b, s);
+    return launch_conv3_bwd(cw.d1, x, p->conv1_w, cw.wp1, B, H, W, C, Cq, E_PLAIN, nullptr, 0.f, dx, cw.slab, cw.colsum, gr->conv1_w,
+                            gr->conv1_b, s);
 }

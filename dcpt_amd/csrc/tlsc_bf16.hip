@@ -172,9 +172,6 @@ extern "C" int dcpt_box_mean_bf16(const uint16_t* in, uint16_t* out, void* ws, s
     if (k1 > H) k1 = H;   // arch_util.py:381 k = min(size, kernel)
     if (k2 > W) k2 = W;
     const size_t need = dcpt_box_mean_bf16_ws_bytes(B, H, W, C, k1, k2);
-    if (ws == nullptr || ws_bytes < need) {
-        dcpt_set_error("box_mean_bf16: workspace too small (%zu < %zu)", ws_bytes, need);
-        return DCPT_ERR_WS;
-    }
+    DCPT_CHECK_WS("box_mean_bf16", ws, ws_bytes, need);
     return launch_box_mean_bf16(in, (float*)ws, out, B, H, W, C, k1, k2, (hipStream_t)stream);
 }
