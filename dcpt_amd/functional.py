@@ -41,15 +41,44 @@ def release_workspaces():
     _ws_cache.clear()
 
 
-def _require_gpu(*ts):
+_NO_CPU = "dcpt_amd kernels run on a HIP device only (got a CPU tensor); there is no CPU fallback"
+
+
+def _require(ts, dtypes, what, none_ok=True):
+    """every tensor of ``ts`` on the device and of one of ``dtypes`` (``what``: the message for another dtype)"""
     for t in ts:
-        if t is None:
+        if t is None and none_ok:
             continue
         if not t.is_cuda:
-            raise _lib.DcptHipError(
-                "dcpt_amd kernels run on a HIP device only (got a CPU tensor); there is no CPU fallback")
-        if t.dtype != torch.float32:
-            raise _lib.DcptHipError(f"dcpt_amd kernels are fp32 (got {t.dtype})")
+            raise _lib.DcptHipError(_NO_CPU)
+        if t.dtype not in dtypes:
+            raise _lib.DcptHipError(what.format(t.dtype))
+
+
+def _require_gpu(*ts):
+    _require(ts, (torch.float32,), "dcpt_amd kernels are fp32 (got {})")
+
+
+def _require_gpu_feat(*ts):
+    """feature maps of the ops that exist in both storage types: fp32 or bf16, on the device"""
+    _require(ts, (torch.float32, torch.bfloat16), "feature maps are fp32 or bf16 (got {})")
+
+
+def _require_gpu_bf16(*ts):
+    _require(ts, (torch.bfloat16,), "the bf16-storage path takes torch.bfloat16 activations (got {})", none_ok=False)
+
+
+# An incoming gradient of an op in bf16 storage that is not bf16 itself: the two policies (DESIGN.md section 4 lists which op has which)
+def _grad_strict(dy, bf):
+    """strict: a gradient in another dtype than the bf16 storage is an error"""
+    if bf:
+        _require_gpu_bf16(dy)
+    return dy
+
+
+def _grad_cast(dy, dtype):
+    """cast: the gradient is brought to the op's storage dtype"""
+    return dy if dy.dtype == dtype else dy.to(dtype)
 
 
 def _nhwc(x: torch.Tensor) -> torch.Tensor:
@@ -73,8 +102,42 @@ def _empty_nhwc(n, c, h, w, dev) -> torch.Tensor:
     return torch.empty_strided((n, c, h, w), (h * w * c, 1, w * c, c), dtype=torch.float32, device=dev)
 
 
+def _empty_nhwc_bf16(n, c, h, w, dev) -> torch.Tensor:
+    """bf16-storage path (BASELINE.json configs[2]): activations / saved tensors torch.bfloat16 (channels_last), parameters fp32"""
+    return torch.empty_strided((n, c, h, w), (h * w * c, 1, w * c, c), dtype=torch.bfloat16, device=dev)
+
+
+def _empty(bf):
+    """the feature-map allocator of a storage type.  _workspace, _empty_nhwc and _empty_nhwc_bf16 are the three names tests/redzone.py
+    swaps on this module: they are looked up when called, and the op's own frame calls what this returns."""
+    return _empty_nhwc_bf16 if bf else _empty_nhwc
+
+
 def _p(t):
     return 0 if t is None else t.data_ptr()
+
+
+def _struct(cls, ts):
+    """a *Params / grads struct of the ABI over tensors (None: a NULL field)"""
+    return cls(*[_p(t) for t in ts])
+
+
+def _call(fn, ptrs, dims, dev, ws_bytes=None):
+    """The one argument convention of the C ABI (include/dcpt_hip.h): pointers, [workspace, workspace bytes,] integer / float geometry,
+    stream.  Of ``ptrs`` a tensor becomes its address, None a null pointer and a ctypes struct a reference; integers and ctypes arrays
+    pass through.  ``ws_bytes``: the workspace is requested here, through the module's ``_workspace``."""
+    args = []
+    for a in ptrs:
+        if isinstance(a, torch.Tensor):
+            args.append(a.data_ptr())
+        elif isinstance(a, C.Structure):
+            args.append(C.byref(a))
+        else:
+            args.append(a)
+    if ws_bytes is not None:
+        ws = _workspace(dev, ws_bytes)
+        args += (ws.data_ptr(), ws.numel())
+    check(fn(*args, *dims, _stream(dev)), fn.__name__)
 
 
 def _contig(t):
@@ -243,12 +306,9 @@ class _NAFBlockFn(torch.autograd.Function):
         stats = None if infer else torch.empty((4, M), dtype=torch.float32, device=dev)
         pooled = torch.empty((B, Cc), dtype=torch.float32, device=dev)
         s = torch.empty((B, Cc), dtype=torch.float32, device=dev)
-        ps = NafBlockParams(*[p.data_ptr() for p in params])
         sv = _saved_f32(t1, t2, y, v, stats, pooled, s, xn)
-        nws = lib.dcpt_nafblock_fwd_ws_bytes(B, H, W, Cc)
-        ws = _workspace(dev, nws)
-        check(lib.dcpt_nafblock_fwd(C.byref(ps), inp.data_ptr(), out.data_ptr(), C.byref(sv), ws.data_ptr(), ws.numel(),
-                                    B, H, W, Cc, _stream(dev)), "dcpt_nafblock_fwd")
+        _call(lib.dcpt_nafblock_fwd, (_struct(NafBlockParams, params), inp, out, sv), (B, H, W, Cc), dev,
+              lib.dcpt_nafblock_fwd_ws_bytes(B, H, W, Cc))
         if not infer:
             ctx.has_xn = xn is not None
             ctx.save_for_backward(inp, t1, t2, y, v, stats, pooled, s, *(() if xn is None else (xn,)), *params)
@@ -266,14 +326,9 @@ class _NAFBlockFn(torch.autograd.Function):
         dev = inp.device
         grads = _grad_buffers(params, ctx.owners)
         dinp = _empty_nhwc(B, Cc, H, W, dev)
-        ps = NafBlockParams(*[p.data_ptr() for p in params])
-        gs = NafBlockGrads(*[g.data_ptr() for g in grads])
         sv = _saved_f32(t1, t2, y, v, stats, pooled, s, xn)
-        nws = lib.dcpt_nafblock_bwd_ws_bytes(B, H, W, Cc)
-        ws = _workspace(dev, nws)
-        check(lib.dcpt_nafblock_bwd(C.byref(ps), C.byref(gs), inp.data_ptr(), C.byref(sv), dout.data_ptr(),
-                                    dinp.data_ptr(), ws.data_ptr(), ws.numel(), B, H, W, Cc, _stream(dev)),
-              "dcpt_nafblock_bwd")
+        _call(lib.dcpt_nafblock_bwd, (_struct(NafBlockParams, params), _struct(NafBlockGrads, grads), inp, sv, dout, dinp), (B, H, W, Cc), dev,
+              lib.dcpt_nafblock_bwd_ws_bytes(B, H, W, Cc))
         return (dinp, None, *grads)
 
 
@@ -284,29 +339,6 @@ def nafblock(inp: torch.Tensor, params: Dict[str, torch.Tensor]) -> torch.Tensor
 
 # ------------------------------------------------------------------------------------------------
 # bf16-storage path (BASELINE.json configs[2]): activations / saved tensors torch.bfloat16 (channels_last), parameters fp32
-def _empty_nhwc_bf16(n, c, h, w, dev) -> torch.Tensor:
-    return torch.empty_strided((n, c, h, w), (h * w * c, 1, w * c, c), dtype=torch.bfloat16, device=dev)
-
-
-def _require_gpu_feat(*ts):
-    """feature maps of the ops that exist in both storage types: fp32 or bf16, on the device"""
-    for t in ts:
-        if t is None:
-            continue
-        if not t.is_cuda:
-            raise _lib.DcptHipError("dcpt_amd kernels run on a HIP device only (got a CPU tensor); there is no CPU fallback")
-        if t.dtype not in (torch.float32, torch.bfloat16):
-            raise _lib.DcptHipError(f"feature maps are fp32 or bf16 (got {t.dtype})")
-
-
-def _require_gpu_bf16(*ts):
-    for t in ts:
-        if not t.is_cuda:
-            raise _lib.DcptHipError("dcpt_amd kernels run on a HIP device only (got a CPU tensor); there is no CPU fallback")
-        if t.dtype != torch.bfloat16:
-            raise _lib.DcptHipError(f"the bf16-storage path takes torch.bfloat16 activations (got {t.dtype})")
-
-
 def _saved_bf16(t1, v, acts, stats, sca, infer):
     """dcpt_nafblock_saved_bf16 over the forward's buffers.  acts / stats have 5 / 4 rows, or 3 / 2 where the fused second half keeps
     nothing but v (dcpt_nafblock_bf16_fused_ffn): the missing pointers are NULL when no backward follows (``infer``: the library then
@@ -353,11 +385,9 @@ class _NAFBlockBf16Fn(torch.autograd.Function):
         acts = torch.empty((3 if slim else 5, B, H, W, Cc), dtype=torch.bfloat16, device=dev)   # t2, y, LN1(inp) [, LN2(y), SimpleGate(v)]
         stats = torch.empty((2 if slim else 4, M), dtype=torch.float32, device=dev)
         sca = torch.empty((2, B, Cc), dtype=torch.float32, device=dev)           # pooled, s
-        ps = NafBlockParams(*[p.data_ptr() for p in params])
         sv = _saved_bf16(t1, v, acts, stats, sca, infer)
-        ws = _workspace(dev, lib.dcpt_nafblock_fwd_bf16_ws_bytes(B, H, W, Cc))
-        check(lib.dcpt_nafblock_fwd_bf16(C.byref(ps), _p(packed), 0 if packed is None else packed.numel(), inp.data_ptr(), out.data_ptr(),
-                                         C.byref(sv), ws.data_ptr(), ws.numel(), B, H, W, Cc, _stream(dev)), "dcpt_nafblock_fwd_bf16")
+        _call(lib.dcpt_nafblock_fwd_bf16, (_struct(NafBlockParams, params), *_pkargs(packed), inp, out, sv), (B, H, W, Cc), dev,
+              lib.dcpt_nafblock_fwd_bf16_ws_bytes(B, H, W, Cc))
         ctx.packed = packed   # (a plain byte buffer owned by the module; the backward of THIS forward reads the same pack)
         if not nograd:
             ctx.save_for_backward(inp, t1, v, acts, stats, sca, *params)
@@ -367,19 +397,14 @@ class _NAFBlockBf16Fn(torch.autograd.Function):
     def backward(ctx, dout):
         lib = _lib.load()
         inp, t1, v, acts, stats, sca, *params = ctx.saved_tensors
-        dout = _nhwc(dout if dout.dtype == torch.bfloat16 else dout.to(torch.bfloat16))
+        dout = _nhwc(_grad_cast(dout, torch.bfloat16))
         B, Cc, H, W = inp.shape
         dev = inp.device
         grads = _grad_buffers(params, ctx.owners)
         dinp = _empty_nhwc_bf16(B, Cc, H, W, dev)
-        ps = NafBlockParams(*[p.data_ptr() for p in params])
-        gs = NafBlockGrads(*[g.data_ptr() for g in grads])
         sv = _saved_bf16(t1, v, acts, stats, sca, False)
-        ws = _workspace(dev, lib.dcpt_nafblock_bwd_bf16_ws_bytes(B, H, W, Cc))
-        packed = ctx.packed
-        check(lib.dcpt_nafblock_bwd_bf16(C.byref(ps), _p(packed), 0 if packed is None else packed.numel(), C.byref(gs), inp.data_ptr(),
-                                         C.byref(sv), dout.data_ptr(), dinp.data_ptr(), ws.data_ptr(), ws.numel(), B, H, W, Cc, _stream(dev)),
-              "dcpt_nafblock_bwd_bf16")
+        _call(lib.dcpt_nafblock_bwd_bf16, (_struct(NafBlockParams, params), *_pkargs(ctx.packed), _struct(NafBlockGrads, grads), inp, sv, dout,
+                                           dinp), (B, H, W, Cc), dev, lib.dcpt_nafblock_bwd_bf16_ws_bytes(B, H, W, Cc))
         return (dinp, None, None, *grads)
 
 
@@ -481,8 +506,7 @@ class PackedWeightsBf16:
             nbytes = lib.dcpt_nafblock_wpack_bf16_bytes(Cc)
             if self.buf is None or self.buf.numel() != nbytes or self.buf.device != dev:
                 self.buf = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            pp = NafBlockParams(*[p.data_ptr() for p in ps])
-            check(lib.dcpt_nafblock_wpack_bf16(C.byref(pp), self.buf.data_ptr(), self.buf.numel(), Cc, _stream(dev)), "dcpt_nafblock_wpack_bf16")
+            _call(lib.dcpt_nafblock_wpack_bf16, (_struct(NafBlockParams, ps), self.buf, self.buf.numel()), (Cc,), dev)
             self.key = key
             self.tag(params)
             self.stream = _stream(dev)
@@ -516,9 +540,9 @@ def pack_blocks_bf16(blocks) -> int:
         need = lib.dcpt_nafblock_wpack_bf16_bytes(Cc)
         if pk.buf is None or pk.buf.numel() != need or pk.buf.device != dev:
             pk.buf = torch.empty(need, dtype=torch.uint8, device=dev)
-        ps_arr[i] = NafBlockParams(*[p.data_ptr() for p in ps])
+        ps_arr[i] = _struct(NafBlockParams, ps)
         bufs[i], nbytes[i], widths[i] = pk.buf.data_ptr(), need, Cc
-    check(lib.dcpt_nafblock_wpack_bf16_multi(ps_arr, bufs, nbytes, widths, n, _stream(dev)), "dcpt_nafblock_wpack_bf16_multi")
+    _call(lib.dcpt_nafblock_wpack_bf16_multi, (ps_arr, bufs, nbytes, widths), (n,), dev)
     ev = torch.cuda.Event()
     ev.record(torch.cuda.current_stream(dev))
     for pk, params, key in stale:
@@ -582,7 +606,7 @@ def pack_convs_bf16(convs) -> int:
         if pk.buf is None or pk.buf.numel() != need or pk.buf.device != dev:
             pk.buf = torch.empty(need, dtype=torch.uint8, device=dev)
         ws[i], bufs[i], nbytes[i], cin[i], cout[i], ksz[i] = w_.data_ptr(), pk.buf.data_ptr(), need, Ci, Co, ks
-    check(lib.dcpt_conv_wpack_bf16_multi(ws, bufs, nbytes, cin, cout, ksz, n, _stream(dev)), "dcpt_conv_wpack_bf16_multi")
+    _call(lib.dcpt_conv_wpack_bf16_multi, (ws, bufs, nbytes, cin, cout, ksz), (n,), dev)
     ev = torch.cuda.Event()
     ev.record(torch.cuda.current_stream(dev))
     for pk, w, key in stale:
@@ -636,9 +660,7 @@ def conv1x1_wgrad_bf16(dy: torch.Tensor, x: torch.Tensor, with_bias: bool = True
     nws = lib.dcpt_conv1x1_wgrad_bf16_ws_bytes(M, N, K)
     if nws == 0:
         raise _lib.DcptHipError(f"conv1x1_wgrad_bf16: N={N}, K={K} must be positive multiples of 8")
-    ws = _workspace(dev, nws)
-    check(lib.dcpt_conv1x1_wgrad_bf16(dy2.data_ptr(), x2.data_ptr(), dW.data_ptr(), _p(db), ws.data_ptr(), ws.numel(), M, N, K, _stream(dev)),
-          "dcpt_conv1x1_wgrad_bf16")
+    _call(lib.dcpt_conv1x1_wgrad_bf16, (dy2, x2, dW, db), (M, N, K), dev, nws)
     return (dW, db) if with_bias else dW
 
 
@@ -667,7 +689,7 @@ def _cast(lib, x, to_bf16):
         raise _lib.DcptHipError("cast: element count must be a multiple of 8")
     y = torch.empty_like(x, dtype=dst)   # preserves the (dense NHWC) strides
     fn = lib.dcpt_cast_f32_bf16 if to_bf16 else lib.dcpt_cast_bf16_f32
-    check(fn(x.data_ptr(), y.data_ptr(), x.numel(), _stream(x.device)), fn.__name__)
+    _call(fn, (x, y), (x.numel(),), x.device)
     return y
 
 
@@ -689,10 +711,8 @@ def nafblock_local(inp: torch.Tensor, params: Dict[str, torch.Tensor], k1: int, 
     inp = _nhwc(inp)
     B, Cc, H, W = inp.shape
     out = _empty_nhwc(B, Cc, H, W, inp.device)
-    pp = NafBlockParams(*[p.data_ptr() for p in ps])
-    ws = _workspace(inp.device, lib.dcpt_nafblock_local_ws_bytes(B, H, W, Cc, k1, k2))
-    check(lib.dcpt_nafblock_local_fwd(C.byref(pp), inp.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(), B, H, W, Cc,
-                                      int(k1), int(k2), _stream(inp.device)), "dcpt_nafblock_local_fwd")
+    _call(lib.dcpt_nafblock_local_fwd, (_struct(NafBlockParams, ps), inp, out), (B, H, W, Cc, int(k1), int(k2)), inp.device,
+          lib.dcpt_nafblock_local_ws_bytes(B, H, W, Cc, k1, k2))
     return out
 
 
@@ -712,11 +732,8 @@ def nafblock_local_bf16(inp: torch.Tensor, params: Dict[str, torch.Tensor], k1: 
         raise _lib.DcptHipError(f"the bf16-storage path needs channel counts that are multiples of 8 (got {Cc})")
     buf = packed.get(params) if packed is not None else None
     out = _empty_nhwc_bf16(B, Cc, H, W, inp.device)
-    pp = NafBlockParams(*[p.data_ptr() for p in ps])
-    ws = _workspace(inp.device, lib.dcpt_nafblock_local_fwd_bf16_ws_bytes(B, H, W, Cc, int(k1), int(k2)))
-    check(lib.dcpt_nafblock_local_fwd_bf16(C.byref(pp), None if buf is None else buf.data_ptr(), 0 if buf is None else buf.numel(), inp.data_ptr(),
-                                           out.data_ptr(), ws.data_ptr(), ws.numel(), B, H, W, Cc, int(k1), int(k2), _stream(inp.device)),
-          "dcpt_nafblock_local_fwd_bf16")
+    _call(lib.dcpt_nafblock_local_fwd_bf16, (_struct(NafBlockParams, ps), *_pkargs(buf), inp, out), (B, H, W, Cc, int(k1), int(k2)), inp.device,
+          lib.dcpt_nafblock_local_fwd_bf16_ws_bytes(B, H, W, Cc, int(k1), int(k2)))
     return out
 
 
@@ -730,9 +747,7 @@ def box_mean_bf16(x: torch.Tensor, k1: int, k2: int) -> torch.Tensor:
     if Cc % 8:
         raise _lib.DcptHipError(f"box_mean_bf16 needs a channel count that is a multiple of 8 (got {Cc})")
     out = _empty_nhwc_bf16(B, Cc, H, W, x.device)
-    ws = _workspace(x.device, lib.dcpt_box_mean_bf16_ws_bytes(B, H, W, Cc, int(k1), int(k2)))
-    check(lib.dcpt_box_mean_bf16(x.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(), B, H, W, Cc, int(k1), int(k2), _stream(x.device)),
-          "dcpt_box_mean_bf16")
+    _call(lib.dcpt_box_mean_bf16, (x, out), (B, H, W, Cc, int(k1), int(k2)), x.device, lib.dcpt_box_mean_bf16_ws_bytes(B, H, W, Cc, int(k1), int(k2)))
     return out
 
 
@@ -841,11 +856,11 @@ class _TapSplitStrideFn(torch.autograd.Function):
         gs = _nhwc(gs)
         if g is None:
             g = _empty_nhwc(B, Cc, H, W, gs.device)
-            check(lib.dcpt_grid_scatter(gs.data_ptr(), g.data_ptr(), B, lo, hi, H, W, Cc, s, _stream(gs.device)), "dcpt_grid_scatter")
+            _call(lib.dcpt_grid_scatter, (gs, g), (B, lo, hi, H, W, Cc, s), gs.device)
             return g, None, None, None
         if not _is_nhwc(g) or not _private_grad(g):
             g = _force_nhwc(g)
-        check(lib.dcpt_grid_add(g.data_ptr(), gs.data_ptr(), B, lo, hi, H, W, Cc, s, _stream(gs.device)), "dcpt_grid_add")
+        _call(lib.dcpt_grid_add, (g, gs), (B, lo, hi, H, W, Cc, s), gs.device)
         return g, None, None, None
 
 
@@ -876,8 +891,7 @@ class _LayerNorm2dFn(torch.autograd.Function):
         y = _empty_nhwc(B, Cc, H, W, x.device)
         stats = torch.empty((2, M), dtype=torch.float32, device=x.device)
         w_, b_ = _contig(weight.detach()), _contig(bias.detach())
-        check(lib.dcpt_ln2d_fwd(x.data_ptr(), w_.data_ptr(), b_.data_ptr(), y.data_ptr(), stats[0].data_ptr(),
-                                stats[1].data_ptr(), M, Cc, float(eps), _stream(x.device)), "dcpt_ln2d_fwd")
+        _call(lib.dcpt_ln2d_fwd, (x, w_, b_, y, stats[0], stats[1]), (M, Cc, float(eps)), x.device)
         ctx.save_for_backward(x, stats, w_)
         return y
 
@@ -891,11 +905,7 @@ class _LayerNorm2dFn(torch.autograd.Function):
         dx = _empty_nhwc(B, Cc, H, W, x.device)
         dw = torch.empty_like(w_)
         db = torch.empty_like(w_)
-        nws = lib.dcpt_ln2d_bwd_ws_bytes(M, Cc)
-        ws = _workspace(x.device, nws)
-        check(lib.dcpt_ln2d_bwd(dy.data_ptr(), x.data_ptr(), stats[0].data_ptr(), stats[1].data_ptr(), w_.data_ptr(),
-                                dx.data_ptr(), dw.data_ptr(), db.data_ptr(), ws.data_ptr(), ws.numel(), M, Cc,
-                                _stream(x.device)), "dcpt_ln2d_bwd")
+        _call(lib.dcpt_ln2d_bwd, (dy, x, stats[0], stats[1], w_, dx, dw, db), (M, Cc), x.device, lib.dcpt_ln2d_bwd_ws_bytes(M, Cc))
         return dx, dw, db, None
 
 
@@ -917,9 +927,8 @@ class _IntroFn(torch.autograd.Function):
         B, Cin, H, W = x.shape
         Cout = w_.shape[0]
         bf = bool(out_bf16)
-        y = (_empty_nhwc_bf16 if bf else _empty_nhwc)(B, Cout, H, W, x.device)
-        fn = lib.dcpt_conv3x3_in_fwd_bf16 if bf else lib.dcpt_conv3x3_in_fwd
-        check(fn(x.data_ptr(), w_.data_ptr(), _p(b_), y.data_ptr(), B, H, W, Cin, Cout, _stream(x.device)), fn.__name__)
+        y = _empty(bf)(B, Cout, H, W, x.device)
+        _call(lib.dcpt_conv3x3_in_fwd_bf16 if bf else lib.dcpt_conv3x3_in_fwd, (x, w_, b_, y), (B, H, W, Cin, Cout), x.device)
         ctx.save_for_backward(x, w_)
         ctx.has_bias, ctx.bf = bias is not None, bf
         return y
@@ -928,20 +937,15 @@ class _IntroFn(torch.autograd.Function):
     def backward(ctx, dy):
         lib = _lib.load()
         x, w_ = ctx.saved_tensors
-        if ctx.bf:
-            _require_gpu_bf16(dy)
-        dy = _nhwc(dy)
+        dy = _nhwc(_grad_strict(dy, ctx.bf))
         B, Cin, H, W = x.shape
         Cout = w_.shape[0]
         dev = x.device
         dw = torch.empty_like(w_)
         db = torch.empty((Cout,), dtype=torch.float32, device=dev)
         dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
-        nws = lib.dcpt_conv3x3_in_bwd_ws_bytes(B, H, W, Cin, Cout)
-        ws = _workspace(dev, nws)
-        fn = lib.dcpt_conv3x3_in_bwd_bf16 if ctx.bf else lib.dcpt_conv3x3_in_bwd
-        check(fn(dy.data_ptr(), x.data_ptr(), w_.data_ptr(), _p(dx), dw.data_ptr(), db.data_ptr(), ws.data_ptr(), ws.numel(), B, H, W,
-                 Cin, Cout, _stream(dev)), fn.__name__)
+        _call(lib.dcpt_conv3x3_in_bwd_bf16 if ctx.bf else lib.dcpt_conv3x3_in_bwd, (dy, x, w_, dx, dw, db), (B, H, W, Cin, Cout), dev,
+              lib.dcpt_conv3x3_in_bwd_ws_bytes(B, H, W, Cin, Cout))
         return dx, dw, (db if ctx.has_bias else None), None
 
 
@@ -960,8 +964,8 @@ class _EndingFn(torch.autograd.Function):
         B, Cin, H, W = x.shape
         Cout = w_.shape[0]
         y = torch.empty((B, Cout, H, W), dtype=torch.float32, device=x.device)
-        fn = lib.dcpt_conv3x3_out_fwd_bf16 if x.dtype == torch.bfloat16 else lib.dcpt_conv3x3_out_fwd
-        check(fn(x.data_ptr(), w_.data_ptr(), _p(b_), _p(res_), y.data_ptr(), B, H, W, Cin, Cout, _stream(x.device)), fn.__name__)
+        _call(lib.dcpt_conv3x3_out_fwd_bf16 if x.dtype == torch.bfloat16 else lib.dcpt_conv3x3_out_fwd, (x, w_, b_, res_, y),
+              (B, H, W, Cin, Cout), x.device)
         ctx.save_for_backward(x, w_)
         ctx.has_bias = bias is not None
         ctx.has_res = res is not None
@@ -976,14 +980,11 @@ class _EndingFn(torch.autograd.Function):
         B, Cin, H, W = x.shape
         Cout = w_.shape[0]
         dev = x.device
-        dx = (_empty_nhwc_bf16 if bf else _empty_nhwc)(B, Cin, H, W, dev)
+        dx = _empty(bf)(B, Cin, H, W, dev)
         dw = torch.empty_like(w_)
         db = torch.empty((Cout,), dtype=torch.float32, device=dev)
-        nws = lib.dcpt_conv3x3_out_bwd_ws_bytes(B, H, W, Cin, Cout)
-        ws = _workspace(dev, nws)
-        fn = lib.dcpt_conv3x3_out_bwd_bf16 if bf else lib.dcpt_conv3x3_out_bwd
-        check(fn(dy.data_ptr(), x.data_ptr(), w_.data_ptr(), dx.data_ptr(), dw.data_ptr(), db.data_ptr(), ws.data_ptr(), ws.numel(),
-                 B, H, W, Cin, Cout, _stream(dev)), fn.__name__)
+        _call(lib.dcpt_conv3x3_out_bwd_bf16 if bf else lib.dcpt_conv3x3_out_bwd, (dy, x, w_, dx, dw, db), (B, H, W, Cin, Cout), dev,
+              lib.dcpt_conv3x3_out_bwd_ws_bytes(B, H, W, Cin, Cout))
         return dx, dw, (db if ctx.has_bias else None), (dy if ctx.has_res and ctx.needs_input_grad[3] else None)
 
 
@@ -997,50 +998,59 @@ def conv3x3_out(x, weight, bias, res=None):
 
 
 # ------------------------------------------------------------------------------------------------
+def _down2x2_ws(lib, bf):
+    return lib.dcpt_down2x2_bf16_ws_bytes if bf else lib.dcpt_down2x2_ws_bytes
+
+
+def _down_fwd(lib, ctx, x, weight, bias):
+    """Conv2d(C, 2C, 2, 2) for _DownFn / _DownSkipFn (each has checked x its own way): keeps (x, w_) on ctx, returns y and the NHWC x"""
+    _require_gpu(weight, bias)
+    x = _nhwc(x)
+    bf = x.dtype == torch.bfloat16
+    w_, b_ = _contig(weight.detach()), (None if bias is None else _contig(bias.detach()))
+    B, Cc, H, W = x.shape
+    if H % 2 or W % 2:
+        raise ValueError(f"down2x2: H={H}, W={W} must be even")
+    y = _empty(bf)(B, 2 * Cc, H // 2, W // 2, x.device)
+    _call(lib.dcpt_down2x2_fwd_bf16 if bf else lib.dcpt_down2x2_fwd, (x, w_, b_, y), (B, H, W, Cc), x.device,
+          _down2x2_ws(lib, bf)(B, H, W, Cc, 0))
+    ctx.save_for_backward(x, w_)
+    ctx.has_bias = bias is not None
+    return y, x
+
+
+def _down_bwd(lib, ctx, dy, dx_add):
+    """backward of _down_fwd: dx = dx_add + conv^T(dy) (dx_add may be None); dy and dx_add dense NHWC in x's storage"""
+    x, w_ = ctx.saved_tensors
+    bf = x.dtype == torch.bfloat16
+    B, Cc, H, W = x.shape
+    dev = x.device
+    dx = _empty(bf)(B, Cc, H, W, dev)
+    dw = torch.empty_like(w_)
+    db = torch.empty((2 * Cc,), dtype=torch.float32, device=dev)
+    _call(lib.dcpt_down2x2_bwd_bf16 if bf else lib.dcpt_down2x2_bwd, (dy, x, w_, dx_add, dx, dw, db), (B, H, W, Cc), dev,
+          _down2x2_ws(lib, bf)(B, H, W, Cc, 1))
+    return dx, dw, (db if ctx.has_bias else None)
+
+
+# (known, and behaviour: _DownFn notes the gemm mode for fp32 storage only, _DownSkipFn for both storages)
 @_remember_gemm_mode_fp32
 class _DownFn(torch.autograd.Function):
     """Conv2d(C, 2C, 2, 2) (reference nafnet_arch.py:230); fp32 or bf16 storage (edge_bf16.hip) by x.dtype, parameters fp32."""
 
     @staticmethod
     def forward(ctx, x, weight, bias):
-        lib = _lib.load()
         _require_gpu_feat(x)
-        _require_gpu(weight, bias)
-        x = _nhwc(x)
-        bf = x.dtype == torch.bfloat16
-        w_, b_ = _contig(weight.detach()), (None if bias is None else _contig(bias.detach()))
-        B, Cc, H, W = x.shape
-        if H % 2 or W % 2:
-            raise ValueError(f"down2x2: H={H}, W={W} must be even")
-        y = (_empty_nhwc_bf16 if bf else _empty_nhwc)(B, 2 * Cc, H // 2, W // 2, x.device)
-        nws = (lib.dcpt_down2x2_bf16_ws_bytes if bf else lib.dcpt_down2x2_ws_bytes)(B, H, W, Cc, 0)
-        ws = _workspace(x.device, nws)
-        fn = lib.dcpt_down2x2_fwd_bf16 if bf else lib.dcpt_down2x2_fwd
-        check(fn(x.data_ptr(), w_.data_ptr(), _p(b_), y.data_ptr(), ws.data_ptr(), ws.numel(), B, H, W, Cc, _stream(x.device)),
-              fn.__name__)
-        ctx.save_for_backward(x, w_)
-        ctx.has_bias = bias is not None
-        return y
+        return _down_fwd(_lib.load(), ctx, x, weight, bias)[0]
 
     @staticmethod
     def backward(ctx, dy):
-        lib = _lib.load()
-        x, w_ = ctx.saved_tensors
-        bf = x.dtype == torch.bfloat16
-        if bf:
-            _require_gpu_bf16(dy)
-        dy = _nhwc(dy)
-        B, Cc, H, W = x.shape
-        dev = x.device
-        dx = (_empty_nhwc_bf16 if bf else _empty_nhwc)(B, Cc, H, W, dev)
-        dw = torch.empty_like(w_)
-        db = torch.empty((2 * Cc,), dtype=torch.float32, device=dev)
-        nws = (lib.dcpt_down2x2_bf16_ws_bytes if bf else lib.dcpt_down2x2_ws_bytes)(B, H, W, Cc, 1)
-        ws = _workspace(dev, nws)
-        fn = lib.dcpt_down2x2_bwd_bf16 if bf else lib.dcpt_down2x2_bwd
-        check(fn(dy.data_ptr(), x.data_ptr(), w_.data_ptr(), None, dx.data_ptr(), dw.data_ptr(), db.data_ptr(), ws.data_ptr(), ws.numel(),
-                 B, H, W, Cc, _stream(dev)), fn.__name__)
-        return dx, dw, (db if ctx.has_bias else None)
+        dy = _nhwc(_grad_strict(dy, ctx.saved_tensors[0].dtype == torch.bfloat16))
+        return _down_bwd(_lib.load(), ctx, dy, None)
+
+
+def _up_ps_ws(lib, bf):
+    return lib.dcpt_up_ps_bf16_ws_bytes if bf else lib.dcpt_up_ps_ws_bytes
 
 
 @_remember_gemm_mode_fp32
@@ -1060,12 +1070,8 @@ class _UpFn(torch.autograd.Function):
         w_ = _contig(weight.detach())
         skip_ = None if skip is None else _nhwc(skip)
         B, Cc, H, W = x.shape
-        y = (_empty_nhwc_bf16 if bf else _empty_nhwc)(B, Cc // 2, 2 * H, 2 * W, x.device)
-        nws = (lib.dcpt_up_ps_bf16_ws_bytes if bf else lib.dcpt_up_ps_ws_bytes)(B, H, W, Cc, 0)
-        ws = _workspace(x.device, nws)
-        fn = lib.dcpt_up_ps_fwd_bf16 if bf else lib.dcpt_up_ps_fwd
-        check(fn(x.data_ptr(), w_.data_ptr(), _p(skip_), y.data_ptr(), ws.data_ptr(), ws.numel(), B, H, W, Cc, _stream(x.device)),
-              fn.__name__)
+        y = _empty(bf)(B, Cc // 2, 2 * H, 2 * W, x.device)
+        _call(lib.dcpt_up_ps_fwd_bf16 if bf else lib.dcpt_up_ps_fwd, (x, w_, skip_, y), (B, H, W, Cc), x.device, _up_ps_ws(lib, bf)(B, H, W, Cc, 0))
         ctx.save_for_backward(x, w_)
         ctx.has_skip = skip is not None
         return y
@@ -1075,18 +1081,12 @@ class _UpFn(torch.autograd.Function):
         lib = _lib.load()
         x, w_ = ctx.saved_tensors
         bf = x.dtype == torch.bfloat16
-        if bf:
-            _require_gpu_bf16(dy)
-        dy = _nhwc(dy)
+        dy = _nhwc(_grad_strict(dy, bf))
         B, Cc, H, W = x.shape
         dev = x.device
-        dx = (_empty_nhwc_bf16 if bf else _empty_nhwc)(B, Cc, H, W, dev)
+        dx = _empty(bf)(B, Cc, H, W, dev)
         dw = torch.empty_like(w_)
-        nws = (lib.dcpt_up_ps_bf16_ws_bytes if bf else lib.dcpt_up_ps_ws_bytes)(B, H, W, Cc, 1)
-        ws = _workspace(dev, nws)
-        fn = lib.dcpt_up_ps_bwd_bf16 if bf else lib.dcpt_up_ps_bwd
-        check(fn(dy.data_ptr(), x.data_ptr(), w_.data_ptr(), dx.data_ptr(), dw.data_ptr(), ws.data_ptr(), ws.numel(), B, H, W, Cc,
-                 _stream(dev)), fn.__name__)
+        _call(lib.dcpt_up_ps_bwd_bf16 if bf else lib.dcpt_up_ps_bwd, (dy, x, w_, dx, dw), (B, H, W, Cc), dev, _up_ps_ws(lib, bf)(B, H, W, Cc, 1))
         return dx, dw, (dy if ctx.has_skip else None)
 
 
@@ -1104,44 +1104,17 @@ class _DownSkipFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias):
-        lib = _lib.load()
-        bf = x.dtype == torch.bfloat16
-        (_require_gpu_bf16 if bf else _require_gpu)(x)
-        _require_gpu(weight, bias)
-        x = _nhwc(x)
-        w_, b_ = _contig(weight.detach()), (None if bias is None else _contig(bias.detach()))
-        B, Cc, H, W = x.shape
-        if H % 2 or W % 2:
-            raise ValueError(f"down2x2: H={H}, W={W} must be even")
-        y = (_empty_nhwc_bf16 if bf else _empty_nhwc)(B, 2 * Cc, H // 2, W // 2, x.device)
-        ws = _workspace(x.device, (lib.dcpt_down2x2_bf16_ws_bytes if bf else lib.dcpt_down2x2_ws_bytes)(B, H, W, Cc, 0))
-        fn = lib.dcpt_down2x2_fwd_bf16 if bf else lib.dcpt_down2x2_fwd
-        check(fn(x.data_ptr(), w_.data_ptr(), _p(b_), y.data_ptr(), ws.data_ptr(), ws.numel(), B, H, W, Cc, _stream(x.device)),
-              fn.__name__)
-        ctx.save_for_backward(x, w_)
-        ctx.has_bias, ctx.bf = bias is not None, bf
+        (_require_gpu_bf16 if x.dtype == torch.bfloat16 else _require_gpu)(x)
+        y, x = _down_fwd(_lib.load(), ctx, x, weight, bias)
         return y, x.view(x.shape)
 
     @staticmethod
     def backward(ctx, dy, dskip):
-        lib = _lib.load()
-        x, w_ = ctx.saved_tensors
-        bf = ctx.bf
-        B, Cc, H, W = x.shape
-        dev = x.device
         if dy is None:   # (only the skip was used downstream)
             return dskip, None, None
-        dy = _nhwc(dy)
         if dskip is not None:
-            dskip = _nhwc(dskip if dskip.dtype == x.dtype else dskip.to(x.dtype))
-        dx = (_empty_nhwc_bf16 if bf else _empty_nhwc)(B, Cc, H, W, dev)
-        dw = torch.empty_like(w_)
-        db = torch.empty((2 * Cc,), dtype=torch.float32, device=dev)
-        ws = _workspace(dev, (lib.dcpt_down2x2_bf16_ws_bytes if bf else lib.dcpt_down2x2_ws_bytes)(B, H, W, Cc, 1))
-        fn = lib.dcpt_down2x2_bwd_bf16 if bf else lib.dcpt_down2x2_bwd
-        check(fn(dy.data_ptr(), x.data_ptr(), w_.data_ptr(), _p(dskip), dx.data_ptr(), dw.data_ptr(), db.data_ptr(), ws.data_ptr(), ws.numel(),
-                 B, H, W, Cc, _stream(dev)), fn.__name__)
-        return dx, dw, (db if ctx.has_bias else None)
+            dskip = _nhwc(_grad_cast(dskip, ctx.saved_tensors[0].dtype))
+        return _down_bwd(_lib.load(), ctx, _nhwc(dy), dskip)
 
 
 def down2x2_skip(x, weight, bias):
@@ -1169,8 +1142,8 @@ def fused_bias_act(x, bias, ref, act: int, grad: int, alpha: float, scale: float
         step_b *= int(d)
     b_ = _contig(bias) if use_bias else None
     r_ = _contig(ref) if use_ref else None
-    check(lib.dcpt_fused_bias_act(x.data_ptr(), _p(b_), _p(r_), y.data_ptr(), x.numel(), x.shape[1] if x.dim() > 1 else 1,
-                                  step_b, act, grad, float(alpha), float(scale), _stream(x.device)), "dcpt_fused_bias_act")
+    _call(lib.dcpt_fused_bias_act, (x, b_, r_, y), (x.numel(), x.shape[1] if x.dim() > 1 else 1, step_b, act, grad, float(alpha), float(scale)),
+          x.device)
     return y
 
 
@@ -1198,6 +1171,10 @@ def fused_leaky_relu(x, bias, negative_slope=0.2, scale=2 ** 0.5):
 
 # ------------------------------------------------------------------------------------------------
 # degradation-classifier head (reference basicsr/archs/degrad_classify_arch.py)
+def _conv_ln_ws(lib, bf):
+    return lib.dcpt_conv_ln_bf16_ws_bytes if bf else lib.dcpt_conv_ln_ws_bytes
+
+
 def _conv_ln_fwd(lib, x, w_, pk, lw, lb, res, relu):
     """ONE conv -> channels-first LayerNorm -> [+res] -> [ReLU] group: dcpt_conv_ln_fwd, or dcpt_conv_ln_fwd_bf16 with the conv's cached operand
     images ``pk`` (a byte buffer or None), by x.dtype.  Returns z (conv output), y and the LayerNorm statistics [2][B H W]."""
@@ -1205,13 +1182,12 @@ def _conv_ln_fwd(lib, x, w_, pk, lw, lb, res, relu):
     B, Cin, H, W = x.shape
     Cout, ks = w_.shape[0], w_.shape[2]
     dev = x.device
-    empty = _empty_nhwc_bf16 if bf else _empty_nhwc
-    z, y = empty(B, Cout, H, W, dev), empty(B, Cout, H, W, dev)
+    z, y = _empty(bf)(B, Cout, H, W, dev), _empty(bf)(B, Cout, H, W, dev)
     stats = torch.empty((2, B * H * W), dtype=torch.float32, device=dev)
-    ws = _workspace(dev, (lib.dcpt_conv_ln_bf16_ws_bytes if bf else lib.dcpt_conv_ln_ws_bytes)(B, H, W, Cin, Cout, ks, 0))
-    fn = lib.dcpt_conv_ln_fwd_bf16 if bf else lib.dcpt_conv_ln_fwd
-    check(fn(x.data_ptr(), w_.data_ptr(), *(_pkargs(pk) if bf else ()), lw.data_ptr(), lb.data_ptr(), _p(res), int(bool(relu)), z.data_ptr(),
-             y.data_ptr(), stats[0].data_ptr(), stats[1].data_ptr(), ws.data_ptr(), ws.numel(), B, H, W, Cin, Cout, ks, _stream(dev)), fn.__name__)
+    # (irregular: the relu flag sits between the pointers, the bf16 form takes the (pointer, bytes) pair of the weight pack)
+    _call(lib.dcpt_conv_ln_fwd_bf16 if bf else lib.dcpt_conv_ln_fwd,
+          (x, w_, *(_pkargs(pk) if bf else ()), lw, lb, res, int(bool(relu)), z, y, stats[0], stats[1]), (B, H, W, Cin, Cout, ks), dev,
+          _conv_ln_ws(lib, bf)(B, H, W, Cin, Cout, ks, 0))
     return z, y, stats
 
 
@@ -1222,16 +1198,13 @@ def _conv_ln_bwd(lib, dy, x, w_, pk, lw, z, y, stats, dx_add, has_res, relu):
     B, Cin, H, W = x.shape
     Cout, ks = w_.shape[0], w_.shape[2]
     dev = x.device
-    empty = _empty_nhwc_bf16 if bf else _empty_nhwc
-    dx = empty(B, Cin, H, W, dev)
+    dx = _empty(bf)(B, Cin, H, W, dev)
     dw = torch.empty_like(w_)
     dlw, dlb = torch.empty_like(lw), torch.empty_like(lw)
-    dres = empty(B, Cout, H, W, dev) if has_res else None
-    ws = _workspace(dev, (lib.dcpt_conv_ln_bf16_ws_bytes if bf else lib.dcpt_conv_ln_ws_bytes)(B, H, W, Cin, Cout, ks, 1))
-    fn = lib.dcpt_conv_ln_bwd_bf16 if bf else lib.dcpt_conv_ln_bwd
-    check(fn(dy.data_ptr(), x.data_ptr(), w_.data_ptr(), *(_pkargs(pk) if bf else ()), lw.data_ptr(), z.data_ptr(), y.data_ptr(),
-             stats[0].data_ptr(), stats[1].data_ptr(), _p(dx_add), dx.data_ptr(), dw.data_ptr(), dlw.data_ptr(), dlb.data_ptr(), _p(dres),
-             ws.data_ptr(), ws.numel(), B, H, W, Cin, Cout, ks, int(relu), _stream(dev)), fn.__name__)
+    dres = _empty(bf)(B, Cout, H, W, dev) if has_res else None
+    _call(lib.dcpt_conv_ln_bwd_bf16 if bf else lib.dcpt_conv_ln_bwd,
+          (dy, x, w_, *(_pkargs(pk) if bf else ()), lw, z, y, stats[0], stats[1], dx_add, dx, dw, dlw, dlb, dres),
+          (B, H, W, Cin, Cout, ks, int(relu)), dev, _conv_ln_ws(lib, bf)(B, H, W, Cin, Cout, ks, 1))
     return dx, dw, dlw, dlb, dres
 
 
@@ -1258,7 +1231,7 @@ class _ConvLNFn(torch.autograd.Function):
     def backward(ctx, dy):
         lib = _lib.load()
         x, w_, lw, z, y, stats = ctx.saved_tensors
-        dy = _nhwc(dy.to(torch.bfloat16) if x.dtype == torch.bfloat16 and dy.dtype != torch.bfloat16 else dy)
+        dy = _nhwc(_grad_cast(dy, torch.bfloat16) if x.dtype == torch.bfloat16 else dy)   # (fp32 storage: taken as it comes)
         return (*_conv_ln_bwd(lib, dy, x, w_, ctx.pk, lw, z, y, stats, None, ctx.has_res, ctx.relu), None, None)
 
 
@@ -1301,7 +1274,6 @@ class _BottleneckFn(torch.autograd.Function):
             saved += [w_, lw_, z, y, stats]
             cur = y
         ctx.save_for_backward(*saved)
-        ctx.bf = bf
         ctx.pkbufs = pkbufs   # (the backward of THIS forward reads the same operand images)
         return cur
 
@@ -1327,17 +1299,14 @@ class _BottleneckFn(torch.autograd.Function):
             z, y = _empty_nhwc_bf16(B, Cout, H, W, dev), _empty_nhwc_bf16(B, Cout, H, W, dev)
             stats = torch.empty((2, M), dtype=torch.float32, device=dev)
             pkp, pkn = _pk(pck, w)
-            garr[k] = _lib.BneckGroup(w_.data_ptr(), pkp, pkn, lw_.data_ptr(), lb_.data_ptr(), z.data_ptr(), y.data_ptr(), stats[0].data_ptr(),
-                                      stats[1].data_ptr(), None, None, None)
+            garr[k] = _lib.BneckGroup(w_.data_ptr(), pkp, pkn, *[t.data_ptr() for t in (lw_, lb_, z, y, stats[0], stats[1])], None, None, None)
             pkbufs.append(pck.buf if pkp is not None else None)
             saved += [w_, lw_, z, y, stats]
             keep.append(lb_)
-        ws = _workspace(dev, lib.dcpt_bottleneck_bf16_ws_bytes(B, H, W, C_, 0))
-        check(lib.dcpt_bottleneck_fwd_bf16(x.data_ptr(), garr, ws.data_ptr(), ws.numel(), B, H, W, C_, _stream(dev)), "dcpt_bottleneck_fwd_bf16")
+        _call(lib.dcpt_bottleneck_fwd_bf16, (x, garr), (B, H, W, C_), dev, lib.dcpt_bottleneck_bf16_ws_bytes(B, H, W, C_, 0))
         # the LayerNorm biases last: the backward recomputes the inner ReLU masks from z with them, so an in-place update between forward and
         # backward must trip autograd's version check
         ctx.save_for_backward(*saved, *keep)
-        ctx.bf = True
         ctx.pkbufs = pkbufs   # (the backward of THIS forward reads the same operand images)
         return saved[-2]
 
@@ -1347,20 +1316,17 @@ class _BottleneckFn(torch.autograd.Function):
         x = sv[0]
         dev = x.device
         B, C_, H, W = x.shape
-        g = _nhwc(dy if dy.dtype == torch.bfloat16 else dy.to(torch.bfloat16))
+        g = _nhwc(_grad_cast(dy, torch.bfloat16))
         garr = (_lib.BneckGroup * 3)()
         grads = []
         for k in range(3):
             w_, lw_, z, y, stats = sv[1 + 5 * k: 6 + 5 * k]
             dw, dlw, dlb = torch.empty_like(w_), torch.empty_like(lw_), torch.empty_like(lw_)
-            pk = ctx.pkbufs[k]
-            garr[k] = _lib.BneckGroup(w_.data_ptr(), _p(pk), 0 if pk is None else pk.numel(), lw_.data_ptr(), sv[16 + k].data_ptr(), z.data_ptr(), y.data_ptr(),
-                                      stats[0].data_ptr(), stats[1].data_ptr(), dw.data_ptr(), dlw.data_ptr(), dlb.data_ptr())
+            garr[k] = _lib.BneckGroup(w_.data_ptr(), *_pkargs(ctx.pkbufs[k]),
+                                      *[t.data_ptr() for t in (lw_, sv[16 + k], z, y, stats[0], stats[1], dw, dlw, dlb)])
             grads += [dw, dlw, dlb]
         dx = _empty_nhwc_bf16(B, C_, H, W, dev)
-        ws = _workspace(dev, lib.dcpt_bottleneck_bf16_ws_bytes(B, H, W, C_, 1))
-        check(lib.dcpt_bottleneck_bwd_bf16(g.data_ptr(), x.data_ptr(), garr, dx.data_ptr(), ws.data_ptr(), ws.numel(), B, H, W, C_, _stream(dev)),
-              "dcpt_bottleneck_bwd_bf16")
+        _call(lib.dcpt_bottleneck_bwd_bf16, (g, x, garr, dx), (B, H, W, C_), dev, lib.dcpt_bottleneck_bf16_ws_bytes(B, H, W, C_, 1))
         return (dx, *grads, None)
 
     @staticmethod
@@ -1369,8 +1335,8 @@ class _BottleneckFn(torch.autograd.Function):
         if ctx.fused:
             return _BottleneckFn._backward_bf16(ctx, lib, dy)
         sv = ctx.saved_tensors
-        x, bf = sv[0], ctx.bf
-        g = _nhwc(dy if (not bf or dy.dtype == torch.bfloat16) else dy.to(torch.bfloat16))
+        x = sv[0]
+        g = _nhwc(_grad_cast(dy, torch.bfloat16) if x.dtype == torch.bfloat16 else dy)
         grads, dshort = [None] * 9, None
         for k in (2, 1, 0):   # conv3 (its dres = the shortcut gradient), conv2, conv1 (dx = dx_add + ...)
             w_, lw_, z, y, stats = sv[1 + 5 * k: 6 + 5 * k]
@@ -1401,8 +1367,7 @@ class _PatchUnfoldFn(torch.autograd.Function):
         Kp = (Cin * ksize * ksize + 1 + 3) // 4 * 4
         Ho, Wo = (H + 2 * pad - ksize) // stride + 1, (W + 2 * pad - ksize) // stride + 1
         A = _empty_nhwc(B, Kp, Ho, Wo, x.device)
-        check(lib.dcpt_patch_unfold(x.data_ptr(), A.data_ptr(), B, Cin, H, W, ksize, stride, pad, Kp, _stream(x.device)),
-              "dcpt_patch_unfold")
+        _call(lib.dcpt_patch_unfold, (x, A), (B, Cin, H, W, ksize, stride, pad, Kp), x.device)
         ctx.geom = (B, Cin, H, W, ksize, stride, pad, Kp)
         return A
 
@@ -1412,8 +1377,7 @@ class _PatchUnfoldFn(torch.autograd.Function):
         B, Cin, H, W, ksize, stride, pad, Kp = ctx.geom
         dA = _nhwc(dA)
         dx = torch.empty((B, Cin, H, W), dtype=torch.float32, device=dA.device)
-        check(lib.dcpt_patch_fold(dA.data_ptr(), dx.data_ptr(), B, Cin, H, W, ksize, stride, pad, Kp, _stream(dA.device)),
-              "dcpt_patch_fold")
+        _call(lib.dcpt_patch_fold, (dA, dx), (B, Cin, H, W, ksize, stride, pad, Kp), dA.device)
         return dx, None, None, None
 
 
@@ -1428,6 +1392,10 @@ def conv_embed_ln(x, weight, bias, lnw, lnb, stride=2, pad=3):
         cols.append(weight.new_zeros(dim, kp - cin * ks * ks - 1))
     wext = torch.cat(cols, dim=1).reshape(dim, kp, 1, 1)
     return conv_ln(A, wext, lnw, lnb, None, relu=False)
+
+
+def _pool_relu_ws(lib, bf):
+    return lib.dcpt_conv1x1_pool_relu_bf16_ws_bytes if bf else lib.dcpt_conv1x1_pool_relu_ws_bytes
 
 
 @_remember_gemm_mode_fp32
@@ -1445,14 +1413,11 @@ class _ConvPoolReluFn(torch.autograd.Function):
         B, Cin, H, W = x.shape
         Cout = w_.shape[0]
         dev = x.device
-        empty = _empty_nhwc_bf16 if bf else _empty_nhwc
-        z = empty(B, Cout, H, W, dev)
-        y = empty(B, Cout, H // 2, W // 2, dev)
-        ws = _workspace(dev, (lib.dcpt_conv1x1_pool_relu_bf16_ws_bytes if bf else lib.dcpt_conv1x1_pool_relu_ws_bytes)(B, H, W, Cin, Cout, 0))
+        z = _empty(bf)(B, Cout, H, W, dev)
+        y = _empty(bf)(B, Cout, H // 2, W // 2, dev)
         ctx.pk = _pk_buf(packed, weight)
-        fn = lib.dcpt_conv1x1_pool_relu_fwd_bf16 if bf else lib.dcpt_conv1x1_pool_relu_fwd
-        check(fn(x.data_ptr(), w_.data_ptr(), *(_pkargs(ctx.pk) if bf else ()), z.data_ptr(), y.data_ptr(), ws.data_ptr(), ws.numel(),
-                 B, H, W, Cin, Cout, _stream(dev)), fn.__name__)
+        _call(lib.dcpt_conv1x1_pool_relu_fwd_bf16 if bf else lib.dcpt_conv1x1_pool_relu_fwd, (x, w_, *(_pkargs(ctx.pk) if bf else ()), z, y),
+              (B, H, W, Cin, Cout), dev, _pool_relu_ws(lib, bf)(B, H, W, Cin, Cout, 0))
         ctx.save_for_backward(x, w_, z)
         return y
 
@@ -1461,16 +1426,14 @@ class _ConvPoolReluFn(torch.autograd.Function):
         lib = _lib.load()
         x, w_, z = ctx.saved_tensors
         bf = x.dtype == torch.bfloat16
-        dy = _nhwc(dy.to(torch.bfloat16) if bf and dy.dtype != torch.bfloat16 else dy)
+        dy = _nhwc(_grad_cast(dy, torch.bfloat16) if bf else dy)
         B, Cin, H, W = x.shape
         Cout = w_.shape[0]
         dev = x.device
-        dx = (_empty_nhwc_bf16 if bf else _empty_nhwc)(B, Cin, H, W, dev)
+        dx = _empty(bf)(B, Cin, H, W, dev)
         dw = torch.empty_like(w_)
-        ws = _workspace(dev, (lib.dcpt_conv1x1_pool_relu_bf16_ws_bytes if bf else lib.dcpt_conv1x1_pool_relu_ws_bytes)(B, H, W, Cin, Cout, 1))
-        fn = lib.dcpt_conv1x1_pool_relu_bwd_bf16 if bf else lib.dcpt_conv1x1_pool_relu_bwd
-        check(fn(dy.data_ptr(), x.data_ptr(), w_.data_ptr(), *(_pkargs(ctx.pk) if bf else ()), z.data_ptr(), dx.data_ptr(), dw.data_ptr(),
-                 ws.data_ptr(), ws.numel(), B, H, W, Cin, Cout, _stream(dev)), fn.__name__)
+        _call(lib.dcpt_conv1x1_pool_relu_bwd_bf16 if bf else lib.dcpt_conv1x1_pool_relu_bwd,
+              (dy, x, w_, *(_pkargs(ctx.pk) if bf else ()), z, dx, dw), (B, H, W, Cin, Cout), dev, _pool_relu_ws(lib, bf)(B, H, W, Cin, Cout, 1))
         return dx, dw, None
 
 
@@ -1499,10 +1462,8 @@ class _MixFn(torch.autograd.Function):
         bf = feat.dtype == torch.bfloat16
         if bf and prev_ is not None and prev_.dtype != torch.bfloat16:
             raise _lib.DcptHipError("mix: prev and feat must have the same storage dtype")
-        out = (_empty_nhwc_bf16 if bf else _empty_nhwc)(*feat.shape, feat.device)
-        fn = lib.dcpt_mix_fwd_bf16 if bf else lib.dcpt_mix_fwd
-        check(fn(_p(prev_), feat.data_ptr(), mw.data_ptr(), mw.numel(), int(idx), out.data_ptr(), feat.numel(), _stream(feat.device)),
-              fn.__name__)
+        out = _empty(bf)(*feat.shape, feat.device)
+        _call(lib.dcpt_mix_fwd_bf16 if bf else lib.dcpt_mix_fwd, (prev_, feat, mw, mw.numel(), int(idx), out), (feat.numel(),), feat.device)
         ctx.save_for_backward(feat, mw)
         ctx.idx, ctx.has_prev = int(idx), prev is not None
         return out
@@ -1512,14 +1473,12 @@ class _MixFn(torch.autograd.Function):
         lib = _lib.load()
         feat, mw = ctx.saved_tensors
         bf = feat.dtype == torch.bfloat16
-        dout = _nhwc(dout if dout.dtype == feat.dtype else dout.to(feat.dtype))
+        dout = _nhwc(_grad_cast(dout, feat.dtype))
         dev = feat.device
-        dfeat = (_empty_nhwc_bf16 if bf else _empty_nhwc)(*feat.shape, dev)
+        dfeat = _empty(bf)(*feat.shape, dev)
         dmix = torch.empty_like(mw)
-        ws = _workspace(dev, lib.dcpt_mix_bwd_ws_bytes(feat.numel()))
-        fn = lib.dcpt_mix_bwd_bf16 if bf else lib.dcpt_mix_bwd
-        check(fn(dout.data_ptr(), feat.data_ptr(), mw.data_ptr(), mw.numel(), ctx.idx, dfeat.data_ptr(), dmix.data_ptr(), ws.data_ptr(),
-                 ws.numel(), feat.numel(), _stream(dev)), fn.__name__)
+        _call(lib.dcpt_mix_bwd_bf16 if bf else lib.dcpt_mix_bwd, (dout, feat, mw, mw.numel(), ctx.idx, dfeat, dmix), (feat.numel(),), dev,
+              lib.dcpt_mix_bwd_ws_bytes(feat.numel()))
         return (dout if ctx.has_prev else None), dfeat, dmix, None
 
 
@@ -1557,8 +1516,7 @@ class _MixStrideFn(torch.autograd.Function):
             raise ValueError(f"mix: prev {tuple(prev_.shape)} does not match the tap {(B, Cc, H // s, W // s)}")
         mw = _contig(mixing_weights.detach())
         out = _empty_nhwc(B, Cc, H // s, W // s, feat.device)
-        check(lib.dcpt_mix_stride_fwd(_p(prev_), feat.data_ptr(), mw.data_ptr(), mw.numel(), int(idx), out.data_ptr(), B, H, W, Cc, s,
-                                      sb, sh, sw, _stream(feat.device)), "dcpt_mix_stride_fwd")
+        _call(lib.dcpt_mix_stride_fwd, (prev_, feat, mw, mw.numel(), int(idx), out), (B, H, W, Cc, s, sb, sh, sw), feat.device)
         ctx.save_for_backward(feat, mw)
         ctx.meta = (int(idx), prev is not None, s, sb, sh, sw)
         return out
@@ -1574,14 +1532,13 @@ class _MixStrideFn(torch.autograd.Function):
         dout = _nhwc(dout)
         dfeat = _empty_nhwc(B, Cc, H // s, W // s, dev)
         dmix = torch.empty_like(mw)
-        ws = _workspace(dev, lib.dcpt_mix_stride_bwd_ws_bytes(dfeat.numel()))
-        check(lib.dcpt_mix_stride_bwd(dout.data_ptr(), feat.data_ptr(), mw.data_ptr(), mw.numel(), idx, dfeat.data_ptr(), dmix.data_ptr(),
-                                      ws.data_ptr(), ws.numel(), B, H, W, Cc, s, sb, sh, sw, _stream(dev)), "dcpt_mix_stride_bwd")
+        _call(lib.dcpt_mix_stride_bwd, (dout, feat, mw, mw.numel(), idx, dfeat, dmix), (B, H, W, Cc, s, sb, sh, sw), dev,
+              lib.dcpt_mix_stride_bwd_ws_bytes(dfeat.numel()))
         if not ctx.needs_input_grad[1]:
             dfeat = None
         elif s > 1:
             full = _empty_nhwc(B, Cc, H, W, dev)
-            check(lib.dcpt_grid_scatter(dfeat.data_ptr(), full.data_ptr(), B, 0, B, H, W, Cc, s, _stream(dev)), "dcpt_grid_scatter")
+            _call(lib.dcpt_grid_scatter, (dfeat, full), (B, 0, B, H, W, Cc, s), dev)
             dfeat = full
         return (dout if has_prev else None), dfeat, dmix, None, None
 
@@ -1615,11 +1572,9 @@ class _MeanPoolFCFn(torch.autograd.Function):
         dev = x.device
         pooled = torch.empty((B, Cc), dtype=torch.float32, device=dev)
         logits = torch.empty((B, NC), dtype=torch.float32, device=dev)
-        ws = _workspace(dev, lib.dcpt_meanpool_fc_ws_bytes(B, H * W, Cc))
         bf = x.dtype == torch.bfloat16   # bf16-storage feature map: pooled in fp32 straight from it, its gradient stored in bf16
-        fn = lib.dcpt_meanpool_fc_fwd_bf16 if bf else lib.dcpt_meanpool_fc_fwd
-        check(fn(x.data_ptr(), fw_.data_ptr(), _p(fb_), pooled.data_ptr(), logits.data_ptr(), ws.data_ptr(), ws.numel(), B, H * W, Cc, NC,
-                 _stream(dev)), fn.__name__)
+        _call(lib.dcpt_meanpool_fc_fwd_bf16 if bf else lib.dcpt_meanpool_fc_fwd, (x, fw_, fb_, pooled, logits), (B, H * W, Cc, NC), dev,
+              lib.dcpt_meanpool_fc_ws_bytes(B, H * W, Cc))
         ctx.save_for_backward(pooled, fw_)
         ctx.shape, ctx.has_bias, ctx.bf = (B, Cc, H, W), fb is not None, bf
         return logits
@@ -1632,13 +1587,11 @@ class _MeanPoolFCFn(torch.autograd.Function):
         NC = fw_.shape[0]
         dev = pooled.device
         dl = _contig(dlogits)
-        dx = (_empty_nhwc_bf16 if ctx.bf else _empty_nhwc)(B, Cc, H, W, dev)
+        dx = _empty(ctx.bf)(B, Cc, H, W, dev)
         dfw = torch.empty_like(fw_)
         dfb = torch.empty((NC,), dtype=torch.float32, device=dev)
-        ws = _workspace(dev, lib.dcpt_meanpool_fc_ws_bytes(B, H * W, Cc))
-        fn = lib.dcpt_meanpool_fc_bwd_bf16 if ctx.bf else lib.dcpt_meanpool_fc_bwd
-        check(fn(dl.data_ptr(), pooled.data_ptr(), fw_.data_ptr(), dx.data_ptr(), dfw.data_ptr(), dfb.data_ptr(), ws.data_ptr(), ws.numel(),
-                 B, H * W, Cc, NC, _stream(dev)), fn.__name__)
+        _call(lib.dcpt_meanpool_fc_bwd_bf16 if ctx.bf else lib.dcpt_meanpool_fc_bwd, (dl, pooled, fw_, dx, dfw, dfb), (B, H * W, Cc, NC), dev,
+              lib.dcpt_meanpool_fc_ws_bytes(B, H * W, Cc))
         return dx, dfw, (dfb if ctx.has_bias else None)
 
 
@@ -1649,6 +1602,10 @@ def meanpool_fc(x, fw, fb):
 # ------------------------------------------------------------------------------------------------
 # Restormer pieces (reference basicsr/archs/restormer_arch.py)
 from ._lib import GdfnParams, GdfnSaved, MdtaParams, MdtaSaved  # noqa: E402
+
+
+def _conv_ws(lib, bf):
+    return lib.dcpt_conv_bf16_ws_bytes if bf else lib.dcpt_conv_ws_bytes
 
 
 @_remember_gemm_mode_fp32
@@ -1666,11 +1623,9 @@ class _ConvFn(torch.autograd.Function):
         B, Cin, H, W = x.shape
         Cout, ks = w_.shape[0], w_.shape[2]
         dev = x.device
-        y = (_empty_nhwc_bf16 if bf else _empty_nhwc)(B, Cout, H, W, dev)
-        ws = _workspace(dev, (lib.dcpt_conv_bf16_ws_bytes if bf else lib.dcpt_conv_ws_bytes)(B, H, W, Cin, Cout, ks, 0))
-        fn = lib.dcpt_conv_fwd_bf16 if bf else lib.dcpt_conv_fwd
-        check(fn(x.data_ptr(), w_.data_ptr(), y.data_ptr(), ws.data_ptr(), ws.numel(), B, H, W, Cin, Cout, ks, _stream(dev)),
-              fn.__name__)
+        y = _empty(bf)(B, Cout, H, W, dev)
+        _call(lib.dcpt_conv_fwd_bf16 if bf else lib.dcpt_conv_fwd, (x, w_, y), (B, H, W, Cin, Cout, ks), dev,
+              _conv_ws(lib, bf)(B, H, W, Cin, Cout, ks, 0))
         ctx.save_for_backward(x, w_)
         return y
 
@@ -1679,18 +1634,14 @@ class _ConvFn(torch.autograd.Function):
         lib = _lib.load()
         x, w_ = ctx.saved_tensors
         bf = x.dtype == torch.bfloat16
-        if bf:
-            _require_gpu_bf16(dy)
-        dy = _nhwc(dy)
+        dy = _nhwc(_grad_strict(dy, bf))
         B, Cin, H, W = x.shape
         Cout, ks = w_.shape[0], w_.shape[2]
         dev = x.device
-        dx = (_empty_nhwc_bf16 if bf else _empty_nhwc)(B, Cin, H, W, dev)
+        dx = _empty(bf)(B, Cin, H, W, dev)
         dw = torch.empty_like(w_)
-        ws = _workspace(dev, (lib.dcpt_conv_bf16_ws_bytes if bf else lib.dcpt_conv_ws_bytes)(B, H, W, Cin, Cout, ks, 1))
-        fn = lib.dcpt_conv_bwd_bf16 if bf else lib.dcpt_conv_bwd
-        check(fn(dy.data_ptr(), x.data_ptr(), w_.data_ptr(), dx.data_ptr(), dw.data_ptr(), ws.data_ptr(), ws.numel(), B, H, W, Cin,
-                 Cout, ks, _stream(dev)), fn.__name__)
+        _call(lib.dcpt_conv_bwd_bf16 if bf else lib.dcpt_conv_bwd, (dy, x, w_, dx, dw), (B, H, W, Cin, Cout, ks), dev,
+              _conv_ws(lib, bf)(B, H, W, Cin, Cout, ks, 1))
         return dx, dw
 
 
@@ -1703,12 +1654,12 @@ def _shuffle(lib, x, up):
     bf = x.dtype == torch.bfloat16
     B, Cc, H, W = x.shape
     if up:
-        y = (_empty_nhwc_bf16 if bf else _empty_nhwc)(B, Cc // 4, 2 * H, 2 * W, x.device)
+        y = _empty(bf)(B, Cc // 4, 2 * H, 2 * W, x.device)
         fn = lib.dcpt_pixel_shuffle_bf16 if bf else lib.dcpt_pixel_shuffle
     else:
-        y = (_empty_nhwc_bf16 if bf else _empty_nhwc)(B, 4 * Cc, H // 2, W // 2, x.device)
+        y = _empty(bf)(B, 4 * Cc, H // 2, W // 2, x.device)
         fn = lib.dcpt_pixel_unshuffle_bf16 if bf else lib.dcpt_pixel_unshuffle
-    check(fn(x.data_ptr(), y.data_ptr(), B, H, W, Cc, _stream(x.device)), fn.__name__)
+    _call(fn, (x, y), (B, H, W, Cc), x.device)
     return y
 
 
@@ -1723,7 +1674,7 @@ class _PixelShuffleFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        (_require_gpu_bf16 if ctx.bf else _require_gpu)(dy)
+        (_require_gpu_bf16 if ctx.bf else _require_gpu)(dy)   # (strict in either storage; _grad_strict knows bf16 storage only)
         return _shuffle(_lib.load(), dy, not ctx.up), None
 
 
@@ -1748,9 +1699,8 @@ class _ConcatFn(torch.autograd.Function):
         bf = a.dtype == torch.bfloat16
         B, Ca, H, W = a.shape
         Cb = b.shape[1]
-        out = (_empty_nhwc_bf16 if bf else _empty_nhwc)(B, Ca + Cb, H, W, a.device)
-        fn = lib.dcpt_concat_channels_bf16 if bf else lib.dcpt_concat_channels
-        check(fn(a.data_ptr(), b.data_ptr(), out.data_ptr(), B * H * W, Ca, Cb, _stream(a.device)), fn.__name__)
+        out = _empty(bf)(B, Ca + Cb, H, W, a.device)
+        _call(lib.dcpt_concat_channels_bf16 if bf else lib.dcpt_concat_channels, (a, b, out), (B * H * W, Ca, Cb), a.device)
         ctx.dims, ctx.bf = (Ca, Cb), bf
         return out
 
@@ -1758,15 +1708,12 @@ class _ConcatFn(torch.autograd.Function):
     def backward(ctx, dout):
         lib = _lib.load()
         bf = ctx.bf
-        if bf:
-            _require_gpu_bf16(dout)
-        dout = _nhwc(dout)
+        dout = _nhwc(_grad_strict(dout, bf))
         Ca, Cb = ctx.dims
         B, _, H, W = dout.shape
-        da = (_empty_nhwc_bf16 if bf else _empty_nhwc)(B, Ca, H, W, dout.device)
-        db = (_empty_nhwc_bf16 if bf else _empty_nhwc)(B, Cb, H, W, dout.device)
-        fn = lib.dcpt_split_channels_bf16 if bf else lib.dcpt_split_channels
-        check(fn(dout.data_ptr(), da.data_ptr(), db.data_ptr(), B * H * W, Ca, Cb, _stream(dout.device)), fn.__name__)
+        da = _empty(bf)(B, Ca, H, W, dout.device)
+        db = _empty(bf)(B, Cb, H, W, dout.device)
+        _call(lib.dcpt_split_channels_bf16 if bf else lib.dcpt_split_channels, (dout, da, db), (B * H * W, Ca, Cb), dout.device)
         return da, db
 
 
@@ -1844,6 +1791,22 @@ def _restormer_mode(dev) -> str:
 # grad mode is off inside Function.forward) runs as "lean" / not full and keeps nothing, while an fp32 forward allocates what the save
 # mode says whatever the grad mode; and bit 1 of the workspace queries' mode argument (everything kept: a smaller workspace) exists in
 # the bf16 queries only.
+def _ws_mode(bf, full, backward):
+    """the mode argument of the MDTA / GDFN workspace queries: bit 0 = backward; bit 1 (bf16 queries only) = everything was kept"""
+    return int(backward) | (2 if bf and full else 0)
+
+
+def _mdta_saved(stats, qkv1, qkv, nrm, att, out_att, xn):
+    """dcpt_mdta_saved over the forward's buffers (qkv1 / out_att / xn: None where the save mode does not keep them)"""
+    return _struct(MdtaSaved, (stats[0], stats[1], qkv1, qkv, nrm, att[0], att[1], att[2], out_att, xn))
+
+
+def _mdta_fns(lib, bf):
+    """(forward, backward, workspace query) of the storage type"""
+    return ((lib.dcpt_mdta_bf16_fwd, lib.dcpt_mdta_bf16_bwd, lib.dcpt_mdta_bf16_ws_bytes) if bf
+            else (lib.dcpt_mdta_fwd, lib.dcpt_mdta_bwd, lib.dcpt_mdta_ws_bytes))
+
+
 @_remember_gemm_mode_fp32
 class _MDTAFn(torch.autograd.Function):
     """x + project_out(attn(LN(x)))  (restormer_arch.py:103-145, :156-157) -> dcpt_mdta_fwd / _bwd or dcpt_mdta_bf16_fwd / _bwd."""
@@ -1860,25 +1823,18 @@ class _MDTAFn(torch.autograd.Function):
         dev = x.device
         M, ch = B * H * W, Cc // heads
         nograd = bf and not train
-        y = (_empty_nhwc_bf16 if bf else _empty_nhwc)(B, Cc, H, W, dev)
+        y = _empty(bf)(B, Cc, H, W, dev)
         stats = torch.empty((2, M), dtype=torch.float32, device=dev)
         mode = "lean" if nograd else _restormer_mode(dev)
-        qkv1 = None if mode == "lean" else (_empty_nhwc_bf16 if bf else _empty_nhwc)(B, 3 * Cc, H, W, dev)
-        qkv = (_empty_nhwc_bf16 if bf else _empty_nhwc)(B, 3 * Cc, H, W, dev)
+        qkv1 = None if mode == "lean" else _empty(bf)(B, 3 * Cc, H, W, dev)
+        qkv = _empty(bf)(B, 3 * Cc, H, W, dev)
         nrm = torch.empty((B, 2 * Cc), dtype=torch.float32, device=dev)
         att = torch.empty((3, B, heads, ch, ch), dtype=torch.float32, device=dev)
-        out_att = None if mode != "full" else (_empty_nhwc_bf16 if bf else _empty_nhwc)(B, Cc, H, W, dev)
-        xn = None if mode != "full" else (_empty_nhwc_bf16 if bf else _empty_nhwc)(B, Cc, H, W, dev)
-        sv = MdtaSaved(stats[0].data_ptr(), stats[1].data_ptr(), _p(qkv1), qkv.data_ptr(), nrm.data_ptr(),
-                       att[0].data_ptr(), att[1].data_ptr(), att[2].data_ptr(), _p(out_att), _p(xn))
-        pp = MdtaParams(*[_p(t) for t in ps])
-        if bf:
-            ws = _workspace(dev, lib.dcpt_mdta_bf16_ws_bytes(B, H, W, Cc, heads, 2 if mode == "full" else 0))
-        else:
-            ws = _workspace(dev, lib.dcpt_mdta_ws_bytes(B, H, W, Cc, heads, 0))
-        fn = lib.dcpt_mdta_bf16_fwd if bf else lib.dcpt_mdta_fwd
-        check(fn(C.byref(pp), x.data_ptr(), y.data_ptr(), C.byref(sv), ws.data_ptr(), ws.numel(), B, H, W, Cc, heads, int(flags),
-                 _stream(dev)), fn.__name__)
+        out_att = None if mode != "full" else _empty(bf)(B, Cc, H, W, dev)
+        xn = None if mode != "full" else _empty(bf)(B, Cc, H, W, dev)
+        fwd, _, ws_bytes = _mdta_fns(lib, bf)
+        _call(fwd, (_struct(MdtaParams, ps), x, y, _mdta_saved(stats, qkv1, qkv, nrm, att, out_att, xn)), (B, H, W, Cc, heads, int(flags)), dev,
+              ws_bytes(B, H, W, Cc, heads, _ws_mode(bf, mode == "full", False)))
         ctx.heads, ctx.flags = heads, int(flags)
         ctx.has_bias = ps[1] is not None
         if nograd:   # nothing is kept for a backward pass that cannot happen
@@ -1900,33 +1856,23 @@ class _MDTAFn(torch.autograd.Function):
             norm_w, qkv_w, dw_w, proj_w, temp = ps
             norm_b = None
         bf = x.dtype == torch.bfloat16
-        if bf:
-            _require_gpu_bf16(dy)
-        dy = _nhwc(dy)
+        dy = _nhwc(_grad_strict(dy, bf))
         B, Cc, H, W = x.shape
         dev = x.device
-        dx = (_empty_nhwc_bf16 if bf else _empty_nhwc)(B, Cc, H, W, dev)
+        dx = _empty(bf)(B, Cc, H, W, dev)
         plist = [norm_w, norm_b, qkv_w, dw_w, proj_w, temp]
         grads = [None if t is None else torch.empty_like(t) for t in plist]
-        sv = MdtaSaved(stats[0].data_ptr(), stats[1].data_ptr(), _p(qkv1), qkv.data_ptr(), nrm.data_ptr(),
-                       att[0].data_ptr(), att[1].data_ptr(), att[2].data_ptr(), _p(out_att), _p(xn))
-        pp = MdtaParams(*[_p(t) for t in plist])
-        gg = MdtaParams(*[_p(t) for t in grads])
-        if bf:
-            ws = _workspace(dev, lib.dcpt_mdta_bf16_ws_bytes(B, H, W, Cc, ctx.heads, 3 if all(ctx.kept) else 1))
-        else:
-            ws = _workspace(dev, lib.dcpt_mdta_ws_bytes(B, H, W, Cc, ctx.heads, 1))
-        fn = lib.dcpt_mdta_bf16_bwd if bf else lib.dcpt_mdta_bwd
-        check(fn(C.byref(pp), C.byref(gg), x.data_ptr(), C.byref(sv), dy.data_ptr(), dx.data_ptr(), ws.data_ptr(), ws.numel(), B, H, W,
-                 Cc, ctx.heads, ctx.flags, _stream(dev)), fn.__name__)
+        _, bwd, ws_bytes = _mdta_fns(lib, bf)
+        _call(bwd, (_struct(MdtaParams, plist), _struct(MdtaParams, grads), x, _mdta_saved(stats, qkv1, qkv, nrm, att, out_att, xn), dy, dx),
+              (B, H, W, Cc, ctx.heads, ctx.flags), dev, ws_bytes(B, H, W, Cc, ctx.heads, _ws_mode(bf, all(ctx.kept), True)))
         return (dx, *grads, None, None, None)
 
 
 LN_BIASFREE, LN_EPS_1E5, ATTN_SOFTMAX = 1, 2, 4   # include/dcpt_hip.h: DCPT_LN_BIASFREE, DCPT_LN_EPS_1E5, DCPT_ATTN_SOFTMAX
 
 
-def _train(*ts) -> bool:
-    """a backward pass can follow (autograd.Function.forward itself always runs with grad mode off)"""
+def _wants_grad(*ts) -> bool:
+    """a backward pass can follow; decided by the caller (autograd.Function.forward itself always runs with grad mode off)"""
     return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in ts)
 
 
@@ -1934,8 +1880,19 @@ def mdta(x, norm_w, norm_b, qkv_w, dw_w, proj_w, temperature, heads, biasfree, e
     """``eps_1e5`` / ``softmax``: the PromptIR variants (LayerNorm eps 1e-5, softmax instead of ReLU attention).  x and the result are
     fp32 or torch.bfloat16 NHWC maps (bf16 activation storage)."""
     flags = (LN_BIASFREE if biasfree else 0) | (LN_EPS_1E5 if eps_1e5 else 0) | (ATTN_SOFTMAX if softmax else 0)
-    train = _train(x, norm_w, norm_b, qkv_w, dw_w, proj_w, temperature)
+    train = _wants_grad(x, norm_w, norm_b, qkv_w, dw_w, proj_w, temperature)
     return _MDTAFn.apply(x, norm_w, norm_b, qkv_w, dw_w, proj_w, temperature, heads, flags, train)
+
+
+def _gdfn_saved(stats, u, t, xn):
+    """dcpt_gdfn_saved over the forward's buffers (t / xn: None unless everything is kept)"""
+    return _struct(GdfnSaved, (stats[0], stats[1], u, t, xn))
+
+
+def _gdfn_fns(lib, bf):
+    """(forward, backward, workspace query) of the storage type"""
+    return ((lib.dcpt_gdfn_bf16_fwd, lib.dcpt_gdfn_bf16_bwd, lib.dcpt_gdfn_bf16_ws_bytes) if bf
+            else (lib.dcpt_gdfn_fwd, lib.dcpt_gdfn_bwd, lib.dcpt_gdfn_ws_bytes))
 
 
 @_remember_gemm_mode_fp32
@@ -1957,21 +1914,15 @@ class _GDFNFn(torch.autograd.Function):
         hidden = ps[4].shape[1]
         hp = (hidden + 7) // 8 * 8 if bf else (hidden + 3) // 4 * 4
         nograd = bf and not train
-        y = (_empty_nhwc_bf16 if bf else _empty_nhwc)(B, Cc, H, W, dev)
+        y = _empty(bf)(B, Cc, H, W, dev)
         stats = torch.empty((2, M), dtype=torch.float32, device=dev)
         full = not nograd and _restormer_mode(dev) == "full"
-        u = (_empty_nhwc_bf16 if bf else _empty_nhwc)(B, 2 * hp, H, W, dev)
-        t = (_empty_nhwc_bf16 if bf else _empty_nhwc)(B, hp, H, W, dev) if full else None
-        xn = (_empty_nhwc_bf16 if bf else _empty_nhwc)(B, Cc, H, W, dev) if full else None
-        sv = GdfnSaved(stats[0].data_ptr(), stats[1].data_ptr(), u.data_ptr(), _p(t), _p(xn))
-        pp = GdfnParams(*[_p(q) for q in ps])
-        if bf:
-            ws = _workspace(dev, lib.dcpt_gdfn_bf16_ws_bytes(B, H, W, Cc, hidden, 2 if full else 0))
-        else:
-            ws = _workspace(dev, lib.dcpt_gdfn_ws_bytes(B, H, W, Cc, hidden, 0))
-        fn = lib.dcpt_gdfn_bf16_fwd if bf else lib.dcpt_gdfn_fwd
-        check(fn(C.byref(pp), x.data_ptr(), y.data_ptr(), C.byref(sv), ws.data_ptr(), ws.numel(), B, H, W, Cc, hidden, int(flags),
-                 _stream(dev)), fn.__name__)
+        u = _empty(bf)(B, 2 * hp, H, W, dev)
+        t = _empty(bf)(B, hp, H, W, dev) if full else None
+        xn = _empty(bf)(B, Cc, H, W, dev) if full else None
+        fwd, _, ws_bytes = _gdfn_fns(lib, bf)
+        _call(fwd, (_struct(GdfnParams, ps), x, y, _gdfn_saved(stats, u, t, xn)), (B, H, W, Cc, hidden, int(flags)), dev,
+              ws_bytes(B, H, W, Cc, hidden, _ws_mode(bf, full, False)))
         ctx.full = full
         ctx.has_bias, ctx.flags, ctx.hidden = ps[1] is not None, int(flags), hidden
         if nograd:
@@ -1992,30 +1943,21 @@ class _GDFNFn(torch.autograd.Function):
             norm_w, in_w, dw_w, out_w = ps
             norm_b = None
         bf = x.dtype == torch.bfloat16
-        if bf:
-            _require_gpu_bf16(dy)
-        dy = _nhwc(dy)
+        dy = _nhwc(_grad_strict(dy, bf))
         B, Cc, H, W = x.shape
         dev = x.device
-        dx = (_empty_nhwc_bf16 if bf else _empty_nhwc)(B, Cc, H, W, dev)
+        dx = _empty(bf)(B, Cc, H, W, dev)
         plist = [norm_w, norm_b, in_w, dw_w, out_w]
         grads = [None if q is None else torch.empty_like(q) for q in plist]
-        sv = GdfnSaved(stats[0].data_ptr(), stats[1].data_ptr(), u.data_ptr(), _p(t), _p(xn))
-        pp = GdfnParams(*[_p(q) for q in plist])
-        gg = GdfnParams(*[_p(q) for q in grads])
-        if bf:
-            ws = _workspace(dev, lib.dcpt_gdfn_bf16_ws_bytes(B, H, W, Cc, ctx.hidden, 3 if ctx.full else 1))
-        else:
-            ws = _workspace(dev, lib.dcpt_gdfn_ws_bytes(B, H, W, Cc, ctx.hidden, 1))
-        fn = lib.dcpt_gdfn_bf16_bwd if bf else lib.dcpt_gdfn_bwd
-        check(fn(C.byref(pp), C.byref(gg), x.data_ptr(), C.byref(sv), dy.data_ptr(), dx.data_ptr(), ws.data_ptr(), ws.numel(), B, H, W,
-                 Cc, ctx.hidden, ctx.flags, _stream(dev)), fn.__name__)
+        _, bwd, ws_bytes = _gdfn_fns(lib, bf)
+        _call(bwd, (_struct(GdfnParams, plist), _struct(GdfnParams, grads), x, _gdfn_saved(stats, u, t, xn), dy, dx),
+              (B, H, W, Cc, ctx.hidden, ctx.flags), dev, ws_bytes(B, H, W, Cc, ctx.hidden, _ws_mode(bf, ctx.full, True)))
         return (dx, *grads, None, None)
 
 
 def gdfn(x, norm_w, norm_b, in_w, dw_w, out_w, biasfree, eps_1e5=False):
     flags = (LN_BIASFREE if biasfree else 0) | (LN_EPS_1E5 if eps_1e5 else 0)
-    return _GDFNFn.apply(x, norm_w, norm_b, in_w, dw_w, out_w, flags, _train(x, norm_w, norm_b, in_w, dw_w, out_w))
+    return _GDFNFn.apply(x, norm_w, norm_b, in_w, dw_w, out_w, flags, _wants_grad(x, norm_w, norm_b, in_w, dw_w, out_w))
 
 
 def mdta_bf16(x, norm_w, norm_b, qkv_w, dw_w, proj_w, temperature, heads, biasfree, eps_1e5=False, softmax=False):
@@ -2048,9 +1990,8 @@ class _PromptMixFn(torch.autograd.Function):
         dev = lg.device
         bf = bool(out_bf16)
         wsm = torch.empty((B, L), dtype=torch.float32, device=dev)
-        out = (_empty_nhwc_bf16 if bf else _empty_nhwc)(B, D, H, W, dev)
-        fn = lib.dcpt_prompt_mix_fwd_bf16 if bf else lib.dcpt_prompt_mix_fwd
-        check(fn(lg.data_ptr(), pp.data_ptr(), wsm.data_ptr(), out.data_ptr(), B, L, D, S, H, W, _stream(dev)), fn.__name__)
+        out = _empty(bf)(B, D, H, W, dev)
+        _call(lib.dcpt_prompt_mix_fwd_bf16 if bf else lib.dcpt_prompt_mix_fwd, (lg, pp, wsm, out), (B, L, D, S, H, W), dev)
         ctx.save_for_backward(pp, wsm)
         ctx.geom, ctx.bf = (B, L, D, S, H, W), bf
         return out
@@ -2060,16 +2001,12 @@ class _PromptMixFn(torch.autograd.Function):
         lib = _lib.load()
         pp, wsm = ctx.saved_tensors
         B, L, D, S, H, W = ctx.geom
-        if ctx.bf:
-            _require_gpu_bf16(dout)
-        dout = _nhwc(dout)
+        dout = _nhwc(_grad_strict(dout, ctx.bf))
         dev = dout.device
         dlogits = torch.empty((B, L), dtype=torch.float32, device=dev)
         dparam = torch.empty_like(pp)
-        ws = _workspace(dev, lib.dcpt_prompt_mix_bwd_ws_bytes(B, D, S))
-        fn = lib.dcpt_prompt_mix_bwd_bf16 if ctx.bf else lib.dcpt_prompt_mix_bwd
-        check(fn(dout.data_ptr(), pp.data_ptr(), wsm.data_ptr(), dlogits.data_ptr(), dparam.data_ptr(), ws.data_ptr(), ws.numel(),
-                 B, L, D, S, H, W, _stream(dev)), fn.__name__)
+        _call(lib.dcpt_prompt_mix_bwd_bf16 if ctx.bf else lib.dcpt_prompt_mix_bwd, (dout, pp, wsm, dlogits, dparam), (B, L, D, S, H, W), dev,
+              lib.dcpt_prompt_mix_bwd_ws_bytes(B, D, S))
         return dlogits, dparam, None, None, None
 
 
@@ -2085,8 +2022,12 @@ def prompt_mix(logits, prompt_param, H, W, out_bf16=False):
 from ._lib import SwinAttnParams, SwinAttnSaved, SwinMlpParams, SwinMlpSaved  # noqa: E402
 
 
-def _wants_grad(*ts) -> bool:
-    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in ts)
+def _swin_attn_saved(stats, qkv, att, lse):
+    return _struct(SwinAttnSaved, (stats[0], stats[1], qkv, att, lse))
+
+
+def _swin_mlp_saved(stats, h):
+    return _struct(SwinMlpSaved, (stats[0], stats[1], h))
 
 
 @_remember_gemm_mode
@@ -2103,17 +2044,15 @@ class _SwinAttnFn(torch.autograd.Function):
         dev = x.device
         M = B * H * W
         y = _empty_nhwc(B, Cc, H, W, dev)
-        pp = SwinAttnParams(*[t.data_ptr() for t in ps])
-        ws = _workspace(dev, lib.dcpt_swin_attn_ws_bytes(B, H, W, Cc, heads, 0))
         sv = None
         if grad_mode:
             stats = torch.empty((2, M), dtype=torch.float32, device=dev)
             qkv = torch.empty((M, 3 * Cc), dtype=torch.float32, device=dev)
             att = torch.empty((M, Cc), dtype=torch.float32, device=dev)
             lse = torch.empty((M, heads), dtype=torch.float32, device=dev)
-            sv = SwinAttnSaved(stats[0].data_ptr(), stats[1].data_ptr(), qkv.data_ptr(), att.data_ptr(), lse.data_ptr())
-        check(lib.dcpt_swin_attn_fwd(C.byref(pp), x.data_ptr(), y.data_ptr(), None if sv is None else C.byref(sv), ws.data_ptr(), ws.numel(),
-                                     B, H, W, Cc, heads, window, shift, _stream(dev)), "dcpt_swin_attn_fwd")
+            sv = _swin_attn_saved(stats, qkv, att, lse)
+        _call(lib.dcpt_swin_attn_fwd, (_struct(SwinAttnParams, ps), x, y, sv), (B, H, W, Cc, heads, window, shift), dev,
+              lib.dcpt_swin_attn_ws_bytes(B, H, W, Cc, heads, 0))
         if grad_mode:
             ctx.save_for_backward(x, stats, qkv, att, lse, *ps)
         ctx.geom = (heads, window, shift)
@@ -2129,12 +2068,8 @@ class _SwinAttnFn(torch.autograd.Function):
         dev = x.device
         dx = _empty_nhwc(B, Cc, H, W, dev)
         grads = [torch.empty_like(t) for t in ps]
-        sv = SwinAttnSaved(stats[0].data_ptr(), stats[1].data_ptr(), qkv.data_ptr(), att.data_ptr(), lse.data_ptr())
-        pp = SwinAttnParams(*[t.data_ptr() for t in ps])
-        gg = SwinAttnParams(*[t.data_ptr() for t in grads])
-        ws = _workspace(dev, lib.dcpt_swin_attn_ws_bytes(B, H, W, Cc, heads, 1))
-        check(lib.dcpt_swin_attn_bwd(C.byref(pp), C.byref(gg), x.data_ptr(), C.byref(sv), dy.data_ptr(), dx.data_ptr(), ws.data_ptr(),
-                                     ws.numel(), B, H, W, Cc, heads, window, shift, _stream(dev)), "dcpt_swin_attn_bwd")
+        _call(lib.dcpt_swin_attn_bwd, (_struct(SwinAttnParams, ps), _struct(SwinAttnParams, grads), x, _swin_attn_saved(stats, qkv, att, lse),
+                                       dy, dx), (B, H, W, Cc, heads, window, shift), dev, lib.dcpt_swin_attn_ws_bytes(B, H, W, Cc, heads, 1))
         return (dx, None, None, None, None, *grads)
 
 
@@ -2157,15 +2092,13 @@ class _SwinMlpFn(torch.autograd.Function):
         dev = x.device
         M, hidden = B * H * W, ps[2].shape[0]
         y = _empty_nhwc(B, Cc, H, W, dev)
-        pp = SwinMlpParams(*[t.data_ptr() for t in ps])
-        ws = _workspace(dev, lib.dcpt_swin_mlp_ws_bytes(B, H, W, Cc, hidden, 0))
         sv = None
         if grad_mode:
             stats = torch.empty((2, M), dtype=torch.float32, device=dev)
             h = torch.empty((M, hidden), dtype=torch.float32, device=dev)
-            sv = SwinMlpSaved(stats[0].data_ptr(), stats[1].data_ptr(), h.data_ptr())
-        check(lib.dcpt_swin_mlp_fwd(C.byref(pp), x.data_ptr(), y.data_ptr(), None if sv is None else C.byref(sv), ws.data_ptr(), ws.numel(),
-                                    B, H, W, Cc, hidden, _stream(dev)), "dcpt_swin_mlp_fwd")
+            sv = _swin_mlp_saved(stats, h)
+        _call(lib.dcpt_swin_mlp_fwd, (_struct(SwinMlpParams, ps), x, y, sv), (B, H, W, Cc, hidden), dev,
+              lib.dcpt_swin_mlp_ws_bytes(B, H, W, Cc, hidden, 0))
         if grad_mode:
             ctx.save_for_backward(x, stats, h, *ps)
         return y
@@ -2180,12 +2113,8 @@ class _SwinMlpFn(torch.autograd.Function):
         hidden = ps[2].shape[0]
         dx = _empty_nhwc(B, Cc, H, W, dev)
         grads = [torch.empty_like(t) for t in ps]
-        sv = SwinMlpSaved(stats[0].data_ptr(), stats[1].data_ptr(), h.data_ptr())
-        pp = SwinMlpParams(*[t.data_ptr() for t in ps])
-        gg = SwinMlpParams(*[t.data_ptr() for t in grads])
-        ws = _workspace(dev, lib.dcpt_swin_mlp_ws_bytes(B, H, W, Cc, hidden, 1))
-        check(lib.dcpt_swin_mlp_bwd(C.byref(pp), C.byref(gg), x.data_ptr(), C.byref(sv), dy.data_ptr(), dx.data_ptr(), ws.data_ptr(),
-                                    ws.numel(), B, H, W, Cc, hidden, _stream(dev)), "dcpt_swin_mlp_bwd")
+        _call(lib.dcpt_swin_mlp_bwd, (_struct(SwinMlpParams, ps), _struct(SwinMlpParams, grads), x, _swin_mlp_saved(stats, h), dy, dx),
+              (B, H, W, Cc, hidden), dev, lib.dcpt_swin_mlp_ws_bytes(B, H, W, Cc, hidden, 1))
         return (dx, None, *grads)
 
 
@@ -2207,9 +2136,7 @@ class _Conv3x3ResFn(torch.autograd.Function):
         B, Cc, H, W = x.shape
         dev = x.device
         y = _empty_nhwc(B, Cc, H, W, dev)
-        ws = _workspace(dev, lib.dcpt_conv3x3_res_ws_bytes(B, H, W, Cc, 0))
-        check(lib.dcpt_conv3x3_res_fwd(x.data_ptr(), w_.data_ptr(), b_.data_ptr(), res.data_ptr(), y.data_ptr(), ws.data_ptr(), ws.numel(),
-                                       B, H, W, Cc, _stream(dev)), "dcpt_conv3x3_res_fwd")
+        _call(lib.dcpt_conv3x3_res_fwd, (x, w_, b_, res, y), (B, H, W, Cc), dev, lib.dcpt_conv3x3_res_ws_bytes(B, H, W, Cc, 0))
         ctx.save_for_backward(x, w_)
         return y
 
@@ -2223,9 +2150,7 @@ class _Conv3x3ResFn(torch.autograd.Function):
         dx = _empty_nhwc(B, Cc, H, W, dev)
         dw = torch.empty_like(w_)
         db = torch.empty((Cc,), dtype=torch.float32, device=dev)
-        ws = _workspace(dev, lib.dcpt_conv3x3_res_ws_bytes(B, H, W, Cc, 1))
-        check(lib.dcpt_conv3x3_res_bwd(dy.data_ptr(), x.data_ptr(), w_.data_ptr(), dx.data_ptr(), dw.data_ptr(), db.data_ptr(), ws.data_ptr(),
-                                       ws.numel(), B, H, W, Cc, _stream(dev)), "dcpt_conv3x3_res_bwd")
+        _call(lib.dcpt_conv3x3_res_bwd, (dy, x, w_, dx, dw, db), (B, H, W, Cc), dev, lib.dcpt_conv3x3_res_ws_bytes(B, H, W, Cc, 1))
         return dx, dw, db, dy
 
 
@@ -2246,8 +2171,7 @@ class _ImgAffineFn(torch.autograd.Function):
         if m.numel() != Cc:
             raise ValueError(f"mean has {m.numel()} entries for {Cc} channels")
         y = torch.empty_like(x)
-        check(lib.dcpt_img_affine(x.data_ptr(), m.data_ptr(), y.data_ptr(), B, Cc, H * W, float(r), int(direction), _stream(x.device)),
-              "dcpt_img_affine")
+        _call(lib.dcpt_img_affine, (x, m, y), (B, Cc, H * W, float(r), int(direction)), x.device)
         ctx.geom = (float(r), int(direction))
         return y
 
@@ -2258,7 +2182,7 @@ class _ImgAffineFn(torch.autograd.Function):
         dy = _contig(dy)
         B, Cc, H, W = dy.shape
         dx = torch.empty_like(dy)
-        check(lib.dcpt_img_affine(dy.data_ptr(), None, dx.data_ptr(), B, Cc, H * W, r, direction, _stream(dy.device)), "dcpt_img_affine")
+        _call(lib.dcpt_img_affine, (dy, None, dx), (B, Cc, H * W, r, direction), dy.device)
         return dx, None, None, None
 
 
@@ -2269,6 +2193,11 @@ def img_affine(x, mean, r, direction):
 # ------------------------------------------------------------------------------------------------
 # RCAN (include/dcpt_hip.h dcpt_rcab_*, dcpt_conv3x3_ps_*).  Feature maps are (B, C, H, W) channels_last tensors.
 from ._lib import RcabParams, RcabSaved  # noqa: E402
+
+
+def _rcab_saved(h, t, ps_):
+    """dcpt_rcab_saved: h, t and the two [B][C] rows (pooled mean, sigmoid scale) of ``ps_``"""
+    return _struct(RcabSaved, (h, t, ps_[0], ps_[1]))
 
 
 @_remember_gemm_mode
@@ -2285,16 +2214,14 @@ class _RcabFn(torch.autograd.Function):
         Cr = ps[4].shape[0]
         dev = x.device
         y = _empty_nhwc(B, Cc, H, W, dev)
-        pp = RcabParams(*[t.data_ptr() for t in ps])
-        ws = _workspace(dev, lib.dcpt_rcab_ws_bytes(B, H, W, Cc, Cr, 0))
+        ws = _workspace(dev, lib.dcpt_rcab_ws_bytes(B, H, W, Cc, Cr, 0))   # (asked for before h and t, as it always was: passed inside ptrs)
         sv = None
         if grad_mode:
             h = _empty_nhwc(B, Cc, H, W, dev)
             t = _empty_nhwc(B, Cc, H, W, dev)
             ps_ = torch.empty((2, B, Cc), dtype=torch.float32, device=dev)
-            sv = RcabSaved(h.data_ptr(), t.data_ptr(), ps_[0].data_ptr(), ps_[1].data_ptr())
-        check(lib.dcpt_rcab_fwd(C.byref(pp), x.data_ptr(), y.data_ptr(), None if sv is None else C.byref(sv), ws.data_ptr(), ws.numel(),
-                                B, H, W, Cc, Cr, float(res_scale), _stream(dev)), "dcpt_rcab_fwd")
+            sv = _rcab_saved(h, t, ps_)
+        _call(lib.dcpt_rcab_fwd, (_struct(RcabParams, ps), x, y, sv, ws, ws.numel()), (B, H, W, Cc, Cr, float(res_scale)), dev)
         if grad_mode:
             ctx.save_for_backward(x, h, t, ps_, *ps)
         ctx.res_scale = float(res_scale)
@@ -2310,12 +2237,8 @@ class _RcabFn(torch.autograd.Function):
         dev = x.device
         dx = _empty_nhwc(B, Cc, H, W, dev)
         grads = [torch.empty_like(p) for p in ps]
-        sv = RcabSaved(h.data_ptr(), t.data_ptr(), ps_[0].data_ptr(), ps_[1].data_ptr())
-        pp = RcabParams(*[p.data_ptr() for p in ps])
-        gg = RcabParams(*[g.data_ptr() for g in grads])
-        ws = _workspace(dev, lib.dcpt_rcab_ws_bytes(B, H, W, Cc, Cr, 1))
-        check(lib.dcpt_rcab_bwd(C.byref(pp), C.byref(gg), x.data_ptr(), C.byref(sv), dy.data_ptr(), dx.data_ptr(), ws.data_ptr(), ws.numel(),
-                                B, H, W, Cc, Cr, ctx.res_scale, _stream(dev)), "dcpt_rcab_bwd")
+        _call(lib.dcpt_rcab_bwd, (_struct(RcabParams, ps), _struct(RcabParams, grads), x, _rcab_saved(h, t, ps_), dy, dx),
+              (B, H, W, Cc, Cr, ctx.res_scale), dev, lib.dcpt_rcab_ws_bytes(B, H, W, Cc, Cr, 1))
         return (dx, None, None, *grads)
 
 
@@ -2340,9 +2263,7 @@ class _Conv3x3PsFn(torch.autograd.Function):
             raise ValueError(f"conv3x3_ps: weight {tuple(w_.shape)} for C={Cc}, r={r} (expected ({r * r * Cc}, {Cc}, 3, 3))")
         dev = x.device
         y = _empty_nhwc(B, Cc, r * H, r * W, dev)
-        ws = _workspace(dev, lib.dcpt_conv3x3_ps_ws_bytes(B, H, W, Cc, r, 0))
-        check(lib.dcpt_conv3x3_ps_fwd(x.data_ptr(), w_.data_ptr(), b_.data_ptr(), y.data_ptr(), ws.data_ptr(), ws.numel(), B, H, W, Cc, r,
-                                      _stream(dev)), "dcpt_conv3x3_ps_fwd")
+        _call(lib.dcpt_conv3x3_ps_fwd, (x, w_, b_, y), (B, H, W, Cc, r), dev, lib.dcpt_conv3x3_ps_ws_bytes(B, H, W, Cc, r, 0))
         ctx.save_for_backward(x, w_)
         ctx.r = r
         return y
@@ -2358,9 +2279,7 @@ class _Conv3x3PsFn(torch.autograd.Function):
         dx = _empty_nhwc(B, Cc, H, W, dev)
         dw = torch.empty_like(w_)
         db = torch.empty((w_.shape[0],), dtype=torch.float32, device=dev)
-        ws = _workspace(dev, lib.dcpt_conv3x3_ps_ws_bytes(B, H, W, Cc, r, 1))
-        check(lib.dcpt_conv3x3_ps_bwd(dy.data_ptr(), x.data_ptr(), w_.data_ptr(), dx.data_ptr(), dw.data_ptr(), db.data_ptr(), ws.data_ptr(),
-                                      ws.numel(), B, H, W, Cc, r, _stream(dev)), "dcpt_conv3x3_ps_bwd")
+        _call(lib.dcpt_conv3x3_ps_bwd, (dy, x, w_, dx, dw, db), (B, H, W, Cc, r), dev, lib.dcpt_conv3x3_ps_ws_bytes(B, H, W, Cc, r, 1))
         return dx, dw, db, None
 
 
@@ -2392,10 +2311,9 @@ def rcab_bf16(x, conv1_w, conv1_b, conv2_w, conv2_b, ca1_w, ca1_b, ca2_w, ca2_b,
         raise ValueError(f"rcab_bf16: parameter shapes do not fit C={Cc} (conv {tuple(ps_[0].shape)} / {tuple(ps_[2].shape)}, CA {tuple(ps_[4].shape)})")
     dev = x.device
     y = _empty_nhwc_bf16(B, Cc, H, W, dev)
-    ws = _workspace(dev, _check_ws("rcab_bf16", lib.dcpt_rcab_bf16_ws_bytes(B, H, W, Cc, Cr), f"B={B} H={H} W={W} C={Cc} Cr={Cr}; C % 8 == 0"))
-    pp = RcabParams(*[t.data_ptr() for t in ps_])
-    check(lib.dcpt_rcab_fwd_bf16(C.byref(pp), *_pk(packed1, conv1_w), *_pk(packed2, conv2_w), x.data_ptr(), y.data_ptr(), ws.data_ptr(),
-                                 ws.numel(), B, H, W, Cc, Cr, float(res_scale), _stream(dev)), "dcpt_rcab_fwd_bf16")
+    nws = _check_ws("rcab_bf16", lib.dcpt_rcab_bf16_ws_bytes(B, H, W, Cc, Cr), f"B={B} H={H} W={W} C={Cc} Cr={Cr}; C % 8 == 0")
+    _call(lib.dcpt_rcab_fwd_bf16, (_struct(RcabParams, ps_), *_pk(packed1, conv1_w), *_pk(packed2, conv2_w), x, y),
+          (B, H, W, Cc, Cr, float(res_scale)), dev, nws)
     return y
 
 
@@ -2413,9 +2331,8 @@ def conv3x3_res_bf16(x, weight, bias, res, packed: PackedConvBf16 = None):
         raise ValueError(f"conv3x3_res_bf16: residual {tuple(res.shape)} for a map {tuple(x.shape)}")
     dev = x.device
     y = _empty_nhwc_bf16(B, Cc, H, W, dev)
-    ws = _workspace(dev, _check_ws("conv3x3_res_bf16", lib.dcpt_conv3x3_res_bf16_ws_bytes(B, H, W, Cc), f"B={B} H={H} W={W} C={Cc}; C % 8 == 0"))
-    check(lib.dcpt_conv3x3_res_fwd_bf16(x.data_ptr(), w_.data_ptr(), *_pk(packed, weight), b_.data_ptr(), res.data_ptr(), y.data_ptr(),
-                                        ws.data_ptr(), ws.numel(), B, H, W, Cc, _stream(dev)), "dcpt_conv3x3_res_fwd_bf16")
+    nws = _check_ws("conv3x3_res_bf16", lib.dcpt_conv3x3_res_bf16_ws_bytes(B, H, W, Cc), f"B={B} H={H} W={W} C={Cc}; C % 8 == 0")
+    _call(lib.dcpt_conv3x3_res_fwd_bf16, (x, w_, *_pk(packed, weight), b_, res, y), (B, H, W, Cc), dev, nws)
     return y
 
 
@@ -2431,10 +2348,10 @@ def conv3x3_ps_bf16(x, weight, bias, r, packed: PackedConvBf16 = None):
     B, Cc, H, W = x.shape
     _check_conv_weight("conv3x3_ps_bf16", w_, b_, r * r * Cc, Cc)
     dev = x.device
+    # (the workspace is asked for before y, as it always was: passed inside ptrs)
     ws = _workspace(dev, _check_ws("conv3x3_ps_bf16", lib.dcpt_conv3x3_ps_bf16_ws_bytes(B, H, W, Cc, r), f"B={B} H={H} W={W} C={Cc} r={r}; C % 8 == 0, r 2 or 3"))
     y = _empty_nhwc_bf16(B, Cc, r * H, r * W, dev)
-    check(lib.dcpt_conv3x3_ps_fwd_bf16(x.data_ptr(), w_.data_ptr(), *_pk(packed, weight), b_.data_ptr(), y.data_ptr(), ws.data_ptr(), ws.numel(),
-                                       B, H, W, Cc, r, _stream(dev)), "dcpt_conv3x3_ps_fwd_bf16")
+    _call(lib.dcpt_conv3x3_ps_fwd_bf16, (x, w_, *_pk(packed, weight), b_, y, ws, ws.numel()), (B, H, W, Cc, r), dev)
     return y
 
 
@@ -2478,14 +2395,12 @@ class _Conv3x3ActFn(torch.autograd.Function):
         what = f"B={B} H={H} W={W} Cin={Cin} Cout={Cout}: channels must be multiples of 4"
         if up2:
             y = _empty_nhwc(B, Cout, 2 * H, 2 * W, dev)
-            ws = _workspace(dev, _check_ws(name, lib.dcpt_up2_conv3x3_act_ws_bytes(B, H, W, Cin, 0), what))
-            check(lib.dcpt_up2_conv3x3_act_fwd(x.data_ptr(), w_.data_ptr(), b_.data_ptr(), y.data_ptr(), ws.data_ptr(), ws.numel(), B, H, W,
-                                               Cin, slope, _stream(dev)), "dcpt_up2_conv3x3_act_fwd")
+            _call(lib.dcpt_up2_conv3x3_act_fwd, (x, w_, b_, y), (B, H, W, Cin, slope), dev,
+                  _check_ws(name, lib.dcpt_up2_conv3x3_act_ws_bytes(B, H, W, Cin, 0), what))
         else:
             y = _empty_nhwc(B, Cout, H, W, dev)
-            ws = _workspace(dev, _check_ws(name, lib.dcpt_conv3x3_act_ws_bytes(B, H, W, Cin, Cout, 0), what))
-            check(lib.dcpt_conv3x3_act_fwd(x.data_ptr(), w_.data_ptr(), b_.data_ptr(), y.data_ptr(), ws.data_ptr(), ws.numel(), B, H, W, Cin,
-                                           Cout, slope, _stream(dev)), "dcpt_conv3x3_act_fwd")
+            _call(lib.dcpt_conv3x3_act_fwd, (x, w_, b_, y), (B, H, W, Cin, Cout, slope), dev,
+                  _check_ws(name, lib.dcpt_conv3x3_act_ws_bytes(B, H, W, Cin, Cout, 0), what))
         ctx.save_for_backward(x, y, w_)
         ctx.geom = (slope, up2)
         return y
@@ -2503,15 +2418,11 @@ class _Conv3x3ActFn(torch.autograd.Function):
         dw = torch.empty_like(w_)
         db = torch.empty((Cout,), dtype=torch.float32, device=dev)
         if up2:
-            ws = _workspace(dev, lib.dcpt_up2_conv3x3_act_ws_bytes(B, H, W, Cin, 1))
-            check(lib.dcpt_up2_conv3x3_act_bwd(dy.data_ptr(), x.data_ptr(), y.data_ptr(), w_.data_ptr(), dx.data_ptr(), dw.data_ptr(),
-                                               db.data_ptr(), ws.data_ptr(), ws.numel(), B, H, W, Cin, slope, _stream(dev)),
-                  "dcpt_up2_conv3x3_act_bwd")
+            _call(lib.dcpt_up2_conv3x3_act_bwd, (dy, x, y, w_, dx, dw, db), (B, H, W, Cin, slope), dev,
+                  lib.dcpt_up2_conv3x3_act_ws_bytes(B, H, W, Cin, 1))
         else:
-            ws = _workspace(dev, lib.dcpt_conv3x3_act_ws_bytes(B, H, W, Cin, Cout, 1))
-            check(lib.dcpt_conv3x3_act_bwd(dy.data_ptr(), x.data_ptr(), y.data_ptr(), w_.data_ptr(), dx.data_ptr(), dw.data_ptr(),
-                                           db.data_ptr(), ws.data_ptr(), ws.numel(), B, H, W, Cin, Cout, slope, _stream(dev)),
-                  "dcpt_conv3x3_act_bwd")
+            _call(lib.dcpt_conv3x3_act_bwd, (dy, x, y, w_, dx, dw, db), (B, H, W, Cin, Cout, slope), dev,
+                  lib.dcpt_conv3x3_act_ws_bytes(B, H, W, Cin, Cout, 1))
         return dx, dw, db, None, None
 
 
@@ -2545,9 +2456,7 @@ class _Conv3x3PsOutFn(torch.autograd.Function):
         nws = _check_ws("conv3x3_ps_out", lib.dcpt_conv3x3_ps_out_ws_bytes(B, H, W, Cc, Cimg, r, 0),
                         f"C={Cc} Cimg={Cimg} r={r}: C a multiple of 4, at most 4 image channels, r in 2, 3, 4")
         y = torch.empty((B, Cimg, r * H, r * W), dtype=torch.float32, device=dev)
-        ws = _workspace(dev, nws)
-        check(lib.dcpt_conv3x3_ps_out_fwd(x.data_ptr(), w_.data_ptr(), b_.data_ptr(), y.data_ptr(), ws.data_ptr(), ws.numel(), B, H, W, Cc,
-                                          Cimg, r, _stream(dev)), "dcpt_conv3x3_ps_out_fwd")
+        _call(lib.dcpt_conv3x3_ps_out_fwd, (x, w_, b_, y), (B, H, W, Cc, Cimg, r), dev, nws)
         ctx.save_for_backward(x, w_)
         ctx.geom = (Cimg, r)
         return y
@@ -2563,9 +2472,8 @@ class _Conv3x3PsOutFn(torch.autograd.Function):
         dx = _empty_nhwc(B, Cc, H, W, dev)
         dw = torch.empty_like(w_)
         db = torch.empty((w_.shape[0],), dtype=torch.float32, device=dev)
-        ws = _workspace(dev, lib.dcpt_conv3x3_ps_out_ws_bytes(B, H, W, Cc, Cimg, r, 1))
-        check(lib.dcpt_conv3x3_ps_out_bwd(dy.data_ptr(), x.data_ptr(), w_.data_ptr(), dx.data_ptr(), dw.data_ptr(), db.data_ptr(),
-                                          ws.data_ptr(), ws.numel(), B, H, W, Cc, Cimg, r, _stream(dev)), "dcpt_conv3x3_ps_out_bwd")
+        _call(lib.dcpt_conv3x3_ps_out_bwd, (dy, x, w_, dx, dw, db), (B, H, W, Cc, Cimg, r), dev,
+              lib.dcpt_conv3x3_ps_out_ws_bytes(B, H, W, Cc, Cimg, r, 1))
         return dx, dw, db, None
 
 
@@ -2597,10 +2505,7 @@ class _Conv3convResFn(torch.autograd.Function):
         a1 = a2 = None
         if grad_mode:
             a1, a2 = _empty_nhwc(B, Cq, H, W, dev), _empty_nhwc(B, Cq, H, W, dev)
-        pp = Conv3convParams(*[t.data_ptr() for t in ps])
-        ws = _workspace(dev, nws)
-        check(lib.dcpt_conv3conv_res_fwd(C.byref(pp), x.data_ptr(), res.data_ptr(), y.data_ptr(), _p(a1), _p(a2), ws.data_ptr(), ws.numel(),
-                                         B, H, W, Cc, _stream(dev)), "dcpt_conv3conv_res_fwd")
+        _call(lib.dcpt_conv3conv_res_fwd, (_struct(Conv3convParams, ps), x, res, y, a1, a2), (B, H, W, Cc), dev, nws)
         if grad_mode:
             ctx.save_for_backward(x, a1, a2, *ps)
         return y
@@ -2614,11 +2519,8 @@ class _Conv3convResFn(torch.autograd.Function):
         dev = x.device
         dx = _empty_nhwc(B, Cc, H, W, dev)
         grads = [torch.empty_like(p) for p in ps]
-        pp = Conv3convParams(*[p.data_ptr() for p in ps])
-        gg = Conv3convParams(*[g.data_ptr() for g in grads])
-        ws = _workspace(dev, lib.dcpt_conv3conv_res_ws_bytes(B, H, W, Cc, 1))
-        check(lib.dcpt_conv3conv_res_bwd(C.byref(pp), C.byref(gg), x.data_ptr(), a1.data_ptr(), a2.data_ptr(), dy.data_ptr(), dx.data_ptr(),
-                                         ws.data_ptr(), ws.numel(), B, H, W, Cc, _stream(dev)), "dcpt_conv3conv_res_bwd")
+        _call(lib.dcpt_conv3conv_res_bwd, (_struct(Conv3convParams, ps), _struct(Conv3convParams, grads), x, a1, a2, dy, dx), (B, H, W, Cc), dev,
+              lib.dcpt_conv3conv_res_ws_bytes(B, H, W, Cc, 1))
         return (dx, None, dy, *grads)
 
 
@@ -2657,6 +2559,5 @@ def image_metric_sums(img, img2, crop_border=0, test_y_channel=False, image_rang
     sums = torch.empty(B, 1 if luma else Cc, dtype=torch.float64, device=dev) if ssim else None
     nws = lib.dcpt_imgmetric_ws_bytes(B, Cc, H, W, crop, flags)   # (0 for arguments the entry point refuses: it then names the reason)
     ws = _workspace(dev, nws)
-    check(lib.dcpt_imgmetric(img.data_ptr(), img2.data_ptr(), sse.data_ptr(), _p(sums), ws.data_ptr(), nws, B, Cc, H, W, crop, flags,
-                             _stream(dev)), "dcpt_imgmetric")
+    _call(lib.dcpt_imgmetric, (img, img2, sse, sums, ws, nws), (B, Cc, H, W, crop, flags), dev)   # (irregular: the queried size, not the buffer's)
     return sse, sums
