@@ -146,6 +146,21 @@ struct GemmNTB {
 // N (= row length) for which the two LayerNorm epilogues exist on a launch of M rows; conv3: the implicit 3 x 3 form of the GEMM
 bool gemm_nt_bf16_ln_epi_ok(int64_t M, int N, int K, int conv3, int gC);
 int launch_gemm_nt_bf16(const GemmNTB& p, int epi, hipStream_t s);
+// The two common fills (the bf16 twins of gemm.h's); the caller sets the epilogue fields (bias, res / ldres, cscale, aux, gate, colpart, P, psr,
+// the LayerNorm fields), the batching (nb, s?) and, for the scatter epilogues, gH / gW / gC afterwards.  nb stays 0: launch_gemm_nt_bf16
+// reads nb < 1 as 1 before anything else looks at it.
+// Linear layer on rows: C[m][n] = sum_k A[m][k] Bw[n][k]
+inline GemmNTB gemm_ntb_linear(const bf16_t* A, int lda, int64_t M, int K, const bf16_t* Bw, int N, bf16_t* C, int ldc) {
+    GemmNTB g{};
+    g.M = M; g.A = A; g.lda = lda; g.K = K; g.Bw = Bw; g.N = N; g.C = C; g.ldc = ldc;
+    return g;
+}
+// Implicit 3x3 conv (conv3) of the NHWC map x [B][H][W][Cin] with the operand image Bw [Cout][9 Cin]
+inline GemmNTB gemm_ntb_conv3(const bf16_t* x, int B, int H, int W, int Cin, const bf16_t* Bw, int Cout, bf16_t* C, int ldc) {
+    GemmNTB g{};
+    g.M = (int64_t)B * H * W; g.A = x; g.K = 9 * Cin; g.conv3 = 1; g.gH = H; g.gW = W; g.gC = Cin; g.Bw = Bw; g.N = Cout; g.C = C; g.ldc = ldc;
+    return g;
+}
 // 256 x 256-tile kernel for the wide levels (gemm_bf16_256.hip); launch_gemm_nt_bf16 routes eligible launches to it
 bool gemm_nt_bf16_256_ok(const GemmNTB& p, int epi, int min_tiles = 192);   // min_tiles: fill most of the 256 CUs
 int launch_gemm_nt_bf16_256(const GemmNTB& p, int epi, hipStream_t s);
@@ -226,6 +241,13 @@ struct FinSlab {
     int N, K, splits, tiles_k, ks_div, cs_rows;   // splits = partial sums per tile; cs_rows = rows of colsum (blocks per tile)
     int conv3;                                    // != 0: K = 9 * Ci packed as tap * Ci + ic, written as dW[n][ic][tap] (a dense 3 x 3's weight layout)
 };
+// the slab job of one planned problem of the grouped launch: one partial sum per slot, one column-sum row per block of a tile, unweighted
+// (ks_div = 1); the caller adds dW / dbias, the gain operands, kscale and conv3
+inline FinSlab fin_slab(const TnProb& q) {
+    FinSlab f{};
+    f.slab = q.slab; f.colsum = q.colsum; f.N = q.N; f.K = q.K; f.splits = q.slots; f.cs_rows = q.splits; f.tiles_k = q.tiles_k; f.ks_div = 1;
+    return f;
+}
 struct FinCols {
     const float* part;
     float *out0, *out1;

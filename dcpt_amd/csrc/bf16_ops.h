@@ -38,6 +38,38 @@ using WpackBJobs = WpackBJobsT<WPACKB_MAX_JOBS>;
 using WpackBJobsL = WpackBJobsT<WPACKB_MAX_JOBS_L>;
 int launch_wpack_bf16(const WpackBJobs& jobs, hipStream_t s);
 int launch_wpack_bf16(const WpackBJobsL& jobs, hipStream_t s, int grid_cap = 256);   // grid.x <= grid_cap (x up to 80 jobs in grid.y)
+// job i of a launch (mode = the `transpose` code above); kscale / nimg (the per-image form) stay the caller's.  nimg 0 and 1 are one job:
+// the kernel and the launcher both read nimg > 0 ? nimg : 1.
+template <typename J>
+inline void wpack_job(J& j, int i, const float* in, bf16_t* out, int N, int K, int mode, const float* rs = nullptr) {
+    j.in[i] = in; j.out[i] = out; j.N[i] = N; j.K[i] = K; j.transpose[i] = mode; j.rs[i] = rs;
+}
+inline int launch_wpack_bf16_one(const float* in, bf16_t* out, int N, int K, int mode, hipStream_t s) {
+    WpackBJobs j{};
+    j.n = 1;
+    wpack_job(j, 0, in, out, N, K, mode);
+    return launch_wpack_bf16(j, s);
+}
+// The bf16-storage weight gradient of a layer on rows on the 128-tile TN kernel, start to end (the twin of kernels.h's wgrad_need /
+// launch_wgrad): plans the split, runs launch_gemm_tn_bf16 into slab / colsum and reduces with the fp32 reducer:
+//   dW = sum_m X[m][n] Y'(m, k) in the layout of `mode` (WR_PLAIN / WR_CONV3 / WR_DOWN / WR_UP),  db[n] = sum_m X[m][n]
+// proto carries the gathers (yconv / xg2 / yg2 with gH, gW, gC); colsum == null: no bias gradient; gain as launch_wgrad's.
+// wgrad_need_bf16 raises *slab_floats / *colsum_floats (either may be null) to what one such gradient needs.
+void wgrad_need_bf16(int64_t M, int N, int K, size_t* slab_floats, size_t* colsum_floats);
+int launch_wgrad_bf16(const GemmTNB& proto, const bf16_t* X, int ldx, int N, const bf16_t* Y, int ldy, int K, int64_t M, float* slab, float* colsum,
+                      float* dW, float* db, int mode, hipStream_t s, const WgradGain& gain = WgradGain{});
+
+// A conv's two operand images as ONE cached buffer (dcpt_conv_wpack_bf16_multi, ABI 14): the forward image [Cout][ks ks Cin] at offset 0, the
+// data gradient's (transposed; flipped taps for the dense 3 x 3) at wpack_half_bytes.  `pk` = that buffer or nullptr (pack in the call).
+inline size_t wpack_half_bytes(int Cin, int Cout, int ks) { return (((size_t)Cout * ks * ks * Cin * sizeof(bf16_t)) + 255) & ~(size_t)255; }
+inline const bf16_t* pk_fwd(const void* pk) { return static_cast<const bf16_t*>(pk); }
+inline const bf16_t* pk_bwd(const void* pk, int Cin, int Cout, int ks) {
+    return reinterpret_cast<const bf16_t*>(static_cast<const char*>(pk) + wpack_half_bytes(Cin, Cout, ks));
+}
+inline int pk_check(const void* pk, size_t pk_bytes, int Cin, int Cout, int ks, const char* who) {
+    DCPT_CHECK_ARG(pk == nullptr || pk_bytes >= 2 * wpack_half_bytes(Cin, Cout, ks), "%s: packed weights too small (dcpt_conv_wpack_bf16_bytes)", who);
+    return DCPT_OK;
+}
 int launch_scale_rows_bf16(const bf16_t* x, const float* simg, bf16_t* out, int64_t M, int C, int P, hipStream_t s);
 int launch_sca_ds_part_bf16(const bf16_t* dts, const bf16_t* t2, float* ds_part, int B, int C, int P, int nslices, hipStream_t s);
 

@@ -597,6 +597,26 @@ static int launch_wpack_bf16_t(const WpackBJobsT<MAXJ>& jobs, hipStream_t s, int
 int launch_wpack_bf16(const WpackBJobs& jobs, hipStream_t s) { return launch_wpack_bf16_t(jobs, s); }
 int launch_wpack_bf16(const WpackBJobsL& jobs, hipStream_t s, int grid_cap) { return launch_wpack_bf16_t(jobs, s, grid_cap); }
 
+void wgrad_need_bf16(int64_t M, int N, int K, size_t* slab_floats, size_t* colsum_floats) {
+    int sp;
+    int64_t rps;
+    gemm_tn_bf16_plan(M, N, K, &sp, &rps);
+    const size_t a = (size_t)sp * N * K, b = (size_t)sp * gemm_tn_bf16_tiles_k(N, K) * N;
+    if (slab_floats && a > *slab_floats) *slab_floats = a;
+    if (colsum_floats && b > *colsum_floats) *colsum_floats = b;
+}
+
+int launch_wgrad_bf16(const GemmTNB& proto, const bf16_t* X, int ldx, int N, const bf16_t* Y, int ldy, int K, int64_t M, float* slab, float* colsum,
+                      float* dW, float* db, int mode, hipStream_t s, const WgradGain& gain) {
+    GemmTNB t = proto;
+    t.X = X; t.ldx = ldx; t.N = N; t.Y = Y; t.ldy = ldy; t.K = K; t.M = M;
+    t.slab = slab; t.colsum = colsum;
+    gemm_tn_bf16_plan(M, N, K, &t.splits, &t.rows_per_split);   // the plan wgrad_need_bf16 sized the buffers with
+    DCPT_TRY(launch_gemm_tn_bf16(t, s));
+    return launch_wgrad_reduce(slab, colsum, t.splits, colsum ? t.splits * gemm_tn_bf16_tiles_k(N, K) : 0, N, K, gain.rowscale, gain.W, gain.wbias,
+                               dW, gain.dgain, db, mode, s);
+}
+
 int launch_scale_rows_bf16(const bf16_t* x, const float* simg, bf16_t* out, int64_t M, int C, int P, hipStream_t s) {
     DCPT_CHECK_ARG(C % 8 == 0, "scale_rows_bf16: C=%d", C);
     scale_rows_bf16_kernel<<<dim3(grid_for(M * (C / 8))), dim3(256), 0, s>>>(x, simg, out, M, C, P);

@@ -102,7 +102,7 @@ struct DownWs {
     int64_t rps;
 };
 size_t down_layout(int B, int H, int W, int C, int backward, void* base, size_t bytes, DownWs* out) {
-    WsAlloc a(base, base ? bytes : (size_t)-1);
+    WsAlloc a(base, bytes);
     DownWs w{};
     w.wp = a.get<float>((size_t)8 * C * C);
     if (backward) {
@@ -173,7 +173,7 @@ struct UpWs {
     int64_t rps;
 };
 size_t up_layout(int B, int H, int W, int C, int backward, void* base, size_t bytes, UpWs* out) {
-    WsAlloc a(base, base ? bytes : (size_t)-1);
+    WsAlloc a(base, bytes);
     UpWs w{};
     w.wp = a.get<float>((size_t)2 * C * C);
     if (backward) {
@@ -282,7 +282,7 @@ const char* metric_check(int B, int C, int H, int W, int crop, int flags) {
     return nullptr;
 }
 size_t metric_layout(int B, int C, int H, int W, int crop, int flags, void* base, size_t bytes, MetricWs* out) {
-    WsAlloc a(base, base ? bytes : (size_t)-1);
+    WsAlloc a(base, bytes);
     const int Cp = ((flags & DCPT_METRIC_Y) && C == 3) ? 1 : C;
     const size_t n = (size_t)B * Cp * metric_num_tiles(H - 2 * crop, W - 2 * crop);
     MetricWs w{};

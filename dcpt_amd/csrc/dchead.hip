@@ -322,13 +322,6 @@ __global__ __launch_bounds__(256) void bcast_rows_kernel(const float* __restrict
     }
 }
 
-inline unsigned grid_for(int64_t n) {
-    int64_t nb = cdiv64(n, 256);
-    if (nb > 8192) nb = 8192;
-    if (nb < 1) nb = 1;
-    return (unsigned)nb;
-}
-
 struct ConvWs {
     float* wp;      // packed / transposed weights
     float* dz;      // [M][Cout]  (backward)
@@ -339,7 +332,7 @@ struct ConvWs {
 
 size_t conv_layout(int B, int H, int W, int Cin, int Cout, int ks, int backward, bool with_ln, void* base, size_t bytes,
                    ConvWs* out) {
-    WsAlloc a(base, base ? bytes : (size_t)-1);
+    WsAlloc a(base, bytes);
     ConvWs w{};
     const int K = ks * ks * Cin;
     const int64_t M = (int64_t)B * H * W;
@@ -463,7 +456,7 @@ extern "C" int dcpt_conv1x1_pool_relu_fwd(const float* x, const float* w, float*
     DCPT_CHECK_ARG(H % 2 == 0 && W % 2 == 0 && Cin % 4 == 0 && Cout % 4 == 0, "conv1x1_pool_relu_fwd: bad shape");
     ConvWs cw{};
     DCPT_TRY(conv_fwd(x, w, z, cw, B, H, W, Cin, Cout, 1, s));
-    pool_relu_fwd_kernel<<<dim3(grid_for((int64_t)B * (H / 2) * (W / 2) * (Cout / 4))), dim3(256), 0, s>>>(z, y, B, H, W, Cout);
+    pool_relu_fwd_kernel<<<dim3(ew_grid_8k((int64_t)B * (H / 2) * (W / 2) * (Cout / 4))), dim3(256), 0, s>>>(z, y, B, H, W, Cout);
     DCPT_CHECK_LAUNCH("pool_relu_fwd");
     return DCPT_OK;
 }
@@ -475,7 +468,7 @@ extern "C" int dcpt_conv1x1_pool_relu_bwd(const float* dy, const float* x, const
     ConvWs cw;
     const size_t need = conv_layout(B, H, W, Cin, Cout, 1, 1, false, ws, ws_bytes, &cw);
     DCPT_CHECK_WS("conv1x1_pool_relu_bwd", ws, ws_bytes, need);
-    pool_relu_bwd_kernel<<<dim3(grid_for((int64_t)B * (H / 2) * (W / 2) * (Cout / 4))), dim3(256), 0, s>>>(z, dy, cw.dz, B, H, W, Cout);
+    pool_relu_bwd_kernel<<<dim3(ew_grid_8k((int64_t)B * (H / 2) * (W / 2) * (Cout / 4))), dim3(256), 0, s>>>(z, dy, cw.dz, B, H, W, Cout);
     DCPT_CHECK_LAUNCH("pool_relu_bwd");
     return conv_bwd(cw.dz, x, w, dx, dw, cw, B, H, W, Cin, Cout, 1, s);
 }
@@ -484,7 +477,7 @@ extern "C" int dcpt_conv1x1_pool_relu_bwd(const float* dy, const float* x, const
 template <typename ST>
 static int mix_fwd_t(const ST* prev, const ST* feat, const float* mixing_weights, int n, int idx, ST* out, int64_t numel, hipStream_t s) {
     DCPT_CHECK_ARG(feat && mixing_weights && out && n >= 1 && n <= 64 && idx >= 0 && idx < n && numel % 4 == 0, "mix_fwd: bad argument");
-    mix_fwd_kernel<ST><<<dim3(grid_for(numel / 4)), dim3(256), 0, s>>>(prev, feat, mixing_weights, n, idx, out, numel / 4);
+    mix_fwd_kernel<ST><<<dim3(ew_grid_8k(numel / 4)), dim3(256), 0, s>>>(prev, feat, mixing_weights, n, idx, out, numel / 4);
     DCPT_CHECK_LAUNCH("mix_fwd");
     return DCPT_OK;
 }
@@ -497,14 +490,14 @@ extern "C" int dcpt_mix_fwd_bf16(const uint16_t* prev, const uint16_t* feat, con
     return mix_fwd_t<bf16_t>(prev, feat, mixing_weights, n, idx, out, numel, (hipStream_t)stream);
 }
 
-extern "C" size_t dcpt_mix_bwd_ws_bytes(int64_t numel) { return align_up((size_t)grid_for(numel / 4) * sizeof(float), 256); }
+extern "C" size_t dcpt_mix_bwd_ws_bytes(int64_t numel) { return align_up((size_t)ew_grid_8k(numel / 4) * sizeof(float), 256); }
 
 template <typename ST>
 static int mix_bwd_t(const ST* dout, const ST* feat, const float* mixing_weights, int n, int idx, ST* dfeat, float* dmix, void* ws,
                      size_t ws_bytes, int64_t numel, hipStream_t s) {
     DCPT_CHECK_ARG(dout && feat && mixing_weights && dfeat && dmix && n >= 1 && n <= 64 && numel % 4 == 0, "mix_bwd: bad argument");
     DCPT_CHECK_WS("mix_bwd", ws, ws_bytes, dcpt_mix_bwd_ws_bytes(numel));
-    const unsigned nb = grid_for(numel / 4);
+    const unsigned nb = ew_grid_8k(numel / 4);
     mix_bwd_kernel<ST><<<dim3(nb), dim3(256), 0, s>>>(dout, feat, mixing_weights, n, idx, dfeat, (float*)ws, numel / 4);
     DCPT_CHECK_LAUNCH("mix_bwd");
     mix_bwd_final_kernel<<<dim3(1), dim3(256), 0, s>>>((float*)ws, (int)nb, mixing_weights, n, idx, dmix);
@@ -541,7 +534,7 @@ extern "C" int dcpt_mix_stride_fwd(const float* prev, const float* feat, const f
     TapGeom g;
     DCPT_TRY(tap_geom("mix_stride_fwd", feat, B, H, W, C, s, sb, sh, sw, &g));
     const int64_t nq = (int64_t)B * g.Hc * g.Wc * g.nq;
-    mix_stride_fwd_kernel<<<dim3(grid_for(nq)), dim3(256), 0, (hipStream_t)stream>>>(prev, feat, mixing_weights, n, idx, out, g, nq);
+    mix_stride_fwd_kernel<<<dim3(ew_grid_8k(nq)), dim3(256), 0, (hipStream_t)stream>>>(prev, feat, mixing_weights, n, idx, out, g, nq);
     DCPT_CHECK_LAUNCH("mix_stride_fwd");
     trace_tag("head.mix_stride_fwd");
     return DCPT_OK;
@@ -558,7 +551,7 @@ extern "C" int dcpt_mix_stride_bwd(const float* dout, const float* feat, const f
     DCPT_TRY(tap_geom("mix_stride_bwd", feat, B, H, W, C, s, sb, sh, sw, &g));
     const int64_t nq = (int64_t)B * g.Hc * g.Wc * g.nq;
     DCPT_CHECK_WS("mix_stride_bwd", ws, ws_bytes, dcpt_mix_stride_bwd_ws_bytes(nq * 4));
-    const unsigned nb = grid_for(nq);
+    const unsigned nb = ew_grid_8k(nq);
     mix_stride_bwd_kernel<<<dim3(nb), dim3(256), 0, (hipStream_t)stream>>>(dout, feat, mixing_weights, n, idx, dfeat_c, (float*)ws, g, nq);
     DCPT_CHECK_LAUNCH("mix_stride_bwd");
     mix_bwd_final_kernel<<<dim3(1), dim3(256), 0, (hipStream_t)stream>>>((float*)ws, (int)nb, mixing_weights, n, idx, dmix);
@@ -572,7 +565,7 @@ extern "C" int dcpt_grid_add(float* g, const float* dfeat_c, int B, int lo, int 
     TapGeom tg;
     DCPT_TRY(tap_geom("grid_add", g, hi - lo, H, W, C, s, (int64_t)H * W * C, (int64_t)W * C, C, &tg));
     const int64_t nq = (int64_t)(hi - lo) * tg.Hc * tg.Wc * tg.nq;
-    grid_add_kernel<<<dim3(grid_for(nq)), dim3(256), 0, (hipStream_t)stream>>>(g + (int64_t)lo * H * W * C, dfeat_c, tg, nq);
+    grid_add_kernel<<<dim3(ew_grid_8k(nq)), dim3(256), 0, (hipStream_t)stream>>>(g + (int64_t)lo * H * W * C, dfeat_c, tg, nq);
     DCPT_CHECK_LAUNCH("grid_add");
     trace_tag("head.grid_add");
     return DCPT_OK;
@@ -584,7 +577,7 @@ extern "C" int dcpt_grid_scatter(const float* dfeat_c, float* out, int B, int lo
     TapGeom tg;
     DCPT_TRY(tap_geom("grid_scatter", out, B, H, W, C, s, (int64_t)H * W * C, (int64_t)W * C, C, &tg));
     const int64_t nq = (int64_t)B * H * W * (C / 4);
-    grid_scatter_kernel<<<dim3(grid_for(nq)), dim3(256), 0, (hipStream_t)stream>>>(dfeat_c, out, lo, hi, H, W, C / 4, s, nq);
+    grid_scatter_kernel<<<dim3(ew_grid_8k(nq)), dim3(256), 0, (hipStream_t)stream>>>(dfeat_c, out, lo, hi, H, W, C / 4, s, nq);
     DCPT_CHECK_LAUNCH("grid_scatter");
     trace_tag("head.grid_scatter");
     return DCPT_OK;
@@ -634,7 +627,7 @@ static int meanpool_fc_bwd_t(const float* dlogits, const float* pooled, const fl
     const int64_t mx = (int64_t)B * C > (int64_t)NC * C ? (int64_t)B * C : (int64_t)NC * C;
     fc_bwd_kernel<<<dim3((unsigned)cdiv64(mx, 256), 3), dim3(256), 0, s>>>(dlogits, pooled, fw, dxrow, dfw, dfb, B, C, NC, 1.0f / (float)P);
     DCPT_CHECK_LAUNCH("fc_bwd");
-    bcast_rows_kernel<ST><<<dim3(grid_for((int64_t)B * P * (C / 4))), dim3(256), 0, s>>>(dxrow, dx, B, P, C);
+    bcast_rows_kernel<ST><<<dim3(ew_grid_8k((int64_t)B * P * (C / 4))), dim3(256), 0, s>>>(dxrow, dx, B, P, C);
     DCPT_CHECK_LAUNCH("bcast_rows");
     return DCPT_OK;
 }
@@ -717,7 +710,7 @@ extern "C" int dcpt_patch_unfold(const float* x, float* A, int B, int Cin, int H
     DCPT_CHECK_ARG(Kp % 4 == 0 && Kp >= Cin * ksize * ksize + 1, "patch_unfold: Kp=%d must be a multiple of 4 and >= Cin*k*k + 1", Kp);
     const int Ho = (H + 2 * pad - ksize) / stride + 1, Wo = (W + 2 * pad - ksize) / stride + 1;
     DCPT_CHECK_ARG(Ho > 0 && Wo > 0, "patch_unfold: image smaller than the kernel");
-    patch_unfold_kernel<<<dim3(grid_for((int64_t)B * Ho * Wo * (Kp / 4))), dim3(256), 0, (hipStream_t)stream>>>(x, A, B, Cin, H, W, Ho, Wo, ksize,
+    patch_unfold_kernel<<<dim3(ew_grid_8k((int64_t)B * Ho * Wo * (Kp / 4))), dim3(256), 0, (hipStream_t)stream>>>(x, A, B, Cin, H, W, Ho, Wo, ksize,
                                                                                                           stride, pad, Kp);
     DCPT_CHECK_LAUNCH("patch_unfold");
     return DCPT_OK;
@@ -729,7 +722,7 @@ extern "C" int dcpt_patch_fold(const float* dA, float* dx, int B, int Cin, int H
     DCPT_CHECK_ARG(Kp % 4 == 0 && Kp >= Cin * ksize * ksize + 1, "patch_fold: Kp=%d must be a multiple of 4 and >= Cin*k*k + 1", Kp);
     const int Ho = (H + 2 * pad - ksize) / stride + 1, Wo = (W + 2 * pad - ksize) / stride + 1;
     DCPT_CHECK_ARG(Ho > 0 && Wo > 0, "patch_fold: image smaller than the kernel");
-    patch_fold_kernel<<<dim3(grid_for((int64_t)B * Cin * H * W)), dim3(256), 0, (hipStream_t)stream>>>(dA, dx, B, Cin, H, W, Ho, Wo, ksize, stride,
+    patch_fold_kernel<<<dim3(ew_grid_8k((int64_t)B * Cin * H * W)), dim3(256), 0, (hipStream_t)stream>>>(dA, dx, B, Cin, H, W, Ho, Wo, ksize, stride,
                                                                                                    pad, Kp);
     DCPT_CHECK_LAUNCH("patch_fold");
     return DCPT_OK;

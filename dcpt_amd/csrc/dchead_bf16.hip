@@ -12,13 +12,6 @@
 
 namespace {
 
-inline unsigned grid_for(int64_t n) {
-    int64_t nb = cdiv64(n, 256);
-    if (nb > 8192) nb = 8192;
-    if (nb < 1) nb = 1;
-    return (unsigned)nb;
-}
-
 __device__ __forceinline__ float4 ldb4(const bf16_t* p) { return bf4_unpack(*reinterpret_cast<const u32x2*>(p)); }
 __device__ __forceinline__ void stb4(bf16_t* p, float4 v) { *reinterpret_cast<u32x2*>(p) = bf4_pack(v); }
 
@@ -88,8 +81,6 @@ struct ConvWsB {
     bf16_t* dz;     // [M][Cout]  (backward)
     float* slab;
     float* lnpart;
-    int splits;
-    int64_t rps;
     int ln_nblk;     // blocks of the stand-alone LayerNorm backward (rows of lnpart it writes)
     int ln_tiles;    // 128-row tiles of the GEMM whose epilogue does that LayerNorm backward instead (rows of lnpart it writes)
     bool tn256;     // weight gradient on the 256 x 256-tile kernel + finisher (gemm_tn_bf16_256.hip)
@@ -100,7 +91,7 @@ struct ConvWsB {
 bool conv_tn256(int Cin, int Cout, int ks) { return gemm_tn_bf16_256_ok(Cout, ks * ks * Cin) && (ks == 1 || Cin % 128 == 0); }
 
 size_t conv_layout(int B, int H, int W, int Cin, int Cout, int ks, int backward, bool with_ln, void* base, size_t bytes, ConvWsB* out) {
-    WsAlloc a(base, base ? bytes : (size_t)-1);
+    WsAlloc a(base, bytes);
     ConvWsB w{};
     const int K = ks * ks * Cin;
     const int64_t M = (int64_t)B * H * W;
@@ -118,8 +109,9 @@ size_t conv_layout(int B, int H, int W, int Cin, int Cout, int ks, int backward,
             gemm_tn_bf16_256_plan(w.wg);
             q.slab = a.get<float>(gemm_tn_bf16_256_slab_floats(q));
         } else {
-            gemm_tn_bf16_plan(M, Cout, K, &w.splits, &w.rps);
-            w.slab = a.get<float>((size_t)w.splits * Cout * K);
+            size_t sl = 0;
+            wgrad_need_bf16(M, Cout, K, &sl, nullptr);
+            w.slab = a.get<float>(sl);
         }
         if (with_ln) {
             w.ln_nblk = ln_bwd_bf16_num_blocks(M, Cout);
@@ -134,38 +126,18 @@ size_t conv_layout(int B, int H, int W, int Cin, int Cout, int ks, int backward,
     return a.off;
 }
 
+// one operand image packed in the call (`pk` below = the cached images of bf16_ops.h, or nullptr: pack here)
 int pack(const float* w, bf16_t* out, int N, int K, int mode, hipStream_t s) {
     trace_tag("head.wpack_per_call");   // (not reached with the per-step cached images: dcpt_conv_wpack_bf16_multi)
-    WpackBJobs j{};
-    j.n = 1;
-    j.in[0] = w; j.out[0] = out; j.N[0] = N; j.K[0] = K; j.transpose[0] = mode;
-    return launch_wpack_bf16(j, s);
-}
-
-// A conv's two operand images as ONE cached buffer (dcpt_conv_wpack_bf16_multi, ABI 14): the forward image [Cout][ks ks Cin] at offset 0, the
-// data gradient's (transposed; flipped taps for the dense 3 x 3) at wpack_half_bytes.  `pk` below = that buffer or nullptr (pack in the call).
-size_t wpack_half_bytes(int Cin, int Cout, int ks) { return (((size_t)Cout * ks * ks * Cin * sizeof(bf16_t)) + 255) & ~(size_t)255; }
-inline const bf16_t* pk_fwd(const void* pk) { return static_cast<const bf16_t*>(pk); }
-inline const bf16_t* pk_bwd(const void* pk, int Cin, int Cout, int ks) {
-    return reinterpret_cast<const bf16_t*>(static_cast<const char*>(pk) + wpack_half_bytes(Cin, Cout, ks));
-}
-inline int pk_check(const void* pk, size_t pk_bytes, int Cin, int Cout, int ks, const char* who) {
-    DCPT_CHECK_ARG(pk == nullptr || pk_bytes >= 2 * wpack_half_bytes(Cin, Cout, ks), "%s: packed weights too small (dcpt_conv_wpack_bf16_bytes)", who);
-    return DCPT_OK;
+    return launch_wpack_bf16_one(w, out, N, K, mode, s);
 }
 
 // the forward GEMM of a conv (weights packed here unless the caller holds the cached images)
 int conv_fwd_problem(GemmNTB& g, const bf16_t* x, const float* w, bf16_t* z, const ConvWsB& cw, int B, int H, int W, int Cin, int Cout, int ks,
                      hipStream_t s, const void* pk) {
-    g = GemmNTB{};
-    g.M = (int64_t)B * H * W; g.A = x; g.N = Cout; g.C = z; g.ldc = Cout; g.Bw = pk ? pk_fwd(pk) : cw.wp;
-    if (ks == 1) {
-        if (!pk) DCPT_TRY(pack(w, cw.wp, Cout, Cin, 0, s));
-        g.lda = Cin; g.K = Cin;
-    } else {
-        if (!pk) DCPT_TRY(pack(w, cw.wp, Cout, 9 * Cin, 2, s));
-        g.K = 9 * Cin; g.conv3 = 1; g.gH = H; g.gW = W; g.gC = Cin;
-    }
+    if (!pk) DCPT_TRY(pack(w, cw.wp, Cout, ks * ks * Cin, ks == 1 ? 0 : 2, s));
+    const bf16_t* Bw = pk ? pk_fwd(pk) : cw.wp;
+    g = ks == 1 ? gemm_ntb_linear(x, Cin, (int64_t)B * H * W, Cin, Bw, Cout, z, Cout) : gemm_ntb_conv3(x, B, H, W, Cin, Bw, Cout, z, Cout);
     return DCPT_OK;
 }
 
@@ -217,8 +189,9 @@ int conv_bwd(const bf16_t* dz, const bf16_t* x, const float* w, bf16_t* dx, floa
              int ks, hipStream_t s, const FinCols* ln = nullptr, const bf16_t* dx_add = nullptr, const void* pk = nullptr,
              const LnBelow* below = nullptr) {
     const int64_t M = (int64_t)B * H * W;
-    GemmNTB g{};
-    g.M = M; g.A = dz; g.N = Cin; g.C = dx; g.ldc = Cin; g.Bw = pk ? pk_bwd(pk, Cin, Cout, ks) : cw.wp;
+    const bf16_t* Bw = pk ? pk_bwd(pk, Cin, Cout, ks) : cw.wp;
+    // dx = dz W: a linear layer on the rows of dz, or the 3 x 3 conv of dz with the transposed, tap-flipped image
+    GemmNTB g = ks == 1 ? gemm_ntb_linear(dz, Cout, M, Cout, Bw, Cin, dx, Cin) : gemm_ntb_conv3(dz, B, H, W, Cout, Bw, Cin, dx, Cin);
     g.res = dx_add; g.ldres = Cin;
     int EDX = dx_add ? EB_RESID : EB_PLAIN;   // dx = dx_add + dz W (the shortcut gradient of a bottleneck block rides in the epilogue)
     if (below) {   // the data gradient never reaches memory: the epilogue turns it into the gradient of the conv output below
@@ -229,44 +202,31 @@ int conv_bwd(const bf16_t* dz, const bf16_t* x, const float* w, bf16_t* dx, floa
         g.C = below->dz; g.aux = below->z; g.relu = below->lnb != nullptr; g.lnb = below->lnb; g.mu = below->mu; g.rstd = below->rstd; g.lnw = below->lnw; g.colpart = below->colpart;
         EDX = EB_LNBWDM;
     }
-    if (cw.tn256) {   // data gradient as before; the weight gradient as one 256-tile launch + one finisher launch (which also takes the LN sums)
-        if (!pk && dx) DCPT_TRY(pack(w, cw.wp, Cout, ks * ks * Cin, ks == 1 ? 1 : 3, s));
-        if (ks == 1) {
-            g.lda = Cout; g.K = Cout;
-        } else {
-            g.K = 9 * Cout; g.conv3 = 1; g.gH = H; g.gW = W; g.gC = Cout;
-        }
-        if (dx) DCPT_TRY(launch_gemm_nt_bf16(g, EDX, s));
+    // without the finisher (which takes the LN sums on the 256-tile path) they are reduced first, ahead of the pack
+    if (ln && !cw.tn256) DCPT_TRY(launch_colpart_reduce(ln->part, ln->R, 2, ln->C, ln->out0, ln->out1, nullptr, s));
+    if (dx) {
+        if (!pk) DCPT_TRY(pack(w, cw.wp, Cout, ks * ks * Cin, ks == 1 ? 1 : 3, s));
+        DCPT_TRY(launch_gemm_nt_bf16(g, EDX, s));
+    }
+    if (cw.tn256) {   // the weight gradient as one 256-tile launch + one finisher launch (which also takes the LN sums)
         GemmTNG wg = cw.wg;
         wg.p[0].X = dz; wg.p[0].Y = x;
         DCPT_TRY(launch_gemm_tn_bf16_256(wg, s));
         FinJobs f{};
         f.nslab = 1;
-        f.slab[0].slab = wg.p[0].slab; f.slab[0].N = Cout; f.slab[0].K = wg.p[0].K; f.slab[0].splits = wg.p[0].slots; f.slab[0].cs_rows = wg.p[0].splits;
-        f.slab[0].tiles_k = wg.p[0].tiles_k; f.slab[0].ks_div = 1; f.slab[0].dW = dw; f.slab[0].conv3 = ks == 3;
+        f.slab[0] = fin_slab(wg.p[0]);
+        f.slab[0].dW = dw; f.slab[0].conv3 = ks == 3;
         if (ln) {
             f.ncols = 1;
             f.cols[0] = *ln;
         }
         return launch_wgrad_finish(f, s);
     }
-    if (ln) DCPT_TRY(launch_colpart_reduce(ln->part, ln->R, 2, ln->C, ln->out0, ln->out1, nullptr, s));
     GemmTNB t{};
-    t.M = M; t.X = dz; t.ldx = Cout; t.N = Cout; t.Y = x; t.slab = cw.slab; t.colsum = nullptr; t.splits = cw.splits; t.rows_per_split = cw.rps;
-    if (ks == 1) {
-        if (!pk && dx) DCPT_TRY(pack(w, cw.wp, Cout, Cin, 1, s));
-        g.lda = Cout; g.K = Cout;
-        if (dx) DCPT_TRY(launch_gemm_nt_bf16(g, EDX, s));
-        t.ldy = Cin; t.K = Cin;
-        DCPT_TRY(launch_gemm_tn_bf16(t, s));
-        return launch_wgrad_reduce(cw.slab, nullptr, cw.splits, 0, Cout, Cin, nullptr, nullptr, nullptr, dw, nullptr, nullptr, WR_PLAIN, s);
+    if (ks == 3) {
+        t.yconv = 1; t.gH = H; t.gW = W; t.gC = Cin;
     }
-    if (!pk && dx) DCPT_TRY(pack(w, cw.wp, Cout, 9 * Cin, 3, s));
-    g.K = 9 * Cout; g.conv3 = 1; g.gH = H; g.gW = W; g.gC = Cout;
-    if (dx) DCPT_TRY(launch_gemm_nt_bf16(g, EDX, s));
-    t.K = 9 * Cin; t.yconv = 1; t.gH = H; t.gW = W; t.gC = Cin; t.ldy = Cin;
-    DCPT_TRY(launch_gemm_tn_bf16(t, s));
-    return launch_wgrad_reduce(cw.slab, nullptr, cw.splits, 0, Cout, 9 * Cin, nullptr, nullptr, nullptr, dw, nullptr, nullptr, WR_CONV3, s);
+    return launch_wgrad_bf16(t, dz, Cout, Cout, x, Cin, ks * ks * Cin, M, cw.slab, nullptr, dw, nullptr, ks == 3 ? WR_CONV3 : WR_PLAIN, s);
 }
 
 bool conv_shape_ok(int Cin, int Cout, int ks) { return (ks == 1 || ks == 3) && Cin % 8 == 0 && Cout % 8 == 0 && Cout <= 1024; }
@@ -338,7 +298,7 @@ size_t bneck_layout(int B, int H, int W, int C, int backward, void* base, size_t
         off += align_up(conv_layout(B, H, W, gm.Cin[k], gm.Cout[k], gm.ks[k], backward, true, b, left, &w.cw[k]), 256);
     }
     if (backward) {
-        WsAlloc a(base ? static_cast<char*>(base) + off : nullptr, base ? (bytes > off ? bytes - off : 0) : (size_t)-1);
+        WsAlloc a(base ? static_cast<char*>(base) + off : nullptr, bytes > off ? bytes - off : 0);
         w.dshort = a.get<bf16_t>((size_t)M * C);
         const bool all_fused = conv_bwd_below_ok(M, gm.Cin[2], gm.Cout[2], 1) && conv_bwd_below_ok(M, gm.Cin[1], gm.Cout[1], 3);
         if (!all_fused) w.dybuf = a.get<bf16_t>((size_t)M * 2 * C);
@@ -436,7 +396,7 @@ extern "C" int dcpt_conv1x1_pool_relu_fwd_bf16(const uint16_t* x, const float* w
     const size_t need = conv_layout(B, H, W, Cin, Cout, 1, 0, false, ws, ws_bytes, &cw);
     DCPT_CHECK_WS("conv1x1_pool_relu_fwd_bf16", ws, ws_bytes, need);
     DCPT_TRY(conv_fwd(x, w, z, cw, B, H, W, Cin, Cout, 1, s, wpacked));
-    pool_relu_fwd_bf16_kernel<<<dim3(grid_for((int64_t)B * (H / 2) * (W / 2) * (Cout / 4))), dim3(256), 0, s>>>(z, y, B, H, W, Cout);
+    pool_relu_fwd_bf16_kernel<<<dim3(ew_grid_8k((int64_t)B * (H / 2) * (W / 2) * (Cout / 4))), dim3(256), 0, s>>>(z, y, B, H, W, Cout);
     DCPT_CHECK_LAUNCH("pool_relu_fwd_bf16");
     return DCPT_OK;
 }
@@ -451,7 +411,7 @@ extern "C" int dcpt_conv1x1_pool_relu_bwd_bf16(const uint16_t* dy, const uint16_
     ConvWsB cw;
     const size_t need = conv_layout(B, H, W, Cin, Cout, 1, 1, false, ws, ws_bytes, &cw);
     DCPT_CHECK_WS("conv1x1_pool_relu_bwd_bf16", ws, ws_bytes, need);
-    pool_relu_bwd_bf16_kernel<<<dim3(grid_for((int64_t)B * (H / 2) * (W / 2) * (Cout / 4))), dim3(256), 0, s>>>(z, dy, cw.dz, B, H, W, Cout);
+    pool_relu_bwd_bf16_kernel<<<dim3(ew_grid_8k((int64_t)B * (H / 2) * (W / 2) * (Cout / 4))), dim3(256), 0, s>>>(z, dy, cw.dz, B, H, W, Cout);
     DCPT_CHECK_LAUNCH("pool_relu_bwd_bf16");
     return conv_bwd(cw.dz, x, w, dx, dw, cw, B, H, W, Cin, Cout, 1, s, nullptr, nullptr, wpacked);
 }
@@ -477,11 +437,8 @@ extern "C" int dcpt_conv_wpack_bf16_multi(const float* const* w, void* const* pa
             if ((ksize[i] == 3) != (pass == 0)) continue;
             const int K = ksize[i] * ksize[i] * Cin[i];
             for (int f = 0; f < 2; ++f) {
-                j.in[j.n] = w[i];
-                j.out[j.n] = f == 0 ? const_cast<bf16_t*>(pk_fwd(packed[i])) : const_cast<bf16_t*>(pk_bwd(packed[i], Cin[i], Cout[i], ksize[i]));
-                j.N[j.n] = Cout[i]; j.K[j.n] = K;
-                j.transpose[j.n] = (ksize[i] == 1 ? 0 : 2) + f;
-                ++j.n;
+                bf16_t* out = const_cast<bf16_t*>(f == 0 ? pk_fwd(packed[i]) : pk_bwd(packed[i], Cin[i], Cout[i], ksize[i]));
+                wpack_job(j, j.n++, w[i], out, Cout[i], K, (ksize[i] == 1 ? 0 : 2) + f);
             }
             if (j.n == WPACKB_MAX_JOBS_L) {
                 DCPT_TRY(launch_wpack_bf16(j, s, pass == 0 ? 1024 : 256));

@@ -64,21 +64,25 @@ static inline int dcpt_tuning(const char* name, int dflt) {
 
 static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
-// grid of a 256-thread grid-stride element-wise kernel over n elements (not kernels.h's grid_for: that one has another block cap)
-static inline unsigned ew_grid(int64_t n) {
+// grid of a 256-thread grid-stride element-wise kernel over n elements: at most 16384 blocks, or 8192 (ew_grid_8k: the classifier head's
+// kernels in dchead.hip / dchead_bf16.hip; dcpt_mix_bwd_ws_bytes is sized by it).  bf16_ops.hip's private grid_for is a third cap (4096).
+static inline unsigned ew_grid_cap(int64_t n, int64_t cap) {
     int64_t nb = cdiv64(n, 256);
-    if (nb > 16384) nb = 16384;
+    if (nb > cap) nb = cap;
     return (unsigned)(nb < 1 ? 1 : nb);
 }
+static inline unsigned ew_grid(int64_t n) { return ew_grid_cap(n, 16384); }
+static inline unsigned ew_grid_8k(int64_t n) { return ew_grid_cap(n, 8192); }
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
-// Bump allocator over a caller-owned workspace (the caller -- PyTorch -- owns every buffer).
+// Bump allocator over a caller-owned workspace (the caller -- PyTorch -- owns every buffer).  A null base is a size query: nothing is
+// handed out that could be written, the capacity is unbounded and `off` ends as the bytes the layout needs.
 struct WsAlloc {
     char* base;
     size_t cap;
     size_t off;
     bool ok;
-    WsAlloc(void* p, size_t bytes) : base((char*)p), cap(bytes), off(0), ok(true) {}
+    WsAlloc(void* p, size_t bytes) : base((char*)p), cap(p ? bytes : (size_t)-1), off(0), ok(true) {}
     template <typename T>
     T* get(size_t n) {
         size_t bytes = align_up(n * sizeof(T), 256);

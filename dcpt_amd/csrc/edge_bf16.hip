@@ -15,20 +15,19 @@ struct EdgeWsB {
     bf16_t* wp;      // packed bf16 weight of the launch
     float* slab;
     float* colsum;
-    int splits;
-    int64_t rps;
 };
 
 // down: weight [2C][C][2][2]; forward pack [2C][4C], backward pack [4C][2C]; wgrad slabs [splits][2C][4C]
 size_t down_layout_b(int B, int H, int W, int C, int backward, void* base, size_t bytes, EdgeWsB* out) {
-    WsAlloc a(base, base ? bytes : (size_t)-1);
+    WsAlloc a(base, bytes);
     EdgeWsB w{};
     w.wp = a.get<bf16_t>((size_t)8 * C * C);
     if (backward) {
         const int64_t Mc = (int64_t)B * (H / 2) * (W / 2);
-        gemm_tn_bf16_plan(Mc, 2 * C, 4 * C, &w.splits, &w.rps);
-        w.slab = a.get<float>((size_t)w.splits * 8 * C * C);
-        w.colsum = a.get<float>((size_t)w.splits * gemm_tn_bf16_tiles_k(2 * C, 4 * C) * 2 * C);
+        size_t sl = 0, cs = 0;
+        wgrad_need_bf16(Mc, 2 * C, 4 * C, &sl, &cs);
+        w.slab = a.get<float>(sl);
+        w.colsum = a.get<float>(cs);
     }
     if (out) *out = w;
     return a.off;
@@ -36,21 +35,16 @@ size_t down_layout_b(int B, int H, int W, int C, int backward, void* base, size_
 
 // up: weight [2C][C]; forward pack [2C][C] (rows permuted to (i, j)-major), backward pack [C][2C]; wgrad slabs [splits][2C][C]
 size_t up_layout_b(int B, int H, int W, int C, int backward, void* base, size_t bytes, EdgeWsB* out) {
-    WsAlloc a(base, base ? bytes : (size_t)-1);
+    WsAlloc a(base, bytes);
     EdgeWsB w{};
     w.wp = a.get<bf16_t>((size_t)2 * C * C);
     if (backward) {
-        gemm_tn_bf16_plan((int64_t)B * H * W, 2 * C, C, &w.splits, &w.rps);
-        w.slab = a.get<float>((size_t)w.splits * 2 * C * C);
+        size_t sl = 0;
+        wgrad_need_bf16((int64_t)B * H * W, 2 * C, C, &sl, nullptr);
+        w.slab = a.get<float>(sl);
     }
     if (out) *out = w;
     return a.off;
-}
-
-int pack1(const float* w, bf16_t* out, int N, int K, int mode, hipStream_t s) {
-    WpackBJobs j{};
-    j.in[0] = w; j.out[0] = out; j.N[0] = N; j.K[0] = K; j.nimg[0] = 1; j.transpose[0] = mode; j.n = 1;
-    return launch_wpack_bf16(j, s);
 }
 
 }  // namespace
@@ -68,7 +62,7 @@ extern "C" int dcpt_down2x2_fwd_bf16(const uint16_t* x, const float* w, const fl
     EdgeWsB d;
     const size_t need = down_layout_b(B, H, W, C, 0, ws, ws_bytes, &d);
     DCPT_CHECK_WS("down2x2_fwd_bf16", ws, ws_bytes, need);
-    DCPT_TRY(pack1(w, d.wp, 2 * C, 4 * C, 4, s));
+    DCPT_TRY(launch_wpack_bf16_one(w, d.wp, 2 * C, 4 * C, 4, s));
     GemmNTB g{};
     g.M = (int64_t)B * (H / 2) * (W / 2);
     g.A = x; g.K = 4 * C; g.gather2 = 1; g.gH = H / 2; g.gW = W / 2; g.gC = C;
@@ -86,19 +80,15 @@ extern "C" int dcpt_down2x2_bwd_bf16(const uint16_t* dy, const uint16_t* x, cons
     DCPT_CHECK_WS("down2x2_bwd_bf16", ws, ws_bytes, need);
     const int64_t Mc = (int64_t)B * (H / 2) * (W / 2);
     // dx (fine) = scatter(dy [Mc][2C] x Wp^T):  Bw [N = 4C][K = 2C]
-    DCPT_TRY(pack1(w, d.wp, 2 * C, 4 * C, 5, s));
-    GemmNTB g{};
-    g.M = Mc; g.A = dy; g.lda = 2 * C; g.K = 2 * C; g.Bw = d.wp; g.N = 4 * C; g.C = dx; g.ldc = 4 * C;
+    DCPT_TRY(launch_wpack_bf16_one(w, d.wp, 2 * C, 4 * C, 5, s));
+    GemmNTB g = gemm_ntb_linear(dy, 2 * C, Mc, 2 * C, d.wp, 4 * C, dx, 4 * C);
     g.gH = H / 2; g.gW = W / 2; g.gC = C;
     g.res = dx_add;   // (the skip connection's gradient joins in the scatter epilogue)
     DCPT_TRY(launch_gemm_nt_bf16(g, dx_add ? EB_SCATTER_ADD : EB_SCATTER, s));
     // dW packed [2C][4C] = sum_m dy[m][oc] * gather(x)[m][k'],  db = column sums of dy
     GemmTNB t{};
-    t.M = Mc; t.X = dy; t.ldx = 2 * C; t.N = 2 * C; t.Y = x; t.ldy = 4 * C; t.K = 4 * C; t.yg2 = 1; t.gH = H / 2; t.gW = W / 2; t.gC = C;
-    t.slab = d.slab; t.colsum = d.colsum; t.splits = d.splits; t.rows_per_split = d.rps;
-    DCPT_TRY(launch_gemm_tn_bf16(t, s));
-    return launch_wgrad_reduce(d.slab, d.colsum, d.splits, d.splits * gemm_tn_bf16_tiles_k(2 * C, 4 * C), 2 * C, 4 * C, nullptr, nullptr, nullptr, dw,
-                               nullptr, dbias, WR_DOWN, s);
+    t.yg2 = 1; t.gH = H / 2; t.gW = W / 2; t.gC = C;
+    return launch_wgrad_bf16(t, dy, 2 * C, 2 * C, x, 4 * C, 4 * C, Mc, d.slab, d.colsum, dw, dbias, WR_DOWN, s);
 }
 
 // ---- up: x [B][H][W][C] -> y [B][2H][2W][C/2] = PixelShuffle2(conv1x1(x)) + skip ---------------------------------------------
@@ -112,9 +102,8 @@ extern "C" int dcpt_up_ps_fwd_bf16(const uint16_t* x, const float* w, const uint
     EdgeWsB u;
     const size_t need = up_layout_b(B, H, W, C, 0, ws, ws_bytes, &u);
     DCPT_CHECK_WS("up_ps_fwd_bf16", ws, ws_bytes, need);
-    DCPT_TRY(pack1(w, u.wp, 2 * C, C, 6, s));
-    GemmNTB g{};
-    g.M = (int64_t)B * H * W; g.A = x; g.lda = C; g.K = C; g.Bw = u.wp; g.N = 2 * C; g.C = y; g.ldc = 2 * C;
+    DCPT_TRY(launch_wpack_bf16_one(w, u.wp, 2 * C, C, 6, s));
+    GemmNTB g = gemm_ntb_linear(x, C, (int64_t)B * H * W, C, u.wp, 2 * C, y, 2 * C);
     g.gH = H; g.gW = W; g.gC = C / 2; g.res = skip;
     return launch_gemm_nt_bf16(g, skip ? EB_SCATTER_ADD : EB_SCATTER, s);
 }
@@ -129,16 +118,14 @@ extern "C" int dcpt_up_ps_bwd_bf16(const uint16_t* dy, const uint16_t* x, const 
     DCPT_CHECK_WS("up_ps_bwd_bf16", ws, ws_bytes, need);
     const int64_t M = (int64_t)B * H * W;
     // dx[m][ic] = sum_n' gather(dy)[m][n'] * Wp[n'][ic]:  Bw [N = C][K = 2C] = Wp^T
-    DCPT_TRY(pack1(w, u.wp, 2 * C, C, 7, s));
+    DCPT_TRY(launch_wpack_bf16_one(w, u.wp, 2 * C, C, 7, s));
     GemmNTB g{};
     g.M = M; g.A = dy; g.K = 2 * C; g.gather2 = 1; g.gH = H; g.gW = W; g.gC = C / 2; g.Bw = u.wp; g.N = C; g.C = dx; g.ldc = C;
     DCPT_TRY(launch_gemm_nt_bf16(g, EB_PLAIN, s));
     // dW packed [2C][C] = sum_m gather(dy)[m][n'] * x[m][ic]
     GemmTNB t{};
-    t.M = M; t.X = dy; t.ldx = 2 * C; t.N = 2 * C; t.xg2 = 1; t.Y = x; t.ldy = C; t.K = C; t.gH = H; t.gW = W; t.gC = C / 2;
-    t.slab = u.slab; t.colsum = nullptr; t.splits = u.splits; t.rows_per_split = u.rps;
-    DCPT_TRY(launch_gemm_tn_bf16(t, s));
-    return launch_wgrad_reduce(u.slab, nullptr, u.splits, 0, 2 * C, C, nullptr, nullptr, nullptr, dw, nullptr, nullptr, WR_UP, s);
+    t.xg2 = 1; t.gH = H; t.gW = W; t.gC = C / 2;
+    return launch_wgrad_bf16(t, dy, 2 * C, 2 * C, x, C, C, M, u.slab, nullptr, dw, nullptr, WR_UP, s);
 }
 
 // ---- intro-type conv: image NCHW fp32 (Cin <= 4) -> features NHWC bf16 ---------------------------------------------------------

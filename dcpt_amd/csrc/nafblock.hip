@@ -30,7 +30,7 @@ struct FwdWs {
 };
 
 size_t fwd_ws_layout(int B, int H, int W, int C, void* base, size_t bytes, FwdWs* out) {
-    WsAlloc a(base, base ? bytes : (size_t)-1);
+    WsAlloc a(base, bytes);
     DwGeom g{B, H, W, C};
     const int nblk = dw_ring_num_blocks_per_image(g, 4);
     float* w2p = a.get<float>((size_t)9 * 2 * C);
@@ -60,7 +60,7 @@ struct BwdWs {
 bool ln_in_epilogue(int C);
 bool ffn_fused_f32(int C);
 size_t bwd_ws_layout(int B, int H, int W, int C, void* base, size_t bytes, BwdWs* out) {
-    WsAlloc a(base, base ? bytes : (size_t)-1);
+    WsAlloc a(base, bytes);
     const int64_t M = (int64_t)B * H * W;
     const int P = H * W;
     DwGeom g{B, H, W, C};
@@ -365,7 +365,7 @@ struct LocalWs {
     int nblk_pool;
 };
 size_t local_layout(int B, int H, int W, int C, int k2, void* base, size_t bytes, LocalWs* out) {
-    WsAlloc a(base, base ? bytes : (size_t)-1);
+    WsAlloc a(base, bytes);
     const int64_t M = (int64_t)B * H * W;
     DwGeom g{B, H, W, C};
     LocalWs w{};

@@ -61,7 +61,7 @@ struct FwdWsB {
 bool conv3_scale_activations(int P, int C) { return P < 2 * C; }
 
 size_t fwd_layout(int B, int H, int W, int C, void* base, size_t bytes, FwdWsB* out) {
-    WsAlloc a(base, base ? bytes : (size_t)-1);
+    WsAlloc a(base, bytes);
     DwGeom g{B, H, W, C};
     FwdWsB w{};
     w.nblk_pool = dw_ring_num_blocks_per_image(g, 2);
@@ -127,7 +127,7 @@ bool plan_wg256(int64_t M, int C, int P, GemmTNG* g, bool* conv3_images) {
 }
 
 size_t bwd_layout(int B, int H, int W, int C, void* base, size_t bytes, BwdWsB* out) {
-    WsAlloc a(base, base ? bytes : (size_t)-1);
+    WsAlloc a(base, bytes);
     const int64_t M = (int64_t)B * H * W;
     const int P = H * W;
     DwGeom g{B, H, W, C};
@@ -144,19 +144,16 @@ size_t bwd_layout(int B, int H, int W, int C, void* base, size_t bytes, BwdWsB* 
     w.dts = a.get<bf16_t>((size_t)M * C);
     w.dt1 = a.get<bf16_t>((size_t)M * 2 * C);
     w.t2s = a.get<bf16_t>((size_t)M * C);
-    int sp1, sp2, sp3;
-    int64_t r1, r2, r3;
-    gemm_tn_bf16_plan(M, 2 * C, C, &sp1, &r1);
-    gemm_tn_bf16_plan(M, C, C, &sp2, &r2);
-    size_t slab1 = (size_t)sp1 * 2 * C * C, slab2 = (size_t)sp2 * C * C;
-    size_t cs1 = (size_t)sp1 * gemm_tn_bf16_tiles_k(2 * C, C) * 2 * C, cs2 = (size_t)sp2 * gemm_tn_bf16_tiles_k(C, C) * C;
+    // one slab / column-sum buffer for the [2C][C] and [C][C] gradients in turn, and for conv3's per-image plan (B7) where there is one
+    wgrad_need_bf16(M, 2 * C, C, &w.slab_elems, &w.colsum_elems);
+    wgrad_need_bf16(M, C, C, &w.slab_elems, &w.colsum_elems);
+    int sp3;
+    int64_t r3;
     if (gemm_tn_bf16_plan_images(M, C, C, P, &sp3, &r3)) {
         const size_t s3 = (size_t)sp3 * C * C, c3 = (size_t)sp3 * gemm_tn_bf16_tiles_k(C, C) * C;
-        if (s3 > slab2) slab2 = s3;
-        if (c3 > cs2) cs2 = c3;
+        if (s3 > w.slab_elems) w.slab_elems = s3;
+        if (c3 > w.colsum_elems) w.colsum_elems = c3;
     }
-    w.slab_elems = slab1 > slab2 ? slab1 : slab2;
-    w.colsum_elems = cs1 > cs2 ? cs1 : cs2;
     w.tn256 = !ffn_fused(C) && plan_wg256(M, C, P, &w.wg, &w.conv3_images);
     if (w.tn256) {
         w.slab_elems = w.colsum_elems = 0;
@@ -201,17 +198,6 @@ size_t bwd_layout(int B, int H, int W, int C, void* base, size_t bytes, BwdWsB* 
     return a.off;
 }
 
-// G[n][k] = sum_m X[m][n] Y[m][k] into fp32 slabs, then dW = rowscale * sum(slabs) (+ gain / bias gradients) -- fp32 reducer of misc.hip
-int wgrad_b(const bf16_t* X, int N, const bf16_t* Y, int K, int64_t M, float* slab, float* colsum, const float* rowscale, const float* Wfor_gain,
-            const float* wbias, float* dW, float* dgain, float* dbias, hipStream_t s) {
-    GemmTNB t{};
-    t.X = X; t.ldx = N; t.N = N; t.Y = Y; t.ldy = K; t.K = K; t.M = M; t.slab = slab; t.colsum = colsum;
-    gemm_tn_bf16_plan(M, N, K, &t.splits, &t.rows_per_split);
-    DCPT_TRY(launch_gemm_tn_bf16(t, s));
-    return launch_wgrad_reduce(slab, colsum, t.splits, t.splits * gemm_tn_bf16_tiles_k(N, K), N, K, rowscale, Wfor_gain, wbias, dW, dgain, dbias,
-                               WR_PLAIN, s);
-}
-
 bool shape_ok(int B, int H, int W, int C) { return B > 0 && B <= 65535 && H > 0 && W > 0 && C > 0 && C % 8 == 0 && C <= 1024; }
 
 // The operand copies of a block's weights that depend on the PARAMETERS only (not on activations): bf16 [N][K] copies for the forward
@@ -223,7 +209,7 @@ struct PackB {
     float* w2p;
 };
 size_t pack_layout(int C, void* base, size_t bytes, PackB* out) {
-    WsAlloc a(base, base ? bytes : (size_t)-1);
+    WsAlloc a(base, bytes);
     PackB k{};
     k.W1 = a.get<bf16_t>((size_t)2 * C * C);
     k.W4 = a.get<bf16_t>((size_t)2 * C * C);
@@ -244,21 +230,20 @@ constexpr int PACK_JOBS = 12;   // jobs of one block at most
 template <typename J>
 int pack_jobs(const dcpt_nafblock_params* p, const PackB& k, int C, J& j, int b) {   // the block's nine or ten jobs at j[b ..]; returns their number
     const int C2 = 2 * C;
-    if (k.Wf) {
-        j.in[b + 9] = p->conv4_w; j.rs[b + 9] = p->conv5_w; j.out[b + 9] = k.Wf; j.N[b + 9] = 3 * C; j.K[b + 9] = C; j.transpose[b + 9] = 9;
-        j.in[b + 10] = p->conv1_w; j.rs[b + 10] = nullptr; j.out[b + 10] = k.Wf1; j.N[b + 10] = 2 * C; j.K[b + 10] = C; j.transpose[b + 10] = 9;
-        j.in[b + 11] = p->conv3_w; j.rs[b + 11] = p->beta; j.out[b + 11] = k.WfT3; j.N[b + 11] = C; j.K[b + 11] = C; j.transpose[b + 11] = 10;
-    }
-    j.in[b + 8] = p->conv3_w; j.out[b + 8] = k.W3; j.N[b + 8] = C; j.K[b + 8] = C;
-    j.in[b + 0] = p->conv1_w; j.out[b + 0] = k.W1; j.N[b + 0] = C2; j.K[b + 0] = C;
-    j.in[b + 1] = p->conv4_w; j.out[b + 1] = k.W4; j.N[b + 1] = C2; j.K[b + 1] = C;
-    j.in[b + 2] = p->conv5_w; j.out[b + 2] = k.W5; j.N[b + 2] = C; j.K[b + 2] = C;
-    j.in[b + 3] = p->conv5_w; j.out[b + 3] = k.wT5; j.rs[b + 3] = p->gamma; j.N[b + 3] = C;  j.K[b + 3] = C; j.transpose[b + 3] = 1;
-    j.in[b + 4] = p->conv4_w; j.out[b + 4] = k.wT4; j.rs[b + 4] = nullptr;  j.N[b + 4] = C2; j.K[b + 4] = C; j.transpose[b + 4] = 1;
-    j.in[b + 5] = p->conv3_w; j.out[b + 5] = k.wT3; j.rs[b + 5] = p->beta;  j.N[b + 5] = C;  j.K[b + 5] = C; j.transpose[b + 5] = 1;
-    j.in[b + 6] = p->conv1_w; j.out[b + 6] = k.wT1; j.rs[b + 6] = nullptr;  j.N[b + 6] = C2; j.K[b + 6] = C; j.transpose[b + 6] = 1;
-    j.in[b + 7] = p->conv2_w; j.out[b + 7] = reinterpret_cast<bf16_t*>(k.w2p); j.N[b + 7] = C2; j.K[b + 7] = 9; j.transpose[b + 7] = 8;
-    return k.Wf ? 12 : 9;
+    wpack_job(j, b + 0, p->conv1_w, k.W1, C2, C, 0);
+    wpack_job(j, b + 1, p->conv4_w, k.W4, C2, C, 0);
+    wpack_job(j, b + 2, p->conv5_w, k.W5, C, C, 0);
+    wpack_job(j, b + 3, p->conv5_w, k.wT5, C, C, 1, p->gamma);
+    wpack_job(j, b + 4, p->conv4_w, k.wT4, C2, C, 1);
+    wpack_job(j, b + 5, p->conv3_w, k.wT3, C, C, 1, p->beta);
+    wpack_job(j, b + 6, p->conv1_w, k.wT1, C2, C, 1);
+    wpack_job(j, b + 7, p->conv2_w, reinterpret_cast<bf16_t*>(k.w2p), C2, 9, 8);
+    wpack_job(j, b + 8, p->conv3_w, k.W3, C, C, 0);
+    if (!k.Wf) return 9;
+    wpack_job(j, b + 9, p->conv4_w, k.Wf, 3 * C, C, 9, p->conv5_w);
+    wpack_job(j, b + 10, p->conv1_w, k.Wf1, 2 * C, C, 9);
+    wpack_job(j, b + 11, p->conv3_w, k.WfT3, C, C, 10, p->beta);
+    return 12;
 }
 int pack_all(const dcpt_nafblock_params* p, const PackB& k, int C, hipStream_t s) {
     WpackBJobs j{};
@@ -332,8 +317,8 @@ int fwd_head_bf16(const dcpt_nafblock_params* p, const bf16_t* inp, const HeadB&
         DCPT_TRY(launch_chain_head_bf16(f, C, s));
     } else {
         DCPT_TRY(launch_ln_fwd_bf16(inp, p->norm1_w, p->norm1_b, h.xn1, h.mu1, h.rstd1, M, C, eps, s));
-        GemmNTB g{};
-        g.M = M; g.A = h.xn1; g.lda = C; g.K = C; g.Bw = h.W1; g.N = 2 * C; g.C = h.t1; g.ldc = 2 * C; g.bias = p->conv1_b;
+        GemmNTB g = gemm_ntb_linear(h.xn1, C, M, C, h.W1, 2 * C, h.t1, 2 * C);
+        g.bias = p->conv1_b;
         DCPT_TRY(launch_gemm_nt_bf16(g, EB_BIAS, s));
     }
     DwGeom dg{B, H, W, C};
@@ -368,12 +353,11 @@ int fwd_ffn_bf16(const dcpt_nafblock_params* p, bf16_t* y, bf16_t* out, const Ta
     bf16_t* const xn2 = t.xn2 ? t.xn2 : t.xn2_ws;
     bf16_t* const gt = t.g ? t.g : t.g_ws;
     DCPT_TRY(launch_ln_fwd_bf16(y, p->norm2_w, p->norm2_b, xn2, t.mu2 ? t.mu2 : t.mu2_ws, t.rstd2 ? t.rstd2 : t.rstd2_ws, M, C, eps, s));
-    GemmNTB g{};
-    g.M = M; g.A = xn2; g.lda = C; g.K = C; g.Bw = t.W4; g.N = 2 * C; g.C = t.v; g.ldc = 2 * C; g.bias = p->conv4_b; g.gate = gt;
+    GemmNTB g = gemm_ntb_linear(xn2, C, M, C, t.W4, 2 * C, t.v, 2 * C);
+    g.bias = p->conv4_b; g.gate = gt;
     DCPT_TRY(launch_gemm_nt_bf16(g, EB_BIASGATE, s));
-    g = GemmNTB{};
-    g.M = M; g.A = gt; g.lda = C; g.K = C; g.Bw = t.W5; g.N = C; g.C = out; g.ldc = C; g.bias = p->conv5_b; g.res = y; g.ldres = C;
-    g.cscale = p->gamma;
+    g = gemm_ntb_linear(gt, C, M, C, t.W5, C, out, C);
+    g.bias = p->conv5_b; g.res = y; g.ldres = C; g.cscale = p->gamma;
     return launch_gemm_nt_bf16(g, EB_RESID, s);
 }
 }  // namespace
@@ -404,22 +388,16 @@ static int nafblock_fwd_bf16_impl(const dcpt_nafblock_params* p, const uint16_t*
         if (w.scale_act) w.W3 = k.W3;
     } else {
         j.n = 3;
-        if (w.scale_act) {
-            j.in[j.n] = p->conv3_w; j.out[j.n] = w.W3; j.N[j.n] = C; j.K[j.n] = C;
-            ++j.n;
-        }
+        wpack_job(j, 0, p->conv1_w, w.W1, 2 * C, C, 0);
+        wpack_job(j, 1, p->conv4_w, w.W4, 2 * C, C, 0);
+        wpack_job(j, 2, p->conv5_w, w.W5, C, C, 0);
+        if (w.scale_act) wpack_job(j, j.n++, p->conv3_w, w.W3, C, C, 0);
         if (w.Wf) {
-            j.in[j.n] = p->conv4_w; j.rs[j.n] = p->conv5_w; j.out[j.n] = w.Wf; j.N[j.n] = 3 * C; j.K[j.n] = C; j.transpose[j.n] = 9;
-            ++j.n;
-            j.in[j.n] = p->conv1_w; j.rs[j.n] = nullptr; j.out[j.n] = w.Wf1; j.N[j.n] = 2 * C; j.K[j.n] = C; j.transpose[j.n] = 9;
-            ++j.n;
+            wpack_job(j, j.n++, p->conv4_w, w.Wf, 3 * C, C, 9, p->conv5_w);
+            wpack_job(j, j.n++, p->conv1_w, w.Wf1, 2 * C, C, 9);
         }
-        j.in[0] = p->conv1_w; j.out[0] = w.W1; j.N[0] = 2 * C; j.K[0] = C;
-        j.in[1] = p->conv4_w; j.out[1] = w.W4; j.N[1] = 2 * C; j.K[1] = C;
-        j.in[2] = p->conv5_w; j.out[2] = w.W5; j.N[2] = C; j.K[2] = C;
         DCPT_TRY(launch_wpack_bf16(j, s));
     }
-    GemmNTB g{};
     {
         HeadB h{};
         h.W1 = w.W1; h.Wf1 = w.Wf1; h.w2p = w.w2p; h.pack_dw = !packed; h.t1 = sv->t1; h.xn1 = sv->xn1; h.t2 = sv->t2; h.mu1 = sv->mu1;
@@ -427,22 +405,22 @@ static int nafblock_fwd_bf16_impl(const dcpt_nafblock_params* p, const uint16_t*
         DCPT_TRY(fwd_head_bf16(p, inp, h, B, H, W, C, s));
     }
     DCPT_TRY(launch_sca_fwd(w.pool_part, w.nblk_pool, p->sca_w, p->sca_b, sv->pooled, sv->s, B, C, P, s));
-    g = GemmNTB{};
+    GemmNTB g;
     if (w.scale_act) {
         // y = inp + (conv3(t2 * s) + b3) * beta with the scale on the activations (small images): one pass over t2, one GEMM
         DCPT_TRY(launch_scale_rows_bf16(sv->t2, sv->s, w.t2s, M, C, P, s));
-        g.M = M; g.A = w.t2s; g.lda = C; g.K = C; g.Bw = w.W3; g.N = C; g.C = sv->y; g.ldc = C; g.bias = p->conv3_b;
-        g.res = inp; g.ldres = C; g.cscale = p->beta;
+        g = gemm_ntb_linear(w.t2s, C, M, C, w.W3, C, sv->y, C);
     } else {
         // ... with the per-image scale in the weights, one GEMM problem per image
         j = WpackBJobs{};
         j.n = 1;
-        j.in[0] = p->conv3_w; j.out[0] = w.W3s; j.N[0] = C; j.K[0] = C; j.kscale[0] = sv->s; j.nimg[0] = B;
+        wpack_job(j, 0, p->conv3_w, w.W3s, C, C, 0);
+        j.kscale[0] = sv->s; j.nimg[0] = B;
         DCPT_TRY(launch_wpack_bf16(j, s));
-        g.M = P; g.A = sv->t2; g.lda = C; g.K = C; g.Bw = w.W3s; g.N = C; g.C = sv->y; g.ldc = C; g.bias = p->conv3_b;
-        g.res = inp; g.ldres = C; g.cscale = p->beta;
+        g = gemm_ntb_linear(sv->t2, C, P, C, w.W3s, C, sv->y, C);
         g.nb = B; g.sA = (int64_t)P * C; g.sB = (int64_t)C * C; g.sC = (int64_t)P * C; g.sR = (int64_t)P * C;
     }
+    g.bias = p->conv3_b; g.res = inp; g.ldres = C; g.cscale = p->beta;
     DCPT_TRY(launch_gemm_nt_bf16(g, EB_RESID, s));
     TailB t{};
     t.W4 = w.W4; t.W5 = w.W5; t.Wf = w.Wf; t.v = sv->v; t.xn2 = sv->xn2; t.g = sv->g; t.mu2 = sv->mu2; t.rstd2 = sv->rstd2;
@@ -472,7 +450,7 @@ struct LocalWsB {
     float *mu, *rstd;
 };
 size_t local_layout_bf16(int B, int H, int W, int C, void* base, size_t bytes, LocalWsB* out) {
-    WsAlloc a(base, base ? bytes : (size_t)-1);
+    WsAlloc a(base, bytes);
     const size_t M = (size_t)B * H * W;
     DwGeom g{B, H, W, C};
     LocalWsB w{};
@@ -525,18 +503,17 @@ extern "C" int dcpt_nafblock_local_fwd_bf16(const dcpt_nafblock_params* p, const
         DCPT_CHECK_ARG(pack_layout(C, const_cast<void*>(packed), packed_bytes, &k) <= packed_bytes, "nafblock_local_fwd_bf16: packed weights buffer too small");
         w.W1 = k.W1; w.W4 = k.W4; w.W5 = k.W5; w.W3 = k.W3; w.w2p = k.w2p; w.Wf = k.Wf; w.Wf1 = k.Wf1;
         j.n = 1;
-        j.in[0] = p->sca_w; j.out[0] = w.Wsca; j.N[0] = C; j.K[0] = C;
+        wpack_job(j, 0, p->sca_w, w.Wsca, C, C, 0);
     } else {
         j.n = 5;
-        j.in[0] = p->conv1_w; j.out[0] = w.W1; j.N[0] = 2 * C; j.K[0] = C;
-        j.in[1] = p->conv4_w; j.out[1] = w.W4; j.N[1] = 2 * C; j.K[1] = C;
-        j.in[2] = p->conv5_w; j.out[2] = w.W5; j.N[2] = C; j.K[2] = C;
-        j.in[3] = p->conv3_w; j.out[3] = w.W3; j.N[3] = C; j.K[3] = C;
-        j.in[4] = p->sca_w; j.out[4] = w.Wsca; j.N[4] = C; j.K[4] = C;
+        wpack_job(j, 0, p->conv1_w, w.W1, 2 * C, C, 0);
+        wpack_job(j, 1, p->conv4_w, w.W4, 2 * C, C, 0);
+        wpack_job(j, 2, p->conv5_w, w.W5, C, C, 0);
+        wpack_job(j, 3, p->conv3_w, w.W3, C, C, 0);
+        wpack_job(j, 4, p->sca_w, w.Wsca, C, C, 0);
         if (w.Wf) {
-            j.in[5] = p->conv4_w; j.rs[5] = p->conv5_w; j.out[5] = w.Wf; j.N[5] = 3 * C; j.K[5] = C; j.transpose[5] = 9;
-            j.in[6] = p->conv1_w; j.rs[6] = nullptr; j.out[6] = w.Wf1; j.N[6] = 2 * C; j.K[6] = C; j.transpose[6] = 9;
-            j.n = 7;
+            wpack_job(j, j.n++, p->conv4_w, w.Wf, 3 * C, C, 9, p->conv5_w);
+            wpack_job(j, j.n++, p->conv1_w, w.Wf1, 2 * C, C, 9);
         }
     }
     DCPT_TRY(launch_wpack_bf16(j, s));
@@ -546,12 +523,11 @@ extern "C" int dcpt_nafblock_local_fwd_bf16(const dcpt_nafblock_params* p, const
     DCPT_TRY(fwd_head_bf16(p, inp, h, B, H, W, C, s));
     bf16_t* const mmap = w.xn;   // LN1(inp) is dead
     DCPT_TRY(launch_box_mean_bf16(w.t2, reinterpret_cast<float*>(w.t1), mmap, B, H, W, C, k1, k2, s));
-    GemmNTB g{};
-    g.M = M; g.A = mmap; g.lda = C; g.K = C; g.Bw = w.Wsca; g.N = C; g.C = w.t2s; g.ldc = C; g.bias = p->sca_b; g.res = w.t2; g.ldres = C;
+    GemmNTB g = gemm_ntb_linear(mmap, C, M, C, w.Wsca, C, w.t2s, C);
+    g.bias = p->sca_b; g.res = w.t2; g.ldres = C;
     DCPT_TRY(launch_gemm_nt_bf16(g, EB_MUL, s));
-    g = GemmNTB{};
-    g.M = M; g.A = w.t2s; g.lda = C; g.K = C; g.Bw = w.W3; g.N = C; g.C = w.y; g.ldc = C; g.bias = p->conv3_b; g.res = inp; g.ldres = C;
-    g.cscale = p->beta;
+    g = gemm_ntb_linear(w.t2s, C, M, C, w.W3, C, w.y, C);
+    g.bias = p->conv3_b; g.res = inp; g.ldres = C; g.cscale = p->beta;
     DCPT_TRY(launch_gemm_nt_bf16(g, EB_RESID, s));
     TailB t{};
     t.W4 = w.W4; t.W5 = w.W5; t.Wf = w.Wf;
@@ -581,14 +557,11 @@ static int nafblock_bwd_bf16_impl(const dcpt_nafblock_params* p, const dcpt_nafb
     } else {
         WpackBJobs j{};
         j.n = 4;
-        if (w.mid) {
-            j.in[4] = p->conv3_w; j.rs[4] = p->beta; j.out[4] = w.WfT3; j.N[4] = C; j.K[4] = C; j.transpose[4] = 10;
-            j.n = 5;
-        }
-        j.in[0] = p->conv5_w; j.out[0] = w.wT5; j.rs[0] = p->gamma; j.N[0] = C;  j.K[0] = C; j.transpose[0] = 1;
-        j.in[1] = p->conv4_w; j.out[1] = w.wT4; j.rs[1] = nullptr;  j.N[1] = C2; j.K[1] = C; j.transpose[1] = 1;
-        j.in[2] = p->conv3_w; j.out[2] = w.wT3; j.rs[2] = p->beta;  j.N[2] = C;  j.K[2] = C; j.transpose[2] = 1;
-        j.in[3] = p->conv1_w; j.out[3] = w.wT1; j.rs[3] = nullptr;  j.N[3] = C2; j.K[3] = C; j.transpose[3] = 1;
+        wpack_job(j, 0, p->conv5_w, w.wT5, C, C, 1, p->gamma);
+        wpack_job(j, 1, p->conv4_w, w.wT4, C2, C, 1);
+        wpack_job(j, 2, p->conv3_w, w.wT3, C, C, 1, p->beta);
+        wpack_job(j, 3, p->conv1_w, w.wT1, C2, C, 1);
+        if (w.mid) wpack_job(j, j.n++, p->conv3_w, w.WfT3, C, C, 10, p->beta);
         DCPT_TRY(launch_wpack_bf16(j, s));
         DCPT_TRY(launch_dw_pack_weights(p->conv2_w, w.w2p, C2, s));
     }
@@ -600,8 +573,11 @@ static int nafblock_bwd_bf16_impl(const dcpt_nafblock_params* p, const dcpt_nafb
     Side* sd = (side_mode == 1 || (side_mode == 2 && !w.tn256)) ? side_for(s) : nullptr;
     hipStream_t sw = side_stream(sd, s);
     DCPT_TRY(side_fork(sd, 0, s));
-    GemmNTB g{};
+    GemmNTB g;
     const bool ffn = ffn_fused(C);
+    // the weight gradients of the levels without the grouped launch: one slab / column-sum buffer in turn, on the side stream
+    const GemmTNB tn{};
+    const WgradGain gain5{p->gamma, p->conv5_w, p->conv5_b, gr->gamma}, gain3{p->beta, p->conv3_w, p->conv3_b, gr->beta};
     if (ffn) {
         // B1 + B3 + B5 in one pass (ffn_bf16.hip): dv for conv4's weight gradient and dy = dout + LayerNorm2 backward
         FfnBwdB f{};
@@ -621,25 +597,24 @@ static int nafblock_bwd_bf16_impl(const dcpt_nafblock_params* p, const dcpt_nafb
         DCPT_TRY(launch_colpart_reduce(w.ffn_part, ffn_bwd_bf16_waves(M), 2, C, gr->norm2_w, gr->norm2_b, nullptr, sw));
     } else {
         // B1: dv = SimpleGate'(dout * gamma * W5; v)
-        g.M = M; g.A = dout; g.lda = C; g.K = C; g.Bw = w.wT5; g.N = C; g.C = w.dv; g.ldc = C2; g.aux = sv->v;
+        g = gemm_ntb_linear(dout, C, M, C, w.wT5, C, w.dv, C2);
+        g.aux = sv->v;
         DCPT_TRY(launch_gemm_nt_bf16(g, EB_SGBWD, s));
         // B2: conv5 / gamma gradients
-        if (!w.tn256) DCPT_TRY(wgrad_b(dout, C, sv->g, C, M, w.slab, w.colsum, p->gamma, p->conv5_w, p->conv5_b, gr->conv5_w, gr->gamma, gr->conv5_b, sw));
+        if (!w.tn256) DCPT_TRY(launch_wgrad_bf16(tn, dout, C, C, sv->g, C, C, M, w.slab, w.colsum, gr->conv5_w, gr->conv5_b, WR_PLAIN, sw, gain5));
         DCPT_TRY(side_fork(sd, 1, s));
         // B3: gradient of LN2's output
-        g = GemmNTB{};
-        g.M = M; g.A = w.dv; g.lda = C2; g.K = C2; g.Bw = w.wT4; g.N = C; g.C = w.gln; g.ldc = C;
+        g = gemm_ntb_linear(w.dv, C2, M, C2, w.wT4, C, w.gln, C);
         DCPT_TRY(launch_gemm_nt_bf16(g, EB_PLAIN, s));
         // B4: conv4 gradients
-        if (!w.tn256) DCPT_TRY(wgrad_b(w.dv, C2, sv->xn2, C, M, w.slab, w.colsum, nullptr, nullptr, nullptr, gr->conv4_w, nullptr, gr->conv4_b, sw));
+        if (!w.tn256) DCPT_TRY(launch_wgrad_bf16(tn, w.dv, C2, C2, sv->xn2, C, C, M, w.slab, w.colsum, gr->conv4_w, gr->conv4_b, WR_PLAIN, sw));
         // B5: dy = dout + LN2-backward  (with the chain kernel: part of B6 below)
         if (!w.mid) DCPT_TRY(launch_ln_bwd_bf16(w.gln, sv->y, sv->mu2, sv->rstd2, p->norm2_w, dout, w.dy, w.lnpart, w.ln_nblk, M, C, s));
         DCPT_TRY(side_fork(sd, 2, s));
         if (!w.tn256) DCPT_TRY(launch_colpart_reduce(w.lnpart, w.mid ? ln_tiles : w.ln_nblk, 2, C, gr->norm2_w, gr->norm2_b, nullptr, sw));
     }
     // B6: dts = d(t2 * s) (+ SCA's per-image channel sums out of the epilogue when an image is a whole number of 128-pixel tiles)
-    g = GemmNTB{};
-    g.M = M; g.A = w.dy; g.lda = C; g.K = C; g.Bw = w.wT3; g.N = C; g.C = w.dts; g.ldc = C;
+    g = gemm_ntb_linear(w.dy, C, M, C, w.wT3, C, w.dts, C);
     if (w.mid && !ffn) {   // B5 + B6 per 128-pixel tile, the LayerNorm backward as the GEMM's tile load (chain_bf16.hip)
         ChainMidB q{};
         q.gln = w.gln; q.y = sv->y; q.dout = dout; q.t2 = sv->t2; q.mu = sv->mu2; q.rstd = sv->rstd2; q.lnw = p->norm2_w; q.Wf = w.WfT3;
@@ -666,7 +641,7 @@ static int nafblock_bwd_bf16_impl(const dcpt_nafblock_params* p, const dcpt_nafb
                                                 p->conv3_b, gr->conv3_w, gr->beta, gr->conv3_b, WR_PLAIN, sv->s, (int)(P / t.rows_per_split), sw));
         } else {
             DCPT_TRY(launch_scale_rows_bf16(sv->t2, sv->s, w.t2s, M, C, P, sw));
-            DCPT_TRY(wgrad_b(w.dy, C, w.t2s, C, M, w.slab, w.colsum, p->beta, p->conv3_w, p->conv3_b, gr->conv3_w, gr->beta, gr->conv3_b, sw));
+            DCPT_TRY(launch_wgrad_bf16(tn, w.dy, C, C, w.t2s, C, C, M, w.slab, w.colsum, gr->conv3_w, gr->conv3_b, WR_PLAIN, sw, gain3));
         }
     }
     // B8: SCA backward
@@ -689,16 +664,15 @@ static int nafblock_bwd_bf16_impl(const dcpt_nafblock_params* p, const dcpt_nafb
         FfnBwdB f{};
         f.dout = w.dy; f.v = w.dt1; f.y = inp; f.wT4 = w.wT1; f.lnw = p->norm1_w; f.dy = dinp; f.lnpart = w.ffn_part1; f.M = M; f.eps = 1e-6f;
         DCPT_TRY(launch_conv_ln_bwd_tail_bf16(f, C, s));
-        DCPT_TRY(wgrad_b(w.dt1, C2, sv->xn1, C, M, w.slab, w.colsum, nullptr, nullptr, nullptr, gr->conv1_w, nullptr, gr->conv1_b, sw));
+        DCPT_TRY(launch_wgrad_bf16(tn, w.dt1, C2, C2, sv->xn1, C, C, M, w.slab, w.colsum, gr->conv1_w, gr->conv1_b, WR_PLAIN, sw));
         DCPT_TRY(side_fork(sd, 5, s));
         DCPT_TRY(launch_colpart_reduce(w.ffn_part1, ffn_bwd_bf16_waves(M), 2, C, gr->norm1_w, gr->norm1_b, nullptr, sw));
     } else {
         // B11: gradient of LN1's output
-        g = GemmNTB{};
-        g.M = M; g.A = w.dt1; g.lda = C2; g.K = C2; g.Bw = w.wT1; g.N = C; g.C = w.gln; g.ldc = C;
+        g = gemm_ntb_linear(w.dt1, C2, M, C2, w.wT1, C, w.gln, C);
         DCPT_TRY(launch_gemm_nt_bf16(g, EB_PLAIN, s));
         // B12: conv1 gradients
-        if (!w.tn256) DCPT_TRY(wgrad_b(w.dt1, C2, sv->xn1, C, M, w.slab, w.colsum, nullptr, nullptr, nullptr, gr->conv1_w, nullptr, gr->conv1_b, sw));
+        if (!w.tn256) DCPT_TRY(launch_wgrad_bf16(tn, w.dt1, C2, C2, sv->xn1, C, C, M, w.slab, w.colsum, gr->conv1_w, gr->conv1_b, WR_PLAIN, sw));
         // B13: dinp = dy + LN1-backward
         DCPT_TRY(launch_ln_bwd_bf16(w.gln, inp, sv->mu1, sv->rstd1, p->norm1_w, w.dy, dinp, w.lnpart2, w.ln_nblk, M, C, s));
         DCPT_TRY(side_fork(sd, 5, s));
@@ -707,11 +681,7 @@ static int nafblock_bwd_bf16_impl(const dcpt_nafblock_params* p, const dcpt_nafb
             // dgain = W . G + b sum dO, db = gain sum dO) and every other parameter-gradient reduction of the block, one launch
             FinJobs f{};
             f.nslab = 4;
-            const TnProb* q[4] = {&w.wg.p[0], &w.wg.p[1], &w.wg.p[2], &w.wg.p[3]};
-            for (int i = 0; i < 4; ++i) {
-                f.slab[i].slab = q[i]->slab; f.slab[i].colsum = q[i]->colsum; f.slab[i].N = q[i]->N; f.slab[i].K = q[i]->K;
-                f.slab[i].splits = q[i]->slots; f.slab[i].cs_rows = q[i]->splits; f.slab[i].tiles_k = q[i]->tiles_k; f.slab[i].ks_div = 1;
-            }
+            for (int i = 0; i < 4; ++i) f.slab[i] = fin_slab(w.wg.p[i]);
             f.slab[0].rowscale = p->gamma; f.slab[0].W = p->conv5_w; f.slab[0].wbias = p->conv5_b;
             f.slab[0].dW = gr->conv5_w; f.slab[0].dgain = gr->gamma; f.slab[0].dbias = gr->conv5_b;
             f.slab[1].dW = gr->conv4_w; f.slab[1].dbias = gr->conv4_b;
@@ -719,7 +689,7 @@ static int nafblock_bwd_bf16_impl(const dcpt_nafblock_params* p, const dcpt_nafb
             f.slab[2].dW = gr->conv3_w; f.slab[2].dgain = gr->beta; f.slab[2].dbias = gr->conv3_b;
             if (w.conv3_images) {   // slots per image: 1 (whole images per block) or the number of ranges an image is cut into
                 f.slab[2].kscale = sv->s;
-                f.slab[2].ks_div = q[2]->seg_rows > 0 ? 1 : (int)(P / q[2]->rows_per_split);
+                f.slab[2].ks_div = w.wg.p[2].seg_rows > 0 ? 1 : (int)(P / w.wg.p[2].rows_per_split);
             }
             f.slab[3].dW = gr->conv1_w; f.slab[3].dbias = gr->conv1_b;
             f.ncols = 3;
@@ -747,11 +717,10 @@ namespace {
 struct WgWs {
     bool tn256;
     GemmTNG g;
-    GemmTNB t;
     float *slab, *colsum;
 };
 size_t wg_layout(int64_t M, int N, int K, void* base, size_t bytes, WgWs* out) {
-    WsAlloc a(base, base ? bytes : (size_t)-1);
+    WsAlloc a(base, bytes);
     WgWs w{};
     w.tn256 = gemm_tn_bf16_256_ok(N, K);
     if (w.tn256) {
@@ -761,10 +730,10 @@ size_t wg_layout(int64_t M, int N, int K, void* base, size_t bytes, WgWs* out) {
         w.g.p[0].slab = a.get<float>(gemm_tn_bf16_256_slab_floats(w.g.p[0]));
         w.g.p[0].colsum = a.get<float>(gemm_tn_bf16_256_colsum_floats(w.g.p[0]));
     } else {
-        w.t.ldx = w.t.N = N; w.t.ldy = w.t.K = K; w.t.M = M;
-        gemm_tn_bf16_plan(M, N, K, &w.t.splits, &w.t.rows_per_split);
-        w.slab = a.get<float>((size_t)w.t.splits * N * K);
-        w.colsum = a.get<float>((size_t)w.t.splits * gemm_tn_bf16_tiles_k(N, K) * N);
+        size_t sl = 0, cs = 0;
+        wgrad_need_bf16(M, N, K, &sl, &cs);
+        w.slab = a.get<float>(sl);
+        w.colsum = a.get<float>(cs);
     }
     if (out) *out = w;
     return a.off;
@@ -789,15 +758,11 @@ extern "C" int dcpt_conv1x1_wgrad_bf16(const uint16_t* dY, const uint16_t* X, fl
         DCPT_TRY(launch_gemm_tn_bf16_256(w.g, s));
         FinJobs f{};
         f.nslab = 1;
-        f.slab[0].slab = w.g.p[0].slab; f.slab[0].colsum = w.g.p[0].colsum; f.slab[0].N = N; f.slab[0].K = K; f.slab[0].splits = w.g.p[0].slots;
-        f.slab[0].cs_rows = w.g.p[0].splits;
-        f.slab[0].tiles_k = w.g.p[0].tiles_k; f.slab[0].ks_div = 1; f.slab[0].dW = dW; f.slab[0].dbias = db;
+        f.slab[0] = fin_slab(w.g.p[0]);
+        f.slab[0].dW = dW; f.slab[0].dbias = db;
         return launch_wgrad_finish(f, s);
     }
-    w.t.X = dY; w.t.Y = X; w.t.slab = w.slab; w.t.colsum = db ? w.colsum : nullptr;
-    DCPT_TRY(launch_gemm_tn_bf16(w.t, s));
-    return launch_wgrad_reduce(w.slab, w.t.colsum, w.t.splits, w.t.splits * gemm_tn_bf16_tiles_k(N, K), N, K, nullptr, nullptr, nullptr, dW, nullptr, db,
-                               WR_PLAIN, s);
+    return launch_wgrad_bf16(GemmTNB{}, dY, N, N, X, K, K, M, w.slab, db ? w.colsum : nullptr, dW, db, WR_PLAIN, s);
 }
 
 extern "C" int dcpt_cast_f32_bf16(const float* x, uint16_t* y, int64_t n, dcpt_stream_t stream) {

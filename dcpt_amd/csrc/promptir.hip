@@ -166,13 +166,6 @@ __global__ __launch_bounds__(256) void prompt_mix_bwd_logits_kernel(const float*
     }
 }
 
-inline unsigned grid_for(int64_t n) {
-    int64_t nb = (n + 255) / 256;
-    if (nb > 16384) nb = 16384;
-    if (nb < 1) nb = 1;
-    return (unsigned)nb;
-}
-
 }  // namespace
 
 extern "C" size_t dcpt_prompt_mix_bwd_ws_bytes(int B, int D, int S) { return align_up((size_t)B * D * S * S * sizeof(float), 256); }
@@ -183,7 +176,7 @@ template <typename T>
 int prompt_mix_fwd(const float* logits, const float* param, float* weights, T* out, int B, int L, int D, int S, int H, int W, hipStream_t s) {
     prompt_softmax_kernel<<<dim3(cdiv(B, 64)), dim3(64), 0, s>>>(logits, weights, B, L);
     DCPT_CHECK_LAUNCH("prompt_softmax");
-    prompt_mix_fwd_kernel<T><<<dim3(grid_for((int64_t)B * H * W * (D / 4))), dim3(256), 0, s>>>(weights, param, out, B, L, D, S, H, W);
+    prompt_mix_fwd_kernel<T><<<dim3(ew_grid((int64_t)B * H * W * (D / 4))), dim3(256), 0, s>>>(weights, param, out, B, L, D, S, H, W);
     DCPT_CHECK_LAUNCH("prompt_mix_fwd");
     return DCPT_OK;
 }
@@ -193,9 +186,9 @@ int prompt_mix_bwd(const T* dout, const float* param, const float* weights, floa
                    int L, int D, int S, int H, int W, const char* name, hipStream_t s) {
     DCPT_CHECK_WS(name, ws, ws_bytes, dcpt_prompt_mix_bwd_ws_bytes(B, D, S));
     float* dP = (float*)ws;
-    prompt_mix_bwd_dp_kernel<T><<<dim3(grid_for((int64_t)B * S * S * D)), dim3(256), 0, s>>>(dout, dP, B, D, S, H, W);
+    prompt_mix_bwd_dp_kernel<T><<<dim3(ew_grid((int64_t)B * S * S * D)), dim3(256), 0, s>>>(dout, dP, B, D, S, H, W);
     DCPT_CHECK_LAUNCH("prompt_mix_bwd_dp");
-    prompt_mix_bwd_param_kernel<<<dim3(grid_for((int64_t)L * D * S * S)), dim3(256), 0, s>>>(dP, weights, dparam, B, L, D, S);
+    prompt_mix_bwd_param_kernel<<<dim3(ew_grid((int64_t)L * D * S * S)), dim3(256), 0, s>>>(dP, weights, dparam, B, L, D, S);
     DCPT_CHECK_LAUNCH("prompt_mix_bwd_param");
     prompt_mix_bwd_logits_kernel<<<dim3(B), dim3(256), 0, s>>>(dP, param, weights, dlogits, L, D, S);
     DCPT_CHECK_LAUNCH("prompt_mix_bwd_logits");

@@ -228,7 +228,7 @@ struct RcabWs {
 };
 
 size_t rcab_layout(int B, int H, int W, int C, int Cr, int backward, void* base, size_t bytes, RcabWs* out) {
-    WsAlloc a(base, base ? bytes : (size_t)-1);
+    WsAlloc a(base, bytes);
     RcabWs w{};
     const int64_t M = (int64_t)B * H * W;
     w.wp1 = a.get<float>((size_t)9 * C * C);
@@ -273,7 +273,7 @@ struct PsWs {
 };
 
 size_t ps_layout(int B, int H, int W, int C, int r, int backward, void* base, size_t bytes, PsWs* out) {
-    WsAlloc a(base, base ? bytes : (size_t)-1);
+    WsAlloc a(base, bytes);
     PsWs w{};
     const int64_t M = (int64_t)B * H * W;
     const int N = r * r * C;

@@ -74,27 +74,12 @@ bool ps_ok(int B, int H, int W, int C, int r) {
 // the forward operand image [Cout][9 C] of a conv: the first half of its cached pack, or packed here into `wp`
 int operand(const float* w, const void* pk, bf16_t* wp, int C, int Cout, const bf16_t** out, hipStream_t s) {
     if (pk) {
-        *out = static_cast<const bf16_t*>(pk);
+        *out = pk_fwd(pk);
         return DCPT_OK;
     }
     trace_tag("rcan_bf16.wpack_per_call");   // (not reached with the network's cached images)
-    WpackBJobs j{};
-    j.n = 1;
-    j.in[0] = w; j.out[0] = wp; j.N[0] = Cout; j.K[0] = 9 * C; j.transpose[0] = 2;
     *out = wp;
-    return launch_wpack_bf16(j, s);
-}
-int pk_check(const float* w, const void* pk, size_t pk_bytes, int C, int Cout, const char* who) {
-    DCPT_CHECK_ARG(w || pk, "%s: null argument (weights)", who);
-    DCPT_CHECK_ARG(pk == nullptr || pk_bytes >= dcpt_conv_wpack_bf16_bytes(C, Cout, 3), "%s: packed weights too small (dcpt_conv_wpack_bf16_bytes)", who);
-    return DCPT_OK;
-}
-
-GemmNTB conv3_problem(const bf16_t* x, const bf16_t* Bw, bf16_t* y, int B, int H, int W, int C, int Cout, const float* bias) {
-    GemmNTB g{};
-    g.M = (int64_t)B * H * W; g.A = x; g.K = 9 * C; g.conv3 = 1; g.gH = H; g.gW = W; g.gC = C; g.Bw = Bw; g.N = Cout; g.C = y; g.ldc = Cout;
-    g.bias = bias; g.nb = 1;
-    return g;
+    return launch_wpack_bf16_one(w, wp, Cout, 9 * C, 2, s);
 }
 
 struct RcabWsB {
@@ -104,7 +89,7 @@ struct RcabWsB {
     float *pooled, *s;   // [B][C]
 };
 size_t rcab_layout(int B, int H, int W, int C, void* base, size_t bytes, RcabWsB* out) {
-    WsAlloc a(base, base ? bytes : (size_t)-1);
+    WsAlloc a(base, bytes);
     RcabWsB w{};
     const int64_t M = (int64_t)B * H * W;
     w.wp1 = a.get<bf16_t>((size_t)9 * C * C);
@@ -133,8 +118,10 @@ extern "C" int dcpt_rcab_fwd_bf16(const dcpt_rcab_params* p, const void* wpacked
     DCPT_CHECK_ARG(p && x && y && p->conv1_b && p->conv2_b && p->ca1_w && p->ca1_b && p->ca2_w && p->ca2_b, "rcab_fwd_bf16: null argument");
     DCPT_CHECK_ARG(rcab_ok(B, H, W, C, Cr), "rcab_fwd_bf16: B=%d H=%d W=%d C=%d Cr=%d (C a positive multiple of 8 up to 1024, 1 <= Cr <= C, one map inside the 32-bit windows)",
                    B, H, W, C, Cr);
-    DCPT_TRY(pk_check(p->conv1_w, wpacked1, wpacked1_bytes, C, C, "rcab_fwd_bf16"));
-    DCPT_TRY(pk_check(p->conv2_w, wpacked2, wpacked2_bytes, C, C, "rcab_fwd_bf16"));
+    DCPT_CHECK_ARG(p->conv1_w || wpacked1, "rcab_fwd_bf16: null argument (weights)");
+    DCPT_TRY(pk_check(wpacked1, wpacked1_bytes, C, C, 3, "rcab_fwd_bf16"));
+    DCPT_CHECK_ARG(p->conv2_w || wpacked2, "rcab_fwd_bf16: null argument (weights)");
+    DCPT_TRY(pk_check(wpacked2, wpacked2_bytes, C, C, 3, "rcab_fwd_bf16"));
     RcabWsB w;
     const size_t need = rcab_layout(B, H, W, C, ws, ws_bytes, &w);
     DCPT_CHECK_WS("rcab_fwd_bf16", ws, ws_bytes, need);
@@ -145,11 +132,12 @@ extern "C" int dcpt_rcab_fwd_bf16(const dcpt_rcab_params* p, const void* wpacked
     DCPT_TRY(operand(p->conv1_w, wpacked1, w.wp1, C, C, &b1, s));
     DCPT_TRY(operand(p->conv2_w, wpacked2, w.wp2, C, C, &b2, s));
     // h = relu(conv1(x) + b1)
-    GemmNTB g = conv3_problem(x, b1, w.h, B, H, W, C, C, p->conv1_b);
+    GemmNTB g = gemm_ntb_conv3(x, B, H, W, C, b1, C, w.h, C);
+    g.bias = p->conv1_b;
     DCPT_TRY(launch_gemm_nt_bf16(g, EB_BIASRELU, s));
     // t = conv2(h) + b2, and the per-image column sums of its fp32 values
-    g = conv3_problem(w.h, b2, w.t, B, H, W, C, C, p->conv2_b);
-    g.colpart = w.colpart; g.P = P;
+    g = gemm_ntb_conv3(w.h, B, H, W, C, b2, C, w.t, C);
+    g.bias = p->conv2_b; g.colpart = w.colpart; g.P = P;
     DCPT_TRY(launch_gemm_nt_bf16(g, EB_BIASCOL, s));
     DCPT_TRY(launch_rcan_ca_fwd(w.colpart, p->ca1_w, p->ca1_b, p->ca2_w, p->ca2_b, w.pooled, w.s, B, P, C, Cr, s));
     const int64_t n8 = M * C / 8;
@@ -171,14 +159,15 @@ extern "C" int dcpt_conv3x3_res_fwd_bf16(const uint16_t* x, const float* w, cons
     DCPT_CHECK_ARG(x && bias && res && y, "conv3x3_res_fwd_bf16: null argument");
     DCPT_CHECK_ARG(conv3_ok(B, H, W, C, C), "conv3x3_res_fwd_bf16: B=%d H=%d W=%d C=%d (C a positive multiple of 8 up to 1024, one map inside the 32-bit windows)",
                    B, H, W, C);
-    DCPT_TRY(pk_check(w, wpacked, wpacked_bytes, C, C, "conv3x3_res_fwd_bf16"));
+    DCPT_CHECK_ARG(w || wpacked, "conv3x3_res_fwd_bf16: null argument (weights)");
+    DCPT_TRY(pk_check(wpacked, wpacked_bytes, C, C, 3, "conv3x3_res_fwd_bf16"));
     const size_t need = dcpt_conv3x3_res_bf16_ws_bytes(B, H, W, C);
     DCPT_CHECK_WS("conv3x3_res_fwd_bf16", ws, ws_bytes, need);
     trace_tag("rcan_bf16.res_fwd");
     const bf16_t* bw;
     DCPT_TRY(operand(w, wpacked, static_cast<bf16_t*>(ws), C, C, &bw, s));
-    GemmNTB g = conv3_problem(x, bw, y, B, H, W, C, C, bias);
-    g.res = res;
+    GemmNTB g = gemm_ntb_conv3(x, B, H, W, C, bw, C, y, C);
+    g.bias = bias; g.res = res;
     return launch_gemm_nt_bf16(g, EB_RESID, s);
 }
 
@@ -195,13 +184,14 @@ extern "C" int dcpt_conv3x3_ps_fwd_bf16(const uint16_t* x, const float* w, const
     DCPT_CHECK_ARG(ps_ok(B, H, W, C, r), "conv3x3_ps_fwd_bf16: B=%d H=%d W=%d C=%d r=%d (C a positive multiple of 8 up to 1024, r 2 or 3, one map inside the 32-bit windows)",
                    B, H, W, C, r);
     const int N = r * r * C;
-    DCPT_TRY(pk_check(w, wpacked, wpacked_bytes, C, N, "conv3x3_ps_fwd_bf16"));
+    DCPT_CHECK_ARG(w || wpacked, "conv3x3_ps_fwd_bf16: null argument (weights)");
+    DCPT_TRY(pk_check(wpacked, wpacked_bytes, C, N, 3, "conv3x3_ps_fwd_bf16"));
     const size_t need = dcpt_conv3x3_ps_bf16_ws_bytes(B, H, W, C, r);
     DCPT_CHECK_WS("conv3x3_ps_fwd_bf16", ws, ws_bytes, need);
     trace_tag("rcan_bf16.ps_fwd");
     const bf16_t* bw;
     DCPT_TRY(operand(w, wpacked, static_cast<bf16_t*>(ws), C, N, &bw, s));
-    GemmNTB g = conv3_problem(x, bw, y, B, H, W, C, N, bias);
-    g.psr = r;
+    GemmNTB g = gemm_ntb_conv3(x, B, H, W, C, bw, N, y, N);
+    g.bias = bias; g.psr = r;
     return launch_gemm_nt_bf16(g, EB_PSHUF, s);
 }

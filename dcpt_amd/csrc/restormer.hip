@@ -269,13 +269,6 @@ __global__ void concat_kernel(float* __restrict__ a, float* __restrict__ b, floa
     }
 }
 
-inline unsigned grid_for(int64_t n) {
-    int64_t nb = cdiv64(n, 256);
-    if (nb > 16384) nb = 16384;
-    if (nb < 1) nb = 1;
-    return (unsigned)nb;
-}
-
 inline int attn_splits(int P, int nbatch) {
     int s = 512 / (nbatch > 0 ? nbatch : 1);
     const int cap = P / 256 > 0 ? P / 256 : 1;
@@ -307,7 +300,7 @@ struct MdtaWs {
 };
 
 size_t mdta_layout(int B, int H, int W, int c, int heads, int backward, void* base, size_t bytes, MdtaWs* out) {
-    WsAlloc a(base, base ? bytes : (size_t)-1);
+    WsAlloc a(base, bytes);
     MdtaWs w{};
     const int64_t M = (int64_t)B * H * W;
     const int P = H * W, ch = c / heads;
@@ -369,7 +362,7 @@ struct GdfnWs {
 };
 
 size_t gdfn_layout(int B, int H, int W, int c, int hp, int backward, void* base, size_t bytes, GdfnWs* out) {
-    WsAlloc a(base, base ? bytes : (size_t)-1);
+    WsAlloc a(base, bytes);
     GdfnWs w{};
     const int64_t M = (int64_t)B * H * W;
     w.wp_in = a.get<float>((size_t)2 * hp * c);
@@ -596,9 +589,9 @@ extern "C" int dcpt_gdfn_fwd(const dcpt_gdfn_params* p, const float* x, float* y
     const size_t need = gdfn_layout(B, H, W, C, hp, 0, ws, ws_bytes, &w);
     DCPT_CHECK_WS("gdfn_fwd", ws, ws_bytes, need);
     const int64_t M = (int64_t)B * H * W;
-    gdfn_pack_kernel<<<dim3(grid_for((int64_t)2 * hp * C)), dim3(256), 0, s>>>(p->in_w, w.wp_in, C, hidden, hp, 0);
-    gdfn_pack_kernel<<<dim3(grid_for((int64_t)18 * hp)), dim3(256), 0, s>>>(p->dw_w, w.w2p, C, hidden, hp, 1);
-    gdfn_pack_kernel<<<dim3(grid_for((int64_t)C * hp)), dim3(256), 0, s>>>(p->out_w, w.wp_out, C, hidden, hp, 2);
+    gdfn_pack_kernel<<<dim3(ew_grid((int64_t)2 * hp * C)), dim3(256), 0, s>>>(p->in_w, w.wp_in, C, hidden, hp, 0);
+    gdfn_pack_kernel<<<dim3(ew_grid((int64_t)18 * hp)), dim3(256), 0, s>>>(p->dw_w, w.w2p, C, hidden, hp, 1);
+    gdfn_pack_kernel<<<dim3(ew_grid((int64_t)C * hp)), dim3(256), 0, s>>>(p->out_w, w.wp_out, C, hidden, hp, 2);
     DCPT_CHECK_LAUNCH("gdfn_pack");
     float* xn = sv->xn ? sv->xn : w.r_xn;   // lean mode: LN(x) and the gated product live in the workspace (recomputed in backward)
     float* tg = sv->t ? sv->t : w.r_t;
@@ -627,9 +620,9 @@ extern "C" int dcpt_gdfn_bwd(const dcpt_gdfn_params* p, const dcpt_gdfn_params_g
     const size_t need = gdfn_layout(B, H, W, C, hp, 1, ws, ws_bytes, &w);
     DCPT_CHECK_WS("gdfn_bwd", ws, ws_bytes, need);
     const int64_t M = (int64_t)B * H * W;
-    gdfn_pack_kernel<<<dim3(grid_for((int64_t)18 * hp)), dim3(256), 0, s>>>(p->dw_w, w.w2p, C, hidden, hp, 1);
-    gdfn_pack_kernel<<<dim3(grid_for((int64_t)hp * C)), dim3(256), 0, s>>>(p->out_w, w.wT_out, C, hidden, hp, 3);
-    gdfn_pack_kernel<<<dim3(grid_for((int64_t)C * 2 * hp)), dim3(256), 0, s>>>(p->in_w, w.wT_in, C, hidden, hp, 4);
+    gdfn_pack_kernel<<<dim3(ew_grid((int64_t)18 * hp)), dim3(256), 0, s>>>(p->dw_w, w.w2p, C, hidden, hp, 1);
+    gdfn_pack_kernel<<<dim3(ew_grid((int64_t)hp * C)), dim3(256), 0, s>>>(p->out_w, w.wT_out, C, hidden, hp, 3);
+    gdfn_pack_kernel<<<dim3(ew_grid((int64_t)C * 2 * hp)), dim3(256), 0, s>>>(p->in_w, w.wT_in, C, hidden, hp, 4);
     DCPT_CHECK_LAUNCH("gdfn_pack");
     float* g_in = w.gpad;                       // [2hp][c] (also reused as [2hp*9])
     float* g_out = w.gpad + (size_t)2 * hp * (C > 9 ? C : 9);  // [c][hp]
@@ -657,7 +650,7 @@ extern "C" int dcpt_gdfn_bwd(const dcpt_gdfn_params* p, const dcpt_gdfn_params_g
     DCPT_TRY(launch_gemm_nt(g, A_PLAIN, E_PLAIN, s));
     if (!t_from_bwd) {
         DCPT_TRY(launch_wgrad(tp, A_PLAIN, dy, C, C, tg, hp, hp, M, w.slab, nullptr, g_out, nullptr, WR_PLAIN, sw));
-        gdfn_unpack_kernel<<<dim3(grid_for((int64_t)C * hidden)), dim3(256), 0, sw>>>(g_out, gr->out_w, C, hidden, hp, 2);
+        gdfn_unpack_kernel<<<dim3(ew_grid((int64_t)C * hidden)), dim3(256), 0, sw>>>(g_out, gr->out_w, C, hidden, hp, 2);
         DCPT_CHECK_LAUNCH("gdfn_unpack_out");
     }
     // gate backward, depthwise backward
@@ -667,7 +660,7 @@ extern "C" int dcpt_gdfn_bwd(const dcpt_gdfn_params* p, const dcpt_gdfn_params_g
         DCPT_TRY(launch_dw_ring_bwd_gelu_f32(w.dt, sv->u, w.w2p, w.du, w.wpart, B, H, W, hp, s, t_from_bwd ? w.r_t : nullptr));
         if (t_from_bwd) {
             DCPT_TRY(launch_wgrad(tp, A_PLAIN, dy, C, C, tg, hp, hp, M, w.slab, nullptr, g_out, nullptr, WR_PLAIN, sw));
-            gdfn_unpack_kernel<<<dim3(grid_for((int64_t)C * hidden)), dim3(256), 0, sw>>>(g_out, gr->out_w, C, hidden, hp, 2);
+            gdfn_unpack_kernel<<<dim3(ew_grid((int64_t)C * hidden)), dim3(256), 0, sw>>>(g_out, gr->out_w, C, hidden, hp, 2);
             DCPT_CHECK_LAUNCH("gdfn_unpack_out");
         }
     } else {
@@ -676,7 +669,7 @@ extern "C" int dcpt_gdfn_bwd(const dcpt_gdfn_params* p, const dcpt_gdfn_params_g
     }
     DCPT_TRY(side_fork(sd, 1, s));          // du, depthwise partial sums (dt is dead from here on)
     DCPT_TRY(launch_dw_wgrad_reduce(w.wpart, B * nblk_dwb, 2 * hp, g_in, w.dt /*unused bias grad*/, sw));
-    gdfn_unpack_kernel<<<dim3(grid_for((int64_t)2 * hidden * 9)), dim3(256), 0, sw>>>(g_in, gr->dw_w, C, hidden, hp, 1);
+    gdfn_unpack_kernel<<<dim3(ew_grid((int64_t)2 * hidden * 9)), dim3(256), 0, sw>>>(g_in, gr->dw_w, C, hidden, hp, 1);
     DCPT_CHECK_LAUNCH("gdfn_unpack_dw");
     // project_in
     g = GemmNT{};
@@ -684,7 +677,7 @@ extern "C" int dcpt_gdfn_bwd(const dcpt_gdfn_params* p, const dcpt_gdfn_params_g
     DCPT_TRY(launch_gemm_nt(g, A_PLAIN, E_PLAIN, s));
     tp = GemmTN{};
     DCPT_TRY(launch_wgrad(tp, A_PLAIN, w.du, 2 * hp, 2 * hp, xn, C, C, M, w.slab, nullptr, g_in, nullptr, WR_PLAIN, sw));
-    gdfn_unpack_kernel<<<dim3(grid_for((int64_t)2 * hidden * C)), dim3(256), 0, sw>>>(g_in, gr->in_w, C, hidden, hp, 0);
+    gdfn_unpack_kernel<<<dim3(ew_grid((int64_t)2 * hidden * C)), dim3(256), 0, sw>>>(g_in, gr->in_w, C, hidden, hp, 0);
     DCPT_CHECK_LAUNCH("gdfn_unpack_in");
     DCPT_TRY(launch_ln_bwd_ex(w.dxn, x, sv->mu, sv->rstd, p->norm_w, dy, nullptr, nullptr, biasfree, dx, w.lnpart, w.ln_nblk, M, C, s));
     DCPT_TRY(side_fork(sd, 2, s));          // LayerNorm partial sums
@@ -695,28 +688,28 @@ extern "C" int dcpt_gdfn_bwd(const dcpt_gdfn_params* p, const dcpt_gdfn_params_g
 // =====================================================================================================
 extern "C" int dcpt_pixel_unshuffle(const float* x, float* y, int B, int H, int W, int C, dcpt_stream_t stream) {
     DCPT_CHECK_ARG(x && y && H % 2 == 0 && W % 2 == 0, "pixel_unshuffle: bad argument");
-    pixel_shuffle_kernel<<<dim3(grid_for((int64_t)B * H * W * C)), dim3(256), 0, (hipStream_t)stream>>>(x, y, B, H / 2, W / 2, C, 0);
+    pixel_shuffle_kernel<<<dim3(ew_grid((int64_t)B * H * W * C)), dim3(256), 0, (hipStream_t)stream>>>(x, y, B, H / 2, W / 2, C, 0);
     DCPT_CHECK_LAUNCH("pixel_unshuffle");
     return DCPT_OK;
 }
 
 extern "C" int dcpt_pixel_shuffle(const float* x, float* y, int B, int H, int W, int C4, dcpt_stream_t stream) {
     DCPT_CHECK_ARG(x && y && C4 % 4 == 0, "pixel_shuffle: bad argument");
-    pixel_shuffle_kernel<<<dim3(grid_for((int64_t)B * H * W * C4)), dim3(256), 0, (hipStream_t)stream>>>(x, y, B, H, W, C4 / 4, 1);
+    pixel_shuffle_kernel<<<dim3(ew_grid((int64_t)B * H * W * C4)), dim3(256), 0, (hipStream_t)stream>>>(x, y, B, H, W, C4 / 4, 1);
     DCPT_CHECK_LAUNCH("pixel_shuffle");
     return DCPT_OK;
 }
 
 extern "C" int dcpt_concat_channels(const float* a, const float* b, float* out, int64_t M, int Ca, int Cb, dcpt_stream_t stream) {
     DCPT_CHECK_ARG(a && b && out && Ca % 4 == 0 && Cb % 4 == 0, "concat_channels: bad argument");
-    concat_kernel<<<dim3(grid_for(M * ((Ca + Cb) / 4))), dim3(256), 0, (hipStream_t)stream>>>((float*)a, (float*)b, out, M, Ca, Cb, 0);
+    concat_kernel<<<dim3(ew_grid(M * ((Ca + Cb) / 4))), dim3(256), 0, (hipStream_t)stream>>>((float*)a, (float*)b, out, M, Ca, Cb, 0);
     DCPT_CHECK_LAUNCH("concat_channels");
     return DCPT_OK;
 }
 
 extern "C" int dcpt_split_channels(const float* cat, float* a, float* b, int64_t M, int Ca, int Cb, dcpt_stream_t stream) {
     DCPT_CHECK_ARG(a && b && cat && Ca % 4 == 0 && Cb % 4 == 0, "split_channels: bad argument");
-    concat_kernel<<<dim3(grid_for(M * ((Ca + Cb) / 4))), dim3(256), 0, (hipStream_t)stream>>>(a, b, (float*)cat, M, Ca, Cb, 1);
+    concat_kernel<<<dim3(ew_grid(M * ((Ca + Cb) / 4))), dim3(256), 0, (hipStream_t)stream>>>(a, b, (float*)cat, M, Ca, Cb, 1);
     DCPT_CHECK_LAUNCH("split_channels");
     return DCPT_OK;
 }
@@ -764,14 +757,14 @@ int launch_mdta_dtemp_reduce(const float* part, float* dtemp, int B, int heads, 
 
 int launch_gdfn_pack(const float* in, float* out, int c, int h, int hp, int mode, hipStream_t s) {
     const int64_t n = mode == 1 ? (int64_t)18 * hp : (mode == 0 || mode == 4) ? (int64_t)2 * hp * c : (int64_t)c * hp;
-    gdfn_pack_kernel<<<dim3(grid_for(n)), dim3(256), 0, s>>>(in, out, c, h, hp, mode);
+    gdfn_pack_kernel<<<dim3(ew_grid(n)), dim3(256), 0, s>>>(in, out, c, h, hp, mode);
     DCPT_CHECK_LAUNCH("gdfn_pack");
     return DCPT_OK;
 }
 
 int launch_gdfn_unpack(const float* in, float* out, int c, int h, int hp, int mode, hipStream_t s) {
     const int64_t n = mode == 0 ? (int64_t)2 * h * c : mode == 1 ? (int64_t)2 * h * 9 : (int64_t)c * h;
-    gdfn_unpack_kernel<<<dim3(grid_for(n)), dim3(256), 0, s>>>(in, out, c, h, hp, mode);
+    gdfn_unpack_kernel<<<dim3(ew_grid(n)), dim3(256), 0, s>>>(in, out, c, h, hp, mode);
     DCPT_CHECK_LAUNCH("gdfn_unpack");
     return DCPT_OK;
 }

@@ -25,13 +25,6 @@ namespace {
 __device__ __forceinline__ float bf2f(bf16_t v) { return bf_lo((uint32_t)v); }
 __device__ __forceinline__ bf16_t f2bf(float v) { return (bf16_t)(bf_pack(v, 0.f) & 0xffffu); }
 
-inline unsigned grid_for(int64_t n) {
-    int64_t nb = cdiv64(n, 256);
-    if (nb > 16384) nb = 16384;
-    if (nb < 1) nb = 1;
-    return (unsigned)nb;
-}
-
 // ---- LayerNorm over bf16 rows (one wave per row, fp32 statistics two-pass) -----------------------------------------------
 // WithBias (:43-59):  y = (x - mu) * rstd * w + b;   BiasFree (:26-40):  y = x * rstd * w  (variance about the mean, mean kept)
 constexpr int LN_MAXJ = 16;   // C <= 1024
@@ -616,24 +609,9 @@ int pack_bf16(const float* w, float* stage, bf16_t* out, int N, int K, bool tran
     return launch_cast_f32_bf16(src, out, (int64_t)N * K, s);
 }
 
-// weight gradient dW[N][K] = sum_m X[m][n] Y[m][k] (bf16 operands, fp32 slabs reduced in a fixed order)
-int wgrad(const bf16_t* X, int ldx, int N, const bf16_t* Y, int ldy, int K, int64_t M, float* slab, float* dW, hipStream_t s) {
-    GemmTNB t{};
-    t.M = M; t.X = X; t.ldx = ldx; t.N = N; t.Y = Y; t.ldy = ldy; t.K = K; t.slab = slab;
-    gemm_tn_bf16_plan(M, N, K, &t.splits, &t.rows_per_split);
-    DCPT_TRY(launch_gemm_tn_bf16(t, s));
-    return launch_wgrad_reduce(slab, nullptr, t.splits, 0, N, K, nullptr, nullptr, nullptr, dW, nullptr, nullptr, WR_PLAIN, s);
-}
-size_t wgrad_slab_floats(int64_t M, int N, int K) {
-    int sp;
-    int64_t r;
-    gemm_tn_bf16_plan(M, N, K, &sp, &r);
-    return (size_t)sp * N * K;
-}
-
 int nt(const bf16_t* A, int lda, const bf16_t* Bw, int N, int K, bf16_t* C, int ldc, int64_t M, const bf16_t* res, hipStream_t s) {
-    GemmNTB g{};
-    g.M = M; g.A = A; g.lda = lda; g.K = K; g.Bw = Bw; g.N = N; g.C = C; g.ldc = ldc; g.res = res;
+    GemmNTB g = gemm_ntb_linear(A, lda, M, K, Bw, N, C, ldc);
+    g.res = res;
     return launch_gemm_nt_bf16(g, res ? EB_RESID : EB_PLAIN, s);
 }
 
@@ -658,7 +636,7 @@ bool mdta_shape_ok(int B, int H, int W, int C, int heads) {
 
 // kept: the caller supplies xn, qkv1 and out_att (full save mode), so their workspace copies are not reserved
 size_t mdta_layout(int B, int H, int W, int c, int heads, int backward, bool kept, void* base, size_t bytes, MdtaWsB* out) {
-    WsAlloc a(base, base ? bytes : (size_t)-1);
+    WsAlloc a(base, bytes);
     MdtaWsB w{};
     const int64_t M = (int64_t)B * H * W;
     const int P = H * W, ch = c / heads;
@@ -687,8 +665,10 @@ size_t mdta_layout(int B, int H, int W, int c, int heads, int backward, bool kep
         w.cqk = a.get<float>((size_t)B * 2 * c);
         w.dtpart = a.get<float>((size_t)B * heads);
         w.scr2 = a.get<float>((size_t)3 * c);
-        const size_t s1 = wgrad_slab_floats(M, 3 * c, c), s2 = wgrad_slab_floats(M, c, c);
-        w.slab = a.get<float>(s1 > s2 ? s1 : s2);
+        size_t sl = 0;   // qkv and project_out share the slabs
+        wgrad_need_bf16(M, 3 * c, c, &sl, nullptr);
+        wgrad_need_bf16(M, c, c, &sl, nullptr);
+        w.slab = a.get<float>(sl);
         w.nblk_dwb = H;   // tap-gradient partials per image row
         w.wpart = a.get<float>((size_t)B * w.nblk_dwb * 10 * 3 * c);
         w.lnpart = a.get<float>((size_t)ln_bwd_waves(M) * 2 * c);
@@ -713,7 +693,7 @@ int gdfn_hp(int hidden) { return (hidden + 7) / 8 * 8; }
 
 // kept: the caller supplies xn and t (full save mode)
 size_t gdfn_layout(int B, int H, int W, int c, int hp, int backward, bool kept, void* base, size_t bytes, GdfnWsB* out) {
-    WsAlloc a(base, base ? bytes : (size_t)-1);
+    WsAlloc a(base, bytes);
     GdfnWsB w{};
     const int64_t M = (int64_t)B * H * W;
     w.w_in = a.get<bf16_t>((size_t)2 * hp * c);
@@ -729,8 +709,10 @@ size_t gdfn_layout(int B, int H, int W, int c, int hp, int backward, bool kept, 
         w.dt = a.get<bf16_t>((size_t)M * hp);
         w.du = a.get<bf16_t>((size_t)M * 2 * hp);
         w.dxn = a.get<bf16_t>((size_t)M * c);
-        const size_t s1 = wgrad_slab_floats(M, 2 * hp, c), s2 = wgrad_slab_floats(M, c, hp);
-        w.slab = a.get<float>(s1 > s2 ? s1 : s2);
+        size_t sl = 0;   // project_in and project_out share the slabs
+        wgrad_need_bf16(M, 2 * hp, c, &sl, nullptr);
+        wgrad_need_bf16(M, c, hp, &sl, nullptr);
+        w.slab = a.get<float>(sl);
         w.nblk_dwb = dw_ring_bwd_num_blocks_per_image(DwGeom{B, H, W, hp});
         w.wpart = a.get<float>((size_t)B * w.nblk_dwb * 10 * 2 * hp);
         w.lnpart = a.get<float>((size_t)ln_bwd_waves(M) * 2 * c);
@@ -832,7 +814,7 @@ extern "C" int dcpt_mdta_bf16_bwd(const dcpt_mdta_params* p, const dcpt_mdta_par
     // d_att = dy Wproj ; dWproj = dy^T out_att
     DCPT_TRY(pack_bf16(p->proj_w, w.stage, w.wp, C, C, true, s));
     DCPT_TRY(nt(dyb, C, w.wp, C, C, w.d_att, C, M, nullptr, s));
-    DCPT_TRY(wgrad(dyb, C, C, out_att, C, C, M, w.slab, gr->proj_w, s));
+    DCPT_TRY(launch_wgrad_bf16(GemmTNB{}, dyb, C, C, out_att, C, C, M, w.slab, nullptr, gr->proj_w, nullptr, WR_PLAIN, s));
     // dattn = d_att^T v (per image and head);  dv = d_att attn  (attn^T as the applied matrix)
     DCPT_TRY(launch_gram(w.d_att, C, qkv + 2 * C, C3, w.gslab, B, P, heads, ch, s));
     DCPT_TRY(launch_apply(sv->attnT, w.d_att, C, nullptr, 0, nullptr, 0, w.dqkv + 2 * C, C3, B, P, heads, ch, s));
@@ -857,7 +839,7 @@ extern "C" int dcpt_mdta_bf16_bwd(const dcpt_mdta_params* p, const dcpt_mdta_par
     // qkv 1x1
     DCPT_TRY(pack_bf16(p->qkv_w, w.stage, w.wq, C3, C, true, s));
     DCPT_TRY(nt(w.dqkv1, C3, w.wq, C, C3, w.dxn, C, M, nullptr, s));
-    DCPT_TRY(wgrad(w.dqkv1, C3, C3, xn, C, C, M, w.slab, gr->qkv_w, s));
+    DCPT_TRY(launch_wgrad_bf16(GemmTNB{}, w.dqkv1, C3, C3, xn, C, C, M, w.slab, nullptr, gr->qkv_w, nullptr, WR_PLAIN, s));
     // dx = dy + LN-backward
     DCPT_TRY(launch_ln_bwd_rows(w.dxn, xb, sv->mu, sv->rstd, p->norm_w, dyb, reinterpret_cast<bf16_t*>(dx), w.lnpart, M, C, biasfree, s));
     return launch_colpart_reduce(w.lnpart, ln_bwd_waves(M), 2, C, gr->norm_w, biasfree ? nullptr : gr->norm_b, nullptr, s);
@@ -933,7 +915,7 @@ extern "C" int dcpt_gdfn_bf16_bwd(const dcpt_gdfn_params* p, const dcpt_gdfn_par
     DCPT_TRY(launch_gdfn_pack(p->out_w, w.stage, C, hidden, hp, 3, s));
     DCPT_TRY(launch_cast_f32_bf16(w.stage, w.w_out, (int64_t)hp * C, s));
     DCPT_TRY(nt(dyb, C, w.w_out, hp, C, w.dt, hp, M, nullptr, s));
-    DCPT_TRY(wgrad(dyb, C, C, tg, hp, hp, M, w.slab, g_out, s));
+    DCPT_TRY(launch_wgrad_bf16(GemmTNB{}, dyb, C, C, tg, hp, hp, M, w.slab, nullptr, g_out, nullptr, WR_PLAIN, s));
     DCPT_TRY(launch_gdfn_unpack(g_out, gr->out_w, C, hidden, hp, 2, s));
     // gate + depthwise backward in one pass on the ring
     DCPT_TRY(launch_dw_ring_bwd_gelu_bf16(w.dt, u, w.w2p, w.du, w.wpart, B, H, W, hp, s));
@@ -943,7 +925,7 @@ extern "C" int dcpt_gdfn_bf16_bwd(const dcpt_gdfn_params* p, const dcpt_gdfn_par
     DCPT_TRY(launch_gdfn_pack(p->in_w, w.stage, C, hidden, hp, 4, s));
     DCPT_TRY(launch_cast_f32_bf16(w.stage, w.w_in, (int64_t)C * 2 * hp, s));
     DCPT_TRY(nt(w.du, 2 * hp, w.w_in, C, 2 * hp, w.dxn, C, M, nullptr, s));
-    DCPT_TRY(wgrad(w.du, 2 * hp, 2 * hp, xn, C, C, M, w.slab, g_in, s));
+    DCPT_TRY(launch_wgrad_bf16(GemmTNB{}, w.du, 2 * hp, 2 * hp, xn, C, C, M, w.slab, nullptr, g_in, nullptr, WR_PLAIN, s));
     DCPT_TRY(launch_gdfn_unpack(g_in, gr->in_w, C, hidden, hp, 0, s));
     DCPT_TRY(launch_ln_bwd_rows(w.dxn, xb, sv->mu, sv->rstd, p->norm_w, dyb, reinterpret_cast<bf16_t*>(dx), w.lnpart, M, C, biasfree, s));
     return launch_colpart_reduce(w.lnpart, ln_bwd_waves(M), 2, C, gr->norm_w, biasfree ? nullptr : gr->norm_b, nullptr, s);
@@ -986,7 +968,7 @@ __global__ void concat_bf16_kernel(bf16_t* __restrict__ a, bf16_t* __restrict__ 
 extern "C" int dcpt_pixel_unshuffle_bf16(const uint16_t* x, uint16_t* y, int B, int H, int W, int C, dcpt_stream_t stream) {
     DCPT_CHECK_ARG(x && y && B > 0 && H > 0 && W > 0 && C > 0 && H % 2 == 0 && W % 2 == 0, "pixel_unshuffle_bf16: bad argument");
     trace_tag("rst_bf16.pixel_shuffle");
-    pixel_shuffle_bf16_kernel<<<dim3(grid_for((int64_t)B * H * W * C)), dim3(256), 0, (hipStream_t)stream>>>(x, y, B, H / 2, W / 2, C, 0);
+    pixel_shuffle_bf16_kernel<<<dim3(ew_grid((int64_t)B * H * W * C)), dim3(256), 0, (hipStream_t)stream>>>(x, y, B, H / 2, W / 2, C, 0);
     DCPT_CHECK_LAUNCH("pixel_unshuffle_bf16");
     return DCPT_OK;
 }
@@ -994,7 +976,7 @@ extern "C" int dcpt_pixel_unshuffle_bf16(const uint16_t* x, uint16_t* y, int B, 
 extern "C" int dcpt_pixel_shuffle_bf16(const uint16_t* x, uint16_t* y, int B, int H, int W, int C4, dcpt_stream_t stream) {
     DCPT_CHECK_ARG(x && y && B > 0 && H > 0 && W > 0 && C4 > 0 && C4 % 4 == 0, "pixel_shuffle_bf16: bad argument");
     trace_tag("rst_bf16.pixel_shuffle");
-    pixel_shuffle_bf16_kernel<<<dim3(grid_for((int64_t)B * H * W * C4)), dim3(256), 0, (hipStream_t)stream>>>(x, y, B, H, W, C4 / 4, 1);
+    pixel_shuffle_bf16_kernel<<<dim3(ew_grid((int64_t)B * H * W * C4)), dim3(256), 0, (hipStream_t)stream>>>(x, y, B, H, W, C4 / 4, 1);
     DCPT_CHECK_LAUNCH("pixel_shuffle_bf16");
     return DCPT_OK;
 }
@@ -1002,7 +984,7 @@ extern "C" int dcpt_pixel_shuffle_bf16(const uint16_t* x, uint16_t* y, int B, in
 extern "C" int dcpt_concat_channels_bf16(const uint16_t* a, const uint16_t* b, uint16_t* out, int64_t M, int Ca, int Cb, dcpt_stream_t stream) {
     DCPT_CHECK_ARG(a && b && out && M > 0 && Ca > 0 && Cb > 0 && Ca % 8 == 0 && Cb % 8 == 0, "concat_channels_bf16: bad argument (channels %% 8)");
     trace_tag("rst_bf16.concat");
-    concat_bf16_kernel<<<dim3(grid_for(M * ((Ca + Cb) / 8))), dim3(256), 0, (hipStream_t)stream>>>((bf16_t*)a, (bf16_t*)b, out, M, Ca, Cb, 0);
+    concat_bf16_kernel<<<dim3(ew_grid(M * ((Ca + Cb) / 8))), dim3(256), 0, (hipStream_t)stream>>>((bf16_t*)a, (bf16_t*)b, out, M, Ca, Cb, 0);
     DCPT_CHECK_LAUNCH("concat_channels_bf16");
     return DCPT_OK;
 }
@@ -1010,7 +992,7 @@ extern "C" int dcpt_concat_channels_bf16(const uint16_t* a, const uint16_t* b, u
 extern "C" int dcpt_split_channels_bf16(const uint16_t* cat, uint16_t* a, uint16_t* b, int64_t M, int Ca, int Cb, dcpt_stream_t stream) {
     DCPT_CHECK_ARG(a && b && cat && M > 0 && Ca > 0 && Cb > 0 && Ca % 8 == 0 && Cb % 8 == 0, "split_channels_bf16: bad argument (channels %% 8)");
     trace_tag("rst_bf16.concat");
-    concat_bf16_kernel<<<dim3(grid_for(M * ((Ca + Cb) / 8))), dim3(256), 0, (hipStream_t)stream>>>(a, b, (bf16_t*)cat, M, Ca, Cb, 1);
+    concat_bf16_kernel<<<dim3(ew_grid(M * ((Ca + Cb) / 8))), dim3(256), 0, (hipStream_t)stream>>>(a, b, (bf16_t*)cat, M, Ca, Cb, 1);
     DCPT_CHECK_LAUNCH("split_channels_bf16");
     return DCPT_OK;
 }

@@ -256,7 +256,7 @@ struct AttnWs {
 };
 
 size_t attn_layout(int B, int H, int W, int C, int backward, void* base, size_t bytes, AttnWs* out) {
-    WsAlloc a(base, base ? bytes : (size_t)-1);
+    WsAlloc a(base, bytes);
     AttnWs w{};
     const int64_t M = (int64_t)B * H * W;
     if (!backward) {
@@ -293,7 +293,7 @@ struct MlpWs {
 };
 
 size_t mlp_layout(int B, int H, int W, int C, int hidden, int backward, void* base, size_t bytes, MlpWs* out) {
-    WsAlloc a(base, base ? bytes : (size_t)-1);
+    WsAlloc a(base, bytes);
     MlpWs w{};
     const int64_t M = (int64_t)B * H * W;
     w.g = a.get<float>((size_t)M * hidden);
@@ -325,7 +325,7 @@ struct ConvResWs {
 };
 
 size_t convres_layout(int B, int H, int W, int C, int backward, void* base, size_t bytes, ConvResWs* out) {
-    WsAlloc a(base, base ? bytes : (size_t)-1);
+    WsAlloc a(base, bytes);
     ConvResWs w{};
     const int64_t M = (int64_t)B * H * W;
     w.wp = a.get<float>((size_t)9 * C * C);

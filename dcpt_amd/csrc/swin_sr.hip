@@ -104,7 +104,7 @@ struct ActWs {
 };
 // up = 1: output grid 2H x 2W (Mo = 4 M)
 size_t act_layout(int B, int H, int W, int Cin, int Cout, int up, int backward, void* base, size_t bytes, ActWs* out) {
-    WsAlloc a(base, base ? bytes : (size_t)-1);
+    WsAlloc a(base, bytes);
     ActWs w{};
     const int64_t Mo = (int64_t)B * H * W * (up ? 4 : 1);
     w.wp = a.get<float>((size_t)9 * Cin * Cout);
@@ -176,7 +176,7 @@ struct PsOutWs {
 inline int ps_npad(int Cimg, int r) { return (r * r * Cimg + 3) & ~3; }
 
 size_t psout_layout(int B, int H, int W, int C, int Cimg, int r, int backward, void* base, size_t bytes, PsOutWs* out) {
-    WsAlloc a(base, base ? bytes : (size_t)-1);
+    WsAlloc a(base, bytes);
     PsOutWs w{};
     const int64_t M = (int64_t)B * H * W;
     const int Np = ps_npad(Cimg, r);
@@ -214,7 +214,7 @@ struct C3Ws {
     float *slab, *colsum;
 };
 size_t c3_layout(int B, int H, int W, int C, int backward, void* base, size_t bytes, C3Ws* out) {
-    WsAlloc a(base, base ? bytes : (size_t)-1);
+    WsAlloc a(base, bytes);
     C3Ws w{};
     const int64_t M = (int64_t)B * H * W;
     const int Cq = C / 4;

@@ -67,11 +67,37 @@ class Case:
         return self.par(tag + ".w", c, offset=1.0), self.par(tag + ".b", c)
 
 
-def _nafblock(k, bf, c=64, hw=16):
+def _nafblock_params(k, c, grad=True):
     shapes = dict(norm1_w=(c,), norm1_b=(c,), conv1_w=(2 * c, c, 1, 1), conv1_b=(2 * c,), conv2_w=(2 * c, 1, 3, 3), conv2_b=(2 * c,),
                   conv3_w=(c, c, 1, 1), conv3_b=(c,), sca_w=(c, c, 1, 1), sca_b=(c,), norm2_w=(c,), norm2_b=(c,), conv4_w=(2 * c, c, 1, 1),
                   conv4_b=(2 * c,), conv5_w=(c, c, 1, 1), conv5_b=(c,), beta=(1, c, 1, 1), gamma=(1, c, 1, 1))
-    params = {n: k.par(n, *shapes[n], offset=1.0 if n in ("norm1_w", "norm2_w") else 0.0) for n in _lib.PARAM_FIELDS}
+    return {n: k.par(n, *shapes[n], offset=1.0 if n in ("norm1_w", "norm2_w") else 0.0, grad=grad) for n in _lib.PARAM_FIELDS}
+
+
+def _nafblock_bf16(k, c, hw, packed):
+    """bf16 storage at another width: ``packed`` = through a PackedWeightsBf16 cache, else packed in the call"""
+    return DF.nafblock_bf16(k.fmap("x", 2, c, hw, hw, True), _nafblock_params(k, c), packed=DF.PackedWeightsBf16() if packed else None)
+
+
+def _nafblock_local_bf16(k, c, hw, packed):
+    return DF.nafblock_local_bf16(k.fmap("x", 2, c, hw, hw, True, grad=False), _nafblock_params(k, c, grad=False), 5, 7,
+                                  packed=DF.PackedWeightsBf16() if packed else None)
+
+
+def _bottleneck(k, bf, b, c, cb, h, w, packed=False):
+    """cb = 2 c: the geometry of the one-call bf16 entry points; any other mid width: one call per conv -> LayerNorm group"""
+    ps = (k.par("conv1", cb, c, 1, 1), *k.ln("ln1", cb), k.par("conv2", cb, cb, 3, 3), *k.ln("ln2", cb), k.par("conv3", c, cb, 1, 1), *k.ln("ln3", c))
+    return DF.bottleneck(k.fmap("x", b, c, h, w, bf), *ps, packs=tuple(DF.PackedConvBf16() for _ in range(3)) if packed else None)
+
+
+def _wgrad_bf16(k, m, n, kk, with_bias):
+    dy = keyed_input(f"{k.name}.dy", (m, n), lo=-1.0, hi=1.0).to(DEV).to(BF)
+    x = keyed_input(f"{k.name}.x", (m, kk), lo=-1.0, hi=1.0).to(DEV).to(BF)
+    return DF.conv1x1_wgrad_bf16(dy, x, with_bias=with_bias)
+
+
+def _nafblock(k, bf, c=64, hw=16):
+    params = _nafblock_params(k, c)
     x = k.fmap("x", 2, c, hw, hw, bf)
     return DF.nafblock_bf16(x, params) if bf else DF.nafblock(x, params)
 
@@ -172,6 +198,20 @@ def _cases():
             k.fmap("x", 2, 64, 14, 16, bf), k.par("weight", 128, 64, 1, 1)))
         add("mix" + s, lambda k, bf=bf: DF.mix(k.fmap("prev", 2, 64, 14, 16, bf), k.fmap("feat", 2, 64, 14, 16, bf), k.par("w", 4), 1))
         add("prompt_mix" + s, lambda k, bf=bf: DF.prompt_mix(k.par("logits", 2, 5), k.par("param", 1, 5, 64, 16, 16), 14, 16, out_bf16=bf))
+    # the bf16 op host layer (LABNOTES 4r): the paths of the 128-tile weight-gradient helper, the 256-tile launch + finisher, the cached
+    # operand images and the TLSC forward that the cases above do not reach
+    add("bottleneck_bf16.c16.one_call", lambda k: _bottleneck(k, True, 2, 16, 32, 6, 10))
+    add("bottleneck_bf16.c16.one_call.packed", lambda k: _bottleneck(k, True, 2, 16, 32, 6, 10, packed=True))
+    add("bottleneck_bf16.c16.per_group", lambda k: _bottleneck(k, True, 2, 16, 24, 6, 10))
+    add("bottleneck_bf16.c128", lambda k: _bottleneck(k, True, 1, 128, 256, 16, 16))   # conv2's weight gradient: 256-tile kernel + finisher
+    for m, n, kk in ((300, 256, 512), (513, 64, 128)):
+        for wb in (True, False):
+            add(f"conv1x1_wgrad_bf16.{m}x{n}x{kk}.{'bias' if wb else 'nobias'}", lambda k, a=(m, n, kk), wb=wb: _wgrad_bf16(k, *a, wb), False)
+    for pk in (True, False):
+        add(f"nafblock_bf16.c256.{'packed' if pk else 'unpacked'}", lambda k, pk=pk: _nafblock_bf16(k, 256, 16, pk))   # grouped launch + finisher
+        add(f"nafblock_bf16.c128.{'packed' if pk else 'unpacked'}", lambda k, pk=pk: _nafblock_bf16(k, 128, 8, pk))    # four 128-tile weight gradients
+        add(f"nafblock_local_bf16.c64.{'packed' if pk else 'unpacked'}", lambda k, pk=pk: _nafblock_local_bf16(k, 64, 16, pk), False)
+    add("conv_nobias_bf16.k1", lambda k: DF.conv_nobias(k.fmap("x", 2, 48, 13, 16, True), k.par("weight", 96, 48, 1, 1)))
     return out
 
 
