@@ -155,8 +155,8 @@ class PromptIR_NoImg_DC(_DCHead):
     def __init__(self, feature_dims, num_res_blocks=2, num_classes=3, downsample=False, act_dtype="fp32"):
         super().__init__()
         if downsample and act_dtype != "fp32":
-            raise NotImplementedError("downsample=True (SwinIR's token taps) is fp32 only: SwinIR has no bf16 storage mode and its width "
-                                      "180 is not a multiple of 8")
+            raise NotImplementedError("downsample=True (SwinIR's token taps) is fp32 only: SwinIR's bf16 storage mode is inference-only (no tap "
+                                      "pass) and its width 180 is not a multiple of 8")
         self.downsample = bool(downsample)
         self._build_stages(feature_dims, num_res_blocks, num_classes)
         self._set_act_dtype(act_dtype)

@@ -12,6 +12,16 @@ Every Swin block is two autograd nodes: ``dcpt_swin_attn_*`` (LayerNorm in the q
 kernel on the un-shifted token rows -> proj GEMM + bias + residual) and ``dcpt_swin_mlp_*`` (LayerNorm -> fc1 -> erf GELU ->
 fc2 + bias + residual).  Token maps are channels_last (B, C, H, W) tensors, whose NHWC rows are the reference's (B, L, C) tokens.
 Child modules only own the parameters.
+
+``act_dtype="bf16"`` (this repo's extension, default "fp32"; ``network_g.act_dtype`` in the options, ``set_act_dtype`` on an existing network):
+INFERENCE of the restoration form (``upsampler=''``, ``'1conv'``) on bf16 activation storage.  Token maps are bf16 rows PADDED to 16 bytes:
+``Cp`` = embed_dim rounded up to a multiple of 8 (184 for 180, 40 for 36), heads padded to ``hdp`` = head_dim rounded up to a multiple of 8
+(32 for 30), pad columns exact zeros everywhere -- they come from zero-padded operands (``pad_block_params`` and the padded conv weights,
+built once per parameter version, cached per module as plain attributes and refreshed at the top of the forward where stale), not from
+masking in kernels.  ``conv_first`` emits the bf16 map, every block is ``dcpt_swin_attn_fwd_bf16`` + ``dcpt_swin_mlp_fwd_bf16``, the RSTB convs
+and ``conv_after_body`` are ``dcpt_conv3x3_res_fwd_bf16`` at width Cp, ``conv_last`` takes the bf16 map to the fp32 image.  Parameters,
+LayerNorm statistics, scores, softmax and accumulation stay fp32; the state_dict does not depend on the mode.  There is no backward pass and
+no tap pass: a bf16 forward that would have to record a graph, or ``hook=True``, raises ``NotImplementedError``.
 """
 from __future__ import annotations
 
@@ -22,6 +32,70 @@ from basicsr.utils.registry import ARCH_REGISTRY
 from dcpt_amd import functional as DF
 
 LN_EPS = 1e-5   # nn.LayerNorm default, the reference's norm_layer
+_ACT_DTYPES = ("fp32", "bf16")
+BF16_MAX_CP = 256   # launch_conv3x3_b2s_bf16 (conv_last) and the padded-row LayerNorm hold at most 256 channels per pixel
+
+
+def pad8(n: int) -> int:
+    """the padding rule of the bf16 path: rows (Cp) and heads (hdp) are rounded up to a multiple of 8 elements = 16 bytes"""
+    return (int(n) + 7) // 8 * 8
+
+
+def _pad_to(t, shape):
+    out = t.new_zeros(shape)
+    out[tuple(slice(0, n) for n in t.shape)] = t
+    return out
+
+
+def pad_block_params(blk):
+    """The zero-padded fp32 parameter set of one Swin block for the bf16 path (dict; on the parameters' device, CPU included):
+    norm1_w / norm1_b / norm2_w / norm2_b / proj_b / fc2_b [Cp], qkv_w [3 heads hdp][Cp] and qkv_b [3 heads hdp] with the reference's row
+    s*C + h*hd + d at (s*heads + h)*hdp + d, proj_w [Cp][heads hdp] with the reference's column h*hd + d at h*hdp + d, fc1_w [hidden][Cp],
+    fc1_b [hidden], fc2_w [Cp][hidden].  Pad rows, pad columns and pad entries are zero, so pad columns of every map stay exactly zero."""
+    C_, heads = blk.dim, blk.num_heads
+    hd = C_ // heads
+    Cp, hdp = pad8(C_), pad8(hd)
+    a, m = blk.attn, blk.mlp
+    hidden = m.fc1.weight.shape[0]
+    d = lambda t: t.detach().float()   # noqa: E731
+    return {
+        "norm1_w": _pad_to(d(blk.norm1.weight), (Cp,)), "norm1_b": _pad_to(d(blk.norm1.bias), (Cp,)),
+        "qkv_w": _pad_to(d(a.qkv.weight).reshape(3, heads, hd, C_), (3, heads, hdp, Cp)).reshape(3 * heads * hdp, Cp),
+        "qkv_b": _pad_to(d(a.qkv.bias).reshape(3, heads, hd), (3, heads, hdp)).reshape(3 * heads * hdp),
+        "proj_w": _pad_to(d(a.proj.weight).reshape(C_, heads, hd), (Cp, heads, hdp)).reshape(Cp, heads * hdp),
+        "proj_b": _pad_to(d(a.proj.bias), (Cp,)),
+        "norm2_w": _pad_to(d(blk.norm2.weight), (Cp,)), "norm2_b": _pad_to(d(blk.norm2.bias), (Cp,)),
+        "fc1_w": _pad_to(d(m.fc1.weight), (hidden, Cp)), "fc1_b": d(m.fc1.bias).clone(),
+        "fc2_w": _pad_to(d(m.fc2.weight), (Cp, hidden)), "fc2_b": _pad_to(d(m.fc2.bias), (Cp,)),
+    }
+
+
+_BF16_IMAGES = ("qkv_w", "proj_w", "fc1_w", "fc2_w")   # the GEMM weight operands: rounded to bf16 once, here
+
+
+def _cache(mod):
+    if getattr(mod, "_swin_bf16", None) is None:
+        mod._swin_bf16 = DF.SwinPackBf16()
+    return mod._swin_bf16
+
+
+def _refresh_conv(conv, cout_p, cin_p, packed=True):
+    """the zero-padded weight / bias of a 3 x 3 conv at the padded width (and, for the GEMM convs, the cache of its bf16 operand images);
+    returns (cache, rebuilt)"""
+    pk = _cache(conv)
+    if packed and pk.conv is None:
+        pk.conv = DF.PackedConvBf16()
+
+    def build():
+        return {"w": _pad_to(conv.weight.detach().float(), (cout_p, cin_p, 3, 3)), "b": _pad_to(conv.bias.detach().float(), (cout_p,))}
+
+    return pk, pk.refresh((conv.weight, conv.bias), build)
+
+
+def _refresh_norm(norm, Cp):
+    pk = _cache(norm)
+    return pk, pk.refresh((norm.weight, norm.bias), lambda: {"w": _pad_to(norm.weight.detach().float(), (Cp,)),
+                                                             "b": _pad_to(norm.bias.detach().float(), (Cp,))})
 
 
 def _pair(v):
@@ -64,7 +138,30 @@ class SwinTransformerBlock(nn.Module):
         self.norm2 = nn.LayerNorm(dim)
         self.mlp = Mlp(dim, hidden)
 
+    def _params(self):
+        a, m = self.attn, self.mlp
+        return (self.norm1.weight, self.norm1.bias, a.qkv.weight, a.qkv.bias, a.proj.weight, a.proj.bias, self.norm2.weight, self.norm2.bias,
+                m.fc1.weight, m.fc1.bias, m.fc2.weight, m.fc2.bias)
+
+    def refresh_bf16(self) -> bool:
+        """the block's padded operands for the bf16 path, rebuilt if a parameter changed; True if they were"""
+
+        def build():
+            P = pad_block_params(self)
+            return {k: (v.to(torch.bfloat16) if k in _BF16_IMAGES else v).contiguous() for k, v in P.items()}
+
+        return _cache(self).refresh(self._params(), build)
+
+    def _forward_bf16(self, x):
+        self.refresh_bf16()
+        t = self._swin_bf16.t
+        x = DF.swin_attn_bf16(x, (t["norm1_w"], t["norm1_b"], t["qkv_w"], t["qkv_b"], t["proj_w"], t["proj_b"]), self.dim, self.num_heads,
+                              pad8(self.dim // self.num_heads), self.window_size, self.shift_size)
+        return DF.swin_mlp_bf16(x, (t["norm2_w"], t["norm2_b"], t["fc1_w"], t["fc1_b"], t["fc2_w"], t["fc2_b"]), self.dim)
+
     def forward(self, x):
+        if x.dtype == torch.bfloat16:   # bf16 storage (SwinIR.set_act_dtype): the maps follow the dtype conv_first emitted
+            return self._forward_bf16(x)
         a, m = self.attn, self.mlp
         x = DF.swin_attn(x, self.norm1.weight, self.norm1.bias, a.qkv.weight, a.qkv.bias, a.proj.weight, a.proj.bias, self.num_heads,
                          self.window_size, self.shift_size)
@@ -95,6 +192,13 @@ def _apply_residual_conv(conv, t, res):
     return DF.conv3conv_res(t, conv[0].weight, conv[0].bias, conv[2].weight, conv[2].bias, conv[4].weight, conv[4].bias, res)
 
 
+def _conv_res_bf16(conv, t, res):
+    """bf16(res + conv(t)) at the padded width, from the conv's padded weight and its cached operand image"""
+    Cp = t.shape[1]
+    pk, _ = _refresh_conv(conv, Cp, Cp)
+    return DF.conv3x3_res_bf16(t, pk.t["w"], pk.t["b"], res, pk.conv)
+
+
 class RSTB(nn.Module):
     """residual Swin group: x + conv(blocks(x)), conv = one 3x3 conv or the 3conv bottleneck."""
 
@@ -107,6 +211,8 @@ class RSTB(nn.Module):
         t = x
         for blk in self.residual_group.blocks:
             t = blk(t)
+        if x.dtype == torch.bfloat16:
+            return _conv_res_bf16(self.conv, t, x)
         return _apply_residual_conv(self.conv, t, x)
 
 
@@ -158,8 +264,10 @@ class SwinIR(nn.Module):
     def __init__(self, img_size=128, patch_size=1, in_chans=3, embed_dim=180, depths=(6, 6, 6, 6, 6, 6), num_heads=(6, 6, 6, 6, 6, 6),
                  window_size=8, mlp_ratio=2.0, qkv_bias=True, qk_scale=None, drop_rate=0.0, attn_drop_rate=0.0, drop_path_rate=0.0,
                  norm_layer=nn.LayerNorm, ape=False, patch_norm=True, use_checkpoint=False, upscale=1, img_range=1.0, upsampler="",
-                 resi_connection="1conv", **kwargs):
+                 resi_connection="1conv", act_dtype="fp32", **kwargs):
         super().__init__()
+        if act_dtype not in _ACT_DTYPES:
+            raise ValueError(f"act_dtype must be one of {_ACT_DTYPES}, got {act_dtype!r}")
         if upsampler == "":
             if upscale != 1:
                 raise NotImplementedError(f"upscale={upscale} without an upsampler: the restoration form (upsampler '') has upscale 1")
@@ -224,7 +332,52 @@ class SwinIR(nn.Module):
             self.lrelu = nn.LeakyReLU(negative_slope=0.2, inplace=True)
         else:
             self.conv_last = nn.Conv2d(embed_dim, in_chans, 3, 1, 1)
+        self.resi_connection = resi_connection
         self.apply(self._init_weights)
+        self.pack_builds = 0   # how many cached operand sets the bf16 forwards have (re)built so far
+        self.set_act_dtype(act_dtype)
+
+    def set_act_dtype(self, act_dtype):
+        """"fp32" (the reference's arithmetic) or "bf16" (inference of the restoration form on bf16 activation storage); parameters untouched"""
+        if act_dtype not in _ACT_DTYPES:
+            raise ValueError(f"act_dtype must be one of {_ACT_DTYPES}, got {act_dtype!r}")
+        if act_dtype == "bf16":
+            if self.upsampler != "":
+                raise NotImplementedError(f"act_dtype='bf16' with upsampler={self.upsampler!r}: bf16 storage covers the restoration form (upsampler '') only")
+            if self.resi_connection == "3conv":
+                raise NotImplementedError("act_dtype='bf16' with resi_connection='3conv': bf16 storage covers '1conv' only")
+            if pad8(self.embed_dim) > BF16_MAX_CP:
+                raise NotImplementedError(f"act_dtype='bf16' with embed_dim={self.embed_dim}: the padded width {pad8(self.embed_dim)} is above "
+                                          f"{BF16_MAX_CP} (the ending conv and the padded-row LayerNorm hold at most {BF16_MAX_CP} channels per pixel)")
+            for layer in self.layers():
+                for blk in layer.residual_group.blocks:
+                    hidden = blk.mlp.fc1.weight.shape[0]
+                    if hidden % 8:
+                        raise NotImplementedError(f"act_dtype='bf16' with an mlp hidden width of {hidden}: it must be a multiple of 8")
+        self.act_dtype = act_dtype
+
+    def padded_dim(self) -> int:
+        """Cp: the row length of the bf16 token maps (embed_dim rounded up to a multiple of 8)"""
+        return pad8(self.embed_dim)
+
+    def _refresh_bf16(self):
+        """every stale padded operand set of the network rebuilt, the 3 x 3 operand images of the GEMM convs in one pack call"""
+        Cp, n = self.padded_dim(), 0
+        n += _refresh_conv(self.conv_first, Cp, self.conv_first.in_channels, packed=False)[1]
+        n += _refresh_conv(self.conv_last, self.conv_last.out_channels, Cp, packed=False)[1]
+        for norm in (self.patch_embed.norm, self.norm):
+            if norm is not None:
+                n += _refresh_norm(norm, Cp)[1]
+        convs = []
+        for layer in self.layers():
+            n += sum(blk.refresh_bf16() for blk in layer.residual_group.blocks)
+            convs.append(layer.conv)
+        convs.append(self.conv_after_body)
+        for conv in convs:
+            n += _refresh_conv(conv, Cp, Cp)[1]
+        DF.pack_convs_bf16([(c._swin_bf16.conv, c._swin_bf16.t["w"]) for c in convs])
+        self.pack_builds += n
+        return n
 
     @staticmethod
     def _init_weights(m):
@@ -241,7 +394,33 @@ class SwinIR(nn.Module):
     def block_window(self) -> int:
         return self.encode_layers[0].residual_group.blocks[0].window_size
 
+    def _forward_bf16(self, xn, mean):
+        """the restoration form on bf16 rows of padded_dim() channels: no torch op touches a feature map"""
+        self._refresh_bf16()
+        C_ = self.embed_dim
+        first, last = self.conv_first._swin_bf16.t, self.conv_last._swin_bf16.t
+        x_first = DF.conv3x3_in(xn, first["w"], first["b"], out_bf16=True)
+        t = x_first
+        if self.patch_embed.norm is not None:
+            pn = self.patch_embed.norm._swin_bf16.t
+            t = DF.ln_pad_bf16(t, pn["w"], pn["b"], C_, LN_EPS)
+        for layer in self.layers():
+            t = layer(t)
+        fn = self.norm._swin_bf16.t
+        t = DF.ln_pad_bf16(t, fn["w"], fn["b"], C_, LN_EPS)
+        res = _conv_res_bf16(self.conv_after_body, t, x_first)
+        out = DF.conv3x3_out(res, last["w"], last["b"], xn)
+        return DF.img_affine(out, mean, self.img_range, 1)
+
     def forward(self, x, hook=False):
+        bf = self.act_dtype == "bf16"
+        if bf:   # (before anything else, CPU tensors included)
+            if hook:
+                raise NotImplementedError("SwinIR: bf16 storage for SwinIR is inference-only: the tap pass (hook=True) belongs to training; "
+                                          "switch to set_act_dtype('fp32')")
+            if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+                raise NotImplementedError("SwinIR: bf16 storage for SwinIR is inference-only (there is no bf16 backward pass); run the forward under "
+                                          "torch.no_grad() or switch to set_act_dtype('fp32')")
         _, cin, H, W = x.shape
         ws = self.block_window()
         if H % ws or W % ws:
@@ -249,6 +428,8 @@ class SwinIR(nn.Module):
         self.mean = self.mean.type_as(x)
         mean = self.mean.reshape(-1).expand(cin) if self.mean.numel() == 1 else self.mean.reshape(-1)
         xn = DF.img_affine(x, mean, self.img_range, 0)
+        if bf:
+            return self._forward_bf16(xn, mean)
         x_first = DF.conv3x3_in(xn, self.conv_first.weight, self.conv_first.bias)
         t = x_first
         if self.patch_embed.norm is not None:

@@ -4,7 +4,7 @@ contract (that is bench.py).  Prints one JSON line per workload.
 
     python bench_extra.py --workload dcpt|dcpt_swinir|restormer|promptir|infer2k|naf|swinir|rcan|val_metrics|step_tail|tlsc [--dtype fp32|bf16] [--steps K] [--warmup W]
 
-``--dtype bf16`` (dcpt, naf, infer2k, restormer, promptir; rcan: the inference line only, next to fp32): every feature map of the encoder in bf16 storage with fp32 accumulation (act_dtype="bf16";
+``--dtype bf16`` (dcpt, naf, infer2k, restormer, promptir; rcan: the inference line only, next to fp32; swinir: the restoration form's inference, next to fp32): every feature map of the encoder in bf16 storage with fp32 accumulation (act_dtype="bf16";
 dcpt: the classifier head too unless --head-dtype fp32); images, parameters and the optimizer stay fp32.  Its lines carry BOTH
 rooflines: the bf16 MFMA peak (2.5 PF dense) and the HBM roof with the bf16 algorithmic bytes -- in bf16 the network is HBM-bound
 (SURVEY 8d).
@@ -222,6 +222,70 @@ def run_swinir(dev, steps=5, warmup=2, B=8, S=256, train_batches=(12, 8, 4, 2, 1
                    train_mfma_frac=round(flops / dt / 157.3e12, 4), train_peak_mem_gb=round(torch.cuda.max_memory_allocated() / 2 ** 30, 2))
         break
     return res
+
+
+def run_swinir_bf16(dev, steps=5, warmup=2, B=8, S=256):
+    """the restoration-form inference of run_swinir on bf16 activation storage (SwinIR.set_act_dtype): fp32 and bf16 calls alternate in this
+    process, the median per-call wall time of each (one synchronize per call), the peak memory of one call above the resident state (weights,
+    padded operand caches, workspaces) and the kernel launches of one bf16 call from the library's launch trace.  The protocol of
+    ``--workload rcan --dtype bf16``."""
+    import ctypes
+
+    from basicsr.archs import build_network
+    from dcpt_amd import _lib
+    from dcpt_amd.keyed_init import fill_module_
+
+    g = torch.Generator(device=dev).manual_seed(1234)
+    net = fill_module_(build_network(dict(type="SwinIR", **SWINIR_5D))).to(dev).eval()
+    fpp = swinir_fwd_flops_per_pixel(**SWINIR_5D)
+    x = torch.rand((B, 3, S, S), generator=g, device=dev)
+
+    def infer():
+        with torch.no_grad():
+            net(x)
+
+    times, peaks = {"fp32": [], "bf16": []}, {}
+    for act in ("fp32", "bf16"):   # warm both paths (workspaces, operand caches), then the peak of one call above what stays resident
+        net.set_act_dtype(act)
+        for _ in range(max(warmup, 1)):
+            infer()
+        torch.cuda.synchronize()
+        base = torch.cuda.memory_allocated()
+        torch.cuda.reset_peak_memory_stats()
+        infer()
+        torch.cuda.synchronize()
+        peaks[act] = torch.cuda.max_memory_allocated() - base
+    lib = _lib.load()
+    lib.dcpt_trace_enable(1)   # (net is in bf16 mode here)
+    infer()
+    torch.cuda.synchronize()
+    buf = ctypes.create_string_buffer(int(lib.dcpt_trace_read(None, 0)) + 16)
+    lib.dcpt_trace_read(buf, len(buf))
+    lib.dcpt_trace_enable(0)
+    tags = {ln.rpartition(" ")[0]: int(ln.rpartition(" ")[2]) for ln in buf.value.decode().splitlines() if ln.strip()}
+    # one tag per launch: the padded LayerNorm, the window kernel, every GEMM by its tile class, the two edge convs; + the two img_affine
+    launches = 2 + sum(v for k, v in tags.items() if k in ("swin_bf16.ln_pad_fwd", "swin_bf16.wattn_fwd", "edge.s2b_bf16", "edge.b2s_bf16")
+                       or (k.startswith("nt_bf16.") and ".epi_" not in k))
+    for _ in range(steps):
+        for act in ("fp32", "bf16"):
+            net.set_act_dtype(act)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            infer()
+            torch.cuda.synchronize()
+            times[act].append(time.perf_counter() - t0)
+    net.set_act_dtype("fp32")
+    med = {k: sorted(v)[len(v) // 2] for k, v in times.items()}
+    f = fpp * S * S * B
+    return dict(workload=f"SwinIR 5D (embed 180 -> rows of {net.padded_dim()}, depths [6]*6, heads [6]*6, ws 8, mlp 2) inference, {B} x {S}x{S}, "
+                         "fp32 and bf16 storage alternating",
+                fwd_gflop_per_image=round(fpp * S * S / 1e9, 1), infer_batch=B, infer_ms_per_batch=round(med["fp32"] * 1e3, 2),
+                infer_ms_per_batch_bf16=round(med["bf16"] * 1e3, 2), infer_ms_per_batch_min=round(min(times["fp32"]) * 1e3, 2),
+                infer_ms_per_batch_bf16_min=round(min(times["bf16"]) * 1e3, 2), bf16_speedup=round(med["fp32"] / med["bf16"], 3),
+                infer_tflops=round(f / med["fp32"] / 1e12, 2), infer_tflops_bf16=round(f / med["bf16"] / 1e12, 2),
+                peak_act_mem_mb=round(peaks["fp32"] / 2 ** 20, 1), peak_act_mem_mb_bf16=round(peaks["bf16"] / 2 ** 20, 1),
+                launches_per_call_bf16=launches, window_kernel_launches=tags.get("swin_bf16.wattn_fwd", 0),
+                timing="median of per-call wall times, one synchronize per call", steps=steps, warmup=warmup)
 
 
 def rcan_fwd_flops_per_lr_pixel(num_in_ch=3, num_out_ch=3, num_feat=64, num_group=10, num_block=16, upscale=4, **_):
@@ -655,7 +719,9 @@ def main():
         if (args.upsampler == "") != (args.upscale == 1):
             raise SystemExit("--upsampler and --upscale go together (an upsampler needs a scale above 1)")
         sr = args.upsampler != ""   # the SR forms are measured at 64 x 64 LR, training at the inference batch first
-        res = run_swinir(dev, args.steps, args.warmup, args.batch or 8, args.size or (64 if sr else 256),
+        if args.dtype not in ("fp32", "bf16") or (args.dtype == "bf16" and sr):
+            raise SystemExit("--workload swinir: --dtype fp32, or bf16 for the restoration form's inference")
+        res = run_swinir_bf16(dev, args.steps, args.warmup, args.batch or 8, args.size or 256) if args.dtype == "bf16" else run_swinir(dev, args.steps, args.warmup, args.batch or 8, args.size or (64 if sr else 256),
                          train_batches=(args.batch or 8, 4, 2, 1) if sr else (12, 8, 4, 2, 1), upsampler=args.upsampler, upscale=args.upscale)
     elif args.workload == "rcan":
         if args.dtype not in ("fp32", "bf16"):

@@ -89,6 +89,14 @@ class SwinMlpSaved(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in SWIN_MLP_SAVED_FIELDS]
 
 
+class SwinAttnBf16Params(C.Structure):   # dcpt_swin_attn_bf16_params: the field order of SwinAttnParams; the weights are bf16 operand images
+    _fields_ = [(n, C.c_void_p) for n in SWIN_ATTN_PARAM_FIELDS]
+
+
+class SwinMlpBf16Params(C.Structure):   # dcpt_swin_mlp_bf16_params
+    _fields_ = [(n, C.c_void_p) for n in SWIN_MLP_PARAM_FIELDS]
+
+
 RCAB_PARAM_FIELDS = ("conv1_w", "conv1_b", "conv2_w", "conv2_b", "ca1_w", "ca1_b", "ca2_w", "ca2_b")
 RCAB_SAVED_FIELDS = ("h", "t", "pooled", "s")
 
@@ -283,6 +291,12 @@ SIGNATURES = {
     "dcpt_conv3x3_res_fwd_bf16": (cint, [f32p, f32p, C.c_void_p, sz, f32p, f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint, stream_t]),
     "dcpt_conv3x3_ps_bf16_ws_bytes": (sz, [cint, cint, cint, cint, cint]),
     "dcpt_conv3x3_ps_fwd_bf16": (cint, [f32p, f32p, C.c_void_p, sz, f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint, cint, stream_t]),
+    "dcpt_ln_pad_fwd_bf16": (cint, [f32p, f32p, f32p, f32p, i64, cint, cint, C.c_float, stream_t]),
+    "dcpt_swin_attn_bf16_ws_bytes": (sz, [cint, cint, cint, cint, cint, cint, cint, cint]),
+    "dcpt_swin_attn_fwd_bf16": (cint, [C.POINTER(SwinAttnBf16Params), f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint, cint, cint, cint, cint,
+                                       cint, stream_t]),
+    "dcpt_swin_mlp_bf16_ws_bytes": (sz, [cint, cint, cint, cint, cint, cint]),
+    "dcpt_swin_mlp_fwd_bf16": (cint, [C.POINTER(SwinMlpBf16Params), f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint, cint, cint, stream_t]),
     "dcpt_conv3x3_ps_out_ws_bytes": (sz, [cint, cint, cint, cint, cint, cint, cint]),
     "dcpt_conv3x3_ps_out_fwd": (cint, [f32p, f32p, f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint, cint, cint, stream_t]),
     "dcpt_conv3x3_ps_out_bwd": (cint, [f32p, f32p, f32p, f32p, f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint, cint, cint, stream_t]),

@@ -91,7 +91,9 @@ enum GemmEpiB { EB_PLAIN = 0, EB_BIAS = 1, EB_RESID = 2, EB_SGBWD = 3, EB_BIASGA
                 // RCAN in bf16 storage (rcan_bf16.hip), conv3 operand only, 128-row kernel only:
                 EB_BIASRELU = 12,   // C = relu(acc + bias)
                 EB_BIASCOL = 13,    // C = acc + bias AND colpart[(tile, image)][n] = the fp32 column sums of acc + bias over the tile's rows (row tiles per image)
-                EB_PSHUF = 14 };    // C = PixelShuffle(psr)(acc + bias): the scatter epilogue with a bias, for psr in {2, 3}
+                EB_PSHUF = 14,      // C = PixelShuffle(psr)(acc + bias): the scatter epilogue with a bias, for psr in {2, 3}
+                // SwinIR in bf16 storage (swin_bf16.hip), plain A operand only, 128-row kernel only:
+                EB_BIASGELU = 15 }; // C = gelu(acc + bias), exact erf GELU on the fp32 value, one rounding
 
 // C[m][n] = sum_k A[m][k] * Bw[n][k]  on v_mfma_f32_32x32x16_bf16; A, Bw, C, res, aux, gate bf16; bias / cscale / colpart fp32.
 struct GemmNTB {

@@ -782,6 +782,7 @@ int launch_wgrad_mfma(const ST* big, const float* small, float* part, int nblk, 
 int launch_conv3x3_s2b_bf16(const float* x, const float* w, const float* bias, bf16_t* y, int B, int H, int W, int Cs, int Cb, int wmode,
                             hipStream_t s) {
     EDGE_CHECK("conv3x3_s2b_bf16", 2048);
+    trace_tag("edge.s2b_bf16");   // (next to the form's tag: the feature side is bf16)
     trace_tag(edge_mfma_ok(Cs, Cb) ? "edge.s2b_mfma" : "edge.s2b_valu");
     if (edge_mfma_ok(Cs, Cb)) DCPT_TRY(launch_s2b_mfma<bf16_t>(x, w, bias, y, B, H, W, Cs, Cb, wmode, s));
     else EDGE_GO_B(conv3x3_s2b_kernel, x, w, bias, y, B, H, W, Cb, wmode);
@@ -792,6 +793,7 @@ int launch_conv3x3_b2s_bf16(const bf16_t* x, const float* w, const float* bias, 
                             int wmode, hipStream_t s) {
     EDGE_CHECK("conv3x3_b2s_bf16", 2048);
     DCPT_CHECK_ARG(Cb <= 256, "conv3x3_b2s_bf16: Cb=%d > 256 (one wave must hold all channel quads of a pixel)", Cb);
+    trace_tag("edge.b2s_bf16");
     trace_tag(edge_mfma_ok(Cs, Cb) ? "edge.b2s_mfma" : "edge.b2s_valu");
     if (edge_mfma_ok(Cs, Cb)) DCPT_TRY(launch_b2s_mfma<bf16_t>(x, w, bias, res, y, B, H, W, Cs, Cb, wmode, s));
     else EDGE_GO_B(conv3x3_b2s_kernel, x, w, bias, res, y, B, H, W, Cb, wmode);

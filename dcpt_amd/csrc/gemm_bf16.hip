@@ -485,6 +485,7 @@ int launch_gemm_nt_bf16(const GemmNTB& pin, int epi, hipStream_t s) {
     if (epi == EB_DOTCOL) DCPT_CHECK_ARG(p.colpart && p.res && p.nb == 1, "gemm_nt_bf16: column-dot epilogue needs colpart and res");
     if (epi == EB_RESID) DCPT_CHECK_ARG(p.res, "gemm_nt_bf16: residual epilogue needs res");
     if (epi == EB_MUL) DCPT_CHECK_ARG(p.res && !p.conv3 && !p.gather2, "gemm_nt_bf16: multiply epilogue needs res and a plain A operand");
+    if (epi == EB_BIASGELU) DCPT_CHECK_ARG(!p.conv3 && !p.gather2 && p.nb == 1, "gemm_nt_bf16: GELU epilogue exists for the plain A operand only");
     if (epi == EB_SGBWD) DCPT_CHECK_ARG(p.aux && p.ldc == 2 * p.N, "gemm_nt_bf16: SimpleGate-backward epilogue needs aux and ldc == 2N");
     if (epi == EB_LNFWD)
         DCPT_CHECK_ARG(p.y2 && p.lnw && p.lnb && p.mu_out && p.rstd_out && p.ldc == p.N && p.nb == 1 && !p.gather2 &&
@@ -515,6 +516,7 @@ int launch_gemm_nt_bf16(const GemmNTB& pin, int epi, hipStream_t s) {
     }
     trace_tag(p.conv3 ? "nt_bf16.128_conv3" : p.gather2 ? "nt_bf16.128_gather2" : "nt_bf16.128");
     if (epi == EB_MUL) trace_tag("nt_bf16.epi_mul.128");
+    if (epi == EB_BIASGELU) trace_tag("nt_bf16.epi_biasgelu.128");   // (the only class that has it: gemm_nt_bf16_256_ok / _tall_ok refuse it)
     switch (epi) {
         case EB_PLAIN: return launch_nt<EB_PLAIN>(p, s);
         case EB_BIAS: return launch_nt<EB_BIAS>(p, s);
@@ -530,6 +532,7 @@ int launch_gemm_nt_bf16(const GemmNTB& pin, int epi, hipStream_t s) {
         case EB_BIASRELU: return launch_nt<EB_BIASRELU>(p, s);
         case EB_BIASCOL: return launch_nt<EB_BIASCOL>(p, s);
         case EB_PSHUF: return launch_nt<EB_PSHUF>(p, s);
+        case EB_BIASGELU: return launch_nt<EB_BIASGELU>(p, s);
     }
     dcpt_set_error("gemm_nt_bf16: unknown epilogue %d", epi);
     return DCPT_ERR_ARG;

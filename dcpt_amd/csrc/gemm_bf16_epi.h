@@ -25,6 +25,10 @@ __device__ __forceinline__ int64_t fine_elem_r(const P& p, int64_t m, int r) {
     return ((b * (r * p.gH) + r * h) * (int64_t)(r * p.gW) + r * w) * p.gC;
 }
 
+// erf GELU (torch.nn.GELU default): the expression of swin.hip's gelu_fwd_kernel
+__device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752f)); }
+__device__ __forceinline__ float4 gelu_erf4(float4 a) { return make_float4(gelu_erf(a.x), gelu_erf(a.y), gelu_erf(a.z), gelu_erf(a.w)); }
+
 template <int EK, int BM, int BN, int NT = 256>   // NT: threads of the block
 __device__ __forceinline__ void epilogue8(const GemmNTB& p, float* __restrict__ Cs, int64_t m0, int n0, int tid) {
     constexpr bool GATE = (EK == EB_BIASGATE);
@@ -39,7 +43,7 @@ __device__ __forceinline__ void epilogue8(const GemmNTB& p, float* __restrict__ 
     const bool nok = GATE ? (n < Ch) : (n < p.N);
     const int ldres = p.ldres ? p.ldres : p.ldc;
     f8 bias = f8_zero(), bias2 = f8_zero(), cs = f8{make_float4(1.f, 1.f, 1.f, 1.f), make_float4(1.f, 1.f, 1.f, 1.f)};
-    if constexpr (EK == EB_BIAS || EK == EB_RESID || EK == EB_MUL || EK == EB_BIASRELU || EK == EB_BIASCOL) {
+    if constexpr (EK == EB_BIAS || EK == EB_RESID || EK == EB_MUL || EK == EB_BIASRELU || EK == EB_BIASCOL || EK == EB_BIASGELU) {
         if (p.bias && nok) bias = f8_ld(p.bias + n);
     }
     if constexpr (GATE) {
@@ -160,6 +164,9 @@ __device__ __forceinline__ void epilogue8(const GemmNTB& p, float* __restrict__ 
                 const f8 u = f8_add(v, bias);
                 bbuf_st8(rsC, o, f8{make_float4(fmaxf(u.lo.x, 0.f), fmaxf(u.lo.y, 0.f), fmaxf(u.lo.z, 0.f), fmaxf(u.lo.w, 0.f)),
                                     make_float4(fmaxf(u.hi.x, 0.f), fmaxf(u.hi.y, 0.f), fmaxf(u.hi.z, 0.f), fmaxf(u.hi.w, 0.f))});
+            } else if constexpr (EK == EB_BIASGELU) {
+                const f8 u = f8_add(v, bias);
+                bbuf_st8(rsC, o, f8{gelu_erf4(u.lo), gelu_erf4(u.hi)});
             } else if constexpr (EK == EB_RESID) {
                 bbuf_st8(rsC, o, f8_fma(f8_add(v, bias), cs, pre1[it]));
             } else if constexpr (EK == EB_MUL) {

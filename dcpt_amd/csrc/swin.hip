@@ -17,29 +17,13 @@
 #include "gemm.h"
 #include "kernels.h"
 #include "prof.h"
+#include "swin_win.h"
 #include "../../include/dcpt_hip.h"
 
 namespace {
 
 constexpr float SWIN_LN_EPS = 1e-5f;   // nn.LayerNorm default
-constexpr int WT = 64;                 // max tokens per window (ws^2 <= 64)
-constexpr int SP = WT + 1;             // LDS row stride of the token x token tiles
-
-struct WinGeom {
-    int B, H, W, C, heads, hd, ws, shift, nwy, nwx, N, NP;
-};
-
-__device__ __forceinline__ int64_t win_token_row(const WinGeom& g, int win, int t) {
-    const int per_img = g.nwy * g.nwx;
-    const int b = win / per_img, r = win - b * per_img;
-    const int wy = r / g.nwx, wx = r - wy * g.nwx;
-    const int i = t / g.ws, j = t - i * g.ws;
-    int py = wy * g.ws + i + g.shift;
-    int px = wx * g.ws + j + g.shift;
-    if (py >= g.H) py -= g.H;
-    if (px >= g.W) px -= g.W;
-    return ((int64_t)b * g.H + py) * g.W + px;
-}
+constexpr int SP = WT + 1;             // LDS row stride of the token x token tiles (WT, WinGeom, win_token_row: swin_win.h)
 
 // one 32 x 32 fp32 MFMA tile: acc += sum_{k < K} A(i, k) B(k, j); A(i, k) = a[i * sa_i + k * sa_k], B(k, j) = b[k * sb_k + j * sb_j]
 // (LDS pointers already offset to the tile); K even
@@ -217,13 +201,6 @@ int check_window(int B, int H, int W, int C, int heads, int window, int shift, c
     DCPT_CHECK_ARG(H % window == 0 && W % window == 0, "%s: H=%d W=%d must be multiples of the window size %d", who, H, W, window);
     DCPT_CHECK_ARG(shift >= 0 && shift < window, "%s: shift %d must be in [0, window)", who, shift);
     return DCPT_OK;
-}
-
-WinGeom win_geom(int B, int H, int W, int C, int heads, int window, int shift) {
-    WinGeom g;
-    g.B = B; g.H = H; g.W = W; g.C = C; g.heads = heads; g.hd = C / heads; g.ws = window; g.shift = shift;
-    g.nwy = H / window; g.nwx = W / window; g.N = window * window; g.NP = g.N <= 32 ? 32 : 64;
-    return g;
 }
 
 int launch_wattn_fwd(const float* qkv, float* out, float* lse, const WinGeom& g, hipStream_t s) {

@@ -2356,6 +2356,128 @@ def conv3x3_ps_bf16(x, weight, bias, r, packed: PackedConvBf16 = None):
 
 
 # ------------------------------------------------------------------------------------------------
+# SwinIR on bf16 activation storage (include/dcpt_hip.h dcpt_swin_attn_fwd_bf16, dcpt_swin_mlp_fwd_bf16, dcpt_ln_pad_fwd_bf16): forward only, on
+# PADDED rows -- maps are torch.bfloat16 channels_last (B, Cp, H, W) with Cp = C rounded up to a multiple of 8 and exact zeros in the pad
+# channels; the operands (zero-padded fp32 vectors, bf16 weight images) are built by the caller (basicsr/archs/swinir_arch.py) once per
+# parameter version and kept in a SwinPackBf16.
+from ._lib import SwinAttnBf16Params, SwinMlpBf16Params  # noqa: E402
+
+
+class SwinPackBf16:
+    """Cache of ONE module's padded operands for the bf16 SwinIR path: ``t`` maps names to tensors, rebuilt by ``refresh`` when a parameter's
+    address or ``_version`` (or the pack generation) has changed -- the staleness rule of PackedConvBf16.  ``conv``: the PackedConvBf16 of the
+    module's padded 3 x 3 weight ``t['w']`` where it has one.  A plain attribute of its module: not part of the state_dict."""
+
+    def __init__(self):
+        self.key = None
+        self.t = {}
+        self.conv = None
+        self.stream = None
+        self.event = None
+
+    def __deepcopy__(self, memo):   # a copied module starts with an empty cache of its own
+        return type(self)()
+
+    def __reduce__(self):
+        return (type(self), ())
+
+    @staticmethod
+    def key_of(params):
+        return (_PACK_GENERATION,) + tuple((p.data_ptr(), p._version, p.device) for p in params)
+
+    def refresh(self, params, build) -> bool:
+        """rebuild ``t`` = build() if stale; True if it was.  ``build`` runs torch ops on the parameters' device: load-time work."""
+        key = self.key_of(params)
+        if key == self.key:
+            if self.stream is not None and self.stream != _stream(params[0].device):
+                torch.cuda.current_stream(params[0].device).wait_event(self.event)
+            return False
+        with torch.no_grad():
+            self.t = build()
+        if self.conv is not None:
+            self.conv.key = None   # (a new padded weight may reuse the old one's address)
+        self.key = key
+        if params[0].is_cuda:
+            self.event = torch.cuda.Event()
+            self.event.record(torch.cuda.current_stream(params[0].device))
+            self.stream = _stream(params[0].device)
+        return True
+
+
+def _swin_inference_only(name, *ts):
+    if _wants_grad(*ts):
+        raise NotImplementedError(f"{name}: bf16 storage for SwinIR is inference-only (there is no backward pass); run it under torch.no_grad()")
+
+
+def _padded_map(name, x, C_):
+    x = _nhwc(x)
+    Cp = x.shape[1]
+    if not 0 < C_ <= Cp or Cp % 8:
+        raise ValueError(f"{name}: a map of {Cp} channels for C={C_} (C <= Cp, Cp % 8 == 0)")
+    return x, Cp
+
+
+def ln_pad_bf16(x, weight_p, bias_p, C_, eps=1e-5):
+    """bf16(LayerNorm over the first C_ channels of every pixel * w + b), pad channels written as 0; weight_p / bias_p fp32 [Cp]"""
+    lib = _lib.load()
+    _require_gpu_bf16(x)
+    _require_gpu(weight_p, bias_p)
+    _swin_inference_only("ln_pad_bf16", x, weight_p, bias_p)
+    x, Cp = _padded_map("ln_pad_bf16", x, int(C_))
+    if tuple(weight_p.shape) != (Cp,) or tuple(bias_p.shape) != (Cp,):
+        raise ValueError(f"ln_pad_bf16: weight {tuple(weight_p.shape)} / bias {tuple(bias_p.shape)} for Cp={Cp}")
+    B, _, H, W = x.shape
+    y = _empty_nhwc_bf16(B, Cp, H, W, x.device)
+    _call(lib.dcpt_ln_pad_fwd_bf16, (x, _contig(weight_p), _contig(bias_p), y), (B * H * W, int(C_), Cp, float(eps)), x.device)
+    return y
+
+
+def _swin_operands(name, ops, shapes):
+    ops = [_contig(t.detach()) for t in ops]
+    for t, (shape, dtype) in zip(ops, shapes):
+        if tuple(t.shape) != shape or t.dtype != dtype or not t.is_cuda:
+            raise ValueError(f"{name}: operand {tuple(t.shape)} {t.dtype} on {t.device} (expected {shape} {dtype} on the device)")
+    return ops
+
+
+def swin_attn_bf16(x, ops, C_, heads, hdp, window, shift):
+    """bf16(x + proj(WMSA(qkv(LN1(x))))) on padded rows; ``ops`` = (norm_w [Cp], norm_b [Cp], qkv_w bf16 [3 heads hdp][Cp], qkv_b [3 heads hdp],
+    proj_w bf16 [Cp][heads hdp], proj_b [Cp]), zero-padded (dcpt_swin_attn_bf16_params)"""
+    lib = _lib.load()
+    _require_gpu_bf16(x)
+    _swin_inference_only("swin_attn_bf16", x, *ops)
+    C_, heads, hdp, window, shift = int(C_), int(heads), int(hdp), int(window), int(shift)
+    x, Cp = _padded_map("swin_attn_bf16", x, C_)
+    HD, f32, bf = heads * hdp, torch.float32, torch.bfloat16
+    ops = _swin_operands("swin_attn_bf16", ops, [((Cp,), f32), ((Cp,), f32), ((3 * HD, Cp), bf), ((3 * HD,), f32), ((Cp, HD), bf), ((Cp,), f32)])
+    B, _, H, W = x.shape
+    dev = x.device
+    y = _empty_nhwc_bf16(B, Cp, H, W, dev)
+    nws = _check_ws("swin_attn_bf16", lib.dcpt_swin_attn_bf16_ws_bytes(B, H, W, C_, Cp, heads, hdp, window),
+                    f"B={B} H={H} W={W} C={C_} Cp={Cp} heads={heads} hdp={hdp} window={window}")
+    _call(lib.dcpt_swin_attn_fwd_bf16, (_struct(SwinAttnBf16Params, ops), x, y), (B, H, W, C_, Cp, heads, hdp, window, shift), dev, nws)
+    return y
+
+
+def swin_mlp_bf16(x, ops, C_):
+    """bf16(x + fc2(gelu(fc1(LN2(x))))) on padded rows; ``ops`` = (norm_w [Cp], norm_b [Cp], fc1_w bf16 [hidden][Cp], fc1_b [hidden],
+    fc2_w bf16 [Cp][hidden], fc2_b [Cp]) (dcpt_swin_mlp_bf16_params)"""
+    lib = _lib.load()
+    _require_gpu_bf16(x)
+    _swin_inference_only("swin_mlp_bf16", x, *ops)
+    C_ = int(C_)
+    x, Cp = _padded_map("swin_mlp_bf16", x, C_)
+    hidden, f32, bf = int(ops[3].numel()), torch.float32, torch.bfloat16
+    ops = _swin_operands("swin_mlp_bf16", ops, [((Cp,), f32), ((Cp,), f32), ((hidden, Cp), bf), ((hidden,), f32), ((Cp, hidden), bf), ((Cp,), f32)])
+    B, _, H, W = x.shape
+    dev = x.device
+    y = _empty_nhwc_bf16(B, Cp, H, W, dev)
+    nws = _check_ws("swin_mlp_bf16", lib.dcpt_swin_mlp_bf16_ws_bytes(B, H, W, C_, Cp, hidden), f"B={B} H={H} W={W} C={C_} Cp={Cp} hidden={hidden}")
+    _call(lib.dcpt_swin_mlp_fwd_bf16, (_struct(SwinMlpBf16Params, ops), x, y), (B, H, W, C_, Cp, hidden), dev, nws)
+    return y
+
+
+# ------------------------------------------------------------------------------------------------
 # SwinIR super-resolution tail and the "3conv" residual (include/dcpt_hip.h dcpt_conv3x3_act_*, dcpt_up2_conv3x3_act_*,
 # dcpt_conv3x3_ps_out_*, dcpt_conv3conv_res_*).
 from ._lib import Conv3convParams  # noqa: E402

@@ -632,6 +632,45 @@ int dcpt_conv3x3_res_fwd_bf16(const uint16_t* x, const float* w, const void* wpa
 size_t dcpt_conv3x3_ps_bf16_ws_bytes(int B, int H, int W, int C, int r);
 int dcpt_conv3x3_ps_fwd_bf16(const uint16_t* x, const float* w, const void* wpacked, size_t wpacked_bytes, const float* bias, uint16_t* y,
                              void* ws, size_t ws_bytes, int B, int H, int W, int C, int r, dcpt_stream_t stream);
+/* ---- SwinIR inference on bf16 activation storage (swin_bf16.hip) -------------------------------------------------------------------
+ * Forward only, the DCPT variant (no relative-position bias, no shift mask).  PADDED ROWS: token maps are bf16 NHWC rows [M][Cp], M = B*H*W,
+ * Cp = C rounded up to a multiple of 8 (184 for 180), Cp <= 256; heads are padded to hdp = head_dim rounded up to a multiple of 8 (32 for
+ * 30), hdp <= 64: qkv is [M][3*heads*hdp] with slice (s, h, d) at column (s*heads + h)*hdp + d, the attention output [M][heads*hdp].  Pad
+ * columns hold exact zeros everywhere, BY CONSTRUCTION OF THE OPERANDS, which the caller builds once per parameter version: weight operand
+ * images (bf16, row-major [N][K]) with zero rows for pad outputs and zero columns for pad inputs, biases and LayerNorm vectors (fp32)
+ * zero-padded.  Larger multiples than 8 for Cp / hdp are the caller's choice.  Values are rounded to bf16 where they are stored (operand
+ * images, LN output, qkv, P, attention output, proj + residual, fc1 + GELU, fc2 + residual); statistics, scores, softmax and accumulation
+ * are fp32.  Every *_ws_bytes needs no device and returns 0 for unsupported arguments; arguments are checked before the first launch.  No
+ * synchronisation, no global state, no atomics (bit-identical run to run); a row's result does not depend on the batch around it.
+ * LayerNorm on padded rows (nn.LayerNorm, swinir_arch.py:325, :370 norm1 / norm2, PatchEmbed.norm :683-690, SwinIR.norm :964, :1056):
+ *   y[m][c] = bf16((x[m][c] - mean_m) * rstd_m * w[c] + b[c]) for c < C, 0 for C <= c < Cp; mean / biased variance in fp32, two-pass, over
+ *   the C real channels; w, b [Cp] (only the first C entries are read). */
+int dcpt_ln_pad_fwd_bf16(const uint16_t* x, const float* w, const float* b, uint16_t* y, int64_t M, int C, int Cp, float eps,
+                         dcpt_stream_t stream);
+/* Attention half (SwinTransformerBlock :319-372 up to the first residual, WindowAttention :142-195):
+ *   y = bf16(x + proj(WMSA(qkv(LN1(x)))))  in four launches: LayerNorm, qkv GEMM + bias, window kernel, proj GEMM + bias + residual.
+ *   Windows of window x window tokens on the map rolled by -shift (wrapping, unmasked) by addressing; per (window, head)
+ *   softmax(head_dim^-0.5 q k^T) v on the bf16 matrix pipe, the scale (REAL head_dim = C / heads) applied to the fp32 scores.
+ *   Supported: 0 < C <= Cp, Cp % 8 == 0, Cp <= 256, C % heads == 0, C / heads <= hdp <= 64, hdp % 8 == 0, window^2 <= 64, H and W multiples of
+ *   window, 0 <= shift < window. */
+typedef struct {
+    const float* norm_w; const float* norm_b;       /* [Cp] fp32, zero-padded */
+    const uint16_t* qkv_w; const float* qkv_b;      /* bf16 [3*heads*hdp][Cp], fp32 [3*heads*hdp]: row (s*heads + h)*hdp + d = reference row s*C + h*hd + d */
+    const uint16_t* proj_w; const float* proj_b;    /* bf16 [Cp][heads*hdp] (column h*hdp + d = reference column h*hd + d), fp32 [Cp] */
+} dcpt_swin_attn_bf16_params;
+size_t dcpt_swin_attn_bf16_ws_bytes(int B, int H, int W, int C, int Cp, int heads, int hdp, int window);
+int dcpt_swin_attn_fwd_bf16(const dcpt_swin_attn_bf16_params* p, const uint16_t* x, uint16_t* y, void* ws, size_t ws_bytes, int B, int H, int W,
+                            int C, int Cp, int heads, int hdp, int window, int shift, dcpt_stream_t stream);
+/* MLP half (:370, Mlp :17-41):  y = bf16(x + fc2(gelu(fc1(LN2(x))))), exact erf GELU in the fc1 GEMM's epilogue; three launches.
+ *   hidden % 8 == 0 (hidden rows are not padded). */
+typedef struct {
+    const float* norm_w; const float* norm_b;     /* [Cp] fp32, zero-padded */
+    const uint16_t* fc1_w; const float* fc1_b;    /* bf16 [hidden][Cp], fp32 [hidden] */
+    const uint16_t* fc2_w; const float* fc2_b;    /* bf16 [Cp][hidden], fp32 [Cp] */
+} dcpt_swin_mlp_bf16_params;
+size_t dcpt_swin_mlp_bf16_ws_bytes(int B, int H, int W, int C, int Cp, int hidden);
+int dcpt_swin_mlp_fwd_bf16(const dcpt_swin_mlp_bf16_params* p, const uint16_t* x, uint16_t* y, void* ws, size_t ws_bytes, int B, int H, int W,
+                           int C, int Cp, int hidden, dcpt_stream_t stream);
 /* ---- SwinIR super-resolution tail and the "3conv" residual (basicsr/archs/swinir_arch.py) ---------------------------------------------
  * fp32, NHWC feature maps, implicit-GEMM convs with the LeakyReLU in the GEMM epilogue.  Every *_ws_bytes returns 0 for unsupported
  * arguments.  Backward takes the activation mask from the sign of the saved OUTPUT y (y > 0: 1, else slope; 0 <= slope <= 1).
