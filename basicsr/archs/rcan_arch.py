@@ -15,6 +15,11 @@ INFERENCE on bf16 activation storage.  ``conv_first`` emits a bf16 map, every RC
 to the fp32 image: no fp32 feature map of the network's width exists.  Parameters, accumulation, the pooled mean, the CA FCs and the sigmoid
 stay fp32.  There is no backward pass: a bf16 forward that would have to record one raises ``NotImplementedError``.  The bf16 operand images
 of the 3 x 3 weights are cached per conv (``DF.PackedConvBf16``) and the stale ones refreshed in one call at the top of the forward.
+
+``act_dtype="bf16_res32"``: the same inference path with the RESIDUAL STREAM -- the map that runs through the 160 RCAB adds and the group
+convs -- kept in fp32 next to its bf16 image (``DF.Stream32``): ``conv_first`` emits fp32, every RCAB is ``dcpt_rcab_fwd_bf16_res32``, the group
+convs and ``conv_after_body`` are ``dcpt_conv3x3_res_fwd_bf16_res32`` (the latter writes only the bf16 map: the stream ends there).  Every conv
+operand is still bf16, h and t are bf16; only the stream's own rounding is gone.  Same restrictions, same parameters, same cached packs.
 """
 from __future__ import annotations
 
@@ -27,7 +32,8 @@ from basicsr.utils.registry import ARCH_REGISTRY
 from dcpt_amd import functional as DF
 
 
-_ACT_DTYPES = ("fp32", "bf16")
+_ACT_DTYPES = ("fp32", "bf16", "bf16_res32")
+_BF16_MODES = ("bf16", "bf16_res32")   # inference on bf16 maps; the second keeps the residual stream in fp32
 
 
 def _pack_of(conv):
@@ -65,6 +71,9 @@ class RCAB(nn.Module):
 
     def forward(self, x):
         c1, c2, att = self.rcab[0], self.rcab[2], self.rcab[3].attention
+        if isinstance(x, DF.Stream32):   # bf16 maps around the fp32 residual stream
+            return DF.Stream32(*DF.rcab_bf16_res32(x.s, x.sb, c1.weight, c1.bias, c2.weight, c2.bias, att[1].weight, att[1].bias, att[3].weight,
+                                                   att[3].bias, self.res_scale, _pack_of(c1), _pack_of(c2)))
         if x.dtype == torch.bfloat16:   # bf16 storage (RCAN.set_act_dtype): the maps follow the dtype conv_first emitted
             return DF.rcab_bf16(x, c1.weight, c1.bias, c2.weight, c2.bias, att[1].weight, att[1].bias, att[3].weight, att[3].bias, self.res_scale,
                                 _pack_of(c1), _pack_of(c2))
@@ -82,6 +91,8 @@ class ResidualGroup(nn.Module):
         t = x
         for blk in self.residual_group:
             t = blk(t)
+        if isinstance(x, DF.Stream32):
+            return DF.Stream32(*DF.conv3x3_res_bf16_res32(t.sb, self.conv.weight, self.conv.bias, x.s, _pack_of(self.conv), out_bf16=True))
         if x.dtype == torch.bfloat16:
             return DF.conv3x3_res_bf16(t, self.conv.weight, self.conv.bias, x, _pack_of(self.conv))
         return DF.conv3x3_res(t, self.conv.weight, self.conv.bias, x)
@@ -137,11 +148,12 @@ class RCAN(nn.Module):
         self.set_act_dtype(act_dtype)
 
     def set_act_dtype(self, act_dtype):
-        """"fp32" (the reference's arithmetic) or "bf16" (inference on bf16 activation storage); the parameters are untouched"""
+        """"fp32" (the reference's arithmetic), "bf16" (inference on bf16 activation storage) or "bf16_res32" (the same with the residual stream
+        in fp32); the parameters are untouched"""
         if act_dtype not in _ACT_DTYPES:
             raise ValueError(f"act_dtype must be one of {_ACT_DTYPES}, got {act_dtype!r}")
-        if act_dtype == "bf16" and self._num_feat % 8:
-            raise ValueError(f"act_dtype='bf16' needs num_feat % 8 == 0 (16-byte bf16 channel vectors), got num_feat={self._num_feat}")
+        if act_dtype in _BF16_MODES and self._num_feat % 8:
+            raise ValueError(f"act_dtype={act_dtype!r} needs num_feat % 8 == 0 (16-byte bf16 channel vectors), got num_feat={self._num_feat}")
         self.act_dtype = act_dtype
 
     def _convs_bf16(self):
@@ -160,7 +172,7 @@ class RCAN(nn.Module):
         mean = self.mean.reshape(-1)
         if mean.numel() != cin:
             raise ValueError(f"RCAN: rgb_mean has {mean.numel()} entries for a {cin}-channel input")
-        bf = self.act_dtype == "bf16"
+        bf, res32 = self.act_dtype in _BF16_MODES, self.act_dtype == "bf16_res32"
         if bf:
             if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
                 raise NotImplementedError("RCAN: bf16 storage for RCAN is inference-only (there is no bf16 backward pass); run the forward under "
@@ -168,11 +180,14 @@ class RCAN(nn.Module):
             if x.is_cuda:   # the operand images of all 3 x 3 weights in one call where they are stale; the convs then find their pack current
                 DF.pack_convs_bf16(self._convs_bf16())
         xn = DF.img_affine(x, mean, self.img_range, 0)
-        x_first = DF.conv3x3_in(xn, self.conv_first.weight, self.conv_first.bias, out_bf16=bf)
-        t = x_first
+        x_first = DF.conv3x3_in(xn, self.conv_first.weight, self.conv_first.bias, out_bf16=bf and not res32)
+        t = DF.Stream32(x_first, DF.to_bf16(x_first)) if res32 else x_first
         for group in self.body:
             t = group(t)
-        if bf:
+        if res32:   # the stream ends here: only the bf16 map the upsampler reads is written
+            res = DF.conv3x3_res_bf16_res32(t.sb, self.conv_after_body.weight, self.conv_after_body.bias, x_first, _pack_of(self.conv_after_body),
+                                            out_f32=False, out_bf16=True)[1]
+        elif bf:
             res = DF.conv3x3_res_bf16(t, self.conv_after_body.weight, self.conv_after_body.bias, x_first, _pack_of(self.conv_after_body))
         else:
             res = DF.conv3x3_res(t, self.conv_after_body.weight, self.conv_after_body.bias, x_first)

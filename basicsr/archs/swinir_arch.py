@@ -22,6 +22,12 @@ masking in kernels.  ``conv_first`` emits the bf16 map, every block is ``dcpt_sw
 and ``conv_after_body`` are ``dcpt_conv3x3_res_fwd_bf16`` at width Cp, ``conv_last`` takes the bf16 map to the fp32 image.  Parameters,
 LayerNorm statistics, scores, softmax and accumulation stay fp32; the state_dict does not depend on the mode.  There is no backward pass and
 no tap pass: a bf16 forward that would have to record a graph, or ``hook=True``, raises ``NotImplementedError``.
+
+``act_dtype="bf16_res32"``: the same inference path with the RESIDUAL STREAM -- the token map that runs through the 72 residual adds and the
+RSTB convs -- kept in fp32 padded rows (``DF.Stream32``): ``conv_first`` emits fp32 at width Cp, every LayerNorm reads fp32 rows and writes
+bf16, every block is ``dcpt_swin_attn_fwd_bf16_res32`` + ``dcpt_swin_mlp_fwd_bf16_res32`` (the last block of an RSTB also writes the bf16 image
+its conv reads), the RSTB convs are ``dcpt_conv3x3_res_fwd_bf16_res32`` with fp32 out, ``conv_after_body`` the same with only the bf16 map
+out.  Every GEMM operand is still bf16; only the stream's own rounding is gone.  Same restrictions, same parameters, same cached operands.
 """
 from __future__ import annotations
 
@@ -32,7 +38,8 @@ from basicsr.utils.registry import ARCH_REGISTRY
 from dcpt_amd import functional as DF
 
 LN_EPS = 1e-5   # nn.LayerNorm default, the reference's norm_layer
-_ACT_DTYPES = ("fp32", "bf16")
+_ACT_DTYPES = ("fp32", "bf16", "bf16_res32")
+_BF16_MODES = ("bf16", "bf16_res32")   # inference on bf16 maps; the second keeps the residual stream in fp32
 BF16_MAX_CP = 256   # launch_conv3x3_b2s_bf16 (conv_last) and the padded-row LayerNorm hold at most 256 channels per pixel
 
 
@@ -159,7 +166,20 @@ class SwinTransformerBlock(nn.Module):
                               pad8(self.dim // self.num_heads), self.window_size, self.shift_size)
         return DF.swin_mlp_bf16(x, (t["norm2_w"], t["norm2_b"], t["fc1_w"], t["fc1_b"], t["fc2_w"], t["fc2_b"]), self.dim)
 
+    def _forward_res32(self, x, out_bf16, inplace=False):
+        """the block on the fp32 residual stream x (padded rows); ``out_bf16``: the MLP half also writes the stream's bf16 image; ``inplace``: the
+        stream is updated where it lies (x is the caller's own map: an RSTB's blocks after its first) -- the MLP half always updates the
+        attention half's output in place, so a block holds one fp32 map, or none, besides its input"""
+        self.refresh_bf16()
+        t = self._swin_bf16.t
+        x = DF.swin_attn_bf16_res32(x, (t["norm1_w"], t["norm1_b"], t["qkv_w"], t["qkv_b"], t["proj_w"], t["proj_b"]), self.dim, self.num_heads,
+                                    pad8(self.dim // self.num_heads), self.window_size, self.shift_size, inplace=inplace)
+        return DF.Stream32(*DF.swin_mlp_bf16_res32(x, (t["norm2_w"], t["norm2_b"], t["fc1_w"], t["fc1_b"], t["fc2_w"], t["fc2_b"]), self.dim,
+                                                   out_bf16=out_bf16, inplace=True))
+
     def forward(self, x):
+        if isinstance(x, DF.Stream32):   # bf16 maps around the fp32 residual stream
+            return self._forward_res32(x.s, True)
         if x.dtype == torch.bfloat16:   # bf16 storage (SwinIR.set_act_dtype): the maps follow the dtype conv_first emitted
             return self._forward_bf16(x)
         a, m = self.attn, self.mlp
@@ -199,6 +219,15 @@ def _conv_res_bf16(conv, t, res):
     return DF.conv3x3_res_bf16(t, pk.t["w"], pk.t["b"], res, pk.conv)
 
 
+def _conv_res_res32(conv, t, res, stream_out):
+    """res + conv(t) at the padded width from the fp32 accumulator, t bf16 and res fp32: the new fp32 stream (``stream_out``), or only its bf16
+    map where the stream ends"""
+    Cp = t.shape[1]
+    pk, _ = _refresh_conv(conv, Cp, Cp)
+    y, yb = DF.conv3x3_res_bf16_res32(t, pk.t["w"], pk.t["b"], res, pk.conv, out_f32=stream_out, out_bf16=not stream_out)
+    return DF.Stream32(y, None) if stream_out else yb
+
+
 class RSTB(nn.Module):
     """residual Swin group: x + conv(blocks(x)), conv = one 3x3 conv or the 3conv bottleneck."""
 
@@ -208,6 +237,13 @@ class RSTB(nn.Module):
         self.conv = _residual_conv(dim, resi_connection)
 
     def forward(self, x):
+        if isinstance(x, DF.Stream32):   # only the last block writes the bf16 image of the stream: the conv's operand
+            blocks, t = self.residual_group.blocks, x
+            for i, blk in enumerate(blocks):   # the first block leaves x (the conv's residual) alone, the others update their own map in place
+                t = blk._forward_res32(t.s, i == len(blocks) - 1, inplace=i > 0)
+            sb = t.sb
+            del t   # (the stream's fp32 map is dead once its bf16 image exists: not held while the conv's output is allocated)
+            return _conv_res_res32(self.conv, sb, x.s, True)
         t = x
         for blk in self.residual_group.blocks:
             t = blk(t)
@@ -338,22 +374,23 @@ class SwinIR(nn.Module):
         self.set_act_dtype(act_dtype)
 
     def set_act_dtype(self, act_dtype):
-        """"fp32" (the reference's arithmetic) or "bf16" (inference of the restoration form on bf16 activation storage); parameters untouched"""
+        """"fp32" (the reference's arithmetic), "bf16" (inference of the restoration form on bf16 activation storage) or "bf16_res32" (the same
+        with the residual stream in fp32); parameters untouched"""
         if act_dtype not in _ACT_DTYPES:
             raise ValueError(f"act_dtype must be one of {_ACT_DTYPES}, got {act_dtype!r}")
-        if act_dtype == "bf16":
+        if act_dtype in _BF16_MODES:
             if self.upsampler != "":
-                raise NotImplementedError(f"act_dtype='bf16' with upsampler={self.upsampler!r}: bf16 storage covers the restoration form (upsampler '') only")
+                raise NotImplementedError(f"act_dtype={act_dtype!r} with upsampler={self.upsampler!r}: bf16 storage covers the restoration form (upsampler '') only")
             if self.resi_connection == "3conv":
-                raise NotImplementedError("act_dtype='bf16' with resi_connection='3conv': bf16 storage covers '1conv' only")
+                raise NotImplementedError(f"act_dtype={act_dtype!r} with resi_connection='3conv': bf16 storage covers '1conv' only")
             if pad8(self.embed_dim) > BF16_MAX_CP:
-                raise NotImplementedError(f"act_dtype='bf16' with embed_dim={self.embed_dim}: the padded width {pad8(self.embed_dim)} is above "
+                raise NotImplementedError(f"act_dtype={act_dtype!r} with embed_dim={self.embed_dim}: the padded width {pad8(self.embed_dim)} is above "
                                           f"{BF16_MAX_CP} (the ending conv and the padded-row LayerNorm hold at most {BF16_MAX_CP} channels per pixel)")
             for layer in self.layers():
                 for blk in layer.residual_group.blocks:
                     hidden = blk.mlp.fc1.weight.shape[0]
                     if hidden % 8:
-                        raise NotImplementedError(f"act_dtype='bf16' with an mlp hidden width of {hidden}: it must be a multiple of 8")
+                        raise NotImplementedError(f"act_dtype={act_dtype!r} with an mlp hidden width of {hidden}: it must be a multiple of 8")
         self.act_dtype = act_dtype
 
     def padded_dim(self) -> int:
@@ -398,22 +435,31 @@ class SwinIR(nn.Module):
         """the restoration form on bf16 rows of padded_dim() channels: no torch op touches a feature map"""
         self._refresh_bf16()
         C_ = self.embed_dim
+        res32 = self.act_dtype == "bf16_res32"
+        ln = DF.ln_pad_bf16_res32 if res32 else DF.ln_pad_bf16
         first, last = self.conv_first._swin_bf16.t, self.conv_last._swin_bf16.t
-        x_first = DF.conv3x3_in(xn, first["w"], first["b"], out_bf16=True)
+        x_first = DF.conv3x3_in(xn, first["w"], first["b"], out_bf16=not res32)
         t = x_first
         if self.patch_embed.norm is not None:
             pn = self.patch_embed.norm._swin_bf16.t
-            t = DF.ln_pad_bf16(t, pn["w"], pn["b"], C_, LN_EPS)
+            t = ln(t, pn["w"], pn["b"], C_, LN_EPS)
+            if res32:   # a LayerNorm output is a bf16 storage point; the stream starts from that value, exactly
+                t = DF.to_f32(t)
+        if res32:
+            t = DF.Stream32(t, None)
         for layer in self.layers():
             t = layer(t)
         fn = self.norm._swin_bf16.t
-        t = DF.ln_pad_bf16(t, fn["w"], fn["b"], C_, LN_EPS)
-        res = _conv_res_bf16(self.conv_after_body, t, x_first)
+        t = ln(t.s if res32 else t, fn["w"], fn["b"], C_, LN_EPS)
+        if res32:   # the stream ends here: only the bf16 map conv_last reads is written
+            res = _conv_res_res32(self.conv_after_body, t, x_first, False)
+        else:
+            res = _conv_res_bf16(self.conv_after_body, t, x_first)
         out = DF.conv3x3_out(res, last["w"], last["b"], xn)
         return DF.img_affine(out, mean, self.img_range, 1)
 
     def forward(self, x, hook=False):
-        bf = self.act_dtype == "bf16"
+        bf = self.act_dtype in _BF16_MODES
         if bf:   # (before anything else, CPU tensors included)
             if hook:
                 raise NotImplementedError("SwinIR: bf16 storage for SwinIR is inference-only: the tap pass (hook=True) belongs to training; "

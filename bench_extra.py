@@ -2,7 +2,7 @@
 """Secondary workloads of BASELINE.json (configs[2..4]) on ONE MI355X -- evidence for DESIGN.md, not the driver's
 contract (that is bench.py).  Prints one JSON line per workload.
 
-    python bench_extra.py --workload dcpt|dcpt_swinir|restormer|promptir|infer2k|naf|swinir|rcan|val_metrics|step_tail|tlsc [--dtype fp32|bf16] [--steps K] [--warmup W]
+    python bench_extra.py --workload dcpt|dcpt_swinir|restormer|promptir|infer2k|naf|swinir|rcan|val_metrics|step_tail|tlsc [--dtype fp32|bf16|bf16_res32] [--steps K] [--warmup W]
 
 ``--dtype bf16`` (dcpt, naf, infer2k, restormer, promptir; rcan: the inference line only, next to fp32; swinir: the restoration form's inference, next to fp32): every feature map of the encoder in bf16 storage with fp32 accumulation (act_dtype="bf16";
 dcpt: the classifier head too unless --head-dtype fp32); images, parameters and the optimizer stay fp32.  Its lines carry BOTH
@@ -224,11 +224,12 @@ def run_swinir(dev, steps=5, warmup=2, B=8, S=256, train_batches=(12, 8, 4, 2, 1
     return res
 
 
-def run_swinir_bf16(dev, steps=5, warmup=2, B=8, S=256):
+def run_swinir_bf16(dev, steps=5, warmup=2, B=8, S=256, res32=False):
     """the restoration-form inference of run_swinir on bf16 activation storage (SwinIR.set_act_dtype): fp32 and bf16 calls alternate in this
     process, the median per-call wall time of each (one synchronize per call), the peak memory of one call above the resident state (weights,
     padded operand caches, workspaces) and the kernel launches of one bf16 call from the library's launch trace.  The protocol of
-    ``--workload rcan --dtype bf16``."""
+    ``--workload rcan --dtype bf16``.  ``res32`` (--dtype bf16_res32): bf16_res32 calls (the fp32 residual stream) alternate with the two as
+    a third mode, and the line carries its median, minimum and peak memory as well."""
     import ctypes
 
     from basicsr.archs import build_network
@@ -244,8 +245,9 @@ def run_swinir_bf16(dev, steps=5, warmup=2, B=8, S=256):
         with torch.no_grad():
             net(x)
 
-    times, peaks = {"fp32": [], "bf16": []}, {}
-    for act in ("fp32", "bf16"):   # warm both paths (workspaces, operand caches), then the peak of one call above what stays resident
+    modes = ("fp32", "bf16_res32", "bf16") if res32 else ("fp32", "bf16")
+    times, peaks = {act: [] for act in modes}, {}
+    for act in modes:   # warm the paths (workspaces, operand caches), then the peak of one call above what stays resident
         net.set_act_dtype(act)
         for _ in range(max(warmup, 1)):
             infer()
@@ -267,7 +269,7 @@ def run_swinir_bf16(dev, steps=5, warmup=2, B=8, S=256):
     launches = 2 + sum(v for k, v in tags.items() if k in ("swin_bf16.ln_pad_fwd", "swin_bf16.wattn_fwd", "edge.s2b_bf16", "edge.b2s_bf16")
                        or (k.startswith("nt_bf16.") and ".epi_" not in k))
     for _ in range(steps):
-        for act in ("fp32", "bf16"):
+        for act in modes:
             net.set_act_dtype(act)
             torch.cuda.synchronize()
             t0 = time.perf_counter()
@@ -277,6 +279,11 @@ def run_swinir_bf16(dev, steps=5, warmup=2, B=8, S=256):
     net.set_act_dtype("fp32")
     med = {k: sorted(v)[len(v) // 2] for k, v in times.items()}
     f = fpp * S * S * B
+    extra = {}
+    if res32:
+        extra = dict(modes=list(modes), infer_ms_per_batch_bf16_res32=round(med["bf16_res32"] * 1e3, 2),
+                     infer_ms_per_batch_bf16_res32_min=round(min(times["bf16_res32"]) * 1e3, 2),
+                     bf16_res32_speedup=round(med["fp32"] / med["bf16_res32"], 3), peak_act_mem_mb_bf16_res32=round(peaks["bf16_res32"] / 2 ** 20, 1))
     return dict(workload=f"SwinIR 5D (embed 180 -> rows of {net.padded_dim()}, depths [6]*6, heads [6]*6, ws 8, mlp 2) inference, {B} x {S}x{S}, "
                          "fp32 and bf16 storage alternating",
                 fwd_gflop_per_image=round(fpp * S * S / 1e9, 1), infer_batch=B, infer_ms_per_batch=round(med["fp32"] * 1e3, 2),
@@ -285,7 +292,7 @@ def run_swinir_bf16(dev, steps=5, warmup=2, B=8, S=256):
                 infer_tflops=round(f / med["fp32"] / 1e12, 2), infer_tflops_bf16=round(f / med["bf16"] / 1e12, 2),
                 peak_act_mem_mb=round(peaks["fp32"] / 2 ** 20, 1), peak_act_mem_mb_bf16=round(peaks["bf16"] / 2 ** 20, 1),
                 launches_per_call_bf16=launches, window_kernel_launches=tags.get("swin_bf16.wattn_fwd", 0),
-                timing="median of per-call wall times, one synchronize per call", steps=steps, warmup=warmup)
+                timing="median of per-call wall times, one synchronize per call", steps=steps, warmup=warmup, **extra)
 
 
 def rcan_fwd_flops_per_lr_pixel(num_in_ch=3, num_out_ch=3, num_feat=64, num_group=10, num_block=16, upscale=4, **_):
@@ -306,7 +313,8 @@ def run_rcan(dev, steps=5, warmup=2, B=16, S=48, S_inf=256, dtype="fp32"):
     """the default x4 RCAN (64 features, 10 x 16 RCABs): one training step (fwd + L1 + bwd + AdamW) at B x S^2 LR patches, and inference of
     one S_inf^2 LR image; rates against the fp32-MFMA roof from the FLOPs counted above.  ``dtype="bf16"``: the inference line also holds the
     same network on bf16 activation storage (set_act_dtype), fp32 and bf16 images alternating in this process, with the peak memory of each
-    above the resident state (weights, weight packs, workspaces); training stays fp32 (there is no bf16 backward)"""
+    above the resident state (weights, weight packs, workspaces); training stays fp32 (there is no bf16 backward).  ``dtype="bf16_res32"``:
+    the same with bf16_res32 images (the fp32 residual stream) alternating as a third mode"""
     from basicsr.archs import build_network
     from dcpt_amd.keyed_init import fill_module_
     from dcpt_amd.optim import FusedAdamW
@@ -343,9 +351,10 @@ def run_rcan(dev, steps=5, warmup=2, B=16, S=48, S_inf=256, dtype="fp32"):
     infer_line = dict(workload=f"RCAN x4 inference, 1 x {S_inf}x{S_inf} LR -> {4 * S_inf}x{4 * S_inf}, fp32",
                       fwd_mflop_per_lr_pixel=round(fpp / 1e6, 3), ms_per_image=round(dt_inf * 1e3, 2), alg_tflops=round(f_inf / dt_inf / 1e12, 2),
                       mfma_frac=round(f_inf / dt_inf / 157.3e12, 4), roof_ms=round(f_inf / 157.3e12 * 1e3, 2), steps=steps, warmup=warmup)
-    if dtype == "bf16":
-        times, peaks = {"fp32": [], "bf16": []}, {}
-        for act in ("fp32", "bf16"):   # warm both paths (workspaces, weight packs), then the peak of one image above what stays resident
+    if dtype in ("bf16", "bf16_res32"):
+        modes = ("fp32", "bf16_res32", "bf16") if dtype == "bf16_res32" else ("fp32", "bf16")
+        times, peaks = {act: [] for act in modes}, {}
+        for act in modes:   # warm the paths (workspaces, weight packs), then the peak of one image above what stays resident
             net.set_act_dtype(act)
             for _ in range(max(warmup, 1)):
                 infer()
@@ -356,7 +365,7 @@ def run_rcan(dev, steps=5, warmup=2, B=16, S=48, S_inf=256, dtype="fp32"):
             torch.cuda.synchronize()
             peaks[act] = torch.cuda.max_memory_allocated() - base
         for _ in range(steps):
-            for act in ("fp32", "bf16"):
+            for act in modes:
                 net.set_act_dtype(act)
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
@@ -372,6 +381,11 @@ def run_rcan(dev, steps=5, warmup=2, B=16, S=48, S_inf=256, dtype="fp32"):
                           alg_tflops_bf16=round(f_inf / med["bf16"] / 1e12, 2), mfma_frac=round(f_inf / med["fp32"] / 157.3e12, 4),
                           peak_act_mem_mb=round(peaks["fp32"] / 2 ** 20, 1), peak_act_mem_mb_bf16=round(peaks["bf16"] / 2 ** 20, 1),
                           timing="median of per-image wall times, one synchronize per image")
+        if dtype == "bf16_res32":
+            infer_line.update(modes=list(modes), ms_per_image_bf16_res32=round(med["bf16_res32"] * 1e3, 2),
+                              ms_per_image_bf16_res32_min=round(min(times["bf16_res32"]) * 1e3, 2),
+                              bf16_res32_speedup=round(med["fp32"] / med["bf16_res32"], 3),
+                              peak_act_mem_mb_bf16_res32=round(peaks["bf16_res32"] / 2 ** 20, 1))
     return [train, infer_line]
 
 
@@ -547,7 +561,7 @@ def run_step_tail(dev, steps=50, warmup=5, rounds=7, max_norm=1.0, decay=0.999):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", required=True, choices=["dcpt", "dcpt_swinir", "restormer", "promptir", "infer2k", "naf", "swinir", "rcan", "val_metrics", "step_tail", "tlsc"])
-    ap.add_argument("--dtype", default="fp32", choices=["fp32", "bf16", "bf16_tail32", "bf16_edge32"])
+    ap.add_argument("--dtype", default="fp32", choices=["fp32", "bf16", "bf16_tail32", "bf16_edge32", "bf16_res32"])
     ap.add_argument("--head-dtype", default=None, choices=["fp32", "bf16"], help="dcpt: classifier-head activations (default: --dtype)")
     ap.add_argument("--restormer-save", default="balanced", choices=["auto", "lean", "balanced", "full"], help="what the Restormer halves keep for backward")
     ap.add_argument("--optimizer", default="dcpt", choices=["dcpt", "torch"], help="A/B: torch = torch.optim.AdamW(fused=True) instead of dcpt_amd.optim.FusedAdamW")
@@ -588,6 +602,8 @@ def main():
             raise SystemExit(subprocess.call([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
                                               "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__), *sys.argv[1:]]))
         return bench.spawn_ranks(args.gpus, script=os.path.abspath(__file__))
+    if args.dtype == "bf16_res32" and args.workload not in ("rcan", "swinir"):
+        raise SystemExit("--dtype bf16_res32: the fp32 residual stream exists for --workload rcan and swinir")
     rank, local_rank, world = (int(os.environ.get(k, d)) for k, d in (("RANK", "0"), ("LOCAL_RANK", "0"), ("WORLD_SIZE", "1")))
     if world != args.gpus:
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}: launch one rank per GPU")
@@ -719,13 +735,13 @@ def main():
         if (args.upsampler == "") != (args.upscale == 1):
             raise SystemExit("--upsampler and --upscale go together (an upsampler needs a scale above 1)")
         sr = args.upsampler != ""   # the SR forms are measured at 64 x 64 LR, training at the inference batch first
-        if args.dtype not in ("fp32", "bf16") or (args.dtype == "bf16" and sr):
-            raise SystemExit("--workload swinir: --dtype fp32, or bf16 for the restoration form's inference")
-        res = run_swinir_bf16(dev, args.steps, args.warmup, args.batch or 8, args.size or 256) if args.dtype == "bf16" else run_swinir(dev, args.steps, args.warmup, args.batch or 8, args.size or (64 if sr else 256),
+        if args.dtype not in ("fp32", "bf16", "bf16_res32") or (args.dtype != "fp32" and sr):
+            raise SystemExit("--workload swinir: --dtype fp32, or bf16 / bf16_res32 for the restoration form's inference")
+        res = run_swinir_bf16(dev, args.steps, args.warmup, args.batch or 8, args.size or 256, res32=args.dtype == "bf16_res32") if args.dtype != "fp32" else run_swinir(dev, args.steps, args.warmup, args.batch or 8, args.size or (64 if sr else 256),
                          train_batches=(args.batch or 8, 4, 2, 1) if sr else (12, 8, 4, 2, 1), upsampler=args.upsampler, upscale=args.upscale)
     elif args.workload == "rcan":
-        if args.dtype not in ("fp32", "bf16"):
-            raise SystemExit("--workload rcan: --dtype fp32 or bf16")
+        if args.dtype not in ("fp32", "bf16", "bf16_res32"):
+            raise SystemExit("--workload rcan: --dtype fp32, bf16 or bf16_res32")
         lines = run_rcan(dev, args.steps, args.warmup, args.batch or 16, args.size or 48, dtype=args.dtype)
         for line in lines[:-1]:
             print(json.dumps(line), flush=True)

@@ -297,6 +297,20 @@ SIGNATURES = {
                                        cint, stream_t]),
     "dcpt_swin_mlp_bf16_ws_bytes": (sz, [cint, cint, cint, cint, cint, cint]),
     "dcpt_swin_mlp_fwd_bf16": (cint, [C.POINTER(SwinMlpBf16Params), f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint, cint, cint, stream_t]),
+    # RCAN / SwinIR with an fp32 residual stream (act_dtype "bf16_res32")
+    "dcpt_rcab_bf16_res32_ws_bytes": (sz, [cint, cint, cint, cint, cint]),
+    "dcpt_rcab_fwd_bf16_res32": (cint, [C.POINTER(RcabParams), C.c_void_p, sz, C.c_void_p, sz, f32p, f32p, f32p, f32p, C.c_void_p, sz, cint, cint,
+                                        cint, cint, cint, C.c_float, stream_t]),
+    "dcpt_conv3x3_res_bf16_res32_ws_bytes": (sz, [cint, cint, cint, cint]),
+    "dcpt_conv3x3_res_fwd_bf16_res32": (cint, [f32p, f32p, C.c_void_p, sz, f32p, f32p, f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint,
+                                               stream_t]),
+    "dcpt_ln_pad_fwd_bf16_res32": (cint, [f32p, f32p, f32p, f32p, i64, cint, cint, C.c_float, stream_t]),
+    "dcpt_swin_attn_bf16_res32_ws_bytes": (sz, [cint, cint, cint, cint, cint, cint, cint, cint]),
+    "dcpt_swin_attn_fwd_bf16_res32": (cint, [C.POINTER(SwinAttnBf16Params), f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint, cint, cint, cint,
+                                             cint, cint, stream_t]),
+    "dcpt_swin_mlp_bf16_res32_ws_bytes": (sz, [cint, cint, cint, cint, cint, cint]),
+    "dcpt_swin_mlp_fwd_bf16_res32": (cint, [C.POINTER(SwinMlpBf16Params), f32p, f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint, cint, cint,
+                                            stream_t]),
     "dcpt_conv3x3_ps_out_ws_bytes": (sz, [cint, cint, cint, cint, cint, cint, cint]),
     "dcpt_conv3x3_ps_out_fwd": (cint, [f32p, f32p, f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint, cint, cint, stream_t]),
     "dcpt_conv3x3_ps_out_bwd": (cint, [f32p, f32p, f32p, f32p, f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint, cint, cint, stream_t]),

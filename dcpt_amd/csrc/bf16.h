@@ -93,7 +93,9 @@ enum GemmEpiB { EB_PLAIN = 0, EB_BIAS = 1, EB_RESID = 2, EB_SGBWD = 3, EB_BIASGA
                 EB_BIASCOL = 13,    // C = acc + bias AND colpart[(tile, image)][n] = the fp32 column sums of acc + bias over the tile's rows (row tiles per image)
                 EB_PSHUF = 14,      // C = PixelShuffle(psr)(acc + bias): the scatter epilogue with a bias, for psr in {2, 3}
                 // SwinIR in bf16 storage (swin_bf16.hip), plain A operand only, 128-row kernel only:
-                EB_BIASGELU = 15 }; // C = gelu(acc + bias), exact erf GELU on the fp32 value, one rounding
+                EB_BIASGELU = 15,   // C = gelu(acc + bias), exact erf GELU on the fp32 value, one rounding
+                // RCAN / SwinIR with an fp32 residual stream (act_dtype "bf16_res32"), plain A or conv3 operand, 128-row kernel only:
+                EB_RESID32 = 16 };  // v = acc + bias + res32 in fp32:  C32 = v (fp32 rows) and / or C = bf16(v); either output may be null, not both
 
 // C[m][n] = sum_k A[m][k] * Bw[n][k]  on v_mfma_f32_32x32x16_bf16; A, Bw, C, res, aux, gate bf16; bias / cscale / colpart fp32.
 struct GemmNTB {
@@ -144,6 +146,11 @@ struct GemmNTB {
     // channel c, and it is conv channel c psr^2 + i psr + j: Bw rows and bias entries are read in the conv's own order (a cached operand image
     // serves as it is), the permutation is applied by the loader / the epilogue.
     int psr;
+    // EB_RESID32: the fp32 residual stream.  res32 [M][ldres or ldc] and C32 [M][ldc] are fp32 rows with the strides (in elements) of res / C;
+    // C32 == null: only the bf16 image C is written (the stream ends here); C == null: only the stream.  A 128-row tile's fp32 rows span
+    // 128 * ld * 4 bytes of the 32-bit buffer window, twice the bf16 rows': launch_gemm_nt_bf16 checks that bound.
+    const float* res32;
+    float* C32;
 };
 // N (= row length) for which the two LayerNorm epilogues exist on a launch of M rows; conv3: the implicit 3 x 3 form of the GEMM
 bool gemm_nt_bf16_ln_epi_ok(int64_t M, int N, int K, int conv3, int gC);

@@ -216,7 +216,7 @@ int launch_nt(const GemmNTB& p, hipStream_t s) {
     const unsigned nb = (unsigned)(p.nb > 0 ? p.nb : 1);
     const int ncols = GATE ? p.N / 2 : p.N;
     constexpr bool CONV_ONLY = (EK == EB_BIASRELU || EK == EB_BIASCOL || EK == EB_PSHUF);   // (checked by launch_gemm_nt_bf16: no plain-A instance)
-    if constexpr (EK == EB_PLAIN || EK == EB_LNFWD || EK == EB_LNBWDM || EK == EB_RESID || CONV_ONLY) {
+    if constexpr (EK == EB_PLAIN || EK == EB_LNFWD || EK == EB_LNBWDM || EK == EB_RESID || EK == EB_RESID32 || CONV_ONLY) {
         if (p.conv3) {
             const int64_t tm = (EK == EB_BIASCOL) ? (p.M / p.P) * cdiv(p.P, 128) : cdiv64(p.M, 128);   // (EB_BIASCOL: row tiles per image)
             if (ncols <= 64) gemm_nt_bf16_kernel<128, 64, 4, 1, EK, 1><<<dim3((unsigned)(tm * cdiv(ncols, 64)), nb), dim3(256), 0, s>>>(p);
@@ -453,12 +453,12 @@ void tn_shape(int N, int K, int* bn, int* bk) {
 int launch_gemm_nt_bf16(const GemmNTB& pin, int epi, hipStream_t s) {
     GemmNTB p = pin;
     if (p.nb < 1) p.nb = 1;
-    DCPT_CHECK_ARG(p.A && p.Bw && (p.C || epi == EB_BIASGATE) && p.M > 0 && p.N > 0 && p.K > 0, "gemm_nt_bf16: null operand or empty problem");
+    DCPT_CHECK_ARG(p.A && p.Bw && (p.C || epi == EB_BIASGATE || (epi == EB_RESID32 && p.C32)) && p.M > 0 && p.N > 0 && p.K > 0, "gemm_nt_bf16: null operand or empty problem");
     DCPT_CHECK_ARG(p.K % 8 == 0 && p.N % 8 == 0 && p.lda % 8 == 0 && p.ldc % 8 == 0 && p.ldres % 8 == 0,
                    "gemm_nt_bf16: K=%d, N=%d and the row strides must be multiples of 8 (16-byte rows)", p.K, p.N);
     if (p.conv3)
-        DCPT_CHECK_ARG((epi == EB_PLAIN || epi == EB_LNFWD || epi == EB_LNBWDM || epi == EB_RESID || epi == EB_BIASRELU || epi == EB_BIASCOL ||
-                        epi == EB_PSHUF) &&
+        DCPT_CHECK_ARG((epi == EB_PLAIN || epi == EB_LNFWD || epi == EB_LNBWDM || epi == EB_RESID || epi == EB_RESID32 || epi == EB_BIASRELU ||
+                        epi == EB_BIASCOL || epi == EB_PSHUF) &&
                            p.gC % 8 == 0 && p.K == 9 * p.gC && p.nb == 1 && (double)(130 + 2 * p.gW + 2) * p.gC * 2.0 < 1.0e9,
                        "gemm_nt_bf16: conv3 needs the plain, a LayerNorm, the residual or an RCAN epilogue, K == 9 * gC, gC %% 8 == 0");
     if (epi == EB_BIASRELU || epi == EB_BIASCOL || epi == EB_PSHUF)
@@ -486,6 +486,9 @@ int launch_gemm_nt_bf16(const GemmNTB& pin, int epi, hipStream_t s) {
     if (epi == EB_RESID) DCPT_CHECK_ARG(p.res, "gemm_nt_bf16: residual epilogue needs res");
     if (epi == EB_MUL) DCPT_CHECK_ARG(p.res && !p.conv3 && !p.gather2, "gemm_nt_bf16: multiply epilogue needs res and a plain A operand");
     if (epi == EB_BIASGELU) DCPT_CHECK_ARG(!p.conv3 && !p.gather2 && p.nb == 1, "gemm_nt_bf16: GELU epilogue exists for the plain A operand only");
+    if (epi == EB_RESID32)   // (fp32 rows: a tile's last row ends at 4 (127 ld + N) bytes of its window)
+        DCPT_CHECK_ARG(p.res32 && !p.gather2 && p.nb == 1 && 4.0 * (128.0 * (double)(p.ldc > p.ldres ? p.ldc : p.ldres) + (double)p.N) < (double)WIN_BYTES,
+                       "gemm_nt_bf16: fp32-residual epilogue needs res32, one problem and 128 fp32 rows inside the 32-bit window");
     if (epi == EB_SGBWD) DCPT_CHECK_ARG(p.aux && p.ldc == 2 * p.N, "gemm_nt_bf16: SimpleGate-backward epilogue needs aux and ldc == 2N");
     if (epi == EB_LNFWD)
         DCPT_CHECK_ARG(p.y2 && p.lnw && p.lnb && p.mu_out && p.rstd_out && p.ldc == p.N && p.nb == 1 && !p.gather2 &&
@@ -499,6 +502,7 @@ int launch_gemm_nt_bf16(const GemmNTB& pin, int epi, hipStream_t s) {
     double bytes = mk + mn * (epi == EB_SGBWD ? 4 : epi == EB_BIASGATE ? 1.5 : 1) + (double)p.N * p.K;
     if (epi == EB_RESID || epi == EB_DOTCOL || epi == EB_SCATTER_ADD || epi == EB_MUL) bytes += mn;
     if (epi == EB_LNFWD) bytes += mn * (p.res ? 2 : 1);
+    if (epi == EB_RESID32) bytes += mn * (2 + (p.C32 ? 2 : 0) - (p.C ? 0 : 1));   // (in bf16 units: fp32 residual in, fp32 and / or bf16 out)
     if (epi == EB_LNBWDM) bytes += mn * (1 + (p.ymask ? 1 : 0) + (p.y2 ? 1 : 0));
     ProfScope prof(s, PROF_NT + 256 + epi, p.M, p.N, p.K, 2.0 * mn * p.K * p.nb, bytes * 2.0 * p.nb);
     if (epi == EB_MUL) trace_tag("nt_bf16.epi_mul");   // (next to the tile-class tag below: the TLSC block's attention product)
@@ -517,6 +521,7 @@ int launch_gemm_nt_bf16(const GemmNTB& pin, int epi, hipStream_t s) {
     trace_tag(p.conv3 ? "nt_bf16.128_conv3" : p.gather2 ? "nt_bf16.128_gather2" : "nt_bf16.128");
     if (epi == EB_MUL) trace_tag("nt_bf16.epi_mul.128");
     if (epi == EB_BIASGELU) trace_tag("nt_bf16.epi_biasgelu.128");   // (the only class that has it: gemm_nt_bf16_256_ok / _tall_ok refuse it)
+    if (epi == EB_RESID32) trace_tag("nt_bf16.epi_resid32.128");   // (128-row class only, as the GELU epilogue)
     switch (epi) {
         case EB_PLAIN: return launch_nt<EB_PLAIN>(p, s);
         case EB_BIAS: return launch_nt<EB_BIAS>(p, s);
@@ -533,6 +538,7 @@ int launch_gemm_nt_bf16(const GemmNTB& pin, int epi, hipStream_t s) {
         case EB_BIASCOL: return launch_nt<EB_BIASCOL>(p, s);
         case EB_PSHUF: return launch_nt<EB_PSHUF>(p, s);
         case EB_BIASGELU: return launch_nt<EB_BIASGELU>(p, s);
+        case EB_RESID32: return launch_nt<EB_RESID32>(p, s);
     }
     dcpt_set_error("gemm_nt_bf16: unknown epilogue %d", epi);
     return DCPT_ERR_ARG;

@@ -394,6 +394,7 @@ bool gemm_nt_bf16_256_ok(const GemmNTB& p, int epi, int min_tiles) {
     if (p.gather2 || epi == EB_SCATTER || epi == EB_SCATTER_ADD) return false;
     if (epi == EB_BIASRELU || epi == EB_BIASCOL || epi == EB_PSHUF) return false;   // (the RCAN epilogues: 128-row kernel only)
     if (epi == EB_BIASGELU) return false;   // (SwinIR's fc1 epilogue: 128-row kernel only)
+    if (epi == EB_RESID32) return false;    // (the fp32 residual stream: 128-row kernel only)
     const bool lnepi = epi == EB_LNFWD || epi == EB_LNBWDM;
     if (lnepi && p.N != 256) return false;
     if (p.conv3 && ((epi != EB_PLAIN && !lnepi) || p.gC % 64 != 0 || p.K != 9 * p.gC || p.K / 64 >= 2048 || (p.nb > 1))) return false;

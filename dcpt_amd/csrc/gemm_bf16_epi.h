@@ -43,7 +43,8 @@ __device__ __forceinline__ void epilogue8(const GemmNTB& p, float* __restrict__ 
     const bool nok = GATE ? (n < Ch) : (n < p.N);
     const int ldres = p.ldres ? p.ldres : p.ldc;
     f8 bias = f8_zero(), bias2 = f8_zero(), cs = f8{make_float4(1.f, 1.f, 1.f, 1.f), make_float4(1.f, 1.f, 1.f, 1.f)};
-    if constexpr (EK == EB_BIAS || EK == EB_RESID || EK == EB_MUL || EK == EB_BIASRELU || EK == EB_BIASCOL || EK == EB_BIASGELU) {
+    if constexpr (EK == EB_BIAS || EK == EB_RESID || EK == EB_MUL || EK == EB_BIASRELU || EK == EB_BIASCOL || EK == EB_BIASGELU ||
+                  EK == EB_RESID32) {
         if (p.bias && nok) bias = f8_ld(p.bias + n);
     }
     if constexpr (GATE) {
@@ -94,6 +95,10 @@ __device__ __forceinline__ void epilogue8(const GemmNTB& p, float* __restrict__ 
     f8 lnb8 = f8_zero();
     if constexpr (EK == EB_SGBWD) rsX = make_rsrc(p.aux + m0 * (2 * (int64_t)p.N));
     if constexpr (GATE) rsX = make_rsrc(p.gate + m0 * (int64_t)Ch);
+    if constexpr (EK == EB_RESID32) {   // fp32 rows: byte offsets are 4 (row * ld + n), the second half of a group 16 bytes on
+        rsR = make_rsrc(p.res32 + m0 * (int64_t)ldres);
+        rsX = make_rsrc(p.C32 + m0 * (int64_t)p.ldc);
+    }
     f8 dot = f8_zero(), dot2 = f8_zero(), lnw8 = f8_zero();
     if constexpr (EK == EB_LNFWD || EK == EB_LNBWDM) {
         if (nok) lnw8 = f8_ld(p.lnw + n);
@@ -118,6 +123,10 @@ __device__ __forceinline__ void epilogue8(const GemmNTB& p, float* __restrict__ 
             pre2[it] = f8_zero();
             if constexpr (EK == EB_RESID || EK == EB_DOTCOL || EK == EB_MUL)
                 pre1[it] = bbuf_ld8(rsR, ok ? ((uint32_t)rl * (uint32_t)ldres + (uint32_t)n) * 2u : ROW_SENT);
+            if constexpr (EK == EB_RESID32) {
+                const uint32_t ro = ok ? ((uint32_t)rl * (uint32_t)ldres + (uint32_t)n) * 4u : ROW_SENT;
+                pre1[it] = f8{buf_ld4(rsR, ro), buf_ld4(rsR, ro + 16u)};
+            }
             if constexpr (EK == EB_SCATTER_ADD) pre1[it] = bbuf_ld8(rsR, ok ? (uint32_t)((fine_elem(p, m0 + rl) - cbase) * 2) + coladd : ROW_SENT);
             if constexpr (EK == EB_SGBWD) {
                 const uint32_t xo = ok ? ((uint32_t)rl * (uint32_t)p.N * 2u + (uint32_t)n) * 2u : ROW_SENT;
@@ -169,6 +178,14 @@ __device__ __forceinline__ void epilogue8(const GemmNTB& p, float* __restrict__ 
                 bbuf_st8(rsC, o, f8{gelu_erf4(u.lo), gelu_erf4(u.hi)});
             } else if constexpr (EK == EB_RESID) {
                 bbuf_st8(rsC, o, f8_fma(f8_add(v, bias), cs, pre1[it]));
+            } else if constexpr (EK == EB_RESID32) {
+                const f8 u = f8_add(f8_add(v, bias), pre1[it]);   // fp32 all the way: the stream is not rounded
+                if (p.C32) {
+                    const uint32_t so = ok ? ((uint32_t)rl * (uint32_t)p.ldc + (uint32_t)n) * 4u : ROW_SENT;
+                    buf_st4(rsX, so, u.lo);
+                    buf_st4(rsX, so + 16u, u.hi);
+                }
+                if (p.C) bbuf_st8(rsC, o, u);   // (C == null: rsC was built from a null base and is never used, as with the gate epilogue's optional C)
             } else if constexpr (EK == EB_MUL) {
                 bbuf_st8(rsC, o, f8_mul(f8_add(v, bias), pre1[it]));   // (rows past M: the store is dropped by the range check)
             } else if constexpr (EK == EB_SGBWD) {

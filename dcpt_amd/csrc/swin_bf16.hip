@@ -6,6 +6,11 @@
 // Forward only: nothing is kept for a backward pass, there is none.  The RSTB conv, conv_after_body, conv_first and conv_last are the existing
 // dcpt_conv3x3_res_fwd_bf16 / dcpt_conv3x3_in_fwd_bf16 / dcpt_conv3x3_out_fwd_bf16 at the padded width.
 //
+// FP32 RESIDUAL STREAM (the *_bf16_res32 entry points, act_dtype "bf16_res32"): the map x that runs through the residual adds is fp32 padded
+// rows [M][Cp]; everything else is as above.  The LayerNorm reads the fp32 rows (same statistics, same bf16 output), the proj / fc2 GEMMs end
+// in EB_RESID32 (acc + bias + x in fp32, stored as fp32 rows, optionally also as the bf16 image an RSTB conv reads): the stream is never
+// rounded, every GEMM operand is still bf16.  One host path serves both forms (attn_run / mlp_run below).
+//
 // PADDED ROWS.  SwinIR's default width is 180 with 6 heads of 30 channels; every bf16 kernel of the library works on 16-byte rows.  The rule:
 //   Cp  = C rounded up to a multiple of 8 (184 for 180, 40 for 36): token maps are bf16 NHWC rows [M][Cp], M = B*H*W
 //   hdp = hd rounded up to a multiple of 8 (32 for 30, 8 for 6):    qkv is [M][3*heads*hdp], slice (s, h, d) at column (s*heads + h)*hdp + d,
@@ -49,7 +54,9 @@ constexpr int LNP_MAX_CP = 256;        // a row lives in 32 lanes of 8 channels
 // ---- LayerNorm on padded rows ---------------------------------------------------------------------------------------------------------------
 // y[m][c] = bf16((x[m][c] - mean) * rstd * w[c] + b[c]) for c < C, 0 for C <= c < Cp; statistics two-pass in fp32 over the C real channels
 // (biased variance, eps inside the sqrt).  A row lives in 32 lanes (lane q: channels 8q .. 8q + 7), 8 rows per 256-thread block and pass.
-__global__ __launch_bounds__(256) void ln_pad_fwd_bf16_kernel(const bf16_t* __restrict__ x, const float* __restrict__ w, const float* __restrict__ b,
+// TIn: bf16_t (bf16 rows) or float (the fp32 residual stream: two 16-byte loads per lane, the values enter the statistics unrounded).
+template <typename TIn>
+__global__ __launch_bounds__(256) void ln_pad_fwd_bf16_kernel(const TIn* __restrict__ x, const float* __restrict__ w, const float* __restrict__ b,
                                                               bf16_t* __restrict__ y, int64_t M, int C, int Cp, float eps) {
     const int q = threadIdx.x & 31, c0 = 8 * q;
     const bool cok = c0 < Cp;
@@ -66,7 +73,16 @@ __global__ __launch_bounds__(256) void ln_pad_fwd_bf16_kernel(const bf16_t* __re
         const int64_t row = rb * 8 + (threadIdx.x >> 5);
         const bool ok = row < M && cok;
         float v[8];
-        {
+        if constexpr (sizeof(TIn) == 4) {
+            float4 lo = f4_zero(), hi = f4_zero();
+            if (ok) {
+                const float* xr = x + row * (int64_t)Cp + c0;
+                lo = *reinterpret_cast<const float4*>(xr);
+                hi = *reinterpret_cast<const float4*>(xr + 4);
+            }
+            v[0] = lo.x; v[1] = lo.y; v[2] = lo.z; v[3] = lo.w;
+            v[4] = hi.x; v[5] = hi.y; v[6] = hi.z; v[7] = hi.w;
+        } else {
             uint4 u = make_uint4(0u, 0u, 0u, 0u);
             if (ok) u = *reinterpret_cast<const uint4*>(x + row * (int64_t)Cp + c0);
             v[0] = bf_lo(u.x); v[1] = bf_hi(u.x); v[2] = bf_lo(u.y); v[3] = bf_hi(u.y);
@@ -96,14 +112,32 @@ __global__ __launch_bounds__(256) void ln_pad_fwd_bf16_kernel(const bf16_t* __re
 
 bool ln_pad_ok(int64_t M, int C, int Cp) { return M > 0 && C > 0 && C <= Cp && Cp % 8 == 0 && Cp <= LNP_MAX_CP; }
 
-int launch_ln_pad_fwd_bf16(const bf16_t* x, const float* w, const float* b, bf16_t* y, int64_t M, int C, int Cp, float eps, hipStream_t s) {
+// the map a half reads and adds to: bf16 rows (x32 == null) or the fp32 residual stream (x == null)
+struct RowsIn {
+    const bf16_t* x;
+    const float* x32;
+};
+
+int launch_ln_pad_fwd_bf16(RowsIn in, const float* w, const float* b, bf16_t* y, int64_t M, int C, int Cp, float eps, hipStream_t s) {
     DCPT_CHECK_ARG(ln_pad_ok(M, C, Cp), "ln_pad_fwd_bf16: M=%lld C=%d Cp=%d (0 < C <= Cp, Cp a multiple of 8, at most %d)", (long long)M, C, Cp, LNP_MAX_CP);
-    trace_tag("swin_bf16.ln_pad_fwd");
+    trace_tag(in.x32 ? "swin_bf16.ln_pad_fwd_f32in" : "swin_bf16.ln_pad_fwd");
     int64_t nb = cdiv64(M, 8);
     if (nb > 4096) nb = 4096;
-    ln_pad_fwd_bf16_kernel<<<dim3((unsigned)nb), dim3(256), 0, s>>>(x, w, b, y, M, C, Cp, eps);
+    if (in.x32) ln_pad_fwd_bf16_kernel<float><<<dim3((unsigned)nb), dim3(256), 0, s>>>(in.x32, w, b, y, M, C, Cp, eps);
+    else ln_pad_fwd_bf16_kernel<bf16_t><<<dim3((unsigned)nb), dim3(256), 0, s>>>(in.x, w, b, y, M, C, Cp, eps);
     DCPT_CHECK_LAUNCH("ln_pad_fwd_bf16");
     return DCPT_OK;
+}
+
+// the GEMM that closes a half: y = x + (A Bw^T + bias) -- bf16 rows (EB_RESID), or the fp32 stream with its optional bf16 image (EB_RESID32)
+int launch_resid_gemm(GemmNTB g, RowsIn in, bf16_t* y, float* y32, hipStream_t s) {
+    g.C = y;
+    if (!in.x32) {
+        g.res = in.x;
+        return launch_gemm_nt_bf16(g, EB_RESID, s);
+    }
+    g.res32 = in.x32; g.C32 = y32;
+    return launch_gemm_nt_bf16(g, EB_RESID32, s);
 }
 
 // ---- window attention -----------------------------------------------------------------------------------------------------------------------
@@ -278,7 +312,9 @@ int launch_wattn_bf16(const bf16_t* qkv, bf16_t* out, const WinGeom& g, int hdp,
 
 // ---- argument checks (before the first launch; the workspace queries answer 0 without a device) -----------------------------------------------
 // the limits launch_gemm_nt_bf16 enforces for the widest launch of a half (N columns over M rows)
+// (the fp32-residual epilogue's own bound, 128 fp32 rows of Cp columns inside the 32-bit window, is implied by Cp <= LNP_MAX_CP: 132 KB)
 bool rows_ok(int B, int H, int W, int C, int Cp, int Nmax) {
+    static_assert(4.0 * (128.0 * LNP_MAX_CP + LNP_MAX_CP) < (double)WIN_BYTES, "EB_RESID32 rows of a half inside the buffer window");
     if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || C > Cp || Cp % 8 != 0 || Cp > LNP_MAX_CP) return false;
     if ((int64_t)H * W >= (1 << 30) || (int64_t)B * H * W >= (1ll << 40)) return false;
     const int64_t M = (int64_t)B * H * W;
@@ -318,13 +354,66 @@ size_t mlp_layout_b(int64_t M, int Cp, int hidden, void* base, size_t bytes, Mlp
     return a.off;
 }
 
+// ---- the two halves, both storage forms of the residual map (in / y / y32 as launch_resid_gemm's) ------------------------------------------
+int attn_run(const char* who, const dcpt_swin_attn_bf16_params* p, RowsIn in, bf16_t* y, float* y32, void* ws, size_t ws_bytes, int B, int H, int W,
+             int C, int Cp, int heads, int hdp, int window, int shift, hipStream_t s) {
+    DCPT_CHECK_ARG(p && (in.x || in.x32) && (y || y32) && p->norm_w && p->norm_b && p->qkv_w && p->qkv_b && p->proj_w && p->proj_b, "%s: null argument",
+                   who);
+    DCPT_CHECK_ARG(attn_ok(B, H, W, C, Cp, heads, hdp, window),
+                   "%s: B=%d H=%d W=%d C=%d Cp=%d heads=%d hdp=%d window=%d (0 < C <= Cp, Cp a multiple of 8 up to %d, C %% heads == 0, "
+                   "head_dim <= hdp <= 64 with hdp a multiple of 8, window^2 <= %d, H and W multiples of the window)",
+                   who, B, H, W, C, Cp, heads, hdp, window, LNP_MAX_CP, WT);
+    DCPT_CHECK_ARG(shift >= 0 && shift < window, "%s: shift %d must be in [0, window)", who, shift);
+    const int64_t M = (int64_t)B * H * W;
+    const int HD = heads * hdp;
+    AttnWsB w;
+    const size_t need = attn_layout_b(M, Cp, HD, ws, ws_bytes, &w);
+    DCPT_CHECK_WS(who, ws, ws_bytes, need);
+    trace_tag(in.x32 ? "swin_bf16.attn_fwd_res32" : "swin_bf16.attn_fwd");
+    DCPT_TRY(launch_ln_pad_fwd_bf16(in, p->norm_w, p->norm_b, w.xn, M, C, Cp, SWIN_LN_EPS, s));
+    GemmNTB g = gemm_ntb_linear(w.xn, Cp, M, Cp, p->qkv_w, 3 * HD, w.qkv, 3 * HD);
+    g.bias = p->qkv_b;
+    DCPT_TRY(launch_gemm_nt_bf16(g, EB_BIAS, s));
+    DCPT_TRY(launch_wattn_bf16(w.qkv, w.att, win_geom(B, H, W, C, heads, window, shift), hdp, s));
+    g = gemm_ntb_linear(w.att, HD, M, HD, p->proj_w, Cp, nullptr, Cp);
+    g.bias = p->proj_b;
+    return launch_resid_gemm(g, in, y, y32, s);
+}
+
+int mlp_run(const char* who, const dcpt_swin_mlp_bf16_params* p, RowsIn in, bf16_t* y, float* y32, void* ws, size_t ws_bytes, int B, int H, int W,
+            int C, int Cp, int hidden, hipStream_t s) {
+    DCPT_CHECK_ARG(p && (in.x || in.x32) && (y || y32) && p->norm_w && p->norm_b && p->fc1_w && p->fc1_b && p->fc2_w && p->fc2_b, "%s: null argument",
+                   who);
+    DCPT_CHECK_ARG(mlp_ok(B, H, W, C, Cp, hidden),
+                   "%s: B=%d H=%d W=%d C=%d Cp=%d hidden=%d (0 < C <= Cp, Cp a multiple of 8 up to %d, hidden a positive multiple of 8)", who, B, H, W, C,
+                   Cp, hidden, LNP_MAX_CP);
+    const int64_t M = (int64_t)B * H * W;
+    MlpWsB w;
+    const size_t need = mlp_layout_b(M, Cp, hidden, ws, ws_bytes, &w);
+    DCPT_CHECK_WS(who, ws, ws_bytes, need);
+    trace_tag(in.x32 ? "swin_bf16.mlp_fwd_res32" : "swin_bf16.mlp_fwd");
+    DCPT_TRY(launch_ln_pad_fwd_bf16(in, p->norm_w, p->norm_b, w.xn, M, C, Cp, SWIN_LN_EPS, s));
+    GemmNTB g = gemm_ntb_linear(w.xn, Cp, M, Cp, p->fc1_w, hidden, w.g, hidden);
+    g.bias = p->fc1_b;
+    DCPT_TRY(launch_gemm_nt_bf16(g, EB_BIASGELU, s));
+    g = gemm_ntb_linear(w.g, hidden, M, hidden, p->fc2_w, Cp, nullptr, Cp);
+    g.bias = p->fc2_b;
+    return launch_resid_gemm(g, in, y, y32, s);
+}
+
 }  // namespace
 
 // =====================================================================================================
 extern "C" int dcpt_ln_pad_fwd_bf16(const uint16_t* x, const float* w, const float* b, uint16_t* y, int64_t M, int C, int Cp, float eps,
                                     dcpt_stream_t stream) {
     DCPT_CHECK_ARG(x && w && b && y, "ln_pad_fwd_bf16: null argument");
-    return launch_ln_pad_fwd_bf16(x, w, b, y, M, C, Cp, eps, (hipStream_t)stream);
+    return launch_ln_pad_fwd_bf16(RowsIn{x, nullptr}, w, b, y, M, C, Cp, eps, (hipStream_t)stream);
+}
+
+extern "C" int dcpt_ln_pad_fwd_bf16_res32(const float* x, const float* w, const float* b, uint16_t* y, int64_t M, int C, int Cp, float eps,
+                                          dcpt_stream_t stream) {
+    DCPT_CHECK_ARG(x && w && b && y, "ln_pad_fwd_bf16_res32: null argument");
+    return launch_ln_pad_fwd_bf16(RowsIn{nullptr, x}, w, b, y, M, C, Cp, eps, (hipStream_t)stream);
 }
 
 // =====================================================================================================
@@ -332,30 +421,20 @@ extern "C" size_t dcpt_swin_attn_bf16_ws_bytes(int B, int H, int W, int C, int C
     if (!attn_ok(B, H, W, C, Cp, heads, hdp, window)) return 0;
     return attn_layout_b((int64_t)B * H * W, Cp, heads * hdp, nullptr, 0, nullptr);
 }
+// (the stream form keeps the same bf16 intermediates: LN output, qkv, attention output)
+extern "C" size_t dcpt_swin_attn_bf16_res32_ws_bytes(int B, int H, int W, int C, int Cp, int heads, int hdp, int window) {
+    return dcpt_swin_attn_bf16_ws_bytes(B, H, W, C, Cp, heads, hdp, window);
+}
 
 extern "C" int dcpt_swin_attn_fwd_bf16(const dcpt_swin_attn_bf16_params* p, const uint16_t* x, uint16_t* y, void* ws, size_t ws_bytes, int B, int H,
                                        int W, int C, int Cp, int heads, int hdp, int window, int shift, dcpt_stream_t stream) {
-    hipStream_t s = (hipStream_t)stream;
-    DCPT_CHECK_ARG(p && x && y && p->norm_w && p->norm_b && p->qkv_w && p->qkv_b && p->proj_w && p->proj_b, "swin_attn_fwd_bf16: null argument");
-    DCPT_CHECK_ARG(attn_ok(B, H, W, C, Cp, heads, hdp, window),
-                   "swin_attn_fwd_bf16: B=%d H=%d W=%d C=%d Cp=%d heads=%d hdp=%d window=%d (0 < C <= Cp, Cp a multiple of 8 up to %d, C %% heads == 0, "
-                   "head_dim <= hdp <= 64 with hdp a multiple of 8, window^2 <= %d, H and W multiples of the window)",
-                   B, H, W, C, Cp, heads, hdp, window, LNP_MAX_CP, WT);
-    DCPT_CHECK_ARG(shift >= 0 && shift < window, "swin_attn_fwd_bf16: shift %d must be in [0, window)", shift);
-    const int64_t M = (int64_t)B * H * W;
-    const int HD = heads * hdp;
-    AttnWsB w;
-    const size_t need = attn_layout_b(M, Cp, HD, ws, ws_bytes, &w);
-    DCPT_CHECK_WS("swin_attn_fwd_bf16", ws, ws_bytes, need);
-    trace_tag("swin_bf16.attn_fwd");
-    DCPT_TRY(launch_ln_pad_fwd_bf16(x, p->norm_w, p->norm_b, w.xn, M, C, Cp, SWIN_LN_EPS, s));
-    GemmNTB g = gemm_ntb_linear(w.xn, Cp, M, Cp, p->qkv_w, 3 * HD, w.qkv, 3 * HD);
-    g.bias = p->qkv_b;
-    DCPT_TRY(launch_gemm_nt_bf16(g, EB_BIAS, s));
-    DCPT_TRY(launch_wattn_bf16(w.qkv, w.att, win_geom(B, H, W, C, heads, window, shift), hdp, s));
-    g = gemm_ntb_linear(w.att, HD, M, HD, p->proj_w, Cp, y, Cp);
-    g.bias = p->proj_b; g.res = x;
-    return launch_gemm_nt_bf16(g, EB_RESID, s);
+    return attn_run("swin_attn_fwd_bf16", p, RowsIn{x, nullptr}, y, nullptr, ws, ws_bytes, B, H, W, C, Cp, heads, hdp, window, shift, (hipStream_t)stream);
+}
+
+extern "C" int dcpt_swin_attn_fwd_bf16_res32(const dcpt_swin_attn_bf16_params* p, const float* x, float* y, void* ws, size_t ws_bytes, int B, int H,
+                                             int W, int C, int Cp, int heads, int hdp, int window, int shift, dcpt_stream_t stream) {
+    return attn_run("swin_attn_fwd_bf16_res32", p, RowsIn{nullptr, x}, nullptr, y, ws, ws_bytes, B, H, W, C, Cp, heads, hdp, window, shift,
+                    (hipStream_t)stream);
 }
 
 // =====================================================================================================
@@ -363,24 +442,17 @@ extern "C" size_t dcpt_swin_mlp_bf16_ws_bytes(int B, int H, int W, int C, int Cp
     if (!mlp_ok(B, H, W, C, Cp, hidden)) return 0;
     return mlp_layout_b((int64_t)B * H * W, Cp, hidden, nullptr, 0, nullptr);
 }
+extern "C" size_t dcpt_swin_mlp_bf16_res32_ws_bytes(int B, int H, int W, int C, int Cp, int hidden) {
+    return dcpt_swin_mlp_bf16_ws_bytes(B, H, W, C, Cp, hidden);
+}
 
 extern "C" int dcpt_swin_mlp_fwd_bf16(const dcpt_swin_mlp_bf16_params* p, const uint16_t* x, uint16_t* y, void* ws, size_t ws_bytes, int B, int H,
                                       int W, int C, int Cp, int hidden, dcpt_stream_t stream) {
-    hipStream_t s = (hipStream_t)stream;
-    DCPT_CHECK_ARG(p && x && y && p->norm_w && p->norm_b && p->fc1_w && p->fc1_b && p->fc2_w && p->fc2_b, "swin_mlp_fwd_bf16: null argument");
-    DCPT_CHECK_ARG(mlp_ok(B, H, W, C, Cp, hidden),
-                   "swin_mlp_fwd_bf16: B=%d H=%d W=%d C=%d Cp=%d hidden=%d (0 < C <= Cp, Cp a multiple of 8 up to %d, hidden a positive multiple of 8)", B, H,
-                   W, C, Cp, hidden, LNP_MAX_CP);
-    const int64_t M = (int64_t)B * H * W;
-    MlpWsB w;
-    const size_t need = mlp_layout_b(M, Cp, hidden, ws, ws_bytes, &w);
-    DCPT_CHECK_WS("swin_mlp_fwd_bf16", ws, ws_bytes, need);
-    trace_tag("swin_bf16.mlp_fwd");
-    DCPT_TRY(launch_ln_pad_fwd_bf16(x, p->norm_w, p->norm_b, w.xn, M, C, Cp, SWIN_LN_EPS, s));
-    GemmNTB g = gemm_ntb_linear(w.xn, Cp, M, Cp, p->fc1_w, hidden, w.g, hidden);
-    g.bias = p->fc1_b;
-    DCPT_TRY(launch_gemm_nt_bf16(g, EB_BIASGELU, s));
-    g = gemm_ntb_linear(w.g, hidden, M, hidden, p->fc2_w, Cp, y, Cp);
-    g.bias = p->fc2_b; g.res = x;
-    return launch_gemm_nt_bf16(g, EB_RESID, s);
+    return mlp_run("swin_mlp_fwd_bf16", p, RowsIn{x, nullptr}, y, nullptr, ws, ws_bytes, B, H, W, C, Cp, hidden, (hipStream_t)stream);
+}
+
+extern "C" int dcpt_swin_mlp_fwd_bf16_res32(const dcpt_swin_mlp_bf16_params* p, const float* x, float* y, uint16_t* y_bf16, void* ws, size_t ws_bytes,
+                                            int B, int H, int W, int C, int Cp, int hidden, dcpt_stream_t stream) {
+    DCPT_CHECK_ARG(y, "swin_mlp_fwd_bf16_res32: null argument");
+    return mlp_run("swin_mlp_fwd_bf16_res32", p, RowsIn{nullptr, x}, y_bf16, y, ws, ws_bytes, B, H, W, C, Cp, hidden, (hipStream_t)stream);
 }

@@ -11,7 +11,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os as _os
-from typing import Dict, Tuple
+from typing import Dict, NamedTuple, Optional, Tuple
 
 import torch
 from torch.optim.optimizer import register_optimizer_step_post_hook
@@ -2475,6 +2475,131 @@ def swin_mlp_bf16(x, ops, C_):
     nws = _check_ws("swin_mlp_bf16", lib.dcpt_swin_mlp_bf16_ws_bytes(B, H, W, C_, Cp, hidden), f"B={B} H={H} W={W} C={C_} Cp={Cp} hidden={hidden}")
     _call(lib.dcpt_swin_mlp_fwd_bf16, (_struct(SwinMlpBf16Params, ops), x, y), (B, H, W, C_, Cp, hidden), dev, nws)
     return y
+
+
+# ------------------------------------------------------------------------------------------------
+# RCAN / SwinIR on bf16 maps around an fp32 residual stream (include/dcpt_hip.h, the *_bf16_res32 entry points): forward only.  The stream is
+# a torch.float32 channels_last map (SwinIR: padded to Cp), its image a torch.bfloat16 map of the same shape; operands as for the bf16 ops.
+class Stream32(NamedTuple):
+    """what the blocks of a bf16_res32 network hand on: the fp32 residual stream and its bf16 image (None where no conv will read it)"""
+    s: torch.Tensor
+    sb: Optional[torch.Tensor]
+
+
+def _require_stream(name, s, sb=None):
+    _require_gpu(s)
+    s = _nhwc(s)
+    if sb is None:
+        return s, None
+    _require_gpu_bf16(sb)
+    sb = _nhwc(sb)
+    if sb.shape != s.shape:
+        raise ValueError(f"{name}: bf16 image {tuple(sb.shape)} of a stream {tuple(s.shape)}")
+    return s, sb
+
+
+def rcab_bf16_res32(s, sb, conv1_w, conv1_b, conv2_w, conv2_b, ca1_w, ca1_b, ca2_w, ca2_b, res_scale=1.0, packed1: PackedConvBf16 = None,
+                    packed2: PackedConvBf16 = None):
+    """(S', bf16(S')) with S' = S + res_scale * CA(conv2(relu(conv1(Sb)))) in fp32: rcab_bf16 with the residual map ``s`` kept in fp32 and the
+    convs reading its bf16 image ``sb``"""
+    lib = _lib.load()
+    ps = (conv1_w, conv1_b, conv2_w, conv2_b, ca1_w, ca1_b, ca2_w, ca2_b)
+    _require_gpu(*ps)
+    _inference_only("rcab_bf16_res32", s, sb, *ps)
+    s, sb = _require_stream("rcab_bf16_res32", s, sb)
+    ps_ = [_contig(t.detach()) for t in ps]
+    B, Cc, H, W = s.shape
+    Cr = ps_[4].shape[0]
+    if tuple(ps_[0].shape) != (Cc, Cc, 3, 3) or tuple(ps_[2].shape) != (Cc, Cc, 3, 3) or ps_[4].numel() != Cr * Cc or ps_[6].numel() != Cr * Cc:
+        raise ValueError(f"rcab_bf16_res32: parameter shapes do not fit C={Cc} (conv {tuple(ps_[0].shape)} / {tuple(ps_[2].shape)}, CA {tuple(ps_[4].shape)})")
+    dev = s.device
+    y, yb = _empty_nhwc(B, Cc, H, W, dev), _empty_nhwc_bf16(B, Cc, H, W, dev)
+    nws = _check_ws("rcab_bf16_res32", lib.dcpt_rcab_bf16_res32_ws_bytes(B, H, W, Cc, Cr), f"B={B} H={H} W={W} C={Cc} Cr={Cr}; C % 8 == 0")
+    _call(lib.dcpt_rcab_fwd_bf16_res32, (_struct(RcabParams, ps_), *_pk(packed1, conv1_w), *_pk(packed2, conv2_w), s, sb, y, yb),
+          (B, H, W, Cc, Cr, float(res_scale)), dev, nws)
+    return y, yb
+
+
+def conv3x3_res_bf16_res32(x, weight, bias, res, packed: PackedConvBf16 = None, out_f32=True, out_bf16=False):
+    """v = res + conv3x3(x) + bias with x bf16 and the residual ``res`` fp32, from the fp32 accumulator; returns (v or None, bf16(v) or None)
+    as ``out_f32`` / ``out_bf16`` ask (at least one)"""
+    lib = _lib.load()
+    _require_gpu_bf16(x)
+    _require_gpu(weight, bias)
+    _inference_only("conv3x3_res_bf16_res32", x, res, weight, bias)
+    if not (out_f32 or out_bf16):
+        raise ValueError("conv3x3_res_bf16_res32: no output asked for")
+    res, x = _require_stream("conv3x3_res_bf16_res32", res, x)
+    w_, b_ = _contig(weight.detach()), _contig(bias.detach())
+    B, Cc, H, W = x.shape
+    _check_conv_weight("conv3x3_res_bf16_res32", w_, b_, Cc, Cc)
+    dev = x.device
+    y = _empty_nhwc(B, Cc, H, W, dev) if out_f32 else None
+    yb = _empty_nhwc_bf16(B, Cc, H, W, dev) if out_bf16 else None
+    nws = _check_ws("conv3x3_res_bf16_res32", lib.dcpt_conv3x3_res_bf16_res32_ws_bytes(B, H, W, Cc), f"B={B} H={H} W={W} C={Cc}; C % 8 == 0")
+    _call(lib.dcpt_conv3x3_res_fwd_bf16_res32, (x, w_, *_pk(packed, weight), b_, res, y, yb), (B, H, W, Cc), dev, nws)
+    return y, yb
+
+
+def ln_pad_bf16_res32(x, weight_p, bias_p, C_, eps=1e-5):
+    """ln_pad_bf16 of an fp32 padded map (the residual stream): the statistics see the unrounded values, the output is bf16"""
+    lib = _lib.load()
+    _require_gpu(x, weight_p, bias_p)
+    _swin_inference_only("ln_pad_bf16_res32", x, weight_p, bias_p)
+    x, Cp = _padded_map("ln_pad_bf16_res32", x, int(C_))
+    if tuple(weight_p.shape) != (Cp,) or tuple(bias_p.shape) != (Cp,):
+        raise ValueError(f"ln_pad_bf16_res32: weight {tuple(weight_p.shape)} / bias {tuple(bias_p.shape)} for Cp={Cp}")
+    B, _, H, W = x.shape
+    y = _empty_nhwc_bf16(B, Cp, H, W, x.device)
+    _call(lib.dcpt_ln_pad_fwd_bf16_res32, (x, _contig(weight_p), _contig(bias_p), y), (B * H * W, int(C_), Cp, float(eps)), x.device)
+    return y
+
+
+def _inplace_layout(name, x, inplace):
+    """an in-place update needs the caller's own dense NHWC memory: any other layout would be copied first and the copy updated"""
+    if inplace and (x.dim() != 4 or _nhwc(x) is not x):
+        raise ValueError(f"{name}: inplace=True needs a dense channels_last map (got shape {tuple(x.shape)}, strides {x.stride()})")
+
+
+def swin_attn_bf16_res32(x, ops, C_, heads, hdp, window, shift, inplace=False):
+    """x + proj(WMSA(qkv(LN1(x)))) in fp32 on padded rows: swin_attn_bf16 with the residual map fp32 in and out (``ops`` as there).
+    ``inplace``: the result overwrites x (the entry point allows y == x; x must be dense channels_last, else ValueError) -- for a caller that
+    owns x and keeps no other use of it"""
+    lib = _lib.load()
+    _require_gpu(x)
+    _swin_inference_only("swin_attn_bf16_res32", x, *ops)
+    C_, heads, hdp, window, shift = int(C_), int(heads), int(hdp), int(window), int(shift)
+    _inplace_layout("swin_attn_bf16_res32", x, inplace)
+    x, Cp = _padded_map("swin_attn_bf16_res32", x, C_)
+    HD, f32, bf = heads * hdp, torch.float32, torch.bfloat16
+    ops = _swin_operands("swin_attn_bf16_res32", ops, [((Cp,), f32), ((Cp,), f32), ((3 * HD, Cp), bf), ((3 * HD,), f32), ((Cp, HD), bf), ((Cp,), f32)])
+    B, _, H, W = x.shape
+    dev = x.device
+    y = x if inplace else _empty_nhwc(B, Cp, H, W, dev)
+    nws = _check_ws("swin_attn_bf16_res32", lib.dcpt_swin_attn_bf16_res32_ws_bytes(B, H, W, C_, Cp, heads, hdp, window),
+                    f"B={B} H={H} W={W} C={C_} Cp={Cp} heads={heads} hdp={hdp} window={window}")
+    _call(lib.dcpt_swin_attn_fwd_bf16_res32, (_struct(SwinAttnBf16Params, ops), x, y), (B, H, W, C_, Cp, heads, hdp, window, shift), dev, nws)
+    return y
+
+
+def swin_mlp_bf16_res32(x, ops, C_, out_bf16=False, inplace=False):
+    """(y, bf16(y) or None) with y = x + fc2(gelu(fc1(LN2(x)))) in fp32 on padded rows (``ops`` as swin_mlp_bf16's); ``out_bf16``: also the
+    bf16 image, the operand of the conv that follows an RSTB's last block; ``inplace``: y overwrites x, as swin_attn_bf16_res32's"""
+    lib = _lib.load()
+    _require_gpu(x)
+    _swin_inference_only("swin_mlp_bf16_res32", x, *ops)
+    C_ = int(C_)
+    _inplace_layout("swin_mlp_bf16_res32", x, inplace)
+    x, Cp = _padded_map("swin_mlp_bf16_res32", x, C_)
+    hidden, f32, bf = int(ops[3].numel()), torch.float32, torch.bfloat16
+    ops = _swin_operands("swin_mlp_bf16_res32", ops, [((Cp,), f32), ((Cp,), f32), ((hidden, Cp), bf), ((hidden,), f32), ((Cp, hidden), bf), ((Cp,), f32)])
+    B, _, H, W = x.shape
+    dev = x.device
+    y = x if inplace else _empty_nhwc(B, Cp, H, W, dev)
+    yb = _empty_nhwc_bf16(B, Cp, H, W, dev) if out_bf16 else None
+    nws = _check_ws("swin_mlp_bf16_res32", lib.dcpt_swin_mlp_bf16_res32_ws_bytes(B, H, W, C_, Cp, hidden), f"B={B} H={H} W={W} C={C_} Cp={Cp} hidden={hidden}")
+    _call(lib.dcpt_swin_mlp_fwd_bf16_res32, (_struct(SwinMlpBf16Params, ops), x, y, yb), (B, H, W, C_, Cp, hidden), dev, nws)
+    return y, yb
 
 
 # ------------------------------------------------------------------------------------------------

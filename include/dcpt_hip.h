@@ -671,6 +671,45 @@ typedef struct {
 size_t dcpt_swin_mlp_bf16_ws_bytes(int B, int H, int W, int C, int Cp, int hidden);
 int dcpt_swin_mlp_fwd_bf16(const dcpt_swin_mlp_bf16_params* p, const uint16_t* x, uint16_t* y, void* ws, size_t ws_bytes, int B, int H, int W,
                            int C, int Cp, int hidden, dcpt_stream_t stream);
+/* ---- RCAN and SwinIR inference: bf16 maps around an fp32 residual stream (act_dtype "bf16_res32"; rcan_bf16.hip, swin_bf16.hip) ----------
+ * The two sections above with ONE map kept in fp32: the residual stream S, the map every residual add reads and writes (RCAN: NHWC
+ * [M][C]; SwinIR: padded rows [M][Cp], pad columns exact zeros by construction as above).  Every other map is bf16 as above, and every
+ * GEMM / conv operand is bf16: the matrix pipe reads the bf16 image Sb = bf16(S), never S.  S is never rounded: an update whose branch is
+ * zero returns S bit for bit.  Restrictions, workspaces (the *_res32_ws_bytes queries answer what the bf16 queries answer), argument
+ * checks, determinism and batch consistency as in the two sections above; fp32 rows are 16-byte aligned.
+ * RCAN:  conv_first -> S (dcpt_conv3x3_in_fwd), Sb by dcpt_cast_f32_bf16.
+ *   RCAB:  h = bf16(relu(conv1(Sb) + b1)),  t = bf16(conv2(h) + b2),  s = the fp32 CA of the fp32 column sums as above;
+ *          y = S + res_scale * t * s in fp32,  y_bf16 = bf16(y)  (one pass).  x = S, x_bf16 = Sb; all four maps are required. */
+size_t dcpt_rcab_bf16_res32_ws_bytes(int B, int H, int W, int C, int Cr);
+int dcpt_rcab_fwd_bf16_res32(const dcpt_rcab_params* p, const void* wpacked1, size_t wpacked1_bytes, const void* wpacked2, size_t wpacked2_bytes,
+                             const float* x, const uint16_t* x_bf16, float* y, uint16_t* y_bf16, void* ws, size_t ws_bytes, int B, int H, int W,
+                             int C, int Cr, float res_scale, dcpt_stream_t stream);
+/* Residual conv (RCAN group conv / conv_after_body, SwinIR RSTB conv / conv_after_body at width Cp):  v = res + conv3x3(x) + bias from the
+ *   fp32 accumulator, x bf16 (the stream's image, or a LayerNorm output), res fp32;  y = v (fp32) and / or y_bf16 = bf16(v).  Either output
+ *   may be NULL, not both: y only where the next reader is a LayerNorm, both where it is a conv, y_bf16 only where the stream ends
+ *   (conv_after_body). */
+size_t dcpt_conv3x3_res_bf16_res32_ws_bytes(int B, int H, int W, int C);
+int dcpt_conv3x3_res_fwd_bf16_res32(const uint16_t* x, const float* w, const void* wpacked, size_t wpacked_bytes, const float* bias,
+                                    const float* res, float* y, uint16_t* y_bf16, void* ws, size_t ws_bytes, int B, int H, int W, int C,
+                                    dcpt_stream_t stream);
+/* SwinIR:  conv_first -> S at width Cp (dcpt_conv3x3_in_fwd with the zero-padded weight): the fp32 residual of conv_after_body.  With
+ *   patch_norm the map that enters the first RSTB is LN(conv_first): a LayerNorm output, i.e. a bf16 storage point as everywhere else, so
+ *   the stream through the RSTBs STARTS from that bf16 value (widened exactly by dcpt_cast_bf16_f32) and is never rounded afterwards.
+ *   LayerNorm on padded rows with fp32 input: dcpt_ln_pad_fwd_bf16 with x fp32 [M][Cp] -- the same two-pass fp32 statistics over the C real
+ *   channels (of the unrounded values), bf16 output, pad outputs 0.  No workspace. */
+int dcpt_ln_pad_fwd_bf16_res32(const float* x, const float* w, const float* b, uint16_t* y, int64_t M, int C, int Cp, float eps,
+                               dcpt_stream_t stream);
+/*   Attention half:  y = x + proj(WMSA(qkv(LN1(x)))) with x, y fp32 [M][Cp]; the four launches of dcpt_swin_attn_fwd_bf16, the proj GEMM
+ *   adding the fp32 residual to its fp32 accumulator.  y == x is allowed in both halves (the stream updated in place: the closing GEMM reads
+ *   and writes each element of it in one thread, and nothing else reads x after the LayerNorm); a partial overlap is not. */
+size_t dcpt_swin_attn_bf16_res32_ws_bytes(int B, int H, int W, int C, int Cp, int heads, int hdp, int window);
+int dcpt_swin_attn_fwd_bf16_res32(const dcpt_swin_attn_bf16_params* p, const float* x, float* y, void* ws, size_t ws_bytes, int B, int H, int W,
+                                  int C, int Cp, int heads, int hdp, int window, int shift, dcpt_stream_t stream);
+/*   MLP half:  y = x + fc2(gelu(fc1(LN2(x)))) with x, y fp32 [M][Cp];  y_bf16 (optional, NULL: not written) = bf16(y), the operand of the RSTB
+ *   conv after the last block of an RSTB. */
+size_t dcpt_swin_mlp_bf16_res32_ws_bytes(int B, int H, int W, int C, int Cp, int hidden);
+int dcpt_swin_mlp_fwd_bf16_res32(const dcpt_swin_mlp_bf16_params* p, const float* x, float* y, uint16_t* y_bf16, void* ws, size_t ws_bytes, int B,
+                                 int H, int W, int C, int Cp, int hidden, dcpt_stream_t stream);
 /* ---- SwinIR super-resolution tail and the "3conv" residual (basicsr/archs/swinir_arch.py) ---------------------------------------------
  * fp32, NHWC feature maps, implicit-GEMM convs with the LeakyReLU in the GEMM epilogue.  Every *_ws_bytes returns 0 for unsupported
  * arguments.  Backward takes the activation mask from the sign of the saved OUTPUT y (y > 0: 1, else slope; 0 <= slope <= 1).
