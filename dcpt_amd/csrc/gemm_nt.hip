@@ -249,10 +249,15 @@ int launch_cfg(const GemmNT& p, hipStream_t s) {
     const int64_t tiles = cdiv64(p.M, 128) * (GATE ? cdiv(p.N / 2, bn / 2) : cdiv(p.N, bn));
     const dim3 grid((unsigned)tiles, nbatch);
     if (bn == 64) {
+        trace_tag("nt_f32.128x64");
         gemm_nt_kernel<128, 64, 4, 1, AK, EK, 32><<<grid, dim3(256), 0, s>>>(p);
     } else if (bn == 96) {
-        if constexpr (!GATE && EK != E_LNBWD && EK != E_RESIDLN) gemm_nt_kernel<128, 96, 4, 1, AK, EK, 32><<<grid, dim3(256), 0, s>>>(p);
+        if constexpr (!GATE && EK != E_LNBWD && EK != E_RESIDLN) {
+            trace_tag("nt_f32.128x96");
+            gemm_nt_kernel<128, 96, 4, 1, AK, EK, 32><<<grid, dim3(256), 0, s>>>(p);
+        }
     } else {
+        trace_tag("nt_f32.128x128");
         gemm_nt_kernel<128, 128, 2, 2, AK, EK, 32><<<grid, dim3(256), 0, s>>>(p);
     }
     DCPT_CHECK_LAUNCH("gemm_nt");

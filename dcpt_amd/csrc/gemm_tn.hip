@@ -266,12 +266,14 @@ int launch_cfg(const GemmTN& p, hipStream_t s) {
     if constexpr (PLAIN) {
         if (bk == 96) {
             const int tiles = cdiv(p.N, 128) * cdiv(p.K, 96);
+            trace_tag("tn_f32.128x96");
             gemm_tn_kernel<128, 96, 4, 1, XK, YK><<<dim3(tiles * p.splits, nbatch), dim3(256), 0, s>>>(p);
             DCPT_CHECK_LAUNCH("gemm_tn");
             return DCPT_OK;
         }
         if (bn == 96) {
             const int tiles = cdiv(p.N, 96) * cdiv(p.K, 128);
+            trace_tag("tn_f32.96x128");
             gemm_tn_kernel<96, 128, 1, 4, XK, YK><<<dim3(tiles * p.splits, nbatch), dim3(256), 0, s>>>(p);
             DCPT_CHECK_LAUNCH("gemm_tn");
             return DCPT_OK;
@@ -279,15 +281,19 @@ int launch_cfg(const GemmTN& p, hipStream_t s) {
     }
     if (bn == 64 && bk == 64) {
         const int tiles = cdiv(p.N, 64) * cdiv(p.K, 64);
+        trace_tag("tn_f32.64x64");
         gemm_tn_kernel<64, 64, 2, 2, XK, YK><<<dim3(tiles * p.splits, nbatch), dim3(256), 0, s>>>(p);
     } else if (bk == 64) {
         const int tiles = cdiv(p.N, 128) * cdiv(p.K, 64);
+        trace_tag("tn_f32.128x64");
         gemm_tn_kernel<128, 64, 4, 1, XK, YK><<<dim3(tiles * p.splits, nbatch), dim3(256), 0, s>>>(p);
     } else if (bn == 64) {
         const int tiles = cdiv(p.N, 64) * cdiv(p.K, 128);
+        trace_tag("tn_f32.64x128");
         gemm_tn_kernel<64, 128, 1, 4, XK, YK><<<dim3(tiles * p.splits, nbatch), dim3(256), 0, s>>>(p);
     } else {
         const int tiles = cdiv(p.N, 128) * cdiv(p.K, 128);
+        trace_tag("tn_f32.128x128");
         gemm_tn_kernel<128, 128, 2, 2, XK, YK><<<dim3(tiles * p.splits, nbatch), dim3(256), 0, s>>>(p);
     }
     DCPT_CHECK_LAUNCH("gemm_tn");

@@ -928,6 +928,7 @@ int launch_gemm_nt_x3(const GemmNT& pin, int aload, int epi, hipStream_t s) {
         }
     }
     const dim3 grid((unsigned)(cdiv64(p.M, 256) * (p.N / 256)), (unsigned)(p.nb1 * p.nb2));
+    trace_tag("nt_f32.x3");
     switch (epi) {
         case E_PLAIN: gemm_nt_x3_kernel<E_PLAIN><<<grid, dim3(512), 0, s>>>(x); break;
         case E_BIAS: gemm_nt_x3_kernel<E_BIAS><<<grid, dim3(512), 0, s>>>(x); break;
@@ -970,6 +971,7 @@ bool gemm_tn_x3_ok(const GemmTN& p, int xload, int yload) {
 
 int launch_gemm_tn_x3(const GemmTN& p, int fp32_tiles_k, hipStream_t s) {
     const unsigned blocks = (unsigned)((p.N / 256) * (p.K / 256) * p.splits);
+    trace_tag("tn_f32.x3");
     gemm_tn_x3_kernel<<<dim3(blocks), dim3(512), 0, s>>>(p, fp32_tiles_k);
     DCPT_CHECK_LAUNCH("gemm_tn_x3");
     return DCPT_OK;

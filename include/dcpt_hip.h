@@ -270,7 +270,10 @@ int dcpt_bottleneck_bwd_bf16(const uint16_t* dout, const uint16_t* x, const dcpt
 /* ABI 15: launch trace for tests.  dcpt_trace_enable(1) clears and starts it: from then on every dispatch decision of the library counts the
  * kernel family it launched under a fixed name ("head.conv3x3+ln_fwd_epilogue", "nt_bf16.256", ...); dcpt_trace_read writes "name count\n"
  * lines into buf (NUL-terminated, truncated to cap) and returns the bytes the whole text needs.  Off (the default) it costs one load per launch.
- * A parity test uses it to assert WHICH kernel produced the result it compared (tests/kernel_trace.py). */
+ * A parity test uses it to assert WHICH kernel produced the result it compared (tests/kernel_trace.py).
+ * The fp32 GEMMs name the tile of every launch: "nt_f32.128x64" / "nt_f32.128x96" / "nt_f32.128x128" (BM x BN of launch_gemm_nt),
+ * "tn_f32.64x64" / ".128x64" / ".64x128" / ".128x128" / ".128x96" / ".96x128" (the N x K output tile of launch_gemm_tn), and
+ * "nt_f32.x3" / "tn_f32.x3" where the opt-in bf16x3 mode takes the launch instead. */
 int dcpt_trace_enable(int on);
 size_t dcpt_trace_read(char* buf, size_t cap);
 
