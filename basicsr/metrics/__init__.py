@@ -24,14 +24,18 @@ C2 = (0.03 L)^2, float64; tests/test_plumbing_cpu.py::test_metrics_match_indepen
 
 ``calculate_psnr_device`` / ``calculate_ssim_device`` / ``MetricSums`` score BCHW tensors that are already on the device with the fused HIP
 kernel of dcpt_amd/csrc/metrics.hip (same arithmetic, image_range 255 or 1); the host functions above stay the yardstick they are tested
-against (tests/test_gpu_metrics.py)."""
+against (tests/test_gpu_metrics.py).
+
+``calculate_ssim_pt`` (reference psnr_ssim.py:436-480) is the differentiable SSIM of the losses: (B, C, H, W) fp32 device tensors in, the
+per-image SSIM as a float64 tensor out, forward and gradient on the fused fp64 kernels of dcpt_amd/csrc/ssim_loss.hip."""
 from copy import deepcopy
 
 import numpy as np
 
 from basicsr.utils.registry import METRIC_REGISTRY
 
-__all__ = ["calculate_metric", "calculate_psnr", "calculate_ssim", "calculate_psnr_device", "calculate_ssim_device", "MetricSums"]
+__all__ = ["calculate_metric", "calculate_psnr", "calculate_ssim", "calculate_psnr_device", "calculate_ssim_device", "MetricSums",
+           "calculate_ssim_pt"]
 
 
 def _reorder(img, input_order):
@@ -203,6 +207,16 @@ def calculate_ssim_device(img, img2, crop_border, input_order="BCHW", test_y_cha
     acc = MetricSums(crop_border, input_order, test_y_channel, image_range, psnr=False)
     acc.add(img, img2)
     return acc.result()["ssim"][0]
+
+
+@METRIC_REGISTRY.register()
+def calculate_ssim_pt(img, img2, crop_border, test_y_channel=False, image_range=255, **kwargs):
+    """the reference's ``calculate_ssim_pt`` (psnr_ssim.py:436-480, ``_ssim_pth`` :515-559): images in [0, 1] of shape (B, 3 / 1, H, W),
+    cropped, optionally reduced to luma, compared in float64 with C1 = (0.01 image_range)^2, C2 = (0.03 image_range)^2; returns the
+    float64 tensor (B,) of per-image SSIM, differentiable with respect to ``img`` (dcpt_amd.functional.ssim_pt; nothing synchronises)"""
+    from dcpt_amd import functional as DF
+
+    return DF.ssim_pt(img, img2, crop_border, test_y_channel, image_range)
 
 
 def calculate_metric(data, opt):

@@ -63,7 +63,8 @@ class BaseModel:
             keys = list(pending.keys())
             vals = [pending[k] for k in keys]
             if vals and all(torch.is_tensor(v) for v in vals) and len({v.device for v in vals}) == 1:
-                floats = torch.stack([v.detach().float().reshape(()) for v in vals]).tolist()   # one transfer, one synchronisation
+                # one transfer, one synchronisation (as float64: exact for an fp32 loss, and a float64 loss -- SSIMLoss -- keeps its digits)
+                floats = torch.stack([v.detach().double().reshape(()) for v in vals]).tolist()
             else:
                 floats = [float(v) for v in vals]
             self.__dict__["_log_values"] = OrderedDict(zip(keys, floats))

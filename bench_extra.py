@@ -2,7 +2,7 @@
 """Secondary workloads of BASELINE.json (configs[2..4]) on ONE MI355X -- evidence for DESIGN.md, not the driver's
 contract (that is bench.py).  Prints one JSON line per workload.
 
-    python bench_extra.py --workload dcpt|dcpt_swinir|restormer|promptir|infer2k|naf|swinir|rcan|val_metrics|step_tail|tlsc [--dtype fp32|bf16|bf16_res32] [--steps K] [--warmup W]
+    python bench_extra.py --workload dcpt|dcpt_swinir|restormer|promptir|infer2k|naf|swinir|rcan|val_metrics|step_tail|tlsc|ssim_loss [--dtype fp32|bf16|bf16_res32] [--steps K] [--warmup W]
 
 ``--dtype bf16`` (dcpt, naf, infer2k, restormer, promptir; rcan: the inference line only, next to fp32; swinir: the restoration form's inference, next to fp32): every feature map of the encoder in bf16 storage with fp32 accumulation (act_dtype="bf16";
 dcpt: the classifier head too unless --head-dtype fp32); images, parameters and the optimizer stay fp32.  Its lines carry BOTH
@@ -558,9 +558,81 @@ def run_step_tail(dev, steps=50, warmup=5, rounds=7, max_norm=1.0, decay=0.999):
                      "the two routes alternating in one process; max_norm below the gradient norm: both routes multiply every gradient")
 
 
+def run_ssim_loss(dev, steps=20, warmup=3, B=32, S=256):
+    """SSIMMSELoss forward + backward at B x 3 x S x S (the loss alone: ``pred`` is a leaf): the kernel route (basicsr.losses.SSIMMSELoss,
+    dcpt_amd/csrc/ssim_loss.hip) against a torch route on the device, the reference's arithmetic as it stands there -- five grouped 11 x 11
+    fp64 ``F.conv2d`` passes and autograd's transposes.  The two alternate call by call in one process; each call is bracketed by device
+    events; median and minimum of the per-call times after the warm-up.  If the torch route cannot run on the device its error text is
+    recorded instead."""
+    import statistics
+
+    import numpy as np
+    import torch.nn.functional as F
+
+    from basicsr.losses import SSIMMSELoss
+
+    g = torch.Generator(device=dev).manual_seed(1234)
+    target = torch.rand((B, 3, S, S), generator=g, device=dev)
+    pred = (target + 0.05 * torch.randn((B, 3, S, S), generator=g, device=dev)).clamp(0, 1).requires_grad_(True)
+    crit = SSIMMSELoss()
+    x = np.arange(11, dtype=np.float64) - 5.0
+    k = np.exp(-(x ** 2) / (2 * 1.5 ** 2))
+    k /= k.sum()
+    win = torch.from_numpy(np.outer(k, k)).to(dev).view(1, 1, 11, 11).expand(3, 1, 11, 11).contiguous()
+    c1, c2 = 0.01 ** 2, 0.03 ** 2
+
+    def torch_loss():
+        a, b = pred.double(), target.double()
+        cv = lambda t: F.conv2d(t, win, groups=3)   # noqa: E731
+        mu1, mu2 = cv(a), cv(b)
+        mu1_sq, mu2_sq, mu12 = mu1 * mu1, mu2 * mu2, mu1 * mu2
+        s1, s2, s12 = cv(a * a) - mu1_sq, cv(b * b) - mu2_sq, cv(a * b) - mu12
+        ssim = (((2 * mu12 + c1) / (mu1_sq + mu2_sq + c1)) * ((2 * s12 + c2) / (s1 + s2 + c2))).mean([1, 2, 3])
+        return 0.1 * (1 - ssim.mean()) + F.mse_loss(pred, target)
+
+    vals = {}
+
+    def call(name, fn):
+        pred.grad = None
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        loss = fn()
+        loss.backward()
+        e1.record()
+        e1.synchronize()
+        vals[name] = float(loss.detach())
+        return e0.elapsed_time(e1)
+
+    routes = {"kernel": lambda: crit(pred, target), "torch": torch_loss}
+    torch_error = None
+    try:
+        call("torch", torch_loss)
+    except Exception as e:  # noqa: BLE001  (recorded, not hidden: the line then holds the kernel route alone)
+        torch_error = f"{type(e).__name__}: {e}"[:400]
+        routes.pop("torch")
+    times = {n: [] for n in routes}
+    for i in range(warmup + steps):
+        for n, fn in routes.items():
+            t = call(n, fn)
+            if i >= warmup:
+                times[n].append(t)
+    res = dict(workload=f"SSIMMSELoss forward + backward, {B} x 3 x {S} x {S}, fp64 SSIM term, loss alone (pred is a leaf)",
+               kernel_ms_median=round(statistics.median(times["kernel"]), 4), kernel_ms_min=round(min(times["kernel"]), 4),
+               kernel_share_of_117ms_fp32_step=round(statistics.median(times["kernel"]) / 117.0, 4), loss_kernel=vals["kernel"],
+               calls=steps, warmup=warmup, plane_cap_mib=64,
+               note="device events around each forward + backward call, the two routes alternating in one process; "
+                    "117 ms: the fp32 NAFNet-64 step of bench.py the loss would join")
+    if torch_error is None:
+        res.update(torch_ms_median=round(statistics.median(times["torch"]), 4), torch_ms_min=round(min(times["torch"]), 4),
+                   ratio_median=round(statistics.median(times["torch"]) / statistics.median(times["kernel"]), 2), loss_torch=vals["torch"])
+    else:
+        res["torch_route_error"] = torch_error
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", required=True, choices=["dcpt", "dcpt_swinir", "restormer", "promptir", "infer2k", "naf", "swinir", "rcan", "val_metrics", "step_tail", "tlsc"])
+    ap.add_argument("--workload", required=True, choices=["dcpt", "dcpt_swinir", "restormer", "promptir", "infer2k", "naf", "swinir", "rcan", "val_metrics", "step_tail", "tlsc", "ssim_loss"])
     ap.add_argument("--dtype", default="fp32", choices=["fp32", "bf16", "bf16_tail32", "bf16_edge32", "bf16_res32"])
     ap.add_argument("--head-dtype", default=None, choices=["fp32", "bf16"], help="dcpt: classifier-head activations (default: --dtype)")
     ap.add_argument("--restormer-save", default="balanced", choices=["auto", "lean", "balanced", "full"], help="what the Restormer halves keep for backward")
@@ -750,6 +822,8 @@ def main():
         res = run_val_metrics(dev, args.steps, args.warmup)
     elif args.workload == "step_tail":
         res = run_step_tail(dev, max(args.steps, 20), args.warmup)
+    elif args.workload == "ssim_loss":
+        res = run_ssim_loss(dev, max(args.steps, 20), max(args.warmup, 3), args.batch or 32, args.size or 256)
     elif args.workload == "tlsc":
         res = run_tlsc(dev, args.steps, args.warmup, tile=args.tile, streams=args.tile_streams)
     else:

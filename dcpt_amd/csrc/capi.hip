@@ -310,3 +310,64 @@ extern "C" int dcpt_imgmetric(const float* img, const float* img2, void* sse_out
     return launch_imgmetric(img, img2, sse_out, ssim_out, m.ssim_part, m.sse_part, B, C, H, W, crop_border, (flags & DCPT_METRIC_Y) != 0,
                             (flags & DCPT_METRIC_RANGE1) ? 1 : 255, want_ssim, (hipStream_t)stream);
 }
+
+// ---------------------------------------------------------------------------------------------
+// SSIM as a training loss (ssim_loss.hip)
+namespace {
+struct SsimLossWs {
+    double* part;     // [B * C'][tiles]
+    double* planes;   // [chunk images * C'][3][Hm][Wm] (backward)
+};
+// 0 on success; the message names what is wrong with the shape / flags (the words dcpt_imgmetric uses for the same faults)
+const char* ssim_loss_check(int B, int C, int H, int W, int crop, int flags) {
+    if (B <= 0 || H <= 0 || W <= 0) return "ssim_loss: bad shape";
+    if (C != 1 && C != 3) return "ssim_loss: C must be 1 or 3";
+    if (crop < 0) return "ssim_loss: crop_border must be >= 0";
+    if (flags & ~DCPT_METRIC_Y) return "ssim_loss: unknown flag (only DCPT_METRIC_Y is taken)";
+    if (H - 2 * crop <= 0 || W - 2 * crop <= 0) return "ssim_loss: nothing left after the crop";
+    if (H - 2 * crop < 11 || W - 2 * crop < 11) return "ssim_loss: SSIM needs a cropped image of at least 11 x 11";
+    if ((int64_t)B * C > 65535) return "ssim_loss: B * C above 65535";
+    return nullptr;
+}
+size_t ssim_loss_layout(int B, int C, int H, int W, int crop, int flags, int backward, void* base, size_t bytes, SsimLossWs* out) {
+    WsAlloc a(base, bytes);
+    const int Cp = ((flags & DCPT_METRIC_Y) && C == 3) ? 1 : C;
+    const int Hc = H - 2 * crop, Wc = W - 2 * crop;
+    SsimLossWs w{};
+    w.part = a.get<double>((size_t)B * Cp * ssim_loss_num_tiles(Hc, Wc));
+    if (backward) w.planes = (double*)a.get<char>((size_t)ssim_loss_chunk_images(B, Cp, Hc, Wc) * ssim_loss_plane_bytes(Cp, Hc, Wc));
+    if (out) *out = w;
+    return a.off;
+}
+}  // namespace
+
+extern "C" size_t dcpt_ssim_loss_ws_bytes(int B, int C, int H, int W, int crop_border, int flags, int backward) {
+    if (ssim_loss_check(B, C, H, W, crop_border, flags)) return 0;
+    return ssim_loss_layout(B, C, H, W, crop_border, flags, backward != 0, nullptr, 0, nullptr);
+}
+
+extern "C" int dcpt_ssim_loss_fwd(const float* pred, const float* target, double* ssim_sum, void* ws, size_t ws_bytes, int B, int C, int H, int W,
+                                  int crop_border, int flags, double image_range, dcpt_stream_t stream) {
+    DCPT_CHECK_ARG(pred && target && ssim_sum, "ssim_loss_fwd: null argument");
+    const char* bad = ssim_loss_check(B, C, H, W, crop_border, flags);
+    DCPT_CHECK_ARG(!bad, "%s (B=%d C=%d H=%d W=%d crop_border=%d flags=0x%x)", bad, B, C, H, W, crop_border, flags);
+    DCPT_CHECK_ARG(image_range > 0, "ssim_loss: image_range must be > 0 (got %g)", image_range);
+    SsimLossWs m;
+    const size_t need = ssim_loss_layout(B, C, H, W, crop_border, flags, 0, ws, ws_bytes, &m);
+    DCPT_CHECK_WS("ssim_loss_fwd", ws, ws_bytes, need);
+    return launch_ssim_loss_fwd(pred, target, ssim_sum, m.part, B, C, H, W, crop_border, (flags & DCPT_METRIC_Y) != 0, image_range,
+                                (hipStream_t)stream);
+}
+
+extern "C" int dcpt_ssim_loss_bwd(const float* pred, const float* target, const double* gscale, float* dpred, void* ws, size_t ws_bytes, int B,
+                                  int C, int H, int W, int crop_border, int flags, double image_range, dcpt_stream_t stream) {
+    DCPT_CHECK_ARG(pred && target && gscale && dpred, "ssim_loss_bwd: null argument");
+    const char* bad = ssim_loss_check(B, C, H, W, crop_border, flags);
+    DCPT_CHECK_ARG(!bad, "%s (B=%d C=%d H=%d W=%d crop_border=%d flags=0x%x)", bad, B, C, H, W, crop_border, flags);
+    DCPT_CHECK_ARG(image_range > 0, "ssim_loss: image_range must be > 0 (got %g)", image_range);
+    SsimLossWs m;
+    const size_t need = ssim_loss_layout(B, C, H, W, crop_border, flags, 1, ws, ws_bytes, &m);
+    DCPT_CHECK_WS("ssim_loss_bwd", ws, ws_bytes, need);
+    return launch_ssim_loss_bwd(pred, target, gscale, dpred, m.planes, B, C, H, W, crop_border, (flags & DCPT_METRIC_Y) != 0, image_range,
+                                (hipStream_t)stream);
+}

@@ -180,3 +180,15 @@ int launch_gdfn_unpack(const float* in, float* out, int c, int h, int hp, int mo
 int metric_num_tiles(int Hc, int Wc);
 int launch_imgmetric(const float* img, const float* img2, void* sse_out, double* ssim_out, double* ssim_part, void* sse_part, int B, int C,
                      int H, int W, int crop, int luma, int range, int want_ssim, hipStream_t s);
+
+// ---- ssim_loss.hip --------------------------------------------------------------------------
+// SSIM as a loss (dcpt_ssim_loss_fwd / _bwd): the forward writes one partial per tile into part[B * C'][ssim_loss_num_tiles]; the backward
+// keeps Pa, Pb, Pc of ssim_loss_chunk_images images at a time in planes (ssim_loss_plane_bytes per image).
+extern "C" size_t dcpt_ssim_loss_plane_cap;   // bytes of planes held at a time (64 MiB; a data symbol for the tests, not in the ABI)
+int ssim_loss_num_tiles(int Hc, int Wc);
+size_t ssim_loss_plane_bytes(int Cp, int Hc, int Wc);
+int ssim_loss_chunk_images(int B, int Cp, int Hc, int Wc);
+int launch_ssim_loss_fwd(const float* pred, const float* target, double* ssim_sum, double* part, int B, int C, int H, int W, int crop, int luma,
+                         double range, hipStream_t s);
+int launch_ssim_loss_bwd(const float* pred, const float* target, const double* gscale, float* dpred, double* planes, int B, int C, int H, int W,
+                         int crop, int luma, double range, hipStream_t s);

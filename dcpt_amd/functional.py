@@ -2808,3 +2808,66 @@ def image_metric_sums(img, img2, crop_border=0, test_y_channel=False, image_rang
     ws = _workspace(dev, nws)
     _call(lib.dcpt_imgmetric, (img, img2, sse, sums, ws, nws), (B, Cc, H, W, crop, flags), dev)   # (irregular: the queried size, not the buffer's)
     return sse, sums
+
+
+# ------------------------------------------------------------------------------------------------
+# SSIM as a training loss (include/dcpt_hip.h dcpt_ssim_loss_fwd / _bwd): the reference's calculate_ssim_pt with its gradient, in fp64 on
+# the device, without its grouped fp64 convolutions.
+def ssim_plane_cap(nbytes=None):
+    """bytes of fp64 planes the backward pass of ``ssim_pt`` holds at a time (the batch goes through in chunks of whole images, at least
+    one): returns the value, sets it first if ``nbytes`` is given.  The tests shrink it to drive the chunk loop with small images."""
+    cap = C.c_size_t.in_dll(_lib.load(), "dcpt_ssim_loss_plane_cap")
+    if nbytes is not None:
+        cap.value = int(nbytes)
+    return int(cap.value)
+
+
+def _ssim_geom(pred, crop_border, test_y_channel):
+    B, Cc, H, W = pred.shape
+    crop = int(crop_border)
+    cp = 1 if (test_y_channel and Cc == 3) else Cc
+    return (B, Cc, H, W, crop, _METRIC_Y if test_y_channel else 0), cp, cp * (H - 2 * crop - 10) * (W - 2 * crop - 10)
+
+
+class _SsimPtFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, target, crop_border, test_y_channel, image_range):
+        lib = _lib.load()
+        pred, target = _contig(pred), _contig(target)
+        dev = pred.device
+        dims, cp, count = _ssim_geom(pred, crop_border, test_y_channel)
+        sums = torch.empty(dims[0], cp, dtype=torch.float64, device=dev)
+        nws = lib.dcpt_ssim_loss_ws_bytes(*dims, 0)   # (0 for arguments the entry point refuses: it then names the reason)
+        ws = _workspace(dev, nws)
+        _call(lib.dcpt_ssim_loss_fwd, (pred, target, sums, ws, nws), (*dims, float(image_range)), dev)   # (irregular: the queried size)
+        ctx.save_for_backward(pred, target)
+        ctx.args = (crop_border, test_y_channel, float(image_range))
+        return sums.sum(1) / count
+
+    @staticmethod
+    def backward(ctx, dssim):
+        lib = _lib.load()
+        pred, target = ctx.saved_tensors
+        crop_border, test_y_channel, image_range = ctx.args
+        dev = pred.device
+        dims, cp, count = _ssim_geom(pred, crop_border, test_y_channel)
+        gscale = _contig((dssim.to(torch.float64) / count).reshape(-1, 1).expand(-1, cp))
+        dpred = torch.empty_like(pred)
+        nws = lib.dcpt_ssim_loss_ws_bytes(*dims, 1)
+        ws = _workspace(dev, nws)
+        _call(lib.dcpt_ssim_loss_bwd, (pred, target, gscale, dpred, ws, nws), (*dims, image_range), dev)
+        return dpred, None, None, None, None
+
+
+def ssim_pt(pred, target, crop_border=0, test_y_channel=False, image_range=1.0):
+    """The reference's ``calculate_ssim_pt`` (basicsr/metrics/psnr_ssim.py:436-480): ``pred`` / ``target`` (B, C, H, W) fp32 device tensors,
+    C in {1, 3}; returns the per-image SSIM as a float64 tensor (B,), differentiable with respect to ``pred`` (fp32 gradient, rounded once
+    from fp64).  ``target`` gets no gradient: one that requires it is refused."""
+    if not (torch.is_tensor(pred) and torch.is_tensor(target)):
+        raise _lib.DcptHipError(f"ssim_pt takes device tensors (got {type(pred).__name__}, {type(target).__name__})")
+    _require_gpu(pred, target)
+    if pred.dim() != 4 or pred.shape != target.shape:
+        raise ValueError(f"expected two (B, C, H, W) tensors of one shape, got {tuple(pred.shape)} and {tuple(target.shape)}")
+    if target.requires_grad:
+        raise NotImplementedError("ssim_pt differentiates with respect to pred only; detach the target")
+    return _SsimPtFn.apply(pred, target, int(crop_border), bool(test_y_channel), image_range)

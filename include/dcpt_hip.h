@@ -804,6 +804,31 @@ size_t dcpt_imgmetric_ws_bytes(int B, int C, int H, int W, int crop_border, int 
 int dcpt_imgmetric(const float* img, const float* img2, void* sse_out, double* ssim_out, void* ws, size_t ws_bytes, int B, int C, int H, int W,
                    int crop_border, int flags, dcpt_stream_t stream);
 
+/* ---- SSIM as a training loss: per-image SSIM sums and their gradient, on the device ------------------------
+ * replaces the fp64 arithmetic of basicsr/metrics/psnr_ssim.py:436-480 (calculate_ssim_pt) and :515-559 (_ssim_pth: five grouped 11 x 11
+ * fp64 F.conv2d passes, and their transposes under autograd) as the losses of basicsr/losses/basic_loss.py:152-232 (SSIMLoss, SSIMMSELoss)
+ * call it.  pred, target: dense NCHW fp32 [B][C][H][W], C in {1, 3}.  crop_border pixels are dropped on every side by addressing; with
+ * DCPT_METRIC_Y and C == 3 both images become ONE luma channel, Y = (((r 65.481f + g 128.553f) + b 24.966f) + 16.0f) / 255.0f with every
+ * product, sum and the division rounded to fp32 in this order (basicsr/utils/color_util.py:222-254 rgb2ycbcr_pt(y_only=True), an fp32
+ * matmul there); the values are widened to fp64 and everything after that is fp64: 11-tap Gaussian (sigma 1.5), "valid" window,
+ * C1 = (0.01 image_range)^2, C2 = (0.03 image_range)^2.  C' = 1 for luma, C otherwise; the map has (H' - 10) x (W' - 10) positions,
+ * H' = H - 2 crop_border.
+ *   dcpt_ssim_loss_fwd   ssim_sum[B][C'] = the sum of the SSIM map of (image, channel); the caller divides by the count (the reference's
+ *                        ssim_map.mean([1, 2, 3])).  Two launches.
+ *   dcpt_ssim_loss_bwd   dpred[B][C][H][W] = the gradient of sum_{b,c'} gscale[b][c'] * ssim_sum[b][c'] with respect to pred, rounded once
+ *                        to fp32; gscale is a DEVICE array, nothing is read back.  Every element is written: pixels inside the crop border
+ *                        get exactly 0; with luma the three channels get dY * (65.481f, 128.553f, 24.966f) / 255, formed in fp64.  Two
+ *                        launches per chunk of whole images: the workspace holds three fp64 planes per map (24 bytes per position) for at
+ *                        most max(one image, 64 MiB) at a time.  target gets no gradient.
+ * No atomics: the same input gives the same bits.  Errors (before any launch): null pointers, C not in {1, 3}, a flag other than
+ * DCPT_METRIC_Y, image_range <= 0, a cropped size under 11 x 11, B * C above 65535, workspace too small.  dcpt_ssim_loss_ws_bytes needs no
+ * device and returns 0 for arguments the entry points refuse. */
+size_t dcpt_ssim_loss_ws_bytes(int B, int C, int H, int W, int crop_border, int flags, int backward);
+int dcpt_ssim_loss_fwd(const float* pred, const float* target, double* ssim_sum, void* ws, size_t ws_bytes, int B, int C, int H, int W,
+                       int crop_border, int flags, double image_range, dcpt_stream_t stream);
+int dcpt_ssim_loss_bwd(const float* pred, const float* target, const double* gscale, float* dpred, void* ws, size_t ws_bytes, int B, int C,
+                       int H, int W, int crop_border, int flags, double image_range, dcpt_stream_t stream);
+
 /* ---- optional launch profiling (bench.py) -------------------------------------------------------
  * While enabled, MFMA GEMM launches are bracketed by HIP events on their own stream: every launch for on = 1, every
  * on-th launch for on > 1 (sampling keeps the perturbation of a timed region small: an event pair costs ~3 us of queue time).
