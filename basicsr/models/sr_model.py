@@ -13,6 +13,7 @@ from torch.nn import functional as F
 
 from basicsr.archs import build_network
 from basicsr.losses import build_loss
+from basicsr.losses.loss_util import get_refined_artifact_map
 from basicsr.metrics import calculate_metric
 from basicsr.utils import get_root_logger
 from basicsr.utils.registry import MODEL_REGISTRY
@@ -60,7 +61,13 @@ class SRModel(BaseModel):
             self._init_ema()
             self.net_g_ema.eval()
         self.cri_pix = build_loss(train_opt["pixel_opt"]).to(self.device) if train_opt.get("pixel_opt") else None
-        if self.cri_pix is None:
+        # the LDL term (reference sr_model.py:88-91, :145-153): its weights exist for ``ldl_std: true`` only -- with anything else the
+        # reference's get_refined_artifact_map reads an unbound name at the first step; here the options are refused at once
+        self.cri_ldl = build_loss(train_opt["ldl_opt"]).to(self.device) if train_opt.get("ldl_opt") else None
+        if self.cri_ldl is not None and train_opt.get("ldl_std") is not True:
+            raise ValueError(f"train.ldl_opt needs train.ldl_std: true (got {train_opt.get('ldl_std')!r}): the artifact map of the "
+                             f"reference's std=False path needs an EMA output that SRModel never passes")
+        if self.cri_pix is None and self.cri_ldl is None:
             raise ValueError("Both pixel and perceptual losses are None.")
         self.setup_optimizers()
         self._setup_fused_step_tail()
@@ -134,9 +141,15 @@ class SRModel(BaseModel):
         self.optimizer_g.zero_grad()
         self.output = self.net_g(self.lq)
         loss_dict = OrderedDict()
-        l_pix = self.cri_pix(self.output, self.gt)
-        loss_dict["l_pix"] = l_pix
-        l_pix.backward()
+        l_total = None   # (a lone term is differentiated as it is: without ldl_opt the step issues the launches it always did)
+        if self.cri_pix is not None:
+            l_total = loss_dict["l_pix"] = self.cri_pix(self.output, self.gt)
+        if getattr(self, "cri_ldl", None) is not None:   # reference sr_model.py:145-153; the weights are not detached
+            pixel_weight = get_refined_artifact_map(self.gt, self.output, std=self.opt["train"]["ldl_std"])
+            l_ldl = (pixel_weight * self.cri_ldl(self.output, self.gt)).mean()
+            l_total = l_ldl if l_total is None else l_total + l_ldl
+            loss_dict["l_ldl"] = l_ldl
+        l_total.backward()
         fused_tail = getattr(self, "fused_step_tail", False)
         if fused_tail:
             self._fused_step_tail()

@@ -2,7 +2,7 @@
 """Secondary workloads of BASELINE.json (configs[2..4]) on ONE MI355X -- evidence for DESIGN.md, not the driver's
 contract (that is bench.py).  Prints one JSON line per workload.
 
-    python bench_extra.py --workload dcpt|dcpt_swinir|restormer|promptir|infer2k|naf|swinir|rcan|val_metrics|step_tail|tlsc|ssim_loss [--dtype fp32|bf16|bf16_res32] [--steps K] [--warmup W]
+    python bench_extra.py --workload dcpt|dcpt_swinir|restormer|promptir|infer2k|naf|swinir|rcan|val_metrics|step_tail|tlsc|ssim_loss|ldl [--dtype fp32|bf16|bf16_res32] [--steps K] [--warmup W]
 
 ``--dtype bf16`` (dcpt, naf, infer2k, restormer, promptir; rcan: the inference line only, next to fp32; swinir: the restoration form's inference, next to fp32): every feature map of the encoder in bf16 storage with fp32 accumulation (act_dtype="bf16";
 dcpt: the classifier head too unless --head-dtype fp32); images, parameters and the optimizer stay fp32.  Its lines carry BOTH
@@ -630,9 +630,90 @@ def run_ssim_loss(dev, steps=20, warmup=3, B=32, S=256):
     return res
 
 
+def run_ldl(dev, steps=20, warmup=3, B=32, S=256):
+    """The LDL term alone at B x 3 x S x S, ``out`` a leaf: ``w = get_refined_artifact_map(gt, out, std=True); (w * |out - gt|).mean()
+    .backward()``.  The kernel route (basicsr.losses.loss_util, dcpt_amd/csrc/ldl.hip) against a torch route on the device: the reference's
+    expression as it runs there, in fp32 -- F.pad(reflect), unfold(7).unfold(7), torch.std, the standardisation and the tanh under autograd.
+    The two alternate call by call in one process; each call is bracketed by device events; median and minimum of the per-call times after
+    the warm-up, and each route's peak memory above what is resident between calls.  If the torch route cannot run at B its error text is
+    recorded and it is timed at the largest of B / 2, B / 4, .. at which it runs."""
+    import statistics
+
+    import torch.nn.functional as F
+
+    from basicsr.losses.loss_util import get_refined_artifact_map
+
+    g = torch.Generator(device=dev).manual_seed(1234)
+    gt = torch.rand((B, 3, S, S), generator=g, device=dev)
+    out = (gt + 0.05 * torch.randn((B, 3, S, S), generator=g, device=dev)).requires_grad_(True)
+
+    def kernel_loss(o, t):
+        return (get_refined_artifact_map(t, o, std=True) * (o - t).abs()).mean()
+
+    def torch_loss(o, t):
+        r = (t - o).abs()
+        win = F.pad(r, [3, 3, 3, 3], mode="reflect").unfold(2, 7, 1).unfold(3, 7, 1)
+        u = torch.std(win, dim=(-1, -2), unbiased=True)
+        u = (u - u.mean()) / u.std()
+        return ((u.tanh() + 1) / 2 * (o - t).abs()).mean()
+
+    vals, peaks = {}, {}
+
+    def call(name, fn, nb):
+        o, t = (out, gt) if nb == B else (out_small, gt[:nb])
+        o.grad = None
+        torch.cuda.synchronize(dev)
+        base = torch.cuda.memory_allocated(dev)
+        torch.cuda.reset_peak_memory_stats(dev)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        loss = fn(o, t)
+        loss.backward()
+        e1.record()
+        e1.synchronize()
+        vals[name] = float(loss.detach())
+        peaks[name] = max(peaks.get(name, 0), torch.cuda.max_memory_allocated(dev) - base)
+        return e0.elapsed_time(e1)
+
+    torch_errors, tb, out_small = [], B, None
+    while tb >= 1:
+        out_small = out if tb == B else out.detach()[:tb].clone().requires_grad_(True)
+        try:
+            call("torch", torch_loss, tb)
+            break
+        except Exception as e:  # noqa: BLE001  (recorded, not hidden)
+            torch_errors.append(f"batch {tb}: {type(e).__name__}: {e}"[:300])
+            out_small = None
+            torch.cuda.empty_cache()
+            tb //= 2
+    routes = {"kernel": (kernel_loss, B)}
+    if tb >= 1:
+        routes["torch"] = (torch_loss, tb)
+    peaks.clear()
+    times = {n: [] for n in routes}
+    for i in range(warmup + steps):
+        for n, (fn, nb) in routes.items():
+            t = call(n, fn, nb)
+            if i >= warmup:
+                times[n].append(t)
+    res = dict(workload=f"LDL term forward + backward, {B} x 3 x {S} x {S}: w = get_refined_artifact_map(gt, out, std=True); "
+                        f"(w * |out - gt|).mean().backward(), out a leaf",
+               kernel_ms_median=round(statistics.median(times["kernel"]), 4), kernel_ms_min=round(min(times["kernel"]), 4),
+               kernel_peak_mb=round(peaks["kernel"] / 1e6, 1), loss_kernel=vals["kernel"], calls=steps, warmup=warmup,
+               note="device events around each forward + backward call, the two routes alternating in one process; peak memory of a call "
+                    "above what is allocated between calls; the torch route is the reference's fp32 expression under autograd")
+    if "torch" in routes:
+        res.update(torch_batch=tb, torch_ms_median=round(statistics.median(times["torch"]), 4), torch_ms_min=round(min(times["torch"]), 4),
+                   torch_peak_mb=round(peaks["torch"] / 1e6, 1), loss_torch=vals["torch"],
+                   ratio_median=round(statistics.median(times["torch"]) / statistics.median(times["kernel"]), 2))
+    if torch_errors:
+        res["torch_route_errors"] = torch_errors
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", required=True, choices=["dcpt", "dcpt_swinir", "restormer", "promptir", "infer2k", "naf", "swinir", "rcan", "val_metrics", "step_tail", "tlsc", "ssim_loss"])
+    ap.add_argument("--workload", required=True, choices=["dcpt", "dcpt_swinir", "restormer", "promptir", "infer2k", "naf", "swinir", "rcan", "val_metrics", "step_tail", "tlsc", "ssim_loss", "ldl"])
     ap.add_argument("--dtype", default="fp32", choices=["fp32", "bf16", "bf16_tail32", "bf16_edge32", "bf16_res32"])
     ap.add_argument("--head-dtype", default=None, choices=["fp32", "bf16"], help="dcpt: classifier-head activations (default: --dtype)")
     ap.add_argument("--restormer-save", default="balanced", choices=["auto", "lean", "balanced", "full"], help="what the Restormer halves keep for backward")
@@ -824,6 +905,8 @@ def main():
         res = run_step_tail(dev, max(args.steps, 20), args.warmup)
     elif args.workload == "ssim_loss":
         res = run_ssim_loss(dev, max(args.steps, 20), max(args.warmup, 3), args.batch or 32, args.size or 256)
+    elif args.workload == "ldl":
+        res = run_ldl(dev, max(args.steps, 20), max(args.warmup, 3), args.batch or 32, args.size or 256)
     elif args.workload == "tlsc":
         res = run_tlsc(dev, args.steps, args.warmup, tile=args.tile, streams=args.tile_streams)
     else:

@@ -336,6 +336,9 @@ SIGNATURES = {
     "dcpt_ssim_loss_ws_bytes": (sz, [cint, cint, cint, cint, cint, cint, cint]),
     "dcpt_ssim_loss_fwd": (cint, [f32p, f32p, C.c_void_p, C.c_void_p, sz, cint, cint, cint, cint, cint, cint, C.c_double, stream_t]),
     "dcpt_ssim_loss_bwd": (cint, [f32p, f32p, C.c_void_p, f32p, C.c_void_p, sz, cint, cint, cint, cint, cint, cint, C.c_double, stream_t]),
+    "dcpt_ldl_weight_ws_bytes": (sz, [cint, cint, cint, cint, cint]),
+    "dcpt_ldl_weight_fwd": (cint, [f32p, f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint, stream_t]),
+    "dcpt_ldl_weight_bwd": (cint, [f32p, f32p, f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint, stream_t]),
     "dcpt_trace_enable": (cint, [cint]),
     "dcpt_trace_read": (sz, [C.c_char_p, sz]),
     "dcpt_prof_enable": (cint, [cint]),

@@ -371,3 +371,59 @@ extern "C" int dcpt_ssim_loss_bwd(const float* pred, const float* target, const 
     return launch_ssim_loss_bwd(pred, target, gscale, dpred, m.planes, B, C, H, W, crop_border, (flags & DCPT_METRIC_Y) != 0, image_range,
                                 (hipStream_t)stream);
 }
+
+// ---------------------------------------------------------------------------------------------
+// The LDL artifact-weight map (ldl.hip)
+namespace {
+// 0 on success; the message names what is wrong with the shape
+const char* ldl_check(int B, int C, int H, int W) {
+    if (B <= 0 || C <= 0 || H <= 0 || W <= 0) return "ldl_weight: bad shape";
+    if ((int64_t)B * C * H * W < 2) return "ldl_weight: the std over the map needs B * C * H * W >= 2";
+    if (H < 4 || W < 4) return "ldl_weight: reflect padding by 3 needs H >= 4 and W >= 4";
+    if ((int64_t)B * C > 65535) return "ldl_weight: B * C above 65535";
+    if ((int64_t)H * W > ((int64_t)1 << 30)) return "ldl_weight: a plane above 2^30 pixels";
+    return nullptr;
+}
+size_t ldl_layout(int B, int C, int H, int W, int backward, void* base, size_t bytes, LdlWs* out) {
+    WsAlloc a(base, bytes);
+    const size_t N = (size_t)B * C * H * W;
+    LdlWs w{};
+    w.scal = a.get<double>(8);
+    w.part = a.get<double>(2 * (size_t)ldl_num_partials(B, C, H, W));
+    w.u = a.get<double>(N);
+    w.mu = a.get<double>(N);
+    if (backward) {
+        w.gv = a.get<double>(N);
+        w.gvmu = a.get<double>(N);
+    }
+    if (out) *out = w;
+    return a.off;
+}
+}  // namespace
+
+extern "C" size_t dcpt_ldl_weight_ws_bytes(int B, int C, int H, int W, int backward) {
+    if (ldl_check(B, C, H, W)) return 0;
+    return ldl_layout(B, C, H, W, backward != 0, nullptr, 0, nullptr);
+}
+
+extern "C" int dcpt_ldl_weight_fwd(const float* gt, const float* out, float* w, void* ws, size_t ws_bytes, int B, int C, int H, int W,
+                                   dcpt_stream_t stream) {
+    DCPT_CHECK_ARG(gt && out && w, "ldl_weight_fwd: null argument");
+    const char* bad = ldl_check(B, C, H, W);
+    DCPT_CHECK_ARG(!bad, "%s (B=%d C=%d H=%d W=%d)", bad, B, C, H, W);
+    LdlWs m;
+    const size_t need = ldl_layout(B, C, H, W, 0, ws, ws_bytes, &m);
+    DCPT_CHECK_WS("ldl_weight_fwd", ws, ws_bytes, need);
+    return launch_ldl_weight_fwd(gt, out, w, m, B, C, H, W, (hipStream_t)stream);
+}
+
+extern "C" int dcpt_ldl_weight_bwd(const float* gt, const float* out, const float* gw, float* dout, void* ws, size_t ws_bytes, int B, int C,
+                                   int H, int W, dcpt_stream_t stream) {
+    DCPT_CHECK_ARG(gt && out && gw && dout, "ldl_weight_bwd: null argument");
+    const char* bad = ldl_check(B, C, H, W);
+    DCPT_CHECK_ARG(!bad, "%s (B=%d C=%d H=%d W=%d)", bad, B, C, H, W);
+    LdlWs m;
+    const size_t need = ldl_layout(B, C, H, W, 1, ws, ws_bytes, &m);
+    DCPT_CHECK_WS("ldl_weight_bwd", ws, ws_bytes, need);
+    return launch_ldl_weight_bwd(gt, out, gw, dout, m, B, C, H, W, (hipStream_t)stream);
+}

@@ -192,3 +192,16 @@ int launch_ssim_loss_fwd(const float* pred, const float* target, double* ssim_su
                          double range, hipStream_t s);
 int launch_ssim_loss_bwd(const float* pred, const float* target, const double* gscale, float* dpred, double* planes, int B, int C, int H, int W,
                          int crop, int luma, double range, hipStream_t s);
+
+// ---- ldl.hip --------------------------------------------------------------------------------
+// The LDL artifact-weight map (dcpt_ldl_weight_fwd / _bwd).  The workspace, all fp64: scal = m, s, sum(Gz), sum(Gz z); part = two rows of
+// ldl_num_partials per-workgroup partials (one per tile of the tile kernel, one per LDL_CHUNK elements of the element-wise kernels);
+// u, mu = the forward's planes, which the backward reads; gv, gvmu = the backward's planes.
+#define LDL_CHUNK 4096
+struct LdlWs {
+    double *scal, *part, *u, *mu, *gv, *gvmu;
+};
+int64_t ldl_num_partials(int B, int C, int H, int W);
+int launch_ldl_weight_fwd(const float* gt, const float* out, float* w, const LdlWs& ws, int B, int C, int H, int W, hipStream_t s);
+int launch_ldl_weight_bwd(const float* gt, const float* out, const float* gw, float* dout, const LdlWs& ws, int B, int C, int H, int W,
+                          hipStream_t s);

@@ -2871,3 +2871,49 @@ def ssim_pt(pred, target, crop_border=0, test_y_channel=False, image_range=1.0):
     if target.requires_grad:
         raise NotImplementedError("ssim_pt differentiates with respect to pred only; detach the target")
     return _SsimPtFn.apply(pred, target, int(crop_border), bool(test_y_channel), image_range)
+
+
+# ------------------------------------------------------------------------------------------------
+# The LDL artifact-weight map (include/dcpt_hip.h dcpt_ldl_weight_fwd / _bwd): the reference's get_refined_artifact_map(std=True) with its
+# gradient, in fp64 on the device, without the 49-fold unfold of the residual.
+class _LdlWeightFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, gt, out):
+        lib = _lib.load()
+        gt, out = _contig(gt), _contig(out)
+        dev = out.device
+        dims = tuple(out.shape)
+        w = torch.empty_like(out)
+        if ctx.needs_input_grad[1]:
+            # the backward reads what the forward leaves (m, s, the planes u and mu): a buffer of this call's own, of the backward's size
+            nws = lib.dcpt_ldl_weight_ws_bytes(*dims, 1)   # (0 for a shape the entry point refuses: it then names the reason)
+            ws = torch.empty(max(nws, 1), dtype=torch.uint8, device=dev)
+            ctx.save_for_backward(gt, out, ws)
+        else:
+            nws = lib.dcpt_ldl_weight_ws_bytes(*dims, 0)
+            ws = _workspace(dev, nws)
+        _call(lib.dcpt_ldl_weight_fwd, (gt, out, w, ws, nws), dims, dev)   # (irregular: the queried size, not the buffer's)
+        return w
+
+    @staticmethod
+    def backward(ctx, gw):
+        lib = _lib.load()
+        gt, out, ws = ctx.saved_tensors
+        dout = torch.empty_like(out)
+        _call(lib.dcpt_ldl_weight_bwd, (gt, out, _contig(gw.float()), dout, ws, ws.numel()), tuple(out.shape), out.device)
+        return None, dout
+
+
+def ldl_weight(gt, out):
+    """The reference's ``get_refined_artifact_map(gt, out, std=True)`` (basicsr/losses/loss_util.py:100-165, window 7, no ``img_ema``):
+    ``gt`` / ``out`` (B, C, H, W) fp32 device tensors, H, W >= 4; returns the weight map w = (tanh((u - mean u) / std u) + 1) / 2 of the local
+    7 x 7 standard deviation u of |gt - out| as an fp32 tensor of the same shape, differentiable with respect to ``out`` (the map is not
+    detached in the reference either; fp32 gradient, rounded once from fp64).  ``gt`` gets no gradient: one that requires it is refused."""
+    if not (torch.is_tensor(gt) and torch.is_tensor(out)):
+        raise _lib.DcptHipError(f"ldl_weight takes device tensors (got {type(gt).__name__}, {type(out).__name__})")
+    _require_gpu(gt, out)
+    if out.dim() != 4 or out.shape != gt.shape:
+        raise ValueError(f"expected two (B, C, H, W) tensors of one shape, got {tuple(gt.shape)} and {tuple(out.shape)}")
+    if gt.requires_grad:
+        raise NotImplementedError("ldl_weight differentiates with respect to out only; detach the target")
+    return _LdlWeightFn.apply(gt, out)

@@ -829,6 +829,32 @@ int dcpt_ssim_loss_fwd(const float* pred, const float* target, double* ssim_sum,
 int dcpt_ssim_loss_bwd(const float* pred, const float* target, const double* gscale, float* dpred, void* ws, size_t ws_bytes, int B, int C,
                        int H, int W, int crop_border, int flags, double image_range, dcpt_stream_t stream);
 
+/* ---- LDL artifact weights: the refined artifact map and its gradient, on the device ----------------------
+ * replaces basicsr/losses/loss_util.py:100-130 (get_local_weights: F.pad(reflect), unfold(7).unfold(7), torch.std, the standardisation and
+ * the tanh) and :133-165 (get_refined_artifact_map) on the one path basicsr/models/sr_model.py:145-153 reaches -- std=True, ksize 7, no
+ * img_ema -- together with what autograd does to those lines.  gt, out: dense NCHW fp32 [B][C][H][W], N = B C H W.  The window is 7 x 7
+ * and nothing else.
+ *     r = |gt - out|;  u = unbiased std of r over the 7 x 7 window around each pixel, r reflect-padded by 3;
+ *     m = mean(u), s = unbiased std(u) over all N elements;  w = (tanh((u - m) / s) + 1) / 2
+ * All of it in fp64; the one departure from the reference: r is |double(gt) - double(out)|, the exact difference, where the reference
+ * rounds the difference to fp32 first.
+ *   dcpt_ldl_weight_fwd   w[B][C][H][W] fp32, rounded once.  Five launches.  It leaves m, s and the fp64 planes u and mu (the window mean)
+ *                         in ws.  out == gt everywhere gives s = 0 and w = NaN everywhere, as the reference's expression does.
+ *   dcpt_ldl_weight_bwd   dout[B][C][H][W] fp32 = the gradient with respect to out of sum(gw * w), gw [B][C][H][W] fp32 on the device,
+ *                         rounded once.  Four launches.  It READS what the forward left: ws must be the buffer dcpt_ldl_weight_fwd wrote
+ *                         for the same gt and out, untouched since, and at least dcpt_ldl_weight_ws_bytes(.., backward = 1) bytes (the
+ *                         forward's layout is a prefix of the backward's).  The state is this argument; the library keeps none.  gt gets
+ *                         no gradient.
+ * m, s and the two global sums of the backward stay in ws: nothing is read back, no call synchronises.  No atomics, every sum in a fixed
+ * order: the same input gives the same bits.  Errors (before any launch): null pointers, B C H W < 2, H < 4 or W < 4 (reflect padding by
+ * 3), B * C above 65535, a plane above 2^30 pixels, workspace too small (return code 2).  dcpt_ldl_weight_ws_bytes needs no device and
+ * returns 0 for a shape the entry points refuse. */
+size_t dcpt_ldl_weight_ws_bytes(int B, int C, int H, int W, int backward);
+int dcpt_ldl_weight_fwd(const float* gt, const float* out, float* w, void* ws, size_t ws_bytes, int B, int C, int H, int W,
+                        dcpt_stream_t stream);
+int dcpt_ldl_weight_bwd(const float* gt, const float* out, const float* gw, float* dout, void* ws, size_t ws_bytes, int B, int C, int H,
+                        int W, dcpt_stream_t stream);
+
 /* ---- optional launch profiling (bench.py) -------------------------------------------------------
  * While enabled, MFMA GEMM launches are bracketed by HIP events on their own stream: every launch for on = 1, every
  * on-th launch for on > 1 (sampling keeps the perturbation of a timed region small: an event pair costs ~3 us of queue time).
