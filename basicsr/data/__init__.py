@@ -1,5 +1,5 @@
 """Dataset plumbing for ``test.py`` (reference basicsr/data/__init__.py:33-118).  The reference's IO stack
-(cv2, lmdb, on-the-fly degradations) is out of scope; what the hot path needs from it
+(cv2, lmdb, the demosaic and inpainting degradations) is out of scope; what the hot path needs from it
 is a dict with ``lq``/``gt`` float32 CHW tensors in [0,1] (+ ``dataset_idx``).  A minimal PIL reader covers
 paired folders; when a configured root does not exist (the YAMLs point at /mnt/nasv3/...), a seeded synthetic
 pair stands in so the CLI still runs end to end."""
@@ -166,6 +166,76 @@ class PairedImageDenoiseDataset(tdata.Dataset):
         hwc += rs.normal(0, sigma / 255.0, hwc.shape)   # float64 noise accumulated into the float32 image, as `img_lq += ...`
         lq = torch.from_numpy(hwc.transpose(2, 0, 1)).float().contiguous()
         return _labelled({"lq": lq, "gt": gt.contiguous(), "lq_path": path, "gt_path": path}, self.opt)
+
+
+@DATASET_REGISTRY.register()
+class PairedImageJPEGCARDataset(tdata.Dataset):
+    """GT folder + on-the-fly JPEG compression artifacts (reference basicsr/data/paired_image_dataset.py:425-580, folder mode, PIL
+    reader).  Options: ``dataroot_gt``, ``q_type`` constant / random / choice with ``q_range``, ``gt_size`` (default 128), ``use_hflip``,
+    ``use_rot``, ``center_crop``.  The train phase crops at scale 1 and augments, other phases apply the optional centre crop (:516-530);
+    the quality is drawn from Python's ``random`` exactly as the reference draws it (:532-537), after the crop and the augmentation.
+
+    ``jpeg_backend: pil`` (default): ``lq`` is ``(gt * 255).round()`` as uint8, encoded as a JPEG of that quality by PIL, decoded and
+    divided by 255 -- a stand-in for the reference's ``cv2.imencode`` / ``imdecode`` (:539-546).  Both are libjpeg with the standard
+    tables and 4:2:0 chroma, but cv2 is not a dependency of this package and the stand-in has not been compared with it byte for byte;
+    PIL takes an integer quality, so a ``random`` draw is truncated for the encoder.
+
+    ``jpeg_backend: device``: the sample carries ``gt``, ``jpeg_quality`` (a float32 scalar) and the paths, and no ``lq``; the model's
+    ``feed_data`` makes ``lq`` on the device with the DiffJPEG kernel (``dcpt_amd.functional.diffjpeg(gt, quality, uint8_io=True)``), the
+    codec the reference's dataset names as its alternative (:466-468, :564-565)."""
+
+    def __init__(self, opt):
+        super().__init__()
+        self.opt = opt
+        self.gt_root = opt["dataroot_gt"]
+        self.q_type = opt["q_type"]
+        self.q_range = opt["q_range"]
+        assert self.q_type in ["constant", "random", "choice"]
+        self.backend = opt.get("jpeg_backend", "pil")
+        if self.backend not in ("pil", "device"):
+            raise ValueError(f"jpeg_backend must be 'pil' or 'device', got {self.backend!r}")
+        self.gt_size = opt.get("gt_size", 128)
+        self.names = sorted(f for f in scandir(self.gt_root) if f.endswith(_IMG_EXT))
+
+    def __len__(self):
+        return len(self.names)
+
+    @staticmethod
+    def _pil_round_trip(gt, quality):
+        import io
+
+        from PIL import Image
+
+        hwc = (gt.permute(1, 2, 0) * 255).round().to(torch.uint8).contiguous().numpy()
+        buf = io.BytesIO()
+        Image.fromarray(hwc).save(buf, format="JPEG", quality=int(quality))
+        buf.seek(0)
+        with Image.open(buf) as im:
+            dec = np.asarray(im.convert("RGB"), dtype=np.float32) / 255.0
+        return torch.from_numpy(dec).permute(2, 0, 1).contiguous()
+
+    def __getitem__(self, index):
+        import random
+
+        path = osp.join(self.gt_root, self.names[index])
+        gt = _read_rgb(path)
+        if self.opt.get("phase") == "train":
+            _, gt = paired_random_crop_augment(gt, gt, {**self.opt, "gt_size": self.gt_size, "scale": 1})
+        elif self.opt.get("center_crop") is not None:
+            gt = _center_crop(gt, self.opt["center_crop"])
+        gt = gt.contiguous()
+        if self.q_type == "constant":
+            q_value = self.q_range
+        elif self.q_type == "random":
+            q_value = random.uniform(self.q_range[0], self.q_range[1])
+        else:
+            q_value = random.choice(self.q_range)
+        sample = {"gt": gt, "lq_path": path, "gt_path": path}
+        if self.backend == "device":
+            sample["jpeg_quality"] = torch.tensor(float(q_value), dtype=torch.float32)
+        else:
+            sample["lq"] = self._pil_round_trip(gt, q_value)
+        return _labelled(sample, self.opt)
 
 
 DATASET_REGISTRY._obj_map["PairedImageDehazeDataset"] = PairedImageDataset

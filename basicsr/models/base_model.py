@@ -33,6 +33,14 @@ class BaseModel:
     def feed_data(self, data):
         pass
 
+    def _lq_on_device(self, data):
+        """the degraded batch of ``feed_data``: ``data["lq"]`` moved to the device, as ever; a batch of a ``jpeg_backend: device`` set
+        (PairedImageJPEGCARDataset: ``gt`` and ``jpeg_quality``, no ``lq``) gets it from the JPEG round trip of ``gt`` on the device"""
+        if "lq" not in data and "jpeg_quality" in data:
+            gt = data["gt"].to(self.device, non_blocking=True)
+            return DF.diffjpeg(gt, data["jpeg_quality"].to(self.device, non_blocking=True), uint8_io=True)
+        return data["lq"].to(self.device, non_blocking=True)
+
     def optimize_parameters(self, current_iter):
         pass
 

@@ -91,7 +91,7 @@ class DCDistModel(SRModel):
         self.hook_outputs.append(output)
 
     def feed_data(self, data):
-        self.lq = data["lq"].to(self.device, non_blocking=True)
+        self.lq = self._lq_on_device(data)
         if "dataset_idx" in data:
             self.dataset_idx = data["dataset_idx"].to(self.device, non_blocking=True)
         if "dataset_idx" in self.opt:   # one degradation for the whole run (:147-150)

@@ -140,7 +140,7 @@ class DCPTModel(BaseModel):
             self.optimizers.append(opt)
 
     def feed_data(self, data):
-        self.lq = data["lq"].to(self.device, non_blocking=True)
+        self.lq = self._lq_on_device(data)
         self.dataset_idx = data["dataset_idx"].to(self.device, non_blocking=True)
         if "gt" in data:
             self.gt = data["gt"].to(self.device, non_blocking=True)

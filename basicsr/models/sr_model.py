@@ -132,7 +132,7 @@ class SRModel(BaseModel):
         self.optimizers.append(self.optimizer_g)
 
     def feed_data(self, data):
-        self.lq = data["lq"].to(self.device, non_blocking=True)
+        self.lq = self._lq_on_device(data)
         if "gt" in data:
             self.gt = data["gt"].to(self.device, non_blocking=True)
 

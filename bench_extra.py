@@ -2,7 +2,7 @@
 """Secondary workloads of BASELINE.json (configs[2..4]) on ONE MI355X -- evidence for DESIGN.md, not the driver's
 contract (that is bench.py).  Prints one JSON line per workload.
 
-    python bench_extra.py --workload dcpt|dcpt_swinir|restormer|promptir|infer2k|naf|swinir|rcan|val_metrics|step_tail|tlsc|ssim_loss|ldl [--dtype fp32|bf16|bf16_res32] [--steps K] [--warmup W]
+    python bench_extra.py --workload dcpt|dcpt_swinir|restormer|promptir|infer2k|naf|swinir|rcan|val_metrics|step_tail|tlsc|ssim_loss|ldl|jpeg [--dtype fp32|bf16|bf16_res32] [--steps K] [--warmup W]
 
 ``--dtype bf16`` (dcpt, naf, infer2k, restormer, promptir; rcan: the inference line only, next to fp32; swinir: the restoration form's inference, next to fp32): every feature map of the encoder in bf16 storage with fp32 accumulation (act_dtype="bf16";
 dcpt: the classifier head too unless --head-dtype fp32); images, parameters and the optimizer stay fp32.  Its lines carry BOTH
@@ -711,9 +711,126 @@ def run_ldl(dev, steps=20, warmup=3, B=32, S=256):
     return res
 
 
+def run_jpeg(dev, steps=20, warmup=3, B=32, S=256):
+    """The JPEG round trip of a B x 3 x S x S batch with one quality per image (10 / 20 / 30 / 40 in turn), ``uint8_io`` off: the kernel
+    route (dcpt_amd.functional.diffjpeg, dcpt_amd/csrc/jpeg.hip) against a torch route on the device, the reference DiffJPEG's arithmetic
+    op by op in fp32 (pad, colour tensordot, avg_pool2d, block split, the two 64-term tensordots per component, table division, round,
+    and the way back).  The two alternate call by call in one process; each call is bracketed by device events; median and minimum of the
+    per-call times after the warm-up, each route's peak memory above what is resident between calls, and the host time of a PIL JPEG
+    encode + decode of the same B images (what ``jpeg_backend: pil`` does per sample)."""
+    import io
+    import itertools
+    import math
+    import statistics
+    import time
+
+    import numpy as np
+    import torch.nn.functional as F
+    from PIL import Image
+
+    from dcpt_amd import functional as DF
+
+    g = torch.Generator(device=dev).manual_seed(1234)
+    low = torch.rand((B, 3, S // 8, S // 8), generator=g, device=dev)
+    x = (F.interpolate(low, size=(S, S), mode="bilinear", align_corners=False) + 0.04 * torch.randn((B, 3, S, S), generator=g, device=dev)).clamp(0, 1)
+    q = torch.tensor([(10.0, 20.0, 30.0, 40.0)[i % 4] for i in range(B)], device=dev)
+
+    luma = torch.tensor([[16, 11, 10, 16, 24, 40, 51, 61], [12, 12, 14, 19, 26, 58, 60, 55], [14, 13, 16, 24, 40, 57, 69, 56],
+                         [14, 17, 22, 29, 51, 87, 80, 62], [18, 22, 37, 56, 68, 109, 103, 77], [24, 35, 55, 64, 81, 104, 113, 92],
+                         [49, 64, 78, 87, 103, 121, 120, 101], [72, 92, 95, 98, 112, 100, 103, 99]], dtype=torch.float32, device=dev).t().contiguous()
+    chroma = torch.full((8, 8), 99.0, device=dev)
+    chroma[:4, :4] = torch.tensor([[17, 18, 24, 47], [18, 21, 26, 66], [24, 26, 56, 99], [47, 66, 99, 99]], dtype=torch.float32, device=dev).t()
+    to_ycc = torch.tensor([[0.299, 0.587, 0.114], [-0.168736, -0.331264, 0.5], [0.5, -0.418688, -0.081312]], device=dev).t().contiguous()
+    to_rgb = torch.tensor([[1.0, 0.0, 1.402], [1.0, -0.344136, -0.714136], [1.0, 1.772, 0.0]], device=dev).t().contiguous()
+    shift = torch.tensor([0.0, 128.0, 128.0], device=dev)
+    fwd4 = torch.zeros((8, 8, 8, 8))
+    inv4 = torch.zeros((8, 8, 8, 8))
+    for a, b, u, v in itertools.product(range(8), repeat=4):
+        fwd4[a, b, u, v] = math.cos((2 * a + 1) * u * math.pi / 16) * math.cos((2 * b + 1) * v * math.pi / 16)
+        inv4[a, b, u, v] = math.cos((2 * u + 1) * a * math.pi / 16) * math.cos((2 * v + 1) * b * math.pi / 16)
+    fwd4, inv4 = fwd4.to(dev), inv4.to(dev)
+    alpha = torch.tensor([1 / math.sqrt(2)] + [1.0] * 7)
+    alpha2 = torch.outer(alpha, alpha).to(dev)
+
+    def split(p):
+        n, h, w = p.shape
+        return p.view(n, h // 8, 8, w // 8, 8).permute(0, 1, 3, 2, 4).contiguous().view(n, -1, 8, 8)
+
+    def merge(p, h, w):
+        return p.view(p.shape[0], h // 8, w // 8, 8, 8).permute(0, 1, 3, 2, 4).contiguous().view(p.shape[0], h, w)
+
+    def torch_route(img, quality):
+        n, _, h, w = img.shape
+        factor = (torch.where(quality < 50, 5000.0 / quality, 200.0 - quality * 2) / 100.0).view(n, 1, 1, 1)
+        hp, wp = h + (-h % 16), w + (-w % 16)
+        im = F.pad(img, (0, wp - w, 0, hp - h)) * 255
+        ycc = torch.tensordot(im.permute(0, 2, 3, 1), to_ycc, dims=1) + shift
+        planes = ycc.permute(0, 3, 1, 2).clone()
+        comps = [ycc[..., 0], F.avg_pool2d(planes[:, 1:2], 2).squeeze(1), F.avg_pool2d(planes[:, 2:3], 2).squeeze(1)]
+        out = []
+        for k, comp in enumerate(comps):
+            table = (luma if k == 0 else chroma).expand(n, 1, 8, 8) * factor
+            coef = (alpha2 * 0.25) * torch.tensordot(split(comp) - 128, fwd4, dims=2)
+            deq = torch.round(coef / table) * table
+            rec = 0.25 * torch.tensordot(deq * alpha2, inv4, dims=2) + 128
+            out.append(merge(rec, hp // (1 if k == 0 else 2), wp // (1 if k == 0 else 2)))
+        up = [out[0]] + [c.unsqueeze(-1).repeat(1, 1, 2, 2).view(n, hp, wp) for c in out[1:]]
+        rgb = torch.tensordot(torch.stack(up, 3) + (-shift), to_rgb, dims=1).permute(0, 3, 1, 2)
+        rgb = torch.min(255 * torch.ones_like(rgb), torch.max(torch.zeros_like(rgb), rgb)) / 255
+        return rgb[:, :, :h, :w]
+
+    routes = {"kernel": lambda: DF.diffjpeg(x, q), "torch": lambda: torch_route(x, q)}
+    peaks, last = {}, {}
+
+    def call(name):
+        torch.cuda.synchronize(dev)
+        base = torch.cuda.memory_allocated(dev)
+        torch.cuda.reset_peak_memory_stats(dev)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        y = routes[name]()
+        e1.record()
+        e1.synchronize()
+        peaks[name] = max(peaks.get(name, 0), torch.cuda.max_memory_allocated(dev) - base)
+        last[name] = y
+        return e0.elapsed_time(e1)
+
+    times = {n: [] for n in routes}
+    with torch.no_grad():
+        for i in range(warmup + steps):
+            for n in routes:
+                t = call(n)
+                if i >= warmup:
+                    times[n].append(t)
+    diff = (last["kernel"] - last["torch"]).abs()
+    hwc = (x.permute(0, 2, 3, 1) * 255).round().to(torch.uint8).cpu().numpy()
+    qs = [int(v) for v in q.tolist()]
+    pil = []
+    for _ in range(3):
+        t0 = time.perf_counter()
+        for im, qq in zip(hwc, qs):
+            buf = io.BytesIO()
+            Image.fromarray(im).save(buf, format="JPEG", quality=qq)
+            buf.seek(0)
+            np.asarray(Image.open(buf).convert("RGB"), dtype=np.float32)
+        pil.append((time.perf_counter() - t0) * 1e3)
+    return dict(workload=f"JPEG round trip, {B} x 3 x {S} x {S}, one quality per image (10 / 20 / 30 / 40): DiffJPEG(differentiable=False)",
+                kernel_ms_median=round(statistics.median(times["kernel"]), 4), kernel_ms_min=round(min(times["kernel"]), 4),
+                torch_ms_median=round(statistics.median(times["torch"]), 4), torch_ms_min=round(min(times["torch"]), 4),
+                ratio_median=round(statistics.median(times["torch"]) / statistics.median(times["kernel"]), 2),
+                kernel_peak_mb=round(peaks["kernel"] / 1e6, 1), torch_peak_mb=round(peaks["torch"] / 1e6, 1),
+                pil_host_ms_min=round(min(pil), 2), pil_images=B,
+                max_abs_diff=float(diff.max()), share_above_1e_3=float((diff > 1e-3).float().mean()), calls=steps, warmup=warmup,
+                note="device events around each call, the two routes alternating in one process; peak memory of a call above what is "
+                     "allocated between calls (the kernel route's is its output and the [B] quality tensor); the torch route is the "
+                     "reference's fp32 op sequence; max_abs_diff / share_above_1e_3 compare the two routes' outputs (a coefficient the fp32 "
+                     "route rounds the other way shows as a block-sized difference); pil_host_ms_min is one thread's encode + decode of "
+                     "all B images, best of 3")
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", required=True, choices=["dcpt", "dcpt_swinir", "restormer", "promptir", "infer2k", "naf", "swinir", "rcan", "val_metrics", "step_tail", "tlsc", "ssim_loss", "ldl"])
+    ap.add_argument("--workload", required=True, choices=["dcpt", "dcpt_swinir", "restormer", "promptir", "infer2k", "naf", "swinir", "rcan", "val_metrics", "step_tail", "tlsc", "ssim_loss", "ldl", "jpeg"])
     ap.add_argument("--dtype", default="fp32", choices=["fp32", "bf16", "bf16_tail32", "bf16_edge32", "bf16_res32"])
     ap.add_argument("--head-dtype", default=None, choices=["fp32", "bf16"], help="dcpt: classifier-head activations (default: --dtype)")
     ap.add_argument("--restormer-save", default="balanced", choices=["auto", "lean", "balanced", "full"], help="what the Restormer halves keep for backward")
@@ -907,6 +1024,8 @@ def main():
         res = run_ssim_loss(dev, max(args.steps, 20), max(args.warmup, 3), args.batch or 32, args.size or 256)
     elif args.workload == "ldl":
         res = run_ldl(dev, max(args.steps, 20), max(args.warmup, 3), args.batch or 32, args.size or 256)
+    elif args.workload == "jpeg":
+        res = run_jpeg(dev, max(args.steps, 20), max(args.warmup, 3), args.batch or 32, args.size or 256)
     elif args.workload == "tlsc":
         res = run_tlsc(dev, args.steps, args.warmup, tile=args.tile, streams=args.tile_streams)
     else:

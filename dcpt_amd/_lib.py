@@ -339,6 +339,7 @@ SIGNATURES = {
     "dcpt_ldl_weight_ws_bytes": (sz, [cint, cint, cint, cint, cint]),
     "dcpt_ldl_weight_fwd": (cint, [f32p, f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint, stream_t]),
     "dcpt_ldl_weight_bwd": (cint, [f32p, f32p, f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint, stream_t]),
+    "dcpt_diffjpeg_fwd": (cint, [f32p, f32p, f32p, cint, cint, cint, cint, cint, stream_t]),
     "dcpt_trace_enable": (cint, [cint]),
     "dcpt_trace_read": (sz, [C.c_char_p, sz]),
     "dcpt_prof_enable": (cint, [cint]),

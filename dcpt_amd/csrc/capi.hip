@@ -427,3 +427,15 @@ extern "C" int dcpt_ldl_weight_bwd(const float* gt, const float* out, const floa
     DCPT_CHECK_WS("ldl_weight_bwd", ws, ws_bytes, need);
     return launch_ldl_weight_bwd(gt, out, gw, dout, m, B, C, H, W, (hipStream_t)stream);
 }
+
+// ---------------------------------------------------------------------------------------------
+// The DiffJPEG round trip (jpeg.hip)
+extern "C" int dcpt_diffjpeg_fwd(const float* x, const float* quality, float* y, int B, int C, int H, int W, int flags, dcpt_stream_t stream) {
+    DCPT_CHECK_ARG(x && quality && y, "diffjpeg_fwd: null argument");
+    DCPT_CHECK_ARG(B > 0 && H > 0 && W > 0, "diffjpeg_fwd: bad shape (B=%d C=%d H=%d W=%d)", B, C, H, W);
+    DCPT_CHECK_ARG(C == 1 || C == 3, "diffjpeg_fwd: C must be 1 or 3 (got %d)", C);
+    DCPT_CHECK_ARG((flags & ~(DCPT_JPEG_DIFF_ROUND | DCPT_JPEG_UINT8_IO)) == 0, "diffjpeg_fwd: unknown flags 0x%x", flags);
+    DCPT_CHECK_ARG(B <= 65535, "diffjpeg_fwd: B above 65535 (got %d)", B);
+    DCPT_CHECK_ARG((int64_t)H * W <= ((int64_t)1 << 30), "diffjpeg_fwd: a plane above 2^30 pixels (H=%d W=%d)", H, W);
+    return launch_diffjpeg_fwd(x, quality, y, B, C, H, W, flags, (hipStream_t)stream);
+}

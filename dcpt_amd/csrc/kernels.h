@@ -205,3 +205,7 @@ int64_t ldl_num_partials(int B, int C, int H, int W);
 int launch_ldl_weight_fwd(const float* gt, const float* out, float* w, const LdlWs& ws, int B, int C, int H, int W, hipStream_t s);
 int launch_ldl_weight_bwd(const float* gt, const float* out, const float* gw, float* dout, const LdlWs& ws, int B, int C, int H, int W,
                           hipStream_t s);
+
+// ---- jpeg.hip -------------------------------------------------------------------------------
+// The DiffJPEG round trip (dcpt_diffjpeg_fwd): x, y fp32 NCHW planes, quality [B] on the device; one launch, no workspace.
+int launch_diffjpeg_fwd(const float* x, const float* quality, float* y, int B, int C, int H, int W, int flags, hipStream_t s);

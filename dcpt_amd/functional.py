@@ -2289,9 +2289,9 @@ def conv3x3_ps(x, weight, bias, r):
 
 # RCAN on bf16 activation storage (include/dcpt_hip.h dcpt_rcab_fwd_bf16, dcpt_conv3x3_res_fwd_bf16, dcpt_conv3x3_ps_fwd_bf16): forward only.
 # Feature maps are torch.bfloat16 channels_last, parameters fp32; ``packed*``: the conv's PackedConvBf16 cache (without it the call packs).
-def _inference_only(name, *ts):
+def _inference_only(name, *ts, what="bf16 storage for RCAN"):
     if _wants_grad(*ts):
-        raise NotImplementedError(f"{name}: bf16 storage for RCAN is inference-only (there is no backward pass); run it under torch.no_grad()")
+        raise NotImplementedError(f"{name}: {what} is inference-only (there is no backward pass); run it under torch.no_grad()")
 
 
 def rcab_bf16(x, conv1_w, conv1_b, conv2_w, conv2_b, ca1_w, ca1_b, ca2_w, ca2_b, res_scale=1.0, packed1: PackedConvBf16 = None,
@@ -2917,3 +2917,40 @@ def ldl_weight(gt, out):
     if gt.requires_grad:
         raise NotImplementedError("ldl_weight differentiates with respect to out only; detach the target")
     return _LdlWeightFn.apply(gt, out)
+
+
+# ------------------------------------------------------------------------------------------------
+# The DiffJPEG round trip (include/dcpt_hip.h dcpt_diffjpeg_fwd): the reference's DiffJPEG.forward (basicsr/utils/diffjpeg.py:494-523) as one
+# fp64 kernel, one read and one write of the batch.
+JPEG_DIFF_ROUND, JPEG_UINT8_IO = 1, 2   # include/dcpt_hip.h DCPT_JPEG_*
+
+
+def diffjpeg(x, quality, differentiable=False, uint8_io=False):
+    """The JPEG round trip of ``DiffJPEG(differentiable).forward(x, quality)``: ``x`` (B, 1 or 3, H, W) fp32 device tensor in [0, 1] (any
+    strides: it is made contiguous NCHW); ``quality`` a Python number in (0, 100) -- at 100 the reference's factor is 0 and it divides by
+    zero -- or a (B,) tensor with one quality per image.  Returns the decoded batch, fp32 NCHW.  ``differentiable=True`` runs the
+    reference's cubic ``diff_round`` in the FORWARD; there is no backward pass (an input that requires grad raises under grad mode).
+    ``uint8_io=True``: the input is first rounded to the 8-bit grid and the output is ``rint(decoded) / 255``, what the reference's dataset
+    gets from ``cv2.imencode`` / ``imdecode`` (paired_image_dataset.py:539-546).  One departure from the reference: the caller's quality
+    tensor is NOT modified (the reference overwrites it in place with the factors, diffjpeg.py:504-505)."""
+    if not torch.is_tensor(x):
+        raise _lib.DcptHipError(f"diffjpeg takes a device tensor (got {type(x).__name__})")
+    _require_gpu(x)
+    if x.dim() != 4 or x.shape[1] not in (1, 3):
+        raise ValueError(f"diffjpeg: expected a (B, 1 or 3, H, W) batch, got {tuple(x.shape)}")
+    _inference_only("diffjpeg", x, what="the JPEG round trip")
+    B, C, H, W = x.shape
+    dev = x.device
+    if torch.is_tensor(quality):
+        if quality.numel() != B or quality.dim() > 1:
+            raise ValueError(f"diffjpeg: quality must be a number or a ({B},) tensor, got {tuple(quality.shape)}")
+        q = quality.detach().to(device=dev, dtype=torch.float32).reshape(B).contiguous()   # (read by the kernel, never written)
+    else:
+        if not 0 < float(quality) < 100:
+            raise ValueError(f"diffjpeg: quality must lie in (0, 100), got {quality!r} (at 100 the quantisation factor is 0)")
+        q = torch.full((B,), float(quality), dtype=torch.float32, device=dev)
+    x = x.detach().contiguous()
+    y = torch.empty_like(x)
+    flags = (JPEG_DIFF_ROUND if differentiable else 0) | (JPEG_UINT8_IO if uint8_io else 0)
+    _call(_lib.load().dcpt_diffjpeg_fwd, (x, q, y), (B, C, H, W, flags), dev)
+    return y

@@ -855,6 +855,29 @@ int dcpt_ldl_weight_fwd(const float* gt, const float* out, float* w, void* ws, s
 int dcpt_ldl_weight_bwd(const float* gt, const float* out, const float* gw, float* dout, void* ws, size_t ws_bytes, int B, int C, int H,
                         int W, dcpt_stream_t stream);
 
+/* ---- DiffJPEG: the JPEG round trip of a batch, on the device -------------------------------------------
+ * replaces basicsr/utils/diffjpeg.py:494-523 (DiffJPEG.forward) with everything it calls: the zero padding to a multiple of 16 (:509-515),
+ * x * 255 and RGB -> YCbCr (:59-85, :256), the 2 x 2 chroma mean (:88-119), block splitting and the 8 x 8 DCT of v - 128 with the
+ * alpha / 4 scale (:122-171), the division by table * factor with the transposed luma table and the chroma table (:15-34, :174-231),
+ * factor = quality_to_factor(quality[b]) per image (:42-55, evaluated in the kernel: 50 / q below 50, 2 - q / 50 from 50 on), the rounding
+ * (torch.round, or with DCPT_JPEG_DIFF_ROUND diff_round, :37-39: round(t) + (t - round(t))^3), the dequantisation (:273-318), the iDCT
+ * + 128 (:321-346), block merging, the 2 x 2 chroma repeat (:349-398), YCbCr -> RGB (:401-423), the clamp to [0, 255] and / 255
+ * (:467-470) and the crop (:519); C == 1 uses the plane as all three channels and returns the mean of the three decoded channels
+ * (:507-508, :521-522).  With DCPT_JPEG_UINT8_IO the input is first put on the 8-bit grid, rint(x * 255), and the output is
+ * rint(clamped) / 255: what basicsr/data/paired_image_dataset.py:539-546 gets from cv2.imencode / imdecode of the rounded image (with
+ * C == 1, rint of the mean of the three clamped channels).
+ *   x, y      dense NCHW fp32 [B][C][H][W] in [0, 1] -- the layout of lq / gt, not the NHWC of the feature maps; C = 1 or 3
+ *   quality   [B] fp32 on the device, one value per image; it is read, never written (the reference overwrites it with the factors)
+ * One launch; one read of x and one write of y; the pad is addressed, never stored.  fp64 from the pixel load to the one rounding to
+ * fp32 at the store, so the rounding of a coefficient never hinges on an fp32 summation order; the one departure from the reference: its
+ * fp32 pipeline can round a coefficient the other way when the exact value lies within about 1e-4 of a tie.  No workspace, no atomics, no
+ * host synchronisation, no global state; an image's result does not depend on the batch around it; the same input gives the same bits.
+ * Errors (before the launch): null pointers, non-positive sizes, C not 1 or 3, unknown flag bits, B above 65535, a plane above 2^30
+ * pixels. */
+#define DCPT_JPEG_DIFF_ROUND 1   /* differentiable=True: the cubic rounding */
+#define DCPT_JPEG_UINT8_IO 2     /* 8-bit input and output grids */
+int dcpt_diffjpeg_fwd(const float* x, const float* quality, float* y, int B, int C, int H, int W, int flags, dcpt_stream_t stream);
+
 /* ---- optional launch profiling (bench.py) -------------------------------------------------------
  * While enabled, MFMA GEMM launches are bracketed by HIP events on their own stream: every launch for on = 1, every
  * on-th launch for on > 1 (sampling keeps the perturbation of a timed region small: an event pair costs ~3 us of queue time).
