@@ -27,15 +27,23 @@ kernel of dcpt_amd/csrc/metrics.hip (same arithmetic, image_range 255 or 1); the
 against (tests/test_gpu_metrics.py).
 
 ``calculate_ssim_pt`` (reference psnr_ssim.py:436-480) is the differentiable SSIM of the losses: (B, C, H, W) fp32 device tensors in, the
-per-image SSIM as a float64 tensor out, forward and gradient on the fused fp64 kernels of dcpt_amd/csrc/ssim_loss.hip."""
+per-image SSIM as a float64 tensor out, forward and gradient on the fused fp64 kernels of dcpt_amd/csrc/ssim_loss.hip.
+
+``calculate_niqe`` / ``calculate_niqe_device`` / ``NiqeSums`` (reference basicsr/metrics/niqe.py) live in basicsr/metrics/niqe.py: the no-reference
+metric, on the host in numpy float64 and on the fused fp64 kernels of dcpt_amd/csrc/niqe.hip, with one shared host finish."""
 from copy import deepcopy
 
 import numpy as np
 
 from basicsr.utils.registry import METRIC_REGISTRY
 
+from .niqe import NiqeSums, calculate_niqe, calculate_niqe_device
+
 __all__ = ["calculate_metric", "calculate_psnr", "calculate_ssim", "calculate_psnr_device", "calculate_ssim_device", "MetricSums",
-           "calculate_ssim_pt"]
+           "calculate_ssim_pt", "calculate_niqe", "calculate_niqe_device", "NiqeSums"]
+
+METRIC_REGISTRY.register()(calculate_niqe)
+METRIC_REGISTRY.register()(calculate_niqe_device)
 
 
 def _reorder(img, input_order):
@@ -160,15 +168,22 @@ class MetricSums:
         cp = 1 if (self.test_y_channel and c == 3) else c
         self._parts.append((sse, sums, hc * wc * cp, (hc - 10) * (wc - 10)))
 
-    def result(self):
+    def pending(self):
+        """the device tensors ``result`` needs, flat, as 8-byte words (the exact int64 sums bit for bit): a caller that holds several
+        accumulators concatenates them, transfers once and hands every accumulator its slice (``result(host)``)"""
+        import torch
+
+        return [t.reshape(-1).view(torch.int64) for sse, sums, _, _ in self._parts for t in (sse, sums) if t is not None]
+
+    def result(self, host=None):
+        """``host``: the int64 numpy array of ``torch.cat(self.pending())`` if the caller made the transfer; else it is made here"""
         import torch
 
         out = {"psnr": [], "ssim": []}
         if not self._parts:
             return out
-        # one transfer: every piece travels as 8-byte words (the exact int64 sums bit for bit)
-        flat = [t.reshape(-1).view(torch.int64) for sse, sums, _, _ in self._parts for t in (sse, sums) if t is not None]
-        host = torch.cat(flat).cpu().numpy()
+        if host is None:
+            host = torch.cat(self.pending()).cpu().numpy()   # one transfer
         pos = 0
         for sse, sums, npix, npos in self._parts:
             raw = host[pos:pos + sse.numel()]

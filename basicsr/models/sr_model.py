@@ -389,8 +389,14 @@ class SRModel(BaseModel):
             del self.lq, self.output
             if hasattr(self, "gt"):
                 del self.gt
-        for key, acc in sums.items():   # the one synchronisation of the device route: every image's sums in one transfer
-            per_batch = acc.result()
+        # the one synchronisation of the device route: every accumulator's sums of every image in one transfer
+        pending = {key: acc.pending() for key, acc in sums.items()}
+        flat = [t for ts in pending.values() for t in ts]
+        host, pos = (torch.cat(flat).cpu().numpy() if flat else None), 0
+        for key, acc in sums.items():
+            n_words = sum(t.numel() for t in pending[key])
+            per_batch = acc.result(host[pos:pos + n_words]) if flat else acc.result()
+            pos += n_words
             for m, (k, kind) in on_device.items():
                 if k == key:
                     for v in per_batch[kind]:
@@ -409,13 +415,18 @@ class SRModel(BaseModel):
 
     def _device_metric_plan(self, metrics_opt, clamp):
         """``val.device_metrics: true`` (opt-in): which metrics are scored on the device (basicsr.metrics.MetricSums), as
-        {name: ((crop_border, test_y_channel, image_range), "psnr" | "ssim")}.  Only what the kernel mirrors exactly qualifies: clamped
-        images, ``calculate_psnr`` / ``calculate_ssim``, BCHW order, image_range 255 or 1; any other metric keeps the host function, and
-        without ``clamp`` (raw outputs, NaNs included) or off the GPU the whole call does."""
+        {name: ((crop_border, test_y_channel, image_range), "psnr" | "ssim")}, and ``calculate_niqe`` (basicsr.metrics.NiqeSums) as
+        {name: (("niqe", crop_border, pris_params), "niqe")}.  Only what the kernels mirror exactly qualifies: clamped images,
+        ``calculate_psnr`` / ``calculate_ssim`` / ``calculate_niqe``, BCHW order, image_range 255 or 1; any other metric keeps the host
+        function, and without ``clamp`` (raw outputs, NaNs included) or off the GPU the whole call does."""
         if not self.opt["val"].get("device_metrics", False) or not clamp or self.device.type != "cuda":
             return {}
         plan = {}
         for m, mo in metrics_opt.items():
+            if mo.get("type") == "calculate_niqe":   # basicsr.metrics.NiqeSums: its own accumulator per (crop_border, pris_params)
+                if mo.get("input_order", "BCHW") == "BCHW":
+                    plan[m] = (("niqe", int(mo.get("crop_border", 0)), mo.get("pris_params")), "niqe")
+                continue
             kind = {"calculate_psnr": "psnr", "calculate_ssim": "ssim"}.get(mo.get("type"))
             if kind is None or mo.get("input_order", "BCHW") != "BCHW" or mo.get("image_range", 255) not in (255, 1):
                 continue
@@ -425,7 +436,7 @@ class SRModel(BaseModel):
     def _validate_on_device(self, val_data, name, save_img, metrics_opt, on_device, sums, results):
         """one validation batch of the device route: clamp on the device, hand ``self.output`` / ``self.gt`` to the accumulators without
         ``get_current_visuals()``; the result travels to the host only for ``save_img`` or a metric that stayed on the host"""
-        from basicsr.metrics import MetricSums
+        from basicsr.metrics import MetricSums, NiqeSums
 
         result_dev = self.output.detach().float().clamp(0, 1)
         host_metrics = [m for m in metrics_opt if m not in on_device] if hasattr(self, "gt") else []
@@ -445,8 +456,11 @@ class SRModel(BaseModel):
         for key in dict.fromkeys(key for key, _ in on_device.values()):   # one accumulator (one launch pair) per distinct option set
             if key not in sums:
                 kinds = {k for kk, k in on_device.values() if kk == key}
-                sums[key] = MetricSums(crop_border=key[0], test_y_channel=key[1], image_range=key[2], psnr="psnr" in kinds,
-                                       ssim="ssim" in kinds)
+                if key[0] == "niqe":
+                    sums[key] = NiqeSums(crop_border=key[1], pris_params=key[2])
+                else:
+                    sums[key] = MetricSums(crop_border=key[0], test_y_channel=key[1], image_range=key[2], psnr="psnr" in kinds,
+                                           ssim="ssim" in kinds)
             sums[key].add(result_dev, gt_dev)
         if host_metrics:
             gt = gt_dev.cpu().numpy()

@@ -2,7 +2,7 @@
 """Secondary workloads of BASELINE.json (configs[2..4]) on ONE MI355X -- evidence for DESIGN.md, not the driver's
 contract (that is bench.py).  Prints one JSON line per workload.
 
-    python bench_extra.py --workload dcpt|dcpt_swinir|restormer|promptir|infer2k|naf|swinir|rcan|val_metrics|step_tail|tlsc|ssim_loss|ldl|jpeg [--dtype fp32|bf16|bf16_res32] [--steps K] [--warmup W]
+    python bench_extra.py --workload dcpt|dcpt_swinir|restormer|promptir|infer2k|naf|swinir|rcan|val_metrics|step_tail|tlsc|ssim_loss|ldl|jpeg|niqe [--dtype fp32|bf16|bf16_res32] [--steps K] [--warmup W]
 
 ``--dtype bf16`` (dcpt, naf, infer2k, restormer, promptir; rcan: the inference line only, next to fp32; swinir: the restoration form's inference, next to fp32): every feature map of the encoder in bf16 storage with fp32 accumulation (act_dtype="bf16";
 dcpt: the classifier head too unless --head-dtype fp32); images, parameters and the optimizer stay fp32.  Its lines carry BOTH
@@ -828,9 +828,57 @@ def run_jpeg(dev, steps=20, warmup=3, B=32, S=256):
                      "all B images, best of 3")
 
 
+def run_niqe(dev, steps=20, warmup=3, H=1080, W=2048):
+    """NIQE of one 1 x 3 x H x W image (a smooth random field plus fine noise, no flat block): the host ``calculate_niqe`` (numpy float64,
+    one thread's wall time, best of 2) against ``calculate_niqe_device`` (the fused fp64 kernels of dcpt_amd/csrc/niqe.hip + the host
+    finish; device events around each whole call, which ends with the one transfer and the 36 x 36 algebra) and against the launches
+    alone (dcpt_amd.functional.niqe_stats).  The pristine model is read from DCPT_NIQE_PRIS_PARAMS, else tests/golden."""
+    import statistics
+
+    from basicsr.metrics import calculate_niqe, calculate_niqe_device
+    from dcpt_amd import functional as DF
+
+    pris = os.environ.get("DCPT_NIQE_PRIS_PARAMS") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "tests", "golden",
+                                                                    "niqe_pris_params.npz")
+    g = torch.Generator().manual_seed(19)
+    low = torch.rand((1, 3, H // 16, W // 16), generator=g) * 0.5 + 0.25
+    img = (torch.nn.functional.interpolate(low, size=(H, W), mode="bicubic", align_corners=False)
+           + 0.02 * torch.randn((1, 3, H, W), generator=g)).clamp(0, 1)
+    x = img.to(dev)
+    host_ms = []
+    for _ in range(2):
+        t0 = time.perf_counter()
+        host = calculate_niqe(img.numpy(), 0, pris_params=pris)
+        host_ms.append((time.perf_counter() - t0) * 1e3)
+    routes = {"device": lambda: calculate_niqe_device(x, 0, pris_params=pris), "launches": lambda: DF.niqe_stats(x, 0)}
+    peaks, last, times = {}, {}, {n: [] for n in routes}
+    for i in range(warmup + steps):
+        for n, fn in routes.items():
+            torch.cuda.synchronize(dev)
+            base = torch.cuda.memory_allocated(dev)
+            torch.cuda.reset_peak_memory_stats(dev)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            last[n] = fn()
+            e1.record()
+            e1.synchronize()
+            peaks[n] = max(peaks.get(n, 0), torch.cuda.max_memory_allocated(dev) - base)
+            if i >= warmup:
+                times[n].append(e0.elapsed_time(e1))
+    return dict(workload=f"NIQE of one 1 x 3 x {H} x {W} image, crop_border 0",
+                host_ms_min=round(min(host_ms), 1), device_ms_median=round(statistics.median(times["device"]), 3),
+                device_ms_min=round(min(times["device"]), 3), launches_ms_median=round(statistics.median(times["launches"]), 4),
+                launches_ms_min=round(min(times["launches"]), 4), device_peak_mb=round(peaks["device"] / 1e6, 1),
+                niqe_host=host, niqe_device=last["device"], rel_diff=abs(host - last["device"]) / abs(host), calls=steps, warmup=warmup,
+                note="device events around each call; device_ms is calculate_niqe_device whole (six launches, the one transfer of the "
+                     "[3][231][2][5][6] sums, the numpy finish), launches_ms the six launches alone without a synchronisation inside; "
+                     "peak memory of a call above the resident image (MSCN plane, x0.5 image, resize intermediate in the workspace, "
+                     "sums); host_ms_min is numpy float64 on one thread's wall clock, best of 2")
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", required=True, choices=["dcpt", "dcpt_swinir", "restormer", "promptir", "infer2k", "naf", "swinir", "rcan", "val_metrics", "step_tail", "tlsc", "ssim_loss", "ldl", "jpeg"])
+    ap.add_argument("--workload", required=True, choices=["dcpt", "dcpt_swinir", "restormer", "promptir", "infer2k", "naf", "swinir", "rcan", "val_metrics", "step_tail", "tlsc", "ssim_loss", "ldl", "jpeg", "niqe"])
     ap.add_argument("--dtype", default="fp32", choices=["fp32", "bf16", "bf16_tail32", "bf16_edge32", "bf16_res32"])
     ap.add_argument("--head-dtype", default=None, choices=["fp32", "bf16"], help="dcpt: classifier-head activations (default: --dtype)")
     ap.add_argument("--restormer-save", default="balanced", choices=["auto", "lean", "balanced", "full"], help="what the Restormer halves keep for backward")
@@ -1026,6 +1074,8 @@ def main():
         res = run_ldl(dev, max(args.steps, 20), max(args.warmup, 3), args.batch or 32, args.size or 256)
     elif args.workload == "jpeg":
         res = run_jpeg(dev, max(args.steps, 20), max(args.warmup, 3), args.batch or 32, args.size or 256)
+    elif args.workload == "niqe":
+        res = run_niqe(dev, max(args.steps, 20), max(args.warmup, 3))
     elif args.workload == "tlsc":
         res = run_tlsc(dev, args.steps, args.warmup, tile=args.tile, streams=args.tile_streams)
     else:

@@ -340,6 +340,11 @@ SIGNATURES = {
     "dcpt_ldl_weight_fwd": (cint, [f32p, f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint, stream_t]),
     "dcpt_ldl_weight_bwd": (cint, [f32p, f32p, f32p, f32p, C.c_void_p, sz, cint, cint, cint, cint, stream_t]),
     "dcpt_diffjpeg_fwd": (cint, [f32p, f32p, f32p, cint, cint, cint, cint, cint, stream_t]),
+    "dcpt_imresize_ws_bytes": (sz, [cint, cint, cint, cint, cint, cint, cint]),
+    "dcpt_imresize_fwd": (cint, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, sz, cint, cint, cint,
+                                 cint, cint, cint, cint, i64, i64, cint, stream_t]),
+    "dcpt_niqe_mscn_fwd": (cint, [C.c_void_p, C.c_void_p, cint, cint, cint, cint, cint, stream_t]),
+    "dcpt_niqe_block_stats_fwd": (cint, [C.c_void_p, C.c_void_p, cint, cint, cint, cint, stream_t]),
     "dcpt_trace_enable": (cint, [cint]),
     "dcpt_trace_read": (sz, [C.c_char_p, sz]),
     "dcpt_prof_enable": (cint, [cint]),

@@ -439,3 +439,68 @@ extern "C" int dcpt_diffjpeg_fwd(const float* x, const float* quality, float* y,
     DCPT_CHECK_ARG((int64_t)H * W <= ((int64_t)1 << 30), "diffjpeg_fwd: a plane above 2^30 pixels (H=%d W=%d)", H, W);
     return launch_diffjpeg_fwd(x, quality, y, B, C, H, W, flags, (hipStream_t)stream);
 }
+
+// ---------------------------------------------------------------------------------------------
+// MATLAB-bicubic resize and the NIQE pixel work (niqe.hip)
+namespace {
+const char* imresize_check(int P, int H, int W, int Ho, int Wo, int Kh, int Kw) {
+    if (P <= 0 || H <= 0 || W <= 0 || Ho <= 0 || Wo <= 0) return "imresize: bad shape";
+    if (Kh <= 0 || Kw <= 0 || Kh > 4096 || Kw > 4096) return "imresize: the tap count per axis must lie in 1..4096";
+    if ((int64_t)H * W > ((int64_t)1 << 30) || (int64_t)Ho * Wo > ((int64_t)1 << 30) || (int64_t)Ho * W > ((int64_t)1 << 30))
+        return "imresize: a plane above 2^30 pixels";
+    if ((int64_t)P * Ho * W > ((int64_t)1 << 36) || (int64_t)P * Ho * Wo > ((int64_t)1 << 36)) return "imresize: above 2^36 elements";
+    return nullptr;
+}
+}  // namespace
+
+extern "C" size_t dcpt_imresize_ws_bytes(int P, int H, int W, int Ho, int Wo, int Kh, int Kw) {
+    if (imresize_check(P, H, W, Ho, Wo, Kh, Kw)) return 0;
+    return align_up((size_t)P * Ho * W * sizeof(double), 256);
+}
+
+extern "C" int dcpt_imresize_fwd(const void* x, void* y, const int* first_h, const double* w_h, const int* first_w, const double* w_w, void* ws,
+                                 size_t ws_bytes, int P, int H, int W, int Ho, int Wo, int Kh, int Kw, int64_t plane_stride,
+                                 int64_t row_stride, int flags, dcpt_stream_t stream) {
+    DCPT_CHECK_ARG(x && y && first_h && w_h && first_w && w_w, "imresize_fwd: null argument");
+    const char* bad = imresize_check(P, H, W, Ho, Wo, Kh, Kw);
+    DCPT_CHECK_ARG(!bad, "%s (P=%d H=%d W=%d Ho=%d Wo=%d Kh=%d Kw=%d)", bad, P, H, W, Ho, Wo, Kh, Kw);
+    DCPT_CHECK_ARG((flags & ~(DCPT_IMRESIZE_X_F64 | DCPT_IMRESIZE_Y_F64 | DCPT_IMRESIZE_QUANT8)) == 0, "imresize_fwd: unknown flags 0x%x", flags);
+    DCPT_CHECK_ARG(!((flags & DCPT_IMRESIZE_QUANT8) && (flags & DCPT_IMRESIZE_X_F64)), "imresize_fwd: DCPT_IMRESIZE_QUANT8 takes an fp32 source");
+    DCPT_CHECK_ARG(row_stride >= W && plane_stride >= (int64_t)(H - 1) * row_stride + W,
+                   "imresize_fwd: strides overlap (plane_stride=%lld row_stride=%lld H=%d W=%d)", (long long)plane_stride, (long long)row_stride,
+                   H, W);
+    DCPT_CHECK_WS("imresize_fwd", ws, ws_bytes, dcpt_imresize_ws_bytes(P, H, W, Ho, Wo, Kh, Kw));
+    return launch_imresize_fwd(x, y, first_h, w_h, first_w, w_w, (double*)ws, P, H, W, Ho, Wo, Kh, Kw, plane_stride, row_stride,
+                               (flags & DCPT_IMRESIZE_X_F64) != 0, (flags & DCPT_IMRESIZE_Y_F64) != 0, (flags & DCPT_IMRESIZE_QUANT8) != 0,
+                               (hipStream_t)stream);
+}
+
+extern "C" int dcpt_niqe_mscn_fwd(const void* x, double* n, int P, int H, int W, int crop_border, int scale, dcpt_stream_t stream) {
+    DCPT_CHECK_ARG(x && n, "niqe_mscn_fwd: null argument");
+    DCPT_CHECK_ARG(P > 0 && H > 0 && W > 0 && crop_border >= 0, "niqe_mscn_fwd: bad shape (P=%d H=%d W=%d crop_border=%d)", P, H, W, crop_border);
+    DCPT_CHECK_ARG(scale == 1 || scale == 2, "niqe_mscn_fwd: scale must be 1 or 2 (got %d)", scale);
+    DCPT_CHECK_ARG(P <= 65535, "niqe_mscn_fwd: above 65535 planes (got %d)", P);
+    DCPT_CHECK_ARG((int64_t)H * W <= ((int64_t)1 << 30), "niqe_mscn_fwd: a plane above 2^30 pixels (H=%d W=%d)", H, W);
+    int Hc = H, Wc = W;
+    if (scale == 1) {
+        DCPT_CHECK_ARG((int64_t)2 * crop_border < H && (int64_t)2 * crop_border < W, "niqe_mscn_fwd: nothing left after the crop (H=%d W=%d crop_border=%d)",
+                       H, W, crop_border);
+        Hc = (H - 2 * crop_border) / 96 * 96;
+        Wc = (W - 2 * crop_border) / 96 * 96;
+        DCPT_CHECK_ARG(Hc > 0 && Wc > 0, "niqe_mscn_fwd: no whole 96 x 96 block in the cropped plane (H=%d W=%d crop_border=%d)", H, W, crop_border);
+    } else {
+        DCPT_CHECK_ARG(crop_border == 0 && H % 48 == 0 && W % 48 == 0,
+                       "niqe_mscn_fwd: scale 2 takes whole 48 x 48 blocks and no crop (H=%d W=%d crop_border=%d)", H, W, crop_border);
+    }
+    return launch_niqe_mscn_fwd(x, n, P, H, W, crop_border, Hc, Wc, scale, (hipStream_t)stream);
+}
+
+extern "C" int dcpt_niqe_block_stats_fwd(const double* n, double* stats, int P, int H, int W, int block, dcpt_stream_t stream) {
+    DCPT_CHECK_ARG(n && stats, "niqe_block_stats_fwd: null argument");
+    DCPT_CHECK_ARG(block == 96 || block == 48, "niqe_block_stats_fwd: block must be 96 or 48 (got %d)", block);
+    DCPT_CHECK_ARG(P > 0 && H > 0 && W > 0 && H % block == 0 && W % block == 0,
+                   "niqe_block_stats_fwd: the plane must hold whole blocks (P=%d H=%d W=%d block=%d)", P, H, W, block);
+    DCPT_CHECK_ARG(P <= 65535, "niqe_block_stats_fwd: above 65535 planes (got %d)", P);
+    DCPT_CHECK_ARG((int64_t)H * W <= ((int64_t)1 << 30), "niqe_block_stats_fwd: a plane above 2^30 pixels (H=%d W=%d)", H, W);
+    return launch_niqe_block_stats_fwd(n, stats, P, H, W, block, (hipStream_t)stream);
+}

@@ -209,3 +209,12 @@ int launch_ldl_weight_bwd(const float* gt, const float* out, const float* gw, fl
 // ---- jpeg.hip -------------------------------------------------------------------------------
 // The DiffJPEG round trip (dcpt_diffjpeg_fwd): x, y fp32 NCHW planes, quality [B] on the device; one launch, no workspace.
 int launch_diffjpeg_fwd(const float* x, const float* quality, float* y, int B, int C, int H, int W, int flags, hipStream_t s);
+
+// ---- niqe.hip -------------------------------------------------------------------------------
+// MATLAB-bicubic resize (dcpt_imresize_fwd): t is the fp64 intermediate [P][Ho][W].  NIQE (dcpt_niqe_mscn_fwd, dcpt_niqe_block_stats_fwd):
+// the fp64 MSCN plane [P][Hc][Wc] of the cropped region and the [P][nblk][5][6] sums per block.
+int launch_imresize_fwd(const void* x, void* y, const int* first_h, const double* w_h, const int* first_w, const double* w_w, double* t, int P,
+                        int H, int W, int Ho, int Wo, int Kh, int Kw, int64_t plane_stride, int64_t row_stride, int x_f64, int y_f64,
+                        int quant, hipStream_t s);
+int launch_niqe_mscn_fwd(const void* x, double* n, int P, int H, int W, int crop, int Hc, int Wc, int scale, hipStream_t s);
+int launch_niqe_block_stats_fwd(const double* n, double* stats, int P, int H, int W, int block, hipStream_t s);

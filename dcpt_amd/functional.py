@@ -2954,3 +2954,124 @@ def diffjpeg(x, quality, differentiable=False, uint8_io=False):
     flags = (JPEG_DIFF_ROUND if differentiable else 0) | (JPEG_UINT8_IO if uint8_io else 0)
     _call(_lib.load().dcpt_diffjpeg_fwd, (x, q, y), (B, C, H, W, flags), dev)
     return y
+
+
+# ------------------------------------------------------------------------------------------------
+# MATLAB-bicubic resize and the pixel work of NIQE (include/dcpt_hip.h dcpt_imresize_fwd, dcpt_niqe_mscn_fwd, dcpt_niqe_block_stats_fwd):
+# the reference's basicsr/utils/matlab_functions.py::imresize and the per-pixel part of basicsr/metrics/niqe.py in fp64.  Forward only.
+IMRESIZE_X_F64, IMRESIZE_Y_F64, IMRESIZE_QUANT8 = 1, 2, 4   # include/dcpt_hip.h DCPT_IMRESIZE_*
+_RESIZE_TABLES: Dict[tuple, tuple] = {}                    # (length, scale, antialiasing, device) -> (first int32 [out], weights fp64 [out][K])
+
+
+def _resize_tables(n, scale, antialiasing, dev):
+    key = (int(n), float(scale), bool(antialiasing), dev.type, dev.index)
+    hit = _RESIZE_TABLES.get(key)
+    if hit is None:
+        from .matlab_resize import weights_indices
+
+        first, weights = weights_indices(n, scale, antialiasing)   # (ValueError for an input shorter than the kernel reaches)
+        hit = (torch.from_numpy(first).to(dev), torch.from_numpy(weights).to(dev))
+        _RESIZE_TABLES[key] = hit
+    return hit
+
+
+def _imresize_planes(x, P, H, W, plane_stride, row_stride, scale, antialiasing, y, flags):
+    """the resize of P planes read from ``x`` with the given strides into the dense ``y`` [P][Ho][Wo]; returns (Ho, Wo)"""
+    lib = _lib.load()
+    dev = x.device
+    (fh, wh), (fw, ww) = _resize_tables(H, scale, antialiasing, dev), _resize_tables(W, scale, antialiasing, dev)
+    Ho, Wo, Kh, Kw = fh.numel(), fw.numel(), wh.shape[1], ww.shape[1]
+    if y is not None:
+        if y.numel() != P * Ho * Wo or not y.is_contiguous():
+            raise ValueError(f"imresize: the output must be a dense tensor of {P} x {Ho} x {Wo} elements, got {tuple(y.shape)}")
+        nws = _check_ws("imresize", lib.dcpt_imresize_ws_bytes(P, H, W, Ho, Wo, Kh, Kw), f"P={P} H={H} W={W} -> {Ho} x {Wo}")
+        ws = _workspace(dev, nws)
+        _call(lib.dcpt_imresize_fwd, (x, y, fh, wh, fw, ww, ws, nws), (P, H, W, Ho, Wo, Kh, Kw, plane_stride, row_stride, flags), dev)
+    return Ho, Wo
+
+
+def imresize(x, scale, antialiasing=True, out_dtype=None):
+    """``imresize`` of the reference (MATLAB bicubic, one scale for both axes) on a (B, C, H, W) device tensor, fp32 or fp64; returns
+    (B, C, ceil(H scale), ceil(W scale)) of ``out_dtype`` (fp32 or fp64; default: the input's).  fp64 from the load to the one rounding at
+    the store.  An input shorter than the kernel reaches raises ValueError."""
+    if not torch.is_tensor(x):
+        raise _lib.DcptHipError(f"imresize takes a device tensor (got {type(x).__name__}); host arrays go to basicsr.utils.imresize")
+    _require((x,), (torch.float32, torch.float64), "imresize takes fp32 or fp64 planes (got {})")
+    if x.dim() != 4:
+        raise ValueError(f"imresize: expected a (B, C, H, W) tensor, got {tuple(x.shape)}")
+    out_dtype = out_dtype or x.dtype
+    if out_dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"imresize: the output is fp32 or fp64 (got {out_dtype})")
+    _inference_only("imresize", x, what="the MATLAB-bicubic resize")
+    x = _contig(x.detach())
+    B, Cc, H, W = x.shape
+    Ho, Wo = _imresize_planes(x, B * Cc, H, W, H * W, W, scale, antialiasing, None, 0)
+    y = torch.empty(B, Cc, Ho, Wo, dtype=out_dtype, device=x.device)
+    flags = (IMRESIZE_X_F64 if x.dtype == torch.float64 else 0) | (IMRESIZE_Y_F64 if out_dtype == torch.float64 else 0)
+    _imresize_planes(x, B * Cc, H, W, H * W, W, scale, antialiasing, y, flags)
+    return y
+
+
+def niqe_mscn(x, crop_border=0, scale=1, out=None):
+    """the MSCN planes of one NIQE scale: ``scale=1`` takes the (P, H, W) fp32 image in [0, 1] (8-bit rounding, crop_border and the crop to
+    whole 96 x 96 blocks by addressing), ``scale=2`` the (P, H, W) fp64 resize output; returns fp64 (P, Hc, Wc) (``out``: written in place)"""
+    lib = _lib.load()
+    _require((x,), (torch.float32,) if scale == 1 else (torch.float64,), "niqe_mscn: scale 1 reads fp32, scale 2 fp64 (got {})")
+    if x.dim() != 3 or not x.is_contiguous():
+        raise ValueError(f"niqe_mscn: expected dense (P, H, W) planes, got {tuple(x.shape)}")
+    P, H, W = x.shape
+    crop = int(crop_border)
+    Hc, Wc = ((H - 2 * crop) // 96 * 96, (W - 2 * crop) // 96 * 96) if scale == 1 else (H, W)
+    if out is None:
+        out = torch.empty(P, max(Hc, 0), max(Wc, 0), dtype=torch.float64, device=x.device)
+    elif out.dtype != torch.float64 or out.numel() != P * Hc * Wc or not out.is_contiguous():
+        raise ValueError(f"niqe_mscn: out must be a dense fp64 tensor of {P} x {Hc} x {Wc} elements")
+    _call(lib.dcpt_niqe_mscn_fwd, (x, out), (P, H, W, crop, int(scale)), x.device)
+    return out
+
+
+def niqe_block_stats(n, block, out=None):
+    """fp64 MSCN planes (P, H, W), H and W multiples of ``block`` (96 or 48) -> the sums (P, nblk, 5, 6) fp64, blocks column-major"""
+    lib = _lib.load()
+    _require((n,), (torch.float64,), "niqe_block_stats reads fp64 MSCN planes (got {})")
+    if n.dim() != 3 or not n.is_contiguous():
+        raise ValueError(f"niqe_block_stats: expected dense (P, H, W) planes, got {tuple(n.shape)}")
+    P, H, W = n.shape
+    block = int(block)
+    nblk = (H // block) * (W // block) if block > 0 else 0
+    if out is None:
+        out = torch.empty(P, nblk, 5, 6, dtype=torch.float64, device=n.device)
+    elif out.dtype != torch.float64 or out.numel() != P * nblk * 30 or not out.is_contiguous():
+        raise ValueError(f"niqe_block_stats: out must be a dense fp64 tensor of {P} x {nblk} x 5 x 6 elements")
+    _call(lib.dcpt_niqe_block_stats_fwd, (n, out), (P, H, W, block), n.device)
+    return out
+
+
+def niqe_stats(img, crop_border=0, parts=False):
+    """The pixel work of NIQE for a (B, C, H, W) fp32 device tensor in [0, 1]: returns the sums (B * C, nblk, 2, 5, 6) fp64 on the device
+    -- scale 1 (96 x 96 blocks) and scale 2 (48 x 48 blocks of the x0.5 image) -- for basicsr.metrics.niqe.niqe_from_stats.  Five
+    launches (MSCN, block sums, the two resize passes straight from the fp32 image, MSCN, block sums), nothing synchronises.  ``parts``:
+    also {"mscn1", "img2", "mscn2"}, the intermediates (img2: the resize output in [0, 1])."""
+    if not torch.is_tensor(img):
+        raise _lib.DcptHipError(f"niqe_stats takes a device tensor (got {type(img).__name__}); host arrays go to basicsr.metrics.calculate_niqe")
+    _require_gpu(img)
+    if img.dim() != 4:
+        raise ValueError(f"niqe_stats: expected a (B, C, H, W) tensor, got {tuple(img.shape)}")
+    img = _contig(img.detach())
+    B, Cc, H, W = img.shape
+    P, crop = B * Cc, int(crop_border)
+    if crop < 0 or (H - 2 * crop) // 96 < 1 or (W - 2 * crop) // 96 < 1:
+        raise ValueError(f"niqe_stats: no whole 96 x 96 block in a {H} x {W} plane with crop_border {crop}")
+    dev = img.device
+    planes = img.view(P, H, W)
+    n1 = niqe_mscn(planes, crop, 1)
+    s1 = niqe_block_stats(n1, 96)
+    Hc, Wc = n1.shape[1:]
+    # the x0.5 image straight from the fp32 input: the cropped region by offset and strides, the 8-bit rounding at the load
+    src = planes[:, crop:, crop:]
+    x2 = torch.empty(P, Hc // 2, Wc // 2, dtype=torch.float64, device=dev)
+    _imresize_planes(src, P, Hc, Wc, H * W, W, 0.5, True, x2, IMRESIZE_Y_F64 | IMRESIZE_QUANT8)
+    n2 = niqe_mscn(x2, 0, 2, out=None if parts else n1.view(-1)[: x2.numel()].view(x2.shape))
+    s2 = niqe_block_stats(n2, 48)
+    stats = torch.stack((s1, s2), dim=2)
+    return (stats, {"mscn1": n1, "img2": x2, "mscn2": n2}) if parts else stats

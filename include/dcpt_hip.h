@@ -878,6 +878,51 @@ int dcpt_ldl_weight_bwd(const float* gt, const float* out, const float* gw, floa
 #define DCPT_JPEG_UINT8_IO 2     /* 8-bit input and output grids */
 int dcpt_diffjpeg_fwd(const float* x, const float* quality, float* y, int B, int C, int H, int W, int flags, dcpt_stream_t stream);
 
+/* ---- MATLAB-bicubic resize and the pixel work of NIQE, on the device ------------------------------------
+ * Three entry points in fp64 from the pixel load to the store.  No atomics, every sum in a fixed order (two runs give the same bits), a
+ * plane's result does not depend on the planes around it, no host synchronisation, no global state; arguments are checked before the
+ * first launch.
+ *
+ * dcpt_imresize_fwd replaces basicsr/utils/matlab_functions.py:89-186 (imresize) for tables the host built as
+ * calculate_weights_indices does (:17-86): the H pass (:148-155), then the W pass (:172-177), the symmetric padded copies (:135-146,
+ * :159-170) being addressing only (index -1 -> 0, -2 -> 1, n -> n - 1, ...; an index that would still leave the plane is clamped to it).
+ *   x          planes [P][H][W], fp32 or fp64 (DCPT_IMRESIZE_X_F64); plane p starts at x + p * plane_stride elements and its rows are
+ *              row_stride elements apart (dense: H * W and W), so a crop is a pointer offset.  With DCPT_IMRESIZE_QUANT8 (fp32 only) a
+ *              tap reads rint(255 x) / 255: the 8-bit image / 255.0 of niqe.py:144.
+ *   y          dense [P][Ho][Wo], fp32 or fp64 (DCPT_IMRESIZE_Y_F64); the one rounding is at this store
+ *   first_h/w  int32 [Ho] / [Wo] on the device: the first tap of an output row / column; may be negative or reach past the end
+ *   w_h / w_w  fp64 [Ho][Kh] / [Wo][Kw] on the device: the weights; zero-weight taps are harmless
+ *   ws         dcpt_imresize_ws_bytes: the fp64 intermediate [P][Ho][W] (0 for arguments the entry point refuses; needs no device)
+ * Errors: null pointers, non-positive sizes, tap counts outside 1..4096, a plane above 2^30 pixels, above 2^36 elements, unknown flags,
+ * QUANT8 on an fp64 source, strides under the plane's extent, a workspace that is too small.
+ *
+ * dcpt_niqe_mscn_fwd replaces niqe.py:121-129 (mu, sigma and the normalised image of one scale) with the crop to whole blocks (:114-117):
+ *   scale 1    x fp32 [P][H][W] in [0, 1]; the region starts at (crop_border, crop_border) and is Hc x Wc with
+ *              Hc = (H - 2 crop_border) / 96 * 96, Wc likewise; a pixel is rint(255 x), half to even (niqe.py:218)
+ *   scale 2    x fp64 [P][H][W], the resize output of niqe.py:144, read as 255 x (:145); H and W multiples of 48, crop_border 0
+ *   n          fp64 [P][Hc][Wc]
+ * The 7 x 7 window exp(-(i^2 + j^2) / (2 (7/6)^2)), normalised, is computed, the borders replicate the region's edge pixel
+ * (mode="nearest"), and the moments are taken around the window's centre pixel p: mu = p + sum w (x - p), var = sum w (x - p)^2 -
+ * (mu - p)^2, n = (p - mu) / (sqrt|var| + 1): a constant window gives n = 0 exactly.
+ *
+ * dcpt_niqe_block_stats_fwd replaces the sums of niqe.py:24-37 (estimate_aggd_param) over the five maps of :56-66 (compute_feature) for
+ * every block of :132-139:
+ *   n          fp64 [P][H][W], H and W multiples of block (96 at scale 1, 48 at scale 2)
+ *   stats      fp64 [P][nblk][5][6], blocks column-major (index idx_w * (H / block) + idx_h); maps: the block, then its product with
+ *              np.roll(block, s, axis=(0, 1)) for s = [0, 1], [1, 0], [1, 1], [1, -1], the roll wrapping inside the block; values:
+ *              count of x < 0, sum of x^2 over them, count of x > 0, sum of x^2 over them, sum |x| and sum x^2 over all
+ * Errors of both: null pointers, bad shape, a scale other than 1 / 2 or a block other than 96 / 48, planes without whole blocks, above
+ * 65535 planes, a plane above 2^30 pixels. */
+#define DCPT_IMRESIZE_X_F64 1    /* x is fp64 (else fp32) */
+#define DCPT_IMRESIZE_Y_F64 2    /* y is fp64 (else fp32) */
+#define DCPT_IMRESIZE_QUANT8 4   /* a tap reads rint(255 x) / 255 */
+size_t dcpt_imresize_ws_bytes(int P, int H, int W, int Ho, int Wo, int Kh, int Kw);
+int dcpt_imresize_fwd(const void* x, void* y, const int* first_h, const double* w_h, const int* first_w, const double* w_w, void* ws,
+                      size_t ws_bytes, int P, int H, int W, int Ho, int Wo, int Kh, int Kw, int64_t plane_stride, int64_t row_stride,
+                      int flags, dcpt_stream_t stream);
+int dcpt_niqe_mscn_fwd(const void* x, double* n, int P, int H, int W, int crop_border, int scale, dcpt_stream_t stream);
+int dcpt_niqe_block_stats_fwd(const double* n, double* stats, int P, int H, int W, int block, dcpt_stream_t stream);
+
 /* ---- optional launch profiling (bench.py) -------------------------------------------------------
  * While enabled, MFMA GEMM launches are bracketed by HIP events on their own stream: every launch for on = 1, every
  * on-th launch for on > 1 (sampling keeps the perturbation of a timed region small: an event pair costs ~3 us of queue time).
