@@ -4,7 +4,8 @@
 // x1 = the top 8 of the exact remainder x - x0, x2 = the exact rest: 24 bits in all).  A product a*b is then nine piece products, each of
 // them EXACT in fp32 (8 x 8 significand bits); the kernel keeps the six with i + j <= 2,
 //     a*b ~= a0 b0 + a0 b1 + a1 b0 + a1 b1 + a0 b2 + a2 b0,
-// the dropped ones (a1 b2, a2 b1, a2 b2) are <= 2^-24 |a b| each, i.e. below the rounding error an fp32 FMA makes on the full product.
+// the dropped ones (a1 b2, a2 b1 < 2^-22 |a b| each, typically 2^-25; a2 b2 < 2^-30 |a b|) are of the size of the rounding error an fp32 FMA
+// makes on the full product but carry its sign: below the fp32 kernel's accumulated error only in sums of some tens of products (X3_TN_MIN_ROWS).
 // Sums are accumulated in fp32 by v_mfma_f32_32x32x16_bf16.  The matrix pipe runs bf16 at 16x the fp32-MFMA rate, so six bf16 MFMAs
 // replace eight fp32 MFMAs of a k = 16 block at 3/8 of their issue time -- an fp32-CLASS GEMM (not bit-identical to the fp32-MFMA path:
 // the summation order and the dropped 2^-24 terms differ; tests/test_gpu_x3.py measures both paths against fp64).  This is a SEPARATELY
@@ -947,9 +948,16 @@ int launch_gemm_nt_x3(const GemmNT& pin, int aload, int epi, hipStream_t s) {
 // shapes the TN kernel takes: full 256 x 256 output tiles, plain operands, dense enough rows
 bool gemm_tn_x3_shape_ok(int N, int K) { return g_x3_scratch != nullptr && N % 256 == 0 && K % 256 == 0; }
 
+// The shortest reduction the mode takes.  The three dropped piece products are up to 2^-22 of a product and carry ITS sign, so a sum of
+// L products keeps a relative error of ~5e-8 whatever L is, while the fp32-MFMA kernel's fmaf chain has ~1.8e-8 sqrt(L): the mode is
+// fp32-class only from L ~ 20-30 on.  Measured against float64 on a weight gradient of ONE pixel (one product per element): rms 5.7e-8 /
+// max 1.3e-7 against 2.5e-8 / 3.0e-8 of the fp32 kernel (tests/test_gpu_x3_ops.py); from 64 rows on its error is 0.83 of the fp32
+// kernel's.  An NT launch has K >= 64 by its k-tiling; the weight gradient of a map of fewer pixels stays on the fp32 kernel.
+constexpr int64_t X3_TN_MIN_ROWS = 64;
+
 // split plan for such a shape: one block per CU (tiles x splits ~ 256), chunks of >= 256 pixels, multiples of 32
 bool gemm_tn_x3_plan(int64_t M, int N, int K, int* splits, int64_t* rows_per_split) {
-    if (!gemm_tn_x3_shape_ok(N, K)) return false;
+    if (!gemm_tn_x3_shape_ok(N, K) || M < X3_TN_MIN_ROWS) return false;
     const int64_t tiles = (int64_t)(N / 256) * (K / 256);
     int64_t want = 256 / tiles;
     const int64_t max_by_rows = cdiv64(M, 256);
@@ -963,7 +971,7 @@ bool gemm_tn_x3_plan(int64_t M, int N, int K, int* splits, int64_t* rows_per_spl
 }
 
 bool gemm_tn_x3_ok(const GemmTN& p, int xload, int yload) {
-    if (!gemm_tn_x3_shape_ok(p.N, p.K) || xload != A_PLAIN || yload != A_PLAIN) return false;
+    if (!gemm_tn_x3_shape_ok(p.N, p.K) || p.M < X3_TN_MIN_ROWS || xload != A_PLAIN || yload != A_PLAIN) return false;
     if ((p.nb1 > 1) || (p.nb2 > 1) || p.ldx % 4 != 0 || p.ldy % 4 != 0 || p.rows_per_split % 16 != 0) return false;
     const int64_t blocks = (int64_t)(p.N / 256) * (p.K / 256) * p.splits;
     return blocks >= (g_x3_min_tiles > 1 ? 128 : 1);

@@ -109,7 +109,8 @@ int dcpt_nafblock_bwd(const dcpt_nafblock_params* p, const dcpt_nafblock_grads* 
 /* ---- Opt-in GEMM precision mode "bf16x3" (gemm_x3.hip): while a scratch buffer is registered, the wide fp32 NT GEMMs of every entry point
  * (plain or per-image-scaled A operand, N % 256 == 0, K % 16 == 0, >= 192 tiles of 256 x 256) run on the bf16 matrix pipe with both operands
  * split into three bfloat16 pieces (x = x0 + x1 + x2 exactly), six piece products per element pair, fp32 accumulation: fp32-CLASS results
- * (dropped terms <= 2^-24 relative; not bit-identical to the default fp32-MFMA kernels).  PROCESS-WIDE state: the scratch (>= 6 bytes per
+ * (not bit-identical to the default fp32-MFMA kernels; the dropped terms are up to 2^-22 of a product, below the fp32 kernel's own error only
+ * in a sum of some tens of products, so a weight gradient over fewer than 64 pixels keeps the fp32 kernel).  PROCESS-WIDE state: the scratch (>= 6 bytes per
  * element of the largest A operand + weights) is shared by all launches, which must therefore all be on ONE stream while the mode is on.
  * scratch == NULL switches the mode off (the default).  The reference computes in fp32; this mode is reported separately. */
 /* min_tiles: launches with fewer 256 x 256 tiles keep the fp32-MFMA kernels (<= 0: the default, 192 -- most of the 256 CUs busy). */

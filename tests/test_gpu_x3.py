@@ -3,8 +3,11 @@ pipe with both operands split into three bfloat16 pieces (x = x0 + x1 + x2 exact
 NOT the product default and never the headline; what is established here is that it is fp32-CLASS:
 
 * a level-3 GEMM against an fp64 product: its error is not larger than the exact-fp32-MFMA kernel's;
-* the fp32 parity bar unchanged: NAFBlock / NAFNet golden vectors of the real reference at the fp32 tolerances, with the mode FORCED onto
-  every eligible launch (min_tiles = 1) -- tools/x3_e2e.sh runs the whole fp32 parity suite this way (52 tests);
+* the fp32 parity bar unchanged: the full NAFNet-64 golden vectors of the real reference at the fp32 tolerances, with the mode FORCED onto
+  every eligible launch (min_tiles = 1) -- tools/x3_e2e.sh runs the whole fp32 parity suite this way (52 tests).  The C = 64 block golden
+  and the tiny-net golden run beside it are NOT evidence for the mode: no GEMM of the first and only two forward GEMMs of the second's
+  middle block (on 8 pixels) have the N % 256 == 0 the mode needs, which the launch trace asserts.  What each epilogue, operand form and ragged extent of the
+  kernels computes is held to float64 in tests/test_gpu_x3_ops.py;
 * NAFNet-64 [1,1,1,28] on a 256 x 256 image against the oracle evaluated in FLOAT64: output and input-gradient errors of the forced
   bf16x3 run vs the fp32-MFMA run;
 * at the bench size (B = 32, where the launcher selects the mode by itself) one training step's loss and gradients against the fp32 step.
@@ -72,11 +75,25 @@ def test_gemm_error_vs_fp64_not_above_fp32_mfma(dev, x3, shape):
 def test_nafblock_and_tiny_net_goldens_at_fp32_tolerance_with_the_mode_forced(dev, x3, golden_dir):
     """the reference's own vectors (tests/golden/nafblock_c64.npz, nafnet_tiny.npz) at the tolerances of tests/test_gpu_parity.py"""
     import tests.test_gpu_parity as P
+    from kernel_trace import kernel_trace
 
     x3(min_tiles=1)
-    P.test_nafblock_golden(torch.device("cuda:0"), golden_dir, 64)
-    P.test_nafnet_tiny_golden(torch.device("cuda:0"), golden_dir)
-    P.test_nafnet_full_golden(torch.device("cuda:0"), golden_dir)
+    with kernel_trace() as blk:
+        P.test_nafblock_golden(torch.device("cuda:0"), golden_dir, 64)
+    with kernel_trace() as tiny:
+        P.test_nafnet_tiny_golden(torch.device("cuda:0"), golden_dir)
+    with kernel_trace() as full:
+        P.test_nafnet_full_golden(torch.device("cuda:0"), golden_dir)
+    for name, tr in (("C = 64 block", blk), ("tiny net", tiny), ("full net", full)):
+        print(f"{name}: nt_f32.x3 {tr['nt_f32.x3']} launches, tn_f32.x3 {tr['tn_f32.x3']}; fp32 families {tr.families('nt_f32.1')} {tr.families('tn_f32.')}")
+    # a launch is eligible only with N % 256 == 0 (gemm_nt_x3_ok, gemm_tn_x3_shape_ok).  None at C = 64 (N <= 128): that run is a golden
+    # check of the fp32 kernels with the switch on and says nothing about the mode.  In the tiny net (width 8) only the middle block, C = 128,
+    # has such launches: conv1 (E_BIAS) and conv4 (E_BIASGATE) with N = 2C = 256 on its 8 pixels, in each of the test's two forward passes;
+    # every other GEMM of the net, every backward GEMM (N = C, or the LayerNorm-backward epilogue) and every weight gradient (K = 128)
+    # stays fp32
+    blk.assert_not_ran("nt_f32.x3", "tn_f32.x3")
+    assert (tiny["nt_f32.x3"], tiny["tn_f32.x3"]) == (4, 0), tiny.counts
+    full.assert_ran("nt_f32.x3", "tn_f32.x3")
 
 
 def test_nafnet64_against_the_fp64_oracle(dev, x3):
