@@ -1,5 +1,5 @@
 """Dataset plumbing for ``test.py`` (reference basicsr/data/__init__.py:33-118).  The reference's IO stack
-(cv2, lmdb, the demosaic and inpainting degradations) is out of scope; what the hot path needs from it
+(cv2, lmdb) is out of scope; what the hot path needs from it
 is a dict with ``lq``/``gt`` float32 CHW tensors in [0,1] (+ ``dataset_idx``).  A minimal PIL reader covers
 paired folders; when a configured root does not exist (the YAMLs point at /mnt/nasv3/...), a seeded synthetic
 pair stands in so the CLI still runs end to end."""
@@ -238,7 +238,216 @@ class PairedImageJPEGCARDataset(tdata.Dataset):
         return _labelled(sample, self.opt)
 
 
-DATASET_REGISTRY._obj_map["PairedImageDehazeDataset"] = PairedImageDataset
+DEMOSAIC_METHODS = ("malvar", "bilinear")   # the int a ``demosaic_backend: device`` sample carries in ``mosaic`` is the index
+
+
+def _round_to_grid(s, unit):
+    """rint(clamp(S / unit, 0, 255)) in integers, half to even"""
+    q, r = np.divmod(s, unit)
+    q = q + ((2 * r > unit) | ((2 * r == unit) & (q % 2 == 1)))
+    return np.clip(q, 0, 255)
+
+
+def demosaic_host(gt, method="malvar"):
+    """``dcpt_amd.functional.demosaic(gt[None], method, uint8_io=True)[0]`` on the host, in numpy integers (include/dcpt_hip.h
+    dcpt_demosaic_fwd states the arithmetic): the RGGB mosaic of the 8-bit image ``rint(clamp(gt, 0, 1) * 255)``, the Malvar (reflect
+    padding, units of 1/16) or bilinear (circular padding, units of 1/4) tap sums, ``rint(clamp(S / unit, 0, 255)) / 255`` half to even.
+    Integer-exact, so it equals the kernel's result bit for bit.  gt: (3, H, W) float32 with H, W >= 3; returns (3, H, W) float32."""
+    if method not in DEMOSAIC_METHODS:
+        raise ValueError(f"demosaic_method must be one of {DEMOSAIC_METHODS}, got {method!r}")
+    _, h, w = gt.shape
+    if h < 3 or w < 3:
+        raise ValueError(f"the demosaic needs an image of at least 3 x 3, got ({h}, {w})")
+    v = torch.round(gt.float().clamp(0, 1) * 255).numpy().astype(np.int64)
+    rows, cols = np.indices((h, w)) % 2
+    site = np.where(rows != cols, 1, np.where(rows == 0, 0, 2))   # the colour of each RGGB site
+    cfa = np.take_along_axis(v, site[None], 0)[0]
+    out = np.empty((3, h, w), dtype=np.int64)
+    if method == "malvar":
+        p = np.pad(cfa, 2, mode="reflect")
+
+        def at(dy, dx):
+            return p[2 + dy:2 + dy + h, 2 + dx:2 + dx + w]
+
+        c = at(0, 0)
+        h1, v1 = at(0, -1) + at(0, 1), at(-1, 0) + at(1, 0)
+        h2, v2 = at(0, -2) + at(0, 2), at(-2, 0) + at(2, 0)
+        d = at(-1, -1) + at(-1, 1) + at(1, -1) + at(1, 1)
+        g = 8 * c + 4 * (h1 + v1) - 2 * (h2 + v2)
+        cross = 12 * c + 4 * d - 3 * (h2 + v2)
+        hz = 10 * c + 8 * h1 - 2 * h2 + v2 - 2 * d
+        vt = 10 * c + 8 * v1 - 2 * v2 + h2 - 2 * d
+        out[1] = np.where(site == 1, 16 * c, g)
+        out[0] = np.where(site == 0, 16 * c, np.where(site == 2, cross, np.where(rows == 0, hz, vt)))
+        out[2] = np.where(site == 2, 16 * c, np.where(site == 0, cross, np.where(rows == 0, vt, hz)))
+        unit = 16
+    else:
+        sparse = np.stack([np.where(site == k, cfa, 0) for k in range(3)])
+        p = np.pad(sparse, ((0, 0), (1, 1), (1, 1)), mode="wrap")
+        out[:] = 0
+        for dy in (-1, 0, 1):
+            for dx in (-1, 0, 1):
+                win = p[:, 1 + dy:1 + dy + h, 1 + dx:1 + dx + w]
+                out[0] += (2 - abs(dy)) * (2 - abs(dx)) * win[0]
+                out[2] += (2 - abs(dy)) * (2 - abs(dx)) * win[2]
+                out[1] += (4 if dy == dx == 0 else (1 if dy == 0 or dx == 0 else 0)) * win[1]
+        unit = 4
+    return torch.from_numpy(_round_to_grid(out, unit).astype(np.float32) / np.float32(255))
+
+
+def line_mask_host(lines, n_lines, thick, h, w):
+    """the (H, W) boolean stroke mask of dcpt_inpaint_lines_fwd in numpy int64: a pixel within ``thick / 2`` of one of the first
+    ``n_lines`` segments ``x1, y1, x2, y2``"""
+    py, px = np.indices((h, w), dtype=np.int64)
+    mask = np.zeros((h, w), dtype=bool)
+    t2 = int(thick) * int(thick)
+    for x1, y1, x2, y2 in [[int(v) for v in row] for row in lines[:n_lines]]:
+        qx, qy, dx, dy = px - x1, py - y1, x2 - x1, y2 - y1
+        a, seg = qx * dx + qy * dy, dx * dx + dy * dy
+        head = 4 * (qx * qx + qy * qy) <= t2
+        tail = 4 * ((qx - dx) ** 2 + (qy - dy) ** 2) <= t2
+        side = 4 * (qx * dy - qy * dx) ** 2 <= t2 * seg
+        mask |= np.where(a <= 0, head, np.where(a >= seg, tail, side))
+    return mask
+
+
+class _GTFolderDataset(tdata.Dataset):
+    """a GT folder read with PIL; the train phase crops at scale 1 (``gt_size``, default 128) and augments, other phases apply the optional
+    ``center_crop``"""
+
+    def __init__(self, opt):
+        super().__init__()
+        self.opt = opt
+        self.gt_root = opt["dataroot_gt"]
+        self.gt_size = opt.get("gt_size", 128)
+        self.names = sorted(f for f in scandir(self.gt_root) if f.endswith(_IMG_EXT))
+
+    def __len__(self):
+        return len(self.names)
+
+    def _gt(self, index):
+        path = osp.join(self.gt_root, self.names[index])
+        gt = _read_rgb(path)
+        if self.opt.get("phase") == "train":
+            _, gt = paired_random_crop_augment(gt, gt, {**self.opt, "gt_size": self.gt_size, "scale": 1})
+        elif self.opt.get("center_crop") is not None:
+            gt = _center_crop(gt, self.opt["center_crop"])
+        return gt.contiguous(), path
+
+
+def _backend(opt, key):
+    backend = opt.get(key, "host")
+    if backend not in ("host", "device"):
+        raise ValueError(f"{key} must be 'host' or 'device', got {backend!r}")
+    return backend
+
+
+@DATASET_REGISTRY.register()
+class PairedImageMosaicDataset(_GTFolderDataset):
+    """GT folder + on-the-fly Bayer mosaic and demosaic (reference basicsr/data/paired_image_dataset.py:732-870, folder mode, PIL reader):
+    ``lq`` is the RGGB mosaic of the 8-bit ``gt`` put back to three channels by a linear demosaic.  Options: ``dataroot_gt``, ``gt_size``
+    (default 128), ``use_hflip``, ``use_rot``, ``center_crop``, ``demosaic_method: malvar | bilinear``, ``demosaic_backend``.
+
+    The reference demosaics with cv2's edge-aware ``COLOR_BAYER_BG2BGR_EA``; cv2 is not a dependency of this package.  Malvar-He-Cutler
+    (``dm_matlab``) is the form the reference's own ``basicsr/utils/mosaic_util.py`` offers, with ``dm`` (bilinear) beside it; the two have
+    NOT been compared with cv2's result here.  Odd image sizes are supported, an extension: the reference's ``mosaic_CFA_Bayer`` refuses them.
+
+    ``demosaic_backend: host`` (default): ``lq`` is computed in the worker in numpy integers (``demosaic_host``) and equals the device
+    result bit for bit.  ``demosaic_backend: device``: the sample carries ``gt``, ``mosaic`` (an int32 scalar: 0 malvar, 1 bilinear) and
+    the paths, and no ``lq``; the model's ``feed_data`` makes ``lq`` with ``dcpt_amd.functional.demosaic(gt, method, uint8_io=True)``."""
+
+    def __init__(self, opt):
+        super().__init__(opt)
+        self.backend = _backend(opt, "demosaic_backend")
+        self.method = opt.get("demosaic_method", "malvar")
+        if self.method not in DEMOSAIC_METHODS:
+            raise ValueError(f"demosaic_method must be one of {DEMOSAIC_METHODS}, got {self.method!r}")
+
+    def __getitem__(self, index):
+        gt, path = self._gt(index)
+        sample = {"gt": gt, "lq_path": path, "gt_path": path}
+        if self.backend == "device":
+            sample["mosaic"] = torch.tensor(DEMOSAIC_METHODS.index(self.method), dtype=torch.int32)
+        else:
+            sample["lq"] = demosaic_host(gt, self.method)
+        return _labelled(sample, self.opt)
+
+
+@DATASET_REGISTRY.register()
+class PairedImageInpaintingDataset(_GTFolderDataset):
+    """GT folder + on-the-fly line masks (reference basicsr/data/paired_image_dataset.py:873-1029, folder mode, PIL reader).  After the crop
+    and the augmentation the strokes are drawn from Python's ``random`` in the reference's order (:981-1019): ``randint(5, 10)`` strokes,
+    ``randint(5, 10)`` thick, ``choice(['white', 'black'])``, then per stroke ``randint(0, w), randint(0, h), randint(0, w),
+    randint(0, h)``.  A masked pixel of ``lq`` is 1 (white) or 0 in every channel, every other pixel ``clamp(gt, 0, 1)``.
+
+    The reference rasterises with ``cv2.polylines(mask, [pts], 0, (1, 1, 1), thick)``, which draws a quad plus round caps; the rule here
+    -- a pixel within ``thick / 2`` of the segment, in exact integers (include/dcpt_hip.h dcpt_inpaint_lines_fwd) -- is the ideal shape of
+    that and may differ from cv2 at boundary pixels.  UNVERIFIED: cv2 is not a dependency of this package.
+
+    ``inpaint_backend: host`` (default): a numpy mask by that rule in the worker (``line_mask_host``).  ``inpaint_backend: device``: the
+    sample carries ``gt``, ``inpaint_lines`` (int32 (10, 4), unused rows zero), ``inpaint_meta`` (int32 (3,): n_lines, thick, white) and
+    the paths, and no ``lq``; the model's ``feed_data`` makes ``lq`` with ``dcpt_amd.functional.inpaint_lines``.
+
+    ``stroke_seed: k`` (an extension; default none, the reference's behaviour): image ``index`` draws its strokes from a
+    ``random.Random(k + index)`` of its own instead of the process-wide generator, so a validation set shows the same masks on every
+    visit and two sets over one folder show the same masks."""
+
+    def __init__(self, opt):
+        super().__init__(opt)
+        self.backend = _backend(opt, "inpaint_backend")
+        self.stroke_seed = opt.get("stroke_seed")
+
+    def __getitem__(self, index):
+        import random
+
+        gt, path = self._gt(index)
+        _, h, w = gt.shape
+        if self.stroke_seed is not None:
+            random = random.Random(self.stroke_seed + index)   # (the same calls in the same order, on a generator of the image's own)
+        l_num, l_thick = random.randint(5, 10), random.randint(5, 10)
+        white = random.choice(["white", "black"]) == "white"
+        lines = np.zeros((10, 4), dtype=np.int32)
+        for k in range(l_num):
+            lines[k] = (random.randint(0, w), random.randint(0, h), random.randint(0, w), random.randint(0, h))
+        sample = {"gt": gt, "lq_path": path, "gt_path": path}
+        if self.backend == "device":
+            sample["inpaint_lines"] = torch.from_numpy(lines)
+            sample["inpaint_meta"] = torch.tensor([l_num, l_thick, int(white)], dtype=torch.int32)
+        else:
+            lq = gt.clamp(0, 1)
+            lq[:, torch.from_numpy(line_mask_host(lines, l_num, l_thick, h, w))] = 1.0 if white else 0.0
+            sample["lq"] = lq
+        return _labelled(sample, self.opt)
+
+
+@DATASET_REGISTRY.register()
+class PairedImageDehazeDataset(tdata.Dataset):
+    """Hazy folder + GT folder with several hazy images per GT (reference basicsr/data/paired_image_dataset.py:583-729, folder mode, PIL
+    reader): the LQ folder is listed, and the GT of ``<lq_name>`` is ``dataroot_gt/<lq_name.split("_")[0] + suffix>`` (``suffix`` default
+    ``.jpg``; SOTS: ``0001_0.8_0.2.jpg`` -> ``0001.png`` with ``suffix: .png``).  Train phase = paired random crop at scale 1 + flips /
+    rotation, other phases = optional ``center_crop``.  One departure from the reference: ``lq_path`` is the real LQ path (the reference
+    returns the GT path under both keys, so the saved validation images of one GT overwrite each other)."""
+
+    def __init__(self, opt):
+        super().__init__()
+        self.opt = opt
+        self.gt_root, self.lq_root = opt["dataroot_gt"], opt["dataroot_lq"]
+        self.suffix = opt.get("suffix", ".jpg")
+        self.names = sorted(f for f in scandir(self.lq_root) if f.endswith(_IMG_EXT))
+
+    def __len__(self):
+        return len(self.names)
+
+    def __getitem__(self, index):
+        name = self.names[index]
+        lq_path = osp.join(self.lq_root, name)
+        gt_path = osp.join(self.gt_root, osp.basename(name).split("_")[0] + self.suffix)
+        lq, gt = _read_rgb(lq_path), _read_rgb(gt_path)
+        if self.opt.get("phase") == "train":
+            lq, gt = paired_random_crop_augment(lq, gt, {**self.opt, "scale": 1})
+        elif self.opt.get("center_crop") is not None:
+            lq, gt = _center_crop(lq, self.opt["center_crop"]), _center_crop(gt, self.opt["center_crop"])
+        return _labelled({"lq": lq, "gt": gt, "lq_path": lq_path, "gt_path": gt_path}, self.opt)
 
 
 def build_dataset(dataset_opt):

@@ -35,10 +35,22 @@ class BaseModel:
 
     def _lq_on_device(self, data):
         """the degraded batch of ``feed_data``: ``data["lq"]`` moved to the device, as ever; a batch of a ``jpeg_backend: device`` set
-        (PairedImageJPEGCARDataset: ``gt`` and ``jpeg_quality``, no ``lq``) gets it from the JPEG round trip of ``gt`` on the device"""
+        (PairedImageJPEGCARDataset: ``gt`` and ``jpeg_quality``, no ``lq``) gets it from the JPEG round trip of ``gt`` on the device, a
+        batch of a ``demosaic_backend: device`` set (PairedImageMosaicDataset: ``gt`` and ``mosaic``, the method's index) from the demosaic
+        kernel, and a batch of an ``inpaint_backend: device`` set (PairedImageInpaintingDataset: ``gt``, ``inpaint_lines``,
+        ``inpaint_meta``) from the line-mask kernel"""
         if "lq" not in data and "jpeg_quality" in data:
             gt = data["gt"].to(self.device, non_blocking=True)
             return DF.diffjpeg(gt, data["jpeg_quality"].to(self.device, non_blocking=True), uint8_io=True)
+        if "lq" not in data and "mosaic" in data:
+            gt = data["gt"].to(self.device, non_blocking=True)
+            methods = set(data["mosaic"].reshape(-1).tolist())   # (a host tensor: one data set, one method)
+            if len(methods) != 1 or not methods <= set(range(len(DF.DEMOSAIC_METHODS))):
+                raise ValueError(f"a batch carries one demosaic method, 0 (malvar) or 1 (bilinear); got {sorted(methods)}")
+            return DF.demosaic(gt, DF.DEMOSAIC_METHODS[methods.pop()], uint8_io=True)
+        if "lq" not in data and "inpaint_meta" in data:
+            gt = data["gt"].to(self.device, non_blocking=True)
+            return DF.inpaint_lines(gt, data["inpaint_lines"], data["inpaint_meta"])
         return data["lq"].to(self.device, non_blocking=True)
 
     def optimize_parameters(self, current_iter):

@@ -2,7 +2,7 @@
 """Secondary workloads of BASELINE.json (configs[2..4]) on ONE MI355X -- evidence for DESIGN.md, not the driver's
 contract (that is bench.py).  Prints one JSON line per workload.
 
-    python bench_extra.py --workload dcpt|dcpt_swinir|restormer|promptir|infer2k|naf|swinir|rcan|val_metrics|step_tail|tlsc|ssim_loss|ldl|jpeg|niqe [--dtype fp32|bf16|bf16_res32] [--steps K] [--warmup W]
+    python bench_extra.py --workload dcpt|dcpt_swinir|restormer|promptir|infer2k|naf|swinir|rcan|val_metrics|step_tail|tlsc|ssim_loss|ldl|jpeg|niqe|degrade [--dtype fp32|bf16|bf16_res32] [--steps K] [--warmup W]
 
 ``--dtype bf16`` (dcpt, naf, infer2k, restormer, promptir; rcan: the inference line only, next to fp32; swinir: the restoration form's inference, next to fp32): every feature map of the encoder in bf16 storage with fp32 accumulation (act_dtype="bf16";
 dcpt: the classifier head too unless --head-dtype fp32); images, parameters and the optimizer stay fp32.  Its lines carry BOTH
@@ -828,6 +828,99 @@ def run_jpeg(dev, steps=20, warmup=3, B=32, S=256):
                      "all B images, best of 3")
 
 
+def run_degrade(dev, steps=20, warmup=3, B=16, S=256):
+    """The two on-the-fly degradations of a B x 3 x S x S batch (dcpt_amd/csrc/degrade.hip), each against a torch route on the device; two
+    result lines.  Demosaic (Malvar, fp32 path, the mosaic fused): ``dcpt_amd.functional.demosaic`` against the mask-multiply mosaic, a
+    reflect pad, one ``conv2d`` with the four 5 x 5 kernels and strided assignment by site.  Line mask: ``dcpt_amd.functional.inpaint_lines``
+    against the same int64 rule as broadcast tensor arithmetic over (B, 10, S, S).  The two routes of a pair alternate call by call in one
+    process; each call is bracketed by device events; median and minimum of the per-call times after the warm-up, each route's peak
+    memory above what is resident between calls."""
+    import statistics
+
+    import torch.nn.functional as F
+
+    from dcpt_amd import functional as DF
+
+    g = torch.Generator(device=dev).manual_seed(1234)
+    low = torch.rand((B, 3, S // 8, S // 8), generator=g, device=dev)
+    x = (F.interpolate(low, size=(S, S), mode="bilinear", align_corners=False) + 0.04 * torch.randn((B, 3, S, S), generator=g, device=dev)).clamp(0, 1)
+    rows, cols = torch.arange(S, device=dev).view(S, 1) % 2, torch.arange(S, device=dev).view(1, S) % 2
+    site = torch.stack([(rows == 0) & (cols == 0), rows != cols, (rows == 1) & (cols == 1)]).float()
+    k = torch.zeros((4, 1, 5, 5), device=dev)   # kgrb, krbg0, its transpose, krbbr, in units of 1/16
+    k[0, 0, 2, 2], k[1, 0, 2, 2], k[3, 0, 2, 2] = 8, 10, 12
+    for a in (1, 3):
+        k[0, 0, 2, a] = k[0, 0, a, 2] = 4
+        k[1, 0, 2, a] = 8
+        for b in (1, 3):
+            k[1, 0, a, b], k[3, 0, a, b] = -2, 4
+    for a in (0, 4):
+        k[0, 0, 2, a] = k[0, 0, a, 2] = k[1, 0, 2, a] = -2
+        k[1, 0, a, 2] = 1
+        k[3, 0, 2, a] = k[3, 0, a, 2] = -3
+    k[2] = k[1].transpose(1, 2)
+    k = k / 16
+
+    def torch_demosaic(img):
+        cfa = (img * site).sum(1, keepdim=True)
+        conv = F.conv2d(F.pad(cfa, (2, 2, 2, 2), mode="reflect"), k)
+        rgb = cfa.repeat(1, 3, 1, 1)
+        rgb[:, 1, 0::2, 0::2], rgb[:, 1, 1::2, 1::2] = conv[:, 0, 0::2, 0::2], conv[:, 0, 1::2, 1::2]
+        rgb[:, 0, 0::2, 1::2], rgb[:, 0, 1::2, 0::2], rgb[:, 0, 1::2, 1::2] = conv[:, 1, 0::2, 1::2], conv[:, 2, 1::2, 0::2], conv[:, 3, 1::2, 1::2]
+        rgb[:, 2, 0::2, 1::2], rgb[:, 2, 1::2, 0::2], rgb[:, 2, 0::2, 0::2] = conv[:, 2, 0::2, 1::2], conv[:, 1, 1::2, 0::2], conv[:, 3, 0::2, 0::2]
+        return rgb
+
+    lines = torch.randint(0, S + 1, (B, 10, 4), generator=g, device=dev, dtype=torch.int32)
+    meta = torch.stack([torch.randint(5, 11, (B,), generator=g, device=dev), torch.randint(5, 11, (B,), generator=g, device=dev),
+                        torch.arange(B, device=dev) % 2], dim=1).to(torch.int32)
+    py, px = torch.arange(S, device=dev).view(1, 1, S, 1), torch.arange(S, device=dev).view(1, 1, 1, S)
+
+    def torch_inpaint(img, ln, mt):
+        ln = ln.long()
+        x1, y1, x2, y2 = (ln[:, :, i].view(B, 10, 1, 1) for i in range(4))
+        qx, qy, dx, dy = px - x1, py - y1, x2 - x1, y2 - y1
+        a, seg = qx * dx + qy * dy, dx * dx + dy * dy
+        t2 = (mt[:, 1].long() ** 2).view(B, 1, 1, 1)
+        hit = torch.where(a <= 0, 4 * (qx * qx + qy * qy) <= t2,
+                          torch.where(a >= seg, 4 * ((qx - dx) ** 2 + (qy - dy) ** 2) <= t2, 4 * (qx * dy - qy * dx) ** 2 <= t2 * seg))
+        hit = hit & (torch.arange(10, device=dev).view(1, 10, 1, 1) < mt[:, 0].view(B, 1, 1, 1))
+        mask = hit.any(1, keepdim=True)
+        return torch.where(mask, mt[:, 2].float().view(B, 1, 1, 1), img.clamp(0, 1))
+
+    pairs = {"demosaic": {"kernel": lambda: DF.demosaic(x), "torch": lambda: torch_demosaic(x)},
+             "inpaint_lines": {"kernel": lambda: DF.inpaint_lines(x, lines, meta), "torch": lambda: torch_inpaint(x, lines, meta)}}
+    what = {"demosaic": f"Bayer mosaic + Malvar demosaic, {B} x 3 x {S} x {S}, fp32 path",
+            "inpaint_lines": f"line-mask inpainting degradation, {B} x 3 x {S} x {S}, 5-10 strokes 5-10 thick per image"}
+    out = []
+    for name, routes in pairs.items():
+        peaks, last, times = {}, {}, {n: [] for n in routes}
+        with torch.no_grad():
+            for i in range(warmup + steps):
+                for n, fn in routes.items():
+                    torch.cuda.synchronize(dev)
+                    base = torch.cuda.memory_allocated(dev)
+                    torch.cuda.reset_peak_memory_stats(dev)
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    last[n] = fn()
+                    e1.record()
+                    e1.synchronize()
+                    peaks[n] = max(peaks.get(n, 0), torch.cuda.max_memory_allocated(dev) - base)
+                    if i >= warmup:
+                        times[n].append(e0.elapsed_time(e1))
+        moved = 4 * x.numel() * (5 / 3 if name == "demosaic" else 2)   # demosaic reads 2 of 3 planes' lines (every other row of R and B)
+        out.append(dict(workload=what[name], kernel_ms_median=round(statistics.median(times["kernel"]), 4),
+                        kernel_ms_min=round(min(times["kernel"]), 4), torch_ms_median=round(statistics.median(times["torch"]), 4),
+                        torch_ms_min=round(min(times["torch"]), 4),
+                        ratio_median=round(statistics.median(times["torch"]) / statistics.median(times["kernel"]), 2),
+                        kernel_gb_per_s_at_min=round(moved / (min(times["kernel"]) * 1e-3) / 1e9, 1),
+                        kernel_peak_mb=round(peaks["kernel"] / 1e6, 1), torch_peak_mb=round(peaks["torch"] / 1e6, 1),
+                        max_abs_diff=float((last["kernel"] - last["torch"]).abs().max()), calls=steps, warmup=warmup,
+                        note="device events around each call (the op's host side included), the two routes alternating in one process; "
+                             "peak memory of a call above what is allocated between calls; kernel_gb_per_s_at_min counts the bytes the "
+                             "algorithm needs (one read of the lines touched, one write) over the fastest call"))
+    return out
+
+
 def run_niqe(dev, steps=20, warmup=3, H=1080, W=2048):
     """NIQE of one 1 x 3 x H x W image (a smooth random field plus fine noise, no flat block): the host ``calculate_niqe`` (numpy float64,
     one thread's wall time, best of 2) against ``calculate_niqe_device`` (the fused fp64 kernels of dcpt_amd/csrc/niqe.hip + the host
@@ -878,7 +971,7 @@ def run_niqe(dev, steps=20, warmup=3, H=1080, W=2048):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", required=True, choices=["dcpt", "dcpt_swinir", "restormer", "promptir", "infer2k", "naf", "swinir", "rcan", "val_metrics", "step_tail", "tlsc", "ssim_loss", "ldl", "jpeg", "niqe"])
+    ap.add_argument("--workload", required=True, choices=["dcpt", "dcpt_swinir", "restormer", "promptir", "infer2k", "naf", "swinir", "rcan", "val_metrics", "step_tail", "tlsc", "ssim_loss", "ldl", "jpeg", "niqe", "degrade"])
     ap.add_argument("--dtype", default="fp32", choices=["fp32", "bf16", "bf16_tail32", "bf16_edge32", "bf16_res32"])
     ap.add_argument("--head-dtype", default=None, choices=["fp32", "bf16"], help="dcpt: classifier-head activations (default: --dtype)")
     ap.add_argument("--restormer-save", default="balanced", choices=["auto", "lean", "balanced", "full"], help="what the Restormer halves keep for backward")
@@ -1076,6 +1169,10 @@ def main():
         res = run_jpeg(dev, max(args.steps, 20), max(args.warmup, 3), args.batch or 32, args.size or 256)
     elif args.workload == "niqe":
         res = run_niqe(dev, max(args.steps, 20), max(args.warmup, 3))
+    elif args.workload == "degrade":
+        lines = run_degrade(dev, max(args.steps, 20), max(args.warmup, 3), args.batch or 16, args.size or 256)
+        print(json.dumps(lines[0]), flush=True)
+        res = lines[1]
     elif args.workload == "tlsc":
         res = run_tlsc(dev, args.steps, args.warmup, tile=args.tile, streams=args.tile_streams)
     else:

@@ -504,3 +504,26 @@ extern "C" int dcpt_niqe_block_stats_fwd(const double* n, double* stats, int P, 
     DCPT_CHECK_ARG((int64_t)H * W <= ((int64_t)1 << 30), "niqe_block_stats_fwd: a plane above 2^30 pixels (H=%d W=%d)", H, W);
     return launch_niqe_block_stats_fwd(n, stats, P, H, W, block, (hipStream_t)stream);
 }
+
+// ---------------------------------------------------------------------------------------------
+// The demosaic and the line-mask inpainting degradation (degrade.hip)
+extern "C" int dcpt_demosaic_fwd(const float* x, float* y, int B, int C, int H, int W, int flags, dcpt_stream_t stream) {
+    DCPT_CHECK_ARG(x && y, "demosaic_fwd: null argument");
+    DCPT_CHECK_ARG(x != y, "demosaic_fwd: x and y must be different buffers (a pixel reads its neighbours)");
+    DCPT_CHECK_ARG(C == 1 || C == 3, "demosaic_fwd: C must be 1 or 3 (got %d)", C);
+    DCPT_CHECK_ARG(H >= 3 && W >= 3, "demosaic_fwd: H and W must be at least 3 (H=%d W=%d)", H, W);
+    DCPT_CHECK_ARG(B >= 1 && B <= 65535, "demosaic_fwd: B outside 1..65535 (got %d)", B);
+    DCPT_CHECK_ARG((int64_t)H * W <= ((int64_t)1 << 30), "demosaic_fwd: a plane above 2^30 pixels (H=%d W=%d)", H, W);
+    DCPT_CHECK_ARG((flags & ~(DCPT_DEMOSAIC_BILINEAR | DCPT_DEMOSAIC_UINT8_IO)) == 0, "demosaic_fwd: unknown flags 0x%x", flags);
+    return launch_demosaic_fwd(x, y, B, C, H, W, flags, (hipStream_t)stream);
+}
+
+extern "C" int dcpt_inpaint_lines_fwd(const float* x, const int* lines, const int* meta, float* y, int B, int C, int H, int W,
+                                      dcpt_stream_t stream) {
+    DCPT_CHECK_ARG(x && lines && meta && y, "inpaint_lines_fwd: null argument");
+    DCPT_CHECK_ARG(B > 0 && H > 0 && W > 0, "inpaint_lines_fwd: bad shape (B=%d C=%d H=%d W=%d)", B, C, H, W);
+    DCPT_CHECK_ARG(C == 1 || C == 3, "inpaint_lines_fwd: C must be 1 or 3 (got %d)", C);
+    DCPT_CHECK_ARG(H <= 16384 && W <= 16384, "inpaint_lines_fwd: H or W above 16384 (H=%d W=%d)", H, W);
+    DCPT_CHECK_ARG(B <= 65535, "inpaint_lines_fwd: B above 65535 (got %d)", B);
+    return launch_inpaint_lines_fwd(x, lines, meta, y, B, C, H, W, (hipStream_t)stream);
+}

@@ -218,3 +218,9 @@ int launch_imresize_fwd(const void* x, void* y, const int* first_h, const double
                         int quant, hipStream_t s);
 int launch_niqe_mscn_fwd(const void* x, double* n, int P, int H, int W, int crop, int Hc, int Wc, int scale, hipStream_t s);
 int launch_niqe_block_stats_fwd(const double* n, double* stats, int P, int H, int W, int block, hipStream_t s);
+
+// ---- degrade.hip ----------------------------------------------------------------------------
+// The demosaic (dcpt_demosaic_fwd: x [B][C][H][W] with C = 1 the CFA plane or C = 3 an RGB image mosaicked while loading, y [B][3][H][W]) and
+// the line-mask inpainting degradation (dcpt_inpaint_lines_fwd: lines int32 [B][10][4], meta int32 [B][3]); one launch each, no workspace.
+int launch_demosaic_fwd(const float* x, float* y, int B, int C, int H, int W, int flags, hipStream_t s);
+int launch_inpaint_lines_fwd(const float* x, const int* lines, const int* meta, float* y, int B, int C, int H, int W, hipStream_t s);

@@ -2957,6 +2957,70 @@ def diffjpeg(x, quality, differentiable=False, uint8_io=False):
 
 
 # ------------------------------------------------------------------------------------------------
+# The demosaic and the line-mask inpainting degradation (include/dcpt_hip.h dcpt_demosaic_fwd, dcpt_inpaint_lines_fwd): lq from gt in one
+# launch each, one read and one write of the batch.
+DEMOSAIC_BILINEAR, DEMOSAIC_UINT8_IO = 1, 2   # include/dcpt_hip.h DCPT_DEMOSAIC_*
+DEMOSAIC_METHODS = ("malvar", "bilinear")     # the index is the int a ``demosaic_backend: device`` sample carries in ``mosaic``
+INPAINT_MAX_LINES, INPAINT_MAX_THICK, INPAINT_MAX_COORD = 10, 64, 16384
+
+
+def demosaic(x, method="malvar", uint8_io=False):
+    """Bayer demosaic of a batch: ``x`` (B, 3, H, W) an RGB image, mosaicked (RGGB) inside the kernel, or (B, 1, H, W) the CFA plane
+    itself; fp32 device tensor (any strides: it is made contiguous NCHW), H and W at least 3, odd sizes allowed.  Returns (B, 3, H, W).
+    ``method="malvar"``: Malvar-He-Cutler with reflect padding, the reference's ``dm_matlab``; ``"bilinear"``: its ``dm`` (circular
+    padding).  ``uint8_io=False``: fp32 sums of the raw input, what the reference's functions return.  ``uint8_io=True``: the input is put
+    on the 8-bit grid, the taps are summed in integers and the output is ``rint(clamp(S / 16, 0, 255)) / 255``.  Forward only."""
+    if not torch.is_tensor(x):
+        raise _lib.DcptHipError(f"demosaic takes a device tensor (got {type(x).__name__})")
+    _require_gpu(x)
+    if x.dim() != 4 or x.shape[1] not in (1, 3) or x.shape[0] < 1 or x.shape[2] < 3 or x.shape[3] < 3:
+        raise ValueError(f"demosaic: expected a (B, 1 or 3, H >= 3, W >= 3) batch, got {tuple(x.shape)}")
+    if method not in DEMOSAIC_METHODS:
+        raise ValueError(f"demosaic: method must be one of {DEMOSAIC_METHODS}, got {method!r}")
+    _inference_only("demosaic", x, what="the demosaic")
+    B, C, H, W = x.shape
+    x = x.detach().contiguous()
+    y = torch.empty((B, 3, H, W), dtype=torch.float32, device=x.device)
+    flags = (DEMOSAIC_BILINEAR if method == "bilinear" else 0) | (DEMOSAIC_UINT8_IO if uint8_io else 0)
+    _call(_lib.load().dcpt_demosaic_fwd, (x, y), (B, C, H, W, flags), x.device)
+    return y
+
+
+def inpaint_lines(x, lines, meta):
+    """The inpainting degradation: ``x`` (B, 1 or 3, H, W) fp32 device tensor; ``lines`` (B, 10, 4) integers ``x1, y1, x2, y2`` per stroke;
+    ``meta`` (B, 3) integers ``n_lines, thick, white``.  A pixel within ``thick / 2`` of one of the first ``n_lines`` segments becomes 1
+    (``white``) or 0 in every channel, any other ``clamp(x, 0, 1)``.  ``lines`` / ``meta`` on the host are validated here (``n_lines`` in
+    0..10, ``thick`` in 1..64, coordinates in -16384..16384) and copied to the device; device tensors are not read back, and the kernel
+    clamps them to those ranges.  Returns a new tensor.  Forward only."""
+    if not torch.is_tensor(x):
+        raise _lib.DcptHipError(f"inpaint_lines takes a device tensor (got {type(x).__name__})")
+    _require_gpu(x)
+    if x.dim() != 4 or x.shape[1] not in (1, 3) or 0 in x.shape or x.shape[2] > INPAINT_MAX_COORD or x.shape[3] > INPAINT_MAX_COORD:
+        raise ValueError(f"inpaint_lines: expected a (B, 1 or 3, H, W) batch with H, W <= {INPAINT_MAX_COORD}, got {tuple(x.shape)}")
+    B, C, H, W = x.shape
+    if not torch.is_tensor(lines) or not torch.is_tensor(meta) or lines.is_floating_point() or meta.is_floating_point():
+        raise ValueError("inpaint_lines: lines and meta must be integer tensors")
+    if tuple(lines.shape) != (B, INPAINT_MAX_LINES, 4) or tuple(meta.shape) != (B, 3):
+        raise ValueError(f"inpaint_lines: expected lines ({B}, {INPAINT_MAX_LINES}, 4) and meta ({B}, 3), got {tuple(lines.shape)} and "
+                         f"{tuple(meta.shape)}")
+    if not meta.is_cuda:
+        if bool(((meta[:, 0] < 0) | (meta[:, 0] > INPAINT_MAX_LINES)).any()):
+            raise ValueError(f"inpaint_lines: n_lines must lie in 0..{INPAINT_MAX_LINES}, got {meta[:, 0].tolist()}")
+        if bool(((meta[:, 1] < 1) | (meta[:, 1] > INPAINT_MAX_THICK)).any()):
+            raise ValueError(f"inpaint_lines: thick must lie in 1..{INPAINT_MAX_THICK}, got {meta[:, 1].tolist()}")
+    if not lines.is_cuda and bool((lines.abs() > INPAINT_MAX_COORD).any()):
+        raise ValueError(f"inpaint_lines: an endpoint lies outside -{INPAINT_MAX_COORD}..{INPAINT_MAX_COORD}")
+    _inference_only("inpaint_lines", x, what="the inpainting degradation")
+    dev = x.device
+    lines = lines.to(device=dev, dtype=torch.int32).contiguous()
+    meta = meta.to(device=dev, dtype=torch.int32).contiguous()
+    x = x.detach().contiguous()
+    y = torch.empty_like(x)
+    _call(_lib.load().dcpt_inpaint_lines_fwd, (x, lines, meta, y), (B, C, H, W), dev)
+    return y
+
+
+# ------------------------------------------------------------------------------------------------
 # MATLAB-bicubic resize and the pixel work of NIQE (include/dcpt_hip.h dcpt_imresize_fwd, dcpt_niqe_mscn_fwd, dcpt_niqe_block_stats_fwd):
 # the reference's basicsr/utils/matlab_functions.py::imresize and the per-pixel part of basicsr/metrics/niqe.py in fp64.  Forward only.
 IMRESIZE_X_F64, IMRESIZE_Y_F64, IMRESIZE_QUANT8 = 1, 2, 4   # include/dcpt_hip.h DCPT_IMRESIZE_*

@@ -924,6 +924,46 @@ int dcpt_imresize_fwd(const void* x, void* y, const int* first_h, const double* 
 int dcpt_niqe_mscn_fwd(const void* x, double* n, int P, int H, int W, int crop_border, int scale, dcpt_stream_t stream);
 int dcpt_niqe_block_stats_fwd(const double* n, double* stats, int P, int H, int W, int block, dcpt_stream_t stream);
 
+/* ---- on-the-fly degradations: demosaic and line-mask inpainting, on the device ---------------------------
+ * dcpt_demosaic_fwd replaces basicsr/utils/mosaic_util.py dm_matlab (default) and dm (DCPT_DEMOSAIC_BILINEAR), with the Bayer mosaic of
+ * mosaic_CFA_Bayer fused in front of them when C == 3.
+ *   x   dense NCHW fp32 [B][C][H][W]: C == 3 an RGB image, of which the kernel reads the CFA sample only -- R at (even row, even column),
+ *       B at (odd, odd), G elsewhere (RGGB, masks_CFA_Bayer); C == 1 the CFA plane itself
+ *   y   dense NCHW fp32 [B][3][H][W]; a different buffer than x (a pixel reads its neighbours)
+ * Default, Malvar-He-Cutler on the CFA plane reflect-padded by 2 (-1 -> 1, -2 -> 2, H -> H - 2, H + 1 -> H - 3).  Taps in units of 1/16:
+ *   kgrb    G at an R or B site:  centre 8, the four axis neighbours at distance 1: 4, at distance 2: -2
+ *   krbg0   R at (even, odd) and B at (odd, even):  centre 10, left / right 8, two left / right -2, two up / down 1, diagonals -2
+ *   krbg0'  (transposed) R at (odd, even) and B at (even, odd)
+ *   krbbr   R at a B site and B at an R site:  centre 12, diagonals 4, the axis neighbours at distance 2: -3
+ *   the sample the CFA holds passes through
+ * DCPT_DEMOSAIC_BILINEAR: 3 x 3 taps on the three sparse colour planes with circular padding, in units of 1/4: R and B
+ * (2 - |dy|) (2 - |dx|), G centre 4 and the four axis neighbours 1; a neighbour counts for the colour of the position it wraps to.
+ * Without DCPT_DEMOSAIC_UINT8_IO y = sum w x in fp32 on the raw x, no clamp, no rounding (what dm_matlab / dm return; the weights are
+ * dyadic, so a Malvar output is a 13-term fp32 sum: within 13 * 2^-24 * 2.5 * max|x|).  With it the arithmetic is integer and exact:
+ * v = rint(clamp(x, 0, 1) * 255) with the product in fp32, S = sum tap * v, y = float(rint(clamp(S / 16, 0, 255))) / 255.0f (S / 4 for
+ * bilinear), rint half to even: the 8-bit image a camera pipeline would hand on, divided by 255.
+ * Odd H and W are supported, an extension: the reference's mosaic_CFA_Bayer refuses them.
+ * One launch, no workspace, no atomics, no host synchronisation; the same input gives the same bits.
+ * Errors (before the launch): null pointers, x == y, C not 1 or 3, H or W below 3 (the reflection needs 3), B outside 1..65535, a plane
+ * above 2^30 pixels, unknown flag bits.
+ *
+ * dcpt_inpaint_lines_fwd replaces PairedImageInpaintingDataset.inpainting (basicsr/data/paired_image_dataset.py:1009-1029) once the strokes
+ * are drawn: the mask of up to 10 thick line segments and np.clip(img +- mask, 0, 1).
+ *   x, y    dense NCHW fp32 [B][C][H][W], C = 1 or 3; x == y (in place) is allowed
+ *   lines   int32 [B][10][4] on the device: x1, y1, x2, y2 of each stroke (column, row)
+ *   meta    int32 [B][3] on the device: n_lines, thick, white
+ * A pixel p = (px, py) is masked when it lies within thick / 2 of one of the first n_lines segments, decided in exact 64-bit integers with
+ * q = p - P1, d = P2 - P1, a = q . d, L = d . d:  a <= 0: 4 |q|^2 <= thick^2 (also L = 0);  a >= L: 4 |q - d|^2 <= thick^2;  otherwise
+ * 4 (q x d)^2 <= thick^2 L.  A masked pixel becomes 1 if white, else 0, in every channel; every other pixel clamp(x, 0, 1).  This is the
+ * ideal shape of cv2.polylines with a thickness (a quad plus round caps); the two have not been compared.
+ * The entry point cannot see lines and meta without a synchronisation, so the kernel CLAMPS them: n_lines to 0..10, thick to 1..64, an
+ * endpoint coordinate to -16384..16384 (which keeps 4 (q x d)^2 inside 64 bits).  Validate them on the host where they are host data.
+ * Errors (before the launch): null pointers, non-positive sizes, C not 1 or 3, H or W above 16384, B above 65535. */
+#define DCPT_DEMOSAIC_BILINEAR 1   /* dm (bilinear, circular padding) instead of dm_matlab (Malvar, reflect padding) */
+#define DCPT_DEMOSAIC_UINT8_IO 2   /* 8-bit input and output grids, integer arithmetic */
+int dcpt_demosaic_fwd(const float* x, float* y, int B, int C, int H, int W, int flags, dcpt_stream_t stream);
+int dcpt_inpaint_lines_fwd(const float* x, const int* lines, const int* meta, float* y, int B, int C, int H, int W, dcpt_stream_t stream);
+
 /* ---- optional launch profiling (bench.py) -------------------------------------------------------
  * While enabled, MFMA GEMM launches are bracketed by HIP events on their own stream: every launch for on = 1, every
  * on-th launch for on > 1 (sampling keeps the perturbation of a timed region small: an event pair costs ~3 us of queue time).
