@@ -463,6 +463,7 @@ int dw_num_blocks_generic(int B, int H, int W, int Ctot) {
 }
 
 int launch_dw_gelu_fwd(const float* u, const float* w2p, float* t, int B, int H, int W, int Ch, hipStream_t s) {
+    trace_tag("dw.reg_gelu_fwd_f32");
     DCPT_CHECK_ARG(Ch % 4 == 0 && B <= 65535, "dw_gelu_fwd: Ch=%d must be a multiple of 4", Ch);
     DwP p{};
     p.in0 = u; p.w2p = w2p; p.out = t; p.B = B; p.H = H; p.W = W; p.C = Ch;
@@ -475,6 +476,7 @@ int launch_dw_gelu_fwd(const float* u, const float* w2p, float* t, int B, int H,
 }
 
 int launch_dw_gelu_bwd_a(const float* dt, const float* u, const float* w2p, float* da, int B, int H, int W, int Ch, hipStream_t s) {
+    trace_tag("dw.reg_gelu_bwd_a_f32");
     DCPT_CHECK_ARG(Ch % 4 == 0 && B <= 65535, "dw_gelu_bwd_a: Ch=%d must be a multiple of 4", Ch);
     DwP p{};
     p.in0 = u; p.in1 = dt; p.w2p = w2p; p.out = da; p.B = B; p.H = H; p.W = W; p.C = Ch;
@@ -488,6 +490,7 @@ int launch_dw_gelu_bwd_a(const float* dt, const float* u, const float* w2p, floa
 
 int launch_dw_plain_fwd(const float* x, const float* w2p, float* y, float* sq_part, int nsq, int B, int H, int W, int Ctot,
                         hipStream_t s) {
+    trace_tag("dw.reg_plain_fwd_f32");
     DCPT_CHECK_ARG(Ctot % 4 == 0 && nsq % 4 == 0 && B <= 65535, "dw_plain_fwd: Ctot=%d", Ctot);
     DwP p{};
     p.in0 = x; p.w2p = w2p; p.out = y; p.part = sq_part; p.B = B; p.H = H; p.W = W; p.Ctot = Ctot;
@@ -501,6 +504,7 @@ int launch_dw_plain_fwd(const float* x, const float* w2p, float* y, float* sq_pa
 // dx = dw^T(dy) over Ctot channels, wpart[B*nblk][10][Ctot] (nblk = dw_num_blocks_generic)
 int launch_dw_generic_bwd(const float* dy, const float* x, const float* w2p, float* dx, float* wpart, int B, int H, int W, int Ctot,
                           hipStream_t s) {
+    trace_tag("dw.reg_bwd_f32");
     DCPT_CHECK_ARG(Ctot % 4 == 0 && B <= 65535, "dw_generic_bwd: Ctot=%d", Ctot);
     DwP p{};
     p.in0 = dy; p.in1 = x; p.w2p = w2p; p.out = dx; p.part = wpart; p.B = B; p.H = H; p.W = W; p.Ctot = Ctot;

@@ -772,10 +772,12 @@ int launch_dw_ring_bwd_fused_bf16(const bf16_t* dts, const bf16_t* t1, const flo
 // and the plain depthwise backward dx = dw^T(dy) + tap gradients over Ctot channels (Ctot % 8 == 0); wpart as above with C = Ch / Ctot / 2
 int launch_dw_ring_bwd_gelu_f32(const float* dt, const float* u, const float* w2p, float* du, float* wpart, int B, int H, int W, int Ch, hipStream_t s,
                                 float* tout) {
+    trace_tag("dw.ring_gelu_bwd_f32");
     const DwGeom g{B, H, W, Ch};
     return launch_bwd<float, 1>(dt, u, w2p, nullptr, nullptr, nullptr, du, wpart, g, s, tout);
 }
 int launch_dw_ring_bwd_plain_f32(const float* dy, const float* x, const float* w2p, float* dx, float* wpart, int B, int H, int W, int Ctot, hipStream_t s) {
+    trace_tag("dw.ring_plain_bwd_f32");
     DCPT_CHECK_ARG(Ctot % 8 == 0, "depthwise ring: Ctot=%d must be a multiple of 8", Ctot);
     const DwGeom g{B, H, W, Ctot / 2};
     return launch_bwd<float, 2>(dy, x, w2p, nullptr, nullptr, nullptr, dx, wpart, g, s);
@@ -783,6 +785,7 @@ int launch_dw_ring_bwd_plain_f32(const float* dy, const float* x, const float* w
 
 // Restormer GDFN forward on the ring (fp32): t [M][Ch] = gelu(dw(u)[:, :Ch]) * dw(u)[:, Ch:]
 int launch_dw_ring_gelu_fwd_f32(const float* u, const float* w2p, float* t, int B, int H, int W, int Ch, hipStream_t s) {
+    trace_tag("dw.ring_gelu_fwd_f32");
     const DwGeom g{B, H, W, Ch};
     return launch_fwd<float, 1>(u, w2p, nullptr, t, nullptr, g, s);
 }

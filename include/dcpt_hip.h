@@ -274,7 +274,12 @@ int dcpt_bottleneck_bwd_bf16(const uint16_t* dout, const uint16_t* x, const dcpt
  * A parity test uses it to assert WHICH kernel produced the result it compared (tests/kernel_trace.py).
  * The fp32 GEMMs name the tile of every launch: "nt_f32.128x64" / "nt_f32.128x96" / "nt_f32.128x128" (BM x BN of launch_gemm_nt),
  * "tn_f32.64x64" / ".128x64" / ".64x128" / ".128x128" / ".128x96" / ".96x128" (the N x K output tile of launch_gemm_tn), and
- * "nt_f32.x3" / "tn_f32.x3" where the opt-in bf16x3 mode takes the launch instead. */
+ * "nt_f32.x3" / "tn_f32.x3" where the opt-in bf16x3 mode takes the launch instead.
+ * The fp32 depthwise launches of the Restormer / PromptIR halves name their form: MDTA "dw.reg_plain_fwd_f32" (register kernel, always),
+ * backward "dw.ring_plain_bwd_f32" (row ring, 3C % 8 == 0) or "dw.reg_bwd_f32" (register kernel, otherwise); GDFN "dw.ring_gelu_fwd_f32" /
+ * "dw.ring_gelu_bwd_f32", and "dw.reg_gelu_fwd_f32" / "dw.reg_gelu_bwd_a_f32" (+ "dw.reg_bwd_f32") for the register forms behind them,
+ * which no legal fp32 shape reaches (tests/test_gpu_restormer_halves.py).  Their bf16 twins: "rst_bf16.dw_sq_fwd", "rst_bf16.dw_plain_bwd",
+ * "dw.ring_gelu_fwd_bf16", "dw.ring_bwd_gelu_bf16". */
 int dcpt_trace_enable(int on);
 size_t dcpt_trace_read(char* buf, size_t cap);
 
