@@ -13,7 +13,7 @@ from torch.utils import data as tdata
 from basicsr.utils import get_root_logger, scandir
 from basicsr.utils.registry import DATASET_REGISTRY
 
-__all__ = ["build_dataset", "build_dataloader", "paired_random_crop_augment"]
+__all__ = ["build_dataset", "build_dataloader", "paired_random_crop_augment", "degrade_collate"]
 _IMG_EXT = (".png", ".jpg", ".jpeg", ".bmp", ".tif", ".tiff", ".PNG", ".JPG")
 
 
@@ -132,7 +132,15 @@ class PairedImageDenoiseDataset(tdata.Dataset):
     """GT folder + on-the-fly Gaussian noise (reference basicsr/data/paired_image_dataset.py:276-421).  The noise reproduces
     the reference's draw exactly (:388-402): ``sigma`` from ``sigma_type`` constant / random / choice (Python's ``random``),
     ``np.random.seed(index)`` in the train phase and ``seed(0)`` otherwise, ``normal(0, sigma / 255, (H, W, 3))`` on the
-    **HWC**, RGB-ordered float32 image AFTER the crop / augmentation, added in float32."""
+    **HWC**, RGB-ordered float32 image AFTER the crop / augmentation, added in float32.
+
+    ``noise_backend: host`` (default) is that draw.  ``noise_backend: device``: the sample carries ``gt``, ``noise_sigma`` (a float32
+    scalar, from the same ``random`` draw in the same order as the host path), ``noise_key`` (an int64 scalar) and the paths, and no
+    ``lq``; the model's ``feed_data`` makes ``lq`` with ``dcpt_amd.functional.gaussian_noise(gt, noise_sigma, noise_key)``, unclipped
+    like the host path.  In the train phase the key is ``random.getrandbits(63)``: fresh noise every epoch, reproducible under the
+    loader's worker seeding.  In other phases it is ``(noise_seed << 32) | index`` (``noise_seed`` default 0): a validation set sees
+    the same noise on every visit.  The device stream is Philox4x32-10, not MT19937, so its noise equals the host path's in
+    distribution and not in value: numbers comparable with the paper's ``np.random.seed(0)`` test noise need the ``host`` backend."""
 
     def __init__(self, opt):
         super().__init__()
@@ -141,6 +149,12 @@ class PairedImageDenoiseDataset(tdata.Dataset):
         self.sigma_type = opt.get("sigma_type", "constant")
         self.sigma_range = opt["sigma_range"]
         assert self.sigma_type in ["constant", "random", "choice"]
+        self.backend = opt.get("noise_backend", "host")
+        if self.backend not in ("host", "device"):
+            raise ValueError(f"noise_backend must be 'host' or 'device', got {self.backend!r}")
+        self.noise_seed = int(opt.get("noise_seed", 0))
+        if not 0 <= self.noise_seed < (1 << 31):
+            raise ValueError(f"noise_seed must lie in 0..2^31 - 1, got {self.noise_seed}")
         self.names = sorted(f for f in scandir(self.gt_root) if f.endswith(_IMG_EXT))
 
     def __len__(self):
@@ -161,6 +175,10 @@ class PairedImageDenoiseDataset(tdata.Dataset):
             sigma = random.uniform(self.sigma_range[0], self.sigma_range[1])
         else:
             sigma = random.choice(self.sigma_range)
+        if self.backend == "device":
+            key = random.getrandbits(63) if self.opt.get("phase") == "train" else (self.noise_seed << 32) | index
+            return _labelled({"gt": gt.contiguous(), "lq_path": path, "gt_path": path, "noise_sigma": torch.tensor(float(sigma), dtype=torch.float32),
+                              "noise_key": torch.tensor(key, dtype=torch.int64)}, self.opt)
         rs = np.random.RandomState(index if self.opt.get("phase") == "train" else 0)   # == np.random.seed(...); np.random.normal
         hwc = gt.permute(1, 2, 0).contiguous().numpy().copy()
         hwc += rs.normal(0, sigma / 255.0, hwc.shape)   # float64 noise accumulated into the float32 image, as `img_lq += ...`
@@ -450,6 +468,47 @@ class PairedImageDehazeDataset(tdata.Dataset):
         return _labelled({"lq": lq, "gt": gt, "lq_path": lq_path, "gt_path": gt_path}, self.opt)
 
 
+# which key makes a sample which kind of a mixed batch (``degrade_kind``), and the keys that kind brings along
+DEGRADE_KINDS = (("lq", ("lq",)), ("noise_sigma", ("noise_sigma", "noise_key")), ("jpeg_quality", ("jpeg_quality",)), ("mosaic", ("mosaic",)),
+                 ("inpaint_meta", ("inpaint_lines", "inpaint_meta")))
+
+
+def degrade_collate(samples):
+    """``collate_fn`` of the train loader.  Samples with identical key sets -- every batch of a single data set -- give exactly
+    ``default_collate(samples)``.  A batch of a ``ConcatDataset`` over sets with different device backends mixes samples that carry
+    different keys, which the default collate refuses; it is collated as: the keys common to all samples (``gt``, the paths,
+    ``dataset_idx``) as usual; ``degrade_kind``, an int32 ``[B]`` host tensor: 0 the sample has ``lq``, 1 ``noise_sigma``, 2
+    ``jpeg_quality``, 3 ``mosaic``, 4 ``inpaint_meta``; and each kind's own keys (``lq`` included) stacked over THAT KIND'S samples in
+    batch order.  ``BaseModel._lq_on_device`` makes the ``lq`` rows of each kind from its ``gt`` rows."""
+    from torch.utils.data import default_collate
+
+    keys = set(samples[0].keys())
+    if all(set(s.keys()) == keys for s in samples[1:]):
+        return default_collate(samples)
+    kinds = []
+    for s in samples:
+        kind = [k for k, (key, _) in enumerate(DEGRADE_KINDS) if key in s]
+        if len(kind) != 1:
+            raise ValueError(f"a sample of a mixed batch carries exactly one of {[key for key, _ in DEGRADE_KINDS]}; got the keys "
+                             f"{sorted(s.keys())}")
+        kinds.append(kind[0])
+    shapes = sorted({tuple(s["gt"].shape) for s in samples})
+    if len(shapes) != 1:
+        raise ValueError(f"the samples of a mixed batch have gt of different sizes {shapes}: give every train set the same gt_size")
+    own = {k for _, ks in DEGRADE_KINDS for k in ks}
+    common = set.intersection(*(set(s.keys()) for s in samples)) - own
+    loose = set.union(*(set(s.keys()) for s in samples)) - own - common
+    if loose:
+        raise ValueError(f"the keys {sorted(loose)} are carried by some samples of a mixed batch only")
+    batch = default_collate([{k: s[k] for k in s if k in common} for s in samples])
+    batch["degrade_kind"] = torch.tensor(kinds, dtype=torch.int32)
+    for kind, (_, ks) in enumerate(DEGRADE_KINDS):
+        rows = [s for s, kd in zip(samples, kinds) if kd == kind]
+        if rows:
+            batch.update(default_collate([{k: s[k] for k in ks} for s in rows]))
+    return batch
+
+
 def build_dataset(dataset_opt):
     dataset_opt = deepcopy(dataset_opt)
     logger = get_root_logger()
@@ -483,6 +542,6 @@ def build_dataloader(dataset, dataset_opt, num_gpu=1, dist=False, sampler=None, 
             random.seed(s)
 
         return tdata.DataLoader(dataset, batch_size=batch, shuffle=sampler is None, sampler=sampler, num_workers=workers,
-                                drop_last=True, worker_init_fn=worker_init if seed is not None else None,
+                                drop_last=True, worker_init_fn=worker_init if seed is not None else None, collate_fn=degrade_collate,
                                 pin_memory=dataset_opt.get("pin_memory", False), persistent_workers=False)
     raise ValueError(f"Wrong dataset phase: {phase}. Supported ones are 'train', 'val' and 'test'.")

@@ -38,7 +38,15 @@ class BaseModel:
         (PairedImageJPEGCARDataset: ``gt`` and ``jpeg_quality``, no ``lq``) gets it from the JPEG round trip of ``gt`` on the device, a
         batch of a ``demosaic_backend: device`` set (PairedImageMosaicDataset: ``gt`` and ``mosaic``, the method's index) from the demosaic
         kernel, and a batch of an ``inpaint_backend: device`` set (PairedImageInpaintingDataset: ``gt``, ``inpaint_lines``,
-        ``inpaint_meta``) from the line-mask kernel"""
+        ``inpaint_meta``) from the line-mask kernel, and a batch of a ``noise_backend: device`` set (PairedImageDenoiseDataset: ``gt``,
+        ``noise_sigma``, ``noise_key``) from the Philox noise kernel, unclipped like the host path.  A mixed batch
+        (``basicsr.data.degrade_collate``: ``degrade_kind`` per sample, each kind's keys stacked over its own samples) gets every kind's rows
+        from that kind's op on its ``gt`` rows"""
+        if "degrade_kind" in data:
+            return self._lq_mixed(data)
+        if "lq" not in data and "noise_sigma" in data:
+            gt = data["gt"].to(self.device, non_blocking=True)
+            return DF.gaussian_noise(gt, data["noise_sigma"], data["noise_key"])
         if "lq" not in data and "jpeg_quality" in data:
             gt = data["gt"].to(self.device, non_blocking=True)
             return DF.diffjpeg(gt, data["jpeg_quality"].to(self.device, non_blocking=True), uint8_io=True)
@@ -52,6 +60,38 @@ class BaseModel:
             gt = data["gt"].to(self.device, non_blocking=True)
             return DF.inpaint_lines(gt, data["inpaint_lines"], data["inpaint_meta"])
         return data["lq"].to(self.device, non_blocking=True)
+
+    def _lq_mixed(self, data):
+        """``lq`` of a mixed batch: allocated like ``gt``; for each kind present the rows of that kind (read from the HOST tensor
+        ``degrade_kind``: no synchronisation) are gathered from ``gt``, degraded by the kind's op and scattered back.  Demosaic rows are
+        grouped by method, so one batch may hold both."""
+        gt = data["gt"].to(self.device, non_blocking=True)
+        kind = data["degrade_kind"].reshape(-1).tolist()
+        if len(kind) != gt.shape[0] or not set(kind) <= set(range(5)):
+            raise ValueError(f"degrade_kind must hold one of 0..4 for each of the {gt.shape[0]} images, got {kind}")
+        lq = torch.empty_like(gt)
+
+        def put(rows, op):
+            index = torch.tensor(rows, dtype=torch.long).to(self.device, non_blocking=True)
+            lq.index_copy_(0, index, op(gt.index_select(0, index)))
+
+        for k in sorted(set(kind)):
+            rows = [i for i, v in enumerate(kind) if v == k]
+            if k == 0:
+                put(rows, lambda g: data["lq"].to(self.device, non_blocking=True))
+            elif k == 1:
+                put(rows, lambda g: DF.gaussian_noise(g, data["noise_sigma"], data["noise_key"]))
+            elif k == 2:
+                put(rows, lambda g: DF.diffjpeg(g, data["jpeg_quality"].to(self.device, non_blocking=True), uint8_io=True))
+            elif k == 3:
+                methods = data["mosaic"].reshape(-1).tolist()
+                if len(methods) != len(rows) or not set(methods) <= set(range(len(DF.DEMOSAIC_METHODS))):
+                    raise ValueError(f"mosaic holds 0 (malvar) or 1 (bilinear) for each demosaic image; got {methods}")
+                for m in sorted(set(methods)):
+                    put([r for r, v in zip(rows, methods) if v == m], lambda g, m=m: DF.demosaic(g, DF.DEMOSAIC_METHODS[m], uint8_io=True))
+            else:
+                put(rows, lambda g: DF.inpaint_lines(g, data["inpaint_lines"], data["inpaint_meta"]))
+        return lq
 
     def optimize_parameters(self, current_iter):
         pass

@@ -2,7 +2,7 @@
 """Secondary workloads of BASELINE.json (configs[2..4]) on ONE MI355X -- evidence for DESIGN.md, not the driver's
 contract (that is bench.py).  Prints one JSON line per workload.
 
-    python bench_extra.py --workload dcpt|dcpt_swinir|restormer|promptir|infer2k|naf|swinir|rcan|val_metrics|step_tail|tlsc|ssim_loss|ldl|jpeg|niqe|degrade [--dtype fp32|bf16|bf16_res32] [--steps K] [--warmup W]
+    python bench_extra.py --workload dcpt|dcpt_swinir|restormer|promptir|infer2k|naf|swinir|rcan|val_metrics|step_tail|tlsc|ssim_loss|ldl|jpeg|niqe|degrade|noise [--dtype fp32|bf16|bf16_res32] [--steps K] [--warmup W]
 
 ``--dtype bf16`` (dcpt, naf, infer2k, restormer, promptir; rcan: the inference line only, next to fp32; swinir: the restoration form's inference, next to fp32): every feature map of the encoder in bf16 storage with fp32 accumulation (act_dtype="bf16";
 dcpt: the classifier head too unless --head-dtype fp32); images, parameters and the optimizer stay fp32.  Its lines carry BOTH
@@ -921,6 +921,105 @@ def run_degrade(dev, steps=20, warmup=3, B=16, S=256):
     return out
 
 
+def run_noise(dev, steps=20, warmup=3, B=32, S=256):
+    """Gaussian noise on a B x 3 x S x S batch with one sigma per image (dcpt_amd/csrc/noise.hip) and ``feed_data`` of a mixed batch; two
+    result lines.  Line 1: ``dcpt_amd.functional.gaussian_noise`` against the torch route on the device (``gt + sigma / 255 * randn_like``)
+    and the host route of PairedImageDenoiseDataset (``RandomState(i).normal`` over S x S x 3 plus the add, the B images on one thread,
+    best of 3).  Line 2: ``BaseModel._lq_on_device`` on a mixed batch (B / 4 images of each of noise, JPEG, demosaic, inpainting; gt on
+    the host, as a loader hands it over) against the same four ops on four separate B / 4-image batches.  The routes of a pair alternate
+    call by call in one process; each call is bracketed by device events; median and minimum of the per-call times after the warm-up,
+    each route's peak memory above what is resident between calls."""
+    import statistics
+    import time
+
+    import numpy as np
+    import torch.nn.functional as F
+
+    from basicsr.models.base_model import BaseModel
+    from dcpt_amd import functional as DF
+
+    g = torch.Generator(device=dev).manual_seed(1234)
+    low = torch.rand((B, 3, S // 8, S // 8), generator=g, device=dev)
+    x = F.interpolate(low, size=(S, S), mode="bilinear", align_corners=False).clamp(0, 1)
+    sig_host = torch.tensor([(15.0, 25.0, 50.0)[i % 3] for i in range(B)])
+    sigma, key = sig_host.to(dev), torch.arange(B, dtype=torch.int64, device=dev) + (7 << 32)
+    scale = (sigma / 255).view(-1, 1, 1, 1)
+
+    def measure(routes):
+        peaks, last, times, wall = {}, {}, {n: [] for n in routes}, {n: [] for n in routes}
+        with torch.no_grad():
+            for i in range(warmup + steps):
+                for n, fn in routes.items():
+                    torch.cuda.synchronize(dev)
+                    base = torch.cuda.memory_allocated(dev)
+                    torch.cuda.reset_peak_memory_stats(dev)
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    t0 = time.perf_counter()
+                    e0.record()
+                    last[n] = fn()
+                    e1.record()
+                    e1.synchronize()
+                    t1 = time.perf_counter()
+                    peaks[n] = max(peaks.get(n, 0), torch.cuda.max_memory_allocated(dev) - base)
+                    if i >= warmup:
+                        times[n].append(e0.elapsed_time(e1))
+                        wall[n].append((t1 - t0) * 1e3)
+        return peaks, last, times, wall
+
+    peaks, last, times, _ = measure({"kernel": lambda: DF.gaussian_noise(x, sigma, key), "torch": lambda: x + scale * torch.randn_like(x)})
+    xh = x.cpu().permute(0, 2, 3, 1).contiguous().numpy()
+    host = []
+    for _ in range(3):
+        t0 = time.perf_counter()
+        for i in range(B):
+            hwc = xh[i].copy()
+            hwc += np.random.RandomState(i).normal(0, float(sig_host[i]) / 255.0, hwc.shape)
+        host.append((time.perf_counter() - t0) * 1e3)
+    noise = (last["kernel"] - x) / scale
+    moved = 8 * x.numel()
+    kmin = min(times["kernel"])
+    first = dict(workload=f"Gaussian noise, {B} x 3 x {S} x {S}, one sigma per image (15 / 25 / 50): gt + sigma / 255 * n",
+                 kernel_ms_median=round(statistics.median(times["kernel"]), 4), kernel_ms_min=round(kmin, 4),
+                 torch_ms_median=round(statistics.median(times["torch"]), 4), torch_ms_min=round(min(times["torch"]), 4),
+                 ratio_median=round(statistics.median(times["torch"]) / statistics.median(times["kernel"]), 2),
+                 host_ms_min=round(min(host), 2), host_ms_per_image=round(min(host) / B, 3),
+                 kernel_gb_per_s_at_min=round(moved / (kmin * 1e-3) / 1e9, 1), kernel_gnormals_per_s_at_min=round(x.numel() / (kmin * 1e-3) / 1e9, 2),
+                 kernel_peak_mb=round(peaks["kernel"] / 1e6, 1), torch_peak_mb=round(peaks["torch"] / 1e6, 1),
+                 kernel_noise_mean=round(float(noise.mean()), 5), kernel_noise_std=round(float(noise.std()), 5), calls=steps, warmup=warmup,
+                 note="device events around each call (the op's host side included), the two device routes alternating in one process; peak "
+                      "memory of a call above what is allocated between calls; kernel_gb_per_s_at_min counts one read and one write of the "
+                      "batch over the fastest call, to set against the HBM rate; host_ms_min is one thread's RandomState(i).normal + add for "
+                      "all B images, best of 3; the three routes draw different streams: they agree in distribution, not in value")
+
+    # feed_data of a mixed batch against four single-kind batches
+    model = BaseModel(dict(num_gpu=1, is_train=False))
+    n = B // 4
+    gt = x.cpu()
+    gi = torch.Generator().manual_seed(99)
+    lines = torch.randint(0, S + 1, (n, 10, 4), generator=gi, dtype=torch.int32)
+    meta = torch.stack([torch.randint(5, 11, (n,), generator=gi), torch.randint(5, 11, (n,), generator=gi), torch.arange(n) % 2], dim=1).to(torch.int32)
+    own = [dict(noise_sigma=sig_host[:n].clone(), noise_key=torch.arange(n, dtype=torch.int64)),
+           dict(jpeg_quality=torch.tensor([(10.0, 20.0, 30.0, 40.0)[i % 4] for i in range(n)])),
+           dict(mosaic=torch.zeros(n, dtype=torch.int32)), dict(inpaint_lines=lines, inpaint_meta=meta)]
+    kind = torch.tensor([1 + i % 4 for i in range(4 * n)], dtype=torch.int32)      # interleaved, as a shuffled loader hands them over
+    mixed = dict(gt=gt[:4 * n], degrade_kind=kind)
+    for d in own:
+        mixed.update(d)
+    single = [dict(gt=gt[:4 * n][kind == k + 1].contiguous(), **own[k]) for k in range(4)]
+    peaks, last, times, wall = measure({"mixed": lambda: model._lq_on_device(mixed), "separate": lambda: [model._lq_on_device(d) for d in single]})
+    same = all(torch.equal(last["mixed"][kind.to(dev) == k + 1], last["separate"][k]) for k in range(4))
+    second = dict(workload=f"feed_data's lq of a mixed batch, {4 * n} x 3 x {S} x {S}: {n} each of noise, JPEG, demosaic, inpainting, gt from the host",
+                  mixed_ms_median=round(statistics.median(times["mixed"]), 4), mixed_ms_min=round(min(times["mixed"]), 4),
+                  separate_ms_median=round(statistics.median(times["separate"]), 4), separate_ms_min=round(min(times["separate"]), 4),
+                  mixed_wall_ms_median=round(statistics.median(wall["mixed"]), 4), separate_wall_ms_median=round(statistics.median(wall["separate"]), 4),
+                  mixed_peak_mb=round(peaks["mixed"] / 1e6, 1), separate_peak_mb=round(peaks["separate"] / 1e6, 1), rows_bit_identical=bool(same),
+                  calls=steps, warmup=warmup,
+                  note="mixed: one transfer of gt, then per kind index_select -> the kind's kernel -> index_copy_ into lq; separate: the same "
+                       "four kernels on four batches of their own (four transfers, no gather or scatter); both include the pageable "
+                       "host-to-device copy of gt; the wall times add the host side after the last launch")
+    return [first, second]
+
+
 def run_niqe(dev, steps=20, warmup=3, H=1080, W=2048):
     """NIQE of one 1 x 3 x H x W image (a smooth random field plus fine noise, no flat block): the host ``calculate_niqe`` (numpy float64,
     one thread's wall time, best of 2) against ``calculate_niqe_device`` (the fused fp64 kernels of dcpt_amd/csrc/niqe.hip + the host
@@ -971,7 +1070,7 @@ def run_niqe(dev, steps=20, warmup=3, H=1080, W=2048):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", required=True, choices=["dcpt", "dcpt_swinir", "restormer", "promptir", "infer2k", "naf", "swinir", "rcan", "val_metrics", "step_tail", "tlsc", "ssim_loss", "ldl", "jpeg", "niqe", "degrade"])
+    ap.add_argument("--workload", required=True, choices=["dcpt", "dcpt_swinir", "restormer", "promptir", "infer2k", "naf", "swinir", "rcan", "val_metrics", "step_tail", "tlsc", "ssim_loss", "ldl", "jpeg", "niqe", "degrade", "noise"])
     ap.add_argument("--dtype", default="fp32", choices=["fp32", "bf16", "bf16_tail32", "bf16_edge32", "bf16_res32"])
     ap.add_argument("--head-dtype", default=None, choices=["fp32", "bf16"], help="dcpt: classifier-head activations (default: --dtype)")
     ap.add_argument("--restormer-save", default="balanced", choices=["auto", "lean", "balanced", "full"], help="what the Restormer halves keep for backward")
@@ -1171,6 +1270,10 @@ def main():
         res = run_niqe(dev, max(args.steps, 20), max(args.warmup, 3))
     elif args.workload == "degrade":
         lines = run_degrade(dev, max(args.steps, 20), max(args.warmup, 3), args.batch or 16, args.size or 256)
+        print(json.dumps(lines[0]), flush=True)
+        res = lines[1]
+    elif args.workload == "noise":
+        lines = run_noise(dev, max(args.steps, 20), max(args.warmup, 3), args.batch or 32, args.size or 256)
         print(json.dumps(lines[0]), flush=True)
         res = lines[1]
     elif args.workload == "tlsc":

@@ -527,3 +527,17 @@ extern "C" int dcpt_inpaint_lines_fwd(const float* x, const int* lines, const in
     DCPT_CHECK_ARG(B <= 65535, "inpaint_lines_fwd: B above 65535 (got %d)", B);
     return launch_inpaint_lines_fwd(x, lines, meta, y, B, C, H, W, (hipStream_t)stream);
 }
+
+// ---------------------------------------------------------------------------------------------
+// Gaussian noise from a per-image Philox stream (noise.hip)
+extern "C" int dcpt_gauss_noise_fwd(const float* x, const float* sigma, const long long* key, const int* gray, float* y, int B, int C, int H,
+                                    int W, int flags, dcpt_stream_t stream) {
+    DCPT_CHECK_ARG((flags & ~(DCPT_NOISE_CLIP | DCPT_NOISE_ROUND8 | DCPT_NOISE_ONLY)) == 0, "gauss_noise_fwd: unknown flags 0x%x", flags);
+    DCPT_CHECK_ARG((x || (flags & DCPT_NOISE_ONLY)) && sigma && key && y, "gauss_noise_fwd: null argument");
+    DCPT_CHECK_ARG(B > 0 && C > 0 && H > 0 && W > 0, "gauss_noise_fwd: bad shape (B=%d C=%d H=%d W=%d)", B, C, H, W);
+    // (the counter's first word holds element / 4; compared by division: C * H * W itself may leave 64 bits)
+    DCPT_CHECK_ARG((int64_t)C <= (((int64_t)1 << 34) - 1) / ((int64_t)H * W), "gauss_noise_fwd: C * H * W must stay below 2^34 (C=%d H=%d W=%d)",
+                   C, H, W);
+    DCPT_CHECK_ARG((int64_t)B <= ((int64_t)1 << 40) / ((int64_t)C * H * W), "gauss_noise_fwd: a batch above 2^40 elements (B=%d)", B);
+    return launch_gauss_noise_fwd(x, sigma, key, gray, y, B, C, H, W, flags, (hipStream_t)stream);
+}

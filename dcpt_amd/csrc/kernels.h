@@ -224,3 +224,9 @@ int launch_niqe_block_stats_fwd(const double* n, double* stats, int P, int H, in
 // the line-mask inpainting degradation (dcpt_inpaint_lines_fwd: lines int32 [B][10][4], meta int32 [B][3]); one launch each, no workspace.
 int launch_demosaic_fwd(const float* x, float* y, int B, int C, int H, int W, int flags, hipStream_t s);
 int launch_inpaint_lines_fwd(const float* x, const int* lines, const int* meta, float* y, int B, int C, int H, int W, hipStream_t s);
+
+// ---- noise.hip ------------------------------------------------------------------------------
+// Gaussian noise from a Philox4x32-10 stream per image (dcpt_gauss_noise_fwd: sigma fp32 [B], key int64 [B], gray int32 [B] or null on the
+// device; x may be null with DCPT_NOISE_ONLY; in place allowed); one launch, no workspace.
+int launch_gauss_noise_fwd(const float* x, const float* sigma, const long long* key, const int* gray, float* y, int B, int C, int H, int W,
+                           int flags, hipStream_t s);

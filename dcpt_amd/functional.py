@@ -3021,6 +3021,67 @@ def inpaint_lines(x, lines, meta):
 
 
 # ------------------------------------------------------------------------------------------------
+# Gaussian noise from a per-image Philox4x32-10 stream (include/dcpt_hip.h dcpt_gauss_noise_fwd): lq from gt in one launch.
+NOISE_CLIP, NOISE_ROUND8, NOISE_ONLY = 1, 2, 4   # include/dcpt_hip.h DCPT_NOISE_*
+NOISE_MAX_ELEMS = 1 << 34                        # C * H * W of one image stays below this
+
+
+def _per_image(name, v, B, dtype, dev):
+    """a per-image argument as a (B,) device tensor: a Python number for every image, or a tensor of B values (0-d or one value: for every
+    image); a device tensor is never read back"""
+    if torch.is_tensor(v):
+        if v.numel() not in (1, B) or v.dim() > 1 and v.numel() != B:
+            raise ValueError(f"gaussian_noise: {name} must be a number or hold {B} values, got {tuple(v.shape)}")
+        v = v.detach().reshape(-1).to(device=dev, dtype=dtype, non_blocking=True)
+        return (v.expand(B) if v.numel() != B else v).contiguous()
+    return torch.full((B,), v, dtype=dtype, device=dev)
+
+
+def gaussian_noise(x, sigma, key, gray=None, clip=False, rounds=False, noise_only=False, out=None):
+    """``x + sigma / 255 * n`` with n standard normal: ``x`` (B, C, H, W) fp32 device tensor (any strides: it is made contiguous NCHW),
+    ``sigma`` the standard deviation on the 0..255 scale, ``key`` the 64-bit key of the image's Philox4x32-10 stream (include/dcpt_hip.h
+    states the generator), ``gray`` non-zero for one noise plane shared by the channels.  ``sigma``, ``key`` and ``gray`` are Python
+    numbers (for every image: one key gives every image the same noise) or tensors of B values, on the host or the device; a device
+    tensor is not read back, so only a host sigma is checked (a negative one raises).  The sum is taken in fp64 and rounded once;
+    ``sigma == 0`` without flags returns ``x`` bit for bit.  ``clip``: clamp to [0, 1]; ``rounds``: ``rint(255 v) / 255`` after it;
+    ``noise_only``: the noise term without ``x`` (``x`` then gives the shape and the device only).  ``out``: a contiguous fp32 tensor
+    of x's shape on its device to write into; ``out=x`` works in place.  An image's result depends on its own values only, not on the
+    batch around it.  Forward only."""
+    if not torch.is_tensor(x):
+        raise _lib.DcptHipError(f"gaussian_noise takes a device tensor (got {type(x).__name__})")
+    _require_gpu(x)
+    if x.dim() != 4 or 0 in x.shape or x.shape[1] * x.shape[2] * x.shape[3] >= NOISE_MAX_ELEMS:
+        raise ValueError(f"gaussian_noise: expected a non-empty (B, C, H, W) batch with C * H * W < 2^34, got {tuple(x.shape)}")
+    _inference_only("gaussian_noise", x, what="the noise degradation")
+    B, C, H, W = x.shape
+    dev = x.device
+    host_sigma = sigma if not torch.is_tensor(sigma) else (None if sigma.is_cuda else sigma)
+    if host_sigma is not None and bool(torch.as_tensor(host_sigma).lt(0).any()):
+        raise ValueError(f"gaussian_noise: sigma must not be negative, got {host_sigma!r}")
+    if not torch.is_tensor(key):
+        key = int(key)
+        if not -(1 << 63) <= key < (1 << 64):
+            raise ValueError(f"gaussian_noise: key must fit 64 bits, got {key}")
+        key = key - (1 << 64) if key >= (1 << 63) else key   # (the same 64 bits as a signed value)
+    elif key.is_floating_point():
+        raise ValueError("gaussian_noise: key must be an integer tensor")
+    sigma = _per_image("sigma", sigma if torch.is_tensor(sigma) else float(sigma), B, torch.float32, dev)
+    key = _per_image("key", key, B, torch.int64, dev)
+    if gray is not None:
+        gray = _per_image("gray", gray.ne(0) if torch.is_tensor(gray) else int(bool(gray)), B, torch.int32, dev)
+    x = x.detach().contiguous()   # (no copy of a contiguous x, so out=x stays in place)
+    if out is None:
+        out = torch.empty_like(x)
+    else:
+        if not torch.is_tensor(out) or out.shape != x.shape or out.device != dev or out.dtype != torch.float32 or not out.is_contiguous():
+            raise ValueError(f"gaussian_noise: out must be a contiguous fp32 tensor of shape {tuple(x.shape)} on {dev}")
+        _inference_only("gaussian_noise", out, what="the noise degradation")
+    flags = (NOISE_CLIP if clip else 0) | (NOISE_ROUND8 if rounds else 0) | (NOISE_ONLY if noise_only else 0)
+    _call(_lib.load().dcpt_gauss_noise_fwd, (None if noise_only else x, sigma, key, gray, out), (B, C, H, W, flags), dev)
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
 # MATLAB-bicubic resize and the pixel work of NIQE (include/dcpt_hip.h dcpt_imresize_fwd, dcpt_niqe_mscn_fwd, dcpt_niqe_block_stats_fwd):
 # the reference's basicsr/utils/matlab_functions.py::imresize and the per-pixel part of basicsr/metrics/niqe.py in fp64.  Forward only.
 IMRESIZE_X_F64, IMRESIZE_Y_F64, IMRESIZE_QUANT8 = 1, 2, 4   # include/dcpt_hip.h DCPT_IMRESIZE_*

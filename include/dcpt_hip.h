@@ -969,6 +969,33 @@ int dcpt_niqe_block_stats_fwd(const double* n, double* stats, int P, int H, int 
 int dcpt_demosaic_fwd(const float* x, float* y, int B, int C, int H, int W, int flags, dcpt_stream_t stream);
 int dcpt_inpaint_lines_fwd(const float* x, const int* lines, const int* meta, float* y, int B, int C, int H, int W, dcpt_stream_t stream);
 
+/* ---- on-the-fly degradations: Gaussian noise from a counter-based generator, on the device ---------------------
+ * dcpt_gauss_noise_fwd replaces the Gaussian family of basicsr/data/degradations.py:530-634 (generate_ / add_ / random_generate_ /
+ * random_add_gaussian_noise_pt) and the noise of PairedImageDenoiseDataset (basicsr/data/paired_image_dataset.py:390-402) with one launch
+ * for the batch.  The reference draws from torch.randn / np.random.normal, sequential generators that cannot be restated in parallel; the
+ * stream here is Philox4x32-10, so results match the reference's in distribution and not in value.
+ *   x       dense NCHW fp32 [B][C][H][W]; unused and may be null with DCPT_NOISE_ONLY
+ *   sigma   fp32 [B] on the device: the standard deviation of image b on the 0..255 scale
+ *   key     int64 [B] on the device: the Philox key of image b (words: its low and its high 32 bits)
+ *   gray    int32 [B] on the device or null: non-zero gives image b one noise plane shared by its channels
+ *   y       dense NCHW fp32 [B][C][H][W]; y == x (in place) is allowed
+ * Generator: Philox4x32-10, multipliers 0xD2511F53 and 0xCD9E8D57, key increments 0x9E3779B9 and 0xBB67AE85, counter (q, 0, 0, 0); known
+ * answer: counter 0, key 0 -> 6627e8d5 e169c58d bc57ac4c 9b00dbd8.  Normals, in fp64 from the outputs x0..x3 of counter q:
+ * u_i = (x_i + 0.5) 2^-32, r0 = sqrt(-2 ln u0), r1 = sqrt(-2 ln u2), n_4q..4q+3 = r0 cos 2 pi u1, r0 sin 2 pi u1, r1 cos 2 pi u3,
+ * r1 sin 2 pi u3.  Colour noise: element e of the image's C H W values in NCHW order takes n_e; gray noise: pixel p of H W takes n_p in
+ * every channel.  y = float(double(x) + double(sigma[b]) / 255 * n), rounded once; sigma[b] == 0 without flags returns x bit for bit.
+ * DCPT_NOISE_CLIP clamps to [0, 1]; DCPT_NOISE_ROUND8 takes rint(255 v) / 255, half to even, after the clamp (with CLIP:
+ * clamp(round(255 v), 0, 255) / 255 of add_gaussian_noise_pt); DCPT_NOISE_ONLY writes sigma / 255 * n instead of the sum.
+ * An image's result depends on its own (x, sigma, key, gray) only, not on the batch around it or its position in it.  One launch, no
+ * workspace, no atomics, no host synchronisation; the same input gives the same bits.
+ * Errors (before the launch): null x (without DCPT_NOISE_ONLY), sigma, key or y, non-positive extents, C H W at or above 2^34 (the
+ * counter's first word holds element / 4), a batch above 2^40 elements, unknown flag bits. */
+#define DCPT_NOISE_CLIP 1     /* clamp to [0, 1] */
+#define DCPT_NOISE_ROUND8 2   /* rint(255 v) / 255 */
+#define DCPT_NOISE_ONLY 4     /* write the noise, not x + noise */
+int dcpt_gauss_noise_fwd(const float* x, const float* sigma, const long long* key, const int* gray, float* y, int B, int C, int H, int W,
+                         int flags, dcpt_stream_t stream);
+
 /* ---- optional launch profiling (bench.py) -------------------------------------------------------
  * While enabled, MFMA GEMM launches are bracketed by HIP events on their own stream: every launch for on = 1, every
  * on-th launch for on > 1 (sampling keeps the perturbation of a timed region small: an event pair costs ~3 us of queue time).
