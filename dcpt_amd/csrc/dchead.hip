@@ -132,7 +132,21 @@ __global__ __launch_bounds__(256) void mix_bwd_kernel(const ST* __restrict__ dou
     if (threadIdx.x == 0) part[blockIdx.x] = red[0];
 }
 
-// dmix[j] = ds * s_i * (delta_ij - s_j),  ds = sum_blocks part
+// 1 - softmax(w)[i] as the sum of the other weights: no cancellation when s_i is close to 1
+__device__ __forceinline__ float softmax_rest(const float* w, int n, int i) {
+    float m = w[0];
+    for (int j = 1; j < n; ++j) m = fmaxf(m, w[j]);
+    float s = 0.f, r = 0.f;
+    for (int j = 0; j < n; ++j) {
+        const float e = expf(w[j] - m);
+        s += e;
+        if (j != i) r += e;
+    }
+    return r / s;
+}
+
+// dmix[j] = ds * s_i * (delta_ij - s_j),  ds = sum_blocks part.  For j == i with s_i > 1/2 the factor 1 - s_i is softmax_rest: in fp32
+// 1 - s_i keeps no digit once s_i rounds to 1, and the whole gradient is of that size then (at s_i <= 1/2 the difference is as good).
 __global__ __launch_bounds__(256) void mix_bwd_final_kernel(const float* __restrict__ part, int nblk, const float* __restrict__ mw,
                                                             int n, int idx, float* __restrict__ dmix) {
     __shared__ float red[256];
@@ -147,7 +161,9 @@ __global__ __launch_bounds__(256) void mix_bwd_final_kernel(const float* __restr
     if (threadIdx.x < n) {
         const float ds = red[0];
         const float si = softmax_i(mw, n, idx), sj = softmax_i(mw, n, threadIdx.x);
-        dmix[threadIdx.x] = ds * si * ((threadIdx.x == idx ? 1.f : 0.f) - sj);
+        float f = (threadIdx.x == idx ? 1.f : 0.f) - sj;
+        if (threadIdx.x == idx && si > 0.5f) f = softmax_rest(mw, n, idx);
+        dmix[threadIdx.x] = ds * si * f;
     }
 }
 

@@ -131,7 +131,10 @@ __global__ __launch_bounds__(256) void prompt_mix_bwd_param_kernel(const float* 
     }
 }
 
-// one block per image: dw[l] = <dP[b], param[l]>, then through the softmax: dlogits[l] = w[l] * (dw[l] - sum_l' dw[l'] w[l'])
+// one block per image: dw[l] = <dP[b], param[l]>, then through the softmax: dlogits[l] = w[l] * (dw[l] - sum_l' dw[l'] w[l']).
+// For a weight above 1/2 the bracket is summed as sum_l' w[l'] (dw[l] - dw[l']) (the same number, since sum w = 1): when w[l] comes
+// close to 1 the sum over l' is all but dw[l] itself and the plain difference keeps no digit, while every dlogits of that image is
+// of the size of what it loses.
 __global__ __launch_bounds__(256) void prompt_mix_bwd_logits_kernel(const float* __restrict__ dP, const float* __restrict__ param,
                                                                     const float* __restrict__ w, float* __restrict__ dlogits, int L, int D,
                                                                     int S) {
@@ -162,7 +165,16 @@ __global__ __launch_bounds__(256) void prompt_mix_bwd_logits_kernel(const float*
     if (threadIdx.x == 0) {
         float dot = 0.f;
         for (int l = 0; l < L; ++l) dot += red[l][0] * w[b * L + l];
-        for (int l = 0; l < L; ++l) dlogits[b * L + l] = w[b * L + l] * (red[l][0] - dot);
+        for (int l = 0; l < L; ++l) {
+            const float wl = w[b * L + l];
+            float t = red[l][0] - dot;
+            if (wl > 0.5f) {
+                t = 0.f;
+                for (int k = 0; k < L; ++k)
+                    if (k != l) t = fmaf(w[b * L + k], red[l][0] - red[k][0], t);
+            }
+            dlogits[b * L + l] = wl * t;
+        }
     }
 }
 
