@@ -195,7 +195,11 @@ OTHER_BLOCKS = [(180, 6, 8, 4, 2, 16, 24),   # default geometry
                 (36, 6, 8, 0, 3, 8, 8),      # hd 6 -> 8, three images inside two row tiles
                 (64, 2, 8, 4, 1, 8, 16),     # hd = 32, no padding anywhere
                 (64, 1, 4, 2, 2, 12, 8),     # hd = 64, N = 16 < NP: the softmax mask is live
-                (56, 2, 7, 3, 1, 14, 21)]    # N = 49, hd 28 -> 32
+                (56, 2, 7, 3, 1, 14, 21),    # N = 49, hd 28 -> 32
+                (40, 1, 5, 1, 1, 10, 5),     # N = 25, hd 40: DP 64 with NP 32
+                (96, 2, 6, 5, 1, 12, 6),     # N = 36, hd 48, one window across
+                (24, 2, 1, 0, 2, 3, 5),      # N = 1
+                (36, 1, 3, 2, 1, 6, 9)]      # N = 9, shift ws - 1
 
 
 @pytest.mark.parametrize("C_,heads,ws,shift,B,H,W", OTHER_BLOCKS)
