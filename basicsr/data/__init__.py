@@ -13,7 +13,7 @@ from torch.utils import data as tdata
 from basicsr.utils import get_root_logger, scandir
 from basicsr.utils.registry import DATASET_REGISTRY
 
-__all__ = ["build_dataset", "build_dataloader", "paired_random_crop_augment", "degrade_collate"]
+__all__ = ["build_dataset", "build_dataloader", "paired_random_crop_augment", "degrade_collate", "filter2d_host"]
 _IMG_EXT = (".png", ".jpg", ".jpeg", ".bmp", ".tif", ".tiff", ".PNG", ".JPG")
 
 
@@ -438,6 +438,115 @@ class PairedImageInpaintingDataset(_GTFolderDataset):
         return _labelled(sample, self.opt)
 
 
+BLUR_MAX_K = 51   # the largest kernel of dcpt_filter2d_fwd
+
+
+def filter2d_host(gt, kernel):
+    """``dcpt_amd.functional.filter2d(gt[None], kernel[None])[0]`` on the host, in numpy float64 with the kernel's tap order
+    (include/dcpt_hip.h dcpt_filter2d_fwd): the image reflect-padded by K // 2, one accumulator per output, ``acc += kernel[dy][dx] *
+    xpad[.. + dy][.. + dx]`` for dy outer and dx inner, both ascending, rounded once to fp32.  A product of two fp32 values is exact in
+    float64, so the multiply-add rounds where the kernel's fused one does and the result equals the kernel's bit for bit.  ``gt``:
+    (C, H, W) float32 tensor or array, ``kernel``: (K, K), K odd, 1..51, K // 2 < H and W; returns (C, H, W) float32 of gt's kind."""
+    as_tensor = torch.is_tensor(gt)
+    x = (gt.detach().cpu().numpy() if as_tensor else np.asarray(gt)).astype(np.float32, copy=False)
+    k = (kernel.detach().cpu().numpy() if torch.is_tensor(kernel) else np.asarray(kernel)).astype(np.float32, copy=False)
+    if x.ndim != 3 or k.ndim != 2 or k.shape[0] != k.shape[1]:
+        raise ValueError(f"filter2d_host takes a (C, H, W) image and a (K, K) kernel, got {x.shape} and {k.shape}")
+    K, (_, h, w) = k.shape[0], x.shape
+    if K % 2 == 0 or not 1 <= K <= BLUR_MAX_K:
+        raise ValueError(f"the blur kernel size must be odd and lie in 1..{BLUR_MAX_K}, got {K}")
+    if K // 2 >= h or K // 2 >= w:
+        raise ValueError(f"the reflect padding K // 2 = {K // 2} must be smaller than the image, got ({h}, {w})")
+    r = K // 2
+    p = np.pad(x.astype(np.float64), ((0, 0), (r, r), (r, r)), mode="reflect")
+    k = k.astype(np.float64)
+    acc = np.zeros(x.shape, dtype=np.float64)
+    for dy in range(K):
+        for dx in range(K):
+            acc += k[dy, dx] * p[:, dy:dy + h, dx:dx + w]
+    out = acc.astype(np.float32)
+    return torch.from_numpy(out) if as_tensor else out
+
+
+@DATASET_REGISTRY.register()
+class PairedImageBlurDataset(_GTFolderDataset):
+    """GT folder + on-the-fly synthetic blur: ``lq`` is ``gt`` filtered with a random kernel of the reference's blur toolbox
+    (basicsr/data/degradations.py ``random_mixed_kernels`` / ``circular_lowpass_kernel``, the first-order blur of its Real-ESRGAN data sets).
+    Options: ``dataroot_gt``, ``gt_size`` (default 128), ``use_hflip``, ``use_rot``, ``center_crop``; ``blur_kernel_size`` (odd, 3..51,
+    default 21); ``kernel_list`` (default all six kinds), ``kernel_prob`` (default uniform), ``blur_sigma`` (default [0.2, 3]),
+    ``betag_range`` (default [0.5, 4]), ``betap_range`` (default [1, 2]); ``sinc_prob`` (default 0); ``blur_backend``; ``kernel_seed``.
+
+    After the crop and the augmentation, with probability ``sinc_prob`` (one ``uniform`` draw of ``np.random``, made only when
+    ``sinc_prob`` > 0) the kernel is ``circular_lowpass_kernel(uniform(pi / 3, pi), K)``, otherwise ``random_mixed_kernels(kernel_list,
+    kernel_prob, K, blur_sigma, blur_sigma, [-pi, pi], betag_range, betap_range, noise_range=None)``; it is cast to fp32.  The draws come
+    from the process-wide ``random`` / ``np.random``; with ``kernel_seed: k`` (an extension, the idea of ``stroke_seed``) image ``index``
+    draws from ``(random.Random(k + index), np.random.RandomState(k + index))`` of its own, so a validation set sees the same blur on
+    every visit.
+
+    ``blur_backend: host`` (default): ``lq = filter2d_host(gt, kernel)`` in the worker, equal to the device result bit for bit.
+    ``blur_backend: device``: the sample carries ``gt``, ``blur_kernel`` ((K, K) fp32) and the paths, and no ``lq``; the model's
+    ``feed_data`` makes ``lq`` with ``dcpt_amd.functional.filter2d(gt, blur_kernel)``."""
+
+    KINDS = ("iso", "aniso", "generalized_iso", "generalized_aniso", "plateau_iso", "plateau_aniso")
+
+    def __init__(self, opt):
+        super().__init__(opt)
+        self.backend = _backend(opt, "blur_backend")
+        self.K = opt.get("blur_kernel_size", 21)
+        if not isinstance(self.K, int) or self.K % 2 == 0 or not 3 <= self.K <= BLUR_MAX_K:
+            raise ValueError(f"blur_kernel_size must be odd and lie in 3..{BLUR_MAX_K}, got {self.K!r}")
+        self.kernel_list = list(opt.get("kernel_list", self.KINDS))
+        self.kernel_prob = list(opt.get("kernel_prob", [1.0 / len(self.kernel_list)] * len(self.kernel_list)))
+        if not self.kernel_list or not set(self.kernel_list) <= set(self.KINDS):
+            raise ValueError(f"kernel_list holds kinds of {self.KINDS}, got {self.kernel_list}")
+        if len(self.kernel_prob) != len(self.kernel_list) or min(self.kernel_prob) < 0 or sum(self.kernel_prob) <= 0:
+            raise ValueError(f"kernel_prob must hold one non-negative weight per entry of kernel_list, got {self.kernel_prob}")
+        self.blur_sigma = self._range(opt, "blur_sigma", [0.2, 3])
+        self.betag_range = self._range(opt, "betag_range", [0.5, 4])
+        self.betap_range = self._range(opt, "betap_range", [1, 2])
+        self.sinc_prob = float(opt.get("sinc_prob", 0))
+        if not 0 <= self.sinc_prob <= 1:
+            raise ValueError(f"sinc_prob must lie in [0, 1], got {self.sinc_prob}")
+        self.kernel_seed = opt.get("kernel_seed")
+        if opt.get("phase") == "train" and self.gt_size <= self.K // 2:
+            raise ValueError(f"gt_size {self.gt_size} must exceed blur_kernel_size // 2 = {self.K // 2} (the reflect padding of the blur)")
+
+    @staticmethod
+    def _range(opt, key, default):
+        v = opt.get(key, default)
+        if not isinstance(v, (list, tuple)) or len(v) != 2 or not 0 < v[0] < v[1]:
+            raise ValueError(f"{key} must be [low, high] with 0 < low < high, got {v!r}")
+        return [float(v[0]), float(v[1])]
+
+    def blur_kernel(self, index):
+        """the (K, K) fp32 kernel of image ``index``: its own generators under ``kernel_seed``, the process-wide ones otherwise"""
+        import math
+        import random
+
+        from basicsr.data.degradations import circular_lowpass_kernel, random_mixed_kernels
+
+        rng = (random, np.random) if self.kernel_seed is None else (random.Random(self.kernel_seed + index),
+                                                                      np.random.RandomState(self.kernel_seed + index))
+        if self.sinc_prob > 0 and rng[1].uniform() < self.sinc_prob:
+            kernel = circular_lowpass_kernel(rng[1].uniform(math.pi / 3, math.pi), self.K)
+        else:
+            kernel = random_mixed_kernels(self.kernel_list, self.kernel_prob, self.K, self.blur_sigma, self.blur_sigma, [-math.pi, math.pi],
+                                          self.betag_range, self.betap_range, noise_range=None, rng=rng)
+        return torch.from_numpy(kernel.astype(np.float32))
+
+    def __getitem__(self, index):
+        gt, path = self._gt(index)
+        if min(gt.shape[1:]) <= self.K // 2:
+            raise ValueError(f"the image {path} of {tuple(gt.shape[1:])} must exceed blur_kernel_size // 2 = {self.K // 2} in both directions")
+        kernel = self.blur_kernel(index)
+        sample = {"gt": gt, "lq_path": path, "gt_path": path}
+        if self.backend == "device":
+            sample["blur_kernel"] = kernel
+        else:
+            sample["lq"] = filter2d_host(gt, kernel)
+        return _labelled(sample, self.opt)
+
+
 @DATASET_REGISTRY.register()
 class PairedImageDehazeDataset(tdata.Dataset):
     """Hazy folder + GT folder with several hazy images per GT (reference basicsr/data/paired_image_dataset.py:583-729, folder mode, PIL
@@ -470,7 +579,7 @@ class PairedImageDehazeDataset(tdata.Dataset):
 
 # which key makes a sample which kind of a mixed batch (``degrade_kind``), and the keys that kind brings along
 DEGRADE_KINDS = (("lq", ("lq",)), ("noise_sigma", ("noise_sigma", "noise_key")), ("jpeg_quality", ("jpeg_quality",)), ("mosaic", ("mosaic",)),
-                 ("inpaint_meta", ("inpaint_lines", "inpaint_meta")))
+                 ("inpaint_meta", ("inpaint_lines", "inpaint_meta")), ("blur_kernel", ("blur_kernel",)))
 
 
 def degrade_collate(samples):
@@ -478,7 +587,7 @@ def degrade_collate(samples):
     ``default_collate(samples)``.  A batch of a ``ConcatDataset`` over sets with different device backends mixes samples that carry
     different keys, which the default collate refuses; it is collated as: the keys common to all samples (``gt``, the paths,
     ``dataset_idx``) as usual; ``degrade_kind``, an int32 ``[B]`` host tensor: 0 the sample has ``lq``, 1 ``noise_sigma``, 2
-    ``jpeg_quality``, 3 ``mosaic``, 4 ``inpaint_meta``; and each kind's own keys (``lq`` included) stacked over THAT KIND'S samples in
+    ``jpeg_quality``, 3 ``mosaic``, 4 ``inpaint_meta``, 5 ``blur_kernel``; and each kind's own keys (``lq`` included) stacked over THAT KIND'S samples in
     batch order.  ``BaseModel._lq_on_device`` makes the ``lq`` rows of each kind from its ``gt`` rows."""
     from torch.utils.data import default_collate
 
@@ -495,6 +604,10 @@ def degrade_collate(samples):
     shapes = sorted({tuple(s["gt"].shape) for s in samples})
     if len(shapes) != 1:
         raise ValueError(f"the samples of a mixed batch have gt of different sizes {shapes}: give every train set the same gt_size")
+    ksizes = sorted({tuple(s["blur_kernel"].shape) for s in samples if "blur_kernel" in s})
+    if len(ksizes) > 1:
+        raise ValueError(f"the blur samples of a mixed batch have kernels of different sizes {ksizes}: give every blur train set the same "
+                         "blur_kernel_size")
     own = {k for _, ks in DEGRADE_KINDS for k in ks}
     common = set.intersection(*(set(s.keys()) for s in samples)) - own
     loose = set.union(*(set(s.keys()) for s in samples)) - own - common

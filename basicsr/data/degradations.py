@@ -14,14 +14,179 @@ Departures from the reference:
   * ``rounds`` rounds half to even on ``255 v`` like ``torch.round``; with ``clip`` the clamp comes first, which gives the same value as
     the reference's ``clamp(round(255 v), 0, 255) / 255``.
 
-Out of scope: the Poisson family, the blur-kernel generators (``bivariate_*``, ``random_mixed_kernels``, ``circular_lowpass_kernel``),
-``filter2D`` / ``USMSharp``, JPEG compression (see ``dcpt_amd.functional.diffjpeg``) and the numpy forms (``generate_gaussian_noise``,
-``add_gaussian_noise``, ``random_*`` without ``_pt``)."""
+The blur-kernel generators of the reference (:17-479) are here too, on the host in numpy float64 with the reference's names, argument
+lists and defaults: ``sigma_matrix2``, ``mesh_grid``, ``pdf2``, ``cdf2``, ``bivariate_Gaussian``, ``bivariate_generalized_Gaussian``,
+``bivariate_plateau``, their ``random_*`` forms, ``random_mixed_kernels`` and ``circular_lowpass_kernel``.  They make the same draws from
+``random`` and ``np.random`` in the same order as the reference, so a seeded call gives the reference's kernel.  One extension: every
+``random_*`` function takes ``rng=None``, a pair (a ``random.Random``-like object, a ``np.random.RandomState``-like object) used in place
+of the two modules.  The kernels are applied by ``basicsr.utils.filter2D`` (device; ``USMSharp`` is built on it) or
+``basicsr.data.filter2d_host``.
+
+Out of scope: the Poisson family, JPEG compression (see ``dcpt_amd.functional.diffjpeg``) and the numpy forms of the noise functions
+(``generate_gaussian_noise``, ``add_gaussian_noise``, ``random_*`` without ``_pt``)."""
+import math
+import random
+
+import numpy as np
 import torch
 
 from dcpt_amd import functional as DF
 
+# (the star-import list stays the device functions; the host-side blur-kernel generators below are public module attributes, imported by
+# name as the reference's callers do)
 __all__ = ["generate_gaussian_noise_pt", "add_gaussian_noise_pt", "random_generate_gaussian_noise_pt", "random_add_gaussian_noise_pt"]
+
+
+# ---- blur kernels (host, numpy float64) ------------------------------------------------------------------
+def sigma_matrix2(sig_x, sig_y, theta):
+    """the covariance U diag(sig_x^2, sig_y^2) U^T of an axis-aligned Gaussian rotated by ``theta`` (radians)"""
+    c, s = np.cos(theta), np.sin(theta)
+    u = np.array([[c, -s], [s, c]])
+    return np.dot(u, np.dot(np.array([[sig_x ** 2, 0], [0, sig_y ** 2]]), u.T))
+
+
+def mesh_grid(kernel_size):
+    """the grid centred at zero: ``xy`` (K, K, 2) with xy[i, j] = (x_j, y_i), and ``xx``, ``yy`` (K, K)"""
+    ax = np.arange(-kernel_size // 2 + 1.0, kernel_size // 2 + 1.0)
+    xx, yy = np.meshgrid(ax, ax)
+    return np.stack((xx, yy), axis=2), xx, yy
+
+
+def _quadratic_form(sigma_matrix, grid):
+    """g^T Sigma^-1 g at every grid point g"""
+    return np.sum(np.dot(grid, np.linalg.inv(sigma_matrix)) * grid, 2)
+
+
+def pdf2(sigma_matrix, grid):
+    """the un-normalised bivariate Gaussian density exp(-g^T Sigma^-1 g / 2) on the grid"""
+    return np.exp(-0.5 * _quadratic_form(sigma_matrix, grid))
+
+
+def cdf2(d_matrix, grid):
+    """the CDF of the standard bivariate normal at ``grid @ d_matrix`` (the skew of a skewed Gaussian); needs scipy"""
+    from scipy.stats import multivariate_normal
+
+    return multivariate_normal([0, 0], [[1, 0], [0, 1]]).cdf(np.dot(grid, d_matrix))
+
+
+def _sigma(sig_x, sig_y, theta, isotropic):
+    return np.array([[sig_x ** 2, 0], [0, sig_x ** 2]]) if isotropic else sigma_matrix2(sig_x, sig_y, theta)
+
+
+def bivariate_Gaussian(kernel_size, sig_x, sig_y, theta, grid=None, isotropic=True):
+    """the normalised Gaussian kernel; ``isotropic`` uses ``sig_x`` alone"""
+    if grid is None:
+        grid, _, _ = mesh_grid(kernel_size)
+    kernel = pdf2(_sigma(sig_x, sig_y, theta, isotropic), grid)
+    return kernel / np.sum(kernel)
+
+
+def bivariate_generalized_Gaussian(kernel_size, sig_x, sig_y, theta, beta, grid=None, isotropic=True):
+    """the normalised generalised Gaussian exp(-(g^T Sigma^-1 g)^beta / 2); beta = 1 is the Gaussian"""
+    if grid is None:
+        grid, _, _ = mesh_grid(kernel_size)
+    kernel = np.exp(-0.5 * np.power(_quadratic_form(_sigma(sig_x, sig_y, theta, isotropic), grid), beta))
+    return kernel / np.sum(kernel)
+
+
+def bivariate_plateau(kernel_size, sig_x, sig_y, theta, beta, grid=None, isotropic=True):
+    """the normalised plateau kernel 1 / ((g^T Sigma^-1 g)^beta + 1)"""
+    if grid is None:
+        grid, _, _ = mesh_grid(kernel_size)
+    kernel = np.reciprocal(np.power(_quadratic_form(_sigma(sig_x, sig_y, theta, isotropic), grid), beta) + 1)
+    return kernel / np.sum(kernel)
+
+
+def _generators(rng):
+    return (random, np.random) if rng is None else rng
+
+
+def _draw_shape(nr, kernel_size, sigma_x_range, sigma_y_range, rotation_range, isotropic):
+    """sigma_x, then (anisotropic only) sigma_y and the rotation, each one ``uniform`` of the numpy generator"""
+    assert kernel_size % 2 == 1, "Kernel size must be an odd number."
+    assert sigma_x_range[0] < sigma_x_range[1], "Wrong sigma_x_range."
+    sigma_x = nr.uniform(sigma_x_range[0], sigma_x_range[1])
+    if isotropic is False:
+        assert sigma_y_range[0] < sigma_y_range[1], "Wrong sigma_y_range."
+        assert rotation_range[0] < rotation_range[1], "Wrong rotation_range."
+        return sigma_x, nr.uniform(sigma_y_range[0], sigma_y_range[1]), nr.uniform(rotation_range[0], rotation_range[1])
+    return sigma_x, sigma_x, 0
+
+
+def _draw_beta(nr, beta_range):
+    """one draw picks the side of 1, a second the value on it (the range is taken to straddle 1)"""
+    if nr.uniform() < 0.5:
+        return nr.uniform(beta_range[0], 1)
+    return nr.uniform(1, beta_range[1])
+
+
+def _noisy(nr, kernel, noise_range):
+    """multiplicative noise, one uniform draw per entry, and the final normalisation"""
+    if noise_range is not None:
+        assert noise_range[0] < noise_range[1], "Wrong noise range."
+        kernel = kernel * nr.uniform(noise_range[0], noise_range[1], size=kernel.shape)
+    return kernel / np.sum(kernel)
+
+
+def random_bivariate_Gaussian(kernel_size, sigma_x_range, sigma_y_range, rotation_range, noise_range=None, isotropic=True, rng=None):
+    nr = _generators(rng)[1]
+    sigma_x, sigma_y, rotation = _draw_shape(nr, kernel_size, sigma_x_range, sigma_y_range, rotation_range, isotropic)
+    return _noisy(nr, bivariate_Gaussian(kernel_size, sigma_x, sigma_y, rotation, isotropic=isotropic), noise_range)
+
+
+def random_bivariate_generalized_Gaussian(kernel_size, sigma_x_range, sigma_y_range, rotation_range, beta_range, noise_range=None,
+                                          isotropic=True, rng=None):
+    nr = _generators(rng)[1]
+    sigma_x, sigma_y, rotation = _draw_shape(nr, kernel_size, sigma_x_range, sigma_y_range, rotation_range, isotropic)
+    beta = _draw_beta(nr, beta_range)
+    return _noisy(nr, bivariate_generalized_Gaussian(kernel_size, sigma_x, sigma_y, rotation, beta, isotropic=isotropic), noise_range)
+
+
+def random_bivariate_plateau(kernel_size, sigma_x_range, sigma_y_range, rotation_range, beta_range, noise_range=None, isotropic=True,
+                             rng=None):
+    nr = _generators(rng)[1]
+    sigma_x, sigma_y, rotation = _draw_shape(nr, kernel_size, sigma_x_range, sigma_y_range, rotation_range, isotropic)
+    beta = _draw_beta(nr, beta_range)
+    return _noisy(nr, bivariate_plateau(kernel_size, sigma_x, sigma_y, rotation, beta, isotropic=isotropic), noise_range)
+
+
+def random_mixed_kernels(kernel_list, kernel_prob, kernel_size=21, sigma_x_range=(0.6, 5), sigma_y_range=(0.6, 5),
+                         rotation_range=(-math.pi, math.pi), betag_range=(0.5, 8), betap_range=(0.5, 8), noise_range=None, rng=None):
+    """one kernel of a type drawn from ``kernel_list`` with the weights ``kernel_prob`` (``random.choices``): ``iso``, ``aniso``,
+    ``generalized_iso``, ``generalized_aniso``, ``plateau_iso``, ``plateau_aniso``.  As in the reference the plateau kernels take no
+    multiplicative noise, and an unknown type is an error here (the reference fails on the unbound result)."""
+    kernel_type = _generators(rng)[0].choices(kernel_list, kernel_prob)[0]
+    family, _, shape = kernel_type.rpartition("_")
+    if shape not in ("iso", "aniso") or family not in ("", "generalized", "plateau"):
+        raise ValueError(f"unknown kernel type {kernel_type!r}")
+    common = (kernel_size, sigma_x_range, sigma_y_range, rotation_range)
+    if family == "":
+        return random_bivariate_Gaussian(*common, noise_range=noise_range, isotropic=shape == "iso", rng=rng)
+    if family == "generalized":
+        return random_bivariate_generalized_Gaussian(*common, betag_range, noise_range=noise_range, isotropic=shape == "iso", rng=rng)
+    return random_bivariate_plateau(*common, betap_range, noise_range=None, isotropic=shape == "iso", rng=rng)
+
+
+def circular_lowpass_kernel(cutoff, kernel_size, pad_to=0):
+    """the normalised 2-D sinc (jinc) filter cutoff J1(cutoff d) / (2 pi d) at distance d from the centre, cutoff^2 / (4 pi) at it;
+    ``cutoff`` in radians (pi is the maximum), ``pad_to`` an odd size to zero-pad to (0: none); needs scipy"""
+    from scipy import special
+
+    assert kernel_size % 2 == 1, "Kernel size must be an odd number."
+    mid = (kernel_size - 1) / 2
+    ii, jj = np.indices((kernel_size, kernel_size), dtype=float)
+    d = np.sqrt((ii - mid) ** 2 + (jj - mid) ** 2)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        kernel = cutoff * special.j1(cutoff * d) / (2 * np.pi * d)
+    kernel[(kernel_size - 1) // 2, (kernel_size - 1) // 2] = cutoff ** 2 / (4 * np.pi)
+    kernel = kernel / np.sum(kernel)
+    if pad_to > kernel_size:
+        pad = (pad_to - kernel_size) // 2
+        kernel = np.pad(kernel, ((pad, pad), (pad, pad)))
+    return kernel
+
+
+# ---- Gaussian noise (device) --------------------------------------------------------------------------------
 
 
 def _keys(b, key):

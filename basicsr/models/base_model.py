@@ -39,7 +39,8 @@ class BaseModel:
         batch of a ``demosaic_backend: device`` set (PairedImageMosaicDataset: ``gt`` and ``mosaic``, the method's index) from the demosaic
         kernel, and a batch of an ``inpaint_backend: device`` set (PairedImageInpaintingDataset: ``gt``, ``inpaint_lines``,
         ``inpaint_meta``) from the line-mask kernel, and a batch of a ``noise_backend: device`` set (PairedImageDenoiseDataset: ``gt``,
-        ``noise_sigma``, ``noise_key``) from the Philox noise kernel, unclipped like the host path.  A mixed batch
+        ``noise_sigma``, ``noise_key``) from the Philox noise kernel, unclipped like the host path, and a batch of a ``blur_backend: device``
+        set (PairedImageBlurDataset: ``gt`` and ``blur_kernel``, one (K, K) kernel per image) from the blur kernel.  A mixed batch
         (``basicsr.data.degrade_collate``: ``degrade_kind`` per sample, each kind's keys stacked over its own samples) gets every kind's rows
         from that kind's op on its ``gt`` rows"""
         if "degrade_kind" in data:
@@ -59,6 +60,9 @@ class BaseModel:
         if "lq" not in data and "inpaint_meta" in data:
             gt = data["gt"].to(self.device, non_blocking=True)
             return DF.inpaint_lines(gt, data["inpaint_lines"], data["inpaint_meta"])
+        if "lq" not in data and "blur_kernel" in data:
+            gt = data["gt"].to(self.device, non_blocking=True)
+            return DF.filter2d(gt, data["blur_kernel"])
         return data["lq"].to(self.device, non_blocking=True)
 
     def _lq_mixed(self, data):
@@ -67,8 +71,8 @@ class BaseModel:
         grouped by method, so one batch may hold both."""
         gt = data["gt"].to(self.device, non_blocking=True)
         kind = data["degrade_kind"].reshape(-1).tolist()
-        if len(kind) != gt.shape[0] or not set(kind) <= set(range(5)):
-            raise ValueError(f"degrade_kind must hold one of 0..4 for each of the {gt.shape[0]} images, got {kind}")
+        if len(kind) != gt.shape[0] or not set(kind) <= set(range(6)):
+            raise ValueError(f"degrade_kind must hold one of 0..5 for each of the {gt.shape[0]} images, got {kind}")
         lq = torch.empty_like(gt)
 
         def put(rows, op):
@@ -89,8 +93,10 @@ class BaseModel:
                     raise ValueError(f"mosaic holds 0 (malvar) or 1 (bilinear) for each demosaic image; got {methods}")
                 for m in sorted(set(methods)):
                     put([r for r, v in zip(rows, methods) if v == m], lambda g, m=m: DF.demosaic(g, DF.DEMOSAIC_METHODS[m], uint8_io=True))
-            else:
+            elif k == 4:
                 put(rows, lambda g: DF.inpaint_lines(g, data["inpaint_lines"], data["inpaint_meta"]))
+            else:
+                put(rows, lambda g: DF.filter2d(g, data["blur_kernel"]))
         return lq
 
     def optimize_parameters(self, current_iter):

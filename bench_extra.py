@@ -2,7 +2,7 @@
 """Secondary workloads of BASELINE.json (configs[2..4]) on ONE MI355X -- evidence for DESIGN.md, not the driver's
 contract (that is bench.py).  Prints one JSON line per workload.
 
-    python bench_extra.py --workload dcpt|dcpt_swinir|restormer|promptir|infer2k|naf|swinir|rcan|val_metrics|step_tail|tlsc|ssim_loss|ldl|jpeg|niqe|degrade|noise [--dtype fp32|bf16|bf16_res32] [--steps K] [--warmup W]
+    python bench_extra.py --workload dcpt|dcpt_swinir|restormer|promptir|infer2k|naf|swinir|rcan|val_metrics|step_tail|tlsc|ssim_loss|ldl|jpeg|niqe|degrade|noise|blur [--dtype fp32|bf16|bf16_res32] [--steps K] [--warmup W]
 
 ``--dtype bf16`` (dcpt, naf, infer2k, restormer, promptir; rcan: the inference line only, next to fp32; swinir: the restoration form's inference, next to fp32): every feature map of the encoder in bf16 storage with fp32 accumulation (act_dtype="bf16";
 dcpt: the classifier head too unless --head-dtype fp32); images, parameters and the optimizer stay fp32.  Its lines carry BOTH
@@ -1020,6 +1020,90 @@ def run_noise(dev, steps=20, warmup=3, B=32, S=256):
     return [first, second]
 
 
+def run_blur(dev, steps=20, warmup=3, B=32, S=256, K=21):
+    """Synthetic blur of a B x 3 x S x S batch with one K x K kernel per image (dcpt_amd/csrc/blur.hip): ``dcpt_amd.functional.filter2d``
+    against the reference's form on the same device (``F.pad(mode="reflect")`` plus ``F.conv2d`` with B * 3 groups and the kernels repeated
+    over the channels), the two alternating call by call in one process, device events around each call, each route's peak memory above what
+    is resident between calls; ``USMSharp`` at radius 50 (two 51 x 51 blurs and the element-wise steps) the same way on its own; and
+    ``basicsr.data.filter2d_host`` over the B images on one host thread (one pass).  One result line.  The fp64 rate counts the kernel's
+    own 2 K^2 B C H W flops over its fastest call."""
+    import statistics
+    import time
+
+    import torch.nn.functional as F
+
+    from basicsr.data import filter2d_host
+    from basicsr.data.degradations import random_mixed_kernels
+    from basicsr.utils import USMSharp
+    from dcpt_amd import functional as DF
+
+    import random
+
+    import numpy as np
+
+    g = torch.Generator(device=dev).manual_seed(1234)
+    low = torch.rand((B, 3, S // 8, S // 8), generator=g, device=dev)
+    x = (F.interpolate(low, size=(S, S), mode="bilinear", align_corners=False) + 0.05 * torch.randn((B, 3, S, S), generator=g, device=dev)).clamp(0, 1)
+    rng = (random.Random(77), np.random.RandomState(77))
+    kinds = ["iso", "aniso", "generalized_iso", "generalized_aniso", "plateau_iso", "plateau_aniso"]
+    kern_host = torch.from_numpy(np.stack([random_mixed_kernels(kinds, [1 / 6] * 6, K, (0.2, 3), (0.2, 3), rng=rng) for _ in range(B)]).astype(np.float32))
+    kern = kern_host.to(dev)
+
+    def torch_route():
+        r = K // 2
+        p = F.pad(x, (r, r, r, r), mode="reflect")
+        w = kern.view(B, 1, K, K).repeat(1, 3, 1, 1).view(B * 3, 1, K, K)
+        return F.conv2d(p.view(1, B * 3, S + 2 * r, S + 2 * r), w, groups=B * 3).view(B, 3, S, S)
+
+    def measure(routes):
+        peaks, last, times = {}, {}, {n: [] for n in routes}
+        with torch.no_grad():
+            for i in range(warmup + steps):
+                for n, fn in routes.items():
+                    torch.cuda.synchronize(dev)
+                    base = torch.cuda.memory_allocated(dev)
+                    torch.cuda.reset_peak_memory_stats(dev)
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    last[n] = fn()
+                    e1.record()
+                    e1.synchronize()
+                    peaks[n] = max(peaks.get(n, 0), torch.cuda.max_memory_allocated(dev) - base)
+                    if i >= warmup:
+                        times[n].append(e0.elapsed_time(e1))
+        return peaks, last, times
+
+    peaks, last, times = measure({"kernel": lambda: DF.filter2d(x, kern), "torch": torch_route})
+    diff = float((last["kernel"].double() - last["torch"].double()).abs().max())
+    usm = USMSharp(50).to(dev)
+    upeaks, _, utimes = measure({"usm": lambda: usm(x)})
+    xh = x.cpu()
+    t0 = time.perf_counter()
+    host0 = None
+    for i in range(B):
+        lq = filter2d_host(xh[i], kern_host[i])
+        host0 = lq if host0 is None else host0
+    host_ms = (time.perf_counter() - t0) * 1e3
+    same = bool(torch.equal(host0.view(torch.int32), last["kernel"][0].cpu().view(torch.int32)))
+    kmin, umin = min(times["kernel"]), min(utimes["usm"])
+    flops = 2.0 * K * K * x.numel()
+    return dict(workload=f"synthetic blur, {B} x 3 x {S} x {S}, one {K} x {K} kernel per image: filter2D",
+                kernel_ms_median=round(statistics.median(times["kernel"]), 4), kernel_ms_min=round(kmin, 4),
+                torch_ms_median=round(statistics.median(times["torch"]), 4), torch_ms_min=round(min(times["torch"]), 4),
+                ratio_median=round(statistics.median(times["torch"]) / statistics.median(times["kernel"]), 2),
+                kernel_fp64_tflops_at_min=round(flops / (kmin * 1e-3) / 1e12, 2),
+                kernel_peak_mb=round(peaks["kernel"] / 1e6, 1), torch_peak_mb=round(peaks["torch"] / 1e6, 1),
+                kernel_vs_torch_max_abs=float(f"{diff:.3e}"), host_row0_bit_identical=same,
+                usm_radius50_ms_median=round(statistics.median(utimes["usm"]), 4), usm_radius50_ms_min=round(umin, 4),
+                usm_fp64_tflops_at_min=round(2 * 2.0 * 51 * 51 * x.numel() / (umin * 1e-3) / 1e12, 2), usm_peak_mb=round(upeaks["usm"] / 1e6, 1),
+                host_ms=round(host_ms, 1), host_ms_per_image=round(host_ms / B, 2), calls=steps, warmup=warmup,
+                note="device events around each call (the op's host side included), filter2d and the torch form (F.pad reflect + F.conv2d "
+                     "with B * C groups, the kernels repeated over the channels) alternating in one process; peak memory of a call above "
+                     "what is allocated between calls; kernel_fp64_tflops_at_min = 2 K^2 B C H W flops over the fastest call (the usm figure "
+                     "counts its two 51 x 51 blurs over the whole forward, element-wise steps included); host_ms is filter2d_host (numpy "
+                     "float64, the kernel's tap order) over the B images on one thread, one pass")
+
+
 def run_niqe(dev, steps=20, warmup=3, H=1080, W=2048):
     """NIQE of one 1 x 3 x H x W image (a smooth random field plus fine noise, no flat block): the host ``calculate_niqe`` (numpy float64,
     one thread's wall time, best of 2) against ``calculate_niqe_device`` (the fused fp64 kernels of dcpt_amd/csrc/niqe.hip + the host
@@ -1070,7 +1154,7 @@ def run_niqe(dev, steps=20, warmup=3, H=1080, W=2048):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", required=True, choices=["dcpt", "dcpt_swinir", "restormer", "promptir", "infer2k", "naf", "swinir", "rcan", "val_metrics", "step_tail", "tlsc", "ssim_loss", "ldl", "jpeg", "niqe", "degrade", "noise"])
+    ap.add_argument("--workload", required=True, choices=["dcpt", "dcpt_swinir", "restormer", "promptir", "infer2k", "naf", "swinir", "rcan", "val_metrics", "step_tail", "tlsc", "ssim_loss", "ldl", "jpeg", "niqe", "degrade", "noise", "blur"])
     ap.add_argument("--dtype", default="fp32", choices=["fp32", "bf16", "bf16_tail32", "bf16_edge32", "bf16_res32"])
     ap.add_argument("--head-dtype", default=None, choices=["fp32", "bf16"], help="dcpt: classifier-head activations (default: --dtype)")
     ap.add_argument("--restormer-save", default="balanced", choices=["auto", "lean", "balanced", "full"], help="what the Restormer halves keep for backward")
@@ -1276,6 +1360,8 @@ def main():
         lines = run_noise(dev, max(args.steps, 20), max(args.warmup, 3), args.batch or 32, args.size or 256)
         print(json.dumps(lines[0]), flush=True)
         res = lines[1]
+    elif args.workload == "blur":
+        res = run_blur(dev, max(args.steps, 20), max(args.warmup, 3), args.batch or 32, args.size or 256)
     elif args.workload == "tlsc":
         res = run_tlsc(dev, args.steps, args.warmup, tile=args.tile, streams=args.tile_streams)
     else:

@@ -541,3 +541,20 @@ extern "C" int dcpt_gauss_noise_fwd(const float* x, const float* sigma, const lo
     DCPT_CHECK_ARG((int64_t)B <= ((int64_t)1 << 40) / ((int64_t)C * H * W), "gauss_noise_fwd: a batch above 2^40 elements (B=%d)", B);
     return launch_gauss_noise_fwd(x, sigma, key, gray, y, B, C, H, W, flags, (hipStream_t)stream);
 }
+
+// ---------------------------------------------------------------------------------------------
+// Synthetic blur: a K x K correlation per image under reflect padding (blur.hip)
+extern "C" int dcpt_filter2d_fwd(const float* x, const float* kern, float* y, int B, int C, int H, int W, int K, int kern_per_image,
+                                 dcpt_stream_t stream) {
+    DCPT_CHECK_ARG(x && kern && y, "filter2d_fwd: null argument");
+    DCPT_CHECK_ARG(B >= 1 && C >= 1 && H >= 1 && W >= 1, "filter2d_fwd: bad shape (B=%d C=%d H=%d W=%d)", B, C, H, W);
+    DCPT_CHECK_ARG(K >= 1 && K <= 51 && (K & 1) == 1, "filter2d_fwd: K must be odd and lie in 1..51 (got %d)", K);
+    DCPT_CHECK_ARG(K / 2 < H && K / 2 < W, "filter2d_fwd: the reflect padding K / 2 = %d must be smaller than H and W (H=%d W=%d)", K / 2, H, W);
+    const int64_t tiles = cdiv64(W, 64) * cdiv64(H, 32);   // (blur.hip: one workgroup per 32 x 64 tile of a plane, a one-dimensional grid)
+    DCPT_CHECK_ARG((int64_t)B * C <= (int64_t)0x7fffffff / tiles, "filter2d_fwd: more than 2^31 - 1 tiles of 32 x 64 (B=%d C=%d H=%d W=%d)", B, C,
+                   H, W);
+    const uintptr_t xa = (uintptr_t)x, ya = (uintptr_t)y;
+    const uint64_t bytes = (uint64_t)B * C * H * W * sizeof(float);   // (below 2^31 * 2048 * 4)
+    DCPT_CHECK_ARG(xa + bytes <= ya || ya + bytes <= xa, "filter2d_fwd: y overlaps x (a tile reads its neighbours' pixels: not in place)");
+    return launch_filter2d_fwd(x, kern, y, B, C, H, W, K, kern_per_image != 0, (hipStream_t)stream);
+}

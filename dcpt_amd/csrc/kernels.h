@@ -230,3 +230,8 @@ int launch_inpaint_lines_fwd(const float* x, const int* lines, const int* meta, 
 // device; x may be null with DCPT_NOISE_ONLY; in place allowed); one launch, no workspace.
 int launch_gauss_noise_fwd(const float* x, const float* sigma, const long long* key, const int* gray, float* y, int B, int C, int H, int W,
                            int flags, hipStream_t s);
+
+// ---- blur.hip -------------------------------------------------------------------------------
+// The K x K correlation of every plane with its image's kernel under reflect padding (dcpt_filter2d_fwd: kern fp32 [B][K][K], or [1][K][K]
+// with per_image == 0; K odd, 1..51, K / 2 < H, W); fp64 accumulation in the tap order of the header; one launch, no workspace.
+int launch_filter2d_fwd(const float* x, const float* kern, float* y, int B, int C, int H, int W, int K, int per_image, hipStream_t s);

@@ -3082,6 +3082,43 @@ def gaussian_noise(x, sigma, key, gray=None, clip=False, rounds=False, noise_onl
 
 
 # ------------------------------------------------------------------------------------------------
+# Synthetic blur (include/dcpt_hip.h dcpt_filter2d_fwd): the reference's filter2D (basicsr/utils/img_process_util.py:7-31) as one launch,
+# without the padded copy of the batch and the weight repeated over the channels.
+FILTER2D_MAX_K = 51
+
+
+def filter2d(x, kernel):
+    """The K x K correlation (no flip, as ``F.conv2d``) of every channel of image b with ``kernel[b]`` over the image reflect-padded by
+    K // 2: ``x`` (B, C, H, W) fp32 device tensor (any strides: it is made contiguous NCHW); ``kernel`` (B, K, K), or (1, K, K) for one
+    kernel shared by the batch, any float dtype on any device (it is copied to fp32 on x's device); K odd, 1..51, K // 2 < H and W.
+    Returns a new fp32 NCHW tensor.  Each output is one fp64 sum over the taps, rows outer and columns inner, rounded once to fp32
+    (the header states it; ``basicsr.data.filter2d_host`` gives the same bits on the host).  Forward only."""
+    if not torch.is_tensor(x):
+        raise _lib.DcptHipError(f"filter2d takes a device tensor (got {type(x).__name__})")
+    _require_gpu(x)
+    if x.dim() != 4 or 0 in x.shape:
+        raise ValueError(f"filter2d: expected a non-empty (B, C, H, W) batch, got {tuple(x.shape)}")
+    B, C, H, W = x.shape
+    if not torch.is_tensor(kernel) or not kernel.is_floating_point() or kernel.dim() != 3 or kernel.shape[1] != kernel.shape[2] \
+            or kernel.shape[0] not in (1, B):
+        raise ValueError(f"filter2d: kernel must be a float ({B}, K, K) or (1, K, K) tensor, got "
+                         f"{tuple(kernel.shape) if torch.is_tensor(kernel) else type(kernel).__name__}")
+    K = kernel.shape[-1]
+    if K % 2 == 0 or not 1 <= K <= FILTER2D_MAX_K:
+        raise ValueError(f"filter2d: K must be odd and lie in 1..{FILTER2D_MAX_K}, got a kernel of {tuple(kernel.shape)}")
+    if K // 2 >= H or K // 2 >= W:
+        raise ValueError(f"filter2d: the reflect padding K // 2 = {K // 2} must be smaller than H and W, got x {tuple(x.shape)} and a "
+                         f"kernel of {tuple(kernel.shape)}")
+    _inference_only("filter2d", x, kernel, what="the blur")
+    dev = x.device
+    kernel = kernel.detach().to(device=dev, dtype=torch.float32, non_blocking=True).contiguous()
+    x = x.detach().contiguous()
+    y = torch.empty_like(x)
+    _call(_lib.load().dcpt_filter2d_fwd, (x, kernel, y), (B, C, H, W, K, int(kernel.shape[0] != 1)), dev)
+    return y
+
+
+# ------------------------------------------------------------------------------------------------
 # MATLAB-bicubic resize and the pixel work of NIQE (include/dcpt_hip.h dcpt_imresize_fwd, dcpt_niqe_mscn_fwd, dcpt_niqe_block_stats_fwd):
 # the reference's basicsr/utils/matlab_functions.py::imresize and the per-pixel part of basicsr/metrics/niqe.py in fp64.  Forward only.
 IMRESIZE_X_F64, IMRESIZE_Y_F64, IMRESIZE_QUANT8 = 1, 2, 4   # include/dcpt_hip.h DCPT_IMRESIZE_*

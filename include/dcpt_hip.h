@@ -996,6 +996,26 @@ int dcpt_inpaint_lines_fwd(const float* x, const int* lines, const int* meta, fl
 int dcpt_gauss_noise_fwd(const float* x, const float* sigma, const long long* key, const int* gray, float* y, int B, int C, int H, int W,
                          int flags, dcpt_stream_t stream);
 
+/* ---- on-the-fly degradations: synthetic blur, on the device -----------------------------------------------------
+ * dcpt_filter2d_fwd replaces filter2D of basicsr/utils/img_process_util.py:7-31 (F.pad(mode="reflect") plus F.conv2d with B * C groups,
+ * which materialises the padded batch and a weight repeated over the channels), the blur of USMSharp.forward (:73-82) with it.
+ *   x      dense NCHW fp32 [B][C][H][W]
+ *   kern   fp32 [B][K][K] when kern_per_image != 0, else [1][K][K] shared by the batch; every channel of an image uses its image's kernel
+ *   y      dense NCHW fp32 [B][C][H][W]; must not overlap x (an output reads its neighbours' pixels)
+ * A correlation, no flip, as F.conv2d, over the image reflect-padded by r = K / 2: index -i reads i and H - 1 + i reads H - 1 - i (the edge
+ * sample is not repeated):
+ *     y[b][c][i][j] = sum over dy, dx in 0 .. K - 1 of kern[b][dy][dx] * xpad[b][c][i + dy][j + dx],  xpad[p][q] = x[refl(p - r)][refl(q - r)]
+ * Arithmetic, per output: acc = 0.0 (double); for dy = 0 .. K - 1 (outer), for dx = 0 .. K - 1 (inner), both ascending:
+ *     acc = fma((double)kern[b][dy][dx], (double)xpad[..], acc);     y = (float)acc, the one fp32 rounding.
+ * The product of two fp32 values is exact in fp64, so a step rounds once whether it is a fused multiply-add or a multiply and an add, and
+ * the sum has ONE value: a host loop of plain float64 multiply-adds in that order (basicsr.data.filter2d_host) gives the same bits.  The
+ * sum is not split over lanes, rows or partial accumulators.
+ * One launch, no workspace, no atomics, no host synchronisation; the same input gives the same bits.
+ * Errors (before the launch): null pointers; B, C, H or W below 1; K even, below 1 or above 51; K / 2 >= H or K / 2 >= W (torch's reflect
+ * padding refuses it too); y overlapping x; more than 2^31 - 1 tiles of 32 x 64 in the batch. */
+int dcpt_filter2d_fwd(const float* x, const float* kern, float* y, int B, int C, int H, int W, int K, int kern_per_image,
+                      dcpt_stream_t stream);
+
 /* ---- optional launch profiling (bench.py) -------------------------------------------------------
  * While enabled, MFMA GEMM launches are bracketed by HIP events on their own stream: every launch for on = 1, every
  * on-th launch for on > 1 (sampling keeps the perturbation of a timed region small: an event pair costs ~3 us of queue time).
