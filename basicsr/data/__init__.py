@@ -140,18 +140,39 @@ class PairedImageDenoiseDataset(tdata.Dataset):
     like the host path.  In the train phase the key is ``random.getrandbits(63)``: fresh noise every epoch, reproducible under the
     loader's worker seeding.  In other phases it is ``(noise_seed << 32) | index`` (``noise_seed`` default 0): a validation set sees
     the same noise on every visit.  The device stream is Philox4x32-10, not MT19937, so its noise equals the host path's in
-    distribution and not in value: numbers comparable with the paper's ``np.random.seed(0)`` test noise need the ``host`` backend."""
+    distribution and not in value: numbers comparable with the paper's ``np.random.seed(0)`` test noise need the ``host`` backend.
+
+    ``noise_type: gaussian`` (default) is all of the above.  ``noise_type: poisson`` (shot noise, ``noise_backend: device`` only: there is
+    no host form): ``sigma_type`` / ``sigma_range`` are not read; after the crop and the augmentation the sample draws its scale from
+    ``poisson_scale`` (a number, or ``[lo, hi]`` for one ``random.uniform``), then its gray decision (``random.random() < gray_prob``,
+    default 0; the draw is always made), then the key as above.  It carries ``gt``, ``poisson_scale`` (float32 scalar), ``poisson_gray``
+    (int32 scalar), ``noise_key`` and the paths, and no ``lq``; ``feed_data`` makes ``lq`` with
+    ``dcpt_amd.functional.poisson_noise(gt, poisson_scale, noise_key, gray=poisson_gray, clip=True)``, clipped as ``add_poisson_noise_pt``
+    defaults.  Poisson samples form batches of their own kind only: they have no ``degrade_kind``, and ``degrade_collate`` refuses them
+    next to samples of another kind."""
 
     def __init__(self, opt):
         super().__init__()
         self.opt = opt
         self.gt_root = opt["dataroot_gt"]
-        self.sigma_type = opt.get("sigma_type", "constant")
-        self.sigma_range = opt["sigma_range"]
-        assert self.sigma_type in ["constant", "random", "choice"]
         self.backend = opt.get("noise_backend", "host")
         if self.backend not in ("host", "device"):
             raise ValueError(f"noise_backend must be 'host' or 'device', got {self.backend!r}")
+        self.noise_type = opt.get("noise_type", "gaussian")
+        if self.noise_type not in ("gaussian", "poisson"):
+            raise ValueError(f"noise_type must be 'gaussian' or 'poisson', got {self.noise_type!r}")
+        if self.noise_type == "poisson":
+            if self.backend != "device":
+                raise ValueError("noise_type: poisson needs noise_backend: device (Poisson noise has no host backend)")
+            self.poisson_scale = opt.get("poisson_scale", 1.0)
+            ok = isinstance(self.poisson_scale, (int, float)) or (isinstance(self.poisson_scale, (list, tuple)) and len(self.poisson_scale) == 2)
+            if not ok or min(self.poisson_scale if isinstance(self.poisson_scale, (list, tuple)) else [self.poisson_scale]) < 0:
+                raise ValueError(f"poisson_scale must be a non-negative number or [lo, hi], got {self.poisson_scale!r}")
+            self.gray_prob = float(opt.get("gray_prob", 0))
+        else:
+            self.sigma_type = opt.get("sigma_type", "constant")
+            self.sigma_range = opt["sigma_range"]
+            assert self.sigma_type in ["constant", "random", "choice"]
         self.noise_seed = int(opt.get("noise_seed", 0))
         if not 0 <= self.noise_seed < (1 << 31):
             raise ValueError(f"noise_seed must lie in 0..2^31 - 1, got {self.noise_seed}")
@@ -169,6 +190,13 @@ class PairedImageDenoiseDataset(tdata.Dataset):
             _, gt = paired_random_crop_augment(gt, gt, {**self.opt, "scale": 1})   # the reference crops at scale 1 here (:368-370)
         elif self.opt.get("center_crop") is not None:
             gt = _center_crop(gt, self.opt["center_crop"])
+        if self.noise_type == "poisson":
+            scale = random.uniform(*self.poisson_scale) if isinstance(self.poisson_scale, (list, tuple)) else self.poisson_scale
+            gray = random.random() < self.gray_prob
+            key = random.getrandbits(63) if self.opt.get("phase") == "train" else (self.noise_seed << 32) | index
+            return _labelled({"gt": gt.contiguous(), "lq_path": path, "gt_path": path, "poisson_scale": torch.tensor(float(scale), dtype=torch.float32),
+                              "poisson_gray": torch.tensor(int(gray), dtype=torch.int32), "noise_key": torch.tensor(key, dtype=torch.int64)},
+                             self.opt)
         if self.sigma_type == "constant":
             sigma = self.sigma_range
         elif self.sigma_type == "random":
@@ -588,7 +616,9 @@ def degrade_collate(samples):
     different keys, which the default collate refuses; it is collated as: the keys common to all samples (``gt``, the paths,
     ``dataset_idx``) as usual; ``degrade_kind``, an int32 ``[B]`` host tensor: 0 the sample has ``lq``, 1 ``noise_sigma``, 2
     ``jpeg_quality``, 3 ``mosaic``, 4 ``inpaint_meta``, 5 ``blur_kernel``; and each kind's own keys (``lq`` included) stacked over THAT KIND'S samples in
-    batch order.  ``BaseModel._lq_on_device`` makes the ``lq`` rows of each kind from its ``gt`` rows."""
+    batch order.  ``BaseModel._lq_on_device`` makes the ``lq`` rows of each kind from its ``gt`` rows.  Poisson-noise samples
+    (``noise_type: poisson``: ``poisson_scale``, ``poisson_gray``, ``noise_key``) are none of the six kinds: they collate among themselves
+    and are refused in a mixed batch."""
     from torch.utils.data import default_collate
 
     keys = set(samples[0].keys())

@@ -1,6 +1,7 @@
 """The Gaussian-noise family of the reference's basicsr/data/degradations.py (:530-634) on the fused Philox kernel
 (``dcpt_amd.functional.gaussian_noise``, include/dcpt_hip.h dcpt_gauss_noise_fwd): the reference's names and signatures plus one trailing
-keyword ``key=None``.  ``img`` is a (b, c, h, w) float32 device tensor; each call is ONE kernel launch for the batch.
+keyword ``key=None``.  ``img`` is a (b, c, h, w) float32 device tensor; each call is ONE kernel launch for the batch.  (The Poisson family
+follows further down.)
 
 ``key``: the 64-bit key of image 0's noise stream; image ``b`` uses ``key + b``.  With ``key=None`` a 63-bit base is drawn from torch's
 default CPU generator, so ``torch.manual_seed`` governs the noise.  ``sigma`` and ``gray_noise`` take a number or a per-image tensor, as
@@ -22,8 +23,23 @@ lists and defaults: ``sigma_matrix2``, ``mesh_grid``, ``pdf2``, ``cdf2``, ``biva
 of the two modules.  The kernels are applied by ``basicsr.utils.filter2D`` (device; ``USMSharp`` is built on it) or
 ``basicsr.data.filter2d_host``.
 
-Out of scope: the Poisson family, JPEG compression (see ``dcpt_amd.functional.diffjpeg``) and the numpy forms of the noise functions
-(``generate_gaussian_noise``, ``add_gaussian_noise``, ``random_*`` without ``_pt``)."""
+The Poisson (shot-noise) family of the reference (:690-814) is here as well, on two fused kernels (``dcpt_amd.functional.poisson_noise``,
+include/dcpt_hip.h dcpt_poisson_noise_fwd: a level-count pass and a sampler, two launches per call whatever the batch):
+``generate_poisson_noise_pt``, ``add_poisson_noise_pt``, ``random_generate_poisson_noise_pt`` and ``random_add_poisson_noise_pt`` with the
+reference's names, argument order and defaults plus the trailing ``key=None``; keys and the ``random_*`` draws (first the b scales, then
+the b gray draws, then the key) as for the Gaussian functions.  They are public module attributes, imported by name.  Departures from
+the reference:
+  * the draws come from Philox4x32-10 by inversion, not from ``torch.poisson``: values match in distribution, not in value;
+  * the rate and the quantised image are fp64, not fp32 (the levels are identical for inputs on the 8-bit grid);
+  * a gray flag SELECTS the gray noise for its image where the reference blends ``noise (1 - g) + noise_gray g``: the same thing for
+    flags in {0, 1};
+  * gray noise needs 1 or 3 channels (the reference's ``rgb_to_grayscale`` refuses other counts too);
+  * the sampler resolves ``u`` to 2^-32, so a count whose probability is below that is never drawn.
+Batches of one kind only: a ``noise_type: poisson`` sample of PairedImageDenoiseDataset has no ``degrade_kind`` of its own, and
+``basicsr.data.degrade_collate`` refuses it next to samples of another kind.
+
+Out of scope: JPEG compression (see ``dcpt_amd.functional.diffjpeg``) and the numpy forms of the noise functions
+(``generate_gaussian_noise``, ``add_gaussian_noise``, ``generate_poisson_noise``, ``add_poisson_noise``, ``random_*`` without ``_pt``)."""
 import math
 import random
 
@@ -234,3 +250,38 @@ def random_add_gaussian_noise_pt(img, sigma_range=(0, 1.0), gray_prob=0, clip=Tr
     """``img`` + that noise (reference :623-634)"""
     sigma, gray = _random(img, sigma_range, gray_prob)
     return _noise(img, sigma, gray, key, clip=clip, rounds=rounds)
+
+
+# ---- Poisson noise (device) ---------------------------------------------------------------------------------
+
+
+def _poisson(img, scale, gray_noise, key, **flags):
+    if not torch.is_tensor(img) or img.dim() != 4:
+        raise ValueError("expected a (b, c, h, w) tensor")
+    b = img.shape[0]
+    if not torch.is_tensor(gray_noise):
+        gray_noise = int(gray_noise > 0)
+    return DF.poisson_noise(img, scale, _keys(b, key), gray=gray_noise, **flags)
+
+
+def generate_poisson_noise_pt(img, scale=1.0, gray_noise=0, key=None):
+    """the shot noise ``scale * (Poisson(q vals) / vals - q)`` of the shape of ``img``, q the image (or its gray values) on the 8-bit grid
+    and vals its level count rounded up to a power of two (reference :690-738)"""
+    return _poisson(img, scale, gray_noise, key, noise_only=True)
+
+
+def add_poisson_noise_pt(img, scale=1.0, clip=True, rounds=False, gray_noise=0, key=None):
+    """``img`` + Poisson noise, clamped to [0, 1] (``clip``) and / or rounded to the 8-bit grid (``rounds``) (reference :741-763)"""
+    return _poisson(img, scale, gray_noise, key, clip=clip, rounds=rounds)
+
+
+def random_generate_poisson_noise_pt(img, scale_range=(0, 1.0), gray_prob=0, key=None):
+    """noise with a scale drawn uniformly from ``scale_range`` and gray with probability ``gray_prob``, per image (reference :792-800)"""
+    scale, gray = _random(img, scale_range, gray_prob)
+    return _poisson(img, scale, gray, key, noise_only=True)
+
+
+def random_add_poisson_noise_pt(img, scale_range=(0, 1.0), gray_prob=0, clip=True, rounds=False, key=None):
+    """``img`` + that noise (reference :803-814)"""
+    scale, gray = _random(img, scale_range, gray_prob)
+    return _poisson(img, scale, gray, key, clip=clip, rounds=rounds)

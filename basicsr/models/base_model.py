@@ -40,7 +40,9 @@ class BaseModel:
         kernel, and a batch of an ``inpaint_backend: device`` set (PairedImageInpaintingDataset: ``gt``, ``inpaint_lines``,
         ``inpaint_meta``) from the line-mask kernel, and a batch of a ``noise_backend: device`` set (PairedImageDenoiseDataset: ``gt``,
         ``noise_sigma``, ``noise_key``) from the Philox noise kernel, unclipped like the host path, and a batch of a ``blur_backend: device``
-        set (PairedImageBlurDataset: ``gt`` and ``blur_kernel``, one (K, K) kernel per image) from the blur kernel.  A mixed batch
+        set (PairedImageBlurDataset: ``gt`` and ``blur_kernel``, one (K, K) kernel per image) from the blur kernel, and a batch of a
+        ``noise_type: poisson`` set (PairedImageDenoiseDataset: ``gt``, ``poisson_scale``, ``poisson_gray``, ``noise_key``) from the Poisson
+        noise kernels, clipped as ``add_poisson_noise_pt`` defaults (single-kind batches only).  A mixed batch
         (``basicsr.data.degrade_collate``: ``degrade_kind`` per sample, each kind's keys stacked over its own samples) gets every kind's rows
         from that kind's op on its ``gt`` rows"""
         if "degrade_kind" in data:
@@ -48,6 +50,9 @@ class BaseModel:
         if "lq" not in data and "noise_sigma" in data:
             gt = data["gt"].to(self.device, non_blocking=True)
             return DF.gaussian_noise(gt, data["noise_sigma"], data["noise_key"])
+        if "lq" not in data and "poisson_scale" in data:
+            gt = data["gt"].to(self.device, non_blocking=True)
+            return DF.poisson_noise(gt, data["poisson_scale"], data["noise_key"], gray=data["poisson_gray"], clip=True)
         if "lq" not in data and "jpeg_quality" in data:
             gt = data["gt"].to(self.device, non_blocking=True)
             return DF.diffjpeg(gt, data["jpeg_quality"].to(self.device, non_blocking=True), uint8_io=True)

@@ -2,7 +2,7 @@
 """Secondary workloads of BASELINE.json (configs[2..4]) on ONE MI355X -- evidence for DESIGN.md, not the driver's
 contract (that is bench.py).  Prints one JSON line per workload.
 
-    python bench_extra.py --workload dcpt|dcpt_swinir|restormer|promptir|infer2k|naf|swinir|rcan|val_metrics|step_tail|tlsc|ssim_loss|ldl|jpeg|niqe|degrade|noise|blur [--dtype fp32|bf16|bf16_res32] [--steps K] [--warmup W]
+    python bench_extra.py --workload dcpt|dcpt_swinir|restormer|promptir|infer2k|naf|swinir|rcan|val_metrics|step_tail|tlsc|ssim_loss|ldl|jpeg|niqe|degrade|noise|blur|poisson [--dtype fp32|bf16|bf16_res32] [--steps K] [--warmup W]
 
 ``--dtype bf16`` (dcpt, naf, infer2k, restormer, promptir; rcan: the inference line only, next to fp32; swinir: the restoration form's inference, next to fp32): every feature map of the encoder in bf16 storage with fp32 accumulation (act_dtype="bf16";
 dcpt: the classifier head too unless --head-dtype fp32); images, parameters and the optimizer stay fp32.  Its lines carry BOTH
@@ -1020,6 +1020,83 @@ def run_noise(dev, steps=20, warmup=3, B=32, S=256):
     return [first, second]
 
 
+def run_poisson(dev, steps=20, warmup=3, B=32, S=256):
+    """Poisson (shot) noise on a B x 3 x S x S batch at scale 1 with one key per image, images with all 256 levels (dcpt_amd/csrc/noise.hip):
+    ``dcpt_amd.functional.poisson_noise`` against the reference's expression restated in torch on the same device (the rounded copy, the
+    per-image ``len(torch.unique(...))`` loop with its read-backs, ``torch.poisson``, the blend; colour noise only, as a call with
+    ``gray_noise=0`` runs it), the two alternating call by call in one process; device events around each call, each route's peak memory
+    above what is resident between calls.  The two kernels' own times come from the library's launch timing (dcpt_prof_enable) in a
+    second, separate pass of ``steps`` calls.  One result line."""
+    import ctypes as C
+    import statistics
+
+    import numpy as np
+    import torch.nn.functional as F
+
+    from dcpt_amd import _lib
+    from dcpt_amd import functional as DF
+
+    g = torch.Generator(device=dev).manual_seed(1234)
+    low = torch.rand((B, 3, S // 8, S // 8), generator=g, device=dev)
+    x = (F.interpolate(low, size=(S, S), mode="bilinear", align_corners=False) * 1.2 - 0.1).clamp(0, 1)
+    x[:, 0, 0, :256] = torch.arange(256, device=dev) / 255.0   # (every level present, whatever the field above holds)
+    x = ((x * 255.0).round() / 255.0).contiguous()             # 8-bit images, as a loader hands them over
+    key = torch.arange(B, dtype=torch.int64, device=dev) + (9 << 32)
+
+    def torch_route():
+        img = torch.clamp((x * 255.0).round(), 0, 255) / 255.0
+        vals_list = [len(torch.unique(img[i, :, :, :])) for i in range(B)]
+        vals_list = [2 ** np.ceil(np.log2(vals)) for vals in vals_list]
+        vals = img.new_tensor(vals_list).view(B, 1, 1, 1)
+        out = torch.poisson(img * vals) / vals
+        return x + (out - img) * 1.0
+
+    peaks, last, times = {}, {}, {"kernel": [], "torch": []}
+    routes = {"kernel": lambda: DF.poisson_noise(x, 1.0, key), "torch": torch_route}
+    with torch.no_grad():
+        for i in range(warmup + steps):
+            for n, fn in routes.items():
+                torch.cuda.synchronize(dev)
+                base = torch.cuda.memory_allocated(dev)
+                torch.cuda.reset_peak_memory_stats(dev)
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                last[n] = fn()
+                e1.record()
+                e1.synchronize()
+                peaks[n] = max(peaks.get(n, 0), torch.cuda.max_memory_allocated(dev) - base)
+                if i >= warmup:
+                    times[n].append(e0.elapsed_time(e1))
+        _, vals = DF.poisson_noise(x, 1.0, key, return_vals=True)
+        lib = _lib.load()
+        lib.dcpt_prof_enable(1)
+        for _ in range(steps):
+            DF.poisson_noise(x, 1.0, key)
+        torch.cuda.synchronize(dev)
+        rows = (C.c_double * (8 * 16))()
+        nrows = lib.dcpt_prof_read(rows, 16)
+        lib.dcpt_prof_enable(0)
+    per = {int(rows[8 * j]): rows[8 * j + 5] / max(rows[8 * j + 4], 1.0) for j in range(nrows)}
+    noise = {n: last[n] - x for n in routes}
+    kmin = min(times["kernel"])
+    return dict(workload=f"Poisson noise, {B} x 3 x {S} x {S}, scale 1, one key per image, 256 levels per image: gt + (Poisson(q vals) / vals - q)",
+                kernel_ms_median=round(statistics.median(times["kernel"]), 4), kernel_ms_min=round(kmin, 4),
+                torch_ms_median=round(statistics.median(times["torch"]), 4), torch_ms_min=round(min(times["torch"]), 4),
+                ratio_median=round(statistics.median(times["torch"]) / statistics.median(times["kernel"]), 2),
+                levels_kernel_ms_mean=round(per.get(1032, float("nan")), 4), sampler_kernel_ms_mean=round(per.get(1033, float("nan")), 4),
+                kernel_gsamples_per_s_at_min=round(x.numel() / (kmin * 1e-3) / 1e9, 2),
+                kernel_peak_mb=round(peaks["kernel"] / 1e6, 1), torch_peak_mb=round(peaks["torch"] / 1e6, 1),
+                vals=sorted(set(vals.tolist())), mean_rate=round(float(x.mean()) * 256, 1),
+                kernel_noise_mean=round(float(noise["kernel"].mean()), 6), kernel_noise_std=round(float(noise["kernel"].std()), 5),
+                torch_noise_mean=round(float(noise["torch"].mean()), 6), torch_noise_std=round(float(noise["torch"].std()), 5),
+                calls=steps, warmup=warmup,
+                note="device events around each call (the op's host side included), the two routes alternating in one process; peak memory "
+                     "of a call above what is allocated between calls; the torch route is the reference's expression for colour noise "
+                     "(one torch.unique and one read-back per image, torch.poisson, the blend); levels / sampler_kernel_ms_mean are the "
+                     "library's per-launch event timing over a separate pass of `calls` calls; the two routes draw different streams: "
+                     "they agree in distribution (the noise mean and std of both are given), not in value")
+
+
 def run_blur(dev, steps=20, warmup=3, B=32, S=256, K=21):
     """Synthetic blur of a B x 3 x S x S batch with one K x K kernel per image (dcpt_amd/csrc/blur.hip): ``dcpt_amd.functional.filter2d``
     against the reference's form on the same device (``F.pad(mode="reflect")`` plus ``F.conv2d`` with B * 3 groups and the kernels repeated
@@ -1154,7 +1231,7 @@ def run_niqe(dev, steps=20, warmup=3, H=1080, W=2048):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", required=True, choices=["dcpt", "dcpt_swinir", "restormer", "promptir", "infer2k", "naf", "swinir", "rcan", "val_metrics", "step_tail", "tlsc", "ssim_loss", "ldl", "jpeg", "niqe", "degrade", "noise", "blur"])
+    ap.add_argument("--workload", required=True, choices=["dcpt", "dcpt_swinir", "restormer", "promptir", "infer2k", "naf", "swinir", "rcan", "val_metrics", "step_tail", "tlsc", "ssim_loss", "ldl", "jpeg", "niqe", "degrade", "noise", "blur", "poisson"])
     ap.add_argument("--dtype", default="fp32", choices=["fp32", "bf16", "bf16_tail32", "bf16_edge32", "bf16_res32"])
     ap.add_argument("--head-dtype", default=None, choices=["fp32", "bf16"], help="dcpt: classifier-head activations (default: --dtype)")
     ap.add_argument("--restormer-save", default="balanced", choices=["auto", "lean", "balanced", "full"], help="what the Restormer halves keep for backward")
@@ -1362,6 +1439,8 @@ def main():
         res = lines[1]
     elif args.workload == "blur":
         res = run_blur(dev, max(args.steps, 20), max(args.warmup, 3), args.batch or 32, args.size or 256)
+    elif args.workload == "poisson":
+        res = run_poisson(dev, max(args.steps, 20), max(args.warmup, 3), args.batch or 32, args.size or 256)
     elif args.workload == "tlsc":
         res = run_tlsc(dev, args.steps, args.warmup, tile=args.tile, streams=args.tile_streams)
     else:

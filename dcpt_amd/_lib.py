@@ -348,6 +348,8 @@ SIGNATURES = {
     "dcpt_demosaic_fwd": (cint, [f32p, f32p, cint, cint, cint, cint, cint, stream_t]),
     "dcpt_inpaint_lines_fwd": (cint, [f32p, C.c_void_p, C.c_void_p, f32p, cint, cint, cint, cint, stream_t]),
     "dcpt_gauss_noise_fwd": (cint, [f32p, f32p, C.c_void_p, C.c_void_p, f32p, cint, cint, cint, cint, cint, stream_t]),
+    "dcpt_poisson_noise_ws_bytes": (sz, [cint, cint, cint, cint]),
+    "dcpt_poisson_noise_fwd": (cint, [f32p, f32p, C.c_void_p, C.c_void_p, f32p, C.c_void_p, sz, cint, cint, cint, cint, cint, stream_t]),
     "dcpt_filter2d_fwd": (cint, [f32p, f32p, f32p, cint, cint, cint, cint, cint, cint, stream_t]),
     "dcpt_trace_enable": (cint, [cint]),
     "dcpt_trace_read": (sz, [C.c_char_p, sz]),

@@ -542,6 +542,31 @@ extern "C" int dcpt_gauss_noise_fwd(const float* x, const float* sigma, const lo
     return launch_gauss_noise_fwd(x, sigma, key, gray, y, B, C, H, W, flags, (hipStream_t)stream);
 }
 
+// Poisson (shot) noise on the same stream: a level-count pass and the sampler (noise.hip)
+namespace {
+const char* poisson_check(int B, int C, int H, int W) {
+    if (B <= 0 || C <= 0 || H <= 0 || W <= 0) return "bad shape";
+    if ((int64_t)C > (((int64_t)1 << 34) - 1) / ((int64_t)H * W)) return "C * H * W must stay below 2^34";
+    if ((int64_t)B > ((int64_t)1 << 40) / ((int64_t)C * H * W)) return "a batch above 2^40 elements";
+    return nullptr;
+}
+}  // namespace
+
+extern "C" size_t dcpt_poisson_noise_ws_bytes(int B, int C, int H, int W) {
+    return poisson_check(B, C, H, W) ? 0 : poisson_noise_ws_bytes(B, C, H, W);
+}
+
+extern "C" int dcpt_poisson_noise_fwd(const float* x, const float* scale, const long long* key, const int* gray, float* y, void* ws,
+                                      size_t ws_bytes, int B, int C, int H, int W, int flags, dcpt_stream_t stream) {
+    DCPT_CHECK_ARG((flags & ~(DCPT_NOISE_CLIP | DCPT_NOISE_ROUND8 | DCPT_NOISE_ONLY)) == 0, "poisson_noise_fwd: unknown flags 0x%x", flags);
+    DCPT_CHECK_ARG(x && scale && key && y && ws, "poisson_noise_fwd: null argument");   // (x also with DCPT_NOISE_ONLY: the rate depends on it)
+    const char* bad = poisson_check(B, C, H, W);
+    DCPT_CHECK_ARG(!bad, "poisson_noise_fwd: %s (B=%d C=%d H=%d W=%d)", bad, B, C, H, W);
+    DCPT_CHECK_ARG(!gray || C == 1 || C == 3, "poisson_noise_fwd: gray noise needs C = 1 or 3 (got %d)", C);
+    DCPT_CHECK_WS("poisson_noise_fwd", ws, ws_bytes, dcpt_poisson_noise_ws_bytes(B, C, H, W));
+    return launch_poisson_noise_fwd(x, scale, key, gray, y, ws, B, C, H, W, flags, (hipStream_t)stream);
+}
+
 // ---------------------------------------------------------------------------------------------
 // Synthetic blur: a K x K correlation per image under reflect padding (blur.hip)
 extern "C" int dcpt_filter2d_fwd(const float* x, const float* kern, float* y, int B, int C, int H, int W, int K, int kern_per_image,

@@ -230,6 +230,11 @@ int launch_inpaint_lines_fwd(const float* x, const int* lines, const int* meta, 
 // device; x may be null with DCPT_NOISE_ONLY; in place allowed); one launch, no workspace.
 int launch_gauss_noise_fwd(const float* x, const float* sigma, const long long* key, const int* gray, float* y, int B, int C, int H, int W,
                            int flags, hipStream_t s);
+// Poisson (shot) noise on the same stream (dcpt_poisson_noise_fwd: scale fp32 [B]; x is always read): the level-count pass and the sampler,
+// two launches; ws holds vals int32 [B] at its head and one 256-bit mask per (image, chunk) behind it (poisson_noise_ws_bytes, shape-only).
+size_t poisson_noise_ws_bytes(int B, int C, int H, int W);
+int launch_poisson_noise_fwd(const float* x, const float* scale, const long long* key, const int* gray, float* y, void* ws, int B, int C, int H,
+                             int W, int flags, hipStream_t s);
 
 // ---- blur.hip -------------------------------------------------------------------------------
 // The K x K correlation of every plane with its image's kernel under reflect padding (dcpt_filter2d_fwd: kern fp32 [B][K][K], or [1][K][K]

@@ -3026,12 +3026,12 @@ NOISE_CLIP, NOISE_ROUND8, NOISE_ONLY = 1, 2, 4   # include/dcpt_hip.h DCPT_NOISE
 NOISE_MAX_ELEMS = 1 << 34                        # C * H * W of one image stays below this
 
 
-def _per_image(name, v, B, dtype, dev):
+def _per_image(name, v, B, dtype, dev, op="gaussian_noise"):
     """a per-image argument as a (B,) device tensor: a Python number for every image, or a tensor of B values (0-d or one value: for every
     image); a device tensor is never read back"""
     if torch.is_tensor(v):
         if v.numel() not in (1, B) or v.dim() > 1 and v.numel() != B:
-            raise ValueError(f"gaussian_noise: {name} must be a number or hold {B} values, got {tuple(v.shape)}")
+            raise ValueError(f"{op}: {name} must be a number or hold {B} values, got {tuple(v.shape)}")
         v = v.detach().reshape(-1).to(device=dev, dtype=dtype, non_blocking=True)
         return (v.expand(B) if v.numel() != B else v).contiguous()
     return torch.full((B,), v, dtype=dtype, device=dev)
@@ -3047,37 +3047,66 @@ def gaussian_noise(x, sigma, key, gray=None, clip=False, rounds=False, noise_onl
     ``noise_only``: the noise term without ``x`` (``x`` then gives the shape and the device only).  ``out``: a contiguous fp32 tensor
     of x's shape on its device to write into; ``out=x`` works in place.  An image's result depends on its own values only, not on the
     batch around it.  Forward only."""
+    x, sigma, key, gray, out, flags = _noise_args("gaussian_noise", x, "sigma", sigma, key, gray, clip, rounds, noise_only, out)
+    _call(_lib.load().dcpt_gauss_noise_fwd, (None if noise_only else x, sigma, key, gray, out), (*x.shape, flags), x.device)
+    return out
+
+
+def _noise_args(op, x, amp_name, amp, key, gray, clip, rounds, noise_only, out):
+    """the arguments the two noise ops share, checked and brought to the device: returns (x, amp, key, gray, out, flags)"""
     if not torch.is_tensor(x):
-        raise _lib.DcptHipError(f"gaussian_noise takes a device tensor (got {type(x).__name__})")
+        raise _lib.DcptHipError(f"{op} takes a device tensor (got {type(x).__name__})")
     _require_gpu(x)
     if x.dim() != 4 or 0 in x.shape or x.shape[1] * x.shape[2] * x.shape[3] >= NOISE_MAX_ELEMS:
-        raise ValueError(f"gaussian_noise: expected a non-empty (B, C, H, W) batch with C * H * W < 2^34, got {tuple(x.shape)}")
-    _inference_only("gaussian_noise", x, what="the noise degradation")
-    B, C, H, W = x.shape
+        raise ValueError(f"{op}: expected a non-empty (B, C, H, W) batch with C * H * W < 2^34, got {tuple(x.shape)}")
+    _inference_only(op, x, what="the noise degradation")
+    B = x.shape[0]
     dev = x.device
-    host_sigma = sigma if not torch.is_tensor(sigma) else (None if sigma.is_cuda else sigma)
-    if host_sigma is not None and bool(torch.as_tensor(host_sigma).lt(0).any()):
-        raise ValueError(f"gaussian_noise: sigma must not be negative, got {host_sigma!r}")
+    host_amp = amp if not torch.is_tensor(amp) else (None if amp.is_cuda else amp)
+    if host_amp is not None and bool(torch.as_tensor(host_amp).lt(0).any()):
+        raise ValueError(f"{op}: {amp_name} must not be negative, got {host_amp!r}")
     if not torch.is_tensor(key):
         key = int(key)
         if not -(1 << 63) <= key < (1 << 64):
-            raise ValueError(f"gaussian_noise: key must fit 64 bits, got {key}")
+            raise ValueError(f"{op}: key must fit 64 bits, got {key}")
         key = key - (1 << 64) if key >= (1 << 63) else key   # (the same 64 bits as a signed value)
     elif key.is_floating_point():
-        raise ValueError("gaussian_noise: key must be an integer tensor")
-    sigma = _per_image("sigma", sigma if torch.is_tensor(sigma) else float(sigma), B, torch.float32, dev)
-    key = _per_image("key", key, B, torch.int64, dev)
+        raise ValueError(f"{op}: key must be an integer tensor")
+    amp = _per_image(amp_name, amp if torch.is_tensor(amp) else float(amp), B, torch.float32, dev, op)
+    key = _per_image("key", key, B, torch.int64, dev, op)
     if gray is not None:
-        gray = _per_image("gray", gray.ne(0) if torch.is_tensor(gray) else int(bool(gray)), B, torch.int32, dev)
+        gray = _per_image("gray", gray.ne(0) if torch.is_tensor(gray) else int(bool(gray)), B, torch.int32, dev, op)
     x = x.detach().contiguous()   # (no copy of a contiguous x, so out=x stays in place)
     if out is None:
         out = torch.empty_like(x)
     else:
         if not torch.is_tensor(out) or out.shape != x.shape or out.device != dev or out.dtype != torch.float32 or not out.is_contiguous():
-            raise ValueError(f"gaussian_noise: out must be a contiguous fp32 tensor of shape {tuple(x.shape)} on {dev}")
-        _inference_only("gaussian_noise", out, what="the noise degradation")
+            raise ValueError(f"{op}: out must be a contiguous fp32 tensor of shape {tuple(x.shape)} on {dev}")
+        _inference_only(op, out, what="the noise degradation")
     flags = (NOISE_CLIP if clip else 0) | (NOISE_ROUND8 if rounds else 0) | (NOISE_ONLY if noise_only else 0)
-    _call(_lib.load().dcpt_gauss_noise_fwd, (None if noise_only else x, sigma, key, gray, out), (B, C, H, W, flags), dev)
+    return x, amp, key, gray, out, flags
+
+
+def poisson_noise(x, scale, key, gray=None, clip=False, rounds=False, noise_only=False, out=None, return_vals=False):
+    """Poisson (shot) noise of the reference's ``generate_poisson_noise_pt``: ``x + scale * (Poisson(q vals) / vals - q)`` with ``q`` the
+    image on the 8-bit grid and ``vals`` the number of its distinct levels rounded up to a power of two (include/dcpt_hip.h
+    dcpt_poisson_noise_fwd states the level count, the Philox stream and the sampler).  Arguments as for ``gaussian_noise``, with ``scale``
+    in place of ``sigma``: per-image values are Python numbers or tensors of B values on the host or the device, a device tensor is not read
+    back (only a host scale is checked: a negative one raises).  ``gray`` non-zero: the noise is made from the image's gray values, one plane
+    shared by the channels; it needs 1 or 3 channels.  ``noise_only`` writes the noise term; ``x`` is read all the same, the rate depends on
+    it.  ``scale == 0`` without flags returns ``x`` bit for bit; ``out=x`` works in place.  Two launches: the level count and the sampler.
+    ``return_vals=True`` returns ``(out, vals)`` with ``vals`` the int32 (B,) device tensor of the per-image level counts.  Forward only."""
+    x, scale, key, gray, out, flags = _noise_args("poisson_noise", x, "scale", scale, key, gray, clip, rounds, noise_only, out)
+    B, C, H, W = x.shape
+    if gray is not None and C not in (1, 3):
+        raise ValueError(f"poisson_noise: gray noise needs 1 or 3 channels, got {C}")
+    lib = _lib.load()
+    dev = x.device
+    nws = _check_ws("poisson_noise", lib.dcpt_poisson_noise_ws_bytes(B, C, H, W), f"B={B} C={C} H={H} W={W}")
+    ws = _workspace(dev, nws)
+    _call(lib.dcpt_poisson_noise_fwd, (x, scale, key, gray, out, ws, nws), (B, C, H, W, flags), dev)
+    if return_vals:
+        return out, ws[:4 * B].view(torch.int32).clone()   # (the workspace is reused by the next op of the stream)
     return out
 
 

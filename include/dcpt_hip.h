@@ -996,6 +996,42 @@ int dcpt_inpaint_lines_fwd(const float* x, const int* lines, const int* meta, fl
 int dcpt_gauss_noise_fwd(const float* x, const float* sigma, const long long* key, const int* gray, float* y, int B, int C, int H, int W,
                          int flags, dcpt_stream_t stream);
 
+/* ---- on-the-fly degradations: Poisson (shot) noise, on the device --------------------------------------------------
+ * dcpt_poisson_noise_fwd replaces the Poisson family of basicsr/data/degradations.py:637-814 (generate_ / add_ / random_generate_ /
+ * random_add_poisson_noise_pt): the per-image len(torch.unique(...)) loop (a sort and a host synchronisation per image) becomes the
+ * population count of a 256-bit presence mask, torch.poisson a sampler by inversion on the Philox stream of dcpt_gauss_noise_fwd.  Two
+ * launches for the batch, no sort, no read-back, no atomics; the same input gives the same bits, whatever the grid.
+ *   x       dense NCHW fp32 [B][C][H][W]; always read (the rate depends on it), also with DCPT_NOISE_ONLY
+ *   scale   fp32 [B] on the device: the factor on the noise of image b
+ *   key     int64 [B] on the device: the Philox key of image b (words: its low and its high 32 bits)
+ *   gray    int32 [B] on the device or null: non-zero gives image b noise made from its gray values, one plane shared by its channels
+ *   y       dense NCHW fp32 [B][C][H][W]; y == x (in place) is allowed
+ *   ws      dcpt_poisson_noise_ws_bytes(B, C, H, W) bytes (the query needs no device; 0 for an invalid shape).  On return (in stream order)
+ *           its first B int32 hold vals[b]; the rest is scratch.
+ * Per image b, with n = C H W and plane = H W:
+ *   level(v) = (int) fmin(fmax(rint(255.0 * (double)v), 0.0), 255.0): half to even, NaN gives 0, so a level lies in 0..255.
+ *   Colour image (gray null or gray[b] == 0): l_e = level(x_e) for every element e of the image, all channels.
+ *   Gray image (gray[b] != 0; C must be 1 or 3): one value per pixel, g_p = x_p for C == 1 and (0.2989 R + 0.587 G) + 0.114 B for C == 3,
+ *   in fp64 from the fp32 samples, each product and each sum rounded on its own; l_p = level(g_p).
+ *   U = the number of distinct l of the image; vals = the smallest power of two >= U (U = 1 -> 1; at most 256).
+ *   lambda = (double)(l * vals) / 255.0, one IEEE division of an exact integer; lambda <= 256.
+ *   Uniforms: Philox4x32-10 as for dcpt_gauss_noise_fwd, key words the low / high half of key[b], counter (q, 0, 0, 0); its outputs x0..x3
+ *   give u_j = (x_j + 0.5) 2^-32, and u_j belongs to element 4 q + j of the image (gray: to pixel 4 q + j, shared by the channels).
+ *   Sampler: inversion by upward search in fp64, every product and sum rounded on its own (no fused multiply-add):
+ *       p = exp(-lambda); s = p; k = 0;  while (s < u && k < 1023) { k += 1; p = (p * lambda) * R[k]; s = s + p; }
+ *   with R[k] = 1.0 / k correctly rounded.  The cap 1023 only guards termination: for lambda <= 256 the sum passes the largest u,
+ *   1 - 2^-33, long before it.
+ *   Output, in fp64 and rounded once to fp32:  t = scale[b] * (k / vals - l / 255.0);  y = float((double)x + t).  Flags as for
+ *   dcpt_gauss_noise_fwd: DCPT_NOISE_CLIP clamps to [0, 1], DCPT_NOISE_ROUND8 then takes rint(255 v) / 255, DCPT_NOISE_ONLY writes t.
+ *   scale[b] == 0 without flags returns x bit for bit.
+ * An image's result depends on its own (x, scale, key, gray) only.  In place works: the level pass has finished before the sampling kernel
+ * starts, and a lane reads its own elements before it writes them.
+ * Errors (before any launch): unknown flag bits; null x, scale, key, y or ws; a workspace below the query; non-positive extents, C H W at
+ * or above 2^34, a batch above 2^40 elements; gray given with C other than 1 or 3. */
+size_t dcpt_poisson_noise_ws_bytes(int B, int C, int H, int W);
+int dcpt_poisson_noise_fwd(const float* x, const float* scale, const long long* key, const int* gray, float* y, void* ws, size_t ws_bytes,
+                           int B, int C, int H, int W, int flags, dcpt_stream_t stream);
+
 /* ---- on-the-fly degradations: synthetic blur, on the device -----------------------------------------------------
  * dcpt_filter2d_fwd replaces filter2D of basicsr/utils/img_process_util.py:7-31 (F.pad(mode="reflect") plus F.conv2d with B * C groups,
  * which materialises the padded batch and a weight repeated over the channels), the blur of USMSharp.forward (:73-82) with it.
@@ -1021,7 +1057,8 @@ int dcpt_filter2d_fwd(const float* x, const float* kern, float* y, int B, int C,
  * on-th launch for on > 1 (sampling keeps the perturbation of a timed region small: an event pair costs ~3 us of queue time).
  * dcpt_prof_read waits for them and writes rows of 8 doubles {class id, M, N, K, launches, total ms,
  * algorithmic flops, algorithmic bytes}, one per (class, shape); class id = 16*loaderA + epilogue (NT) or
- * 512 + 8*loaderX + loaderY (TN). */
+ * 512 + 8*loaderX + loaderY (TN); 1024 + i for a few non-GEMM launches (1032 / 1033: the level pass and the sampler of
+ * dcpt_poisson_noise_fwd, M = the batch's elements). */
 int dcpt_prof_enable(int on);
 int dcpt_prof_read(double* out, int max_rows);
 
