@@ -81,18 +81,9 @@ class DCPTModel(BaseModel):
         containers (ModuleList / ModuleDict) left out: what the reference's rule selects on its DDP-wrapped net, where
         ``module.decode_layers0`` has one dot -- SwinIR's decoder RSTBs, attributes of the net itself, which the published multi-GPU
         runs tapped (on the bare net the one-dot rule picks their never-called ``residual_group`` / ``conv`` children instead)."""
-        hook_names = self.opt.get("hook_names", None)
-        if hook_names is None:
-            raise ValueError("hook_names is required (e.g. 'decoder' for NAFNet, 'decoder_level' for Restormer)")
-        depth = self.opt.get("hook_depth", 1)
-        if depth not in (0, 1):
-            raise ValueError(f"hook_depth must be 0 or 1, got {depth!r}")
-        net = self.get_bare_model(self.net_g)
-        if depth == 0:
-            return [(name, m) for name, m in net.named_children()
-                    if hook_names in name and not isinstance(m, (torch.nn.ModuleList, torch.nn.ModuleDict))]
-        # reference :65-68 (it walks the wrapped net, whose names gain a "module." prefix under DDP and then never match)
-        return [(name, m) for name, m in net.named_modules() if hook_names in name and name.count(".") == 1]
+        from basicsr.utils.knn_probe import select_hook_modules   # (the rule itself: shared with the kNN probe's FeatureTaps)
+
+        return select_hook_modules(self.get_bare_model(self.net_g), self.opt.get("hook_names", None), self.opt.get("hook_depth", 1))
 
     def install_hooks(self):
         picked = self.select_hook_modules()

@@ -2,7 +2,7 @@
 """Secondary workloads of BASELINE.json (configs[2..4]) on ONE MI355X -- evidence for DESIGN.md, not the driver's
 contract (that is bench.py).  Prints one JSON line per workload.
 
-    python bench_extra.py --workload dcpt|dcpt_swinir|restormer|promptir|infer2k|naf|swinir|rcan|val_metrics|step_tail|tlsc|ssim_loss|ldl|jpeg|niqe|degrade|noise|blur|poisson [--dtype fp32|bf16|bf16_res32] [--steps K] [--warmup W]
+    python bench_extra.py --workload dcpt|dcpt_swinir|restormer|promptir|infer2k|naf|swinir|rcan|val_metrics|step_tail|tlsc|ssim_loss|ldl|jpeg|niqe|degrade|noise|blur|poisson|knn [--dtype fp32|bf16|bf16_res32] [--steps K] [--warmup W]
 
 ``--dtype bf16`` (dcpt, naf, infer2k, restormer, promptir; rcan: the inference line only, next to fp32; swinir: the restoration form's inference, next to fp32): every feature map of the encoder in bf16 storage with fp32 accumulation (act_dtype="bf16";
 dcpt: the classifier head too unless --head-dtype fp32); images, parameters and the optimizer stay fp32.  Its lines carry BOTH
@@ -1181,6 +1181,105 @@ def run_blur(dev, steps=20, warmup=3, B=32, S=256, K=21):
                      "float64, the kernel's tap order) over the B images on one thread, one pass")
 
 
+def run_knn(dev, steps=20, warmup=3, N=500, D=524288, classes=5, k=5):
+    """The kNN degradation probe at the reference's size (basicsr/utils/knn_probe.py, dcpt_amd/csrc/knn.hip): N seeded fp32 rows of D values
+    (a NAFNet-32 last decoder map at 128 x 128) in ``classes`` clusters, the reference's five seeded 67/33 splits.  Routes, alternating call
+    by call in one process with device events around each call: ``pairwise_sqdist`` (the fp64 MFMA kernels) and then ``knn_vote`` over the
+    five splits; ``torch.cdist`` of the rows cast to fp64 plus ``topk`` per split on the device.  ``knn_probe`` end to end (split rule,
+    kernels, the one transfer, the reports) and, where it is installed, scikit-learn's ``KNeighborsClassifier(5)`` on 16 host threads
+    (one pass over the five splits, wall time) are timed on their own.  The fp64 rate counts 2 N^2 D flops over the fastest call."""
+    import statistics
+    import time
+
+    import numpy as np
+
+    from basicsr.utils import knn_probe, train_test_indices
+    from basicsr.utils.knn_probe import KNN_SEEDS
+    from dcpt_amd import _lib
+    from dcpt_amd import functional as DF
+
+    g = torch.Generator(device=dev).manual_seed(1234)
+    labels = np.arange(N) % classes + 1
+    centres = torch.randn((classes, D), generator=g, device=dev)
+    x = torch.randn((N, D), generator=g, device=dev)
+    x += 0.05 * centres[torch.from_numpy(labels - 1).to(dev)]
+    del centres
+    splits = [train_test_indices(N, 0.33, s) for s in KNN_SEEDS]
+    train = torch.from_numpy(np.stack([tr for tr, _ in splits])).to(dev)
+    test = torch.from_numpy(np.stack([te for _, te in splits])).to(dev)
+    lab_dev = torch.from_numpy(labels).to(dev)
+    d2 = torch.empty((N, N), dtype=torch.float64, device=dev)
+
+    def kernel_route():
+        DF.pairwise_sqdist(x, out=d2)
+        return DF.knn_vote(d2, lab_dev, train, test, k)[0]
+
+    def torch_route():
+        x64 = x.double()
+        dist = torch.cdist(x64, x64)
+        return torch.stack([dist[test[s]][:, train[s]].topk(k, dim=1, largest=False).indices for s in range(len(splits))])
+
+    routes = {"kernel": kernel_route, "pdist2": lambda: DF.pairwise_sqdist(x, out=d2), "torch": torch_route}
+    peaks, last, times = {}, {}, {n: [] for n in routes}
+    with torch.no_grad():
+        for i in range(warmup + steps):
+            for n, fn in routes.items():
+                torch.cuda.synchronize(dev)
+                base = torch.cuda.memory_allocated(dev)
+                torch.cuda.reset_peak_memory_stats(dev)
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                last[n] = fn()
+                e1.record()
+                e1.synchronize()
+                peaks[n] = max(peaks.get(n, 0), torch.cuda.max_memory_allocated(dev) - base)
+                if i >= warmup:
+                    times[n].append(e0.elapsed_time(e1))
+
+    def votes(nbr_labels):   # (largest count, smallest label): the rule of dcpt_knn_vote_fwd
+        out = np.empty(nbr_labels.shape[:-1], dtype=np.int64)
+        for idx in np.ndindex(*out.shape):
+            vals, counts = np.unique(nbr_labels[idx], return_counts=True)
+            out[idx] = vals[np.argmax(counts)]
+        return out
+
+    pred_kernel = last["kernel"].cpu().numpy()
+    train_h = train.cpu().numpy()
+    pred_torch = votes(np.stack([labels[train_h[s][last["torch"][s].cpu().numpy()]] for s in range(len(splits))]))
+    torch.cuda.synchronize(dev)
+    t0 = time.perf_counter()
+    reports, mean_acc = knn_probe(x, labels)
+    probe_ms = (time.perf_counter() - t0) * 1e3
+    lib = _lib.load()
+    nws = lib.dcpt_pdist2_ws_bytes(N, N, D, 0)
+    al = lambda b: (b + 255) // 256 * 256   # noqa: E731
+    ksplit = next((c for c in range(1, 65536) if al(8 * c * N * N) + 2 * al(8 * c * N) == nws), None)
+    res = dict(workload=f"kNN degradation probe: {N} fp32 rows of {D} values, {classes} labels, k = {k}, five seeded 67/33 splits",
+               pdist2_ms_median=round(statistics.median(times["pdist2"]), 3), pdist2_ms_min=round(min(times["pdist2"]), 3),
+               pdist2_fp64_tflops_at_min=round(2.0 * N * N * D / (min(times["pdist2"]) * 1e-3) / 1e12, 2), fp64_matrix_peak_tflops_published=78.6,
+               pdist2_plus_vote_ms_median=round(statistics.median(times["kernel"]), 3),
+               torch_cdist_fp64_topk_ms_median=round(statistics.median(times["torch"]), 3), torch_cdist_fp64_topk_ms_min=round(min(times["torch"]), 3),
+               knn_probe_end_to_end_ms=round(probe_ms, 2), mean_accuracy=round(mean_acc, 4), ksplit_chosen=ksplit, workspace_mb=round(nws / 1e6, 1),
+               kernel_peak_mb=round(peaks["kernel"] / 1e6, 1), torch_peak_mb=round(peaks["torch"] / 1e6, 1),
+               predictions_differing_kernel_vs_torch=int((pred_kernel != pred_torch).sum()), predictions=int(pred_kernel.size),
+               probe_vs_kernel_route_differing=int(sum((r["pred"] != pred_kernel[s]).sum() for s, r in enumerate(reports))),
+               calls=steps, warmup=warmup,
+               note="device events around each call, the routes alternating in one process; pdist2 = pairwise_sqdist alone (norm, MFMA and "
+                    "finishing launches), kernel route = pairwise_sqdist + knn_vote over the five splits, torch route = the rows cast to fp64, "
+                    "torch.cdist and topk per split; peak memory of a call above what is allocated between calls; knn_probe_end_to_end_ms is one "
+                    "wall-clock call with the transfer and the host reports")
+    try:
+        from sklearn.neighbors import KNeighborsClassifier
+    except ImportError:
+        res["sklearn"] = "not installed"
+        return res
+    xh = x.cpu().numpy()
+    t0 = time.perf_counter()
+    pred_sk = np.stack([KNeighborsClassifier(n_neighbors=k, n_jobs=16).fit(xh[tr], labels[tr]).predict(xh[te]) for tr, te in splits])
+    res.update(sklearn_16_threads_ms=round((time.perf_counter() - t0) * 1e3, 1), predictions_differing_kernel_vs_sklearn=int((pred_kernel != pred_sk).sum()))
+    return res
+
+
 def run_niqe(dev, steps=20, warmup=3, H=1080, W=2048):
     """NIQE of one 1 x 3 x H x W image (a smooth random field plus fine noise, no flat block): the host ``calculate_niqe`` (numpy float64,
     one thread's wall time, best of 2) against ``calculate_niqe_device`` (the fused fp64 kernels of dcpt_amd/csrc/niqe.hip + the host
@@ -1231,7 +1330,7 @@ def run_niqe(dev, steps=20, warmup=3, H=1080, W=2048):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", required=True, choices=["dcpt", "dcpt_swinir", "restormer", "promptir", "infer2k", "naf", "swinir", "rcan", "val_metrics", "step_tail", "tlsc", "ssim_loss", "ldl", "jpeg", "niqe", "degrade", "noise", "blur", "poisson"])
+    ap.add_argument("--workload", required=True, choices=["dcpt", "dcpt_swinir", "restormer", "promptir", "infer2k", "naf", "swinir", "rcan", "val_metrics", "step_tail", "tlsc", "ssim_loss", "ldl", "jpeg", "niqe", "degrade", "noise", "blur", "poisson", "knn"])
     ap.add_argument("--dtype", default="fp32", choices=["fp32", "bf16", "bf16_tail32", "bf16_edge32", "bf16_res32"])
     ap.add_argument("--head-dtype", default=None, choices=["fp32", "bf16"], help="dcpt: classifier-head activations (default: --dtype)")
     ap.add_argument("--restormer-save", default="balanced", choices=["auto", "lean", "balanced", "full"], help="what the Restormer halves keep for backward")
@@ -1441,6 +1540,8 @@ def main():
         res = run_blur(dev, max(args.steps, 20), max(args.warmup, 3), args.batch or 32, args.size or 256)
     elif args.workload == "poisson":
         res = run_poisson(dev, max(args.steps, 20), max(args.warmup, 3), args.batch or 32, args.size or 256)
+    elif args.workload == "knn":
+        res = run_knn(dev, max(args.steps, 20), max(args.warmup, 3), args.batch or 500, args.size or 524288)
     elif args.workload == "tlsc":
         res = run_tlsc(dev, args.steps, args.warmup, tile=args.tile, streams=args.tile_streams)
     else:

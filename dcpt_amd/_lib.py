@@ -351,6 +351,11 @@ SIGNATURES = {
     "dcpt_poisson_noise_ws_bytes": (sz, [cint, cint, cint, cint]),
     "dcpt_poisson_noise_fwd": (cint, [f32p, f32p, C.c_void_p, C.c_void_p, f32p, C.c_void_p, sz, cint, cint, cint, cint, cint, stream_t]),
     "dcpt_filter2d_fwd": (cint, [f32p, f32p, f32p, cint, cint, cint, cint, cint, cint, stream_t]),
+    "dcpt_pdist2_ws_bytes": (sz, [cint, cint, C.c_longlong, cint]),
+    "dcpt_pdist2_fwd": (cint, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, sz, cint, cint, C.c_longlong, C.c_longlong, C.c_longlong,
+                               C.c_longlong, cint, cint, stream_t]),
+    "dcpt_knn_vote_fwd": (cint, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, cint, cint, cint, cint, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, stream_t]),
     "dcpt_trace_enable": (cint, [cint]),
     "dcpt_trace_read": (sz, [C.c_char_p, sz]),
     "dcpt_prof_enable": (cint, [cint]),

@@ -583,3 +583,47 @@ extern "C" int dcpt_filter2d_fwd(const float* x, const float* kern, float* y, in
     DCPT_CHECK_ARG(xa + bytes <= ya || ya + bytes <= xa, "filter2d_fwd: y overlaps x (a tile reads its neighbours' pixels: not in place)");
     return launch_filter2d_fwd(x, kern, y, B, C, H, W, K, kern_per_image != 0, (hipStream_t)stream);
 }
+
+// ---------------------------------------------------------------------------------------------
+// The kNN degradation probe: fp64 squared distances on the fp64 MFMA, and the neighbour vote (knn.hip)
+namespace {
+// the effective chunk count of a call, or 0 with `why` set for a refused shape
+int pdist2_ksplit(int Nq, int Nt, long long D, int ksplit, const char** why) {
+    *why = nullptr;
+    if (Nq < 1 || Nt < 1 || D < 1) *why = "Nq, Nt and D must be at least 1";
+    else if (Nq > PDIST2_MAX_ROWS || Nt > PDIST2_MAX_ROWS) *why = "more than 65535 rows";
+    else if (ksplit < 0 || (long long)ksplit > (D + 3) / 4) *why = "ksplit must lie in 0 .. ceil(D / 4)";
+    else if (ksplit > PDIST2_MAX_KSPLIT) *why = "ksplit above 65535";
+    if (*why) return 0;
+    return ksplit ? ksplit : pdist2_auto_ksplit(Nq, Nt, D);
+}
+}  // namespace
+
+extern "C" size_t dcpt_pdist2_ws_bytes(int Nq, int Nt, long long D, int ksplit) {
+    const char* why;
+    const int ks = pdist2_ksplit(Nq, Nt, D, ksplit, &why);
+    return ks ? pdist2_ws_bytes(Nq, Nt, ks) : 0;
+}
+
+extern "C" int dcpt_pdist2_fwd(const void* xq, const void* xt, double* d2, void* ws, size_t ws_bytes, int Nq, int Nt, long long D, long long ldq,
+                               long long ldt, long long ldd, int ksplit, int flags, dcpt_stream_t stream) {
+    DCPT_CHECK_ARG((flags & ~DCPT_PDIST_BF16) == 0, "pdist2_fwd: unknown flags 0x%x", flags);
+    DCPT_CHECK_ARG(xq && xt && d2 && ws, "pdist2_fwd: null argument");
+    const char* why;
+    const int ks = pdist2_ksplit(Nq, Nt, D, ksplit, &why);
+    DCPT_CHECK_ARG(ks, "pdist2_fwd: %s (Nq=%d Nt=%d D=%lld ksplit=%d)", why, Nq, Nt, D, ksplit);
+    DCPT_CHECK_ARG(ldq >= D && ldt >= D && ldd >= Nt, "pdist2_fwd: a leading dimension below its extent (ldq=%lld ldt=%lld D=%lld ldd=%lld Nt=%d)",
+                   ldq, ldt, D, ldd, Nt);
+    DCPT_CHECK_WS("pdist2_fwd", ws, ws_bytes, pdist2_ws_bytes(Nq, Nt, ks));
+    return launch_pdist2_fwd(xq, xt, d2, ws, Nq, Nt, D, ldq, ldt, ldd, ks, (flags & DCPT_PDIST_BF16) != 0, (hipStream_t)stream);
+}
+
+extern "C" int dcpt_knn_vote_fwd(const double* d2, long long ldd, const int* q_idx, const int* t_idx, const int* labels, int S, int nq, int nt, int k,
+                                 int* nbr, double* nbr_d2, int* pred, dcpt_stream_t stream) {
+    DCPT_CHECK_ARG(d2 && q_idx && t_idx && labels && nbr && nbr_d2 && pred, "knn_vote_fwd: null argument");
+    DCPT_CHECK_ARG(S >= 1 && nq >= 1 && nt >= 1, "knn_vote_fwd: S, nq and nt must be at least 1 (S=%d nq=%d nt=%d)", S, nq, nt);
+    DCPT_CHECK_ARG(k >= 1 && k <= 32 && k <= nt, "knn_vote_fwd: k must lie in 1 .. min(32, nt) (k=%d nt=%d)", k, nt);
+    DCPT_CHECK_ARG(ldd >= 1, "knn_vote_fwd: bad leading dimension (ldd=%lld)", ldd);
+    DCPT_CHECK_ARG((int64_t)S * nq <= (int64_t)0x7fffffff, "knn_vote_fwd: more than 2^31 - 1 queries over the splits (S=%d nq=%d)", S, nq);
+    return launch_knn_vote_fwd(d2, ldd, q_idx, t_idx, labels, S, nq, nt, k, nbr, nbr_d2, pred, (hipStream_t)stream);
+}

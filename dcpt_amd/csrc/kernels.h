@@ -240,3 +240,16 @@ int launch_poisson_noise_fwd(const float* x, const float* scale, const long long
 // The K x K correlation of every plane with its image's kernel under reflect padding (dcpt_filter2d_fwd: kern fp32 [B][K][K], or [1][K][K]
 // with per_image == 0; K odd, 1..51, K / 2 < H, W); fp64 accumulation in the tap order of the header; one launch, no workspace.
 int launch_filter2d_fwd(const float* x, const float* kern, float* y, int B, int C, int H, int W, int K, int per_image, hipStream_t s);
+
+// ---- knn.hip --------------------------------------------------------------------------------
+// Squared Euclidean distances between the rows of two fp32 / bf16 matrices in fp64 (dcpt_pdist2_fwd): the k-range in `ksplit` >= 1 chunks,
+// partial norms, partial 64 x 64 tiles on the fp64 MFMA and the finishing pass: four launches; ws holds the partial tiles [ksplit][Nq][Nt]
+// and the partial norms [ksplit][Nq], [ksplit][Nt] behind them (pdist2_ws_bytes, shape-only).  pdist2_auto_ksplit: the count for ksplit 0.
+constexpr int PDIST2_MAX_KSPLIT = 65535, PDIST2_MAX_ROWS = 65535;
+int pdist2_auto_ksplit(int Nq, int Nt, int64_t D);
+size_t pdist2_ws_bytes(int Nq, int Nt, int ksplit);
+int launch_pdist2_fwd(const void* xq, const void* xt, double* d2, void* ws, int Nq, int Nt, int64_t D, int64_t ldq, int64_t ldt, int64_t ldd,
+                      int ksplit, int bf16, hipStream_t s);
+// The k nearest training columns of every query row and their majority label, S splits in one launch (dcpt_knn_vote_fwd); no workspace.
+int launch_knn_vote_fwd(const double* d2, int64_t ldd, const int* q_idx, const int* t_idx, const int* labels, int S, int nq, int nt, int k, int* nbr,
+                        double* nbr_d2, int* pred, hipStream_t s);

@@ -3148,6 +3148,98 @@ def filter2d(x, kernel):
 
 
 # ------------------------------------------------------------------------------------------------
+# The kNN degradation probe (include/dcpt_hip.h dcpt_pdist2_fwd, dcpt_knn_vote_fwd): fp64 squared distances between flattened feature rows
+# on the fp64 matrix cores, and the k-nearest-neighbour majority vote over them.  Forward only.
+PDIST_BF16 = 1                           # include/dcpt_hip.h DCPT_PDIST_BF16
+PDIST_MAX_ROWS, KNN_MAX_K = 65535, 32
+
+
+def _feature_rows(op, name, x):
+    if not torch.is_tensor(x):
+        raise _lib.DcptHipError(f"{op} takes device tensors (got {type(x).__name__} for {name})")
+    _require_gpu_feat(x)
+    if x.dim() != 2 or 0 in x.shape or x.stride(1) != 1 or (x.shape[0] > 1 and x.stride(0) < x.shape[1]):
+        raise ValueError(f"{op}: {name} must be a non-empty 2-D tensor with contiguous rows, got shape {tuple(x.shape)} strides {x.stride()}")
+    return x.detach()
+
+
+def pairwise_sqdist(xq, xt=None, ksplit=0, out=None):
+    """Squared Euclidean distances between the rows of ``xq`` (Nq, D) and ``xt`` (Nt, D; None: ``xq`` itself) as a float64 (Nq, Nt) device
+    tensor.  The operands are fp32 or bf16 device tensors of one dtype whose rows are contiguous; any row stride of at least D is allowed.
+    Every element is converted to fp64 and ``max(0, (|q|^2 + |t|^2) - 2 q.t)`` is summed in fp64 on the fp64 matrix cores, the k-range in
+    ``ksplit`` chunks (0: chosen from the shape); an entry depends on its two rows, D, the dtype and the effective ``ksplit`` only, so two
+    runs and permuted rows give the same bits (include/dcpt_hip.h states the arithmetic).  ``out``: a float64 (Nq, Nt) device tensor with
+    contiguous rows to write into.  Forward only."""
+    xq = _feature_rows("pairwise_sqdist", "xq", xq)
+    xt = xq if xt is None else _feature_rows("pairwise_sqdist", "xt", xt)
+    if xt.dtype != xq.dtype or xt.device != xq.device or xt.shape[1] != xq.shape[1]:
+        raise ValueError(f"pairwise_sqdist: xq {tuple(xq.shape)} {xq.dtype} on {xq.device} and xt {tuple(xt.shape)} {xt.dtype} on {xt.device} "
+                         "must share the dtype, the device and the row length")
+    (Nq, D), Nt, dev = xq.shape, xt.shape[0], xq.device
+    ksplit = int(ksplit)
+    if max(Nq, Nt) > PDIST_MAX_ROWS or not 0 <= ksplit <= min((D + 3) // 4, 65535):
+        raise ValueError(f"pairwise_sqdist: at most {PDIST_MAX_ROWS} rows and ksplit in 0 .. min(ceil(D / 4), 65535), got Nq={Nq} Nt={Nt} D={D} "
+                         f"ksplit={ksplit}")
+    if out is None:
+        out = torch.empty((Nq, Nt), dtype=torch.float64, device=dev)
+    elif not torch.is_tensor(out) or tuple(out.shape) != (Nq, Nt) or out.dtype != torch.float64 or out.device != dev or out.stride(1) != 1 \
+            or (Nq > 1 and out.stride(0) < Nt):
+        raise ValueError(f"pairwise_sqdist: out must be a float64 ({Nq}, {Nt}) tensor with contiguous rows on {dev}")
+    lib = _lib.load()
+    nws = _check_ws("pairwise_sqdist", lib.dcpt_pdist2_ws_bytes(Nq, Nt, D, ksplit), f"Nq={Nq} Nt={Nt} D={D} ksplit={ksplit}")
+    ws = _workspace(dev, nws)
+    ldq, ldt, ldd = (t.stride(0) if t.shape[0] > 1 else t.shape[1] for t in (xq, xt, out))
+    _call(lib.dcpt_pdist2_fwd, (xq, xt, out, ws, nws), (Nq, Nt, D, ldq, ldt, ldd, ksplit, PDIST_BF16 if xq.dtype == torch.bfloat16 else 0), dev)
+    return out
+
+
+def _index_lists(name, v, bound, dev):
+    """an (S, n) index argument as a contiguous int32 device tensor; a host tensor or nested list is checked against 0 .. bound - 1"""
+    if not torch.is_tensor(v):
+        v = torch.as_tensor(v)
+    if v.is_floating_point() or v.dtype == torch.bool or v.dim() != 2 or 0 in v.shape:
+        raise ValueError(f"knn_vote: {name} must be a non-empty (S, n) integer tensor or nested list, got {tuple(v.shape)} {v.dtype}")
+    if not v.is_cuda and (int(v.min()) < 0 or int(v.max()) >= bound):
+        raise ValueError(f"knn_vote: {name} holds an index outside 0 .. {bound - 1}")
+    return v.detach().to(device=dev, dtype=torch.int32, non_blocking=True).contiguous()
+
+
+def knn_vote(d2, labels, train_idx, test_idx, k):
+    """The k nearest training columns of every query row of ``d2`` and their majority label, for S splits in one launch.  ``d2``: float64
+    (Nq, Nt) device tensor with contiguous rows; ``labels``: Nt integer labels of d2's columns (any int32 value; tensor or list);
+    ``train_idx`` (S, nt) the columns and ``test_idx`` (S, nq) the rows that split s uses: integer tensors or nested lists; host values
+    are checked against d2's shape and copied, device tensors are not read back.  Returns ``(pred, nbr, nbr_d2)``: int32 (S, nq), int32
+    (S, nq, k) positions in the split's ``train_idx`` nearest first, and their float64 distances.  Neighbours are ordered by (distance,
+    position) -- equal distances go to the lower position, a NaN after every number; on equal counts the smallest label wins.  Nothing
+    is read back from the device."""
+    if not torch.is_tensor(d2):
+        raise _lib.DcptHipError(f"knn_vote takes a device tensor (got {type(d2).__name__})")
+    _require((d2,), (torch.float64,), "knn_vote: d2 must be float64 (got {})")
+    if d2.dim() != 2 or 0 in d2.shape or d2.stride(1) != 1 or (d2.shape[0] > 1 and d2.stride(0) < d2.shape[1]):
+        raise ValueError(f"knn_vote: d2 must be a non-empty 2-D tensor with contiguous rows, got {tuple(d2.shape)} strides {d2.stride()}")
+    dev = d2.device
+    if not torch.is_tensor(labels):
+        labels = torch.as_tensor(labels)
+    if labels.is_floating_point() or labels.dim() != 1 or labels.numel() != d2.shape[1]:
+        raise ValueError(f"knn_vote: labels must be {d2.shape[1]} integers, one per column of d2, got {tuple(labels.shape)} {labels.dtype}")
+    labels = labels.detach().to(device=dev, dtype=torch.int32, non_blocking=True).contiguous()
+    t_idx = _index_lists("train_idx", train_idx, d2.shape[1], dev)
+    q_idx = _index_lists("test_idx", test_idx, d2.shape[0], dev)
+    (S, nt), nq, k = t_idx.shape, q_idx.shape[1], int(k)
+    if q_idx.shape[0] != S:
+        raise ValueError(f"knn_vote: train_idx has {S} splits and test_idx {q_idx.shape[0]}")
+    if not 1 <= k <= min(KNN_MAX_K, nt):
+        raise ValueError(f"knn_vote: k must lie in 1 .. min({KNN_MAX_K}, nt = {nt}), got {k}")
+    d2 = d2.detach()
+    nbr = torch.empty((S, nq, k), dtype=torch.int32, device=dev)
+    nbr_d2 = torch.empty((S, nq, k), dtype=torch.float64, device=dev)
+    pred = torch.empty((S, nq), dtype=torch.int32, device=dev)
+    ldd = d2.stride(0) if d2.shape[0] > 1 else d2.shape[1]
+    _call(_lib.load().dcpt_knn_vote_fwd, (d2, ldd, q_idx, t_idx, labels), (S, nq, nt, k, nbr.data_ptr(), nbr_d2.data_ptr(), pred.data_ptr()), dev)
+    return pred, nbr, nbr_d2
+
+
+# ------------------------------------------------------------------------------------------------
 # MATLAB-bicubic resize and the pixel work of NIQE (include/dcpt_hip.h dcpt_imresize_fwd, dcpt_niqe_mscn_fwd, dcpt_niqe_block_stats_fwd):
 # the reference's basicsr/utils/matlab_functions.py::imresize and the per-pixel part of basicsr/metrics/niqe.py in fp64.  Forward only.
 IMRESIZE_X_F64, IMRESIZE_Y_F64, IMRESIZE_QUANT8 = 1, 2, 4   # include/dcpt_hip.h DCPT_IMRESIZE_*

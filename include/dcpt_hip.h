@@ -1052,13 +1052,52 @@ int dcpt_poisson_noise_fwd(const float* x, const float* scale, const long long* 
 int dcpt_filter2d_fwd(const float* x, const float* kern, float* y, int B, int C, int H, int W, int K, int kern_per_image,
                       dcpt_stream_t stream);
 
+/* ---- the kNN degradation probe: fp64 distances and the neighbour vote, on the device ------------------------------
+ * replaces what the reference's knn.py leaves to scikit-learn on the host (KNeighborsClassifier(5).fit / predict over the flattened decoder
+ * features of knn_gen.py): the distances between a few hundred rows of 10^5 .. 10^6 numbers each, and the majority vote.
+ *
+ * dcpt_pdist2_fwd: d2[i][j] = the squared Euclidean distance between row i of xq and row j of xt.
+ *   xq     [Nq] rows of D elements, row i at element i ldq; fp32, or bf16 with DCPT_PDIST_BF16 (both operands)
+ *   xt     [Nt] rows of D elements, row j at element j ldt; xq == xt is allowed
+ *   d2     fp64 [Nq] rows of Nt, row i at element i ldd
+ * Arithmetic: every element is converted to fp64 (exact).  G_ij = sum_k q_ik t_jk, n_i = sum_k q_ik^2, m_j = sum_k t_jk^2; each product of
+ * two fp32 or bf16 values is exact in fp64, the sums are fp64 in an order the kernel fixes (the k-range in `ksplit` chunks, a chunk's sum
+ * in ascending k on the fp64 matrix cores for G and over 256 interleaved lanes and a fixed tree for n and m, the chunks added in chunk order).
+ *     d2[i][j] = max(0, (n_i + m_j) - 2 G_ij)          (a NaN stays a NaN)
+ * ksplit: the number of chunks of the k-range, chunk c = columns [c L, min(D, (c + 1) L)) with L = 4 ceil(ceil(D / 4) / ksplit); 0: the
+ * library chooses from the shape (about 1024 workgroups of 64 x 64 tiles, chunks of at least 512 columns), a positive value forces it.
+ * Partial tiles and norms go to the workspace with plain stores and a second pass adds them: no atomics.
+ * Contract: d2[i][j] depends only on row i of xq, row j of xt, D, the element type and the effective ksplit -- not on i, j, Nq, Nt, the
+ * leading dimensions or the other rows.  So two runs give the same bits, permuting the rows of xt permutes the columns of d2 bit for bit,
+ * and duplicate rows get equal distances.  (Not promised: a zero diagonal or bitwise symmetry for xq == xt.)
+ * dcpt_pdist2_ws_bytes needs no device and returns 0 for a refused shape.  Four launches, no host synchronisation.
+ * Errors (before any launch): unknown flag bits; null pointers; Nq, Nt or D below 1; Nq or Nt above 65535; ldq or ldt below D, ldd below
+ * Nt; ksplit below 0, above ceil(D / 4) or above 65535; a workspace below the query.
+ *
+ * dcpt_knn_vote_fwd: the k nearest training columns of every query row of d2 and their majority label, for S splits in one launch.
+ *   d2       fp64, row r at element r ldd
+ *   q_idx    int32 [S][nq], t_idx int32 [S][nt]: the rows and the columns of d2 that split s uses (device memory; not checked)
+ *   labels   int32, labels[c] the label of column c of d2 (any value)
+ *   nbr      int32 [S][nq][k]: positions in the split's t_idx, nearest first;  nbr_d2 fp64 [S][nq][k]: their distances;  pred int32 [S][nq]
+ * Neighbours are ordered by (distance, position in t_idx) ascending -- a stable sort: equal distances go to the lower position, -0 equals
+ * +0 -- and a NaN distance ranks after every number.  The predicted label has the largest count among the k neighbours; on equal counts
+ * the smallest label value wins (scikit-learn's uniform-weight vote).  One wave per (query, split), one launch, no workspace.
+ * Errors (before the launch): null pointers; S, nq or nt below 1; k below 1, above 32 or above nt; ldd below 1. */
+#define DCPT_PDIST_BF16 1   /* rows are bf16 instead of fp32 (the taps of a bf16-storage encoder) */
+size_t dcpt_pdist2_ws_bytes(int Nq, int Nt, long long D, int ksplit);
+int dcpt_pdist2_fwd(const void* xq, const void* xt, double* d2, void* ws, size_t ws_bytes, int Nq, int Nt, long long D, long long ldq,
+                    long long ldt, long long ldd, int ksplit, int flags, dcpt_stream_t stream);
+int dcpt_knn_vote_fwd(const double* d2, long long ldd, const int* q_idx, const int* t_idx, const int* labels, int S, int nq, int nt, int k,
+                      int* nbr, double* nbr_d2, int* pred, dcpt_stream_t stream);
+
 /* ---- optional launch profiling (bench.py) -------------------------------------------------------
  * While enabled, MFMA GEMM launches are bracketed by HIP events on their own stream: every launch for on = 1, every
  * on-th launch for on > 1 (sampling keeps the perturbation of a timed region small: an event pair costs ~3 us of queue time).
  * dcpt_prof_read waits for them and writes rows of 8 doubles {class id, M, N, K, launches, total ms,
  * algorithmic flops, algorithmic bytes}, one per (class, shape); class id = 16*loaderA + epilogue (NT) or
  * 512 + 8*loaderX + loaderY (TN); 1024 + i for a few non-GEMM launches (1032 / 1033: the level pass and the sampler of
- * dcpt_poisson_noise_fwd, M = the batch's elements). */
+ * dcpt_poisson_noise_fwd, M = the batch's elements; 1034 .. 1036: the norm, MFMA and finishing passes of dcpt_pdist2_fwd; 1037:
+ * dcpt_knn_vote_fwd). */
 int dcpt_prof_enable(int on);
 int dcpt_prof_read(double* out, int max_rows);
 
