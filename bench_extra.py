@@ -2,7 +2,7 @@
 """Secondary workloads of BASELINE.json (configs[2..4]) on ONE MI355X -- evidence for DESIGN.md, not the driver's
 contract (that is bench.py).  Prints one JSON line per workload.
 
-    python bench_extra.py --workload dcpt|dcpt_swinir|restormer|promptir|infer2k|naf|swinir|rcan|val_metrics|step_tail|tlsc|ssim_loss|ldl|jpeg|niqe|degrade|noise|blur|poisson|knn [--dtype fp32|bf16|bf16_res32] [--steps K] [--warmup W]
+    python bench_extra.py --workload dcpt|dcpt_swinir|restormer|promptir|infer2k|naf|swinir|rcan|val_metrics|step_tail|tlsc|ssim_loss|ldl|jpeg|niqe|degrade|noise|blur|poisson|knn|tsne [--dtype fp32|bf16|bf16_res32] [--steps K] [--warmup W]
 
 ``--dtype bf16`` (dcpt, naf, infer2k, restormer, promptir; rcan: the inference line only, next to fp32; swinir: the restoration form's inference, next to fp32): every feature map of the encoder in bf16 storage with fp32 accumulation (act_dtype="bf16";
 dcpt: the classifier head too unless --head-dtype fp32); images, parameters and the optimizer stay fp32.  Its lines carry BOTH
@@ -1280,6 +1280,115 @@ def run_knn(dev, steps=20, warmup=3, N=500, D=524288, classes=5, k=5):
     return res
 
 
+def run_tsne(dev, sizes=(500, 4096), D=64, classes=5, max_iter=2000):
+    """Exact t-SNE on the device (basicsr/utils/tsne.py, dcpt_amd/csrc/tsne.hip) at the kNN workload's row count and at 4096 rows: seeded
+    blobs of D values in ``classes`` clusters, unit-length rows, perplexity 30, the full ``max_iter``-iteration schedule from the "random"
+    start (wall time of ``tsne_embed`` on the resident distance matrix, with its read-back every 50 iterations).  Next to it: the
+    affinities alone; 50 iterations in one ``tsne_steps`` call and the same 50 written as float64 torch expressions on the same device
+    (device events, alternating, median of 5 after 1 warm-up); where scikit-learn is installed ``TSNE(method="exact")`` and the default
+    Barnes-Hut on the host (wall time, one run; the exact method at more than 1000 rows for 250 iterations only).  One dict per size."""
+    import statistics
+    import time
+
+    import numpy as np
+
+    from basicsr.utils import neighbour_label_share, tsne_embed
+    from dcpt_amd import functional as DF
+
+    EPS = 2.0 ** -52
+
+    def torch_steps(P, Y, update, gains, n, ex, mom, lr):
+        Pe = ex * P
+        for _ in range(n):
+            diff = Y[:, None, :] - Y[None, :, :]
+            w = 1.0 / (1.0 + (diff * diff).sum(-1))
+            w.fill_diagonal_(0.0)
+            Q = torch.clamp_min(w / w.sum(), EPS)
+            g = 4.0 * (((Pe - Q) * w)[:, :, None] * diff).sum(1)
+            gains = torch.clamp_min(torch.where(update * g < 0.0, gains + 0.2, gains * 0.8), 0.01)
+            update = mom * update - lr * (g * gains)
+            Y = Y + update
+        return Y
+
+    out = []
+    for N in sizes:
+        rs = np.random.RandomState(1234)
+        labels = np.arange(N) % classes
+        X = (10.0 * rs.standard_normal((classes, D))[labels] + rs.standard_normal((N, D))).astype(np.float32)
+        x = torch.from_numpy(X).to(dev)
+        x = x / x.norm(dim=1, keepdim=True)
+        d2 = DF.pairwise_sqdist(x)
+        lr = max(N / 12.0 / 4.0, 50.0)
+
+        def timed(fn):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize(dev)
+            e0.record()
+            r = fn()
+            e1.record()
+            e1.synchronize()
+            return e0.elapsed_time(e1), r
+
+        aff = [timed(lambda: DF.tsne_affinities(d2, 30.0)) for _ in range(4)]
+        P = aff[-1][1][0]
+        Y0 = torch.from_numpy(1e-4 * np.random.RandomState(0).standard_normal((N, 2))).to(dev)
+        t_kernel, t_torch = [], []
+        for i in range(6):
+            Y, u, g = Y0.clone(), torch.zeros_like(Y0), torch.ones_like(Y0)
+            tk, _ = timed(lambda: DF.tsne_steps(P, Y, u, g, 50, 12.0, 0.5, lr))
+            tt, Yt = timed(lambda: torch_steps(P, Y0, torch.zeros_like(Y0), torch.ones_like(Y0), 50, 12.0, 0.5, lr))
+            if i:
+                t_kernel.append(tk / 50)
+                t_torch.append(tt / 50)
+        agree = float((Y - Yt).abs().max() / Yt.abs().max())
+        torch.cuda.synchronize(dev)
+        base = torch.cuda.memory_allocated(dev)
+        torch.cuda.reset_peak_memory_stats(dev)
+        t0 = time.perf_counter()
+        res = tsne_embed(d2=d2, max_iter=max_iter, init="random")
+        torch.cuda.synchronize(dev)
+        wall = time.perf_counter() - t0
+        peak = torch.cuda.max_memory_allocated(dev) - base
+        torch.cuda.reset_peak_memory_stats(dev)
+        base = torch.cuda.memory_allocated(dev)
+        torch_steps(P, Y0, torch.zeros_like(Y0), torch.ones_like(Y0), 1, 12.0, 0.5, lr)
+        torch.cuda.synchronize(dev)
+        peak_torch = torch.cuda.max_memory_allocated(dev) - base
+        line = dict(workload=f"exact t-SNE of {N} unit-length rows ({D} values, {classes} blobs), perplexity 30, {max_iter} iterations, random start",
+                    affinities_ms_median=round(statistics.median(t for t, _ in aff[1:]), 3),
+                    schedule_wall_s=round(wall, 3), schedule_ms_per_iteration=round(wall * 1e3 / (res["n_iter"] + 1), 4), n_iter=res["n_iter"],
+                    kl_divergence=round(res["kl_divergence"], 6), neighbour_label_share=neighbour_label_share(res["embedding"], labels, 5),
+                    steps50_kernel_ms_per_iteration_median=round(statistics.median(t_kernel), 4),
+                    steps50_kernel_ms_per_iteration_min=round(min(t_kernel), 4),
+                    steps50_torch_fp64_ms_per_iteration_median=round(statistics.median(t_torch), 4),
+                    steps50_torch_fp64_ms_per_iteration_min=round(min(t_torch), 4),
+                    kernel_vs_torch_after_50_steps_rel=agree, schedule_peak_mb_above_inputs=round(peak / 1e6, 1),
+                    torch_step_peak_mb_above_inputs=round(peak_torch / 1e6, 1),
+                    note="schedule = tsne_embed on the resident distance matrix: affinities, the descent in chunks of 50 with one read-back of two "
+                         "numbers per chunk, the final KL and the transfer of the embedding, wall clock; steps50 = device events around 50 "
+                         "iterations, the two routes alternating, 5 timed after 1 warm-up; peak memory of a call above what is allocated before "
+                         "it (for the schedule that includes P, N^2 doubles)")
+        try:
+            from sklearn.manifold import TSNE
+        except ImportError:
+            line["sklearn"] = "not installed"
+            out.append(line)
+            continue
+        xh = x.cpu().numpy()
+        it_exact = max_iter if N <= 1000 else 250
+        for key, kw, its in (("sklearn_exact", dict(method="exact"), it_exact), ("sklearn_barnes_hut", dict(), max_iter)):
+            print(f"tsne N={N}: {key}, {its} iterations on the host ...", file=sys.stderr, flush=True)
+            t0 = time.perf_counter()
+            ts = TSNE(n_components=2, max_iter=its, init="random", random_state=0, **kw)
+            Ys = ts.fit_transform(xh)
+            dt = time.perf_counter() - t0
+            line.update({f"{key}_wall_s": round(dt, 2), f"{key}_iterations": int(ts.n_iter_) + 1,
+                         f"{key}_ms_per_iteration": round(dt * 1e3 / (int(ts.n_iter_) + 1), 3), f"{key}_kl": round(float(ts.kl_divergence_), 6) if ts.kl_divergence_ < 1e300 else None,   # (max_iter = 250: scikit-learn's second phase is empty and its error stays at the float maximum)
+                         f"{key}_neighbour_label_share": neighbour_label_share(Ys, labels, 5)})
+        out.append(line)
+    return out
+
+
 def run_niqe(dev, steps=20, warmup=3, H=1080, W=2048):
     """NIQE of one 1 x 3 x H x W image (a smooth random field plus fine noise, no flat block): the host ``calculate_niqe`` (numpy float64,
     one thread's wall time, best of 2) against ``calculate_niqe_device`` (the fused fp64 kernels of dcpt_amd/csrc/niqe.hip + the host
@@ -1330,7 +1439,7 @@ def run_niqe(dev, steps=20, warmup=3, H=1080, W=2048):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", required=True, choices=["dcpt", "dcpt_swinir", "restormer", "promptir", "infer2k", "naf", "swinir", "rcan", "val_metrics", "step_tail", "tlsc", "ssim_loss", "ldl", "jpeg", "niqe", "degrade", "noise", "blur", "poisson", "knn"])
+    ap.add_argument("--workload", required=True, choices=["dcpt", "dcpt_swinir", "restormer", "promptir", "infer2k", "naf", "swinir", "rcan", "val_metrics", "step_tail", "tlsc", "ssim_loss", "ldl", "jpeg", "niqe", "degrade", "noise", "blur", "poisson", "knn", "tsne"])
     ap.add_argument("--dtype", default="fp32", choices=["fp32", "bf16", "bf16_tail32", "bf16_edge32", "bf16_res32"])
     ap.add_argument("--head-dtype", default=None, choices=["fp32", "bf16"], help="dcpt: classifier-head activations (default: --dtype)")
     ap.add_argument("--restormer-save", default="balanced", choices=["auto", "lean", "balanced", "full"], help="what the Restormer halves keep for backward")
@@ -1542,6 +1651,11 @@ def main():
         res = run_poisson(dev, max(args.steps, 20), max(args.warmup, 3), args.batch or 32, args.size or 256)
     elif args.workload == "knn":
         res = run_knn(dev, max(args.steps, 20), max(args.warmup, 3), args.batch or 500, args.size or 524288)
+    elif args.workload == "tsne":
+        lines = run_tsne(dev, (args.batch,) if args.batch else (500, 4096))
+        for ln in lines[:-1]:
+            print(json.dumps(ln), flush=True)
+        res = lines[-1]
     elif args.workload == "tlsc":
         res = run_tlsc(dev, args.steps, args.warmup, tile=args.tile, streams=args.tile_streams)
     else:

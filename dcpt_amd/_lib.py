@@ -356,6 +356,12 @@ SIGNATURES = {
                                C.c_longlong, cint, cint, stream_t]),
     "dcpt_knn_vote_fwd": (cint, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, cint, cint, cint, cint, C.c_void_p, C.c_void_p,
                                  C.c_void_p, stream_t]),
+    "dcpt_tsne_steps_ws_bytes": (sz, [cint]),
+    "dcpt_tsne_affinity_fwd": (cint, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, cint, C.c_double, stream_t]),
+    "dcpt_tsne_joint_fwd": (cint, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p, sz, cint, stream_t]),
+    "dcpt_tsne_steps_fwd": (cint, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, sz, cint, cint, cint,
+                                   C.c_double, C.c_double, C.c_double, C.c_double, stream_t]),
+    "dcpt_tsne_kl_fwd": (cint, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, sz, cint, cint, C.c_double, stream_t]),
     "dcpt_trace_enable": (cint, [cint]),
     "dcpt_trace_read": (sz, [C.c_char_p, sz]),
     "dcpt_prof_enable": (cint, [cint]),

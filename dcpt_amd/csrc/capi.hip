@@ -627,3 +627,59 @@ extern "C" int dcpt_knn_vote_fwd(const double* d2, long long ldd, const int* q_i
     DCPT_CHECK_ARG((int64_t)S * nq <= (int64_t)0x7fffffff, "knn_vote_fwd: more than 2^31 - 1 queries over the splits (S=%d nq=%d)", S, nq);
     return launch_knn_vote_fwd(d2, ldd, q_idx, t_idx, labels, S, nq, nt, k, nbr, nbr_d2, pred, (hipStream_t)stream);
 }
+
+// ---------------------------------------------------------------------------------------------
+// Exact t-SNE on the distance matrix of the probe (tsne.hip)
+namespace {
+bool tsne_finite(double v) { return v == v && v - v == 0.0; }
+}  // namespace
+
+extern "C" size_t dcpt_tsne_steps_ws_bytes(int N) { return (N >= 2 && N <= TSNE_MAX_ROWS) ? tsne_ws_bytes(N) : 0; }
+
+extern "C" int dcpt_tsne_affinity_fwd(const double* d2, long long ldd, double* pcond, long long ldp, double* beta, int* steps, int N,
+                                      double perplexity, dcpt_stream_t stream) {
+    DCPT_CHECK_ARG(d2 && pcond && beta && steps, "tsne_affinity_fwd: null argument");
+    DCPT_CHECK_ARG(N >= 2 && N <= TSNE_MAX_ROWS, "tsne_affinity_fwd: N must lie in 2 .. 65535 (N=%d)", N);
+    DCPT_CHECK_ARG(tsne_finite(perplexity) && perplexity >= 1.0 && perplexity < (double)N,
+                   "tsne_affinity_fwd: the perplexity must be finite and lie in [1, N) (perplexity=%g N=%d)", perplexity, N);
+    DCPT_CHECK_ARG(ldd >= N && ldp >= N, "tsne_affinity_fwd: a leading dimension below N (ldd=%lld ldp=%lld N=%d)", ldd, ldp, N);
+    DCPT_CHECK_ARG((const void*)d2 != (const void*)pcond, "tsne_affinity_fwd: pcond must not be d2 (every step reads the distances again)");
+    return launch_tsne_affinity_fwd(d2, ldd, pcond, ldp, beta, steps, N, perplexity, (hipStream_t)stream);
+}
+
+extern "C" int dcpt_tsne_joint_fwd(const double* pcond, long long ldp, double* P, long long ldo, void* ws, size_t ws_bytes, int N,
+                                   dcpt_stream_t stream) {
+    DCPT_CHECK_ARG(pcond && P, "tsne_joint_fwd: null argument");
+    DCPT_CHECK_ARG(N >= 2 && N <= TSNE_MAX_ROWS, "tsne_joint_fwd: N must lie in 2 .. 65535 (N=%d)", N);
+    DCPT_CHECK_ARG(ldp >= N && ldo >= N, "tsne_joint_fwd: a leading dimension below N (ldp=%lld ldo=%lld N=%d)", ldp, ldo, N);
+    DCPT_CHECK_ARG((const void*)pcond != (const void*)P || ldp == ldo, "tsne_joint_fwd: P over pcond needs the same leading dimension");
+    DCPT_CHECK_WS("tsne_joint_fwd", ws, ws_bytes, tsne_ws_bytes(N));
+    return launch_tsne_joint_fwd(pcond, ldp, P, ldo, ws, N, (hipStream_t)stream);
+}
+
+extern "C" int dcpt_tsne_steps_fwd(const double* P, long long ldp, double* Y, double* update, double* gains, double* stats, void* ws,
+                                   size_t ws_bytes, int N, int out_dims, int n_steps, double exaggeration, double momentum, double lr,
+                                   double min_gain, dcpt_stream_t stream) {
+    DCPT_CHECK_ARG(P && Y && update && gains && stats, "tsne_steps_fwd: null argument");
+    DCPT_CHECK_ARG(out_dims == 2, "tsne_steps_fwd: only two output dimensions exist (out_dims=%d)", out_dims);
+    DCPT_CHECK_ARG(N >= 2 && N <= TSNE_MAX_ROWS, "tsne_steps_fwd: N must lie in 2 .. 65535 (N=%d)", N);
+    DCPT_CHECK_ARG(ldp >= N, "tsne_steps_fwd: a leading dimension below N (ldp=%lld N=%d)", ldp, N);
+    DCPT_CHECK_ARG(n_steps >= 0, "tsne_steps_fwd: n_steps below 0 (%d)", n_steps);
+    DCPT_CHECK_ARG(tsne_finite(exaggeration) && tsne_finite(momentum) && tsne_finite(lr) && tsne_finite(min_gain),
+                   "tsne_steps_fwd: exaggeration, momentum, lr and min_gain must be finite");
+    DCPT_CHECK_ARG(((uintptr_t)Y & 15) == 0, "tsne_steps_fwd: Y must be 16-byte aligned (a point is read as one pair)");
+    DCPT_CHECK_WS("tsne_steps_fwd", ws, ws_bytes, tsne_ws_bytes(N));
+    return launch_tsne_steps_fwd(P, ldp, Y, update, gains, stats, ws, N, n_steps, exaggeration, momentum, lr, min_gain, (hipStream_t)stream);
+}
+
+extern "C" int dcpt_tsne_kl_fwd(const double* P, long long ldp, const double* Y, double* grad, double* stats, void* ws, size_t ws_bytes, int N,
+                                int out_dims, double exaggeration, dcpt_stream_t stream) {
+    DCPT_CHECK_ARG(P && Y && grad && stats, "tsne_kl_fwd: null argument");
+    DCPT_CHECK_ARG(out_dims == 2, "tsne_kl_fwd: only two output dimensions exist (out_dims=%d)", out_dims);
+    DCPT_CHECK_ARG(N >= 2 && N <= TSNE_MAX_ROWS, "tsne_kl_fwd: N must lie in 2 .. 65535 (N=%d)", N);
+    DCPT_CHECK_ARG(ldp >= N, "tsne_kl_fwd: a leading dimension below N (ldp=%lld N=%d)", ldp, N);
+    DCPT_CHECK_ARG(tsne_finite(exaggeration), "tsne_kl_fwd: the exaggeration must be finite");
+    DCPT_CHECK_ARG(((uintptr_t)Y & 15) == 0, "tsne_kl_fwd: Y must be 16-byte aligned (a point is read as one pair)");
+    DCPT_CHECK_WS("tsne_kl_fwd", ws, ws_bytes, tsne_ws_bytes(N));
+    return launch_tsne_kl_fwd(P, ldp, Y, grad, stats, ws, N, exaggeration, (hipStream_t)stream);
+}

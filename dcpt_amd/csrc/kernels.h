@@ -253,3 +253,17 @@ int launch_pdist2_fwd(const void* xq, const void* xt, double* d2, void* ws, int 
 // The k nearest training columns of every query row and their majority label, S splits in one launch (dcpt_knn_vote_fwd); no workspace.
 int launch_knn_vote_fwd(const double* d2, int64_t ldd, const int* q_idx, const int* t_idx, const int* labels, int S, int nq, int nt, int k, int* nbr,
                         double* nbr_d2, int* pred, hipStream_t s);
+
+// ---- tsne.hip -------------------------------------------------------------------------------
+// Exact t-SNE on an fp64 squared-distance matrix (dcpt_tsne_*_fwd): the perplexity search per row, the symmetric joint probabilities, and
+// descent iterations of two plain launches each.  One workspace layout serves the joint pass (N row sums) and the descent (the second
+// embedding buffer and three per-row partials): tsne_ws_bytes, shape-only.
+constexpr int TSNE_MAX_ROWS = 65535;
+size_t tsne_ws_bytes(int N);
+int launch_tsne_affinity_fwd(const double* d2, int64_t ldd, double* pcond, int64_t ldp, double* beta, int* steps, int N, double perplexity,
+                             hipStream_t s);
+int launch_tsne_joint_fwd(const double* pcond, int64_t ldp, double* P, int64_t ldo, void* ws, int N, hipStream_t s);
+int launch_tsne_steps_fwd(const double* P, int64_t ldp, double* Y, double* update, double* gains, double* stats, void* ws, int N, int n_steps,
+                          double exaggeration, double momentum, double lr, double min_gain, hipStream_t s);
+int launch_tsne_kl_fwd(const double* P, int64_t ldp, const double* Y, double* grad, double* stats, void* ws, int N, double exaggeration,
+                       hipStream_t s);

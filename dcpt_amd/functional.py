@@ -10,6 +10,7 @@ shapes while the kernels see contiguous channel rows.  The 3-channel image stays
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os as _os
 from typing import Dict, NamedTuple, Optional, Tuple
 
@@ -3237,6 +3238,98 @@ def knn_vote(d2, labels, train_idx, test_idx, k):
     ldd = d2.stride(0) if d2.shape[0] > 1 else d2.shape[1]
     _call(_lib.load().dcpt_knn_vote_fwd, (d2, ldd, q_idx, t_idx, labels), (S, nq, nt, k, nbr.data_ptr(), nbr_d2.data_ptr(), pred.data_ptr()), dev)
     return pred, nbr, nbr_d2
+
+
+# ------------------------------------------------------------------------------------------------
+# Exact t-SNE on the probe's distance matrix (include/dcpt_hip.h dcpt_tsne_affinity_fwd, dcpt_tsne_joint_fwd, dcpt_tsne_steps_fwd,
+# dcpt_tsne_kl_fwd): scikit-learn's method="exact" rules in fp64, two output dimensions.  Forward only.
+TSNE_MAX_ROWS = 65535
+
+
+def _tsne_matrix(op, name, m, N=None):
+    """a float64 (N, N) device tensor with contiguous rows -> (detached tensor, leading dimension)"""
+    if not torch.is_tensor(m):
+        raise _lib.DcptHipError(f"{op} takes device tensors (got {type(m).__name__} for {name})")
+    _require((m,), (torch.float64,), op + ": " + name + " must be float64 (got {})")
+    if m.dim() != 2 or m.shape[0] != m.shape[1] or m.stride(1) != 1 or m.stride(0) < m.shape[1] or (N is not None and m.shape[0] != N):
+        raise ValueError(f"{op}: {name} must be a square 2-D tensor with contiguous rows" + (f" of {N} rows" if N is not None else "")
+                         + f", got shape {tuple(m.shape)} strides {m.stride()}")
+    if not 2 <= m.shape[0] <= TSNE_MAX_ROWS:
+        raise ValueError(f"{op}: N must lie in 2 .. {TSNE_MAX_ROWS}, got {m.shape[0]}")
+    return m.detach(), m.stride(0)
+
+
+def _tsne_points(op, name, y, N, dev):
+    """a dense float64 (N, 2) tensor on ``dev``"""
+    if not torch.is_tensor(y):
+        raise _lib.DcptHipError(f"{op} takes device tensors (got {type(y).__name__} for {name})")
+    _require((y,), (torch.float64,), op + ": " + name + " must be float64 (got {})")
+    if y.dim() != 2 or y.shape[1] != 2:
+        raise ValueError(f"{op}: only two output dimensions exist; {name} must be ({N}, 2), got {tuple(y.shape)}")
+    if y.shape[0] != N or y.device != dev or not y.is_contiguous():
+        raise ValueError(f"{op}: {name} must be a contiguous ({N}, 2) tensor on {dev}, got {tuple(y.shape)} strides {y.stride()} on {y.device}")
+    return y.detach()
+
+
+def tsne_affinities(d2, perplexity, return_conditional=False):
+    """The joint probabilities of exact t-SNE from a float64 (N, N) squared-distance device tensor with contiguous rows (what
+    ``pairwise_sqdist`` returns): per row the binary search on beta for the given perplexity (at most 100 steps, tolerance 1e-5 on the
+    entropy), then ``P = max((pcond + pcond^t) / sum, 2^-52)`` with a zero diagonal.  Returns ``(P, beta, steps)``: float64 (N, N),
+    symmetric bit for bit; float64 (N,); int32 (N,) the index of the last search step of a row.  The diagonal of ``d2`` is never read, and
+    the distances are not rounded to float32 as scikit-learn does.  ``return_conditional``: also return the conditional affinities of the
+    search, float64 (N, N), as a fourth value.  Nothing is read back."""
+    d2, ldd = _tsne_matrix("tsne_affinities", "d2", d2)
+    N, dev, perplexity = d2.shape[0], d2.device, float(perplexity)
+    if not (math.isfinite(perplexity) and 1.0 <= perplexity < N):
+        raise ValueError(f"tsne_affinities: the perplexity must be finite and lie in [1, N = {N}), got {perplexity}")
+    P = torch.empty((N, N), dtype=torch.float64, device=dev)
+    beta = torch.empty(N, dtype=torch.float64, device=dev)
+    steps = torch.empty(N, dtype=torch.int32, device=dev)
+    lib = _lib.load()
+    nws = _check_ws("tsne_affinities", lib.dcpt_tsne_steps_ws_bytes(N), f"N={N}")
+    ws = _workspace(dev, nws)
+    pcond = torch.empty_like(P) if return_conditional else P   # (the joint pass may write over its input)
+    _call(lib.dcpt_tsne_affinity_fwd, (d2, ldd, pcond, N, beta, steps), (N, perplexity), dev)
+    _call(lib.dcpt_tsne_joint_fwd, (pcond, N, P, N, ws, nws), (N,), dev)
+    return (P, beta, steps, pcond) if return_conditional else (P, beta, steps)
+
+
+def tsne_steps(P, Y, update, gains, n_steps, exaggeration, momentum, lr, min_gain=0.01):
+    """``n_steps`` descent iterations of exact t-SNE on ``Y``, ``update`` and ``gains`` (contiguous float64 (N, 2) device tensors), in
+    place, with ``exaggeration * P`` for P, scikit-learn's gain rule (+0.2 / x0.8, floor ``min_gain``), ``momentum`` and step ``lr``.
+    Returns ``stats``, a float64 device tensor of 2: the KL divergence at the Y before the last move and the norm of the last gain-scaled
+    gradient.  Nothing is read back; with ``n_steps = 0`` nothing is launched and ``stats`` is NaN."""
+    P, ldp = _tsne_matrix("tsne_steps", "P", P)
+    N, dev = P.shape[0], P.device
+    Y, update, gains = (_tsne_points("tsne_steps", n, t, N, dev) for n, t in (("Y", Y), ("update", update), ("gains", gains)))
+    n_steps = int(n_steps)
+    pars = tuple(float(v) for v in (exaggeration, momentum, lr, min_gain))
+    if n_steps < 0 or not all(math.isfinite(v) for v in pars):
+        raise ValueError(f"tsne_steps: n_steps must be at least 0 and exaggeration, momentum, lr, min_gain finite, got {n_steps} {pars}")
+    stats = torch.full((2,), float("nan"), dtype=torch.float64, device=dev)
+    lib = _lib.load()
+    nws = _check_ws("tsne_steps", lib.dcpt_tsne_steps_ws_bytes(N), f"N={N}")
+    ws = _workspace(dev, nws)
+    _call(lib.dcpt_tsne_steps_fwd, (P, ldp, Y, update, gains, stats, ws, nws), (N, 2, n_steps, *pars), dev)
+    return stats
+
+
+def tsne_kl(P, Y, exaggeration=1.0):
+    """The KL divergence of exact t-SNE and its plain gradient at ``Y`` (contiguous float64 (N, 2) device tensor), which does not move:
+    ``(kl, grad)``, a float64 device scalar and a float64 (N, 2) tensor, with ``exaggeration * P`` for P.  Nothing is read back."""
+    P, ldp = _tsne_matrix("tsne_kl", "P", P)
+    N, dev = P.shape[0], P.device
+    Y = _tsne_points("tsne_kl", "Y", Y, N, dev)
+    exaggeration = float(exaggeration)
+    if not math.isfinite(exaggeration):
+        raise ValueError(f"tsne_kl: the exaggeration must be finite, got {exaggeration}")
+    grad = torch.empty((N, 2), dtype=torch.float64, device=dev)
+    stats = torch.empty(2, dtype=torch.float64, device=dev)
+    lib = _lib.load()
+    nws = _check_ws("tsne_kl", lib.dcpt_tsne_steps_ws_bytes(N), f"N={N}")
+    ws = _workspace(dev, nws)
+    _call(lib.dcpt_tsne_kl_fwd, (P, ldp, Y, grad, stats, ws, nws), (N, 2, exaggeration), dev)
+    return stats[0], grad
 
 
 # ------------------------------------------------------------------------------------------------

@@ -1090,6 +1090,56 @@ int dcpt_pdist2_fwd(const void* xq, const void* xt, double* d2, void* ws, size_t
 int dcpt_knn_vote_fwd(const double* d2, long long ldd, const int* q_idx, const int* t_idx, const int* labels, int S, int nq, int nt, int k,
                       int* nbr, double* nbr_d2, int* pred, dcpt_stream_t stream);
 
+/* ---- exact t-SNE of the probe's features, on the device -------------------------------------------------------------
+ * the other half of the reference's feature analysis (t_sne.py: sklearn.manifold.TSNE(n_components=2) on the unit-length rows): the rules
+ * of scikit-learn's method="exact", as functions of the squared-distance matrix dcpt_pdist2_fwd produces.  All arithmetic is fp64; plain
+ * launches, plain stores, no atomics; two runs give the same bits; a row's result depends on that row's inputs and on N only.
+ * EPS = 2^-52.  Every sum is taken in one of two orders: BLOCK order -- lane t of 256 adds its terms j = t, t + 256, ... in ascending j,
+ * the 256 sums go through a fixed binary tree (t += t + 128, 64, ... 1) -- or WAVE order -- lane t of 64 adds j = t, t + 64, ..., the 64
+ * sums go through the xor butterfly 32, 16, ... 1.  N is 2 .. 65535 everywhere and only two output dimensions exist.
+ *
+ * dcpt_tsne_affinity_fwd: d2 fp64 [N] rows of N, row i at element i ldd -> pcond fp64 (row i at i ldp), beta fp64 [N], steps int32 [N].
+ * Per row i, j over all columns but i (the diagonal of d2 is never read; pcond[i][i] = 0):
+ *     beta = 1; lo = -inf; hi = +inf
+ *     for l in 0..99:
+ *         p_j = exp(-d2[i][j] * beta);  s = sum_j p_j (block order);  if s == 0: s = 1e-8;  p_j = p_j / s
+ *         sd = sum_j d2[i][j] * p_j (block order);  e = log(s) + beta * sd - log(perplexity);  if |e| <= 1e-5: break
+ *         e > 0: lo = beta; beta = beta * 2 if hi == +inf else (beta + hi) / 2
+ *         else:  hi = beta; beta = beta / 2 if lo == -inf else (beta + lo) / 2
+ * pcond holds the p of the last step run, steps the index l of that step (99 when the search did not end), beta the value after the loop.
+ * scikit-learn rounds the distances to float32 before this search; the kernel does not.  beta moves by exact dyadic arithmetic.
+ * Errors: null pointers, N outside 2 .. 65535, a perplexity that is not finite or outside [1, N), ldd or ldp below N, pcond == d2.
+ *
+ * dcpt_tsne_joint_fwd: r_i = sum_{j != i} (pcond_ij + pcond_ji) (block order), S = max(sum_i r_i, EPS) (block order over i),
+ *     P_ij = P_ji = max((pcond_ij + pcond_ji) / S, EPS) for i != j, P_ii = 0.     P (row i at i ldo) may be pcond; P is symmetric bit for bit.
+ * ws: dcpt_tsne_steps_ws_bytes(N).  Errors: null pointers, N, ldp or ldo below N, P == pcond with ldo != ldp, a short workspace.
+ *
+ * dcpt_tsne_steps_fwd: n_steps >= 0 descent iterations on Y, update and gains (fp64 [N][2] each, dense), in place.  One iteration, with
+ * P' = exaggeration P and w_ij = 1 / (1 + (dx^2 + dy^2)), (dx, dy) = y_i - y_j, an IEEE division:
+ *     z_i = sum_{j != i} w_ij (wave order);  Z = sum_i z_i (wave order over i);  Q_ij = max(w_ij / Z, EPS)
+ *     g_i = 4 * sum_{j != i} (P'_ij - Q_ij) w_ij (y_i - y_j)      (wave order, per component)
+ *     per component: gains = (update * g < 0) ? gains + 0.2 : gains * 0.8;  gains = max(gains, min_gain);  g = g * gains;
+ *                    update = momentum * update - lr * g;  y = y + update
+ * On the last of the n_steps iterations also (device array stats[2]; nothing is read back):
+ *     stats[0] = sum_i [ sum_{j != i} P'_ij log(max(P'_ij, EPS) / Q_ij) (wave order) ] (block order over i)    -- at the Y before that move
+ *     stats[1] = sqrt( sum_i (g_i0^2 + g_i1^2) (block order over i) ) of the gain-scaled g: scikit-learn's gradient norm
+ * n_steps = 0 touches nothing.  Two launches per iteration, a third on the last; the new points go to a second embedding buffer in the
+ * workspace, so no wave reads a row that another writes.  out_dims must be 2.
+ * dcpt_tsne_kl_fwd: the same evaluation at a Y that does not move: grad fp64 [N][2] = the plain g, stats[0] as above, stats[1] = |g|.
+ * dcpt_tsne_steps_ws_bytes needs no device; it returns 0 for N outside 2 .. 65535 and serves the joint pass, the steps and the KL pass.
+ * Errors (before any launch): null pointers, out_dims other than 2, N outside 2 .. 65535, ldp below N, n_steps below 0, a parameter that
+ * is not finite, a Y that is not 16-byte aligned, a workspace below the query. */
+size_t dcpt_tsne_steps_ws_bytes(int N);
+int dcpt_tsne_affinity_fwd(const double* d2, long long ldd, double* pcond, long long ldp, double* beta, int* steps, int N,
+                           double perplexity, dcpt_stream_t stream);
+int dcpt_tsne_joint_fwd(const double* pcond, long long ldp, double* P, long long ldo, void* ws, size_t ws_bytes, int N,
+                        dcpt_stream_t stream);
+int dcpt_tsne_steps_fwd(const double* P, long long ldp, double* Y, double* update, double* gains, double* stats, void* ws,
+                        size_t ws_bytes, int N, int out_dims, int n_steps, double exaggeration, double momentum, double lr,
+                        double min_gain, dcpt_stream_t stream);
+int dcpt_tsne_kl_fwd(const double* P, long long ldp, const double* Y, double* grad, double* stats, void* ws, size_t ws_bytes, int N,
+                     int out_dims, double exaggeration, dcpt_stream_t stream);
+
 /* ---- optional launch profiling (bench.py) -------------------------------------------------------
  * While enabled, MFMA GEMM launches are bracketed by HIP events on their own stream: every launch for on = 1, every
  * on-th launch for on > 1 (sampling keeps the perturbation of a timed region small: an event pair costs ~3 us of queue time).
@@ -1097,7 +1147,7 @@ int dcpt_knn_vote_fwd(const double* d2, long long ldd, const int* q_idx, const i
  * algorithmic flops, algorithmic bytes}, one per (class, shape); class id = 16*loaderA + epilogue (NT) or
  * 512 + 8*loaderX + loaderY (TN); 1024 + i for a few non-GEMM launches (1032 / 1033: the level pass and the sampler of
  * dcpt_poisson_noise_fwd, M = the batch's elements; 1034 .. 1036: the norm, MFMA and finishing passes of dcpt_pdist2_fwd; 1037:
- * dcpt_knn_vote_fwd). */
+ * dcpt_knn_vote_fwd; 1038 .. 1042: the affinity, joint, z-partial, gradient and statistics launches of dcpt_tsne_*_fwd, M = N). */
 int dcpt_prof_enable(int on);
 int dcpt_prof_read(double* out, int max_rows);
 
