@@ -416,9 +416,12 @@ class SRModel(BaseModel):
     def _device_metric_plan(self, metrics_opt, clamp):
         """``val.device_metrics: true`` (opt-in): which metrics are scored on the device (basicsr.metrics.MetricSums), as
         {name: ((crop_border, test_y_channel, image_range), "psnr" | "ssim")}, and ``calculate_niqe`` (basicsr.metrics.NiqeSums) as
-        {name: (("niqe", crop_border, pris_params), "niqe")}.  Only what the kernels mirror exactly qualifies: clamped images,
-        ``calculate_psnr`` / ``calculate_ssim`` / ``calculate_niqe``, BCHW order, image_range 255 or 1; any other metric keeps the host
-        function, and without ``clamp`` (raw outputs, NaNs included) or off the GPU the whole call does."""
+        {name: (("niqe", crop_border, pris_params), "niqe")}; ``calculate_msssim`` / ``calculate_ssim_matlab`` / ``calculate_nrmse`` as
+        {name: ((kind, crop_border, test_y_channel, image_range[, weights tuple or None]), kind)}, kind = "msssim" | "ssim_matlab" | "nrmse"
+        (MetricSums with that kind alone).  Only what the kernels mirror exactly qualifies: clamped images, these metric types, BCHW
+        order, image_range 255 or 1, at most 8 MS-SSIM weights; any other metric (``calculate_psnr_pt`` among them: it takes tensors, which
+        validation does not hand out) keeps the host function, and without ``clamp`` (raw outputs, NaNs included) or off the GPU the whole
+        call does."""
         if not self.opt["val"].get("device_metrics", False) or not clamp or self.device.type != "cuda":
             return {}
         plan = {}
@@ -427,10 +430,21 @@ class SRModel(BaseModel):
                 if mo.get("input_order", "BCHW") == "BCHW":
                     plan[m] = (("niqe", int(mo.get("crop_border", 0)), mo.get("pris_params")), "niqe")
                 continue
-            kind = {"calculate_psnr": "psnr", "calculate_ssim": "ssim"}.get(mo.get("type"))
+            kind = {"calculate_psnr": "psnr", "calculate_ssim": "ssim", "calculate_msssim": "msssim", "calculate_ssim_matlab": "ssim_matlab",
+                    "calculate_nrmse": "nrmse"}.get(mo.get("type"))
             if kind is None or mo.get("input_order", "BCHW") != "BCHW" or mo.get("image_range", 255) not in (255, 1):
                 continue
-            plan[m] = ((int(mo.get("crop_border", 0)), bool(mo.get("test_y_channel", False)), mo.get("image_range", 255)), kind)
+            key = (int(mo.get("crop_border", 0)), bool(mo.get("test_y_channel", False)), mo.get("image_range", 255))
+            if kind in ("psnr", "ssim"):
+                plan[m] = (key, kind)
+                continue
+            # the further kinds: an accumulator of their own per option set, the key carries the kind and its extra options
+            weights = mo.get("weights")
+            if kind == "msssim":
+                if weights is not None and not 1 <= len(weights) <= 8:   # (the kernel's level cap; an empty list fails on the host as in the reference)
+                    continue
+                key += (None if weights is None else tuple(float(w) for w in weights),)
+            plan[m] = ((kind, *key), kind)
         return plan
 
     def _validate_on_device(self, val_data, name, save_img, metrics_opt, on_device, sums, results):
@@ -458,6 +472,9 @@ class SRModel(BaseModel):
                 kinds = {k for kk, k in on_device.values() if kk == key}
                 if key[0] == "niqe":
                     sums[key] = NiqeSums(crop_border=key[1], pris_params=key[2])
+                elif isinstance(key[0], str):   # ("msssim", crop_border, test_y_channel, image_range, weights) / ("ssim_matlab" | "nrmse", ...)
+                    sums[key] = MetricSums(crop_border=key[1], test_y_channel=key[2], image_range=key[3], psnr=False, ssim=False,
+                                           weights=list(key[4]) if len(key) > 4 and key[4] is not None else None, **{key[0]: True})
                 else:
                     sums[key] = MetricSums(crop_border=key[0], test_y_channel=key[1], image_range=key[2], psnr="psnr" in kinds,
                                            ssim="ssim" in kinds)

@@ -2,7 +2,7 @@
 """Secondary workloads of BASELINE.json (configs[2..4]) on ONE MI355X -- evidence for DESIGN.md, not the driver's
 contract (that is bench.py).  Prints one JSON line per workload.
 
-    python bench_extra.py --workload dcpt|dcpt_swinir|restormer|promptir|infer2k|naf|swinir|rcan|val_metrics|step_tail|tlsc|ssim_loss|ldl|jpeg|niqe|degrade|noise|blur|poisson|knn|tsne [--dtype fp32|bf16|bf16_res32] [--steps K] [--warmup W]
+    python bench_extra.py --workload dcpt|dcpt_swinir|restormer|promptir|infer2k|naf|swinir|rcan|val_metrics|val_metrics_ms|step_tail|tlsc|ssim_loss|ldl|jpeg|niqe|degrade|noise|blur|poisson|knn|tsne [--dtype fp32|bf16|bf16_res32] [--steps K] [--warmup W]
 
 ``--dtype bf16`` (dcpt, naf, infer2k, restormer, promptir; rcan: the inference line only, next to fp32; swinir: the restoration form's inference, next to fp32): every feature map of the encoder in bf16 storage with fp32 accumulation (act_dtype="bf16";
 dcpt: the classifier head too unless --head-dtype fp32); images, parameters and the optimizer stay fp32.  Its lines carry BOTH
@@ -492,6 +492,78 @@ def run_val_metrics(dev, steps=5, warmup=2, H=1080, W=2048):
                 device_ms=round(dt * 1e3, 3), steps=steps, warmup=warmup, psnr_host=psnr_h, psnr_device=vals["psnr"][0], ssim_host=ssim_h,
                 ssim_device=vals["ssim"][0], note="device_ms: clamp of both images + two launches + one 32-byte transfer, host clock around "
                                                   "a synchronised region")
+
+
+def run_val_metrics_ms(dev, steps=5, warmup=2, H=1080, W=2048):
+    """MS-SSIM, MATLAB SSIM and NRMSE of one 3 x H x W pair (crop_border 0, RGB, image_range 255), one JSON line each: the host function of
+    basicsr.metrics on the arrays SRModel.get_current_visuals hands it (one repetition, the copies timed apart) against the device function
+    (kernels of dcpt_amd/csrc/metrics_ms.hip, sums fetched in one transfer) and against the same arithmetic as float64 torch expressions
+    on the device (F.conv2d with the outer-product window, F.pad(mode="replicate"); value fetched with one .item())."""
+    import torch.nn.functional as F
+
+    from basicsr.metrics import (MSSSIM_WEIGHTS, calculate_msssim, calculate_msssim_device, calculate_nrmse, calculate_nrmse_device,
+                                 calculate_ssim_matlab, calculate_ssim_matlab_device)
+
+    g = torch.Generator(device=dev).manual_seed(1234)
+    gt = torch.rand((1, 3, H, W), generator=g, device=dev)
+    out = (gt + 0.05 * torch.randn((1, 3, H, W), generator=g, device=dev)).clamp(0, 1)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    res_h, gt_h = out.cpu().numpy(), gt.cpu().numpy()
+    t_copy = time.perf_counter() - t0
+    k1 = torch.exp(-((torch.arange(11, dtype=torch.float64, device=dev) - 5.0) ** 2) / (2 * 1.5 ** 2))
+    k1 = k1 / k1.sum()
+    win = torch.outer(k1, k1).view(1, 1, 11, 11)
+    c1, c2 = (0.01 * 255) ** 2, (0.03 * 255) ** 2
+    quant = lambda t: (t * 255.0).round().double()  # noqa: E731
+
+    def moments(x, y, w):
+        cv = lambda t: F.conv2d(t, w, groups=w.shape[0])  # noqa: E731
+        mu1, mu2 = cv(x), cv(y)
+        return mu1 * mu1, mu2 * mu2, mu1 * mu2, cv(x * x) - mu1 * mu1, cv(y * y) - mu2 * mu2, cv(x * y) - mu1 * mu2
+
+    def blur(t):
+        p = F.pad(t, (0, 1, 0, 1), mode="replicate")
+        return 0.25 * ((p[..., :-1, :-1] + p[..., :-1, 1:]) + (p[..., 1:, :-1] + p[..., 1:, 1:]))
+
+    def torch_msssim():
+        x, y, v = quant(out), quant(gt), 1.0
+        for k, wk in enumerate(MSSSIM_WEIGHTS):
+            m1, m2, m12, s1, s2, s12 = moments(x[:, k % 3:k % 3 + 1], y[:, k % 3:k % 3 + 1], win)
+            cs = (2 * s12 + c2) / (s1 + s2 + c2)
+            last = k == len(MSSSIM_WEIGHTS) - 1
+            v = v * ((((2 * m12 + c1) / (m1 + m2 + c1)) * cs).mean() if last else cs.mean()) ** wk
+            if not last:
+                x, y = blur(x), blur(y)
+        return v.item()
+
+    def torch_matlab():
+        pad = lambda t: F.pad(t, (5, 5, 5, 5), mode="replicate")  # noqa: E731
+        m1, m2, m12, s1, s2, s12 = moments(pad(quant(out)), pad(quant(gt)), win.expand(3, 1, 11, 11))
+        per = (((2 * m12 + c1) * (2 * s12 + c2)) / ((m1 + m2 + c1) * (s1 + s2 + c2))).mean(dim=(0, 2, 3))
+        return ((per.sum() + per[-1]) / 4).item()
+
+    def torch_nrmse():
+        x, y = quant(out), quant(gt)
+        return (((x - y) ** 2).mean().sqrt() / (x.max() - x.min())).item()
+
+    lines = []
+    for name, host_fn, dev_fn, torch_fn in (("MS-SSIM (5 levels)", calculate_msssim, calculate_msssim_device, torch_msssim),
+                                            ("MATLAB SSIM", calculate_ssim_matlab, calculate_ssim_matlab_device, torch_matlab),
+                                            ("NRMSE", calculate_nrmse, calculate_nrmse_device, torch_nrmse)):
+        t0 = time.perf_counter()
+        v_host = host_fn(res_h, gt_h, 0)
+        t_host = time.perf_counter() - t0
+        vals = {}
+        dt_dev = timed(lambda: vals.update(device=dev_fn(out, gt, 0)), steps, warmup)
+        dt_torch = timed(lambda: vals.update(torch=torch_fn()), steps, warmup)
+        lines.append(dict(workload=f"validation metric of one 3 x {H} x {W} pair: {name}, crop_border 0, RGB, image_range 255",
+                          host_ms=round(t_host * 1e3, 2), host_copy_ms=round(t_copy * 1e3, 2), host_repetitions=1,
+                          device_ms=round(dt_dev * 1e3, 3), torch_fp64_ms=round(dt_torch * 1e3, 3), steps=steps, warmup=warmup,
+                          value_host=v_host, value_device=vals["device"], value_torch_fp64=vals["torch"],
+                          note="host_ms excludes host_copy_ms (the two device-to-host copies the host route needs, shared by the three "
+                               "metrics); device_ms / torch_fp64_ms: host clock around a synchronised region, the result fetched each step"))
+    return lines
 
 
 def run_step_tail(dev, steps=50, warmup=5, rounds=7, max_norm=1.0, decay=0.999):
@@ -1439,7 +1511,7 @@ def run_niqe(dev, steps=20, warmup=3, H=1080, W=2048):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", required=True, choices=["dcpt", "dcpt_swinir", "restormer", "promptir", "infer2k", "naf", "swinir", "rcan", "val_metrics", "step_tail", "tlsc", "ssim_loss", "ldl", "jpeg", "niqe", "degrade", "noise", "blur", "poisson", "knn", "tsne"])
+    ap.add_argument("--workload", required=True, choices=["dcpt", "dcpt_swinir", "restormer", "promptir", "infer2k", "naf", "swinir", "rcan", "val_metrics", "val_metrics_ms", "step_tail", "tlsc", "ssim_loss", "ldl", "jpeg", "niqe", "degrade", "noise", "blur", "poisson", "knn", "tsne"])
     ap.add_argument("--dtype", default="fp32", choices=["fp32", "bf16", "bf16_tail32", "bf16_edge32", "bf16_res32"])
     ap.add_argument("--head-dtype", default=None, choices=["fp32", "bf16"], help="dcpt: classifier-head activations (default: --dtype)")
     ap.add_argument("--restormer-save", default="balanced", choices=["auto", "lean", "balanced", "full"], help="what the Restormer halves keep for backward")
@@ -1627,6 +1699,11 @@ def main():
         res = lines[-1]
     elif args.workload == "val_metrics":
         res = run_val_metrics(dev, args.steps, args.warmup)
+    elif args.workload == "val_metrics_ms":
+        lines = run_val_metrics_ms(dev, args.steps, args.warmup)
+        for line in lines[:-1]:
+            print(json.dumps(line), flush=True)
+        res = lines[-1]
     elif args.workload == "step_tail":
         res = run_step_tail(dev, max(args.steps, 20), args.warmup)
     elif args.workload == "ssim_loss":

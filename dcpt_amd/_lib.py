@@ -333,6 +333,12 @@ SIGNATURES = {
     "dcpt_bottleneck_bwd_bf16": (cint, [f32p, f32p, C.POINTER(BneckGroup), f32p, C.c_void_p, sz, cint, cint, cint, cint, stream_t]),
     "dcpt_imgmetric_ws_bytes": (sz, [cint, cint, cint, cint, cint, cint]),
     "dcpt_imgmetric": (cint, [f32p, f32p, C.c_void_p, C.c_void_p, C.c_void_p, sz, cint, cint, cint, cint, cint, cint, stream_t]),
+    "dcpt_msssim_ws_bytes": (sz, [cint, cint, cint, cint, cint, cint, cint]),
+    "dcpt_msssim": (cint, [f32p, f32p, C.c_void_p, C.c_void_p, sz, cint, cint, cint, cint, cint, cint, cint, stream_t]),
+    "dcpt_ssim_matlab_ws_bytes": (sz, [cint, cint, cint, cint, cint, cint]),
+    "dcpt_ssim_matlab": (cint, [f32p, f32p, C.c_void_p, C.c_void_p, sz, cint, cint, cint, cint, cint, cint, stream_t]),
+    "dcpt_imgrange_ws_bytes": (sz, [cint, cint, cint, cint, cint, cint]),
+    "dcpt_imgrange": (cint, [f32p, C.c_void_p, C.c_void_p, sz, cint, cint, cint, cint, cint, cint, stream_t]),
     "dcpt_ssim_loss_ws_bytes": (sz, [cint, cint, cint, cint, cint, cint, cint]),
     "dcpt_ssim_loss_fwd": (cint, [f32p, f32p, C.c_void_p, C.c_void_p, sz, cint, cint, cint, cint, cint, cint, C.c_double, stream_t]),
     "dcpt_ssim_loss_bwd": (cint, [f32p, f32p, C.c_void_p, f32p, C.c_void_p, sz, cint, cint, cint, cint, cint, cint, C.c_double, stream_t]),

@@ -312,6 +312,99 @@ extern "C" int dcpt_imgmetric(const float* img, const float* img2, void* sse_out
 }
 
 // ---------------------------------------------------------------------------------------------
+// MS-SSIM, MATLAB SSIM and the NRMSE range (metrics_ms.hip)
+namespace {
+enum { MS_MSSSIM, MS_MATLAB, MS_RANGE };
+// 0 on success; the message names what is wrong with the shape / flags (the words dcpt_imgmetric uses for the same faults)
+const char* msmetric_check(int kind, int B, int C, int H, int W, int crop, int flags, int levels) {
+    static const char* const msg[3][8] = {
+        {"msssim: bad shape", "msssim: C must be 1 or 3", "msssim: crop_border must be >= 0",
+         "msssim: unknown flag (DCPT_METRIC_Y and DCPT_METRIC_RANGE1 are taken)", "msssim: nothing left after the crop",
+         "msssim: MS-SSIM needs a cropped image of at least 11 x 11", "msssim: levels must be 1 .. 8", "msssim: B * C * levels above 65535"},
+        {"ssim_matlab: bad shape", "ssim_matlab: C must be 1 or 3", "ssim_matlab: crop_border must be >= 0",
+         "ssim_matlab: unknown flag (DCPT_METRIC_Y and DCPT_METRIC_RANGE1 are taken)", "ssim_matlab: nothing left after the crop", "", "",
+         "ssim_matlab: B * C above 65535"},
+        {"imgrange: bad shape", "imgrange: C must be 1 or 3", "imgrange: crop_border must be >= 0",
+         "imgrange: unknown flag (DCPT_METRIC_Y and DCPT_METRIC_RANGE1 are taken)", "imgrange: nothing left after the crop", "", "",
+         "imgrange: B * C above 65535"}};
+    const char* const* w = msg[kind];
+    if (B <= 0 || H <= 0 || W <= 0) return w[0];
+    if (C != 1 && C != 3) return w[1];
+    if (crop < 0) return w[2];
+    if (flags & ~(DCPT_METRIC_Y | DCPT_METRIC_RANGE1)) return w[3];
+    if ((int64_t)H - 2 * (int64_t)crop <= 0 || (int64_t)W - 2 * (int64_t)crop <= 0) return w[4];
+    if (kind == MS_MSSSIM && (H - 2 * crop < 11 || W - 2 * crop < 11)) return w[5];
+    if (kind == MS_MSSSIM && (levels < 1 || levels > MSSSIM_MAX_LEVELS)) return w[6];
+    if ((int64_t)B * C * (kind == MS_MSSSIM ? levels : 1) > 65535) return w[7];   // (the grid's y extent; C, not C': one bound for both luma settings)
+    return nullptr;
+}
+size_t msmetric_part_doubles(int kind, int B, int C, int H, int W, int crop, int flags, int levels) {
+    const int Cp = ((flags & DCPT_METRIC_Y) && C == 3) ? 1 : C;
+    const int Hc = H - 2 * crop, Wc = W - 2 * crop;
+    if (kind == MS_MSSSIM) return (size_t)B * levels * metric_num_tiles(Hc, Wc) * 2;
+    if (kind == MS_MATLAB) return (size_t)B * Cp * ssim_matlab_num_tiles(Hc, Wc);
+    return (size_t)B * (size_t)imgrange_num_chunks(Cp, Hc, Wc) * 2;
+}
+size_t msmetric_layout(int kind, int B, int C, int H, int W, int crop, int flags, int levels, void* base, size_t bytes, double** part) {
+    WsAlloc a(base, bytes);
+    double* p = a.get<double>(msmetric_part_doubles(kind, B, C, H, W, crop, flags, levels));
+    if (part) *part = p;
+    return a.off;
+}
+}  // namespace
+
+extern "C" size_t dcpt_msssim_ws_bytes(int B, int C, int H, int W, int crop_border, int flags, int levels) {
+    if (msmetric_check(MS_MSSSIM, B, C, H, W, crop_border, flags, levels)) return 0;
+    return msmetric_layout(MS_MSSSIM, B, C, H, W, crop_border, flags, levels, nullptr, 0, nullptr);
+}
+
+extern "C" int dcpt_msssim(const float* img, const float* img2, double* out, void* ws, size_t ws_bytes, int B, int C, int H, int W,
+                           int crop_border, int flags, int levels, dcpt_stream_t stream) {
+    DCPT_CHECK_ARG(img && img2 && out, "msssim: null argument");
+    const char* bad = msmetric_check(MS_MSSSIM, B, C, H, W, crop_border, flags, levels);
+    DCPT_CHECK_ARG(!bad, "%s (B=%d C=%d H=%d W=%d crop_border=%d flags=0x%x levels=%d)", bad, B, C, H, W, crop_border, flags, levels);
+    double* part;
+    const size_t need = msmetric_layout(MS_MSSSIM, B, C, H, W, crop_border, flags, levels, ws, ws_bytes, &part);
+    DCPT_CHECK_WS("msssim", ws, ws_bytes, need);
+    return launch_msssim(img, img2, out, part, B, C, H, W, crop_border, (flags & DCPT_METRIC_Y) != 0, (flags & DCPT_METRIC_RANGE1) ? 1 : 255,
+                         levels, (hipStream_t)stream);
+}
+
+extern "C" size_t dcpt_ssim_matlab_ws_bytes(int B, int C, int H, int W, int crop_border, int flags) {
+    if (msmetric_check(MS_MATLAB, B, C, H, W, crop_border, flags, 1)) return 0;
+    return msmetric_layout(MS_MATLAB, B, C, H, W, crop_border, flags, 1, nullptr, 0, nullptr);
+}
+
+extern "C" int dcpt_ssim_matlab(const float* img, const float* img2, double* out, void* ws, size_t ws_bytes, int B, int C, int H, int W,
+                                int crop_border, int flags, dcpt_stream_t stream) {
+    DCPT_CHECK_ARG(img && img2 && out, "ssim_matlab: null argument");
+    const char* bad = msmetric_check(MS_MATLAB, B, C, H, W, crop_border, flags, 1);
+    DCPT_CHECK_ARG(!bad, "%s (B=%d C=%d H=%d W=%d crop_border=%d flags=0x%x)", bad, B, C, H, W, crop_border, flags);
+    double* part;
+    const size_t need = msmetric_layout(MS_MATLAB, B, C, H, W, crop_border, flags, 1, ws, ws_bytes, &part);
+    DCPT_CHECK_WS("ssim_matlab", ws, ws_bytes, need);
+    return launch_ssim_matlab(img, img2, out, part, B, C, H, W, crop_border, (flags & DCPT_METRIC_Y) != 0,
+                              (flags & DCPT_METRIC_RANGE1) ? 1 : 255, (hipStream_t)stream);
+}
+
+extern "C" size_t dcpt_imgrange_ws_bytes(int B, int C, int H, int W, int crop_border, int flags) {
+    if (msmetric_check(MS_RANGE, B, C, H, W, crop_border, flags, 1)) return 0;
+    return msmetric_layout(MS_RANGE, B, C, H, W, crop_border, flags, 1, nullptr, 0, nullptr);
+}
+
+extern "C" int dcpt_imgrange(const float* img, double* out, void* ws, size_t ws_bytes, int B, int C, int H, int W, int crop_border, int flags,
+                             dcpt_stream_t stream) {
+    DCPT_CHECK_ARG(img && out, "imgrange: null argument");
+    const char* bad = msmetric_check(MS_RANGE, B, C, H, W, crop_border, flags, 1);
+    DCPT_CHECK_ARG(!bad, "%s (B=%d C=%d H=%d W=%d crop_border=%d flags=0x%x)", bad, B, C, H, W, crop_border, flags);
+    double* part;
+    const size_t need = msmetric_layout(MS_RANGE, B, C, H, W, crop_border, flags, 1, ws, ws_bytes, &part);
+    DCPT_CHECK_WS("imgrange", ws, ws_bytes, need);
+    return launch_imgrange(img, out, part, B, C, H, W, crop_border, (flags & DCPT_METRIC_Y) != 0, (flags & DCPT_METRIC_RANGE1) ? 1 : 255,
+                           (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------------------------------------
 // SSIM as a training loss (ssim_loss.hip)
 namespace {
 struct SsimLossWs {

@@ -181,6 +181,21 @@ int metric_num_tiles(int Hc, int Wc);
 int launch_imgmetric(const float* img, const float* img2, void* sse_out, double* ssim_out, double* ssim_part, void* sse_part, int B, int C,
                      int H, int W, int crop, int luma, int range, int want_ssim, hipStream_t s);
 
+// ---- metrics_ms.hip -----------------------------------------------------------------------
+// MS-SSIM (dcpt_msssim): one launch over (tile, image, level) on metrics.hip's tile, level k after k box passes in LDS; part holds
+// [B][levels][metric_num_tiles][2] sums of the SSIM and CS maps, out [B][levels][2].  MATLAB SSIM (dcpt_ssim_matlab): the window at every
+// pixel under replicate padding; part [B * C'][ssim_matlab_num_tiles], out [B][C'].  Range (dcpt_imgrange): min / max of the scored values of
+// one image; part [B][imgrange_num_chunks][2], out [B][2].  Each is a tile kernel plus a fixed-order reduce.
+#define MSSSIM_MAX_LEVELS 8
+#define METRIC_RANGE_CHUNK 4096
+int ssim_matlab_num_tiles(int Hc, int Wc);
+int64_t imgrange_num_chunks(int Cp, int Hc, int Wc);
+int launch_msssim(const float* img, const float* img2, double* out, double* part, int B, int C, int H, int W, int crop, int luma, int range,
+                  int levels, hipStream_t s);
+int launch_ssim_matlab(const float* img, const float* img2, double* out, double* part, int B, int C, int H, int W, int crop, int luma, int range,
+                       hipStream_t s);
+int launch_imgrange(const float* img, double* out, double* part, int B, int C, int H, int W, int crop, int luma, int range, hipStream_t s);
+
 // ---- ssim_loss.hip --------------------------------------------------------------------------
 // SSIM as a loss (dcpt_ssim_loss_fwd / _bwd): the forward writes one partial per tile into part[B * C'][ssim_loss_num_tiles]; the backward
 // keeps Pa, Pb, Pc of ssim_loss_chunk_images images at a time in planes (ssim_loss_plane_bytes per image).

@@ -10,63 +10,16 @@
 #include <math.h>
 
 #include "kernels.h"
+#include "metric_front.h"
 #include "prof.h"
 
 // every product and sum rounds on its own, as numpy's element-wise passes do (mu1 * mu1 is one array there, the subtraction another)
 #pragma clang fp contract(off)
 
 namespace {
-constexpr int TH = METRIC_TH, TW = METRIC_TW, WIN = 11;
+constexpr int TH = METRIC_TH, TW = METRIC_TW, WIN = METRIC_WIN;   // (the front end, block_sum and the taps: metric_front.h)
 constexpr int SH = TH + WIN - 1, SW = TW + WIN - 1;   // staged rows / columns
-constexpr int NT = 256;
-
-struct Gauss {
-    double g[WIN];
-};
-
-struct MetricGeom {
-    int C, Cp;           // input channels, scored channels (1 for luma)
-    int H, W, crop;
-    int Hc, Wc;          // cropped size
-    int nty, ntx;        // tiles of SSIM-map positions
-    int luma, quant, ssim, int_sse;
-    float range;         // 255 or 1
-    double c1, c2;
-};
-
-// the value the metric is evaluated on, as the host forms it (basicsr/metrics/__init__.py::_images / _to_y)
-__device__ __forceinline__ float quantise(float v) { return fminf(fmaxf(rintf(v * 255.0f), 0.0f), 255.0f); }
-
-__device__ __forceinline__ float metric_value(const float* __restrict__ img, int64_t plane, int64_t off, const MetricGeom& m) {
-    if (!m.luma) {
-        const float v = img[off];
-        return m.quant ? quantise(v) : v;
-    }
-    float r = img[off], g = img[off + plane], b = img[off + 2 * plane];
-    if (m.quant) {
-        r = quantise(r);
-        g = quantise(g);
-        b = quantise(b);
-    }
-    // x = value / image_range in fp32, the dot product and (.. + 16) / 255 in fp64, rounded to fp32, times image_range in fp32
-    const double xb = (double)__fdiv_rn(b, m.range), xg = (double)__fdiv_rn(g, m.range), xr = (double)__fdiv_rn(r, m.range);
-    const double y = (xb * 24.966 + xg * 128.553 + xr * 65.481 + 16.0) / 255.0;
-    return __fmul_rn((float)y, m.range);
-}
-
-template <typename T>
-__device__ __forceinline__ T block_sum(T v, T* red) {   // fixed tree over the NT threads: the same bits on every run
-    const int tid = threadIdx.x;
-    red[tid] = v;
-    __syncthreads();
-    for (int s = NT / 2; s > 0; s >>= 1) {
-        if (tid < s) red[tid] += red[tid + s];
-        __syncthreads();
-    }
-    const T r = red[0];
-    __syncthreads();
-    return r;
-}
+constexpr int NT = METRIC_NT;
 
 __global__ __launch_bounds__(NT) void metric_tile_kernel(const float* __restrict__ img, const float* __restrict__ img2,
                                                          double* __restrict__ ssim_part, unsigned long long* __restrict__ sse_part,
@@ -203,28 +156,11 @@ int metric_num_tiles(int Hc, int Wc) {
 
 int launch_imgmetric(const float* img, const float* img2, void* sse_out, double* ssim_out, double* ssim_part, void* sse_part, int B, int C,
                      int H, int W, int crop, int luma, int range, int want_ssim, hipStream_t s) {
-    MetricGeom m{};
-    m.C = C;
-    m.luma = luma && C == 3;
-    m.Cp = m.luma ? 1 : C;
-    m.H = H; m.W = W; m.crop = crop;
-    m.Hc = H - 2 * crop; m.Wc = W - 2 * crop;
+    MetricGeom m = metric_geom(C, H, W, crop, luma, range);
     const int oh = m.Hc > WIN - 1 ? m.Hc - (WIN - 1) : 1, ow = m.Wc > WIN - 1 ? m.Wc - (WIN - 1) : 1;
     m.nty = cdiv(oh, TH); m.ntx = cdiv(ow, TW);
-    m.quant = range == 255;
     m.ssim = want_ssim;
-    m.int_sse = m.quant && !m.luma;
-    m.range = (float)range;
-    m.c1 = (0.01 * range) * (0.01 * range);
-    m.c2 = (0.03 * range) * (0.03 * range);
-    Gauss gw;   // cv2.getGaussianKernel(11, 1.5): exp(-(i - 5)^2 / (2 sigma^2)), normalised to sum 1
-    double sum = 0.0;
-    for (int i = 0; i < WIN; ++i) {
-        const double x = (double)i - 5.0;
-        gw.g[i] = exp(-(x * x) / (2.0 * 1.5 * 1.5));
-        sum += gw.g[i];
-    }
-    for (int i = 0; i < WIN; ++i) gw.g[i] /= sum;
+    const Gauss gw = metric_gauss_taps();
     const int ntiles = m.nty * m.ntx;
     trace_tag(want_ssim ? "metric.tile_ssim" : "metric.tile_psnr");
     metric_tile_kernel<<<dim3((unsigned)ntiles, (unsigned)(B * m.Cp)), dim3(NT), 0, s>>>(img, img2, ssim_part, (unsigned long long*)sse_part, m,

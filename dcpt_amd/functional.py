@@ -2812,6 +2812,67 @@ def image_metric_sums(img, img2, crop_border=0, test_y_channel=False, image_rang
 
 
 # ------------------------------------------------------------------------------------------------
+# MS-SSIM, MATLAB SSIM and the NRMSE range (include/dcpt_hip.h dcpt_msssim, dcpt_ssim_matlab, dcpt_imgrange; dcpt_amd/csrc/metrics_ms.hip):
+# the sums basicsr.metrics finishes on the host, no autograd, no host sync.
+MSMETRIC_TILE = METRIC_TILE   # (TH, TW) of metrics_ms.hip: map positions (MS-SSIM) / output pixels (MATLAB SSIM) per workgroup
+MSSSIM_MAX_LEVELS = 8         # MSSSIM_MAX_LEVELS of dcpt_amd/csrc/kernels.h
+RANGE_CHUNK = 4096            # METRIC_RANGE_CHUNK: scored values per workgroup of the range kernel
+
+
+def _msmetric_args(name, host_name, imgs, crop_border, test_y_channel, image_range):
+    """the checks of ``image_metric_sums``; returns the contiguous tensors, the geometry (B, C, H, W, crop, flags) and C'"""
+    if not all(torch.is_tensor(t) for t in imgs):
+        raise _lib.DcptHipError(f"{name} takes device tensors (got {type(imgs[0]).__name__}); host arrays go to basicsr.metrics.{host_name}")
+    _require_gpu(*imgs)
+    if imgs[0].dim() != 4 or any(t.shape != imgs[0].shape for t in imgs):
+        raise ValueError(f"expected (B, C, H, W) tensors of one shape, got {[tuple(t.shape) for t in imgs]}")
+    if image_range not in (255, 1):
+        raise ValueError(f"image_range {image_range}: the device metrics know 255 and 1")
+    imgs = [_contig(t.detach()) for t in imgs]
+    B, Cc, H, W = imgs[0].shape
+    flags = (_METRIC_Y if test_y_channel else 0) | (_METRIC_RANGE1 if image_range == 1 else 0)
+    return imgs, (B, Cc, H, W, int(crop_border), flags), 1 if (test_y_channel and Cc == 3) else Cc
+
+
+def msssim_sums(img, img2, crop_border=0, test_y_channel=False, image_range=255, levels=5):
+    """``img`` / ``img2`` as for ``image_metric_sums``.  Returns the float64 device tensor (B, levels, 2): for evaluation k of the reference's
+    ``calculate_msssim`` the sums of the SSIM map and of the CS map over the (H' - 10) (W' - 10) positions of channel k mod C' after k box
+    blurs.  One launch for all levels plus one reduce; nothing is synchronised."""
+    lib = _lib.load()
+    (img, img2), dims, _ = _msmetric_args("msssim_sums", "calculate_msssim", (img, img2), crop_border, test_y_channel, image_range)
+    levels = int(levels)
+    out = torch.empty(dims[0], min(max(levels, 1), MSSSIM_MAX_LEVELS), 2, dtype=torch.float64, device=img.device)   # (a refused count never launches)
+    nws = lib.dcpt_msssim_ws_bytes(*dims, levels)   # (0 for arguments the entry point refuses: it then names the reason)
+    ws = _workspace(img.device, nws)
+    _call(lib.dcpt_msssim, (img, img2, out, ws, nws), (*dims, levels), img.device)   # (irregular: the queried size, not the buffer's)
+    return out
+
+
+def ssim_matlab_sums(img, img2, crop_border=0, test_y_channel=False, image_range=255):
+    """Returns the float64 device tensor (B, C'): the sum of the reference's ``calculate_ssim_matlab`` map (the 11 x 11 Gaussian window at
+    every pixel under replicate padding) over the H' W' pixels of each scored channel.  Nothing is synchronised."""
+    lib = _lib.load()
+    (img, img2), dims, cp = _msmetric_args("ssim_matlab_sums", "calculate_ssim_matlab", (img, img2), crop_border, test_y_channel, image_range)
+    out = torch.empty(dims[0], cp, dtype=torch.float64, device=img.device)
+    nws = lib.dcpt_ssim_matlab_ws_bytes(*dims)
+    ws = _workspace(img.device, nws)
+    _call(lib.dcpt_ssim_matlab, (img, img2, out, ws, nws), dims, img.device)
+    return out
+
+
+def image_range_minmax(img, crop_border=0, test_y_channel=False, image_range=255):
+    """Returns the float64 device tensor (B, 2): the minimum and the maximum of each image's scored values (after quantisation / crop / luma),
+    what the reference's ``calculate_nrmse`` divides by.  Nothing is synchronised."""
+    lib = _lib.load()
+    (img,), dims, _ = _msmetric_args("image_range_minmax", "calculate_nrmse", (img,), crop_border, test_y_channel, image_range)
+    out = torch.empty(dims[0], 2, dtype=torch.float64, device=img.device)
+    nws = lib.dcpt_imgrange_ws_bytes(*dims)
+    ws = _workspace(img.device, nws)
+    _call(lib.dcpt_imgrange, (img, out, ws, nws), dims, img.device)
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
 # SSIM as a training loss (include/dcpt_hip.h dcpt_ssim_loss_fwd / _bwd): the reference's calculate_ssim_pt with its gradient, in fp64 on
 # the device, without its grouped fp64 convolutions.
 def ssim_plane_cap(nbytes=None):

@@ -810,6 +810,33 @@ size_t dcpt_imgmetric_ws_bytes(int B, int C, int H, int W, int crop_border, int 
 int dcpt_imgmetric(const float* img, const float* img2, void* sse_out, double* ssim_out, void* ws, size_t ws_bytes, int B, int C, int H, int W,
                    int crop_border, int flags, dcpt_stream_t stream);
 
+/* ---- validation metrics: MS-SSIM, MATLAB SSIM and the NRMSE range, on the device -------------------------
+ * img, img2, crop_border, the front end and the flags DCPT_METRIC_Y / DCPT_METRIC_RANGE1 as for dcpt_imgmetric (DCPT_METRIC_SSIM is not
+ * taken); C' = 1 for luma, C otherwise; H' = H - 2 crop_border.  All window arithmetic is fp64, every product and sum rounds on its own.
+ *   dcpt_msssim       replaces basicsr/metrics/psnr_ssim.py:334-432 (calculate_msssim) with its _ssim (:483-512) and its cv2.filter2D box
+ *                     blurs (:410-423).  out[B][levels][2] = for evaluation k the sums of the SSIM map and of the CS map
+ *                     (2 s12 + C2) / (s1 + s2 + C2) over the (H' - 10) x (W' - 10) "valid" positions of channel k mod C' of both images after
+ *                     k passes of out[y][x] = 0.25 ((a[y][x] + a[y][x+1]) + (a[y+1][x] + a[y+1][x+1])), an index past the last row / column
+ *                     reading the last one (the reference does not decimate, and blurs inside its channel loop).  The host divides by the
+ *                     count and forms prod(cs_k ^ w_k) ssim_{L-1} ^ w_{L-1}.  One launch over (tile, image, level) + one reduce.
+ *   dcpt_ssim_matlab  replaces :201-330 (SSIM_MATLAB_Pytorch, calculate_ssim_matlab): out[B][C'] = the sum over all H' x W' pixels of
+ *                     ((2 mu12 + C1) (2 s12 + C2)) / ((mu1^2 + mu2^2 + C1) (s1 + s2 + C2)), the 11 x 11 window under replicate padding of
+ *                     5; any H', W' >= 1.  fp64 where the reference's Conv2d is fp32.  The host divides by H' W' and doubles the last channel.
+ *   dcpt_imgrange     replaces img.max() - img.min() of :563-612 (calculate_nrmse): out[B][2] = the minimum and the maximum of image b's
+ *                     scored values (exact fp32 numbers, stored as fp64); the squared error comes from dcpt_imgmetric.
+ * Two launches each on `stream`, no atomics: the same input gives the same bits.  Errors (before any launch): null pointers, C not in
+ * {1, 3}, crop_border < 0, unknown flag bits, a cropped size <= 0, for dcpt_msssim a cropped size under 11 x 11 or levels outside 1 .. 8,
+ * B * C (* levels) above 65535, workspace too small.  The *_ws_bytes need no device and return 0 for arguments the entry point refuses. */
+size_t dcpt_msssim_ws_bytes(int B, int C, int H, int W, int crop_border, int flags, int levels);
+int dcpt_msssim(const float* img, const float* img2, double* out, void* ws, size_t ws_bytes, int B, int C, int H, int W, int crop_border,
+                int flags, int levels, dcpt_stream_t stream);
+size_t dcpt_ssim_matlab_ws_bytes(int B, int C, int H, int W, int crop_border, int flags);
+int dcpt_ssim_matlab(const float* img, const float* img2, double* out, void* ws, size_t ws_bytes, int B, int C, int H, int W, int crop_border,
+                     int flags, dcpt_stream_t stream);
+size_t dcpt_imgrange_ws_bytes(int B, int C, int H, int W, int crop_border, int flags);
+int dcpt_imgrange(const float* img, double* out, void* ws, size_t ws_bytes, int B, int C, int H, int W, int crop_border, int flags,
+                  dcpt_stream_t stream);
+
 /* ---- SSIM as a training loss: per-image SSIM sums and their gradient, on the device ------------------------
  * replaces the fp64 arithmetic of basicsr/metrics/psnr_ssim.py:436-480 (calculate_ssim_pt) and :515-559 (_ssim_pth: five grouped 11 x 11
  * fp64 F.conv2d passes, and their transposes under autograd) as the losses of basicsr/losses/basic_loss.py:152-232 (SSIMLoss, SSIMMSELoss)
