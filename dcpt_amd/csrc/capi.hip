@@ -270,16 +270,31 @@ struct MetricWs {
     double* ssim_part;
     void* sse_part;
 };
-// 0 on success; the message names what is wrong with the shape / flags
-const char* metric_check(int B, int C, int H, int W, int crop, int flags) {
-    if (B <= 0 || H <= 0 || W <= 0) return "imgmetric: bad shape";
-    if (C != 1 && C != 3) return "imgmetric: C must be 1 or 3";
-    if (crop < 0) return "imgmetric: crop_border must be >= 0";
-    if (flags & ~(DCPT_METRIC_Y | DCPT_METRIC_SSIM | DCPT_METRIC_RANGE1)) return "imgmetric: unknown flag (image_range is 255, or 1 with DCPT_METRIC_RANGE1)";
-    if (H - 2 * crop <= 0 || W - 2 * crop <= 0) return "imgmetric: nothing left after the crop";
-    if ((flags & DCPT_METRIC_SSIM) && (H - 2 * crop < 11 || W - 2 * crop < 11)) return "imgmetric: SSIM needs a cropped image of at least 11 x 11";
-    if ((int64_t)B * C > 65535) return "imgmetric: B * C above 65535";
-    return nullptr;
+// The one check of every metric-shaped entry point (imgmetric, msssim, ssim_matlab, imgrange, ssim_loss): 0 on success, else the message
+// that names what is wrong with the shape / flags, "<op>: ...".  `taken` are the flags the op accepts and `taken_text` what the message
+// says about them; `window` names what needs a cropped image of 11 x 11 (null: any size will do); `levels` is MS-SSIM's count (null: the
+// op has none).  The message lives until this thread's next call.
+const char* metric_check(const char* op, int taken, const char* taken_text, const char* window, const int* levels, int B, int C, int H, int W,
+                         int crop, int flags) {
+    static thread_local char msg[160];
+    char text[128];
+    const int64_t Hc = (int64_t)H - 2 * (int64_t)crop, Wc = (int64_t)W - 2 * (int64_t)crop;
+    if (B <= 0 || H <= 0 || W <= 0) snprintf(text, sizeof text, "bad shape");
+    else if (C != 1 && C != 3) snprintf(text, sizeof text, "C must be 1 or 3");
+    else if (crop < 0) snprintf(text, sizeof text, "crop_border must be >= 0");
+    else if (flags & ~taken) snprintf(text, sizeof text, "unknown flag (%s)", taken_text);
+    else if (Hc <= 0 || Wc <= 0) snprintf(text, sizeof text, "nothing left after the crop");
+    else if (window && (Hc < 11 || Wc < 11)) snprintf(text, sizeof text, "%s needs a cropped image of at least 11 x 11", window);
+    else if (levels && (*levels < 1 || *levels > MSSSIM_MAX_LEVELS)) snprintf(text, sizeof text, "levels must be 1 .. %d", MSSSIM_MAX_LEVELS);
+    // (the grid's y extent; C, not C': one bound for both luma settings)
+    else if ((int64_t)B * C * (levels ? *levels : 1) > 65535) snprintf(text, sizeof text, "B * C%s above 65535", levels ? " * levels" : "");
+    else return nullptr;
+    snprintf(msg, sizeof msg, "%s: %s", op, text);
+    return msg;
+}
+const char* imgmetric_check(int B, int C, int H, int W, int crop, int flags) {
+    return metric_check("imgmetric", DCPT_METRIC_Y | DCPT_METRIC_SSIM | DCPT_METRIC_RANGE1, "image_range is 255, or 1 with DCPT_METRIC_RANGE1",
+                        (flags & DCPT_METRIC_SSIM) ? "SSIM" : nullptr, nullptr, B, C, H, W, crop, flags);
 }
 size_t metric_layout(int B, int C, int H, int W, int crop, int flags, void* base, size_t bytes, MetricWs* out) {
     WsAlloc a(base, bytes);
@@ -294,7 +309,7 @@ size_t metric_layout(int B, int C, int H, int W, int crop, int flags, void* base
 }  // namespace
 
 extern "C" size_t dcpt_imgmetric_ws_bytes(int B, int C, int H, int W, int crop_border, int flags) {
-    if (metric_check(B, C, H, W, crop_border, flags)) return 0;
+    if (imgmetric_check(B, C, H, W, crop_border, flags)) return 0;
     return metric_layout(B, C, H, W, crop_border, flags, nullptr, 0, nullptr);
 }
 
@@ -302,7 +317,7 @@ extern "C" int dcpt_imgmetric(const float* img, const float* img2, void* sse_out
                               int H, int W, int crop_border, int flags, dcpt_stream_t stream) {
     const int want_ssim = (flags & DCPT_METRIC_SSIM) != 0;
     DCPT_CHECK_ARG(img && img2 && sse_out && (ssim_out || !want_ssim), "imgmetric: null argument");
-    const char* bad = metric_check(B, C, H, W, crop_border, flags);
+    const char* bad = imgmetric_check(B, C, H, W, crop_border, flags);
     DCPT_CHECK_ARG(!bad, "%s (B=%d C=%d H=%d W=%d crop_border=%d flags=0x%x)", bad, B, C, H, W, crop_border, flags);
     MetricWs m;
     const size_t need = metric_layout(B, C, H, W, crop_border, flags, ws, ws_bytes, &m);
@@ -315,28 +330,11 @@ extern "C" int dcpt_imgmetric(const float* img, const float* img2, void* sse_out
 // MS-SSIM, MATLAB SSIM and the NRMSE range (metrics_ms.hip)
 namespace {
 enum { MS_MSSSIM, MS_MATLAB, MS_RANGE };
-// 0 on success; the message names what is wrong with the shape / flags (the words dcpt_imgmetric uses for the same faults)
 const char* msmetric_check(int kind, int B, int C, int H, int W, int crop, int flags, int levels) {
-    static const char* const msg[3][8] = {
-        {"msssim: bad shape", "msssim: C must be 1 or 3", "msssim: crop_border must be >= 0",
-         "msssim: unknown flag (DCPT_METRIC_Y and DCPT_METRIC_RANGE1 are taken)", "msssim: nothing left after the crop",
-         "msssim: MS-SSIM needs a cropped image of at least 11 x 11", "msssim: levels must be 1 .. 8", "msssim: B * C * levels above 65535"},
-        {"ssim_matlab: bad shape", "ssim_matlab: C must be 1 or 3", "ssim_matlab: crop_border must be >= 0",
-         "ssim_matlab: unknown flag (DCPT_METRIC_Y and DCPT_METRIC_RANGE1 are taken)", "ssim_matlab: nothing left after the crop", "", "",
-         "ssim_matlab: B * C above 65535"},
-        {"imgrange: bad shape", "imgrange: C must be 1 or 3", "imgrange: crop_border must be >= 0",
-         "imgrange: unknown flag (DCPT_METRIC_Y and DCPT_METRIC_RANGE1 are taken)", "imgrange: nothing left after the crop", "", "",
-         "imgrange: B * C above 65535"}};
-    const char* const* w = msg[kind];
-    if (B <= 0 || H <= 0 || W <= 0) return w[0];
-    if (C != 1 && C != 3) return w[1];
-    if (crop < 0) return w[2];
-    if (flags & ~(DCPT_METRIC_Y | DCPT_METRIC_RANGE1)) return w[3];
-    if ((int64_t)H - 2 * (int64_t)crop <= 0 || (int64_t)W - 2 * (int64_t)crop <= 0) return w[4];
-    if (kind == MS_MSSSIM && (H - 2 * crop < 11 || W - 2 * crop < 11)) return w[5];
-    if (kind == MS_MSSSIM && (levels < 1 || levels > MSSSIM_MAX_LEVELS)) return w[6];
-    if ((int64_t)B * C * (kind == MS_MSSSIM ? levels : 1) > 65535) return w[7];   // (the grid's y extent; C, not C': one bound for both luma settings)
-    return nullptr;
+    static const char* const op[3] = {"msssim", "ssim_matlab", "imgrange"};
+    const bool ms = kind == MS_MSSSIM;
+    return metric_check(op[kind], DCPT_METRIC_Y | DCPT_METRIC_RANGE1, "DCPT_METRIC_Y and DCPT_METRIC_RANGE1 are taken", ms ? "MS-SSIM" : nullptr,
+                        ms ? &levels : nullptr, B, C, H, W, crop, flags);
 }
 size_t msmetric_part_doubles(int kind, int B, int C, int H, int W, int crop, int flags, int levels) {
     const int Cp = ((flags & DCPT_METRIC_Y) && C == 3) ? 1 : C;
@@ -411,16 +409,8 @@ struct SsimLossWs {
     double* part;     // [B * C'][tiles]
     double* planes;   // [chunk images * C'][3][Hm][Wm] (backward)
 };
-// 0 on success; the message names what is wrong with the shape / flags (the words dcpt_imgmetric uses for the same faults)
 const char* ssim_loss_check(int B, int C, int H, int W, int crop, int flags) {
-    if (B <= 0 || H <= 0 || W <= 0) return "ssim_loss: bad shape";
-    if (C != 1 && C != 3) return "ssim_loss: C must be 1 or 3";
-    if (crop < 0) return "ssim_loss: crop_border must be >= 0";
-    if (flags & ~DCPT_METRIC_Y) return "ssim_loss: unknown flag (only DCPT_METRIC_Y is taken)";
-    if (H - 2 * crop <= 0 || W - 2 * crop <= 0) return "ssim_loss: nothing left after the crop";
-    if (H - 2 * crop < 11 || W - 2 * crop < 11) return "ssim_loss: SSIM needs a cropped image of at least 11 x 11";
-    if ((int64_t)B * C > 65535) return "ssim_loss: B * C above 65535";
-    return nullptr;
+    return metric_check("ssim_loss", DCPT_METRIC_Y, "only DCPT_METRIC_Y is taken", "SSIM", nullptr, B, C, H, W, crop, flags);
 }
 size_t ssim_loss_layout(int B, int C, int H, int W, int crop, int flags, int backward, void* base, size_t bytes, SsimLossWs* out) {
     WsAlloc a(base, bytes);

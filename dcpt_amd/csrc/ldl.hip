@@ -24,7 +24,8 @@
 // by reflect addressing: no padded copy exists), runs the separable box pass of r - pivot and (r - pivot)^2, writes u and mu as fp64
 // planes and one partial of sum(u); the pivot is the smallest r of the staged tile: sums of shifted values do not cancel the way raw
 // sum(r^2) - sum(r)^2 / 49 does on a smooth residual, and, r being non-negative, a tile that holds an all-zero window has pivot 0, so that
-// window's u is exactly 0; (2) one workgroup adds the partials in a fixed order: m; (3) sum((u - m)^2) per chunk of CHUNK elements;
+// window's u is exactly 0; (2) one workgroup adds the partials in a fixed order (sum_reduce_kernel of block_sum.h, whose tree every block
+// sum and the pivot's minimum here go through as well): m; (3) sum((u - m)^2) per chunk of CHUNK elements;
 // (4) the same reduce kernel: s; (5) w.  Backward, four launches: (1) Gz per element and the partials of sum(Gz), sum(Gz z) per chunk;
 // (2) the reduce kernel; (3) the planes Gv and Gv mu; (4) one workgroup per TH x TW tile of input pixels stages both planes with a 3-wide
 // zero halo, runs T as two separable gather passes, combines with r and the sign and writes Gout.  m, s and the two sums stay in the
@@ -33,6 +34,7 @@
 // out == gt everywhere gives u = 0, m = 0, s = 0, z = 0 / 0: w is NaN everywhere, which is what the reference's expression gives.
 #include <math.h>
 
+#include "block_sum.h"
 #include "kernels.h"
 #include "prof.h"
 
@@ -41,7 +43,7 @@
 namespace {
 constexpr int TH = METRIC_TH, TW = METRIC_TW, WIN = 7, PAD = 3;
 constexpr int SH = TH + WIN - 1, SW = TW + WIN - 1;   // staged rows / columns
-constexpr int NT = 256;
+constexpr int NT = BLOCK_NT;
 constexpr int CHUNK = LDL_CHUNK;                      // elements per workgroup of the element-wise kernels that leave a partial
 
 struct LdlGeom {
@@ -49,19 +51,6 @@ struct LdlGeom {
     int nty, ntx;
     int64_t N;
 };
-
-__device__ __forceinline__ double block_sum(double v, double* red) {   // fixed tree over the NT threads: the same bits on every run
-    const int tid = threadIdx.x;
-    red[tid] = v;
-    __syncthreads();
-    for (int s = NT / 2; s > 0; s >>= 1) {
-        if (tid < s) red[tid] += red[tid + s];
-        __syncthreads();
-    }
-    const double r = red[0];
-    __syncthreads();
-    return r;
-}
 
 __device__ __forceinline__ int reflect(int q, int n) { return q < 0 ? -q : (q >= n ? 2 * (n - 1) - q : q); }
 
@@ -88,14 +77,7 @@ __global__ __launch_bounds__(NT) void ldl_tile_kernel(const float* __restrict__ 
         }
         sr[r][c] = v;
     }
-    red[tid] = lo;
-    __syncthreads();
-    for (int s = NT / 2; s > 0; s >>= 1) {
-        if (tid < s) red[tid] = fmin(red[tid], red[tid + s]);
-        __syncthreads();
-    }
-    const double pivot = red[0];   // (finite: the tile's first pixel is in the plane)
-    __syncthreads();
+    const double pivot = block_tree(lo, red, [](double a, double b) { return fmin(a, b); });   // (finite: the tile's first pixel is in the plane)
     // ---- horizontal pass of r - pivot and its square ----
     for (int i = tid; i < SH * TW; i += NT) {
         const int r = i / TW, c = i - r * TW;
@@ -130,19 +112,6 @@ __global__ __launch_bounds__(NT) void ldl_tile_kernel(const float* __restrict__ 
     }
     acc = block_sum(acc, red);
     if (tid == 0) part[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] = acc;
-}
-
-// workgroup j adds part[j][0 .. np) in a fixed order; MODE 0: dst[j] = sum / N (the mean), 1: dst[j] = sqrt(sum / (N - 1)) (the unbiased
-// std from the sum of squared deviations), 2: dst[j] = sum
-template <int MODE>
-__global__ __launch_bounds__(NT) void ldl_reduce_kernel(const double* __restrict__ part, double* __restrict__ dst, int64_t np, int64_t N) {
-    __shared__ double red[NT];
-    const int tid = threadIdx.x;
-    const double* p = part + (int64_t)blockIdx.x * np;
-    double a = 0.0;
-    for (int64_t i = tid; i < np; i += NT) a += p[i];
-    a = block_sum(a, red);
-    if (tid == 0) dst[blockIdx.x] = MODE == 0 ? a / (double)N : (MODE == 1 ? sqrt(a / (double)(N - 1)) : a);
 }
 
 // part[blockIdx.x] = sum over the workgroup's CHUNK elements of (u - m)^2
@@ -318,13 +287,13 @@ int launch_ldl_weight_fwd(const float* gt, const float* out, float* w, const Ldl
     ldl_tile_kernel<<<dim3((unsigned)ntiles, (unsigned)(B * C)), dim3(NT), 0, s>>>(gt, out, ws.u, ws.mu, ws.part, m);
     DCPT_CHECK_LAUNCH("ldl_weight_fwd tile");
     trace_tag("ldl.reduce");
-    ldl_reduce_kernel<0><<<dim3(1), dim3(NT), 0, s>>>(ws.part, ws.scal, (int64_t)B * C * ntiles, m.N);
+    sum_reduce_kernel<SUM_MEAN><<<dim3(1), dim3(NT), 0, s>>>(ws.part, ws.scal, (int64_t)B * C * ntiles, 1, m.N);
     DCPT_CHECK_LAUNCH("ldl_weight_fwd mean");
     trace_tag("ldl.dev");
     ldl_dev_kernel<<<dim3(chunks), dim3(NT), 0, s>>>(ws.u, ws.scal, ws.part, m.N);
     DCPT_CHECK_LAUNCH("ldl_weight_fwd dev");
     trace_tag("ldl.reduce");
-    ldl_reduce_kernel<1><<<dim3(1), dim3(NT), 0, s>>>(ws.part, ws.scal + 1, (int64_t)chunks, m.N);
+    sum_reduce_kernel<SUM_STD><<<dim3(1), dim3(NT), 0, s>>>(ws.part, ws.scal + 1, (int64_t)chunks, 1, m.N);
     DCPT_CHECK_LAUNCH("ldl_weight_fwd std");
     trace_tag("ldl.w");
     ldl_w_kernel<<<dim3(ew), dim3(NT), 0, s>>>(ws.u, ws.scal, w, m.N);
@@ -340,7 +309,7 @@ int launch_ldl_weight_bwd(const float* gt, const float* out, const float* gw, fl
     ldl_gz_kernel<<<dim3(chunks), dim3(NT), 0, s>>>(ws.u, gw, ws.scal, ws.part, (int64_t)chunks, m.N);
     DCPT_CHECK_LAUNCH("ldl_weight_bwd gz");
     trace_tag("ldl.reduce");
-    ldl_reduce_kernel<2><<<dim3(2), dim3(NT), 0, s>>>(ws.part, ws.scal + 2, (int64_t)chunks, m.N);
+    sum_reduce_kernel<SUM_PLAIN><<<dim3(2), dim3(NT), 0, s>>>(ws.part, ws.scal + 2, (int64_t)chunks, 1, m.N);   // (the two rows of part)
     DCPT_CHECK_LAUNCH("ldl_weight_bwd sums");
     trace_tag("ldl.gv");
     ldl_gv_kernel<<<dim3(ew), dim3(NT), 0, s>>>(ws.u, ws.mu, gw, ws.scal, ws.gv, ws.gvmu, m.N);

@@ -1,19 +1,14 @@
 // The front end the metric kernels share (metrics.hip: PSNR / SSIM; metrics_ms.hip: MS-SSIM, MATLAB SSIM, the NRMSE range): the value a
-// metric is evaluated on, as basicsr/metrics/__init__.py::_images / _to_y forms it, the fixed-order block sum and the 11 Gaussian taps.
-// Every kernel that includes this compiles under `#pragma clang fp contract(off)`.
+// metric is evaluated on, as basicsr/metrics/__init__.py::_images / _to_y forms it.  The window passes and the taps are window_f64.h's, the
+// block sum block_sum.h's.  As there, a function whose products feed sums says `#pragma clang fp contract(off)` in its own body: the
+// rounding does not depend on where this header is included.
 #pragma once
 #include <math.h>
 
 #include "dcpt_common.h"
+#include "window_f64.h"
 
 namespace {
-constexpr int METRIC_WIN = 11;
-constexpr int METRIC_NT = 256;   // threads per workgroup of every metric kernel (block_sum's tree is built for it)
-
-struct Gauss {
-    double g[METRIC_WIN];
-};
-
 struct MetricGeom {
     int C, Cp;           // input channels, scored channels (1 for luma)
     int H, W, crop;
@@ -28,6 +23,7 @@ struct MetricGeom {
 __device__ __forceinline__ float quantise(float v) { return fminf(fmaxf(rintf(v * 255.0f), 0.0f), 255.0f); }
 
 __device__ __forceinline__ float metric_value(const float* __restrict__ img, int64_t plane, int64_t off, const MetricGeom& m) {
+#pragma clang fp contract(off)
     if (!m.luma) {
         const float v = img[off];
         return m.quant ? quantise(v) : v;
@@ -42,33 +38,6 @@ __device__ __forceinline__ float metric_value(const float* __restrict__ img, int
     const double xb = (double)__fdiv_rn(b, m.range), xg = (double)__fdiv_rn(g, m.range), xr = (double)__fdiv_rn(r, m.range);
     const double y = (xb * 24.966 + xg * 128.553 + xr * 65.481 + 16.0) / 255.0;
     return __fmul_rn((float)y, m.range);
-}
-
-template <typename T>
-__device__ __forceinline__ T block_sum(T v, T* red) {   // fixed tree over the METRIC_NT threads: the same bits on every run
-    const int tid = threadIdx.x;
-    red[tid] = v;
-    __syncthreads();
-    for (int s = METRIC_NT / 2; s > 0; s >>= 1) {
-        if (tid < s) red[tid] += red[tid + s];
-        __syncthreads();
-    }
-    const T r = red[0];
-    __syncthreads();
-    return r;
-}
-
-// cv2.getGaussianKernel(11, 1.5): exp(-(i - 5)^2 / (2 sigma^2)), normalised to sum 1
-inline Gauss metric_gauss_taps() {
-    Gauss gw;
-    double sum = 0.0;
-    for (int i = 0; i < METRIC_WIN; ++i) {
-        const double x = (double)i - 5.0;
-        gw.g[i] = exp(-(x * x) / (2.0 * 1.5 * 1.5));
-        sum += gw.g[i];
-    }
-    for (int i = 0; i < METRIC_WIN; ++i) gw.g[i] /= sum;
-    return gw;
 }
 
 // the geometry and constants every metric launcher fills the same way (tiles are set by the caller)

@@ -4,21 +4,22 @@
 //
 // One workgroup per TH x TW tile of SSIM-map positions of one (image, channel).  It stages the (TH + 10) x (TW + 10) values of both
 // images in LDS (every value on every path is an fp32 number: an integer 0..255, an fp32 luma, or the fp32 input itself), runs the
-// horizontal pass of x, y, x^2, y^2, xy into LDS in fp64, then the vertical pass and the SSIM value in registers.  The squared error is
-// taken while staging, each pixel by the one tile that owns it.  Every workgroup stores one SSIM partial and one squared-error partial
-// with ordinary stores; a second kernel adds the partials of an image in a fixed order.  No atomics: two runs give identical bits.
+// horizontal pass of x, y, x^2, y^2, xy into LDS in fp64, then the vertical pass and the SSIM value in registers (both passes and the taps:
+// window_f64.h; the front end: metric_front.h; the block sum: block_sum.h).  The squared error is taken while staging, each pixel by the one
+// tile that owns it.  Every workgroup stores one SSIM partial and one squared-error partial with ordinary stores; a second kernel adds the
+// partials of an image in a fixed order.  No atomics: two runs give identical bits.
 #include <math.h>
 
 #include "kernels.h"
 #include "metric_front.h"
 #include "prof.h"
 
-// every product and sum rounds on its own, as numpy's element-wise passes do (mu1 * mu1 is one array there, the subtraction another)
+// every product and sum rounds on its own, as numpy's element-wise passes do (the shared headers say so per function; this covers the rest)
 #pragma clang fp contract(off)
 
 namespace {
-constexpr int TH = METRIC_TH, TW = METRIC_TW, WIN = METRIC_WIN;   // (the front end, block_sum and the taps: metric_front.h)
-constexpr int SH = TH + WIN - 1, SW = TW + WIN - 1;   // staged rows / columns
+constexpr int TH = METRIC_TH, TW = METRIC_TW, WIN = METRIC_WIN;
+constexpr int SH = METRIC_SH, SW = METRIC_SW;   // staged rows / columns
 constexpr int NT = METRIC_NT;
 
 __global__ __launch_bounds__(NT) void metric_tile_kernel(const float* __restrict__ img, const float* __restrict__ img2,
@@ -64,44 +65,15 @@ __global__ __launch_bounds__(NT) void metric_tile_kernel(const float* __restrict
 
     double acc = 0.0;
     if (m.ssim) {
-        // ---- horizontal pass of the five maps ----
-        for (int i = tid; i < SH * TW; i += NT) {
-            const int r = i / TW, c = i - r * TW;
-            double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0, a4 = 0.0;
-#pragma unroll
-            for (int k = 0; k < WIN; ++k) {
-                const double x = (double)sx[r][c + k], y = (double)sy[r][c + k], g = gw.g[k];
-                a0 += g * x;
-                a1 += g * y;
-                a2 += g * (x * x);
-                a3 += g * (y * y);
-                a4 += g * (x * y);
-            }
-            hp[0][r][c] = a0;
-            hp[1][r][c] = a1;
-            hp[2][r][c] = a2;
-            hp[3][r][c] = a3;
-            hp[4][r][c] = a4;
-        }
+        const Gauss taps = gw;   // (a copy made here: the PSNR-only path never loads the taps; window_f64.h)
+        gauss_rows<float, SW>(sx, sy, hp, taps);
         __syncthreads();
-        // ---- vertical pass, SSIM value ----
         for (int i = tid; i < TH * TW; i += NT) {
             const int r = i / TW, c = i - r * TW;
             if (y0 + r >= m.Hc - (WIN - 1) || x0 + c >= m.Wc - (WIN - 1)) continue;
-            double mu1 = 0.0, mu2 = 0.0, e11 = 0.0, e22 = 0.0, e12 = 0.0;
-#pragma unroll
-            for (int k = 0; k < WIN; ++k) {
-                const double g = gw.g[k];
-                mu1 += g * hp[0][r + k][c];
-                mu2 += g * hp[1][r + k][c];
-                e11 += g * hp[2][r + k][c];
-                e22 += g * hp[3][r + k][c];
-                e12 += g * hp[4][r + k][c];
-            }
-            const double mu1_sq = mu1 * mu1, mu2_sq = mu2 * mu2, mu12 = mu1 * mu2;
-            const double s1 = e11 - mu1_sq, s2 = e22 - mu2_sq, s12 = e12 - mu12;
-            const double cs = (2.0 * s12 + m.c2) / (s1 + s2 + m.c2);
-            acc += ((2.0 * mu12 + m.c1) / (mu1_sq + mu2_sq + m.c1)) * cs;
+            const Moments o = gauss_col(hp, r, c, taps);
+            const double cs = (2.0 * o.s12 + m.c2) / (o.s1 + o.s2 + m.c2);
+            acc += ((2.0 * o.mu12 + m.c1) / (o.mu1_sq + o.mu2_sq + m.c1)) * cs;
         }
         acc = block_sum(acc, red);
     }
@@ -160,7 +132,7 @@ int launch_imgmetric(const float* img, const float* img2, void* sse_out, double*
     const int oh = m.Hc > WIN - 1 ? m.Hc - (WIN - 1) : 1, ow = m.Wc > WIN - 1 ? m.Wc - (WIN - 1) : 1;
     m.nty = cdiv(oh, TH); m.ntx = cdiv(ow, TW);
     m.ssim = want_ssim;
-    const Gauss gw = metric_gauss_taps();
+    const Gauss gw = gauss_taps();
     const int ntiles = m.nty * m.ntx;
     trace_tag(want_ssim ? "metric.tile_ssim" : "metric.tile_psnr");
     metric_tile_kernel<<<dim3((unsigned)ntiles, (unsigned)(B * m.Cp)), dim3(NT), 0, s>>>(img, img2, ssim_part, (unsigned long long*)sse_part, m,

@@ -1,7 +1,8 @@
 // The remaining reference metrics on the device (include/dcpt_hip.h dcpt_msssim, dcpt_ssim_matlab, dcpt_imgrange): the sums behind
 // basicsr/metrics calculate_msssim, calculate_ssim_matlab and the value range calculate_nrmse divides by, step by step as the host forms
-// compute them.  The front end (quantise, crop by addressing, BT.601 luma), the block sum and the Gaussian taps are metrics.hip's own
-// (metric_front.h).  All window arithmetic is fp64; every product and sum rounds on its own.
+// compute them.  The front end (quantise, crop by addressing, BT.601 luma) is metrics.hip's own (metric_front.h), the Gaussian taps and
+// the two window passes are window_f64.h's, the block tree and the reduce kernel block_sum.h's.  All window arithmetic is fp64; every
+// product and sum rounds on its own.
 //
 // MS-SSIM, all levels in ONE launch.  The reference does not decimate: evaluation k scores channel k mod C' of the images after k passes of
 // the 2 x 2 box filter anchored at (0, 0), out[y][x] = 0.25 ((a[y][x] + a[y][x+1]) + (a[y+1][x] + a[y+1][x+1])), an index past the last row
@@ -21,7 +22,8 @@
 //
 // Range: per-image min and max of the first image's metric values over all scored channels (exact, so the order is immaterial).
 //
-// Every workgroup stores its partials with ordinary stores; a second kernel adds (or min / max-es) them in a fixed order.  No atomics.
+// Every workgroup stores its partials with ordinary stores; a second kernel (sum_reduce_kernel of block_sum.h, or the range's own) adds or
+// min / max-es them in a fixed order.  No atomics.
 #include <math.h>
 
 #include "kernels.h"
@@ -32,61 +34,12 @@
 
 namespace {
 constexpr int TH = METRIC_TH, TW = METRIC_TW, WIN = METRIC_WIN, PAD = WIN / 2;
-constexpr int SH = TH + WIN - 1, SW = TW + WIN - 1;   // rows / columns the Gaussian passes read
+constexpr int SH = METRIC_SH, SW = METRIC_SW;         // rows / columns the Gaussian passes read
 constexpr int NT = METRIC_NT;
 constexpr int KMAX = MSSSIM_MAX_LEVELS - 1;           // box passes of the deepest level
 constexpr int BH = SH + KMAX, BW = SW + KMAX;         // staged rows / columns of the deepest level
 constexpr int BPT = (BH * BW + NT - 1) / NT;          // elements of one box pass per thread
 static_assert(2 * BH * BW * 8 + 5 * SH * TW * 8 + NT * 8 <= 64 * 1024, "static LDS of the MS-SSIM kernel");
-
-// horizontal pass of x, y, x^2, y^2, xy over SH rows: hp[j][r][c] = sum_k g[k] v_j[r][c + k]
-template <typename T, int LD>
-__device__ __forceinline__ void gauss_rows(const T (*sx)[LD], const T (*sy)[LD], double (*hp)[SH][TW], const Gauss& gw) {
-    for (int i = threadIdx.x; i < SH * TW; i += NT) {
-        const int r = i / TW, c = i - r * TW;
-        double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0, a4 = 0.0;
-#pragma unroll
-        for (int k = 0; k < WIN; ++k) {
-            const double x = (double)sx[r][c + k], y = (double)sy[r][c + k], g = gw.g[k];
-            a0 += g * x;
-            a1 += g * y;
-            a2 += g * (x * x);
-            a3 += g * (y * y);
-            a4 += g * (x * y);
-        }
-        hp[0][r][c] = a0;
-        hp[1][r][c] = a1;
-        hp[2][r][c] = a2;
-        hp[3][r][c] = a3;
-        hp[4][r][c] = a4;
-    }
-}
-
-struct Moments {
-    double mu1_sq, mu2_sq, mu12, s1, s2, s12;
-};
-
-// vertical pass at (r, c) and the moments every SSIM form is built from
-__device__ __forceinline__ Moments gauss_col(const double (*hp)[SH][TW], int r, int c, const Gauss& gw) {
-    double mu1 = 0.0, mu2 = 0.0, e11 = 0.0, e22 = 0.0, e12 = 0.0;
-#pragma unroll
-    for (int k = 0; k < WIN; ++k) {
-        const double g = gw.g[k];
-        mu1 += g * hp[0][r + k][c];
-        mu2 += g * hp[1][r + k][c];
-        e11 += g * hp[2][r + k][c];
-        e22 += g * hp[3][r + k][c];
-        e12 += g * hp[4][r + k][c];
-    }
-    Moments o;
-    o.mu1_sq = mu1 * mu1;
-    o.mu2_sq = mu2 * mu2;
-    o.mu12 = mu1 * mu2;
-    o.s1 = e11 - o.mu1_sq;
-    o.s2 = e22 - o.mu2_sq;
-    o.s12 = e12 - o.mu12;
-    return o;
-}
 
 // ---- MS-SSIM: grid (tile, image * L + level) -> part[image][level][tile][2] = sums of the SSIM map and of the CS map -------------------
 __global__ __launch_bounds__(NT) void msssim_level_kernel(const float* __restrict__ img, const float* __restrict__ img2, double* __restrict__ part,
@@ -197,39 +150,19 @@ __global__ __launch_bounds__(NT) void ssim_matlab_tile_kernel(const float* __res
     if (tid == 0) part[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] = acc;
 }
 
-// out[g][j] = sum over the tiles of group g of part[g][tile][j], j < nj: one workgroup per group, fixed order
-__global__ __launch_bounds__(NT) void sum_reduce_kernel(const double* __restrict__ part, double* __restrict__ out, int ntiles, int nj) {
-    __shared__ double red[NT];
-    const int tid = threadIdx.x;
-    const double* p = part + (int64_t)blockIdx.x * ntiles * nj;
-    for (int j = 0; j < nj; ++j) {
-        double a = 0.0;
-        for (int i = tid; i < ntiles; i += NT) a += p[(int64_t)i * nj + j];
-        a = block_sum(a, red);
-        if (tid == 0) out[(int64_t)blockIdx.x * nj + j] = a;
-    }
-}
-
 // ---- range: grid (chunk of RANGE_CHUNK scored values, image) -> part[image][chunk][2] = min, max ---------------------------------------
-__device__ __forceinline__ void block_minmax(float& lo, float& hi, float (*red)[NT]) {
-    const int tid = threadIdx.x;
-    red[0][tid] = lo;
-    red[1][tid] = hi;
-    __syncthreads();
-    for (int s = NT / 2; s > 0; s >>= 1) {
-        if (tid < s) {
-            red[0][tid] = fminf(red[0][tid], red[0][tid + s]);
-            red[1][tid] = fmaxf(red[1][tid], red[1][tid + s]);
-        }
-        __syncthreads();
-    }
-    lo = red[0][0];
-    hi = red[1][0];
-    __syncthreads();
+struct MinMax {
+    float lo, hi;
+};
+
+__device__ __forceinline__ void block_minmax(float& lo, float& hi, MinMax* red) {   // (the tree of block_sum.h; exact, so any order would do)
+    const MinMax r = block_tree(MinMax{lo, hi}, red, [](MinMax a, MinMax b) { return MinMax{fminf(a.lo, b.lo), fmaxf(a.hi, b.hi)}; });
+    lo = r.lo;
+    hi = r.hi;
 }
 
 __global__ __launch_bounds__(NT) void range_tile_kernel(const float* __restrict__ img, double* __restrict__ part, MetricGeom m) {
-    __shared__ float red[2][NT];
+    __shared__ MinMax red[NT];
     const int tid = threadIdx.x, b = blockIdx.y;
     const int64_t plane = (int64_t)m.H * m.W, cplane = (int64_t)m.Hc * m.Wc, n = cplane * m.Cp;
     const float* pb = img + (int64_t)b * m.C * plane;
@@ -254,7 +187,7 @@ __global__ __launch_bounds__(NT) void range_tile_kernel(const float* __restrict_
 }
 
 __global__ __launch_bounds__(NT) void range_reduce_kernel(const double* __restrict__ part, double* __restrict__ out, int nchunks) {
-    __shared__ float red[2][NT];
+    __shared__ MinMax red[NT];
     const int tid = threadIdx.x, b = blockIdx.x;
     const double* p = part + (int64_t)b * nchunks * 2;
     float lo = INFINITY, hi = -INFINITY;   // (the partials are fp32 numbers)
@@ -279,13 +212,13 @@ int launch_msssim(const float* img, const float* img2, double* out, double* part
     MetricGeom m = metric_geom(C, H, W, crop, luma, range);
     m.nty = cdiv(m.Hc - (WIN - 1), TH);
     m.ntx = cdiv(m.Wc - (WIN - 1), TW);
-    const Gauss gw = metric_gauss_taps();
+    const Gauss gw = gauss_taps();
     const int ntiles = m.nty * m.ntx;
     trace_tag("metric.ms_level");
     msssim_level_kernel<<<dim3((unsigned)ntiles, (unsigned)(B * levels)), dim3(NT), 0, s>>>(img, img2, part, m, gw, levels);
     DCPT_CHECK_LAUNCH("msssim level");
     trace_tag("metric.ms_reduce");
-    sum_reduce_kernel<<<dim3((unsigned)(B * levels)), dim3(NT), 0, s>>>(part, out, ntiles, 2);
+    sum_reduce_kernel<SUM_PLAIN><<<dim3((unsigned)(B * levels)), dim3(NT), 0, s>>>(part, out, ntiles, 2, 0);
     DCPT_CHECK_LAUNCH("msssim reduce");
     return DCPT_OK;
 }
@@ -295,13 +228,13 @@ int launch_ssim_matlab(const float* img, const float* img2, double* out, double*
     MetricGeom m = metric_geom(C, H, W, crop, luma, range);
     m.nty = cdiv(m.Hc, TH);
     m.ntx = cdiv(m.Wc, TW);
-    const Gauss gw = metric_gauss_taps();
+    const Gauss gw = gauss_taps();
     const int ntiles = m.nty * m.ntx;
     trace_tag("metric.matlab_tile");
     ssim_matlab_tile_kernel<<<dim3((unsigned)ntiles, (unsigned)(B * m.Cp)), dim3(NT), 0, s>>>(img, img2, part, m, gw);
     DCPT_CHECK_LAUNCH("ssim_matlab tile");
     trace_tag("metric.matlab_reduce");
-    sum_reduce_kernel<<<dim3((unsigned)(B * m.Cp)), dim3(NT), 0, s>>>(part, out, ntiles, 1);
+    sum_reduce_kernel<SUM_PLAIN><<<dim3((unsigned)(B * m.Cp)), dim3(NT), 0, s>>>(part, out, ntiles, 1, 0);
     DCPT_CHECK_LAUNCH("ssim_matlab reduce");
     return DCPT_OK;
 }

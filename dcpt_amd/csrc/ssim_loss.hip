@@ -11,8 +11,9 @@
 //     Pa = w [2 my (A2 - A1) / (B1 B2) - S (2 mx / B1 - 2 mx / B2)],  Pb = -w S / B2,  Pc = 2 w A1 / (B1 B2)
 // where Gt* is the transposed ("full") window over maps that are zero outside the valid region.
 //
-// Forward: one workgroup per TH x TW tile of map positions of one (image, channel), staged as metrics.hip stages it; one partial per
-// workgroup, a second kernel adds an image's partials in a fixed order.  Backward: (a) the same tile kernel writes Pa, Pb, Pc as three fp64
+// Forward: one workgroup per TH x TW tile of map positions of one (image, channel), staged as metrics.hip stages it, the two window passes
+// and the taps shared with it (window_f64.h); one partial per workgroup, a second kernel (sum_reduce_kernel of block_sum.h) adds an image's
+// partials in a fixed order.  Backward: (a) the same tile kernel writes Pa, Pb, Pc as three fp64
 // planes of the map's size, (b) a gather kernel, one workgroup per TH x TW tile of INPUT pixels, stages the planes with a 10-wide halo
 // (zero outside the map by bounds in the load), runs the transposed separable pass, combines with x and y, applies the luma chain rule and
 // rounds once to fp32.  It writes every element of dpred, the zeros of the crop border included.  The batch goes through the planes in
@@ -21,8 +22,10 @@
 
 #include "kernels.h"
 #include "prof.h"
+#include "window_f64.h"
 
 // every product and sum rounds on its own: the luma is a fixed sequence of fp32 roundings, the moments those of element-wise fp64 passes
+// (window_f64.h, which says so per function; this covers the rest of the file)
 #pragma clang fp contract(off)
 
 // Bytes of fp64 planes the backward pass keeps at a time (at least one image's).  Not part of the ABI: a data symbol the tests shrink to
@@ -32,13 +35,9 @@ size_t dcpt_ssim_loss_plane_cap = (size_t)64 << 20;
 }
 
 namespace {
-constexpr int TH = METRIC_TH, TW = METRIC_TW, WIN = 11;
-constexpr int SH = TH + WIN - 1, SW = TW + WIN - 1;   // staged rows / columns
-constexpr int NT = 256;
-
-struct Gauss {
-    double g[WIN];
-};
+constexpr int TH = METRIC_TH, TW = METRIC_TW, WIN = METRIC_WIN;
+constexpr int SH = METRIC_SH, SW = METRIC_SW;   // staged rows / columns
+constexpr int NT = METRIC_NT;
 
 struct SsimGeom {
     int C, Cp;           // input channels, scored channels (1 for luma)
@@ -64,19 +63,6 @@ __device__ __forceinline__ float ssim_value(const float* __restrict__ img, int64
     const float rg = r * YR + g * YG;
     const float rgb = rg + b * YB;
     return (rgb + 16.0f) / 255.0f;
-}
-
-__device__ __forceinline__ double block_sum(double v, double* red) {   // fixed tree over the NT threads: the same bits on every run
-    const int tid = threadIdx.x;
-    red[tid] = v;
-    __syncthreads();
-    for (int s = NT / 2; s > 0; s >>= 1) {
-        if (tid < s) red[tid] += red[tid + s];
-        __syncthreads();
-    }
-    const double r = red[0];
-    __syncthreads();
-    return r;
 }
 
 // MAPS = false: part[blockIdx.y][tile] = sum of S over the tile.  MAPS = true: planes[blockIdx.y][3][Hm][Wm] = Pa, Pb, Pc.
@@ -109,25 +95,8 @@ __global__ __launch_bounds__(NT) void ssim_tile_kernel(const float* __restrict__
         sy[r][c] = vy;
     }
     __syncthreads();
-    // ---- horizontal pass of the five maps ----
-    for (int i = tid; i < SH * TW; i += NT) {
-        const int r = i / TW, c = i - r * TW;
-        double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0, a4 = 0.0;
-#pragma unroll
-        for (int k = 0; k < WIN; ++k) {
-            const double x = (double)sx[r][c + k], y = (double)sy[r][c + k], g = gw.g[k];
-            a0 += g * x;
-            a1 += g * y;
-            a2 += g * (x * x);
-            a3 += g * (y * y);
-            a4 += g * (x * y);
-        }
-        hp[0][r][c] = a0;
-        hp[1][r][c] = a1;
-        hp[2][r][c] = a2;
-        hp[3][r][c] = a3;
-        hp[4][r][c] = a4;
-    }
+    const Gauss taps = gw;   // (a copy made here, where the passes start: window_f64.h)
+    gauss_rows<float, SW>(sx, sy, hp, taps);
     __syncthreads();
     // ---- vertical pass, S and its partial derivatives ----
     const double w = MAPS ? gscale[(int64_t)b * m.Cp + ch] : 0.0;
@@ -137,19 +106,9 @@ __global__ __launch_bounds__(NT) void ssim_tile_kernel(const float* __restrict__
     for (int i = tid; i < TH * TW; i += NT) {
         const int r = i / TW, c = i - r * TW;
         if (y0 + r >= m.Hm || x0 + c >= m.Wm) continue;
-        double mx = 0.0, my = 0.0, exx = 0.0, eyy = 0.0, exy = 0.0;
-#pragma unroll
-        for (int k = 0; k < WIN; ++k) {
-            const double g = gw.g[k];
-            mx += g * hp[0][r + k][c];
-            my += g * hp[1][r + k][c];
-            exx += g * hp[2][r + k][c];
-            eyy += g * hp[3][r + k][c];
-            exy += g * hp[4][r + k][c];
-        }
-        const double mxx = mx * mx, myy = my * my, mxy = mx * my;
-        const double sxx = exx - mxx, syy = eyy - myy, sxy = exy - mxy;
-        const double A1 = 2.0 * mxy + m.c1, A2 = 2.0 * sxy + m.c2, B1 = mxx + myy + m.c1, B2 = sxx + syy + m.c2;
+        const Moments o = gauss_col(hp, r, c, taps);
+        const double mx = o.mu1, my = o.mu2;
+        const double A1 = 2.0 * o.mu12 + m.c1, A2 = 2.0 * o.s12 + m.c2, B1 = o.mu1_sq + o.mu2_sq + m.c1, B2 = o.s1 + o.s2 + m.c2;
         const double S = (A1 / B1) * (A2 / B2);
         if (MAPS) {
             const double b12 = B1 * B2;
@@ -165,17 +124,6 @@ __global__ __launch_bounds__(NT) void ssim_tile_kernel(const float* __restrict__
         acc = block_sum(acc, red);
         if (tid == 0) part[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] = acc;
     }
-}
-
-// one workgroup per (image, channel): out[j] = sum over the tiles of j, in a fixed order
-__global__ __launch_bounds__(NT) void ssim_reduce_kernel(const double* __restrict__ part, double* __restrict__ out, int ntiles) {
-    __shared__ double red[NT];
-    const int tid = threadIdx.x;
-    const double* p = part + (int64_t)blockIdx.x * ntiles;
-    double a = 0.0;
-    for (int i = tid; i < ntiles; i += NT) a += p[i];
-    a = block_sum(a, red);
-    if (tid == 0) out[blockIdx.x] = a;
 }
 
 // one workgroup per TH x TW tile of input pixels of one (image, scored channel); blockIdx.y as in ssim_tile_kernel
@@ -270,18 +218,6 @@ SsimGeom ssim_geom(int C, int H, int W, int crop, int luma, double range) {
     m.c2 = (0.03 * range) * (0.03 * range);
     return m;
 }
-
-Gauss ssim_gauss() {   // cv2.getGaussianKernel(11, 1.5): exp(-(i - 5)^2 / (2 sigma^2)), normalised to sum 1
-    Gauss gw;
-    double sum = 0.0;
-    for (int i = 0; i < WIN; ++i) {
-        const double x = (double)i - 5.0;
-        gw.g[i] = exp(-(x * x) / (2.0 * 1.5 * 1.5));
-        sum += gw.g[i];
-    }
-    for (int i = 0; i < WIN; ++i) gw.g[i] /= sum;
-    return gw;
-}
 }  // namespace
 
 int ssim_loss_num_tiles(int Hc, int Wc) { return cdiv(Hc - (WIN - 1), TH) * cdiv(Wc - (WIN - 1), TW); }
@@ -298,13 +234,13 @@ int ssim_loss_chunk_images(int B, int Cp, int Hc, int Wc) {
 int launch_ssim_loss_fwd(const float* pred, const float* target, double* ssim_sum, double* part, int B, int C, int H, int W, int crop, int luma,
                          double range, hipStream_t s) {
     const SsimGeom m = ssim_geom(C, H, W, crop, luma, range);
-    const Gauss gw = ssim_gauss();
+    const Gauss gw = gauss_taps();
     const int ntiles = m.nty * m.ntx;
     trace_tag("ssim_loss.tile_fwd");
     ssim_tile_kernel<false><<<dim3((unsigned)ntiles, (unsigned)(B * m.Cp)), dim3(NT), 0, s>>>(pred, target, part, nullptr, nullptr, m, gw, 0);
     DCPT_CHECK_LAUNCH("ssim_loss_fwd tile");
     trace_tag("ssim_loss.reduce");
-    ssim_reduce_kernel<<<dim3((unsigned)(B * m.Cp)), dim3(NT), 0, s>>>(part, ssim_sum, ntiles);
+    sum_reduce_kernel<SUM_PLAIN><<<dim3((unsigned)(B * m.Cp)), dim3(NT), 0, s>>>(part, ssim_sum, ntiles, 1, 0);
     DCPT_CHECK_LAUNCH("ssim_loss_fwd reduce");
     return DCPT_OK;
 }
@@ -312,7 +248,7 @@ int launch_ssim_loss_fwd(const float* pred, const float* target, double* ssim_su
 int launch_ssim_loss_bwd(const float* pred, const float* target, const double* gscale, float* dpred, double* planes, int B, int C, int H, int W,
                          int crop, int luma, double range, hipStream_t s) {
     const SsimGeom m = ssim_geom(C, H, W, crop, luma, range);
-    const Gauss gw = ssim_gauss();
+    const Gauss gw = gauss_taps();
     const int chunk = ssim_loss_chunk_images(B, m.Cp, m.Hc, m.Wc);
     for (int b0 = 0; b0 < B; b0 += chunk) {   // (stream order: the gather of one chunk is done with the planes before the next map kernel)
         const int n = B - b0 < chunk ? B - b0 : chunk;

@@ -4,7 +4,7 @@
 //
 // Sums.  Two orders occur and nothing else:
 //   block order  lane t of the 256 adds its terms j = t, t + 256, ... in ascending j; the 256 sums go through a fixed binary tree in LDS
-//                (t += t + 128, then 64, ... 1).
+//                (t += t + 128, then 64, ... 1): block_sum.h, shared with the metric and loss kernels.
 //   wave order   lane t of the 64 adds its terms j = t, t + 64, ... in ascending j; the 64 sums go through the xor butterfly 32, 16, ... 1
 //                (a + b and b + a are the same bits, so every lane ends with the same value).
 // A row's result depends on that row's inputs and on N only: a row is owned by one workgroup (affinities, joint) or one wave (descent), and a
@@ -30,32 +30,19 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "block_sum.h"
 #include "kernels.h"
 #include "prof.h"
 
 namespace {
-constexpr int NT = 256;        // lanes of a workgroup (four waves)
+constexpr int NT = BLOCK_NT;   // lanes of a workgroup (four waves)
 constexpr int ROWS = NT / 64;  // descent: rows (waves) of a workgroup
 constexpr int YT = 1024;       // descent: points of one LDS tile, a multiple of 256
 constexpr double EPS = 2.220446049250313080847263336181640625e-16;   // 2^-52
 constexpr int PROF_TSNE_AFFINITY = PROF_OTHER + 14, PROF_TSNE_JOINT = PROF_OTHER + 15, PROF_TSNE_ZROW = PROF_OTHER + 16,
               PROF_TSNE_GRAD = PROF_OTHER + 17, PROF_TSNE_STATS = PROF_OTHER + 18;
 
-// block order, second half: the tree over the 256 lane sums; every lane returns the total, and `red` may be reused at once
-__device__ __forceinline__ double block_sum(double v, double* red) {
-    red[threadIdx.x] = v;
-    __syncthreads();
-#pragma unroll
-    for (int w = NT / 2; w >= 1; w >>= 1) {
-        if ((int)threadIdx.x < w) red[threadIdx.x] = red[threadIdx.x] + red[threadIdx.x + w];
-        __syncthreads();
-    }
-    const double r = red[0];
-    __syncthreads();
-    return r;
-}
-
-// wave order, second half
+// block order, second half: block_sum of block_sum.h.  wave order, second half:
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) v = v + __shfl_xor(v, d, 64);

@@ -2790,24 +2790,16 @@ def image_metric_sums(img, img2, crop_border=0, test_y_channel=False, image_rang
     (exact) for image_range 255 without luma, float64 otherwise; ``ssim_sums`` (B, C') float64 holds the sum of the SSIM map per scored
     channel (C' = 1 for luma), or None with ``ssim=False``."""
     lib = _lib.load()
-    if not (torch.is_tensor(img) and torch.is_tensor(img2)):
-        raise _lib.DcptHipError(f"image_metric_sums takes device tensors (got {type(img).__name__}); host arrays go to basicsr.metrics.calculate_psnr / calculate_ssim")
-    _require_gpu(img, img2)
-    if img.dim() != 4 or img.shape != img2.shape:
-        raise ValueError(f"expected two (B, C, H, W) tensors of one shape, got {tuple(img.shape)} and {tuple(img2.shape)}")
-    if image_range not in (255, 1):
-        raise ValueError(f"image_range {image_range}: the device metrics know 255 and 1")
-    img, img2 = _contig(img.detach()), _contig(img2.detach())
-    B, Cc, H, W = img.shape
-    dev = img.device
-    luma = bool(test_y_channel) and Cc == 3
-    flags = (_METRIC_Y if test_y_channel else 0) | (_METRIC_SSIM if ssim else 0) | (_METRIC_RANGE1 if image_range == 1 else 0)
-    crop = int(crop_border)
+    (img, img2), dims, cp = _msmetric_args("image_metric_sums", "calculate_psnr / calculate_ssim", (img, img2), crop_border, test_y_channel,
+                                           image_range, _METRIC_SSIM if ssim else 0,
+                                           "expected two (B, C, H, W) tensors of one shape, got {0[0]} and {0[1]}")
+    B, dev = dims[0], img.device
+    luma = cp != dims[1]
     sse = torch.empty(B, dtype=torch.int64 if (image_range == 255 and not luma) else torch.float64, device=dev)
-    sums = torch.empty(B, 1 if luma else Cc, dtype=torch.float64, device=dev) if ssim else None
-    nws = lib.dcpt_imgmetric_ws_bytes(B, Cc, H, W, crop, flags)   # (0 for arguments the entry point refuses: it then names the reason)
+    sums = torch.empty(B, cp, dtype=torch.float64, device=dev) if ssim else None
+    nws = lib.dcpt_imgmetric_ws_bytes(*dims)   # (0 for arguments the entry point refuses: it then names the reason)
     ws = _workspace(dev, nws)
-    _call(lib.dcpt_imgmetric, (img, img2, sse, sums, ws, nws), (B, Cc, H, W, crop, flags), dev)   # (irregular: the queried size, not the buffer's)
+    _call(lib.dcpt_imgmetric, (img, img2, sse, sums, ws, nws), dims, dev)   # (irregular: the queried size, not the buffer's)
     return sse, sums
 
 
@@ -2819,19 +2811,28 @@ MSSSIM_MAX_LEVELS = 8         # MSSSIM_MAX_LEVELS of dcpt_amd/csrc/kernels.h
 RANGE_CHUNK = 4096            # METRIC_RANGE_CHUNK: scored values per workgroup of the range kernel
 
 
-def _msmetric_args(name, host_name, imgs, crop_border, test_y_channel, image_range):
-    """the checks of ``image_metric_sums``; returns the contiguous tensors, the geometry (B, C, H, W, crop, flags) and C'"""
-    if not all(torch.is_tensor(t) for t in imgs):
-        raise _lib.DcptHipError(f"{name} takes device tensors (got {type(imgs[0]).__name__}); host arrays go to basicsr.metrics.{host_name}")
+def _scored_channels(channels, test_y_channel):
+    """C': the luma of an RGB image is one channel"""
+    return 1 if (test_y_channel and channels == 3) else channels
+
+
+def _msmetric_args(name, host_name, imgs, crop_border, test_y_channel, image_range, more_flags=0, mismatch="expected (B, C, H, W) tensors of one shape, got {}"):
+    """the checks every metric op makes before the call; returns the contiguous tensors, the geometry (B, C, H, W, crop, flags) and C'.
+    ``mismatch``: the wording of the shape error, formatted with the list of shapes"""
+    # (plain comparisons, no generator or loop over the one or two images: this runs once per validation image, in front of a ~0.1 ms launch)
+    img, img2 = imgs[0], imgs[-1]   # (``imgs`` holds one or two images: for the one-image op img2 is img itself and its checks repeat img's)
+    if not (torch.is_tensor(img) and torch.is_tensor(img2)):
+        raise _lib.DcptHipError(f"{name} takes device tensors (got {type(img).__name__}); host arrays go to basicsr.metrics.{host_name}")
     _require_gpu(*imgs)
-    if imgs[0].dim() != 4 or any(t.shape != imgs[0].shape for t in imgs):
-        raise ValueError(f"expected (B, C, H, W) tensors of one shape, got {[tuple(t.shape) for t in imgs]}")
+    if img.dim() != 4 or img2.shape != img.shape:
+        raise ValueError(mismatch.format([tuple(t.shape) for t in imgs]))
     if image_range not in (255, 1):
         raise ValueError(f"image_range {image_range}: the device metrics know 255 and 1")
-    imgs = [_contig(t.detach()) for t in imgs]
-    B, Cc, H, W = imgs[0].shape
-    flags = (_METRIC_Y if test_y_channel else 0) | (_METRIC_RANGE1 if image_range == 1 else 0)
-    return imgs, (B, Cc, H, W, int(crop_border), flags), 1 if (test_y_channel and Cc == 3) else Cc
+    B, Cc, H, W = img.shape
+    img = _contig(img.detach())
+    imgs = (img, _contig(img2.detach())) if len(imgs) == 2 else (img,)
+    flags = (_METRIC_Y if test_y_channel else 0) | (_METRIC_RANGE1 if image_range == 1 else 0) | more_flags
+    return imgs, (B, Cc, H, W, int(crop_border), flags), _scored_channels(Cc, test_y_channel)
 
 
 def msssim_sums(img, img2, crop_border=0, test_y_channel=False, image_range=255, levels=5):
@@ -2887,7 +2888,7 @@ def ssim_plane_cap(nbytes=None):
 def _ssim_geom(pred, crop_border, test_y_channel):
     B, Cc, H, W = pred.shape
     crop = int(crop_border)
-    cp = 1 if (test_y_channel and Cc == 3) else Cc
+    cp = _scored_channels(Cc, test_y_channel)
     return (B, Cc, H, W, crop, _METRIC_Y if test_y_channel else 0), cp, cp * (H - 2 * crop - 10) * (W - 2 * crop - 10)
 
 

@@ -36,10 +36,10 @@ BF = torch.bfloat16
 
 
 class Case:
-    """one op call: ``leaves`` collects every tensor whose gradient is recorded"""
+    """one op call: ``leaves`` collects every tensor whose gradient is recorded; ``after`` undoes a setting the case changed"""
 
     def __init__(self, name):
-        self.name, self.leaves = name, {}
+        self.name, self.leaves, self.after = name, {}, None
 
     def fmap(self, tag, b, c, h, w, bf=False, grad=True):
         x = keyed_input(f"{self.name}.{tag}", (b, c, h, w), lo=-1.0, hi=1.0).to(DEV).contiguous(memory_format=torch.channels_last)
@@ -142,6 +142,29 @@ def _conv3conv_res(k):
     return DF.conv3conv_res(k.fmap("x", 2, c, 13, 17), *k.conv("1", q, c, 3), *k.conv("2", q, q, 1), *k.conv("3", c, q, 3), k.fmap("res", 2, c, 13, 17))
 
 
+def _ssim_pt(k, luma):
+    """three images through the backward's chunk loop one at a time: the plane cap holds one image's Pa, Pb, Pc"""
+    b, c, h, w, crop = 3, 3, 29, 45, 1
+    cap = DF.ssim_plane_cap()
+    k.after = lambda: DF.ssim_plane_cap(cap)   # (the chunk loop is the backward's: the cap stays until _run is through)
+    DF.ssim_plane_cap((1 if luma else c) * 3 * (h - 2 * crop - 10) * (w - 2 * crop - 10) * 8)
+    return DF.ssim_pt(k.image("pred", b, c, h, w, grad=True), k.image("target", b, c, h, w), crop, luma)
+
+
+def _tsne(k):
+    """affinities, three descent steps and the KL divergence at N = 300 (more than one stride of the 256 lanes)"""
+    n = 300
+    x = keyed_input(f"{k.name}.x", (n, 8), lo=-1.0, hi=1.0).double()
+    d2 = ((x[:, None, :] - x[None, :, :]) ** 2).sum(-1)
+    d2 = (0.5 * (d2 + d2.t())).to(DEV)
+    y = (keyed_input(f"{k.name}.y", (n, 2), lo=-1.0, hi=1.0).double() * 1e-2).to(DEV)
+    update, gains = torch.zeros_like(y), torch.ones_like(y)
+    p, beta, steps = DF.tsne_affinities(d2, 30.0)
+    stats = DF.tsne_steps(p, y, update, gains, 3, 12.0, 0.5, 200.0)
+    kl, grad = DF.tsne_kl(p, y)
+    return p, beta, steps, y, update, gains, stats, kl.reshape(1), grad
+
+
 def _cases():
     """(name, f(Case) -> output or tuple of outputs, needs backward)"""
     out = []
@@ -212,6 +235,25 @@ def _cases():
         add(f"nafblock_bf16.c128.{'packed' if pk else 'unpacked'}", lambda k, pk=pk: _nafblock_bf16(k, 128, 8, pk))    # four 128-tile weight gradients
         add(f"nafblock_local_bf16.c64.{'packed' if pk else 'unpacked'}", lambda k, pk=pk: _nafblock_local_bf16(k, 64, 16, pk), False)
     add("conv_nobias_bf16.k1", lambda k: DF.conv_nobias(k.fmap("x", 2, 48, 13, 16, True), k.par("weight", 96, 48, 1, 1)))
+    # the fp64 window, block-sum and reduce kernels (metrics, MS-SSIM, MATLAB SSIM, range, SSIM loss, LDL, t-SNE) at the smallest shapes that
+    # reach every ragged edge of the 16 x 32 tile under the window of 11: (29, 45) cropped by 1 leaves a 17 x 33 map, 2 x 2 tiles whose last
+    # row and column hold one position
+    pair = lambda k, *s: (k.image("a", *s), k.image("b", *s))   # noqa: E731
+    for rng in (255, 1):
+        for luma in (False, True):
+            tag = f"r{rng}.{'y' if luma else 'rgb'}"
+            add(f"image_metric_sums.{tag}", lambda k, r=rng, y=luma: DF.image_metric_sums(*pair(k, 2, 3, 29, 45), 1, y, r), False)
+    add("image_metric_sums.psnr_only", lambda k: DF.image_metric_sums(*pair(k, 1, 3, 5, 7), ssim=False)[0], False)
+    add("msssim_sums.l5.rgb", lambda k: DF.msssim_sums(*pair(k, 2, 3, 29, 45), 1, False, 255, 5), False)   # the channel cycles k mod 3
+    add("msssim_sums.l8.y.r1", lambda k: DF.msssim_sums(*pair(k, 2, 3, 29, 45), 1, True, 1, 8), False)
+    add("ssim_matlab_sums", lambda k: DF.ssim_matlab_sums(*pair(k, 2, 3, 17, 33), 0), False)
+    add("ssim_matlab_sums.narrow", lambda k: DF.ssim_matlab_sums(*pair(k, 1, 1, 5, 7), 1), False)   # narrower than the halo: clamps on both sides
+    add("image_range_minmax", lambda k: DF.image_range_minmax(k.image("a", 2, 3, 40, 61), 1), False)   # 6726 values: two chunks, the second ragged
+    for luma in (False, True):
+        add(f"ssim_pt.{'y' if luma else 'rgb'}", lambda k, y=luma: _ssim_pt(k, y))
+    add("ldl_weight", lambda k: DF.ldl_weight(k.image("gt", 2, 3, 17, 33), k.image("out", 2, 3, 17, 33, grad=True)))
+    add("ldl_weight.5x5", lambda k: DF.ldl_weight(k.image("gt", 1, 1, 5, 5), k.image("out", 1, 1, 5, 5, grad=True)))   # both reflect folds on the same pixels
+    add("tsne", _tsne, False)
     return out
 
 
@@ -230,25 +272,29 @@ def _trace_text(lib):
 def _run(name, fn, backward):
     """-> ({tensor name: sha256}, outputs kept alive)"""
     k = Case(name)
-    if backward:
-        res = fn(k)
-    else:
-        with torch.no_grad():
+    try:
+        if backward:
             res = fn(k)
-    outs = list(res) if isinstance(res, tuple) else [res]
-    hashes = {}
-    if backward:
-        loss = 0
+        else:
+            with torch.no_grad():
+                res = fn(k)
+        outs = list(res) if isinstance(res, tuple) else [res]
+        hashes = {}
+        if backward:
+            loss = 0
+            for i, o in enumerate(outs):
+                cot = keyed_input(f"{name}.cot{i}", tuple(o.shape), lo=-1.0, hi=1.0).to(DEV)
+                loss = loss + (o.float() * cot).sum()
+            loss.backward()
+            for tag, leaf in k.leaves.items():
+                if leaf.grad is not None:
+                    hashes["grad." + tag] = _sha(leaf.grad)
         for i, o in enumerate(outs):
-            cot = keyed_input(f"{name}.cot{i}", tuple(o.shape), lo=-1.0, hi=1.0).to(DEV)
-            loss = loss + (o.float() * cot).sum()
-        loss.backward()
-        for tag, leaf in k.leaves.items():
-            if leaf.grad is not None:
-                hashes["grad." + tag] = _sha(leaf.grad)
-    for i, o in enumerate(outs):
-        hashes[f"out{i}"] = _sha(o)
-    torch.cuda.synchronize()
+            hashes[f"out{i}"] = _sha(o)
+        torch.cuda.synchronize()
+    finally:
+        if k.after:
+            k.after()
     return hashes
 
 
