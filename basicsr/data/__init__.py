@@ -576,6 +576,91 @@ class PairedImageBlurDataset(_GTFolderDataset):
 
 
 @DATASET_REGISTRY.register()
+class RealESRGANDataset(_GTFolderDataset):
+    """GT folder + the three blur kernels of the second-order degradation chain (Real-ESRGAN's data set): the sample carries ``gt``,
+    ``kernel1``, ``kernel2``, ``sinc_kernel`` (21 x 21 fp32 each) and the paths, and no ``lq``; the model's ``feed_data`` makes ``lq`` on the
+    device with ``basicsr.data.degradations.apply_second_order`` from the options of its ``degradation:`` block.  Options: ``dataroot_gt``,
+    ``gt_size`` (default 128), ``use_hflip``, ``use_rot``, ``center_crop``; ``kernel_list`` / ``kernel_prob``, ``blur_sigma``,
+    ``betag_range``, ``betap_range``, ``sinc_prob`` and their ``*2`` forms for the second kernel (defaults: those of
+    PairedImageBlurDataset, a ``*2`` option defaulting to its first-order value); ``final_sinc_prob`` (default 0.8); ``kernel_seed``.
+
+    ``kernel1`` / ``kernel2``: a size from the odd numbers 7..21 (``random.choice``); with ``sinc_prob`` (one ``uniform`` of ``np.random``)
+    ``circular_lowpass_kernel(w, size, pad_to=21)`` with w uniform in [pi / 3, pi] for a size below 13 and in [pi / 5, pi] otherwise, else
+    ``random_mixed_kernels(kernel_list, kernel_prob, size, blur_sigma, blur_sigma, [-pi, pi], betag_range, betap_range, noise_range=None)``
+    zero-padded to 21.  ``sinc_kernel``: with ``final_sinc_prob`` ``circular_lowpass_kernel(uniform(pi / 3, pi), size, pad_to=21)`` for
+    another size of that list, else the unit pulse at the centre.  ``kernel_seed`` as for PairedImageBlurDataset: image ``index`` draws
+    from generators of its own.  These samples form batches of their own kind: ``degrade_collate`` refuses them in a mixed batch."""
+
+    K = 21
+    SIZES = tuple(range(7, 22, 2))
+
+    def __init__(self, opt):
+        super().__init__(opt)
+        blur = PairedImageBlurDataset
+        self.first, self.second = {}, {}
+        for cfg, sfx in ((self.first, ""), (self.second, "2")):
+            base = {} if sfx == "" else self.first
+            cfg["kernel_list"] = list(opt.get("kernel_list" + sfx, base.get("kernel_list", blur.KINDS)))
+            n = len(cfg["kernel_list"])
+            cfg["kernel_prob"] = list(opt.get("kernel_prob" + sfx, base.get("kernel_prob", [1.0 / n] * n)))
+            if not cfg["kernel_list"] or not set(cfg["kernel_list"]) <= set(blur.KINDS):
+                raise ValueError(f"kernel_list{sfx} holds kinds of {blur.KINDS}, got {cfg['kernel_list']}")
+            if len(cfg["kernel_prob"]) != n or min(cfg["kernel_prob"]) < 0 or sum(cfg["kernel_prob"]) <= 0:
+                raise ValueError(f"kernel_prob{sfx} must hold one non-negative weight per entry of kernel_list{sfx}, got {cfg['kernel_prob']}")
+            for key, default in (("blur_sigma", [0.2, 3]), ("betag_range", [0.5, 4]), ("betap_range", [1, 2])):
+                cfg[key] = blur._range(opt, key + sfx, base.get(key, default))
+            cfg["sinc_prob"] = float(opt.get("sinc_prob" + sfx, base.get("sinc_prob", 0)))
+        self.final_sinc_prob = float(opt.get("final_sinc_prob", 0.8))
+        for name, p in (("sinc_prob", self.first["sinc_prob"]), ("sinc_prob2", self.second["sinc_prob"]), ("final_sinc_prob", self.final_sinc_prob)):
+            if not 0 <= p <= 1:
+                raise ValueError(f"{name} must lie in [0, 1], got {p}")
+        self.kernel_seed = opt.get("kernel_seed")
+        if opt.get("phase") == "train" and self.gt_size <= self.K // 2:
+            raise ValueError(f"gt_size {self.gt_size} must exceed {self.K // 2}, the reflect padding of the {self.K} x {self.K} blur")
+
+    def _padded(self, kernel):
+        pad = (self.K - kernel.shape[0]) // 2
+        return torch.from_numpy(np.pad(kernel, ((pad, pad), (pad, pad))).astype(np.float32))
+
+    def _blur_kernel(self, rng, cfg):
+        import math
+
+        from basicsr.data.degradations import circular_lowpass_kernel, random_mixed_kernels
+
+        size = rng[0].choice(self.SIZES)
+        if rng[1].uniform() < cfg["sinc_prob"]:
+            kernel = circular_lowpass_kernel(rng[1].uniform(math.pi / 3 if size < 13 else math.pi / 5, math.pi), size)
+        else:
+            kernel = random_mixed_kernels(cfg["kernel_list"], cfg["kernel_prob"], size, cfg["blur_sigma"], cfg["blur_sigma"], [-math.pi, math.pi],
+                                          cfg["betag_range"], cfg["betap_range"], noise_range=None, rng=rng)
+        return self._padded(kernel)
+
+    def kernels(self, index):
+        """``(kernel1, kernel2, sinc_kernel)`` of image ``index``: its own generators under ``kernel_seed``, the process-wide ones otherwise"""
+        import math
+        import random
+
+        from basicsr.data.degradations import circular_lowpass_kernel
+
+        rng = (random, np.random) if self.kernel_seed is None else (random.Random(self.kernel_seed + index),
+                                                                      np.random.RandomState(self.kernel_seed + index))
+        kernel1, kernel2 = self._blur_kernel(rng, self.first), self._blur_kernel(rng, self.second)
+        if rng[1].uniform() < self.final_sinc_prob:
+            sinc = self._padded(circular_lowpass_kernel(rng[1].uniform(math.pi / 3, math.pi), rng[0].choice(self.SIZES)))
+        else:
+            sinc = torch.zeros(self.K, self.K)
+            sinc[self.K // 2, self.K // 2] = 1.0
+        return kernel1, kernel2, sinc
+
+    def __getitem__(self, index):
+        gt, path = self._gt(index)
+        if min(gt.shape[1:]) <= self.K // 2:
+            raise ValueError(f"the image {path} of {tuple(gt.shape[1:])} must exceed {self.K // 2} pixels in both directions")
+        kernel1, kernel2, sinc = self.kernels(index)
+        return _labelled({"gt": gt, "kernel1": kernel1, "kernel2": kernel2, "sinc_kernel": sinc, "lq_path": path, "gt_path": path}, self.opt)
+
+
+@DATASET_REGISTRY.register()
 class PairedImageDehazeDataset(tdata.Dataset):
     """Hazy folder + GT folder with several hazy images per GT (reference basicsr/data/paired_image_dataset.py:583-729, folder mode, PIL
     reader): the LQ folder is listed, and the GT of ``<lq_name>`` is ``dataroot_gt/<lq_name.split("_")[0] + suffix>`` (``suffix`` default

@@ -42,7 +42,8 @@ class BaseModel:
         ``noise_sigma``, ``noise_key``) from the Philox noise kernel, unclipped like the host path, and a batch of a ``blur_backend: device``
         set (PairedImageBlurDataset: ``gt`` and ``blur_kernel``, one (K, K) kernel per image) from the blur kernel, and a batch of a
         ``noise_type: poisson`` set (PairedImageDenoiseDataset: ``gt``, ``poisson_scale``, ``poisson_gray``, ``noise_key``) from the Poisson
-        noise kernels, clipped as ``add_poisson_noise_pt`` defaults (single-kind batches only).  A mixed batch
+        noise kernels, clipped as ``add_poisson_noise_pt`` defaults (single-kind batches only), and a batch of a RealESRGANDataset
+        (``gt``, ``kernel1``, ``kernel2``, ``sinc_kernel``) from the second-order chain (``_lq_second_order``; single-kind batches only).  A mixed batch
         (``basicsr.data.degrade_collate``: ``degrade_kind`` per sample, each kind's keys stacked over its own samples) gets every kind's rows
         from that kind's op on its ``gt`` rows"""
         if "degrade_kind" in data:
@@ -68,7 +69,38 @@ class BaseModel:
         if "lq" not in data and "blur_kernel" in data:
             gt = data["gt"].to(self.device, non_blocking=True)
             return DF.filter2d(gt, data["blur_kernel"])
+        if "lq" not in data and "kernel1" in data:
+            return self._lq_second_order(data)
         return data["lq"].to(self.device, non_blocking=True)
+
+    def _lq_second_order(self, data):
+        """``lq`` of a RealESRGANDataset batch (``gt``, ``kernel1``, ``kernel2``, ``sinc_kernel``, no ``lq``): the second-order degradation
+        chain of ``basicsr.data.degradations`` on the device, its draws made on the host from the options' top-level ``degradation:`` block
+        and ``scale``.  With ``degradation.gt_usm: true`` the ground truth is ``USMSharp()(gt)``; the chain starts from it and
+        ``_gt_on_device`` hands it to ``feed_data``."""
+        from basicsr.data.degradations import apply_second_order, draw_second_order_plan
+        from basicsr.utils import USMSharp
+
+        opt = self.opt.get("degradation")
+        if opt is None:
+            raise ValueError("a batch of RealESRGANDataset needs the options' `degradation:` block (the second-order chain's ranges)")
+        gt = data["gt"].to(self.device, non_blocking=True)
+        if opt.get("gt_usm", False):
+            if getattr(self, "_usm_sharpener", None) is None:
+                self._usm_sharpener = USMSharp().to(self.device)
+            with torch.no_grad():
+                gt = self._usm_sharpener(gt)
+        self._second_order_gt = gt
+        B, _, H, W = gt.shape
+        plan = draw_second_order_plan(opt, B, H, W, int(self.opt["scale"]))
+        return apply_second_order(gt, data["kernel1"], data["kernel2"], data["sinc_kernel"], plan)
+
+    def _gt_on_device(self, data):
+        """``data["gt"]`` on the device; for a batch of the second-order chain the ground truth the chain started from (sharpened under
+        ``gt_usm``).  Call it after ``_lq_on_device``."""
+        if "lq" not in data and "kernel1" in data:
+            return self._second_order_gt
+        return data["gt"].to(self.device, non_blocking=True)
 
     def _lq_mixed(self, data):
         """``lq`` of a mixed batch: allocated like ``gt``; for each kind present the rows of that kind (read from the HOST tensor

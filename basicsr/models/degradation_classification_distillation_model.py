@@ -97,7 +97,7 @@ class DCDistModel(SRModel):
         if "dataset_idx" in self.opt:   # one degradation for the whole run (:147-150)
             self.dataset_idx = torch.full((self.lq.shape[0],), int(self.opt["dataset_idx"]), dtype=torch.long, device=self.device)
         if "gt" in data:
-            self.gt = data["gt"].to(self.device, non_blocking=True)
+            self.gt = self._gt_on_device(data)
 
     def optimize_parameters(self, current_iter):
         self.net_dc.eval()

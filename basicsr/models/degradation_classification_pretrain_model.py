@@ -134,7 +134,7 @@ class DCPTModel(BaseModel):
         self.lq = self._lq_on_device(data)
         self.dataset_idx = data["dataset_idx"].to(self.device, non_blocking=True)
         if "gt" in data:
-            self.gt = data["gt"].to(self.device, non_blocking=True)
+            self.gt = self._gt_on_device(data)
 
     # -- the step ----------------------------------------------------------------------------------
     def optimize_parameters(self, current_iter):

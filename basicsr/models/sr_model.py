@@ -134,7 +134,7 @@ class SRModel(BaseModel):
     def feed_data(self, data):
         self.lq = self._lq_on_device(data)
         if "gt" in data:
-            self.gt = data["gt"].to(self.device, non_blocking=True)
+            self.gt = self._gt_on_device(data)
 
     def optimize_parameters(self, current_iter):
         self.net_g.train()

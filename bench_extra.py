@@ -2,7 +2,7 @@
 """Secondary workloads of BASELINE.json (configs[2..4]) on ONE MI355X -- evidence for DESIGN.md, not the driver's
 contract (that is bench.py).  Prints one JSON line per workload.
 
-    python bench_extra.py --workload dcpt|dcpt_swinir|restormer|promptir|infer2k|naf|swinir|rcan|val_metrics|val_metrics_ms|step_tail|tlsc|ssim_loss|ldl|jpeg|niqe|degrade|noise|blur|poisson|knn|tsne [--dtype fp32|bf16|bf16_res32] [--steps K] [--warmup W]
+    python bench_extra.py --workload dcpt|dcpt_swinir|restormer|promptir|infer2k|naf|swinir|rcan|val_metrics|val_metrics_ms|step_tail|tlsc|ssim_loss|ldl|jpeg|niqe|degrade|noise|blur|poisson|degrade_chain|knn|tsne [--dtype fp32|bf16|bf16_res32] [--steps K] [--warmup W]
 
 ``--dtype bf16`` (dcpt, naf, infer2k, restormer, promptir; rcan: the inference line only, next to fp32; swinir: the restoration form's inference, next to fp32): every feature map of the encoder in bf16 storage with fp32 accumulation (act_dtype="bf16";
 dcpt: the classifier head too unless --head-dtype fp32); images, parameters and the optimizer stay fp32.  Its lines carry BOTH
@@ -1253,6 +1253,101 @@ def run_blur(dev, steps=20, warmup=3, B=32, S=256, K=21):
                      "float64, the kernel's tap order) over the B images on one thread, one pass")
 
 
+def run_degrade_chain(dev, steps=20, warmup=3, B=32, S=256, scale=4):
+    """The resize kernel and the second-order degradation chain on a B x 3 x S x S batch (dcpt_amd/csrc/resize.hip,
+    basicsr/data/degradations.py).  Line 1: ``dcpt_amd.functional.interpolate`` per mode at the scale factors 1.5, 0.5 and 0.15 against
+    ``F.interpolate`` (fp32) on the same device, the two alternating call by call, device events around each call.  Line 2:
+    ``apply_second_order`` over eight seeded plans of the shipped options (options/realsr/train_SwinIR_realSR_x4.yml) against the same
+    chain with ``F.interpolate`` in place of the kernel, alternating plan by plan, and each route's peak memory above what is resident
+    between calls.  The bandwidth figure counts one read of the source and one write of the result over the kernel's fastest call."""
+    import random
+    import statistics
+
+    import numpy as np
+    import torch.nn.functional as F
+
+    from basicsr.data import degradations as D
+    from dcpt_amd import functional as DF
+
+    g = torch.Generator(device=dev).manual_seed(1234)
+    low = torch.rand((B, 3, S // 8, S // 8), generator=g, device=dev)
+    x = (F.interpolate(low, size=(S, S), mode="bilinear", align_corners=False) + 0.05 * torch.randn((B, 3, S, S), generator=g, device=dev)).clamp(0, 1)
+
+    def torch_interp(x, size=None, scale_factor=None, mode="bilinear", clip=False, rounds=False):
+        return F.interpolate(x, size=size, scale_factor=scale_factor, mode=mode, **({} if mode == "area" else {"align_corners": False}))
+
+    def measure(routes, calls):
+        peaks, last, times = {}, {}, {n: [] for n in routes}
+        with torch.no_grad():
+            for i in range(warmup + calls):
+                for n, fn in routes.items():
+                    torch.cuda.synchronize(dev)
+                    base = torch.cuda.memory_allocated(dev)
+                    torch.cuda.reset_peak_memory_stats(dev)
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    last[n] = fn(i)
+                    e1.record()
+                    e1.synchronize()
+                    peaks[n] = max(peaks.get(n, 0), torch.cuda.max_memory_allocated(dev) - base)
+                    if i >= warmup:
+                        times[n].append(e0.elapsed_time(e1))
+        return peaks, last, times
+
+    per_mode = {}
+    for mode in DF.INTERP_MODES:
+        for sf in (1.5, 0.5, 0.15):
+            peaks, last, times = measure({"kernel": lambda i: DF.interpolate(x, scale_factor=sf, mode=mode),
+                                          "torch": lambda i: torch_interp(x, scale_factor=sf, mode=mode)}, steps)
+            kmin = min(times["kernel"])
+            per_mode[f"{mode}@{sf}"] = dict(
+                out=list(last["kernel"].shape[2:]), kernel_ms_median=round(statistics.median(times["kernel"]), 4), kernel_ms_min=round(kmin, 4),
+                torch_ms_median=round(statistics.median(times["torch"]), 4), torch_ms_min=round(min(times["torch"]), 4),
+                ratio_median=round(statistics.median(times["torch"]) / statistics.median(times["kernel"]), 2),
+                kernel_gb_s_at_min=round(4.0 * (x.numel() + last["kernel"].numel()) / (kmin * 1e-3) / 1e9, 1),
+                kernel_vs_torch_max_abs=float(f"{float((last['kernel'] - last['torch']).abs().max()):.3e}"))
+    first = dict(workload=f"interpolate, {B} x 3 x {S} x {S}, per mode at scale_factor 1.5 / 0.5 / 0.15 (ratios 1/1.5, 1/0.5, 1/0.15), against F.interpolate fp32",
+                 results=per_mode, calls=steps, warmup=warmup,
+                 note="device events around each call (the op's host side included), the kernel and F.interpolate alternating in one process; "
+                      "kernel_gb_s_at_min = 4 bytes x (source + result elements) over the fastest call")
+
+    opt = dict(resize_prob=[0.2, 0.7, 0.1], resize_range=[0.15, 1.5], gaussian_noise_prob=0.5, noise_range=[1, 30], poisson_scale_range=[0.05, 3],
+               gray_noise_prob=0.4, jpeg_range=[30, 95], second_blur_prob=0.8, resize_prob2=[0.3, 0.4, 0.3], resize_range2=[0.3, 1.2],
+               gaussian_noise_prob2=0.5, noise_range2=[1, 25], poisson_scale_range2=[0.05, 2.5], gray_noise_prob2=0.4, jpeg_range2=[30, 95])
+    rng = (random.Random(77), np.random.RandomState(77))
+    kinds = ["iso", "aniso", "generalized_iso", "generalized_aniso", "plateau_iso", "plateau_aniso"]
+    kernels = [torch.from_numpy(np.stack([D.random_mixed_kernels(kinds, [0.45, 0.25, 0.12, 0.03, 0.12, 0.03], 21, (0.2, 3), (0.2, 3), rng=rng)
+                                          for _ in range(B)]).astype(np.float32)).to(dev) for _ in range(3)]
+    plans = [D.draw_second_order_plan(opt, B, S, S, scale, rng=rng) for _ in range(8)]
+
+    def chain(interp):
+        def run(i):
+            saved, DF.interpolate = DF.interpolate, interp
+            try:
+                return D.apply_second_order(x, *kernels, plans[i % len(plans)])
+            finally:
+                DF.interpolate = saved
+        return run
+
+    calls = max(steps, 2 * len(plans))
+    peaks, last, times = measure({"kernel": chain(DF.interpolate), "torch": chain(torch_interp)}, calls)
+    second = dict(workload=f"second-order degradation chain, {B} x 3 x {S} x {S} -> x{scale}, eight seeded plans of the shipped options: apply_second_order",
+                  kernel_ms_median=round(statistics.median(times["kernel"]), 4), kernel_ms_min=round(min(times["kernel"]), 4),
+                  torch_ms_median=round(statistics.median(times["torch"]), 4), torch_ms_min=round(min(times["torch"]), 4),
+                  ratio_median=round(statistics.median(times["torch"]) / statistics.median(times["kernel"]), 3),
+                  kernel_peak_mb=round(peaks["kernel"] / 1e6, 1), torch_peak_mb=round(peaks["torch"] / 1e6, 1),
+                  lq_max_abs_between_routes=float(f"{float((last['kernel'] - last['torch']).abs().max()):.3e}"),
+                  plans=[dict(resize1=[round(p["resize1"]["scale_factor"], 3), p["resize1"]["mode"]], noise1=p["noise1"]["kind"],
+                              second_blur=p["second_blur"], resize2=[list(p["resize2"]["size"]), p["resize2"]["mode"]], noise2=p["noise2"]["kind"],
+                              final_first=p["final_first"], final_mode=p["final_mode"]) for p in plans],
+                  calls=calls, warmup=warmup,
+                  note="device events around each call, host side of the ops and the plan's small host-to-device copies included; the two routes "
+                       "alternate and see the same plan in the same call; `torch` is the same chain with F.interpolate (fp32) in place of "
+                       "dcpt_amd.functional.interpolate; peak memory of a call above what is allocated between calls; the routes' lq may "
+                       "differ by grid steps where a JPEG coefficient or the final rounding sits next to a tie")
+    return [first, second]
+
+
 def run_knn(dev, steps=20, warmup=3, N=500, D=524288, classes=5, k=5):
     """The kNN degradation probe at the reference's size (basicsr/utils/knn_probe.py, dcpt_amd/csrc/knn.hip): N seeded fp32 rows of D values
     (a NAFNet-32 last decoder map at 128 x 128) in ``classes`` clusters, the reference's five seeded 67/33 splits.  Routes, alternating call
@@ -1511,7 +1606,7 @@ def run_niqe(dev, steps=20, warmup=3, H=1080, W=2048):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", required=True, choices=["dcpt", "dcpt_swinir", "restormer", "promptir", "infer2k", "naf", "swinir", "rcan", "val_metrics", "val_metrics_ms", "step_tail", "tlsc", "ssim_loss", "ldl", "jpeg", "niqe", "degrade", "noise", "blur", "poisson", "knn", "tsne"])
+    ap.add_argument("--workload", required=True, choices=["dcpt", "dcpt_swinir", "restormer", "promptir", "infer2k", "naf", "swinir", "rcan", "val_metrics", "val_metrics_ms", "step_tail", "tlsc", "ssim_loss", "ldl", "jpeg", "niqe", "degrade", "noise", "blur", "poisson", "degrade_chain", "knn", "tsne"])
     ap.add_argument("--dtype", default="fp32", choices=["fp32", "bf16", "bf16_tail32", "bf16_edge32", "bf16_res32"])
     ap.add_argument("--head-dtype", default=None, choices=["fp32", "bf16"], help="dcpt: classifier-head activations (default: --dtype)")
     ap.add_argument("--restormer-save", default="balanced", choices=["auto", "lean", "balanced", "full"], help="what the Restormer halves keep for backward")
@@ -1726,6 +1821,10 @@ def main():
         res = run_blur(dev, max(args.steps, 20), max(args.warmup, 3), args.batch or 32, args.size or 256)
     elif args.workload == "poisson":
         res = run_poisson(dev, max(args.steps, 20), max(args.warmup, 3), args.batch or 32, args.size or 256)
+    elif args.workload == "degrade_chain":
+        lines = run_degrade_chain(dev, max(args.steps, 20), max(args.warmup, 3), args.batch or 32, args.size or 256)
+        print(json.dumps(lines[0]), flush=True)
+        res = lines[1]
     elif args.workload == "knn":
         res = run_knn(dev, max(args.steps, 20), max(args.warmup, 3), args.batch or 500, args.size or 524288)
     elif args.workload == "tsne":

@@ -357,6 +357,7 @@ SIGNATURES = {
     "dcpt_poisson_noise_ws_bytes": (sz, [cint, cint, cint, cint]),
     "dcpt_poisson_noise_fwd": (cint, [f32p, f32p, C.c_void_p, C.c_void_p, f32p, C.c_void_p, sz, cint, cint, cint, cint, cint, stream_t]),
     "dcpt_filter2d_fwd": (cint, [f32p, f32p, f32p, cint, cint, cint, cint, cint, cint, stream_t]),
+    "dcpt_interp_fwd": (cint, [f32p, f32p, cint, cint, cint, cint, cint, cint, cint, C.c_double, C.c_double, cint, stream_t]),
     "dcpt_pdist2_ws_bytes": (sz, [cint, cint, C.c_longlong, cint]),
     "dcpt_pdist2_fwd": (cint, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, sz, cint, cint, C.c_longlong, C.c_longlong, C.c_longlong,
                                C.c_longlong, cint, cint, stream_t]),

@@ -668,6 +668,28 @@ extern "C" int dcpt_filter2d_fwd(const float* x, const float* kern, float* y, in
 }
 
 // ---------------------------------------------------------------------------------------------
+// The resize of the second-order degradation chain: F.interpolate's area / bilinear / bicubic (resize.hip)
+extern "C" int dcpt_interp_fwd(const float* x, float* y, int B, int C, int H, int W, int Ho, int Wo, int mode, double ratio_h, double ratio_w,
+                               int flags, dcpt_stream_t stream) {
+    DCPT_CHECK_ARG(x && y, "interp_fwd: null argument");
+    DCPT_CHECK_ARG(B >= 1 && C >= 1 && H >= 1 && W >= 1 && Ho >= 1 && Wo >= 1, "interp_fwd: bad shape (B=%d C=%d H=%d W=%d Ho=%d Wo=%d)", B, C, H,
+                   W, Ho, Wo);
+    DCPT_CHECK_ARG(mode == DCPT_INTERP_AREA || mode == DCPT_INTERP_BILINEAR || mode == DCPT_INTERP_BICUBIC,
+                   "interp_fwd: unknown mode %d (0 area, 1 bilinear, 2 bicubic)", mode);
+    DCPT_CHECK_ARG((flags & ~(DCPT_INTERP_CLIP | DCPT_INTERP_ROUND8)) == 0, "interp_fwd: unknown flags 0x%x", flags);
+    const int64_t pin = (int64_t)H * W, pout = (int64_t)Ho * Wo, cap = (int64_t)1 << 30;
+    DCPT_CHECK_ARG(pin <= cap && pout <= cap, "interp_fwd: a plane above 2^30 pixels (H=%d W=%d Ho=%d Wo=%d)", H, W, Ho, Wo);
+    DCPT_CHECK_ARG((int64_t)B * C <= ((int64_t)1 << 40) / (pin > pout ? pin : pout), "interp_fwd: a batch above 2^40 elements (B=%d C=%d)", B, C);
+    if (mode != DCPT_INTERP_AREA)   // (the area taps are made from the sizes alone; the comparisons are false for a NaN)
+        DCPT_CHECK_ARG(ratio_h > 0.0 && ratio_h <= 0x1p30 && ratio_w > 0.0 && ratio_w <= 0x1p30,
+                       "interp_fwd: the ratios must lie in (0, 2^30] (ratio_h=%g ratio_w=%g)", ratio_h, ratio_w);
+    const uintptr_t xa = (uintptr_t)x, ya = (uintptr_t)y;
+    const uint64_t xbytes = (uint64_t)B * C * pin * sizeof(float), ybytes = (uint64_t)B * C * pout * sizeof(float);
+    DCPT_CHECK_ARG(xa + xbytes <= ya || ya + ybytes <= xa, "interp_fwd: y overlaps x (an output reads several source pixels: not in place)");
+    return launch_interp_fwd(x, y, B, C, H, W, Ho, Wo, mode, ratio_h, ratio_w, flags, (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------------------------------------
 // The kNN degradation probe: fp64 squared distances on the fp64 MFMA, and the neighbour vote (knn.hip)
 namespace {
 // the effective chunk count of a call, or 0 with `why` set for a refused shape

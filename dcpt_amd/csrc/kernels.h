@@ -256,6 +256,12 @@ int launch_poisson_noise_fwd(const float* x, const float* scale, const long long
 // with per_image == 0; K odd, 1..51, K / 2 < H, W); fp64 accumulation in the tap order of the header; one launch, no workspace.
 int launch_filter2d_fwd(const float* x, const float* kern, float* y, int B, int C, int H, int W, int K, int per_image, hipStream_t s);
 
+// ---- resize.hip -----------------------------------------------------------------------------
+// F.interpolate's area / bilinear / bicubic resize of dense NCHW fp32 planes (dcpt_interp_fwd: mode 0 / 1 / 2, the ratios are source pixels
+// per destination pixel); fp64 taps and sums in the header's order; one launch, no workspace.
+int launch_interp_fwd(const float* x, float* y, int B, int C, int H, int W, int Ho, int Wo, int mode, double ratio_h, double ratio_w, int flags,
+                      hipStream_t s);
+
 // ---- knn.hip --------------------------------------------------------------------------------
 // Squared Euclidean distances between the rows of two fp32 / bf16 matrices in fp64 (dcpt_pdist2_fwd): the k-range in `ksplit` >= 1 chunks,
 // partial norms, partial 64 x 64 tiles on the fp64 MFMA and the finishing pass: four launches; ws holds the partial tiles [ksplit][Nq][Nt]

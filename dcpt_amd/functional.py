@@ -3211,6 +3211,63 @@ def filter2d(x, kernel):
 
 
 # ------------------------------------------------------------------------------------------------
+# The resize of the second-order degradation chain (include/dcpt_hip.h dcpt_interp_fwd): F.interpolate's area / bilinear / bicubic modes
+# with align_corners=False as one launch, taps and sums in fp64.
+INTERP_MODES = ("area", "bilinear", "bicubic")   # the index is the mode of the C ABI (DCPT_INTERP_*)
+INTERP_CLIP, INTERP_ROUND8 = 1, 2                # include/dcpt_hip.h DCPT_INTERP_*
+INTERP_MAX_PLANE = 1 << 30
+
+
+def interp_geometry(in_size, size=None, scale_factor=None):
+    """torch's rules for the output size and the source-per-destination ratios of ``F.interpolate`` (align_corners=False,
+    recompute_scale_factor unset): with ``scale_factor`` (a number or a pair) ``Ho = floor(H * sf)`` in double and ``ratio = 1 / sf``; with
+    ``size`` (an int or a pair) ``ratio = H / Ho``.  Returns ``((Ho, Wo), (ratio_h, ratio_w))``; needs no device."""
+    if (size is None) == (scale_factor is None):
+        raise ValueError("interpolate: exactly one of size and scale_factor must be given")
+    H, W = (int(v) for v in in_size)
+    if scale_factor is not None:
+        sf = tuple(scale_factor) if isinstance(scale_factor, (tuple, list)) else (scale_factor, scale_factor)
+        if len(sf) != 2 or not all(isinstance(v, (int, float)) and math.isfinite(v) and v > 0 for v in sf):
+            raise ValueError(f"interpolate: scale_factor must be a positive number or a pair of them, got {scale_factor!r}")
+        out = (int(math.floor(float(H * sf[0]))), int(math.floor(float(W * sf[1]))))
+        ratio = (1.0 / sf[0], 1.0 / sf[1])
+    else:
+        out = tuple(size) if isinstance(size, (tuple, list)) else (size, size)
+        if len(out) != 2 or not all(isinstance(v, int) and not isinstance(v, bool) for v in out):
+            raise ValueError(f"interpolate: size must be an int or a pair of ints, got {size!r}")
+        ratio = (H / out[0] if out[0] > 0 else 0.0, W / out[1] if out[1] > 0 else 0.0)
+    if min(out) < 1:
+        raise ValueError(f"interpolate: the output size must be positive, got {out} from an input of {(H, W)}")
+    return out, ratio
+
+
+def interpolate(x, size=None, scale_factor=None, mode="bilinear", clip=False, rounds=False):
+    """``F.interpolate(x, size, scale_factor, mode, align_corners=False)`` for ``mode`` ``"area"``, ``"bilinear"`` or ``"bicubic"``: ``x``
+    (B, C, H, W) fp32 device tensor (any strides: it is made contiguous NCHW); exactly one of ``size`` (an int or a pair) and
+    ``scale_factor`` (a number or a pair) with torch's rules for the output size and the ratios (``interp_geometry``).  The taps and both
+    sums are fp64 and an output is rounded once (include/dcpt_hip.h states the arithmetic), so the result is within one fp32 rounding of
+    torch's float64 result.  ``clip``: clamp to [0, 1]; ``rounds``: ``rint(255 v) / 255`` after it.  Returns a new fp32 NCHW tensor; one
+    launch, nothing is read back.  Forward only; ``align_corners=True``, ``nearest`` and antialiasing are not offered."""
+    if not torch.is_tensor(x):
+        raise _lib.DcptHipError(f"interpolate takes a device tensor (got {type(x).__name__})")
+    _require_gpu(x)
+    if x.dim() != 4 or 0 in x.shape:
+        raise ValueError(f"interpolate: expected a non-empty (B, C, H, W) batch, got {tuple(x.shape)}")
+    if mode not in INTERP_MODES:
+        raise ValueError(f"interpolate: mode must be one of {INTERP_MODES}, got {mode!r}")
+    B, C, H, W = x.shape
+    (Ho, Wo), (rh, rw) = interp_geometry((H, W), size, scale_factor)
+    if H * W > INTERP_MAX_PLANE or Ho * Wo > INTERP_MAX_PLANE:
+        raise ValueError(f"interpolate: a plane above 2^30 pixels ({(H, W)} -> {(Ho, Wo)})")
+    _inference_only("interpolate", x, what="the resize")
+    x = x.detach().contiguous()
+    y = torch.empty((B, C, Ho, Wo), dtype=torch.float32, device=x.device)
+    flags = (INTERP_CLIP if clip else 0) | (INTERP_ROUND8 if rounds else 0)
+    _call(_lib.load().dcpt_interp_fwd, (x, y), (B, C, H, W, Ho, Wo, INTERP_MODES.index(mode), rh, rw, flags), x.device)
+    return y
+
+
+# ------------------------------------------------------------------------------------------------
 # The kNN degradation probe (include/dcpt_hip.h dcpt_pdist2_fwd, dcpt_knn_vote_fwd): fp64 squared distances between flattened feature rows
 # on the fp64 matrix cores, and the k-nearest-neighbour majority vote over them.  Forward only.
 PDIST_BF16 = 1                           # include/dcpt_hip.h DCPT_PDIST_BF16

@@ -1079,6 +1079,38 @@ int dcpt_poisson_noise_fwd(const float* x, const float* scale, const long long* 
 int dcpt_filter2d_fwd(const float* x, const float* kern, float* y, int B, int C, int H, int W, int K, int kern_per_image,
                       dcpt_stream_t stream);
 
+/* ---- on-the-fly degradations: the resize of the second-order chain, on the device ---------------------------------
+ * dcpt_interp_fwd replaces F.interpolate(mode = "area" | "bilinear" | "bicubic", align_corners=False, no antialiasing) as the reference's
+ * Real-ESRGAN degradation chain calls it.  (dcpt_imresize_fwd is another arithmetic: MATLAB bicubic with antialiasing from host tables.)
+ *   x        dense NCHW fp32 [B][C][H][W]
+ *   y        dense NCHW fp32 [B][C][Ho][Wo]; must not overlap x
+ *   mode     DCPT_INTERP_AREA, DCPT_INTERP_BILINEAR or DCPT_INTERP_BICUBIC
+ *   ratio_h, ratio_w   source pixels per destination pixel.  torch uses 1 / scale_factor when a scale factor is given and H / Ho when a
+ *            size is given; the caller passes whichever applies.  Not used by the area mode.
+ * The taps of output index d of one axis (n source samples, m destination samples, ratio r); source coordinates in fp64, each product and
+ * sum rounded on its own:
+ *   area (adaptive_avg_pool2d): s = floor(d n / m), e = ceil((d + 1) n / m) in integers; taps s .. e - 1, each weighted 1.0 / (e - s).
+ *   bilinear: src = max((d + 0.5) r - 0.5, 0); i0 = min(floor(src), n - 1); t = src - i0; i1 = min(i0 + 1, n - 1); taps i0, i1 with the
+ *       weights 1 - t, t.
+ *   bicubic (A = -0.75): src = (d + 0.5) r - 0.5, not clamped; i0 = floor(src); t = src - i0; taps clamp(i0 - 1 + k, 0, n - 1), k = 0 .. 3,
+ *       with the weights c2(t + 1), c1(t), c1(1 - t), c2(2 - t);  c1(v) = ((A + 2) v - (A + 3)) v v + 1,
+ *       c2(v) = ((A v - 5 A) v + 8 A) v - 4 A.
+ * Arithmetic, per output (i, j), with the row taps (ia, wh[a]) of i and the column taps (jb, ww[b]) of j, in fp64:
+ *     acc = 0;  for a ascending: { inner = 0;  for b ascending: inner = fma(ww[b], (double)x[ia][jb], inner);  acc = fma(wh[a], inner, acc); }
+ * DCPT_INTERP_CLIP clamps acc to [0, 1]; DCPT_INTERP_ROUND8 then takes rint(255 v) / 255, half to even (as DCPT_NOISE_*);
+ * y = (float)acc, the one fp32 rounding.  An output of equal size (ratio 1) returns x.
+ * One launch, no workspace, no atomics, no host synchronisation; the same input gives the same bits.  The taps of an output tile are
+ * computed once per workgroup and shared by the image's channels; the source is read through the caches, not staged (resize.hip says why).
+ * Errors (before the launch): null pointers; non-positive extents; an unknown mode or flag bit; a source or destination plane above 2^30
+ * pixels; a batch above 2^40 elements; for bilinear and bicubic a ratio that is not in (0, 2^30] (a NaN included); y overlapping x. */
+#define DCPT_INTERP_AREA 0
+#define DCPT_INTERP_BILINEAR 1
+#define DCPT_INTERP_BICUBIC 2
+#define DCPT_INTERP_CLIP 1     /* clamp to [0, 1] */
+#define DCPT_INTERP_ROUND8 2   /* rint(255 v) / 255 */
+int dcpt_interp_fwd(const float* x, float* y, int B, int C, int H, int W, int Ho, int Wo, int mode, double ratio_h, double ratio_w, int flags,
+                    dcpt_stream_t stream);
+
 /* ---- the kNN degradation probe: fp64 distances and the neighbour vote, on the device ------------------------------
  * replaces what the reference's knn.py leaves to scikit-learn on the host (KNeighborsClassifier(5).fit / predict over the flattened decoder
  * features of knn_gen.py): the distances between a few hundred rows of 10^5 .. 10^6 numbers each, and the majority vote.
